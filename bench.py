@@ -16,6 +16,9 @@ Timing protocol: frames are pre-staged in HBM before the clock sta
 pass, min/max are reported beside it.  Extract is timed separately (`extract_s`), so is the host-buffer entry point
 (`host_path_mpts`, PCIe inclusive, never `value`).
 
+--dump-outputs DIR writes what the last timed pass computed (extracted rows, occupied cells) as DIR/<name>.npy; the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+
 For N>1 the driver launches one rank per GPU with torch.distributed.run; every rank fuses its own camera stream into
 the shared grid (weak scaling) and the engine merges occupancy / statistics over RCCL.
 """
@@ -59,6 +62,9 @@ HBM_MEASURED_GBPS = 6290.0  # MI355X_MICROARCH.md: float4 copy
 PMC_JSON = {"c1": os.path.join(ROOT, "profiles", "r04_pmc_hot_path.json"), "c3": os.path.join(ROOT, "profiles", "r04_c3_pmc_hot_path.json")}
 SIMDS, CLOCK_HZ = 1024, 2.4e9  # MI355X_MICROARCH.md: 256 CUs x 4 SIMDs, 2.4 GHz; one VALU wave-instruction holds a SIMD's issue for 4 cycles
 KERNEL_SOURCES = ("kernels.hpp", "tables.hpp", "stats.hpp", "geometry.hpp", "det_math.hpp", "hfpf.hip")
+# --dump-outputs: at most this many extracted rows (72 B each as written) and occupied cells (12 B each) go to disk, 50 MB in all;
+# above that, a sample of row positions drawn with DUMP_SEED (the same positions every run of the same output size)
+DUMP_MAX_ROWS, DUMP_MAX_CELLS, DUMP_SEED = 1 << 19, 1 << 20, 0xD0D0
 
 
 def log(*a):
@@ -117,6 +123,30 @@ def cpu_baseline(poses, seed, n_sample, variant="faithful"):
             "sample": "first %d frames of the same stream, clean after frame %d and at the end, %s, %s (%.1f s)" % (n_sample, half, how, storage, dt)}
 
 
+def dump_outputs(out_dir, rows, occ):
+    """What the timed path hands its caller after the last timed pass: the extracted voxel rows (downloadData) and the occupied
+    cells, both sorted by cell, written as out_dir/<name>.npy in float32 (indices and the f32 fields, exact) or float64 (the u32
+    count and colour, exact).  sizes.npy holds the full row and cell counts when a sample is written."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(n, cap):
+        if n <= cap:
+            return slice(None)
+        return np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+
+    r = rows[sample(len(rows), DUMP_MAX_ROWS)]
+    c = occ[sample(len(occ), DUMP_MAX_CELLS)]
+    cols = lambda *names: np.stack([r[f] for f in names], axis=1).astype(np.float32)  # noqa: E731
+    arrays = {"rows_cell": cols("ix", "iy", "iz"), "rows_count": r["count"].astype(np.float64),
+              "rows_xyz": cols("x", "y", "z"), "rows_normal": cols("nx", "ny", "nz"), "rows_sd": cols("sdx", "sdy", "sdz"),
+              "rows_dist": cols("mean_dist", "sd_dist"), "rows_rgb": r["rgb"].astype(np.float64),
+              "occupied_cell": c.astype(np.float32), "sizes": np.array([len(rows), len(occ)], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("dumped %d of %d rows and %d of %d occupied cells to %s (%.1f MB)" % (
+        len(r), len(rows), len(c), len(occ), out_dir, sum(a.nbytes for a in arrays.values()) / 1e6))
+
+
 def claim_stdout():
     """The contract is ONE JSON line on stdout.  Gloo and RCCL print banners on file descriptor 1 from C code, so keep a private
     handle to the real stdout for that line and point fd 1 (and Python's sys.stdout) at stderr for everything else."""
@@ -159,6 +189,7 @@ def main():
     ap.add_argument("--write-dir", default=None, help="also time writing test_cloud.pcd (ASCII + binary) and meta.csv there")
     ap.add_argument("--host-path-frames", type=int, default=200, help="frames also pushed through the host-buffer entry point (0 = skip)")
     ap.add_argument("--allow-host-staged", action="store_true", help="rehearsals with several ranks on ONE GPU: fall back to the gloo host-staged transport when RCCL cannot form a communicator")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the extracted rows and occupied cells of the last timed pass as DIR/<name>.npy (untimed)")
     args = ap.parse_args()
     global W, H, NPTS, BBOX, RES
     wl = WORKLOADS[args.workload]
@@ -195,8 +226,12 @@ def main():
         n_dev = torch.cuda.device_count()  # does not initialise the GPU
         if n_dev > 0:
             device = local_rank % n_dev  # rehearsals with more ranks than GPUs share devices
+    # The point log takes nearly every in-bbox point of the first clean epoch, into 64 append regions of max_log_points / 64 entries
+    # that fill unevenly: room for twice an epoch, else a short stream (--steps 2, one epoch) overflows a region
+    epoch_frames = min(clean_every, n_gen) if clean_every else n_gen
+    log_frames = max(n_gen, 64, 2 * epoch_frames)
     grid = hfpf.OccupancyGrid(resolution=RES, bbox=BBOX, device=device, max_bricks=400000,
-                              max_log_points=min(max(n_gen, 64) * NPTS, (1 << 31) - 64), max_normals=24 << 20,
+                              max_log_points=min(log_frames * NPTS, (1 << 31) - 64), max_normals=24 << 20,
                               max_frames=max(n_gen * max(world, 1) + 16, 4096),
                               frame_width=int(os.environ.get("HFPF_FRAME_WIDTH", W)),  # organised W x H frames: 16x16-pixel tiles
                               max_call_points=call_frames * NPTS)  # per-call bins sized at create, like the other pools
@@ -278,6 +313,11 @@ def main():
     clean_ms, clean_passes = grid.kernel_time(1)
     grid.kernel_timing(False)
     ctr = grid.counters()  # of the last pass (the grid is cleared between passes)
+    if args.dump_outputs:
+        last_rows = grid.extract()  # every rank: a collective with several ranks
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last_rows, grid.occupied())
+        del last_rows
 
     # ---- one more pass, untimed, with an event pair around every kernel of every integrate call: the per-kernel breakdown ----
     per_kernel = None

@@ -3,8 +3,8 @@
  * Deterministic float trig used by the oracle's eigen33 restatement (see hfpf_oracle.cpp).
  *
  * Why this exists: the reference reaches atan2f/cosf/sinf through pcl::eigen33 -> computeRoots
- * (call site OccupancyGrid.hpp:289; PCL is a third-party dependency that is NOT under
- * /root/reference and is version-unpinned: CMakeLists.txt:213 `find_package(PCL 1.7 REQUIRED)`).
+ * (call site OccupancyGrid.hpp:289; PCL is a third-party dependency that is NOT part of the
+ * reference's sources and is version-unpinned: CMakeLists.txt:213 `find_package(PCL 1.7 REQUIRED)`).
  * libm results differ by ulps between glibc versions and from any GPU math library, and one ulp in
  * theta can flip a discrete voxel-registration decision downstream.  The oracle therefore DEFINES
  * these three leaves: evaluate in IEEE f64 with a fixed operation order (no FMA contraction; build

@@ -2,6 +2,8 @@
 import ctypes as C
 import os
 import re
+import subprocess
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -49,10 +51,13 @@ def test_create_fails_loudly_without_gpu_or_with_bad_config(hfpf_mod):
     assert e.value.code == -1
     with pytest.raises(hfpf_mod.HfpfError):
         hfpf_mod.OccupancyGrid(bbox=(0, 1, 0, 1))
-    try:
-        import torch
-        has_gpu = torch.cuda.is_available()
-    except Exception:
+    # Ask torch in a child process: torch carries its own HIP runtime, and initialising it here leaves the engine's runtime
+    # without a device for every later test in this process.
+    probe = subprocess.run([sys.executable, "-c", "import torch; print(int(torch.cuda.is_available()))"], capture_output=True, text=True,
+                           timeout=300)
+    if probe.returncode == 0:
+        has_gpu = probe.stdout.strip().endswith("1")
+    else:
         has_gpu = os.path.exists("/dev/kfd")
     if not has_gpu:
         with pytest.raises(hfpf_mod.HfpfError) as e:

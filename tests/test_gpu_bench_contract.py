@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -41,6 +42,30 @@ def test_bench_prints_one_contract_line():
     assert d["clean_passes"] == 4 and d["counters"]["dep_pairs_tested"] > 0 and d["warnings"] == []
     assert r["traffic"] is None or r["traffic"] > 0
     assert r["kernel_source_sha"] and r["traffic_source"]
+
+
+def test_bench_steps_and_dumped_outputs(tmp_path):
+    """--steps sets the frames of every timed pass, also for a stream that one clean epoch covers (every point is buffered); two runs
+    with the same arguments dump the same outputs of the last pass."""
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0",
+                              "--repeats", "2", "--cpu-sample", "0", "--host-path-frames", "0", "--dump-outputs", str(tmp_path / run)],
+                             capture_output=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr.decode()[-2000:]
+        d = json.loads(out.stdout.decode().strip())
+        assert d["steps"] == 2 and d["config"]["frames"] == 100
+        assert d["counters"]["points_presented"] == 100 * 640 * 480  # of the last pass (clear resets it)
+        assert d["counters"]["frames_integrated"] == 2 * 100  # since create: 2 passes of 2 steps x 50 frames, no warm-up
+        files = sorted(os.listdir(str(tmp_path / run)))
+        dumps.append({f: np.load(str(tmp_path / run / f)) for f in files})
+        assert dumps[-1]["sizes.npy"][0] == d["rows_extracted"] > 0
+        assert len(dumps[-1]["rows_xyz.npy"]) == min(d["rows_extracted"], 1 << 19)  # bench.DUMP_MAX_ROWS: a sample above it
+        assert sum(a.nbytes for a in dumps[-1].values()) <= 64 << 20
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for f, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64), f
+        assert np.array_equal(a, dumps[1][f]), f
 
 
 def test_bench_two_ranks_one_line_on_stdout():

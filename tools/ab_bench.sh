@@ -2,7 +2,7 @@
 # GPU box: the bench line itself (un-profiled, median of 10 passes) for several builds of libhfpf.so on one box -- for changes whose effect
 # sits between kernels (launch counts, host waits) and does not show in tools/ab_kernels.sh's per-kernel averages.
 # usage: [AB_ARGS="--workload c3"] tools/ab_bench.sh <name>=<path to libhfpf.so> ...
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $R/gpurun_out
 for spec in "$@"; do
   name=${spec%%=*}; lib=${spec#*=}

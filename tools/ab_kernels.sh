@@ -2,7 +2,7 @@
 # GPU box: per-kernel average durations (rocprofv3 --kernel-trace --stats) of the default bench for several builds of libhfpf.so,
 # for A/B decisions below the bench's ~1.5 % run-to-run noise.
 # usage: [AB_ARGS="--workload c3"] tools/ab_kernels.sh <name>=<path to libhfpf.so> ...   (results: gpurun_out/ab_<name>/, one summary line per build)
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 for spec in "$@"; do

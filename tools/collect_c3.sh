@@ -4,7 +4,7 @@
 # Summarise: tools/pmc_table.py gpurun_out/<tag>_mem k_integrate k_update k_replay k_register k_depinc > ...
 # usage: tools/collect_c3.sh <tag>
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-c3}
 mkdir -p $R/gpurun_out
 cd $R

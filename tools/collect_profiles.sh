@@ -9,7 +9,7 @@
 #                                                tools/pmc_table.py   gpurun_out/<tag>_sq  > profiles/rNN_bottleneck_counters.md
 # usage: tools/collect_profiles.sh <tag>
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-prof}
 mkdir -p $R/gpurun_out
 cd $R

@@ -2,7 +2,7 @@
 # GPU box: one rocprofv3 --pmc pass per counter set (kernel-trace only beside it) over one timed pass of the default bench.
 # usage: [BENCH_ARGS="--workload c3"] tools/pmc_passes.sh <out-prefix> "<set 1>" "<set 2>" ...   (results under gpurun_out/<prefix>_<i>/)
 # A pass whose counter set the hardware cannot schedule fails fast and is skipped; a timeout stops the script.
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 P=$1; shift
 mkdir -p $R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
