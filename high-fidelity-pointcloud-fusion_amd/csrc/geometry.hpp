@@ -73,6 +73,29 @@ HFPF_HD F3 transform_point(const double* T, float x, float y, float z)
     return q;
 }
 
+// Back-projection of one depth-image pixel (hfpf_integrate_depth; the contract is stated in include/hfpf.h, modelled on
+// depth_image_proc's convertDepth).  raw = the pixel's depth sample as stored: a uint16 count (f32 = false; valid iff != 0,
+// z = count * unit) or the bits of an f32 in metres (f32 = true; valid iff finite, z = d).  cx, cy = (float) of the principal
+// point; sx, sy = (float)(unit / fx), (float)(unit / fy) for counts, (float)(1 / fx), (float)(1 / fy) for metres (host-rounded).
+// Every operation f32, left to right, unfused.  Invalid pixels are NaN in all three coordinates, as NaN records of a cloud.
+HFPF_HD F3 depth_backproject(uint32_t u, uint32_t v, uint32_t raw, bool f32, float cx, float cy, float sx, float sy, float unit)
+{
+    const float d = f32 ? __builtin_bit_cast(float, raw) : (float)raw;
+    const bool valid = f32 ? __builtin_isfinite(d) : raw != 0u;
+    if (!valid) {
+        const float q = __builtin_bit_cast(float, 0x7FC00000u);
+        return {q, q, q};
+    }
+    return {(((float)u - cx) * d) * sx, (((float)v - cy) * d) * sy, f32 ? d : d * unit};
+}
+
+// The colour bytes of one pixel as the reference decodes an rgb field (node.cpp:170-216): 0x00RRGGBB, alpha dropped.
+// b0..b2 = the pixel's first three bytes; bgr = the image stores blue first (HFPF_COLOR_BGR8 / BGRA8).
+HFPF_HD uint32_t color_pack(uint32_t b0, uint32_t b1, uint32_t b2, bool bgr)
+{
+    return bgr ? (b2 << 16) | (b1 << 8) | b0 : (b0 << 16) | (b1 << 8) | b2;
+}
+
 // node.cpp:251-255 z-clip in the camera frame: strict on both sides, NaN rejected.
 HFPF_HD bool zclip_pass(const GridParams& g, float z) { return (z < g.zc_hi) && (z > g.zc_lo); }
 

@@ -171,6 +171,23 @@ constexpr size_t kXferChunk = 16u << 20;  // bytes per pinned chunk of extract's
 constexpr int kProbeFrames = HFPF_PROBE_FRAMES;  // frames of a plan-less batch that go ahead of the rest to measure the per-brick demand
 constexpr int kFrameSlots = 8;  // uploads run ahead of the kernels by up to this many frames
 
+// A validated hfpf_depth_image as the kernels take it (depth_spec below).  32-bit fields only: two specs are compared with memcmp
+// (a batch of waiting host frames must share one).
+struct DepthSpec {
+    uint32_t width, height, depth_f32, depth_step, color_bpp, color_bgr, color_step;
+    float cx, cy, sx, sy, unit;
+    uint32_t color_off;  // host frame path: byte offset of the colour image in a ring slot (behind the depth image, 256-aligned)
+    size_t depth_bytes() const { return (size_t)(height - 1) * depth_step + (size_t)width * (depth_f32 ? 4u : 2u); }
+    size_t color_bytes() const { return color_bpp ? (size_t)(height - 1) * color_step + (size_t)width * color_bpp : 0; }
+};
+static_assert(sizeof(DepthSpec) == 13 * 4, "DepthSpec is compared bytewise");
+
+DepthLayout depth_layout(const DepthSpec& d, const void* dev_color, uint64_t color_stride)
+{
+    return DepthLayout{d.color_bpp ? (const uint8_t*)dev_color : nullptr, color_stride, d.width, d.depth_step, d.color_step, d.depth_f32,
+                       d.color_bpp, d.color_bgr, d.cx, d.cy, d.sx, d.sy, d.unit};
+}
+
 }  // namespace
 
 struct hfpf_handle {
@@ -230,6 +247,8 @@ struct hfpf_handle {
     uint32_t pend_n = 0, pend_first = 0;  // uploaded, not yet launched: slots [pend_first, pend_first + pend_n)
     uint32_t pend_pts = 0;
     uint32_t pend_lay[5] = {0, 0, 0, 0, 0};  // point_step, off_x, off_y, off_z, off_rgb of the pending frames
+    bool pend_depth = false;                  // ... or: the pending frames are depth images of this spec
+    DepthSpec pend_ds{};
     double pend_pose[kFrameSlots * 12];
     int host_batch = 4;                   // HFPF_HOST_BATCH (1 = every frame launches on its own)
     hipEvent_t busy_ev = nullptr;         // recorded behind the last launch of the host-frame path
@@ -774,15 +793,17 @@ int pick_update_shape(hfpf_handle* h, double points, uint32_t nb)
     return h->upd_wide ? 1 : 0;
 }
 
+// dl != nullptr: the frames are depth images (dev_base / frame_stride address the depth images, n_points = width * height, the
+// cloud layout is unused); the caller has validated them (depth_spec, plus the device alignment of hfpf_integrate_depth_device).
 int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_frames, uint64_t frame_stride, uint32_t n_points,
                             uint32_t point_step, uint32_t off_x, uint32_t off_y, uint32_t off_z, uint32_t off_rgb, const double* poses,
-                            const uint32_t* frame_ids)
+                            const uint32_t* frame_ids, const DepthLayout* dl = nullptr)
 {
     if (!dev_base || !poses || n_frames == 0) return fail(h, HFPF_ERR_BAD_ARG, "integrate: null buffer/poses or zero frames");
     if (n_points == 0) return HFPF_OK;
-    if ((point_step & 3) || (off_x & 3) || (off_y & 3) || (off_z & 3) || (off_rgb & 3) || ((uintptr_t)dev_base & 3) || (frame_stride & 3))
+    if (!dl && ((point_step & 3) || (off_x & 3) || (off_y & 3) || (off_z & 3) || (off_rgb & 3) || ((uintptr_t)dev_base & 3) || (frame_stride & 3)))
         return fail(h, HFPF_ERR_BAD_ARG, "integrate: fields must be 4-byte aligned");
-    if (std::max(std::max(off_x, off_y), std::max(off_z, off_rgb)) + 4 > point_step)
+    if (!dl && std::max(std::max(off_x, off_y), std::max(off_z, off_rgb)) + 4 > point_step)
         return fail(h, HFPF_ERR_BAD_ARG, "integrate: field offset beyond point_step");
     if (n_frames > 65535) return fail(h, HFPF_ERR_BAD_ARG, "integrate: at most 65535 frames per call");
     h->pub_seq = 0;  // kernels are about to be enqueued: a counter snapshot already on its way is no longer the latest
@@ -799,12 +820,13 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
     HIPCHK(h, hipMemcpyAsync(s->d_pose, s->h_pose, (size_t)n_frames * (12 * sizeof(double) + sizeof(uint32_t)), hipMemcpyHostToDevice, h->stream));  // poses + ids
 
     const FrameLayout lay{point_step, off_x, off_y, off_z, off_rgb};
-    const bool packed = point_step == 16 && off_x == 0 && off_y == 4 && off_z == 8 && off_rgb == 12 && ((uintptr_t)dev_base & 15) == 0 &&
+    const bool packed = !dl && point_step == 16 && off_x == 0 && off_y == 4 && off_z == 8 && off_rgb == 12 && ((uintptr_t)dev_base & 15) == 0 &&
                         (frame_stride & 15) == 0;
     const dim3 block(256);
     const uint64_t n_tiles = (uint64_t)blocks_for(n_points, 256) * n_frames;
     // 16x16-pixel tiles when the caller told us the image width and the frame tiles exactly (hfpf_config.frame_width)
-    const uint32_t fw = h->cfg.frame_width;
+    // (a depth frame carries its own width)
+    const uint32_t fw = dl ? dl->width : h->cfg.frame_width;
     const uint32_t row_w = (fw >= 16 && fw % 16 == 0 && n_points % fw == 0 && (n_points / fw) % 16 == 0) ? fw : 0u;
     const dim3 grid((unsigned)std::min<uint64_t>(n_tiles, (uint64_t)h->integrate_grid));
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -843,11 +865,18 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
     hipLaunchKernelGGL((k_integrate<P, C, true>), pgrid, block, 0, h->stream,                                                                        \
                        IntegrateArgs{h->g, h->t}, (const uint8_t*)dev_base, frame_stride, n_points, launch_frames, lay, (const double*)s->d_pose, \
                        (const uint32_t*)s->d_ids, row_w, log_rot, probe, pre_possible)
-        if (packed && !color) HFPF_LAUNCH_PROBE(true, false);
+#define HFPF_LAUNCH_PROBE_DEPTH(C)                                                                                                                 \
+    hipLaunchKernelGGL((k_integrate<false, C, true, true>), pgrid, block, 0, h->stream,                                                               \
+                       IntegrateArgs{h->g, h->t}, (const uint8_t*)dev_base, frame_stride, n_points, launch_frames, *dl, (const double*)s->d_pose, \
+                       (const uint32_t*)s->d_ids, row_w, log_rot, probe, pre_possible)
+        if (dl && !color) HFPF_LAUNCH_PROBE_DEPTH(false);
+        else if (dl) HFPF_LAUNCH_PROBE_DEPTH(true);
+        else if (packed && !color) HFPF_LAUNCH_PROBE(true, false);
         else if (packed && color) HFPF_LAUNCH_PROBE(true, true);
         else if (!color) HFPF_LAUNCH_PROBE(false, false);
         else HFPF_LAUNCH_PROBE(false, true);
 #undef HFPF_LAUNCH_PROBE
+#undef HFPF_LAUNCH_PROBE_DEPTH
         HIPCHK(h, hipGetLastError());
         int rcp = read_counters(h);  // bricks the dry run claimed
         if (rcp) return rcp;
@@ -949,14 +978,22 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
     hipLaunchKernelGGL((k_integrate<P, C, B>), grid, block, 0, h->stream,                                                                           \
                        IntegrateArgs{h->g, h->t}, (const uint8_t*)dev_base, frame_stride, n_points, launch_frames, lay, (const double*)s->d_pose, \
                        (const uint32_t*)s->d_ids, row_w, log_rot, probe, pre_possible)
+#define HFPF_LAUNCH_INTEGRATE_DEPTH(C, B)                                                                                                          \
+    hipLaunchKernelGGL((k_integrate<false, C, B, true>), grid, block, 0, h->stream,                                                                   \
+                       IntegrateArgs{h->g, h->t}, (const uint8_t*)dev_base, frame_stride, n_points, launch_frames, *dl, (const double*)s->d_pose, \
+                       (const uint32_t*)s->d_ids, row_w, log_rot, probe, pre_possible)
     if (!bin) {
-        if (packed && !color) HFPF_LAUNCH_INTEGRATE(true, false, false);
+        if (dl && !color) HFPF_LAUNCH_INTEGRATE_DEPTH(false, false);
+        else if (dl) HFPF_LAUNCH_INTEGRATE_DEPTH(true, false);
+        else if (packed && !color) HFPF_LAUNCH_INTEGRATE(true, false, false);
         else if (packed && color) HFPF_LAUNCH_INTEGRATE(true, true, false);
         else if (!color) HFPF_LAUNCH_INTEGRATE(false, false, false);
         else HFPF_LAUNCH_INTEGRATE(false, true, false);
         for (int k = 0; k < 3; k++) HIPCHK(h, detail_mark());
     } else {
-        if (packed && !color) HFPF_LAUNCH_INTEGRATE(true, false, true);
+        if (dl && !color) HFPF_LAUNCH_INTEGRATE_DEPTH(false, true);
+        else if (dl) HFPF_LAUNCH_INTEGRATE_DEPTH(true, true);
+        else if (packed && !color) HFPF_LAUNCH_INTEGRATE(true, false, true);
         else if (packed && color) HFPF_LAUNCH_INTEGRATE(true, true, true);
         else if (!color) HFPF_LAUNCH_INTEGRATE(false, false, true);
         else HFPF_LAUNCH_INTEGRATE(false, true, true);
@@ -996,6 +1033,7 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
         h->bin_prev_points = (double)n_points * n_frames;
     }
 #undef HFPF_LAUNCH_INTEGRATE
+#undef HFPF_LAUNCH_INTEGRATE_DEPTH
     HIPCHK(h, hipGetLastError());
     if (h->timing_detail) h->ev_detail_ran.push_back(detail_ran);
     detail_guard.done = true;
@@ -1668,8 +1706,10 @@ static int flush_pending_locked(hfpf_handle* h)
         seen |= 1u << which;
         HIPCHK(h, hipStreamWaitEvent(h->stream, h->fslot[first + k].copied, 0));
     }
-    int rc = integrate_device_locked(h, (const char*)h->ring_d + (size_t)first * h->ring_cap, n, h->ring_cap, h->pend_pts, h->pend_lay[0], h->pend_lay[1],
-                                     h->pend_lay[2], h->pend_lay[3], h->pend_lay[4], h->pend_pose, nullptr);
+    const char* ring = (const char*)h->ring_d + (size_t)first * h->ring_cap;
+    const DepthLayout dl = depth_layout(h->pend_ds, ring + h->pend_ds.color_off, h->ring_cap);
+    int rc = integrate_device_locked(h, ring, n, h->ring_cap, h->pend_pts, h->pend_lay[0], h->pend_lay[1], h->pend_lay[2], h->pend_lay[3],
+                                     h->pend_lay[4], h->pend_pose, nullptr, h->pend_depth ? &dl : nullptr);
     // frames that were accepted with HFPF_OK are lost: whichever entry point found them waiting, the handle stops until hfpf_clear
     if (rc) return poison_on_error(h, rc);
     for (uint32_t k = 0; k < n; k++) {
@@ -1687,27 +1727,33 @@ static int flush_pending_locked(hfpf_handle* h)
 // waiting in front of it -- when the engine's stream is idle or the batch is full, otherwise leave it pending (the next frame,
 // or any other call on the handle, launches it).  The upload of frame k+1 overlaps the kernels of frame k; `bounce` = copy the
 // caller's (pageable) buffer into the slot's pinned buffer first, so that the caller's memory is free again when the call returns.
+// ds != nullptr: a depth frame (validated by depth_spec): `base` is its depth image, `color` its colour image (or nullptr), both go
+// into the slot (colour at ds->color_off), n_points = width * height, the cloud layout is unused.
 static int integrate_host_locked(hfpf_handle* h, const void* base, bool bounce, uint32_t n_points, uint32_t point_step, uint32_t off_x,
-                                 uint32_t off_y, uint32_t off_z, uint32_t off_rgb, const double pose[12])
+                                 uint32_t off_y, uint32_t off_z, uint32_t off_rgb, const double pose[12], const DepthSpec* ds = nullptr,
+                                 const void* color = nullptr)
 {
     if (!base || !pose) return fail(h, HFPF_ERR_BAD_ARG, "integrate: null buffer or pose");
     if (int rc0 = check_usable(h)) return rc0;
     int rc;
-    if (n_points == 0) {
+    if (n_points == 0 && !ds) {
         if ((rc = flush_pending_locked(h))) return rc;  // frame ids stay in arrival order
         h->next_frame_id++;
         h->frames_integrated++;
         h->dirty = true;
         return HFPF_OK;
     }
-    if ((point_step & 3) || (off_x & 3) || (off_y & 3) || (off_z & 3) || (off_rgb & 3))
+    if (!ds && ((point_step & 3) || (off_x & 3) || (off_y & 3) || (off_z & 3) || (off_rgb & 3)))
         return fail(h, HFPF_ERR_BAD_ARG, "integrate: fields must be 4-byte aligned");
-    if (std::max(std::max(off_x, off_y), std::max(off_z, off_rgb)) + 4 > point_step)
+    if (!ds && std::max(std::max(off_x, off_y), std::max(off_z, off_rgb)) + 4 > point_step)
         return fail(h, HFPF_ERR_BAD_ARG, "integrate: field offset beyond point_step");
-    const uint32_t lay[5] = {point_step, off_x, off_y, off_z, off_rgb};
-    const size_t bytes = (size_t)n_points * point_step;
-    // a frame of another shape, or a slot that is not the batch's neighbour (ring wrap), closes the pending batch
-    if (h->pend_n && (h->pend_pts != n_points || memcmp(h->pend_lay, lay, sizeof lay) != 0 || (uint32_t)h->fslot_next != h->pend_first + h->pend_n)) {
+    const uint32_t lay[5] = {ds ? 0u : point_step, ds ? 0u : off_x, ds ? 0u : off_y, ds ? 0u : off_z, ds ? 0u : off_rgb};
+    const size_t bytes = ds ? (ds->color_bpp ? ds->color_off + ds->color_bytes() : ds->depth_bytes()) : (size_t)n_points * point_step;
+    // a frame of another kind or shape (depth frames: size, formats, intrinsics), or a slot that is not the batch's neighbour
+    // (ring wrap), closes the pending batch
+    const bool kind_differs = h->pend_depth != (ds != nullptr) || (ds && memcmp(&h->pend_ds, ds, sizeof *ds) != 0);
+    if (h->pend_n && (kind_differs || h->pend_pts != n_points || memcmp(h->pend_lay, lay, sizeof lay) != 0 ||
+                      (uint32_t)h->fslot_next != h->pend_first + h->pend_n)) {
         if ((rc = flush_pending_locked(h))) return rc;
     }
     if (h->ring_cap < bytes) {  // (re)size the ring: nothing may be in flight in it
@@ -1745,17 +1791,30 @@ static int integrate_host_locked(hfpf_handle* h, const void* base, bool bounce, 
             f.cap_h = h->ring_cap;
         }
         // the caller's buffer is free again when this call returns
-        host_copy(h, f.h, base, bytes);
+        if (ds) {  // depth image, then the colour image at its offset (the gap between them is uploaded but never read)
+            host_copy(h, f.h, base, ds->depth_bytes());
+            if (ds->color_bpp) host_copy(h, (char*)f.h + ds->color_off, color, ds->color_bytes());
+        } else {
+            host_copy(h, f.h, base, bytes);
+        }
         src = f.h;
     }
     const uint32_t which = slot % (uint32_t)h->n_copy_streams;
     hipStream_t cs = which ? h->copy_more[which - 1] : h->copy_stream;
-    HIPCHK(h, hipMemcpyAsync((char*)h->ring_d + (size_t)slot * h->ring_cap, src, bytes, hipMemcpyHostToDevice, cs));
+    char* dst = (char*)h->ring_d + (size_t)slot * h->ring_cap;
+    if (ds && !bounce) {  // two page-locked buffers of the caller: two uploads
+        HIPCHK(h, hipMemcpyAsync(dst, base, ds->depth_bytes(), hipMemcpyHostToDevice, cs));
+        if (ds->color_bpp) HIPCHK(h, hipMemcpyAsync(dst + ds->color_off, color, ds->color_bytes(), hipMemcpyHostToDevice, cs));
+    } else {
+        HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, cs));
+    }
     HIPCHK(h, hipEventRecord(f.copied, cs));
     if (h->pend_n == 0) {
         h->pend_first = slot;
         h->pend_pts = n_points;
         memcpy(h->pend_lay, lay, sizeof lay);
+        h->pend_depth = ds != nullptr;
+        if (ds) h->pend_ds = *ds;
     }
     memcpy(h->pend_pose + 12 * h->pend_n, pose, 12 * sizeof(double));
     h->pend_n++;
@@ -1797,6 +1856,103 @@ int hfpf_integrate_pinned(hfpf_handle* h, const void* pinned_base, uint32_t n_po
         }
     }
     return integrate_host_locked(h, pinned_base, false, n_points, point_step, off_x, off_y, off_z, off_rgb, pose);
+}
+
+// hfpf_depth_image -> DepthSpec, with every check include/hfpf.h lists (HFPF_ERR_BAD_ARG; nothing on the handle changes).
+static int depth_spec(hfpf_handle* h, const hfpf_depth_image* d, const void* depth, const void* color, DepthSpec* out)
+{
+    if (!d) return fail(h, HFPF_ERR_BAD_ARG, "depth image: null descriptor");
+    if (d->struct_size != sizeof(hfpf_depth_image) || d->reserved != 0)
+        return fail(h, HFPF_ERR_BAD_ARG, "depth image: struct_size must be %zu and reserved 0", sizeof(hfpf_depth_image));
+    if (!depth) return fail(h, HFPF_ERR_BAD_ARG, "depth image: null depth buffer");
+    const uint64_t n = (uint64_t)d->width * d->height;
+    if (n == 0 || n > (1ull << 31)) return fail(h, HFPF_ERR_BAD_ARG, "depth image: %u x %u pixels", d->width, d->height);
+    uint32_t dbpp = 0, cbpp = 0;
+    if (d->depth_format == HFPF_DEPTH_U16) dbpp = 2;
+    else if (d->depth_format == HFPF_DEPTH_F32) dbpp = 4;
+    else return fail(h, HFPF_ERR_BAD_ARG, "depth image: unknown depth_format %u", d->depth_format);
+    if (d->color_format == HFPF_COLOR_RGB8 || d->color_format == HFPF_COLOR_BGR8) cbpp = 3;
+    else if (d->color_format == HFPF_COLOR_RGBA8 || d->color_format == HFPF_COLOR_BGRA8) cbpp = 4;
+    else if (d->color_format != HFPF_COLOR_NONE) return fail(h, HFPF_ERR_BAD_ARG, "depth image: unknown color_format %u", d->color_format);
+    if ((uint64_t)d->depth_step < (uint64_t)d->width * dbpp || d->depth_step % dbpp)
+        return fail(h, HFPF_ERR_BAD_ARG, "depth image: depth_step %u (width %u, %u-byte samples)", d->depth_step, d->width, dbpp);
+    if (cbpp && ((uint64_t)d->color_step < (uint64_t)d->width * cbpp || (cbpp == 4 && d->color_step % 4)))
+        return fail(h, HFPF_ERR_BAD_ARG, "depth image: color_step %u (width %u, %u bytes per pixel)", d->color_step, d->width, cbpp);
+    if (!cbpp && color) return fail(h, HFPF_ERR_BAD_ARG, "depth image: a colour buffer given with HFPF_COLOR_NONE");
+    if (cbpp && !color) return fail(h, HFPF_ERR_BAD_ARG, "depth image: null colour buffer for color_format %u", d->color_format);
+    if (!(std::isfinite(d->fx) && d->fx > 0) || !(std::isfinite(d->fy) && d->fy > 0) || !std::isfinite(d->cx) || !std::isfinite(d->cy))
+        return fail(h, HFPF_ERR_BAD_ARG, "depth image: intrinsics fx %g fy %g cx %g cy %g", d->fx, d->fy, d->cx, d->cy);
+    const bool f32 = d->depth_format == HFPF_DEPTH_F32;
+    if (!f32 && !(std::isfinite(d->depth_scale) && d->depth_scale > 0))
+        return fail(h, HFPF_ERR_BAD_ARG, "depth image: depth_scale %g", (double)d->depth_scale);
+    DepthSpec ds{};
+    ds.width = d->width;
+    ds.height = d->height;
+    ds.depth_f32 = f32 ? 1u : 0u;
+    ds.depth_step = d->depth_step;
+    ds.color_bpp = cbpp;
+    ds.color_bgr = (d->color_format == HFPF_COLOR_BGR8 || d->color_format == HFPF_COLOR_BGRA8) ? 1u : 0u;
+    ds.color_step = cbpp ? d->color_step : 0u;
+    // the rounding of the contract (include/hfpf.h): each constant from its double, once, here
+    ds.cx = (float)d->cx;
+    ds.cy = (float)d->cy;
+    ds.unit = f32 ? 1.0f : d->depth_scale;
+    ds.sx = f32 ? (float)(1.0 / d->fx) : (float)((double)d->depth_scale / d->fx);
+    ds.sy = f32 ? (float)(1.0 / d->fy) : (float)((double)d->depth_scale / d->fy);
+    const size_t coff = cbpp ? (ds.depth_bytes() + 255) & ~(size_t)255 : 0;
+    if (coff > 0xFFFFFFFFull) return fail(h, HFPF_ERR_BAD_ARG, "depth image: %zu bytes", ds.depth_bytes());
+    ds.color_off = (uint32_t)coff;
+    *out = ds;
+    return HFPF_OK;
+}
+
+static bool is_pinned_host(const void* p)
+{
+    hipPointerAttribute_t attr;
+    const hipError_t e = hipPointerGetAttributes(&attr, p);
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e == hipSuccess && attr.type == hipMemoryTypeHost;
+}
+
+int hfpf_integrate_depth(hfpf_handle* h, const hfpf_depth_image* desc, const void* depth, const void* color, const double pose[12])
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    DepthSpec ds;
+    if (int rc = depth_spec(h, desc, depth, color, &ds)) return rc;
+    return integrate_host_locked(h, depth, true, ds.width * ds.height, 0, 0, 0, 0, 0, pose, &ds, color);
+}
+
+int hfpf_integrate_depth_pinned(hfpf_handle* h, const hfpf_depth_image* desc, const void* depth, const void* color, const double pose[12])
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    DepthSpec ds;
+    if (int rc = depth_spec(h, desc, depth, color, &ds)) return rc;
+    if (!is_pinned_host(depth) || (color && !is_pinned_host(color)))
+        return fail(h, HFPF_ERR_BAD_ARG, "integrate_depth_pinned: an image is not page-locked host memory (hfpf_host_alloc / hipHostRegister); use hfpf_integrate_depth");
+    return integrate_host_locked(h, depth, false, ds.width * ds.height, 0, 0, 0, 0, 0, pose, &ds, color);
+}
+
+int hfpf_integrate_depth_device(hfpf_handle* h, const hfpf_depth_image* desc, const void* dev_depth, uint64_t depth_frame_stride, const void* dev_color,
+                                uint64_t color_frame_stride, uint32_t n_frames, const double* poses, const uint32_t* frame_ids)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    DepthSpec ds;
+    if (int rc = depth_spec(h, desc, dev_depth, dev_color, &ds)) return rc;
+    const uint32_t dbpp = ds.depth_f32 ? 4u : 2u, calign = ds.color_bpp == 4 ? 4u : 1u;
+    if ((uintptr_t)dev_depth % dbpp || depth_frame_stride % dbpp || (uintptr_t)dev_color % calign || color_frame_stride % calign)
+        return fail(h, HFPF_ERR_BAD_ARG, "integrate_depth_device: images and frame strides must be aligned to the sample size");
+    if (n_frames > 1 && (depth_frame_stride < ds.depth_bytes() || (ds.color_bpp && color_frame_stride < ds.color_bytes())))
+        return fail(h, HFPF_ERR_BAD_ARG, "integrate_depth_device: frame stride below the image size");
+    if (int rcf = flush_pending_locked(h)) return rcf;  // host frames still waiting for their launch
+    if (int rc = check_usable(h)) return rc;
+    const DepthLayout dl = depth_layout(ds, dev_color, color_frame_stride);
+    return integrate_device_locked(h, dev_depth, n_frames, depth_frame_stride, ds.width * ds.height, 0, 0, 0, 0, 0, poses, frame_ids, &dl);
 }
 
 int hfpf_host_alloc(hfpf_handle* h, uint64_t bytes, void** host_ptr)
@@ -2475,6 +2631,30 @@ int hfpf_probe_project(hfpf_handle* h, uint64_t n, const float* pts, const float
     PROBE_DOWN(proj_out, h->probe_d, n * 12);
     PROBE_DOWN(dist_out, h->probe_e, n * 8);
     PROBE_DOWN(member_out, h->probe_f, n);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return HFPF_OK;
+}
+
+int hfpf_probe_depth(hfpf_handle* h, const hfpf_depth_image* desc, const void* depth, const void* color, float* xyz_out, uint32_t* rgb_out)
+{
+    if (!h || !xyz_out || !rgb_out) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    DepthSpec ds;
+    int rc = depth_spec(h, desc, depth, color, &ds);
+    if (rc) return rc;
+    const uint32_t n = ds.width * ds.height;
+    PROBE_UP(h->probe_a, depth, ds.depth_bytes());
+    if (ds.color_bpp) {
+        PROBE_UP(h->probe_b, color, ds.color_bytes());
+    }
+    if ((rc = scratch(h, h->probe_c, (size_t)n * 12))) return rc;
+    if ((rc = scratch(h, h->probe_d, (size_t)n * 4))) return rc;
+    hipLaunchKernelGGL(k_probe_depth, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, depth_layout(ds, h->probe_b.p, 0), (const uint8_t*)h->probe_a.p, n,
+                       (float*)h->probe_c.p, (uint32_t*)h->probe_d.p);
+    HIPCHK(h, hipGetLastError());
+    PROBE_DOWN(xyz_out, h->probe_c, (size_t)n * 12);
+    PROBE_DOWN(rgb_out, h->probe_d, (size_t)n * 4);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return HFPF_OK;
 }

@@ -17,13 +17,54 @@
 //   K6 k_extract_*        ordered compaction of normal_found voxels            (grid.hpp:463-480)
 //      k_epoch_*          multi-GPU exchange of newly occupied cells
 #pragma once
+#include <type_traits>
+
 #include "stats.hpp"
 
 namespace hfpf {
 
+typedef float vf4 __attribute__((ext_vector_type(4)));  // native vector type (the nontemporal builtins do not take HIP's float4)
+
 struct FrameLayout {
     uint32_t point_step, off_x, off_y, off_z, off_rgb;
 };
+
+// A batch of registered depth + colour images (hfpf_integrate_depth*): frame f's depth image at frames + f * frame_stride (the
+// kernel's own arguments), its colour image at color + f * color_stride.  Every frame of a launch has the same size, formats and
+// intrinsics (the host batches only such frames).  Pixel (u, v) is point i = v * width + u.
+struct DepthLayout {
+    const uint8_t* color;  // nullptr when color_bpp == 0
+    uint64_t color_stride;
+    uint32_t width, depth_step, color_step;
+    uint32_t depth_f32;   // 0: uint16 counts, 1: f32 metres
+    uint32_t color_bpp;   // 0 (no colour: rgb = 0), 3 or 4 bytes per pixel
+    uint32_t color_bgr;   // 1: blue first
+    float cx, cy, sx, sy, unit;  // depth_backproject's constants, host-rounded
+};
+
+// Issue the loads of pixel i of one depth frame: returns (depth sample bits, 0x00RRGGBB, u, v) as raw bits, so that the caller
+// can carry it across a tile like a packed record and convert it where it is used.  Sub-dword loads only: a row is never read
+// past u's own bytes, so no load crosses the end of a row's step or of the image (an RGB8 pixel is three byte loads).
+// WANT_RGB = false skips the colour bytes (the session does not fuse colour; rgb = 0).
+template <bool WANT_RGB>
+__device__ __forceinline__ vf4 depth_fetch(const uint8_t* __restrict__ dimg, const uint8_t* __restrict__ cimg, const DepthLayout& L, uint32_t i)
+{
+    const uint32_t v = i / L.width, u = i - v * L.width;
+    const uint8_t* drow = dimg + (uint64_t)v * L.depth_step;
+    const uint32_t raw = L.depth_f32 ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(drow) + u)
+                                     : (uint32_t)__builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(drow) + u);
+    uint32_t rgb = 0;
+    if (WANT_RGB && L.color_bpp) {
+        const uint8_t* px = cimg + (uint64_t)v * L.color_step + (uint64_t)u * L.color_bpp;
+        if (L.color_bpp == 4) {
+            const uint32_t w = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(px));
+            rgb = color_pack(w & 0xFFu, (w >> 8) & 0xFFu, (w >> 16) & 0xFFu, L.color_bgr != 0);
+        } else {
+            rgb = color_pack(px[0], px[1], px[2], L.color_bgr != 0);
+        }
+    }
+    return vf4{__uint_as_float(raw), __uint_as_float(rgb), __uint_as_float(u), __uint_as_float(v)};
+}
 
 // ------------------------------------------------------------------------------------------------
 // K1.  Persistent grid: block b walks tiles b, b+gridDim.x, ... of 256 consecutive points; a tile never
@@ -58,7 +99,6 @@ constexpr int kImportTiles = HFPF_REG_TILES;  // k_epoch_import: tiles per workg
 // from an upper bound, which saves a host round trip between two kernels of a clean pass.
 constexpr uint64_t kCountOnDevice = ~0ull;
 constexpr int kListTiles = 4;  // same idea for the k_depinc_* list builders (not k_gate: it is latency-heavy per cell and needs every workgroup it can get)
-typedef float vf4 __attribute__((ext_vector_type(4)));  // native vector type (the nontemporal builtins do not take HIP's float4)
 
 // Wave-cooperative flush of statistic deltas: lanes with `member` park their delta (5 words, + 3 colour sums, + record id)
 // in the wave's LDS queue, kQueueRows at a time, and the wave replays the queue with 8 lanes per record, so one
@@ -284,10 +324,12 @@ __device__ __forceinline__ const Tables& kernarg_tables()
 #ifndef HFPF_INT_WAVES_BIN
 #define HFPF_INT_WAVES_BIN 7
 #endif
-template <bool PACKED16, bool COLOR, bool BIN>
+// Three input forms: PACKED16 (x, y, z, rgb as 16-byte records), the generic FrameLayout loader, and DEPTH (registered depth +
+// colour images, DepthLayout: each lane reads its pixel's samples and back-projects them in registers, depth_backproject).
+template <bool PACKED16, bool COLOR, bool BIN, bool DEPTH = false>
 __global__ __launch_bounds__(256, BIN ? HFPF_INT_WAVES_BIN : HFPF_INT_WAVES) void k_integrate(const IntegrateArgs A, const uint8_t* __restrict__ frames,
                                                    const uint64_t frame_stride, const uint32_t n_pts, const uint32_t n_frames,
-                                                   const FrameLayout lay, const double* __restrict__ poses,
+                                                   const std::conditional_t<DEPTH, DepthLayout, FrameLayout> lay, const double* __restrict__ poses,
                                                    const uint32_t* __restrict__ frame_ids, const uint32_t row_w, const uint32_t log_rot,
                                                    const uint32_t probe, const uint32_t pre_possible)
 {
@@ -330,8 +372,8 @@ __global__ __launch_bounds__(256, BIN ? HFPF_INT_WAVES_BIN : HFPF_INT_WAVES) voi
             i_out = (ty * 16u + py) * row_w + tx * 16u + px;
         }
     };
-    // The frame read of the NEXT tile is issued before this tile's table lookups (packed records only): the stream from HBM
-    // is the longest latency of a tile and nothing in the tile depends on it but its own first instruction.
+    // The frame read of the NEXT tile is issued before this tile's table lookups (packed records and depth images): the stream
+    // from HBM is the longest latency of a tile and nothing in the tile depends on it but its own first instructions.
     uint32_t pre_f = 0, pre_i = 0;
     vf4 pre = {0.f, 0.f, 0.f, 0.f};
     const uint32_t n_tiles32 = (uint32_t)n_tiles;
@@ -339,6 +381,8 @@ __global__ __launch_bounds__(256, BIN ? HFPF_INT_WAVES_BIN : HFPF_INT_WAVES) voi
         locate(blockIdx.x, pre_f, pre_i);
         if (PACKED16 && pre_i < n_pts)
             pre = __builtin_nontemporal_load(reinterpret_cast<const vf4*>(frames + (uint64_t)pre_f * frame_stride) + pre_i);  // read once
+        if constexpr (DEPTH)
+            if (pre_i < n_pts) pre = depth_fetch<COLOR>(frames + (uint64_t)pre_f * frame_stride, lay.color + (uint64_t)pre_f * lay.color_stride, lay, pre_i);
     }
     for (uint32_t tile = blockIdx.x; tile < n_tiles32; tile += gridDim.x) {
         const uint32_t f = pre_f, i = pre_i;
@@ -347,6 +391,8 @@ __global__ __launch_bounds__(256, BIN ? HFPF_INT_WAVES_BIN : HFPF_INT_WAVES) voi
             locate(tile + gridDim.x, pre_f, pre_i);
             if (PACKED16 && pre_i < n_pts)
                 pre = __builtin_nontemporal_load(reinterpret_cast<const vf4*>(frames + (uint64_t)pre_f * frame_stride) + pre_i);
+            if constexpr (DEPTH)
+                if (pre_i < n_pts) pre = depth_fetch<COLOR>(frames + (uint64_t)pre_f * frame_stride, lay.color + (uint64_t)pre_f * lay.color_stride, lay, pre_i);
         }
         double T[12];
 #pragma unroll
@@ -368,7 +414,14 @@ __global__ __launch_bounds__(256, BIN ? HFPF_INT_WAVES_BIN : HFPF_INT_WAVES) voi
         float x = 0.f, y = 0.f, z = 0.f;
         uint32_t rgb = 0;
         if (act) {
-            if (PACKED16) {
+            if constexpr (DEPTH) {
+                const F3 c = depth_backproject(__float_as_uint(nv.z), __float_as_uint(nv.w), __float_as_uint(nv.x), lay.depth_f32 != 0, lay.cx,
+                                               lay.cy, lay.sx, lay.sy, lay.unit);
+                x = c.x;
+                y = c.y;
+                z = c.z;
+                rgb = __float_as_uint(nv.y);
+            } else if (PACKED16) {
                 x = nv.x;
                 y = nv.y;
                 z = nv.z;
@@ -2170,6 +2223,20 @@ __global__ __launch_bounds__(256) void k_occupied_keys(const GridParams g, const
 }
 
 // ---- leaf probes (tests only; same device functions as the kernels above) -------------------------
+// One depth image, pixel by pixel, through the loads and the back-projection of k_integrate's DEPTH form.
+__global__ void k_probe_depth(const DepthLayout L, const uint8_t* __restrict__ dimg, const uint32_t n, float* __restrict__ xyz_out,
+                              uint32_t* __restrict__ rgb_out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const vf4 r = depth_fetch<true>(dimg, L.color, L, i);
+    const F3 c = depth_backproject(__float_as_uint(r.z), __float_as_uint(r.w), __float_as_uint(r.x), L.depth_f32 != 0, L.cx, L.cy, L.sx, L.sy, L.unit);
+    xyz_out[3 * (uint64_t)i] = c.x;
+    xyz_out[3 * (uint64_t)i + 1] = c.y;
+    xyz_out[3 * (uint64_t)i + 2] = c.z;
+    rgb_out[i] = __float_as_uint(r.y);
+}
+
 __global__ void k_probe_points(const GridParams g, const double* __restrict__ pose, const float* __restrict__ xyz, const uint64_t n,
                                float* __restrict__ q_out, int32_t* __restrict__ idx_out, uint8_t* __restrict__ flags_out)
 {

@@ -132,31 +132,51 @@ int hfpf_node_destroy(hfpf_node* n)
     return HFPF_OK;
 }
 
-int hfpf_node_on_point_cloud(hfpf_node* n, const hfpf_cloud_msg* msg)
+// onReceivedPointCloud up to the integrate call (node.cpp:327-344): 1 = integrate with `pose`, 0 = dropped.
+static int gate_and_lookup(hfpf_node* n, const char* frame_id, double pose[12])
 {
-    if (!n || !msg) return HFPF_ERR_BAD_ARG;
     n->received++;
     {
         std::lock_guard<std::mutex> lk(n->frame_mtx);
-        n->pointcloud_frame_ = msg->frame_id ? msg->frame_id : "";  // node.cpp:329
+        n->pointcloud_frame_ = frame_id ? frame_id : "";  // node.cpp:329
     }
     n->cloud_subscription_started_ = true;  // node.cpp:330
     if (!n->start_) {                       // node.cpp:331
         n->dropped_not_started++;
         return 0;
     }
-    double pose[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};  // Affine3d::Identity(), node.cpp:333
+    const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};  // Affine3d::Identity(), node.cpp:333
+    memcpy(pose, identity, sizeof identity);
     if (n->tf) {
         char err[256] = {0};
-        if (n->tf(n->tf_user, n->fusion_frame.c_str(), msg->frame_id ? msg->frame_id : "", pose, err, sizeof err) != 0) {
+        if (n->tf(n->tf_user, n->fusion_frame.c_str(), frame_id ? frame_id : "", pose, err, sizeof err) != 0) {
             fprintf(stderr, "[hfpf_node] WARN %s\n", err);  // ROS_WARN + drop, node.cpp:340-344
             n->dropped_tf++;
             return 0;
         }
     }
+    return 1;
+}
+
+int hfpf_node_on_point_cloud(hfpf_node* n, const hfpf_cloud_msg* msg)
+{
+    if (!n || !msg) return HFPF_ERR_BAD_ARG;
+    double pose[12];
+    if (gate_and_lookup(n, msg->frame_id, pose) == 0) return 0;
     if (!msg->data || msg->point_step == 0) return nfail(n, HFPF_ERR_BAD_ARG, "empty PointCloud2");
     const uint32_t n_points = msg->row_step / msg->point_step;  // first row only, node.cpp:185,190
     int rc = hfpf_integrate(n->grid, msg->data, n_points, msg->point_step, msg->off_x, msg->off_y, msg->off_z, msg->off_rgb, pose);
+    if (rc != HFPF_OK) return nfail(n, rc, hfpf_last_error(n->grid));
+    n->integrated++;
+    return 1;
+}
+
+int hfpf_node_on_depth_image(hfpf_node* n, const hfpf_depth_msg* msg)
+{
+    if (!n || !msg) return HFPF_ERR_BAD_ARG;
+    double pose[12];
+    if (gate_and_lookup(n, msg->frame_id, pose) == 0) return 0;
+    int rc = hfpf_integrate_depth(n->grid, &msg->image, msg->depth, msg->color, pose);
     if (rc != HFPF_OK) return nfail(n, rc, hfpf_last_error(n->grid));
     n->integrated++;
     return 1;

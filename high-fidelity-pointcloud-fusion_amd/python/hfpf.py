@@ -87,7 +87,52 @@ EXPORTS = [
     "hfpf_probe_points", "hfpf_probe_normals", "hfpf_probe_project", "hfpf_probe_trig",
     "hfpf_dist_unique_id", "hfpf_dist_init", "hfpf_dist_info", "hfpf_dist_disable", "hfpf_epoch_export", "hfpf_epoch_import", "hfpf_stats_export",
     "hfpf_extract_with_stats", "hfpf_device_download", "hfpf_device_copy", "hfpf_epoch_import_gathered",
+    "hfpf_integrate_depth", "hfpf_integrate_depth_pinned", "hfpf_integrate_depth_device", "hfpf_probe_depth",
 ]
+
+# hfpf_depth_image formats (include/hfpf.h)
+DEPTH_U16, DEPTH_F32 = 1, 2
+COLOR_NONE, COLOR_RGB8, COLOR_BGR8, COLOR_RGBA8, COLOR_BGRA8 = 0, 1, 2, 3, 4
+COLOR_BPP = {COLOR_NONE: 0, COLOR_RGB8: 3, COLOR_BGR8: 3, COLOR_RGBA8: 4, COLOR_BGRA8: 4}
+
+
+class DepthImage(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("depth_format", C.c_uint32),
+                ("depth_step", C.c_uint32), ("depth_scale", C.c_float), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("color_format", C.c_uint32), ("color_step", C.c_uint32),
+                ("reserved", C.c_uint64)]
+
+
+def depth_desc(width, height, depth_format, depth_step, K, color_format=COLOR_NONE, color_step=0, depth_scale=0.001):
+    """An hfpf_depth_image; K = (fx, fy, cx, cy)."""
+    d = DepthImage()
+    d.struct_size = C.sizeof(DepthImage)
+    d.width, d.height, d.depth_format, d.depth_step = width, height, depth_format, depth_step
+    d.depth_scale = depth_scale
+    d.fx, d.fy, d.cx, d.cy = (float(k) for k in K)
+    d.color_format, d.color_step = color_format, color_step
+    return d
+
+
+def _image_desc(depth, K, color, color_format, depth_scale):
+    """Descriptor of numpy images: the depth dtype picks the format (uint16 counts / float32 metres), the row strides give the
+    steps (rows may be padded: a view of a wider array), a 3- or 4-channel uint8 colour image defaults to RGB8 / RGBA8."""
+    if depth.ndim != 2 or depth.dtype not in (np.uint16, np.float32) or depth.strides[1] != depth.itemsize:
+        raise ValueError("depth must be a 2-D uint16 or float32 image with contiguous rows")
+    fmt = DEPTH_U16 if depth.dtype == np.uint16 else DEPTH_F32
+    H, W = depth.shape
+    cstep = 0
+    if color is None:
+        color_format = COLOR_NONE
+    else:
+        if color.dtype != np.uint8 or color.ndim != 3 or color.shape[:2] != depth.shape or color.strides[2] != 1 or color.strides[1] != color.shape[2]:
+            raise ValueError("color must be a HxWx3 or HxWx4 uint8 image with contiguous rows, the size of the depth image")
+        if color_format is None:
+            color_format = COLOR_RGB8 if color.shape[2] == 3 else COLOR_RGBA8
+        if COLOR_BPP.get(color_format) != color.shape[2]:
+            raise ValueError("color_format %r does not match a %d-channel image" % (color_format, color.shape[2]))
+        cstep = color.strides[0]
+    return depth_desc(W, H, fmt, depth.strides[0], K, color_format, cstep, depth_scale)
 
 EPOCH_REC_DTYPE = np.dtype([("key", "<u8"), ("first_frame", "<u4"), ("vx", "<f4"), ("vy", "<f4"), ("vz", "<f4"), ("pad", "<u4", (2,))])
 assert EPOCH_REC_DTYPE.itemsize == 32
@@ -158,6 +203,10 @@ def lib():
     L.hfpf_device_download.argtypes = [vp, vp, vp, u64]
     L.hfpf_device_copy.argtypes = [vp, vp, vp, u64]
     L.hfpf_epoch_import_gathered.argtypes = [vp, vp, u64, i32, i32, vp]
+    L.hfpf_integrate_depth.argtypes = [vp, C.POINTER(DepthImage), vp, vp, vp]
+    L.hfpf_integrate_depth_pinned.argtypes = [vp, C.POINTER(DepthImage), vp, vp, vp]
+    L.hfpf_integrate_depth_device.argtypes = [vp, C.POINTER(DepthImage), vp, u64, vp, u64, u32, vp, vp]
+    L.hfpf_probe_depth.argtypes = [vp, C.POINTER(DepthImage), vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -289,6 +338,30 @@ class OccupancyGrid:
             ids = np.ascontiguousarray(frame_ids, dtype=np.uint32)
         self._chk(lib().hfpf_integrate_device(self._h, C.c_void_p(dev_ptr), n_frames, frame_stride, n_points, point_step,
                                               off_x, off_y, off_z, off_rgb, _p(poses), _p(ids) if ids is not None else None))
+
+    def integrate_depth(self, depth, pose, K, color=None, color_format=None, depth_scale=0.001):
+        """One registered depth (+ colour) frame from numpy images in pageable memory (hfpf_integrate_depth).
+        K = (fx, fy, cx, cy); depth uint16 (counts of depth_scale metres) or float32 (metres)."""
+        d = _image_desc(depth, K, color, color_format, depth_scale)
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        self._chk(lib().hfpf_integrate_depth(self._h, C.byref(d), C.c_void_p(depth.ctypes.data),
+                                             C.c_void_p(color.ctypes.data) if color is not None else None, _p(pose)))
+
+    def integrate_depth_pinned(self, depth, pose, K, color=None, color_format=None, depth_scale=0.001):
+        """The same for images that are views of page-locked memory (host_alloc); they must stay untouched until the next sync."""
+        d = _image_desc(depth, K, color, color_format, depth_scale)
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        self._chk(lib().hfpf_integrate_depth_pinned(self._h, C.byref(d), C.c_void_p(depth.ctypes.data),
+                                                    C.c_void_p(color.ctypes.data) if color is not None else None, _p(pose)))
+
+    def integrate_depth_device(self, desc, dev_depth, depth_frame_stride, n_frames, poses, dev_color=0, color_frame_stride=0,
+                               frame_ids=None):
+        """n_frames depth frames resident in HBM (hfpf_integrate_depth_device); desc from depth_desc()."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(n_frames, 12)
+        ids = np.ascontiguousarray(frame_ids, dtype=np.uint32) if frame_ids is not None else None
+        self._chk(lib().hfpf_integrate_depth_device(self._h, C.byref(desc), C.c_void_p(dev_depth), depth_frame_stride,
+                                                    C.c_void_p(dev_color) if dev_color else None, color_frame_stride, n_frames,
+                                                    _p(poses), _p(ids) if ids is not None else None))
 
     @property
     def state_changed(self):
@@ -463,6 +536,16 @@ class OccupancyGrid:
         self.last_member_kernel_form = (member & 2) != 0
         self.last_hoisted_division_same = (member & 4) != 0
         return proj, dist, (member & 1) != 0
+
+    def probe_depth(self, depth, K, color=None, color_format=None, depth_scale=0.001):
+        """The kernels' depth-pixel loads + back-projection on one image: (H*W x 3 f32 xyz, H*W u32 rgb)."""
+        d = _image_desc(depth, K, color, color_format, depth_scale)
+        n = d.width * d.height
+        xyz = np.zeros((n, 3), np.float32)
+        rgb = np.zeros(n, np.uint32)
+        self._chk(lib().hfpf_probe_depth(self._h, C.byref(d), C.c_void_p(depth.ctypes.data),
+                                         C.c_void_p(color.ctypes.data) if color is not None else None, _p(xyz), _p(rgb)))
+        return xyz, rgb
 
     def probe_trig(self, y, x):
         y = np.ascontiguousarray(y, dtype=np.float32)

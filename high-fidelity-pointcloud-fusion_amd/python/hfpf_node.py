@@ -15,7 +15,7 @@ TF_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_d
 
 EXPORTS = ["hfpf_node_default_params", "hfpf_node_create", "hfpf_node_destroy", "hfpf_node_last_error", "hfpf_node_on_point_cloud",
            "hfpf_node_start", "hfpf_node_stop", "hfpf_node_reset", "hfpf_node_process", "hfpf_node_clean_now", "hfpf_node_grid",
-           "hfpf_node_get_stats", "hfpf_node_set_publisher"]
+           "hfpf_node_get_stats", "hfpf_node_set_publisher", "hfpf_node_on_depth_image"]
 
 
 class Params(C.Structure):
@@ -28,6 +28,10 @@ class CloudMsg(C.Structure):
     _fields_ = [("data", C.c_void_p), ("height", C.c_uint32), ("width", C.c_uint32), ("point_step", C.c_uint32),
                 ("row_step", C.c_uint32), ("off_x", C.c_uint32), ("off_y", C.c_uint32), ("off_z", C.c_uint32),
                 ("off_rgb", C.c_uint32), ("frame_id", C.c_char_p)]
+
+
+class DepthMsg(C.Structure):
+    _fields_ = [("depth", C.c_void_p), ("color", C.c_void_p), ("image", hfpf.DepthImage), ("frame_id", C.c_char_p)]
 
 
 class TriggerResponse(C.Structure):
@@ -51,6 +55,7 @@ def lib():
         L.hfpf_node_last_error.argtypes = [C.c_void_p]
         L.hfpf_node_last_error.restype = C.c_char_p
         L.hfpf_node_on_point_cloud.argtypes = [C.c_void_p, C.POINTER(CloudMsg)]
+        L.hfpf_node_on_depth_image.argtypes = [C.c_void_p, C.POINTER(DepthMsg)]
         for f in ("start", "stop", "reset", "process"):
             getattr(L, "hfpf_node_" + f).argtypes = [C.c_void_p, C.POINTER(TriggerResponse)]
         L.hfpf_node_clean_now.argtypes = [C.c_void_p]
@@ -145,6 +150,15 @@ class FusionNode:
         m = CloudMsg(buf.ctypes.data, height, width, point_step, width * point_step, offsets[0], offsets[1], offsets[2], offsets[3],
                      frame_id.encode())
         rc = lib().hfpf_node_on_point_cloud(self._h, C.byref(m))
+        if rc < 0:
+            raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
+        return rc
+
+    def publish_depth(self, depth, K, color=None, color_format=None, depth_scale=0.001, frame_id="camera"):
+        """A synchronised depth Image (+ colour Image) with its CameraInfo K = (fx, fy, cx, cy).  Returns 1 / 0 as publish."""
+        d = hfpf._image_desc(depth, K, color, color_format, depth_scale)
+        m = DepthMsg(depth.ctypes.data, color.ctypes.data if color is not None else None, d, frame_id.encode())
+        rc = lib().hfpf_node_on_depth_image(self._h, C.byref(m))
         if rc < 0:
             raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
         return rc

@@ -37,6 +37,8 @@ def lib():
         L.hfpf_synth_frame.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_void_p,
                                        C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                        C.c_uint32, C.c_void_p]
+        L.hfpf_synth_depth_frame.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_void_p,
+                                             C.c_double, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -66,3 +68,15 @@ def frame(seed, frame_idx, W, H, pose34, noise_sigma=0.0005, nan_permille=20, fx
                            layout["off_x"], layout["off_y"], layout["off_z"], layout["off_rgb"],
                            out.ctypes.data_as(C.c_void_p))
     return out
+
+
+def depth_frame(seed, frame_idx, W, H, pose34, noise_sigma=0.0005, nan_permille=20, fx=0.0, depth_scale=0.001):
+    """The same frame as `frame` renders, as the camera's native output: (uint16 HxW depth counts of depth_scale metres,
+    0 = no reading; uint8 HxWx3 RGB image; K = (fx, fy, cx, cy))."""
+    depth = np.empty((H, W), dtype=np.uint16)
+    rgb = np.empty((H, W, 3), dtype=np.uint8)
+    K = np.zeros(4, dtype=np.float64)
+    p = np.ascontiguousarray(pose34, dtype=np.float64).reshape(12)
+    lib().hfpf_synth_depth_frame(seed, frame_idx, W, H, fx, p.ctypes.data_as(C.c_void_p), noise_sigma, nan_permille, depth_scale,
+                                 depth.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p), K.ctypes.data_as(C.c_void_p))
+    return depth, rgb, tuple(float(k) for k in K)

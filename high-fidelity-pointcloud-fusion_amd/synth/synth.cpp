@@ -11,6 +11,7 @@
 // box [-0.20,-0.08]x[-0.10,0.10]x[0.40,0.60]; nominal camera at the origin looking along +z,
 // pinhole fx=fy=615*(W/640) (or fx_override: a W x H crop of a finer sensor), cx=W/2, cy=H/2.  Depth noise ~ N(0, sigma^2) (Irwin-Hall of 4),
 // nan_permille of pixels are NaN (all three coordinates), rgb = hash of (frame, pixel).
+// hfpf_synth_depth_frame renders the same pixels as a uint16 depth image + RGB8 image (the camera's native output).
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -113,6 +114,39 @@ void hfpf_synth_pose(uint64_t seed, uint32_t frame_idx, double max_angle_deg, do
     }
 }
 
+// One pixel of the scene as the sensor sees it: the ray direction dc (camera frame, dc[2] = 1), the measured depth along +z
+// (noise included) and the colour.  Returns false for a pixel without a reading (NaN by lot, or no surface hit).
+struct Pixel {
+    double dc[3];
+    double depth;
+    uint32_t rgb;
+};
+static bool render_pixel(uint64_t seed, uint32_t frame_idx, uint32_t W, uint32_t u, uint32_t v, double fx, double fy, double cx, double cy,
+                         const double pose[12], double noise_sigma, uint32_t nan_permille, Pixel& px)
+{
+    const double o[3] = {pose[3], pose[7], pose[11]};
+    const uint64_t pix = (uint64_t)v * W + u;
+    uint64_t h = splitmix64(seed + 0x51ED27ull * (uint64_t)frame_idx + pix * 0x9E3779B1ull);
+    px.dc[0] = ((double)u + 0.5 - cx) / fx;
+    px.dc[1] = ((double)v + 0.5 - cy) / fy;
+    px.dc[2] = 1.0;
+    double dw[3];
+    for (int k = 0; k < 3; k++) dw[k] = pose[4 * k] * px.dc[0] + pose[4 * k + 1] * px.dc[1] + pose[4 * k + 2] * px.dc[2];
+    double t = ray_scene(o, dw);
+    h = splitmix64(h);
+    const bool is_nan = (uint32_t)(h % 1000u) < nan_permille;
+    double g = 0;
+    for (int k = 0; k < 4; k++) {
+        h = splitmix64(h);
+        g += u01(h);
+    }
+    g = (g - 2.0) * 1.7320508075688772;  // unit variance
+    px.depth = t + g * noise_sigma;
+    h = splitmix64(h);
+    px.rgb = (uint32_t)(h & 0x00FFFFFFu);
+    return !(is_nan || t > 1e29);
+}
+
 // Renders one frame in the CAMERA frame (what the sensor publishes) into `out`
 // (W*H records of point_step bytes; bytes outside the four fields are zeroed).
 void hfpf_synth_frame(uint64_t seed, uint32_t frame_idx, uint32_t W, uint32_t H, double fx_override,
@@ -120,7 +154,6 @@ void hfpf_synth_frame(uint64_t seed, uint32_t frame_idx, uint32_t W, uint32_t H,
                       uint32_t off_z, uint32_t off_rgb, void* out)
 {
     const double fx = fx_override > 0 ? fx_override : 615.0 * ((double)W / 640.0), fy = fx, cx = W / 2.0, cy = H / 2.0;
-    const double o[3] = {pose[3], pose[7], pose[11]};
     uint8_t* base = (uint8_t*)out;
     // GPU boxes expose every host CPU but grant a small share: cap the team instead of one thread per visible CPU
     const int n_threads = omp_get_max_threads() < 16 ? omp_get_max_threads() : 16;
@@ -130,37 +163,54 @@ void hfpf_synth_frame(uint64_t seed, uint32_t frame_idx, uint32_t W, uint32_t H,
             const uint64_t pix = (uint64_t)v * W + u;
             uint8_t* rec = base + pix * (uint64_t)point_step;
             memset(rec, 0, point_step);
-            uint64_t h = splitmix64(seed + 0x51ED27ull * (uint64_t)frame_idx + pix * 0x9E3779B1ull);
-            const double dc[3] = {((double)u + 0.5 - cx) / fx, ((double)v + 0.5 - cy) / fy, 1.0};
-            double dw[3];
-            for (int k = 0; k < 3; k++) dw[k] = pose[4 * k] * dc[0] + pose[4 * k + 1] * dc[1] + pose[4 * k + 2] * dc[2];
-            double t = ray_scene(o, dw);
-            h = splitmix64(h);
-            const bool is_nan = (uint32_t)(h % 1000u) < nan_permille;
-            double g = 0;
-            for (int k = 0; k < 4; k++) {
-                h = splitmix64(h);
-                g += u01(h);
-            }
-            g = (g - 2.0) * 1.7320508075688772;  // unit variance
+            Pixel px;
             float x, y, z;
-            if (is_nan || t > 1e29) {
+            if (!render_pixel(seed, frame_idx, W, u, (uint32_t)v, fx, fy, cx, cy, pose, noise_sigma, nan_permille, px)) {
                 uint32_t q = 0x7FC00000u;
                 memcpy(&x, &q, 4);
                 y = x;
                 z = x;
             } else {
-                double depth = t + g * noise_sigma;
-                x = (float)(dc[0] * depth);
-                y = (float)(dc[1] * depth);
-                z = (float)depth;
+                x = (float)(px.dc[0] * px.depth);
+                y = (float)(px.dc[1] * px.depth);
+                z = (float)px.depth;
             }
-            h = splitmix64(h);
-            uint32_t rgb = (uint32_t)(h & 0x00FFFFFFu);
             memcpy(rec + off_x, &x, 4);
             memcpy(rec + off_y, &y, 4);
             memcpy(rec + off_z, &z, 4);
-            memcpy(rec + off_rgb, &rgb, 4);
+            memcpy(rec + off_rgb, &px.rgb, 4);
+        }
+    }
+}
+
+// The same frame as the camera's own output: a uint16 depth image (W*H counts of depth_scale metres, rounded to nearest; 0 where
+// hfpf_synth_frame emits NaN or the depth is outside 1..65535 counts) and a registered RGB8 image (W*H*3 bytes, the colour
+// hfpf_synth_frame gives the pixel).  K_out = fx, fy, cx, cy of the same pinhole with pixel centres at integer coordinates
+// (cx = W/2 - 0.5: hfpf_synth_frame casts its rays through u + 0.5).
+void hfpf_synth_depth_frame(uint64_t seed, uint32_t frame_idx, uint32_t W, uint32_t H, double fx_override, const double pose[12],
+                            double noise_sigma, uint32_t nan_permille, double depth_scale, uint16_t* depth_out, uint8_t* rgb_out,
+                            double K_out[4])
+{
+    const double fx = fx_override > 0 ? fx_override : 615.0 * ((double)W / 640.0), fy = fx, cx = W / 2.0, cy = H / 2.0;
+    K_out[0] = fx;
+    K_out[1] = fy;
+    K_out[2] = cx - 0.5;
+    K_out[3] = cy - 0.5;
+    const int n_threads = omp_get_max_threads() < 16 ? omp_get_max_threads() : 16;
+#pragma omp parallel for schedule(static) num_threads(n_threads)
+    for (int64_t v = 0; v < (int64_t)H; v++) {
+        for (uint32_t u = 0; u < W; u++) {
+            const uint64_t pix = (uint64_t)v * W + u;
+            Pixel px;
+            uint16_t d = 0;
+            if (render_pixel(seed, frame_idx, W, u, (uint32_t)v, fx, fy, cx, cy, pose, noise_sigma, nan_permille, px)) {
+                const double c = floor(px.depth / depth_scale + 0.5);
+                if (c >= 1.0 && c <= 65535.0) d = (uint16_t)c;
+            }
+            depth_out[pix] = d;
+            rgb_out[3 * pix] = (uint8_t)(px.rgb >> 16);
+            rgb_out[3 * pix + 1] = (uint8_t)(px.rgb >> 8);
+            rgb_out[3 * pix + 2] = (uint8_t)px.rgb;
         }
     }
 }

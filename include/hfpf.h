@@ -161,6 +161,65 @@ int hfpf_integrate_device(hfpf_handle* h, const void* dev_base, uint32_t n_frame
                           uint32_t n_points, uint32_t point_step, uint32_t off_x, uint32_t off_y, uint32_t off_z,
                           uint32_t off_rgb, const double* poses, const uint32_t* frame_ids);
 
+/* ---- registered depth + colour images (the sensor's own output instead of a PointCloud2) ----------------------------------
+ * A depth frame is DEFINED as the organised cloud this f32 arithmetic makes of it (modelled on depth_image_proc's convertDepth /
+ * point_cloud_xyzrgb); that cloud is then fused exactly as hfpf_integrate fuses a cloud, so rows and counters are byte-identical
+ * to those of the equivalent packed cloud (x, y, z, rgb; 16 bytes) through hfpf_integrate.  Per frame, on the host:
+ * cxf = (float)cx, cyf = (float)cy, and
+ *   HFPF_DEPTH_U16 (16UC1): unit = depth_scale (metres per count), sx = (float)((double)unit / fx), sy = (float)((double)unit / fy);
+ *                           pixel (u, v) with count d is valid iff d != 0;
+ *                           x = (((float)u - cxf) * (float)d) * sx, y = (((float)v - cyf) * (float)d) * sy, z = (float)d * unit
+ *   HFPF_DEPTH_F32 (32FC1, metres): sx = (float)(1.0 / fx), sy = (float)(1.0 / fy); valid iff isfinite(d);
+ *                           x = (((float)u - cxf) * d) * sx, y likewise, z = d
+ * Every operation f32, left to right, never contracted.  An invalid pixel becomes x = y = z = NaN: it counts in points_presented
+ * and fails the z-clip, as a NaN record of a cloud does.  Colour (same width x height as the depth image) becomes
+ * rgb = r << 16 | g << 8 | b, alpha dropped (what the reference's decode makes of an rgb field, node.cpp:170-216); HFPF_COLOR_NONE
+ * gives rgb = 0.  Points are in row-major order, i = v * width + u; viewpoint and frame ids behave as for a cloud.  Lens
+ * distortion is not modelled.  hfpf_config.frame_width is ignored: a depth frame carries its own width (16x16-pixel tiles when
+ * width and height are multiples of 16). */
+#define HFPF_DEPTH_U16 1 /* sensor_msgs/Image "16UC1" / "mono16": uint16 counts of depth_scale metres, 0 = no reading */
+#define HFPF_DEPTH_F32 2 /* "32FC1": f32 metres, non-finite = no reading */
+#define HFPF_COLOR_NONE 0
+#define HFPF_COLOR_RGB8 1  /* "rgb8" */
+#define HFPF_COLOR_BGR8 2  /* "bgr8" */
+#define HFPF_COLOR_RGBA8 3 /* "rgba8" */
+#define HFPF_COLOR_BGRA8 4 /* "bgra8" */
+
+/* One frame's (or a batch's) image geometry, formats and pinhole intrinsics (sensor_msgs/CameraInfo K: fx = K[0], fy = K[4],
+ * cx = K[2], cy = K[5]).  Rejected with HFPF_ERR_BAD_ARG (the handle stays usable): struct_size != sizeof, reserved != 0,
+ * width * height = 0 or above 2^31, an unknown format, depth_step below width * sample size or not a multiple of the sample
+ * size (2 / 4 bytes), color_step below width * bytes per pixel (3 / 4) or, for the 4-byte formats, not a multiple of 4,
+ * fx / fy not finite and positive, cx / cy not finite, depth_scale not finite and positive (U16 only; F32 ignores it),
+ * a NULL depth image, a colour image with HFPF_COLOR_NONE or none with another format.  An image occupies
+ * (height - 1) * step + width * bytes per pixel bytes; nothing behind that is read. */
+typedef struct hfpf_depth_image {
+    uint32_t struct_size;  /* = sizeof(hfpf_depth_image) */
+    uint32_t width, height;
+    uint32_t depth_format; /* HFPF_DEPTH_* */
+    uint32_t depth_step;   /* bytes per depth image row (sensor_msgs/Image step) */
+    float depth_scale;     /* metres per count of HFPF_DEPTH_U16 (0.001f for most sensors) */
+    double fx, fy, cx, cy;
+    uint32_t color_format; /* HFPF_COLOR_* */
+    uint32_t color_step;   /* bytes per colour image row (ignored with HFPF_COLOR_NONE) */
+    uint64_t reserved;     /* 0 */
+} hfpf_depth_image;
+
+/* hfpf_integrate for one depth frame (+ its registered colour image, or NULL with HFPF_COLOR_NONE) in pageable HOST memory:
+ * both images are copied into the pinned staging before the call returns; the upload, batching (HFPF_HOST_BATCH), deferred
+ * errors and the refusal of work after a failure are those of hfpf_integrate.  A depth frame takes ~5 bytes per pixel over
+ * the link instead of the 16-32 of a cloud.  Cloud and depth frames may be interleaved freely on one handle; a batch of waiting
+ * frames holds frames of one kind, size, format and intrinsics only. */
+int hfpf_integrate_depth(hfpf_handle* h, const hfpf_depth_image* desc, const void* depth, const void* color, const double pose_3x4[12]);
+/* ... from PAGE-LOCKED host memory; both buffers must stay untouched as hfpf_integrate_pinned says. */
+int hfpf_integrate_depth_pinned(hfpf_handle* h, const hfpf_depth_image* desc, const void* depth, const void* color, const double pose_3x4[12]);
+/* ... for n_frames depth frames resident in HBM: frame f's depth image at dev_depth + f * depth_frame_stride, its colour image at
+ * dev_color + f * color_frame_stride (dev_color NULL with HFPF_COLOR_NONE).  Device pointers and strides must be multiples of the
+ * sample size (depth 2 / 4, colour 4 for the 4-byte formats).  poses and frame_ids as hfpf_integrate_device (frame_ids NULL =
+ * auto; global ids for the multi-GPU schedule).  One launch covers the batch; asynchronous on the engine's stream. */
+int hfpf_integrate_depth_device(hfpf_handle* h, const hfpf_depth_image* desc, const void* dev_depth, uint64_t depth_frame_stride,
+                                const void* dev_color, uint64_t color_frame_stride, uint32_t n_frames, const double* poses,
+                                const uint32_t* frame_ids);
+
 /* OccupancyGrid::state_changed (grid.hpp:110; read at node.cpp:306). Returns 0/1, or a negative status. */
 int hfpf_is_dirty(hfpf_handle* h);
 /* OccupancyGrid::updateThicknessVectors<N,K> (grid.hpp:311-454; call sites node.cpp:311,317).

@@ -37,6 +37,16 @@ typedef struct hfpf_cloud_msg {
     const char* frame_id;                  /* header.frame_id */
 } hfpf_cloud_msg;
 
+/* A registered depth image (+ colour image) of an RGB-D camera: two sensor_msgs/Image of one stamp and the depth camera's
+ * CameraInfo (approximate-time synchronised by the caller).  `image` carries width, height, both encodings as HFPF_DEPTH_* /
+ * HFPF_COLOR_*, both row steps and K (include/hfpf.h, hfpf_depth_image). */
+typedef struct hfpf_depth_msg {
+    const void* depth;      /* depth Image data */
+    const void* color;      /* colour Image data, or NULL with image.color_format = HFPF_COLOR_NONE */
+    hfpf_depth_image image;
+    const char* frame_id;   /* header.frame_id of the depth image */
+} hfpf_depth_msg;
+
 /* std_srvs/TriggerResponse */
 typedef struct hfpf_trigger_response {
     int32_t success;
@@ -58,6 +68,10 @@ const char* hfpf_node_last_error(const hfpf_node* n);
  * Returns 1 = integrated, 0 = dropped (not started, or tf failure: warn + drop, node.cpp:340-344), < 0 = error.
  * Only the first row is consumed: n = row_step / point_step (node.cpp:185,190). */
 int hfpf_node_on_point_cloud(hfpf_node* n, const hfpf_cloud_msg* msg);
+
+/* The same callback for a depth frame: the start/stop gating, frame bookkeeping and tf lookup of hfpf_node_on_point_cloud by
+ * msg->frame_id, then hfpf_integrate_depth.  Same return values. */
+int hfpf_node_on_depth_image(hfpf_node* n, const hfpf_depth_msg* msg);
 
 /* ~start ~stop ~reset ~process (node.cpp:154-157, 351-440). start/stop/reset set success=true like the reference;
  * process writes <directory_name>/test_cloud.pcd and /meta.csv (node.cpp:395-396), clears the grid (node.cpp:438)

@@ -9,6 +9,7 @@
  *                       reference's form, bit 1 = the form the kernels use (squared distance against the largest passing value),
  *                       bit 2 = the form with the hoisted division gives the same membership, parameter and distance bit for bit
  *   hfpf_probe_trig     the deterministic atan2/cos/sin used inside the plane fit
+ *   hfpf_probe_depth    the depth-image pixel loads and back-projection (depth_backproject) of hfpf_integrate_depth
  * All pointers are HOST pointers; the probes copy in, launch, copy out and synchronise.
  */
 #ifndef HFPF_PROBE_H
@@ -26,6 +27,10 @@ int hfpf_probe_normals(hfpf_handle* h, uint64_t n, const int32_t* cells, const u
                        float* normals_out, int32_t* totals_out);
 int hfpf_probe_project(hfpf_handle* h, uint64_t n, const float* pts, const float* centres, const float* normals,
                        float* proj_out, double* dist_out, uint8_t* member_out);
+/* The depth-image loads + back-projection of the integrate kernel's depth form (hfpf_integrate_depth) on one image in host
+ * memory: width*height points, xyz_out = 3 floats each (NaN for invalid pixels), rgb_out = 0x00RRGGBB each. */
+int hfpf_probe_depth(hfpf_handle* h, const hfpf_depth_image* desc, const void* depth, const void* color, float* xyz_out,
+                     uint32_t* rgb_out);
 int hfpf_probe_trig(hfpf_handle* h, uint64_t n, const float* y, const float* x, float* atan2_out, float* cos_out,
                     float* sin_out);
 
