@@ -262,6 +262,7 @@ struct hfpf_handle {
 
     // scratch
     DevBuf sort_tmp, keys_a, keys_b, vals_a, vals_b, rows_dev, probe_a, probe_b, probe_c, probe_d, probe_e, probe_f;
+    DevBuf zbuf, render_pose, render_out;  // hfpf_render*: z-buffers of one chunk of views, the views' poses, hfpf_render's device planes
     unsigned long long* h_ctr = nullptr;  // pinned mirror of the counters
     unsigned long long* mbox = nullptr;   // coherent pinned mailbox k_publish_counters writes (HFPF_MAILBOX=0: blit copies + synchronize)
     unsigned long long mbox_seq = 0;
@@ -1598,7 +1599,7 @@ int hfpf_destroy(hfpf_handle* h)
     (void)hipStreamSynchronize(h->stream);
     for (void* p : h->allocs) (void)hipFree(p);
     for (DevBuf* b : {&h->sort_tmp, &h->keys_a, &h->keys_b, &h->vals_a, &h->vals_b, &h->rows_dev, &h->probe_a, &h->probe_b, &h->probe_c, &h->probe_d,
-                      &h->probe_e, &h->probe_f})
+                      &h->probe_e, &h->probe_f, &h->zbuf, &h->render_pose, &h->render_out})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf* b : {&h->ex_send, &h->ex_recv, &h->ex_counts, &h->stats_total, &h->bin_pt_buf, &h->bin_rgb_buf, &h->bin_sums, &h->ovf_pt_buf, &h->ovf_aux_buf, &h->pend_a, &h->pend_b})
         if (b->p) (void)hipFree(b->p);
@@ -2014,17 +2015,13 @@ int hfpf_clean(hfpf_handle* h)
     return rc;
 }
 
-// Shared tail of extract: `stats` are the (possibly merged) sums to finalise.
-static int extract_locked(hfpf_handle* h, const unsigned long long* stats, const hfpf_extract_opts* o, hfpf_row** rows, uint64_t* n_rows)
+// First half of extract (and of a render): the row set of `opt` built on the device into h->rows_dev, row j = the j-th in
+// lexicographic (x, y, z) order; *n_out rows.  `stats` are the (possibly merged) sums to finalise.
+static int build_rows_locked(hfpf_handle* h, const unsigned long long* stats, const ExtractOpts& opt, uint64_t* n_out)
 {
-    ExtractOpts opt{0.0, -1, 0};
-    if (o) {
-        opt.min_count = o->min_count;
-        opt.classify_threshold = o->classify_threshold;
-        opt.paint_white = o->paint_white ? 1 : 0;
-    }
     Tables& t = h->t;
     int rc;
+    *n_out = 0;
     const uint64_t n = h->h_ctr[C_NORMALS];
     if (n == 0) return HFPF_OK;
     if ((rc = scratch(h, h->keys_a, n * 8))) return rc;
@@ -2042,29 +2039,21 @@ static int extract_locked(hfpf_handle* h, const unsigned long long* stats, const
     hipLaunchKernelGGL(k_extract_rows, dim3(blocks_for(nr, 256)), dim3(256), 0, h->stream, h->g, t, stats, nr, opt, (const uint64_t*)h->keys_b.p,
                        (const uint32_t*)h->vals_b.p, (Row*)h->rows_dev.p);
     HIPCHK(h, hipGetLastError());
-    // (2 MB-aligned and advised as huge pages: a fresh 125 MB result is then ~60 page faults instead of 30,000 while it is filled)
-    hfpf_row* host = nullptr;
-    {
-        void* mem = nullptr;
-        const size_t want = nr * sizeof(hfpf_row);
-        if (want >= (4u << 20) && posix_memalign(&mem, 2u << 20, (want + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1)) == 0) {
-            (void)madvise(mem, (want + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1), MADV_HUGEPAGE);
-            host = (hfpf_row*)mem;
-        } else {
-            host = (hfpf_row*)malloc(want);
-        }
-    }
-    if (!host) return fail(h, HFPF_ERR_CAPACITY, "extract: host allocation of %llu rows failed", (unsigned long long)nr);
-    // The rows go to pageable memory the caller will free(): a direct device-to-pageable copy runs at ~10 GB/s through the
-    // runtime's own staging.  Two pinned 16 MB buffers instead: chunk i+1 crosses the link while chunk i is copied out by the
-    // caller and the helper threads.
-    const size_t total = nr * sizeof(Row);
+    *n_out = nr;
+    return HFPF_OK;
+}
+
+// Device -> pageable host copy, complete on return.  A direct device-to-pageable copy runs at ~10 GB/s through the runtime's own
+// staging.  Copies of at least `pinned_from` bytes go through the two pinned 16 MB buffers instead: chunk i+1 crosses the link while
+// chunk i is copied out by the caller and the helper threads.
+static hipError_t download_pageable(hfpf_handle* h, void* host, const void* dev, size_t total, size_t pinned_from = 2 * kXferChunk)
+{
     hipError_t e = hipSuccess;
-    if (h->xfer_pin[0] && total >= 2 * kXferChunk) {
+    if (h->xfer_pin[0] && total >= pinned_from) {
         const size_t n_chunks = (total + kXferChunk - 1) / kXferChunk;
         auto issue = [&](size_t i) -> hipError_t {
             const size_t off = i * kXferChunk, len = std::min(kXferChunk, total - off);
-            const hipError_t r = hipMemcpyAsync(h->xfer_pin[i & 1], (const char*)h->rows_dev.p + off, len, hipMemcpyDeviceToHost, h->stream);
+            const hipError_t r = hipMemcpyAsync(h->xfer_pin[i & 1], (const char*)dev + off, len, hipMemcpyDeviceToHost, h->stream);
             return r != hipSuccess ? r : hipEventRecord(h->xfer_ev[i & 1], h->stream);
         };
         e = issue(0);
@@ -2078,9 +2067,39 @@ static int extract_locked(hfpf_handle* h, const unsigned long long* stats, const
         }
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     } else {
-        e = hipMemcpyAsync(host, h->rows_dev.p, total, hipMemcpyDeviceToHost, h->stream);
+        e = hipMemcpyAsync(host, dev, total, hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     }
+    return e;
+}
+
+// Shared tail of extract: `stats` are the (possibly merged) sums to finalise.
+static int extract_locked(hfpf_handle* h, const unsigned long long* stats, const hfpf_extract_opts* o, hfpf_row** rows, uint64_t* n_rows)
+{
+    ExtractOpts opt{0.0, -1, 0};
+    if (o) {
+        opt.min_count = o->min_count;
+        opt.classify_threshold = o->classify_threshold;
+        opt.paint_white = o->paint_white ? 1 : 0;
+    }
+    uint64_t nr = 0;
+    if (int rc = build_rows_locked(h, stats, opt, &nr)) return rc;
+    if (nr == 0) return HFPF_OK;
+    // (2 MB-aligned and advised as huge pages: a fresh 125 MB result is then ~60 page faults instead of 30,000 while it is filled)
+    hfpf_row* host = nullptr;
+    {
+        void* mem = nullptr;
+        const size_t want = nr * sizeof(hfpf_row);
+        if (want >= (4u << 20) && posix_memalign(&mem, 2u << 20, (want + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1)) == 0) {
+            (void)madvise(mem, (want + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1), MADV_HUGEPAGE);
+            host = (hfpf_row*)mem;
+        } else {
+            host = (hfpf_row*)malloc(want);
+        }
+    }
+    if (!host) return fail(h, HFPF_ERR_CAPACITY, "extract: host allocation of %llu rows failed", (unsigned long long)nr);
+    // The rows go to pageable memory the caller will free()
+    const hipError_t e = download_pageable(h, host, h->rows_dev.p, nr * sizeof(Row));
     if (e != hipSuccess) {
         free(host);
         return fail(h, HFPF_ERR_HIP, "extract copy: %s", hipGetErrorString(e));
@@ -2143,6 +2162,110 @@ int hfpf_extract_with_stats(hfpf_handle* h, const void* dev_words, const void* d
     if ((rc = check_device_errors(h))) return rc;
     (void)dev_cwords;  // colour sums travel in words 5-7 of the statistics records since ABI 3
     return extract_locked(h, (const unsigned long long*)dev_words, nullptr, rows, n_rows);
+}
+
+// ---- render (include/hfpf.h) ----------------------------------------------------------------------------------------------
+static bool render_opts_ok(const hfpf_render_opts* o, const hfpf_render_planes* pl)
+{
+    if (!o || !pl || o->struct_size != sizeof(hfpf_render_opts) || o->reserved != 0) return false;
+    if (o->flags & ~(HFPF_RENDER_CULL_BACKFACES | HFPF_RENDER_WORLD_NORMALS)) return false;
+    const uint64_t wh = (uint64_t)o->width * o->height;
+    if (wh == 0 || wh > (1ull << 31)) return false;
+    if (!(std::isfinite(o->fx) && o->fx > 0.0 && std::isfinite(o->fy) && o->fy > 0.0 && std::isfinite(o->cx) && std::isfinite(o->cy))) return false;
+    if (!(std::isfinite(o->z_near) && std::isfinite(o->z_far) && 0.0 < o->z_near && o->z_near < o->z_far)) return false;
+    if (std::isnan(o->min_count)) return false;
+    if (o->splat_radius < -1 || o->splat_radius > 15 || o->max_splat_radius < 0 || o->max_splat_radius > 15) return false;
+    return pl->depth || pl->normal || pl->rgb || pl->count || pl->voxel;
+}
+
+// What extract does in front of its row set (single GPU): launch waiting host frames, refuse a failed handle, read the counters.
+static int render_prelude_locked(hfpf_handle* h)
+{
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (h->dist_on) return fail(h, HFPF_ERR_STATE, "render: not available on a handle with an RCCL communicator (hfpf_dist_disable drops it)");
+    int rc = poison_on_error(h, flush_pending_locked(h));  // host frames still waiting for their launch
+    if (!rc) rc = check_usable(h);
+    if (!rc) rc = read_counters(h);
+    if (!rc) rc = poison_on_error(h, check_device_errors(h));
+    return rc;
+}
+
+// The row set once, then per chunk of views: z-buffers to all ones, k_render_splat, k_render_resolve into the device planes.
+static int render_locked(hfpf_handle* h, const hfpf_render_opts* o, uint32_t n_views, const double* poses, const hfpf_render_planes& dev)
+{
+    int rc;
+    uint64_t nr = 0;
+    const ExtractOpts opt{std::max(1.0, o->min_count), -1, 0};  // count >= max(1, min_count), the compare of k_extract_keys
+    if ((rc = build_rows_locked(h, h->t.stats, opt, &nr))) return rc;
+    if (nr > 0xFFFFFFFFull) return fail(h, HFPF_ERR_CAPACITY, "render: %llu rows do not fit the 32-bit row field of a z-buffer word", (unsigned long long)nr);
+    const uint64_t WH = (uint64_t)o->width * o->height;
+    const uint32_t per_chunk = (uint32_t)std::min<uint64_t>({(uint64_t)kRenderChunkViews, std::max<uint64_t>(1, kRenderZbufBytes / (8 * WH)), n_views});
+    if ((rc = scratch(h, h->zbuf, per_chunk * WH * 8))) return rc;
+    if ((rc = scratch(h, h->render_pose, (size_t)n_views * 12 * sizeof(double)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->render_pose.p, poses, (size_t)n_views * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    RenderParams p{};
+    p.width = o->width;
+    p.height = o->height;
+    p.cull = (o->flags & HFPF_RENDER_CULL_BACKFACES) ? 1u : 0u;
+    p.world_normals = (o->flags & HFPF_RENDER_WORLD_NORMALS) ? 1u : 0u;
+    p.radius = o->splat_radius;
+    p.max_radius = o->max_splat_radius;
+    p.fx = o->fx, p.fy = o->fy, p.cx = o->cx, p.cy = o->cy, p.z_near = o->z_near, p.z_far = o->z_far;
+    p.r_num = (0.5 * h->g.res) * std::max(o->fx, o->fy);
+    const Row* rows = (const Row*)h->rows_dev.p;
+    unsigned long long* zb = (unsigned long long*)h->zbuf.p;
+    for (uint32_t v0 = 0; v0 < n_views; v0 += per_chunk) {
+        p.n_views = std::min(per_chunk, n_views - v0);
+        const uint64_t pix = p.n_views * WH, off = v0 * WH;
+        const double* pose_d = (const double*)h->render_pose.p + 12ull * v0;
+        HIPCHK(h, hipMemsetAsync(zb, 0xFF, pix * 8, h->stream));
+        if (nr) hipLaunchKernelGGL(k_render_splat, dim3(blocks_for(nr, 256)), dim3(256), 0, h->stream, rows, (uint32_t)nr, pose_d, p, zb);
+        const RenderPlanes pl{dev.depth ? dev.depth + off : nullptr, dev.normal ? dev.normal + 3 * off : nullptr, dev.rgb ? dev.rgb + off : nullptr,
+                              dev.count ? dev.count + off : nullptr, dev.voxel ? dev.voxel + 3 * off : nullptr};
+        hipLaunchKernelGGL(k_render_resolve, dim3(blocks_for(pix, 256)), dim3(256), 0, h->stream, rows, (const unsigned long long*)zb, pose_d, p, pl);
+        HIPCHK(h, hipGetLastError());
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return HFPF_OK;
+}
+
+int hfpf_render_device(hfpf_handle* h, const hfpf_render_opts* o, uint32_t n_views, const double* poses, const hfpf_render_planes* dev_out)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (!render_opts_ok(o, dev_out)) return fail(h, HFPF_ERR_BAD_ARG, "render: invalid options or planes");
+    if (n_views == 0) return HFPF_OK;
+    if (!poses) return fail(h, HFPF_ERR_BAD_ARG, "render: NULL poses");
+    if (int rc = render_prelude_locked(h)) return rc;
+    return render_locked(h, o, n_views, poses, *dev_out);
+}
+
+int hfpf_render(hfpf_handle* h, const hfpf_render_opts* o, const double pose_3x4[12], const hfpf_render_planes* host_out)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (!render_opts_ok(o, host_out) || !pose_3x4) return fail(h, HFPF_ERR_BAD_ARG, "render: invalid options, pose or planes");
+    if (int rc = render_prelude_locked(h)) return rc;
+    // device planes, each 256-byte aligned, in one scratch buffer; then one download per requested plane
+    const uint64_t WH = (uint64_t)o->width * o->height;
+    void* host[5] = {host_out->depth, host_out->normal, host_out->rgb, host_out->count, host_out->voxel};
+    const uint64_t bytes[5] = {4 * WH, 12 * WH, 4 * WH, 4 * WH, 12 * WH};
+    uint64_t off[5], total = 0;
+    for (int k = 0; k < 5; k++) {
+        off[k] = total;
+        if (host[k]) total += (bytes[k] + 255) & ~255ull;
+    }
+    if (int rc = scratch(h, h->render_out, total)) return rc;
+    char* base = (char*)h->render_out.p;
+    auto at = [&](int k) -> void* { return host[k] ? base + off[k] : nullptr; };
+    const hfpf_render_planes dev{(float*)at(0), (float*)at(1), (uint32_t*)at(2), (uint32_t*)at(3), (int32_t*)at(4)};
+    if (int rc = render_locked(h, o, 1, pose_3x4, dev)) return rc;
+    for (int k = 0; k < 5; k++) {
+        if (!host[k]) continue;
+        const hipError_t e = download_pageable(h, host[k], base + off[k], bytes[k], 0);  // every plane through the pinned buffers
+        if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "render copy: %s", hipGetErrorString(e));
+    }
+    return HFPF_OK;
 }
 
 int hfpf_stats_export(hfpf_handle* h, const void** dev_words, uint64_t* n_words, const void** dev_cwords, uint64_t* n_cwords)

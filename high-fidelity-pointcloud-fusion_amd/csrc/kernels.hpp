@@ -2100,6 +2100,121 @@ __global__ __launch_bounds__(256) void k_extract_rows(const GridParams g, const 
 }
 
 
+// ---- render (hfpf_render*, include/hfpf.h) ----------------------------------------------------------------------------
+// The rows are the extract row set (k_extract_keys -> sort -> k_extract_rows) with min_count raised to max(1, min_count): row j is
+// the j-th in lexicographic (ix, iy, iz) order, so "smallest row index" is the contract's tie rule.  A z-buffer word is
+// bits(depth32) << 32 | row: depth32 > 0 (zc > z_near > 0), so the unsigned order of the words is (depth, lex) order and the
+// pixel's winner is the 64-bit minimum -- independent of the order the candidates arrive in.  The buffer starts all ones.
+constexpr int kRenderChunkViews = 64;                 // views per splat launch (their poses sit in LDS: 6 KB)
+constexpr size_t kRenderZbufBytes = 256ull << 20;     // z-buffer scratch of one chunk (one view may exceed it alone)
+constexpr unsigned long long kRenderEmpty = ~0ull;
+
+struct RenderParams {
+    uint32_t width, height;
+    uint32_t n_views;        // views of this chunk
+    uint32_t cull;           // HFPF_RENDER_CULL_BACKFACES
+    uint32_t world_normals;  // HFPF_RENDER_WORLD_NORMALS
+    int32_t radius;          // >= 0 fixed, -1 auto
+    int32_t max_radius;
+    uint32_t pad;
+    double fx, fy, cx, cy, z_near, z_far;
+    double r_num;            // (0.5 * res) * max(fx, fy): the auto radius is floor(r_num / zc), evaluated as the contract writes it
+};
+
+// One thread per row, looping over the chunk's views.  Of the 64-byte row only count, x..z and nx..nz are read.  A candidate first
+// reads the pixel's word with a plain load and skips the atomic when it is already <= its own: words only ever decrease, so a stale
+// value is >= the current one and the skip is exact.  Under overdraw most candidates end there.
+__global__ __launch_bounds__(256) void k_render_splat(const Row* __restrict__ rows, const uint32_t n_rows, const double* __restrict__ poses,
+                                                      const RenderParams p, unsigned long long* __restrict__ zbuf)
+{
+    __shared__ double s_pose[kRenderChunkViews * 12];
+    for (uint32_t i = threadIdx.x; i < p.n_views * 12u; i += blockDim.x) s_pose[i] = poses[i];
+    __syncthreads();
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_rows) return;
+    const float4 q0 = *reinterpret_cast<const float4*>(&rows[j].x);   // x, y, z, nx
+    const float2 q1 = *reinterpret_cast<const float2*>(&rows[j].ny);  // ny, nz
+    const double x = q0.x, y = q0.y, z = q0.z, nx = q0.w, ny = q1.x, nz = q1.y;
+    const uint64_t W = p.width, WH = (uint64_t)p.width * p.height;
+    for (uint32_t v = 0; v < p.n_views; v++) {
+        const double* T = &s_pose[12 * v];
+        const double dx = x - T[3], dy = y - T[7], dz = z - T[11];
+        const double zc = (T[2] * dx + T[6] * dy) + T[10] * dz;
+        if (!(p.z_near < zc && zc < p.z_far)) continue;
+        if (p.cull && !(((nx * dx + ny * dy) + nz * dz) < 0.0)) continue;
+        const double xc = (T[0] * dx + T[4] * dy) + T[8] * dz;
+        const double yc = (T[1] * dx + T[5] * dy) + T[9] * dz;
+        const double u = (xc / zc) * p.fx + p.cx;
+        const double w = (yc / zc) * p.fy + p.cy;
+        if (!(fabs(u) < 1073741824.0 && fabs(w) < 1073741824.0)) continue;
+        const int pu = (int)floor(u + 0.5), pv = (int)floor(w + 0.5);
+        int r = p.radius;
+        if (r < 0) {
+            const double ra = floor(p.r_num / zc);
+            r = ra < (double)p.max_radius ? (int)ra : p.max_radius;
+        }
+        const int x0 = max(pu - r, 0), x1 = min(pu + r, (int)p.width - 1);
+        const int y0 = max(pv - r, 0), y1 = min(pv + r, (int)p.height - 1);
+        const unsigned long long word = (unsigned long long)__float_as_uint((float)zc) << 32 | j;
+        unsigned long long* zv = zbuf + v * WH;
+        for (int py = y0; py <= y1; py++)
+            for (int px = x0; px <= x1; px++) {
+                unsigned long long* a = zv + (uint64_t)py * W + (uint64_t)px;
+                if (__hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > word) atomicMin(a, word);
+            }
+    }
+}
+
+// One thread per pixel of the chunk: the winner's row is fetched once and the requested planes are written (NULL planes are
+// skipped).  Plane pointers are already offset to the chunk's first view.
+struct RenderPlanes {
+    float* depth;
+    float* normal;
+    uint32_t* rgb;
+    uint32_t* count;
+    int32_t* voxel;
+};
+__global__ __launch_bounds__(256) void k_render_resolve(const Row* __restrict__ rows, const unsigned long long* __restrict__ zbuf,
+                                                        const double* __restrict__ poses, const RenderParams p, const RenderPlanes o)
+{
+    const uint64_t WH = (uint64_t)p.width * p.height;
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= WH * p.n_views) return;
+    const unsigned long long word = zbuf[i];
+    const float qnan = __uint_as_float(0x7FC00000u);
+    if (word == kRenderEmpty) {
+        if (o.depth) o.depth[i] = qnan;
+        if (o.normal) o.normal[3 * i] = o.normal[3 * i + 1] = o.normal[3 * i + 2] = qnan;
+        if (o.rgb) o.rgb[i] = 0u;
+        if (o.count) o.count[i] = 0u;
+        if (o.voxel) o.voxel[3 * i] = o.voxel[3 * i + 1] = o.voxel[3 * i + 2] = -1;
+        return;
+    }
+    const Row& r = rows[(uint32_t)word];
+    if (o.depth) o.depth[i] = __uint_as_float((uint32_t)(word >> 32));
+    if (o.normal) {
+        float n0 = r.nx, n1 = r.ny, n2 = r.nz;
+        if (!p.world_normals) {
+            const double* T = poses + 12 * (i / WH);
+            const double nx = n0, ny = n1, nz = n2;
+            n0 = (float)((T[0] * nx + T[4] * ny) + T[8] * nz);
+            n1 = (float)((T[1] * nx + T[5] * ny) + T[9] * nz);
+            n2 = (float)((T[2] * nx + T[6] * ny) + T[10] * nz);
+        }
+        o.normal[3 * i] = n0;
+        o.normal[3 * i + 1] = n1;
+        o.normal[3 * i + 2] = n2;
+    }
+    if (o.rgb) o.rgb[i] = r.rgb;
+    if (o.count) o.count[i] = r.count;
+    if (o.voxel) {
+        o.voxel[3 * i] = r.ix;
+        o.voxel[3 * i + 1] = r.iy;
+        o.voxel[3 * i + 2] = r.iz;
+    }
+}
+
+
 // ---- multi-GPU epoch exchange ----------------------------------------------------------
 // Frames shard across ranks; what must be agreed before a clean pass is the occupancy set and, per cell, the
 // smallest frame id that touched it (the viewpoint latch).  Each rank exports the cells IT occupied since

@@ -88,6 +88,7 @@ EXPORTS = [
     "hfpf_dist_unique_id", "hfpf_dist_init", "hfpf_dist_info", "hfpf_dist_disable", "hfpf_epoch_export", "hfpf_epoch_import", "hfpf_stats_export",
     "hfpf_extract_with_stats", "hfpf_device_download", "hfpf_device_copy", "hfpf_epoch_import_gathered",
     "hfpf_integrate_depth", "hfpf_integrate_depth_pinned", "hfpf_integrate_depth_device", "hfpf_probe_depth",
+    "hfpf_render", "hfpf_render_device",
 ]
 
 # hfpf_depth_image formats (include/hfpf.h)
@@ -133,6 +134,38 @@ def _image_desc(depth, K, color, color_format, depth_scale):
             raise ValueError("color_format %r does not match a %d-channel image" % (color_format, color.shape[2]))
         cstep = color.strides[0]
     return depth_desc(W, H, fmt, depth.strides[0], K, color_format, cstep, depth_scale)
+
+# hfpf_render_opts.flags (include/hfpf.h)
+RENDER_CULL_BACKFACES = 1
+RENDER_WORLD_NORMALS = 2
+# render planes: (name, numpy dtype, channels); empty pixels hold NaN (depth, normal), 0 (rgb, count) or -1 (voxel)
+RENDER_PLANES = (("depth", np.float32, 1), ("normal", np.float32, 3), ("rgb", np.uint32, 1), ("count", np.uint32, 1), ("voxel", np.int32, 3))
+
+
+class RenderOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("z_near", C.c_double), ("z_far", C.c_double), ("min_count", C.c_double),
+                ("splat_radius", C.c_int32), ("max_splat_radius", C.c_int32), ("reserved", C.c_uint64)]
+
+
+class RenderPlanes(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name, _, _ in RENDER_PLANES]
+
+
+def render_opts(K, width, height, z_range=(0.01, 100.0), min_count=0.0, splat_radius=0, max_splat_radius=4, cull_backfaces=False,
+                world_normals=False):
+    """An hfpf_render_opts; K = (fx, fy, cx, cy), splat_radius -1 = auto (capped at max_splat_radius)."""
+    o = RenderOpts()
+    o.struct_size = C.sizeof(RenderOpts)
+    o.width, o.height = int(width), int(height)
+    o.flags = (RENDER_CULL_BACKFACES if cull_backfaces else 0) | (RENDER_WORLD_NORMALS if world_normals else 0)
+    o.fx, o.fy, o.cx, o.cy = (float(k) for k in K)
+    o.z_near, o.z_far = (float(z) for z in z_range)
+    o.min_count = float(min_count)
+    o.splat_radius, o.max_splat_radius = int(splat_radius), int(max_splat_radius)
+    return o
+
 
 EPOCH_REC_DTYPE = np.dtype([("key", "<u8"), ("first_frame", "<u4"), ("vx", "<f4"), ("vy", "<f4"), ("vz", "<f4"), ("pad", "<u4", (2,))])
 assert EPOCH_REC_DTYPE.itemsize == 32
@@ -207,6 +240,8 @@ def lib():
     L.hfpf_integrate_depth_pinned.argtypes = [vp, C.POINTER(DepthImage), vp, vp, vp]
     L.hfpf_integrate_depth_device.argtypes = [vp, C.POINTER(DepthImage), vp, u64, vp, u64, u32, vp, vp]
     L.hfpf_probe_depth.argtypes = [vp, C.POINTER(DepthImage), vp, vp, vp, vp]
+    L.hfpf_render.argtypes = [vp, C.POINTER(RenderOpts), vp, C.POINTER(RenderPlanes)]
+    L.hfpf_render_device.argtypes = [vp, C.POINTER(RenderOpts), u32, vp, C.POINTER(RenderPlanes)]
     _lib = L
     return L
 
@@ -396,6 +431,36 @@ class OccupancyGrid:
         n = C.c_uint64()
         self._chk(lib().hfpf_extract_filtered(self._h, C.byref(o), C.byref(rows), C.byref(n)))
         return self._rows_out(rows, n)
+
+    # -- looking at the model from a camera --
+    def render(self, pose, K, width, height, planes=("depth", "normal", "rgb", "count", "voxel"), opts=None, **kw):
+        """One view of the fused model (hfpf_render): pose = camera -> fusion frame 3x4, K = (fx, fy, cx, cy).  Keywords as
+        render_opts (z_range, min_count, splat_radius, max_splat_radius, cull_backfaces, world_normals), or a ready `opts`.
+        Returns {plane: HxW (depth, rgb, count) or HxWx3 (normal, voxel) array} for the requested planes."""
+        o = opts if opts is not None else render_opts(K, width, height, **kw)
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        out, pl = {}, RenderPlanes()
+        for name, dt, ch in RENDER_PLANES:
+            if name in planes:
+                out[name] = np.empty((o.height, o.width, ch) if ch > 1 else (o.height, o.width), dtype=dt)
+                setattr(pl, name, out[name].ctypes.data)
+        unknown = set(planes) - set(out)
+        if unknown:
+            raise ValueError("unknown render planes %s" % sorted(unknown))
+        self._chk(lib().hfpf_render(self._h, C.byref(o), _p(pose), C.byref(pl)))
+        return out
+
+    def render_device(self, poses, K, width, height, dev_planes, opts=None, **kw):
+        """len(poses) views into device planes (hfpf_render_device): dev_planes = {plane: device pointer}; view v of a plane
+        starts v * width * height elements (x 3 for normal and voxel) behind its pointer."""
+        o = opts if opts is not None else render_opts(K, width, height, **kw)
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12)
+        pl = RenderPlanes()
+        for name, ptr in dev_planes.items():
+            if name not in RenderPlanes.__dict__:
+                raise ValueError("unknown render plane %r" % name)
+            setattr(pl, name, ptr)
+        self._chk(lib().hfpf_render_device(self._h, C.byref(o), poses.shape[0], _p(poses), C.byref(pl)))
 
     # -- multi-GPU --
     def dist_init_rccl(self, rank, world, unique_id):

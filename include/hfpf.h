@@ -252,6 +252,60 @@ typedef struct hfpf_extract_opts {
     int32_t reserved0;
 } hfpf_extract_opts;
 int hfpf_extract_filtered(hfpf_handle* h, const hfpf_extract_opts* opts, hfpf_row** rows, uint64_t* n_rows);
+/* ---- rendering the fused model from a camera (the inverse of depth integration; no reference counterpart) -------------------
+ * A render draws exactly the rows hfpf_extract would return at that point of the call sequence (host frames still waiting for
+ * their launch are launched first, as extract does), splatted into a pinhole image.  pose_3x4 follows the integrate convention:
+ * row-major [R|t], camera -> fusion frame.  All arithmetic is f64, left to right, never contracted.  For a row with f32 (x, y, z)
+ * and normal (nx, ny, nz), T = pose_3x4:
+ *   dx = (double)x - T[3], dy = (double)y - T[7], dz = (double)z - T[11]
+ *   xc = (T[0]*dx + T[4]*dy) + T[8]*dz,  yc = (T[1]*dx + T[5]*dy) + T[9]*dz,  zc = (T[2]*dx + T[6]*dy) + T[10]*dz
+ *   the row is drawn iff count >= max(1, min_count) (the compare of hfpf_extract_opts), z_near < zc < z_far and, with
+ *   HFPF_RENDER_CULL_BACKFACES, ((nx*dx + ny*dy) + nz*dz) < 0 (nx.. widened to double)
+ *   u = (xc / zc) * fx + cx,  v = (yc / zc) * fy + cy;  skipped unless |u| < 2^30 and |v| < 2^30
+ *   pu = floor(u + 0.5), pv = floor(v + 0.5)   (the pixel whose centre back-projects onto the row: the inverse of a depth frame)
+ *   r = splat_radius, or for -1: min(max_splat_radius, floor(((0.5 * res) * max(fx, fy)) / zc)), res = hfpf_get_dims' resolution
+ *   candidates: every pixel (pu + i, pv + j), |i|, |j| <= r, inside [0, width) x [0, height);  depth32 = (float)zc
+ * Each pixel takes the candidate with the smallest depth32; ties go to the lexicographically smallest (ix, iy, iz), so the image
+ * does not depend on scheduling.  From the winner: depth = depth32; rgb, count and voxel = the row's own values; normal = the
+ * row's normal in the camera frame ((T[0]*nx + T[4]*ny) + T[8]*nz, (T[1]*nx + T[5]*ny) + T[9]*nz, (T[2]*nx + T[6]*ny) + T[10]*nz,
+ * each rounded to f32) or, with HFPF_RENDER_WORLD_NORMALS, as stored.  Empty pixels: depth and normal NaN (0x7FC00000), rgb and
+ * count 0, voxel -1.
+ * A render changes nothing on the handle: tables, counters and later results are those without it, except that device_bytes
+ * counts the scratch it keeps (8 bytes per pixel per view of a chunk of at most 256 MB, plus the row set and, for hfpf_render,
+ * its planes).  Rejected with HFPF_ERR_BAD_ARG (the handle stays usable): struct_size != sizeof, unknown flags, reserved != 0,
+ * width * height = 0 or above 2^31, fx / fy not finite and positive, cx / cy not finite, not 0 < z_near < z_far with both
+ * finite, min_count NaN, splat_radius outside -1..15, max_splat_radius outside 0..15, a NULL pose array, every plane NULL.
+ * A handle with an RCCL communicator returns HFPF_ERR_STATE (a distributed render is not provided); a failed handle returns
+ * HFPF_ERR_STATE as extract does.  Both calls return when the planes are complete. */
+#define HFPF_RENDER_CULL_BACKFACES 1u /* skip rows whose normal faces away from the camera */
+#define HFPF_RENDER_WORLD_NORMALS 2u  /* normal plane in the fusion frame (default: camera frame) */
+
+typedef struct hfpf_render_opts {
+    uint32_t struct_size;   /* = sizeof(hfpf_render_opts) */
+    uint32_t width, height; /* image size; width * height in 1..2^31 */
+    uint32_t flags;         /* HFPF_RENDER_* */
+    double fx, fy, cx, cy;  /* pinhole intrinsics, as hfpf_depth_image */
+    double z_near, z_far;   /* a row is drawn iff z_near < zc < z_far */
+    double min_count;       /* rows with count < max(1, min_count) are not drawn */
+    int32_t splat_radius;   /* >= 0: fixed half-width in pixels (0 = one pixel); -1: auto per row (above) */
+    int32_t max_splat_radius; /* cap of the auto radius, 0..15 */
+    uint64_t reserved;      /* 0 */
+} hfpf_render_opts;
+
+typedef struct hfpf_render_planes { /* every plane optional (NULL = not produced); at least one non-NULL */
+    float* depth;    /* width * height: camera-frame z in metres */
+    float* normal;   /* width * height * 3 */
+    uint32_t* rgb;   /* width * height: the row's rgb (0x00RRGGBB) */
+    uint32_t* count; /* width * height: the row's count */
+    int32_t* voxel;  /* width * height * 3: the row's ix, iy, iz */
+} hfpf_render_planes;
+
+/* One view into pageable HOST planes. */
+int hfpf_render(hfpf_handle* h, const hfpf_render_opts* o, const double pose_3x4[12], const hfpf_render_planes* host_out);
+/* n_views views (poses = n_views * 12 f64 in HOST memory) into DEVICE planes: view v's plane starts v * width * height elements
+ * (times 3 for normal and voxel) behind the plane's base.  The row set is built once for all views.  n_views = 0 does nothing. */
+int hfpf_render_device(hfpf_handle* h, const hfpf_render_opts* o, uint32_t n_views, const double* poses, const hfpf_render_planes* dev_out);
+
 /* <directory_name>/test_cloud.pcd (node.cpp:395): PCD v0.7 ASCII, FIELDS x y z rgb normal_x normal_y normal_z curvature */
 int hfpf_write_pcd(const hfpf_row* rows, uint64_t n_rows, const char* path);
 /* <directory_name>/meta.csv (node.cpp:396) with the header string of grid.hpp:462 */
