@@ -263,6 +263,7 @@ struct hfpf_handle {
     // scratch
     DevBuf sort_tmp, keys_a, keys_b, vals_a, vals_b, rows_dev, probe_a, probe_b, probe_c, probe_d, probe_e, probe_f;
     DevBuf zbuf, render_pose, render_out;  // hfpf_render*: z-buffers of one chunk of views, the views' poses, hfpf_render's device planes
+    DevBuf track_in, track_acc;            // hfpf_track*: a host frame's device copy, the 30 int64 sums of one iteration
     unsigned long long* h_ctr = nullptr;  // pinned mirror of the counters
     unsigned long long* mbox = nullptr;   // coherent pinned mailbox k_publish_counters writes (HFPF_MAILBOX=0: blit copies + synchronize)
     unsigned long long mbox_seq = 0;
@@ -1599,7 +1600,7 @@ int hfpf_destroy(hfpf_handle* h)
     (void)hipStreamSynchronize(h->stream);
     for (void* p : h->allocs) (void)hipFree(p);
     for (DevBuf* b : {&h->sort_tmp, &h->keys_a, &h->keys_b, &h->vals_a, &h->vals_b, &h->rows_dev, &h->probe_a, &h->probe_b, &h->probe_c, &h->probe_d,
-                      &h->probe_e, &h->probe_f, &h->zbuf, &h->render_pose, &h->render_out})
+                      &h->probe_e, &h->probe_f, &h->zbuf, &h->render_pose, &h->render_out, &h->track_in, &h->track_acc})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf* b : {&h->ex_send, &h->ex_recv, &h->ex_counts, &h->stats_total, &h->bin_pt_buf, &h->bin_rgb_buf, &h->bin_sums, &h->ovf_pt_buf, &h->ovf_aux_buf, &h->pend_a, &h->pend_b})
         if (b->p) (void)hipFree(b->p);
@@ -2165,24 +2166,28 @@ int hfpf_extract_with_stats(hfpf_handle* h, const void* dev_words, const void* d
 }
 
 // ---- render (include/hfpf.h) ----------------------------------------------------------------------------------------------
-static bool render_opts_ok(const hfpf_render_opts* o, const hfpf_render_planes* pl)
+static bool view_opts_ok(const hfpf_render_opts* o)
 {
-    if (!o || !pl || o->struct_size != sizeof(hfpf_render_opts) || o->reserved != 0) return false;
+    if (!o || o->struct_size != sizeof(hfpf_render_opts) || o->reserved != 0) return false;
     if (o->flags & ~(HFPF_RENDER_CULL_BACKFACES | HFPF_RENDER_WORLD_NORMALS)) return false;
     const uint64_t wh = (uint64_t)o->width * o->height;
     if (wh == 0 || wh > (1ull << 31)) return false;
     if (!(std::isfinite(o->fx) && o->fx > 0.0 && std::isfinite(o->fy) && o->fy > 0.0 && std::isfinite(o->cx) && std::isfinite(o->cy))) return false;
     if (!(std::isfinite(o->z_near) && std::isfinite(o->z_far) && 0.0 < o->z_near && o->z_near < o->z_far)) return false;
     if (std::isnan(o->min_count)) return false;
-    if (o->splat_radius < -1 || o->splat_radius > 15 || o->max_splat_radius < 0 || o->max_splat_radius > 15) return false;
-    return pl->depth || pl->normal || pl->rgb || pl->count || pl->voxel;
+    return !(o->splat_radius < -1 || o->splat_radius > 15 || o->max_splat_radius < 0 || o->max_splat_radius > 15);
+}
+
+static bool render_opts_ok(const hfpf_render_opts* o, const hfpf_render_planes* pl)
+{
+    return view_opts_ok(o) && pl && (pl->depth || pl->normal || pl->rgb || pl->count || pl->voxel);
 }
 
 // What extract does in front of its row set (single GPU): launch waiting host frames, refuse a failed handle, read the counters.
-static int render_prelude_locked(hfpf_handle* h)
+static int render_prelude_locked(hfpf_handle* h, const char* what = "render")
 {
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (h->dist_on) return fail(h, HFPF_ERR_STATE, "render: not available on a handle with an RCCL communicator (hfpf_dist_disable drops it)");
+    if (h->dist_on) return fail(h, HFPF_ERR_STATE, "%s: not available on a handle with an RCCL communicator (hfpf_dist_disable drops it)", what);
     int rc = poison_on_error(h, flush_pending_locked(h));  // host frames still waiting for their launch
     if (!rc) rc = check_usable(h);
     if (!rc) rc = read_counters(h);
@@ -2190,8 +2195,14 @@ static int render_prelude_locked(hfpf_handle* h)
     return rc;
 }
 
-// The row set once, then per chunk of views: z-buffers to all ones, k_render_splat, k_render_resolve into the device planes.
-static int render_locked(hfpf_handle* h, const hfpf_render_opts* o, uint32_t n_views, const double* poses, const hfpf_render_planes& dev)
+// The views of a render (or the model view of a track): the row set, the z-buffer scratch of one chunk of views, the poses on the
+// device and the splat's parameters.
+struct RenderViews {
+    uint64_t n_rows;
+    uint32_t n_views, per_chunk;
+    RenderParams p;
+};
+static int render_views_locked(hfpf_handle* h, const hfpf_render_opts* o, uint32_t n_views, const double* poses, RenderViews* rv)
 {
     int rc;
     uint64_t nr = 0;
@@ -2203,7 +2214,8 @@ static int render_locked(hfpf_handle* h, const hfpf_render_opts* o, uint32_t n_v
     if ((rc = scratch(h, h->zbuf, per_chunk * WH * 8))) return rc;
     if ((rc = scratch(h, h->render_pose, (size_t)n_views * 12 * sizeof(double)))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->render_pose.p, poses, (size_t)n_views * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    RenderParams p{};
+    RenderParams& p = rv->p;
+    p = RenderParams{};
     p.width = o->width;
     p.height = o->height;
     p.cull = (o->flags & HFPF_RENDER_CULL_BACKFACES) ? 1u : 0u;
@@ -2212,17 +2224,42 @@ static int render_locked(hfpf_handle* h, const hfpf_render_opts* o, uint32_t n_v
     p.max_radius = o->max_splat_radius;
     p.fx = o->fx, p.fy = o->fy, p.cx = o->cx, p.cy = o->cy, p.z_near = o->z_near, p.z_far = o->z_far;
     p.r_num = (0.5 * h->g.res) * std::max(o->fx, o->fy);
+    rv->n_rows = nr;
+    rv->n_views = n_views;
+    rv->per_chunk = per_chunk;
+    return HFPF_OK;
+}
+
+// The z-buffers of the chunk of views starting at v0, left in h->zbuf: all ones, then k_render_splat.  Sets rv->p.n_views.
+static int render_splat_locked(hfpf_handle* h, RenderViews* rv, uint32_t v0)
+{
+    RenderParams& p = rv->p;
+    p.n_views = std::min(rv->per_chunk, rv->n_views - v0);
+    const uint64_t pix = p.n_views * (uint64_t)p.width * p.height;
+    const double* pose_d = (const double*)h->render_pose.p + 12ull * v0;
+    HIPCHK(h, hipMemsetAsync(h->zbuf.p, 0xFF, pix * 8, h->stream));
+    if (rv->n_rows)
+        hipLaunchKernelGGL(k_render_splat, dim3(blocks_for(rv->n_rows, 256)), dim3(256), 0, h->stream, (const Row*)h->rows_dev.p, (uint32_t)rv->n_rows,
+                           pose_d, p, (unsigned long long*)h->zbuf.p);
+    HIPCHK(h, hipGetLastError());
+    return HFPF_OK;
+}
+
+// The row set once, then per chunk of views: the z-buffers (render_splat_locked), k_render_resolve into the device planes.
+static int render_locked(hfpf_handle* h, const hfpf_render_opts* o, uint32_t n_views, const double* poses, const hfpf_render_planes& dev)
+{
+    RenderViews rv;
+    if (int rc = render_views_locked(h, o, n_views, poses, &rv)) return rc;
+    const uint64_t WH = (uint64_t)o->width * o->height;
     const Row* rows = (const Row*)h->rows_dev.p;
-    unsigned long long* zb = (unsigned long long*)h->zbuf.p;
-    for (uint32_t v0 = 0; v0 < n_views; v0 += per_chunk) {
-        p.n_views = std::min(per_chunk, n_views - v0);
+    for (uint32_t v0 = 0; v0 < n_views; v0 += rv.per_chunk) {
+        if (int rc = render_splat_locked(h, &rv, v0)) return rc;
+        const RenderParams& p = rv.p;
         const uint64_t pix = p.n_views * WH, off = v0 * WH;
         const double* pose_d = (const double*)h->render_pose.p + 12ull * v0;
-        HIPCHK(h, hipMemsetAsync(zb, 0xFF, pix * 8, h->stream));
-        if (nr) hipLaunchKernelGGL(k_render_splat, dim3(blocks_for(nr, 256)), dim3(256), 0, h->stream, rows, (uint32_t)nr, pose_d, p, zb);
         const RenderPlanes pl{dev.depth ? dev.depth + off : nullptr, dev.normal ? dev.normal + 3 * off : nullptr, dev.rgb ? dev.rgb + off : nullptr,
                               dev.count ? dev.count + off : nullptr, dev.voxel ? dev.voxel + 3 * off : nullptr};
-        hipLaunchKernelGGL(k_render_resolve, dim3(blocks_for(pix, 256)), dim3(256), 0, h->stream, rows, (const unsigned long long*)zb, pose_d, p, pl);
+        hipLaunchKernelGGL(k_render_resolve, dim3(blocks_for(pix, 256)), dim3(256), 0, h->stream, rows, (const unsigned long long*)h->zbuf.p, pose_d, p, pl);
         HIPCHK(h, hipGetLastError());
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2266,6 +2303,263 @@ int hfpf_render(hfpf_handle* h, const hfpf_render_opts* o, const double pose_3x4
         if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "render copy: %s", hipGetErrorString(e));
     }
     return HFPF_OK;
+}
+
+// ---- pose tracking (include/hfpf.h) -------------------------------------------------------------------------------------
+static bool track_opts_ok(const hfpf_track_opts* o)
+{
+    if (!o || o->struct_size != sizeof(hfpf_track_opts) || o->reserved != 0) return false;
+    if (o->max_iterations < 1 || o->max_iterations > 64 || o->stride < 1 || o->stride > 16 || o->min_inliers < 6) return false;
+    if (!(o->max_distance > 0.0 && o->max_distance <= 1.0)) return false;
+    if (!(std::isfinite(o->damping) && o->damping >= 0.0)) return false;
+    if (!(std::isfinite(o->eps_rotation) && o->eps_rotation >= 0.0 && std::isfinite(o->eps_translation) && o->eps_translation >= 0.0)) return false;
+    return view_opts_ok(&o->view);
+}
+
+static bool track_args_ok(const double* pose, const hfpf_track_result* res)
+{
+    if (!pose || !res || res->struct_size != sizeof(hfpf_track_result)) return false;
+    for (int k = 0; k < 12; k++)
+        if (!std::isfinite(pose[k])) return false;
+    return true;
+}
+
+// Pageable host -> device copy, complete on return: chunks through the two pinned 16 MB buffers (the mirror of download_pageable),
+// or the runtime's own staging when they are missing.
+static hipError_t upload_pageable(hfpf_handle* h, void* dev, const void* host, size_t total)
+{
+    hipError_t e = hipSuccess;
+    if (!h->xfer_pin[0]) {
+        e = hipMemcpyAsync(dev, host, total, hipMemcpyHostToDevice, h->stream);
+        return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
+    }
+    const size_t n_chunks = (total + kXferChunk - 1) / kXferChunk;
+    for (size_t i = 0; i < n_chunks && e == hipSuccess; i++) {
+        const size_t off = i * kXferChunk, len = std::min(kXferChunk, total - off);
+        if (i >= 2) e = hipEventSynchronize(h->xfer_ev[i & 1]);  // the copy out of this buffer two chunks ago
+        if (e != hipSuccess) break;
+        host_copy(h, h->xfer_pin[i & 1], (const char*)host + off, len);
+        e = hipMemcpyAsync((char*)dev + off, h->xfer_pin[i & 1], len, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipEventRecord(h->xfer_ev[i & 1], h->stream);
+    }
+    return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
+}
+
+// The frame of a track: a depth image (ds) or a cloud (lay, n_points), in host memory (copied to h->track_in) or on the device.
+struct TrackFrame {
+    const void* host;
+    const void* dev;
+    bool depth;
+    DepthSpec ds;
+    FrameLayout lay;
+    uint32_t n_points;
+    uint32_t cols;        // depth: sampled columns
+    uint64_t n_samples;   // sampled points
+    size_t bytes() const { return depth ? ds.depth_bytes() : (size_t)(n_points - 1) * lay.point_step + std::max({lay.off_x, lay.off_y, lay.off_z}) + 4; }
+};
+
+// The sampling of include/hfpf.h; false when more than 2^26 points would be sampled (the headroom of the int64 sums).
+static bool track_sample(TrackFrame& f, uint32_t stride)
+{
+    if (f.depth) {
+        f.cols = (f.ds.width + stride - 1) / stride;
+        f.n_samples = (uint64_t)f.cols * ((f.ds.height + stride - 1) / stride);
+    } else {
+        f.cols = 0;
+        f.n_samples = ((uint64_t)f.n_points + stride - 1) / stride;
+    }
+    return f.n_samples <= (1ull << 26);
+}
+
+// (A + damping I) x = -b by Cholesky L L^T, column j outer, then the two triangular solves: the order include/hfpf.h states.
+// false when a pivot is not > 0.
+static bool track_solve(const double A[6][6], const double b[6], double damping, double x[6])
+{
+    double L[6][6] = {};
+    for (int j = 0; j < 6; j++) {
+        double s = A[j][j] + damping;
+        for (int k = 0; k < j; k++) s = s - L[j][k] * L[j][k];
+        if (!(s > 0.0)) return false;
+        L[j][j] = std::sqrt(s);
+        for (int i = j + 1; i < 6; i++) {
+            double t = A[i][j];
+            for (int k = 0; k < j; k++) t = t - L[i][k] * L[j][k];
+            L[i][j] = t / L[j][j];
+        }
+    }
+    double y[6];
+    for (int i = 0; i < 6; i++) {
+        double s = -b[i];
+        for (int k = 0; k < i; k++) s = s - L[i][k] * y[k];
+        y[i] = s / L[i][i];
+    }
+    for (int i = 5; i >= 0; i--) {
+        double s = y[i];
+        for (int k = i + 1; k < 6; k++) s = s - L[k][i] * x[k];
+        x[i] = s / L[i][i];
+    }
+    return true;
+}
+
+// T <- (R(omega) R, (c + R(omega) (t - c)) + tau), R(omega) the Cayley map of include/hfpf.h.
+static void track_update(double T[12], const double xi[6], const double c[3])
+{
+    const double wx = 0.5 * xi[0], wy = 0.5 * xi[1], wz = 0.5 * xi[2];
+    const double ww = (wx * wx + wy * wy) + wz * wz;
+    const double f = 2.0 / (1.0 + ww);
+    const double W[3][3] = {{0.0, -wz, wy}, {wz, 0.0, -wx}, {-wy, wx, 0.0}};
+    double R[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            const double w2 = (W[i][0] * W[0][j] + W[i][1] * W[1][j]) + W[i][2] * W[2][j];
+            R[i][j] = (i == j ? 1.0 : 0.0) + f * (W[i][j] + w2);
+        }
+    const double e[3] = {T[3] - c[0], T[7] - c[1], T[11] - c[2]};
+    double out[12];
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) out[4 * i + j] = (R[i][0] * T[j] + R[i][1] * T[4 + j]) + R[i][2] * T[8 + j];
+        out[4 * i + 3] = (c[i] + ((R[i][0] * e[0] + R[i][1] * e[1]) + R[i][2] * e[2])) + xi[3 + i];
+    }
+    memcpy(T, out, sizeof out);
+}
+
+// Validated arguments in, under the lock: the model view once, then per iteration one k_track_reduce and the host solve.
+static int track_locked(hfpf_handle* h, const hfpf_track_opts* o, TrackFrame& f, const double pose[12], hfpf_track_result* res)
+{
+    int rc;
+    if ((rc = render_prelude_locked(h, "track"))) return rc;
+    const uint8_t* frame = (const uint8_t*)f.dev;
+    if (f.host) {  // one copy per call, through the pinned buffers
+        if ((rc = scratch(h, h->track_in, f.bytes()))) return rc;
+        const hipError_t e = upload_pageable(h, h->track_in.p, f.host, f.bytes());
+        if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "track upload: %s", hipGetErrorString(e));
+        frame = (const uint8_t*)h->track_in.p;
+    }
+    RenderViews rv;
+    if ((rc = render_views_locked(h, &o->view, 1, pose, &rv))) return rc;
+    if ((rc = render_splat_locked(h, &rv, 0))) return rc;
+    if ((rc = scratch(h, h->track_acc, kTrackTerms * sizeof(unsigned long long)))) return rc;
+
+    TrackParams p{};
+    memcpy(p.T, pose, sizeof p.T);
+    memcpy(p.V, pose, sizeof p.V);
+    p.fx = o->view.fx, p.fy = o->view.fy, p.cx = o->view.cx, p.cy = o->view.cy, p.z_near = o->view.z_near, p.z_far = o->view.z_far;
+    p.max_d2 = o->max_distance * o->max_distance;
+    p.zc_lo = h->g.zc_lo, p.zc_hi = h->g.zc_hi;
+    p.width = o->view.width, p.height = o->view.height;
+    p.n_samples = (uint32_t)f.n_samples;
+    p.stride = o->stride;
+    p.cols = f.cols;
+    p.n_points = f.n_points;
+    const double c[3] = {pose[3], pose[7], pose[11]};
+    const bool packed = !f.depth && f.lay.point_step == 16 && f.lay.off_x == 0 && f.lay.off_y == 4 && f.lay.off_z == 8 && ((uintptr_t)frame & 15) == 0;
+    const DepthLayout dl = depth_layout(f.ds, nullptr, 0);
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(kTrackMaxBlocks, blocks_for(f.n_samples, 256));
+    const Row* rows = (const Row*)h->rows_dev.p;
+    const unsigned long long* zb = (const unsigned long long*)h->zbuf.p;
+    unsigned long long* acc = (unsigned long long*)h->track_acc.p;
+    unsigned long long local[kTrackTerms];
+    unsigned long long* back = h->xfer_pin[0] ? (unsigned long long*)h->xfer_pin[0] : local;  // the read-back of the sums
+
+    double T[12], A[6][6] = {}, rr = 0.0;
+    memcpy(T, pose, sizeof T);
+    uint64_t inliers = 0, used = 0;
+    uint32_t flags = 0, it = 0;
+    while (it < o->max_iterations) {
+        it++;
+        memcpy(p.T, T, sizeof p.T);
+        HIPCHK(h, hipMemsetAsync(acc, 0, kTrackTerms * sizeof(unsigned long long), h->stream));
+        if (f.depth)
+            hipLaunchKernelGGL((k_track_reduce<false, true>), dim3(blocks), dim3(256), 0, h->stream, p, frame, dl, rows, zb, acc);
+        else if (packed)
+            hipLaunchKernelGGL((k_track_reduce<true, false>), dim3(blocks), dim3(256), 0, h->stream, p, frame, f.lay, rows, zb, acc);
+        else
+            hipLaunchKernelGGL((k_track_reduce<false, false>), dim3(blocks), dim3(256), 0, h->stream, p, frame, f.lay, rows, zb, acc);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(back, acc, kTrackTerms * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        long long s[kTrackTerms];
+        memcpy(s, back, sizeof s);
+        for (int i = 0, k = 0; i < 6; i++)
+            for (int j = i; j < 6; j++, k++) A[i][j] = A[j][i] = (double)s[k] / kTrackScaleJJ;
+        double b[6];
+        for (int i = 0; i < 6; i++) b[i] = (double)s[21 + i] / kTrackScaleJR;
+        rr = (double)s[27] / kTrackScaleRR;
+        inliers = (uint64_t)s[28];
+        used = (uint64_t)s[29];
+        if (inliers < o->min_inliers) {
+            flags = HFPF_TRACK_TOO_FEW;
+            break;
+        }
+        double xi[6];
+        if (!track_solve(A, b, o->damping, xi)) {
+            flags = HFPF_TRACK_DEGENERATE;
+            break;
+        }
+        track_update(T, xi, c);
+        if ((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2] < o->eps_rotation * o->eps_rotation &&
+            (xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5] < o->eps_translation * o->eps_translation) {
+            flags = HFPF_TRACK_CONVERGED;
+            break;
+        }
+    }
+    res->iterations = it;
+    res->flags = flags;
+    res->reserved = 0;
+    res->points_used = used;
+    res->inliers = inliers;
+    res->rms = inliers ? std::sqrt(rr / (double)inliers) : 0.0;
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) res->information[6 * i + j] = A[i][j];
+    memcpy(res->pose, T, sizeof T);
+    return HFPF_OK;
+}
+
+static int track_depth_common(hfpf_handle* h, const hfpf_track_opts* o, const hfpf_depth_image* desc, const void* depth, bool on_device,
+                              const double pose[12], hfpf_track_result* res)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (!track_opts_ok(o) || !track_args_ok(pose, res)) return fail(h, HFPF_ERR_BAD_ARG, "track: invalid options, pose or result");
+    TrackFrame f{};
+    // the colour fields are validated as integrate validates them, but no colour image is read
+    if (int rc = depth_spec(h, desc, depth, desc && desc->color_format != HFPF_COLOR_NONE ? depth : nullptr, &f.ds)) return rc;
+    f.ds.color_bpp = 0;
+    f.depth = true;
+    f.n_points = f.ds.width * f.ds.height;
+    if (on_device && (uintptr_t)depth % (f.ds.depth_f32 ? 4u : 2u)) return fail(h, HFPF_ERR_BAD_ARG, "track_depth_device: the image must be aligned to the sample size");
+    if (!track_sample(f, o->stride)) return fail(h, HFPF_ERR_BAD_ARG, "track: more than 2^26 sampled points");
+    (on_device ? f.dev : f.host) = depth;
+    return track_locked(h, o, f, pose, res);
+}
+
+int hfpf_track_depth(hfpf_handle* h, const hfpf_track_opts* o, const hfpf_depth_image* desc, const void* depth, const double pose_3x4[12],
+                     hfpf_track_result* result)
+{
+    return track_depth_common(h, o, desc, depth, false, pose_3x4, result);
+}
+
+int hfpf_track_depth_device(hfpf_handle* h, const hfpf_track_opts* o, const hfpf_depth_image* desc, const void* dev_depth, const double pose_3x4[12],
+                            hfpf_track_result* result)
+{
+    return track_depth_common(h, o, desc, dev_depth, true, pose_3x4, result);
+}
+
+int hfpf_track(hfpf_handle* h, const hfpf_track_opts* o, const void* base, uint32_t n_points, uint32_t point_step, uint32_t off_x, uint32_t off_y,
+               uint32_t off_z, const double pose_3x4[12], hfpf_track_result* result)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (!track_opts_ok(o) || !track_args_ok(pose_3x4, result)) return fail(h, HFPF_ERR_BAD_ARG, "track: invalid options, pose or result");
+    if (!base || n_points == 0) return fail(h, HFPF_ERR_BAD_ARG, "track: null cloud or no points");
+    if ((point_step & 3) || (off_x & 3) || (off_y & 3) || (off_z & 3)) return fail(h, HFPF_ERR_BAD_ARG, "track: fields must be 4-byte aligned");
+    if (std::max({off_x, off_y, off_z}) + 4 > point_step) return fail(h, HFPF_ERR_BAD_ARG, "track: field offset beyond point_step");
+    TrackFrame f{};
+    f.host = base;
+    f.lay = FrameLayout{point_step, off_x, off_y, off_z, 0};
+    f.n_points = n_points;
+    if (!track_sample(f, o->stride)) return fail(h, HFPF_ERR_BAD_ARG, "track: more than 2^26 sampled points");
+    return track_locked(h, o, f, pose_3x4, result);
 }
 
 int hfpf_stats_export(hfpf_handle* h, const void** dev_words, uint64_t* n_words, const void** dev_cwords, uint64_t* n_cwords)

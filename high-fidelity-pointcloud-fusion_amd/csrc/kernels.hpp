@@ -2215,6 +2215,150 @@ __global__ __launch_bounds__(256) void k_render_resolve(const Row* __restrict__ 
 }
 
 
+// ---- pose tracking (hfpf_track*, include/hfpf.h) ------------------------------------------------------------------------
+// Frame-to-model point-to-plane ICP with projective association: one launch per iteration sums the 6x6 normal equations of every
+// sampled point at the estimate T_k, the host solves them.  The model view is a render z-buffer (k_render_splat) at the input
+// pose; a word's low 32 bits name the row whose centroid and normal a point is compared with.  Every term is quantised to an
+// int64 and the sums are exact, so the result does not depend on how the points are scheduled.
+constexpr int kTrackTerms = 30;        // 21 J_i J_j (i <= j, i outer), 6 J_i r, r r, inliers, points used
+constexpr double kTrackScaleJJ = 16777216.0;    // 2^24
+constexpr double kTrackScaleJR = 268435456.0;   // 2^28
+constexpr double kTrackScaleRR = 4294967296.0;  // 2^32
+constexpr double kTrackHeadroom = 32.0;         // metres: max(|a.x|, |a.y|, |a.z|) at or above it rejects the point
+constexpr uint32_t kTrackMaxBlocks = 2048;
+
+struct TrackParams {
+    double T[12];          // the estimate T_k, camera -> fusion frame
+    double V[12];          // the view pose (the input pose T0); c = (V[3], V[7], V[11])
+    double fx, fy, cx, cy, z_near, z_far;
+    double max_d2;         // max_distance * max_distance
+    float zc_lo, zc_hi;    // the handle's z-clip as float compares (GridParams)
+    uint32_t width, height;  // the view
+    uint32_t n_samples;    // sampled points
+    uint32_t stride;
+    uint32_t cols;         // depth: sampled columns, ceil(image width / stride)
+    uint32_t n_points;     // cloud: records in the frame
+};
+
+// 64-bit form of wave_inclusive_scan: the same DPP steps on both halves, a 64-bit add between them.  Lane 63 ends with the
+// wave's total (mod 2^64; the int64 sums never wrap).
+template <int CTRL, int ROW_MASK, bool BOUND_ZERO>
+__device__ __forceinline__ unsigned long long dpp_u64(unsigned long long x)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)x, CTRL, ROW_MASK, 0xF, BOUND_ZERO);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(x >> 32), CTRL, ROW_MASK, 0xF, BOUND_ZERO);
+    return (unsigned long long)hi << 32 | lo;
+}
+__device__ __forceinline__ unsigned long long wave_total_u64(unsigned long long x)
+{
+    x += dpp_u64<0x111, 0xF, true>(x);   // row_shr:1
+    x += dpp_u64<0x112, 0xF, true>(x);   // row_shr:2
+    x += dpp_u64<0x114, 0xF, true>(x);   // row_shr:4
+    x += dpp_u64<0x118, 0xF, true>(x);   // row_shr:8
+    x += dpp_u64<0x142, 0xA, false>(x);  // row_bcast:15 into rows 1 and 3
+    x += dpp_u64<0x143, 0xC, false>(x);  // row_bcast:31 into rows 2 and 3
+    return x;
+}
+
+__device__ __forceinline__ unsigned long long track_q(double v, double scale) { return (unsigned long long)(long long)rint(v * scale); }
+
+// The two poses as the loop body reads them: from the kernarg segment (TrackParams is k_track_reduce's FIRST argument), behind an
+// empty asm as kernarg_tables() does.  Taken from the by-value argument, the compiler keeps all 24 doubles in scalar registers for
+// the whole loop and spills some of them.
+__device__ __forceinline__ const TrackParams& track_kernarg()
+{
+    kernarg_ptr p = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const TrackParams*)p;
+}
+
+// One sampled point per thread, grid-stride over at most kTrackMaxBlocks blocks.  Input forms as k_integrate: PACKED16 (16-byte x,
+// y, z, rgb records), the generic FrameLayout loader, DEPTH (u16 or f32 depth image, sub-dword loads, back-projected in
+// registers).  Each thread keeps its 30 sums in registers; the block reduces them (DPP across the wave, LDS across the four
+// waves) and adds them to acc with one 64-bit atomic each.  acc is zeroed by the host before the launch.
+template <bool PACKED16, bool DEPTH>
+__global__ __launch_bounds__(256) void k_track_reduce(const TrackParams p, const uint8_t* __restrict__ frame,
+                                                      const std::conditional_t<DEPTH, DepthLayout, FrameLayout> lay,
+                                                      const Row* __restrict__ rows, const unsigned long long* __restrict__ zbuf,
+                                                      unsigned long long* __restrict__ acc)
+{
+    __shared__ unsigned long long s_part[4][kTrackTerms];
+    unsigned long long sum[kTrackTerms];
+#pragma unroll
+    for (int k = 0; k < kTrackTerms; k++) sum[k] = 0;
+    for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < p.n_samples; s += gridDim.x * blockDim.x) {
+        float x, y, z;
+        if constexpr (DEPTH) {
+            const uint32_t sv = s / p.cols, su = s - sv * p.cols;
+            const uint32_t u = su * p.stride, v = sv * p.stride;
+            const vf4 r = depth_fetch<false>(frame, nullptr, lay, v * lay.width + u);
+            const F3 c = depth_backproject(u, v, __float_as_uint(r.x), lay.depth_f32 != 0, lay.cx, lay.cy, lay.sx, lay.sy, lay.unit);
+            x = c.x, y = c.y, z = c.z;
+        } else if constexpr (PACKED16) {
+            const vf4 r = reinterpret_cast<const vf4*>(frame)[(uint64_t)s * p.stride];
+            x = r.x, y = r.y, z = r.z;
+        } else {
+            const uint8_t* rec = frame + (uint64_t)s * p.stride * lay.point_step;
+            x = *reinterpret_cast<const float*>(rec + lay.off_x);
+            y = *reinterpret_cast<const float*>(rec + lay.off_y);
+            z = *reinterpret_cast<const float*>(rec + lay.off_z);
+        }
+        if (!(__builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z) && z < p.zc_hi && z > p.zc_lo)) continue;
+        sum[29] += 1;
+        const TrackParams& P = track_kernarg();
+        const double* T = P.T;
+        const double* V = P.V;
+        const double px = x, py = y, pz = z;
+        const double wx = ((T[0] * px + T[1] * py) + T[2] * pz) + T[3];
+        const double wy = ((T[4] * px + T[5] * py) + T[6] * pz) + T[7];
+        const double wz = ((T[8] * px + T[9] * py) + T[10] * pz) + T[11];
+        // a = pw - c: also the offset the view's projection starts from
+        const double ax = wx - V[3], ay = wy - V[7], az = wz - V[11];
+        const double zc = (V[2] * ax + V[6] * ay) + V[10] * az;
+        if (!(p.z_near < zc && zc < p.z_far)) continue;
+        const double xc = (V[0] * ax + V[4] * ay) + V[8] * az;
+        const double yc = (V[1] * ax + V[5] * ay) + V[9] * az;
+        const double u = (xc / zc) * p.fx + p.cx;
+        const double w = (yc / zc) * p.fy + p.cy;
+        if (!(fabs(u) < 1073741824.0 && fabs(w) < 1073741824.0)) continue;
+        const int pu = (int)floor(u + 0.5), pv = (int)floor(w + 0.5);
+        if (pu < 0 || pv < 0 || pu >= (int)p.width || pv >= (int)p.height) continue;
+        const unsigned long long word = zbuf[(uint64_t)pv * p.width + (uint64_t)pu];
+        if (word == kRenderEmpty) continue;
+        const Row* row = rows + (uint32_t)word;
+        const float4 q0 = *reinterpret_cast<const float4*>(&row->x);   // x, y, z, nx
+        const float2 q1 = *reinterpret_cast<const float2*>(&row->ny);  // ny, nz
+        const double dx = wx - (double)q0.x, dy = wy - (double)q0.y, dz = wz - (double)q0.z;
+        const double nx = q0.w, ny = q1.x, nz = q1.y;
+        if (!(((dx * dx + dy * dy) + dz * dz) <= p.max_d2)) continue;
+        if (!(((nx * nx + ny * ny) + nz * nz) <= 2.0)) continue;
+        if (!(fmax(fmax(fabs(ax), fabs(ay)), fabs(az)) < kTrackHeadroom)) continue;
+        const double r = (nx * dx + ny * dy) + nz * dz;
+        const double J[6] = {ay * nz - az * ny, az * nx - ax * nz, ax * ny - ay * nx, nx, ny, nz};
+        int k = 0;
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+#pragma unroll
+            for (int j = i; j < 6; j++) sum[k++] += track_q(J[i] * J[j], kTrackScaleJJ);
+#pragma unroll
+        for (int i = 0; i < 6; i++) sum[21 + i] += track_q(J[i] * r, kTrackScaleJR);
+        sum[27] += track_q(r * r, kTrackScaleRR);
+        sum[28] += 1;
+    }
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < kTrackTerms; k++) {
+        const unsigned long long t = wave_total_u64(sum[k]);
+        if (lane == 63) s_part[wave][k] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < kTrackTerms) {
+        const unsigned long long t = (s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + (s_part[2][threadIdx.x] + s_part[3][threadIdx.x]);
+        if (t) atomicAdd(&acc[threadIdx.x], t);
+    }
+}
+
+
 // ---- multi-GPU epoch exchange ----------------------------------------------------------
 // Frames shard across ranks; what must be agreed before a clean pass is the occupancy set and, per cell, the
 // smallest frame id that touched it (the viewpoint latch).  Each rank exports the cells IT occupied since

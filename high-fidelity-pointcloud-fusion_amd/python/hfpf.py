@@ -89,6 +89,7 @@ EXPORTS = [
     "hfpf_extract_with_stats", "hfpf_device_download", "hfpf_device_copy", "hfpf_epoch_import_gathered",
     "hfpf_integrate_depth", "hfpf_integrate_depth_pinned", "hfpf_integrate_depth_device", "hfpf_probe_depth",
     "hfpf_render", "hfpf_render_device",
+    "hfpf_track_depth", "hfpf_track_depth_device", "hfpf_track",
 ]
 
 # hfpf_depth_image formats (include/hfpf.h)
@@ -167,6 +168,48 @@ def render_opts(K, width, height, z_range=(0.01, 100.0), min_count=0.0, splat_ra
     return o
 
 
+# hfpf_track_result.flags (include/hfpf.h)
+TRACK_CONVERGED, TRACK_DEGENERATE, TRACK_TOO_FEW = 1, 2, 4
+
+
+class TrackOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_iterations", C.c_uint32), ("stride", C.c_uint32), ("min_inliers", C.c_uint32),
+                ("view", RenderOpts), ("max_distance", C.c_double), ("damping", C.c_double), ("eps_rotation", C.c_double),
+                ("eps_translation", C.c_double), ("reserved", C.c_uint64)]
+
+
+class TrackResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("points_used", C.c_uint64), ("inliers", C.c_uint64), ("rms", C.c_double), ("information", C.c_double * 36),
+                ("pose", C.c_double * 12)]
+
+
+def track_opts(K, width, height, max_iterations=10, stride=1, min_inliers=6, max_distance=0.02, damping=1e-6, eps_rotation=1e-6,
+               eps_translation=1e-6, z_range=(0.01, 100.0), min_count=0.0, splat_radius=-1, max_splat_radius=4, cull_backfaces=True):
+    """An hfpf_track_opts; the view is a render_opts of (K, width, height) with the view keywords."""
+    o = TrackOpts()
+    o.struct_size = C.sizeof(TrackOpts)
+    o.max_iterations, o.stride, o.min_inliers = int(max_iterations), int(stride), int(min_inliers)
+    o.view = render_opts(K, width, height, z_range=z_range, min_count=min_count, splat_radius=splat_radius,
+                         max_splat_radius=max_splat_radius, cull_backfaces=cull_backfaces)
+    o.max_distance, o.damping = float(max_distance), float(damping)
+    o.eps_rotation, o.eps_translation = float(eps_rotation), float(eps_translation)
+    return o
+
+
+def track_result():
+    r = TrackResult()
+    r.struct_size = C.sizeof(TrackResult)
+    return r
+
+
+def _track_out(r):
+    """(3x4 pose, result dict) of an hfpf_track_result."""
+    pose = np.array(r.pose[:], np.float64).reshape(3, 4)
+    return pose, {"iterations": r.iterations, "flags": r.flags, "points_used": r.points_used, "inliers": r.inliers, "rms": r.rms,
+                  "information": np.array(r.information[:], np.float64).reshape(6, 6), "pose": pose}
+
+
 EPOCH_REC_DTYPE = np.dtype([("key", "<u8"), ("first_frame", "<u4"), ("vx", "<f4"), ("vy", "<f4"), ("vz", "<f4"), ("pad", "<u4", (2,))])
 assert EPOCH_REC_DTYPE.itemsize == 32
 
@@ -242,6 +285,9 @@ def lib():
     L.hfpf_probe_depth.argtypes = [vp, C.POINTER(DepthImage), vp, vp, vp, vp]
     L.hfpf_render.argtypes = [vp, C.POINTER(RenderOpts), vp, C.POINTER(RenderPlanes)]
     L.hfpf_render_device.argtypes = [vp, C.POINTER(RenderOpts), u32, vp, C.POINTER(RenderPlanes)]
+    L.hfpf_track_depth.argtypes = [vp, C.POINTER(TrackOpts), C.POINTER(DepthImage), vp, vp, C.POINTER(TrackResult)]
+    L.hfpf_track_depth_device.argtypes = [vp, C.POINTER(TrackOpts), C.POINTER(DepthImage), vp, vp, C.POINTER(TrackResult)]
+    L.hfpf_track.argtypes = [vp, C.POINTER(TrackOpts), vp, u32, u32, u32, u32, u32, vp, C.POINTER(TrackResult)]
     _lib = L
     return L
 
@@ -461,6 +507,39 @@ class OccupancyGrid:
                 raise ValueError("unknown render plane %r" % name)
             setattr(pl, name, ptr)
         self._chk(lib().hfpf_render_device(self._h, C.byref(o), poses.shape[0], _p(poses), C.byref(pl)))
+
+    # -- correcting a frame's pose against the model --
+    def track_depth(self, depth, pose, K, depth_scale=0.001, opts=None, **kw):
+        """Refine the camera -> fusion pose of one depth image in pageable memory (hfpf_track_depth).  The model view defaults to the
+        image's own intrinsics and size with back faces culled; keywords as track_opts.  Returns (3x4 pose, result dict)."""
+        d = _image_desc(depth, K, None, None, depth_scale)
+        o = opts if opts is not None else track_opts(K, depth.shape[1], depth.shape[0], **kw)
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        r = track_result()
+        self._chk(lib().hfpf_track_depth(self._h, C.byref(o), C.byref(d), C.c_void_p(depth.ctypes.data), _p(pose), C.byref(r)))
+        return _track_out(r)
+
+    def track_depth_device(self, desc, dev_depth, pose, opts=None, **kw):
+        """The same for a depth image resident in HBM (hfpf_track_depth_device); desc from depth_desc()."""
+        o = opts if opts is not None else track_opts((desc.fx, desc.fy, desc.cx, desc.cy), desc.width, desc.height, **kw)
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        r = track_result()
+        self._chk(lib().hfpf_track_depth_device(self._h, C.byref(o), C.byref(desc), C.c_void_p(dev_depth), _p(pose), C.byref(r)))
+        return _track_out(r)
+
+    def track(self, cloud, layout, pose, view_K, width, height, n_points=None, opts=None, **kw):
+        """Refine the pose of one cloud of records in pageable memory (hfpf_track); layout = dict(point_step, off_x, off_y, off_z)
+        (extra keys such as off_rgb are ignored); the model view is (view_K, width, height)."""
+        cloud = np.ascontiguousarray(cloud)
+        step = layout["point_step"]
+        if n_points is None:
+            n_points = cloud.nbytes // step
+        o = opts if opts is not None else track_opts(view_K, width, height, **kw)
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        r = track_result()
+        self._chk(lib().hfpf_track(self._h, C.byref(o), _p(cloud), n_points, step, layout["off_x"], layout["off_y"], layout["off_z"],
+                                   _p(pose), C.byref(r)))
+        return _track_out(r)
 
     # -- multi-GPU --
     def dist_init_rccl(self, rank, world, unique_id):

@@ -306,6 +306,91 @@ int hfpf_render(hfpf_handle* h, const hfpf_render_opts* o, const double pose_3x4
  * (times 3 for normal and voxel) behind the plane's base.  The row set is built once for all views.  n_views = 0 does nothing. */
 int hfpf_render_device(hfpf_handle* h, const hfpf_render_opts* o, uint32_t n_views, const double* poses, const hfpf_render_planes* dev_out);
 
+/* ---- refining a frame's pose against the fused model (frame-to-model point-to-plane ICP; no reference counterpart) -----------
+ * A track takes one frame (a depth image or a cloud) and a pose guess T0 (row-major [R|t], camera -> fusion frame, the integrate
+ * convention) and returns a refined pose in the same convention; the caller then integrates the frame at that pose.  Let
+ * c = (T0[3], T0[7], T0[11]), the input camera centre.  All host and device arithmetic is f64 unless stated, one rounding per
+ * operation, left to right, never contracted.
+ * Model view: the z-buffer hfpf_render would build with opts.view at T0 -- the same row set (host frames still waiting are
+ *   launched first), splat and tie rule; no plane is produced.  Its word bits(depth32) << 32 | j names row j of that row set.
+ * Sampling: depth pixel (u, v) iff u % stride == 0 and v % stride == 0, back-projected by the f32 arithmetic of the depth-frame
+ *   contract above; cloud point i iff i % stride == 0, its f32 x, y, z.  A sampled point p is USED iff x, y, z are finite and
+ *   z_clip_min < z < z_clip_max (the handle's z-clip, as integrate applies it).  At most 2^26 points may be sampled.
+ * Per iteration k = 1, 2, ... with estimate T = T_{k-1}, for every used point p:
+ *   pw = (((T[0]*px + T[1]*py) + T[2]*pz) + T[3], ((T[4]*px + ...) + T[7], ((T[8]*px + ...) + T[11])   (p widened, not rounded)
+ *   a = pw - c; projected into the view with the splat's arithmetic at T0 (dx, dy, dz = a): kept iff z_near < zc < z_far,
+ *   |u|, |v| < 2^30, (pu, pv) = (floor(u + 0.5), floor(v + 0.5)) inside the image and its word not empty (no culling test).
+ *   q = (double)row j's x, y, z;  n = (double)row j's nx, ny, nz;  d = pw - q
+ *   kept iff (d.x*d.x + d.y*d.y) + d.z*d.z <= max_distance * max_distance, (n.x*n.x + n.y*n.y) + n.z*n.z <= 2 and
+ *   max(|a.x|, |a.y|, |a.z|) < 32 (metres: the headroom rule below)
+ *   r = (n.x*d.x + n.y*d.y) + n.z*d.z
+ *   J = (a.y*n.z - a.z*n.y, a.z*n.x - a.x*n.z, a.x*n.y - a.y*n.x, n.x, n.y, n.z)      (twist order omega, tau)
+ *   each kept point (an INLIER) adds (int64) rint(v * s) for v = J_i*J_j (i <= j; s = 2^24), J_i*r (s = 2^28) and r*r (s = 2^32)
+ *   into exact int64 sums, so the sums do not depend on scheduling.  Headroom: |J_i| < 64, |r| < 2, and 2^26 points keep every
+ *   sum below 2^62.
+ * On the host: A = J^T J (sums / 2^24, symmetric), b = J^T r (sums / 2^28), rr = sum / 2^32, all from the int64 sums.
+ *   inliers < min_inliers: HFPF_TRACK_TOO_FEW, stop.
+ *   Cholesky of M = A + damping*I (damping added to the diagonal), j = 0..5:  s = M[j][j] - L[j][0]^2 - ... - L[j][j-1]^2 (each
+ *   subtracted in turn); s > 0 or HFPF_TRACK_DEGENERATE and stop; L[j][j] = sqrt(s); for i = j+1..5: L[i][j] = (M[i][j] -
+ *   L[i][0]*L[j][0] - ... - L[i][j-1]*L[j][j-1]) / L[j][j].  Then y_i = (-b_i - L[i][0]*y_0 - ... - L[i][i-1]*y_{i-1}) / L[i][i]
+ *   for i = 0..5 and xi_i = (y_i - L[i+1][i]*xi_{i+1} - ... - L[5][i]*xi_5) / L[i][i] for i = 5..0.
+ *   xi = (omega, tau); w = 0.5*omega; f = 2 / (1 + ((w.x*w.x + w.y*w.y) + w.z*w.z)); W = [w]x = {{0, -w.z, w.y}, {w.z, 0, -w.x},
+ *   {-w.y, w.x, 0}}; R(omega)[i][j] = I[i][j] + f * (W[i][j] + ((W[i][0]*W[0][j] + W[i][1]*W[1][j]) + W[i][2]*W[2][j])) (Cayley).
+ *   R_k[i][j] = (Rw[i][0]*R[0][j] + Rw[i][1]*R[1][j]) + Rw[i][2]*R[2][j];  t_k[i] = (c[i] + ((Rw[i][0]*e0 + Rw[i][1]*e1) +
+ *   Rw[i][2]*e2)) + tau[i], e = t - c.
+ *   HFPF_TRACK_CONVERGED and stop when (omega.x^2 + omega.y^2) + omega.z^2 < eps_rotation^2 and likewise tau against
+ *   eps_translation (the update is applied first); otherwise stop after max_iterations.
+ * The result: pose = the last estimate (T0 when the first system was TOO_FEW or DEGENERATE), iterations = systems evaluated;
+ * inliers, rms = sqrt(rr / inliers) (0 without inliers) and information = A describe the last system evaluated.  points_used
+ * counts the used points (the same in every iteration).  HFPF_OK is returned whenever the arguments are valid, also for
+ * TOO_FEW, DEGENERATE, an empty handle and a handle before its first clean pass.  A track changes nothing on the handle except
+ * device_bytes (its scratch: a host frame's copy, the view's z-buffer, 240 bytes of sums).  Rejected with HFPF_ERR_BAD_ARG (the
+ * handle stays usable, the result is not written): struct_size != sizeof (options or result), reserved != 0, max_iterations
+ * outside 1..64, stride outside 1..16, min_inliers < 6, not 0 < max_distance <= 1, damping not finite and >= 0, eps_rotation or
+ * eps_translation not finite and >= 0, an invalid view (the checks of hfpf_render_opts), a NULL or non-finite pose, a NULL
+ * result, more than 2^26 sampled points; for depth images every check of hfpf_depth_image (colour fields included; no colour
+ * image is read) and, on the device, an image not aligned to its sample size; for clouds a NULL buffer, n_points = 0, offsets or
+ * point_step not multiples of 4, an offset + 4 beyond point_step.  A handle with an RCCL communicator returns HFPF_ERR_STATE,
+ * as render does.  Every call returns when the result is complete. */
+#define HFPF_TRACK_CONVERGED 1u  /* the last update was below both eps */
+#define HFPF_TRACK_DEGENERATE 2u /* a pivot of the damped system was <= 0; pose = the last good estimate */
+#define HFPF_TRACK_TOO_FEW 4u    /* fewer than min_inliers inliers; pose = the last good estimate */
+
+typedef struct hfpf_track_opts {
+    uint32_t struct_size;    /* = sizeof(hfpf_track_opts) */
+    uint32_t max_iterations; /* 1..64 */
+    uint32_t stride;         /* 1..16: the sampling above */
+    uint32_t min_inliers;    /* >= 6 */
+    hfpf_render_opts view;   /* the model view, rendered once at the input pose (HFPF_RENDER_WORLD_NORMALS has no effect) */
+    double max_distance;     /* association gate in metres, 0 < max_distance <= 1 */
+    double damping;          /* >= 0, added to the diagonal of the 6x6 system */
+    double eps_rotation;     /* radians */
+    double eps_translation;  /* metres */
+    uint64_t reserved;       /* 0 */
+} hfpf_track_opts;
+
+typedef struct hfpf_track_result {
+    uint32_t struct_size;    /* = sizeof(hfpf_track_result), set by the caller */
+    uint32_t iterations;
+    uint32_t flags;          /* HFPF_TRACK_* */
+    uint32_t reserved;
+    uint64_t points_used;    /* sampled points that are finite and pass the z-clip */
+    uint64_t inliers;        /* of the last system evaluated */
+    double rms;              /* sqrt(rr / inliers) of that system */
+    double information[36];  /* its undamped J^T J, row-major, twist order (omega, tau) about the input camera centre */
+    double pose[12];         /* refined pose, row-major [R|t], camera -> fusion frame */
+} hfpf_track_result;
+
+/* A depth image in pageable HOST memory (copied once per call through pinned staging). */
+int hfpf_track_depth(hfpf_handle* h, const hfpf_track_opts* o, const hfpf_depth_image* desc, const void* depth, const double pose_3x4[12],
+                     hfpf_track_result* result);
+/* A depth image in DEVICE memory, read in place. */
+int hfpf_track_depth_device(hfpf_handle* h, const hfpf_track_opts* o, const hfpf_depth_image* desc, const void* dev_depth,
+                            const double pose_3x4[12], hfpf_track_result* result);
+/* A cloud of n_points records of point_step bytes in pageable HOST memory, f32 x, y, z at the given byte offsets (as integrate). */
+int hfpf_track(hfpf_handle* h, const hfpf_track_opts* o, const void* base, uint32_t n_points, uint32_t point_step, uint32_t off_x,
+               uint32_t off_y, uint32_t off_z, const double pose_3x4[12], hfpf_track_result* result);
+
 /* <directory_name>/test_cloud.pcd (node.cpp:395): PCD v0.7 ASCII, FIELDS x y z rgb normal_x normal_y normal_z curvature */
 int hfpf_write_pcd(const hfpf_row* rows, uint64_t n_rows, const char* path);
 /* <directory_name>/meta.csv (node.cpp:396) with the header string of grid.hpp:462 */
