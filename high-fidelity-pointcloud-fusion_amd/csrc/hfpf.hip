@@ -264,6 +264,7 @@ struct hfpf_handle {
     DevBuf sort_tmp, keys_a, keys_b, vals_a, vals_b, rows_dev, probe_a, probe_b, probe_c, probe_d, probe_e, probe_f;
     DevBuf zbuf, render_pose, render_out;  // hfpf_render*: z-buffers of one chunk of views, the views' poses, hfpf_render's device planes
     DevBuf track_in, track_acc;            // hfpf_track*: a host frame's device copy, the 30 int64 sums of one iteration
+    DevBuf query_in, query_out;            // hfpf_query*: a host cloud chunk or depth image, one chunk's hits and rows
     unsigned long long* h_ctr = nullptr;  // pinned mirror of the counters
     unsigned long long* mbox = nullptr;   // coherent pinned mailbox k_publish_counters writes (HFPF_MAILBOX=0: blit copies + synchronize)
     unsigned long long mbox_seq = 0;
@@ -1600,7 +1601,8 @@ int hfpf_destroy(hfpf_handle* h)
     (void)hipStreamSynchronize(h->stream);
     for (void* p : h->allocs) (void)hipFree(p);
     for (DevBuf* b : {&h->sort_tmp, &h->keys_a, &h->keys_b, &h->vals_a, &h->vals_b, &h->rows_dev, &h->probe_a, &h->probe_b, &h->probe_c, &h->probe_d,
-                      &h->probe_e, &h->probe_f, &h->zbuf, &h->render_pose, &h->render_out, &h->track_in, &h->track_acc})
+                      &h->probe_e, &h->probe_f, &h->zbuf, &h->render_pose, &h->render_out, &h->track_in, &h->track_acc,
+                      &h->query_in, &h->query_out})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf* b : {&h->ex_send, &h->ex_recv, &h->ex_counts, &h->stats_total, &h->bin_pt_buf, &h->bin_rgb_buf, &h->bin_sums, &h->ovf_pt_buf, &h->ovf_aux_buf, &h->pend_a, &h->pend_b})
         if (b->p) (void)hipFree(b->p);
@@ -2560,6 +2562,140 @@ int hfpf_track(hfpf_handle* h, const hfpf_track_opts* o, const void* base, uint3
     f.n_points = n_points;
     if (!track_sample(f, o->stride)) return fail(h, HFPF_ERR_BAD_ARG, "track: more than 2^26 sampled points");
     return track_locked(h, o, f, pose_3x4, result);
+}
+
+// ---- point queries (include/hfpf.h) ---------------------------------------------------------------------------------------
+constexpr uint32_t kQueryChunk = 1u << 20;  // points per launch of the host forms: 64 MB of hits + 64 MB of rows of scratch
+
+static bool query_args_ok(const hfpf_query_opts* o, const double* pose)
+{
+    if (!o || o->struct_size != sizeof(hfpf_query_opts) || o->reserved0 != 0 || o->reserved != 0) return false;
+    if ((o->flags & ~HFPF_QUERY_ZCLIP) || o->radius < 0 || o->radius > kQueryMaxRadius) return false;
+    if (std::isnan(o->min_count) || !(o->max_distance > 0.0)) return false;
+    if (!pose) return false;
+    for (int k = 0; k < 12; k++)
+        if (!std::isfinite(pose[k])) return false;
+    return true;
+}
+
+// The points of a query: a depth image (ds) or a cloud (lay, n), in host memory or on the device.
+struct QueryFrame {
+    const void* host;
+    const void* dev;
+    bool depth;
+    DepthSpec ds;
+    FrameLayout lay;
+    uint32_t n;
+    size_t cloud_bytes(uint32_t n_pts) const { return (size_t)(n_pts - 1) * lay.point_step + std::max({lay.off_x, lay.off_y, lay.off_z}) + 4; }
+    bool packed(const void* base) const
+    {
+        return !depth && lay.point_step == 16 && lay.off_x == 0 && lay.off_y == 4 && lay.off_z == 8 && ((uintptr_t)base & 15) == 0;
+    }
+};
+
+// Validated arguments in, under the lock.  The device form is one launch into the caller's buffers; the host forms run chunks of
+// kQueryChunk points through h->query_out and download each through the pinned buffers.
+static int query_locked(hfpf_handle* h, const hfpf_query_opts* o, const QueryFrame& f, const double pose[12], hfpf_query_hit* hits, hfpf_row* rows)
+{
+    int rc;
+    if ((rc = render_prelude_locked(h, "query"))) return rc;
+    if (f.n == 0) return HFPF_OK;
+    QueryParams p{};
+    memcpy(p.T, pose, sizeof p.T);
+    p.min_count = std::max(1.0, o->min_count);
+    p.max_d2 = o->max_distance * o->max_distance;
+    p.radius = o->radius;
+    p.zclip = (o->flags & HFPF_QUERY_ZCLIP) ? 1u : 0u;
+    const DepthLayout dl = f.depth ? depth_layout(f.ds, nullptr, 0) : DepthLayout{};
+    auto launch = [&](const uint8_t* frame, uint64_t first, uint32_t n, QueryHit* dh, Row* dr) -> int {
+        p.first = first;
+        p.n = n;
+        const dim3 grid(blocks_for(n, 256));
+        if (f.depth)
+            hipLaunchKernelGGL((k_query<kQueryDepth>), grid, dim3(256), 0, h->stream, h->g, h->t, p, frame, dl, dh, dr);
+        else if (f.packed(frame))
+            hipLaunchKernelGGL((k_query<kQueryPacked16>), grid, dim3(256), 0, h->stream, h->g, h->t, p, frame, f.lay, dh, dr);
+        else
+            hipLaunchKernelGGL((k_query<kQueryStrided>), grid, dim3(256), 0, h->stream, h->g, h->t, p, frame, f.lay, dh, dr);
+        HIPCHK(h, hipGetLastError());
+        return HFPF_OK;
+    };
+    if (f.dev) {
+        if ((rc = launch((const uint8_t*)f.dev, 0, f.n, (QueryHit*)hits, (Row*)rows))) return rc;
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return HFPF_OK;
+    }
+    const uint32_t chunk = std::min(f.n, kQueryChunk);
+    if ((rc = scratch(h, h->query_out, (size_t)chunk * (sizeof(QueryHit) + (rows ? sizeof(Row) : 0))))) return rc;
+    QueryHit* dh = (QueryHit*)h->query_out.p;
+    Row* dr = rows ? (Row*)((char*)h->query_out.p + (size_t)chunk * sizeof(QueryHit)) : nullptr;
+    if (f.depth) {  // the whole image once; the chunks index into it
+        if ((rc = scratch(h, h->query_in, f.ds.depth_bytes()))) return rc;
+        const hipError_t e = upload_pageable(h, h->query_in.p, f.host, f.ds.depth_bytes());
+        if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "query upload: %s", hipGetErrorString(e));
+    } else if ((rc = scratch(h, h->query_in, f.cloud_bytes(chunk)))) {
+        return rc;
+    }
+    for (uint64_t first = 0; first < f.n; first += chunk) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, f.n - first);
+        uint64_t k_first = first;
+        if (!f.depth) {  // this chunk's records
+            const hipError_t e = upload_pageable(h, h->query_in.p, (const uint8_t*)f.host + first * f.lay.point_step, f.cloud_bytes(n));
+            if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "query upload: %s", hipGetErrorString(e));
+            k_first = 0;
+        }
+        if ((rc = launch((const uint8_t*)h->query_in.p, k_first, n, dh, dr))) return rc;
+        hipError_t e = download_pageable(h, hits + first, dh, (size_t)n * sizeof(QueryHit), 0);
+        if (e == hipSuccess && rows) e = download_pageable(h, rows + first, dr, (size_t)n * sizeof(Row), 0);
+        if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "query download: %s", hipGetErrorString(e));
+    }
+    return HFPF_OK;
+}
+
+static int query_cloud_common(hfpf_handle* h, const hfpf_query_opts* o, const void* base, bool on_device, uint32_t n_points, uint32_t point_step,
+                              uint32_t off_x, uint32_t off_y, uint32_t off_z, const double pose[12], hfpf_query_hit* hits, hfpf_row* rows)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (!query_args_ok(o, pose)) return fail(h, HFPF_ERR_BAD_ARG, "query: invalid options or pose");
+    if (n_points && (!base || !hits)) return fail(h, HFPF_ERR_BAD_ARG, "query: null cloud or hits");
+    if ((point_step & 3) || (off_x & 3) || (off_y & 3) || (off_z & 3)) return fail(h, HFPF_ERR_BAD_ARG, "query: fields must be 4-byte aligned");
+    if (std::max({off_x, off_y, off_z}) + 4 > point_step) return fail(h, HFPF_ERR_BAD_ARG, "query: field offset beyond point_step");
+    if (on_device && (((uintptr_t)base & 3) || ((uintptr_t)hits & 15) || ((uintptr_t)rows & 15)))
+        return fail(h, HFPF_ERR_BAD_ARG, "query_device: the cloud must be 4-byte and hits / rows 16-byte aligned");
+    QueryFrame f{};
+    (on_device ? f.dev : f.host) = base;
+    f.lay = FrameLayout{point_step, off_x, off_y, off_z, 0};
+    f.n = n_points;
+    return query_locked(h, o, f, pose, hits, rows);
+}
+
+int hfpf_query(hfpf_handle* h, const hfpf_query_opts* o, const void* base, uint32_t n_points, uint32_t point_step, uint32_t off_x, uint32_t off_y,
+               uint32_t off_z, const double pose_3x4[12], hfpf_query_hit* hits, hfpf_row* rows)
+{
+    return query_cloud_common(h, o, base, false, n_points, point_step, off_x, off_y, off_z, pose_3x4, hits, rows);
+}
+
+int hfpf_query_device(hfpf_handle* h, const hfpf_query_opts* o, const void* dev_base, uint32_t n_points, uint32_t point_step, uint32_t off_x,
+                      uint32_t off_y, uint32_t off_z, const double pose_3x4[12], hfpf_query_hit* dev_hits, hfpf_row* dev_rows)
+{
+    return query_cloud_common(h, o, dev_base, true, n_points, point_step, off_x, off_y, off_z, pose_3x4, dev_hits, dev_rows);
+}
+
+int hfpf_query_depth(hfpf_handle* h, const hfpf_query_opts* o, const hfpf_depth_image* desc, const void* depth, const double pose_3x4[12],
+                     hfpf_query_hit* hits, hfpf_row* rows)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (!query_args_ok(o, pose_3x4) || !hits) return fail(h, HFPF_ERR_BAD_ARG, "query: invalid options, pose or hits");
+    QueryFrame f{};
+    // the colour fields are validated as integrate validates them, but no colour image is read
+    if (int rc = depth_spec(h, desc, depth, desc && desc->color_format != HFPF_COLOR_NONE ? depth : nullptr, &f.ds)) return rc;
+    f.ds.color_bpp = 0;
+    f.depth = true;
+    f.host = depth;
+    f.n = f.ds.width * f.ds.height;
+    return query_locked(h, o, f, pose_3x4, hits, rows);
 }
 
 int hfpf_stats_export(hfpf_handle* h, const void** dev_words, uint64_t* n_words, const void** dev_cwords, uint64_t* n_cwords)

@@ -2046,15 +2046,27 @@ struct Row {  // = hfpf_row
 };
 static_assert(sizeof(Row) == 64, "row is 64 bytes");
 
-__global__ __launch_bounds__(256) void k_extract_rows(const GridParams g, const Tables t, const unsigned long long* __restrict__ stats,
-                                                      const uint64_t n_rows, const ExtractOpts opt, const uint64_t* __restrict__ keys,
-                                                      const uint32_t* __restrict__ vals, Row* __restrict__ rows)
+// The centroid of record nid (cnt = its count, > 0; s = its statistic words) and the mean em of its line parameter: every projection
+// is a - s*ab (stats.hpp), so centroid = a - E[s]*ab.  Shared by k_extract_rows and k_query, which compares distances to it.
+__device__ __forceinline__ void record_centroid(const GridParams& g, const Tables& t, const long long* s, const uint64_t nid, const long long cnt,
+                                                double& em, float& x, float& y, float& z)
 {
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_rows) return;
-    const uint64_t nid = vals[j];
+    const float4 l0 = t.nv_line[2 * nid], l1 = t.nv_line[2 * nid + 1];
+    const double ax = l0.y, ay = l0.z, az = l0.w, abx = l1.x, aby = l1.y, abz = l1.z;
+    const double inv = 1.0 / (double)cnt;
+    em = ((double)s[SW_S] / (double)g.fs_scale) * inv;  // mean of s, or of u = s - 0.5 (stats.hpp)
+    const double es = HFPF_CENTERED_MOMENTS ? 0.5 + em : em;
+    x = (float)(ax - es * abx);
+    y = (float)(ay - es * aby);
+    z = (float)(az - es * abz);
+}
+
+// The row of record nid at cell (x, y, z), before any colour coding: the per-row body of k_extract_rows, also k_query's winner row.
+__device__ __forceinline__ Row record_row(const GridParams& g, const Tables& t, const unsigned long long* __restrict__ stats, const uint64_t nid,
+                                          const int32_t x, const int32_t y, const int32_t z)
+{
     Row r;
-    key_coords(g, keys[j], r.ix, r.iy, r.iz);
+    r.ix = x, r.iy = y, r.iz = z;
     const long long* s = reinterpret_cast<const long long*>(&stats[nid * kStatWords]);
     const long long cnt = s[SW_COUNT];
     r.count = (uint32_t)cnt;
@@ -2067,15 +2079,12 @@ __global__ __launch_bounds__(256) void k_extract_rows(const GridParams g, const 
         r.mean_dist = r.sd_dist = 0.f;
         r.rgb = 0;
     } else {
-        const float4 l0 = t.nv_line[2 * nid], l1 = t.nv_line[2 * nid + 1];
-        const double ax = l0.y, ay = l0.z, az = l0.w, abx = l1.x, aby = l1.y, abz = l1.z;
+        double em;
+        record_centroid(g, t, s, nid, cnt, em, r.x, r.y, r.z);
+        const float4 l1 = t.nv_line[2 * nid + 1];
+        const double abx = l1.x, aby = l1.y, abz = l1.z;
         const double inv = 1.0 / (double)cnt;
-        // every projection is a - s*ab (stats.hpp): centroid = a - E[s]*ab, per-axis variance = ab_i^2 * var(s)
-        const double em = ((double)s[SW_S] / (double)g.fs_scale) * inv;  // mean of s, or of u = s - 0.5 (stats.hpp)
-        const double es = HFPF_CENTERED_MOMENTS ? 0.5 + em : em;
-        r.x = (float)(ax - es * abx);
-        r.y = (float)(ay - es * aby);
-        r.z = (float)(az - es * abz);
+        // per-axis variance = ab_i^2 * var(s)
         double vs = ((double)s[SW_SS] / (double)g.fss_scale) * inv - em * em;
         const double md = ((double)s[SW_D] / (double)g.fd_scale) * inv;
         double vd = ((double)s[SW_DD] / (double)g.fdd_scale) * inv - md * md;
@@ -2094,6 +2103,18 @@ __global__ __launch_bounds__(256) void k_extract_rows(const GridParams g, const 
             r.rgb = (min(cr, 255u) << 16) | (min(cg, 255u) << 8) | min(cb, 255u);
         }
     }
+    return r;
+}
+
+__global__ __launch_bounds__(256) void k_extract_rows(const GridParams g, const Tables t, const unsigned long long* __restrict__ stats,
+                                                      const uint64_t n_rows, const ExtractOpts opt, const uint64_t* __restrict__ keys,
+                                                      const uint32_t* __restrict__ vals, Row* __restrict__ rows)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_rows) return;
+    int32_t x, y, z;
+    key_coords(g, keys[j], x, y, z);
+    Row r = record_row(g, t, stats, vals[j], x, y, z);
     if (opt.paint_white) r.rgb = 0x00FFFFFFu;
     if (opt.classify_threshold >= 0) r.rgb = (int)r.count > opt.classify_threshold ? 0x00FF0000u : 0x00FFFFFFu;
     rows[j] = r;
@@ -2358,6 +2379,167 @@ __global__ __launch_bounds__(256) void k_track_reduce(const TrackParams p, const
     }
 }
 
+
+// ---- point queries (hfpf_query*, include/hfpf.h) ----------------------------------------------------------------------
+// One lane per point: load and transform it as integrate does, read its own cell's occupancy bit, then walk the rows of the
+// (2r+1)^3 window around its voxel.  r <= 4 makes the window span at most two bricks per axis: at most 8 directory words, and per
+// x-plane of a touched brick one nd_mask normal_found word ANDed with the window's (y, z) mask; the set bits are the cells with a
+// record, stat_id names it.  Candidates are the rows extract would emit (valid cell, count >= max(1, min_count): the compare of
+// k_extract_keys) and their centroid is record_centroid's, so the distances are those of the extracted rows.  The winner is the
+// smallest d2 and then the smallest (x, y, z) key, independent of the walk order.
+constexpr uint32_t kQHitUsed = 1u, kQHitInBbox = 2u, kQHitOccupied = 4u, kQHitHasRow = 8u, kQHitFound = 16u;
+constexpr int kQueryMaxRadius = 4;
+enum QueryForm : int { kQueryPacked16 = 0, kQueryStrided = 1, kQueryDepth = 2 };
+
+struct __attribute__((aligned(16))) QueryHit {  // = hfpf_query_hit
+    int32_t voxel[3];
+    uint32_t flags;
+    int32_t row_voxel[3];
+    uint32_t row_count;
+    float p[3];
+    float distance;
+    float signed_distance;
+    uint32_t reserved[3];
+};
+static_assert(sizeof(QueryHit) == 64, "query hit is 64 bytes");
+
+struct QueryParams {
+    double T[12];        // camera -> fusion frame
+    double min_count;    // max(1, min_count)
+    double max_d2;       // max_distance * max_distance (+inf allowed)
+    uint64_t first;      // frame index of the launch's first point (hit k = point first + k)
+    uint32_t n;          // points of the launch
+    int32_t radius;      // 0..kQueryMaxRadius
+    uint32_t zclip;      // 1: the handle's z-clip decides USED
+};
+
+// (y, z) window mask of one x-plane: bits ly * 8 + lz for ly in [ya, yb], lz in [za, zb] (0 <= a <= b <= 7)
+__device__ __forceinline__ uint64_t plane_window(int ya, int yb, int za, int zb)
+{
+    const uint64_t ybytes = (yb - ya == 7 ? ~0ull : (1ull << (8 * (yb - ya + 1))) - 1ull) << (8 * ya);
+    const uint64_t zbits = (uint64_t)(((1u << (zb - za + 1)) - 1u) << za) * 0x0101010101010101ull;
+    return ybytes & zbits;
+}
+
+template <int FORM>
+__global__ __launch_bounds__(256) void k_query(const GridParams g, const Tables t, const QueryParams p, const uint8_t* __restrict__ frame,
+                                               const std::conditional_t<FORM == kQueryDepth, DepthLayout, FrameLayout> lay,
+                                               QueryHit* __restrict__ hits, Row* __restrict__ rows)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= p.n) return;
+    const uint64_t i = p.first + k;
+    float x, y, z;
+    if constexpr (FORM == kQueryDepth) {
+        const vf4 r = depth_fetch<false>(frame, nullptr, lay, (uint32_t)i);
+        const F3 c = depth_backproject(__float_as_uint(r.z), __float_as_uint(r.w), __float_as_uint(r.x), lay.depth_f32 != 0, lay.cx, lay.cy,
+                                       lay.sx, lay.sy, lay.unit);
+        x = c.x, y = c.y, z = c.z;
+    } else if constexpr (FORM == kQueryPacked16) {
+        const vf4 r = reinterpret_cast<const vf4*>(frame)[i];
+        x = r.x, y = r.y, z = r.z;
+    } else {
+        const uint8_t* rec = frame + i * lay.point_step;
+        x = *reinterpret_cast<const float*>(rec + lay.off_x);
+        y = *reinterpret_cast<const float*>(rec + lay.off_y);
+        z = *reinterpret_cast<const float*>(rec + lay.off_z);
+    }
+    const float qnan = __builtin_bit_cast(float, 0x7FC00000u);
+    QueryHit h;
+    h.voxel[0] = h.voxel[1] = h.voxel[2] = INT_MIN;
+    h.flags = 0;
+    h.row_voxel[0] = h.row_voxel[1] = h.row_voxel[2] = -1;
+    h.row_count = 0;
+    h.p[0] = h.p[1] = h.p[2] = qnan;
+    h.distance = h.signed_distance = qnan;
+    h.reserved[0] = h.reserved[1] = h.reserved[2] = 0;
+    bool found = false;
+    uint32_t best_nid = 0;
+    int32_t wx = -1, wy = -1, wz = -1;
+    if (__builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z) && (!p.zclip || zclip_pass(g, z))) {
+        const F3 q = transform_point(p.T, x, y, z);
+        int32_t v[3];
+        voxel_coords(g, q, v[0], v[1], v[2]);
+        h.flags = kQHitUsed;
+        h.voxel[0] = v[0], h.voxel[1] = v[1], h.voxel[2] = v[2];
+        h.p[0] = q.x, h.p[1] = q.y, h.p[2] = q.z;
+        if (valid_point(g, q)) {
+            h.flags |= kQHitInBbox;
+            // own cell: inside the storage extent (0..dim) for every in-bbox point; checked all the same before the table reads
+            if (v[0] >= 0 && v[1] >= 0 && v[2] >= 0 && v[0] <= g.dim[0] && v[1] <= g.dim[1] && v[2] <= g.dim[2]) {
+                uint64_t plane, bit;
+                slot_plane_bit(slot_lookup(g, t, v[0], v[1], v[2]), plane, bit);
+                if (t.occ_mask[plane] & bit) h.flags |= kQHitOccupied;
+            }
+            // the window, clipped to the valid cells 0..dim-1 (extract emits no other)
+            int lo[3], hi[3];
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                lo[a] = max(v[a] - p.radius, 0);
+                hi[a] = min(v[a] + p.radius, g.dim[a] - 1);
+            }
+            double best_d2 = 0.0, bdx = 0.0, bdy = 0.0, bdz = 0.0;
+            uint64_t best_key = 0;
+            if (lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2]) {
+                for (int bx = lo[0] >> kBrickShift; bx <= hi[0] >> kBrickShift; bx++)
+                    for (int by = lo[1] >> kBrickShift; by <= hi[1] >> kBrickShift; by++)
+                        for (int bz = lo[2] >> kBrickShift; bz <= hi[2] >> kBrickShift; bz++) {
+                            const uint32_t b = t.dir[((uint32_t)bx * (uint32_t)g.bdim[1] + (uint32_t)by) * (uint32_t)g.bdim[2] + (uint32_t)bz];
+                            if (b == 0 || b == kLock) continue;  // untouched (kLock cannot happen between kernels)
+                            const uint64_t wmask = plane_window(max(lo[1] - 8 * by, 0), min(hi[1] - 8 * by, 7), max(lo[2] - 8 * bz, 0),
+                                                                min(hi[2] - 8 * bz, 7));
+                            const int x1 = min(hi[0], 8 * bx + 7);
+                            for (int cx = max(lo[0], 8 * bx); cx <= x1; cx++) {
+                                uint64_t w = t.nd_mask[((uint64_t)b * 8u + (uint32_t)(cx & 7)) * 2] & wmask;
+                                while (w) {
+                                    const int bitn = __builtin_ctzll(w);
+                                    w &= w - 1;
+                                    const int32_t cy = 8 * by + (bitn >> 3), cz = 8 * bz + (bitn & 7);
+                                    const uint32_t nid = t.stat_id[b * kBrickCells + local_index(cx, cy, cz)];
+                                    if (nid == 0) continue;
+                                    const long long* s = reinterpret_cast<const long long*>(&t.stats[(uint64_t)nid * kStatWords]);
+                                    const long long cnt = s[SW_COUNT];
+                                    if ((double)(int)cnt < p.min_count) continue;  // min_count >= 1: cnt > 0 below
+                                    if (cx == v[0] && cy == v[1] && cz == v[2]) h.flags |= kQHitHasRow;
+                                    double em;
+                                    float rx, ry, rz;
+                                    record_centroid(g, t, s, nid, cnt, em, rx, ry, rz);
+                                    const double dx = (double)q.x - (double)rx, dy = (double)q.y - (double)ry, dz = (double)q.z - (double)rz;
+                                    const double d2 = (dx * dx + dy * dy) + dz * dz;
+                                    if (!(d2 <= p.max_d2)) continue;
+                                    const uint64_t key = make_key(g, cx, cy, cz);
+                                    if (!found || d2 < best_d2 || (d2 == best_d2 && key < best_key)) {
+                                        found = true;
+                                        best_d2 = d2, best_key = key, best_nid = nid;
+                                        bdx = dx, bdy = dy, bdz = dz;
+                                        wx = cx, wy = cy, wz = cz;
+                                    }
+                                }
+                            }
+                        }
+            }
+            if (found) {
+                const double nx = t.nv_n[3 * (uint64_t)best_nid], ny = t.nv_n[3 * (uint64_t)best_nid + 1], nz = t.nv_n[3 * (uint64_t)best_nid + 2];
+                h.flags |= kQHitFound;
+                h.row_voxel[0] = wx, h.row_voxel[1] = wy, h.row_voxel[2] = wz;
+                h.row_count = (uint32_t)t.stats[(uint64_t)best_nid * kStatWords + SW_COUNT];
+                h.distance = (float)sqrt(best_d2);
+                h.signed_distance = (float)((nx * bdx + ny * bdy) + nz * bdz);
+            }
+        }
+    }
+    hits[k] = h;
+    if (rows) {
+        Row r;
+        if (found) {
+            r = record_row(g, t, t.stats, best_nid, wx, wy, wz);
+        } else {
+            r = Row{};
+            r.ix = r.iy = r.iz = -1;
+        }
+        rows[k] = r;
+    }
+}
 
 // ---- multi-GPU epoch exchange ----------------------------------------------------------
 // Frames shard across ranks; what must be agreed before a clean pass is the occupancy set and, per cell, the

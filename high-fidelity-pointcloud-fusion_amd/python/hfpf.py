@@ -90,6 +90,7 @@ EXPORTS = [
     "hfpf_integrate_depth", "hfpf_integrate_depth_pinned", "hfpf_integrate_depth_device", "hfpf_probe_depth",
     "hfpf_render", "hfpf_render_device",
     "hfpf_track_depth", "hfpf_track_depth_device", "hfpf_track",
+    "hfpf_query", "hfpf_query_device", "hfpf_query_depth",
 ]
 
 # hfpf_depth_image formats (include/hfpf.h)
@@ -210,6 +211,29 @@ def _track_out(r):
                   "information": np.array(r.information[:], np.float64).reshape(6, 6), "pose": pose}
 
 
+# hfpf_query_opts.flags and hfpf_query_hit.flags (include/hfpf.h)
+QUERY_ZCLIP = 1
+QHIT_USED, QHIT_IN_BBOX, QHIT_OCCUPIED, QHIT_HAS_ROW, QHIT_FOUND = 1, 2, 4, 8, 16
+QUERY_HIT_DTYPE = np.dtype([("voxel", "<i4", (3,)), ("flags", "<u4"), ("row_voxel", "<i4", (3,)), ("row_count", "<u4"),
+                            ("p", "<f4", (3,)), ("distance", "<f4"), ("signed_distance", "<f4"), ("reserved", "<u4", (3,))])
+assert QUERY_HIT_DTYPE.itemsize == 64
+
+
+class QueryOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("radius", C.c_int32), ("reserved0", C.c_int32),
+                ("min_count", C.c_double), ("max_distance", C.c_double), ("reserved", C.c_uint64)]
+
+
+def query_opts(radius=1, min_count=0.0, max_distance=float("inf"), zclip=False):
+    """An hfpf_query_opts: the (2 radius + 1)^3 voxel window, the count and distance gates, HFPF_QUERY_ZCLIP."""
+    o = QueryOpts()
+    o.struct_size = C.sizeof(QueryOpts)
+    o.flags = QUERY_ZCLIP if zclip else 0
+    o.radius = int(radius)
+    o.min_count, o.max_distance = float(min_count), float(max_distance)
+    return o
+
+
 EPOCH_REC_DTYPE = np.dtype([("key", "<u8"), ("first_frame", "<u4"), ("vx", "<f4"), ("vy", "<f4"), ("vz", "<f4"), ("pad", "<u4", (2,))])
 assert EPOCH_REC_DTYPE.itemsize == 32
 
@@ -288,6 +312,9 @@ def lib():
     L.hfpf_track_depth.argtypes = [vp, C.POINTER(TrackOpts), C.POINTER(DepthImage), vp, vp, C.POINTER(TrackResult)]
     L.hfpf_track_depth_device.argtypes = [vp, C.POINTER(TrackOpts), C.POINTER(DepthImage), vp, vp, C.POINTER(TrackResult)]
     L.hfpf_track.argtypes = [vp, C.POINTER(TrackOpts), vp, u32, u32, u32, u32, u32, vp, C.POINTER(TrackResult)]
+    L.hfpf_query.argtypes = [vp, C.POINTER(QueryOpts), vp, u32, u32, u32, u32, u32, vp, vp, vp]
+    L.hfpf_query_device.argtypes = [vp, C.POINTER(QueryOpts), vp, u32, u32, u32, u32, u32, vp, vp, vp]
+    L.hfpf_query_depth.argtypes = [vp, C.POINTER(QueryOpts), C.POINTER(DepthImage), vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -540,6 +567,67 @@ class OccupancyGrid:
         self._chk(lib().hfpf_track(self._h, C.byref(o), _p(cloud), n_points, step, layout["off_x"], layout["off_y"], layout["off_z"],
                                    _p(pose), C.byref(r)))
         return _track_out(r)
+
+    # -- querying the model at given points --
+    def query(self, cloud, pose, layout=None, n_points=None, opts=None, radius=1, min_count=0.0, max_distance=float("inf"), zclip=False,
+              rows=True):
+        """Nearest row within the voxel window of each point of a cloud in pageable memory (hfpf_query).  cloud: an (N, 3) float32
+        array, or records with layout = dict(point_step, off_x, off_y, off_z) (extra keys are ignored).  Returns (hits, rows):
+        numpy arrays of QUERY_HIT_DTYPE and ROW_DTYPE; rows is None with rows=False."""
+        cloud = np.ascontiguousarray(cloud)
+        if layout is None:
+            cloud = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+            layout = dict(point_step=12, off_x=0, off_y=4, off_z=8)
+        step = layout["point_step"]
+        if n_points is None:
+            n_points = cloud.nbytes // step
+        o = opts if opts is not None else query_opts(radius, min_count, max_distance, zclip)
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        hits = np.empty(n_points, QUERY_HIT_DTYPE)
+        out = np.empty(n_points, ROW_DTYPE) if rows else None
+        self._chk(lib().hfpf_query(self._h, C.byref(o), _p(cloud), n_points, step, layout["off_x"], layout["off_y"], layout["off_z"], _p(pose),
+                                   _p(hits), _p(out) if rows else None))
+        return hits, out
+
+    def query_device(self, dev_cloud, n_points, pose, layout=None, dev_hits=0, dev_rows=0, rows=True, opts=None, radius=1, min_count=0.0,
+                     max_distance=float("inf"), zclip=False):
+        """The same for a cloud resident in HBM, read in place (hfpf_query_device); layout defaults to packed (x, y, z) f32 triples.
+        With dev_hits (and dev_rows, or 0 for none) the results stay in those device buffers and None is returned; otherwise they go
+        to scratch device buffers and come back as (hits, rows) numpy arrays as query() returns them."""
+        layout = layout or dict(point_step=12, off_x=0, off_y=4, off_z=8)
+        o = opts if opts is not None else query_opts(radius, min_count, max_distance, zclip)
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        own = not dev_hits
+        if own:
+            dev_hits = self.device_alloc(max(1, n_points) * QUERY_HIT_DTYPE.itemsize)
+            dev_rows = self.device_alloc(max(1, n_points) * ROW_DTYPE.itemsize) if rows else 0
+        try:
+            self._chk(lib().hfpf_query_device(self._h, C.byref(o), C.c_void_p(dev_cloud), n_points, layout["point_step"], layout["off_x"],
+                                              layout["off_y"], layout["off_z"], _p(pose), C.c_void_p(dev_hits),
+                                              C.c_void_p(dev_rows) if dev_rows else None))
+            if not own:
+                return None
+            hits = self.device_download(dev_hits, n_points * QUERY_HIT_DTYPE.itemsize).view(QUERY_HIT_DTYPE)
+            out = self.device_download(dev_rows, n_points * ROW_DTYPE.itemsize).view(ROW_DTYPE) if rows else None
+            return hits, out
+        finally:
+            if own:
+                self.device_free(dev_hits)
+                if dev_rows:
+                    self.device_free(dev_rows)
+
+    def query_depth(self, depth, pose, K, depth_scale=0.001, opts=None, radius=1, min_count=0.0, max_distance=float("inf"), zclip=False,
+                    rows=True):
+        """Query every pixel of one depth image in pageable memory (hfpf_query_depth); hit / row i = pixel (i % W, i // W)."""
+        d = _image_desc(depth, K, None, None, depth_scale)
+        o = opts if opts is not None else query_opts(radius, min_count, max_distance, zclip)
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        n = d.width * d.height
+        hits = np.empty(n, QUERY_HIT_DTYPE)
+        out = np.empty(n, ROW_DTYPE) if rows else None
+        self._chk(lib().hfpf_query_depth(self._h, C.byref(o), C.byref(d), C.c_void_p(depth.ctypes.data), _p(pose), _p(hits),
+                                         _p(out) if rows else None))
+        return hits, out
 
     # -- multi-GPU --
     def dist_init_rccl(self, rank, world, unique_id):

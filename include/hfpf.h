@@ -391,6 +391,87 @@ int hfpf_track_depth_device(hfpf_handle* h, const hfpf_track_opts* o, const hfpf
 int hfpf_track(hfpf_handle* h, const hfpf_track_opts* o, const void* base, uint32_t n_points, uint32_t point_step, uint32_t off_x,
                uint32_t off_y, uint32_t off_z, const double pose_3x4[12], hfpf_track_result* result);
 
+/* ---- querying the fused model at given points (nearest row within a voxel window; no reference counterpart) ----------------
+ * A query takes points (a cloud or a depth image) and a pose T (row-major [R|t], camera -> fusion frame, the integrate
+ * convention) and answers per point: its voxel, whether that voxel is occupied or holds a row, and the nearest row within a
+ * window of voxels around it.  Everything is restatable from hfpf_extract's rows and hfpf_get_occupied's list.  Per point i:
+ * Input: cloud record i's f32 x, y, z; depth pixel i = (i % width, i / width) back-projected by the f32 arithmetic of the
+ *   depth-frame contract above (invalid pixels are NaN).  The point is USED iff x, y, z are finite and, with HFPF_QUERY_ZCLIP,
+ *   z_clip_min < z < z_clip_max (the handle's z-clip, as integrate applies it).  An unused point gets flags = 0,
+ *   voxel = INT_MIN on each axis, p = NaN and the "not found" values below.
+ * Fusion frame: p = (float)(((T[0]*x + T[1]*y) + T[2]*z) + T[3]), likewise rows 1 and 2 (f64, x widened; the rounding of
+ *   integrate).  voxel[a] = (int)floor(((double)p[a] - bbox_min[a]) / res) with res = hfpf_get_dims' resolution, INT_MIN when
+ *   that is NaN or outside the int range: the voxel integrate puts the same point in.  IN_BBOX iff
+ *   bbox_min[a] < (double)p[a] < bbox_max[a] on every axis.  OCCUPIED (IN_BBOX points only) iff hfpf_get_occupied lists voxel.
+ * Candidates (USED and IN_BBOX points only): the rows hfpf_extract would return at this point of the call sequence (host frames
+ *   still waiting are launched first) with count >= max(1, min_count) (the compare of hfpf_extract_opts) and
+ *   max(|ix - voxel[0]|, |iy - voxel[1]|, |iz - voxel[2]|) <= radius.  HAS_ROW iff the row of voxel itself is a candidate.
+ * Distance, f64, left to right, never contracted: d = ((double)p[0] - (double)row.x, ... y, ... z),
+ *   d2 = (d.x*d.x + d.y*d.y) + d.z*d.z; a candidate is kept iff d2 <= max_distance * max_distance.
+ * Winner: the kept candidate with the smallest d2; ties go to the lexicographically smallest (ix, iy, iz) (the smallest extract
+ *   row index), so results do not depend on scheduling.  With a winner: FOUND, row_voxel = its (ix, iy, iz), row_count = its
+ *   count, distance = (float)sqrt(d2), signed_distance = (float)(((double)nx*d.x + (double)ny*d.y) + (double)nz*d.z) (> 0 on the
+ *   side the normal faces, i.e. the sensor side), and rows[i] = its hfpf_row, byte-identical to hfpf_extract's (no colour coding).
+ *   Without one: row_voxel = -1, row_count = 0, distance = signed_distance = NaN (0x7FC00000), rows[i] = {ix = iy = iz = -1, every
+ *   other field 0}.  reserved words are 0.
+ * A query changes nothing on the handle except device_bytes (its scratch: for host forms the input and up to 2^20 points of
+ * output per chunk; chunks do not change a byte of the result).  Rejected with HFPF_ERR_BAD_ARG (the handle stays usable, nothing
+ * is written): struct_size != sizeof, unknown flags, reserved0 or reserved != 0, radius outside 0..4, min_count NaN, not
+ * max_distance > 0 (+inf allowed), a NULL or non-finite pose, NULL hits; for clouds a NULL buffer, offsets or point_step not
+ * multiples of 4, an offset + 4 beyond point_step, and on the device a buffer not 4-byte or hits / rows not 16-byte aligned; for depth
+ * images every check of hfpf_depth_image (colour fields included; no colour image is read).  n_points = 0 returns HFPF_OK after
+ * these checks (buffer and hits may then be NULL) and writes nothing.  A handle with an RCCL communicator returns HFPF_ERR_STATE
+ * (a distributed query is not provided); a failed handle returns HFPF_ERR_STATE as extract does.  Every call returns when its
+ * outputs are complete. */
+#define HFPF_QUERY_ZCLIP 1u      /* opts.flags: apply the handle's camera-frame z-clip to the input point, as integrate does */
+
+typedef struct hfpf_query_opts {
+    uint32_t struct_size;        /* = sizeof(hfpf_query_opts) */
+    uint32_t flags;              /* HFPF_QUERY_* */
+    int32_t radius;              /* 0..4: Chebyshev half-width, in voxels, of the cube searched around the point's voxel */
+    int32_t reserved0;           /* 0 */
+    double min_count;            /* rows with count < max(1, min_count) are not candidates */
+    double max_distance;         /* > 0, +inf allowed: candidates farther than this are ignored */
+    uint64_t reserved;           /* 0 */
+} hfpf_query_opts;
+
+#define HFPF_QHIT_USED 1u        /* x, y, z finite (and inside the z-clip with HFPF_QUERY_ZCLIP) */
+#define HFPF_QHIT_IN_BBOX 2u     /* the transformed point passes integrate's bounding-box test */
+#define HFPF_QHIT_OCCUPIED 4u    /* its voxel is occupied (as hfpf_get_occupied lists it) */
+#define HFPF_QHIT_HAS_ROW 8u     /* its voxel itself holds a candidate row (whatever max_distance says) */
+#define HFPF_QHIT_FOUND 16u      /* a nearest row was found; row_voxel / distance / signed_distance / rows[i] describe it */
+
+typedef struct hfpf_query_hit {  /* 64 bytes */
+    int32_t voxel[3];            /* the point's voxel as integrate indexes it (INT_MIN when not USED) */
+    uint32_t flags;              /* HFPF_QHIT_* */
+    int32_t row_voxel[3];        /* the nearest row's (ix, iy, iz); -1 when not FOUND */
+    uint32_t row_count;          /* its count; 0 when not FOUND */
+    float p[3];                  /* the point in the fusion frame, f32 as integrate rounds it (NaN when not USED) */
+    float distance;              /* |p - row|; NaN when not FOUND */
+    float signed_distance;       /* row normal . (p - row); NaN when not FOUND */
+    uint32_t reserved[3];        /* 0 */
+} hfpf_query_hit;
+
+#ifdef __cplusplus
+static_assert(sizeof(hfpf_query_opts) == 40, "hfpf_query_opts is 40 bytes");
+static_assert(sizeof(hfpf_query_hit) == 64, "hfpf_query_hit is 64 bytes");
+#else
+_Static_assert(sizeof(hfpf_query_opts) == 40, "hfpf_query_opts is 40 bytes");
+_Static_assert(sizeof(hfpf_query_hit) == 64, "hfpf_query_hit is 64 bytes");
+#endif
+
+/* A cloud of n_points records of point_step bytes in pageable HOST memory (layout as hfpf_integrate / hfpf_track); hits[i] and
+ * rows[i] (rows optional: NULL = not produced) describe record i. */
+int hfpf_query(hfpf_handle* h, const hfpf_query_opts* o, const void* base, uint32_t n_points, uint32_t point_step, uint32_t off_x,
+               uint32_t off_y, uint32_t off_z, const double pose_3x4[12], hfpf_query_hit* hits, hfpf_row* rows);
+/* The same cloud in DEVICE memory, read in place; dev_hits / dev_rows are DEVICE pointers. */
+int hfpf_query_device(hfpf_handle* h, const hfpf_query_opts* o, const void* dev_base, uint32_t n_points, uint32_t point_step,
+                      uint32_t off_x, uint32_t off_y, uint32_t off_z, const double pose_3x4[12], hfpf_query_hit* dev_hits,
+                      hfpf_row* dev_rows);
+/* A depth image (no colour is read) in pageable HOST memory; hit / row i = pixel (i % width, i / width). */
+int hfpf_query_depth(hfpf_handle* h, const hfpf_query_opts* o, const hfpf_depth_image* desc, const void* depth,
+                     const double pose_3x4[12], hfpf_query_hit* hits, hfpf_row* rows);
+
 /* <directory_name>/test_cloud.pcd (node.cpp:395): PCD v0.7 ASCII, FIELDS x y z rgb normal_x normal_y normal_z curvature */
 int hfpf_write_pcd(const hfpf_row* rows, uint64_t n_rows, const char* path);
 /* <directory_name>/meta.csv (node.cpp:396) with the header string of grid.hpp:462 */
