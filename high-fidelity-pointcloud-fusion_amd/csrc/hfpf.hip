@@ -796,6 +796,57 @@ int pick_update_shape(hfpf_handle* h, double points, uint32_t nb)
     return h->upd_wide ? 1 : 0;
 }
 
+// A cloud's record layout: x, y, z (and rgb: with_rgb) 4-byte aligned and inside point_step.  what = the entry point named in the
+// message.  The base address and the frame stride are the caller's to check.
+int check_cloud_layout(hfpf_handle* h, const char* what, const FrameLayout& lay, bool with_rgb)
+{
+    const uint32_t off_rgb = with_rgb ? lay.off_rgb : 0u;
+    if ((lay.point_step & 3) || (lay.off_x & 3) || (lay.off_y & 3) || (lay.off_z & 3) || (off_rgb & 3))
+        return fail(h, HFPF_ERR_BAD_ARG, "%s: fields must be 4-byte aligned", what);
+    if (std::max({lay.off_x, lay.off_y, lay.off_z, off_rgb}) + 4 > lay.point_step)
+        return fail(h, HFPF_ERR_BAD_ARG, "%s: field offset beyond point_step", what);
+    return HFPF_OK;
+}
+
+// The cloud can take kFormPacked16: x, y, z at 0, 4, 8 of 16-byte records from a 16-byte aligned base.  with_rgb (integrate, which
+// takes the colour from the same load) also asks for rgb at 12 and 16-byte aligned frames.
+bool packed16(const FrameLayout& lay, const void* base, bool with_rgb, uint64_t frame_stride = 0)
+{
+    return lay.point_step == 16 && lay.off_x == 0 && lay.off_y == 4 && lay.off_z == 8 && ((uintptr_t)base & 15) == 0 &&
+           (!with_rgb || (lay.off_rgb == 12 && (frame_stride & 15) == 0));
+}
+
+// A run-time PointForm as a template argument: fn(std::integral_constant<int, FORM>{}).
+template <typename Fn>
+void with_form(int form, Fn&& fn)
+{
+    if (form == kFormDepth) fn(std::integral_constant<int, kFormDepth>{});
+    else if (form == kFormPacked16) fn(std::integral_constant<int, kFormPacked16>{});
+    else fn(std::integral_constant<int, kFormStrided>{});
+}
+
+// ... and k_integrate's colour and bin switches with it: fn(form, color, bin), each an integral constant.
+template <typename Fn>
+void with_form(int form, bool color, bool bin, Fn&& fn)
+{
+    auto with_bin = [&](auto B) {
+        with_form(form, [&](auto F) {
+            if (!color) fn(F, std::false_type{}, B);
+            else fn(F, std::true_type{}, B);
+        });
+    };
+    if (bin) with_bin(std::true_type{});
+    else with_bin(std::false_type{});
+}
+
+// The layout argument of a FORM kernel: *dl for depth images, lay for clouds.
+template <int FORM>
+const PointLayout<FORM>& form_layout(const FrameLayout& lay, const DepthLayout* dl)
+{
+    if constexpr (FORM == kFormDepth) return *dl;
+    else return lay;
+}
+
 // dl != nullptr: the frames are depth images (dev_base / frame_stride address the depth images, n_points = width * height, the
 // cloud layout is unused); the caller has validated them (depth_spec, plus the device alignment of hfpf_integrate_depth_device).
 int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_frames, uint64_t frame_stride, uint32_t n_points,
@@ -804,15 +855,14 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
 {
     if (!dev_base || !poses || n_frames == 0) return fail(h, HFPF_ERR_BAD_ARG, "integrate: null buffer/poses or zero frames");
     if (n_points == 0) return HFPF_OK;
-    if (!dl && ((point_step & 3) || (off_x & 3) || (off_y & 3) || (off_z & 3) || (off_rgb & 3) || ((uintptr_t)dev_base & 3) || (frame_stride & 3)))
-        return fail(h, HFPF_ERR_BAD_ARG, "integrate: fields must be 4-byte aligned");
-    if (!dl && std::max(std::max(off_x, off_y), std::max(off_z, off_rgb)) + 4 > point_step)
-        return fail(h, HFPF_ERR_BAD_ARG, "integrate: field offset beyond point_step");
+    const FrameLayout lay{point_step, off_x, off_y, off_z, off_rgb};
+    if (!dl && (((uintptr_t)dev_base & 3) || (frame_stride & 3))) return fail(h, HFPF_ERR_BAD_ARG, "integrate: fields must be 4-byte aligned");
+    int rc;
+    if (!dl && (rc = check_cloud_layout(h, "integrate", lay, true))) return rc;
     if (n_frames > 65535) return fail(h, HFPF_ERR_BAD_ARG, "integrate: at most 65535 frames per call");
     h->pub_seq = 0;  // kernels are about to be enqueued: a counter snapshot already on its way is no longer the latest
     StageSlot* s = nullptr;
-    int rc = acquire_stage(h, n_frames, &s);
-    if (rc) return rc;
+    if ((rc = acquire_stage(h, n_frames, &s))) return rc;
     memcpy(s->h_pose, poses, (size_t)n_frames * 12 * sizeof(double));
     for (uint32_t f = 0; f < n_frames; f++) {
         const uint32_t id = frame_ids ? frame_ids[f] : h->next_frame_id + f;
@@ -822,9 +872,7 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
     if (!frame_ids) h->next_frame_id += n_frames;
     HIPCHK(h, hipMemcpyAsync(s->d_pose, s->h_pose, (size_t)n_frames * (12 * sizeof(double) + sizeof(uint32_t)), hipMemcpyHostToDevice, h->stream));  // poses + ids
 
-    const FrameLayout lay{point_step, off_x, off_y, off_z, off_rgb};
-    const bool packed = !dl && point_step == 16 && off_x == 0 && off_y == 4 && off_z == 8 && off_rgb == 12 && ((uintptr_t)dev_base & 15) == 0 &&
-                        (frame_stride & 15) == 0;
+    const int form = dl ? kFormDepth : packed16(lay, dev_base, true, frame_stride) ? kFormPacked16 : kFormStrided;
     const dim3 block(256);
     const uint64_t n_tiles = (uint64_t)blocks_for(n_points, 256) * n_frames;
     // 16x16-pixel tiles when the caller told us the image width and the frame tiles exactly (hfpf_config.frame_width)
@@ -849,7 +897,14 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
     const bool color = h->t.color != 0;
     const bool bin = h->binned;
     const uint32_t pre_possible = (h->h_ctr[C_NORMALS] > 0 || h->normals_possible) ? 1u : 0u;  // a clean pass has run: unoccupied cells may carry a dependant
-    uint32_t launch_frames = n_frames, probe = 0;
+    // k_integrate on the batch's first launch_frames frames; probe = 1: the dry run
+    auto launch_integrate = [&](dim3 grid_, bool bin_, uint32_t launch_frames, uint32_t log_rot, uint32_t probe) {
+        with_form(form, color, bin_, [&](auto F, auto C, auto B) {
+            hipLaunchKernelGGL((k_integrate<F == kFormPacked16, C, B, F == kFormDepth>), grid_, block, 0, h->stream, IntegrateArgs{h->g, h->t},
+                               (const uint8_t*)dev_base, frame_stride, n_points, launch_frames, form_layout<F>(lay, dl), (const double*)s->d_pose,
+                               (const uint32_t*)s->d_ids, row_w, log_rot, probe, pre_possible);
+        });
+    };
     // frames of the dry run: twice as many for a long batch.  For 150 frames of 640x480 with random poses the first 8 find 46 % of
     // the bricks the batch touches and 16 find 50 % (32: 57 %), and the plan made from the larger sample sends 30 % fewer points
     // through the overflow list (268 K instead of 382 K per 1000-frame pass): whole job +1.5 %; 32 frames add nothing.
@@ -860,34 +915,14 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
         // read-back (the brick count), once per session; batches of up to kProbeFrames frames just take the direct forms.
         HIPCHK(h, hipMemsetAsync(h->t.bin_fill, 0, 2 * (h->t.max_bricks + 2) * 4, h->stream));
         HIPCHK(h, hipMemsetAsync(h->t.bin_capb, 0, 2 * (h->t.max_bricks + 2) * 4, h->stream));
-        launch_frames = probe_frames;
-        probe = 1;
-        const uint32_t log_rot = 0;
-        const dim3 pgrid((unsigned)std::min<uint64_t>((uint64_t)blocks_for(n_points, 256) * launch_frames, (uint64_t)h->integrate_grid));
-#define HFPF_LAUNCH_PROBE(P, C)                                                                                                                    \
-    hipLaunchKernelGGL((k_integrate<P, C, true>), pgrid, block, 0, h->stream,                                                                        \
-                       IntegrateArgs{h->g, h->t}, (const uint8_t*)dev_base, frame_stride, n_points, launch_frames, lay, (const double*)s->d_pose, \
-                       (const uint32_t*)s->d_ids, row_w, log_rot, probe, pre_possible)
-#define HFPF_LAUNCH_PROBE_DEPTH(C)                                                                                                                 \
-    hipLaunchKernelGGL((k_integrate<false, C, true, true>), pgrid, block, 0, h->stream,                                                               \
-                       IntegrateArgs{h->g, h->t}, (const uint8_t*)dev_base, frame_stride, n_points, launch_frames, *dl, (const double*)s->d_pose, \
-                       (const uint32_t*)s->d_ids, row_w, log_rot, probe, pre_possible)
-        if (dl && !color) HFPF_LAUNCH_PROBE_DEPTH(false);
-        else if (dl) HFPF_LAUNCH_PROBE_DEPTH(true);
-        else if (packed && !color) HFPF_LAUNCH_PROBE(true, false);
-        else if (packed && color) HFPF_LAUNCH_PROBE(true, true);
-        else if (!color) HFPF_LAUNCH_PROBE(false, false);
-        else HFPF_LAUNCH_PROBE(false, true);
-#undef HFPF_LAUNCH_PROBE
-#undef HFPF_LAUNCH_PROBE_DEPTH
+        const dim3 pgrid((unsigned)std::min<uint64_t>((uint64_t)blocks_for(n_points, 256) * probe_frames, (uint64_t)h->integrate_grid));
+        launch_integrate(pgrid, true, probe_frames, 0, 1);
         HIPCHK(h, hipGetLastError());
         int rcp = read_counters(h);  // bricks the dry run claimed
         if (rcp) return rcp;
         h->bin_have_hist = true;
         h->bin_from_probe = true;  // the plan of the launch below comes from a sample: more slack per region
         h->bin_prev_points = (double)n_points * probe_frames;
-        launch_frames = n_frames;
-        probe = 0;
     }
     const uint32_t nb_known = (uint32_t)h->n_bricks_known;
     // a plan = per-brick bin regions sized from the previous launch's demand; without one nothing is parked (direct forms)
@@ -977,29 +1012,10 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
         return hipEventRecord(e, h->stream);
     };
     HIPCHK(h, detail_mark());
-#define HFPF_LAUNCH_INTEGRATE(P, C, B)                                                                                                              \
-    hipLaunchKernelGGL((k_integrate<P, C, B>), grid, block, 0, h->stream,                                                                           \
-                       IntegrateArgs{h->g, h->t}, (const uint8_t*)dev_base, frame_stride, n_points, launch_frames, lay, (const double*)s->d_pose, \
-                       (const uint32_t*)s->d_ids, row_w, log_rot, probe, pre_possible)
-#define HFPF_LAUNCH_INTEGRATE_DEPTH(C, B)                                                                                                          \
-    hipLaunchKernelGGL((k_integrate<false, C, B, true>), grid, block, 0, h->stream,                                                                   \
-                       IntegrateArgs{h->g, h->t}, (const uint8_t*)dev_base, frame_stride, n_points, launch_frames, *dl, (const double*)s->d_pose, \
-                       (const uint32_t*)s->d_ids, row_w, log_rot, probe, pre_possible)
+    launch_integrate(grid, bin, n_frames, log_rot, 0);
     if (!bin) {
-        if (dl && !color) HFPF_LAUNCH_INTEGRATE_DEPTH(false, false);
-        else if (dl) HFPF_LAUNCH_INTEGRATE_DEPTH(true, false);
-        else if (packed && !color) HFPF_LAUNCH_INTEGRATE(true, false, false);
-        else if (packed && color) HFPF_LAUNCH_INTEGRATE(true, true, false);
-        else if (!color) HFPF_LAUNCH_INTEGRATE(false, false, false);
-        else HFPF_LAUNCH_INTEGRATE(false, true, false);
         for (int k = 0; k < 3; k++) HIPCHK(h, detail_mark());
     } else {
-        if (dl && !color) HFPF_LAUNCH_INTEGRATE_DEPTH(false, true);
-        else if (dl) HFPF_LAUNCH_INTEGRATE_DEPTH(true, true);
-        else if (packed && !color) HFPF_LAUNCH_INTEGRATE(true, false, true);
-        else if (packed && color) HFPF_LAUNCH_INTEGRATE(true, true, true);
-        else if (!color) HFPF_LAUNCH_INTEGRATE(false, false, true);
-        else HFPF_LAUNCH_INTEGRATE(false, true, true);
         {  // the points that found no room in a bin (usually a few thousand, everything for a batch without a plan): direct forms
             const unsigned ogrid = (unsigned)std::min<uint64_t>(blocks_for((uint64_t)n_points * n_frames, 256), 8ull * 256);
             if (color) hipLaunchKernelGGL(k_integrate_overflow<true>, dim3(ogrid), dim3(256), 0, h->stream, h->g, h->t, log_rot);
@@ -1035,8 +1051,6 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
         h->bin_have_hist = true;
         h->bin_prev_points = (double)n_points * n_frames;
     }
-#undef HFPF_LAUNCH_INTEGRATE
-#undef HFPF_LAUNCH_INTEGRATE_DEPTH
     HIPCHK(h, hipGetLastError());
     if (h->timing_detail) h->ev_detail_ran.push_back(detail_ran);
     detail_guard.done = true;
@@ -1747,10 +1761,7 @@ static int integrate_host_locked(hfpf_handle* h, const void* base, bool bounce, 
         h->dirty = true;
         return HFPF_OK;
     }
-    if (!ds && ((point_step & 3) || (off_x & 3) || (off_y & 3) || (off_z & 3) || (off_rgb & 3)))
-        return fail(h, HFPF_ERR_BAD_ARG, "integrate: fields must be 4-byte aligned");
-    if (!ds && std::max(std::max(off_x, off_y), std::max(off_z, off_rgb)) + 4 > point_step)
-        return fail(h, HFPF_ERR_BAD_ARG, "integrate: field offset beyond point_step");
+    if (!ds && (rc = check_cloud_layout(h, "integrate", FrameLayout{point_step, off_x, off_y, off_z, off_rgb}, true))) return rc;
     const uint32_t lay[5] = {ds ? 0u : point_step, ds ? 0u : off_x, ds ? 0u : off_y, ds ? 0u : off_z, ds ? 0u : off_rgb};
     const size_t bytes = ds ? (ds->color_bpp ? ds->color_off + ds->color_bytes() : ds->depth_bytes()) : (size_t)n_points * point_step;
     // a frame of another kind or shape (depth frames: size, formats, intrinsics), or a slot that is not the batch's neighbour
@@ -2318,12 +2329,18 @@ static bool track_opts_ok(const hfpf_track_opts* o)
     return view_opts_ok(&o->view);
 }
 
-static bool track_args_ok(const double* pose, const hfpf_track_result* res)
+// A 3x4 pose of 12 finite doubles.
+static bool pose_ok(const double* pose)
 {
-    if (!pose || !res || res->struct_size != sizeof(hfpf_track_result)) return false;
+    if (!pose) return false;
     for (int k = 0; k < 12; k++)
         if (!std::isfinite(pose[k])) return false;
     return true;
+}
+
+static bool track_args_ok(const double* pose, const hfpf_track_result* res)
+{
+    return res && res->struct_size == sizeof(hfpf_track_result) && pose_ok(pose);
 }
 
 // Pageable host -> device copy, complete on return: chunks through the two pinned 16 MB buffers (the mirror of download_pageable),
@@ -2347,30 +2364,33 @@ static hipError_t upload_pageable(hfpf_handle* h, void* dev, const void* host, s
     return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
 }
 
-// The frame of a track: a depth image (ds) or a cloud (lay, n_points), in host memory (copied to h->track_in) or on the device.
-struct TrackFrame {
+// The points of a track or a query: a depth image (ds, n = width * height) or a cloud of n records (lay), in host memory (the
+// consumer stages them in its scratch) or on the device.
+struct PointSource {
     const void* host;
     const void* dev;
     bool depth;
     DepthSpec ds;
     FrameLayout lay;
-    uint32_t n_points;
-    uint32_t cols;        // depth: sampled columns
-    uint64_t n_samples;   // sampled points
-    size_t bytes() const { return depth ? ds.depth_bytes() : (size_t)(n_points - 1) * lay.point_step + std::max({lay.off_x, lay.off_y, lay.off_z}) + 4; }
+    uint32_t n;
+    // the bytes that hold the first n_pts points: the whole image for a depth image
+    size_t bytes(uint32_t n_pts) const
+    {
+        return depth ? ds.depth_bytes() : (size_t)(n_pts - 1) * lay.point_step + std::max({lay.off_x, lay.off_y, lay.off_z}) + 4;
+    }
+    // the PointForm the kernels read it in from device address base
+    int form(const void* base) const { return depth ? kFormDepth : packed16(lay, base, false) ? kFormPacked16 : kFormStrided; }
 };
 
-// The sampling of include/hfpf.h; false when more than 2^26 points would be sampled (the headroom of the int64 sums).
-static bool track_sample(TrackFrame& f, uint32_t stride)
+// A depth image for a consumer that reads no colour (track, query): the descriptor is validated as integrate validates it, its
+// colour fields included, but no colour image is read (color_bpp = 0).
+static int colorless_depth_source(hfpf_handle* h, const hfpf_depth_image* desc, const void* depth, PointSource* f)
 {
-    if (f.depth) {
-        f.cols = (f.ds.width + stride - 1) / stride;
-        f.n_samples = (uint64_t)f.cols * ((f.ds.height + stride - 1) / stride);
-    } else {
-        f.cols = 0;
-        f.n_samples = ((uint64_t)f.n_points + stride - 1) / stride;
-    }
-    return f.n_samples <= (1ull << 26);
+    if (int rc = depth_spec(h, desc, depth, desc && desc->color_format != HFPF_COLOR_NONE ? depth : nullptr, &f->ds)) return rc;
+    f->ds.color_bpp = 0;
+    f->depth = true;
+    f->n = f->ds.width * f->ds.height;
+    return HFPF_OK;
 }
 
 // (A + damping I) x = -b by Cholesky L L^T, column j outer, then the two triangular solves: the order include/hfpf.h states.
@@ -2426,14 +2446,19 @@ static void track_update(double T[12], const double xi[6], const double c[3])
 }
 
 // Validated arguments in, under the lock: the model view once, then per iteration one k_track_reduce and the host solve.
-static int track_locked(hfpf_handle* h, const hfpf_track_opts* o, TrackFrame& f, const double pose[12], hfpf_track_result* res)
+static int track_locked(hfpf_handle* h, const hfpf_track_opts* o, const PointSource& f, const double pose[12], hfpf_track_result* res)
 {
+    // the sampling of include/hfpf.h, at most 2^26 points (the headroom of the int64 sums); cols: sampled columns of a depth image
+    const uint32_t stride = o->stride;
+    const uint32_t cols = f.depth ? (f.ds.width + stride - 1) / stride : 0u;
+    const uint64_t n_samples = f.depth ? (uint64_t)cols * ((f.ds.height + stride - 1) / stride) : ((uint64_t)f.n + stride - 1) / stride;
+    if (n_samples > (1ull << 26)) return fail(h, HFPF_ERR_BAD_ARG, "track: more than 2^26 sampled points");
     int rc;
     if ((rc = render_prelude_locked(h, "track"))) return rc;
     const uint8_t* frame = (const uint8_t*)f.dev;
     if (f.host) {  // one copy per call, through the pinned buffers
-        if ((rc = scratch(h, h->track_in, f.bytes()))) return rc;
-        const hipError_t e = upload_pageable(h, h->track_in.p, f.host, f.bytes());
+        if ((rc = scratch(h, h->track_in, f.bytes(f.n)))) return rc;
+        const hipError_t e = upload_pageable(h, h->track_in.p, f.host, f.bytes(f.n));
         if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "track upload: %s", hipGetErrorString(e));
         frame = (const uint8_t*)h->track_in.p;
     }
@@ -2449,14 +2474,14 @@ static int track_locked(hfpf_handle* h, const hfpf_track_opts* o, TrackFrame& f,
     p.max_d2 = o->max_distance * o->max_distance;
     p.zc_lo = h->g.zc_lo, p.zc_hi = h->g.zc_hi;
     p.width = o->view.width, p.height = o->view.height;
-    p.n_samples = (uint32_t)f.n_samples;
-    p.stride = o->stride;
-    p.cols = f.cols;
-    p.n_points = f.n_points;
+    p.n_samples = (uint32_t)n_samples;
+    p.stride = stride;
+    p.cols = cols;
+    p.n_points = f.n;
     const double c[3] = {pose[3], pose[7], pose[11]};
-    const bool packed = !f.depth && f.lay.point_step == 16 && f.lay.off_x == 0 && f.lay.off_y == 4 && f.lay.off_z == 8 && ((uintptr_t)frame & 15) == 0;
+    const int form = f.form(frame);
     const DepthLayout dl = depth_layout(f.ds, nullptr, 0);
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(kTrackMaxBlocks, blocks_for(f.n_samples, 256));
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(kTrackMaxBlocks, blocks_for(n_samples, 256));
     const Row* rows = (const Row*)h->rows_dev.p;
     const unsigned long long* zb = (const unsigned long long*)h->zbuf.p;
     unsigned long long* acc = (unsigned long long*)h->track_acc.p;
@@ -2471,12 +2496,9 @@ static int track_locked(hfpf_handle* h, const hfpf_track_opts* o, TrackFrame& f,
         it++;
         memcpy(p.T, T, sizeof p.T);
         HIPCHK(h, hipMemsetAsync(acc, 0, kTrackTerms * sizeof(unsigned long long), h->stream));
-        if (f.depth)
-            hipLaunchKernelGGL((k_track_reduce<false, true>), dim3(blocks), dim3(256), 0, h->stream, p, frame, dl, rows, zb, acc);
-        else if (packed)
-            hipLaunchKernelGGL((k_track_reduce<true, false>), dim3(blocks), dim3(256), 0, h->stream, p, frame, f.lay, rows, zb, acc);
-        else
-            hipLaunchKernelGGL((k_track_reduce<false, false>), dim3(blocks), dim3(256), 0, h->stream, p, frame, f.lay, rows, zb, acc);
+        with_form(form, [&](auto F) {
+            hipLaunchKernelGGL((k_track_reduce<F>), dim3(blocks), dim3(256), 0, h->stream, p, frame, form_layout<F>(f.lay, &dl), rows, zb, acc);
+        });
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipMemcpyAsync(back, acc, kTrackTerms * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2523,14 +2545,9 @@ static int track_depth_common(hfpf_handle* h, const hfpf_track_opts* o, const hf
     if (!h) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
     if (!track_opts_ok(o) || !track_args_ok(pose, res)) return fail(h, HFPF_ERR_BAD_ARG, "track: invalid options, pose or result");
-    TrackFrame f{};
-    // the colour fields are validated as integrate validates them, but no colour image is read
-    if (int rc = depth_spec(h, desc, depth, desc && desc->color_format != HFPF_COLOR_NONE ? depth : nullptr, &f.ds)) return rc;
-    f.ds.color_bpp = 0;
-    f.depth = true;
-    f.n_points = f.ds.width * f.ds.height;
+    PointSource f{};
+    if (int rc = colorless_depth_source(h, desc, depth, &f)) return rc;
     if (on_device && (uintptr_t)depth % (f.ds.depth_f32 ? 4u : 2u)) return fail(h, HFPF_ERR_BAD_ARG, "track_depth_device: the image must be aligned to the sample size");
-    if (!track_sample(f, o->stride)) return fail(h, HFPF_ERR_BAD_ARG, "track: more than 2^26 sampled points");
     (on_device ? f.dev : f.host) = depth;
     return track_locked(h, o, f, pose, res);
 }
@@ -2554,13 +2571,11 @@ int hfpf_track(hfpf_handle* h, const hfpf_track_opts* o, const void* base, uint3
     std::lock_guard<std::mutex> lk(h->mtx);
     if (!track_opts_ok(o) || !track_args_ok(pose_3x4, result)) return fail(h, HFPF_ERR_BAD_ARG, "track: invalid options, pose or result");
     if (!base || n_points == 0) return fail(h, HFPF_ERR_BAD_ARG, "track: null cloud or no points");
-    if ((point_step & 3) || (off_x & 3) || (off_y & 3) || (off_z & 3)) return fail(h, HFPF_ERR_BAD_ARG, "track: fields must be 4-byte aligned");
-    if (std::max({off_x, off_y, off_z}) + 4 > point_step) return fail(h, HFPF_ERR_BAD_ARG, "track: field offset beyond point_step");
-    TrackFrame f{};
+    PointSource f{};
     f.host = base;
     f.lay = FrameLayout{point_step, off_x, off_y, off_z, 0};
-    f.n_points = n_points;
-    if (!track_sample(f, o->stride)) return fail(h, HFPF_ERR_BAD_ARG, "track: more than 2^26 sampled points");
+    f.n = n_points;
+    if (int rc = check_cloud_layout(h, "track", f.lay, false)) return rc;
     return track_locked(h, o, f, pose_3x4, result);
 }
 
@@ -2572,30 +2587,12 @@ static bool query_args_ok(const hfpf_query_opts* o, const double* pose)
     if (!o || o->struct_size != sizeof(hfpf_query_opts) || o->reserved0 != 0 || o->reserved != 0) return false;
     if ((o->flags & ~HFPF_QUERY_ZCLIP) || o->radius < 0 || o->radius > kQueryMaxRadius) return false;
     if (std::isnan(o->min_count) || !(o->max_distance > 0.0)) return false;
-    if (!pose) return false;
-    for (int k = 0; k < 12; k++)
-        if (!std::isfinite(pose[k])) return false;
-    return true;
+    return pose_ok(pose);
 }
-
-// The points of a query: a depth image (ds) or a cloud (lay, n), in host memory or on the device.
-struct QueryFrame {
-    const void* host;
-    const void* dev;
-    bool depth;
-    DepthSpec ds;
-    FrameLayout lay;
-    uint32_t n;
-    size_t cloud_bytes(uint32_t n_pts) const { return (size_t)(n_pts - 1) * lay.point_step + std::max({lay.off_x, lay.off_y, lay.off_z}) + 4; }
-    bool packed(const void* base) const
-    {
-        return !depth && lay.point_step == 16 && lay.off_x == 0 && lay.off_y == 4 && lay.off_z == 8 && ((uintptr_t)base & 15) == 0;
-    }
-};
 
 // Validated arguments in, under the lock.  The device form is one launch into the caller's buffers; the host forms run chunks of
 // kQueryChunk points through h->query_out and download each through the pinned buffers.
-static int query_locked(hfpf_handle* h, const hfpf_query_opts* o, const QueryFrame& f, const double pose[12], hfpf_query_hit* hits, hfpf_row* rows)
+static int query_locked(hfpf_handle* h, const hfpf_query_opts* o, const PointSource& f, const double pose[12], hfpf_query_hit* hits, hfpf_row* rows)
 {
     int rc;
     if ((rc = render_prelude_locked(h, "query"))) return rc;
@@ -2606,17 +2603,14 @@ static int query_locked(hfpf_handle* h, const hfpf_query_opts* o, const QueryFra
     p.max_d2 = o->max_distance * o->max_distance;
     p.radius = o->radius;
     p.zclip = (o->flags & HFPF_QUERY_ZCLIP) ? 1u : 0u;
-    const DepthLayout dl = f.depth ? depth_layout(f.ds, nullptr, 0) : DepthLayout{};
+    const DepthLayout dl = depth_layout(f.ds, nullptr, 0);
     auto launch = [&](const uint8_t* frame, uint64_t first, uint32_t n, QueryHit* dh, Row* dr) -> int {
         p.first = first;
         p.n = n;
         const dim3 grid(blocks_for(n, 256));
-        if (f.depth)
-            hipLaunchKernelGGL((k_query<kQueryDepth>), grid, dim3(256), 0, h->stream, h->g, h->t, p, frame, dl, dh, dr);
-        else if (f.packed(frame))
-            hipLaunchKernelGGL((k_query<kQueryPacked16>), grid, dim3(256), 0, h->stream, h->g, h->t, p, frame, f.lay, dh, dr);
-        else
-            hipLaunchKernelGGL((k_query<kQueryStrided>), grid, dim3(256), 0, h->stream, h->g, h->t, p, frame, f.lay, dh, dr);
+        with_form(f.form(frame), [&](auto F) {
+            hipLaunchKernelGGL((k_query<F>), grid, dim3(256), 0, h->stream, h->g, h->t, p, frame, form_layout<F>(f.lay, &dl), dh, dr);
+        });
         HIPCHK(h, hipGetLastError());
         return HFPF_OK;
     };
@@ -2629,18 +2623,16 @@ static int query_locked(hfpf_handle* h, const hfpf_query_opts* o, const QueryFra
     if ((rc = scratch(h, h->query_out, (size_t)chunk * (sizeof(QueryHit) + (rows ? sizeof(Row) : 0))))) return rc;
     QueryHit* dh = (QueryHit*)h->query_out.p;
     Row* dr = rows ? (Row*)((char*)h->query_out.p + (size_t)chunk * sizeof(QueryHit)) : nullptr;
+    if ((rc = scratch(h, h->query_in, f.bytes(chunk)))) return rc;
     if (f.depth) {  // the whole image once; the chunks index into it
-        if ((rc = scratch(h, h->query_in, f.ds.depth_bytes()))) return rc;
-        const hipError_t e = upload_pageable(h, h->query_in.p, f.host, f.ds.depth_bytes());
+        const hipError_t e = upload_pageable(h, h->query_in.p, f.host, f.bytes(f.n));
         if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "query upload: %s", hipGetErrorString(e));
-    } else if ((rc = scratch(h, h->query_in, f.cloud_bytes(chunk)))) {
-        return rc;
     }
     for (uint64_t first = 0; first < f.n; first += chunk) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, f.n - first);
         uint64_t k_first = first;
         if (!f.depth) {  // this chunk's records
-            const hipError_t e = upload_pageable(h, h->query_in.p, (const uint8_t*)f.host + first * f.lay.point_step, f.cloud_bytes(n));
+            const hipError_t e = upload_pageable(h, h->query_in.p, (const uint8_t*)f.host + first * f.lay.point_step, f.bytes(n));
             if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "query upload: %s", hipGetErrorString(e));
             k_first = 0;
         }
@@ -2659,13 +2651,12 @@ static int query_cloud_common(hfpf_handle* h, const hfpf_query_opts* o, const vo
     std::lock_guard<std::mutex> lk(h->mtx);
     if (!query_args_ok(o, pose)) return fail(h, HFPF_ERR_BAD_ARG, "query: invalid options or pose");
     if (n_points && (!base || !hits)) return fail(h, HFPF_ERR_BAD_ARG, "query: null cloud or hits");
-    if ((point_step & 3) || (off_x & 3) || (off_y & 3) || (off_z & 3)) return fail(h, HFPF_ERR_BAD_ARG, "query: fields must be 4-byte aligned");
-    if (std::max({off_x, off_y, off_z}) + 4 > point_step) return fail(h, HFPF_ERR_BAD_ARG, "query: field offset beyond point_step");
+    PointSource f{};
+    f.lay = FrameLayout{point_step, off_x, off_y, off_z, 0};
+    if (int rc = check_cloud_layout(h, "query", f.lay, false)) return rc;
     if (on_device && (((uintptr_t)base & 3) || ((uintptr_t)hits & 15) || ((uintptr_t)rows & 15)))
         return fail(h, HFPF_ERR_BAD_ARG, "query_device: the cloud must be 4-byte and hits / rows 16-byte aligned");
-    QueryFrame f{};
     (on_device ? f.dev : f.host) = base;
-    f.lay = FrameLayout{point_step, off_x, off_y, off_z, 0};
     f.n = n_points;
     return query_locked(h, o, f, pose, hits, rows);
 }
@@ -2688,13 +2679,9 @@ int hfpf_query_depth(hfpf_handle* h, const hfpf_query_opts* o, const hfpf_depth_
     if (!h) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
     if (!query_args_ok(o, pose_3x4) || !hits) return fail(h, HFPF_ERR_BAD_ARG, "query: invalid options, pose or hits");
-    QueryFrame f{};
-    // the colour fields are validated as integrate validates them, but no colour image is read
-    if (int rc = depth_spec(h, desc, depth, desc && desc->color_format != HFPF_COLOR_NONE ? depth : nullptr, &f.ds)) return rc;
-    f.ds.color_bpp = 0;
-    f.depth = true;
+    PointSource f{};
+    if (int rc = colorless_depth_source(h, desc, depth, &f)) return rc;
     f.host = depth;
-    f.n = f.ds.width * f.ds.height;
     return query_locked(h, o, f, pose_3x4, hits, rows);
 }
 

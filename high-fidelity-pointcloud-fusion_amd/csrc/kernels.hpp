@@ -66,6 +66,34 @@ __device__ __forceinline__ vf4 depth_fetch(const uint8_t* __restrict__ dimg, con
     return vf4{__uint_as_float(raw), __uint_as_float(rgb), __uint_as_float(u), __uint_as_float(v)};
 }
 
+// Camera-frame point of a fetched depth pixel (depth_fetch's (raw, rgb, u, v)).
+__device__ __forceinline__ F3 depth_point(const DepthLayout& L, const vf4 r)
+{
+    return depth_backproject(__float_as_uint(r.z), __float_as_uint(r.w), __float_as_uint(r.x), L.depth_f32 != 0, L.cx, L.cy, L.sx, L.sy, L.unit);
+}
+
+// The three forms an input frame takes (the host picks one per launch): 16-byte (x, y, z, rgb) records, records of any
+// FrameLayout, or a registered depth image (DepthLayout).
+enum PointForm : int { kFormPacked16 = 0, kFormStrided = 1, kFormDepth = 2 };
+template <int FORM>
+using PointLayout = std::conditional_t<FORM == kFormDepth, DepthLayout, FrameLayout>;
+
+// Camera-frame x, y, z of point i of a frame (the colour is not read): record i, or pixel i back-projected.
+template <int FORM>
+__device__ __forceinline__ F3 load_point(const uint8_t* __restrict__ frame, const PointLayout<FORM>& lay, const uint64_t i)
+{
+    if constexpr (FORM == kFormDepth) {
+        return depth_point(lay, depth_fetch<false>(frame, nullptr, lay, (uint32_t)i));
+    } else if constexpr (FORM == kFormPacked16) {
+        const vf4 r = reinterpret_cast<const vf4*>(frame)[i];
+        return F3{r.x, r.y, r.z};
+    } else {
+        const uint8_t* rec = frame + i * lay.point_step;
+        return F3{*reinterpret_cast<const float*>(rec + lay.off_x), *reinterpret_cast<const float*>(rec + lay.off_y),
+                  *reinterpret_cast<const float*>(rec + lay.off_z)};
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // K1.  Persistent grid: block b walks tiles b, b+gridDim.x, ... of 256 consecutive points; a tile never
 // straddles two frames, so the pose stays in scalar registers.  Loop trip counts are wave-uniform, which
@@ -324,8 +352,9 @@ __device__ __forceinline__ const Tables& kernarg_tables()
 #ifndef HFPF_INT_WAVES_BIN
 #define HFPF_INT_WAVES_BIN 7
 #endif
-// Three input forms: PACKED16 (x, y, z, rgb as 16-byte records), the generic FrameLayout loader, and DEPTH (registered depth +
-// colour images, DepthLayout: each lane reads its pixel's samples and back-projects them in registers, depth_backproject).
+// The three PointForms as two switches: PACKED16 = kFormPacked16, DEPTH = kFormDepth (each lane reads its pixel's samples and
+// back-projects them in registers, depth_point), neither = kFormStrided.  The point and its colour are read here, not through
+// load_point: the next tile's record or pixel is fetched ahead of this tile's table lookups, and the colour is needed too.
 template <bool PACKED16, bool COLOR, bool BIN, bool DEPTH = false>
 __global__ __launch_bounds__(256, BIN ? HFPF_INT_WAVES_BIN : HFPF_INT_WAVES) void k_integrate(const IntegrateArgs A, const uint8_t* __restrict__ frames,
                                                    const uint64_t frame_stride, const uint32_t n_pts, const uint32_t n_frames,
@@ -415,8 +444,7 @@ __global__ __launch_bounds__(256, BIN ? HFPF_INT_WAVES_BIN : HFPF_INT_WAVES) voi
         uint32_t rgb = 0;
         if (act) {
             if constexpr (DEPTH) {
-                const F3 c = depth_backproject(__float_as_uint(nv.z), __float_as_uint(nv.w), __float_as_uint(nv.x), lay.depth_f32 != 0, lay.cx,
-                                               lay.cy, lay.sx, lay.sy, lay.unit);
+                const F3 c = depth_point(lay, nv);
                 x = c.x;
                 y = c.y;
                 z = c.z;
@@ -2293,13 +2321,12 @@ __device__ __forceinline__ const TrackParams& track_kernarg()
     return *(const TrackParams*)p;
 }
 
-// One sampled point per thread, grid-stride over at most kTrackMaxBlocks blocks.  Input forms as k_integrate: PACKED16 (16-byte x,
-// y, z, rgb records), the generic FrameLayout loader, DEPTH (u16 or f32 depth image, sub-dword loads, back-projected in
-// registers).  Each thread keeps its 30 sums in registers; the block reduces them (DPP across the wave, LDS across the four
-// waves) and adds them to acc with one 64-bit atomic each.  acc is zeroed by the host before the launch.
-template <bool PACKED16, bool DEPTH>
-__global__ __launch_bounds__(256) void k_track_reduce(const TrackParams p, const uint8_t* __restrict__ frame,
-                                                      const std::conditional_t<DEPTH, DepthLayout, FrameLayout> lay,
+// One sampled point per thread, grid-stride over at most kTrackMaxBlocks blocks, in any PointForm (load_point).  Sample s is pixel
+// (su * stride, sv * stride) of a depth image, record s * stride of a cloud.  Each thread keeps its 30 sums in registers; the
+// block reduces them (DPP across the wave, LDS across the four waves) and adds them to acc with one 64-bit atomic each.  acc is
+// zeroed by the host before the launch.
+template <int FORM>
+__global__ __launch_bounds__(256) void k_track_reduce(const TrackParams p, const uint8_t* __restrict__ frame, const PointLayout<FORM> lay,
                                                       const Row* __restrict__ rows, const unsigned long long* __restrict__ zbuf,
                                                       unsigned long long* __restrict__ acc)
 {
@@ -2308,22 +2335,13 @@ __global__ __launch_bounds__(256) void k_track_reduce(const TrackParams p, const
 #pragma unroll
     for (int k = 0; k < kTrackTerms; k++) sum[k] = 0;
     for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < p.n_samples; s += gridDim.x * blockDim.x) {
-        float x, y, z;
-        if constexpr (DEPTH) {
+        uint64_t i = (uint64_t)s * p.stride;
+        if constexpr (FORM == kFormDepth) {
             const uint32_t sv = s / p.cols, su = s - sv * p.cols;
-            const uint32_t u = su * p.stride, v = sv * p.stride;
-            const vf4 r = depth_fetch<false>(frame, nullptr, lay, v * lay.width + u);
-            const F3 c = depth_backproject(u, v, __float_as_uint(r.x), lay.depth_f32 != 0, lay.cx, lay.cy, lay.sx, lay.sy, lay.unit);
-            x = c.x, y = c.y, z = c.z;
-        } else if constexpr (PACKED16) {
-            const vf4 r = reinterpret_cast<const vf4*>(frame)[(uint64_t)s * p.stride];
-            x = r.x, y = r.y, z = r.z;
-        } else {
-            const uint8_t* rec = frame + (uint64_t)s * p.stride * lay.point_step;
-            x = *reinterpret_cast<const float*>(rec + lay.off_x);
-            y = *reinterpret_cast<const float*>(rec + lay.off_y);
-            z = *reinterpret_cast<const float*>(rec + lay.off_z);
+            i = (sv * p.stride) * lay.width + su * p.stride;
         }
+        const F3 c = load_point<FORM>(frame, lay, i);
+        const float x = c.x, y = c.y, z = c.z;
         if (!(__builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z) && z < p.zc_hi && z > p.zc_lo)) continue;
         sum[29] += 1;
         const TrackParams& P = track_kernarg();
@@ -2381,15 +2399,14 @@ __global__ __launch_bounds__(256) void k_track_reduce(const TrackParams p, const
 
 
 // ---- point queries (hfpf_query*, include/hfpf.h) ----------------------------------------------------------------------
-// One lane per point: load and transform it as integrate does, read its own cell's occupancy bit, then walk the rows of the
-// (2r+1)^3 window around its voxel.  r <= 4 makes the window span at most two bricks per axis: at most 8 directory words, and per
-// x-plane of a touched brick one nd_mask normal_found word ANDed with the window's (y, z) mask; the set bits are the cells with a
-// record, stat_id names it.  Candidates are the rows extract would emit (valid cell, count >= max(1, min_count): the compare of
-// k_extract_keys) and their centroid is record_centroid's, so the distances are those of the extracted rows.  The winner is the
-// smallest d2 and then the smallest (x, y, z) key, independent of the walk order.
+// One lane per point of any PointForm (load_point): transform it as integrate does, read its own cell's occupancy bit, then walk
+// the rows of the (2r+1)^3 window around its voxel.  r <= 4 makes the window span at most two bricks per axis: at most 8
+// directory words, and per x-plane of a touched brick one nd_mask normal_found word ANDed with the window's (y, z) mask; the set
+// bits are the cells with a record, stat_id names it.  Candidates are the rows extract would emit (valid cell, count >= max(1,
+// min_count): the compare of k_extract_keys) and their centroid is record_centroid's, so the distances are those of the extracted
+// rows.  The winner is the smallest d2 and then the smallest (x, y, z) key, independent of the walk order.
 constexpr uint32_t kQHitUsed = 1u, kQHitInBbox = 2u, kQHitOccupied = 4u, kQHitHasRow = 8u, kQHitFound = 16u;
 constexpr int kQueryMaxRadius = 4;
-enum QueryForm : int { kQueryPacked16 = 0, kQueryStrided = 1, kQueryDepth = 2 };
 
 struct __attribute__((aligned(16))) QueryHit {  // = hfpf_query_hit
     int32_t voxel[3];
@@ -2423,27 +2440,12 @@ __device__ __forceinline__ uint64_t plane_window(int ya, int yb, int za, int zb)
 
 template <int FORM>
 __global__ __launch_bounds__(256) void k_query(const GridParams g, const Tables t, const QueryParams p, const uint8_t* __restrict__ frame,
-                                               const std::conditional_t<FORM == kQueryDepth, DepthLayout, FrameLayout> lay,
-                                               QueryHit* __restrict__ hits, Row* __restrict__ rows)
+                                               const PointLayout<FORM> lay, QueryHit* __restrict__ hits, Row* __restrict__ rows)
 {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= p.n) return;
-    const uint64_t i = p.first + k;
-    float x, y, z;
-    if constexpr (FORM == kQueryDepth) {
-        const vf4 r = depth_fetch<false>(frame, nullptr, lay, (uint32_t)i);
-        const F3 c = depth_backproject(__float_as_uint(r.z), __float_as_uint(r.w), __float_as_uint(r.x), lay.depth_f32 != 0, lay.cx, lay.cy,
-                                       lay.sx, lay.sy, lay.unit);
-        x = c.x, y = c.y, z = c.z;
-    } else if constexpr (FORM == kQueryPacked16) {
-        const vf4 r = reinterpret_cast<const vf4*>(frame)[i];
-        x = r.x, y = r.y, z = r.z;
-    } else {
-        const uint8_t* rec = frame + i * lay.point_step;
-        x = *reinterpret_cast<const float*>(rec + lay.off_x);
-        y = *reinterpret_cast<const float*>(rec + lay.off_y);
-        z = *reinterpret_cast<const float*>(rec + lay.off_z);
-    }
+    const F3 c = load_point<FORM>(frame, lay, p.first + k);
+    const float x = c.x, y = c.y, z = c.z;
     const float qnan = __builtin_bit_cast(float, 0x7FC00000u);
     QueryHit h;
     h.voxel[0] = h.voxel[1] = h.voxel[2] = INT_MIN;
@@ -2671,7 +2673,7 @@ __global__ void k_probe_depth(const DepthLayout L, const uint8_t* __restrict__ d
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const vf4 r = depth_fetch<true>(dimg, L.color, L, i);
-    const F3 c = depth_backproject(__float_as_uint(r.z), __float_as_uint(r.w), __float_as_uint(r.x), L.depth_f32 != 0, L.cx, L.cy, L.sx, L.sy, L.unit);
+    const F3 c = depth_point(L, r);
     xyz_out[3 * (uint64_t)i] = c.x;
     xyz_out[3 * (uint64_t)i + 1] = c.y;
     xyz_out[3 * (uint64_t)i + 2] = c.z;

@@ -75,6 +75,17 @@ def _same_result(got, ref, what):
     assert r["information"].tobytes() == np.asarray(ref["information"], np.float64).tobytes(), "%s: information" % what
 
 
+def _wide(cloud):
+    """The records of a packed cloud in a 32-byte layout with x, y, z behind a pad word: the generic loader."""
+    wide = np.zeros((cloud.nbytes // 16, 8), np.uint32)
+    wide[:, 1:4] = cloud.view(np.uint32).reshape(-1, 4)[:, :3]
+    return wide.view(np.uint8).reshape(-1)
+
+
+PACKED = dict(point_step=16, off_x=0, off_y=4, off_z=8)
+WIDE = dict(point_step=32, off_x=4, off_y=8, off_z=12)
+
+
 def _bytes(res):
     pose, r = res
     return pose.tobytes() + r["information"].tobytes() + np.float64(r["rms"]).tobytes() + bytes(
@@ -93,14 +104,22 @@ def session(hfpf_mod, synth_mod):
 
 # ---- 1. bit-exact against the numpy contract -------------------------------------------------------------------------
 
-@pytest.mark.parametrize("stride,fmt", [(1, "u16"), (2, "f32"), (2, "u16"), (1, "f32")])
+# fmt: a u16 or f32 depth image, or the same points as a packed or a 32-byte-record cloud (sampled as record i % stride == 0)
+@pytest.mark.parametrize("stride,fmt", [(1, "u16"), (2, "f32"), (2, "u16"), (1, "f32"), (2, "packed"), (2, "wide")])
 def test_bit_exact_against_track_ref(hfpf_mod, synth_mod, session, stride, fmt):
     sc, g, rows = session
     depth, K, true = _held_out(synth_mod)
-    img = depth if fmt == "u16" else _as_f32(depth)
     guess = _perturb(true, 2.0, (0.006, -0.005, 0.006))  # 1 cm, 2 degrees
-    got = g.track_depth(img, guess, K, stride=stride, **OPTS)
-    ref = _ref(rows, TR.depth_points(img, K, stride), guess, K, 640, 480)
+    if fmt in ("u16", "f32"):
+        img = depth if fmt == "u16" else _as_f32(depth)
+        got = g.track_depth(img, guess, K, stride=stride, **OPTS)
+        ref = _ref(rows, TR.depth_points(img, K, stride), guess, K, 640, 480)
+    else:
+        cloud = depth_ref.packed_cloud(depth, K)
+        xyz = cloud.view(np.float32).reshape(-1, 4)[:, :3]
+        got = g.track(cloud if fmt == "packed" else _wide(cloud), PACKED if fmt == "packed" else WIDE, guess, K, 640, 480,
+                      stride=stride, **OPTS)
+        ref = _ref(rows, TR.cloud_points(xyz, stride), guess, K, 640, 480)
     print("stride %d %s: %d iterations, flags %d, %d of %d used points inliers, rms %.2e, error %s -> %s" % (
         stride, fmt, got[1]["iterations"], got[1]["flags"], got[1]["inliers"], got[1]["points_used"], got[1]["rms"],
         _errors(guess, true), _errors(got[0], true)))
@@ -148,11 +167,8 @@ def test_cloud_host_and_device_depth_agree(hfpf_mod, synth_mod, session):
     guess = _perturb(true, 1.0, (0.004, 0.004, -0.004))
     a = g.track_depth(depth, guess, K, **OPTS)
     cloud = depth_ref.packed_cloud(depth, K)
-    b = g.track(cloud, dict(point_step=16, off_x=0, off_y=4, off_z=8), guess, K, 640, 480, **OPTS)
-    # the same records in a 32-byte layout with x, y, z behind a pad word: the generic loader
-    wide = np.zeros((640 * 480, 8), np.uint32)
-    wide[:, 1:4] = cloud.view(np.uint32).reshape(-1, 4)[:, :3]
-    c = g.track(wide.view(np.uint8).reshape(-1), dict(point_step=32, off_x=4, off_y=8, off_z=12), guess, K, 640, 480, **OPTS)
+    b = g.track(cloud, PACKED, guess, K, 640, 480, **OPTS)
+    c = g.track(_wide(cloud), WIDE, guess, K, 640, 480, **OPTS)
     desc = hfpf_mod.depth_desc(640, 480, hfpf_mod.DEPTH_U16, 640 * 2, K)
     ptr = g.device_alloc(depth.nbytes)
     try:
