@@ -13,8 +13,14 @@ W warm-up steps run the same schedule untimed; the grid is cleared before every 
 
 Timing protocol: frames are pre-staged in HBM before the clock starts; the K-step stream is timed
 --repeats times (clear between), each pass bracketed by barrier + device sync, max over ranks; `value` is the MEDIAN
-pass, min/max are reported beside it.  Extract is timed separately (`extract_s`), so is the host-buffer entry point
-(`host_path_mpts`, PCIe inclusive, never `value`).
+pass, min/max are reported beside it.  With --full, extract is timed separately (`extract_s`), so is the host-buffer entry
+point (`host_path_mpts`, PCIe inclusive, never `value`).
+
+A plain run does only what `value` needs: it stages the frames, warms up, times the passes, dumps (--dump-outputs) and prints
+the line, with the roofline of the timed passes and the counters of the last one.  --full adds the measurements that take runs
+of their own: the per-kernel breakdown pass (roofline.kernels / compute_integrate), extract (`extract_s`; `rows_extracted`
+also with --dump-outputs), the output writers (--write-dir), the host-buffer entry point and the CPU oracle baselines
+(`cpu_baseline*`).
 
 --dump-outputs DIR writes what the last timed pass computed (extracted rows, occupied cells) as DIR/<name>.npy; the inputs are
 seeded, so two builds run with the same arguments can be compared output for output.
@@ -184,13 +190,16 @@ def main():
     ap.add_argument("--clean-every-steps", type=int, default=3, help="clean pass every this many steps (3 x 50 frames = 150 frames ~ 5 s at 30 Hz) + final clean")
     ap.add_argument("--repeats", type=int, default=10, help="timed passes over the K-step stream (median reported; SURVEY 8(d): n >= 10)")
     ap.add_argument("--frames-per-call", type=int, default=0, help="frames handed to one hfpf_integrate_device call (0 = one clean epoch)")
-    ap.add_argument("--cpu-sample", type=int, default=48, help="frames timed on the CPU oracle, sparse and all-cores variants (0 = skip all CPU legs)")
-    ap.add_argument("--cpu-sample-faithful", type=int, default=24, help="frames timed on the faithful variant (dense voxel array + reserve(1000); ~0.4 s per frame on the GPU box)")
-    ap.add_argument("--write-dir", default=None, help="also time writing test_cloud.pcd (ASCII + binary) and meta.csv there")
-    ap.add_argument("--host-path-frames", type=int, default=200, help="frames also pushed through the host-buffer entry point (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also run the measurements beyond `value`: per-kernel breakdown pass, extract, host-buffer entry point, CPU baselines")
+    ap.add_argument("--cpu-sample", type=int, default=48, help="--full: frames timed on the CPU oracle, sparse and all-cores variants (0 = skip all CPU legs)")
+    ap.add_argument("--cpu-sample-faithful", type=int, default=24, help="--full: frames timed on the faithful variant (dense voxel array + reserve(1000); ~0.4 s per frame on an MI355X host)")
+    ap.add_argument("--write-dir", default=None, help="--full: also time writing test_cloud.pcd (ASCII + binary) and meta.csv there")
+    ap.add_argument("--host-path-frames", type=int, default=200, help="--full: frames also pushed through the host-buffer entry point (0 = skip)")
     ap.add_argument("--allow-host-staged", action="store_true", help="rehearsals with several ranks on ONE GPU: fall back to the gloo host-staged transport when RCCL cannot form a communicator")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the extracted rows and occupied cells of the last timed pass as DIR/<name>.npy (untimed)")
     args = ap.parse_args()
+    if args.write_dir and not args.full:
+        ap.error("--write-dir times the output writers after an extract: it needs --full")
     global W, H, NPTS, BBOX, RES
     wl = WORKLOADS[args.workload]
     W, H, BBOX, RES = wl["W"], wl["H"], wl["bbox"], wl["res"]
@@ -256,7 +265,7 @@ def main():
     dev = grid.device_alloc(n_gen * frame_bytes)
     buf = np.empty(frame_bytes, dtype=np.uint8)
     host_frames = []
-    n_host = min(args.host_path_frames, n_gen) if (rank == 0 and world == 1) else 0
+    n_host = min(args.host_path_frames, n_gen) if (args.full and rank == 0 and world == 1) else 0
     pinned = grid.host_alloc(n_host * frame_bytes) if n_host else None  # the same frames in page-locked memory (zero-copy entry point)
     for f in range(n_gen):
         S.frame(seed, f, W, H, poses[f].reshape(3, 4), out=buf)
@@ -313,15 +322,17 @@ def main():
     clean_ms, clean_passes = grid.kernel_time(1)
     grid.kernel_timing(False)
     ctr = grid.counters()  # of the last pass (the grid is cleared between passes)
+    n_rows = None
     if args.dump_outputs:
         last_rows = grid.extract()  # every rank: a collective with several ranks
+        n_rows = len(last_rows)
         if rank == 0:
             dump_outputs(args.dump_outputs, last_rows, grid.occupied())
         del last_rows
 
-    # ---- one more pass, untimed, with an event pair around every kernel of every integrate call: the per-kernel breakdown ----
+    # ---- --full: one more pass, untimed, with an event pair around every kernel of every integrate call: the per-kernel breakdown ----
     per_kernel = None
-    if True:  # every rank: the clean passes inside are collectives
+    if args.full:  # every rank: the clean passes inside are collectives
         grid.clear()
         grid.sync()
         names = (("k_integrate", 2), ("k_update_cells", 3), ("k_buffer", 4))
@@ -342,11 +353,13 @@ def main():
         per_kernel = {name: (pk_first[name][0] + per_kernel_steady[name][0], pk_first[name][1] + per_kernel_steady[name][1]) for name, _ in names}
         grid.kernel_timing(False)
 
-    # ---- extract (timed separately) ----
-    t2 = time.perf_counter()
-    rows = grid.extract()
-    extract_s = time.perf_counter() - t2
-    write_times = None
+    # ---- --full: extract (timed separately) ----
+    extract_s = write_times = None
+    if args.full:
+        t2 = time.perf_counter()
+        rows = grid.extract()
+        extract_s = time.perf_counter() - t2
+        n_rows = len(rows)
     if rank == 0 and args.write_dir:
         os.makedirs(args.write_dir, exist_ok=True)
         tw0 = time.perf_counter()
@@ -499,17 +512,9 @@ def main():
             "value_min": round(total_pts / max(elapsed_all) / 1e6, 3),
             "value_max": round(total_pts / min(elapsed_all) / 1e6, 3),
             "pass_s": [round(e, 6) for e in elapsed_all],
-            "extract_s": round(extract_s, 5),
             "clean_s": round(clean_ms / 1e3 / R, 5),  # HIP-event time of the clean passes of ONE timed pass (inside the timed region)
             "clean_passes": int(round(clean_passes / R)),
-            "rows_extracted": int(len(rows)),
-            "write_times": write_times,
             "integrate_kernel_mpts": round(R * n_frames * NPTS / (k_ms / 1e3) / 1e6, 3) if k_ms > 0 else None,
-            "host_path_mpts": round(host_mpts, 3) if host_mpts else None,  # PCIe inclusive, one frame per call, never `value`
-            "host_path_pinned_mpts": round(host_pinned_mpts, 3) if host_pinned_mpts else None,
-            # one hipMemcpy of the same page-locked frames: the link's own rate on this box (the pinned path's ceiling: x / 16 B per point)
-            "host_link_GBps": round(host_link_gbps, 2) if host_link_gbps else None,
-            "host_path_frames": len(host_frames),
             "counters": {k: int(v) for k, v in ctr.items()},
             "warnings": warnings,
             "roofline": {"bound": "hbm", "kernel": "the integrate call (bin plan + k_integrate + k_update_cells + k_buffer), HIP events on the engine's stream around every call of the timed passes",
@@ -522,13 +527,26 @@ def main():
                          "avg_launch_ms": round(avg_launch_s * 1e3, 5),
                          # secondary ceiling: memory-side atomic requests, chip-wide 1.3 TB/s / 64 B (MI355X_MICROARCH.md);
                          # request counts from the same PMC passes, null when those are not of this build
-                         "kernels": kernels, "compute": compute, "compute_integrate": compute_integrate,
+                         "compute": compute,
                          "secondary": {"bound": "memory-side atomic requests", "unit": "Greq/s",
                                        "achieved": round(atomic_req / avg_launch_s / 1e9, 3) if atomic_req and avg_launch_s > 0 else None,
                                        "peak": round(1300.0 / 64.0, 3),
                                        "frac": round(atomic_req / avg_launch_s / 1e9 / (1300.0 / 64.0), 4) if atomic_req and avg_launch_s > 0 else None}},
         }
-        if args.cpu_sample > 0 and world == 1:  # rank 0 at N=1 only
+        if n_rows is not None:  # an extract ran (--dump-outputs or --full)
+            out["rows_extracted"] = int(n_rows)
+        if args.full:
+            out["roofline"].update(kernels=kernels, compute_integrate=compute_integrate)
+            out.update({
+                "extract_s": round(extract_s, 5),
+                "write_times": write_times,
+                "host_path_mpts": round(host_mpts, 3) if host_mpts else None,  # PCIe inclusive, one frame per call, never `value`
+                "host_path_pinned_mpts": round(host_pinned_mpts, 3) if host_pinned_mpts else None,
+                # one hipMemcpy of the same page-locked frames: the link's own rate on this box (the pinned path's ceiling: x / 16 B per point)
+                "host_link_GBps": round(host_link_gbps, 2) if host_link_gbps else None,
+                "host_path_frames": len(host_frames),
+            })
+        if args.full and args.cpu_sample > 0 and world == 1:  # rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(poses, seed, max(2, min(args.cpu_sample_faithful, args.cpu_sample, n_gen)), "faithful")
             out["cpu_baseline_sparse"] = cpu_baseline(poses, seed, min(args.cpu_sample, n_gen), "sparse")
             out["cpu_baseline_all_cores"] = cpu_baseline(poses, seed, min(args.cpu_sample, n_gen), "all_cores")

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_contract_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "2", "--full",
                           "--frames-per-step", "4", "--repeats", "3", "--cpu-sample", "2", "--host-path-frames", "2"], capture_output=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.strip()]
@@ -68,6 +68,33 @@ def test_bench_steps_and_dumped_outputs(tmp_path):
         assert np.array_equal(a, dumps[1][f]), f
 
 
+def test_bench_plain_run_is_lean_and_dumps_what_full_dumps(tmp_path):
+    """A plain run prints the headline line without the figures of the legs only --full runs (per-kernel breakdown, extract,
+    host path, CPU baselines); the two dump the same outputs of the last timed pass."""
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "1", "--frames-per-step", "4",
+            "--repeats", "2", "--cpu-sample", "2", "--host-path-frames", "2"]
+    lines, dumps = {}, {}
+    for mode in ("plain", "full"):
+        out = subprocess.run(args + ["--dump-outputs", str(tmp_path / mode)] + (["--full"] if mode == "full" else []),
+                             capture_output=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr.decode()[-2000:]
+        lines[mode] = json.loads(out.stdout.decode().strip())
+        dumps[mode] = {f: np.load(str(tmp_path / mode / f)) for f in sorted(os.listdir(str(tmp_path / mode)))}
+    p, f = lines["plain"], lines["full"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "repeats", "pass_s", "counters", "roofline"):
+        assert k in p, k
+    assert p["value"] > 0 and abs(p["ms_per_step"] * p["value"] * 1e3 - p["config"]["points_per_step"]) < 1e-2 * p["config"]["points_per_step"]
+    for k in ("extract_s", "write_times", "host_path_mpts", "host_path_frames", "cpu_baseline", "cpu_baseline_sparse", "vs_cpu_baseline"):
+        assert k not in p and k in f, k
+    assert "kernels" not in p["roofline"] and "compute_integrate" not in p["roofline"] and f["roofline"]["kernels"]["k_integrate"]["calls"] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "repeats", "config", "counters", "rows_extracted"):
+        assert p[k] == f[k], k
+    assert p["rows_extracted"] > 0
+    assert sorted(dumps["plain"]) == sorted(dumps["full"])
+    for name, a in dumps["plain"].items():
+        assert np.array_equal(a, dumps["full"][name]), name
+
+
 def test_bench_two_ranks_one_line_on_stdout():
     """Launched the way the driver launches N > 1 (one rank per GPU; here both ranks share the one GPU, so the RCCL
     communicator is refused and the ranks agree to fall back to the host-staged transport).  Gloo and RCCL print banners on
@@ -75,7 +102,7 @@ def test_bench_two_ranks_one_line_on_stdout():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "2",
-                          "--frames-per-step", "4", "--repeats", "2"],
+                          "--frames-per-step", "4", "--repeats", "2", "--full"],
                          capture_output=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.strip()]

@@ -2,12 +2,12 @@
 """Summarise the rocprofv3 --pmc passes of tools/pmc_passes.sh (one counter set per pass, as MI355X_MICROARCH.md prescribes) for
 the integrate hot path: k_integrate (decode / clip / transform / insert / park) + k_update (per-brick LDS accumulation).
 
-usage: python tools/pmc_summary.py gpurun_out/<mem prefix> profiles/r04_pmc_hot_path [gpurun_out/<sq prefix>] [--workload c3]
+usage: python tools/pmc_summary.py out/<mem prefix> profiles/r04_pmc_hot_path [out/<sq prefix>] [--workload c3]
 (the optional third argument adds the SQ counters of k_update_cells and k_integrate -- instruction counts, active lanes, LDS bank
 conflicts -- as section "sq", which bench.py turns into roofline.compute and roofline.compute_integrate; --workload c3: the passes
 ran `bench.py --workload c3`, i.e. 100 frames of 2048x1536 in calls of 15 -- the same dispatch pattern at another size)
 
-Each pass ran `bench.py --repeats 1 --warmup 0 --cpu-sample 0 --host-path-frames 0`: the 1000-frame configs[1] stream, one
+Each pass ran `bench.py --full --repeats 1 --warmup 0 --cpu-sample 0 --host-path-frames 0`: the 1000-frame configs[1] stream, one
 hfpf_integrate_device call per clean epoch.  k_integrate dispatches: #0 = the dry run of the session's first 8 frames (bin
 demand), #1 = the first epoch (everything is buffered, no dependant exists yet), #2..#6 = steady state, 150 frames each (#7 is
 the 100-frame tail and is left out of the per-launch means); k_update dispatches #0..#4 belong to the steady launches;
@@ -107,7 +107,7 @@ def main():
             continue
     pts = FRAMES_PER_LAUNCH * NPTS
     res = {"source_sha": source_sha(), "points_per_launch": pts, "frames_per_launch": FRAMES_PER_LAUNCH,
-           "source": "rocprofv3 --pmc, separate passes (tools/pmc_passes.sh), bench.py --repeats 1 --warmup 0"}
+           "source": "rocprofv3 --pmc, separate passes (tools/pmc_passes.sh), bench.py --full --repeats 1 --warmup 0"}
     for phase, sel_a, sel_b, sel_c in (("first_epoch_buffer_only", lambda v: v[1:2], None, lambda v: v[:1]),
                                        ("steady_state_after_first_clean", lambda v: v[2:7], lambda v: v[:5], lambda v: v[1:6])):
         # k_integrate_overflow (one dispatch behind every k_integrate but the dry run) belongs to the integrate stage

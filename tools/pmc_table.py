@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Mean counter value per kernel launch from the passes of tools/pmc_passes.sh.
-usage: python tools/pmc_table.py gpurun_out/<prefix> [kernel-substring ...]
+usage: python tools/pmc_table.py out/<prefix> [kernel-substring ...]
 Steady-state launches only: of k_integrate the first two dispatches (dry run, first epoch) and the last (100-frame tail) are left
 out, of k_buffer the first (first epoch) and the last, of k_update the last; other kernels: all dispatches."""
 import collections
