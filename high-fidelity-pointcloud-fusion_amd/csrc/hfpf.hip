@@ -265,6 +265,9 @@ struct hfpf_handle {
     DevBuf zbuf, render_pose, render_out;  // hfpf_render*: z-buffers of one chunk of views, the views' poses, hfpf_render's device planes
     DevBuf track_in, track_acc;            // hfpf_track*: a host frame's device copy, the 30 int64 sums of one iteration
     DevBuf query_in, query_out;            // hfpf_query*: a host cloud chunk or depth image, one chunk's hits and rows
+    // hfpf_extract_mesh*: cube and corner keys, per corner s / record / marks / vertex counts and bases, per cube triangle counts and
+    // bases, the host form's output, a unique count
+    DevBuf mesh_cube, mesh_corner, mesh_kdata, mesh_cdata, mesh_out, mesh_ctr;
     unsigned long long* h_ctr = nullptr;  // pinned mirror of the counters
     unsigned long long* mbox = nullptr;   // coherent pinned mailbox k_publish_counters writes (HFPF_MAILBOX=0: blit copies + synchronize)
     unsigned long long mbox_seq = 0;
@@ -1616,7 +1619,8 @@ int hfpf_destroy(hfpf_handle* h)
     for (void* p : h->allocs) (void)hipFree(p);
     for (DevBuf* b : {&h->sort_tmp, &h->keys_a, &h->keys_b, &h->vals_a, &h->vals_b, &h->rows_dev, &h->probe_a, &h->probe_b, &h->probe_c, &h->probe_d,
                       &h->probe_e, &h->probe_f, &h->zbuf, &h->render_pose, &h->render_out, &h->track_in, &h->track_acc,
-                      &h->query_in, &h->query_out})
+                      &h->query_in, &h->query_out, &h->mesh_cube, &h->mesh_corner, &h->mesh_kdata, &h->mesh_cdata, &h->mesh_out,
+                      &h->mesh_ctr})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf* b : {&h->ex_send, &h->ex_recv, &h->ex_counts, &h->stats_total, &h->bin_pt_buf, &h->bin_rgb_buf, &h->bin_sums, &h->ovf_pt_buf, &h->ovf_aux_buf, &h->pend_a, &h->pend_b})
         if (b->p) (void)hipFree(b->p);
@@ -2087,6 +2091,19 @@ static hipError_t download_pageable(hfpf_handle* h, void* host, const void* dev,
     return e;
 }
 
+// A result array the caller will free(): 2 MB-aligned and advised as huge pages from 4 MB on (a fresh 125 MB result is then ~60 page
+// faults instead of 30,000 while it is filled), plain malloc below.
+static void* host_result_alloc(size_t want)
+{
+    void* mem = nullptr;
+    const size_t huge = (want + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1);
+    if (want >= (4u << 20) && posix_memalign(&mem, 2u << 20, huge) == 0) {
+        (void)madvise(mem, huge, MADV_HUGEPAGE);
+        return mem;
+    }
+    return malloc(want);
+}
+
 // Shared tail of extract: `stats` are the (possibly merged) sums to finalise.
 static int extract_locked(hfpf_handle* h, const unsigned long long* stats, const hfpf_extract_opts* o, hfpf_row** rows, uint64_t* n_rows)
 {
@@ -2099,18 +2116,7 @@ static int extract_locked(hfpf_handle* h, const unsigned long long* stats, const
     uint64_t nr = 0;
     if (int rc = build_rows_locked(h, stats, opt, &nr)) return rc;
     if (nr == 0) return HFPF_OK;
-    // (2 MB-aligned and advised as huge pages: a fresh 125 MB result is then ~60 page faults instead of 30,000 while it is filled)
-    hfpf_row* host = nullptr;
-    {
-        void* mem = nullptr;
-        const size_t want = nr * sizeof(hfpf_row);
-        if (want >= (4u << 20) && posix_memalign(&mem, 2u << 20, (want + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1)) == 0) {
-            (void)madvise(mem, (want + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1), MADV_HUGEPAGE);
-            host = (hfpf_row*)mem;
-        } else {
-            host = (hfpf_row*)malloc(want);
-        }
-    }
+    hfpf_row* host = (hfpf_row*)host_result_alloc(nr * sizeof(hfpf_row));
     if (!host) return fail(h, HFPF_ERR_CAPACITY, "extract: host allocation of %llu rows failed", (unsigned long long)nr);
     // The rows go to pageable memory the caller will free()
     const hipError_t e = download_pageable(h, host, h->rows_dev.p, nr * sizeof(Row));
@@ -2685,6 +2691,195 @@ int hfpf_query_depth(hfpf_handle* h, const hfpf_query_opts* o, const hfpf_depth_
     return query_locked(h, o, f, pose_3x4, hits, rows);
 }
 
+// ---- surface mesh (include/hfpf.h) ----------------------------------------------------------------------------------------
+int hfpf_check_mesh_opts(const hfpf_mesh_opts* o)
+{
+    if (!o || o->struct_size != sizeof(hfpf_mesh_opts) || o->flags != 0 || o->reserved != 0) return HFPF_ERR_BAD_ARG;
+    if (o->radius < 1 || o->radius > kQueryMaxRadius) return HFPF_ERR_BAD_ARG;
+    return !std::isnan(o->min_count) && o->max_distance > 0.0 ? HFPF_OK : HFPF_ERR_BAD_ARG;  // (a NaN max_distance fails the compare)
+}
+static bool mesh_opts_ok(const hfpf_mesh_opts* o) { return hfpf_check_mesh_opts(o) == HFPF_OK; }
+
+// One 1-D dilation of the sorted unique keys in[0, n_in): k_mesh_dilate into keys_a, sort into keys_b, unique into out.  in may be
+// out: scratch() synchronises before it reallocates, and the dilation has read in by then.
+static int mesh_dilate_locked(hfpf_handle* h, DevBuf& in, uint64_t n_in, int axis, int lo, int hi, int32_t lim, DevBuf& out, uint64_t* n_out)
+{
+    const uint64_t n = n_in * (uint64_t)(hi - lo + 1);
+    int rc;
+    if ((rc = scratch(h, h->keys_a, n * 8))) return rc;
+    if ((rc = scratch(h, h->keys_b, n * 8))) return rc;
+    hipLaunchKernelGGL(k_mesh_dilate, dim3(blocks_for(n_in, 256)), dim3(256), 0, h->stream, (const uint64_t*)in.p, n_in, axis, lo, hi, lim,
+                       (uint64_t*)h->keys_a.p);
+    HIPCHK(h, hipGetLastError());
+    unsigned xbits = 0;  // x <= dim[0]: the keys are below 2^(42 + xbits)
+    while ((uint32_t)h->g.dim[0] >> xbits) xbits++;
+    if ((rc = sort_keys_u64(h, (uint64_t*)h->keys_a.p, (uint64_t*)h->keys_b.p, n, 2 * kMeshKeyBits + xbits))) return rc;
+    if ((rc = scratch(h, out, n * 8))) return rc;
+    if ((rc = scratch(h, h->mesh_ctr, 16))) return rc;
+    const uint64_t* sorted = (const uint64_t*)h->keys_b.p;
+    size_t bytes = 0;
+    HIPCHK(h, rocprim::unique(nullptr, bytes, sorted, (uint64_t*)out.p, (uint64_t*)h->mesh_ctr.p, (size_t)n, rocprim::equal_to<uint64_t>(), h->stream));
+    if ((rc = scratch(h, h->sort_tmp, bytes))) return rc;
+    bytes = h->sort_tmp.bytes;
+    HIPCHK(h, rocprim::unique(h->sort_tmp.p, bytes, sorted, (uint64_t*)out.p, (uint64_t*)h->mesh_ctr.p, (size_t)n, rocprim::equal_to<uint64_t>(),
+                              h->stream));
+    uint64_t cnt = 0;
+    HIPCHK(h, hipMemcpyAsync(&cnt, h->mesh_ctr.p, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *n_out = cnt;
+    return HFPF_OK;
+}
+
+// out[0..n] = the exclusive sum of in[0..n] (in[n] = 0, so out[n] is the total, returned in *total).
+static int mesh_scan_locked(hfpf_handle* h, const uint32_t* in, uint32_t* out, uint64_t n, uint64_t* total)
+{
+    size_t bytes = 0;
+    HIPCHK(h, rocprim::exclusive_scan(nullptr, bytes, in, out, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), h->stream));
+    if (int rc = scratch(h, h->sort_tmp, bytes)) return rc;
+    bytes = h->sort_tmp.bytes;
+    HIPCHK(h, rocprim::exclusive_scan(h->sort_tmp.p, bytes, in, out, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), h->stream));
+    uint32_t t = 0;
+    HIPCHK(h, hipMemcpyAsync(&t, out + n, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *total = t;
+    return HFPF_OK;
+}
+
+// Validated arguments in, under the lock.  The row set, the cube set (the rows' cells dilated by 1) and the corner set (the cubes
+// dilated by (0, +1)), the corner samples, the edge marks and triangle counts, two scans, then vertices and triangles into device
+// arrays: new allocations for the device form, h->mesh_out for the host form.  The read-backs are the sizes between the stages.
+static int mesh_locked(hfpf_handle* h, const hfpf_mesh_opts* o, bool on_device, MeshVertex** verts, uint32_t** tris, uint64_t* n_verts,
+                       uint64_t* n_tris)
+{
+    *verts = nullptr, *tris = nullptr, *n_verts = 0, *n_tris = 0;
+    int rc;
+    if ((rc = render_prelude_locked(h, "mesh"))) return rc;
+    for (int a = 0; a < 3; a++)
+        if (h->g.dim[a] >= (1 << kMeshKeyBits) - 1) return fail(h, HFPF_ERR_CAPACITY, "mesh: a grid dimension of 2^21 - 1 cells or more");
+    uint64_t nr = 0;
+    const ExtractOpts opt{std::max(1.0, o->min_count), -1, 0};  // count >= max(1, min_count), the compare of k_extract_keys
+    if ((rc = build_rows_locked(h, h->t.stats, opt, &nr))) return rc;
+    if (nr == 0) return HFPF_OK;
+    if ((rc = scratch(h, h->mesh_cube, nr * 8))) return rc;
+    hipLaunchKernelGGL(k_mesh_row_keys, dim3(blocks_for(nr, 256)), dim3(256), 0, h->stream, (const Row*)h->rows_dev.p, nr, (uint64_t*)h->mesh_cube.p);
+    HIPCHK(h, hipGetLastError());
+    uint64_t n = nr;
+    for (int a = 0; a < 3; a++)
+        if ((rc = mesh_dilate_locked(h, h->mesh_cube, n, a, -1, 1, h->g.dim[a] - 1, h->mesh_cube, &n))) return rc;
+    const uint64_t nc = n;
+    for (int a = 0; a < 3; a++)
+        if ((rc = mesh_dilate_locked(h, a == 0 ? h->mesh_cube : h->mesh_corner, n, a, 0, 1, h->g.dim[a], h->mesh_corner, &n))) return rc;
+    const uint64_t nk = n;
+    // vertex and triangle ids are 32-bit: at most 7 vertices a corner and 12 triangles a cube
+    if (7 * nk >= 0xFFFFFFFFull || 12 * nc >= 0xFFFFFFFFull)
+        return fail(h, HFPF_ERR_CAPACITY, "mesh: %llu corners / %llu cubes exceed the 32-bit vertex and triangle ids", (unsigned long long)nk,
+                    (unsigned long long)nc);
+    const uint64_t K1 = nk + 1, C1 = nc + 1;
+    if ((rc = scratch(h, h->mesh_kdata, K1 * 20))) return rc;
+    if ((rc = scratch(h, h->mesh_cdata, C1 * 8))) return rc;
+    float* s = (float*)h->mesh_kdata.p;
+    uint32_t* nid = (uint32_t*)(s + K1);
+    uint32_t* marks = nid + K1;
+    uint32_t* vcount = marks + K1;
+    uint32_t* vbase = vcount + K1;
+    uint32_t* tcount = (uint32_t*)h->mesh_cdata.p;
+    uint32_t* tbase = tcount + C1;
+    const uint64_t* cubes = (const uint64_t*)h->mesh_cube.p;
+    const uint64_t* corners = (const uint64_t*)h->mesh_corner.p;
+    const MeshParams p{std::max(1.0, o->min_count), o->max_distance * o->max_distance, o->radius};
+    uint32_t* miss = (uint32_t*)h->mesh_ctr.p + 2;  // behind the unique count: set by a corner lookup that misses (a broken invariant)
+    HIPCHK(h, hipMemsetAsync(miss, 0, 4, h->stream));
+    hipLaunchKernelGGL(k_mesh_sample, dim3(blocks_for(nk, 256)), dim3(256), 0, h->stream, h->g, h->t, p, corners, (uint32_t)nk, s, nid);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemsetAsync(marks, 0, K1 * 4, h->stream));
+    hipLaunchKernelGGL(k_mesh_mark, dim3(blocks_for(C1, 256)), dim3(256), 0, h->stream, cubes, (uint32_t)nc, corners, (uint32_t)nk, (const float*)s,
+                       (const uint32_t*)nid, marks, tcount, miss);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_mesh_vcount, dim3(blocks_for(K1, 256)), dim3(256), 0, h->stream, (const uint32_t*)marks, (uint32_t)nk, vcount);
+    HIPCHK(h, hipGetLastError());
+    uint64_t nv = 0, nt = 0;
+    if ((rc = mesh_scan_locked(h, vcount, vbase, nk, &nv))) return rc;
+    if ((rc = mesh_scan_locked(h, tcount, tbase, nc, &nt))) return rc;
+    uint32_t missed = 0;
+    HIPCHK(h, hipMemcpy(&missed, miss, 4, hipMemcpyDeviceToHost));  // (the scan's read-back has synchronised the stream)
+    if (missed) return fail(h, HFPF_ERR_STATE, "mesh: a corner of a cube is missing from the corner set (internal)");
+    if (nv == 0 || nt == 0) return HFPF_OK;
+    MeshVertex* dv = nullptr;
+    uint32_t* dt = nullptr;
+    if (on_device) {
+        HIPCHK(h, hipMalloc(&dv, nv * sizeof(MeshVertex)));
+        if (hipMalloc(&dt, nt * 12) != hipSuccess) {
+            (void)hipFree(dv);
+            return fail(h, HFPF_ERR_HIP, "mesh: device allocation of %llu triangles failed", (unsigned long long)nt);
+        }
+    } else {
+        if ((rc = scratch(h, h->mesh_out, nv * sizeof(MeshVertex) + nt * 12))) return rc;
+        dv = (MeshVertex*)h->mesh_out.p;
+        dt = (uint32_t*)(dv + nv);
+    }
+    hipLaunchKernelGGL(k_mesh_vertices, dim3(blocks_for(nk, 256)), dim3(256), 0, h->stream, h->g, h->t, corners, (uint32_t)nk, (const float*)s,
+                       (const uint32_t*)nid, (const uint32_t*)marks, (const uint32_t*)vbase, dv, miss);
+    hipLaunchKernelGGL(k_mesh_triangles, dim3(blocks_for(nc, 256)), dim3(256), 0, h->stream, cubes, (uint32_t)nc, corners, (uint32_t)nk, (const float*)s,
+                       (const uint32_t*)nid, (const uint32_t*)marks, (const uint32_t*)vbase, (const uint32_t*)tbase, dt, miss);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&missed, miss, 4, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess || missed) {
+        if (on_device) (void)hipFree(dv), (void)hipFree(dt);
+        if (missed) return fail(h, HFPF_ERR_STATE, "mesh: a corner of a cube or an edge is missing from the corner set (internal)");
+        return fail(h, HFPF_ERR_HIP, "mesh: %s", hipGetErrorString(e));
+    }
+    *verts = dv, *tris = dt, *n_verts = nv, *n_tris = nt;
+    return HFPF_OK;
+}
+
+int hfpf_extract_mesh_device(hfpf_handle* h, const hfpf_mesh_opts* o, hfpf_mesh_vertex** dev_verts, uint64_t* n_verts, uint32_t** dev_tris,
+                             uint64_t* n_tris)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (!mesh_opts_ok(o) || !dev_verts || !n_verts || !dev_tris || !n_tris) return fail(h, HFPF_ERR_BAD_ARG, "mesh: invalid options or a NULL output");
+    MeshVertex* dv = nullptr;
+    uint32_t* dt = nullptr;
+    uint64_t nv = 0, nt = 0;
+    const int rc = mesh_locked(h, o, true, &dv, &dt, &nv, &nt);
+    *dev_verts = (hfpf_mesh_vertex*)dv, *dev_tris = dt, *n_verts = nv, *n_tris = nt;
+    return rc;
+}
+
+int hfpf_extract_mesh(hfpf_handle* h, const hfpf_mesh_opts* o, hfpf_mesh_vertex** verts, uint64_t* n_verts, uint32_t** tris, uint64_t* n_tris)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (!mesh_opts_ok(o) || !verts || !n_verts || !tris || !n_tris) return fail(h, HFPF_ERR_BAD_ARG, "mesh: invalid options or a NULL output");
+    *verts = nullptr, *tris = nullptr, *n_verts = 0, *n_tris = 0;
+    MeshVertex* dv = nullptr;
+    uint32_t* dt = nullptr;
+    uint64_t nv = 0, nt = 0;
+    if (int rc = mesh_locked(h, o, false, &dv, &dt, &nv, &nt)) return rc;
+    if (nv == 0) return HFPF_OK;
+    hfpf_mesh_vertex* hv = (hfpf_mesh_vertex*)host_result_alloc(nv * sizeof(hfpf_mesh_vertex));
+    uint32_t* ht = (uint32_t*)host_result_alloc(nt * 12);
+    if (!hv || !ht) {
+        free(hv), free(ht);
+        return fail(h, HFPF_ERR_CAPACITY, "mesh: host allocation of %llu vertices / %llu triangles failed", (unsigned long long)nv, (unsigned long long)nt);
+    }
+    hipError_t e = download_pageable(h, hv, dv, nv * sizeof(hfpf_mesh_vertex));
+    if (e == hipSuccess) e = download_pageable(h, ht, dt, nt * 12);
+    if (e != hipSuccess) {
+        free(hv), free(ht);
+        return fail(h, HFPF_ERR_HIP, "mesh copy: %s", hipGetErrorString(e));
+    }
+    *verts = hv, *tris = ht, *n_verts = nv, *n_tris = nt;
+    return HFPF_OK;
+}
+
+void hfpf_free_mesh(hfpf_mesh_vertex* verts, uint32_t* tris)
+{
+    free(verts);
+    free(tris);
+}
+
 int hfpf_stats_export(hfpf_handle* h, const void** dev_words, uint64_t* n_words, const void** dev_cwords, uint64_t* n_cwords)
 {
     if (!h || !dev_words || !n_words) return HFPF_ERR_BAD_ARG;
@@ -2926,6 +3121,42 @@ int hfpf_write_pcd_xyzrgb(const hfpf_row* rows, uint64_t n, const char* path, ui
         fprintf(f, "%.8g %.8g %.8g %u\n", r.x, r.y, r.z, 0xFF000000u | rgb);
     }
     const bool ok = !ferror(f);
+    return (fclose(f) == 0 && ok) ? HFPF_OK : HFPF_ERR_IO;
+}
+
+// A mesh as binary little-endian PLY: 27 bytes a vertex (x y z nx ny nz as f32, red green blue), 13 a face (count 3, three u32).
+int hfpf_write_ply(const hfpf_mesh_vertex* verts, uint64_t n_verts, const uint32_t* tris, uint64_t n_tris, const char* path)
+{
+    if (!path || (!verts && n_verts) || (!tris && n_tris)) return HFPF_ERR_BAD_ARG;
+    FILE* f = fopen(path, "wb");
+    if (!f) return HFPF_ERR_IO;
+    fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %llu\nproperty float x\nproperty float y\nproperty float z\n"
+               "property float nx\nproperty float ny\nproperty float nz\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n"
+               "element face %llu\nproperty list uchar uint vertex_indices\nend_header\n",
+            (unsigned long long)n_verts, (unsigned long long)n_tris);
+    constexpr uint64_t kChunk = 1u << 16;
+    std::vector<uint8_t> buf(kChunk * 27);
+    bool ok = true;
+    for (uint64_t i0 = 0; i0 < n_verts && ok; i0 += kChunk) {
+        const uint64_t n = std::min(kChunk, n_verts - i0);
+        uint8_t* o = buf.data();
+        for (uint64_t i = i0; i < i0 + n; i++, o += 27) {
+            const hfpf_mesh_vertex& v = verts[i];
+            memcpy(o, &v.x, 24);  // x y z nx ny nz
+            o[24] = (uint8_t)(v.rgb >> 16), o[25] = (uint8_t)(v.rgb >> 8), o[26] = (uint8_t)v.rgb;
+        }
+        ok = fwrite(buf.data(), 27, n, f) == n;
+    }
+    for (uint64_t i0 = 0; i0 < n_tris && ok; i0 += kChunk) {
+        const uint64_t n = std::min(kChunk, n_tris - i0);
+        uint8_t* o = buf.data();
+        for (uint64_t i = i0; i < i0 + n; i++, o += 13) {
+            o[0] = 3;
+            memcpy(o + 1, tris + 3 * i, 12);
+        }
+        ok = fwrite(buf.data(), 13, n, f) == n;
+    }
+    ok = ok && !ferror(f);
     return (fclose(f) == 0 && ok) ? HFPF_OK : HFPF_ERR_IO;
 }
 

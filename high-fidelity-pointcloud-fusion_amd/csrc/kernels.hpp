@@ -2438,6 +2438,70 @@ __device__ __forceinline__ uint64_t plane_window(int ya, int yb, int za, int zb)
     return ybytes & zbits;
 }
 
+// The window walk of a query (and of a mesh's corner samples): the candidate rows of the (2 radius + 1)^3 cells around voxel v,
+// clipped to the valid cells 0..dim-1 (extract emits no other), and the winner among those within max_d2 of q.
+struct WindowNearest {
+    bool found, has_row;  // has_row: v's own cell holds a candidate
+    uint32_t nid;         // the winner's record (found only)
+    int32_t wx, wy, wz;   // its cell, -1 without a winner
+    double d2, dx, dy, dz;  // q - its centroid, f64
+};
+__device__ __forceinline__ WindowNearest window_nearest(const GridParams& g, const Tables& t, const F3 q, const int32_t v[3], const int radius,
+                                                        const double min_count, const double max_d2)
+{
+    WindowNearest r;
+    r.found = r.has_row = false;
+    r.nid = 0;
+    r.wx = r.wy = r.wz = -1;
+    r.d2 = r.dx = r.dy = r.dz = 0.0;
+    uint64_t best_key = 0;
+    int lo[3], hi[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        lo[a] = max(v[a] - radius, 0);
+        hi[a] = min(v[a] + radius, g.dim[a] - 1);
+    }
+    if (lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2]) {
+        for (int bx = lo[0] >> kBrickShift; bx <= hi[0] >> kBrickShift; bx++)
+            for (int by = lo[1] >> kBrickShift; by <= hi[1] >> kBrickShift; by++)
+                for (int bz = lo[2] >> kBrickShift; bz <= hi[2] >> kBrickShift; bz++) {
+                    const uint32_t b = t.dir[((uint32_t)bx * (uint32_t)g.bdim[1] + (uint32_t)by) * (uint32_t)g.bdim[2] + (uint32_t)bz];
+                    if (b == 0 || b == kLock) continue;  // untouched (kLock cannot happen between kernels)
+                    const uint64_t wmask = plane_window(max(lo[1] - 8 * by, 0), min(hi[1] - 8 * by, 7), max(lo[2] - 8 * bz, 0),
+                                                        min(hi[2] - 8 * bz, 7));
+                    const int x1 = min(hi[0], 8 * bx + 7);
+                    for (int cx = max(lo[0], 8 * bx); cx <= x1; cx++) {
+                        uint64_t w = t.nd_mask[((uint64_t)b * 8u + (uint32_t)(cx & 7)) * 2] & wmask;
+                        while (w) {
+                            const int bitn = __builtin_ctzll(w);
+                            w &= w - 1;
+                            const int32_t cy = 8 * by + (bitn >> 3), cz = 8 * bz + (bitn & 7);
+                            const uint32_t nid = t.stat_id[b * kBrickCells + local_index(cx, cy, cz)];
+                            if (nid == 0) continue;
+                            const long long* s = reinterpret_cast<const long long*>(&t.stats[(uint64_t)nid * kStatWords]);
+                            const long long cnt = s[SW_COUNT];
+                            if ((double)(int)cnt < min_count) continue;  // min_count >= 1: cnt > 0 below
+                            if (cx == v[0] && cy == v[1] && cz == v[2]) r.has_row = true;
+                            double em;
+                            float rx, ry, rz;
+                            record_centroid(g, t, s, nid, cnt, em, rx, ry, rz);
+                            const double dx = (double)q.x - (double)rx, dy = (double)q.y - (double)ry, dz = (double)q.z - (double)rz;
+                            const double d2 = (dx * dx + dy * dy) + dz * dz;
+                            if (!(d2 <= max_d2)) continue;
+                            const uint64_t key = make_key(g, cx, cy, cz);
+                            if (!r.found || d2 < r.d2 || (d2 == r.d2 && key < best_key)) {
+                                r.found = true;
+                                r.d2 = d2, best_key = key, r.nid = nid;
+                                r.dx = dx, r.dy = dy, r.dz = dz;
+                                r.wx = cx, r.wy = cy, r.wz = cz;
+                            }
+                        }
+                    }
+                }
+    }
+    return r;
+}
+
 template <int FORM>
 __global__ __launch_bounds__(256) void k_query(const GridParams g, const Tables t, const QueryParams p, const uint8_t* __restrict__ frame,
                                                const PointLayout<FORM> lay, QueryHit* __restrict__ hits, Row* __restrict__ rows)
@@ -2473,53 +2537,12 @@ __global__ __launch_bounds__(256) void k_query(const GridParams g, const Tables 
                 slot_plane_bit(slot_lookup(g, t, v[0], v[1], v[2]), plane, bit);
                 if (t.occ_mask[plane] & bit) h.flags |= kQHitOccupied;
             }
-            // the window, clipped to the valid cells 0..dim-1 (extract emits no other)
-            int lo[3], hi[3];
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                lo[a] = max(v[a] - p.radius, 0);
-                hi[a] = min(v[a] + p.radius, g.dim[a] - 1);
-            }
-            double best_d2 = 0.0, bdx = 0.0, bdy = 0.0, bdz = 0.0;
-            uint64_t best_key = 0;
-            if (lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2]) {
-                for (int bx = lo[0] >> kBrickShift; bx <= hi[0] >> kBrickShift; bx++)
-                    for (int by = lo[1] >> kBrickShift; by <= hi[1] >> kBrickShift; by++)
-                        for (int bz = lo[2] >> kBrickShift; bz <= hi[2] >> kBrickShift; bz++) {
-                            const uint32_t b = t.dir[((uint32_t)bx * (uint32_t)g.bdim[1] + (uint32_t)by) * (uint32_t)g.bdim[2] + (uint32_t)bz];
-                            if (b == 0 || b == kLock) continue;  // untouched (kLock cannot happen between kernels)
-                            const uint64_t wmask = plane_window(max(lo[1] - 8 * by, 0), min(hi[1] - 8 * by, 7), max(lo[2] - 8 * bz, 0),
-                                                                min(hi[2] - 8 * bz, 7));
-                            const int x1 = min(hi[0], 8 * bx + 7);
-                            for (int cx = max(lo[0], 8 * bx); cx <= x1; cx++) {
-                                uint64_t w = t.nd_mask[((uint64_t)b * 8u + (uint32_t)(cx & 7)) * 2] & wmask;
-                                while (w) {
-                                    const int bitn = __builtin_ctzll(w);
-                                    w &= w - 1;
-                                    const int32_t cy = 8 * by + (bitn >> 3), cz = 8 * bz + (bitn & 7);
-                                    const uint32_t nid = t.stat_id[b * kBrickCells + local_index(cx, cy, cz)];
-                                    if (nid == 0) continue;
-                                    const long long* s = reinterpret_cast<const long long*>(&t.stats[(uint64_t)nid * kStatWords]);
-                                    const long long cnt = s[SW_COUNT];
-                                    if ((double)(int)cnt < p.min_count) continue;  // min_count >= 1: cnt > 0 below
-                                    if (cx == v[0] && cy == v[1] && cz == v[2]) h.flags |= kQHitHasRow;
-                                    double em;
-                                    float rx, ry, rz;
-                                    record_centroid(g, t, s, nid, cnt, em, rx, ry, rz);
-                                    const double dx = (double)q.x - (double)rx, dy = (double)q.y - (double)ry, dz = (double)q.z - (double)rz;
-                                    const double d2 = (dx * dx + dy * dy) + dz * dz;
-                                    if (!(d2 <= p.max_d2)) continue;
-                                    const uint64_t key = make_key(g, cx, cy, cz);
-                                    if (!found || d2 < best_d2 || (d2 == best_d2 && key < best_key)) {
-                                        found = true;
-                                        best_d2 = d2, best_key = key, best_nid = nid;
-                                        bdx = dx, bdy = dy, bdz = dz;
-                                        wx = cx, wy = cy, wz = cz;
-                                    }
-                                }
-                            }
-                        }
-            }
+            const WindowNearest wn = window_nearest(g, t, q, v, p.radius, p.min_count, p.max_d2);
+            if (wn.has_row) h.flags |= kQHitHasRow;
+            found = wn.found;
+            best_nid = wn.nid;
+            wx = wn.wx, wy = wn.wy, wz = wn.wz;
+            const double best_d2 = wn.d2, bdx = wn.dx, bdy = wn.dy, bdz = wn.dz;
             if (found) {
                 const double nx = t.nv_n[3 * (uint64_t)best_nid], ny = t.nv_n[3 * (uint64_t)best_nid + 1], nz = t.nv_n[3 * (uint64_t)best_nid + 2];
                 h.flags |= kQHitFound;
@@ -2540,6 +2563,293 @@ __global__ __launch_bounds__(256) void k_query(const GridParams g, const Tables 
             r.ix = r.iy = r.iz = -1;
         }
         rows[k] = r;
+    }
+}
+
+// ---- surface mesh (hfpf_extract_mesh*, include/hfpf.h) --------------------------------------------------------------------
+// Lattice and cube keys are x << 42 | y << 21 | z (21 bits an axis: lattice points reach dim, which make_key's widths do not cover).
+// The cube set is the candidate rows' cells dilated by 1 (three 1-D dilations, each emit -> sort -> unique), the corner set the cubes
+// dilated by (0, +1) the same way; both stay sorted, so a corner's index is a binary search and the scans run in key order.
+constexpr int kMeshKeyBits = 21;
+constexpr uint64_t kMeshKeyMask = (1ull << kMeshKeyBits) - 1ull;
+
+__host__ __device__ constexpr uint64_t mesh_key(const int32_t x, const int32_t y, const int32_t z)
+{
+    return ((uint64_t)x << (2 * kMeshKeyBits)) | ((uint64_t)y << kMeshKeyBits) | (uint64_t)z;
+}
+
+__device__ __forceinline__ int32_t mesh_key_axis(const uint64_t k, const int a) { return (int32_t)((k >> (kMeshKeyBits * (2 - a))) & kMeshKeyMask); }
+
+// The winding table of the Kuhn tetrahedra, derived at compile time.  Cube corner codes are 4 dx + 2 dy + dz; tetrahedron T of the
+// permutation pi (xyz, xzy, yxz, yzx, zxy, zyx) has the corners 0, e_pi1, e_pi1 + e_pi2, 7.  Case m (bit i: corner i inside) gives
+// n triangles; a triangle vertex is the lattice edge (origin code << 3) | direction code, direction = the far corner's code minus
+// the origin's (0 < d <= 7: the corners of a tetrahedron are ordered componentwise).  Edges are (I-th inside, O-th outside) corner
+// pairs; the winding makes the face normal of the edge-midpoint triangle point from the inside corners to the outside ones.
+struct MeshCase {
+    uint8_t n;
+    uint8_t e[2][3];
+};
+struct MeshTable {
+    uint8_t tet[6][4];
+    MeshCase c[6][16];
+};
+
+constexpr MeshTable make_mesh_table()
+{
+    MeshTable m{};
+    const uint8_t tets[6][4] = {{0, 4, 6, 7}, {0, 4, 5, 7}, {0, 2, 6, 7}, {0, 2, 3, 7}, {0, 1, 5, 7}, {0, 1, 3, 7}};
+    for (int t = 0; t < 6; t++) {
+        for (int i = 0; i < 4; i++) m.tet[t][i] = tets[t][i];
+        for (int mask = 0; mask < 16; mask++) {
+            int in[4] = {}, out[4] = {}, ni = 0, no = 0;
+            for (int i = 0; i < 4; i++) {
+                if (mask >> i & 1) in[ni++] = i;
+                else out[no++] = i;
+            }
+            int tri[2][3][2] = {};  // (inside, outside) local corners per triangle vertex
+            int n = 0;
+            if (ni == 1) {
+                n = 1;
+                for (int k = 0; k < 3; k++) tri[0][k][0] = in[0], tri[0][k][1] = out[k];
+            } else if (ni == 3) {
+                n = 1;
+                for (int k = 0; k < 3; k++) tri[0][k][0] = in[k], tri[0][k][1] = out[0];
+            } else if (ni == 2) {  // (e00, e01, e11) and (e00, e11, e10)
+                n = 2;
+                const int q[2][3][2] = {{{0, 0}, {0, 1}, {1, 1}}, {{0, 0}, {1, 1}, {1, 0}}};
+                for (int r = 0; r < 2; r++)
+                    for (int k = 0; k < 3; k++) tri[r][k][0] = in[q[r][k][0]], tri[r][k][1] = out[q[r][k][1]];
+            }
+            m.c[t][mask].n = (uint8_t)n;
+            // the direction the normal should take: |I| * sum(outside corners) - |O| * sum(inside corners)
+            int want[3] = {0, 0, 0};
+            for (int a = 0; a < 3; a++) {
+                for (int k = 0; k < no; k++) want[a] += ni * (tets[t][out[k]] >> (2 - a) & 1);
+                for (int k = 0; k < ni; k++) want[a] -= no * (tets[t][in[k]] >> (2 - a) & 1);
+            }
+            for (int r = 0; r < n; r++) {
+                int mid[3][3] = {};  // twice the edge midpoints
+                uint8_t code[3] = {};
+                for (int k = 0; k < 3; k++) {
+                    const int u = tets[t][tri[r][k][0]], w = tets[t][tri[r][k][1]];
+                    for (int a = 0; a < 3; a++) mid[k][a] = (u >> (2 - a) & 1) + (w >> (2 - a) & 1);
+                    const int lo = u < w ? u : w, hi = u < w ? w : u;
+                    code[k] = (uint8_t)(lo << 3 | (hi - lo));
+                }
+                int ab[3] = {}, ac[3] = {};
+                for (int a = 0; a < 3; a++) ab[a] = mid[1][a] - mid[0][a], ac[a] = mid[2][a] - mid[0][a];
+                const int nrm[3] = {ab[1] * ac[2] - ab[2] * ac[1], ab[2] * ac[0] - ab[0] * ac[2], ab[0] * ac[1] - ab[1] * ac[0]};
+                const int dot = nrm[0] * want[0] + nrm[1] * want[1] + nrm[2] * want[2];
+                m.c[t][mask].e[r][0] = code[0];
+                m.c[t][mask].e[r][1] = dot > 0 ? code[1] : code[2];
+                m.c[t][mask].e[r][2] = dot > 0 ? code[2] : code[1];
+            }
+        }
+    }
+    return m;
+}
+__constant__ MeshTable kMeshTable = make_mesh_table();
+
+struct MeshParams {
+    double min_count;  // max(1, min_count)
+    double max_d2;     // max_distance * max_distance
+    int32_t radius;    // 1..4
+};
+
+struct MeshVertex {  // = hfpf_mesh_vertex
+    float x, y, z, nx, ny, nz;
+    uint32_t rgb, count;
+};
+static_assert(sizeof(MeshVertex) == 32, "mesh vertex is 32 bytes");
+
+// The index of key in the sorted unique keys[0, n).  The callers look up keys the construction puts there; a miss would be a broken
+// invariant: it sets *miss (the host then fails the call) and returns 0, an index that is safe to read.
+__device__ __forceinline__ uint32_t mesh_find(const uint64_t* __restrict__ keys, const uint32_t n, const uint64_t key, uint32_t* __restrict__ miss)
+{
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (keys[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo < n && keys[lo] == key) return lo;
+    atomicOr(miss, 1u);
+    return 0;
+}
+
+// Lattice coordinate c[a] = (float)(bbox_min[a] + (double)i * res): one f64 multiply and add (never contracted), one rounding.
+__device__ __forceinline__ F3 mesh_lattice_point(const GridParams& g, const uint64_t k)
+{
+    F3 c;
+    c.x = (float)(g.min[0] + (double)mesh_key_axis(k, 0) * g.res);
+    c.y = (float)(g.min[1] + (double)mesh_key_axis(k, 1) * g.res);
+    c.z = (float)(g.min[2] + (double)mesh_key_axis(k, 2) * g.res);
+    return c;
+}
+
+// The candidate rows' cells (extract order: already sorted and unique).
+__global__ __launch_bounds__(256) void k_mesh_row_keys(const Row* __restrict__ rows, const uint64_t n, uint64_t* __restrict__ keys)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    keys[j] = mesh_key(rows[j].ix, rows[j].iy, rows[j].iz);
+}
+
+// One 1-D dilation along axis a: key j emits its neighbours at offsets lo..hi, clamped into 0..lim.  A clamped neighbour repeats the
+// offset-0 key or one inside the range (lo <= 0 <= hi and the input lies in 0..lim), so the unique pass drops it.
+__global__ __launch_bounds__(256) void k_mesh_dilate(const uint64_t* __restrict__ in, const uint64_t n, const int a, const int lo, const int hi,
+                                                     const int32_t lim, uint64_t* __restrict__ out)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint64_t k = in[j];
+    const int sh = kMeshKeyBits * (2 - a);
+    const int32_t c = (int32_t)((k >> sh) & kMeshKeyMask);
+    const uint64_t rest = k & ~(kMeshKeyMask << sh);
+    const int w = hi - lo + 1;
+    for (int o = lo; o <= hi; o++) out[j * w + (o - lo)] = rest | ((uint64_t)min(max(c + o, 0), lim) << sh);
+}
+
+// One lane per corner: the hfpf_query hit of lattice point c under the identity pose (transform_point of the identity is c itself).
+// Defined iff FOUND: nid != 0 (record 0 is never a row) and s = its signed distance.
+__global__ __launch_bounds__(256) void k_mesh_sample(const GridParams g, const Tables t, const MeshParams p, const uint64_t* __restrict__ corners,
+                                                     const uint32_t n, float* __restrict__ s_out, uint32_t* __restrict__ nid_out)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const F3 q = mesh_lattice_point(g, corners[k]);
+    float s = 0.f;
+    uint32_t nid = 0;
+    if (valid_point(g, q)) {
+        int32_t v[3];
+        voxel_coords(g, q, v[0], v[1], v[2]);
+        const WindowNearest wn = window_nearest(g, t, q, v, p.radius, p.min_count, p.max_d2);
+        if (wn.found) {
+            const double nx = t.nv_n[3 * (uint64_t)wn.nid], ny = t.nv_n[3 * (uint64_t)wn.nid + 1], nz = t.nv_n[3 * (uint64_t)wn.nid + 2];
+            s = (float)((nx * wn.dx + ny * wn.dy) + nz * wn.dz);
+            nid = wn.nid;
+        }
+    }
+    s_out[k] = s;
+    nid_out[k] = nid;
+}
+
+// The 8 corner indices of cube key ck and its 6 tetrahedron cases; false when a corner is undefined (the cube is not meshed).
+__device__ __forceinline__ bool mesh_cube(const uint64_t ck, const uint64_t* __restrict__ corners, const uint32_t nk, const float* __restrict__ s,
+                                          const uint32_t* __restrict__ nid, uint32_t* __restrict__ miss, uint32_t idx[8], uint32_t cases[6])
+{
+    uint32_t inside = 0;
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        idx[c] = mesh_find(corners, nk, ck + mesh_key(c >> 2, (c >> 1) & 1, c & 1), miss);
+        if (nid[idx[c]] == 0) return false;
+        inside |= (s[idx[c]] < 0.f ? 1u : 0u) << c;
+    }
+#pragma unroll
+    for (int tt = 0; tt < 6; tt++) {
+        uint32_t m = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) m |= (inside >> kMeshTable.tet[tt][i] & 1u) << i;
+        cases[tt] = m;
+    }
+    return true;
+}
+
+// One lane per cube (plus one that zeroes the scan's extra element): OR each crossing edge's direction bit (bit d - 1) into its
+// origin corner's mark, and count the cube's triangles.  The marks are ORs, so they do not depend on the order cubes run in.
+__global__ __launch_bounds__(256) void k_mesh_mark(const uint64_t* __restrict__ cubes, const uint32_t nc, const uint64_t* __restrict__ corners,
+                                                   const uint32_t nk, const float* __restrict__ s, const uint32_t* __restrict__ nid,
+                                                   uint32_t* __restrict__ marks, uint32_t* __restrict__ tri_count, uint32_t* __restrict__ miss)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > nc) return;
+    if (j == nc) {
+        tri_count[nc] = 0;
+        return;
+    }
+    uint32_t idx[8], cases[6];
+    uint32_t n_tri = 0;
+    if (mesh_cube(cubes[j], corners, nk, s, nid, miss, idx, cases)) {
+        uint32_t local[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int tt = 0; tt < 6; tt++) {
+            const MeshCase& mc = kMeshTable.c[tt][cases[tt]];
+            n_tri += mc.n;
+            for (int r = 0; r < mc.n; r++)
+#pragma unroll
+                for (int v = 0; v < 3; v++) local[mc.e[r][v] >> 3] |= 1u << ((mc.e[r][v] & 7) - 1);
+        }
+#pragma unroll
+        for (int c = 0; c < 8; c++)
+            if (local[c]) atomicOr(&marks[idx[c]], local[c]);
+    }
+    tri_count[j] = n_tri;
+}
+
+// Per corner its vertex count (the popcount of its marks); element nk is 0, so element nk of the exclusive scan is the total.
+__global__ __launch_bounds__(256) void k_mesh_vcount(const uint32_t* __restrict__ marks, const uint32_t nk, uint32_t* __restrict__ vcount)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k > nk) return;
+    vcount[k] = k < nk ? (uint32_t)__builtin_popcount(marks[k]) : 0u;
+}
+
+// One lane per corner: its vertices in direction order.  t and p in f64, left to right, never contracted; the attributes come from
+// the row of the endpoint with the smaller |s| (a tie goes to the origin).
+__global__ __launch_bounds__(256) void k_mesh_vertices(const GridParams g, const Tables t, const uint64_t* __restrict__ corners, const uint32_t nk,
+                                                       const float* __restrict__ s, const uint32_t* __restrict__ nid, const uint32_t* __restrict__ marks,
+                                                       const uint32_t* __restrict__ vbase, MeshVertex* __restrict__ out, uint32_t* __restrict__ miss)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nk) return;
+    uint32_t m = marks[k];
+    if (!m) return;
+    uint32_t o = vbase[k];
+    const uint64_t ka = corners[k];
+    const F3 ca = mesh_lattice_point(g, ka);
+    const float sa = s[k];
+    while (m) {
+        const int d = __builtin_ctz(m) + 1;
+        m &= m - 1;
+        const uint64_t kb = ka + mesh_key(d >> 2, (d >> 1) & 1, d & 1);
+        const uint32_t b = mesh_find(corners, nk, kb, miss);
+        const F3 cb = mesh_lattice_point(g, kb);
+        const float sb = s[b];
+        const double tt = (double)sa / ((double)sa - (double)sb);
+        MeshVertex v;
+        v.x = (float)((double)ca.x + tt * ((double)cb.x - (double)ca.x));
+        v.y = (float)((double)ca.y + tt * ((double)cb.y - (double)ca.y));
+        v.z = (float)((double)ca.z + tt * ((double)cb.z - (double)ca.z));
+        const uint32_t w = fabsf(sb) < fabsf(sa) ? nid[b] : nid[k];
+        const Row r = record_row(g, t, t.stats, w, 0, 0, 0);
+        v.nx = r.nx, v.ny = r.ny, v.nz = r.nz;
+        v.rgb = r.rgb;
+        v.count = r.count;
+        out[o++] = v;
+    }
+}
+
+// One lane per cube: its triangles from tbase[j] on, by tetrahedron 0..5 and triangle 0..1.  A vertex id is its origin corner's
+// vbase plus the number of marks below its direction bit.
+__global__ __launch_bounds__(256) void k_mesh_triangles(const uint64_t* __restrict__ cubes, const uint32_t nc, const uint64_t* __restrict__ corners,
+                                                        const uint32_t nk, const float* __restrict__ s, const uint32_t* __restrict__ nid,
+                                                        const uint32_t* __restrict__ marks, const uint32_t* __restrict__ vbase,
+                                                        const uint32_t* __restrict__ tbase, uint32_t* __restrict__ tris, uint32_t* __restrict__ miss)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nc) return;
+    if (tbase[j + 1] == tbase[j]) return;
+    uint32_t idx[8], cases[6];
+    if (!mesh_cube(cubes[j], corners, nk, s, nid, miss, idx, cases)) return;
+    uint64_t o = (uint64_t)tbase[j] * 3;
+    for (int tt = 0; tt < 6; tt++) {
+        const MeshCase& mc = kMeshTable.c[tt][cases[tt]];
+        for (int r = 0; r < mc.n; r++)
+#pragma unroll
+            for (int v = 0; v < 3; v++) {
+                const uint32_t e = mc.e[r][v], c = idx[e >> 3], d = e & 7;
+                tris[o++] = vbase[c] + (uint32_t)__builtin_popcount(marks[c] & ((1u << (d - 1)) - 1u));
+            }
     }
 }
 

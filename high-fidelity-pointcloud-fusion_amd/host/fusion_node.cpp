@@ -29,6 +29,8 @@ struct hfpf_node {
     bool final_clean = false;
     bool write_variants = false;
     hfpf_publish_fn publish = nullptr;  // ~pcl_fusion_node/processed_cloud_normals (node.cpp:158)
+    bool mesh_on = false;               // hfpf_node_set_mesh_output: ~process also writes mesh.ply
+    hfpf_mesh_opts mesh_opts{};
     void* publish_user = nullptr;
     std::thread clean_thread;
     std::mutex cv_mtx;
@@ -229,6 +231,14 @@ int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
     if (rc == HFPF_OK) rc = hfpf_write_meta_csv(rows, nr, meta_location.c_str());
     if (rc == HFPF_OK && n->publish) n->publish(n->publish_user, rows, nr, n->fusion_frame.c_str());  // processed_cloud_, node.cpp:158
     hfpf_free_rows(rows);
+    if (rc == HFPF_OK && n->mesh_on) {  // EXTENSION: a triangle mesh of the same model next to the cloud
+        hfpf_mesh_vertex* mv = nullptr;
+        uint32_t* mt = nullptr;
+        uint64_t nmv = 0, nmt = 0;
+        rc = hfpf_extract_mesh(n->grid, &n->mesh_opts, &mv, &nmv, &mt, &nmt);
+        if (rc == HFPF_OK) rc = hfpf_write_ply(mv, nmv, mt, nmt, (n->directory_name + "/mesh.ply").c_str());
+        hfpf_free_mesh(mv, mt);
+    }
     if (rc == HFPF_OK && n->write_variants) {  // the reference's `#if 0` block, node.cpp:399-437
         struct Variant {
             const char* file;
@@ -281,6 +291,17 @@ int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
     char m[200];
     snprintf(m, sizeof m, "saved %llu points", (unsigned long long)nr);
     set_res(res, true, std::string(m) + " to " + cloud_location);
+    return HFPF_OK;
+}
+
+int hfpf_node_set_mesh_output(hfpf_node* n, const hfpf_mesh_opts* opts)
+{
+    if (!n) return HFPF_ERR_BAD_ARG;
+    if (opts) {
+        if (hfpf_check_mesh_opts(opts) != HFPF_OK) return nfail(n, HFPF_ERR_BAD_ARG, "hfpf_node_set_mesh_output: invalid hfpf_mesh_opts");
+        n->mesh_opts = *opts;
+    }
+    n->mesh_on = opts != nullptr;
     return HFPF_OK;
 }
 

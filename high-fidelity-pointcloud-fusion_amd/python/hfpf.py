@@ -91,6 +91,7 @@ EXPORTS = [
     "hfpf_render", "hfpf_render_device",
     "hfpf_track_depth", "hfpf_track_depth_device", "hfpf_track",
     "hfpf_query", "hfpf_query_device", "hfpf_query_depth",
+    "hfpf_extract_mesh", "hfpf_extract_mesh_device", "hfpf_free_mesh", "hfpf_write_ply", "hfpf_check_mesh_opts",
 ]
 
 # hfpf_depth_image formats (include/hfpf.h)
@@ -234,6 +235,35 @@ def query_opts(radius=1, min_count=0.0, max_distance=float("inf"), zclip=False):
     return o
 
 
+class MeshOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_int32), ("min_count", C.c_double), ("max_distance", C.c_double),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# hfpf_mesh_vertex (include/hfpf.h); triangles are (n, 3) uint32 vertex indices
+MESH_VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("rgb", "<u4"),
+                              ("count", "<u4")])
+assert MESH_VERTEX_DTYPE.itemsize == 32
+
+
+def mesh_opts(radius=2, min_count=0.0, max_distance=float("inf")):
+    """An hfpf_mesh_opts: the query window of the corner samples (1..4), the count gate and the distance gate."""
+    o = MeshOpts()
+    o.struct_size = C.sizeof(MeshOpts)
+    o.radius = int(radius)
+    o.min_count, o.max_distance = float(min_count), float(max_distance)
+    return o
+
+
+def write_ply(verts, tris, path):
+    """hfpf_write_ply of MESH_VERTEX_DTYPE vertices and (n, 3) uint32 triangles (host code, no GPU needed)."""
+    verts = np.ascontiguousarray(verts, MESH_VERTEX_DTYPE)
+    tris = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+    rc = lib().hfpf_write_ply(_p(verts) if len(verts) else None, len(verts), _p(tris) if len(tris) else None, len(tris), str(path).encode())
+    if rc != 0:
+        raise HfpfError(rc, "hfpf_write_ply(%s) failed" % path)
+
+
 EPOCH_REC_DTYPE = np.dtype([("key", "<u8"), ("first_frame", "<u4"), ("vx", "<f4"), ("vy", "<f4"), ("vz", "<f4"), ("pad", "<u4", (2,))])
 assert EPOCH_REC_DTYPE.itemsize == 32
 
@@ -315,6 +345,12 @@ def lib():
     L.hfpf_query.argtypes = [vp, C.POINTER(QueryOpts), vp, u32, u32, u32, u32, u32, vp, vp, vp]
     L.hfpf_query_device.argtypes = [vp, C.POINTER(QueryOpts), vp, u32, u32, u32, u32, u32, vp, vp, vp]
     L.hfpf_query_depth.argtypes = [vp, C.POINTER(QueryOpts), C.POINTER(DepthImage), vp, vp, vp, vp]
+    L.hfpf_extract_mesh.argtypes = [vp, C.POINTER(MeshOpts), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64)]
+    L.hfpf_extract_mesh_device.argtypes = [vp, C.POINTER(MeshOpts), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64)]
+    L.hfpf_free_mesh.argtypes = [vp, vp]
+    L.hfpf_free_mesh.restype = None
+    L.hfpf_write_ply.argtypes = [vp, u64, vp, u64, C.c_char_p]
+    L.hfpf_check_mesh_opts.argtypes = [C.POINTER(MeshOpts)]
     _lib = L
     return L
 
@@ -615,6 +651,32 @@ class OccupancyGrid:
                 self.device_free(dev_hits)
                 if dev_rows:
                     self.device_free(dev_rows)
+
+    # -- a surface of the model --
+    def extract_mesh(self, opts=None, radius=2, min_count=0.0, max_distance=float("inf")):
+        """The triangle mesh of the fused model (hfpf_extract_mesh): (vertices of MESH_VERTEX_DTYPE, (n, 3) uint32 triangles), copied
+        out of the engine's host arrays."""
+        o = opts if opts is not None else mesh_opts(radius, min_count, max_distance)
+        v, nv, t, nt = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+        self._chk(lib().hfpf_extract_mesh(self._h, C.byref(o), C.byref(v), C.byref(nv), C.byref(t), C.byref(nt)))
+        try:
+            verts = np.empty(nv.value, MESH_VERTEX_DTYPE)
+            tris = np.empty((nt.value, 3), np.uint32)
+            if nv.value:
+                C.memmove(verts.ctypes.data, v.value, verts.nbytes)
+            if nt.value:
+                C.memmove(tris.ctypes.data, t.value, tris.nbytes)
+        finally:
+            lib().hfpf_free_mesh(v, t)
+        return verts, tris
+
+    def extract_mesh_device(self, opts=None, radius=2, min_count=0.0, max_distance=float("inf")):
+        """The same mesh in HBM (hfpf_extract_mesh_device): (vertex pointer, n_verts, triangle pointer, n_tris); free both pointers with
+        device_free (they are 0 for an empty mesh)."""
+        o = opts if opts is not None else mesh_opts(radius, min_count, max_distance)
+        v, nv, t, nt = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+        self._chk(lib().hfpf_extract_mesh_device(self._h, C.byref(o), C.byref(v), C.byref(nv), C.byref(t), C.byref(nt)))
+        return v.value or 0, nv.value, t.value or 0, nt.value
 
     def query_depth(self, depth, pose, K, depth_scale=0.001, opts=None, radius=1, min_count=0.0, max_distance=float("inf"), zclip=False,
                     rows=True):

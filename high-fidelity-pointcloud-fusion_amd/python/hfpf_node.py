@@ -15,7 +15,8 @@ TF_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_d
 
 EXPORTS = ["hfpf_node_default_params", "hfpf_node_create", "hfpf_node_destroy", "hfpf_node_last_error", "hfpf_node_on_point_cloud",
            "hfpf_node_start", "hfpf_node_stop", "hfpf_node_reset", "hfpf_node_process", "hfpf_node_clean_now", "hfpf_node_grid",
-           "hfpf_node_get_stats", "hfpf_node_set_publisher", "hfpf_node_on_depth_image"]
+           "hfpf_node_get_stats", "hfpf_node_set_publisher", "hfpf_node_on_depth_image",
+           "hfpf_node_set_mesh_output"]
 
 
 class Params(C.Structure):
@@ -63,6 +64,7 @@ def lib():
         L.hfpf_node_grid.restype = C.c_void_p
         L.hfpf_node_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.hfpf_node_set_publisher.argtypes = [C.c_void_p, PUBLISH_FN, C.c_void_p]
+        L.hfpf_node_set_mesh_output.argtypes = [C.c_void_p, C.POINTER(hfpf.MeshOpts)]
         _lib = L
     return _lib
 
@@ -168,6 +170,14 @@ class FusionNode:
         if rc < 0:
             raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
         return rc
+
+    def set_mesh_output(self, opts=None, **kw):
+        """~process also writes <directory_name>/mesh.ply with these hfpf.mesh_opts (or its keywords); set_mesh_output(None) with no
+        keywords turns it off."""
+        o = opts if opts is not None else (hfpf.mesh_opts(**kw) if kw else None)
+        rc = lib().hfpf_node_set_mesh_output(self._h, C.byref(o) if o is not None else None)
+        if rc < 0:
+            raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
 
     def stats(self):
         s = Stats()

@@ -472,6 +472,83 @@ int hfpf_query_device(hfpf_handle* h, const hfpf_query_opts* o, const void* dev_
 int hfpf_query_depth(hfpf_handle* h, const hfpf_query_opts* o, const hfpf_depth_image* desc, const void* depth,
                      const double pose_3x4[12], hfpf_query_hit* hits, hfpf_row* rows);
 
+/* ---- a triangle mesh of the fused model (point-set surface; no reference counterpart) ----------------------------------------
+ * The zero set of "signed distance to the tangent plane of the nearest row" (hfpf_query's signed_distance), sampled on the voxel
+ * corner lattice and polygonised by Kuhn tetrahedra (Hoppe et al. 1992).  Everything is restatable from hfpf_extract's rows and
+ * hfpf_get_occupied's list (tests/mesh_ref.py):
+ * Rows: the candidates hfpf_query would use at this point of the call sequence (host frames still waiting are launched first):
+ *   count >= max(1, min_count), centroid = the extracted row's x, y, z.
+ * Lattice point (i, j, k), 0 <= i <= dim_x (likewise j, k), sits at c[a] = (float)(bbox_min[a] + (double)i_a * res), one f64
+ *   multiply and add, one rounding.  Its sample is the hfpf_query hit of the f32 point c under the identity pose with the given
+ *   radius, min_count and max_distance (no z-clip).  The sample is DEFINED iff that hit is FOUND; its value s is the hit's
+ *   signed_distance, its row the hit's row.  Lattice points on the bounding box's faces are never IN_BBOX (query's bbox test is
+ *   strict), so they are never defined and cubes touching the box stay open.
+ * Cubes: cube (ix, iy, iz) spans lattice points (ix..ix+1, iy..iy+1, iz..iz+1).  The candidate cubes are the valid cells (0..dim-1)
+ *   within Chebyshev distance 1 of a candidate row's cell.  A cube is MESHED iff all 8 corner samples are defined.  (With radius >= 2
+ *   the row that makes a cube a candidate lies in the window of each of its corners.)
+ * Tetrahedra: a meshed cube splits into the 6 Kuhn tetrahedra along its (0,0,0)-(1,1,1) diagonal: for the axis permutations pi in
+ *   the order xyz, xzy, yxz, yzx, zxy, zyx, tetrahedron T has the corners (local index 0..3) 0, e_pi1, e_pi1 + e_pi2, (1,1,1).  A
+ *   corner is INSIDE iff s < 0.  Neighbouring cubes share their face diagonals, so the mesh has no cracks and no ambiguous case.
+ * Vertices: one per lattice edge that is an edge of a meshed tetrahedron and whose endpoints differ in inside/outside.  A lattice
+ *   edge is (origin a, direction d), d one of the 7 offsets in {0,1}^3 \ {0}, numbered 0..6 in lexicographic order of the offset
+ *   ((0,0,1), (0,1,0), (0,1,1), (1,0,0), (1,0,1), (1,1,0), (1,1,1)); b = a + d.  Position, f64, left to right, never contracted:
+ *   t = (double)s_a / ((double)s_a - (double)s_b), p = (float)((double)c_a + t * ((double)c_b - (double)c_a)) per axis.  nx, ny, nz,
+ *   rgb and count are those of the row of the endpoint with the smaller |s| (a tie goes to a); rgb as hfpf_extract codes it
+ *   (0x00RRGGBB with HFPF_FLAG_FUSE_COLOR, 0 without).  Order: lexicographic by a's (i, j, k), then by direction, so the mesh is
+ *   welded and does not depend on scheduling.
+ * Triangles: a tetrahedron with one or three inside corners gives one triangle, (e00, e01, e02) or (e00, e10, e20); two inside
+ *   corners give the quad (e00, e01, e11), (e00, e11, e10), where eIO is the edge from the I-th inside to the O-th outside corner,
+ *   each counted in local index order.  When the triangle's face normal, with its vertices at the edge midpoints, does not point from
+ *   the inside corners to the outside ones (|I| * sum(outside) - |O| * sum(inside)), its second and third vertices swap: faces look to
+ *   the sensor side, as row normals do.  Order: by the cube's (ix, iy, iz), then tetrahedron 0..5, then triangle 0..1.
+ * Limitation: the function is only as consistent as the rows' orientation.  A row seen at grazing angles (near a silhouette) can
+ * be oriented away from the surface's outside; an edge between its sample and a neighbour's then changes sign without crossing the
+ * surface, and its vertex lies up to one lattice edge off it (on the synthetic sphere of tests/test_gpu_mesh.py at 2 mm: 1.8 % of
+ * the sphere's vertices; the vertices whose two endpoint rows face outwards lie within 0.7 mm, 99 % within 0.3 mm).
+ * A mesh changes nothing on the handle except device_bytes (its scratch: per corner its key and 20 bytes of samples, marks and
+ * counts, per cube its key and 8 bytes of triangle counts, sort buffers of up to three times the largest set, and for the host form
+ * the output; scratch grows by 25 % headroom when it grows).  A corner that the construction does not find in its own corner set
+ * (an internal error) fails the call with HFPF_ERR_STATE and returns no mesh.  A handle before its first clean pass returns HFPF_OK with 0 vertices and 0 triangles
+ * (and NULL arrays).  Rejected with HFPF_ERR_BAD_ARG (the handle stays usable, nothing is written): struct_size != sizeof, flags or
+ * reserved != 0, radius outside 1..4, min_count NaN, max_distance NaN or not > 0 (+inf allowed), a NULL output pointer.  A handle
+ * with an RCCL communicator returns HFPF_ERR_STATE; a failed handle returns HFPF_ERR_STATE as extract does.  Every call returns when
+ * its outputs are complete. */
+typedef struct hfpf_mesh_opts {
+    uint32_t struct_size;        /* = sizeof(hfpf_mesh_opts) */
+    int32_t radius;              /* 1..4 (typically 2): the query window of every corner sample */
+    double min_count;            /* rows with count < max(1, min_count) are not candidates */
+    double max_distance;         /* > 0, +inf allowed: the query's distance gate; corners farther from every row stay undefined */
+    uint32_t flags;              /* 0 */
+    uint32_t reserved;           /* 0 */
+} hfpf_mesh_opts;
+
+typedef struct hfpf_mesh_vertex { /* 32 bytes */
+    float x, y, z;
+    float nx, ny, nz;            /* the attribute row's normal */
+    uint32_t rgb;                /* its colour, 0x00RRGGBB */
+    uint32_t count;              /* its count */
+} hfpf_mesh_vertex;
+
+#ifdef __cplusplus
+static_assert(sizeof(hfpf_mesh_opts) == 32, "hfpf_mesh_opts is 32 bytes");
+static_assert(sizeof(hfpf_mesh_vertex) == 32, "hfpf_mesh_vertex is 32 bytes");
+#else
+_Static_assert(sizeof(hfpf_mesh_opts) == 32, "hfpf_mesh_opts is 32 bytes");
+_Static_assert(sizeof(hfpf_mesh_vertex) == 32, "hfpf_mesh_vertex is 32 bytes");
+#endif
+
+/* HFPF_OK if o passes the checks above, else HFPF_ERR_BAD_ARG (host code, no handle; the node shell uses it too). */
+int hfpf_check_mesh_opts(const hfpf_mesh_opts* o);
+/* The mesh in HOST memory: *verts (n_verts) and *tris (3 * n_tris vertex indices), freed by hfpf_free_mesh. */
+int hfpf_extract_mesh(hfpf_handle* h, const hfpf_mesh_opts* o, hfpf_mesh_vertex** verts, uint64_t* n_verts, uint32_t** tris, uint64_t* n_tris);
+void hfpf_free_mesh(hfpf_mesh_vertex* verts, uint32_t* tris);
+/* The same mesh in DEVICE memory (HBM), each array freed by hfpf_device_free(h, p). */
+int hfpf_extract_mesh_device(hfpf_handle* h, const hfpf_mesh_opts* o, hfpf_mesh_vertex** dev_verts, uint64_t* n_verts, uint32_t** dev_tris,
+                             uint64_t* n_tris);
+/* PLY, format binary_little_endian 1.0: per vertex float x y z nx ny nz, uchar red green blue (from rgb); per face
+ * list uchar uint vertex_indices.  Host code, no GPU needed. */
+int hfpf_write_ply(const hfpf_mesh_vertex* verts, uint64_t n_verts, const uint32_t* tris, uint64_t n_tris, const char* path);
+
 /* <directory_name>/test_cloud.pcd (node.cpp:395): PCD v0.7 ASCII, FIELDS x y z rgb normal_x normal_y normal_z curvature */
 int hfpf_write_pcd(const hfpf_row* rows, uint64_t n_rows, const char* path);
 /* <directory_name>/meta.csv (node.cpp:396) with the header string of grid.hpp:462 */

@@ -88,6 +88,11 @@ int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res);
 typedef void (*hfpf_publish_fn)(void* user, const hfpf_row* rows, uint64_t n_rows, const char* frame_id);
 int hfpf_node_set_publisher(hfpf_node* n, hfpf_publish_fn fn, void* user);
 
+/* EXTENSION: with mesh output set, ~process also writes <directory_name>/mesh.ply: hfpf_extract_mesh of the model it saves, with
+ * these options, through hfpf_write_ply (before the grid is cleared).  NULL turns it off again, the default.  Invalid options are
+ * refused with HFPF_ERR_BAD_ARG and leave the setting as it was.  (hfpf_node_params keeps its size: it is part of the ABI.) */
+int hfpf_node_set_mesh_output(hfpf_node* n, const hfpf_mesh_opts* opts);
+
 /* One iteration of cleanGrid (node.cpp:301-325): clean iff state_changed.  Returns 1 if a pass ran. */
 int hfpf_node_clean_now(hfpf_node* n);
 hfpf_handle* hfpf_node_grid(hfpf_node* n);
