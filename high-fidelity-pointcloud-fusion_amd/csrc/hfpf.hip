@@ -24,6 +24,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -268,6 +269,7 @@ struct hfpf_handle {
     // hfpf_extract_mesh*: cube and corner keys, per corner s / record / marks / vertex counts and bases, per cube triangle counts and
     // bases, the host form's output, a unique count
     DevBuf mesh_cube, mesh_corner, mesh_kdata, mesh_cdata, mesh_out, mesh_ctr;
+    DevBuf ray_in, ray_out, ray_map;       // hfpf_raycast*: a host chunk's rays, a chunk's (or band's) hits, the empty-space maps
     unsigned long long* h_ctr = nullptr;  // pinned mirror of the counters
     unsigned long long* mbox = nullptr;   // coherent pinned mailbox k_publish_counters writes (HFPF_MAILBOX=0: blit copies + synchronize)
     unsigned long long mbox_seq = 0;
@@ -306,6 +308,9 @@ struct hfpf_handle {
     uint64_t n_detail[3] = {0, 0, 0};
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending_clean;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending_ray;  // one pair per k_raycast / k_raycast_view launch (id 5)
+    double t_ray_ms = 0;
+    uint64_t n_ray_timed = 0;
     double t_clean_ms = 0;
     uint64_t n_clean_timed = 0;
     std::vector<hipEvent_t> ev_free;
@@ -1077,8 +1082,17 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
 
 int resolve_timing(hfpf_handle* h)
 {
-    if (h->ev_pending.empty() && h->ev_pending_clean.empty() && h->ev_detail.empty()) return HFPF_OK;
+    if (h->ev_pending.empty() && h->ev_pending_clean.empty() && h->ev_pending_ray.empty() && h->ev_detail.empty()) return HFPF_OK;
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (auto& pr : h->ev_pending_ray) {
+        float ms = 0.f;
+        HIPCHK(h, hipEventElapsedTime(&ms, pr.first, pr.second));
+        h->t_ray_ms += (double)ms;
+        h->n_ray_timed++;
+        h->ev_free.push_back(pr.first);
+        h->ev_free.push_back(pr.second);
+    }
+    h->ev_pending_ray.clear();
     for (auto& pr : h->ev_pending_clean) {
         float ms = 0.f;
         HIPCHK(h, hipEventElapsedTime(&ms, pr.first, pr.second));
@@ -1620,7 +1634,7 @@ int hfpf_destroy(hfpf_handle* h)
     for (DevBuf* b : {&h->sort_tmp, &h->keys_a, &h->keys_b, &h->vals_a, &h->vals_b, &h->rows_dev, &h->probe_a, &h->probe_b, &h->probe_c, &h->probe_d,
                       &h->probe_e, &h->probe_f, &h->zbuf, &h->render_pose, &h->render_out, &h->track_in, &h->track_acc,
                       &h->query_in, &h->query_out, &h->mesh_cube, &h->mesh_corner, &h->mesh_kdata, &h->mesh_cdata, &h->mesh_out,
-                      &h->mesh_ctr})
+                      &h->mesh_ctr, &h->ray_in, &h->ray_out, &h->ray_map})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf* b : {&h->ex_send, &h->ex_recv, &h->ex_counts, &h->stats_total, &h->bin_pt_buf, &h->bin_rgb_buf, &h->bin_sums, &h->ovf_pt_buf, &h->ovf_aux_buf, &h->pend_a, &h->pend_b})
         if (b->p) (void)hipFree(b->p);
@@ -1658,6 +1672,10 @@ int hfpf_destroy(hfpf_handle* h)
         (void)hipEventDestroy(pr.second);
     }
     for (auto& pr : h->ev_pending_clean) {
+        (void)hipEventDestroy(pr.first);
+        (void)hipEventDestroy(pr.second);
+    }
+    for (auto& pr : h->ev_pending_ray) {
         (void)hipEventDestroy(pr.first);
         (void)hipEventDestroy(pr.second);
     }
@@ -2691,6 +2709,214 @@ int hfpf_query_depth(hfpf_handle* h, const hfpf_query_opts* o, const hfpf_depth_
     return query_locked(h, o, f, pose_3x4, hits, rows);
 }
 
+// ---- raycast (include/hfpf.h) ---------------------------------------------------------------------------------------------
+constexpr uint64_t kRayChunk = 1ull << 20;       // rays (or pixels) per launch of the host forms: 24 MB of rays, 64 MB of hits
+constexpr double kRayMaxSamples = 1048576.0;     // samples per ray
+constexpr uint32_t kRayViewsPerLaunch = 32768;   // views per launch (grid.y)
+
+int hfpf_check_raycast_opts(const hfpf_raycast_opts* o)
+{
+    if (!o || o->struct_size != sizeof(hfpf_raycast_opts) || o->reserved0 != 0 || o->reserved != 0) return HFPF_ERR_BAD_ARG;
+    if ((o->flags & ~HFPF_RAYCAST_CULL_BACKFACES) || o->radius < 1 || o->radius > kQueryMaxRadius) return HFPF_ERR_BAD_ARG;
+    if (std::isnan(o->min_count) || !(o->max_distance > 0.0)) return HFPF_ERR_BAD_ARG;
+    if (!(std::isfinite(o->step) && o->step >= 0.125 && o->step <= 4.0)) return HFPF_ERR_BAD_ARG;
+    if (!(std::isfinite(o->t_min) && std::isfinite(o->t_max) && 0.0 <= o->t_min && o->t_min < o->t_max)) return HFPF_ERR_BAD_ARG;
+    return HFPF_OK;
+}
+
+// The checks of a raycast that need the handle: options, pose and the sample count n = floor((t1 - t0) / dt) + 1 <= 2^20.
+static bool ray_args_ok(const hfpf_handle* h, const hfpf_raycast_opts* o, const double* pose, uint32_t n_poses, uint32_t* n_samples)
+{
+    if (hfpf_check_raycast_opts(o) != HFPF_OK) return false;
+    const double q = std::floor((o->t_max - o->t_min) / (o->step * h->g.res));
+    if (!(q < kRayMaxSamples)) return false;
+    *n_samples = (uint32_t)q + 1u;
+    if (n_poses && !pose) return false;
+    for (uint32_t v = 0; v < n_poses; v++)
+        if (!pose_ok(pose + 12ull * v)) return false;
+    return true;
+}
+
+// The empty-space maps of k_raycast in h->ray_map (per directory entry "has a row", then maps 0..2), and the launch parameters.
+static int ray_setup_locked(hfpf_handle* h, const hfpf_raycast_opts* o, uint32_t n_samples, RayParams* p)
+{
+    *p = RayParams{};
+    p->min_count = std::max(1.0, o->min_count);
+    p->max_d2 = o->max_distance * o->max_distance;
+    p->t0 = o->t_min;
+    p->dt = o->step * h->g.res;
+    p->n_samples = n_samples;
+    p->radius = o->radius;
+    p->cull = (o->flags & HFPF_RAYCAST_CULL_BACKFACES) ? 1u : 0u;
+    uint64_t cells[kRayLevels], total = 0;
+    for (int l = 0; l < kRayLevels; l++) {
+        for (int a = 0; a < 3; a++) p->mdim[l][a] = l == 0 ? h->g.bdim[a] : (p->mdim[l - 1][a] + 3) / 4;
+        cells[l] = (uint64_t)p->mdim[l][0] * p->mdim[l][1] * p->mdim[l][2];
+        total += (cells[l] + 255) & ~255ull;
+    }
+    if (cells[0] > 0xFFFFFFFFull) return fail(h, HFPF_ERR_CAPACITY, "raycast: %llu directory entries exceed the 32-bit map index", (unsigned long long)cells[0]);
+    const uint64_t has_bytes = (cells[0] + 255) & ~255ull;
+    if (int rc = scratch(h, h->ray_map, has_bytes + total)) return rc;
+    uint8_t* has = (uint8_t*)h->ray_map.p;
+    uint8_t* m = has + has_bytes;
+    uint8_t* maps[kRayLevels];
+    for (int l = 0; l < kRayLevels; l++) {
+        maps[l] = m;
+        p->map[l] = m;
+        m += (cells[l] + 255) & ~255ull;
+    }
+    hipLaunchKernelGGL(k_ray_map_bricks, dim3(blocks_for(cells[0], 256)), dim3(256), 0, h->stream, h->t, (uint32_t)cells[0], has);
+    hipLaunchKernelGGL(k_ray_map_dilate, dim3(blocks_for(cells[0], 256)), dim3(256), 0, h->stream, (const uint8_t*)has, p->mdim[0][0], p->mdim[0][1],
+                       p->mdim[0][2], maps[0]);
+    for (int l = 1; l < kRayLevels; l++)
+        hipLaunchKernelGGL(k_ray_map_up, dim3(blocks_for(cells[l], 256)), dim3(256), 0, h->stream, (const uint8_t*)maps[l - 1], p->mdim[l - 1][0],
+                           p->mdim[l - 1][1], p->mdim[l - 1][2], p->mdim[l][0], p->mdim[l][1], p->mdim[l][2], maps[l]);
+    HIPCHK(h, hipGetLastError());
+    return HFPF_OK;
+}
+
+// One march launch on the engine's stream, bracketed by an event pair when kernel timing is on (hfpf_get_kernel_time id 5).
+static int ray_launch_locked(hfpf_handle* h, const std::function<void()>& launch)
+{
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (h->timing) {
+        auto get = [&](hipEvent_t& e) -> hipError_t {
+            if (!h->ev_free.empty()) {
+                e = h->ev_free.back();
+                h->ev_free.pop_back();
+                return hipSuccess;
+            }
+            return hipEventCreate(&e);
+        };
+        HIPCHK(h, get(e0));
+        HIPCHK(h, get(e1));
+        HIPCHK(h, hipEventRecord(e0, h->stream));
+    }
+    launch();
+    HIPCHK(h, hipGetLastError());
+    if (h->timing) {
+        HIPCHK(h, hipEventRecord(e1, h->stream));
+        h->ev_pending_ray.emplace_back(e0, e1);
+    }
+    return HFPF_OK;
+}
+
+static int raycast_common(hfpf_handle* h, const hfpf_raycast_opts* o, const hfpf_ray* rays, bool on_device, uint64_t n_rays, const double pose[12],
+                          hfpf_ray_hit* hits)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    uint32_t n_samples = 0;
+    if (!ray_args_ok(h, o, pose, 1, &n_samples)) return fail(h, HFPF_ERR_BAD_ARG, "raycast: invalid options, pose or more than 2^20 samples a ray");
+    if (!hits || (n_rays && !rays)) return fail(h, HFPF_ERR_BAD_ARG, "raycast: null rays or hits");
+    if (on_device && (((uintptr_t)rays & 3) || ((uintptr_t)hits & 15)))
+        return fail(h, HFPF_ERR_BAD_ARG, "raycast_device: rays must be 4-byte and hits 16-byte aligned");
+    int rc;
+    if ((rc = render_prelude_locked(h, "raycast"))) return rc;
+    if (n_rays == 0) return HFPF_OK;
+    RayParams p;
+    if ((rc = ray_setup_locked(h, o, n_samples, &p))) return rc;
+    memcpy(p.T, pose, sizeof p.T);
+    auto launch = [&](const hfpf_ray* dr, uint64_t n, hfpf_ray_hit* dh) -> int {
+        p.n_rays = n;
+        return ray_launch_locked(h, [&] {
+            hipLaunchKernelGGL(k_raycast, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->g, h->t, p, (const float*)dr, (RayHit*)dh);
+        });
+    };
+    if (on_device) {
+        if ((rc = launch(rays, n_rays, hits))) return rc;
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return HFPF_OK;
+    }
+    const uint64_t chunk = std::min(n_rays, kRayChunk);
+    if ((rc = scratch(h, h->ray_in, chunk * sizeof(hfpf_ray)))) return rc;
+    if ((rc = scratch(h, h->ray_out, chunk * sizeof(RayHit)))) return rc;
+    for (uint64_t first = 0; first < n_rays; first += chunk) {
+        const uint64_t n = std::min(chunk, n_rays - first);
+        hipError_t e = upload_pageable(h, h->ray_in.p, rays + first, n * sizeof(hfpf_ray));
+        if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "raycast upload: %s", hipGetErrorString(e));
+        if ((rc = launch((const hfpf_ray*)h->ray_in.p, n, (hfpf_ray_hit*)h->ray_out.p))) return rc;
+        e = download_pageable(h, hits + first, h->ray_out.p, n * sizeof(RayHit), 0);
+        if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "raycast download: %s", hipGetErrorString(e));
+    }
+    return HFPF_OK;
+}
+
+int hfpf_raycast(hfpf_handle* h, const hfpf_raycast_opts* o, const hfpf_ray* rays, uint64_t n_rays, const double pose_3x4[12], hfpf_ray_hit* hits)
+{
+    return raycast_common(h, o, rays, false, n_rays, pose_3x4, hits);
+}
+
+int hfpf_raycast_device(hfpf_handle* h, const hfpf_raycast_opts* o, const hfpf_ray* dev_rays, uint64_t n_rays, const double pose_3x4[12],
+                        hfpf_ray_hit* dev_hits)
+{
+    return raycast_common(h, o, dev_rays, true, n_rays, pose_3x4, dev_hits);
+}
+
+// Views: the device form runs whole images, kRayViewsPerLaunch views a launch; the host form runs one view in bands of whole
+// 8-row tiles of about kRayChunk pixels through h->ray_out.
+static int raycast_view_common(hfpf_handle* h, const hfpf_raycast_opts* o, uint32_t width, uint32_t height, double fx, double fy, double cx, double cy,
+                               uint32_t n_views, const double* poses, bool on_device, hfpf_ray_hit* hits)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    uint32_t n_samples = 0;
+    if (!ray_args_ok(h, o, poses, n_views, &n_samples)) return fail(h, HFPF_ERR_BAD_ARG, "raycast: invalid options, pose or more than 2^20 samples a ray");
+    const uint64_t WH = (uint64_t)width * height;
+    if (WH == 0 || WH > (1ull << 31)) return fail(h, HFPF_ERR_BAD_ARG, "raycast: width * height must lie in 1..2^31");
+    if (!(std::isfinite(fx) && fx > 0.0 && std::isfinite(fy) && fy > 0.0 && std::isfinite(cx) && std::isfinite(cy)))
+        return fail(h, HFPF_ERR_BAD_ARG, "raycast: invalid intrinsics");
+    if (!hits) return fail(h, HFPF_ERR_BAD_ARG, "raycast: null hits");
+    if (on_device && ((uintptr_t)hits & 15)) return fail(h, HFPF_ERR_BAD_ARG, "raycast_view_device: hits must be 16-byte aligned");
+    int rc;
+    if ((rc = render_prelude_locked(h, "raycast"))) return rc;
+    if (n_views == 0) return HFPF_OK;
+    RayParams p;
+    if ((rc = ray_setup_locked(h, o, n_samples, &p))) return rc;
+    p.fx = fx, p.fy = fy, p.cx = cx, p.cy = cy;
+    p.width = width;
+    p.view_stride = WH;
+    if ((rc = scratch(h, h->render_pose, (size_t)n_views * 12 * sizeof(double)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->render_pose.p, poses, (size_t)n_views * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const uint64_t tiles_x = (width + 7ull) / 8;
+    auto launch = [&](uint32_t v0, uint32_t nv, uint32_t row0, uint32_t rows, RayHit* dh) -> int {
+        p.row0 = row0;
+        p.rows = rows;
+        const uint64_t tiles = tiles_x * ((rows + 7ull) / 8);
+        return ray_launch_locked(h, [&] {
+            hipLaunchKernelGGL(k_raycast_view, dim3(blocks_for(tiles * 64, 256), nv), dim3(256), 0, h->stream, h->g, h->t, p,
+                               (const double*)h->render_pose.p + 12ull * v0, dh);
+        });
+    };
+    if (on_device) {
+        for (uint32_t v0 = 0; v0 < n_views; v0 += kRayViewsPerLaunch)
+            if ((rc = launch(v0, std::min(kRayViewsPerLaunch, n_views - v0), 0, height, (RayHit*)hits + v0 * WH))) return rc;
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return HFPF_OK;
+    }
+    const uint32_t band = (uint32_t)std::min<uint64_t>(height, std::max<uint64_t>(8, (kRayChunk / width) & ~7ull));
+    if ((rc = scratch(h, h->ray_out, (uint64_t)band * width * sizeof(RayHit)))) return rc;
+    for (uint32_t row0 = 0; row0 < height; row0 += band) {
+        const uint32_t rows = std::min(band, height - row0);
+        if ((rc = launch(0, 1, row0, rows, (RayHit*)h->ray_out.p))) return rc;
+        const hipError_t e = download_pageable(h, hits + (uint64_t)row0 * width, h->ray_out.p, (uint64_t)rows * width * sizeof(RayHit), 0);
+        if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "raycast download: %s", hipGetErrorString(e));
+    }
+    return HFPF_OK;
+}
+
+int hfpf_raycast_view(hfpf_handle* h, const hfpf_raycast_opts* o, uint32_t width, uint32_t height, double fx, double fy, double cx, double cy,
+                      const double pose_3x4[12], hfpf_ray_hit* hits)
+{
+    return raycast_view_common(h, o, width, height, fx, fy, cx, cy, 1, pose_3x4, false, hits);
+}
+
+int hfpf_raycast_view_device(hfpf_handle* h, const hfpf_raycast_opts* o, uint32_t width, uint32_t height, double fx, double fy, double cx,
+                             double cy, uint32_t n_views, const double* poses, hfpf_ray_hit* dev_hits)
+{
+    return raycast_view_common(h, o, width, height, fx, fy, cx, cy, n_views, poses, true, dev_hits);
+}
+
 // ---- surface mesh (include/hfpf.h) ----------------------------------------------------------------------------------------
 int hfpf_check_mesh_opts(const hfpf_mesh_opts* o)
 {
@@ -3311,18 +3537,25 @@ int hfpf_kernel_timing(hfpf_handle* h, int enable)
         h->n_integrate_launches = 0;
         h->t_clean_ms = 0;
         h->n_clean_timed = 0;
+        h->t_ray_ms = 0;
+        h->n_ray_timed = 0;
     }
     return HFPF_OK;
 }
 
 int hfpf_get_kernel_time(hfpf_handle* h, int kernel_id, double* total_ms, uint64_t* launches)
 {
-    if (!h || kernel_id < 0 || kernel_id > 4) return HFPF_ERR_BAD_ARG;
+    if (!h || kernel_id < 0 || kernel_id > 5) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (int rcf = flush_pending_locked(h)) return rcf;  // host frames still waiting for their launch
     int rc = resolve_timing(h);
     if (rc) return rc;
+    if (kernel_id == 5) {
+        if (total_ms) *total_ms = h->t_ray_ms;
+        if (launches) *launches = h->n_ray_timed;
+        return HFPF_OK;
+    }
     if (kernel_id >= 2) {
         if (total_ms) *total_ms = h->t_detail_ms[kernel_id - 2];
         if (launches) *launches = h->n_detail[kernel_id - 2];

@@ -2566,6 +2566,272 @@ __global__ __launch_bounds__(256) void k_query(const GridParams g, const Tables 
     }
 }
 
+// ---- raycast (hfpf_raycast*, include/hfpf.h) ------------------------------------------------------------------------------
+// The contract is a dense march of query samples; the kernel skips every run of samples it can PROVE undefined.  A sample is
+// undefined when it lies outside the box or when its (2r+1)^3 window holds no row, and r <= 4 < 8 keeps the window of a point of
+// brick b inside b's 27-neighbourhood.  Three byte maps, rebuilt per call from the directory and the normal_found words, say where
+// rows cannot be: map 0 holds per brick "a brick of my 27-neighbourhood has a row", maps 1 and 2 its OR over 4^3 and 16^3 bricks.
+// A sample whose own voxel lies in a zero cell of a map (side S = 8, 32 or 128 cells) is undefined, and so is every sample whose
+// voxel lies in that cell grown by 8 - r cells: its window still stays inside the cell dilated by one brick.  From such a sample the
+// march jumps to the first sample that may leave the grown cell, computed from the ray's cells-per-sample rate, rounded down, with
+// a slack (one cell plus the f32 rounding of the ray's coordinates, in cells) taken off every bound; outside the box it jumps the same way
+// to the face's plane.  Every sample that is evaluated is evaluated as k_query does (voxel_coords, window_nearest), so a skipped run
+// changes no byte.  One lane per ray; view rays are mapped in 8 x 8 pixel tiles per wave so that a wave's rays stay together.
+constexpr uint32_t kRayUsed = 1u, kRayHit = 2u, kRayBackface = 4u, kRayNear = 8u;
+constexpr int kRayLevels = 3;  // map l: cells of 4^l bricks an axis
+
+struct __attribute__((aligned(16))) RayHit {  // = hfpf_ray_hit
+    float t;
+    uint32_t flags;
+    float p[3];
+    float n[3];
+    int32_t row_voxel[3];
+    uint32_t rgb, count, sample;
+    uint32_t reserved[2];
+};
+static_assert(sizeof(RayHit) == 64, "ray hit is 64 bytes");
+
+struct RayParams {
+    double T[12];        // camera -> fusion frame (general rays; view rays read their view's pose from device memory)
+    double min_count;    // max(1, min_count)
+    double max_d2;       // max_distance * max_distance (+inf allowed)
+    double t0, dt;       // t_k = t0 + k * dt
+    double fx, fy, cx, cy;  // views
+    uint64_t n_rays;     // general rays of the launch
+    uint32_t n_samples;  // <= 2^20
+    int32_t radius;      // 1..kQueryMaxRadius
+    uint32_t cull;       // 1: a back crossing does not end the ray
+    uint32_t width, row0, rows;  // views: image width, first image row and rows of the launch (hit 0 = pixel (0, row0))
+    uint64_t view_stride;        // hits between consecutive views (width * height)
+    int32_t mdim[kRayLevels][3];
+    const uint8_t* map[kRayLevels];
+};
+
+// has[i] = 1 iff directory entry i names a brick with a normal_found bit in one of its 8 x-planes
+__global__ __launch_bounds__(256) void k_ray_map_bricks(const Tables t, const uint32_t n_dir, uint8_t* __restrict__ has)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_dir) return;
+    const uint32_t b = t.dir[i];
+    uint64_t w = 0;
+    if (b != 0 && b != kLock)
+        for (uint32_t x = 0; x < 8; x++) w |= t.nd_mask[((uint64_t)b * 8u + x) * 2];
+    has[i] = w != 0;
+}
+
+// out = in dilated by one cell (the brick map: 27-neighbourhood)
+__global__ __launch_bounds__(256) void k_ray_map_dilate(const uint8_t* __restrict__ in, const int dx, const int dy, const int dz, uint8_t* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (uint32_t)dx * (uint32_t)dy * (uint32_t)dz) return;
+    const int z = (int)(i % (uint32_t)dz), y = (int)(i / (uint32_t)dz % (uint32_t)dy), x = (int)(i / ((uint32_t)dz * (uint32_t)dy));
+    uint32_t any = 0;
+    for (int a = max(x - 1, 0); a <= min(x + 1, dx - 1); a++)
+        for (int b = max(y - 1, 0); b <= min(y + 1, dy - 1); b++)
+            for (int c = max(z - 1, 0); c <= min(z + 1, dz - 1); c++) any |= in[((uint32_t)a * (uint32_t)dy + (uint32_t)b) * (uint32_t)dz + (uint32_t)c];
+    out[i] = any != 0;
+}
+
+// out cell = OR of its 4^3 children of in (dims id*; od* = ceil(id* / 4))
+__global__ __launch_bounds__(256) void k_ray_map_up(const uint8_t* __restrict__ in, const int idx_, const int idy, const int idz, const int odx,
+                                                    const int ody, const int odz, uint8_t* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (uint32_t)odx * (uint32_t)ody * (uint32_t)odz) return;
+    const int z = (int)(i % (uint32_t)odz), y = (int)(i / (uint32_t)odz % (uint32_t)ody), x = (int)(i / ((uint32_t)odz * (uint32_t)ody));
+    uint32_t any = 0;
+    for (int a = 4 * x; a < min(4 * x + 4, idx_); a++)
+        for (int b = 4 * y; b < min(4 * y + 4, idy); b++)
+            for (int c = 4 * z; c < min(4 * z + 4, idz); c++) any |= in[((uint32_t)a * (uint32_t)idy + (uint32_t)b) * (uint32_t)idz + (uint32_t)c];
+    out[i] = any != 0;
+}
+
+__device__ __forceinline__ RayHit ray_no_hit()
+{
+    const float qnan = __builtin_bit_cast(float, 0x7FC00000u);
+    RayHit h;
+    h.t = qnan;
+    h.flags = 0;
+    h.p[0] = h.p[1] = h.p[2] = qnan;
+    h.n[0] = h.n[1] = h.n[2] = qnan;
+    h.row_voxel[0] = h.row_voxel[1] = h.row_voxel[2] = -1;
+    h.rgb = h.count = h.sample = 0;
+    h.reserved[0] = h.reserved[1] = 0;
+    return h;
+}
+
+// Samples after the current one (cell coordinate c, `rate` cells a sample, inv = 1 / rate) that stay inside [lo, hi] on this axis.
+__device__ __forceinline__ double ray_axis_run(const double c, const double rate, const double inv, const double lo, const double hi)
+{
+    if (!__builtin_isfinite(c)) return 0.0;  // (a coordinate beyond f32: no claim)
+    if (rate > 0.0) return (hi - c) * inv;
+    if (rate < 0.0) return (lo - c) * inv;
+    return __builtin_inf();
+}
+
+// The march of one USED ray O + t * D (fusion frame).
+__device__ __forceinline__ RayHit ray_march(const GridParams& g, const Tables& t, const RayParams& p, const double O[3], const double D[3])
+{
+    RayHit h = ray_no_hit();
+    h.flags = kRayUsed;
+    double rate[3], inv[3], top[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        rate[a] = (D[a] * p.dt) * g.inv_res;
+        inv[a] = rate[a] != 0.0 ? 1.0 / rate[a] : 0.0;
+        top[a] = (g.max[a] - g.min[a]) * g.inv_res;
+    }
+    // cells taken off every bound of a jump: one, plus twice the f32 spacing of the largest coordinate the ray reaches
+    double reach = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; a++) reach = fmax(reach, fabs(O[a]) + fabs(D[a]) * (p.t0 + (double)(p.n_samples - 1u) * p.dt));
+    const double slack = 1.0 + (reach * 0x1p-22) * g.inv_res;
+    const double grow = (double)(8 - p.radius) - slack;  // cells by which a zero map cell may be left
+    const double inf = __builtin_inf();
+    bool prev_def = false, near = false;
+    float prev_s = 0.f;
+    uint32_t prev_nid = 0;
+    int32_t pwx = -1, pwy = -1, pwz = -1;
+    uint32_t k = 0;
+    while (k < p.n_samples) {
+        const double tk = p.t0 + (double)k * p.dt;
+        F3 q;
+        q.x = (float)(O[0] + tk * D[0]);
+        q.y = (float)(O[1] + tk * D[1]);
+        q.z = (float)(O[2] + tk * D[2]);
+        const double c[3] = {((double)q.x - g.min[0]) * g.inv_res, ((double)q.y - g.min[1]) * g.inv_res, ((double)q.z - g.min[2]) * g.inv_res};
+        double run = -1.0;  // >= 0: this sample is undefined, and so are the next floor(run)
+        int32_t v[3] = {0, 0, 0};
+        if (!valid_point(g, q)) {
+            // beyond a face of the box: undefined up to that face's plane (the best of the faces it lies beyond)
+            run = 0.0;
+            const float qa[3] = {q.x, q.y, q.z};
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                if (qa[a] <= g.bb_lo[a]) run = fmax(run, ray_axis_run(c[a], rate[a], inv[a], -inf, -slack));
+                else if (qa[a] >= g.bb_hi[a]) run = fmax(run, ray_axis_run(c[a], rate[a], inv[a], top[a] + slack, inf));
+            }
+        } else {
+            voxel_coords(g, q, v[0], v[1], v[2]);
+            if (v[0] >= 0 && v[1] >= 0 && v[2] >= 0 && v[0] <= g.dim[0] && v[1] <= g.dim[1] && v[2] <= g.dim[2]) {
+                int lvl = -1;
+#pragma unroll
+                for (int l = 0; l < kRayLevels; l++) {
+                    if (lvl != l - 1) continue;  // the finer map's cell holds rows: so does the coarser one's
+                    const int sh = kBrickShift + 2 * l;
+                    const uint32_t i = ((uint32_t)(v[0] >> sh) * (uint32_t)p.mdim[l][1] + (uint32_t)(v[1] >> sh)) * (uint32_t)p.mdim[l][2] + (uint32_t)(v[2] >> sh);
+                    if (p.map[l][i] == 0) lvl = l;
+                }
+                if (lvl >= 0) {
+                    const int sh = kBrickShift + 2 * lvl;
+                    run = inf;
+#pragma unroll
+                    for (int a = 0; a < 3; a++) {
+                        const double base = (double)((v[a] >> sh) << sh);
+                        run = fmin(run, ray_axis_run(c[a], rate[a], inv[a], base - grow, base + (double)(1 << sh) + grow));
+                    }
+                    run = fmax(run, 0.0);  // (the sample itself is undefined whatever the slack leaves of the cell)
+                }
+            }
+        }
+        if (run >= 0.0) {
+            prev_def = false;
+            if (!(run < (double)p.n_samples)) break;  // (an infinite run: the ray never comes back)
+            k += 1u + (run >= 1.0 ? (uint32_t)run : 0u);
+            continue;
+        }
+        const WindowNearest wn = window_nearest(g, t, q, v, p.radius, p.min_count, p.max_d2);
+        if (!wn.found) {
+            prev_def = false;
+            k++;
+            continue;
+        }
+        near = true;
+        const double nx = t.nv_n[3 * (uint64_t)wn.nid], ny = t.nv_n[3 * (uint64_t)wn.nid + 1], nz = t.nv_n[3 * (uint64_t)wn.nid + 2];
+        const float s = (float)((nx * wn.dx + ny * wn.dy) + nz * wn.dz);
+        if (prev_def && ((prev_s < 0.f) != (s < 0.f))) {
+            const bool back = prev_s < 0.f;
+            if (!(back && p.cull)) {
+                const double w = (double)prev_s / ((double)prev_s - (double)s);
+                const double th = (p.t0 + (double)(k - 1u) * p.dt) + w * p.dt;
+                const bool cur = fabsf(s) < fabsf(prev_s);  // the endpoint with the smaller |s|; a tie goes to k - 1
+                const Row r = record_row(g, t, t.stats, cur ? wn.nid : prev_nid, 0, 0, 0);
+                h.t = (float)th;
+                h.flags |= kRayHit | (back ? kRayBackface : 0u);
+                h.p[0] = (float)(O[0] + th * D[0]);
+                h.p[1] = (float)(O[1] + th * D[1]);
+                h.p[2] = (float)(O[2] + th * D[2]);
+                h.n[0] = r.nx, h.n[1] = r.ny, h.n[2] = r.nz;
+                h.row_voxel[0] = cur ? wn.wx : pwx, h.row_voxel[1] = cur ? wn.wy : pwy, h.row_voxel[2] = cur ? wn.wz : pwz;
+                h.rgb = r.rgb;
+                h.count = r.count;
+                h.sample = k;
+                break;
+            }
+        }
+        prev_def = true;
+        prev_s = s;
+        prev_nid = wn.nid;
+        pwx = wn.wx, pwy = wn.wy, pwz = wn.wz;
+        k++;
+    }
+    if (near) h.flags |= kRayNear;
+    return h;
+}
+
+// General rays: packed {o, d} f32 records in the camera frame, one lane per ray.
+__global__ __launch_bounds__(256) void k_raycast(const GridParams g, const Tables t, const RayParams p, const float* __restrict__ rays,
+                                                 RayHit* __restrict__ hits)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= p.n_rays) return;
+    float in[6];
+#pragma unroll
+    for (int a = 0; a < 6; a++) in[a] = rays[6 * i + a];
+    bool used = true;
+#pragma unroll
+    for (int a = 0; a < 6; a++) used = used && __builtin_isfinite(in[a]);
+    RayHit h = ray_no_hit();
+    if (used) {
+        const double ox = in[0], oy = in[1], oz = in[2], dx = in[3], dy = in[4], dz = in[5];
+        double O[3], W[3], D[3];
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            O[a] = ((p.T[4 * a] * ox + p.T[4 * a + 1] * oy) + p.T[4 * a + 2] * oz) + p.T[4 * a + 3];
+            W[a] = (p.T[4 * a] * dx + p.T[4 * a + 1] * dy) + p.T[4 * a + 2] * dz;
+        }
+        const double L = sqrt((W[0] * W[0] + W[1] * W[1]) + W[2] * W[2]);
+        if (__builtin_isfinite(L) && L > 0.0) {
+#pragma unroll
+            for (int a = 0; a < 3; a++) D[a] = W[a] / L;
+            h = ray_march(g, t, p, O, D);
+        }
+    }
+    hits[i] = h;
+}
+
+// View rays: a wave takes an 8 x 8 pixel tile of view blockIdx.y; the rows p.row0 .. p.row0 + p.rows - 1 of the image.
+__global__ __launch_bounds__(256) void k_raycast_view(const GridParams g, const Tables t, const RayParams p, const double* __restrict__ poses,
+                                                      RayHit* __restrict__ hits)
+{
+    const uint64_t tile = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t tiles_x = (p.width + 7u) >> 3;
+    const uint32_t u = (uint32_t)(tile % tiles_x) * 8u + (lane & 7u);
+    const uint64_t vr = (tile / tiles_x) * 8u + (lane >> 3);
+    if (u >= p.width || vr >= p.rows) return;
+    const double* T = poses + 12ull * blockIdx.y;
+    const double xn = ((double)u - p.cx) / p.fx;
+    const double yn = ((double)(uint32_t)(p.row0 + vr) - p.cy) / p.fy;
+    double O[3], D[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        O[a] = T[4 * a + 3];
+        D[a] = (T[4 * a] * xn + T[4 * a + 1] * yn) + T[4 * a + 2];
+    }
+    hits[(uint64_t)blockIdx.y * p.view_stride + vr * p.width + u] = ray_march(g, t, p, O, D);
+}
+
 // ---- surface mesh (hfpf_extract_mesh*, include/hfpf.h) --------------------------------------------------------------------
 // Lattice and cube keys are x << 42 | y << 21 | z (21 bits an axis: lattice points reach dim, which make_key's widths do not cover).
 // The cube set is the candidate rows' cells dilated by 1 (three 1-D dilations, each emit -> sort -> unique), the corner set the cubes

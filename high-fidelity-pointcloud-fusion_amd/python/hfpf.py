@@ -92,6 +92,7 @@ EXPORTS = [
     "hfpf_track_depth", "hfpf_track_depth_device", "hfpf_track",
     "hfpf_query", "hfpf_query_device", "hfpf_query_depth",
     "hfpf_extract_mesh", "hfpf_extract_mesh_device", "hfpf_free_mesh", "hfpf_write_ply", "hfpf_check_mesh_opts",
+    "hfpf_check_raycast_opts", "hfpf_raycast", "hfpf_raycast_device", "hfpf_raycast_view", "hfpf_raycast_view_device",
 ]
 
 # hfpf_depth_image formats (include/hfpf.h)
@@ -255,6 +256,46 @@ def mesh_opts(radius=2, min_count=0.0, max_distance=float("inf")):
     return o
 
 
+# hfpf_raycast_opts.flags, hfpf_ray_hit.flags, hfpf_ray and hfpf_ray_hit (include/hfpf.h)
+RAYCAST_CULL_BACKFACES = 1
+RAY_USED, RAY_HIT, RAY_BACKFACE, RAY_NEAR = 1, 2, 4, 8
+RAY_DTYPE = np.dtype([("o", "<f4", (3,)), ("d", "<f4", (3,))])
+RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("flags", "<u4"), ("p", "<f4", (3,)), ("n", "<f4", (3,)), ("row_voxel", "<i4", (3,)),
+                          ("rgb", "<u4"), ("count", "<u4"), ("sample", "<u4"), ("reserved", "<u4", (2,))])
+assert RAY_DTYPE.itemsize == 24 and RAY_HIT_DTYPE.itemsize == 64
+
+
+class RaycastOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("radius", C.c_int32), ("reserved0", C.c_int32),
+                ("min_count", C.c_double), ("max_distance", C.c_double), ("step", C.c_double), ("t_min", C.c_double),
+                ("t_max", C.c_double), ("reserved", C.c_uint64)]
+
+
+def raycast_opts(radius=2, min_count=0.0, max_distance=float("inf"), step=0.5, t_range=(0.0, 1.0), cull_backfaces=False):
+    """An hfpf_raycast_opts: the query window of the samples (1..4), the count and distance gates, the sample spacing in voxels and
+    the ray interval (metres along a general ray, z_near / z_far of a view)."""
+    o = RaycastOpts()
+    o.struct_size = C.sizeof(RaycastOpts)
+    o.flags = RAYCAST_CULL_BACKFACES if cull_backfaces else 0
+    o.radius = int(radius)
+    o.min_count, o.max_distance, o.step = float(min_count), float(max_distance), float(step)
+    o.t_min, o.t_max = float(t_range[0]), float(t_range[1])
+    return o
+
+
+def check_raycast_opts(o):
+    """hfpf_check_raycast_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
+    return lib().hfpf_check_raycast_opts(C.byref(o) if o is not None else None)
+
+
+def _rays(rays):
+    """(n, 6) float32 (origin, direction) or RAY_DTYPE records -> contiguous RAY_DTYPE."""
+    rays = np.asarray(rays)
+    if rays.dtype != RAY_DTYPE:
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6).view(RAY_DTYPE).reshape(-1)
+    return np.ascontiguousarray(rays)
+
+
 def write_ply(verts, tris, path):
     """hfpf_write_ply of MESH_VERTEX_DTYPE vertices and (n, 3) uint32 triangles (host code, no GPU needed)."""
     verts = np.ascontiguousarray(verts, MESH_VERTEX_DTYPE)
@@ -351,6 +392,12 @@ def lib():
     L.hfpf_free_mesh.restype = None
     L.hfpf_write_ply.argtypes = [vp, u64, vp, u64, C.c_char_p]
     L.hfpf_check_mesh_opts.argtypes = [C.POINTER(MeshOpts)]
+    dbl = C.c_double
+    L.hfpf_check_raycast_opts.argtypes = [C.POINTER(RaycastOpts)]
+    L.hfpf_raycast.argtypes = [vp, C.POINTER(RaycastOpts), vp, u64, vp, vp]
+    L.hfpf_raycast_device.argtypes = [vp, C.POINTER(RaycastOpts), vp, u64, vp, vp]
+    L.hfpf_raycast_view.argtypes = [vp, C.POINTER(RaycastOpts), u32, u32, dbl, dbl, dbl, dbl, vp, vp]
+    L.hfpf_raycast_view_device.argtypes = [vp, C.POINTER(RaycastOpts), u32, u32, dbl, dbl, dbl, dbl, u32, vp, vp]
     _lib = L
     return L
 
@@ -677,6 +724,63 @@ class OccupancyGrid:
         v, nv, t, nt = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
         self._chk(lib().hfpf_extract_mesh_device(self._h, C.byref(o), C.byref(v), C.byref(nv), C.byref(t), C.byref(nt)))
         return v.value or 0, nv.value, t.value or 0, nt.value
+
+    # -- casting rays against the model --
+    def raycast(self, rays, pose, opts=None, **kw):
+        """First surface crossing of each ray (hfpf_raycast).  rays: (n, 6) float32 (origin, direction) in the camera frame or RAY_DTYPE
+        records in pageable memory; pose = camera -> fusion frame 3x4.  Keywords as raycast_opts().  Returns RAY_HIT_DTYPE hits."""
+        o = opts if opts is not None else raycast_opts(**kw)
+        rays = _rays(rays)
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        hits = np.empty(len(rays), RAY_HIT_DTYPE)
+        self._chk(lib().hfpf_raycast(self._h, C.byref(o), _p(rays) if len(rays) else None, len(rays), _p(pose), _p(hits)))
+        return hits
+
+    def raycast_device(self, dev_rays, n_rays, pose, dev_hits=0, opts=None, **kw):
+        """The same for rays resident in HBM (hfpf_raycast_device).  With dev_hits the hits stay in that device buffer and None is
+        returned; otherwise they go to a scratch device buffer and come back as raycast() returns them."""
+        o = opts if opts is not None else raycast_opts(**kw)
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        own = not dev_hits
+        if own:
+            dev_hits = self.device_alloc(max(1, n_rays) * RAY_HIT_DTYPE.itemsize)
+        try:
+            self._chk(lib().hfpf_raycast_device(self._h, C.byref(o), C.c_void_p(dev_rays), n_rays, _p(pose), C.c_void_p(dev_hits)))
+            if not own:
+                return None
+            return self.device_download(dev_hits, n_rays * RAY_HIT_DTYPE.itemsize).view(RAY_HIT_DTYPE)
+        finally:
+            if own:
+                self.device_free(dev_hits)
+
+    def raycast_view(self, pose, K, width, height, opts=None, **kw):
+        """The view rays of one pinhole view (hfpf_raycast_view): K = (fx, fy, cx, cy), t_range = (z_near, z_far); hit i = pixel
+        (i % width, i // width), its t the camera-frame depth.  Returns (height, width) RAY_HIT_DTYPE hits."""
+        o = opts if opts is not None else raycast_opts(**kw)
+        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        hits = np.empty((int(height), int(width)), RAY_HIT_DTYPE)
+        self._chk(lib().hfpf_raycast_view(self._h, C.byref(o), int(width), int(height), float(K[0]), float(K[1]), float(K[2]), float(K[3]),
+                                          _p(pose), _p(hits) if hits.size else None))
+        return hits
+
+    def raycast_views_device(self, poses, K, width, height, dev_hits=0, opts=None, **kw):
+        """A batch of views into HBM (hfpf_raycast_view_device): poses (n, 3, 4); view v's hits start v * width * height behind
+        dev_hits.  Without dev_hits they go to a scratch device buffer and come back as (n, height, width) hits."""
+        o = opts if opts is not None else raycast_opts(**kw)
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12)
+        n = len(poses) * int(width) * int(height)
+        own = not dev_hits
+        if own:
+            dev_hits = self.device_alloc(max(1, n) * RAY_HIT_DTYPE.itemsize)
+        try:
+            self._chk(lib().hfpf_raycast_view_device(self._h, C.byref(o), int(width), int(height), float(K[0]), float(K[1]), float(K[2]),
+                                                     float(K[3]), len(poses), _p(poses) if len(poses) else None, C.c_void_p(dev_hits)))
+            if not own:
+                return None
+            return self.device_download(dev_hits, n * RAY_HIT_DTYPE.itemsize).view(RAY_HIT_DTYPE).reshape(len(poses), int(height), int(width))
+        finally:
+            if own:
+                self.device_free(dev_hits)
 
     def query_depth(self, depth, pose, K, depth_scale=0.001, opts=None, radius=1, min_count=0.0, max_distance=float("inf"), zclip=False,
                     rows=True):

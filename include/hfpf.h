@@ -549,6 +549,104 @@ int hfpf_extract_mesh_device(hfpf_handle* h, const hfpf_mesh_opts* o, hfpf_mesh_
  * list uchar uint vertex_indices.  Host code, no GPU needed. */
 int hfpf_write_ply(const hfpf_mesh_vertex* verts, uint64_t n_verts, const uint32_t* tris, uint64_t n_tris, const char* path);
 
+/* ---- casting rays against the fused model (first surface crossing per ray; no reference counterpart) ------------------------
+ * The surface is the mesh's: the zero set of "signed distance to the tangent plane of the nearest row" (hfpf_query's
+ * signed_distance), sampled along rays instead of on the lattice.  Everything is restatable from hfpf_extract's rows and
+ * hfpf_get_occupied's list (tests/raycast_ref.py).  Arithmetic is f64, one rounding per operation, left to right, never contracted.
+ * T is a row-major [R|t], camera -> fusion frame.
+ * General ray i: a packed hfpf_ray {o, d} in the camera frame.  O[a] = ((T[4a]*ox + T[4a+1]*oy) + T[4a+2]*oz) + T[4a+3],
+ *   W[a] = (T[4a]*dx + T[4a+1]*dy) + T[4a+2]*dz, L = sqrt((W0*W0 + W1*W1) + W2*W2), D[a] = W[a] / L.  The ray is USED iff its six
+ *   inputs are finite and L is finite and > 0.  t0 = t_min, t1 = t_max, metres along the ray.
+ * View ray of pixel (u, v), i = v*width + u, of the pinhole (width, height, fx, fy, cx, cy): xn = ((double)u - cx) / fx,
+ *   yn = ((double)v - cy) / fy, O = (T[3], T[7], T[11]), D[a] = (T[4a]*xn + T[4a+1]*yn) + T[4a+2].  D is NOT normalised: the ray
+ *   parameter is the camera-frame depth, so t compares directly with a depth frame and with hfpf_render's depth plane.  Always
+ *   USED.  t0 = t_min is z_near, t1 = t_max is z_far.
+ * Samples: dt = step * res (res = hfpf_get_dims' resolution), n = (uint64)floor((t1 - t0) / dt) + 1, t_k = t0 + (double)k * dt for
+ *   k = 0..n-1 (from k, never accumulated), p_k[a] = (float)(O[a] + t_k * D[a]).  Sample k is the hfpf_query hit of the f32 point p_k
+ *   under the identity pose with the call's radius, min_count and max_distance and no z-clip: exactly a mesh corner sample.  It is
+ *   DEFINED iff that hit is FOUND; then s_k is its signed_distance (f32) and its row the hit's row.
+ * Crossing: the ray ends at the smallest k >= 1 for which samples k-1 and k are both defined and (s_{k-1} < 0) != (s_k < 0) (INSIDE
+ *   iff s < 0, as in the mesh).  s_{k-1} >= 0 > s_k is a front crossing; the other direction sets HFPF_RAY_BACKFACE, and with
+ *   HFPF_RAYCAST_CULL_BACKFACES it does not end the ray: the march goes on.
+ * Hit: w = (double)s_{k-1} / ((double)s_{k-1} - (double)s_k), th = t_{k-1} + w * dt, t = (float)th, p[a] = (float)(O[a] + th * D[a]),
+ *   sample = k.  n, row_voxel, rgb and count are those of the row of the endpoint with the smaller |s| (a tie goes to k-1); rgb as
+ *   hfpf_extract codes it, the normal as stored (fusion frame).
+ * Flags: USED; HIT; BACKFACE; NEAR = some sample up to the end of the march was defined (the ray came within the window of a row).
+ * No hit: t, p and n are NaN (0x7FC00000), row_voxel = -1, rgb = count = sample = 0.  An unused ray has flags = 0 and the same values.
+ * Limitation (the mesh's, unchanged): the function is only as consistent as the rows' orientation.  A row oriented inwards near a
+ * silhouette gives a sign change between its sample and a neighbour's that is not a crossing of the surface.
+ * A raycast changes nothing on the handle except device_bytes (its scratch: one byte per brick, per 4^3 and per 16^3 bricks of
+ * empty-space maps, and for the host forms up to 2^20 rays and hits per chunk; chunks do not change a byte of the result).  Host
+ * frames still waiting are launched first.  A handle before its first clean pass returns no hits.  Rejected with HFPF_ERR_BAD_ARG
+ * (the handle stays usable, nothing is written): struct_size != sizeof, unknown flags, reserved0 or reserved != 0, radius outside
+ * 1..4, min_count NaN, not max_distance > 0 (+inf allowed), step not finite or outside 0.125..4, t_min / t_max not finite or not
+ * 0 <= t_min < t_max, more than 2^20 samples per ray, a NULL or non-finite pose, NULL hits, a NULL ray buffer with n_rays > 0; for
+ * views width * height = 0 or above 2^31, fx or fy not finite and positive, cx or cy not finite; on the device rays not 4-byte or
+ * hits not 16-byte aligned.  n_rays = 0 (n_views = 0) returns HFPF_OK after these checks.  A handle with an RCCL communicator
+ * returns HFPF_ERR_STATE (a distributed raycast is not provided); a failed handle returns HFPF_ERR_STATE as extract does.  Every
+ * call returns when its outputs are complete. */
+#define HFPF_RAYCAST_CULL_BACKFACES 1u /* opts.flags: a back crossing does not end the ray */
+
+typedef struct hfpf_ray {        /* 24 bytes, packed */
+    float o[3];                  /* origin, camera frame */
+    float d[3];                  /* direction, camera frame, any length > 0 */
+} hfpf_ray;
+
+typedef struct hfpf_raycast_opts {
+    uint32_t struct_size;        /* = sizeof(hfpf_raycast_opts) */
+    uint32_t flags;              /* HFPF_RAYCAST_* */
+    int32_t radius;              /* 1..4 (typically 2): the query window of every sample */
+    int32_t reserved0;           /* 0 */
+    double min_count;            /* rows with count < max(1, min_count) are not candidates */
+    double max_distance;         /* > 0, +inf allowed: the query's distance gate */
+    double step;                 /* sample spacing in voxels, 0.125..4 (0.5 is the documented default) */
+    double t_min, t_max;         /* finite, 0 <= t_min < t_max: metres along a general ray, z_near / z_far of a view */
+    uint64_t reserved;           /* 0 */
+} hfpf_raycast_opts;
+
+#define HFPF_RAY_USED 1u         /* finite inputs and a direction of finite length > 0 (view rays: always) */
+#define HFPF_RAY_HIT 2u          /* a crossing ended the ray; t / p / n / row_voxel / rgb / count / sample describe it */
+#define HFPF_RAY_BACKFACE 4u     /* that crossing goes from inside (s < 0) to outside */
+#define HFPF_RAY_NEAR 8u         /* some sample of the march was defined */
+
+typedef struct hfpf_ray_hit {    /* 64 bytes */
+    float t;                     /* ray parameter of the crossing (metres; camera-frame depth for views); NaN without a hit */
+    uint32_t flags;              /* HFPF_RAY_* */
+    float p[3];                  /* the crossing in the fusion frame */
+    float n[3];                  /* the attribute row's normal, as stored */
+    int32_t row_voxel[3];        /* its (ix, iy, iz); -1 without a hit */
+    uint32_t rgb;                /* its colour as hfpf_extract codes it */
+    uint32_t count;              /* its count */
+    uint32_t sample;             /* k: the crossing lies between samples k-1 and k */
+    uint32_t reserved[2];        /* 0 */
+} hfpf_ray_hit;
+
+#ifdef __cplusplus
+static_assert(sizeof(hfpf_ray) == 24, "hfpf_ray is 24 bytes");
+static_assert(sizeof(hfpf_raycast_opts) == 64, "hfpf_raycast_opts is 64 bytes");
+static_assert(sizeof(hfpf_ray_hit) == 64, "hfpf_ray_hit is 64 bytes");
+#else
+_Static_assert(sizeof(hfpf_ray) == 24, "hfpf_ray is 24 bytes");
+_Static_assert(sizeof(hfpf_raycast_opts) == 64, "hfpf_raycast_opts is 64 bytes");
+_Static_assert(sizeof(hfpf_ray_hit) == 64, "hfpf_ray_hit is 64 bytes");
+#endif
+
+/* HFPF_OK if o passes the struct checks above, else HFPF_ERR_BAD_ARG (host code, no handle; the sample count needs a handle's
+ * resolution and is checked by the calls). */
+int hfpf_check_raycast_opts(const hfpf_raycast_opts* o);
+/* n_rays rays in pageable HOST memory, hits[i] in HOST memory describes ray i. */
+int hfpf_raycast(hfpf_handle* h, const hfpf_raycast_opts* o, const hfpf_ray* rays, uint64_t n_rays, const double pose_3x4[12],
+                 hfpf_ray_hit* hits);
+/* The same with rays and hits in DEVICE memory: one launch into the caller's buffers. */
+int hfpf_raycast_device(hfpf_handle* h, const hfpf_raycast_opts* o, const hfpf_ray* dev_rays, uint64_t n_rays, const double pose_3x4[12],
+                        hfpf_ray_hit* dev_hits);
+/* The width * height view rays of one pinhole view; hits in HOST memory. */
+int hfpf_raycast_view(hfpf_handle* h, const hfpf_raycast_opts* o, uint32_t width, uint32_t height, double fx, double fy, double cx, double cy,
+                      const double pose_3x4[12], hfpf_ray_hit* hits);
+/* n_views views (poses: n_views * 12 doubles in HOST memory); view v's hits start v * width * height behind dev_hits (DEVICE memory). */
+int hfpf_raycast_view_device(hfpf_handle* h, const hfpf_raycast_opts* o, uint32_t width, uint32_t height, double fx, double fy, double cx,
+                             double cy, uint32_t n_views, const double* poses, hfpf_ray_hit* dev_hits);
+
 /* <directory_name>/test_cloud.pcd (node.cpp:395): PCD v0.7 ASCII, FIELDS x y z rgb normal_x normal_y normal_z curvature */
 int hfpf_write_pcd(const hfpf_row* rows, uint64_t n_rows, const char* path);
 /* <directory_name>/meta.csv (node.cpp:396) with the header string of grid.hpp:462 */
@@ -623,7 +721,8 @@ int hfpf_device_copy(hfpf_handle* h, void* dev_dst, const void* dev_src, uint64_
  * kernel ids: 0 = integrate calls (bin plan + k_integrate + k_update_cells + k_buffer), 1 = whole clean passes (first to last
  * kernel of hfpf_clean, host read-backs included).  enable = 2 additionally brackets the kernels of every integrate call:
  * 2 = k_integrate, 3 = k_update_cells / k_update, 4 = k_buffer (three more event records per call: use it for a breakdown
- * pass, not for the headline timing).  total_ms / launches accumulate since enable. */
+ * pass, not for the headline timing).  5 = k_raycast launches of hfpf_raycast* (the march alone, without the empty-space maps and
+ * the copies; any enable).  total_ms / launches accumulate since enable. */
 int hfpf_kernel_timing(hfpf_handle* h, int enable);
 int hfpf_get_kernel_time(hfpf_handle* h, int kernel_id, double* total_ms, uint64_t* launches);
 
