@@ -270,6 +270,8 @@ struct hfpf_handle {
     // bases, the host form's output, a unique count
     DevBuf mesh_cube, mesh_corner, mesh_kdata, mesh_cdata, mesh_out, mesh_ctr;
     DevBuf ray_in, ray_out, ray_map;       // hfpf_raycast*: a host chunk's rays, a chunk's (or band's) hits, the empty-space maps
+    DevBuf snap_stage, snap_err;           // hfpf_snapshot / hfpf_restore: the staging buffer (or one window of it), the range check's error word
+    bool epoch_used = false;               // epoch records or statistic words have left or entered this handle: no snapshot (include/hfpf.h)
     unsigned long long* h_ctr = nullptr;  // pinned mirror of the counters
     unsigned long long* mbox = nullptr;   // coherent pinned mailbox k_publish_counters writes (HFPF_MAILBOX=0: blit copies + synchronize)
     unsigned long long mbox_seq = 0;
@@ -1634,7 +1636,7 @@ int hfpf_destroy(hfpf_handle* h)
     for (DevBuf* b : {&h->sort_tmp, &h->keys_a, &h->keys_b, &h->vals_a, &h->vals_b, &h->rows_dev, &h->probe_a, &h->probe_b, &h->probe_c, &h->probe_d,
                       &h->probe_e, &h->probe_f, &h->zbuf, &h->render_pose, &h->render_out, &h->track_in, &h->track_acc,
                       &h->query_in, &h->query_out, &h->mesh_cube, &h->mesh_corner, &h->mesh_kdata, &h->mesh_cdata, &h->mesh_out,
-                      &h->mesh_ctr, &h->ray_in, &h->ray_out, &h->ray_map})
+                      &h->mesh_ctr, &h->ray_in, &h->ray_out, &h->ray_map, &h->snap_stage, &h->snap_err})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf* b : {&h->ex_send, &h->ex_recv, &h->ex_counts, &h->stats_total, &h->bin_pt_buf, &h->bin_rgb_buf, &h->bin_sums, &h->ovf_pt_buf, &h->ovf_aux_buf, &h->pend_a, &h->pend_b})
         if (b->p) (void)hipFree(b->p);
@@ -3116,6 +3118,7 @@ int hfpf_stats_export(hfpf_handle* h, const void** dev_words, uint64_t* n_words,
     if (!rc) rc = read_counters(h);
     if (!rc) rc = poison_on_error(h, check_device_errors(h));
     if (rc) return rc;
+    h->epoch_used = true;
     *dev_words = h->t.stats;
     *n_words = (h->h_ctr[C_NORMALS] + 1) * kStatWords;
     if (dev_cwords) *dev_cwords = nullptr;  // colour sums are words 5-7 of the same records
@@ -3133,6 +3136,7 @@ int hfpf_epoch_export(hfpf_handle* h, const void** dev_records, uint64_t* n_reco
     int rc = check_usable(h);
     if (!rc) rc = epoch_export_locked(h, &n, 0);
     if (rc) return rc;
+    h->epoch_used = true;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     *dev_records = h->ex_send.p;
     *n_records = n;
@@ -3145,6 +3149,7 @@ int hfpf_epoch_import(hfpf_handle* h, const void* dev_records, uint64_t n_record
     std::lock_guard<std::mutex> lk(h->mtx);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (int rcf = flush_pending_locked(h)) return rcf;  // host frames still waiting for their launch
+    h->epoch_used = true;
     int rc = epoch_import_locked(h, dev_records, n_records);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller may reuse / free the record buffer
@@ -3160,6 +3165,7 @@ int hfpf_epoch_import_gathered(hfpf_handle* h, const void* dev_buffer, uint64_t 
     if (int rcf = flush_pending_locked(h)) return rcf;  // host frames still waiting for their launch
     if (int rc0 = check_usable(h)) return rc0;
     std::vector<unsigned long long> c(counts, counts + world);
+    h->epoch_used = true;
     int rc = import_gathered_locked(h, dev_buffer, slice_stride_bytes, world, my_rank, c.data());
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller may reuse / free the buffer
@@ -3412,11 +3418,9 @@ int hfpf_write_pcd_binary(const hfpf_row* rows, uint64_t n, const char* path)
     return (fclose(f) == 0 && ok) ? HFPF_OK : HFPF_ERR_IO;
 }
 
-int hfpf_clear(hfpf_handle* h)
+// hfpf_clear under the handle's lock (hfpf_restore begins with it).
+static int clear_locked(hfpf_handle* h)
 {
-    if (!h) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
     h->pend_n = 0;  // host frames still waiting for their launch would be wiped with the rest
     // how far the session got (the counters as the device has them now); a handle whose stream has failed is reset in full
     uint64_t bricks_used = ~0ull, normals_used = ~0ull;
@@ -3427,6 +3431,634 @@ int hfpf_clear(hfpf_handle* h)
     int rc = reset_state(h, bricks_used, normals_used);
     h->dirty = true;  // clearVoxels sets state_changed, grid.hpp:169
     return rc;
+}
+
+int hfpf_clear(hfpf_handle* h)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    return clear_locked(h);
+}
+
+// ---- snapshot / restore (include/hfpf.h) -----------------------------------------------------------------
+// A blob = a 4096-byte header + the payload: sections, each 256-byte aligned, listed in the header as (id, offset, bytes).  The
+// payload is what the staging buffer on the device holds: the pack kernels (kernels.hpp k_snap_*) gather the used prefix of every
+// pool into it and it crosses the link through download_pageable / upload_pageable, whole or in windows.
+}  // extern "C"
+namespace {
+
+constexpr uint32_t kSnapVersion = 1;
+constexpr uint32_t kSnapLayoutRev = 1;  // bump when a table's meaning changes without its shape changing
+constexpr uint64_t kSnapLayoutTag = ((uint64_t)kSnapLayoutRev << 48) | ((uint64_t)kChains << 40) | ((uint64_t)kLogRegions << 32) | ((uint64_t)kStatWords << 24) |
+                                    ((uint64_t)sizeof(DepEntry) << 16) | ((uint64_t)C_COUNT << 8) | (uint64_t)kBrickShift;
+constexpr char kSnapMagic[8] = {'H', 'F', 'P', 'F', 'S', 'N', 'A', 'P'};
+constexpr uint32_t kSnapMaxSections = 32;
+constexpr uint32_t kSnapSemanticFlags = HFPF_FLAG_FUSE_COLOR | HFPF_FLAG_PCL_SHIFTED_COV;
+
+enum SnapSectionId : uint32_t {
+    SS_CTR = 1, SS_LOG_CTR, SS_INFO, SS_FIRST_FRAME, SS_BUF_HEAD, SS_STAT_ID, SS_PRE_DEP, SS_OCC_MASK, SS_ND_MASK, SS_BRICKS, SS_LOG_PT, SS_LOG_RGB,
+    SS_NV_KEY, SS_NV_SLOT, SS_NV_C, SS_NV_N, SS_NV_LINE, SS_STATS, SS_REG_OCC, SS_DEP, SS_OCC_LIST, SS_PREREG, SS_FRAMES, SS_PEND
+};
+struct SnapSection {
+    uint32_t id, reserved;
+    uint64_t offset, bytes;  // offset into the payload (a multiple of 256); bytes without the padding behind them
+};
+struct SnapHeader {  // at the front of the 4096 header bytes; the rest of them is zero.  Every field is naturally aligned: no padding.
+    char magic[8];
+    uint32_t version, header_bytes;
+    uint64_t layout_tag, total_bytes, payload_bytes, payload_checksum, header_checksum;  // header_checksum: over the 4096 bytes with this field 0
+    float resolution;
+    uint32_t flags;
+    double bbox[6];
+    int32_t k, K, gate, reserved0;
+    double cylinder_radius, ball_radius, z_clip_min, z_clip_max;
+    uint64_t need_bricks, log_points, need_normals, need_frames;
+    uint64_t frames_integrated, clean_passes, next_frame_id, voxels_occupied, voxels_with_normal;
+    uint32_t dirty, pend_valid, normals_possible, n_sections;
+    uint64_t gate_done, direct_linked;
+    uint64_t n_bricks, n_normals, n_occ, n_reg, n_prereg, n_dep, n_frames, n_pend;
+    uint64_t n_linked[kLogRegions], log_n[kLogRegions];
+    SnapSection sec[kSnapMaxSections];
+};
+static_assert(sizeof(SnapHeader) <= HFPF_SNAPSHOT_HEADER_BYTES, "the snapshot header has a fixed size");
+static_assert(sizeof(struct hfpf_snapshot_info) == 248, "hfpf_snapshot_info layout");
+
+// 64-bit checksum of n bytes (n a multiple of 32: sections are 256-byte aligned): four interleaved multiply-xorshift lanes over the
+// 8-byte words, folded at the end.  Not cryptographic: it catches truncation, bit rot and mixed-up files.
+uint64_t snap_checksum(const void* data, uint64_t n)
+{
+    const uint64_t kMul = 0x9E3779B97F4A7C15ull;
+    uint64_t a = 0x243F6A8885A308D3ull, b = 0x13198A2E03707344ull, c = 0xA4093822299F31D0ull, d = 0x082EFA98EC4E6C89ull;
+    const uint8_t* p = (const uint8_t*)data;
+    for (uint64_t i = 0; i + 32 <= n; i += 32) {
+        uint64_t w[4];
+        memcpy(w, p + i, 32);
+        a = (a ^ w[0]) * kMul, a ^= a >> 29;
+        b = (b ^ w[1]) * kMul, b ^= b >> 29;
+        c = (c ^ w[2]) * kMul, c ^= c >> 29;
+        d = (d ^ w[3]) * kMul, d ^= d >> 29;
+    }
+    uint64_t r = n;
+    for (uint64_t v : {a, b, c, d}) r = (r ^ v) * kMul, r ^= r >> 32;
+    return r;
+}
+
+uint64_t snap_header_checksum(const uint8_t* hdr)
+{
+    uint8_t tmp[HFPF_SNAPSHOT_HEADER_BYTES];
+    memcpy(tmp, hdr, sizeof tmp);
+    memset(tmp + offsetof(SnapHeader, header_checksum), 0, 8);
+    return snap_checksum(tmp, sizeof tmp);
+}
+
+// The header of a blob, validated as far as the header alone allows: 0, or why not (a static text).
+const char* snap_parse_header(const void* blob, uint64_t bytes, SnapHeader* hd)
+{
+    if (!blob || bytes < HFPF_SNAPSHOT_HEADER_BYTES) return "shorter than a snapshot header";
+    memcpy(hd, blob, sizeof *hd);
+    if (memcmp(hd->magic, kSnapMagic, 8) != 0) return "not a snapshot (magic)";
+    if (hd->version != kSnapVersion || hd->header_bytes != HFPF_SNAPSHOT_HEADER_BYTES) return "unknown snapshot format version";
+    if (hd->header_checksum != snap_header_checksum((const uint8_t*)blob)) return "header checksum mismatch";
+    if (hd->n_sections > kSnapMaxSections || hd->total_bytes != hd->payload_bytes + HFPF_SNAPSHOT_HEADER_BYTES || (hd->payload_bytes & 255u)) return "inconsistent header";
+    return nullptr;
+}
+
+// How much of every pool a session used (from the counters at snapshot, from the header at restore).
+struct SnapUsed {
+    uint64_t n_bricks, n_normals, n_occ, n_reg, n_prereg, n_dep, n_frames, n_pend;
+    uint64_t log_n[kLogRegions];
+};
+
+inline uint64_t up16(uint64_t v) { return (v + 15) & ~15ull; }
+inline uint64_t up256(uint64_t v) { return (v + 255) & ~255ull; }
+// bytes in front of append region r of the colour log that make its first entry's unit 16-byte aligned (entries are 1-based)
+inline uint32_t snap_rgb_head(uint64_t region_cap, int r) { return (uint32_t)((((uint64_t)r * region_cap + 1) & 3u) * 4u); }
+
+// The sections of a session, in file order; the same function lays a blob out at snapshot and reads it back at restore.
+uint32_t snap_layout(const SnapUsed& u, bool color, uint64_t region_cap, SnapSection* sec, uint64_t* payload_bytes)
+{
+    const uint64_t cells = u.n_bricks * (uint64_t)kBrickCells, rec = u.n_normals ? u.n_normals + 1 : 0;
+    uint64_t log_pt = 0, log_rgb = 0;
+    for (int r = 0; r < kLogRegions; r++) {
+        log_pt += u.log_n[r] * sizeof(float4);
+        if (u.log_n[r]) log_rgb += up16(snap_rgb_head(region_cap, r) + u.log_n[r] * 4);
+    }
+    const struct {
+        uint32_t id;
+        uint64_t bytes;
+    } all[] = {{SS_CTR, C_COUNT * 8}, {SS_LOG_CTR, kLogRegions * 16 * 8}, {SS_INFO, cells * 8}, {SS_FIRST_FRAME, cells * 4}, {SS_BUF_HEAD, cells * 4 * kChains},
+               {SS_STAT_ID, cells * 4}, {SS_PRE_DEP, cells * 4}, {SS_OCC_MASK, u.n_bricks * 64}, {SS_ND_MASK, u.n_bricks * 128}, {SS_BRICKS, u.n_bricks * 16},
+               {SS_LOG_PT, log_pt}, {SS_LOG_RGB, color ? log_rgb : 0}, {SS_NV_KEY, rec * 8}, {SS_NV_SLOT, rec * 4}, {SS_NV_C, rec * 12}, {SS_NV_N, rec * 12},
+               {SS_NV_LINE, rec * 32}, {SS_STATS, rec * kStatWords * 8}, {SS_REG_OCC, u.n_reg * 8}, {SS_DEP, u.n_dep * sizeof(DepEntry)}, {SS_OCC_LIST, u.n_occ * 4},
+               {SS_PREREG, u.n_prereg * 4}, {SS_FRAMES, u.n_frames * 16}, {SS_PEND, u.n_pend * 4}};
+    uint32_t n = 0;
+    uint64_t off = 0;
+    for (const auto& a : all) {
+        sec[n++] = SnapSection{a.id, 0u, off, a.bytes};
+        off += up256(a.bytes);
+    }
+    *payload_bytes = off;
+    return n;
+}
+
+struct SnapSpan {  // kernels.hpp SnapSpans, one entry
+    uint64_t pool, stage, bytes;
+    uint32_t head;
+};
+
+// The copy spans of a session on this handle (everything but the two gathered sections).  pend = the pending-cell list.
+void snap_spans(hfpf_handle* h, const SnapUsed& u, const SnapSection* sec, uint32_t n_sec, std::vector<SnapSpan>* out)
+{
+    const Tables& t = h->t;
+    const uint64_t c0 = kBrickCells;  // the first cell of brick 1
+    auto at = [&](uint32_t id) -> const SnapSection& {
+        for (uint32_t i = 0; i < n_sec; i++)
+            if (sec[i].id == id) return sec[i];
+        return sec[0];
+    };
+    auto add = [&](uint32_t id, const void* pool, uint32_t head = 0) {
+        const SnapSection& s = at(id);
+        if (s.bytes) out->push_back(SnapSpan{(uint64_t)(uintptr_t)pool, s.offset, s.bytes, head});
+    };
+    add(SS_CTR, t.ctr);
+    add(SS_LOG_CTR, t.log_ctr);
+    add(SS_INFO, t.info + c0);
+    add(SS_FIRST_FRAME, t.first_frame + c0);
+    add(SS_BUF_HEAD, t.buf_head + c0 * kChains);
+    add(SS_STAT_ID, t.stat_id + c0);
+    add(SS_PRE_DEP, t.pre_dep + c0);
+    add(SS_OCC_MASK, t.occ_mask + 8);
+    add(SS_ND_MASK, t.nd_mask + 16);
+    add(SS_NV_KEY, t.nv_key, 8);  // record 0 does not exist: head
+    add(SS_NV_SLOT, t.nv_slot, 4);
+    add(SS_NV_C, t.nv_c, 12);
+    add(SS_NV_N, t.nv_n, 12);
+    add(SS_NV_LINE, t.nv_line, 32);
+    add(SS_STATS, t.stats);
+    add(SS_REG_OCC, t.reg_occ);
+    add(SS_DEP, t.dep);
+    add(SS_OCC_LIST, t.occ_list);
+    add(SS_PREREG, t.prereg_list);
+    add(SS_PEND, h->pend_a.p);
+    uint64_t off_pt = at(SS_LOG_PT).offset, off_rgb = at(SS_LOG_RGB).offset;
+    for (int r = 0; r < kLogRegions; r++) {
+        if (!u.log_n[r]) continue;
+        const uint64_t first = (uint64_t)r * t.log_region_cap + 1;  // the region's first entry
+        out->push_back(SnapSpan{(uint64_t)(uintptr_t)(t.log_pt + first), off_pt, u.log_n[r] * sizeof(float4), 0u});
+        off_pt += u.log_n[r] * sizeof(float4);
+        if (t.color) {
+            const uint32_t head = snap_rgb_head(t.log_region_cap, r);
+            out->push_back(SnapSpan{(uint64_t)(uintptr_t)(t.log_rgb + (first & ~3ull)), off_rgb, head + u.log_n[r] * 4, head});
+            off_rgb += up16(head + u.log_n[r] * 4);
+        }
+    }
+}
+
+// Pack (device -> staging) or unpack the part of the payload inside the window [w0, w1) (multiples of 16); the staging buffer
+// holds that window from its first byte.
+template <bool PACK>
+int snap_move_window(hfpf_handle* h, const SnapUsed& u, const SnapSection* sec, uint32_t n_sec, const std::vector<SnapSpan>& spans, const SnapLimits& lim, uint64_t w0,
+                     uint64_t w1)
+{
+    uint8_t* stage = (uint8_t*)h->snap_stage.p;
+    SnapSpans sp;
+    memset(&sp, 0, sizeof sp);
+    auto flush = [&]() {
+        if (sp.n == 0) return;
+        hipLaunchKernelGGL(k_snap_copy<PACK>, dim3(sp.tile0[sp.n]), dim3(256), 0, h->stream, sp, stage);
+        memset(&sp, 0, sizeof sp);
+    };
+    for (const SnapSpan& full : spans) {
+        const uint64_t lo = std::max(full.stage, w0), hi = std::min(full.stage + up16(full.bytes), w1);
+        if (lo >= hi) continue;
+        const uint64_t skip = lo - full.stage;  // (a multiple of 16)
+        const uint64_t bytes = std::min(full.bytes - skip, hi - lo);
+        const uint32_t head = (uint32_t)(full.head > skip ? full.head - skip : 0);
+        const uint64_t tiles = (up16(bytes) / 16 + kSnapTileUnits - 1) / kSnapTileUnits;
+        if (sp.n == kSnapSpans || (uint64_t)sp.tile0[sp.n] + tiles > 0x7FFFFFFFull) flush();
+        sp.pool[sp.n] = full.pool + skip;
+        sp.stage[sp.n] = lo - w0;
+        sp.bytes[sp.n] = bytes;
+        sp.head[sp.n] = head;
+        sp.tile0[sp.n + 1] = sp.tile0[sp.n] + (uint32_t)tiles;
+        sp.n++;
+    }
+    flush();
+    // the gathered sections: 16-byte records
+    for (uint32_t i = 0; i < n_sec; i++) {
+        if ((sec[i].id != SS_BRICKS && sec[i].id != SS_FRAMES) || !sec[i].bytes) continue;
+        const uint64_t lo = std::max(sec[i].offset, w0), hi = std::min(sec[i].offset + sec[i].bytes, w1);
+        if (lo >= hi) continue;
+        const uint32_t first = (uint32_t)((lo - sec[i].offset) / 16), n = (uint32_t)((hi - lo) / 16);
+        uint4* rec = (uint4*)(stage + (lo - w0));
+        if (sec[i].id == SS_BRICKS) hipLaunchKernelGGL(k_snap_bricks<PACK>, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->t, lim, rec, first, n, (uint32_t*)h->snap_err.p);
+        else hipLaunchKernelGGL(k_snap_frames<PACK>, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->t, rec, first, n, (uint32_t*)h->snap_err.p);
+    }
+    HIPCHK(h, hipGetLastError());
+    (void)u;
+    return HFPF_OK;
+}
+
+// A staging buffer for `payload` bytes, or -- when the device has no room for it -- for the largest window it has room for (halved
+// until the allocation succeeds; a window is a multiple of 1 MB).  HFPF_TEST_SNAPSHOT_WINDOW=<bytes> (tests) caps it.
+int snap_stage_alloc(hfpf_handle* h, uint64_t payload, uint64_t* window)
+{
+    uint64_t want = std::max<uint64_t>(up256(payload), 4096);
+    if (const char* e = getenv("HFPF_TEST_SNAPSHOT_WINDOW")) want = std::min<uint64_t>(want, std::max<uint64_t>((uint64_t)atoll(e) & ~4095ull, 4096));
+    if (h->snap_stage.p && h->snap_stage.bytes >= want) {
+        *window = want;
+        return HFPF_OK;
+    }
+    if (h->snap_stage.p) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipFree(h->snap_stage.p));
+        h->device_bytes -= h->snap_stage.bytes;
+        h->snap_stage = DevBuf{};
+    }
+    for (;;) {
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, want);
+        if (e == hipSuccess) {
+            h->snap_stage.p = p;
+            h->snap_stage.bytes = want;
+            h->device_bytes += want;
+            *window = want;
+            return HFPF_OK;
+        }
+        (void)hipGetLastError();
+        if (e != hipErrorOutOfMemory || want <= (1u << 20)) return fail(h, HFPF_ERR_HIP, "snapshot staging: hipMalloc(%llu) failed: %s", (unsigned long long)want, hipGetErrorString(e));
+        want = std::max<uint64_t>((want / 2 + (1u << 20) - 1) & ~(uint64_t)((1u << 20) - 1), 1u << 20);
+    }
+}
+
+int snap_refuse_distributed(hfpf_handle* h, const char* what)
+{
+    if (h->dist_on) return fail(h, HFPF_ERR_STATE, "%s: not available on a handle with an RCCL communicator", what);
+    if (h->epoch_used) return fail(h, HFPF_ERR_STATE, "%s: this handle has exchanged epoch records or statistic words; a distributed snapshot is not provided", what);
+    return HFPF_OK;
+}
+
+SnapLimits snap_limits(const hfpf_handle* h, const SnapUsed& u)
+{
+    SnapLimits lim;
+    memset(&lim, 0, sizeof lim);
+    lim.n_slots = (u.n_bricks + 1) * (uint64_t)kBrickCells;
+    lim.n_normals = u.n_normals, lim.n_dep = u.n_dep, lim.n_reg = u.n_reg, lim.n_prereg = u.n_prereg, lim.n_occ = u.n_occ, lim.n_pend = u.n_pend;
+    lim.max_frames = h->t.max_frames;
+    lim.dir_entries = h->dir_entries;
+    lim.region_cap = h->t.log_region_cap;
+    lim.n_bricks = (uint32_t)u.n_bricks;
+    for (int r = 0; r < kLogRegions; r++) lim.log_n[r] = (uint32_t)u.log_n[r];
+    return lim;
+}
+
+int snapshot_locked(hfpf_handle* h, void** blob_out, uint64_t* bytes_out)
+{
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = snap_refuse_distributed(h, "snapshot");
+    if (rc) return rc;
+    // as extract: launch what waits, refuse a failed handle, read the counters (which waits for a clean pass still running)
+    rc = poison_on_error(h, flush_pending_locked(h));
+    if (!rc) rc = check_usable(h);
+    if (!rc) rc = read_counters(h);
+    if (!rc) rc = poison_on_error(h, check_device_errors(h));
+    if (rc) return rc;
+    const Tables& t = h->t;
+    const hfpf_config& c = h->cfg;
+    SnapUsed u{};
+    u.n_bricks = std::min<uint64_t>(h->h_ctr[C_BRICKS], t.max_bricks);
+    u.n_normals = std::min<uint64_t>(h->h_ctr[C_NORMALS], t.max_normals);
+    u.n_occ = std::min<uint64_t>(h->h_ctr[C_OCC], t.max_occ);
+    u.n_reg = std::min<uint64_t>(h->h_ctr[C_REG], t.max_reg);
+    u.n_prereg = std::min<uint64_t>(h->h_ctr[C_PREREG], t.max_reg);
+    u.n_dep = std::min<uint64_t>(h->h_ctr[C_DEP], t.max_dep);
+    u.n_frames = std::min<uint64_t>(h->h_ctr[C_FRAMES], t.max_frames);
+    u.n_pend = h->pend_valid ? h->h_ctr[C_PEND] : 0;
+    if (u.n_pend * 4 > h->pend_a.bytes) return fail(h, HFPF_ERR_STATE, "snapshot: pending-cell list of %llu entries exceeds its buffer (internal)", (unsigned long long)u.n_pend);
+    for (int r = 0; r < kLogRegions; r++) u.log_n[r] = std::min<uint64_t>(h->h_log_ctr[r * 16], t.log_region_cap);
+
+    uint8_t hdr_bytes[HFPF_SNAPSHOT_HEADER_BYTES];
+    memset(hdr_bytes, 0, sizeof hdr_bytes);
+    SnapHeader hd;
+    memset(&hd, 0, sizeof hd);
+    memcpy(hd.magic, kSnapMagic, 8);
+    hd.version = kSnapVersion;
+    hd.header_bytes = HFPF_SNAPSHOT_HEADER_BYTES;
+    hd.layout_tag = kSnapLayoutTag;
+    hd.n_sections = snap_layout(u, t.color != 0, t.log_region_cap, hd.sec, &hd.payload_bytes);
+    hd.total_bytes = hd.payload_bytes + HFPF_SNAPSHOT_HEADER_BYTES;
+    hd.resolution = c.resolution;
+    hd.flags = c.flags;
+    memcpy(hd.bbox, c.bbox, sizeof hd.bbox);
+    hd.k = c.k, hd.K = c.K, hd.gate = c.gate;
+    hd.cylinder_radius = c.cylinder_radius, hd.ball_radius = c.ball_radius, hd.z_clip_min = c.z_clip_min, hd.z_clip_max = c.z_clip_max;
+    {
+        const uint64_t per = 2ull * (uint64_t)c.K + 1ull;  // max_occ = 4 n, max_reg = (2K+1) n, max_dep = 2 max_reg (alloc_tables)
+        uint64_t nn = std::max<uint64_t>(u.n_normals, 1);
+        nn = std::max(nn, (u.n_occ + 3) / 4);
+        nn = std::max(nn, (std::max(u.n_reg, u.n_prereg) + per - 1) / per);
+        nn = std::max(nn, (u.n_dep + 2 * per - 1) / (2 * per));
+        hd.need_normals = nn;
+    }
+    hd.need_bricks = std::max<uint64_t>(u.n_bricks, 1);
+    hd.log_points = c.max_log_points;
+    hd.need_frames = 1;  // raised below to the largest frame id + 1
+    hd.frames_integrated = h->frames_integrated;
+    hd.clean_passes = h->clean_passes;
+    hd.next_frame_id = h->next_frame_id;
+    hd.voxels_occupied = h->h_ctr[C_OCC];
+    hd.voxels_with_normal = h->h_ctr[C_NORMALS];
+    hd.dirty = h->dirty ? 1 : 0;
+    hd.pend_valid = h->pend_valid ? 1 : 0;
+    hd.normals_possible = h->normals_possible ? 1 : 0;
+    hd.gate_done = h->gate_done;
+    hd.direct_linked = h->direct_linked;
+    hd.n_bricks = u.n_bricks, hd.n_normals = u.n_normals, hd.n_occ = u.n_occ, hd.n_reg = u.n_reg, hd.n_prereg = u.n_prereg, hd.n_dep = u.n_dep;
+    hd.n_frames = u.n_frames, hd.n_pend = u.n_pend;
+    for (int r = 0; r < kLogRegions; r++) hd.n_linked[r] = std::min(h->n_linked[r], u.log_n[r]), hd.log_n[r] = u.log_n[r];
+
+    uint64_t window = 0;
+    if ((rc = snap_stage_alloc(h, hd.payload_bytes, &window))) return rc;
+    if ((rc = scratch(h, h->snap_err, 64))) return rc;
+    uint8_t* blob = (uint8_t*)host_result_alloc(hd.total_bytes);
+    if (!blob) return fail(h, HFPF_ERR_CAPACITY, "snapshot: host allocation of %llu bytes failed", (unsigned long long)hd.total_bytes);
+    std::vector<SnapSpan> spans;
+    snap_spans(h, u, hd.sec, hd.n_sections, &spans);
+    const SnapLimits lim = snap_limits(h, u);
+    for (uint64_t w0 = 0; w0 < hd.payload_bytes; w0 += window) {
+        const uint64_t w1 = std::min(hd.payload_bytes, w0 + window);
+        hipError_t e = hipMemsetAsync(h->snap_stage.p, 0, w1 - w0, h->stream);  // the gaps between sections are zero
+        if (e == hipSuccess) rc = snap_move_window<true>(h, u, hd.sec, hd.n_sections, spans, lim, w0, w1);
+        if (e == hipSuccess && !rc) e = download_pageable(h, blob + HFPF_SNAPSHOT_HEADER_BYTES + w0, h->snap_stage.p, w1 - w0);
+        if (e != hipSuccess) rc = fail(h, HFPF_ERR_HIP, "snapshot download: %s", hipGetErrorString(e));
+        if (rc) {
+            free(blob);
+            return rc;
+        }
+    }
+    for (uint32_t i = 0; i < hd.n_sections; i++)  // the largest frame id this session integrated
+        if (hd.sec[i].id == SS_FRAMES)
+            for (uint64_t f = 0; f < u.n_frames; f++) {
+                uint32_t id;
+                memcpy(&id, blob + HFPF_SNAPSHOT_HEADER_BYTES + hd.sec[i].offset + 16 * f, 4);
+                hd.need_frames = std::max<uint64_t>(hd.need_frames, (uint64_t)id + 1);
+            }
+    hd.payload_checksum = snap_checksum(blob + HFPF_SNAPSHOT_HEADER_BYTES, hd.payload_bytes);
+    memcpy(hdr_bytes, &hd, sizeof hd);
+    hd.header_checksum = snap_header_checksum(hdr_bytes);
+    memcpy(hdr_bytes, &hd, sizeof hd);
+    memcpy(blob, hdr_bytes, sizeof hdr_bytes);
+    *blob_out = blob;
+    *bytes_out = hd.total_bytes;
+    return HFPF_OK;
+}
+
+int restore_locked(hfpf_handle* h, const void* blob, uint64_t bytes)
+{
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = snap_refuse_distributed(h, "restore");
+    if (rc) return rc;
+    // ---- everything the host can decide, before the handle is touched ----
+    SnapHeader hd;
+    if (const char* why = snap_parse_header(blob, bytes, &hd)) return fail(h, HFPF_ERR_BAD_ARG, "restore: %s", why);
+    if (hd.layout_tag != kSnapLayoutTag)
+        return fail(h, HFPF_ERR_BAD_ARG, "restore: the snapshot was written by a build with another table layout (tag %llx, this build %llx)", (unsigned long long)hd.layout_tag,
+                    (unsigned long long)kSnapLayoutTag);
+    if (bytes < hd.total_bytes) return fail(h, HFPF_ERR_BAD_ARG, "restore: %llu bytes given, the header says %llu", (unsigned long long)bytes, (unsigned long long)hd.total_bytes);
+    const uint8_t* payload = (const uint8_t*)blob + HFPF_SNAPSHOT_HEADER_BYTES;
+    if (snap_checksum(payload, hd.payload_bytes) != hd.payload_checksum) return fail(h, HFPF_ERR_BAD_ARG, "restore: payload checksum mismatch");
+    const hfpf_config& c = h->cfg;
+    const Tables& t = h->t;
+    uint32_t res_a, res_b;
+    memcpy(&res_a, &hd.resolution, 4);
+    memcpy(&res_b, &c.resolution, 4);
+    if (res_a != res_b || memcmp(hd.bbox, c.bbox, sizeof hd.bbox) != 0 || hd.k != c.k || hd.K != c.K || hd.gate != c.gate ||
+        memcmp(&hd.cylinder_radius, &c.cylinder_radius, 8) != 0 || memcmp(&hd.ball_radius, &c.ball_radius, 8) != 0 || memcmp(&hd.z_clip_min, &c.z_clip_min, 8) != 0 ||
+        memcmp(&hd.z_clip_max, &c.z_clip_max, 8) != 0 || ((hd.flags ^ c.flags) & kSnapSemanticFlags))
+        return fail(h, HFPF_ERR_BAD_CONFIG, "restore: the snapshot was made with another grid configuration (resolution, bbox, k, K, gate, radii, z-clips, colour / covariance flags)");
+    if (hd.log_points != c.max_log_points)
+        return fail(h, HFPF_ERR_BAD_CONFIG, "restore: max_log_points %llu, the snapshot needs exactly %llu (log indices are not remapped)", (unsigned long long)c.max_log_points,
+                    (unsigned long long)hd.log_points);
+    SnapUsed u{};
+    u.n_bricks = hd.n_bricks, u.n_normals = hd.n_normals, u.n_occ = hd.n_occ, u.n_reg = hd.n_reg, u.n_prereg = hd.n_prereg, u.n_dep = hd.n_dep;
+    u.n_frames = hd.n_frames, u.n_pend = hd.n_pend;
+    uint64_t log_total = 0;
+    for (int r = 0; r < kLogRegions; r++) {
+        u.log_n[r] = hd.log_n[r];
+        log_total += hd.log_n[r];
+        if (hd.log_n[r] > t.log_region_cap || hd.n_linked[r] > hd.log_n[r]) return fail(h, HFPF_ERR_BAD_ARG, "restore: log region %d out of range", r);
+    }
+    if (u.n_bricks > t.max_bricks || u.n_normals > t.max_normals || u.n_occ > t.max_occ || u.n_reg > t.max_reg || u.n_prereg > t.max_reg || u.n_dep > t.max_dep ||
+        hd.need_frames > t.max_frames || u.n_frames > t.max_frames)
+        return fail(h, HFPF_ERR_CAPACITY,
+                    "restore: the session needs max_bricks >= %llu, max_normals >= %llu, max_frames >= %llu (this handle: %llu, %llu, %llu)", (unsigned long long)hd.need_bricks,
+                    (unsigned long long)hd.need_normals, (unsigned long long)hd.need_frames, (unsigned long long)t.max_bricks, (unsigned long long)t.max_normals,
+                    (unsigned long long)t.max_frames);
+    if (u.n_pend > u.n_occ || hd.gate_done > u.n_occ) return fail(h, HFPF_ERR_BAD_ARG, "restore: inconsistent header (pending cells)");
+    {   // the section table must be the one this build lays out for these counts, and the counters in the payload the header's
+        SnapSection want[kSnapMaxSections];
+        uint64_t pb = 0;
+        const uint32_t n = snap_layout(u, t.color != 0, t.log_region_cap, want, &pb);
+        if (n != hd.n_sections || pb != hd.payload_bytes || memcmp(want, hd.sec, n * sizeof(SnapSection)) != 0)
+            return fail(h, HFPF_ERR_BAD_ARG, "restore: section table does not match the header's counts");
+        unsigned long long ctr[C_COUNT];
+        memcpy(ctr, payload + hd.sec[0].offset, sizeof ctr);  // (section 0 is SS_CTR)
+        if (ctr[C_BRICKS] != u.n_bricks || ctr[C_NORMALS] != u.n_normals || ctr[C_OCC] != u.n_occ || ctr[C_REG] != u.n_reg || ctr[C_PREREG] != u.n_prereg ||
+            ctr[C_DEP] != u.n_dep || ctr[C_FRAMES] != u.n_frames || ctr[C_ERR] != 0)
+            return fail(h, HFPF_ERR_BAD_ARG, "restore: counters in the payload do not match the header");
+        const uint8_t* lc = payload + hd.sec[1].offset;  // SS_LOG_CTR
+        for (int r = 0; r < kLogRegions; r++) {
+            unsigned long long n_r;
+            memcpy(&n_r, lc + (size_t)r * 16 * 8, 8);
+            if (n_r != u.log_n[r]) return fail(h, HFPF_ERR_BAD_ARG, "restore: log counters in the payload do not match the header");
+        }
+    }
+    (void)log_total;
+    // ---- from here on a failure leaves the handle as after hfpf_clear ----
+    if ((rc = clear_locked(h))) return rc;
+    auto bail = [&](int code) {
+        const std::string msg = h->err;
+        (void)hipStreamSynchronize(h->stream);
+        (void)reset_state(h);  // in full: what was uploaded is not to be trusted
+        h->dirty = true;
+        h->err = msg;
+        return code;
+    };
+    uint64_t window = 0;
+    if ((rc = snap_stage_alloc(h, hd.payload_bytes, &window))) return bail(rc);
+    if ((rc = scratch(h, h->snap_err, 64))) return bail(rc);
+    if (u.n_pend && (rc = scratch(h, h->pend_a, u.n_pend * 4))) return bail(rc);
+    if (hipMemsetAsync(h->snap_err.p, 0, 64, h->stream) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore: hipMemsetAsync failed"));
+    std::vector<SnapSpan> spans;
+    snap_spans(h, u, hd.sec, hd.n_sections, &spans);
+    const SnapLimits lim = snap_limits(h, u);
+    for (uint64_t w0 = 0; w0 < hd.payload_bytes; w0 += window) {
+        const uint64_t w1 = std::min(hd.payload_bytes, w0 + window);
+        const hipError_t e = upload_pageable(h, h->snap_stage.p, payload + w0, w1 - w0);
+        if (e != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore upload: %s", hipGetErrorString(e)));
+        if ((rc = snap_move_window<false>(h, u, hd.sec, hd.n_sections, spans, lim, w0, w1))) return bail(rc);
+        if (w1 < hd.payload_bytes && hipStreamSynchronize(h->stream) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore: unpack failed"));  // the window is reused
+    }
+    // range check of every index a later kernel would follow, before anything else touches the tables
+    if (u.n_bricks) hipLaunchKernelGGL(k_snap_check_slots, dim3(blocks_for(u.n_bricks * (uint64_t)kBrickCells, 256)), dim3(256), 0, h->stream, h->t, lim, (uint32_t*)h->snap_err.p);
+    {
+        uint64_t max_log = 0;
+        for (int r = 0; r < kLogRegions; r++) max_log = std::max(max_log, u.log_n[r]);
+        if (max_log) hipLaunchKernelGGL(k_snap_check_log, dim3(blocks_for(max_log, 256), kLogRegions), dim3(256), 0, h->stream, h->t, lim, (uint32_t*)h->snap_err.p);
+        const uint64_t n_list = std::max({u.n_normals + 1, u.n_reg, u.n_prereg, u.n_occ, u.n_pend});
+        hipLaunchKernelGGL(k_snap_check_lists, dim3(blocks_for(n_list, 256)), dim3(256), 0, h->stream, h->g, h->t, lim, (const uint32_t*)h->pend_a.p, (uint32_t*)h->snap_err.p);
+    }
+    if (hipGetLastError() != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore: launch of the range check failed"));
+    uint32_t err_word = 0;
+    if (hipMemcpyAsync(&err_word, h->snap_err.p, 4, hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
+        return bail(fail(h, HFPF_ERR_HIP, "restore: reading the range check's result failed"));
+    if (err_word) return bail(fail(h, HFPF_ERR_IO, "restore: the snapshot's tables hold indices outside their pools (range check bits 0x%x); the handle has been cleared", err_word));
+    // ---- host mirrors ----
+    h->dirty = hd.dirty != 0;
+    h->pend_valid = hd.pend_valid != 0;
+    h->normals_possible = hd.normals_possible != 0;
+    h->gate_done = hd.gate_done;
+    h->direct_linked = hd.direct_linked;
+    h->frames_integrated = hd.frames_integrated;
+    h->clean_passes = hd.clean_passes;
+    h->next_frame_id = (uint32_t)hd.next_frame_id;
+    for (int r = 0; r < kLogRegions; r++) h->n_linked[r] = hd.n_linked[r];
+    if ((rc = read_counters(h))) return bail(rc);  // h_ctr, h_log_ctr, n_bricks_known from the restored device counters
+    h->n_bricks_before = h->n_bricks_known;
+    if (h->binned) {
+        // Entries the source's direct form appended since its last clean are still unchained; the binned form never runs
+        // k_link_log at a clean pass (its own appends arrive chained), so they are chained here.
+        LinkRanges lr;
+        uint64_t max_new = 0;
+        for (int r = 0; r < kLogRegions; r++) {
+            const uint64_t base = (uint64_t)r * t.log_region_cap;
+            lr.first[r] = (uint32_t)(base + h->n_linked[r] + 1);
+            lr.last[r] = (uint32_t)(base + u.log_n[r]);
+            max_new = std::max(max_new, u.log_n[r] - h->n_linked[r]);
+        }
+        if (max_new && (hd.flags & HFPF_FLAG_DIRECT_UPDATE)) {
+            hipLaunchKernelGGL(k_link_log, dim3(blocks_for(max_new, 256), kLogRegions), dim3(256), 0, h->stream, h->t, lr);
+            if (hipGetLastError() != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore: k_link_log launch failed"));
+            for (int r = 0; r < kLogRegions; r++) h->n_linked[r] = u.log_n[r];
+            h->direct_linked = h->h_ctr[C_BUFFERED];
+        }
+    }
+    return HFPF_OK;
+}
+
+}  // namespace
+extern "C" {
+
+int hfpf_snapshot(hfpf_handle* h, void** blob, uint64_t* bytes)
+{
+    if (!h || !blob || !bytes) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    *blob = nullptr;
+    *bytes = 0;
+    return snapshot_locked(h, blob, bytes);
+}
+
+void hfpf_free_snapshot(void* blob) { free(blob); }
+
+int hfpf_restore(hfpf_handle* h, const void* blob, uint64_t bytes)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (!blob) return fail(h, HFPF_ERR_BAD_ARG, "restore: null blob");
+    return restore_locked(h, blob, bytes);
+}
+
+int hfpf_save(hfpf_handle* h, const char* path)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (!path) return fail(h, HFPF_ERR_BAD_ARG, "save: null path");
+    void* blob = nullptr;
+    uint64_t bytes = 0;
+    if (int rc = snapshot_locked(h, &blob, &bytes)) return rc;
+    FILE* f = fopen(path, "wb");
+    if (!f) {
+        free(blob);
+        return fail(h, HFPF_ERR_IO, "save: cannot open %s for writing", path);
+    }
+    const bool wrote = fwrite(blob, 1, bytes, f) == bytes;
+    const bool closed = fclose(f) == 0;
+    free(blob);
+    if (!wrote || !closed) {
+        remove(path);  // no partial file is left behind
+        return fail(h, HFPF_ERR_IO, "save: short write to %s", path);
+    }
+    return HFPF_OK;
+}
+
+int hfpf_load(hfpf_handle* h, const char* path)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (!path) return fail(h, HFPF_ERR_BAD_ARG, "load: null path");
+    FILE* f = fopen(path, "rb");
+    if (!f) return fail(h, HFPF_ERR_IO, "load: cannot open %s", path);
+    uint8_t hdr[HFPF_SNAPSHOT_HEADER_BYTES];
+    SnapHeader hd;
+    if (fread(hdr, 1, sizeof hdr, f) != sizeof hdr) {
+        fclose(f);
+        return fail(h, HFPF_ERR_IO, "load: %s is shorter than a snapshot header", path);
+    }
+    if (const char* why = snap_parse_header(hdr, sizeof hdr, &hd)) {
+        fclose(f);
+        return fail(h, HFPF_ERR_BAD_ARG, "load: %s: %s", path, why);
+    }
+    uint8_t* blob = (uint8_t*)host_result_alloc(hd.total_bytes);
+    if (!blob) {
+        fclose(f);
+        return fail(h, HFPF_ERR_CAPACITY, "load: host allocation of %llu bytes failed", (unsigned long long)hd.total_bytes);
+    }
+    memcpy(blob, hdr, sizeof hdr);
+    const bool whole = fread(blob + sizeof hdr, 1, hd.payload_bytes, f) == hd.payload_bytes;
+    fclose(f);
+    int rc = whole ? restore_locked(h, blob, hd.total_bytes) : fail(h, HFPF_ERR_IO, "load: %s ends before the %llu bytes its header announces", path, (unsigned long long)hd.total_bytes);
+    free(blob);
+    return rc;
+}
+
+int hfpf_snapshot_info(const void* blob, uint64_t bytes, struct hfpf_snapshot_info* out)
+{
+    if (!blob || !out || out->struct_size != sizeof(struct hfpf_snapshot_info)) return HFPF_ERR_BAD_ARG;
+    SnapHeader hd;
+    if (snap_parse_header(blob, std::min<uint64_t>(bytes, HFPF_SNAPSHOT_HEADER_BYTES), &hd)) return HFPF_ERR_BAD_ARG;
+    struct hfpf_snapshot_info o;
+    memset(&o, 0, sizeof o);
+    o.struct_size = sizeof o;
+    o.format_version = hd.version;
+    o.layout_tag = hd.layout_tag;
+    o.total_bytes = hd.total_bytes;
+    o.payload_bytes = hd.payload_bytes;
+    o.payload_checksum = hd.payload_checksum;
+    o.resolution = hd.resolution;
+    o.flags = hd.flags;
+    memcpy(o.bbox, hd.bbox, sizeof o.bbox);
+    o.k = hd.k, o.K = hd.K, o.gate = hd.gate;
+    o.cylinder_radius = hd.cylinder_radius, o.ball_radius = hd.ball_radius, o.z_clip_min = hd.z_clip_min, o.z_clip_max = hd.z_clip_max;
+    o.max_bricks = hd.need_bricks, o.max_log_points = hd.log_points, o.max_normals = hd.need_normals, o.max_frames = hd.need_frames;
+    o.frames_integrated = hd.frames_integrated, o.clean_passes = hd.clean_passes, o.next_frame_id = hd.next_frame_id;
+    o.voxels_occupied = hd.voxels_occupied, o.voxels_with_normal = hd.voxels_with_normal;
+    *out = o;
+    return HFPF_OK;
+}
+
+int hfpf_config_from_snapshot(const struct hfpf_snapshot_info* info, hfpf_config* cfg)
+{
+    if (!info || !cfg || info->struct_size != sizeof(struct hfpf_snapshot_info)) return HFPF_ERR_BAD_ARG;
+    hfpf_default_config(cfg);
+    cfg->resolution = info->resolution;
+    memcpy(cfg->bbox, info->bbox, sizeof cfg->bbox);
+    cfg->k = info->k, cfg->K = info->K, cfg->gate = info->gate;
+    cfg->cylinder_radius = info->cylinder_radius, cfg->ball_radius = info->ball_radius;
+    cfg->z_clip_min = info->z_clip_min, cfg->z_clip_max = info->z_clip_max;
+    cfg->flags = info->flags & kSnapSemanticFlags;
+    cfg->max_bricks = info->max_bricks, cfg->max_log_points = info->max_log_points, cfg->max_normals = info->max_normals, cfg->max_frames = info->max_frames;
+    return HFPF_OK;
 }
 
 int hfpf_sync(hfpf_handle* h)

@@ -305,6 +305,20 @@ int hfpf_node_set_mesh_output(hfpf_node* n, const hfpf_mesh_opts* opts)
     return HFPF_OK;
 }
 
+int hfpf_node_save_session(hfpf_node* n, const char* path)
+{
+    if (!n || !path) return HFPF_ERR_BAD_ARG;
+    const int rc = hfpf_save(n->grid, path);  // (takes the grid's lock: frames and clean passes fall before or after it)
+    return rc == HFPF_OK ? rc : nfail(n, rc, hfpf_last_error(n->grid));
+}
+
+int hfpf_node_load_session(hfpf_node* n, const char* path)
+{
+    if (!n || !path) return HFPF_ERR_BAD_ARG;
+    const int rc = hfpf_load(n->grid, path);  // start_ / cloud_subscription_started_ and the node's counters stay as they are
+    return rc == HFPF_OK ? rc : nfail(n, rc, hfpf_last_error(n->grid));
+}
+
 int hfpf_node_set_publisher(hfpf_node* n, hfpf_publish_fn fn, void* user)
 {
     if (!n) return HFPF_ERR_BAD_ARG;

@@ -93,6 +93,7 @@ EXPORTS = [
     "hfpf_query", "hfpf_query_device", "hfpf_query_depth",
     "hfpf_extract_mesh", "hfpf_extract_mesh_device", "hfpf_free_mesh", "hfpf_write_ply", "hfpf_check_mesh_opts",
     "hfpf_check_raycast_opts", "hfpf_raycast", "hfpf_raycast_device", "hfpf_raycast_view", "hfpf_raycast_view_device",
+    "hfpf_snapshot", "hfpf_free_snapshot", "hfpf_restore", "hfpf_save", "hfpf_load", "hfpf_snapshot_info", "hfpf_config_from_snapshot",
 ]
 
 # hfpf_depth_image formats (include/hfpf.h)
@@ -305,6 +306,79 @@ def write_ply(verts, tris, path):
         raise HfpfError(rc, "hfpf_write_ply(%s) failed" % path)
 
 
+SNAPSHOT_HEADER_BYTES = 4096  # HFPF_SNAPSHOT_HEADER_BYTES: what snapshot_info needs of a blob or file
+
+
+class SnapshotInfo(C.Structure):
+    """struct hfpf_snapshot_info (include/hfpf.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("format_version", C.c_uint32), ("layout_tag", C.c_uint64), ("total_bytes", C.c_uint64),
+                ("payload_bytes", C.c_uint64), ("payload_checksum", C.c_uint64), ("resolution", C.c_float), ("flags", C.c_uint32),
+                ("bbox", C.c_double * 6), ("k", C.c_int32), ("K", C.c_int32), ("gate", C.c_int32), ("reserved0", C.c_int32),
+                ("cylinder_radius", C.c_double), ("ball_radius", C.c_double), ("z_clip_min", C.c_double), ("z_clip_max", C.c_double),
+                ("max_bricks", C.c_uint64), ("max_log_points", C.c_uint64), ("max_normals", C.c_uint64), ("max_frames", C.c_uint64),
+                ("frames_integrated", C.c_uint64), ("clean_passes", C.c_uint64), ("next_frame_id", C.c_uint64),
+                ("voxels_occupied", C.c_uint64), ("voxels_with_normal", C.c_uint64), ("reserved", C.c_uint64 * 4)]
+
+
+def _snapshot_info_struct(info):
+    """A SnapshotInfo from the dict snapshot_info() returns (or a SnapshotInfo as it is)."""
+    if isinstance(info, SnapshotInfo):
+        return info
+    s = SnapshotInfo()
+    s.struct_size = C.sizeof(SnapshotInfo)
+    for name, ctype in SnapshotInfo._fields_:
+        if name in ("struct_size", "reserved", "reserved0") or name not in info:
+            continue
+        if name == "bbox":
+            for i in range(6):
+                s.bbox[i] = float(info["bbox"][i])
+        else:
+            setattr(s, name, info[name])
+    return s
+
+
+def snapshot_info(blob):
+    """hfpf_snapshot_info: what the header of a snapshot says, as a dict (host code: no handle, no GPU).  blob: bytes-like, at
+    least its first SNAPSHOT_HEADER_BYTES bytes."""
+    raw = np.frombuffer(blob, dtype=np.uint8) if blob is not None else None
+    s = SnapshotInfo()
+    s.struct_size = C.sizeof(SnapshotInfo)
+    rc = lib().hfpf_snapshot_info(_p(raw) if raw is not None and raw.size else None, raw.size if raw is not None else 0, C.byref(s))
+    if rc != 0:
+        raise HfpfError(rc, "not a snapshot of this format (hfpf_snapshot_info)")
+    out = {n: getattr(s, n) for n, _ in SnapshotInfo._fields_ if n not in ("struct_size", "reserved", "reserved0")}
+    out["bbox"] = tuple(s.bbox[:])
+    return out
+
+
+def config_from_snapshot(info):
+    """hfpf_config_from_snapshot: the Config a handle needs to take the snapshot `info` describes (capacities = the needed ones,
+    device and scheduling hints at their defaults).  OccupancyGrid.from_config(cfg) creates it."""
+    c = Config()
+    s = _snapshot_info_struct(info)
+    rc = lib().hfpf_config_from_snapshot(C.byref(s), C.byref(c))
+    if rc != 0:
+        raise HfpfError(rc, "hfpf_config_from_snapshot")
+    return c
+
+
+class _SnapshotBuffer:
+    """Owner of one hfpf_snapshot result (engine-allocated host memory); exposes it to numpy without copying."""
+
+    def __init__(self, ptr, n):
+        self._ptr, self._n = ptr, n
+
+    @property
+    def __array_interface__(self):
+        return {"shape": (self._n,), "typestr": "|u1", "data": (self._ptr, False), "version": 3}
+
+    def __del__(self):
+        try:
+            lib().hfpf_free_snapshot(C.c_void_p(self._ptr))
+        except Exception:
+            pass
+
+
 EPOCH_REC_DTYPE = np.dtype([("key", "<u8"), ("first_frame", "<u4"), ("vx", "<f4"), ("vy", "<f4"), ("vz", "<f4"), ("pad", "<u4", (2,))])
 assert EPOCH_REC_DTYPE.itemsize == 32
 
@@ -398,6 +472,14 @@ def lib():
     L.hfpf_raycast_device.argtypes = [vp, C.POINTER(RaycastOpts), vp, u64, vp, vp]
     L.hfpf_raycast_view.argtypes = [vp, C.POINTER(RaycastOpts), u32, u32, dbl, dbl, dbl, dbl, vp, vp]
     L.hfpf_raycast_view_device.argtypes = [vp, C.POINTER(RaycastOpts), u32, u32, dbl, dbl, dbl, dbl, u32, vp, vp]
+    L.hfpf_snapshot.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    L.hfpf_free_snapshot.argtypes = [vp]
+    L.hfpf_free_snapshot.restype = None
+    L.hfpf_restore.argtypes = [vp, vp, u64]
+    L.hfpf_save.argtypes = [vp, C.c_char_p]
+    L.hfpf_load.argtypes = [vp, C.c_char_p]
+    L.hfpf_snapshot_info.argtypes = [vp, u64, C.POINTER(SnapshotInfo)]
+    L.hfpf_config_from_snapshot.argtypes = [C.POINTER(SnapshotInfo), C.POINTER(Config)]
     _lib = L
     return L
 
@@ -457,14 +539,24 @@ class OccupancyGrid:
         c.max_bricks, c.max_log_points, c.max_normals, c.max_frames = max_bricks, max_log_points, max_normals, max_frames
         c.frame_width = int(frame_width)  # scheduling hint only (16x16-pixel tiles); results do not depend on it
         c.max_call_points = int(max_call_points)  # 0 = per-call bins grown on demand
+        self._create(c)
+
+    def _create(self, c):
         self.cfg = c
         self._transport = None
         self._h = C.c_void_p()
-        rc = L.hfpf_create(C.byref(c), C.byref(self._h))
+        rc = lib().hfpf_create(C.byref(c), C.byref(self._h))
         if rc != 0:
-            msg = L.hfpf_last_error(None).decode()
+            msg = lib().hfpf_last_error(None).decode()
             self._h = None
             raise HfpfError(rc, msg)
+
+    @classmethod
+    def from_config(cls, cfg):
+        """A grid from a ready Config (config_from_snapshot, or default_config with fields changed)."""
+        g = cls.__new__(cls)
+        g._create(cfg)
+        return g
 
     # -- plumbing --
     def _chk(self, rc):
@@ -859,6 +951,27 @@ class OccupancyGrid:
 
     def clear(self):
         self._chk(lib().hfpf_clear(self._h))
+
+    # -- keeping a session --
+    def snapshot(self):
+        """hfpf_snapshot: the handle's state as a uint8 numpy array over the engine's host buffer (bytes-like: bytes(a), a.tobytes(),
+        memoryview(a), file.write(a) all work); freed when the array is collected."""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._chk(lib().hfpf_snapshot(self._h, C.byref(p), C.byref(n)))
+        return np.asarray(_SnapshotBuffer(p.value, n.value))
+
+    def restore(self, blob):
+        """hfpf_restore: clear, then put the state of `blob` (bytes-like) in place."""
+        raw = np.frombuffer(blob, dtype=np.uint8)
+        self._chk(lib().hfpf_restore(self._h, _p(raw) if raw.size else None, raw.size))
+
+    def save(self, path):
+        """hfpf_save: the bytes of snapshot(), written to a file."""
+        self._chk(lib().hfpf_save(self._h, os.fsencode(path)))
+
+    def load(self, path):
+        """hfpf_load: restore() from a file written by save()."""
+        self._chk(lib().hfpf_load(self._h, os.fsencode(path)))
 
     # -- diagnostics / harness --
     def sync(self):

@@ -675,6 +675,82 @@ int hfpf_get_counters(hfpf_handle* h, hfpf_counters* out);
  * xyz may be NULL to query the count; at most cap triplets are written. */
 int hfpf_get_occupied(hfpf_handle* h, int32_t* xyz, uint64_t cap, uint64_t* n_out);
 
+/* ---- snapshot and restore of a fusion session (no reference counterpart: its grid lives and dies with the process) ----------
+ * WHAT A SNAPSHOT IS.  The state of the handle at this point of the call sequence, as one block of HOST memory.  Host frames still
+ * waiting for their launch are launched first and a clean pass that returned without waiting is waited for, as hfpf_extract does;
+ * deferred errors surface here as they do there.  A snapshot may be taken at any point: before the first frame, between integrate
+ * and clean (dirty: points buffered but not yet replayed, cells waiting for the gate), after a clean, after hfpf_clear.  It changes
+ * nothing on the handle except device_bytes (its staging scratch).
+ *
+ * WHAT A RESTORE IS.  hfpf_clear followed by putting that state in place.  Afterwards the handle is indistinguishable from the
+ * source handle at the moment of the snapshot, in this sense:
+ *   1. every read-only call (extract, extract_filtered, get_occupied, is_dirty, render*, query*, extract_mesh*, raycast*, track*)
+ *      returns byte-identical output;
+ *   2. any continuation (integrate*, clean, extract, clear, automatic frame ids included) produces byte-identical rows and occupied
+ *      lists to the same continuation on the source handle;
+ *   3. hfpf_get_counters agrees in every field results depend on: points_presented, points_zclip_pass, points_in_bbox,
+ *      points_buffered, dep_pairs_tested, dep_pairs_member, voxels_occupied, voxels_with_normal, bricks_allocated, registrations,
+ *      frames_integrated, clean_passes, replay_members.  The scheduling diagnostics (points_direct, table_misses,
+ *      update_extra_rounds, dep_entries, device_bytes) and the kernel timings need not.
+ * Scheduling state that results never depend on (bin plans, the shape of the dependant update, staging rings) is not part of a
+ * snapshot.  This relies on what the engine already guarantees -- integer statistic sums, ties broken by key -- and on nothing new.
+ *
+ * COMPATIBILITY.  The target handle must have the same resolution (as f32 bits), bbox, k, K, gate, radii, z-clips and the same
+ * HFPF_FLAG_FUSE_COLOR and HFPF_FLAG_PCL_SHIFTED_COV: HFPF_ERR_BAD_CONFIG otherwise.  It may differ in device,
+ * HFPF_FLAG_DIRECT_UPDATE, frame_width and max_call_points, and in max_bricks, max_normals and max_frames as long as what the
+ * session used fits (HFPF_ERR_CAPACITY otherwise; the handle is not poisoned).  max_log_points must be EQUAL (as the engine
+ * rounded it: hfpf_snapshot_info reports the value to create with): indices into the point log encode its append region, and they
+ * are not remapped.  A snapshot also carries a tag of the layout of the engine's internal tables; a blob with another format
+ * version or layout tag is refused with HFPF_ERR_BAD_ARG.  Snapshots are a RESUME format between builds of one table layout, not
+ * an archive format.
+ *
+ * ERRORS.  Everything the host can decide is decided before a byte reaches the device: NULL arguments, a blob shorter than its
+ * header says, bad magic, version or layout tag, a header or payload whose 64-bit checksum does not match (all HFPF_ERR_BAD_ARG, from
+ * hfpf_load too), configuration or capacity mismatch.  All of these leave the target exactly as it was: usable, same
+ * rows.  hfpf_save / hfpf_load add HFPF_ERR_IO for a file that cannot be opened, read or written in full (a short write removes the
+ * partial file).  A failure after the upload has begun (a HIP error, or the device-side range check of the restored indices:
+ * HFPF_ERR_IO) leaves the handle as after hfpf_clear.  A poisoned handle cannot be snapshotted (HFPF_ERR_STATE, as extract) but
+ * can be restored into.  A handle with an RCCL communicator, or one that has exported or imported epoch records (hfpf_epoch_*,
+ * hfpf_stats_export), returns HFPF_ERR_STATE from all four calls: a distributed snapshot is not provided.
+ *
+ * SIZE.  A snapshot's size follows what the session used, never the pool capacities; unused bytes are zero, so two snapshots of one
+ * state are equal byte for byte.  Between a snapshot and the snapshot of its restore elsewhere the payload and its checksum are equal; of
+ * the header only `flags` may differ (it records the handle's own flags word, HFPF_FLAG_DIRECT_UPDATE included): capacities are not
+ * stored, only the needed ones. */
+#define HFPF_SNAPSHOT_HEADER_BYTES 4096u /* hfpf_snapshot_info needs this many leading bytes of a blob or file */
+/* Filled from the header alone (host code; no handle, no GPU).  struct tag only: the function below carries the same name. */
+struct hfpf_snapshot_info {
+    uint32_t struct_size;     /* = sizeof(struct hfpf_snapshot_info), set by the caller */
+    uint32_t format_version;
+    uint64_t layout_tag;      /* table layout of the build that wrote the blob */
+    uint64_t total_bytes;     /* header + payload = the size of the blob / file */
+    uint64_t payload_bytes;
+    uint64_t payload_checksum;
+    /* the grid configuration the snapshot was made with */
+    float resolution;         /* as the f32 hfpf_config carried */
+    uint32_t flags;           /* HFPF_FLAG_* of the source handle */
+    double bbox[6];
+    int32_t k, K, gate;
+    int32_t reserved0;
+    double cylinder_radius, ball_radius, z_clip_min, z_clip_max;
+    /* the smallest pool capacities a handle needs to take it (max_log_points: exactly this value) */
+    uint64_t max_bricks, max_log_points, max_normals, max_frames;
+    /* the session */
+    uint64_t frames_integrated, clean_passes, next_frame_id, voxels_occupied, voxels_with_normal;
+    uint64_t reserved[4];     /* 0 */
+};
+int hfpf_snapshot(hfpf_handle* h, void** blob, uint64_t* bytes); /* HOST memory, freed by hfpf_free_snapshot */
+void hfpf_free_snapshot(void* blob);
+int hfpf_restore(hfpf_handle* h, const void* blob, uint64_t bytes);
+int hfpf_save(hfpf_handle* h, const char* path); /* the same bytes, written to a file */
+int hfpf_load(hfpf_handle* h, const char* path);
+/* HFPF_ERR_BAD_ARG (nothing written): NULL, bytes below HFPF_SNAPSHOT_HEADER_BYTES, wrong magic, out->struct_size, format version
+ * or header checksum.  The payload is neither needed nor looked at. */
+int hfpf_snapshot_info(const void* blob, uint64_t bytes, struct hfpf_snapshot_info* out);
+/* hfpf_default_config, then the grid configuration of the snapshot, its semantic flags (colour fusion, shifted covariance) and the
+ * needed capacities; device and scheduling hints stay at their defaults. */
+int hfpf_config_from_snapshot(const struct hfpf_snapshot_info* info, hfpf_config* cfg);
+
 /* ---- harness helpers (device staging without any framework) ---- */
 int hfpf_device_alloc(hfpf_handle* h, uint64_t bytes, void** dev_ptr);
 int hfpf_device_free(hfpf_handle* h, void* dev_ptr);

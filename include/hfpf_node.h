@@ -93,6 +93,14 @@ int hfpf_node_set_publisher(hfpf_node* n, hfpf_publish_fn fn, void* user);
  * refused with HFPF_ERR_BAD_ARG and leave the setting as it was.  (hfpf_node_params keeps its size: it is part of the ABI.) */
 int hfpf_node_set_mesh_output(hfpf_node* n, const hfpf_mesh_opts* opts);
 
+/* EXTENSION: keep the grid's session in a file and take it up again (hfpf_save / hfpf_load of include/hfpf.h on the node's grid, with
+ * their errors).  Both run under the grid's own lock, so they are legal while the cloud callback and the clean thread run: a frame
+ * or a clean pass lands wholly before or wholly after them.  Loading replaces the fused data only: the node stays started or stopped
+ * as it was, its counters go on, and the node's grid must match the file as hfpf_restore says (same grid configuration and
+ * max_log_points, pools that hold the session). */
+int hfpf_node_save_session(hfpf_node* n, const char* path);
+int hfpf_node_load_session(hfpf_node* n, const char* path);
+
 /* One iteration of cleanGrid (node.cpp:301-325): clean iff state_changed.  Returns 1 if a pass ran. */
 int hfpf_node_clean_now(hfpf_node* n);
 hfpf_handle* hfpf_node_grid(hfpf_node* n);
