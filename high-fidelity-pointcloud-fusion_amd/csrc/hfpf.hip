@@ -24,7 +24,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -189,54 +188,106 @@ DepthLayout depth_layout(const DepthSpec& d, const void* dev_color, uint64_t col
                        d.color_bpp, d.color_bgr, d.cx, d.cy, d.sx, d.sy, d.unit};
 }
 
+// What the environment overrides (HFPF_*), read once by read_knobs() at hfpf_create.  One exception: HFPF_TEST_SNAPSHOT_WINDOW is
+// read by snap_stage_alloc at every call, because a test sets it on a live handle.
+struct Knobs {
+    int copy_streams = 2;            // HFPF_COPY_STREAMS=1..4: streams the host-frame uploads alternate over
+    bool update_cells = true;        // k_update_cells (cell-sorted form); HFPF_UPDATE_FORM=points: k_update (per-point form), A/B and tests
+    int host_batch = 4;              // HFPF_HOST_BATCH (1 = every frame launches on its own)
+    int upd_shape_forced = -1;       // HFPF_UPD_SHAPE=0|1
+    bool trace_shape = false;        // HFPF_TRACE_SHAPE=1: one stderr line per pick_update_shape() window
+    bool bin_spare = true;           // HFPF_BIN_SPARE=0: no bin regions for bricks the launch discovers
+    bool stream_replay = true;       // HFPF_STREAM_REPLAY=0: every replay walks the chains
+    float bin_slack = 2.0f;          // planned capacity of a bin region = the brick's demand in the previous launch x this (HFPF_BIN_SLACK)
+    bool clean_small_nowait = true;  // small clean passes run without a mid-pass read-back (HFPF_CLEAN_NOWAIT=0 restores it)
+    float test_bin_scale = 1.f;      // tests only (HFPF_TEST_BIN_SCALE): shrinks the planned bin regions so that they overflow into the direct forms
+    bool test_table_skip = false;    // tests only (HFPF_TEST_TABLE_SKIP=1): Tables::test_table_skip
+    bool mailbox = true;             // HFPF_MAILBOX=0: counter read-backs by blit copies + synchronize
+    int stage_threads = 0;           // HFPF_STAGE_THREADS: helpers of the StagePool (default half the process's cores - 1, at most 7; 0 = none)
+};
+
+// The fusion session: the host mirrors that must follow the device tables.  The initialisers are the values of a fresh or cleared
+// handle: reset_state() assigns Session{} and nothing else.  A NEW FIELD GOES HERE, with its note: does a snapshot carry it
+// (session_to_header / header_to_session), and if not, what re-creates it after a restore.
+struct Session {
+    bool dirty = false;                     // snapshot: carried
+    uint64_t n_linked[kLogRegions] = {0};   // per log region: entries already chained.  snapshot: carried
+    uint64_t gate_done = 0;                 // occ_list entries already examined by a gate pass.  snapshot: carried
+    bool pend_valid = false;                // pend_a holds C_PEND cells that a gate pass examined and left without a normal.  snapshot: carried
+    uint64_t direct_linked = 0;             // points buffered by k_integrate's direct form (C_BUFFERED) that k_link_log has already chained.  snapshot: carried
+    bool normals_possible = false;          // a clean pass has run since the last clear (the host mirror of C_NORMALS may lag behind a no-wait pass).  snapshot: carried
+    uint32_t next_frame_id = 0;             // snapshot: carried
+    // A capacity / HIP / collective error in the middle of a clean pass leaves the tables half updated: the handle then refuses
+    // further work (HFPF_ERR_STATE) until hfpf_clear, instead of silently losing candidates on a retry.
+    bool poisoned = false;                  // snapshot: not carried (a failed handle refuses hfpf_snapshot; a restore begins with a clear)
+    std::string poison_msg;
+    // plan of the binned dependant update.  snapshot: not carried; the next integrate call starts without a plan and records one
+    bool bin_have_hist = false;             // bin_fill holds the demand of the previous launch
+    bool bin_from_probe = false;            // ... and that launch was the dry run of a session's first frames
+    double bin_prev_points = 0;             // points presented by that launch (to scale the plan)
+    uint64_t n_bricks_known = 0;            // bricks allocated at the last counter read-back.  snapshot: not carried; the counter read-back of restore
+    uint64_t n_bricks_before = 0;           // ... and at the read-back before the count last changed.  snapshot: not carried; restore sets it to n_bricks_known
+    // pick_update_shape()'s window.  snapshot: not carried, and nothing re-creates it: the first window after a restore covers the
+    // source session's totals
+    unsigned long long upd_miss_seen = 0, upd_member_seen = 0;
+    unsigned long long pub_seq = 0;         // sequence number of a publish enqueued behind the last integrate call and still current (0: none).  snapshot: not carried; 0 makes the next read-back publish for itself
+    // Host frames uploaded, not yet launched: slots [pend_first, pend_first + pend_n); everything but pend_n is dead while pend_n == 0.
+    // snapshot: not carried (hfpf_snapshot launches them first)
+    uint32_t pend_n = 0, pend_first = 0;
+    uint32_t pend_pts = 0;
+    uint32_t pend_lay[5] = {0, 0, 0, 0, 0};  // point_step, off_x, off_y, off_z, off_rgb of the pending frames
+    bool pend_depth = false;                  // ... or: the pending frames are depth images of this spec
+    DepthSpec pend_ds{};
+    double pend_pose[kFrameSlots * 12] = {0};
+    // exchange cursors (multi-GPU, hfpf_epoch_*).  snapshot: not carried; handles that exchange refuse snapshot and restore
+    uint64_t occ_exported = 0;              // occ_list entries already exchanged
+    uint64_t frames_exported = 0, frames_seen = 0;  // frame_list entries already exchanged / as of the last export
+};
+
+using EventPairs = std::vector<std::pair<hipEvent_t, hipEvent_t>>;
+
 }  // namespace
 
+// Four groups: configuration and knobs, the session, resources, kernel timing.
 struct hfpf_handle {
     std::mutex mtx;
+    std::string err;
+
+    // ---- configuration: what the caller asked for (setup_params, alloc_tables) and what the environment overrode ----
     hfpf_config cfg;
     GridParams g;
-    Tables t;
-    hipStream_t stream = nullptr;
-    hipStream_t copy_stream = nullptr;  // host-frame uploads, overlapped with the kernels of earlier frames
-    // ... of ring slots 1, 2, ... modulo n_copy_streams: uploads in flight side by side keep the link busy across the gap between two copies
-    // of one stream (HFPF_COPY_STREAMS=1..4)
-    hipStream_t copy_more[3] = {nullptr, nullptr, nullptr};
-    int n_copy_streams = 2;
-    std::string err;
-    std::vector<void*> allocs;
-    uint64_t device_bytes = 0;
+    Knobs knobs;
+    bool binned = false;  // two-pass (binned) dependant update (default; HFPF_FLAG_DIRECT_UPDATE switches it off)
+    int integrate_grid = 1536;
     size_t dir_entries = 0;
     uint64_t n_slots = 0;
     uint64_t max_touched = 0;
 
-    // host mirrors
-    bool dirty = false;
-    uint64_t n_linked[kLogRegions] = {0};  // per log region: entries already chained
-    unsigned long long* h_log_ctr = nullptr;  // pinned mirror of the region counters
-    int integrate_grid = 1536;
-    int upd_shape_forced = -1;  // HFPF_UPD_SHAPE
-    bool upd_wide = false;      // the 352-slot record table overflowed in this session: k_update_cells takes the 512-slot shape
-    bool trace_shape = false;   // HFPF_TRACE_SHAPE=1: one stderr line per pick_update_shape() window
-    unsigned long long upd_miss_seen = 0, upd_member_seen = 0;
-    uint32_t launch_seq = 0;  // integrate launches so far (rotates the log append regions)
-    uint64_t frames_integrated = 0;
-    bool normals_possible = false;   // a clean pass has run since the last clear (the host mirror of C_NORMALS may lag behind a no-wait pass)
-    bool stream_replay = true;       // HFPF_STREAM_REPLAY=0: every replay walks the chains
-    float bin_slack = 2.0f;          // planned capacity of a bin region = the brick's demand in the previous launch x this (HFPF_BIN_SLACK)
-    bool clean_small_nowait = true;  // small clean passes run without a mid-pass read-back (HFPF_CLEAN_NOWAIT=0 restores it)
-    uint64_t gate_done = 0; // occ_list entries already examined by a gate pass
-    // A capacity / HIP / collective error in the middle of a clean pass leaves the tables half updated: the handle then refuses
-    // further work (HFPF_ERR_STATE) until hfpf_clear, instead of silently losing candidates on a retry.
-    bool poisoned = false;
-    std::string poison_msg;
-    bool pend_valid = false;
-    uint64_t direct_linked = 0;  // points buffered by k_integrate's direct form (C_BUFFERED) that k_link_log has already chained // pend_a holds C_PEND cells that a gate pass examined and left without a normal
-    DevBuf pend_a, pend_b;
-    uint64_t clean_passes = 0;
-    uint32_t next_frame_id = 0;
+    // ---- the session (reset_state) ... ----
+    Session ss;
+    // ... and what an hfpf_clear leaves alone
+    uint64_t frames_integrated = 0;  // hfpf_get_counters reports it per handle; a restore overwrites it.  Kept to preserve behaviour
+    uint64_t clean_passes = 0;       // the same
+    uint32_t launch_seq = 0;         // integrate launches so far (rotates the log append regions).  Kept to preserve behaviour
+    bool upd_wide = false;           // the 352-slot record table overflowed: k_update_cells takes the 512-slot shape.  Stays: the next session on this handle fuses the same kind of scene
+    bool epoch_used = false;         // epoch records or statistic words have left or entered this handle: no snapshot (include/hfpf.h).  Stays: include/hfpf.h says "has exported or imported", ever
+    unsigned long long mbox_seq = 0; // never repeats while the mailbox lives: the flag word still holds the last published number
+    int stage_next = 0, fslot_next = 0;  // cursors of the stage[] and fslot[] rings: the slots and their events outlive a session
 
+    // ---- resources: streams, pools, scratch, pinned staging ----
+    Tables t;
+    hipStream_t stream = nullptr;
+    hipStream_t copy_stream = nullptr;  // host-frame uploads, overlapped with the kernels of earlier frames
+    // ... of ring slots 1, 2, ... modulo knobs.copy_streams: uploads in flight side by side keep the link busy across the gap between
+    // two copies of one stream
+    hipStream_t copy_more[3] = {nullptr, nullptr, nullptr};
+    std::vector<void*> allocs;
+    uint64_t device_bytes = 0;
+    unsigned long long* h_ctr = nullptr;      // pinned mirror of the counters
+    unsigned long long* h_log_ctr = nullptr;  // pinned mirror of the region counters
+    unsigned long long* mbox = nullptr;       // coherent pinned mailbox k_publish_counters writes (null with HFPF_MAILBOX=0)
+    DevBuf pend_a, pend_b;  // the gate's pending-cell lists (Session::pend_valid)
     StageSlot stage[kStageSlots];
-    int stage_next = 0;
     FrameSlot fslot[kFrameSlots];
     // Device side of the host-frame path: ONE allocation of kFrameSlots slots, ring_cap bytes apart, so that consecutive slots
     // form a batch k_integrate can take in one launch (frame_stride = ring_cap).  Frames that arrive while the engine's stream
@@ -245,23 +296,11 @@ struct hfpf_handle {
     // stream idle is launched immediately, so a sensor slower than the engine sees no added latency.
     void* ring_d = nullptr;
     size_t ring_cap = 0;
-    uint32_t pend_n = 0, pend_first = 0;  // uploaded, not yet launched: slots [pend_first, pend_first + pend_n)
-    uint32_t pend_pts = 0;
-    uint32_t pend_lay[5] = {0, 0, 0, 0, 0};  // point_step, off_x, off_y, off_z, off_rgb of the pending frames
-    bool pend_depth = false;                  // ... or: the pending frames are depth images of this spec
-    DepthSpec pend_ds{};
-    double pend_pose[kFrameSlots * 12];
-    int host_batch = 4;                   // HFPF_HOST_BATCH (1 = every frame launches on its own)
     hipEvent_t busy_ev = nullptr;         // recorded behind the last launch of the host-frame path
     bool busy_pending = false;
-    bool update_cells = true;  // k_update_cells (cell-sorted form); HFPF_UPDATE_FORM=points: k_update (per-point form), A/B and tests
     void* xfer_pin[2] = {nullptr, nullptr};  // pinned staging of extract's row download (two chunks in flight)
     hipEvent_t xfer_ev[2] = {nullptr, nullptr};
-    StagePool* stage_pool = nullptr;  // created by the first large bounce copy (HFPF_STAGE_THREADS helpers, default 4; 0 = none)
-    int stage_threads = -1;
-    int fslot_next = 0;
-
-    // scratch
+    StagePool* stage_pool = nullptr;  // created by the first large bounce copy (knobs.stage_threads helpers)
     DevBuf sort_tmp, keys_a, keys_b, vals_a, vals_b, rows_dev, probe_a, probe_b, probe_c, probe_d, probe_e, probe_f;
     DevBuf zbuf, render_pose, render_out;  // hfpf_render*: z-buffers of one chunk of views, the views' poses, hfpf_render's device planes
     DevBuf track_in, track_acc;            // hfpf_track*: a host frame's device copy, the 30 int64 sums of one iteration
@@ -271,46 +310,27 @@ struct hfpf_handle {
     DevBuf mesh_cube, mesh_corner, mesh_kdata, mesh_cdata, mesh_out, mesh_ctr;
     DevBuf ray_in, ray_out, ray_map;       // hfpf_raycast*: a host chunk's rays, a chunk's (or band's) hits, the empty-space maps
     DevBuf snap_stage, snap_err;           // hfpf_snapshot / hfpf_restore: the staging buffer (or one window of it), the range check's error word
-    bool epoch_used = false;               // epoch records or statistic words have left or entered this handle: no snapshot (include/hfpf.h)
-    unsigned long long* h_ctr = nullptr;  // pinned mirror of the counters
-    unsigned long long* mbox = nullptr;   // coherent pinned mailbox k_publish_counters writes (HFPF_MAILBOX=0: blit copies + synchronize)
-    unsigned long long mbox_seq = 0;
-    unsigned long long pub_seq = 0;  // sequence number of a publish enqueued behind the last integrate call and still current (0: none)
-
-    // two-pass (binned) dependant update (default; HFPF_FLAG_DIRECT_UPDATE switches it off)
-    bool binned = false;
-    bool bin_have_hist = false;   // bin_fill holds the demand of the previous launch
-    bool bin_from_probe = false;  // ... and that launch was the dry run of a session's first frames
-    double bin_prev_points = 0;   // points presented by that launch (to scale the plan)
-    uint64_t bin_pool = 0;        // entries in bin_pt
-    uint64_t n_bricks_known = 0;  // bricks allocated at the last counter read-back
-    uint64_t n_bricks_before = 0; // ... and at the read-back before the count last changed
-    bool bin_spare = true;        // HFPF_BIN_SPARE=0: no bin regions for bricks the launch discovers
-    float test_bin_scale = 1.f;   // tests only (HFPF_TEST_BIN_SCALE): shrinks the planned bin regions so that they overflow into the direct forms
+    uint64_t bin_pool = 0;           // entries in bin_pt
     DevBuf bin_pt_buf, bin_rgb_buf, bin_sums;
     DevBuf ovf_pt_buf, ovf_aux_buf;  // overflow list of one integrate launch (points that found no room in a bin)
-
     // multi-GPU: RCCL is resolved at run time so a single-GPU user needs no librccl
     bool dist_on = false;
     int rank = 0, world = 1;
     void* rccl_lib = nullptr;
     void* comm = nullptr;  // ncclComm_t
-    uint64_t occ_exported = 0;  // occ_list entries already exchanged
-    uint64_t frames_exported = 0, frames_seen = 0;  // frame_list entries already exchanged / as of the last export
     uint64_t ex_cap_records = 0;  // records the exchange buffers hold per rank; kept EQUAL on every rank (same initial value, same growth rule)
     DevBuf ex_send, ex_recv, ex_counts, stats_total;
     unsigned long long* h_counts = nullptr;  // pinned, world entries
 
-    // kernel timing
+    // ---- kernel timing ----
     bool timing = false;
     bool timing_detail = false;  // hfpf_kernel_timing(h, 2): also one event pair per kernel of an integrate call (ids 2..4)
     std::vector<hipEvent_t> ev_detail;  // 4 events per call: before k_integrate, after it, after k_update*, after k_buffer
     std::vector<uint8_t> ev_detail_ran;  // per call: bit k = the kernel between events k and k + 1 was launched
     double t_detail_ms[3] = {0, 0, 0};
     uint64_t n_detail[3] = {0, 0, 0};
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending_clean;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending_ray;  // one pair per k_raycast / k_raycast_view launch (id 5)
+    EventPairs ev_pending, ev_pending_clean;
+    EventPairs ev_pending_ray;  // one pair per k_raycast / k_raycast_view launch (id 5)
     double t_ray_ms = 0;
     uint64_t n_ray_timed = 0;
     double t_clean_ms = 0;
@@ -336,14 +356,14 @@ int fail(hfpf_handle* h, int code, const char* fmt, ...)
 
 int check_usable(hfpf_handle* h)
 {
-    if (!h->poisoned) return HFPF_OK;
-    return fail(h, HFPF_ERR_STATE, "handle failed earlier (%s); hfpf_clear resets it", h->poison_msg.c_str());
+    if (!h->ss.poisoned) return HFPF_OK;
+    return fail(h, HFPF_ERR_STATE, "handle failed earlier (%s); hfpf_clear resets it", h->ss.poison_msg.c_str());
 }
 int poison_on_error(hfpf_handle* h, int rc)
 {
-    if ((rc == HFPF_ERR_CAPACITY || rc == HFPF_ERR_HIP || rc == HFPF_ERR_DIST) && !h->poisoned) {
-        h->poisoned = true;
-        h->poison_msg = h->err;
+    if ((rc == HFPF_ERR_CAPACITY || rc == HFPF_ERR_HIP || rc == HFPF_ERR_DIST) && !h->ss.poisoned) {
+        h->ss.poisoned = true;
+        h->ss.poison_msg = h->err;
     }
     return rc;
 }
@@ -371,7 +391,7 @@ int dev_alloc(hfpf_handle* h, T** out, uint64_t count, int memset_byte = 0, bool
 // the previous launch x slack (x 1.5 at least when the plan comes from the dry run's sample) + 64.
 uint64_t bin_pool_entries(const hfpf_handle* h, uint64_t pts, uint64_t bricks)
 {
-    const double per_point = 2.0 * std::max(1.5, (double)h->bin_slack) + 0.125;
+    const double per_point = 2.0 * std::max(1.5, (double)h->knobs.bin_slack) + 0.125;
     return (uint64_t)(per_point * (double)pts) + 128ull * (bricks + 1);
 }
 
@@ -434,8 +454,8 @@ int read_counters(hfpf_handle* h)
     if (h->mbox) {
         // An integrate call ends with a publish of its own (nothing has touched the counters since): the snapshot is already on
         // its way, so the host only waits -- no launch of its own behind a stream that has just drained.
-        unsigned long long seq = h->pub_seq;
-        h->pub_seq = 0;
+        unsigned long long seq = h->ss.pub_seq;
+        h->ss.pub_seq = 0;
         if (seq == 0) {
             seq = ++h->mbox_seq;
             k_publish_counters<<<1, 256, 0, h->stream>>>(h->t.ctr, h->t.log_ctr, h->mbox, seq);
@@ -478,8 +498,8 @@ int read_counters(hfpf_handle* h)
     h->h_ctr[C_TOUCHED_SINGLE] = single;
     {
         const uint64_t nbk = std::min<uint64_t>(h->h_ctr[C_BRICKS], h->t.max_bricks);
-        if (nbk != h->n_bricks_known) h->n_bricks_before = h->n_bricks_known;  // how fast the session discovers bricks (spare bin regions)
-        h->n_bricks_known = nbk;
+        if (nbk != h->ss.n_bricks_known) h->ss.n_bricks_before = h->ss.n_bricks_known;  // how fast the session discovers bricks (spare bin regions)
+        h->ss.n_bricks_known = nbk;
     }
     return HFPF_OK;
 }
@@ -505,6 +525,33 @@ int check_device_errors(hfpf_handle* h)
 
 // Power-of-two scale that keeps one contribution of magnitude < bound below 2^27 (stats.hpp).
 float stat_scale_for(double bound) { return (float)std::ldexp(1.0, 26 - (int)std::floor(std::log2(bound))); }
+
+// The only reader of the environment (but see Knobs): ranges, clamps and defaults of every HFPF_* variable.
+Knobs read_knobs()
+{
+    Knobs k;
+    if (const char* cs = getenv("HFPF_COPY_STREAMS")) k.copy_streams = std::max(1, std::min(atoi(cs), 4));
+    const char* uf = getenv("HFPF_UPDATE_FORM");
+    k.update_cells = !(uf && uf[0] == 'p');
+    if (const char* hb = getenv("HFPF_HOST_BATCH")) k.host_batch = std::max(1, std::min(atoi(hb), kFrameSlots));
+    if (const char* us = getenv("HFPF_UPD_SHAPE")) k.upd_shape_forced = std::max(0, std::min(atoi(us), 1));
+    if (const char* tr = getenv("HFPF_TRACE_SHAPE")) k.trace_shape = tr[0] != '0';
+    if (const char* sp = getenv("HFPF_BIN_SPARE")) k.bin_spare = sp[0] != '0';
+    if (const char* sr = getenv("HFPF_STREAM_REPLAY")) k.stream_replay = sr[0] != '0';
+    if (const char* bs = getenv("HFPF_BIN_SLACK")) k.bin_slack = std::max(1.0f, std::min(4.0f, (float)atof(bs)));
+    if (const char* nw = getenv("HFPF_CLEAN_NOWAIT")) k.clean_small_nowait = nw[0] != '0';
+    if (const char* bs = getenv("HFPF_TEST_BIN_SCALE")) k.test_bin_scale = std::max(0.f, std::min(1.f, (float)atof(bs)));
+    const char* ts = getenv("HFPF_TEST_TABLE_SKIP");
+    k.test_table_skip = ts && ts[0] == '1';
+    const char* mb = getenv("HFPF_MAILBOX");
+    k.mailbox = !mb || mb[0] != '0';
+    int cores = (int)std::thread::hardware_concurrency();
+    cpu_set_t set;
+    if (sched_getaffinity(0, sizeof set, &set) == 0) cores = std::min(cores > 0 ? cores : 1 << 20, CPU_COUNT(&set));  // the process's share
+    const char* st = getenv("HFPF_STAGE_THREADS");
+    k.stage_threads = st ? std::max(0, std::min(atoi(st), 15)) : std::max(0, std::min(7, cores / 2 - 1));
+    return k;
+}
 
 int setup_params(hfpf_handle* h)
 {
@@ -614,24 +661,8 @@ int reset_state(hfpf_handle* h, uint64_t bricks_used = ~0ull, uint64_t normals_u
     HIPCHK(h, hipMemsetAsync(t.bin_off, 0, 2 * (t.max_bricks + 2) * 4, s));
     HIPCHK(h, hipMemsetAsync(t.bin_capb, 0, 2 * (t.max_bricks + 2) * 4, s));
     HIPCHK(h, hipMemsetAsync(t.run_cnt, 0, (t.max_bricks + 2) * 4, s));
-    h->bin_have_hist = false;
-    h->normals_possible = false;
-    h->pend_n = 0;
-    h->pub_seq = 0;
-    h->upd_miss_seen = h->upd_member_seen = 0;  // (upd_wide stays: the next session on this handle fuses the same kind of scene)
-    h->direct_linked = 0;
-    h->n_bricks_known = 0;
-    h->n_bricks_before = 0;
     if (h->h_ctr) memset(h->h_ctr, 0, C_COUNT * sizeof(unsigned long long));  // host mirror follows the device counters
-    h->dirty = false;
-    for (int r = 0; r < kLogRegions; r++) h->n_linked[r] = 0;
-    h->gate_done = 0;
-    h->pend_valid = false;
-    h->poisoned = false;
-    h->poison_msg.clear();
-    h->occ_exported = 0;
-    h->frames_exported = h->frames_seen = 0;
-    h->next_frame_id = 0;
+    h->ss = Session{};
     return HFPF_OK;
 }
 
@@ -680,10 +711,7 @@ int alloc_tables(hfpf_handle* h)
     ALLOC(nv_n, 3 * (t.max_normals + 1), 0, false);
     ALLOC(stats, (t.max_normals + 1) * kStatWords, 0, false);
     t.color = (c.flags & HFPF_FLAG_FUSE_COLOR) ? 1u : 0u;
-    {
-        const char* ts = getenv("HFPF_TEST_TABLE_SKIP");
-        t.test_table_skip = (ts && ts[0] == '1') ? 1u : 0u;
-    }
+    t.test_table_skip = h->knobs.test_table_skip ? 1u : 0u;
     ALLOC(nd_mask, (t.max_bricks + 1) * 8 * 2, 0, false);
     ALLOC(reg_occ, t.max_reg, 0, false);
     ALLOC(dep, t.max_dep + t.max_normals + 1, 0, false);  // dep[] and, behind it, the records' lines (one 32-byte entry each): one entry space
@@ -795,14 +823,14 @@ int pick_update_shape(hfpf_handle* h, double points, uint32_t nb)
 {
     (void)points;
     (void)nb;
-    if (h->upd_shape_forced >= 0) return h->upd_shape_forced;
+    if (h->knobs.upd_shape_forced >= 0) return h->knobs.upd_shape_forced;
     const unsigned long long miss = h->h_ctr[C_TABLE_MISS], member = h->h_ctr[C_DEP_MEMBER] + h->h_ctr[C_REPLAY_MEMBER];
-    if (h->trace_shape)
-        fprintf(stderr, "hfpf: update shape window: %llu table misses, %llu members (%llu of them replayed so far), %s\n", miss - std::min(miss, h->upd_miss_seen),
-                member - std::min(member, h->upd_member_seen), h->h_ctr[C_REPLAY_MEMBER], h->upd_wide ? "wide" : "dense");
-    if (!h->upd_wide && miss > h->upd_miss_seen && (miss - h->upd_miss_seen) * 500ull > member - std::min(member, h->upd_member_seen)) h->upd_wide = true;
-    h->upd_miss_seen = miss;
-    h->upd_member_seen = member;
+    if (h->knobs.trace_shape)
+        fprintf(stderr, "hfpf: update shape window: %llu table misses, %llu members (%llu of them replayed so far), %s\n", miss - std::min(miss, h->ss.upd_miss_seen),
+                member - std::min(member, h->ss.upd_member_seen), h->h_ctr[C_REPLAY_MEMBER], h->upd_wide ? "wide" : "dense");
+    if (!h->upd_wide && miss > h->ss.upd_miss_seen && (miss - h->ss.upd_miss_seen) * 500ull > member - std::min(member, h->ss.upd_member_seen)) h->upd_wide = true;
+    h->ss.upd_miss_seen = miss;
+    h->ss.upd_member_seen = member;
     return h->upd_wide ? 1 : 0;
 }
 
@@ -857,6 +885,44 @@ const PointLayout<FORM>& form_layout(const FrameLayout& lay, const DepthLayout* 
     else return lay;
 }
 
+// Kernel timing.  An event from the handle's pool (resolve_timing gives them back), or a new one.
+hipError_t pooled_event(hfpf_handle* h, hipEvent_t* e)
+{
+    if (h->ev_free.empty()) return hipEventCreate(e);
+    *e = h->ev_free.back();
+    h->ev_free.pop_back();
+    return hipSuccess;
+}
+
+// Bracket work on the engine's stream with a pooled event pair when timing is on: timed_begin in front of it, timed_end behind it
+// files the pair under `list` (ev_pending*), where resolve_timing finds it.
+int timed_begin(hfpf_handle* h, std::pair<hipEvent_t, hipEvent_t>* pr)
+{
+    *pr = {nullptr, nullptr};
+    if (!h->timing) return HFPF_OK;
+    HIPCHK(h, pooled_event(h, &pr->first));
+    HIPCHK(h, pooled_event(h, &pr->second));
+    HIPCHK(h, hipEventRecord(pr->first, h->stream));
+    return HFPF_OK;
+}
+int timed_end(hfpf_handle* h, const std::pair<hipEvent_t, hipEvent_t>& pr, EventPairs& list)
+{
+    if (!pr.first) return HFPF_OK;
+    HIPCHK(h, hipEventRecord(pr.second, h->stream));
+    list.push_back(pr);
+    return HFPF_OK;
+}
+// ... and both around one kernel launch (the march launches of raycast: ev_pending_ray, hfpf_get_kernel_time id 5)
+template <typename Launch>
+int timed_launch(hfpf_handle* h, EventPairs& list, Launch&& launch)
+{
+    std::pair<hipEvent_t, hipEvent_t> timed;
+    if (int rc = timed_begin(h, &timed)) return rc;
+    launch();
+    HIPCHK(h, hipGetLastError());
+    return timed_end(h, timed, list);
+}
+
 // dl != nullptr: the frames are depth images (dev_base / frame_stride address the depth images, n_points = width * height, the
 // cloud layout is unused); the caller has validated them (depth_spec, plus the device alignment of hfpf_integrate_depth_device).
 int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_frames, uint64_t frame_stride, uint32_t n_points,
@@ -870,16 +936,16 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
     int rc;
     if (!dl && (rc = check_cloud_layout(h, "integrate", lay, true))) return rc;
     if (n_frames > 65535) return fail(h, HFPF_ERR_BAD_ARG, "integrate: at most 65535 frames per call");
-    h->pub_seq = 0;  // kernels are about to be enqueued: a counter snapshot already on its way is no longer the latest
+    h->ss.pub_seq = 0;  // kernels are about to be enqueued: a counter snapshot already on its way is no longer the latest
     StageSlot* s = nullptr;
     if ((rc = acquire_stage(h, n_frames, &s))) return rc;
     memcpy(s->h_pose, poses, (size_t)n_frames * 12 * sizeof(double));
     for (uint32_t f = 0; f < n_frames; f++) {
-        const uint32_t id = frame_ids ? frame_ids[f] : h->next_frame_id + f;
+        const uint32_t id = frame_ids ? frame_ids[f] : h->ss.next_frame_id + f;
         if (id >= h->t.max_frames) return fail(h, HFPF_ERR_CAPACITY, "frame id %u >= max_frames %llu", id, (unsigned long long)h->t.max_frames);
         s->h_ids[f] = id;
     }
-    if (!frame_ids) h->next_frame_id += n_frames;
+    if (!frame_ids) h->ss.next_frame_id += n_frames;
     HIPCHK(h, hipMemcpyAsync(s->d_pose, s->h_pose, (size_t)n_frames * (12 * sizeof(double) + sizeof(uint32_t)), hipMemcpyHostToDevice, h->stream));  // poses + ids
 
     const int form = dl ? kFormDepth : packed16(lay, dev_base, true, frame_stride) ? kFormPacked16 : kFormStrided;
@@ -890,23 +956,11 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
     const uint32_t fw = dl ? dl->width : h->cfg.frame_width;
     const uint32_t row_w = (fw >= 16 && fw % 16 == 0 && n_points % fw == 0 && (n_points / fw) % 16 == 0) ? fw : 0u;
     const dim3 grid((unsigned)std::min<uint64_t>(n_tiles, (uint64_t)h->integrate_grid));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->timing) {
-        auto get = [&](hipEvent_t& e) -> hipError_t {
-            if (!h->ev_free.empty()) {
-                e = h->ev_free.back();
-                h->ev_free.pop_back();
-                return hipSuccess;
-            }
-            return hipEventCreate(&e);
-        };
-        HIPCHK(h, get(e0));
-        HIPCHK(h, get(e1));
-        HIPCHK(h, hipEventRecord(e0, h->stream));
-    }
+    std::pair<hipEvent_t, hipEvent_t> timed;
+    if ((rc = timed_begin(h, &timed))) return rc;
     const bool color = h->t.color != 0;
     const bool bin = h->binned;
-    const uint32_t pre_possible = (h->h_ctr[C_NORMALS] > 0 || h->normals_possible) ? 1u : 0u;  // a clean pass has run: unoccupied cells may carry a dependant
+    const uint32_t pre_possible = (h->h_ctr[C_NORMALS] > 0 || h->ss.normals_possible) ? 1u : 0u;  // a clean pass has run: unoccupied cells may carry a dependant
     // k_integrate on the batch's first launch_frames frames; probe = 1: the dry run
     auto launch_integrate = [&](dim3 grid_, bool bin_, uint32_t launch_frames, uint32_t log_rot, uint32_t probe) {
         with_form(form, color, bin_, [&](auto F, auto C, auto B) {
@@ -919,7 +973,7 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
     // the bricks the batch touches and 16 find 50 % (32: 57 %), and the plan made from the larger sample sends 30 % fewer points
     // through the overflow list (268 K instead of 382 K per 1000-frame pass): whole job +1.5 %; 32 frames add nothing.
     const uint32_t probe_frames = n_frames >= 8u * (uint32_t)kProbeFrames ? 2u * (uint32_t)kProbeFrames : (uint32_t)kProbeFrames;
-    if (bin && !h->bin_have_hist && n_frames > probe_frames) {
+    if (bin && !h->ss.bin_have_hist && n_frames > probe_frames) {
         // No plan for the per-brick bins yet (first batch of a session): a dry run of the batch's first frames claims their
         // bricks and records the per-region demand, so that the real launch below parks from its first point.  One extra
         // read-back (the brick count), once per session; batches of up to kProbeFrames frames just take the direct forms.
@@ -930,18 +984,18 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
         HIPCHK(h, hipGetLastError());
         int rcp = read_counters(h);  // bricks the dry run claimed
         if (rcp) return rcp;
-        h->bin_have_hist = true;
-        h->bin_from_probe = true;  // the plan of the launch below comes from a sample: more slack per region
-        h->bin_prev_points = (double)n_points * probe_frames;
+        h->ss.bin_have_hist = true;
+        h->ss.bin_from_probe = true;  // the plan of the launch below comes from a sample: more slack per region
+        h->ss.bin_prev_points = (double)n_points * probe_frames;
     }
-    const uint32_t nb_known = (uint32_t)h->n_bricks_known;
+    const uint32_t nb_known = (uint32_t)h->ss.n_bricks_known;
     // a plan = per-brick bin regions sized from the previous launch's demand; without one nothing is parked (direct forms)
-    const bool have_plan = bin && h->bin_have_hist && nb_known > 0;
+    const bool have_plan = bin && h->ss.bin_have_hist && nb_known > 0;
     // Bricks this launch may discover get spare regions of an average brick's size: as many as the session found between its last
     // two counter read-backs (x2), i.e. half the known bricks right after the dry run and a few hundred in the steady state.
     uint32_t spare = 0, spare_cap = 0;
-    if (have_plan && h->bin_spare) {
-        const uint64_t grown = h->n_bricks_known - std::min(h->n_bricks_known, h->n_bricks_before);
+    if (have_plan && h->knobs.bin_spare) {
+        const uint64_t grown = h->ss.n_bricks_known - std::min(h->ss.n_bricks_known, h->ss.n_bricks_before);
         spare = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(2 * grown, 256), std::max<uint64_t>(nb_known / 2, 256));
         spare = (uint32_t)std::min<uint64_t>(spare, h->t.max_bricks - std::min<uint64_t>(h->t.max_bricks, nb_known));
     }
@@ -975,15 +1029,15 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
         h->t.ovf_aux = (uint2*)h->ovf_aux_buf.p;
         h->t.ovf_cap = pts;
         if (have_plan) {
-            const float scale = (float)((double)pts / std::max(1.0, h->bin_prev_points)) * h->test_bin_scale;
+            const float scale = (float)((double)pts / std::max(1.0, h->ss.bin_prev_points)) * h->knobs.test_bin_scale;
             const uint32_t n_regions = 2u * (nb_known + 1u);  // two per brick: cells with / without a normal
             const uint32_t n_planned = 2u * (nb + 1u);        // ... and the spare ones behind them
             const uint32_t all_regions = 2u * (uint32_t)(h->t.max_bricks + 2);
             int rc2 = scratch(h, h->bin_sums, (size_t)blocks_for(all_regions, kBinPlanTile) * sizeof(uint32_t));
             if (rc2) return rc2;
             hipLaunchKernelGGL(k_bin_plan, dim3(blocks_for(n_planned, kBinPlanTile)), dim3(256), 0, h->stream, h->t, n_regions, n_planned, spare_cap, scale,
-                               h->bin_from_probe ? std::max(1.5f, h->bin_slack) : h->bin_slack, (uint32_t*)h->bin_sums.p);
-            h->bin_from_probe = false;
+                               h->ss.bin_from_probe ? std::max(1.5f, h->knobs.bin_slack) : h->knobs.bin_slack, (uint32_t*)h->bin_sums.p);
+            h->ss.bin_from_probe = false;
             hipLaunchKernelGGL(k_bin_place, dim3(blocks_for(all_regions, kBinPlanTile)), dim3(256), 0, h->stream, h->t, n_planned, all_regions, h->bin_pool,
                                (const uint32_t*)h->bin_sums.p);
         } else {  // no plan yet: no region exists, every lane takes the direct forms, the demand is recorded
@@ -1012,12 +1066,7 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
     auto detail_mark = [&]() -> hipError_t {  // per-kernel boundaries of this call (detail timing only)
         if (!h->timing_detail) return hipSuccess;
         hipEvent_t e = nullptr;
-        if (!h->ev_free.empty()) {
-            e = h->ev_free.back();
-            h->ev_free.pop_back();
-        } else if (hipError_t r = hipEventCreate(&e)) {
-            return r;
-        }
+        if (hipError_t r = pooled_event(h, &e)) return r;
         h->ev_detail.push_back(e);
         return hipEventRecord(e, h->stream);
     };
@@ -1033,9 +1082,9 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
         }
         HIPCHK(h, detail_mark());
         if (have_plan) {
-            if (h->h_ctr[C_NORMALS] > 0 || h->normals_possible) {  // without a normal record no cell has dependants
+            if (h->h_ctr[C_NORMALS] > 0 || h->ss.normals_possible) {  // without a normal record no cell has dependants
                 detail_ran |= 2;
-                if (h->update_cells) {
+                if (h->knobs.update_cells) {
                     const int shape = pick_update_shape(h, (double)n_points * n_frames, nb);
 #define HFPF_LAUNCH_UPDATE(C, S) \
     hipLaunchKernelGGL((k_update_cells<C, S.threads, S.cap, S.slots, S.desc, S.waves>), dim3(nb), dim3(S.threads), 0, h->stream, h->g, h->t, nb)
@@ -1058,26 +1107,23 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
             HIPCHK(h, detail_mark());
             HIPCHK(h, detail_mark());
         }
-        h->bin_have_hist = true;
-        h->bin_prev_points = (double)n_points * n_frames;
+        h->ss.bin_have_hist = true;
+        h->ss.bin_prev_points = (double)n_points * n_frames;
     }
     HIPCHK(h, hipGetLastError());
     if (h->timing_detail) h->ev_detail_ran.push_back(detail_ran);
     detail_guard.done = true;
-    if (h->timing) {
-        HIPCHK(h, hipEventRecord(e1, h->stream));
-        h->ev_pending.emplace_back(e0, e1);
-    }
+    if ((rc = timed_end(h, timed, h->ev_pending))) return rc;
     HIPCHK(h, hipEventRecord(s->done, h->stream));
     s->pending = true;
-    h->dirty = true;  // state_changed = true, grid.hpp:189
+    h->ss.dirty = true;  // state_changed = true, grid.hpp:189
     h->frames_integrated += n_frames;
     if (h->mbox && n_frames >= 4) {  // a batch: the next call is probably a clean pass, which starts by reading the counters
-        h->pub_seq = ++h->mbox_seq;
-        k_publish_counters<<<1, 256, 0, h->stream>>>(h->t.ctr, h->t.log_ctr, h->mbox, h->pub_seq);
+        h->ss.pub_seq = ++h->mbox_seq;
+        k_publish_counters<<<1, 256, 0, h->stream>>>(h->t.ctr, h->t.log_ctr, h->mbox, h->ss.pub_seq);
         HIPCHK(h, hipGetLastError());
     } else {
-        h->pub_seq = 0;
+        h->ss.pub_seq = 0;
     }
     return HFPF_OK;
 }
@@ -1086,33 +1132,22 @@ int resolve_timing(hfpf_handle* h)
 {
     if (h->ev_pending.empty() && h->ev_pending_clean.empty() && h->ev_pending_ray.empty() && h->ev_detail.empty()) return HFPF_OK;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (auto& pr : h->ev_pending_ray) {
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, pr.first, pr.second));
-        h->t_ray_ms += (double)ms;
-        h->n_ray_timed++;
-        h->ev_free.push_back(pr.first);
-        h->ev_free.push_back(pr.second);
-    }
-    h->ev_pending_ray.clear();
-    for (auto& pr : h->ev_pending_clean) {
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, pr.first, pr.second));
-        h->t_clean_ms += (double)ms;
-        h->n_clean_timed++;
-        h->ev_free.push_back(pr.first);
-        h->ev_free.push_back(pr.second);
-    }
-    h->ev_pending_clean.clear();
-    for (auto& pr : h->ev_pending) {
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, pr.first, pr.second));
-        h->t_integrate_ms += (double)ms;
-        h->n_integrate_launches++;
-        h->ev_free.push_back(pr.first);
-        h->ev_free.push_back(pr.second);
-    }
-    h->ev_pending.clear();
+    auto settle = [&](EventPairs& list, double& total_ms, uint64_t& n) -> int {
+        for (auto& pr : list) {
+            float ms = 0.f;
+            HIPCHK(h, hipEventElapsedTime(&ms, pr.first, pr.second));
+            total_ms += (double)ms;
+            n++;
+            h->ev_free.push_back(pr.first);
+            h->ev_free.push_back(pr.second);
+        }
+        list.clear();
+        return HFPF_OK;
+    };
+    int rc;
+    if ((rc = settle(h->ev_pending_ray, h->t_ray_ms, h->n_ray_timed))) return rc;
+    if ((rc = settle(h->ev_pending_clean, h->t_clean_ms, h->n_clean_timed))) return rc;
+    if ((rc = settle(h->ev_pending, h->t_integrate_ms, h->n_integrate_launches))) return rc;
     for (size_t c = 0; 4 * c + 3 < h->ev_detail.size() && c < h->ev_detail_ran.size(); c++) {
         for (int k = 0; k < 3; k++) {
             if (!(h->ev_detail_ran[c] & (1u << k))) continue;  // not launched in this call (e.g. no dependants yet: no k_update_cells)
@@ -1194,17 +1229,17 @@ int epoch_export_locked(hfpf_handle* h, uint64_t* n_out, uint64_t min_capacity_r
     if (rc) return rc;
     if ((rc = check_device_errors(h))) return rc;
     const uint64_t n_occ = std::min<uint64_t>(h->h_ctr[C_OCC], h->t.max_occ);
-    const uint64_t n_cells = n_occ - std::min(n_occ, h->occ_exported);
+    const uint64_t n_cells = n_occ - std::min(n_occ, h->ss.occ_exported);
     const uint64_t n_fr_all = std::min<uint64_t>(h->h_ctr[C_FRAMES], h->t.max_frames);
-    const uint64_t n_frames = n_fr_all - std::min(n_fr_all, h->frames_exported);
+    const uint64_t n_frames = n_fr_all - std::min(n_fr_all, h->ss.frames_exported);
     const uint64_t n_new = n_cells + 2 * n_frames;  // one record per cell, two per frame (its viewpoint)
     if ((rc = scratch(h, h->ex_send, std::max<uint64_t>(std::max(n_new, min_capacity_records), 1) * sizeof(EpochRec)))) return rc;
     if (n_new) {
-        hipLaunchKernelGGL(k_epoch_export, dim3(blocks_for(n_new, 256)), dim3(256), 0, h->stream, h->g, h->t, h->occ_exported, n_cells, h->frames_exported, n_frames,
+        hipLaunchKernelGGL(k_epoch_export, dim3(blocks_for(n_new, 256)), dim3(256), 0, h->stream, h->g, h->t, h->ss.occ_exported, n_cells, h->ss.frames_exported, n_frames,
                            (EpochRec*)h->ex_send.p);
         HIPCHK(h, hipGetLastError());
     }
-    h->frames_seen = n_fr_all;  // (the clean pass that follows the exchange marks them exchanged, like the cells)
+    h->ss.frames_seen = n_fr_all;  // (the clean pass that follows the exchange marks them exchanged, like the cells)
     *n_out = n_new;
     return HFPF_OK;
 }
@@ -1212,7 +1247,7 @@ int epoch_export_locked(hfpf_handle* h, uint64_t* n_out, uint64_t min_capacity_r
 int epoch_import_locked(hfpf_handle* h, const void* dev_records, uint64_t n)
 {
     if (n == 0) return HFPF_OK;
-    h->pub_seq = 0;  // the import changes counters behind any snapshot already on its way
+    h->ss.pub_seq = 0;  // the import changes counters behind any snapshot already on its way
     hipLaunchKernelGGL(k_epoch_import, dim3(blocks_for(n, 256 * kImportTiles)), dim3(256), 0, h->stream, h->g, h->t, (const EpochRec*)dev_records, n);
     HIPCHK(h, hipGetLastError());
     return HFPF_OK;
@@ -1342,10 +1377,10 @@ int clean_locked(hfpf_handle* h, int pre_rc)
     if ((rc = check_device_errors(h))) return rc;
     const uint64_t n_occ = std::min<uint64_t>(h->h_ctr[C_OCC], t.max_occ);
     const uint64_t n_normals = h->h_ctr[C_NORMALS];
-    const uint64_t n_pend = h->pend_valid ? h->h_ctr[C_PEND] : 0;  // cells the previous pass left without a normal (pend_a)
-    h->occ_exported = n_occ;  // everything occupied so far (locally or imported) has been exchanged
-    h->frames_exported = std::max(h->frames_exported, h->frames_seen);  // ... and the viewpoints of the frames the last export covered
-    h->dirty = false;  // state_changed = false, grid.hpp:313
+    const uint64_t n_pend = h->ss.pend_valid ? h->h_ctr[C_PEND] : 0;  // cells the previous pass left without a normal (pend_a)
+    h->ss.occ_exported = n_occ;  // everything occupied so far (locally or imported) has been exchanged
+    h->ss.frames_exported = std::max(h->ss.frames_exported, h->ss.frames_seen);  // ... and the viewpoints of the frames the last export covered
+    h->ss.dirty = false;  // state_changed = false, grid.hpp:313
     h->clean_passes++;
 
     {
@@ -1354,22 +1389,22 @@ int clean_locked(hfpf_handle* h, int pre_rc)
         for (int r = 0; r < kLogRegions; r++) {
             const uint64_t n_r = std::min<uint64_t>(h->h_log_ctr[r * 16], t.log_region_cap);
             const uint64_t base = (uint64_t)r * t.log_region_cap;
-            lr.first[r] = (uint32_t)(base + h->n_linked[r] + 1);
+            lr.first[r] = (uint32_t)(base + h->ss.n_linked[r] + 1);
             lr.last[r] = (uint32_t)(base + n_r);
-            max_new = std::max(max_new, n_r - h->n_linked[r]);
-            h->n_linked[r] = n_r;
+            max_new = std::max(max_new, n_r - h->ss.n_linked[r]);
+            h->ss.n_linked[r] = n_r;
         }
         // entries appended by k_buffer arrive chained; only k_integrate's direct form leaves marked entries behind
-        if (max_new && !h->binned && h->h_ctr[C_BUFFERED] != h->direct_linked) {  // (the binned form chains its few direct appends itself)
+        if (max_new && !h->binned && h->h_ctr[C_BUFFERED] != h->ss.direct_linked) {  // (the binned form chains its few direct appends itself)
             hipLaunchKernelGGL(k_link_log, dim3(blocks_for(max_new, 256), kLogRegions), dim3(256), 0, s, t, lr);
             HIPCHK(h, hipGetLastError());
         }
-        h->direct_linked = h->h_ctr[C_BUFFERED];
+        h->ss.direct_linked = h->h_ctr[C_BUFFERED];
     }
     if (n_occ == 0) return HFPF_OK;
 
     // candidates: the cells that failed the gate last time (pending list) + the cells occupied since (new tail of occ_list)
-    const uint64_t n_new_occ = n_occ - std::min(n_occ, h->gate_done);
+    const uint64_t n_new_occ = n_occ - std::min(n_occ, h->ss.gate_done);
     const uint64_t n_in = n_pend + n_new_occ;  // upper bound of everything this pass can produce per candidate
     if (n_in == 0) return HFPF_OK;
     if ((rc = scratch(h, h->pend_b, n_in * 4))) return rc;
@@ -1385,13 +1420,13 @@ int clean_locked(hfpf_handle* h, int pre_rc)
     const uint64_t live_ub = std::min<uint64_t>(h->h_ctr[C_REG], t.max_reg) + std::min<uint64_t>(h->h_ctr[C_PREREG], t.max_reg);
     bool full = h->h_ctr[C_DEP] + 2 * live_ub + 2 * reg_ub + n_new_occ > t.max_dep;
     // sentinels + the pass's list counters + the pre-dependants of the cells occupied since the last pass become their lists
-    hipLaunchKernelGGL(k_clean_begin, dim3(blocks_for(n_in, 256)), dim3(256), 0, s, t, n_in, (const uint32_t*)(t.occ_list + h->gate_done), n_new_occ, full ? 1u : 0u);
-    launch_gate(h, (const uint32_t*)h->pend_a.p, n_pend, (const uint32_t*)(t.occ_list + h->gate_done), n_new_occ, (uint32_t*)h->pend_b.p);
+    hipLaunchKernelGGL(k_clean_begin, dim3(blocks_for(n_in, 256)), dim3(256), 0, s, t, n_in, (const uint32_t*)(t.occ_list + h->ss.gate_done), n_new_occ, full ? 1u : 0u);
+    launch_gate(h, (const uint32_t*)h->pend_a.p, n_pend, (const uint32_t*)(t.occ_list + h->ss.gate_done), n_new_occ, (uint32_t*)h->pend_b.p);
     HIPCHK(h, hipGetLastError());
-    h->gate_done = n_occ;
-    h->normals_possible = true;
+    h->ss.gate_done = n_occ;
+    h->ss.normals_possible = true;
     std::swap(h->pend_a, h->pend_b);  // cells that got a normal in this pass are dropped by the next gate's kNormal test
-    h->pend_valid = true;             // C_PEND now counts pend_a; the host reads it at the start of the next pass
+    h->ss.pend_valid = true;             // C_PEND now counts pend_a; the host reads it at the start of the next pass
 
     // canonical order: ascending (x,y,z) key; record id = n_normals + rank + 1
     // (with HFPF_MORTON_IDS the candidate keys are Z-order codes: three interleaved axes of the widest axis' bits)
@@ -1412,7 +1447,7 @@ int clean_locked(hfpf_handle* h, int pre_rc)
     // the device, and the host does not wait for the pass at all (no mid-pass read-back: the GPU is not left idle for a host
     // round trip, and the next integrate call is enqueued behind the replay at once).  The bound above makes sure the pass
     // cannot run out of dep[] half-way (the one overflow the host would have to repair by compacting).
-    const bool no_wait = !full && reg_ub < (1ull << 21) && h->clean_small_nowait;
+    const bool no_wait = !full && reg_ub < (1ull << 21) && h->knobs.clean_small_nowait;
     if (!full) {
         hipLaunchKernelGGL(k_depinc_offsets, dim3(blocks_for(reg_ub, 256 * kListTiles)), dim3(256), 0, s, t, kCountOnDevice);
         hipLaunchKernelGGL(k_depinc_fill, dim3(blocks_for(reg_ub, 256)), dim3(256), 0, s, t, reg_first, kCountOnDevice);
@@ -1473,11 +1508,11 @@ int clean_locked(hfpf_handle* h, int pre_rc)
         // brick is new in it) replay by streaming that run: worth its launch over every brick when enough of the touched cells
         // lie in such bricks.  The chain walk takes the others.
         const uint64_t single = full ? 0 : std::min<uint64_t>(h->h_ctr[C_TOUCHED_SINGLE], inc_touched);
-        const bool stream = !full && h->binned && h->stream_replay && single >= (1ull << 16);
+        const bool stream = !full && h->binned && h->knobs.stream_replay && single >= (1ull << 16);
         if (stream) {
-            const uint32_t nbk = (uint32_t)h->n_bricks_known;
+            const uint32_t nbk = (uint32_t)h->ss.n_bricks_known;
 #define HFPF_LAUNCH_STREAM(C, S) hipLaunchKernelGGL((k_update_cells<C, S.threads, S.cap, S.slots, S.desc, S.waves, true>), dim3(nbk), dim3(S.threads), 0, s, h->g, t, nbk)
-            const bool wide = h->upd_shape_forced >= 0 ? h->upd_shape_forced == 1 : h->upd_wide;  // the shape the dependant updates of this session take
+            const bool wide = h->knobs.upd_shape_forced >= 0 ? h->knobs.upd_shape_forced == 1 : h->upd_wide;  // the shape the dependant updates of this session take
             if (t.color && wide) HFPF_LAUNCH_STREAM(true, kUpdWideColor);
             else if (t.color) HFPF_LAUNCH_STREAM(true, kUpdDenseColor);
             else if (wide) HFPF_LAUNCH_STREAM(false, kUpdWide);
@@ -1493,7 +1528,7 @@ int clean_locked(hfpf_handle* h, int pre_rc)
             if (walked >= (1ull << 18)) {
                 if ((rc = scratch(h, h->vals_a, inc_touched * 4))) return rc;
                 unsigned slot_bits = 9;  // slot = brick * 512 + cell; the brick count is as of the read-back just above
-                while ((1ull << slot_bits) < (h->n_bricks_known + 2) * (uint64_t)kBrickCells && slot_bits < 32) slot_bits++;
+                while ((1ull << slot_bits) < (h->ss.n_bricks_known + 2) * (uint64_t)kBrickCells && slot_bits < 32) slot_bits++;
                 if ((rc = sort_keys_u32(h, t.touched_list, (uint32_t*)h->vals_a.p, inc_touched, slot_bits))) return rc;
                 cells = (const uint32_t*)h->vals_a.p;
             }
@@ -1541,6 +1576,7 @@ int hfpf_create(const hfpf_config* cfg, hfpf_handle** out)
     *out = nullptr;
     hfpf_handle* h = new hfpf_handle();
     h->cfg = *cfg;
+    h->knobs = read_knobs();
     auto bail = [&](int rc) {
         g_create_error = h->err;
         for (void* p : h->allocs) (void)hipFree(p);
@@ -1563,8 +1599,7 @@ int hfpf_create(const hfpf_config* cfg, hfpf_handle** out)
     if ((e = hipSetDevice(cfg->device)) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(e)));
     if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)));
     if ((e = hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking)) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)));
-    if (const char* cs = getenv("HFPF_COPY_STREAMS")) h->n_copy_streams = std::max(1, std::min(atoi(cs), 4));
-    for (int k = 0; k + 1 < h->n_copy_streams; k++)
+    for (int k = 0; k + 1 < h->knobs.copy_streams; k++)
         if ((e = hipStreamCreateWithFlags(&h->copy_more[k], hipStreamNonBlocking)) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)));
     if ((e = hipHostMalloc((void**)&h->h_ctr, C_COUNT * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess)
         return bail(fail(h, HFPF_ERR_HIP, "hipHostMalloc: %s", hipGetErrorString(e)));
@@ -1572,23 +1607,10 @@ int hfpf_create(const hfpf_config* cfg, hfpf_handle** out)
     if ((e = hipHostMalloc((void**)&h->h_log_ctr, kLogRegions * 16 * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess)
         return bail(fail(h, HFPF_ERR_HIP, "hipHostMalloc: %s", hipGetErrorString(e)));
     memset(h->h_log_ctr, 0, kLogRegions * 16 * sizeof(unsigned long long));
-    {
-        const char* uf = getenv("HFPF_UPDATE_FORM");
-        h->update_cells = !(uf && uf[0] == 'p');
-        if (const char* hb = getenv("HFPF_HOST_BATCH")) h->host_batch = std::max(1, std::min(atoi(hb), kFrameSlots));
-        if (const char* us = getenv("HFPF_UPD_SHAPE")) h->upd_shape_forced = std::max(0, std::min(atoi(us), 1));
-        if (const char* tr = getenv("HFPF_TRACE_SHAPE")) h->trace_shape = tr[0] != '0';
-        if (const char* sp = getenv("HFPF_BIN_SPARE")) h->bin_spare = sp[0] != '0';
-        if (const char* sr = getenv("HFPF_STREAM_REPLAY")) h->stream_replay = sr[0] != '0';
-        if (const char* bs = getenv("HFPF_BIN_SLACK")) h->bin_slack = std::max(1.0f, std::min(4.0f, (float)atof(bs)));
-        if (const char* nw = getenv("HFPF_CLEAN_NOWAIT")) h->clean_small_nowait = nw[0] != '0';
-        if (const char* bs = getenv("HFPF_TEST_BIN_SCALE")) h->test_bin_scale = std::max(0.f, std::min(1.f, (float)atof(bs)));
-        const char* mb = getenv("HFPF_MAILBOX");
-        if (!mb || mb[0] != '0') {
-            if ((e = hipHostMalloc((void**)&h->mbox, (kMboxWords + 8) * sizeof(unsigned long long), hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess)
-                return bail(fail(h, HFPF_ERR_HIP, "hipHostMalloc (mailbox): %s", hipGetErrorString(e)));
-            memset(h->mbox, 0, (kMboxWords + 8) * sizeof(unsigned long long));
-        }
+    if (h->knobs.mailbox) {
+        if ((e = hipHostMalloc((void**)&h->mbox, (kMboxWords + 8) * sizeof(unsigned long long), hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess)
+            return bail(fail(h, HFPF_ERR_HIP, "hipHostMalloc (mailbox): %s", hipGetErrorString(e)));
+        memset(h->mbox, 0, (kMboxWords + 8) * sizeof(unsigned long long));
     }
     {
         int per_cu = 0, cus = 0;
@@ -1713,18 +1735,11 @@ int hfpf_integrate_device(hfpf_handle* h, const void* dev_base, uint32_t n_frame
 }
 
 // Large host-to-host copies (the bounce copy of hfpf_integrate, the row download of extract) are split over the caller and the
-// helper threads of the handle's StagePool (HFPF_STAGE_THREADS, default half the process's cores - 1, at most 7; 0 = none).
+// helper threads of the handle's StagePool (Knobs::stage_threads).
 static void host_copy(hfpf_handle* h, void* dst, const void* src, size_t bytes)
 {
-    if (h->stage_threads < 0) {
-        const char* e = getenv("HFPF_STAGE_THREADS");
-        int cores = (int)std::thread::hardware_concurrency();
-        cpu_set_t set;
-        if (sched_getaffinity(0, sizeof set, &set) == 0) cores = std::min(cores > 0 ? cores : 1 << 20, CPU_COUNT(&set));  // the process's share
-        h->stage_threads = e ? std::max(0, std::min(atoi(e), 15)) : std::max(0, std::min(7, cores / 2 - 1));
-    }
-    if (h->stage_threads > 0 && bytes >= (1u << 20)) {
-        if (!h->stage_pool) h->stage_pool = new StagePool(h->stage_threads);
+    if (h->knobs.stage_threads > 0 && bytes >= (1u << 20)) {
+        if (!h->stage_pool) h->stage_pool = new StagePool(h->knobs.stage_threads);
         h->stage_pool->copy(dst, src, bytes);
     } else {
         stream_copy((char*)dst, (const char*)src, bytes);
@@ -1734,24 +1749,24 @@ static void host_copy(hfpf_handle* h, void* dst, const void* src, size_t bytes)
 // Hand the uploaded-but-not-launched host frames to the kernels: one integrate launch for the batch.
 static int flush_pending_locked(hfpf_handle* h)
 {
-    if (h->pend_n == 0) return HFPF_OK;
-    const uint32_t first = h->pend_first, n = h->pend_n;
-    h->pend_n = 0;
+    if (h->ss.pend_n == 0) return HFPF_OK;
+    const uint32_t first = h->ss.pend_first, n = h->ss.pend_n;
+    h->ss.pend_n = 0;
     // the handle refuses work until hfpf_clear: frames accepted before the failure surfaced are dropped, and the caller is told
-    if (h->poisoned) return fail(h, HFPF_ERR_STATE, "%u accepted host frame(s) dropped: handle failed earlier (%s); hfpf_clear resets it", n, h->poison_msg.c_str());
-    // The slots of a batch alternate over the copy streams (slot % n_copy_streams): the kernels wait for the LAST upload of every
+    if (h->ss.poisoned) return fail(h, HFPF_ERR_STATE, "%u accepted host frame(s) dropped: handle failed earlier (%s); hfpf_clear resets it", n, h->ss.poison_msg.c_str());
+    // The slots of a batch alternate over the copy streams (slot % knobs.copy_streams): the kernels wait for the LAST upload of every
     // stream that carried one of them -- a stream is in order, so its earlier uploads are done too.  (f.done, recorded behind the
     // kernels below, then also means "this slot's upload has left its pinned bounce buffer".)
     for (uint32_t k = n, seen = 0; k-- > 0;) {
-        const uint32_t which = (first + k) % (uint32_t)h->n_copy_streams;
+        const uint32_t which = (first + k) % (uint32_t)h->knobs.copy_streams;
         if (seen & (1u << which)) continue;
         seen |= 1u << which;
         HIPCHK(h, hipStreamWaitEvent(h->stream, h->fslot[first + k].copied, 0));
     }
     const char* ring = (const char*)h->ring_d + (size_t)first * h->ring_cap;
-    const DepthLayout dl = depth_layout(h->pend_ds, ring + h->pend_ds.color_off, h->ring_cap);
-    int rc = integrate_device_locked(h, ring, n, h->ring_cap, h->pend_pts, h->pend_lay[0], h->pend_lay[1], h->pend_lay[2], h->pend_lay[3],
-                                     h->pend_lay[4], h->pend_pose, nullptr, h->pend_depth ? &dl : nullptr);
+    const DepthLayout dl = depth_layout(h->ss.pend_ds, ring + h->ss.pend_ds.color_off, h->ring_cap);
+    int rc = integrate_device_locked(h, ring, n, h->ring_cap, h->ss.pend_pts, h->ss.pend_lay[0], h->ss.pend_lay[1], h->ss.pend_lay[2], h->ss.pend_lay[3],
+                                     h->ss.pend_lay[4], h->ss.pend_pose, nullptr, h->ss.pend_depth ? &dl : nullptr);
     // frames that were accepted with HFPF_OK are lost: whichever entry point found them waiting, the handle stops until hfpf_clear
     if (rc) return poison_on_error(h, rc);
     for (uint32_t k = 0; k < n; k++) {
@@ -1763,6 +1778,23 @@ static int flush_pending_locked(hfpf_handle* h)
     HIPCHK(h, hipEventRecord(h->busy_ev, h->stream));
     h->busy_pending = true;
     return HFPF_OK;
+}
+
+// What a call that reads the fused model does first: select the device, launch the host frames still waiting (a failure there
+// poisons the handle), refuse a failed handle, read the counters, surface deferred device errors (which poison it too).  Used by
+// extract_filtered, snapshot and -- behind their refusal of distributed handles -- render, track, query, raycast and mesh.
+// Entry points whose sequence DIFFERS keep their own, because aligning them would change what a failed handle returns:
+// hfpf_extract_with_stats (no usability check, no poisoning), hfpf_sync (no usability check; only its error check poisons),
+// hfpf_get_counters and hfpf_get_occupied (flush and read-back only), hfpf_stats_export (its flush does not poison),
+// hfpf_epoch_export (no poisoning), hfpf_epoch_import* (flush only; the gathered form adds the usability check).
+static int read_prologue_locked(hfpf_handle* h)
+{
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = poison_on_error(h, flush_pending_locked(h));
+    if (!rc) rc = check_usable(h);
+    if (!rc) rc = read_counters(h);
+    if (!rc) rc = poison_on_error(h, check_device_errors(h));
+    return rc;
 }
 
 // One host frame: upload on the copy stream into the next slot of the device ring; launch it -- together with the frames still
@@ -1780,9 +1812,9 @@ static int integrate_host_locked(hfpf_handle* h, const void* base, bool bounce, 
     int rc;
     if (n_points == 0 && !ds) {
         if ((rc = flush_pending_locked(h))) return rc;  // frame ids stay in arrival order
-        h->next_frame_id++;
+        h->ss.next_frame_id++;
         h->frames_integrated++;
-        h->dirty = true;
+        h->ss.dirty = true;
         return HFPF_OK;
     }
     if (!ds && (rc = check_cloud_layout(h, "integrate", FrameLayout{point_step, off_x, off_y, off_z, off_rgb}, true))) return rc;
@@ -1790,9 +1822,9 @@ static int integrate_host_locked(hfpf_handle* h, const void* base, bool bounce, 
     const size_t bytes = ds ? (ds->color_bpp ? ds->color_off + ds->color_bytes() : ds->depth_bytes()) : (size_t)n_points * point_step;
     // a frame of another kind or shape (depth frames: size, formats, intrinsics), or a slot that is not the batch's neighbour
     // (ring wrap), closes the pending batch
-    const bool kind_differs = h->pend_depth != (ds != nullptr) || (ds && memcmp(&h->pend_ds, ds, sizeof *ds) != 0);
-    if (h->pend_n && (kind_differs || h->pend_pts != n_points || memcmp(h->pend_lay, lay, sizeof lay) != 0 ||
-                      (uint32_t)h->fslot_next != h->pend_first + h->pend_n)) {
+    const bool kind_differs = h->ss.pend_depth != (ds != nullptr) || (ds && memcmp(&h->ss.pend_ds, ds, sizeof *ds) != 0);
+    if (h->ss.pend_n && (kind_differs || h->ss.pend_pts != n_points || memcmp(h->ss.pend_lay, lay, sizeof lay) != 0 ||
+                      (uint32_t)h->fslot_next != h->ss.pend_first + h->ss.pend_n)) {
         if ((rc = flush_pending_locked(h))) return rc;
     }
     if (h->ring_cap < bytes) {  // (re)size the ring: nothing may be in flight in it
@@ -1838,7 +1870,7 @@ static int integrate_host_locked(hfpf_handle* h, const void* base, bool bounce, 
         }
         src = f.h;
     }
-    const uint32_t which = slot % (uint32_t)h->n_copy_streams;
+    const uint32_t which = slot % (uint32_t)h->knobs.copy_streams;
     hipStream_t cs = which ? h->copy_more[which - 1] : h->copy_stream;
     char* dst = (char*)h->ring_d + (size_t)slot * h->ring_cap;
     if (ds && !bounce) {  // two page-locked buffers of the caller: two uploads
@@ -1848,17 +1880,17 @@ static int integrate_host_locked(hfpf_handle* h, const void* base, bool bounce, 
         HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, cs));
     }
     HIPCHK(h, hipEventRecord(f.copied, cs));
-    if (h->pend_n == 0) {
-        h->pend_first = slot;
-        h->pend_pts = n_points;
-        memcpy(h->pend_lay, lay, sizeof lay);
-        h->pend_depth = ds != nullptr;
-        if (ds) h->pend_ds = *ds;
+    if (h->ss.pend_n == 0) {
+        h->ss.pend_first = slot;
+        h->ss.pend_pts = n_points;
+        memcpy(h->ss.pend_lay, lay, sizeof lay);
+        h->ss.pend_depth = ds != nullptr;
+        if (ds) h->ss.pend_ds = *ds;
     }
-    memcpy(h->pend_pose + 12 * h->pend_n, pose, 12 * sizeof(double));
-    h->pend_n++;
-    h->dirty = true;  // state_changed = true, grid.hpp:189 (the frame is accepted; its kernels follow)
-    bool launch = h->pend_n >= (uint32_t)std::max(1, h->host_batch) || h->fslot_next == 0;  // batch full, or the ring wraps next
+    memcpy(h->ss.pend_pose + 12 * h->ss.pend_n, pose, 12 * sizeof(double));
+    h->ss.pend_n++;
+    h->ss.dirty = true;  // state_changed = true, grid.hpp:189 (the frame is accepted; its kernels follow)
+    bool launch = h->ss.pend_n >= (uint32_t)std::max(1, h->knobs.host_batch) || h->fslot_next == 0;  // batch full, or the ring wraps next
     if (!launch) {
         if (!h->busy_pending) {
             launch = true;
@@ -2019,7 +2051,7 @@ int hfpf_is_dirty(hfpf_handle* h)
 {
     if (!h) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
-    return h->dirty ? 1 : 0;
+    return h->ss.dirty ? 1 : 0;
 }
 
 int hfpf_clean(hfpf_handle* h)
@@ -2035,21 +2067,10 @@ int hfpf_clean(hfpf_handle* h)
     if (!pre) pre = check_usable(h);
     if (pre && !h->dist_on) return pre;
     if (!h->timing || pre) return poison_on_error(h, clean_locked(h, pre));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto get = [&](hipEvent_t& e) -> hipError_t {
-        if (!h->ev_free.empty()) {
-            e = h->ev_free.back();
-            h->ev_free.pop_back();
-            return hipSuccess;
-        }
-        return hipEventCreate(&e);
-    };
-    HIPCHK(h, get(e0));
-    HIPCHK(h, get(e1));
-    HIPCHK(h, hipEventRecord(e0, h->stream));  // after every queued integrate: measures the clean pass alone
+    std::pair<hipEvent_t, hipEvent_t> timed;
+    if (int rc = timed_begin(h, &timed)) return rc;  // after every queued integrate: measures the clean pass alone
     const int rc = poison_on_error(h, clean_locked(h, 0));
-    HIPCHK(h, hipEventRecord(e1, h->stream));
-    h->ev_pending_clean.emplace_back(e0, e1);
+    if (int rc1 = timed_end(h, timed, h->ev_pending_clean)) return rc1;
     return rc;
 }
 
@@ -2160,12 +2181,7 @@ int hfpf_extract_filtered(hfpf_handle* h, const hfpf_extract_opts* opts, hfpf_ro
     *n_rows = 0;
     Tables& t = h->t;
     // (as in hfpf_clean: a local failure in front of the collective travels through the status gather, it does not skip it)
-    int rc = HFPF_OK;
-    if (hipError_t e_ = hipSetDevice(h->cfg.device)) rc = fail(h, HFPF_ERR_HIP, "hipSetDevice failed: %s", hipGetErrorString(e_));
-    if (!rc) rc = poison_on_error(h, flush_pending_locked(h));  // host frames still waiting for their launch
-    if (!rc) rc = check_usable(h);
-    if (!rc) rc = read_counters(h);
-    if (!rc) rc = poison_on_error(h, check_device_errors(h));
+    int rc = read_prologue_locked(h);
     if (rc && !h->dist_on) return rc;
     const unsigned long long* stats = t.stats;
     if (h->dist_on) {
@@ -2222,16 +2238,11 @@ static bool render_opts_ok(const hfpf_render_opts* o, const hfpf_render_planes* 
     return view_opts_ok(o) && pl && (pl->depth || pl->normal || pl->rgb || pl->count || pl->voxel);
 }
 
-// What extract does in front of its row set (single GPU): launch waiting host frames, refuse a failed handle, read the counters.
-static int render_prelude_locked(hfpf_handle* h, const char* what = "render")
+// The read prologue of the calls that work on one GPU's model only.
+static int local_read_prologue_locked(hfpf_handle* h, const char* what = "render")
 {
-    HIPCHK(h, hipSetDevice(h->cfg.device));
     if (h->dist_on) return fail(h, HFPF_ERR_STATE, "%s: not available on a handle with an RCCL communicator (hfpf_dist_disable drops it)", what);
-    int rc = poison_on_error(h, flush_pending_locked(h));  // host frames still waiting for their launch
-    if (!rc) rc = check_usable(h);
-    if (!rc) rc = read_counters(h);
-    if (!rc) rc = poison_on_error(h, check_device_errors(h));
-    return rc;
+    return read_prologue_locked(h);
 }
 
 // The views of a render (or the model view of a track): the row set, the z-buffer scratch of one chunk of views, the poses on the
@@ -2312,7 +2323,7 @@ int hfpf_render_device(hfpf_handle* h, const hfpf_render_opts* o, uint32_t n_vie
     if (!render_opts_ok(o, dev_out)) return fail(h, HFPF_ERR_BAD_ARG, "render: invalid options or planes");
     if (n_views == 0) return HFPF_OK;
     if (!poses) return fail(h, HFPF_ERR_BAD_ARG, "render: NULL poses");
-    if (int rc = render_prelude_locked(h)) return rc;
+    if (int rc = local_read_prologue_locked(h)) return rc;
     return render_locked(h, o, n_views, poses, *dev_out);
 }
 
@@ -2321,7 +2332,7 @@ int hfpf_render(hfpf_handle* h, const hfpf_render_opts* o, const double pose_3x4
     if (!h) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
     if (!render_opts_ok(o, host_out) || !pose_3x4) return fail(h, HFPF_ERR_BAD_ARG, "render: invalid options, pose or planes");
-    if (int rc = render_prelude_locked(h)) return rc;
+    if (int rc = local_read_prologue_locked(h)) return rc;
     // device planes, each 256-byte aligned, in one scratch buffer; then one download per requested plane
     const uint64_t WH = (uint64_t)o->width * o->height;
     void* host[5] = {host_out->depth, host_out->normal, host_out->rgb, host_out->count, host_out->voxel};
@@ -2480,7 +2491,7 @@ static int track_locked(hfpf_handle* h, const hfpf_track_opts* o, const PointSou
     const uint64_t n_samples = f.depth ? (uint64_t)cols * ((f.ds.height + stride - 1) / stride) : ((uint64_t)f.n + stride - 1) / stride;
     if (n_samples > (1ull << 26)) return fail(h, HFPF_ERR_BAD_ARG, "track: more than 2^26 sampled points");
     int rc;
-    if ((rc = render_prelude_locked(h, "track"))) return rc;
+    if ((rc = local_read_prologue_locked(h, "track"))) return rc;
     const uint8_t* frame = (const uint8_t*)f.dev;
     if (f.host) {  // one copy per call, through the pinned buffers
         if ((rc = scratch(h, h->track_in, f.bytes(f.n)))) return rc;
@@ -2621,7 +2632,7 @@ static bool query_args_ok(const hfpf_query_opts* o, const double* pose)
 static int query_locked(hfpf_handle* h, const hfpf_query_opts* o, const PointSource& f, const double pose[12], hfpf_query_hit* hits, hfpf_row* rows)
 {
     int rc;
-    if ((rc = render_prelude_locked(h, "query"))) return rc;
+    if ((rc = local_read_prologue_locked(h, "query"))) return rc;
     if (f.n == 0) return HFPF_OK;
     QueryParams p{};
     memcpy(p.T, pose, sizeof p.T);
@@ -2777,32 +2788,6 @@ static int ray_setup_locked(hfpf_handle* h, const hfpf_raycast_opts* o, uint32_t
     return HFPF_OK;
 }
 
-// One march launch on the engine's stream, bracketed by an event pair when kernel timing is on (hfpf_get_kernel_time id 5).
-static int ray_launch_locked(hfpf_handle* h, const std::function<void()>& launch)
-{
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->timing) {
-        auto get = [&](hipEvent_t& e) -> hipError_t {
-            if (!h->ev_free.empty()) {
-                e = h->ev_free.back();
-                h->ev_free.pop_back();
-                return hipSuccess;
-            }
-            return hipEventCreate(&e);
-        };
-        HIPCHK(h, get(e0));
-        HIPCHK(h, get(e1));
-        HIPCHK(h, hipEventRecord(e0, h->stream));
-    }
-    launch();
-    HIPCHK(h, hipGetLastError());
-    if (h->timing) {
-        HIPCHK(h, hipEventRecord(e1, h->stream));
-        h->ev_pending_ray.emplace_back(e0, e1);
-    }
-    return HFPF_OK;
-}
-
 static int raycast_common(hfpf_handle* h, const hfpf_raycast_opts* o, const hfpf_ray* rays, bool on_device, uint64_t n_rays, const double pose[12],
                           hfpf_ray_hit* hits)
 {
@@ -2814,14 +2799,14 @@ static int raycast_common(hfpf_handle* h, const hfpf_raycast_opts* o, const hfpf
     if (on_device && (((uintptr_t)rays & 3) || ((uintptr_t)hits & 15)))
         return fail(h, HFPF_ERR_BAD_ARG, "raycast_device: rays must be 4-byte and hits 16-byte aligned");
     int rc;
-    if ((rc = render_prelude_locked(h, "raycast"))) return rc;
+    if ((rc = local_read_prologue_locked(h, "raycast"))) return rc;
     if (n_rays == 0) return HFPF_OK;
     RayParams p;
     if ((rc = ray_setup_locked(h, o, n_samples, &p))) return rc;
     memcpy(p.T, pose, sizeof p.T);
     auto launch = [&](const hfpf_ray* dr, uint64_t n, hfpf_ray_hit* dh) -> int {
         p.n_rays = n;
-        return ray_launch_locked(h, [&] {
+        return timed_launch(h, h->ev_pending_ray, [&] {
             hipLaunchKernelGGL(k_raycast, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->g, h->t, p, (const float*)dr, (RayHit*)dh);
         });
     };
@@ -2871,7 +2856,7 @@ static int raycast_view_common(hfpf_handle* h, const hfpf_raycast_opts* o, uint3
     if (!hits) return fail(h, HFPF_ERR_BAD_ARG, "raycast: null hits");
     if (on_device && ((uintptr_t)hits & 15)) return fail(h, HFPF_ERR_BAD_ARG, "raycast_view_device: hits must be 16-byte aligned");
     int rc;
-    if ((rc = render_prelude_locked(h, "raycast"))) return rc;
+    if ((rc = local_read_prologue_locked(h, "raycast"))) return rc;
     if (n_views == 0) return HFPF_OK;
     RayParams p;
     if ((rc = ray_setup_locked(h, o, n_samples, &p))) return rc;
@@ -2885,7 +2870,7 @@ static int raycast_view_common(hfpf_handle* h, const hfpf_raycast_opts* o, uint3
         p.row0 = row0;
         p.rows = rows;
         const uint64_t tiles = tiles_x * ((rows + 7ull) / 8);
-        return ray_launch_locked(h, [&] {
+        return timed_launch(h, h->ev_pending_ray, [&] {
             hipLaunchKernelGGL(k_raycast_view, dim3(blocks_for(tiles * 64, 256), nv), dim3(256), 0, h->stream, h->g, h->t, p,
                                (const double*)h->render_pose.p + 12ull * v0, dh);
         });
@@ -2981,7 +2966,7 @@ static int mesh_locked(hfpf_handle* h, const hfpf_mesh_opts* o, bool on_device, 
 {
     *verts = nullptr, *tris = nullptr, *n_verts = 0, *n_tris = 0;
     int rc;
-    if ((rc = render_prelude_locked(h, "mesh"))) return rc;
+    if ((rc = local_read_prologue_locked(h, "mesh"))) return rc;
     for (int a = 0; a < 3; a++)
         if (h->g.dim[a] >= (1 << kMeshKeyBits) - 1) return fail(h, HFPF_ERR_CAPACITY, "mesh: a grid dimension of 2^21 - 1 cells or more");
     uint64_t nr = 0;
@@ -3153,7 +3138,7 @@ int hfpf_epoch_import(hfpf_handle* h, const void* dev_records, uint64_t n_record
     int rc = epoch_import_locked(h, dev_records, n_records);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller may reuse / free the record buffer
-    h->dirty = true;
+    h->ss.dirty = true;
     return HFPF_OK;
 }
 
@@ -3169,7 +3154,7 @@ int hfpf_epoch_import_gathered(hfpf_handle* h, const void* dev_buffer, uint64_t 
     int rc = import_gathered_locked(h, dev_buffer, slice_stride_bytes, world, my_rank, c.data());
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller may reuse / free the buffer
-    h->dirty = true;
+    h->ss.dirty = true;
     return HFPF_OK;
 }
 
@@ -3421,7 +3406,7 @@ int hfpf_write_pcd_binary(const hfpf_row* rows, uint64_t n, const char* path)
 // hfpf_clear under the handle's lock (hfpf_restore begins with it).
 static int clear_locked(hfpf_handle* h)
 {
-    h->pend_n = 0;  // host frames still waiting for their launch would be wiped with the rest
+    h->ss.pend_n = 0;  // host frames still waiting for their launch would be wiped with the rest
     // how far the session got (the counters as the device has them now); a handle whose stream has failed is reset in full
     uint64_t bricks_used = ~0ull, normals_used = ~0ull;
     if (read_counters(h) == HFPF_OK) {
@@ -3429,7 +3414,7 @@ static int clear_locked(hfpf_handle* h)
         normals_used = h->h_ctr[C_NORMALS];
     }
     int rc = reset_state(h, bricks_used, normals_used);
-    h->dirty = true;  // clearVoxels sets state_changed, grid.hpp:169
+    h->ss.dirty = true;  // clearVoxels sets state_changed, grid.hpp:169
     return rc;
 }
 
@@ -3713,16 +3698,40 @@ SnapLimits snap_limits(const hfpf_handle* h, const SnapUsed& u)
     return lim;
 }
 
+// The host state a snapshot carries, into the header and back: ONE field list, the same order in both.  Everything else in Session
+// is re-created after a restore or needs not be (see the notes there); frames_integrated and clean_passes travel too because a
+// clear leaves them alone.
+void session_to_header(const hfpf_handle* h, const SnapUsed& u, SnapHeader* hd)
+{
+    const Session& ss = h->ss;
+    hd->frames_integrated = h->frames_integrated;
+    hd->clean_passes = h->clean_passes;
+    hd->next_frame_id = ss.next_frame_id;
+    hd->dirty = ss.dirty ? 1 : 0;
+    hd->pend_valid = ss.pend_valid ? 1 : 0;
+    hd->normals_possible = ss.normals_possible ? 1 : 0;
+    hd->gate_done = ss.gate_done;
+    hd->direct_linked = ss.direct_linked;
+    for (int r = 0; r < kLogRegions; r++) hd->n_linked[r] = std::min(ss.n_linked[r], u.log_n[r]);
+}
+void header_to_session(const SnapHeader& hd, hfpf_handle* h)
+{
+    Session& ss = h->ss;
+    h->frames_integrated = hd.frames_integrated;
+    h->clean_passes = hd.clean_passes;
+    ss.next_frame_id = (uint32_t)hd.next_frame_id;
+    ss.dirty = hd.dirty != 0;
+    ss.pend_valid = hd.pend_valid != 0;
+    ss.normals_possible = hd.normals_possible != 0;
+    ss.gate_done = hd.gate_done;
+    ss.direct_linked = hd.direct_linked;
+    for (int r = 0; r < kLogRegions; r++) ss.n_linked[r] = hd.n_linked[r];
+}
+
 int snapshot_locked(hfpf_handle* h, void** blob_out, uint64_t* bytes_out)
 {
-    HIPCHK(h, hipSetDevice(h->cfg.device));
     int rc = snap_refuse_distributed(h, "snapshot");
-    if (rc) return rc;
-    // as extract: launch what waits, refuse a failed handle, read the counters (which waits for a clean pass still running)
-    rc = poison_on_error(h, flush_pending_locked(h));
-    if (!rc) rc = check_usable(h);
-    if (!rc) rc = read_counters(h);
-    if (!rc) rc = poison_on_error(h, check_device_errors(h));
+    if (!rc) rc = read_prologue_locked(h);  // (the counter read-back waits for a clean pass still running)
     if (rc) return rc;
     const Tables& t = h->t;
     const hfpf_config& c = h->cfg;
@@ -3734,7 +3743,7 @@ int snapshot_locked(hfpf_handle* h, void** blob_out, uint64_t* bytes_out)
     u.n_prereg = std::min<uint64_t>(h->h_ctr[C_PREREG], t.max_reg);
     u.n_dep = std::min<uint64_t>(h->h_ctr[C_DEP], t.max_dep);
     u.n_frames = std::min<uint64_t>(h->h_ctr[C_FRAMES], t.max_frames);
-    u.n_pend = h->pend_valid ? h->h_ctr[C_PEND] : 0;
+    u.n_pend = h->ss.pend_valid ? h->h_ctr[C_PEND] : 0;
     if (u.n_pend * 4 > h->pend_a.bytes) return fail(h, HFPF_ERR_STATE, "snapshot: pending-cell list of %llu entries exceeds its buffer (internal)", (unsigned long long)u.n_pend);
     for (int r = 0; r < kLogRegions; r++) u.log_n[r] = std::min<uint64_t>(h->h_log_ctr[r * 16], t.log_region_cap);
 
@@ -3764,19 +3773,12 @@ int snapshot_locked(hfpf_handle* h, void** blob_out, uint64_t* bytes_out)
     hd.need_bricks = std::max<uint64_t>(u.n_bricks, 1);
     hd.log_points = c.max_log_points;
     hd.need_frames = 1;  // raised below to the largest frame id + 1
-    hd.frames_integrated = h->frames_integrated;
-    hd.clean_passes = h->clean_passes;
-    hd.next_frame_id = h->next_frame_id;
     hd.voxels_occupied = h->h_ctr[C_OCC];
     hd.voxels_with_normal = h->h_ctr[C_NORMALS];
-    hd.dirty = h->dirty ? 1 : 0;
-    hd.pend_valid = h->pend_valid ? 1 : 0;
-    hd.normals_possible = h->normals_possible ? 1 : 0;
-    hd.gate_done = h->gate_done;
-    hd.direct_linked = h->direct_linked;
     hd.n_bricks = u.n_bricks, hd.n_normals = u.n_normals, hd.n_occ = u.n_occ, hd.n_reg = u.n_reg, hd.n_prereg = u.n_prereg, hd.n_dep = u.n_dep;
     hd.n_frames = u.n_frames, hd.n_pend = u.n_pend;
-    for (int r = 0; r < kLogRegions; r++) hd.n_linked[r] = std::min(h->n_linked[r], u.log_n[r]), hd.log_n[r] = u.log_n[r];
+    for (int r = 0; r < kLogRegions; r++) hd.log_n[r] = u.log_n[r];
+    session_to_header(h, u, &hd);
 
     uint64_t window = 0;
     if ((rc = snap_stage_alloc(h, hd.payload_bytes, &window))) return rc;
@@ -3881,7 +3883,7 @@ int restore_locked(hfpf_handle* h, const void* blob, uint64_t bytes)
         const std::string msg = h->err;
         (void)hipStreamSynchronize(h->stream);
         (void)reset_state(h);  // in full: what was uploaded is not to be trusted
-        h->dirty = true;
+        h->ss.dirty = true;
         h->err = msg;
         return code;
     };
@@ -3914,18 +3916,9 @@ int restore_locked(hfpf_handle* h, const void* blob, uint64_t bytes)
     if (hipMemcpyAsync(&err_word, h->snap_err.p, 4, hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
         return bail(fail(h, HFPF_ERR_HIP, "restore: reading the range check's result failed"));
     if (err_word) return bail(fail(h, HFPF_ERR_IO, "restore: the snapshot's tables hold indices outside their pools (range check bits 0x%x); the handle has been cleared", err_word));
-    // ---- host mirrors ----
-    h->dirty = hd.dirty != 0;
-    h->pend_valid = hd.pend_valid != 0;
-    h->normals_possible = hd.normals_possible != 0;
-    h->gate_done = hd.gate_done;
-    h->direct_linked = hd.direct_linked;
-    h->frames_integrated = hd.frames_integrated;
-    h->clean_passes = hd.clean_passes;
-    h->next_frame_id = (uint32_t)hd.next_frame_id;
-    for (int r = 0; r < kLogRegions; r++) h->n_linked[r] = hd.n_linked[r];
+    header_to_session(hd, h);
     if ((rc = read_counters(h))) return bail(rc);  // h_ctr, h_log_ctr, n_bricks_known from the restored device counters
-    h->n_bricks_before = h->n_bricks_known;
+    h->ss.n_bricks_before = h->ss.n_bricks_known;
     if (h->binned) {
         // Entries the source's direct form appended since its last clean are still unchained; the binned form never runs
         // k_link_log at a clean pass (its own appends arrive chained), so they are chained here.
@@ -3933,15 +3926,15 @@ int restore_locked(hfpf_handle* h, const void* blob, uint64_t bytes)
         uint64_t max_new = 0;
         for (int r = 0; r < kLogRegions; r++) {
             const uint64_t base = (uint64_t)r * t.log_region_cap;
-            lr.first[r] = (uint32_t)(base + h->n_linked[r] + 1);
+            lr.first[r] = (uint32_t)(base + h->ss.n_linked[r] + 1);
             lr.last[r] = (uint32_t)(base + u.log_n[r]);
-            max_new = std::max(max_new, u.log_n[r] - h->n_linked[r]);
+            max_new = std::max(max_new, u.log_n[r] - h->ss.n_linked[r]);
         }
         if (max_new && (hd.flags & HFPF_FLAG_DIRECT_UPDATE)) {
             hipLaunchKernelGGL(k_link_log, dim3(blocks_for(max_new, 256), kLogRegions), dim3(256), 0, h->stream, h->t, lr);
             if (hipGetLastError() != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore: k_link_log launch failed"));
-            for (int r = 0; r < kLogRegions; r++) h->n_linked[r] = u.log_n[r];
-            h->direct_linked = h->h_ctr[C_BUFFERED];
+            for (int r = 0; r < kLogRegions; r++) h->ss.n_linked[r] = u.log_n[r];
+            h->ss.direct_linked = h->h_ctr[C_BUFFERED];
         }
     }
     return HFPF_OK;

@@ -18,6 +18,7 @@ if [ "$1" = "--rev" ]; then
 fi
 NAME=$1; shift
 mkdir -p $R/build/variants
-/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -fPIC -Wall -Wno-unused-function -Wno-unused-result "$@" \
-  -shared -o $R/build/variants/$NAME.so $SRC/hfpf.hip
+# the engine's flag line lives in csrc/Makefile (the working tree's, also for --rev)
+FLAGS=$(make -s --no-print-directory -C $R/high-fidelity-pointcloud-fusion_amd/csrc print-hipflags)
+/opt/rocm/bin/hipcc $FLAGS "$@" -shared -o $R/build/variants/$NAME.so $SRC/hfpf.hip
 echo "built build/variants/$NAME.so ($*)"
