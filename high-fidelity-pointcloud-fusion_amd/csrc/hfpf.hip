@@ -308,6 +308,9 @@ struct hfpf_handle {
     // hfpf_extract_mesh*: cube and corner keys, per corner s / record / marks / vertex counts and bases, per cube triangle counts and
     // bases, the host form's output, a unique count
     DevBuf mesh_cube, mesh_corner, mesh_kdata, mesh_cdata, mesh_out, mesh_ctr;
+    // hfpf_extract_components*: record -> row, the per-row words (parent, root, component, flags and bases), the component records and
+    // their keep flags, ranks and bases, the host form's output
+    DevBuf comp_index, comp_rows, comp_recs, comp_out;
     DevBuf ray_in, ray_out, ray_map;       // hfpf_raycast*: a host chunk's rays, a chunk's (or band's) hits, the empty-space maps
     DevBuf snap_stage, snap_err;           // hfpf_snapshot / hfpf_restore: the staging buffer (or one window of it), the range check's error word
     uint64_t bin_pool = 0;           // entries in bin_pt
@@ -333,6 +336,9 @@ struct hfpf_handle {
     EventPairs ev_pending_ray;  // one pair per k_raycast / k_raycast_view launch (id 5)
     double t_ray_ms = 0;
     uint64_t n_ray_timed = 0;
+    EventPairs ev_pending_comp;  // one pair per hfpf_extract_components* call (id 6)
+    double t_comp_ms = 0;
+    uint64_t n_comp_timed = 0;
     double t_clean_ms = 0;
     uint64_t n_clean_timed = 0;
     std::vector<hipEvent_t> ev_free;
@@ -773,9 +779,9 @@ int sort_keys_u32(hfpf_handle* h, uint32_t* in, uint32_t* out, uint64_t n, unsig
     return HFPF_OK;
 }
 
-int sort_pairs_u64(hfpf_handle* h, uint64_t* kin, uint64_t* kout, uint32_t* vin, uint32_t* vout, uint64_t n)
+int sort_pairs_u64(hfpf_handle* h, uint64_t* kin, uint64_t* kout, uint32_t* vin, uint32_t* vout, uint64_t n, unsigned bits = 0)
 {
-    const unsigned kb = h->g.key_bits;
+    const unsigned kb = bits ? bits : h->g.key_bits;
     size_t bytes = 0;
     HIPCHK(h, rocprim::radix_sort_pairs<sort_config>(nullptr, bytes, kin, kout, vin, vout, (size_t)n, 0, kb, h->stream));
     int rc = scratch(h, h->sort_tmp, bytes);
@@ -1130,7 +1136,7 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
 
 int resolve_timing(hfpf_handle* h)
 {
-    if (h->ev_pending.empty() && h->ev_pending_clean.empty() && h->ev_pending_ray.empty() && h->ev_detail.empty()) return HFPF_OK;
+    if (h->ev_pending.empty() && h->ev_pending_clean.empty() && h->ev_pending_ray.empty() && h->ev_pending_comp.empty() && h->ev_detail.empty()) return HFPF_OK;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     auto settle = [&](EventPairs& list, double& total_ms, uint64_t& n) -> int {
         for (auto& pr : list) {
@@ -1146,6 +1152,7 @@ int resolve_timing(hfpf_handle* h)
     };
     int rc;
     if ((rc = settle(h->ev_pending_ray, h->t_ray_ms, h->n_ray_timed))) return rc;
+    if ((rc = settle(h->ev_pending_comp, h->t_comp_ms, h->n_comp_timed))) return rc;
     if ((rc = settle(h->ev_pending_clean, h->t_clean_ms, h->n_clean_timed))) return rc;
     if ((rc = settle(h->ev_pending, h->t_integrate_ms, h->n_integrate_launches))) return rc;
     for (size_t c = 0; 4 * c + 3 < h->ev_detail.size() && c < h->ev_detail_ran.size(); c++) {
@@ -1658,7 +1665,7 @@ int hfpf_destroy(hfpf_handle* h)
     for (DevBuf* b : {&h->sort_tmp, &h->keys_a, &h->keys_b, &h->vals_a, &h->vals_b, &h->rows_dev, &h->probe_a, &h->probe_b, &h->probe_c, &h->probe_d,
                       &h->probe_e, &h->probe_f, &h->zbuf, &h->render_pose, &h->render_out, &h->track_in, &h->track_acc,
                       &h->query_in, &h->query_out, &h->mesh_cube, &h->mesh_corner, &h->mesh_kdata, &h->mesh_cdata, &h->mesh_out,
-                      &h->mesh_ctr, &h->ray_in, &h->ray_out, &h->ray_map, &h->snap_stage, &h->snap_err})
+                      &h->mesh_ctr, &h->comp_index, &h->comp_rows, &h->comp_recs, &h->comp_out, &h->ray_in, &h->ray_out, &h->ray_map, &h->snap_stage, &h->snap_err})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf* b : {&h->ex_send, &h->ex_recv, &h->ex_counts, &h->stats_total, &h->bin_pt_buf, &h->bin_rgb_buf, &h->bin_sums, &h->ovf_pt_buf, &h->ovf_aux_buf, &h->pend_a, &h->pend_b})
         if (b->p) (void)hipFree(b->p);
@@ -1700,6 +1707,10 @@ int hfpf_destroy(hfpf_handle* h)
         (void)hipEventDestroy(pr.second);
     }
     for (auto& pr : h->ev_pending_ray) {
+        (void)hipEventDestroy(pr.first);
+        (void)hipEventDestroy(pr.second);
+    }
+    for (auto& pr : h->ev_pending_comp) {
         (void)hipEventDestroy(pr.first);
         (void)hipEventDestroy(pr.second);
     }
@@ -3093,6 +3104,175 @@ void hfpf_free_mesh(hfpf_mesh_vertex* verts, uint32_t* tris)
     free(tris);
 }
 
+// ---- connected components (include/hfpf.h) --------------------------------------------------------------------------------
+int hfpf_check_component_opts(const hfpf_component_opts* o)
+{
+    if (!o || o->struct_size != sizeof(hfpf_component_opts) || o->flags != 0 || o->reserved0 != 0 || o->reserved != 0) return HFPF_ERR_BAD_ARG;
+    if (o->reach < 1 || o->reach > kQueryMaxRadius || std::isnan(o->min_count)) return HFPF_ERR_BAD_ARG;
+    return std::isfinite(o->min_normal_dot) && o->min_normal_dot >= -2.0 && o->min_normal_dot <= 1.0 ? HFPF_OK : HFPF_ERR_BAD_ARG;
+}
+
+struct CompOut {  // device arrays: new allocations for the device form, slices of h->comp_out for the host form
+    Row* rows = nullptr;
+    uint32_t* labels = nullptr;
+    Component* comps = nullptr;
+    uint64_t n_rows = 0, n_comps = 0;
+};
+
+// Validated arguments in, under the lock.  The row set, then (timed as kernel id 6) index, link, flatten, the scan of the root flags,
+// the per-component reductions, the keep flags (through a sort for keep_largest), the scans of kept components and kept rows, and
+// the compaction.  The read-backs are the sizes between the stages.
+static int components_locked(hfpf_handle* h, const hfpf_component_opts* o, bool on_device, bool want_rows, CompOut* out)
+{
+    *out = CompOut{};
+    int rc;
+    if ((rc = local_read_prologue_locked(h, "components"))) return rc;
+    uint64_t nr = 0;
+    const ExtractOpts opt{o->min_count, -1, 0};  // the compare of hfpf_extract_filtered, 0 keeps all
+    if ((rc = build_rows_locked(h, h->t.stats, opt, &nr))) return rc;
+    if (nr == 0) return HFPF_OK;
+    if (nr >= 0xFFFFFFFFull) return fail(h, HFPF_ERR_CAPACITY, "components: %llu rows exceed the 32-bit row index", (unsigned long long)nr);
+    const uint64_t n_rec = h->h_ctr[C_NORMALS];
+    const uint32_t n = (uint32_t)nr;
+    const uint64_t R1 = nr + 1;
+    if ((rc = scratch(h, h->comp_index, (n_rec + 1) * 4))) return rc;
+    if ((rc = scratch(h, h->comp_rows, R1 * 24))) return rc;
+    uint32_t* row_of = (uint32_t*)h->comp_index.p;
+    uint32_t* parent = (uint32_t*)h->comp_rows.p;  // (each of the six arrays has nr + 1 entries)
+    uint32_t* root = parent + R1;
+    uint32_t* comp_of = root + R1;
+    uint32_t* flag = comp_of + R1;   // root flags, later the rows' keep flags
+    uint32_t* cbase = flag + R1;     // scan of the root flags
+    uint32_t* rbase = cbase + R1;    // scan of the rows' keep flags
+    const Row* rows = (const Row*)h->rows_dev.p;
+    const CompParams p{o->min_normal_dot, o->min_points, o->min_rows, o->keep_largest, o->reach};
+    const dim3 grid_r(blocks_for(nr, 256)), grid_r1(blocks_for(R1, 256));
+    std::pair<hipEvent_t, hipEvent_t> timed;
+    if ((rc = timed_begin(h, &timed))) return rc;
+    HIPCHK(h, hipMemsetAsync(row_of, 0xFF, (n_rec + 1) * 4, h->stream));
+    hipLaunchKernelGGL(k_comp_index, grid_r, dim3(256), 0, h->stream, (const uint32_t*)h->vals_b.p, n, row_of, parent);
+    hipLaunchKernelGGL(k_comp_link, grid_r, dim3(256), 0, h->stream, h->g, h->t, p, rows, n, (const uint32_t*)row_of, (uint32_t)n_rec, parent);
+    hipLaunchKernelGGL(k_comp_flatten, grid_r1, dim3(256), 0, h->stream, (const uint32_t*)parent, n, root, flag);
+    HIPCHK(h, hipGetLastError());
+    uint64_t nc = 0;
+    if ((rc = mesh_scan_locked(h, flag, cbase, nr, &nc))) return rc;
+    const uint64_t C1 = nc + 1;
+    if ((rc = scratch(h, h->comp_recs, nc * sizeof(Component) + C1 * 8))) return rc;
+    Component* recs = (Component*)h->comp_recs.p;
+    uint32_t* keep = (uint32_t*)(recs + nc);
+    uint32_t* kbase = keep + C1;
+    const dim3 grid_c1(blocks_for(C1, 256));
+    hipLaunchKernelGGL(k_comp_init, grid_r, dim3(256), 0, h->stream, (const uint32_t*)root, (const uint32_t*)cbase, n, comp_of, recs);
+    hipLaunchKernelGGL(k_comp_reduce, grid_r, dim3(256), 0, h->stream, rows, (const uint32_t*)comp_of, n, recs);
+    if (o->keep_largest == 0) {
+        hipLaunchKernelGGL(k_comp_keep, grid_c1, dim3(256), 0, h->stream, (const Component*)recs, (uint32_t)nc, p, keep);
+        HIPCHK(h, hipGetLastError());
+    } else {  // the row set's sort buffers are free again: k_comp_index has read vals_b, and nc <= nr
+        hipLaunchKernelGGL(k_comp_rank_keys, grid_c1, dim3(256), 0, h->stream, (const Component*)recs, (uint32_t)nc, p, (uint64_t*)h->keys_a.p,
+                           (uint32_t*)h->vals_a.p, keep);
+        HIPCHK(h, hipGetLastError());
+        if ((rc = sort_pairs_u64(h, (uint64_t*)h->keys_a.p, (uint64_t*)h->keys_b.p, (uint32_t*)h->vals_a.p, (uint32_t*)h->vals_b.p, nc, 64))) return rc;
+        const uint32_t front = (uint32_t)std::min<uint64_t>(nc, o->keep_largest);
+        hipLaunchKernelGGL(k_comp_rank_keep, dim3(blocks_for(front, 256)), dim3(256), 0, h->stream, (const uint64_t*)h->keys_b.p,
+                           (const uint32_t*)h->vals_b.p, front, keep);
+        HIPCHK(h, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_comp_row_keep, grid_r1, dim3(256), 0, h->stream, (const uint32_t*)comp_of, (const uint32_t*)keep, n, flag);
+    HIPCHK(h, hipGetLastError());
+    uint64_t nk = 0, nkr = 0;
+    if ((rc = mesh_scan_locked(h, keep, kbase, nc, &nk))) return rc;
+    if ((rc = mesh_scan_locked(h, flag, rbase, nr, &nkr))) return rc;
+    if (nk == 0) return timed_end(h, timed, h->ev_pending_comp);
+    CompOut d;
+    d.n_rows = nkr, d.n_comps = nk;
+    const size_t row_bytes = want_rows ? nkr * sizeof(Row) : 0, label_bytes = (nkr * 4 + 15) & ~(size_t)15;
+    void* owned[3] = {nullptr, nullptr, nullptr};
+    if (on_device) {
+        hipError_t e = want_rows ? hipMalloc(&owned[0], row_bytes) : hipSuccess;
+        if (e == hipSuccess) e = hipMalloc(&owned[1], nkr * 4);
+        if (e == hipSuccess) e = hipMalloc(&owned[2], nk * sizeof(Component));
+        if (e != hipSuccess) {
+            for (void* q : owned) (void)hipFree(q);
+            return fail(h, HFPF_ERR_HIP, "components: device allocation of %llu rows / %llu components failed: %s", (unsigned long long)nkr,
+                        (unsigned long long)nk, hipGetErrorString(e));
+        }
+        d.rows = (Row*)owned[0], d.labels = (uint32_t*)owned[1], d.comps = (Component*)owned[2];
+    } else {
+        if ((rc = scratch(h, h->comp_out, row_bytes + label_bytes + nk * sizeof(Component)))) return rc;
+        char* base = (char*)h->comp_out.p;
+        d.rows = want_rows ? (Row*)base : nullptr;
+        d.labels = (uint32_t*)(base + row_bytes);
+        d.comps = (Component*)(base + row_bytes + label_bytes);
+    }
+    hipLaunchKernelGGL(k_comp_compact, grid_r, dim3(256), 0, h->stream, rows, n, (const uint32_t*)comp_of, (const uint32_t*)keep, (const uint32_t*)kbase,
+                       (const uint32_t*)rbase, (const Component*)recs, d.rows, d.labels, d.comps);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) rc = timed_end(h, timed, h->ev_pending_comp);
+    if (e == hipSuccess && !rc) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess || rc) {
+        for (void* q : owned) (void)hipFree(q);
+        return rc ? rc : fail(h, HFPF_ERR_HIP, "components: %s", hipGetErrorString(e));
+    }
+    *out = d;
+    return HFPF_OK;
+}
+
+static bool component_args_ok(const hfpf_component_opts* o, const void* labels, const void* n_rows, const void* comps, const void* n_comps)
+{
+    return hfpf_check_component_opts(o) == HFPF_OK && labels && n_rows && comps && n_comps;
+}
+
+int hfpf_extract_components_device(hfpf_handle* h, const hfpf_component_opts* o, hfpf_row** dev_rows, uint32_t** dev_labels, uint64_t* n_rows,
+                                   hfpf_component** dev_comps, uint64_t* n_comps)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (!component_args_ok(o, dev_labels, n_rows, dev_comps, n_comps)) return fail(h, HFPF_ERR_BAD_ARG, "components: invalid options or a NULL output");
+    CompOut d;
+    const int rc = components_locked(h, o, true, dev_rows != nullptr, &d);
+    if (dev_rows) *dev_rows = (hfpf_row*)d.rows;
+    *dev_labels = d.labels, *dev_comps = (hfpf_component*)d.comps, *n_rows = d.n_rows, *n_comps = d.n_comps;
+    return rc;
+}
+
+int hfpf_extract_components(hfpf_handle* h, const hfpf_component_opts* o, hfpf_row** rows, uint32_t** labels, uint64_t* n_rows, hfpf_component** comps,
+                            uint64_t* n_comps)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (!component_args_ok(o, labels, n_rows, comps, n_comps)) return fail(h, HFPF_ERR_BAD_ARG, "components: invalid options or a NULL output");
+    if (rows) *rows = nullptr;
+    *labels = nullptr, *comps = nullptr, *n_rows = 0, *n_comps = 0;
+    CompOut d;
+    if (int rc = components_locked(h, o, false, rows != nullptr, &d)) return rc;
+    if (d.n_comps == 0) return HFPF_OK;
+    hfpf_row* hr = rows ? (hfpf_row*)host_result_alloc(d.n_rows * sizeof(hfpf_row)) : nullptr;
+    uint32_t* hl = (uint32_t*)host_result_alloc(d.n_rows * 4);
+    hfpf_component* hc = (hfpf_component*)host_result_alloc(d.n_comps * sizeof(hfpf_component));
+    if ((rows && !hr) || !hl || !hc) {
+        free(hr), free(hl), free(hc);
+        return fail(h, HFPF_ERR_CAPACITY, "components: host allocation of %llu rows / %llu components failed", (unsigned long long)d.n_rows,
+                    (unsigned long long)d.n_comps);
+    }
+    hipError_t e = rows ? download_pageable(h, hr, d.rows, d.n_rows * sizeof(hfpf_row)) : hipSuccess;
+    if (e == hipSuccess) e = download_pageable(h, hl, d.labels, d.n_rows * 4);
+    if (e == hipSuccess) e = download_pageable(h, hc, d.comps, d.n_comps * sizeof(hfpf_component));
+    if (e != hipSuccess) {
+        free(hr), free(hl), free(hc);
+        return fail(h, HFPF_ERR_HIP, "components copy: %s", hipGetErrorString(e));
+    }
+    if (rows) *rows = hr;
+    *labels = hl, *comps = hc, *n_rows = d.n_rows, *n_comps = d.n_comps;
+    return HFPF_OK;
+}
+
+void hfpf_free_components(hfpf_row* rows, uint32_t* labels, hfpf_component* comps)
+{
+    free(rows);
+    free(labels);
+    free(comps);
+}
+
 int hfpf_stats_export(hfpf_handle* h, const void** dev_words, uint64_t* n_words, const void** dev_cwords, uint64_t* n_cwords)
 {
     if (!h || !dev_words || !n_words) return HFPF_ERR_BAD_ARG;
@@ -4164,21 +4344,23 @@ int hfpf_kernel_timing(hfpf_handle* h, int enable)
         h->n_clean_timed = 0;
         h->t_ray_ms = 0;
         h->n_ray_timed = 0;
+        h->t_comp_ms = 0;
+        h->n_comp_timed = 0;
     }
     return HFPF_OK;
 }
 
 int hfpf_get_kernel_time(hfpf_handle* h, int kernel_id, double* total_ms, uint64_t* launches)
 {
-    if (!h || kernel_id < 0 || kernel_id > 5) return HFPF_ERR_BAD_ARG;
+    if (!h || kernel_id < 0 || kernel_id > 6) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (int rcf = flush_pending_locked(h)) return rcf;  // host frames still waiting for their launch
     int rc = resolve_timing(h);
     if (rc) return rc;
-    if (kernel_id == 5) {
-        if (total_ms) *total_ms = h->t_ray_ms;
-        if (launches) *launches = h->n_ray_timed;
+    if (kernel_id >= 5) {
+        if (total_ms) *total_ms = kernel_id == 5 ? h->t_ray_ms : h->t_comp_ms;
+        if (launches) *launches = kernel_id == 5 ? h->n_ray_timed : h->n_comp_timed;
         return HFPF_OK;
     }
     if (kernel_id >= 2) {

@@ -2438,6 +2438,35 @@ __device__ __forceinline__ uint64_t plane_window(int ya, int yb, int za, int zb)
     return ybytes & zbits;
 }
 
+// The enumeration every window walk shares (query, mesh, raycast samples, component links): the cells with a record inside the
+// box [lo, hi] (0 <= lo, hi <= dim - 1 per axis, at most two bricks an axis), brick by brick through the directory, per x-plane of a
+// touched brick the nd_mask normal_found word ANDed with the box's (y, z) mask.  visit(cx, cy, cz, nid) sees each of them once.
+template <typename Visit>
+__device__ __forceinline__ void window_walk(const GridParams& g, const Tables& t, const int lo[3], const int hi[3], Visit&& visit)
+{
+    if (!(lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2])) return;
+    for (int bx = lo[0] >> kBrickShift; bx <= hi[0] >> kBrickShift; bx++)
+        for (int by = lo[1] >> kBrickShift; by <= hi[1] >> kBrickShift; by++)
+            for (int bz = lo[2] >> kBrickShift; bz <= hi[2] >> kBrickShift; bz++) {
+                const uint32_t b = t.dir[((uint32_t)bx * (uint32_t)g.bdim[1] + (uint32_t)by) * (uint32_t)g.bdim[2] + (uint32_t)bz];
+                if (b == 0 || b == kLock) continue;  // untouched (kLock cannot happen between kernels)
+                const uint64_t wmask = plane_window(max(lo[1] - 8 * by, 0), min(hi[1] - 8 * by, 7), max(lo[2] - 8 * bz, 0),
+                                                    min(hi[2] - 8 * bz, 7));
+                const int x1 = min(hi[0], 8 * bx + 7);
+                for (int cx = max(lo[0], 8 * bx); cx <= x1; cx++) {
+                    uint64_t w = t.nd_mask[((uint64_t)b * 8u + (uint32_t)(cx & 7)) * 2] & wmask;
+                    while (w) {
+                        const int bitn = __builtin_ctzll(w);
+                        w &= w - 1;
+                        const int32_t cy = 8 * by + (bitn >> 3), cz = 8 * bz + (bitn & 7);
+                        const uint32_t nid = t.stat_id[b * kBrickCells + local_index(cx, cy, cz)];
+                        if (nid == 0) continue;
+                        visit(cx, cy, cz, nid);
+                    }
+                }
+            }
+}
+
 // The window walk of a query (and of a mesh's corner samples): the candidate rows of the (2 radius + 1)^3 cells around voxel v,
 // clipped to the valid cells 0..dim-1 (extract emits no other), and the winner among those within max_d2 of q.
 struct WindowNearest {
@@ -2461,44 +2490,25 @@ __device__ __forceinline__ WindowNearest window_nearest(const GridParams& g, con
         lo[a] = max(v[a] - radius, 0);
         hi[a] = min(v[a] + radius, g.dim[a] - 1);
     }
-    if (lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2]) {
-        for (int bx = lo[0] >> kBrickShift; bx <= hi[0] >> kBrickShift; bx++)
-            for (int by = lo[1] >> kBrickShift; by <= hi[1] >> kBrickShift; by++)
-                for (int bz = lo[2] >> kBrickShift; bz <= hi[2] >> kBrickShift; bz++) {
-                    const uint32_t b = t.dir[((uint32_t)bx * (uint32_t)g.bdim[1] + (uint32_t)by) * (uint32_t)g.bdim[2] + (uint32_t)bz];
-                    if (b == 0 || b == kLock) continue;  // untouched (kLock cannot happen between kernels)
-                    const uint64_t wmask = plane_window(max(lo[1] - 8 * by, 0), min(hi[1] - 8 * by, 7), max(lo[2] - 8 * bz, 0),
-                                                        min(hi[2] - 8 * bz, 7));
-                    const int x1 = min(hi[0], 8 * bx + 7);
-                    for (int cx = max(lo[0], 8 * bx); cx <= x1; cx++) {
-                        uint64_t w = t.nd_mask[((uint64_t)b * 8u + (uint32_t)(cx & 7)) * 2] & wmask;
-                        while (w) {
-                            const int bitn = __builtin_ctzll(w);
-                            w &= w - 1;
-                            const int32_t cy = 8 * by + (bitn >> 3), cz = 8 * bz + (bitn & 7);
-                            const uint32_t nid = t.stat_id[b * kBrickCells + local_index(cx, cy, cz)];
-                            if (nid == 0) continue;
-                            const long long* s = reinterpret_cast<const long long*>(&t.stats[(uint64_t)nid * kStatWords]);
-                            const long long cnt = s[SW_COUNT];
-                            if ((double)(int)cnt < min_count) continue;  // min_count >= 1: cnt > 0 below
-                            if (cx == v[0] && cy == v[1] && cz == v[2]) r.has_row = true;
-                            double em;
-                            float rx, ry, rz;
-                            record_centroid(g, t, s, nid, cnt, em, rx, ry, rz);
-                            const double dx = (double)q.x - (double)rx, dy = (double)q.y - (double)ry, dz = (double)q.z - (double)rz;
-                            const double d2 = (dx * dx + dy * dy) + dz * dz;
-                            if (!(d2 <= max_d2)) continue;
-                            const uint64_t key = make_key(g, cx, cy, cz);
-                            if (!r.found || d2 < r.d2 || (d2 == r.d2 && key < best_key)) {
-                                r.found = true;
-                                r.d2 = d2, best_key = key, r.nid = nid;
-                                r.dx = dx, r.dy = dy, r.dz = dz;
-                                r.wx = cx, r.wy = cy, r.wz = cz;
-                            }
-                        }
-                    }
-                }
-    }
+    window_walk(g, t, lo, hi, [&](const int32_t cx, const int32_t cy, const int32_t cz, const uint32_t nid) {
+        const long long* s = reinterpret_cast<const long long*>(&t.stats[(uint64_t)nid * kStatWords]);
+        const long long cnt = s[SW_COUNT];
+        if ((double)(int)cnt < min_count) return;  // min_count >= 1: cnt > 0 below
+        if (cx == v[0] && cy == v[1] && cz == v[2]) r.has_row = true;
+        double em;
+        float rx, ry, rz;
+        record_centroid(g, t, s, nid, cnt, em, rx, ry, rz);
+        const double dx = (double)q.x - (double)rx, dy = (double)q.y - (double)ry, dz = (double)q.z - (double)rz;
+        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        if (!(d2 <= max_d2)) return;
+        const uint64_t key = make_key(g, cx, cy, cz);
+        if (!r.found || d2 < r.d2 || (d2 == r.d2 && key < best_key)) {
+            r.found = true;
+            r.d2 = d2, best_key = key, r.nid = nid;
+            r.dx = dx, r.dy = dy, r.dz = dz;
+            r.wx = cx, r.wy = cy, r.wz = cz;
+        }
+    });
     return r;
 }
 
@@ -3118,6 +3128,229 @@ __global__ __launch_bounds__(256) void k_mesh_triangles(const uint64_t* __restri
             }
     }
 }
+
+// ---- connected components (hfpf_extract_components*, include/hfpf.h) -------------------------------------------------------
+// The rows are the extract row set of opts.min_count (k_extract_keys -> sort -> k_extract_rows), row j the j-th in lexicographic
+// order; row_of[] maps a record to its row.  k_comp_link unites every row with its adjacent rows of smaller index in a lock-free
+// union-find over parent[] (parent[x] <= x always: the smaller root wins, so a component's root is its smallest row whatever the
+// schedule), k_comp_flatten names every row's root, a scan over the root flags numbers the components by ascending representative,
+// k_comp_reduce sums them up with integer atomics, and after the keep decision two more scans compact rows, labels and records.
+constexpr uint32_t kCompNone = 0xFFFFFFFFu;
+
+struct __attribute__((aligned(8))) Component {  // = hfpf_component
+    uint32_t first_row, n_rows;
+    unsigned long long points;
+    int32_t lo[3], hi[3];
+    uint32_t source_row, reserved;
+};
+static_assert(sizeof(Component) == 48, "component is 48 bytes");
+
+struct CompParams {
+    double min_dot;                 // min_normal_dot
+    unsigned long long min_points;
+    uint32_t min_rows, keep_largest;
+    int32_t reach;                  // 1..kQueryMaxRadius
+};
+
+// row_of[nid] = j for the records of the sorted row set (row_of is all kCompNone before), parent[j] = j.
+__global__ __launch_bounds__(256) void k_comp_index(const uint32_t* __restrict__ vals, const uint32_t n_rows, uint32_t* __restrict__ row_of,
+                                                    uint32_t* __restrict__ parent)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_rows) return;
+    row_of[vals[j]] = j;
+    parent[j] = j;
+}
+
+__device__ __forceinline__ uint32_t comp_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// The root of x as far as this lane can see, with path halving.  Every value parent[x] ever holds is a row of x's component not
+// above x, so a stale read costs a step and an atomicMin never loses a link.
+__device__ __forceinline__ uint32_t comp_find(uint32_t* parent, uint32_t x)
+{
+    for (;;) {
+        const uint32_t p = comp_load(&parent[x]);
+        if (p == x) return x;
+        const uint32_t gp = comp_load(&parent[p]);
+        if (gp != p) atomicMin(&parent[x], gp);
+        x = gp;
+    }
+}
+
+// Hook the larger root under the smaller.  atomicMin returns what the larger one pointed to: itself, and the hook is done; or
+// another row `old` that got in first.  parent[a] is then min(old, b), which keeps a with one of them, and the pair (old, b) is what
+// remains to be united.
+__device__ __forceinline__ void comp_unite(uint32_t* parent, uint32_t a, uint32_t b)
+{
+    for (;;) {
+        a = comp_find(parent, a);
+        b = comp_find(parent, b);
+        if (a == b) return;
+        if (a < b) {
+            const uint32_t s = a;
+            a = b, b = s;
+        }
+        const uint32_t old = atomicMin(&parent[a], b);
+        if (old == a) return;
+        a = old;
+    }
+}
+
+// One lane per row j, in row order: the rows of the (2 reach + 1)^3 window that precede j lexicographically all have x <= j's x, so
+// only that half of the window is walked.
+__global__ __launch_bounds__(256) void k_comp_link(const GridParams g, const Tables t, const CompParams p, const Row* __restrict__ rows,
+                                                   const uint32_t n_rows, const uint32_t* __restrict__ row_of, const uint32_t n_records,
+                                                   uint32_t* __restrict__ parent)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_rows) return;
+    const int32_t v[3] = {rows[j].ix, rows[j].iy, rows[j].iz};
+    const double nx = rows[j].nx, ny = rows[j].ny, nz = rows[j].nz;
+    int lo[3], hi[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        lo[a] = max(v[a] - p.reach, 0);
+        hi[a] = min(v[a] + (a == 0 ? 0 : p.reach), g.dim[a] - 1);
+    }
+    window_walk(g, t, lo, hi, [&](const int32_t, const int32_t, const int32_t, const uint32_t nid) {
+        if (nid > n_records) return;  // (row_of has n_records + 1 entries; every record of the tables is below that)
+        const uint32_t i = row_of[nid];
+        if (i >= j) return;  // later rows unite with j themselves; kCompNone: a record without a row
+        const double dot = (nx * (double)t.nv_n[3 * (uint64_t)nid] + ny * (double)t.nv_n[3 * (uint64_t)nid + 1]) + nz * (double)t.nv_n[3 * (uint64_t)nid + 2];
+        if (!(dot >= p.min_dot)) return;
+        comp_unite(parent, i, j);
+    });
+}
+
+// root[j] = the root of j (k_comp_link has finished: the forest is final), flag[j] = 1 for a root.  flag has n_rows + 1 entries, the
+// last one 0 for the scan.
+__global__ __launch_bounds__(256) void k_comp_flatten(const uint32_t* __restrict__ parent, const uint32_t n_rows, uint32_t* __restrict__ root,
+                                                      uint32_t* __restrict__ flag)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > n_rows) return;
+    if (j == n_rows) {
+        flag[j] = 0;
+        return;
+    }
+    uint32_t r = j;
+    for (uint32_t q = parent[r]; q != r; q = parent[r]) r = q;
+    root[j] = r;
+    flag[j] = r == j ? 1u : 0u;
+}
+
+// comp_of[j] = the number of j's component (cbase = the exclusive scan of the root flags); a root also sets up its record.
+__global__ __launch_bounds__(256) void k_comp_init(const uint32_t* __restrict__ root, const uint32_t* __restrict__ cbase, const uint32_t n_rows,
+                                                   uint32_t* __restrict__ comp_of, Component* __restrict__ comps)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_rows) return;
+    const uint32_t r = root[j], c = cbase[r];
+    comp_of[j] = c;
+    if (r != j) return;
+    Component k;
+    k.first_row = 0, k.n_rows = 0, k.points = 0;
+    k.lo[0] = k.lo[1] = k.lo[2] = INT_MAX;
+    k.hi[0] = k.hi[1] = k.hi[2] = INT_MIN;
+    k.source_row = j, k.reserved = 0;
+    comps[c] = k;
+}
+
+// n_rows, points and the index box of every component.  Rows are in lexicographic order, so most waves hold rows of one component:
+// such a wave reduces in registers and issues one set of atomics, a mixed wave one set per lane.
+__global__ __launch_bounds__(256) void k_comp_reduce(const Row* __restrict__ rows, const uint32_t* __restrict__ comp_of, const uint32_t n_rows,
+                                                     Component* __restrict__ comps)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = j < n_rows;
+    const uint32_t jj = live ? j : n_rows - 1;  // (n_rows > 0) a dead lane mirrors the last row and adds nothing
+    const uint32_t c = comp_of[jj];
+    uint32_t n = live ? 1u : 0u;
+    unsigned long long pts = live ? (unsigned long long)rows[jj].count : 0ull;
+    int32_t lo[3] = {rows[jj].ix, rows[jj].iy, rows[jj].iz}, hi[3] = {lo[0], lo[1], lo[2]};
+    const bool uniform = __all(c == __shfl(c, 0));
+    if (uniform) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            n += __shfl_down(n, o);
+            pts += __shfl_down(pts, o);
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                lo[a] = min(lo[a], __shfl_down(lo[a], o));
+                hi[a] = max(hi[a], __shfl_down(hi[a], o));
+            }
+        }
+        if ((threadIdx.x & 63u) != 0) return;
+    } else if (!live) {
+        return;
+    }
+    Component* k = &comps[c];
+    atomicAdd(&k->n_rows, n);
+    atomicAdd(&k->points, pts);
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        atomicMin(&k->lo[a], lo[a]);
+        atomicMax(&k->hi[a], hi[a]);
+    }
+}
+
+__device__ __forceinline__ bool comp_passes(const Component& k, const CompParams& p) { return k.n_rows >= p.min_rows && k.points >= p.min_points; }
+
+// keep[c] without keep_largest (keep has n_comps + 1 entries, the last one 0 for the scan) ...
+__global__ __launch_bounds__(256) void k_comp_keep(const Component* __restrict__ comps, const uint32_t n_comps, const CompParams p, uint32_t* __restrict__ keep)
+{
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c > n_comps) return;
+    keep[c] = c < n_comps && comp_passes(comps[c], p) ? 1u : 0u;
+}
+// ... and with it: the sort key puts the passing components in front, n_rows descending, then representative ascending; the others get
+// the all-ones key (a representative is below 2^32 - 1, so no passing key is all ones).
+__global__ __launch_bounds__(256) void k_comp_rank_keys(const Component* __restrict__ comps, const uint32_t n_comps, const CompParams p,
+                                                        uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ keep)
+{
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c > n_comps) return;
+    keep[c] = 0;
+    if (c == n_comps) return;
+    const Component k = comps[c];
+    keys[c] = comp_passes(k, p) ? ((uint64_t)(~k.n_rows) << 32) | k.source_row : ~0ull;
+    vals[c] = c;
+}
+__global__ __launch_bounds__(256) void k_comp_rank_keep(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, const uint32_t n_front,
+                                                        uint32_t* __restrict__ keep)
+{
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < n_front && keys[r] != ~0ull) keep[vals[r]] = 1;
+}
+
+// rkeep[j] = 1 for a row of a kept component (n_rows + 1 entries, the last one 0 for the scan)
+__global__ __launch_bounds__(256) void k_comp_row_keep(const uint32_t* __restrict__ comp_of, const uint32_t* __restrict__ keep, const uint32_t n_rows,
+                                                       uint32_t* __restrict__ rkeep)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > n_rows) return;
+    rkeep[j] = j < n_rows ? keep[comp_of[j]] : 0u;
+}
+
+// The outputs: kept rows (out_rows may be null) and their labels at rbase[j], kept records at kbase[c] (written by the representative).
+__global__ __launch_bounds__(256) void k_comp_compact(const Row* __restrict__ rows, const uint32_t n_rows, const uint32_t* __restrict__ comp_of,
+                                                      const uint32_t* __restrict__ keep, const uint32_t* __restrict__ kbase,
+                                                      const uint32_t* __restrict__ rbase, const Component* __restrict__ comps,
+                                                      Row* __restrict__ out_rows, uint32_t* __restrict__ out_labels, Component* __restrict__ out_comps)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_rows) return;
+    const uint32_t c = comp_of[j];
+    if (!keep[c]) return;
+    const uint32_t o = rbase[j], label = kbase[c];
+    if (out_rows) out_rows[o] = rows[j];
+    out_labels[o] = label;
+    if (comps[c].source_row != j) return;
+    Component k = comps[c];
+    k.first_row = o;
+    out_comps[label] = k;
+}
+
 
 // ---- multi-GPU epoch exchange ----------------------------------------------------------
 // Frames shard across ranks; what must be agreed before a clean pass is the occupancy set and, per cell, the

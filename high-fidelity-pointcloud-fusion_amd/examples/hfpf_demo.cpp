@@ -2,7 +2,8 @@
 // synthetic sensor -> ~start -> N x PointCloud2 callbacks with tf poses -> periodic clean -> ~process ->
 // <dir>/test_cloud.pcd + <dir>/meta.csv.  Prints per-stage wall times.
 //
-//   hfpf_demo <out_dir> [frames=30] [W=640] [H=480] [resolution=0.001] [clean_every=10] [seed=0xF051] [pose_seed=0x5E3]
+//   hfpf_demo [--min-component N] <out_dir> [frames=30] [W=640] [H=480] [resolution=0.001] [clean_every=10] [seed=0xF051] [pose_seed=0x5E3]
+// --min-component N: ~process saves only the connected components (26-neighbourhood) of at least N rows (hfpf_node_set_component_filter).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -40,8 +41,13 @@ double now()
 
 int main(int argc, char** argv)
 {
+    uint32_t min_component = 0;
+    if (argc > 2 && strcmp(argv[1], "--min-component") == 0) {
+        min_component = (uint32_t)strtoul(argv[2], nullptr, 0);
+        argv += 2, argc -= 2;
+    }
     if (argc < 2) {
-        fprintf(stderr, "usage: %s <out_dir> [frames] [W] [H] [resolution] [clean_every] [seed] [pose_seed]\n", argv[0]);
+        fprintf(stderr, "usage: hfpf_demo [--min-component N] <out_dir> [frames] [W] [H] [resolution] [clean_every] [seed] [pose_seed]\n");
         return 2;
     }
     const std::string dir = argv[1];
@@ -67,6 +73,18 @@ int main(int argc, char** argv)
     if (hfpf_node_create(&p, lookup, &tf, &node) != HFPF_OK) {
         fprintf(stderr, "create: %s\n", hfpf_node_last_error(nullptr));
         return 1;
+    }
+    if (min_component) {
+        hfpf_component_opts co;
+        memset(&co, 0, sizeof co);
+        co.struct_size = sizeof co;
+        co.reach = 1;
+        co.min_normal_dot = -2.0;
+        co.min_rows = min_component;
+        if (hfpf_node_set_component_filter(node, &co) != HFPF_OK) {
+            fprintf(stderr, "component filter: %s\n", hfpf_node_last_error(node));
+            return 1;
+        }
     }
     hfpf_trigger_response r;
     hfpf_node_start(node, &r);

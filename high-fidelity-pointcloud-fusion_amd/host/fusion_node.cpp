@@ -31,6 +31,8 @@ struct hfpf_node {
     hfpf_publish_fn publish = nullptr;  // ~pcl_fusion_node/processed_cloud_normals (node.cpp:158)
     bool mesh_on = false;               // hfpf_node_set_mesh_output: ~process also writes mesh.ply
     hfpf_mesh_opts mesh_opts{};
+    bool comp_on = false;               // hfpf_node_set_component_filter: ~process saves the rows of the kept components only
+    hfpf_component_opts comp_opts{};
     void* publish_user = nullptr;
     std::thread clean_thread;
     std::mutex cv_mtx;
@@ -226,11 +228,16 @@ int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
     const std::string meta_location = n->directory_name + "/meta.csv";         // node.cpp:396
     hfpf_row* rows = nullptr;
     uint64_t nr = 0;
-    int rc = hfpf_extract(n->grid, &rows, &nr);  // grid_.downloadData, node.cpp:398
+    uint32_t* labels = nullptr;
+    hfpf_component* comps = nullptr;
+    uint64_t ncomp = 0;
+    int rc = n->comp_on ? hfpf_extract_components(n->grid, &n->comp_opts, &rows, &labels, &nr, &comps, &ncomp)  // EXTENSION: without the specks
+                        : hfpf_extract(n->grid, &rows, &nr);                                                  // grid_.downloadData, node.cpp:398
     if (rc == HFPF_OK) rc = hfpf_write_pcd(rows, nr, cloud_location.c_str());
     if (rc == HFPF_OK) rc = hfpf_write_meta_csv(rows, nr, meta_location.c_str());
     if (rc == HFPF_OK && n->publish) n->publish(n->publish_user, rows, nr, n->fusion_frame.c_str());  // processed_cloud_, node.cpp:158
-    hfpf_free_rows(rows);
+    if (n->comp_on) hfpf_free_components(rows, labels, comps);
+    else hfpf_free_rows(rows);
     if (rc == HFPF_OK && n->mesh_on) {  // EXTENSION: a triangle mesh of the same model next to the cloud
         hfpf_mesh_vertex* mv = nullptr;
         uint32_t* mt = nullptr;
@@ -302,6 +309,18 @@ int hfpf_node_set_mesh_output(hfpf_node* n, const hfpf_mesh_opts* opts)
         n->mesh_opts = *opts;
     }
     n->mesh_on = opts != nullptr;
+    return HFPF_OK;
+}
+
+int hfpf_node_set_component_filter(hfpf_node* n, const hfpf_component_opts* opts)
+{
+    if (!n) return HFPF_ERR_BAD_ARG;
+    if (opts) {
+        if (hfpf_check_component_opts(opts) != HFPF_OK)
+            return nfail(n, HFPF_ERR_BAD_ARG, "hfpf_node_set_component_filter: invalid hfpf_component_opts");
+        n->comp_opts = *opts;
+    }
+    n->comp_on = opts != nullptr;
     return HFPF_OK;
 }
 

@@ -92,6 +92,7 @@ EXPORTS = [
     "hfpf_track_depth", "hfpf_track_depth_device", "hfpf_track",
     "hfpf_query", "hfpf_query_device", "hfpf_query_depth",
     "hfpf_extract_mesh", "hfpf_extract_mesh_device", "hfpf_free_mesh", "hfpf_write_ply", "hfpf_check_mesh_opts",
+    "hfpf_check_component_opts", "hfpf_extract_components", "hfpf_extract_components_device", "hfpf_free_components",
     "hfpf_check_raycast_opts", "hfpf_raycast", "hfpf_raycast_device", "hfpf_raycast_view", "hfpf_raycast_view_device",
     "hfpf_snapshot", "hfpf_free_snapshot", "hfpf_restore", "hfpf_save", "hfpf_load", "hfpf_snapshot_info", "hfpf_config_from_snapshot",
 ]
@@ -255,6 +256,34 @@ def mesh_opts(radius=2, min_count=0.0, max_distance=float("inf")):
     o.radius = int(radius)
     o.min_count, o.max_distance = float(min_count), float(max_distance)
     return o
+
+
+class ComponentOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("reach", C.c_int32), ("reserved0", C.c_int32),
+                ("min_count", C.c_double), ("min_normal_dot", C.c_double), ("min_rows", C.c_uint32), ("keep_largest", C.c_uint32),
+                ("min_points", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+# hfpf_component (include/hfpf.h)
+COMPONENT_DTYPE = np.dtype([("first_row", "<u4"), ("n_rows", "<u4"), ("points", "<u8"), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)),
+                            ("source_row", "<u4"), ("reserved", "<u4")])
+assert COMPONENT_DTYPE.itemsize == 48
+
+
+def component_opts(reach=1, min_count=0.0, min_normal_dot=-2.0, min_rows=0, min_points=0, keep_largest=0):
+    """An hfpf_component_opts: the neighbour reach in voxels (1..4), the count gate of the row set, the normal gate of an edge (-2 =
+    off) and the three keep tests of a component (0 = off)."""
+    o = ComponentOpts()
+    o.struct_size = C.sizeof(ComponentOpts)
+    o.reach = int(reach)
+    o.min_count, o.min_normal_dot = float(min_count), float(min_normal_dot)
+    o.min_rows, o.keep_largest, o.min_points = int(min_rows), int(keep_largest), int(min_points)
+    return o
+
+
+def check_component_opts(o):
+    """hfpf_check_component_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
+    return lib().hfpf_check_component_opts(C.byref(o) if o is not None else None)
 
 
 # hfpf_raycast_opts.flags, hfpf_ray_hit.flags, hfpf_ray and hfpf_ray_hit (include/hfpf.h)
@@ -466,6 +495,11 @@ def lib():
     L.hfpf_free_mesh.restype = None
     L.hfpf_write_ply.argtypes = [vp, u64, vp, u64, C.c_char_p]
     L.hfpf_check_mesh_opts.argtypes = [C.POINTER(MeshOpts)]
+    L.hfpf_check_component_opts.argtypes = [C.POINTER(ComponentOpts)]
+    for fn in (L.hfpf_extract_components, L.hfpf_extract_components_device):
+        fn.argtypes = [vp, C.POINTER(ComponentOpts), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64)]
+    L.hfpf_free_components.argtypes = [vp, vp, vp]
+    L.hfpf_free_components.restype = None
     dbl = C.c_double
     L.hfpf_check_raycast_opts.argtypes = [C.POINTER(RaycastOpts)]
     L.hfpf_raycast.argtypes = [vp, C.POINTER(RaycastOpts), vp, u64, vp, vp]
@@ -816,6 +850,33 @@ class OccupancyGrid:
         v, nv, t, nt = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
         self._chk(lib().hfpf_extract_mesh_device(self._h, C.byref(o), C.byref(v), C.byref(nv), C.byref(t), C.byref(nt)))
         return v.value or 0, nv.value, t.value or 0, nt.value
+
+    # -- connected components, and the model without its specks --
+    def extract_components(self, opts=None, rows=True, device=False, **kw):
+        """The rows of the kept components, their labels and the component records (hfpf_extract_components): (rows of ROW_DTYPE or
+        None with rows=False, uint32 labels, comps of COMPONENT_DTYPE), copied out of the engine's host arrays.  Keywords as
+        component_opts().  device=True runs hfpf_extract_components_device instead and returns (rows pointer, labels pointer, n_rows,
+        comps pointer, n_comps) in HBM; free the pointers with device_free (they are 0 when nothing is kept)."""
+        o = opts if opts is not None else component_opts(**kw)
+        r, l, nr, c, nc = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+        rp = C.byref(r) if rows else None
+        if device:
+            self._chk(lib().hfpf_extract_components_device(self._h, C.byref(o), rp, C.byref(l), C.byref(nr), C.byref(c), C.byref(nc)))
+            return r.value or 0, l.value or 0, nr.value, c.value or 0, nc.value
+        self._chk(lib().hfpf_extract_components(self._h, C.byref(o), rp, C.byref(l), C.byref(nr), C.byref(c), C.byref(nc)))
+        try:
+            out = np.empty(nr.value, ROW_DTYPE) if rows else None
+            labels = np.empty(nr.value, np.uint32)
+            comps = np.empty(nc.value, COMPONENT_DTYPE)
+            if nr.value:
+                if rows:
+                    C.memmove(out.ctypes.data, r.value, out.nbytes)
+                C.memmove(labels.ctypes.data, l.value, labels.nbytes)
+            if nc.value:
+                C.memmove(comps.ctypes.data, c.value, comps.nbytes)
+        finally:
+            lib().hfpf_free_components(r, l, c)
+        return out, labels, comps
 
     # -- casting rays against the model --
     def raycast(self, rays, pose, opts=None, **kw):

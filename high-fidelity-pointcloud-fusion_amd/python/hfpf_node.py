@@ -16,7 +16,7 @@ TF_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_d
 EXPORTS = ["hfpf_node_default_params", "hfpf_node_create", "hfpf_node_destroy", "hfpf_node_last_error", "hfpf_node_on_point_cloud",
            "hfpf_node_start", "hfpf_node_stop", "hfpf_node_reset", "hfpf_node_process", "hfpf_node_clean_now", "hfpf_node_grid",
            "hfpf_node_get_stats", "hfpf_node_set_publisher", "hfpf_node_on_depth_image",
-           "hfpf_node_set_mesh_output", "hfpf_node_save_session", "hfpf_node_load_session"]
+           "hfpf_node_set_mesh_output", "hfpf_node_save_session", "hfpf_node_load_session", "hfpf_node_set_component_filter"]
 
 
 class Params(C.Structure):
@@ -65,6 +65,7 @@ def lib():
         L.hfpf_node_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.hfpf_node_set_publisher.argtypes = [C.c_void_p, PUBLISH_FN, C.c_void_p]
         L.hfpf_node_set_mesh_output.argtypes = [C.c_void_p, C.POINTER(hfpf.MeshOpts)]
+        L.hfpf_node_set_component_filter.argtypes = [C.c_void_p, C.POINTER(hfpf.ComponentOpts)]
         L.hfpf_node_save_session.argtypes = [C.c_void_p, C.c_char_p]
         L.hfpf_node_load_session.argtypes = [C.c_void_p, C.c_char_p]
         _lib = L
@@ -178,6 +179,14 @@ class FusionNode:
         keywords turns it off."""
         o = opts if opts is not None else (hfpf.mesh_opts(**kw) if kw else None)
         rc = lib().hfpf_node_set_mesh_output(self._h, C.byref(o) if o is not None else None)
+        if rc < 0:
+            raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
+
+    def set_component_filter(self, opts=None, **kw):
+        """~process saves only the rows of the components hfpf_extract_components keeps with these hfpf.component_opts (or its
+        keywords); set_component_filter(None) with no keywords turns it off."""
+        o = opts if opts is not None else (hfpf.component_opts(**kw) if kw else None)
+        rc = lib().hfpf_node_set_component_filter(self._h, C.byref(o) if o is not None else None)
         if rc < 0:
             raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
 

@@ -647,6 +647,76 @@ int hfpf_raycast_view(hfpf_handle* h, const hfpf_raycast_opts* o, uint32_t width
 int hfpf_raycast_view_device(hfpf_handle* h, const hfpf_raycast_opts* o, uint32_t width, uint32_t height, double fx, double fy, double cx,
                              double cy, uint32_t n_views, const double* poses, hfpf_ray_hit* dev_hits);
 
+/* ---- connected components of the fused model, and the model without its specks (no reference counterpart) ---------------------
+ * Tells which rows belong together and drops the small islands that float off the surface (flying pixels at depth
+ * discontinuities, a cable that crossed the view), which a count threshold alone cannot remove.  Everything is restatable from
+ * hfpf_extract_filtered's rows (tests/components_ref.py).
+ * Row set: the rows hfpf_extract_filtered would return at this point of the call sequence with the same min_count (rows with
+ *   count < min_count are dropped; 0 keeps all), in lexicographic (ix, iy, iz) order; host frames still waiting are launched first.
+ *   Row j below is the j-th of them.
+ * Adjacency: rows a and b are adjacent iff max(|ix_a - ix_b|, |iy_a - iy_b|, |iz_a - iz_b|) <= reach (1..4; reach 1 is the
+ *   26-neighbourhood) and ((double)nx_a*(double)nx_b + (double)ny_a*(double)ny_b) + (double)nz_a*(double)nz_b >= min_normal_dot:
+ *   f64, left to right, never contracted, on the stored f32 normals.  The dot is taken as is (no absolute value), so it inherits the
+ *   rows' orientation as mesh and raycast do.  The expression is symmetric in a and b, so the relation is; a NaN compares false.
+ *   min_normal_dot = -2 is off: no pair of stored (unit) normals falls below it.
+ * Components: the equivalence classes of the transitive closure.  A component's representative is its smallest row index.
+ * Per component: n_rows = the number of its rows, points = the uint64 sum of their count, lo / hi = the min / max of their voxel
+ *   indices per axis.  All integer reductions: nothing depends on scheduling.
+ * Kept: a component is kept iff n_rows >= min_rows, points >= min_points and (keep_largest == 0 or rank < keep_largest), its rank
+ *   being its position when the components that pass the first two tests are ordered by n_rows descending, then representative
+ *   ascending.
+ * Outputs: rows = the rows of the kept components in their original order, byte-identical to hfpf_extract_filtered's (no colour
+ *   coding); labels[i] = the component of output row i, the kept components numbered 0..n_comps-1 by ascending representative;
+ *   comps[c] = the hfpf_component below.  With min_rows = min_points = keep_largest = 0 the output is the plain labelling of every row.
+ * A call changes nothing on the handle except device_bytes (its scratch: 4 bytes per normal record, 24 per row, 64 per component,
+ * the sort and scan buffers and, for the host form, the output).  Render, track, query, mesh and raycast do NOT honour a component
+ * filter: they see every row.  Rejected with HFPF_ERR_BAD_ARG (the handle stays usable, nothing is written): struct_size != sizeof,
+ * flags, reserved0 or reserved != 0, reach outside 1..4, min_count NaN, min_normal_dot not finite or outside [-2, 1], a NULL n_rows,
+ * n_comps, labels or comps pointer (rows may be NULL: not produced).  An empty handle, or one before its first clean pass, returns
+ * HFPF_OK with 0 rows, 0 components and NULL arrays.  A handle with an RCCL communicator returns HFPF_ERR_STATE (a distributed form
+ * is not provided); a failed handle returns HFPF_ERR_STATE as extract does.  Every call returns when its outputs are complete. */
+typedef struct hfpf_component_opts {
+    uint32_t struct_size;        /* = sizeof(hfpf_component_opts) */
+    uint32_t flags;              /* 0 */
+    int32_t reach;               /* 1..4: Chebyshev distance, in voxels, up to which two rows are neighbours */
+    int32_t reserved0;           /* 0 */
+    double min_count;            /* rows with count < min_count are dropped before the labelling (0 keeps all) */
+    double min_normal_dot;       /* -2..1: neighbours are joined only when their normals' dot product reaches it; -2 = off */
+    uint32_t min_rows;           /* components with fewer rows are dropped (0 keeps all) */
+    uint32_t keep_largest;       /* 0 = off; else only the keep_largest largest components (by n_rows) are kept */
+    uint64_t min_points;         /* components whose counts sum to less are dropped (0 keeps all) */
+    uint64_t reserved;           /* 0 */
+} hfpf_component_opts;
+
+typedef struct hfpf_component {  /* 48 bytes */
+    uint32_t first_row;          /* index of the representative in the output rows */
+    uint32_t n_rows;             /* rows of the component */
+    uint64_t points;             /* sum of count over its rows */
+    int32_t lo[3];               /* min voxel index per axis */
+    int32_t hi[3];               /* max voxel index per axis */
+    uint32_t source_row;         /* the representative's index in the row set (before the keep tests; after the min_count gate) */
+    uint32_t reserved;           /* 0 */
+} hfpf_component;
+
+#ifdef __cplusplus
+static_assert(sizeof(hfpf_component_opts) == 56, "hfpf_component_opts is 56 bytes");
+static_assert(sizeof(hfpf_component) == 48, "hfpf_component is 48 bytes");
+#else
+_Static_assert(sizeof(hfpf_component_opts) == 56, "hfpf_component_opts is 56 bytes");
+_Static_assert(sizeof(hfpf_component) == 48, "hfpf_component is 48 bytes");
+#endif
+
+/* HFPF_OK if o passes the checks above, else HFPF_ERR_BAD_ARG (host code, no handle; the node shell uses it too). */
+int hfpf_check_component_opts(const hfpf_component_opts* o);
+/* Rows (optional: rows == NULL = not produced), labels (n_rows of each) and components (n_comps) in HOST memory, freed by
+ * hfpf_free_components. */
+int hfpf_extract_components(hfpf_handle* h, const hfpf_component_opts* o, hfpf_row** rows, uint32_t** labels, uint64_t* n_rows,
+                            hfpf_component** comps, uint64_t* n_comps);
+void hfpf_free_components(hfpf_row* rows, uint32_t* labels, hfpf_component* comps);
+/* The same in DEVICE memory (HBM), each array freed by hfpf_device_free(h, p). */
+int hfpf_extract_components_device(hfpf_handle* h, const hfpf_component_opts* o, hfpf_row** dev_rows, uint32_t** dev_labels, uint64_t* n_rows,
+                                   hfpf_component** dev_comps, uint64_t* n_comps);
+
 /* <directory_name>/test_cloud.pcd (node.cpp:395): PCD v0.7 ASCII, FIELDS x y z rgb normal_x normal_y normal_z curvature */
 int hfpf_write_pcd(const hfpf_row* rows, uint64_t n_rows, const char* path);
 /* <directory_name>/meta.csv (node.cpp:396) with the header string of grid.hpp:462 */
@@ -684,7 +754,8 @@ int hfpf_get_occupied(hfpf_handle* h, int32_t* xyz, uint64_t cap, uint64_t* n_ou
  *
  * WHAT A RESTORE IS.  hfpf_clear followed by putting that state in place.  Afterwards the handle is indistinguishable from the
  * source handle at the moment of the snapshot, in this sense:
- *   1. every read-only call (extract, extract_filtered, get_occupied, is_dirty, render*, query*, extract_mesh*, raycast*, track*)
+ *   1. every read-only call (extract, extract_filtered, get_occupied, is_dirty, render*, query*, extract_mesh*, raycast*, track*,
+ *      extract_components*)
  *      returns byte-identical output;
  *   2. any continuation (integrate*, clean, extract, clear, automatic frame ids included) produces byte-identical rows and occupied
  *      lists to the same continuation on the source handle;
@@ -798,7 +869,8 @@ int hfpf_device_copy(hfpf_handle* h, void* dev_dst, const void* dev_src, uint64_
  * kernel of hfpf_clean, host read-backs included).  enable = 2 additionally brackets the kernels of every integrate call:
  * 2 = k_integrate, 3 = k_update_cells / k_update, 4 = k_buffer (three more event records per call: use it for a breakdown
  * pass, not for the headline timing).  5 = k_raycast launches of hfpf_raycast* (the march alone, without the empty-space maps and
- * the copies; any enable).  total_ms / launches accumulate since enable. */
+ * the copies; any enable).  6 = the component kernels of one hfpf_extract_components* call (index to compaction, the scans' read-backs
+ * included, without the row set and the copies; any enable).  total_ms / launches accumulate since enable. */
 int hfpf_kernel_timing(hfpf_handle* h, int enable);
 int hfpf_get_kernel_time(hfpf_handle* h, int kernel_id, double* total_ms, uint64_t* launches);
 

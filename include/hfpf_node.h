@@ -93,6 +93,13 @@ int hfpf_node_set_publisher(hfpf_node* n, hfpf_publish_fn fn, void* user);
  * refused with HFPF_ERR_BAD_ARG and leave the setting as it was.  (hfpf_node_params keeps its size: it is part of the ABI.) */
 int hfpf_node_set_mesh_output(hfpf_node* n, const hfpf_mesh_opts* opts);
 
+/* EXTENSION: with a component filter set, ~process saves the model without its specks: test_cloud.pcd and meta.csv (and the
+ * published cloud) hold the rows hfpf_extract_components keeps with these options instead of every row.  mesh.ply and the
+ * write_variants files are not filtered.  NULL turns it off again, the default: the files are then byte-identical to those of a node
+ * that never called this.  Invalid options (hfpf_check_component_opts) are refused with HFPF_ERR_BAD_ARG and leave the setting as it
+ * was. */
+int hfpf_node_set_component_filter(hfpf_node* n, const hfpf_component_opts* opts);
+
 /* EXTENSION: keep the grid's session in a file and take it up again (hfpf_save / hfpf_load of include/hfpf.h on the node's grid, with
  * their errors).  Both run under the grid's own lock, so they are legal while the cloud callback and the clean thread run: a frame
  * or a clean pass lands wholly before or wholly after them.  Loading replaces the fused data only: the node stays started or stopped
