@@ -203,6 +203,7 @@ struct Knobs {
     float test_bin_scale = 1.f;      // tests only (HFPF_TEST_BIN_SCALE): shrinks the planned bin regions so that they overflow into the direct forms
     bool test_table_skip = false;    // tests only (HFPF_TEST_TABLE_SKIP=1): Tables::test_table_skip
     bool mailbox = true;             // HFPF_MAILBOX=0: counter read-backs by blit copies + synchronize
+    int test_dev_tile = kDevTileDefault;  // tests only (HFPF_TEST_DEV_TILE=8..256): triangles per LDS tile of k_dev_rows
     int stage_threads = 0;           // HFPF_STAGE_THREADS: helpers of the StagePool (default half the process's cores - 1, at most 7; 0 = none)
 };
 
@@ -311,6 +312,9 @@ struct hfpf_handle {
     // hfpf_extract_components*: record -> row, the per-row words (parent, root, component, flags and bases), the component records and
     // their keep flags, ranks and bases, the host form's output
     DevBuf comp_index, comp_rows, comp_recs, comp_out;
+    // hfpf_compare_mesh*: the host form's mesh, the transformed vertices and triangle records, the bricks' keys / ranges / counters /
+    // summary, the (brick, triangle) pairs (unsorted and sorted), the host form's output
+    DevBuf dev_mesh, dev_tri, dev_bins, dev_pairs, dev_out;
     DevBuf ray_in, ray_out, ray_map;       // hfpf_raycast*: a host chunk's rays, a chunk's (or band's) hits, the empty-space maps
     DevBuf snap_stage, snap_err;           // hfpf_snapshot / hfpf_restore: the staging buffer (or one window of it), the range check's error word
     uint64_t bin_pool = 0;           // entries in bin_pt
@@ -339,6 +343,9 @@ struct hfpf_handle {
     EventPairs ev_pending_comp;  // one pair per hfpf_extract_components* call (id 6)
     double t_comp_ms = 0;
     uint64_t n_comp_timed = 0;
+    EventPairs ev_pending_dev;  // one pair per hfpf_compare_mesh* call (id 7)
+    double t_dev_ms = 0;
+    uint64_t n_dev_timed = 0;
     double t_clean_ms = 0;
     uint64_t n_clean_timed = 0;
     std::vector<hipEvent_t> ev_free;
@@ -549,6 +556,7 @@ Knobs read_knobs()
     if (const char* bs = getenv("HFPF_TEST_BIN_SCALE")) k.test_bin_scale = std::max(0.f, std::min(1.f, (float)atof(bs)));
     const char* ts = getenv("HFPF_TEST_TABLE_SKIP");
     k.test_table_skip = ts && ts[0] == '1';
+    if (const char* dt = getenv("HFPF_TEST_DEV_TILE")) k.test_dev_tile = std::max(8, std::min(atoi(dt), kDevTileMax));
     const char* mb = getenv("HFPF_MAILBOX");
     k.mailbox = !mb || mb[0] != '0';
     int cores = (int)std::thread::hardware_concurrency();
@@ -1136,7 +1144,9 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
 
 int resolve_timing(hfpf_handle* h)
 {
-    if (h->ev_pending.empty() && h->ev_pending_clean.empty() && h->ev_pending_ray.empty() && h->ev_pending_comp.empty() && h->ev_detail.empty()) return HFPF_OK;
+    if (h->ev_pending.empty() && h->ev_pending_clean.empty() && h->ev_pending_ray.empty() && h->ev_pending_comp.empty() && h->ev_pending_dev.empty() &&
+        h->ev_detail.empty())
+        return HFPF_OK;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     auto settle = [&](EventPairs& list, double& total_ms, uint64_t& n) -> int {
         for (auto& pr : list) {
@@ -1153,6 +1163,7 @@ int resolve_timing(hfpf_handle* h)
     int rc;
     if ((rc = settle(h->ev_pending_ray, h->t_ray_ms, h->n_ray_timed))) return rc;
     if ((rc = settle(h->ev_pending_comp, h->t_comp_ms, h->n_comp_timed))) return rc;
+    if ((rc = settle(h->ev_pending_dev, h->t_dev_ms, h->n_dev_timed))) return rc;
     if ((rc = settle(h->ev_pending_clean, h->t_clean_ms, h->n_clean_timed))) return rc;
     if ((rc = settle(h->ev_pending, h->t_integrate_ms, h->n_integrate_launches))) return rc;
     for (size_t c = 0; 4 * c + 3 < h->ev_detail.size() && c < h->ev_detail_ran.size(); c++) {
@@ -1665,7 +1676,7 @@ int hfpf_destroy(hfpf_handle* h)
     for (DevBuf* b : {&h->sort_tmp, &h->keys_a, &h->keys_b, &h->vals_a, &h->vals_b, &h->rows_dev, &h->probe_a, &h->probe_b, &h->probe_c, &h->probe_d,
                       &h->probe_e, &h->probe_f, &h->zbuf, &h->render_pose, &h->render_out, &h->track_in, &h->track_acc,
                       &h->query_in, &h->query_out, &h->mesh_cube, &h->mesh_corner, &h->mesh_kdata, &h->mesh_cdata, &h->mesh_out,
-                      &h->mesh_ctr, &h->comp_index, &h->comp_rows, &h->comp_recs, &h->comp_out, &h->ray_in, &h->ray_out, &h->ray_map, &h->snap_stage, &h->snap_err})
+                      &h->mesh_ctr, &h->comp_index, &h->comp_rows, &h->comp_recs, &h->comp_out, &h->dev_mesh, &h->dev_tri, &h->dev_bins, &h->dev_pairs, &h->dev_out, &h->ray_in, &h->ray_out, &h->ray_map, &h->snap_stage, &h->snap_err})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf* b : {&h->ex_send, &h->ex_recv, &h->ex_counts, &h->stats_total, &h->bin_pt_buf, &h->bin_rgb_buf, &h->bin_sums, &h->ovf_pt_buf, &h->ovf_aux_buf, &h->pend_a, &h->pend_b})
         if (b->p) (void)hipFree(b->p);
@@ -1711,6 +1722,10 @@ int hfpf_destroy(hfpf_handle* h)
         (void)hipEventDestroy(pr.second);
     }
     for (auto& pr : h->ev_pending_comp) {
+        (void)hipEventDestroy(pr.first);
+        (void)hipEventDestroy(pr.second);
+    }
+    for (auto& pr : h->ev_pending_dev) {
         (void)hipEventDestroy(pr.first);
         (void)hipEventDestroy(pr.second);
     }
@@ -3273,6 +3288,234 @@ void hfpf_free_components(hfpf_row* rows, uint32_t* labels, hfpf_component* comp
     free(comps);
 }
 
+// ---- deviation from a triangle mesh (include/hfpf.h) ------------------------------------------------------------------------
+int hfpf_check_deviation_opts(const hfpf_deviation_opts* o)
+{
+    if (!o || o->struct_size != sizeof(hfpf_deviation_opts) || o->flags != 0 || o->reserved != 0 || std::isnan(o->min_count)) return HFPF_ERR_BAD_ARG;
+    return std::isfinite(o->max_distance) && o->max_distance > 0.0 && o->max_distance <= 1.0 ? HFPF_OK : HFPF_ERR_BAD_ARG;
+}
+
+struct DevOut {  // device arrays: new allocations for the device form; h->rows_dev and h->dev_out for the host form
+    Row* rows = nullptr;
+    Deviation* dev = nullptr;
+    uint64_t n_rows = 0;
+};
+
+static unsigned bits_for_count(uint64_t n)  // bits that hold 0..n-1 (at least 1)
+{
+    unsigned b = 1;
+    while (b < 64 && (1ull << b) < n) b++;
+    return b;
+}
+
+// Validated arguments in, the mesh on the device, under the lock.  The row set; then (timed as kernel id 7) the rows keyed by the
+// brick of their point and sorted, the list of bricks that hold rows, the transformed vertices, the triangles' records and pair count,
+// the pairs, their sort and per-brick ranges, and k_dev_rows.  The read-backs are the sizes between the stages and the summary.
+static int compare_locked(hfpf_handle* h, const hfpf_deviation_opts* o, const void* d_verts, uint64_t n_verts, uint32_t stride, const uint32_t* d_tris,
+                          uint64_t n_tris, const double* pose, bool on_device, bool want_rows, DevOut* out, hfpf_deviation_summary* summary)
+{
+    *out = DevOut{};
+    int rc;
+    uint64_t nr = 0;
+    const ExtractOpts opt{o->min_count, -1, 0};  // the compare of hfpf_extract_filtered, 0 keeps all
+    if ((rc = build_rows_locked(h, h->t.stats, opt, &nr))) return rc;
+    if (nr >= 0xFFFFFFFFull) return fail(h, HFPF_ERR_CAPACITY, "compare_mesh: %llu rows exceed the 32-bit row index", (unsigned long long)nr);
+    const uint32_t n = (uint32_t)nr;
+    const GridParams& g = h->g;
+    DevParams p;
+    memcpy(p.T, pose, sizeof p.T);
+    p.md = o->max_distance, p.md2 = o->max_distance * o->max_distance;
+    double box = 0;
+    for (int a = 0; a < 3; a++) box = std::max(box, std::max(std::fabs(g.min[a]), std::fabs(g.max[a])));
+    // |P - X| for a row point P (inside the bounding box up to the reach of a voxel's statistics, taken generously) and a triangle
+    // point X that can matter (within the inflated box of a triangle that reaches a brick): both within `box` + slack of the origin
+    p.reach = 2.0 * (box + 64.0 * g.res + 4.0 * (double)g.ball_r + o->max_distance);
+    p.face_cap = 4.0 * g.res;
+    p.n_verts = n_verts, p.n_tris = (uint32_t)n_tris, p.stride = stride;
+    p.nb = 0, p.tile = h->knobs.test_dev_tile;
+
+    const size_t R1 = (size_t)n + 1;
+    const size_t bins_bytes = (size_t)n * 8 + DC_WORDS * 8 + sizeof(DevSummary) + (3 * R1 + 2 * (size_t)n) * 4;
+    if ((rc = scratch(h, h->dev_bins, bins_bytes))) return rc;
+    uint64_t* ub_key = (uint64_t*)h->dev_bins.p;
+    unsigned long long* ctr = (unsigned long long*)(ub_key + n);
+    DevSummary* d_sum = (DevSummary*)(ctr + DC_WORDS);
+    uint32_t* flag = (uint32_t*)(d_sum + 1);
+    uint32_t* base = flag + R1;
+    uint32_t* ub_start = base + R1;
+    uint32_t* tstart = ub_start + R1;
+    uint32_t* tend = tstart + n;
+    std::pair<hipEvent_t, hipEvent_t> timed;
+    if ((rc = timed_begin(h, &timed))) return rc;
+    HIPCHK(h, hipMemsetAsync(ctr, 0, DC_WORDS * 8 + sizeof(DevSummary), h->stream));
+    uint64_t nb = 0;
+    const Row* rows = (const Row*)h->rows_dev.p;
+    if (n) {
+        const dim3 grid_r(blocks_for(n, 256)), grid_r1(blocks_for(R1, 256));
+        hipLaunchKernelGGL(k_dev_row_keys, grid_r, dim3(256), 0, h->stream, g, rows, n, (uint64_t*)h->keys_a.p, (uint32_t*)h->vals_a.p);
+        HIPCHK(h, hipGetLastError());
+        const unsigned key_bits = bits_for_count((uint64_t)g.bdim[0] * (uint64_t)g.bdim[1] * (uint64_t)g.bdim[2]);
+        if ((rc = sort_pairs_u64(h, (uint64_t*)h->keys_a.p, (uint64_t*)h->keys_b.p, (uint32_t*)h->vals_a.p, (uint32_t*)h->vals_b.p, n, key_bits))) return rc;
+        hipLaunchKernelGGL(k_dev_row_flags, grid_r1, dim3(256), 0, h->stream, (const uint64_t*)h->keys_b.p, n, flag);
+        HIPCHK(h, hipGetLastError());
+        if ((rc = mesh_scan_locked(h, flag, base, n, &nb))) return rc;
+        hipLaunchKernelGGL(k_dev_bricks, grid_r1, dim3(256), 0, h->stream, (const uint64_t*)h->keys_b.p, (const uint32_t*)flag, (const uint32_t*)base, n, (uint32_t)nb,
+                           ub_key, ub_start);
+        HIPCHK(h, hipMemsetAsync(tstart, 0, 2 * (size_t)n * 4, h->stream));
+    }
+    p.nb = (uint32_t)nb;
+    unsigned long long h_ctr[DC_WORDS] = {0, 0, 0, 0};
+    if (n_tris) {
+        const size_t v_bytes = (size_t)std::max<uint64_t>(n_verts, 1) * 24;
+        if ((rc = scratch(h, h->dev_tri, v_bytes + (size_t)n_tris * sizeof(DevTri)))) return rc;
+        double* V = (double*)h->dev_tri.p;
+        DevTri* recs = (DevTri*)((char*)h->dev_tri.p + v_bytes);
+        const dim3 grid_t(blocks_for(n_tris * 64, 256));
+        hipLaunchKernelGGL(k_dev_verts, dim3(blocks_for(n_verts, 256)), dim3(256), 0, h->stream, p, (const uint8_t*)d_verts, V);
+        hipLaunchKernelGGL(k_dev_tris<false>, grid_t, dim3(256), 0, h->stream, g, p, d_tris, (const double*)V, (const uint64_t*)ub_key, recs, ctr, (uint64_t*)nullptr,
+                           (uint64_t)0);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(h_ctr, ctr, sizeof h_ctr, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        const uint64_t np = h_ctr[DC_PAIRS];
+        if (np) {
+            // the pair list is the one buffer whose size the caller cannot foresee: failing to get it is a capacity answer, and the
+            // handle's tables were not touched, so it stays usable
+            if (np > 0xFFFFFFFEull)
+                return fail(h, HFPF_ERR_CAPACITY, "compare_mesh: %llu (triangle, brick) pairs exceed the 32-bit pair index", (unsigned long long)np);
+            if (scratch(h, h->dev_pairs, (size_t)np * 16) != HFPF_OK) {
+                (void)hipGetLastError();
+                return fail(h, HFPF_ERR_CAPACITY, "compare_mesh: no device memory for %llu (triangle, brick) pairs", (unsigned long long)np);
+            }
+            uint64_t* pairs_in = (uint64_t*)h->dev_pairs.p;
+            uint64_t* pairs = pairs_in + np;
+            hipLaunchKernelGGL(k_dev_tris<true>, grid_t, dim3(256), 0, h->stream, g, p, d_tris, (const double*)V, (const uint64_t*)ub_key, recs, ctr, pairs_in, np);
+            HIPCHK(h, hipGetLastError());
+            if ((rc = sort_keys_u64(h, pairs_in, pairs, np, 32 + bits_for_count(nb)))) return rc;
+            hipLaunchKernelGGL(k_dev_tri_ranges, dim3(blocks_for(np, 256)), dim3(256), 0, h->stream, (const uint64_t*)pairs, (uint32_t)np, (uint32_t)nb, tstart, tend);
+            HIPCHK(h, hipGetLastError());
+        }
+    }
+    DevOut d;
+    d.n_rows = nr;
+    void* owned[2] = {nullptr, nullptr};
+    if (n) {
+        if (on_device) {
+            hipError_t e = hipMalloc(&owned[0], (size_t)n * sizeof(Deviation));
+            if (e == hipSuccess && want_rows) e = hipMalloc(&owned[1], (size_t)n * sizeof(Row));
+            if (e != hipSuccess) {
+                for (void* q : owned) (void)hipFree(q);
+                return fail(h, HFPF_ERR_HIP, "compare_mesh: device allocation of %llu rows failed: %s", (unsigned long long)nr, hipGetErrorString(e));
+            }
+            d.dev = (Deviation*)owned[0], d.rows = (Row*)owned[1];
+        } else {
+            if ((rc = scratch(h, h->dev_out, (size_t)n * sizeof(Deviation)))) return rc;
+            d.dev = (Deviation*)h->dev_out.p, d.rows = want_rows ? (Row*)h->rows_dev.p : nullptr;
+        }
+        const uint64_t* pairs = h->dev_pairs.p ? (const uint64_t*)h->dev_pairs.p + h_ctr[DC_PAIRS] : nullptr;  // read only inside a non-empty range
+        const DevTri* recs = n_tris ? (const DevTri*)((char*)h->dev_tri.p + (size_t)std::max<uint64_t>(n_verts, 1) * 24) : nullptr;
+        hipLaunchKernelGGL(k_dev_rows, dim3((unsigned)nb), dim3(256), 0, h->stream, rows, (const uint32_t*)h->vals_b.p, (const uint32_t*)ub_start, (const uint32_t*)tstart,
+                           (const uint32_t*)tend, pairs, recs, p.md2, (uint32_t)p.tile, d.dev, d_sum);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) rc = timed_end(h, timed, h->ev_pending_dev);
+    if (e == hipSuccess && !rc && on_device && want_rows && n) e = hipMemcpyAsync(d.rows, rows, (size_t)n * sizeof(Row), hipMemcpyDeviceToDevice, h->stream);
+    DevSummary hs;
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(&hs, d_sum, sizeof hs, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && !rc) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess || rc) {
+        for (void* q : owned) (void)hipFree(q);
+        return rc ? rc : fail(h, HFPF_ERR_HIP, "compare_mesh: %s", hipGetErrorString(e));
+    }
+    memset(summary, 0, sizeof *summary);
+    summary->n_rows = nr, summary->n_found = hs.n_found, summary->n_negative = hs.n_negative;
+    summary->n_tris_invalid = h_ctr[DC_INVALID], summary->n_tris_valid = n_tris - h_ctr[DC_INVALID];
+    memcpy(&summary->max_abs, &hs.max_abs_bits, 4);
+    summary->sum_abs_q30 = hs.sum_abs_q30, summary->sum_sq_q30 = hs.sum_sq_q30;
+    *out = d;
+    return HFPF_OK;
+}
+
+// The checks of both forms that need the handle but not the device.  0 = fine, else the text of the fault.
+static const char* compare_args_fault(const hfpf_handle* h, const hfpf_deviation_opts* o, const void* verts, uint64_t n_verts, uint32_t stride, const uint32_t* tris,
+                                      uint64_t n_tris, const double* pose, const void* dev, const void* n_rows, const void* summary, bool on_device)
+{
+    if (hfpf_check_deviation_opts(o) != HFPF_OK) return "invalid hfpf_deviation_opts";
+    if (o->max_distance > 32.0 * h->g.res) return "max_distance exceeds 32 voxels";
+    if (!pose) return "NULL pose";
+    for (int i = 0; i < 12; i++)
+        if (!std::isfinite(pose[i])) return "non-finite pose";
+    if (stride < 12 || (stride & 3)) return "vertex_stride must be at least 12 and a multiple of 4";
+    if ((!verts && n_verts) || (!tris && n_tris)) return "NULL mesh pointer with a non-zero count";
+    if (n_verts >= 0xFFFFFFFFull || n_tris >= 0xFFFFFFFFull) return "n_verts and n_tris must stay below 2^32 - 1";
+    if (!dev || !n_rows || !summary) return "NULL dev, n_rows or summary";
+    if (on_device && ((((uintptr_t)verts) | ((uintptr_t)tris)) & 3)) return "device mesh pointers must be 4-byte aligned";
+    return nullptr;
+}
+
+int hfpf_compare_mesh_device(hfpf_handle* h, const hfpf_deviation_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride,
+                             const uint32_t* dev_tris, uint64_t n_tris, const double* pose_3x4, hfpf_row** dev_rows, hfpf_deviation** dev_dev,
+                             uint64_t* n_rows, hfpf_deviation_summary* summary)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (const char* f = compare_args_fault(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, dev_dev, n_rows, summary, true))
+        return fail(h, HFPF_ERR_BAD_ARG, "compare_mesh_device: %s", f);
+    if (int rc = local_read_prologue_locked(h, "compare_mesh")) return rc;
+    DevOut d;
+    hfpf_deviation_summary s;
+    if (int rc = compare_locked(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, true, dev_rows != nullptr, &d, &s)) return rc;
+    if (dev_rows) *dev_rows = (hfpf_row*)d.rows;
+    *dev_dev = (hfpf_deviation*)d.dev, *n_rows = d.n_rows, *summary = s;
+    return HFPF_OK;
+}
+
+int hfpf_compare_mesh(hfpf_handle* h, const hfpf_deviation_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris,
+                      uint64_t n_tris, const double* pose_3x4, hfpf_row** rows, hfpf_deviation** dev, uint64_t* n_rows, hfpf_deviation_summary* summary)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (const char* f = compare_args_fault(h, o, verts, n_verts, vertex_stride, tris, n_tris, pose_3x4, dev, n_rows, summary, false))
+        return fail(h, HFPF_ERR_BAD_ARG, "compare_mesh: %s", f);
+    if (int rc = local_read_prologue_locked(h, "compare_mesh")) return rc;
+    // the mesh to the device: the vertices as they are (stride and all), the indices behind them at a 16-byte boundary
+    const size_t v_bytes = n_verts ? (size_t)(n_verts - 1) * vertex_stride + 12 : 0, v_room = (v_bytes + 15) & ~(size_t)15, t_bytes = (size_t)n_tris * 12;
+    if (int rc = scratch(h, h->dev_mesh, v_room + t_bytes + 16)) return rc;
+    hipError_t e = v_bytes ? upload_pageable(h, h->dev_mesh.p, verts, v_bytes) : hipSuccess;
+    if (e == hipSuccess && t_bytes) e = upload_pageable(h, (char*)h->dev_mesh.p + v_room, tris, t_bytes);
+    if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "compare_mesh upload: %s", hipGetErrorString(e));
+    DevOut d;
+    hfpf_deviation_summary s;
+    if (int rc = compare_locked(h, o, h->dev_mesh.p, n_verts, vertex_stride, (const uint32_t*)((char*)h->dev_mesh.p + v_room), n_tris, pose_3x4, false, rows != nullptr,
+                                &d, &s))
+        return rc;
+    hfpf_row* hr = nullptr;
+    hfpf_deviation* hd = nullptr;
+    if (d.n_rows) {
+        hr = rows ? (hfpf_row*)host_result_alloc(d.n_rows * sizeof(hfpf_row)) : nullptr;
+        hd = (hfpf_deviation*)host_result_alloc(d.n_rows * sizeof(hfpf_deviation));
+        if ((rows && !hr) || !hd) {
+            free(hr), free(hd);
+            return fail(h, HFPF_ERR_CAPACITY, "compare_mesh: host allocation of %llu rows failed", (unsigned long long)d.n_rows);
+        }
+        e = rows ? download_pageable(h, hr, d.rows, d.n_rows * sizeof(hfpf_row)) : hipSuccess;
+        if (e == hipSuccess) e = download_pageable(h, hd, d.dev, d.n_rows * sizeof(hfpf_deviation));
+        if (e != hipSuccess) {
+            free(hr), free(hd);
+            return fail(h, HFPF_ERR_HIP, "compare_mesh copy: %s", hipGetErrorString(e));
+        }
+    }
+    if (rows) *rows = hr;
+    *dev = hd, *n_rows = d.n_rows, *summary = s;
+    return HFPF_OK;
+}
+
+void hfpf_free_deviation(hfpf_row* rows, hfpf_deviation* dev)
+{
+    free(rows);
+    free(dev);
+}
+
 int hfpf_stats_export(hfpf_handle* h, const void** dev_words, uint64_t* n_words, const void** dev_cwords, uint64_t* n_cwords)
 {
     if (!h || !dev_words || !n_words) return HFPF_ERR_BAD_ARG;
@@ -3555,6 +3798,121 @@ int hfpf_write_ply(const hfpf_mesh_vertex* verts, uint64_t n_verts, const uint32
     }
     ok = ok && !ferror(f);
     return (fclose(f) == 0 && ok) ? HFPF_OK : HFPF_ERR_IO;
+}
+
+// The inverse of hfpf_write_ply (include/hfpf.h).  The header is parsed line by line; the vertex and face counts are checked against
+// the bytes the file has left before anything is allocated.
+int hfpf_read_ply(const char* path, hfpf_mesh_vertex** verts, uint64_t* n_verts, uint32_t** tris, uint64_t* n_tris)
+{
+    if (!path || !verts || !n_verts || !tris || !n_tris) return HFPF_ERR_BAD_ARG;
+    *verts = nullptr, *tris = nullptr, *n_verts = 0, *n_tris = 0;
+    FILE* f = fopen(path, "rb");
+    if (!f) return fail(nullptr, HFPF_ERR_IO, "read_ply: cannot open %s", path);
+    hfpf_mesh_vertex* hv = nullptr;
+    uint32_t* ht = nullptr;
+    auto bad = [&](const char* what) {
+        fclose(f);
+        free(hv), free(ht);
+        return fail(nullptr, HFPF_ERR_IO, "read_ply: %s: %s", path, what);
+    };
+    if (fseek(f, 0, SEEK_END) != 0) return bad("not seekable");
+    const long end = ftell(f);
+    if (end < 0 || fseek(f, 0, SEEK_SET) != 0) return bad("not seekable");
+    auto type_size = [](const char* t) -> int {
+        static const struct { const char* name; int size; } kTypes[] = {{"char", 1}, {"int8", 1}, {"uchar", 1}, {"uint8", 1}, {"short", 2}, {"int16", 2},
+            {"ushort", 2}, {"uint16", 2}, {"int", 4}, {"int32", 4}, {"uint", 4}, {"uint32", 4}, {"float", 4}, {"float32", 4}, {"double", 8}, {"float64", 8}};
+        for (const auto& k : kTypes)
+            if (strcmp(t, k.name) == 0) return k.size;
+        return 0;
+    };
+    auto is_float = [](const char* t) { return strcmp(t, "float") == 0 || strcmp(t, "float32") == 0; };
+    auto is_uchar = [](const char* t) { return strcmp(t, "uchar") == 0 || strcmp(t, "uint8") == 0; };
+    char line[512];
+    if (!fgets(line, sizeof line, f) || strncmp(line, "ply", 3) != 0) return bad("not a PLY file");
+    int element = 0;  // 0 = none yet, 1 = vertex, 2 = face, 3 = one behind them
+    bool format_ok = false, ended = false, face_list = false;
+    unsigned long long nv = 0, nt = 0;
+    int vsize = 0, off[9] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};  // x y z nx ny nz red green blue: byte offsets in a vertex record
+    static const char* const kNames[9] = {"x", "y", "z", "nx", "ny", "nz", "red", "green", "blue"};
+    for (int n_lines = 0; n_lines < 4096 && fgets(line, sizeof line, f); n_lines++) {
+        char a[64] = "", b[64] = "", c[64] = "", d[64] = "", e[64] = "";
+        const int nf = sscanf(line, "%63s %63s %63s %63s %63s", a, b, c, d, e);
+        if (nf < 1 || strcmp(a, "comment") == 0 || strcmp(a, "obj_info") == 0) continue;
+        if (strcmp(a, "end_header") == 0) {
+            ended = true;
+            break;
+        }
+        if (strcmp(a, "format") == 0) {
+            if (nf < 3 || strcmp(b, "binary_little_endian") != 0 || strcmp(c, "1.0") != 0) return bad("only format binary_little_endian 1.0 is read");
+            format_ok = true;
+        } else if (strcmp(a, "element") == 0) {
+            char* tail = nullptr;
+            const unsigned long long cnt = nf >= 3 ? strtoull(c, &tail, 10) : 0;
+            if (nf < 3 || !tail || *tail || c[0] == '-') return bad("malformed element line");
+            if (element == 0 && strcmp(b, "vertex") == 0) element = 1, nv = cnt;
+            else if (element == 1 && strcmp(b, "face") == 0) element = 2, nt = cnt;
+            else if (element >= 2) element = 3;
+            else return bad("the vertex element must come first and the face element second");
+        } else if (strcmp(a, "property") == 0) {
+            if (element == 1) {
+                const int sz = nf >= 3 ? type_size(b) : 0;
+                if (!sz) return bad("a vertex property must be a scalar of a known type");
+                for (int k = 0; k < 9; k++)
+                    if (strcmp(c, kNames[k]) == 0 && (k < 6 ? is_float(b) : is_uchar(b))) off[k] = vsize;
+                vsize += sz;
+            } else if (element == 2) {
+                const bool ok = nf >= 5 && strcmp(b, "list") == 0 && is_uchar(c) && (strcmp(d, "uint") == 0 || strcmp(d, "int") == 0 || strcmp(d, "uint32") == 0 ||
+                                                                                    strcmp(d, "int32") == 0) &&
+                                (strcmp(e, "vertex_indices") == 0 || strcmp(e, "vertex_index") == 0);
+                if (!ok || face_list) return bad("the face element must be one property list uchar uint|int vertex_indices");
+                face_list = true;
+            } else if (element == 0) {
+                return bad("a property outside an element");
+            }
+        } else {
+            return bad("unknown header line");
+        }
+    }
+    if (!ended || !format_ok) return bad("incomplete header");
+    if (element < 1 || off[0] < 0 || off[1] < 0 || off[2] < 0) return bad("the vertex element needs float x, y, z");
+    if (nt && !face_list) return bad("the face element has no vertex_indices list");
+    const long at = ftell(f);
+    if (at < 0) return bad("not seekable");
+    const unsigned long long left = (unsigned long long)(end - at);
+    if (nv >= 0xFFFFFFFFull || nt >= 0xFFFFFFFFull) return bad("more than 2^32 - 2 vertices or faces");
+    if (nv * (unsigned long long)vsize > left || nt * 13ull > left - nv * (unsigned long long)vsize) return bad("the file is shorter than its header claims");
+    hv = (hfpf_mesh_vertex*)malloc(std::max<size_t>((size_t)nv * sizeof(hfpf_mesh_vertex), 1));
+    ht = (uint32_t*)malloc(std::max<size_t>((size_t)nt * 12, 1));
+    if (!hv || !ht) return bad("out of memory");
+    constexpr uint64_t kChunk = 1u << 14;
+    std::vector<uint8_t> buf((size_t)kChunk * std::max(vsize, 13));
+    for (uint64_t i0 = 0; i0 < nv; i0 += kChunk) {
+        const uint64_t n = std::min<uint64_t>(kChunk, nv - i0);
+        if (fread(buf.data(), (size_t)vsize, n, f) != n) return bad("truncated vertex data");
+        for (uint64_t i = 0; i < n; i++) {
+            const uint8_t* r = buf.data() + i * (size_t)vsize;
+            hfpf_mesh_vertex v;
+            memset(&v, 0, sizeof v);
+            float* dst[6] = {&v.x, &v.y, &v.z, &v.nx, &v.ny, &v.nz};
+            for (int k = 0; k < 6; k++)
+                if (off[k] >= 0) memcpy(dst[k], r + off[k], 4);
+            for (int k = 6; k < 9; k++)
+                if (off[k] >= 0) v.rgb |= (uint32_t)r[off[k]] << (8 * (8 - k));
+            hv[i0 + i] = v;
+        }
+    }
+    for (uint64_t i0 = 0; i0 < nt; i0 += kChunk) {
+        const uint64_t n = std::min<uint64_t>(kChunk, nt - i0);
+        if (fread(buf.data(), 13, n, f) != n) return bad("truncated face data");
+        for (uint64_t i = 0; i < n; i++) {
+            const uint8_t* r = buf.data() + i * 13;
+            if (r[0] != 3) return bad("a face that is not a triangle");
+            memcpy(ht + 3 * (i0 + i), r + 1, 12);
+        }
+    }
+    fclose(f);
+    *verts = hv, *tris = ht, *n_verts = nv, *n_tris = nt;
+    return HFPF_OK;
 }
 
 // Same fields as hfpf_write_pcd with DATA binary (40 bytes/point): for outputs where ASCII formatting would dominate.
@@ -4346,21 +4704,23 @@ int hfpf_kernel_timing(hfpf_handle* h, int enable)
         h->n_ray_timed = 0;
         h->t_comp_ms = 0;
         h->n_comp_timed = 0;
+        h->t_dev_ms = 0;
+        h->n_dev_timed = 0;
     }
     return HFPF_OK;
 }
 
 int hfpf_get_kernel_time(hfpf_handle* h, int kernel_id, double* total_ms, uint64_t* launches)
 {
-    if (!h || kernel_id < 0 || kernel_id > 6) return HFPF_ERR_BAD_ARG;
+    if (!h || kernel_id < 0 || kernel_id > 7) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (int rcf = flush_pending_locked(h)) return rcf;  // host frames still waiting for their launch
     int rc = resolve_timing(h);
     if (rc) return rc;
     if (kernel_id >= 5) {
-        if (total_ms) *total_ms = kernel_id == 5 ? h->t_ray_ms : h->t_comp_ms;
-        if (launches) *launches = kernel_id == 5 ? h->n_ray_timed : h->n_comp_timed;
+        if (total_ms) *total_ms = kernel_id == 5 ? h->t_ray_ms : kernel_id == 6 ? h->t_comp_ms : h->t_dev_ms;
+        if (launches) *launches = kernel_id == 5 ? h->n_ray_timed : kernel_id == 6 ? h->n_comp_timed : h->n_dev_timed;
         return HFPF_OK;
     }
     if (kernel_id >= 2) {

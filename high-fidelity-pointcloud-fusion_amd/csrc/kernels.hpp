@@ -3778,4 +3778,391 @@ __global__ __launch_bounds__(256) void k_snap_check_lists(const GridParams g, co
     if (e) atomicOr(err, e);
 }
 
+
+// ---- deviation from a triangle mesh (hfpf_compare_mesh*; contract in include/hfpf.h, numpy restatement tests/deviation_ref.py) ---------
+// The rows are binned by the 8 x 8 x 8-voxel brick their own point P falls in (dev_cell: a monotone function of P, clamped to the
+// grid's bricks, so a point outside the bounding box lands in a rim brick).  A triangle is listed in every such brick that its box,
+// inflated by max_distance and a margin (dev_tri_setup), reaches: monotonicity turns "P inside the inflated box" into "P's brick
+// inside the box's brick range" without a further argument.  Every row then meets the triangles of its brick in ascending index
+// order and keeps the first smallest dd: the contract's winner.
+struct Deviation {  // = hfpf_deviation
+    float signed_distance, distance;
+    uint32_t tri, flags;
+    float q[3];
+    uint32_t reserved;
+};
+static_assert(sizeof(Deviation) == 32, "deviation record is 32 bytes");
+
+struct DevSummary {  // = hfpf_deviation_summary; max_abs as the bits of a non-negative float, which order as the floats do
+    unsigned long long n_rows, n_found, n_negative, n_tris_valid, n_tris_invalid;
+    uint32_t max_abs_bits, pad;
+    long long sum_abs_q30, sum_sq_q30;
+};
+static_assert(sizeof(DevSummary) == 64, "deviation summary is 64 bytes");
+
+struct DevTri {  // a valid triangle in the fusion frame
+    double A[3], B[3], C[3], N[3];
+};
+static_assert(sizeof(DevTri) == 96, "triangle record is 96 bytes");
+
+enum : int { DC_PAIRS = 0, DC_CURSOR = 1, DC_INVALID = 2, DC_WORDS = 4 };  // the counters of one call
+
+struct DevParams {
+    double T[12];        // mesh frame -> fusion frame
+    double md, md2;      // max_distance and its square, as the contract compares
+    double reach;        // an upper bound on |P - X| for any row point P and any point X of a triangle that can matter (host: compare_locked)
+    double face_cap;     // a triangle whose face-region error bound exceeds it is listed in every brick
+    uint64_t n_verts;
+    uint32_t n_tris, stride;
+    uint32_t nb;         // bricks that hold rows
+    int32_t tile;        // triangles per LDS tile of k_dev_rows
+};
+
+constexpr int kDevTileMax = 256, kDevTileDefault = 128;
+constexpr uint32_t kDevFound = 1u, kDevOnEdge = 2u, kDevOnVertex = 4u;
+
+__device__ __forceinline__ double dev_dot(const double* u, const double* v) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
+
+// Brick coordinate of p on axis a.  Monotone non-decreasing in p: a rounded subtraction, a product with a positive constant, floor
+// and the clamp all are.  NaN goes to brick 0.
+__device__ __forceinline__ int32_t dev_cell(const GridParams& g, const int a, const double p)
+{
+    const double c = floor((p - g.min[a]) * (g.inv_res * 0.125));
+    const int32_t top = g.bdim[a] - 1;
+    return !(c > 0.0) ? 0 : (c > (double)top ? top : (int32_t)c);
+}
+__device__ __forceinline__ uint64_t dev_cell_key(const GridParams& g, const int32_t cx, const int32_t cy, const int32_t cz)
+{
+    return ((uint64_t)cx * (uint64_t)g.bdim[1] + (uint64_t)cy) * (uint64_t)g.bdim[2] + (uint64_t)cz;
+}
+
+__global__ __launch_bounds__(256) void k_dev_verts(const DevParams p, const uint8_t* __restrict__ verts, double* __restrict__ V)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= p.n_verts) return;
+    const float* v = (const float*)(verts + i * p.stride);
+    const double x = v[0], y = v[1], z = v[2];
+#pragma unroll
+    for (int a = 0; a < 3; a++) V[3 * i + a] = ((p.T[4 * a] * x + p.T[4 * a + 1] * y) + p.T[4 * a + 2] * z) + p.T[4 * a + 3];
+}
+
+// Triangle k: false when it is invalid.  Else tr, the range lo..hi of bricks its inflated box reaches, and everywhere = list it in
+// every brick.
+//
+// THE MARGIN.  Binning must not lose a pair whose COMPUTED dd passes dd <= md^2.  dd = (rx^2 + ry^2) + rz^2 is a rounded sum of
+// non-negative terms, so dd >= fl(r_a^2) for each axis a, and dd <= md^2 implies |r_a| <= md (1 + 2^-51) with r_a = fl(P_a - Q_a),
+// hence |P_a - Q_a| <= md (1 + 2^-50) for the computed Q.  It remains to bound how far the computed Q can lie outside the box of A,
+// B, C per axis.  With u = 2^-53, M = the largest |coordinate| of the three vertices, L = the longest edge:
+//   vertex regions: Q is a vertex, exactly.
+//   edge regions: the parameter is d/(d - d') with d >= 0 >= d' as computed; fl(d - d') >= d by monotonicity, so the rounded
+//     quotient lies in [0, 1] (0/0 gives NaN: dd is NaN and the triangle is not kept).  Q_a = fl(X_a + fl(t fl(Y_a - X_a))) for an edge
+//     X -> Y: t fl(Y_a - X_a) lies between 0 and Y_a - X_a up to 2u|Y_a - X_a| <= 4uM, the sum rounds by at most u 3M: Q_a leaves
+//     [min, max] of the box by less than 8uM = 2^-50 M.
+//   face region (first order in u, not a proof): the six dots are bounded by L D, D = the largest distance from P to a vertex, and carry
+//     an error of at most 6u L D; a product of two of them 13u L^2 D^2; va, vb, vc 27u L^2 D^2 each; s, whose exact value is NN, 85u
+//     L^2 D^2.  With |v|, |w| <= 1 that moves v and w by at most 112u L^2 D^2 / NN each and Q by 224u L^3 D^2 / NN.  A face region
+//     reached only through a rounded region test is covered too: the exact (v, w) then lies that close to the simplex.  The kernel
+//     takes four times as much, 2^-43 L^3 D^2 / NN, with D replaced by p.reach, a bound over every row; where even that exceeds
+//     p.face_cap (a sliver: NN tiny against L^4) the triangle goes to every brick and needs no bound.
+// The 2^-49 (M + md) term of the inflation covers the edge bound and the rounding of the box itself, fl(min_a - I) and fl(max_a + I).
+__device__ inline bool dev_tri_setup(const GridParams& g, const DevParams& p, const uint32_t* __restrict__ tris, const double* __restrict__ V, const uint32_t k,
+                                     DevTri& tr, int32_t (&lo)[3], int32_t (&hi)[3], bool& everywhere)
+{
+    const uint32_t i0 = tris[3ull * k], i1 = tris[3ull * k + 1], i2 = tris[3ull * k + 2];
+    if (i0 >= p.n_verts || i1 >= p.n_verts || i2 >= p.n_verts) return false;  // before anything is loaded through them
+    double M = 0.0;
+    bool finite = true;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        tr.A[a] = V[3ull * i0 + a], tr.B[a] = V[3ull * i1 + a], tr.C[a] = V[3ull * i2 + a];
+        finite = finite && isfinite(tr.A[a]) && isfinite(tr.B[a]) && isfinite(tr.C[a]);
+        M = fmax(M, fmax(fabs(tr.A[a]), fmax(fabs(tr.B[a]), fabs(tr.C[a]))));
+    }
+    if (!finite) return false;
+    const double ab[3] = {tr.B[0] - tr.A[0], tr.B[1] - tr.A[1], tr.B[2] - tr.A[2]};
+    const double ac[3] = {tr.C[0] - tr.A[0], tr.C[1] - tr.A[1], tr.C[2] - tr.A[2]};
+    const double bc[3] = {tr.C[0] - tr.B[0], tr.C[1] - tr.B[1], tr.C[2] - tr.B[2]};
+    tr.N[0] = ab[1] * ac[2] - ab[2] * ac[1];
+    tr.N[1] = ab[2] * ac[0] - ab[0] * ac[2];
+    tr.N[2] = ab[0] * ac[1] - ab[1] * ac[0];
+    const double NN = dev_dot(tr.N, tr.N);
+    if (!(isfinite(NN) && NN > 0.0)) return false;
+    const double L2 = fmax(dev_dot(ab, ab), fmax(dev_dot(ac, ac), dev_dot(bc, bc)));
+    const double face = 0x1p-43 * ((L2 * sqrt(L2)) * (p.reach * p.reach)) / NN;
+    everywhere = !(face <= p.face_cap);  // also an overflow to inf or NaN
+    const double infl = (p.md * (1.0 + 0x1p-40) + face) + 0x1p-49 * (M + p.md);
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        lo[a] = dev_cell(g, a, fmin(tr.A[a], fmin(tr.B[a], tr.C[a])) - infl);
+        hi[a] = dev_cell(g, a, fmax(tr.A[a], fmax(tr.B[a], tr.C[a])) + infl);
+    }
+    return true;
+}
+
+// One wave per triangle.  EMIT = false: the triangle's record, the count of invalid triangles and of (brick, triangle) pairs.  EMIT =
+// true: the pairs themselves, (brick << 32 | triangle), in any order (a sort follows).  The wave walks the smaller of the brick range
+// and the list of bricks that hold rows, so two triangles through a 125^3-brick grid cost as many steps as there are bricks with rows.
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_dev_tris(const GridParams g, const DevParams p, const uint32_t* __restrict__ tris, const double* __restrict__ V,
+                                                  const uint64_t* __restrict__ ub_key, DevTri* __restrict__ recs, unsigned long long* __restrict__ ctr,
+                                                  uint64_t* __restrict__ pairs, const uint64_t cap)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t kk = ((uint64_t)blockIdx.x * 256u + threadIdx.x) >> 6;
+    if (kk >= p.n_tris) return;  // the whole wave
+    const uint32_t k = (uint32_t)kk;
+    DevTri tr;
+    int32_t lo[3], hi[3];
+    bool everywhere = false;
+    const bool valid = dev_tri_setup(g, p, tris, V, k, tr, lo, hi, everywhere);  // the same in every lane
+    if (!valid) {
+        if (!EMIT && lane == 0) atomicAdd(&ctr[DC_INVALID], 1ull);
+        return;
+    }
+    if (!EMIT && lane < 12) ((double*)&recs[k])[lane] = lane < 3 ? tr.A[lane] : lane < 6 ? tr.B[lane - 3] : lane < 9 ? tr.C[lane - 6] : tr.N[lane - 9];
+    const uint64_t ey = (uint64_t)(hi[1] - lo[1] + 1), ez = (uint64_t)(hi[2] - lo[2] + 1);
+    const uint64_t vol = (uint64_t)(hi[0] - lo[0] + 1) * ey * ez;
+    const bool by_list = everywhere || vol > p.nb;
+    const uint64_t n_it = by_list ? p.nb : vol;
+    unsigned long long cnt = 0;
+    for (uint64_t i0 = 0; i0 < n_it; i0 += 64) {
+        const uint64_t i = i0 + lane;
+        bool hit = false;
+        uint32_t b = 0;
+        if (i < n_it) {
+            if (by_list) {
+                b = (uint32_t)i;
+                hit = everywhere;
+                if (!everywhere) {
+                    const uint64_t key = ub_key[i];
+                    const int32_t cz = (int32_t)(key % (uint64_t)g.bdim[2]);
+                    const uint64_t r = key / (uint64_t)g.bdim[2];
+                    const int32_t cy = (int32_t)(r % (uint64_t)g.bdim[1]), cx = (int32_t)(r / (uint64_t)g.bdim[1]);
+                    hit = cx >= lo[0] && cx <= hi[0] && cy >= lo[1] && cy <= hi[1] && cz >= lo[2] && cz <= hi[2];
+                }
+            } else {
+                const uint64_t r = i / ez;
+                const uint64_t key = dev_cell_key(g, lo[0] + (int32_t)(r / ey), lo[1] + (int32_t)(r % ey), lo[2] + (int32_t)(i % ez));
+                uint32_t l = 0, h = p.nb;
+                while (l < h) {
+                    const uint32_t mid = (l + h) >> 1;
+                    if (ub_key[mid] < key) l = mid + 1;
+                    else h = mid;
+                }
+                hit = l < p.nb && ub_key[l] == key;
+                b = l;
+            }
+        }
+        if (EMIT) {
+            const unsigned long long m = __ballot(hit);
+            if (m) {
+                unsigned long long base = 0;
+                if (lane == 0) base = atomicAdd(&ctr[DC_CURSOR], (unsigned long long)__popcll(m));
+                base = __shfl(base, 0);
+                const unsigned long long at = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+                if (hit && at < cap) pairs[at] = ((uint64_t)b << 32) | k;
+            }
+        } else {
+            cnt += hit ? 1ull : 0ull;
+        }
+    }
+    if (!EMIT) {
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+        if (lane == 0 && cnt) atomicAdd(&ctr[DC_PAIRS], cnt);
+    }
+}
+
+// keys[i] = the brick of row i's point, vals[i] = i
+__global__ __launch_bounds__(256) void k_dev_row_keys(const GridParams g, const Row* __restrict__ rows, const uint32_t n, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const Row& r = rows[i];
+    keys[i] = dev_cell_key(g, dev_cell(g, 0, (double)r.x), dev_cell(g, 1, (double)r.y), dev_cell(g, 2, (double)r.z));
+    vals[i] = i;
+}
+
+// flag[i] = sorted position i opens a brick (i < n); flag[n] = 0 for the scan
+__global__ __launch_bounds__(256) void k_dev_row_flags(const uint64_t* __restrict__ keys, const uint32_t n, uint32_t* __restrict__ flag)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i > n) return;
+    flag[i] = i < n && (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
+}
+
+// ub_key[b] / ub_start[b] = the key and first sorted position of brick b (base = the exclusive scan of flag); ub_start[nb] = n
+__global__ __launch_bounds__(256) void k_dev_bricks(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ base,
+                                                    const uint32_t n, const uint32_t nb, uint64_t* __restrict__ ub_key, uint32_t* __restrict__ ub_start)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i > n) return;
+    if (i == n) ub_start[nb] = n;
+    else if (flag[i]) ub_key[base[i]] = keys[i], ub_start[base[i]] = i;
+}
+
+// tstart[b] .. tend[b] = the sorted pairs of brick b (both arrays zeroed before: a brick without triangles keeps an empty range)
+__global__ __launch_bounds__(256) void k_dev_tri_ranges(const uint64_t* __restrict__ pairs, const uint32_t n, const uint32_t nb, uint32_t* __restrict__ tstart,
+                                                        uint32_t* __restrict__ tend)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t b = (uint32_t)(pairs[i] >> 32);
+    if (b >= nb) return;  // cannot happen: the pairs are k_dev_tris' own
+    if (i == 0 || (uint32_t)(pairs[i - 1] >> 32) != b) tstart[b] = i;
+    if (i + 1 == n || (uint32_t)(pairs[i + 1] >> 32) != b) tend[b] = i + 1;
+}
+
+// The contract's closest point of triangle t (12 doubles: A, B, C, N) to P: Q, the region's flag bits, and dd as the return value.
+__device__ __forceinline__ double dev_closest(const double (&P)[3], const double* __restrict__ t, double (&Q)[3], uint32_t& region)
+{
+    const double* A = t;
+    const double* B = t + 3;
+    const double* C = t + 6;
+    const double ab[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
+    const double ac[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]};
+    const double ap[3] = {P[0] - A[0], P[1] - A[1], P[2] - A[2]};
+    const double d1 = dev_dot(ab, ap), d2 = dev_dot(ac, ap);
+    region = kDevOnVertex;
+    bool done = false;
+    if (d1 <= 0.0 && d2 <= 0.0) {
+        Q[0] = A[0], Q[1] = A[1], Q[2] = A[2];
+        done = true;
+    }
+    double d3 = 0, d4 = 0, d5 = 0, d6 = 0, vc = 0, vb = 0;
+    if (!done) {
+        const double bp[3] = {P[0] - B[0], P[1] - B[1], P[2] - B[2]};
+        d3 = dev_dot(ab, bp), d4 = dev_dot(ac, bp);
+        if (d3 >= 0.0 && d4 <= d3) {
+            Q[0] = B[0], Q[1] = B[1], Q[2] = B[2];
+            done = true;
+        }
+    }
+    if (!done) {
+        vc = d1 * d4 - d3 * d2;
+        if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
+            const double v = d1 / (d1 - d3);
+            Q[0] = A[0] + v * ab[0], Q[1] = A[1] + v * ab[1], Q[2] = A[2] + v * ab[2];
+            region = kDevOnEdge;
+            done = true;
+        }
+    }
+    if (!done) {
+        const double cp[3] = {P[0] - C[0], P[1] - C[1], P[2] - C[2]};
+        d5 = dev_dot(ab, cp), d6 = dev_dot(ac, cp);
+        if (d6 >= 0.0 && d5 <= d6) {
+            Q[0] = C[0], Q[1] = C[1], Q[2] = C[2];
+            done = true;
+        }
+    }
+    if (!done) {
+        vb = d5 * d2 - d1 * d6;
+        if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
+            const double w = d2 / (d2 - d6);
+            Q[0] = A[0] + w * ac[0], Q[1] = A[1] + w * ac[1], Q[2] = A[2] + w * ac[2];
+            region = kDevOnEdge;
+            done = true;
+        }
+    }
+    if (!done) {
+        const double va = d3 * d6 - d5 * d4, e = d4 - d3, f = d5 - d6;
+        if (va <= 0.0 && e >= 0.0 && f >= 0.0) {
+            const double w = e / (e + f);
+            Q[0] = B[0] + w * (C[0] - B[0]), Q[1] = B[1] + w * (C[1] - B[1]), Q[2] = B[2] + w * (C[2] - B[2]);
+            region = kDevOnEdge;
+        } else {
+            const double s = (va + vb) + vc, v = vb / s, w = vc / s;
+            Q[0] = (A[0] + v * ab[0]) + w * ac[0], Q[1] = (A[1] + v * ab[1]) + w * ac[1], Q[2] = (A[2] + v * ab[2]) + w * ac[2];
+            region = 0u;
+        }
+    }
+    const double r[3] = {P[0] - Q[0], P[1] - Q[1], P[2] - Q[2]};
+    return dev_dot(r, r);
+}
+
+// One workgroup per brick that holds rows; a lane holds one row at a time.  The brick's triangles stream through LDS in tiles of
+// `tile` (<= kDevTileMax) and every lane reads them as broadcasts, in ascending index order; a strict "smaller" keeps the first of
+// equal dd.  The deviation record is written once per row; the summary is reduced per wave, then with vector atomics.
+__global__ __launch_bounds__(256) void k_dev_rows(const Row* __restrict__ rows, const uint32_t* __restrict__ srow, const uint32_t* __restrict__ ub_start,
+                                                  const uint32_t* __restrict__ tstart, const uint32_t* __restrict__ tend, const uint64_t* __restrict__ pairs,
+                                                  const DevTri* __restrict__ recs, const double md2, const uint32_t tile, Deviation* __restrict__ out,
+                                                  DevSummary* __restrict__ sum)
+{
+    __shared__ double s_tri[kDevTileMax * 12];
+    __shared__ uint32_t s_idx[kDevTileMax];
+    const uint32_t b = blockIdx.x;
+    const uint32_t r0 = ub_start[b], r1 = ub_start[b + 1];
+    const uint32_t t0 = tstart[b], t1 = tend[b];
+    unsigned long long n_found = 0, n_neg = 0;
+    long long sum_abs = 0, sum_sq = 0;
+    uint32_t max_bits = 0;
+    for (uint32_t rb = r0; rb < r1; rb += 256u) {
+        const uint32_t r = rb + threadIdx.x;
+        const bool have = r < r1;
+        uint32_t row = 0;
+        double P[3] = {0.0, 0.0, 0.0};
+        if (have) {
+            row = srow[r];
+            P[0] = (double)rows[row].x, P[1] = (double)rows[row].y, P[2] = (double)rows[row].z;
+        }
+        bool found = false, neg = false;
+        double best = 0.0, bq[3] = {0.0, 0.0, 0.0};
+        uint32_t btri = 0, breg = 0;
+        for (uint32_t tb = t0; tb < t1; tb += tile) {
+            const uint32_t nt = min(tile, t1 - tb);
+            __syncthreads();  // the previous tile is done with
+            if (threadIdx.x < nt) s_idx[threadIdx.x] = (uint32_t)pairs[tb + threadIdx.x];
+            __syncthreads();
+            for (uint32_t e = threadIdx.x; e < nt * 12u; e += 256u) s_tri[e] = ((const double*)recs)[(uint64_t)s_idx[e / 12u] * 12u + e % 12u];
+            __syncthreads();
+            if (have) {
+                for (uint32_t j = 0; j < nt; j++) {
+                    double Q[3];
+                    uint32_t region;
+                    const double dd = dev_closest(P, &s_tri[j * 12u], Q, region);
+                    if (dd <= md2 && (!found || dd < best)) {
+                        const double* N = &s_tri[j * 12u + 9u];
+                        const double rr[3] = {P[0] - Q[0], P[1] - Q[1], P[2] - Q[2]};
+                        found = true, best = dd, btri = s_idx[j], breg = region, neg = dev_dot(N, rr) < 0.0;
+                        bq[0] = Q[0], bq[1] = Q[1], bq[2] = Q[2];
+                    }
+                }
+            }
+        }
+        if (have) {
+            Deviation d;
+            if (found) {
+                d.distance = (float)sqrt(best);
+                d.signed_distance = neg ? -d.distance : d.distance;
+                d.tri = btri, d.flags = kDevFound | breg;
+                d.q[0] = (float)bq[0], d.q[1] = (float)bq[1], d.q[2] = (float)bq[2];
+                const double w = (double)d.distance;
+                n_found++;
+                n_neg += d.signed_distance < 0.f ? 1u : 0u;
+                max_bits = max(max_bits, __float_as_uint(d.distance));
+                sum_abs += llrint(w * 0x1p30);
+                sum_sq += llrint((w * w) * 0x1p30);
+            } else {
+                d.distance = d.signed_distance = d.q[0] = d.q[1] = d.q[2] = __uint_as_float(0x7FC00000u);
+                d.tri = 0xFFFFFFFFu, d.flags = 0u;
+            }
+            d.reserved = 0u;
+            out[row] = d;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        n_found += __shfl_down(n_found, o);
+        n_neg += __shfl_down(n_neg, o);
+        sum_abs += __shfl_down(sum_abs, o);
+        sum_sq += __shfl_down(sum_sq, o);
+        max_bits = max(max_bits, __shfl_down(max_bits, o));
+    }
+    if ((threadIdx.x & 63u) == 0 && n_found) {
+        atomicAdd(&sum->n_found, n_found);
+        if (n_neg) atomicAdd(&sum->n_negative, n_neg);
+        atomicAdd((unsigned long long*)&sum->sum_abs_q30, (unsigned long long)sum_abs);
+        atomicAdd((unsigned long long*)&sum->sum_sq_q30, (unsigned long long)sum_sq);
+        atomicMax(&sum->max_abs_bits, max_bits);
+    }
+}
+
 }  // namespace hfpf

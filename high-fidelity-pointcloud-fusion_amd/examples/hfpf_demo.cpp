@@ -2,8 +2,11 @@
 // synthetic sensor -> ~start -> N x PointCloud2 callbacks with tf poses -> periodic clean -> ~process ->
 // <dir>/test_cloud.pcd + <dir>/meta.csv.  Prints per-stage wall times.
 //
-//   hfpf_demo [--min-component N] <out_dir> [frames=30] [W=640] [H=480] [resolution=0.001] [clean_every=10] [seed=0xF051] [pose_seed=0x5E3]
+//   hfpf_demo [--min-component N] [--reference mesh.ply [--max-deviation metres]] <out_dir> [frames=30] [W=640] [H=480] [resolution=0.001] [clean_every=10] [seed=0xF051] [pose_seed=0x5E3]
 // --min-component N: ~process saves only the connected components (26-neighbourhood) of at least N rows (hfpf_node_set_component_filter).
+// --reference mesh.ply: ~process also writes deviation.csv and deviation_summary.csv, the saved cloud measured against that mesh
+//   (binary little-endian PLY in the fusion frame; hfpf_node_set_reference_mesh); --max-deviation is the largest distance looked for
+//   (default 10 voxels, at most 32).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -42,12 +45,17 @@ double now()
 int main(int argc, char** argv)
 {
     uint32_t min_component = 0;
-    if (argc > 2 && strcmp(argv[1], "--min-component") == 0) {
-        min_component = (uint32_t)strtoul(argv[2], nullptr, 0);
+    const char* reference = nullptr;
+    double max_deviation = 0.0;
+    while (argc > 2 && strncmp(argv[1], "--", 2) == 0) {
+        if (strcmp(argv[1], "--min-component") == 0) min_component = (uint32_t)strtoul(argv[2], nullptr, 0);
+        else if (strcmp(argv[1], "--reference") == 0) reference = argv[2];
+        else if (strcmp(argv[1], "--max-deviation") == 0) max_deviation = atof(argv[2]);
+        else break;
         argv += 2, argc -= 2;
     }
-    if (argc < 2) {
-        fprintf(stderr, "usage: hfpf_demo [--min-component N] <out_dir> [frames] [W] [H] [resolution] [clean_every] [seed] [pose_seed]\n");
+    if (argc < 2 || strncmp(argv[1], "--", 2) == 0) {
+        fprintf(stderr, "usage: hfpf_demo [--min-component N] [--reference mesh.ply [--max-deviation metres]] <out_dir> [frames] [W] [H] [resolution] [clean_every] [seed] [pose_seed]\n");
         return 2;
     }
     const std::string dir = argv[1];
@@ -83,6 +91,26 @@ int main(int argc, char** argv)
         co.min_rows = min_component;
         if (hfpf_node_set_component_filter(node, &co) != HFPF_OK) {
             fprintf(stderr, "component filter: %s\n", hfpf_node_last_error(node));
+            return 1;
+        }
+    }
+    if (reference) {
+        hfpf_mesh_vertex* mv = nullptr;
+        uint32_t* mt = nullptr;
+        uint64_t nmv = 0, nmt = 0;
+        if (hfpf_read_ply(reference, &mv, &nmv, &mt, &nmt) != HFPF_OK) {
+            fprintf(stderr, "reference: %s\n", hfpf_last_error(nullptr));
+            return 1;
+        }
+        hfpf_deviation_opts dopt;
+        memset(&dopt, 0, sizeof dopt);
+        dopt.struct_size = sizeof dopt;
+        dopt.max_distance = max_deviation > 0 ? max_deviation : 10.0 * (double)res;
+        const double ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+        const int rc = hfpf_node_set_reference_mesh(node, &dopt, mv, nmv, sizeof(hfpf_mesh_vertex), mt, nmt, ident);
+        hfpf_free_mesh(mv, mt);
+        if (rc != HFPF_OK) {
+            fprintf(stderr, "reference: %s\n", hfpf_node_last_error(node));
             return 1;
         }
     }

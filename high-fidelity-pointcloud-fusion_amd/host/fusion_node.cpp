@@ -4,8 +4,10 @@
 // node.cpp:218-263) and the transform/insert thread (updateStates, node.cpp:265-299) existed to overlap CPU work;
 // both stages are one GPU launch now, so the subscriber callback hands the message straight to hfpf_integrate
 // (which copies it to pinned staging and returns).  The clean thread (cleanGrid, node.cpp:301-325) is kept.
+#include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
@@ -33,6 +35,11 @@ struct hfpf_node {
     hfpf_mesh_opts mesh_opts{};
     bool comp_on = false;               // hfpf_node_set_component_filter: ~process saves the rows of the kept components only
     hfpf_component_opts comp_opts{};
+    bool ref_on = false;                // hfpf_node_set_reference_mesh: ~process also writes deviation.csv and deviation_summary.csv
+    hfpf_deviation_opts ref_opts{};
+    std::vector<float> ref_verts;       // packed x, y, z
+    std::vector<uint32_t> ref_tris;
+    double ref_pose[12] = {0};
     void* publish_user = nullptr;
     std::thread clean_thread;
     std::mutex cv_mtx;
@@ -211,6 +218,67 @@ int hfpf_node_reset(hfpf_node* n, hfpf_trigger_response* res)
     return HFPF_OK;
 }
 
+// deviation.csv and deviation_summary.csv beside the cloud: one line per saved row.  The compare runs on the full row set (with the
+// component filter's min_count when one is set); the saved rows are a subsequence of it in the same lexicographic order, so one walk
+// selects their records, and the row part of the summary is rebuilt from the selected records as include/hfpf.h defines it.
+static int write_deviation(hfpf_node* n, const hfpf_row* saved, uint64_t n_saved)
+{
+    hfpf_deviation_opts o = n->ref_opts;
+    if (n->comp_on) o.min_count = n->comp_opts.min_count;
+    hfpf_row* all = nullptr;
+    hfpf_deviation* dev = nullptr;
+    uint64_t n_all = 0;
+    hfpf_deviation_summary s;
+    int rc = hfpf_compare_mesh(n->grid, &o, n->ref_verts.data(), n->ref_verts.size() / 3, 12, n->ref_tris.data(), n->ref_tris.size() / 3, n->ref_pose,
+                               n->comp_on ? &all : nullptr, &dev, &n_all, &s);
+    if (rc != HFPF_OK) return rc;
+    FILE* f = fopen((n->directory_name + "/deviation.csv").c_str(), "w");
+    if (!f) rc = HFPF_ERR_IO;
+    if (f) {
+        fprintf(f, "ix,iy,iz,signed_distance,distance,tri,flags\n");
+        if (n->comp_on) s.n_rows = s.n_found = s.n_negative = 0, s.max_abs = 0.f, s.sum_abs_q30 = s.sum_sq_q30 = 0;
+        uint64_t j = 0;
+        for (uint64_t i = 0; i < n_saved && rc == HFPF_OK; i++) {
+            const hfpf_row& r = saved[i];
+            if (n->comp_on)
+                while (j < n_all && (all[j].ix != r.ix || all[j].iy != r.iy || all[j].iz != r.iz)) j++;
+            else j = i;
+            if (j >= n_all) {
+                rc = HFPF_ERR_STATE;  // cannot happen: both row sets come from one state of the grid
+                break;
+            }
+            const hfpf_deviation& d = dev[j];
+            fprintf(f, "%d,%d,%d,%.9g,%.9g,%u,%u\n", r.ix, r.iy, r.iz, d.signed_distance, d.distance, d.tri, d.flags);
+            if (n->comp_on) {
+                s.n_rows++;
+                if (d.flags & HFPF_DEV_FOUND) {
+                    const double w = (double)d.distance;
+                    s.n_found++;
+                    s.n_negative += d.signed_distance < 0.f ? 1 : 0;
+                    s.max_abs = std::max(s.max_abs, d.distance);
+                    s.sum_abs_q30 += (int64_t)llrint(w * 0x1p30);
+                    s.sum_sq_q30 += (int64_t)llrint((w * w) * 0x1p30);
+                }
+            }
+        }
+        const bool ok = !ferror(f);
+        if (fclose(f) != 0 || !ok) rc = rc == HFPF_OK ? HFPF_ERR_IO : rc;
+    }
+    if (rc == HFPF_OK) {
+        f = fopen((n->directory_name + "/deviation_summary.csv").c_str(), "w");
+        if (!f) rc = HFPF_ERR_IO;
+        else {
+            fprintf(f, "n_rows,n_found,n_negative,n_tris_valid,n_tris_invalid,max_abs,sum_abs_q30,sum_sq_q30\n%llu,%llu,%llu,%llu,%llu,%.9g,%lld,%lld\n",
+                    (unsigned long long)s.n_rows, (unsigned long long)s.n_found, (unsigned long long)s.n_negative, (unsigned long long)s.n_tris_valid,
+                    (unsigned long long)s.n_tris_invalid, s.max_abs, (long long)s.sum_abs_q30, (long long)s.sum_sq_q30);
+            const bool ok = !ferror(f);
+            if (fclose(f) != 0 || !ok) rc = HFPF_ERR_IO;
+        }
+    }
+    hfpf_free_deviation(all, dev);
+    return rc;
+}
+
 int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
 {
     if (!n) return HFPF_ERR_BAD_ARG;
@@ -236,6 +304,7 @@ int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
     if (rc == HFPF_OK) rc = hfpf_write_pcd(rows, nr, cloud_location.c_str());
     if (rc == HFPF_OK) rc = hfpf_write_meta_csv(rows, nr, meta_location.c_str());
     if (rc == HFPF_OK && n->publish) n->publish(n->publish_user, rows, nr, n->fusion_frame.c_str());  // processed_cloud_, node.cpp:158
+    if (rc == HFPF_OK && n->ref_on) rc = write_deviation(n, rows, nr);  // EXTENSION: the saved cloud measured against the reference mesh
     if (n->comp_on) hfpf_free_components(rows, labels, comps);
     else hfpf_free_rows(rows);
     if (rc == HFPF_OK && n->mesh_on) {  // EXTENSION: a triangle mesh of the same model next to the cloud
@@ -321,6 +390,29 @@ int hfpf_node_set_component_filter(hfpf_node* n, const hfpf_component_opts* opts
         n->comp_opts = *opts;
     }
     n->comp_on = opts != nullptr;
+    return HFPF_OK;
+}
+
+int hfpf_node_set_reference_mesh(hfpf_node* n, const hfpf_deviation_opts* opts, const void* verts, uint64_t n_verts, uint32_t vertex_stride,
+                                 const uint32_t* tris, uint64_t n_tris, const double* pose_3x4)
+{
+    if (!n) return HFPF_ERR_BAD_ARG;
+    if (!opts) {
+        n->ref_on = false;
+        n->ref_verts.clear(), n->ref_tris.clear();
+        return HFPF_OK;
+    }
+    bool ok = hfpf_check_deviation_opts(opts) == HFPF_OK && pose_3x4 && vertex_stride >= 12 && (vertex_stride & 3) == 0 && (verts || !n_verts) &&
+              (tris || !n_tris) && n_verts < 0xFFFFFFFFull && n_tris < 0xFFFFFFFFull;
+    for (int i = 0; ok && i < 12; i++) ok = std::isfinite(pose_3x4[i]);
+    if (!ok) return nfail(n, HFPF_ERR_BAD_ARG, "hfpf_node_set_reference_mesh: invalid options, mesh or pose");
+    std::vector<float> v(3 * n_verts);
+    for (uint64_t i = 0; i < n_verts; i++) memcpy(&v[3 * i], (const char*)verts + i * vertex_stride, 12);
+    n->ref_verts.swap(v);
+    n->ref_tris.assign(tris, tris + 3 * n_tris);
+    memcpy(n->ref_pose, pose_3x4, sizeof n->ref_pose);
+    n->ref_opts = *opts;
+    n->ref_on = true;
     return HFPF_OK;
 }
 

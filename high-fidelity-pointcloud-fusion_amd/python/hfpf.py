@@ -93,6 +93,7 @@ EXPORTS = [
     "hfpf_query", "hfpf_query_device", "hfpf_query_depth",
     "hfpf_extract_mesh", "hfpf_extract_mesh_device", "hfpf_free_mesh", "hfpf_write_ply", "hfpf_check_mesh_opts",
     "hfpf_check_component_opts", "hfpf_extract_components", "hfpf_extract_components_device", "hfpf_free_components",
+    "hfpf_check_deviation_opts", "hfpf_compare_mesh", "hfpf_compare_mesh_device", "hfpf_free_deviation", "hfpf_read_ply",
     "hfpf_check_raycast_opts", "hfpf_raycast", "hfpf_raycast_device", "hfpf_raycast_view", "hfpf_raycast_view_device",
     "hfpf_snapshot", "hfpf_free_snapshot", "hfpf_restore", "hfpf_save", "hfpf_load", "hfpf_snapshot_info", "hfpf_config_from_snapshot",
 ]
@@ -284,6 +285,59 @@ def component_opts(reach=1, min_count=0.0, min_normal_dot=-2.0, min_rows=0, min_
 def check_component_opts(o):
     """hfpf_check_component_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
     return lib().hfpf_check_component_opts(C.byref(o) if o is not None else None)
+
+
+class DeviationOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("min_count", C.c_double), ("max_distance", C.c_double),
+                ("reserved", C.c_uint64)]
+
+
+class DeviationSummary(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_found", C.c_uint64), ("n_negative", C.c_uint64), ("n_tris_valid", C.c_uint64),
+                ("n_tris_invalid", C.c_uint64), ("max_abs", C.c_float), ("pad", C.c_uint32), ("sum_abs_q30", C.c_int64),
+                ("sum_sq_q30", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# hfpf_deviation and its flags (include/hfpf.h)
+DEV_FOUND, DEV_ON_EDGE, DEV_ON_VERTEX = 1, 2, 4
+DEVIATION_DTYPE = np.dtype([("signed_distance", "<f4"), ("distance", "<f4"), ("tri", "<u4"), ("flags", "<u4"), ("q", "<f4", (3,)),
+                            ("reserved", "<u4")])
+assert DEVIATION_DTYPE.itemsize == 32
+
+
+def deviation_opts(min_count=0.0, max_distance=0.01):
+    """An hfpf_deviation_opts: the count gate of the row set and the largest distance (metres, at most 32 voxels) a winner may have."""
+    o = DeviationOpts()
+    o.struct_size = C.sizeof(DeviationOpts)
+    o.min_count, o.max_distance = float(min_count), float(max_distance)
+    return o
+
+
+def check_deviation_opts(o):
+    """hfpf_check_deviation_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
+    return lib().hfpf_check_deviation_opts(C.byref(o) if o is not None else None)
+
+
+def read_ply(path):
+    """hfpf_read_ply: (vertices of MESH_VERTEX_DTYPE, (n, 3) uint32 triangles) of a binary little-endian PLY (host code, no GPU
+    needed); HfpfError with the reader's message otherwise."""
+    v, nv, t, nt = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+    rc = lib().hfpf_read_ply(os.fsencode(str(path)), C.byref(v), C.byref(nv), C.byref(t), C.byref(nt))
+    if rc != 0:
+        raise HfpfError(rc, (lib().hfpf_last_error(None) or b"").decode())
+    try:
+        verts = np.empty(nv.value, MESH_VERTEX_DTYPE)
+        tris = np.empty((nt.value, 3), np.uint32)
+        if nv.value:
+            C.memmove(verts.ctypes.data, v.value, verts.nbytes)
+        if nt.value:
+            C.memmove(tris.ctypes.data, t.value, tris.nbytes)
+    finally:
+        lib().hfpf_free_mesh(v, t)
+    return verts, tris
 
 
 # hfpf_raycast_opts.flags, hfpf_ray_hit.flags, hfpf_ray and hfpf_ray_hit (include/hfpf.h)
@@ -500,6 +554,13 @@ def lib():
         fn.argtypes = [vp, C.POINTER(ComponentOpts), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64)]
     L.hfpf_free_components.argtypes = [vp, vp, vp]
     L.hfpf_free_components.restype = None
+    L.hfpf_check_deviation_opts.argtypes = [C.POINTER(DeviationOpts)]
+    for fn in (L.hfpf_compare_mesh, L.hfpf_compare_mesh_device):
+        fn.argtypes = [vp, C.POINTER(DeviationOpts), vp, u64, u32, vp, u64, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64),
+                       C.POINTER(DeviationSummary)]
+    L.hfpf_free_deviation.argtypes = [vp, vp]
+    L.hfpf_free_deviation.restype = None
+    L.hfpf_read_ply.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64)]
     dbl = C.c_double
     L.hfpf_check_raycast_opts.argtypes = [C.POINTER(RaycastOpts)]
     L.hfpf_raycast.argtypes = [vp, C.POINTER(RaycastOpts), vp, u64, vp, vp]
@@ -877,6 +938,42 @@ class OccupancyGrid:
         finally:
             lib().hfpf_free_components(r, l, c)
         return out, labels, comps
+
+    # -- deviation from a triangle mesh --
+    def compare_mesh(self, verts, tris, pose=None, device=False, opts=None, rows=False, n_verts=None, vertex_stride=None, n_tris=None, **kw):
+        """How far the model's rows are from a triangle mesh (hfpf_compare_mesh): (dev of DEVIATION_DTYPE, summary dict), or (rows of
+        ROW_DTYPE, dev, summary) with rows=True.  verts: MESH_VERTEX_DTYPE vertices (stride 32) or an (n, 3) float32 array (stride 12;
+        vertex_stride overrides); tris: (n, 3) uint32; pose: 3x4 [R|t] mesh frame -> fusion frame (identity by default).  Keywords as
+        deviation_opts().  device=True runs hfpf_compare_mesh_device: verts and tris are device pointers (n_verts, vertex_stride and
+        n_tris are then required) and the result is (rows pointer or 0, dev pointer, n_rows, summary); free the pointers with
+        device_free (they are 0 without rows)."""
+        o = opts if opts is not None else deviation_opts(**kw)
+        pose = np.ascontiguousarray(np.eye(4)[:3] if pose is None else pose, np.float64).reshape(12)
+        r, d, nr, s = C.c_void_p(), C.c_void_p(), C.c_uint64(), DeviationSummary()
+        rp = C.byref(r) if rows else None
+        if device:
+            self._chk(lib().hfpf_compare_mesh_device(self._h, C.byref(o), C.c_void_p(verts), int(n_verts), int(vertex_stride), C.c_void_p(tris),
+                                                     int(n_tris), _p(pose), rp, C.byref(d), C.byref(nr), C.byref(s)))
+            return r.value or 0, d.value or 0, nr.value, s.as_dict()
+        verts = np.ascontiguousarray(verts)
+        if verts.dtype != MESH_VERTEX_DTYPE:
+            verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+        stride = int(vertex_stride) if vertex_stride is not None else verts.dtype.itemsize * (1 if verts.dtype == MESH_VERTEX_DTYPE else 3)
+        nv = int(n_verts) if n_verts is not None else len(verts)
+        nt = int(n_tris) if n_tris is not None else len(tris)
+        self._chk(lib().hfpf_compare_mesh(self._h, C.byref(o), _p(verts) if verts.nbytes else None, nv, stride, _p(tris) if tris.nbytes else None, nt,
+                                          _p(pose), rp, C.byref(d), C.byref(nr), C.byref(s)))
+        try:
+            dev = np.empty(nr.value, DEVIATION_DTYPE)
+            out_rows = np.empty(nr.value, ROW_DTYPE) if rows else None
+            if nr.value:
+                C.memmove(dev.ctypes.data, d.value, dev.nbytes)
+                if rows:
+                    C.memmove(out_rows.ctypes.data, r.value, out_rows.nbytes)
+        finally:
+            lib().hfpf_free_deviation(r, d)
+        return (out_rows, dev, s.as_dict()) if rows else (dev, s.as_dict())
 
     # -- casting rays against the model --
     def raycast(self, rays, pose, opts=None, **kw):

@@ -16,7 +16,8 @@ TF_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_d
 EXPORTS = ["hfpf_node_default_params", "hfpf_node_create", "hfpf_node_destroy", "hfpf_node_last_error", "hfpf_node_on_point_cloud",
            "hfpf_node_start", "hfpf_node_stop", "hfpf_node_reset", "hfpf_node_process", "hfpf_node_clean_now", "hfpf_node_grid",
            "hfpf_node_get_stats", "hfpf_node_set_publisher", "hfpf_node_on_depth_image",
-           "hfpf_node_set_mesh_output", "hfpf_node_save_session", "hfpf_node_load_session", "hfpf_node_set_component_filter"]
+           "hfpf_node_set_mesh_output", "hfpf_node_save_session", "hfpf_node_load_session", "hfpf_node_set_component_filter",
+           "hfpf_node_set_reference_mesh"]
 
 
 class Params(C.Structure):
@@ -66,6 +67,8 @@ def lib():
         L.hfpf_node_set_publisher.argtypes = [C.c_void_p, PUBLISH_FN, C.c_void_p]
         L.hfpf_node_set_mesh_output.argtypes = [C.c_void_p, C.POINTER(hfpf.MeshOpts)]
         L.hfpf_node_set_component_filter.argtypes = [C.c_void_p, C.POINTER(hfpf.ComponentOpts)]
+        L.hfpf_node_set_reference_mesh.argtypes = [C.c_void_p, C.POINTER(hfpf.DeviationOpts), C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                                   C.c_uint64, C.c_void_p]
         L.hfpf_node_save_session.argtypes = [C.c_void_p, C.c_char_p]
         L.hfpf_node_load_session.argtypes = [C.c_void_p, C.c_char_p]
         _lib = L
@@ -187,6 +190,25 @@ class FusionNode:
         keywords); set_component_filter(None) with no keywords turns it off."""
         o = opts if opts is not None else (hfpf.component_opts(**kw) if kw else None)
         rc = lib().hfpf_node_set_component_filter(self._h, C.byref(o) if o is not None else None)
+        if rc < 0:
+            raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
+
+    def set_reference_mesh(self, verts=None, tris=None, pose=None, opts=None, **kw):
+        """~process also writes deviation.csv and deviation_summary.csv: the saved cloud against this mesh (hfpf.MESH_VERTEX_DTYPE or
+        (n, 3) float32 vertices, (n, 3) uint32 triangles, a 3x4 pose mesh frame -> fusion frame, identity by default; options as
+        hfpf.deviation_opts).  set_reference_mesh() with no mesh turns it off."""
+        if verts is None:
+            rc = lib().hfpf_node_set_reference_mesh(self._h, None, None, 0, 12, None, 0, None)
+        else:
+            o = opts if opts is not None else hfpf.deviation_opts(**kw)
+            verts = np.ascontiguousarray(verts)
+            if verts.dtype != hfpf.MESH_VERTEX_DTYPE:
+                verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+            stride = 32 if verts.dtype == hfpf.MESH_VERTEX_DTYPE else 12
+            tris = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+            pose = np.ascontiguousarray(np.eye(4)[:3] if pose is None else pose, np.float64).reshape(12)
+            rc = lib().hfpf_node_set_reference_mesh(self._h, C.byref(o), verts.ctypes.data_as(C.c_void_p), len(verts), stride,
+                                                    tris.ctypes.data_as(C.c_void_p), len(tris), pose.ctypes.data_as(C.c_void_p))
         if rc < 0:
             raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
 

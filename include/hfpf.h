@@ -717,6 +717,114 @@ void hfpf_free_components(hfpf_row* rows, uint32_t* labels, hfpf_component* comp
 int hfpf_extract_components_device(hfpf_handle* h, const hfpf_component_opts* o, hfpf_row** dev_rows, uint32_t** dev_labels, uint64_t* n_rows,
                                    hfpf_component** dev_comps, uint64_t* n_comps);
 
+/* ---- deviation of the fused model from a triangle mesh (no reference counterpart) -----------------------------------------------
+ * How far is what was scanned from what it should be: for every row of the model, the closest point of a reference surface (a CAD
+ * model, an earlier scan's mesh.ply, hfpf_extract_mesh's own output) and the signed distance to it.  Everything is restatable from
+ * hfpf_extract_filtered's rows (tests/deviation_ref.py).
+ * Arithmetic: everything below is f64, one rounding per operation, left to right, never contracted.
+ *   dot(u, v) = (u.x*v.x + u.y*v.y) + u.z*v.z; vector sums and differences per component.
+ * Mesh: n_verts vertices, three packed f32 x, y, z at verts + i * vertex_stride (vertex_stride >= 12, a multiple of 4; 32 takes an
+ *   hfpf_mesh_vertex array as hfpf_extract_mesh* returns it); 3 * n_tris u32 indices; pose_3x4 = row-major [R|t] from the mesh frame
+ *   to the fusion frame.  Vertex coordinate a becomes V[a] = ((T[4a]*x + T[4a+1]*y) + T[4a+2]*z) + T[4a+3], x, y, z widened, V kept
+ *   in f64 (not rounded back).
+ * Valid triangles: triangle k with vertices A, B, C is VALID iff its three indices are < n_verts, its nine transformed coordinates
+ *   are finite and NN = dot(N, N) is finite and > 0, where ab = B - A, ac = C - A,
+ *   N = (ab.y*ac.z - ab.z*ac.y, ab.z*ac.x - ab.x*ac.z, ab.x*ac.y - ab.y*ac.x).  Invalid triangles are skipped and counted.  The
+ *   device rejects an index out of range before it loads anything through it: a mesh in HBM is untrusted input.
+ * Row set: the rows hfpf_extract_filtered would return at this point of the call sequence with the same min_count, in lexicographic
+ *   (ix, iy, iz) order; host frames still waiting are launched first.  Row j has P = ((double)x, (double)y, (double)z).
+ * Closest point Q of a valid triangle to P: the seven-region construction, the branches taken in exactly this order:
+ *   ap = P-A; d1 = dot(ab,ap); d2 = dot(ac,ap);          d1<=0 && d2<=0            -> Q = A                             (VERTEX)
+ *   bp = P-B; d3 = dot(ab,bp); d4 = dot(ac,bp);          d3>=0 && d4<=d3           -> Q = B                             (VERTEX)
+ *   vc = d1*d4 - d3*d2;                                  vc<=0 && d1>=0 && d3<=0   -> v = d1/(d1-d3); Q = A + v*ab      (EDGE)
+ *   cp = P-C; d5 = dot(ab,cp); d6 = dot(ac,cp);          d6>=0 && d5<=d6           -> Q = C                             (VERTEX)
+ *   vb = d5*d2 - d1*d6;                                  vb<=0 && d2>=0 && d6<=0   -> w = d2/(d2-d6); Q = A + w*ac      (EDGE)
+ *   va = d3*d6 - d5*d4; e = d4-d3; f = d5-d6;            va<=0 && e>=0 && f>=0     -> w = e/(e+f);    Q = B + w*(C-B)   (EDGE)
+ *   otherwise  s = (va+vb)+vc; v = vb/s; w = vc/s;                                    Q = (A + v*ab) + w*ac             (FACE)
+ *   r = P - Q, dd = dot(r, r).  The triangle is KEPT iff dd <= max_distance * max_distance (a NaN compares false).
+ * Winner: the kept triangle with the smallest dd; ties go to the smallest triangle index, so the result depends on neither scheduling
+ *   nor the acceleration structure.  With a winner: distance = (float)sqrt(dd); signed_distance = dot(N, r) < 0 ? -distance :
+ *   distance (positive on the side the face's winding looks to); q = (float)Q per axis; tri = k; flags = HFPF_DEV_FOUND |
+ *   (HFPF_DEV_ON_EDGE or HFPF_DEV_ON_VERTEX by region).  Without one: distance, signed_distance and q are NaN (0x7FC00000),
+ *   tri = 0xFFFFFFFF, flags = 0.  reserved is 0 either way.
+ *   LIMITATION: on an edge or vertex region the sign is the winning face's, not that of an angle-weighted pseudo-normal, so next to a
+ *   sharp convex or concave edge a row can get the wrong sign.  The two flag bits exist so that a caller can tell.
+ * Summary: integer and max reductions only, nothing depends on order.  The two sums are taken over the found rows from the f32
+ *   distance of the output, widened: sum_abs_q30 = sum of rint((double)distance * 2^30), sum_sq_q30 = sum of
+ *   rint(((double)distance * (double)distance) * 2^30).  max_distance <= 1 m (below), so 2^31 rows keep either under 2^61.
+ * A call changes nothing on the handle except device_bytes (its scratch).  Rejected with HFPF_ERR_BAD_ARG (the handle stays usable,
+ * nothing is written): what hfpf_check_deviation_opts rejects (struct_size != sizeof, flags or reserved != 0, min_count NaN,
+ * max_distance not finite, not > 0 or > 1); max_distance > 32 * res (res = hfpf_get_dims' resolution: the bound that keeps the brick
+ * search finite); a NULL or non-finite pose; vertex_stride < 12 or not a multiple of 4; NULL verts with n_verts != 0 or NULL tris with
+ * n_tris != 0; n_verts or n_tris >= 2^32 - 1; NULL dev, n_rows or summary (rows may be NULL: not produced); for the device form verts
+ * or tris not 4-byte aligned.  n_tris = 0 returns HFPF_OK with the row set and no row found; an empty handle, or one before its
+ * first clean pass, returns HFPF_OK with 0 rows and NULL arrays.  When the list of (triangle, brick) pairs the search needs does not
+ * fit (more than 2^32 - 2 pairs, or no memory for them) the call returns HFPF_ERR_CAPACITY, its message names the pair count, and the
+ * handle stays usable.  A handle with an RCCL communicator, or a failed handle, returns HFPF_ERR_STATE as the other readers do. */
+#define HFPF_DEV_FOUND 1u
+#define HFPF_DEV_ON_EDGE 2u
+#define HFPF_DEV_ON_VERTEX 4u
+
+typedef struct hfpf_deviation_opts {
+    uint32_t struct_size;        /* = sizeof(hfpf_deviation_opts) */
+    uint32_t flags;              /* 0 */
+    double min_count;            /* rows with count < min_count are not compared (0 keeps all) */
+    double max_distance;         /* metres, > 0, <= 32 * res and <= 1: triangles farther from a row are not its winner */
+    uint64_t reserved;           /* 0 */
+} hfpf_deviation_opts;
+
+typedef struct hfpf_deviation {  /* 32 bytes, one per row */
+    float signed_distance;       /* +-distance: positive on the side the winning face's winding looks to */
+    float distance;              /* (float)sqrt(dd) */
+    uint32_t tri;                /* the winning triangle, 0xFFFFFFFF without one */
+    uint32_t flags;              /* HFPF_DEV_* */
+    float q[3];                  /* the closest point, fusion frame */
+    uint32_t reserved;           /* 0 */
+} hfpf_deviation;
+
+typedef struct hfpf_deviation_summary {  /* 64 bytes */
+    uint64_t n_rows;             /* rows compared */
+    uint64_t n_found;            /* ... with a winner */
+    uint64_t n_negative;         /* found rows with signed_distance < 0 */
+    uint64_t n_tris_valid;
+    uint64_t n_tris_invalid;
+    float max_abs;               /* the largest distance, 0 without a found row */
+    uint32_t pad;                /* 0 */
+    int64_t sum_abs_q30;
+    int64_t sum_sq_q30;
+} hfpf_deviation_summary;
+
+#ifdef __cplusplus
+static_assert(sizeof(hfpf_deviation_opts) == 32, "hfpf_deviation_opts is 32 bytes");
+static_assert(sizeof(hfpf_deviation) == 32, "hfpf_deviation is 32 bytes");
+static_assert(sizeof(hfpf_deviation_summary) == 64, "hfpf_deviation_summary is 64 bytes");
+#else
+_Static_assert(sizeof(hfpf_deviation_opts) == 32, "hfpf_deviation_opts is 32 bytes");
+_Static_assert(sizeof(hfpf_deviation) == 32, "hfpf_deviation is 32 bytes");
+_Static_assert(sizeof(hfpf_deviation_summary) == 64, "hfpf_deviation_summary is 64 bytes");
+#endif
+
+/* HFPF_OK if o passes the checks above that need no handle, else HFPF_ERR_BAD_ARG (host code; the node shell uses it too). */
+int hfpf_check_deviation_opts(const hfpf_deviation_opts* o);
+/* Mesh, pose and outputs in HOST memory: *dev (and *rows when rows != NULL: the row set itself) hold *n_rows entries and are freed by
+ * hfpf_free_deviation. */
+int hfpf_compare_mesh(hfpf_handle* h, const hfpf_deviation_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride,
+                      const uint32_t* tris, uint64_t n_tris, const double* pose_3x4, hfpf_row** rows, hfpf_deviation** dev, uint64_t* n_rows,
+                      hfpf_deviation_summary* summary);
+void hfpf_free_deviation(hfpf_row* rows, hfpf_deviation* dev);
+/* The mesh is read in place from DEVICE memory (HBM); *dev_rows and *dev_dev are device arrays, each freed by hfpf_device_free(h, p).
+ * pose_3x4 and summary are in host memory. */
+int hfpf_compare_mesh_device(hfpf_handle* h, const hfpf_deviation_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride,
+                             const uint32_t* dev_tris, uint64_t n_tris, const double* pose_3x4, hfpf_row** dev_rows, hfpf_deviation** dev_dev,
+                             uint64_t* n_rows, hfpf_deviation_summary* summary);
+/* The inverse of hfpf_write_ply (host code, no GPU needed): *verts (n_verts) and *tris (3 * n_tris indices), freed by hfpf_free_mesh.
+ * Accepts format binary_little_endian 1.0 only.  The vertex element must have float x, y, z; float nx, ny, nz and uchar red, green,
+ * blue are optional (absent fields are 0; count is always 0); any other scalar property is skipped by its size.  The face element is
+ * one list uchar uint|int vertex_indices with exactly 3 entries per face.  Other elements may follow the two, none may precede them.
+ * Anything else is HFPF_ERR_IO with a message from hfpf_last_error(NULL).  The counts are checked against the bytes the file has
+ * left before anything is allocated. */
+int hfpf_read_ply(const char* path, hfpf_mesh_vertex** verts, uint64_t* n_verts, uint32_t** tris, uint64_t* n_tris);
+
 /* <directory_name>/test_cloud.pcd (node.cpp:395): PCD v0.7 ASCII, FIELDS x y z rgb normal_x normal_y normal_z curvature */
 int hfpf_write_pcd(const hfpf_row* rows, uint64_t n_rows, const char* path);
 /* <directory_name>/meta.csv (node.cpp:396) with the header string of grid.hpp:462 */
@@ -755,7 +863,7 @@ int hfpf_get_occupied(hfpf_handle* h, int32_t* xyz, uint64_t cap, uint64_t* n_ou
  * WHAT A RESTORE IS.  hfpf_clear followed by putting that state in place.  Afterwards the handle is indistinguishable from the
  * source handle at the moment of the snapshot, in this sense:
  *   1. every read-only call (extract, extract_filtered, get_occupied, is_dirty, render*, query*, extract_mesh*, raycast*, track*,
- *      extract_components*)
+ *      extract_components*, compare_mesh*)
  *      returns byte-identical output;
  *   2. any continuation (integrate*, clean, extract, clear, automatic frame ids included) produces byte-identical rows and occupied
  *      lists to the same continuation on the source handle;
@@ -870,7 +978,9 @@ int hfpf_device_copy(hfpf_handle* h, void* dev_dst, const void* dev_src, uint64_
  * 2 = k_integrate, 3 = k_update_cells / k_update, 4 = k_buffer (three more event records per call: use it for a breakdown
  * pass, not for the headline timing).  5 = k_raycast launches of hfpf_raycast* (the march alone, without the empty-space maps and
  * the copies; any enable).  6 = the component kernels of one hfpf_extract_components* call (index to compaction, the scans' read-backs
- * included, without the row set and the copies; any enable).  total_ms / launches accumulate since enable. */
+ * included, without the row set and the copies; any enable).  7 = the compare kernels of one hfpf_compare_mesh* call (binning to
+ * the row kernel, the read-backs of the sizes included, without the row set and the copies; any enable).  total_ms / launches
+ * accumulate since enable. */
 int hfpf_kernel_timing(hfpf_handle* h, int enable);
 int hfpf_get_kernel_time(hfpf_handle* h, int kernel_id, double* total_ms, uint64_t* launches);
 

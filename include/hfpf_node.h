@@ -100,6 +100,17 @@ int hfpf_node_set_mesh_output(hfpf_node* n, const hfpf_mesh_opts* opts);
  * was. */
 int hfpf_node_set_component_filter(hfpf_node* n, const hfpf_component_opts* opts);
 
+/* EXTENSION: with a reference mesh set, ~process also measures the saved cloud against it (hfpf_compare_mesh of include/hfpf.h) and
+ * writes, beside test_cloud.pcd, deviation.csv (header ix,iy,iz,signed_distance,distance,tri,flags, then one line per row of the saved
+ * cloud, floats as %.9g) and deviation_summary.csv (one header line, one value line: n_rows, n_found, n_negative, n_tris_valid,
+ * n_tris_invalid, max_abs, sum_abs_q30, sum_sq_q30).  The mesh (arguments as hfpf_compare_mesh's, host memory) and the pose are
+ * copied.  With a component filter set the lines are those of the kept rows: the compare runs on the full row set with the filter's
+ * min_count (opts->min_count is then ignored), the kept rows' records are selected and the row part of the summary is rebuilt from
+ * them.  NULL opts turns it off again, the default.  Invalid arguments are refused with HFPF_ERR_BAD_ARG and leave the setting as it
+ * was; max_distance against the grid's resolution is checked by ~process, which then fails as hfpf_compare_mesh does. */
+int hfpf_node_set_reference_mesh(hfpf_node* n, const hfpf_deviation_opts* opts, const void* verts, uint64_t n_verts, uint32_t vertex_stride,
+                                 const uint32_t* tris, uint64_t n_tris, const double* pose_3x4);
+
 /* EXTENSION: keep the grid's session in a file and take it up again (hfpf_save / hfpf_load of include/hfpf.h on the node's grid, with
  * their errors).  Both run under the grid's own lock, so they are legal while the cloud callback and the clean thread run: a frame
  * or a clean pass lands wholly before or wholly after them.  Loading replaces the fused data only: the node stays started or stopped
