@@ -41,9 +41,15 @@ namespace {
 
 thread_local std::string g_create_error;  // last error of a call that has no handle (create, dist_unique_id)
 
+// A lazily grown device buffer (scratch()).  It registers itself with its handle (hfpf_handle::bufs), which is how hfpf_destroy
+// finds it: the handle is never copied or moved, so the address stays good.
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    explicit DevBuf(std::vector<DevBuf*>& registry) { registry.push_back(this); }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    friend void swap(DevBuf& a, DevBuf& b) { std::swap(a.p, b.p), std::swap(a.bytes, b.bytes); }  // the memory changes hands, the registrations stay
 };
 
 struct StageSlot {  // pose / frame-id staging for one in-flight integrate call: n poses (12 doubles each), then n frame ids -- ONE upload
@@ -245,7 +251,15 @@ struct Session {
     uint64_t frames_exported = 0, frames_seen = 0;  // frame_list entries already exchanged / as of the last export
 };
 
-using EventPairs = std::vector<std::pair<hipEvent_t, hipEvent_t>>;
+// Kernel timing (hfpf_get_kernel_time): one row per public kernel id.  Ids 0, 1, 5, 6, 7 bracket work with an event pair (Timed
+// below) that waits in `pending` until resolve_timing adds it to the sums; ids 2..4 use the rows for their sums only (their events
+// are hfpf_handle::ev_detail).
+constexpr int kTimeIntegrate = 0, kTimeClean = 1, kTimeDetail = 2, kTimeRaycast = 5, kTimeComponents = 6, kTimeCompare = 7, kTimedIds = 8;
+struct TimedId {
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+    double ms = 0;
+    uint64_t n = 0;
+};
 
 }  // namespace
 
@@ -287,7 +301,8 @@ struct hfpf_handle {
     unsigned long long* h_ctr = nullptr;      // pinned mirror of the counters
     unsigned long long* h_log_ctr = nullptr;  // pinned mirror of the region counters
     unsigned long long* mbox = nullptr;       // coherent pinned mailbox k_publish_counters writes (null with HFPF_MAILBOX=0)
-    DevBuf pend_a, pend_b;  // the gate's pending-cell lists (Session::pend_valid)
+    std::vector<DevBuf*> bufs;  // every DevBuf below, in declaration order (DevBuf's constructor): what hfpf_destroy frees
+    DevBuf pend_a{bufs}, pend_b{bufs};  // the gate's pending-cell lists (Session::pend_valid)
     StageSlot stage[kStageSlots];
     FrameSlot fslot[kFrameSlots];
     // Device side of the host-frame path: ONE allocation of kFrameSlots slots, ring_cap bytes apart, so that consecutive slots
@@ -302,31 +317,33 @@ struct hfpf_handle {
     void* xfer_pin[2] = {nullptr, nullptr};  // pinned staging of extract's row download (two chunks in flight)
     hipEvent_t xfer_ev[2] = {nullptr, nullptr};
     StagePool* stage_pool = nullptr;  // created by the first large bounce copy (knobs.stage_threads helpers)
-    DevBuf sort_tmp, keys_a, keys_b, vals_a, vals_b, rows_dev, probe_a, probe_b, probe_c, probe_d, probe_e, probe_f;
-    DevBuf zbuf, render_pose, render_out;  // hfpf_render*: z-buffers of one chunk of views, the views' poses, hfpf_render's device planes
-    DevBuf track_in, track_acc;            // hfpf_track*: a host frame's device copy, the 30 int64 sums of one iteration
-    DevBuf query_in, query_out;            // hfpf_query*: a host cloud chunk or depth image, one chunk's hits and rows
+    DevBuf sort_tmp{bufs}, keys_a{bufs}, keys_b{bufs}, vals_a{bufs}, vals_b{bufs}, rows_dev{bufs};
+    DevBuf probe_a{bufs}, probe_b{bufs}, probe_c{bufs}, probe_d{bufs}, probe_e{bufs}, probe_f{bufs};
+    DevBuf result_out{bufs};  // the host forms of the read-outs that return arrays: the device arrays of one call (result_alloc)
+    DevBuf zbuf{bufs}, render_pose{bufs}, render_out{bufs};  // hfpf_render*: z-buffers of one chunk of views, the views' poses, hfpf_render's device planes
+    DevBuf track_in{bufs}, track_acc{bufs};                  // hfpf_track*: a host frame's device copy, the 30 int64 sums of one iteration
+    DevBuf query_in{bufs}, query_out{bufs};                  // hfpf_query*: a host cloud chunk or depth image, one chunk's hits and rows
     // hfpf_extract_mesh*: cube and corner keys, per corner s / record / marks / vertex counts and bases, per cube triangle counts and
-    // bases, the host form's output, a unique count
-    DevBuf mesh_cube, mesh_corner, mesh_kdata, mesh_cdata, mesh_out, mesh_ctr;
+    // bases, a unique count
+    DevBuf mesh_cube{bufs}, mesh_corner{bufs}, mesh_kdata{bufs}, mesh_cdata{bufs}, mesh_ctr{bufs};
     // hfpf_extract_components*: record -> row, the per-row words (parent, root, component, flags and bases), the component records and
-    // their keep flags, ranks and bases, the host form's output
-    DevBuf comp_index, comp_rows, comp_recs, comp_out;
+    // their keep flags, ranks and bases
+    DevBuf comp_index{bufs}, comp_rows{bufs}, comp_recs{bufs};
     // hfpf_compare_mesh*: the host form's mesh, the transformed vertices and triangle records, the bricks' keys / ranges / counters /
-    // summary, the (brick, triangle) pairs (unsorted and sorted), the host form's output
-    DevBuf dev_mesh, dev_tri, dev_bins, dev_pairs, dev_out;
-    DevBuf ray_in, ray_out, ray_map;       // hfpf_raycast*: a host chunk's rays, a chunk's (or band's) hits, the empty-space maps
-    DevBuf snap_stage, snap_err;           // hfpf_snapshot / hfpf_restore: the staging buffer (or one window of it), the range check's error word
+    // summary, the (brick, triangle) pairs (unsorted and sorted)
+    DevBuf dev_mesh{bufs}, dev_tri{bufs}, dev_bins{bufs}, dev_pairs{bufs};
+    DevBuf ray_in{bufs}, ray_out{bufs}, ray_map{bufs};  // hfpf_raycast*: a host chunk's rays, a chunk's (or band's) hits, the empty-space maps
+    DevBuf snap_stage{bufs}, snap_err{bufs};            // hfpf_snapshot / hfpf_restore: the staging buffer (or one window of it), the range check's error word
     uint64_t bin_pool = 0;           // entries in bin_pt
-    DevBuf bin_pt_buf, bin_rgb_buf, bin_sums;
-    DevBuf ovf_pt_buf, ovf_aux_buf;  // overflow list of one integrate launch (points that found no room in a bin)
+    DevBuf bin_pt_buf{bufs}, bin_rgb_buf{bufs}, bin_sums{bufs};
+    DevBuf ovf_pt_buf{bufs}, ovf_aux_buf{bufs};  // overflow list of one integrate launch (points that found no room in a bin)
     // multi-GPU: RCCL is resolved at run time so a single-GPU user needs no librccl
     bool dist_on = false;
     int rank = 0, world = 1;
     void* rccl_lib = nullptr;
     void* comm = nullptr;  // ncclComm_t
     uint64_t ex_cap_records = 0;  // records the exchange buffers hold per rank; kept EQUAL on every rank (same initial value, same growth rule)
-    DevBuf ex_send, ex_recv, ex_counts, stats_total;
+    DevBuf ex_send{bufs}, ex_recv{bufs}, ex_counts{bufs}, stats_total{bufs};
     unsigned long long* h_counts = nullptr;  // pinned, world entries
 
     // ---- kernel timing ----
@@ -334,23 +351,10 @@ struct hfpf_handle {
     bool timing_detail = false;  // hfpf_kernel_timing(h, 2): also one event pair per kernel of an integrate call (ids 2..4)
     std::vector<hipEvent_t> ev_detail;  // 4 events per call: before k_integrate, after it, after k_update*, after k_buffer
     std::vector<uint8_t> ev_detail_ran;  // per call: bit k = the kernel between events k and k + 1 was launched
-    double t_detail_ms[3] = {0, 0, 0};
-    uint64_t n_detail[3] = {0, 0, 0};
-    EventPairs ev_pending, ev_pending_clean;
-    EventPairs ev_pending_ray;  // one pair per k_raycast / k_raycast_view launch (id 5)
-    double t_ray_ms = 0;
-    uint64_t n_ray_timed = 0;
-    EventPairs ev_pending_comp;  // one pair per hfpf_extract_components* call (id 6)
-    double t_comp_ms = 0;
-    uint64_t n_comp_timed = 0;
-    EventPairs ev_pending_dev;  // one pair per hfpf_compare_mesh* call (id 7)
-    double t_dev_ms = 0;
-    uint64_t n_dev_timed = 0;
-    double t_clean_ms = 0;
-    uint64_t n_clean_timed = 0;
-    std::vector<hipEvent_t> ev_free;
-    double t_integrate_ms = 0;
-    uint64_t n_integrate_launches = 0;
+    // One pair per: integrate launch (id 0), clean pass (1), k_raycast / k_raycast_view launch (5), hfpf_extract_components* call (6),
+    // hfpf_compare_mesh* call (7)
+    TimedId timed[kTimedIds];
+    std::vector<hipEvent_t> ev_free;  // the pool the events come from and go back to
 };
 
 namespace {
@@ -762,40 +766,65 @@ int alloc_tables(hfpf_handle* h)
 #endif
 using sort_config = rocprim::radix_sort_config<rocprim::default_config, rocprim::merge_sort_config<512, 1024, HFPF_SORT_BLOCK_ITEMS>, rocprim::default_config>;
 
+// rocPRIM's two-call protocol on h->sort_tmp: fn(tmp, bytes) -> hipError_t is called with tmp = nullptr (it reports the bytes it
+// needs), sort_tmp grows to that, and fn runs with the buffer and all of its bytes.
+template <typename Fn>
+int with_sort_tmp(hfpf_handle* h, Fn&& fn)
+{
+    size_t bytes = 0;
+    HIPCHK(h, fn((void*)nullptr, bytes));
+    if (int rc = scratch(h, h->sort_tmp, bytes)) return rc;
+    bytes = h->sort_tmp.bytes;
+    HIPCHK(h, fn(h->sort_tmp.p, bytes));
+    return HFPF_OK;
+}
+
 // Cell keys: only the low GridParams::key_bits bits are significant (an all-ones sentinel still sorts behind every valid key:
 // a valid cell has x < dim <= 2^bits_x - 1, so its key is never all ones).
 int sort_keys_u64(hfpf_handle* h, uint64_t* in, uint64_t* out, uint64_t n, unsigned bits = 0)
 {
     const unsigned kb = bits ? bits : h->g.key_bits;
-    size_t bytes = 0;
-    HIPCHK(h, rocprim::radix_sort_keys<sort_config>(nullptr, bytes, in, out, (size_t)n, 0, kb, h->stream));
-    int rc = scratch(h, h->sort_tmp, bytes);
-    if (rc) return rc;
-    bytes = h->sort_tmp.bytes;
-    HIPCHK(h, rocprim::radix_sort_keys<sort_config>(h->sort_tmp.p, bytes, in, out, (size_t)n, 0, kb, h->stream));
-    return HFPF_OK;
+    return with_sort_tmp(h, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_keys<sort_config>(tmp, bytes, in, out, (size_t)n, 0, kb, h->stream); });
 }
 
 int sort_keys_u32(hfpf_handle* h, uint32_t* in, uint32_t* out, uint64_t n, unsigned bits = 32)
 {
-    size_t bytes = 0;
-    HIPCHK(h, rocprim::radix_sort_keys<sort_config>(nullptr, bytes, in, out, (size_t)n, 0, bits, h->stream));
-    int rc = scratch(h, h->sort_tmp, bytes);
-    if (rc) return rc;
-    bytes = h->sort_tmp.bytes;
-    HIPCHK(h, rocprim::radix_sort_keys<sort_config>(h->sort_tmp.p, bytes, in, out, (size_t)n, 0, bits, h->stream));
-    return HFPF_OK;
+    return with_sort_tmp(h, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_keys<sort_config>(tmp, bytes, in, out, (size_t)n, 0, bits, h->stream); });
 }
 
 int sort_pairs_u64(hfpf_handle* h, uint64_t* kin, uint64_t* kout, uint32_t* vin, uint32_t* vout, uint64_t n, unsigned bits = 0)
 {
     const unsigned kb = bits ? bits : h->g.key_bits;
-    size_t bytes = 0;
-    HIPCHK(h, rocprim::radix_sort_pairs<sort_config>(nullptr, bytes, kin, kout, vin, vout, (size_t)n, 0, kb, h->stream));
-    int rc = scratch(h, h->sort_tmp, bytes);
-    if (rc) return rc;
-    bytes = h->sort_tmp.bytes;
-    HIPCHK(h, rocprim::radix_sort_pairs<sort_config>(h->sort_tmp.p, bytes, kin, kout, vin, vout, (size_t)n, 0, kb, h->stream));
+    return with_sort_tmp(h, [&](void* tmp, size_t& bytes) {
+        return rocprim::radix_sort_pairs<sort_config>(tmp, bytes, kin, kout, vin, vout, (size_t)n, 0, kb, h->stream);
+    });
+}
+
+// out[0..n] = the exclusive sum of the n + 1 words in[0..n] (in[n] = 0, so out[n] is the total, read back into *total).
+int scan_counts_locked(hfpf_handle* h, const uint32_t* in, uint32_t* out, uint64_t n, uint64_t* total)
+{
+    if (int rc = with_sort_tmp(h, [&](void* tmp, size_t& bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, in, out, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), h->stream);
+        }))
+        return rc;
+    uint32_t t = 0;
+    HIPCHK(h, hipMemcpyAsync(&t, out + n, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *total = t;
+    return HFPF_OK;
+}
+
+// out = the distinct keys of sorted[0, n) in order; their number lands in the first word of `count` (device) and in *n_out.
+int unique_keys_locked(hfpf_handle* h, const uint64_t* sorted, uint64_t n, uint64_t* out, uint64_t* count, uint64_t* n_out)
+{
+    if (int rc = with_sort_tmp(h, [&](void* tmp, size_t& bytes) {
+            return rocprim::unique(tmp, bytes, sorted, out, count, (size_t)n, rocprim::equal_to<uint64_t>(), h->stream);
+        }))
+        return rc;
+    uint64_t cnt = 0;
+    HIPCHK(h, hipMemcpyAsync(&cnt, count, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *n_out = cnt;
     return HFPF_OK;
 }
 
@@ -908,33 +937,47 @@ hipError_t pooled_event(hfpf_handle* h, hipEvent_t* e)
     return hipSuccess;
 }
 
-// Bracket work on the engine's stream with a pooled event pair when timing is on: timed_begin in front of it, timed_end behind it
-// files the pair under `list` (ev_pending*), where resolve_timing finds it.
-int timed_begin(hfpf_handle* h, std::pair<hipEvent_t, hipEvent_t>* pr)
-{
-    *pr = {nullptr, nullptr};
-    if (!h->timing) return HFPF_OK;
-    HIPCHK(h, pooled_event(h, &pr->first));
-    HIPCHK(h, pooled_event(h, &pr->second));
-    HIPCHK(h, hipEventRecord(pr->first, h->stream));
-    return HFPF_OK;
-}
-int timed_end(hfpf_handle* h, const std::pair<hipEvent_t, hipEvent_t>& pr, EventPairs& list)
-{
-    if (!pr.first) return HFPF_OK;
-    HIPCHK(h, hipEventRecord(pr.second, h->stream));
-    list.push_back(pr);
-    return HFPF_OK;
-}
-// ... and both around one kernel launch (the march launches of raycast: ev_pending_ray, hfpf_get_kernel_time id 5)
+// Brackets work on the engine's stream with a pooled event pair when timing is on (with timing off it touches nothing).  The
+// constructor takes the pair and records its first event (check `rc`); file(id) records the second and files the pair under the
+// id's row, where resolve_timing finds it.  A pair that is never filed -- the call left early -- goes back to the pool.
+struct Timed {
+    hfpf_handle* h;
+    std::pair<hipEvent_t, hipEvent_t> pr{nullptr, nullptr};
+    int rc;
+    explicit Timed(hfpf_handle* h_) : h(h_), rc(h_->timing ? begin() : HFPF_OK) {}
+    Timed(const Timed&) = delete;
+    ~Timed()
+    {
+        if (pr.first) h->ev_free.push_back(pr.first);
+        if (pr.second) h->ev_free.push_back(pr.second);
+    }
+    int file(int id)
+    {
+        if (!pr.second) return HFPF_OK;
+        HIPCHK(h, hipEventRecord(pr.second, h->stream));
+        h->timed[id].pending.push_back(pr);
+        pr = {nullptr, nullptr};
+        return HFPF_OK;
+    }
+
+  private:
+    int begin()
+    {
+        HIPCHK(h, pooled_event(h, &pr.first));
+        HIPCHK(h, pooled_event(h, &pr.second));
+        HIPCHK(h, hipEventRecord(pr.first, h->stream));
+        return HFPF_OK;
+    }
+};
+// ... around one kernel launch (the march launches of raycast, kTimeRaycast)
 template <typename Launch>
-int timed_launch(hfpf_handle* h, EventPairs& list, Launch&& launch)
+int timed_launch(hfpf_handle* h, int id, Launch&& launch)
 {
-    std::pair<hipEvent_t, hipEvent_t> timed;
-    if (int rc = timed_begin(h, &timed)) return rc;
+    Timed timed(h);
+    if (timed.rc) return timed.rc;
     launch();
     HIPCHK(h, hipGetLastError());
-    return timed_end(h, timed, list);
+    return timed.file(id);
 }
 
 // dl != nullptr: the frames are depth images (dev_base / frame_stride address the depth images, n_points = width * height, the
@@ -970,8 +1013,8 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
     const uint32_t fw = dl ? dl->width : h->cfg.frame_width;
     const uint32_t row_w = (fw >= 16 && fw % 16 == 0 && n_points % fw == 0 && (n_points / fw) % 16 == 0) ? fw : 0u;
     const dim3 grid((unsigned)std::min<uint64_t>(n_tiles, (uint64_t)h->integrate_grid));
-    std::pair<hipEvent_t, hipEvent_t> timed;
-    if ((rc = timed_begin(h, &timed))) return rc;
+    Timed timed(h);
+    if (timed.rc) return timed.rc;
     const bool color = h->t.color != 0;
     const bool bin = h->binned;
     const uint32_t pre_possible = (h->h_ctr[C_NORMALS] > 0 || h->ss.normals_possible) ? 1u : 0u;  // a clean pass has run: unoccupied cells may carry a dependant
@@ -1127,7 +1170,7 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
     HIPCHK(h, hipGetLastError());
     if (h->timing_detail) h->ev_detail_ran.push_back(detail_ran);
     detail_guard.done = true;
-    if ((rc = timed_end(h, timed, h->ev_pending))) return rc;
+    if ((rc = timed.file(kTimeIntegrate))) return rc;
     HIPCHK(h, hipEventRecord(s->done, h->stream));
     s->pending = true;
     h->ss.dirty = true;  // state_changed = true, grid.hpp:189
@@ -1144,35 +1187,28 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
 
 int resolve_timing(hfpf_handle* h)
 {
-    if (h->ev_pending.empty() && h->ev_pending_clean.empty() && h->ev_pending_ray.empty() && h->ev_pending_comp.empty() && h->ev_pending_dev.empty() &&
-        h->ev_detail.empty())
-        return HFPF_OK;
+    bool pending = !h->ev_detail.empty();
+    for (const TimedId& t : h->timed) pending = pending || !t.pending.empty();
+    if (!pending) return HFPF_OK;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    auto settle = [&](EventPairs& list, double& total_ms, uint64_t& n) -> int {
-        for (auto& pr : list) {
+    for (TimedId& t : h->timed) {
+        for (auto& pr : t.pending) {
             float ms = 0.f;
             HIPCHK(h, hipEventElapsedTime(&ms, pr.first, pr.second));
-            total_ms += (double)ms;
-            n++;
+            t.ms += (double)ms;
+            t.n++;
             h->ev_free.push_back(pr.first);
             h->ev_free.push_back(pr.second);
         }
-        list.clear();
-        return HFPF_OK;
-    };
-    int rc;
-    if ((rc = settle(h->ev_pending_ray, h->t_ray_ms, h->n_ray_timed))) return rc;
-    if ((rc = settle(h->ev_pending_comp, h->t_comp_ms, h->n_comp_timed))) return rc;
-    if ((rc = settle(h->ev_pending_dev, h->t_dev_ms, h->n_dev_timed))) return rc;
-    if ((rc = settle(h->ev_pending_clean, h->t_clean_ms, h->n_clean_timed))) return rc;
-    if ((rc = settle(h->ev_pending, h->t_integrate_ms, h->n_integrate_launches))) return rc;
+        t.pending.clear();
+    }
     for (size_t c = 0; 4 * c + 3 < h->ev_detail.size() && c < h->ev_detail_ran.size(); c++) {
         for (int k = 0; k < 3; k++) {
             if (!(h->ev_detail_ran[c] & (1u << k))) continue;  // not launched in this call (e.g. no dependants yet: no k_update_cells)
             float ms = 0.f;
             HIPCHK(h, hipEventElapsedTime(&ms, h->ev_detail[4 * c + k], h->ev_detail[4 * c + k + 1]));
-            h->t_detail_ms[k] += (double)ms;
-            h->n_detail[k]++;
+            h->timed[kTimeDetail + k].ms += (double)ms;
+            h->timed[kTimeDetail + k].n++;
         }
     }
     for (hipEvent_t e : h->ev_detail) h->ev_free.push_back(e);
@@ -1327,7 +1363,8 @@ int grow_exchange_buffers_locked(hfpf_handle* h, uint64_t records, uint64_t keep
 {
     int rc;
     if (h->ex_send.bytes < records * sizeof(EpochRec)) {
-        DevBuf bigger;
+        std::vector<DevBuf*> unregistered;  // (the allocation moves into ex_send below)
+        DevBuf bigger(unregistered);
         if ((rc = scratch(h, bigger, records * sizeof(EpochRec)))) return rc;
         if (keep) HIPCHK(h, hipMemcpyAsync(bigger.p, h->ex_send.p, keep * sizeof(EpochRec), hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1335,7 +1372,7 @@ int grow_exchange_buffers_locked(hfpf_handle* h, uint64_t records, uint64_t keep
             HIPCHK(h, hipFree(h->ex_send.p));
             h->device_bytes -= h->ex_send.bytes;
         }
-        h->ex_send = bigger;
+        h->ex_send.p = bigger.p, h->ex_send.bytes = bigger.bytes;
     }
     return scratch(h, h->ex_recv, (size_t)h->world * records * sizeof(EpochRec));
 }
@@ -1443,7 +1480,7 @@ int clean_locked(hfpf_handle* h, int pre_rc)
     HIPCHK(h, hipGetLastError());
     h->ss.gate_done = n_occ;
     h->ss.normals_possible = true;
-    std::swap(h->pend_a, h->pend_b);  // cells that got a normal in this pass are dropped by the next gate's kNormal test
+    swap(h->pend_a, h->pend_b);  // cells that got a normal in this pass are dropped by the next gate's kNormal test
     h->ss.pend_valid = true;             // C_PEND now counts pend_a; the host reads it at the start of the next pass
 
     // canonical order: ascending (x,y,z) key; record id = n_normals + rank + 1
@@ -1598,6 +1635,8 @@ int hfpf_create(const hfpf_config* cfg, hfpf_handle** out)
     auto bail = [&](int rc) {
         g_create_error = h->err;
         for (void* p : h->allocs) (void)hipFree(p);
+        for (DevBuf* b : h->bufs)
+            if (b->p) (void)hipFree(b->p);
         if (h->h_ctr) (void)hipHostFree(h->h_ctr);
         if (h->h_log_ctr) (void)hipHostFree(h->h_log_ctr);
         if (h->mbox) (void)hipHostFree(h->mbox);
@@ -1673,12 +1712,7 @@ int hfpf_destroy(hfpf_handle* h)
     (void)hipSetDevice(h->cfg.device);
     (void)hipStreamSynchronize(h->stream);
     for (void* p : h->allocs) (void)hipFree(p);
-    for (DevBuf* b : {&h->sort_tmp, &h->keys_a, &h->keys_b, &h->vals_a, &h->vals_b, &h->rows_dev, &h->probe_a, &h->probe_b, &h->probe_c, &h->probe_d,
-                      &h->probe_e, &h->probe_f, &h->zbuf, &h->render_pose, &h->render_out, &h->track_in, &h->track_acc,
-                      &h->query_in, &h->query_out, &h->mesh_cube, &h->mesh_corner, &h->mesh_kdata, &h->mesh_cdata, &h->mesh_out,
-                      &h->mesh_ctr, &h->comp_index, &h->comp_rows, &h->comp_recs, &h->comp_out, &h->dev_mesh, &h->dev_tri, &h->dev_bins, &h->dev_pairs, &h->dev_out, &h->ray_in, &h->ray_out, &h->ray_map, &h->snap_stage, &h->snap_err})
-        if (b->p) (void)hipFree(b->p);
-    for (DevBuf* b : {&h->ex_send, &h->ex_recv, &h->ex_counts, &h->stats_total, &h->bin_pt_buf, &h->bin_rgb_buf, &h->bin_sums, &h->ovf_pt_buf, &h->ovf_aux_buf, &h->pend_a, &h->pend_b})
+    for (DevBuf* b : h->bufs)
         if (b->p) (void)hipFree(b->p);
     if (h->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy((ncclComm_t_)h->comm);
     if (h->h_counts) (void)hipHostFree(h->h_counts);
@@ -1709,26 +1743,11 @@ int hfpf_destroy(hfpf_handle* h)
             (void)hipStreamSynchronize(cs);
             (void)hipStreamDestroy(cs);
         }
-    for (auto& pr : h->ev_pending) {
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-    }
-    for (auto& pr : h->ev_pending_clean) {
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-    }
-    for (auto& pr : h->ev_pending_ray) {
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-    }
-    for (auto& pr : h->ev_pending_comp) {
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-    }
-    for (auto& pr : h->ev_pending_dev) {
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-    }
+    for (TimedId& t : h->timed)
+        for (auto& pr : t.pending) {
+            (void)hipEventDestroy(pr.first);
+            (void)hipEventDestroy(pr.second);
+        }
     for (auto e : h->ev_detail) (void)hipEventDestroy(e);
     for (auto e : h->ev_free) (void)hipEventDestroy(e);
     if (h->h_ctr) (void)hipHostFree(h->h_ctr);
@@ -2092,11 +2111,11 @@ int hfpf_clean(hfpf_handle* h)
     if (!pre) pre = poison_on_error(h, flush_pending_locked(h));  // host frames still waiting for their launch
     if (!pre) pre = check_usable(h);
     if (pre && !h->dist_on) return pre;
-    if (!h->timing || pre) return poison_on_error(h, clean_locked(h, pre));
-    std::pair<hipEvent_t, hipEvent_t> timed;
-    if (int rc = timed_begin(h, &timed)) return rc;  // after every queued integrate: measures the clean pass alone
+    if (pre) return poison_on_error(h, clean_locked(h, pre));
+    Timed timed(h);  // after every queued integrate: measures the clean pass alone (nothing with timing off)
+    if (timed.rc) return timed.rc;
     const int rc = poison_on_error(h, clean_locked(h, 0));
-    if (int rc1 = timed_end(h, timed, h->ev_pending_clean)) return rc1;
+    if (int rc1 = timed.file(kTimeClean)) return rc1;
     return rc;
 }
 
@@ -2171,6 +2190,76 @@ static void* host_result_alloc(size_t want)
     return malloc(want);
 }
 
+// The arrays a read-out returns, up to three (extract, mesh, components, compare_mesh).  result_alloc gives each a device array;
+// the kernels fill them; the device form hands them to the caller, the host form downloads them with result_to_host.
+struct ResultSet {
+    struct Array {
+        size_t bytes = 0;
+        bool absent = false;           // an optional output the caller passed NULL for: no memory, NULL wherever it would appear
+        const void* borrow = nullptr;  // device memory of the handle that already holds the array: the host form downloads from it
+        void* dev = nullptr;           // the device array (result_alloc)
+    };
+    Array a[3];
+    int n = 0;
+    bool owned = false;  // device form: the arrays are allocations of their own, the caller's once the call succeeds
+    void add(size_t bytes, bool absent = false, const void* borrow = nullptr) { a[n++] = Array{bytes, absent, borrow, nullptr}; }
+    void release()  // error paths of the device form
+    {
+        for (Array& x : a) {
+            if (owned) (void)hipFree(x.dev);
+            x.dev = nullptr;
+        }
+    }
+};
+
+// Device form: one hipMalloc per present array (a borrowed one too: the caller copies it over).  Host form: 16-byte aligned slices of
+// h->result_out, and borrowed arrays where they are.
+static int result_alloc(hfpf_handle* h, ResultSet& set, bool on_device, const char* what)
+{
+    set.owned = on_device;
+    if (on_device) {
+        for (int i = 0; i < set.n; i++) {
+            if (set.a[i].absent) continue;
+            const hipError_t e = hipMalloc(&set.a[i].dev, set.a[i].bytes);
+            if (e == hipSuccess) continue;
+            set.release();
+            return fail(h, HFPF_ERR_HIP, "%s: device allocation of %llu bytes failed: %s", what, (unsigned long long)set.a[i].bytes, hipGetErrorString(e));
+        }
+        return HFPF_OK;
+    }
+    size_t off[3] = {0, 0, 0}, total = 0;
+    for (int i = 0; i < set.n; i++) {
+        off[i] = total;
+        if (!set.a[i].absent && !set.a[i].borrow) total += (set.a[i].bytes + 15) & ~(size_t)15;
+    }
+    if (total)
+        if (int rc = scratch(h, h->result_out, total)) return rc;
+    for (int i = 0; i < set.n; i++)
+        if (!set.a[i].absent) set.a[i].dev = set.a[i].borrow ? const_cast<void*>(set.a[i].borrow) : (char*)h->result_out.p + off[i];
+    return HFPF_OK;
+}
+
+// The host form's tail: every present array into pageable memory the caller will free() (out[i]; NULL for an absent one).
+static int result_to_host(hfpf_handle* h, const ResultSet& set, const char* what, void* out[3])
+{
+    bool ok = true;
+    for (int i = 0; i < 3; i++) {
+        const bool present = i < set.n && !set.a[i].absent;
+        out[i] = present ? host_result_alloc(set.a[i].bytes) : nullptr;
+        ok = ok && (!present || out[i]);
+    }
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < set.n && ok && e == hipSuccess; i++)
+        if (out[i]) e = download_pageable(h, out[i], set.a[i].dev, set.a[i].bytes);
+    if (ok && e == hipSuccess) return HFPF_OK;
+    for (int i = 0; i < 3; i++) {
+        free(out[i]);
+        out[i] = nullptr;
+    }
+    if (!ok) return fail(h, HFPF_ERR_CAPACITY, "%s: host allocation of the result failed", what);
+    return fail(h, HFPF_ERR_HIP, "%s copy: %s", what, hipGetErrorString(e));
+}
+
 // Shared tail of extract: `stats` are the (possibly merged) sums to finalise.
 static int extract_locked(hfpf_handle* h, const unsigned long long* stats, const hfpf_extract_opts* o, hfpf_row** rows, uint64_t* n_rows)
 {
@@ -2181,17 +2270,14 @@ static int extract_locked(hfpf_handle* h, const unsigned long long* stats, const
         opt.paint_white = o->paint_white ? 1 : 0;
     }
     uint64_t nr = 0;
-    if (int rc = build_rows_locked(h, stats, opt, &nr)) return rc;
+    int rc;
+    if ((rc = build_rows_locked(h, stats, opt, &nr))) return rc;
     if (nr == 0) return HFPF_OK;
-    hfpf_row* host = (hfpf_row*)host_result_alloc(nr * sizeof(hfpf_row));
-    if (!host) return fail(h, HFPF_ERR_CAPACITY, "extract: host allocation of %llu rows failed", (unsigned long long)nr);
-    // The rows go to pageable memory the caller will free()
-    const hipError_t e = download_pageable(h, host, h->rows_dev.p, nr * sizeof(Row));
-    if (e != hipSuccess) {
-        free(host);
-        return fail(h, HFPF_ERR_HIP, "extract copy: %s", hipGetErrorString(e));
-    }
-    *rows = host;
+    ResultSet set;
+    set.add(nr * sizeof(Row), false, h->rows_dev.p);
+    void* host[3];
+    if ((rc = result_alloc(h, set, false, "extract")) || (rc = result_to_host(h, set, "extract", host))) return rc;
+    *rows = (hfpf_row*)host[0];
     *n_rows = nr;
     return HFPF_OK;
 }
@@ -2832,7 +2918,7 @@ static int raycast_common(hfpf_handle* h, const hfpf_raycast_opts* o, const hfpf
     memcpy(p.T, pose, sizeof p.T);
     auto launch = [&](const hfpf_ray* dr, uint64_t n, hfpf_ray_hit* dh) -> int {
         p.n_rays = n;
-        return timed_launch(h, h->ev_pending_ray, [&] {
+        return timed_launch(h, kTimeRaycast, [&] {
             hipLaunchKernelGGL(k_raycast, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->g, h->t, p, (const float*)dr, (RayHit*)dh);
         });
     };
@@ -2896,7 +2982,7 @@ static int raycast_view_common(hfpf_handle* h, const hfpf_raycast_opts* o, uint3
         p.row0 = row0;
         p.rows = rows;
         const uint64_t tiles = tiles_x * ((rows + 7ull) / 8);
-        return timed_launch(h, h->ev_pending_ray, [&] {
+        return timed_launch(h, kTimeRaycast, [&] {
             hipLaunchKernelGGL(k_raycast_view, dim3(blocks_for(tiles * 64, 256), nv), dim3(256), 0, h->stream, h->g, h->t, p,
                                (const double*)h->render_pose.p + 12ull * v0, dh);
         });
@@ -2955,42 +3041,15 @@ static int mesh_dilate_locked(hfpf_handle* h, DevBuf& in, uint64_t n_in, int axi
     if ((rc = sort_keys_u64(h, (uint64_t*)h->keys_a.p, (uint64_t*)h->keys_b.p, n, 2 * kMeshKeyBits + xbits))) return rc;
     if ((rc = scratch(h, out, n * 8))) return rc;
     if ((rc = scratch(h, h->mesh_ctr, 16))) return rc;
-    const uint64_t* sorted = (const uint64_t*)h->keys_b.p;
-    size_t bytes = 0;
-    HIPCHK(h, rocprim::unique(nullptr, bytes, sorted, (uint64_t*)out.p, (uint64_t*)h->mesh_ctr.p, (size_t)n, rocprim::equal_to<uint64_t>(), h->stream));
-    if ((rc = scratch(h, h->sort_tmp, bytes))) return rc;
-    bytes = h->sort_tmp.bytes;
-    HIPCHK(h, rocprim::unique(h->sort_tmp.p, bytes, sorted, (uint64_t*)out.p, (uint64_t*)h->mesh_ctr.p, (size_t)n, rocprim::equal_to<uint64_t>(),
-                              h->stream));
-    uint64_t cnt = 0;
-    HIPCHK(h, hipMemcpyAsync(&cnt, h->mesh_ctr.p, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    *n_out = cnt;
-    return HFPF_OK;
-}
-
-// out[0..n] = the exclusive sum of in[0..n] (in[n] = 0, so out[n] is the total, returned in *total).
-static int mesh_scan_locked(hfpf_handle* h, const uint32_t* in, uint32_t* out, uint64_t n, uint64_t* total)
-{
-    size_t bytes = 0;
-    HIPCHK(h, rocprim::exclusive_scan(nullptr, bytes, in, out, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), h->stream));
-    if (int rc = scratch(h, h->sort_tmp, bytes)) return rc;
-    bytes = h->sort_tmp.bytes;
-    HIPCHK(h, rocprim::exclusive_scan(h->sort_tmp.p, bytes, in, out, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), h->stream));
-    uint32_t t = 0;
-    HIPCHK(h, hipMemcpyAsync(&t, out + n, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    *total = t;
-    return HFPF_OK;
+    return unique_keys_locked(h, (const uint64_t*)h->keys_b.p, n, (uint64_t*)out.p, (uint64_t*)h->mesh_ctr.p, n_out);
 }
 
 // Validated arguments in, under the lock.  The row set, the cube set (the rows' cells dilated by 1) and the corner set (the cubes
 // dilated by (0, +1)), the corner samples, the edge marks and triangle counts, two scans, then vertices and triangles into device
-// arrays: new allocations for the device form, h->mesh_out for the host form.  The read-backs are the sizes between the stages.
-static int mesh_locked(hfpf_handle* h, const hfpf_mesh_opts* o, bool on_device, MeshVertex** verts, uint32_t** tris, uint64_t* n_verts,
-                       uint64_t* n_tris)
+// arrays (*out: vertices, triangles).  The read-backs are the sizes between the stages.
+static int mesh_locked(hfpf_handle* h, const hfpf_mesh_opts* o, bool on_device, ResultSet* out, uint64_t* n_verts, uint64_t* n_tris)
 {
-    *verts = nullptr, *tris = nullptr, *n_verts = 0, *n_tris = 0;
+    *out = ResultSet{}, *n_verts = 0, *n_tris = 0;
     int rc;
     if ((rc = local_read_prologue_locked(h, "mesh"))) return rc;
     for (int a = 0; a < 3; a++)
@@ -3037,25 +3096,18 @@ static int mesh_locked(hfpf_handle* h, const hfpf_mesh_opts* o, bool on_device, 
     hipLaunchKernelGGL(k_mesh_vcount, dim3(blocks_for(K1, 256)), dim3(256), 0, h->stream, (const uint32_t*)marks, (uint32_t)nk, vcount);
     HIPCHK(h, hipGetLastError());
     uint64_t nv = 0, nt = 0;
-    if ((rc = mesh_scan_locked(h, vcount, vbase, nk, &nv))) return rc;
-    if ((rc = mesh_scan_locked(h, tcount, tbase, nc, &nt))) return rc;
+    if ((rc = scan_counts_locked(h, vcount, vbase, nk, &nv))) return rc;
+    if ((rc = scan_counts_locked(h, tcount, tbase, nc, &nt))) return rc;
     uint32_t missed = 0;
     HIPCHK(h, hipMemcpy(&missed, miss, 4, hipMemcpyDeviceToHost));  // (the scan's read-back has synchronised the stream)
     if (missed) return fail(h, HFPF_ERR_STATE, "mesh: a corner of a cube is missing from the corner set (internal)");
     if (nv == 0 || nt == 0) return HFPF_OK;
-    MeshVertex* dv = nullptr;
-    uint32_t* dt = nullptr;
-    if (on_device) {
-        HIPCHK(h, hipMalloc(&dv, nv * sizeof(MeshVertex)));
-        if (hipMalloc(&dt, nt * 12) != hipSuccess) {
-            (void)hipFree(dv);
-            return fail(h, HFPF_ERR_HIP, "mesh: device allocation of %llu triangles failed", (unsigned long long)nt);
-        }
-    } else {
-        if ((rc = scratch(h, h->mesh_out, nv * sizeof(MeshVertex) + nt * 12))) return rc;
-        dv = (MeshVertex*)h->mesh_out.p;
-        dt = (uint32_t*)(dv + nv);
-    }
+    ResultSet set;
+    set.add(nv * sizeof(MeshVertex));
+    set.add(nt * 12);
+    if ((rc = result_alloc(h, set, on_device, "mesh"))) return rc;
+    MeshVertex* dv = (MeshVertex*)set.a[0].dev;
+    uint32_t* dt = (uint32_t*)set.a[1].dev;
     hipLaunchKernelGGL(k_mesh_vertices, dim3(blocks_for(nk, 256)), dim3(256), 0, h->stream, h->g, h->t, corners, (uint32_t)nk, (const float*)s,
                        (const uint32_t*)nid, (const uint32_t*)marks, (const uint32_t*)vbase, dv, miss);
     hipLaunchKernelGGL(k_mesh_triangles, dim3(blocks_for(nc, 256)), dim3(256), 0, h->stream, cubes, (uint32_t)nc, corners, (uint32_t)nk, (const float*)s,
@@ -3064,11 +3116,11 @@ static int mesh_locked(hfpf_handle* h, const hfpf_mesh_opts* o, bool on_device, 
     if (e == hipSuccess) e = hipMemcpyAsync(&missed, miss, 4, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess || missed) {
-        if (on_device) (void)hipFree(dv), (void)hipFree(dt);
+        set.release();
         if (missed) return fail(h, HFPF_ERR_STATE, "mesh: a corner of a cube or an edge is missing from the corner set (internal)");
         return fail(h, HFPF_ERR_HIP, "mesh: %s", hipGetErrorString(e));
     }
-    *verts = dv, *tris = dt, *n_verts = nv, *n_tris = nt;
+    *out = set, *n_verts = nv, *n_tris = nt;
     return HFPF_OK;
 }
 
@@ -3078,11 +3130,9 @@ int hfpf_extract_mesh_device(hfpf_handle* h, const hfpf_mesh_opts* o, hfpf_mesh_
     if (!h) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
     if (!mesh_opts_ok(o) || !dev_verts || !n_verts || !dev_tris || !n_tris) return fail(h, HFPF_ERR_BAD_ARG, "mesh: invalid options or a NULL output");
-    MeshVertex* dv = nullptr;
-    uint32_t* dt = nullptr;
-    uint64_t nv = 0, nt = 0;
-    const int rc = mesh_locked(h, o, true, &dv, &dt, &nv, &nt);
-    *dev_verts = (hfpf_mesh_vertex*)dv, *dev_tris = dt, *n_verts = nv, *n_tris = nt;
+    ResultSet set;
+    const int rc = mesh_locked(h, o, true, &set, n_verts, n_tris);
+    *dev_verts = (hfpf_mesh_vertex*)set.a[0].dev, *dev_tris = (uint32_t*)set.a[1].dev;
     return rc;
 }
 
@@ -3092,24 +3142,14 @@ int hfpf_extract_mesh(hfpf_handle* h, const hfpf_mesh_opts* o, hfpf_mesh_vertex*
     std::lock_guard<std::mutex> lk(h->mtx);
     if (!mesh_opts_ok(o) || !verts || !n_verts || !tris || !n_tris) return fail(h, HFPF_ERR_BAD_ARG, "mesh: invalid options or a NULL output");
     *verts = nullptr, *tris = nullptr, *n_verts = 0, *n_tris = 0;
-    MeshVertex* dv = nullptr;
-    uint32_t* dt = nullptr;
+    ResultSet set;
     uint64_t nv = 0, nt = 0;
-    if (int rc = mesh_locked(h, o, false, &dv, &dt, &nv, &nt)) return rc;
+    int rc;
+    if ((rc = mesh_locked(h, o, false, &set, &nv, &nt))) return rc;
     if (nv == 0) return HFPF_OK;
-    hfpf_mesh_vertex* hv = (hfpf_mesh_vertex*)host_result_alloc(nv * sizeof(hfpf_mesh_vertex));
-    uint32_t* ht = (uint32_t*)host_result_alloc(nt * 12);
-    if (!hv || !ht) {
-        free(hv), free(ht);
-        return fail(h, HFPF_ERR_CAPACITY, "mesh: host allocation of %llu vertices / %llu triangles failed", (unsigned long long)nv, (unsigned long long)nt);
-    }
-    hipError_t e = download_pageable(h, hv, dv, nv * sizeof(hfpf_mesh_vertex));
-    if (e == hipSuccess) e = download_pageable(h, ht, dt, nt * 12);
-    if (e != hipSuccess) {
-        free(hv), free(ht);
-        return fail(h, HFPF_ERR_HIP, "mesh copy: %s", hipGetErrorString(e));
-    }
-    *verts = hv, *tris = ht, *n_verts = nv, *n_tris = nt;
+    void* host[3];
+    if ((rc = result_to_host(h, set, "mesh", host))) return rc;
+    *verts = (hfpf_mesh_vertex*)host[0], *tris = (uint32_t*)host[1], *n_verts = nv, *n_tris = nt;
     return HFPF_OK;
 }
 
@@ -3127,19 +3167,14 @@ int hfpf_check_component_opts(const hfpf_component_opts* o)
     return std::isfinite(o->min_normal_dot) && o->min_normal_dot >= -2.0 && o->min_normal_dot <= 1.0 ? HFPF_OK : HFPF_ERR_BAD_ARG;
 }
 
-struct CompOut {  // device arrays: new allocations for the device form, slices of h->comp_out for the host form
-    Row* rows = nullptr;
-    uint32_t* labels = nullptr;
-    Component* comps = nullptr;
-    uint64_t n_rows = 0, n_comps = 0;
-};
-
 // Validated arguments in, under the lock.  The row set, then (timed as kernel id 6) index, link, flatten, the scan of the root flags,
 // the per-component reductions, the keep flags (through a sort for keep_largest), the scans of kept components and kept rows, and
-// the compaction.  The read-backs are the sizes between the stages.
-static int components_locked(hfpf_handle* h, const hfpf_component_opts* o, bool on_device, bool want_rows, CompOut* out)
+// the compaction into *out (rows -- absent without want_rows --, labels, component records).  The read-backs are the sizes between
+// the stages.
+static int components_locked(hfpf_handle* h, const hfpf_component_opts* o, bool on_device, bool want_rows, ResultSet* out, uint64_t* n_rows,
+                             uint64_t* n_comps)
 {
-    *out = CompOut{};
+    *out = ResultSet{}, *n_rows = 0, *n_comps = 0;
     int rc;
     if ((rc = local_read_prologue_locked(h, "components"))) return rc;
     uint64_t nr = 0;
@@ -3162,15 +3197,15 @@ static int components_locked(hfpf_handle* h, const hfpf_component_opts* o, bool 
     const Row* rows = (const Row*)h->rows_dev.p;
     const CompParams p{o->min_normal_dot, o->min_points, o->min_rows, o->keep_largest, o->reach};
     const dim3 grid_r(blocks_for(nr, 256)), grid_r1(blocks_for(R1, 256));
-    std::pair<hipEvent_t, hipEvent_t> timed;
-    if ((rc = timed_begin(h, &timed))) return rc;
+    Timed timed(h);
+    if (timed.rc) return timed.rc;
     HIPCHK(h, hipMemsetAsync(row_of, 0xFF, (n_rec + 1) * 4, h->stream));
     hipLaunchKernelGGL(k_comp_index, grid_r, dim3(256), 0, h->stream, (const uint32_t*)h->vals_b.p, n, row_of, parent);
     hipLaunchKernelGGL(k_comp_link, grid_r, dim3(256), 0, h->stream, h->g, h->t, p, rows, n, (const uint32_t*)row_of, (uint32_t)n_rec, parent);
     hipLaunchKernelGGL(k_comp_flatten, grid_r1, dim3(256), 0, h->stream, (const uint32_t*)parent, n, root, flag);
     HIPCHK(h, hipGetLastError());
     uint64_t nc = 0;
-    if ((rc = mesh_scan_locked(h, flag, cbase, nr, &nc))) return rc;
+    if ((rc = scan_counts_locked(h, flag, cbase, nr, &nc))) return rc;
     const uint64_t C1 = nc + 1;
     if ((rc = scratch(h, h->comp_recs, nc * sizeof(Component) + C1 * 8))) return rc;
     Component* recs = (Component*)h->comp_recs.p;
@@ -3195,40 +3230,24 @@ static int components_locked(hfpf_handle* h, const hfpf_component_opts* o, bool 
     hipLaunchKernelGGL(k_comp_row_keep, grid_r1, dim3(256), 0, h->stream, (const uint32_t*)comp_of, (const uint32_t*)keep, n, flag);
     HIPCHK(h, hipGetLastError());
     uint64_t nk = 0, nkr = 0;
-    if ((rc = mesh_scan_locked(h, keep, kbase, nc, &nk))) return rc;
-    if ((rc = mesh_scan_locked(h, flag, rbase, nr, &nkr))) return rc;
-    if (nk == 0) return timed_end(h, timed, h->ev_pending_comp);
-    CompOut d;
-    d.n_rows = nkr, d.n_comps = nk;
-    const size_t row_bytes = want_rows ? nkr * sizeof(Row) : 0, label_bytes = (nkr * 4 + 15) & ~(size_t)15;
-    void* owned[3] = {nullptr, nullptr, nullptr};
-    if (on_device) {
-        hipError_t e = want_rows ? hipMalloc(&owned[0], row_bytes) : hipSuccess;
-        if (e == hipSuccess) e = hipMalloc(&owned[1], nkr * 4);
-        if (e == hipSuccess) e = hipMalloc(&owned[2], nk * sizeof(Component));
-        if (e != hipSuccess) {
-            for (void* q : owned) (void)hipFree(q);
-            return fail(h, HFPF_ERR_HIP, "components: device allocation of %llu rows / %llu components failed: %s", (unsigned long long)nkr,
-                        (unsigned long long)nk, hipGetErrorString(e));
-        }
-        d.rows = (Row*)owned[0], d.labels = (uint32_t*)owned[1], d.comps = (Component*)owned[2];
-    } else {
-        if ((rc = scratch(h, h->comp_out, row_bytes + label_bytes + nk * sizeof(Component)))) return rc;
-        char* base = (char*)h->comp_out.p;
-        d.rows = want_rows ? (Row*)base : nullptr;
-        d.labels = (uint32_t*)(base + row_bytes);
-        d.comps = (Component*)(base + row_bytes + label_bytes);
-    }
+    if ((rc = scan_counts_locked(h, keep, kbase, nc, &nk))) return rc;
+    if ((rc = scan_counts_locked(h, flag, rbase, nr, &nkr))) return rc;
+    if (nk == 0) return timed.file(kTimeComponents);
+    ResultSet set;
+    set.add(nkr * sizeof(Row), !want_rows);
+    set.add(nkr * 4);
+    set.add(nk * sizeof(Component));
+    if ((rc = result_alloc(h, set, on_device, "components"))) return rc;
     hipLaunchKernelGGL(k_comp_compact, grid_r, dim3(256), 0, h->stream, rows, n, (const uint32_t*)comp_of, (const uint32_t*)keep, (const uint32_t*)kbase,
-                       (const uint32_t*)rbase, (const Component*)recs, d.rows, d.labels, d.comps);
+                       (const uint32_t*)rbase, (const Component*)recs, (Row*)set.a[0].dev, (uint32_t*)set.a[1].dev, (Component*)set.a[2].dev);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) rc = timed_end(h, timed, h->ev_pending_comp);
+    if (e == hipSuccess) rc = timed.file(kTimeComponents);
     if (e == hipSuccess && !rc) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess || rc) {
-        for (void* q : owned) (void)hipFree(q);
+        set.release();
         return rc ? rc : fail(h, HFPF_ERR_HIP, "components: %s", hipGetErrorString(e));
     }
-    *out = d;
+    *out = set, *n_rows = nkr, *n_comps = nk;
     return HFPF_OK;
 }
 
@@ -3243,10 +3262,10 @@ int hfpf_extract_components_device(hfpf_handle* h, const hfpf_component_opts* o,
     if (!h) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
     if (!component_args_ok(o, dev_labels, n_rows, dev_comps, n_comps)) return fail(h, HFPF_ERR_BAD_ARG, "components: invalid options or a NULL output");
-    CompOut d;
-    const int rc = components_locked(h, o, true, dev_rows != nullptr, &d);
-    if (dev_rows) *dev_rows = (hfpf_row*)d.rows;
-    *dev_labels = d.labels, *dev_comps = (hfpf_component*)d.comps, *n_rows = d.n_rows, *n_comps = d.n_comps;
+    ResultSet set;
+    const int rc = components_locked(h, o, true, dev_rows != nullptr, &set, n_rows, n_comps);
+    if (dev_rows) *dev_rows = (hfpf_row*)set.a[0].dev;
+    *dev_labels = (uint32_t*)set.a[1].dev, *dev_comps = (hfpf_component*)set.a[2].dev;
     return rc;
 }
 
@@ -3258,26 +3277,15 @@ int hfpf_extract_components(hfpf_handle* h, const hfpf_component_opts* o, hfpf_r
     if (!component_args_ok(o, labels, n_rows, comps, n_comps)) return fail(h, HFPF_ERR_BAD_ARG, "components: invalid options or a NULL output");
     if (rows) *rows = nullptr;
     *labels = nullptr, *comps = nullptr, *n_rows = 0, *n_comps = 0;
-    CompOut d;
-    if (int rc = components_locked(h, o, false, rows != nullptr, &d)) return rc;
-    if (d.n_comps == 0) return HFPF_OK;
-    hfpf_row* hr = rows ? (hfpf_row*)host_result_alloc(d.n_rows * sizeof(hfpf_row)) : nullptr;
-    uint32_t* hl = (uint32_t*)host_result_alloc(d.n_rows * 4);
-    hfpf_component* hc = (hfpf_component*)host_result_alloc(d.n_comps * sizeof(hfpf_component));
-    if ((rows && !hr) || !hl || !hc) {
-        free(hr), free(hl), free(hc);
-        return fail(h, HFPF_ERR_CAPACITY, "components: host allocation of %llu rows / %llu components failed", (unsigned long long)d.n_rows,
-                    (unsigned long long)d.n_comps);
-    }
-    hipError_t e = rows ? download_pageable(h, hr, d.rows, d.n_rows * sizeof(hfpf_row)) : hipSuccess;
-    if (e == hipSuccess) e = download_pageable(h, hl, d.labels, d.n_rows * 4);
-    if (e == hipSuccess) e = download_pageable(h, hc, d.comps, d.n_comps * sizeof(hfpf_component));
-    if (e != hipSuccess) {
-        free(hr), free(hl), free(hc);
-        return fail(h, HFPF_ERR_HIP, "components copy: %s", hipGetErrorString(e));
-    }
-    if (rows) *rows = hr;
-    *labels = hl, *comps = hc, *n_rows = d.n_rows, *n_comps = d.n_comps;
+    ResultSet set;
+    uint64_t nr = 0, nc = 0;
+    int rc;
+    if ((rc = components_locked(h, o, false, rows != nullptr, &set, &nr, &nc))) return rc;
+    if (nc == 0) return HFPF_OK;
+    void* host[3];
+    if ((rc = result_to_host(h, set, "components", host))) return rc;
+    if (rows) *rows = (hfpf_row*)host[0];
+    *labels = (uint32_t*)host[1], *comps = (hfpf_component*)host[2], *n_rows = nr, *n_comps = nc;
     return HFPF_OK;
 }
 
@@ -3295,12 +3303,6 @@ int hfpf_check_deviation_opts(const hfpf_deviation_opts* o)
     return std::isfinite(o->max_distance) && o->max_distance > 0.0 && o->max_distance <= 1.0 ? HFPF_OK : HFPF_ERR_BAD_ARG;
 }
 
-struct DevOut {  // device arrays: new allocations for the device form; h->rows_dev and h->dev_out for the host form
-    Row* rows = nullptr;
-    Deviation* dev = nullptr;
-    uint64_t n_rows = 0;
-};
-
 static unsigned bits_for_count(uint64_t n)  // bits that hold 0..n-1 (at least 1)
 {
     unsigned b = 1;
@@ -3310,11 +3312,12 @@ static unsigned bits_for_count(uint64_t n)  // bits that hold 0..n-1 (at least 1
 
 // Validated arguments in, the mesh on the device, under the lock.  The row set; then (timed as kernel id 7) the rows keyed by the
 // brick of their point and sorted, the list of bricks that hold rows, the transformed vertices, the triangles' records and pair count,
-// the pairs, their sort and per-brick ranges, and k_dev_rows.  The read-backs are the sizes between the stages and the summary.
+// the pairs, their sort and per-brick ranges, and k_dev_rows into *out (the rows -- absent without want_rows; the host form takes
+// them from h->rows_dev --, the deviations; empty without rows).  The read-backs are the sizes between the stages and the summary.
 static int compare_locked(hfpf_handle* h, const hfpf_deviation_opts* o, const void* d_verts, uint64_t n_verts, uint32_t stride, const uint32_t* d_tris,
-                          uint64_t n_tris, const double* pose, bool on_device, bool want_rows, DevOut* out, hfpf_deviation_summary* summary)
+                          uint64_t n_tris, const double* pose, bool on_device, bool want_rows, ResultSet* out, hfpf_deviation_summary* summary)
 {
-    *out = DevOut{};
+    *out = ResultSet{};
     int rc;
     uint64_t nr = 0;
     const ExtractOpts opt{o->min_count, -1, 0};  // the compare of hfpf_extract_filtered, 0 keeps all
@@ -3345,8 +3348,8 @@ static int compare_locked(hfpf_handle* h, const hfpf_deviation_opts* o, const vo
     uint32_t* ub_start = base + R1;
     uint32_t* tstart = ub_start + R1;
     uint32_t* tend = tstart + n;
-    std::pair<hipEvent_t, hipEvent_t> timed;
-    if ((rc = timed_begin(h, &timed))) return rc;
+    Timed timed(h);
+    if (timed.rc) return timed.rc;
     HIPCHK(h, hipMemsetAsync(ctr, 0, DC_WORDS * 8 + sizeof(DevSummary), h->stream));
     uint64_t nb = 0;
     const Row* rows = (const Row*)h->rows_dev.p;
@@ -3358,7 +3361,7 @@ static int compare_locked(hfpf_handle* h, const hfpf_deviation_opts* o, const vo
         if ((rc = sort_pairs_u64(h, (uint64_t*)h->keys_a.p, (uint64_t*)h->keys_b.p, (uint32_t*)h->vals_a.p, (uint32_t*)h->vals_b.p, n, key_bits))) return rc;
         hipLaunchKernelGGL(k_dev_row_flags, grid_r1, dim3(256), 0, h->stream, (const uint64_t*)h->keys_b.p, n, flag);
         HIPCHK(h, hipGetLastError());
-        if ((rc = mesh_scan_locked(h, flag, base, n, &nb))) return rc;
+        if ((rc = scan_counts_locked(h, flag, base, n, &nb))) return rc;
         hipLaunchKernelGGL(k_dev_bricks, grid_r1, dim3(256), 0, h->stream, (const uint64_t*)h->keys_b.p, (const uint32_t*)flag, (const uint32_t*)base, n, (uint32_t)nb,
                            ub_key, ub_start);
         HIPCHK(h, hipMemsetAsync(tstart, 0, 2 * (size_t)n * 4, h->stream));
@@ -3396,35 +3399,24 @@ static int compare_locked(hfpf_handle* h, const hfpf_deviation_opts* o, const vo
             HIPCHK(h, hipGetLastError());
         }
     }
-    DevOut d;
-    d.n_rows = nr;
-    void* owned[2] = {nullptr, nullptr};
+    ResultSet set;
     if (n) {
-        if (on_device) {
-            hipError_t e = hipMalloc(&owned[0], (size_t)n * sizeof(Deviation));
-            if (e == hipSuccess && want_rows) e = hipMalloc(&owned[1], (size_t)n * sizeof(Row));
-            if (e != hipSuccess) {
-                for (void* q : owned) (void)hipFree(q);
-                return fail(h, HFPF_ERR_HIP, "compare_mesh: device allocation of %llu rows failed: %s", (unsigned long long)nr, hipGetErrorString(e));
-            }
-            d.dev = (Deviation*)owned[0], d.rows = (Row*)owned[1];
-        } else {
-            if ((rc = scratch(h, h->dev_out, (size_t)n * sizeof(Deviation)))) return rc;
-            d.dev = (Deviation*)h->dev_out.p, d.rows = want_rows ? (Row*)h->rows_dev.p : nullptr;
-        }
+        set.add((size_t)n * sizeof(Row), !want_rows, rows);
+        set.add((size_t)n * sizeof(Deviation));
+        if ((rc = result_alloc(h, set, on_device, "compare_mesh"))) return rc;
         const uint64_t* pairs = h->dev_pairs.p ? (const uint64_t*)h->dev_pairs.p + h_ctr[DC_PAIRS] : nullptr;  // read only inside a non-empty range
         const DevTri* recs = n_tris ? (const DevTri*)((char*)h->dev_tri.p + (size_t)std::max<uint64_t>(n_verts, 1) * 24) : nullptr;
         hipLaunchKernelGGL(k_dev_rows, dim3((unsigned)nb), dim3(256), 0, h->stream, rows, (const uint32_t*)h->vals_b.p, (const uint32_t*)ub_start, (const uint32_t*)tstart,
-                           (const uint32_t*)tend, pairs, recs, p.md2, (uint32_t)p.tile, d.dev, d_sum);
+                           (const uint32_t*)tend, pairs, recs, p.md2, (uint32_t)p.tile, (Deviation*)set.a[1].dev, d_sum);
     }
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) rc = timed_end(h, timed, h->ev_pending_dev);
-    if (e == hipSuccess && !rc && on_device && want_rows && n) e = hipMemcpyAsync(d.rows, rows, (size_t)n * sizeof(Row), hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) rc = timed.file(kTimeCompare);
+    if (e == hipSuccess && !rc && on_device && want_rows && n) e = hipMemcpyAsync(set.a[0].dev, rows, (size_t)n * sizeof(Row), hipMemcpyDeviceToDevice, h->stream);
     DevSummary hs;
     if (e == hipSuccess && !rc) e = hipMemcpyAsync(&hs, d_sum, sizeof hs, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && !rc) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess || rc) {
-        for (void* q : owned) (void)hipFree(q);
+        set.release();
         return rc ? rc : fail(h, HFPF_ERR_HIP, "compare_mesh: %s", hipGetErrorString(e));
     }
     memset(summary, 0, sizeof *summary);
@@ -3432,7 +3424,7 @@ static int compare_locked(hfpf_handle* h, const hfpf_deviation_opts* o, const vo
     summary->n_tris_invalid = h_ctr[DC_INVALID], summary->n_tris_valid = n_tris - h_ctr[DC_INVALID];
     memcpy(&summary->max_abs, &hs.max_abs_bits, 4);
     summary->sum_abs_q30 = hs.sum_abs_q30, summary->sum_sq_q30 = hs.sum_sq_q30;
-    *out = d;
+    *out = set;
     return HFPF_OK;
 }
 
@@ -3462,11 +3454,11 @@ int hfpf_compare_mesh_device(hfpf_handle* h, const hfpf_deviation_opts* o, const
     if (const char* f = compare_args_fault(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, dev_dev, n_rows, summary, true))
         return fail(h, HFPF_ERR_BAD_ARG, "compare_mesh_device: %s", f);
     if (int rc = local_read_prologue_locked(h, "compare_mesh")) return rc;
-    DevOut d;
+    ResultSet set;
     hfpf_deviation_summary s;
-    if (int rc = compare_locked(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, true, dev_rows != nullptr, &d, &s)) return rc;
-    if (dev_rows) *dev_rows = (hfpf_row*)d.rows;
-    *dev_dev = (hfpf_deviation*)d.dev, *n_rows = d.n_rows, *summary = s;
+    if (int rc = compare_locked(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, true, dev_rows != nullptr, &set, &s)) return rc;
+    if (dev_rows) *dev_rows = (hfpf_row*)set.a[0].dev;
+    *dev_dev = (hfpf_deviation*)set.a[1].dev, *n_rows = s.n_rows, *summary = s;
     return HFPF_OK;
 }
 
@@ -3484,29 +3476,16 @@ int hfpf_compare_mesh(hfpf_handle* h, const hfpf_deviation_opts* o, const void* 
     hipError_t e = v_bytes ? upload_pageable(h, h->dev_mesh.p, verts, v_bytes) : hipSuccess;
     if (e == hipSuccess && t_bytes) e = upload_pageable(h, (char*)h->dev_mesh.p + v_room, tris, t_bytes);
     if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "compare_mesh upload: %s", hipGetErrorString(e));
-    DevOut d;
+    ResultSet set;
     hfpf_deviation_summary s;
     if (int rc = compare_locked(h, o, h->dev_mesh.p, n_verts, vertex_stride, (const uint32_t*)((char*)h->dev_mesh.p + v_room), n_tris, pose_3x4, false, rows != nullptr,
-                                &d, &s))
+                                &set, &s))
         return rc;
-    hfpf_row* hr = nullptr;
-    hfpf_deviation* hd = nullptr;
-    if (d.n_rows) {
-        hr = rows ? (hfpf_row*)host_result_alloc(d.n_rows * sizeof(hfpf_row)) : nullptr;
-        hd = (hfpf_deviation*)host_result_alloc(d.n_rows * sizeof(hfpf_deviation));
-        if ((rows && !hr) || !hd) {
-            free(hr), free(hd);
-            return fail(h, HFPF_ERR_CAPACITY, "compare_mesh: host allocation of %llu rows failed", (unsigned long long)d.n_rows);
-        }
-        e = rows ? download_pageable(h, hr, d.rows, d.n_rows * sizeof(hfpf_row)) : hipSuccess;
-        if (e == hipSuccess) e = download_pageable(h, hd, d.dev, d.n_rows * sizeof(hfpf_deviation));
-        if (e != hipSuccess) {
-            free(hr), free(hd);
-            return fail(h, HFPF_ERR_HIP, "compare_mesh copy: %s", hipGetErrorString(e));
-        }
-    }
-    if (rows) *rows = hr;
-    *dev = hd, *n_rows = d.n_rows, *summary = s;
+    void* host[3] = {nullptr, nullptr, nullptr};
+    if (s.n_rows)
+        if (int rc = result_to_host(h, set, "compare_mesh", host)) return rc;
+    if (rows) *rows = (hfpf_row*)host[0];
+    *dev = (hfpf_deviation*)host[1], *n_rows = s.n_rows, *summary = s;
     return HFPF_OK;
 }
 
@@ -4197,7 +4176,7 @@ int snap_stage_alloc(hfpf_handle* h, uint64_t payload, uint64_t* window)
         HIPCHK(h, hipStreamSynchronize(h->stream));
         HIPCHK(h, hipFree(h->snap_stage.p));
         h->device_bytes -= h->snap_stage.bytes;
-        h->snap_stage = DevBuf{};
+        h->snap_stage.p = nullptr, h->snap_stage.bytes = 0;
     }
     for (;;) {
         void* p = nullptr;
@@ -4695,41 +4674,21 @@ int hfpf_kernel_timing(hfpf_handle* h, int enable)
     h->timing = enable != 0;
     h->timing_detail = enable == 2;
     if (enable) {
-        for (int k = 0; k < 3; k++) h->t_detail_ms[k] = 0, h->n_detail[k] = 0;
-        h->t_integrate_ms = 0;
-        h->n_integrate_launches = 0;
-        h->t_clean_ms = 0;
-        h->n_clean_timed = 0;
-        h->t_ray_ms = 0;
-        h->n_ray_timed = 0;
-        h->t_comp_ms = 0;
-        h->n_comp_timed = 0;
-        h->t_dev_ms = 0;
-        h->n_dev_timed = 0;
+        for (TimedId& t : h->timed) t.ms = 0, t.n = 0;
     }
     return HFPF_OK;
 }
 
 int hfpf_get_kernel_time(hfpf_handle* h, int kernel_id, double* total_ms, uint64_t* launches)
 {
-    if (!h || kernel_id < 0 || kernel_id > 7) return HFPF_ERR_BAD_ARG;
+    if (!h || kernel_id < 0 || kernel_id >= kTimedIds) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (int rcf = flush_pending_locked(h)) return rcf;  // host frames still waiting for their launch
     int rc = resolve_timing(h);
     if (rc) return rc;
-    if (kernel_id >= 5) {
-        if (total_ms) *total_ms = kernel_id == 5 ? h->t_ray_ms : kernel_id == 6 ? h->t_comp_ms : h->t_dev_ms;
-        if (launches) *launches = kernel_id == 5 ? h->n_ray_timed : kernel_id == 6 ? h->n_comp_timed : h->n_dev_timed;
-        return HFPF_OK;
-    }
-    if (kernel_id >= 2) {
-        if (total_ms) *total_ms = h->t_detail_ms[kernel_id - 2];
-        if (launches) *launches = h->n_detail[kernel_id - 2];
-        return HFPF_OK;
-    }
-    if (total_ms) *total_ms = kernel_id == 0 ? h->t_integrate_ms : h->t_clean_ms;
-    if (launches) *launches = kernel_id == 0 ? h->n_integrate_launches : h->n_clean_timed;
+    if (total_ms) *total_ms = h->timed[kernel_id].ms;
+    if (launches) *launches = h->timed[kernel_id].n;
     return HFPF_OK;
 }
 
