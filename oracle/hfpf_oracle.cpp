@@ -93,7 +93,8 @@ inline V3 normalized3(const V3& a)
 
 // grid.hpp:40-49  projectPointToVector(pt, norm_pt, n); kBballRadius (double 0.015, grid.hpp:35)
 // is converted to the vector's scalar type (float) by Eigen's scalar promotion.
-inline V3 project_point_to_vector(const V3& pt, const V3& norm_pt, const V3& n, float ball_r)
+// s_out (exact moments only): the projection parameter s of proj = a - s*ab, the one number the engine's statistics keep per pair.
+inline V3 project_point_to_vector(const V3& pt, const V3& norm_pt, const V3& n, float ball_r, float* s_out = nullptr)
 {
     V3 d_xyz = mul3(ball_r, n);
     V3 a = sub3(norm_pt, d_xyz);
@@ -102,7 +103,16 @@ inline V3 project_point_to_vector(const V3& pt, const V3& norm_pt, const V3& n, 
     V3 ab = sub3(a, b);
     float s = dot3(ap, ab) / dot3(ab, ab);
     V3 p = sub3(a, mul3(s, ab));
+    if (s_out) *s_out = s;
     return p;
+}
+// The line the function above projects onto, alone: a and ab as f32, formed by the same operations.
+inline void line_of(const V3& norm_pt, const V3& n, float ball_r, V3& a, V3& ab)
+{
+    V3 d_xyz = mul3(ball_r, n);
+    a = sub3(norm_pt, d_xyz);
+    V3 b = add3(norm_pt, d_xyz);
+    ab = sub3(a, b);
 }
 
 // x86 cvttsd2si semantics for double -> int (what `int xv = floor(...)` does in the reference
@@ -253,6 +263,9 @@ struct VoxelInfo {
     // buffered points keep their packed rgb and every cylinder member adds its r, g, b to the voxel it updates.
     std::vector<uint32_t> buffer_rgb;
     uint64_t csum[3] = {0, 0, 0};
+    // EXACT MOMENTS (Config::exact_moments, not in the reference): the engine's integer statistic words 0-4 (csrc/stats.hpp) of the same
+    // members, allocated with the first member; absent = all zero.  The colour words 5-7 are csum.
+    std::unique_ptr<int64_t[]> m;
 };
 
 struct Voxel {
@@ -268,6 +281,11 @@ struct Row {  // 64 bytes; mirrored by oracle.py
     float sdx, sdy, sdz;
     float mean_dist, sd_dist;
     uint32_t rgb;
+};
+
+struct MomentRec {  // 80 bytes; mirrored by oracle.py
+    int32_t ix, iy, iz, pad;
+    int64_t m[8];  // the engine's record: count, sum u, sum u^2, sum d, sum d^2 in fixed point, sums of r, g, b (0 without fuse_color)
 };
 
 struct Config {  // mirrored by oracle.py
@@ -286,6 +304,7 @@ struct Config {  // mirrored by oracle.py
     int32_t fuse_color;      // EXTENSION: 1 = per-voxel mean colour of the cylinder members (definition in extract())
     int32_t dense;           // 1 = the reference's storage: one 16-byte Voxel per cell of the (dim+1)^3 box (grid.hpp:108,626);
                              //     0 = hash map of touched cells (needed for the 10^10-cell configs).  Same results either way.
+    int32_t exact_moments;   // 1 = every member also adds the engine's fixed-point contribution to int64 words (moments(), extract_exact())
 };
 
 class Oracle {
@@ -313,6 +332,15 @@ public:
                     dz.push_back(kk);
                 }
         ball_r_f = (float)c.ball_radius;
+        exact_ = c.exact_moments != 0;
+        {   // the engine's fixed-point scales, restated from this config (hfpf.hip setup_params): one contribution stays below 2^27
+            const double Bs = 0.5 + ((double)c.K + 2.0) * xres_ / (2.0 * c.ball_radius);  // bound of s over the cells of a line
+            const double Bm = Bs - 0.5;                                                  // bound of u = s - 0.5
+            fs_ = stat_scale_for(Bm);
+            fss_ = stat_scale_for(Bm * Bm);
+            fd_ = stat_scale_for(c.cylinder_radius);
+            fdd_ = stat_scale_for(c.cylinder_radius * c.cylinder_radius);
+        }
         if (c.dense) {  // construct(), grid.hpp:626: (xdim+1)(ydim+1)(zdim+1) voxels of {bool occupied; void* data}
             dense_n_ = (size_t)(xdim_ + 1) * (size_t)(ydim_ + 1) * (size_t)(zdim_ + 1);
             dense_ = (Voxel*)calloc(dense_n_, sizeof(Voxel));  // all-zero = {false, nullptr}; pages are touched on first use
@@ -362,6 +390,9 @@ public:
     int xdim_, ydim_, zdim_;
     std::vector<int> dx, dy, dz;
     float ball_r_f;
+    bool exact_ = false;
+    float fs_, fss_, fd_, fdd_;
+    static float stat_scale_for(double bound) { return (float)std::ldexp(1.0, 26 - (int)std::floor(std::log2(bound))); }
     bool state_changed = false;
     uint64_t n_presented = 0, n_zclip_pass = 0, n_inserted = 0;
 
@@ -451,9 +482,30 @@ public:
         d->csum[2] += rgb & 255u;
     }
 
+    // EXACT MOMENTS: one member's contribution as csrc/stats.hpp pair_delta defines it.  f32, unfused (this file is built with
+    // -ffp-contract=off), rintf = round to nearest even, then widened; s = the projection parameter, dist = the f32 norm.
+    void add_moments(VoxelInfo* d, float s, float dist) const
+    {
+        if (!d->m) d->m.reset(new int64_t[5]());
+        const float u = s - 0.5f;
+        d->m[0] += 1;
+        d->m[1] += (int64_t)rintf(u * fs_);
+        d->m[2] += (int64_t)rintf((u * u) * fss_);
+        d->m[3] += (int64_t)rintf(dist * fd_);
+        d->m[4] += (int64_t)rintf((dist * dist) * fdd_);
+    }
+
     // grid.hpp:185-280 addPoints<N>(cloud, viewpoint).  Points are already in the fusion frame.
     // rgb (optional, colour extension): the points' packed colours.
+    // EXACT (here and in clean, capture_mt, clean_mt): the exact-moments form is a second instantiation, so that the form with the
+    // option off is the code it was before the option existed (bench.py times it as the CPU baseline).
     void add_points(const V3* pts, size_t n, const V3& viewpoint, const uint32_t* rgb = nullptr)
+    {
+        if (exact_) add_points_t<true>(pts, n, viewpoint, rgb);
+        else add_points_t<false>(pts, n, viewpoint, rgb);
+    }
+    template <bool EXACT>
+    void add_points_t(const V3* pts, size_t n, const V3& viewpoint, const uint32_t* rgb)
     {
         const bool color = cfg.fuse_color != 0 && rgb != nullptr;
         state_changed = true;
@@ -502,11 +554,13 @@ public:
                 own_coords(data->dependants[i], xx, yy, zz);
                 VoxelInfo* dep = find_voxel(xx, yy, zz)->data;
                 V3 dep_centre = voxel_center(xx, yy, zz);
-                V3 proj = project_point_to_vector(ptv, dep_centre, dep->normal, ball_r_f);
+                float s = 0.f;
+                V3 proj = project_point_to_vector(ptv, dep_centre, dep->normal, ball_r_f, EXACT ? &s : nullptr);
                 double distance_to_normal = (double)norm3(sub3(ptv, proj));
                 if (distance_to_normal < cfg.cylinder_radius) {
                     welford(dep, proj, distance_to_normal);
                     if (color) add_color(dep, rgb[p]);
+                    if constexpr (EXACT) add_moments(dep, s, (float)distance_to_normal);
                 }
             }
         }
@@ -548,6 +602,12 @@ public:
 
     // grid.hpp:311-454 updateThicknessVectors<N,K>
     void clean()
+    {
+        if (exact_) clean_t<true>();
+        else clean_t<false>();
+    }
+    template <bool EXACT>
+    void clean_t()
     {
         state_changed = false;
         std::vector<uint64_t> keys;  // own keys, in processing order
@@ -615,11 +675,13 @@ public:
                         const size_t bl = nd_->buffer.size();
                         for (size_t b = 0; b < bl; b++) {
                             const V3 pt = nd_->buffer[b];
-                            V3 proj = project_point_to_vector(pt, centroid, data->normal, ball_r_f);
+                            float s = 0.f;
+                            V3 proj = project_point_to_vector(pt, centroid, data->normal, ball_r_f, EXACT ? &s : nullptr);
                             double distance_to_normal = (double)norm3(sub3(pt, proj));
                             if (distance_to_normal < cfg.cylinder_radius) {
                                 welford(data, proj, distance_to_normal);
                                 if (cfg.fuse_color && b < nd_->buffer_rgb.size()) add_color(data, nd_->buffer_rgb[b]);
+                                if constexpr (EXACT) add_moments(data, s, (float)distance_to_normal);
                             }
                         }
                     } else {
@@ -693,6 +755,13 @@ public:
     void capture_mt(const uint8_t* base, size_t n, uint32_t point_step, uint32_t off_x, uint32_t off_y, uint32_t off_z,
                     const double* T)
     {
+        if (exact_) capture_mt_t<true>(base, n, point_step, off_x, off_y, off_z, T);
+        else capture_mt_t<false>(base, n, point_step, off_x, off_y, off_z, T);
+    }
+    template <bool EXACT>
+    void capture_mt_t(const uint8_t* base, size_t n, uint32_t point_step, uint32_t off_x, uint32_t off_y, uint32_t off_z,
+                      const double* T)
+    {
         if (!shards_) shards_.reset(new Shard[kShards]);
         state_changed = true;
         const V3 viewpoint = {(float)T[3], (float)T[7], (float)T[11]};
@@ -750,9 +819,13 @@ public:
                 Shard& ds = shards_[shard_of(dk)];
                 std::lock_guard<std::mutex> lk(ds.m);
                 VoxelInfo* dep = ds.map.find(dk)->second.data;
-                V3 proj = project_point_to_vector(q, centre, dep->normal, ball_r_f);
+                float s = 0.f;
+                V3 proj = project_point_to_vector(q, centre, dep->normal, ball_r_f, EXACT ? &s : nullptr);
                 double distance_to_normal = (double)norm3(sub3(q, proj));
-                if (distance_to_normal < cfg.cylinder_radius) welford(dep, proj, distance_to_normal);
+                if (distance_to_normal < cfg.cylinder_radius) {
+                    welford(dep, proj, distance_to_normal);
+                    if constexpr (EXACT) add_moments(dep, s, (float)distance_to_normal);
+                }
             }
         }
         n_presented += presented;
@@ -770,6 +843,12 @@ public:
     }
 
     void clean_mt()
+    {
+        if (exact_) clean_mt_t<true>();
+        else clean_mt_t<false>();
+    }
+    template <bool EXACT>
+    void clean_mt_t()
     {
         state_changed = false;
         if (!shards_) return;
@@ -861,9 +940,13 @@ public:
                     const size_t bl = target->buffer.size();
                     for (size_t b = 0; b < bl; b++) {
                         const V3 pt = target->buffer[b];
-                        V3 proj = project_point_to_vector(pt, centroid, data->normal, ball_r_f);
+                        float s = 0.f;
+                        V3 proj = project_point_to_vector(pt, centroid, data->normal, ball_r_f, EXACT ? &s : nullptr);
                         double distance_to_normal = (double)norm3(sub3(pt, proj));
-                        if (distance_to_normal < cfg.cylinder_radius) welford(data, proj, distance_to_normal);
+                        if (distance_to_normal < cfg.cylinder_radius) {
+                            welford(data, proj, distance_to_normal);
+                            if constexpr (EXACT) add_moments(data, s, (float)distance_to_normal);
+                        }
                     }
                 }
             }
@@ -918,6 +1001,89 @@ public:
             r.mean_dist = d->mean_dist;
             r.sd_dist = d->sd_dist;
             r.rgb = 0;
+        }
+    }
+
+    // ---- EXACT MOMENTS read-outs: the row set and order of extract() (mt = false) or extract_mt() (mt = true) ----
+    std::vector<std::pair<uint64_t, const VoxelInfo*>> emitted(bool mt) const
+    {
+        std::vector<std::pair<uint64_t, const VoxelInfo*>> found;
+        auto take = [&](uint64_t key, const Voxel& v) {
+            if (!v.occupied || !v.data->normal_found) return;
+            int x, y, z;
+            own_coords(key, x, y, z);
+            if (valid_coord(x, y, z)) found.push_back({key, v.data});
+        };
+        if (!mt) {
+            for_each_voxel(take);
+        } else if (shards_) {
+            for (int s = 0; s < kShards; s++)
+                for (auto& kv : shards_[s].map) take(kv.first, kv.second);
+        }
+        std::sort(found.begin(), found.end());
+        return found;
+    }
+    static void words_of(const VoxelInfo* d, int64_t w[8])
+    {
+        for (int i = 0; i < 5; i++) w[i] = d->m ? d->m[i] : 0;
+        for (int i = 0; i < 3; i++) w[5 + i] = (int64_t)d->csum[i];
+    }
+    void moments(bool mt, std::vector<MomentRec>& out) const
+    {
+        const auto found = emitted(mt);
+        out.resize(found.size());
+        for (size_t i = 0; i < found.size(); i++) {
+            MomentRec& r = out[i];
+            own_coords(found[i].first, r.ix, r.iy, r.iz);
+            r.pad = 0;
+            words_of(found[i].second, r.m);
+        }
+    }
+    // The engine's "words -> row" (csrc/kernels.hpp record_centroid / record_row) restated: f64, this operation order, unfused.  a, ab
+    // are the f32 line this oracle projects onto; integer columns and normals are extract()'s.
+    void extract_exact(bool mt, std::vector<Row>& rows) const
+    {
+        const auto found = emitted(mt);
+        rows.resize(found.size());
+        for (size_t i = 0; i < found.size(); i++) {
+            const VoxelInfo* d = found[i].second;
+            Row& r = rows[i];
+            own_coords(found[i].first, r.ix, r.iy, r.iz);
+            r.count = (uint32_t)d->count;
+            r.nx = d->normal.x, r.ny = d->normal.y, r.nz = d->normal.z;
+            r.x = r.y = r.z = 0.f;
+            r.sdx = r.sdy = r.sdz = 0.f;
+            r.mean_dist = r.sd_dist = 0.f;
+            r.rgb = 0;
+            int64_t w[8];
+            words_of(d, w);
+            const int64_t cnt = w[0];
+            if (cnt <= 0) continue;  // the zero row
+            V3 af, abf;
+            line_of(voxel_center(r.ix, r.iy, r.iz), d->normal, ball_r_f, af, abf);
+            const double ax = af.x, ay = af.y, az = af.z, abx = abf.x, aby = abf.y, abz = abf.z;
+            const double inv = 1.0 / (double)cnt;
+            const double em = ((double)w[1] / (double)fs_) * inv;  // mean of u = s - 0.5
+            const double es = 0.5 + em;
+            r.x = (float)(ax - es * abx);
+            r.y = (float)(ay - es * aby);
+            r.z = (float)(az - es * abz);
+            double vs = ((double)w[2] / (double)fss_) * inv - em * em;
+            const double md = ((double)w[3] / (double)fd_) * inv;
+            double vd = ((double)w[4] / (double)fdd_) * inv - md * md;
+            if (cnt == 1) vs = vd = 0.0;
+            vs = fmax(vs, 0.0);
+            r.sdx = (float)(abx * abx * vs);
+            r.sdy = (float)(aby * aby * vs);
+            r.sdz = (float)(abz * abz * vs);
+            r.mean_dist = (float)md;
+            r.sd_dist = (float)fmax(vd, 0.0);
+            if (cfg.fuse_color) {  // mean colour per channel, round half up: floor(sum / cnt + 1/2) in integers
+                const uint32_t cr = (uint32_t)((2 * w[5] + cnt) / (2 * cnt));
+                const uint32_t cg = (uint32_t)((2 * w[6] + cnt) / (2 * cnt));
+                const uint32_t cb = (uint32_t)((2 * w[7] + cnt) / (2 * cnt));
+                r.rgb = (std::min(cr, 255u) << 16) | (std::min(cg, 255u) << 8) | std::min(cb, 255u);
+            }
         }
     }
 
@@ -1026,6 +1192,32 @@ uint64_t horacle_extract_mt(void* h, Row* out, uint64_t cap)
         memcpy(out, rows.data(), n * sizeof(Row));
     }
     return rows.size();
+}
+// exact moments (Config::exact_moments = 1); mt = 1 reads the all-cores variant's store
+uint64_t horacle_moments(void* h, MomentRec* out, uint64_t cap, int32_t mt)
+{
+    std::vector<MomentRec> recs;
+    ((Oracle*)h)->moments(mt != 0, recs);
+    if (out) {
+        uint64_t n = std::min<uint64_t>(cap, recs.size());
+        memcpy(out, recs.data(), n * sizeof(MomentRec));
+    }
+    return recs.size();
+}
+uint64_t horacle_extract_exact(void* h, Row* out, uint64_t cap, int32_t mt)
+{
+    std::vector<Row> rows;
+    ((Oracle*)h)->extract_exact(mt != 0, rows);
+    if (out) {
+        uint64_t n = std::min<uint64_t>(cap, rows.size());
+        memcpy(out, rows.data(), n * sizeof(Row));
+    }
+    return rows.size();
+}
+void horacle_scales(void* h, float out[4])  // fixed-point scales of words 1-4
+{
+    Oracle* o = (Oracle*)h;
+    out[0] = o->fs_, out[1] = o->fss_, out[2] = o->fd_, out[3] = o->fdd_;
 }
 void horacle_counters(void* h, uint64_t out[6])
 {
@@ -1163,5 +1355,6 @@ void horacle_probe_eigen33(const float* m9, float* vec_out)
 }
 uint64_t horacle_sizeof_row(void) { return sizeof(Row); }
 uint64_t horacle_sizeof_config(void) { return sizeof(Config); }
+uint64_t horacle_sizeof_moment(void) { return sizeof(MomentRec); }
 
 }  // extern "C"

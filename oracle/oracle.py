@@ -29,6 +29,7 @@ class Config(C.Structure):
         ("pcl_shifted_cov", C.c_int32),
         ("fuse_color", C.c_int32),
         ("dense", C.c_int32),
+        ("exact_moments", C.c_int32),
     ]
 
 
@@ -41,6 +42,11 @@ ROW_DTYPE = np.dtype(
         ("mean_dist", "<f4"), ("sd_dist", "<f4"), ("rgb", "<u4"),
     ]
 )
+
+
+# One record of OracleGrid.moments(): the cell and the engine's eight int64 statistic words (csrc/stats.hpp): count, sums of
+# rint(u * fs), rint(u*u * fss), rint(d * fd), rint(d*d * fdd), sums of r, g, b (0 without fuse_color).
+MOMENT_DTYPE = np.dtype([("ix", "<i4"), ("iy", "<i4"), ("iz", "<i4"), ("pad", "<i4"), ("m", "<i8", (8,))])
 
 
 def build(force=False):
@@ -84,6 +90,11 @@ def lib():
         L.horacle_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.horacle_extract.restype = C.c_uint64
         L.horacle_counters.argtypes = [C.c_void_p, C.c_void_p]
+        L.horacle_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32]
+        L.horacle_moments.restype = C.c_uint64
+        L.horacle_extract_exact.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32]
+        L.horacle_extract_exact.restype = C.c_uint64
+        L.horacle_scales.argtypes = [C.c_void_p, C.c_void_p]
         L.horacle_occupied.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.horacle_occupied.restype = C.c_uint64
         L.horacle_dependants.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64]
@@ -99,8 +110,10 @@ def lib():
         L.horacle_probe_eigen33.argtypes = [C.c_void_p, C.c_void_p]
         L.horacle_sizeof_row.restype = C.c_uint64
         L.horacle_sizeof_config.restype = C.c_uint64
+        L.horacle_sizeof_moment.restype = C.c_uint64
         assert L.horacle_sizeof_row() == ROW_DTYPE.itemsize
         assert L.horacle_sizeof_config() == C.sizeof(Config)
+        assert L.horacle_sizeof_moment() == MOMENT_DTYPE.itemsize
         _lib = L
     return _lib
 
@@ -110,7 +123,8 @@ def _p(a):
 
 
 def make_config(resolution=0.005, bbox=(-0.8, 1.8, -1.5, 1.5, 0.0, 1.0), k=2, K=3, gate=20, cylinder_radius=0.001,
-                ball_radius=0.015, z_clip=(0.28, 0.6), order_mode=0, reserve=0, pcl_shifted_cov=False, fuse_color=False, dense=False):
+                ball_radius=0.015, z_clip=(0.28, 0.6), order_mode=0, reserve=0, pcl_shifted_cov=False, fuse_color=False, dense=False,
+                exact_moments=False):
     """Defaults are the reference's constants (node.cpp:91-93,163,311; grid.hpp:34-36,352; launch:7)."""
     c = Config()
     c.resolution = resolution
@@ -123,6 +137,9 @@ def make_config(resolution=0.005, bbox=(-0.8, 1.8, -1.5, 1.5, 0.0, 1.0), k=2, K=
     c.pcl_shifted_cov = 1 if pcl_shifted_cov else 0
     c.fuse_color = 1 if fuse_color else 0  # EXTENSION (not in the reference): mean colour of the cylinder members
     c.dense = 1 if dense else 0  # the reference's storage: 16 B per cell of the whole box (grid.hpp:626) instead of a hash map
+    # not in the reference: every member also adds the engine's fixed-point contribution (csrc/stats.hpp) to int64 words, read out
+    # by moments() / extract_exact(); off = the reference's recurrences alone
+    c.exact_moments = 1 if exact_moments else 0
     return c
 
 
@@ -215,6 +232,33 @@ class OracleGrid:
         if n:
             lib().horacle_extract(self._h, _p(rows), n)
         return rows
+
+    # Exact moments (exact_moments=True): the engine's order-free integer statistics of the same members.  Row set and order are
+    # extract()'s; mt=True reads the store of capture_mt()/clean_mt() instead (row set and order of extract_mt()).
+    def moments(self, mt=False):
+        """MOMENT_DTYPE records: the cell and the eight int64 words of every emitted row."""
+        assert self.cfg.exact_moments, "the grid was created without exact_moments=True"
+        n = lib().horacle_moments(self._h, None, 0, int(mt))
+        out = np.zeros(n, dtype=MOMENT_DTYPE)
+        if n:
+            lib().horacle_moments(self._h, _p(out), n, int(mt))
+        return out
+
+    def extract_exact(self, mt=False):
+        """Rows whose float columns are the engine's f64 expression (csrc/kernels.hpp record_row) of those words and the voxel's
+        f32 line; integer columns and normals as extract()."""
+        assert self.cfg.exact_moments, "the grid was created without exact_moments=True"
+        n = lib().horacle_extract_exact(self._h, None, 0, int(mt))
+        rows = np.zeros(n, dtype=ROW_DTYPE)
+        if n:
+            lib().horacle_extract_exact(self._h, _p(rows), n, int(mt))
+        return rows
+
+    def scales(self):
+        """The four power-of-two scales of words 1-4 as this grid restates them from its config (f32)."""
+        out = np.zeros(4, dtype=np.float32)
+        lib().horacle_scales(self._h, _p(out))
+        return out
 
     def counters(self):
         out = np.zeros(6, dtype=np.uint64)
