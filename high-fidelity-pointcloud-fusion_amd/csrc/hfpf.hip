@@ -332,6 +332,7 @@ struct hfpf_handle {
     // hfpf_compare_mesh*: the host form's mesh, the transformed vertices and triangle records, the bricks' keys / ranges / counters /
     // summary, the (brick, triangle) pairs (unsorted and sorted)
     DevBuf dev_mesh{bufs}, dev_tri{bufs}, dev_bins{bufs}, dev_pairs{bufs};
+    DevBuf align_dev{bufs}, align_acc{bufs};  // hfpf_align_mesh*: one iteration's deviation records, its 29 int64 sums
     DevBuf ray_in{bufs}, ray_out{bufs}, ray_map{bufs};  // hfpf_raycast*: a host chunk's rays, a chunk's (or band's) hits, the empty-space maps
     DevBuf snap_stage{bufs}, snap_err{bufs};            // hfpf_snapshot / hfpf_restore: the staging buffer (or one window of it), the range check's error word
     uint64_t bin_pool = 0;           // entries in bin_pt
@@ -3310,20 +3311,71 @@ static unsigned bits_for_count(uint64_t n)  // bits that hold 0..n-1 (at least 1
     return b;
 }
 
-// Validated arguments in, the mesh on the device, under the lock.  The row set; then (timed as kernel id 7) the rows keyed by the
-// brick of their point and sorted, the list of bricks that hold rows, the transformed vertices, the triangles' records and pair count,
-// the pairs, their sort and per-brick ranges, and k_dev_rows into *out (the rows -- absent without want_rows; the host form takes
-// them from h->rows_dev --, the deviations; empty without rows).  The read-backs are the sizes between the stages and the summary.
-static int compare_locked(hfpf_handle* h, const hfpf_deviation_opts* o, const void* d_verts, uint64_t n_verts, uint32_t stride, const uint32_t* d_tris,
-                          uint64_t n_tris, const double* pose, bool on_device, bool want_rows, ResultSet* out, hfpf_deviation_summary* summary)
+// The two halves of a compare, shared with hfpf_align_mesh*.  ROW SIDE (compare_row_side_locked, once per call; it does not depend on
+// the pose): the rows of h->rows_dev keyed by the brick of their point and sorted, and the list of bricks that hold rows.  MESH SIDE
+// (compare_mesh_side_locked, once per pose): the transformed vertices, the triangles' records and pair count, the pairs, their sort
+// and per-brick ranges, and k_dev_rows into a Deviation array.  The read-backs are the sizes between the stages.
+struct DevRowSide {
+    uint32_t n = 0;   // rows
+    uint64_t nb = 0;  // bricks that hold rows
+    // slices of h->dev_bins
+    uint64_t* ub_key = nullptr;
+    unsigned long long* ctr = nullptr;
+    DevSummary* d_sum = nullptr;
+    uint32_t *ub_start = nullptr, *tstart = nullptr, *tend = nullptr;
+};
+
+// what: the caller's name in messages.  Allocates; a compare opens its Timed bracket behind it, before compare_row_side_locked.
+static int compare_row_scratch_locked(hfpf_handle* h, uint64_t nr, const char* what, DevRowSide* rs, uint32_t** flag, uint32_t** base)
 {
-    *out = ResultSet{};
-    int rc;
-    uint64_t nr = 0;
-    const ExtractOpts opt{o->min_count, -1, 0};  // the compare of hfpf_extract_filtered, 0 keeps all
-    if ((rc = build_rows_locked(h, h->t.stats, opt, &nr))) return rc;
-    if (nr >= 0xFFFFFFFFull) return fail(h, HFPF_ERR_CAPACITY, "compare_mesh: %llu rows exceed the 32-bit row index", (unsigned long long)nr);
+    if (nr >= 0xFFFFFFFFull) return fail(h, HFPF_ERR_CAPACITY, "%s: %llu rows exceed the 32-bit row index", what, (unsigned long long)nr);
     const uint32_t n = (uint32_t)nr;
+    const size_t R1 = (size_t)n + 1;
+    const size_t bins_bytes = (size_t)n * 8 + DC_WORDS * 8 + sizeof(DevSummary) + (3 * R1 + 2 * (size_t)n) * 4;
+    if (int rc = scratch(h, h->dev_bins, bins_bytes)) return rc;
+    rs->n = n;
+    rs->ub_key = (uint64_t*)h->dev_bins.p;
+    rs->ctr = (unsigned long long*)(rs->ub_key + n);
+    rs->d_sum = (DevSummary*)(rs->ctr + DC_WORDS);
+    *flag = (uint32_t*)(rs->d_sum + 1);
+    *base = *flag + R1;
+    rs->ub_start = *base + R1;
+    rs->tstart = rs->ub_start + R1;
+    rs->tend = rs->tstart + n;
+    return HFPF_OK;
+}
+
+static int compare_row_side_locked(hfpf_handle* h, DevRowSide* rs, uint32_t* flag, uint32_t* base)
+{
+    const uint32_t n = rs->n;
+    if (!n) return HFPF_OK;
+    int rc;
+    const GridParams& g = h->g;
+    const Row* rows = (const Row*)h->rows_dev.p;
+    const size_t R1 = (size_t)n + 1;
+    const dim3 grid_r(blocks_for(n, 256)), grid_r1(blocks_for(R1, 256));
+    hipLaunchKernelGGL(k_dev_row_keys, grid_r, dim3(256), 0, h->stream, g, rows, n, (uint64_t*)h->keys_a.p, (uint32_t*)h->vals_a.p);
+    HIPCHK(h, hipGetLastError());
+    const unsigned key_bits = bits_for_count((uint64_t)g.bdim[0] * (uint64_t)g.bdim[1] * (uint64_t)g.bdim[2]);
+    if ((rc = sort_pairs_u64(h, (uint64_t*)h->keys_a.p, (uint64_t*)h->keys_b.p, (uint32_t*)h->vals_a.p, (uint32_t*)h->vals_b.p, n, key_bits))) return rc;
+    hipLaunchKernelGGL(k_dev_row_flags, grid_r1, dim3(256), 0, h->stream, (const uint64_t*)h->keys_b.p, n, flag);
+    HIPCHK(h, hipGetLastError());
+    if ((rc = scan_counts_locked(h, flag, base, n, &rs->nb))) return rc;
+    hipLaunchKernelGGL(k_dev_bricks, grid_r1, dim3(256), 0, h->stream, (const uint64_t*)h->keys_b.p, (const uint32_t*)flag, (const uint32_t*)base, n, (uint32_t)rs->nb,
+                       rs->ub_key, rs->ub_start);
+    HIPCHK(h, hipGetLastError());
+    return HFPF_OK;
+}
+
+// The mesh at `pose` against the row side: the counters, the summary and the bricks' triangle ranges are zeroed first, so it may run
+// any number of times behind one row side.  out: n Deviation records (untouched without rows); h_ctr: the DC_WORDS counters read back.
+// The launch of k_dev_rows is left unchecked for the caller's hipGetLastError.
+static int compare_mesh_side_locked(hfpf_handle* h, const DevRowSide& rs, const hfpf_deviation_opts* o, const void* d_verts, uint64_t n_verts, uint32_t stride,
+                                    const uint32_t* d_tris, uint64_t n_tris, const double* pose, Deviation* out, unsigned long long h_ctr[DC_WORDS])
+{
+    int rc;
+    const uint32_t n = rs.n;
+    const uint64_t nb = rs.nb;
     const GridParams& g = h->g;
     DevParams p;
     memcpy(p.T, pose, sizeof p.T);
@@ -3335,39 +3387,10 @@ static int compare_locked(hfpf_handle* h, const hfpf_deviation_opts* o, const vo
     p.reach = 2.0 * (box + 64.0 * g.res + 4.0 * (double)g.ball_r + o->max_distance);
     p.face_cap = 4.0 * g.res;
     p.n_verts = n_verts, p.n_tris = (uint32_t)n_tris, p.stride = stride;
-    p.nb = 0, p.tile = h->knobs.test_dev_tile;
-
-    const size_t R1 = (size_t)n + 1;
-    const size_t bins_bytes = (size_t)n * 8 + DC_WORDS * 8 + sizeof(DevSummary) + (3 * R1 + 2 * (size_t)n) * 4;
-    if ((rc = scratch(h, h->dev_bins, bins_bytes))) return rc;
-    uint64_t* ub_key = (uint64_t*)h->dev_bins.p;
-    unsigned long long* ctr = (unsigned long long*)(ub_key + n);
-    DevSummary* d_sum = (DevSummary*)(ctr + DC_WORDS);
-    uint32_t* flag = (uint32_t*)(d_sum + 1);
-    uint32_t* base = flag + R1;
-    uint32_t* ub_start = base + R1;
-    uint32_t* tstart = ub_start + R1;
-    uint32_t* tend = tstart + n;
-    Timed timed(h);
-    if (timed.rc) return timed.rc;
-    HIPCHK(h, hipMemsetAsync(ctr, 0, DC_WORDS * 8 + sizeof(DevSummary), h->stream));
-    uint64_t nb = 0;
-    const Row* rows = (const Row*)h->rows_dev.p;
-    if (n) {
-        const dim3 grid_r(blocks_for(n, 256)), grid_r1(blocks_for(R1, 256));
-        hipLaunchKernelGGL(k_dev_row_keys, grid_r, dim3(256), 0, h->stream, g, rows, n, (uint64_t*)h->keys_a.p, (uint32_t*)h->vals_a.p);
-        HIPCHK(h, hipGetLastError());
-        const unsigned key_bits = bits_for_count((uint64_t)g.bdim[0] * (uint64_t)g.bdim[1] * (uint64_t)g.bdim[2]);
-        if ((rc = sort_pairs_u64(h, (uint64_t*)h->keys_a.p, (uint64_t*)h->keys_b.p, (uint32_t*)h->vals_a.p, (uint32_t*)h->vals_b.p, n, key_bits))) return rc;
-        hipLaunchKernelGGL(k_dev_row_flags, grid_r1, dim3(256), 0, h->stream, (const uint64_t*)h->keys_b.p, n, flag);
-        HIPCHK(h, hipGetLastError());
-        if ((rc = scan_counts_locked(h, flag, base, n, &nb))) return rc;
-        hipLaunchKernelGGL(k_dev_bricks, grid_r1, dim3(256), 0, h->stream, (const uint64_t*)h->keys_b.p, (const uint32_t*)flag, (const uint32_t*)base, n, (uint32_t)nb,
-                           ub_key, ub_start);
-        HIPCHK(h, hipMemsetAsync(tstart, 0, 2 * (size_t)n * 4, h->stream));
-    }
-    p.nb = (uint32_t)nb;
-    unsigned long long h_ctr[DC_WORDS] = {0, 0, 0, 0};
+    p.nb = (uint32_t)nb, p.tile = h->knobs.test_dev_tile;
+    HIPCHK(h, hipMemsetAsync(rs.ctr, 0, DC_WORDS * 8 + sizeof(DevSummary), h->stream));
+    if (n) HIPCHK(h, hipMemsetAsync(rs.tstart, 0, 2 * (size_t)n * 4, h->stream));
+    for (int i = 0; i < DC_WORDS; i++) h_ctr[i] = 0;
     if (n_tris) {
         const size_t v_bytes = (size_t)std::max<uint64_t>(n_verts, 1) * 24;
         if ((rc = scratch(h, h->dev_tri, v_bytes + (size_t)n_tris * sizeof(DevTri)))) return rc;
@@ -3375,10 +3398,10 @@ static int compare_locked(hfpf_handle* h, const hfpf_deviation_opts* o, const vo
         DevTri* recs = (DevTri*)((char*)h->dev_tri.p + v_bytes);
         const dim3 grid_t(blocks_for(n_tris * 64, 256));
         hipLaunchKernelGGL(k_dev_verts, dim3(blocks_for(n_verts, 256)), dim3(256), 0, h->stream, p, (const uint8_t*)d_verts, V);
-        hipLaunchKernelGGL(k_dev_tris<false>, grid_t, dim3(256), 0, h->stream, g, p, d_tris, (const double*)V, (const uint64_t*)ub_key, recs, ctr, (uint64_t*)nullptr,
+        hipLaunchKernelGGL(k_dev_tris<false>, grid_t, dim3(256), 0, h->stream, g, p, d_tris, (const double*)V, (const uint64_t*)rs.ub_key, recs, rs.ctr, (uint64_t*)nullptr,
                            (uint64_t)0);
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(h_ctr, ctr, sizeof h_ctr, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h_ctr, rs.ctr, DC_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         const uint64_t np = h_ctr[DC_PAIRS];
         if (np) {
@@ -3392,28 +3415,57 @@ static int compare_locked(hfpf_handle* h, const hfpf_deviation_opts* o, const vo
             }
             uint64_t* pairs_in = (uint64_t*)h->dev_pairs.p;
             uint64_t* pairs = pairs_in + np;
-            hipLaunchKernelGGL(k_dev_tris<true>, grid_t, dim3(256), 0, h->stream, g, p, d_tris, (const double*)V, (const uint64_t*)ub_key, recs, ctr, pairs_in, np);
+            hipLaunchKernelGGL(k_dev_tris<true>, grid_t, dim3(256), 0, h->stream, g, p, d_tris, (const double*)V, (const uint64_t*)rs.ub_key, recs, rs.ctr, pairs_in, np);
             HIPCHK(h, hipGetLastError());
             if ((rc = sort_keys_u64(h, pairs_in, pairs, np, 32 + bits_for_count(nb)))) return rc;
-            hipLaunchKernelGGL(k_dev_tri_ranges, dim3(blocks_for(np, 256)), dim3(256), 0, h->stream, (const uint64_t*)pairs, (uint32_t)np, (uint32_t)nb, tstart, tend);
+            hipLaunchKernelGGL(k_dev_tri_ranges, dim3(blocks_for(np, 256)), dim3(256), 0, h->stream, (const uint64_t*)pairs, (uint32_t)np, (uint32_t)nb, rs.tstart, rs.tend);
             HIPCHK(h, hipGetLastError());
         }
     }
+    if (n) {
+        const uint64_t* pairs = h->dev_pairs.p ? (const uint64_t*)h->dev_pairs.p + h_ctr[DC_PAIRS] : nullptr;  // read only inside a non-empty range
+        const DevTri* recs = n_tris ? (const DevTri*)((char*)h->dev_tri.p + (size_t)std::max<uint64_t>(n_verts, 1) * 24) : nullptr;
+        hipLaunchKernelGGL(k_dev_rows, dim3((unsigned)nb), dim3(256), 0, h->stream, (const Row*)h->rows_dev.p, (const uint32_t*)h->vals_b.p, (const uint32_t*)rs.ub_start,
+                           (const uint32_t*)rs.tstart, (const uint32_t*)rs.tend, pairs, recs, p.md2, (uint32_t)p.tile, out, rs.d_sum);
+    }
+    return HFPF_OK;
+}
+
+// Validated arguments in, the mesh on the device, under the lock.  The row set; then (timed as kernel id 7) the row side and the mesh
+// side into *out (the rows -- absent without want_rows; the host form takes them from h->rows_dev --, the deviations; empty without
+// rows), and the read-back of the summary.
+static int compare_locked(hfpf_handle* h, const hfpf_deviation_opts* o, const void* d_verts, uint64_t n_verts, uint32_t stride, const uint32_t* d_tris,
+                          uint64_t n_tris, const double* pose, bool on_device, bool want_rows, ResultSet* out, hfpf_deviation_summary* summary)
+{
+    *out = ResultSet{};
+    int rc;
+    uint64_t nr = 0;
+    const ExtractOpts opt{o->min_count, -1, 0};  // the compare of hfpf_extract_filtered, 0 keeps all
+    if ((rc = build_rows_locked(h, h->t.stats, opt, &nr))) return rc;
+    DevRowSide rs;
+    uint32_t *flag, *base;
+    if ((rc = compare_row_scratch_locked(h, nr, "compare_mesh", &rs, &flag, &base))) return rc;
+    const uint32_t n = rs.n;
+    Timed timed(h);
+    if (timed.rc) return timed.rc;
+    if ((rc = compare_row_side_locked(h, &rs, flag, base))) return rc;
+    const Row* rows = (const Row*)h->rows_dev.p;
     ResultSet set;
     if (n) {
         set.add((size_t)n * sizeof(Row), !want_rows, rows);
         set.add((size_t)n * sizeof(Deviation));
         if ((rc = result_alloc(h, set, on_device, "compare_mesh"))) return rc;
-        const uint64_t* pairs = h->dev_pairs.p ? (const uint64_t*)h->dev_pairs.p + h_ctr[DC_PAIRS] : nullptr;  // read only inside a non-empty range
-        const DevTri* recs = n_tris ? (const DevTri*)((char*)h->dev_tri.p + (size_t)std::max<uint64_t>(n_verts, 1) * 24) : nullptr;
-        hipLaunchKernelGGL(k_dev_rows, dim3((unsigned)nb), dim3(256), 0, h->stream, rows, (const uint32_t*)h->vals_b.p, (const uint32_t*)ub_start, (const uint32_t*)tstart,
-                           (const uint32_t*)tend, pairs, recs, p.md2, (uint32_t)p.tile, (Deviation*)set.a[1].dev, d_sum);
+    }
+    unsigned long long h_ctr[DC_WORDS];
+    if ((rc = compare_mesh_side_locked(h, rs, o, d_verts, n_verts, stride, d_tris, n_tris, pose, (Deviation*)set.a[1].dev, h_ctr))) {
+        set.release();
+        return rc;
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) rc = timed.file(kTimeCompare);
     if (e == hipSuccess && !rc && on_device && want_rows && n) e = hipMemcpyAsync(set.a[0].dev, rows, (size_t)n * sizeof(Row), hipMemcpyDeviceToDevice, h->stream);
     DevSummary hs;
-    if (e == hipSuccess && !rc) e = hipMemcpyAsync(&hs, d_sum, sizeof hs, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(&hs, rs.d_sum, sizeof hs, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && !rc) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess || rc) {
         set.release();
@@ -3445,6 +3497,20 @@ static const char* compare_args_fault(const hfpf_handle* h, const hfpf_deviation
     return nullptr;
 }
 
+// The host forms' mesh to the device (h->dev_mesh): the vertices as they are (stride and all), the indices behind them at a 16-byte
+// boundary (*d_tris).
+static int upload_mesh_locked(hfpf_handle* h, const char* what, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
+                              const uint32_t** d_tris)
+{
+    const size_t v_bytes = n_verts ? (size_t)(n_verts - 1) * vertex_stride + 12 : 0, v_room = (v_bytes + 15) & ~(size_t)15, t_bytes = (size_t)n_tris * 12;
+    if (int rc = scratch(h, h->dev_mesh, v_room + t_bytes + 16)) return rc;
+    hipError_t e = v_bytes ? upload_pageable(h, h->dev_mesh.p, verts, v_bytes) : hipSuccess;
+    if (e == hipSuccess && t_bytes) e = upload_pageable(h, (char*)h->dev_mesh.p + v_room, tris, t_bytes);
+    if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "%s upload: %s", what, hipGetErrorString(e));
+    *d_tris = (const uint32_t*)((char*)h->dev_mesh.p + v_room);
+    return HFPF_OK;
+}
+
 int hfpf_compare_mesh_device(hfpf_handle* h, const hfpf_deviation_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride,
                              const uint32_t* dev_tris, uint64_t n_tris, const double* pose_3x4, hfpf_row** dev_rows, hfpf_deviation** dev_dev,
                              uint64_t* n_rows, hfpf_deviation_summary* summary)
@@ -3470,17 +3536,11 @@ int hfpf_compare_mesh(hfpf_handle* h, const hfpf_deviation_opts* o, const void* 
     if (const char* f = compare_args_fault(h, o, verts, n_verts, vertex_stride, tris, n_tris, pose_3x4, dev, n_rows, summary, false))
         return fail(h, HFPF_ERR_BAD_ARG, "compare_mesh: %s", f);
     if (int rc = local_read_prologue_locked(h, "compare_mesh")) return rc;
-    // the mesh to the device: the vertices as they are (stride and all), the indices behind them at a 16-byte boundary
-    const size_t v_bytes = n_verts ? (size_t)(n_verts - 1) * vertex_stride + 12 : 0, v_room = (v_bytes + 15) & ~(size_t)15, t_bytes = (size_t)n_tris * 12;
-    if (int rc = scratch(h, h->dev_mesh, v_room + t_bytes + 16)) return rc;
-    hipError_t e = v_bytes ? upload_pageable(h, h->dev_mesh.p, verts, v_bytes) : hipSuccess;
-    if (e == hipSuccess && t_bytes) e = upload_pageable(h, (char*)h->dev_mesh.p + v_room, tris, t_bytes);
-    if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "compare_mesh upload: %s", hipGetErrorString(e));
+    const uint32_t* d_tris = nullptr;
+    if (int rc = upload_mesh_locked(h, "compare_mesh", verts, n_verts, vertex_stride, tris, n_tris, &d_tris)) return rc;
     ResultSet set;
     hfpf_deviation_summary s;
-    if (int rc = compare_locked(h, o, h->dev_mesh.p, n_verts, vertex_stride, (const uint32_t*)((char*)h->dev_mesh.p + v_room), n_tris, pose_3x4, false, rows != nullptr,
-                                &set, &s))
-        return rc;
+    if (int rc = compare_locked(h, o, h->dev_mesh.p, n_verts, vertex_stride, d_tris, n_tris, pose_3x4, false, rows != nullptr, &set, &s)) return rc;
     void* host[3] = {nullptr, nullptr, nullptr};
     if (s.n_rows)
         if (int rc = result_to_host(h, set, "compare_mesh", host)) return rc;
@@ -3493,6 +3553,128 @@ void hfpf_free_deviation(hfpf_row* rows, hfpf_deviation* dev)
 {
     free(rows);
     free(dev);
+}
+
+// ---- best-fitting a mesh to the model (include/hfpf.h) ----------------------------------------------------------------------
+int hfpf_check_align_opts(const hfpf_align_opts* o)
+{
+    if (!o || o->struct_size != sizeof(hfpf_align_opts) || (o->flags & ~HFPF_ALIGN_SKIP_BOUNDARY) || o->reserved0 != 0 || o->reserved != 0) return HFPF_ERR_BAD_ARG;
+    if (o->max_iterations < 1 || o->max_iterations > 64 || o->stride < 1 || o->stride > 65536 || o->min_inliers < 6) return HFPF_ERR_BAD_ARG;
+    if (!(std::isfinite(o->damping) && o->damping >= 0.0)) return HFPF_ERR_BAD_ARG;
+    if (!(std::isfinite(o->eps_rotation) && o->eps_rotation >= 0.0 && std::isfinite(o->eps_translation) && o->eps_translation >= 0.0)) return HFPF_ERR_BAD_ARG;
+    return hfpf_check_deviation_opts(&o->compare);
+}
+
+// Validated arguments in, the mesh on the device, under the lock.  The row set; then compare's row side once and per iteration
+// compare's mesh side into h->align_dev, one k_align_reduce and track's host solve.  Not timed: hfpf_get_kernel_time has no id for it.
+static int align_locked(hfpf_handle* h, const hfpf_align_opts* o, const void* d_verts, uint64_t n_verts, uint32_t stride, const uint32_t* d_tris, uint64_t n_tris,
+                        const double* pose, hfpf_align_result* res)
+{
+    int rc;
+    uint64_t nr = 0;
+    const ExtractOpts opt{o->compare.min_count, -1, 0};
+    if ((rc = build_rows_locked(h, h->t.stats, opt, &nr))) return rc;
+    const uint64_t n_samples = (nr + o->stride - 1) / o->stride;
+    if (n_samples > (1ull << 26)) return fail(h, HFPF_ERR_BAD_ARG, "align_mesh: more than 2^26 sampled rows");
+    DevRowSide rs;
+    uint32_t *flag, *base;
+    if ((rc = compare_row_scratch_locked(h, nr, "align_mesh", &rs, &flag, &base))) return rc;
+    if ((rc = scratch(h, h->align_dev, (size_t)std::max<uint32_t>(rs.n, 1) * sizeof(Deviation)))) return rc;
+    if ((rc = scratch(h, h->align_acc, kAlignTerms * sizeof(unsigned long long)))) return rc;
+    AlignParams p{};
+    for (int a = 0; a < 3; a++) p.c[a] = (h->g.min[a] + h->g.max[a]) * 0.5;
+    p.flags = o->flags, p.stride = o->stride, p.n = (uint32_t)n_samples;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(kTrackMaxBlocks, blocks_for(n_samples, 256));
+    Deviation* dev = (Deviation*)h->align_dev.p;
+    unsigned long long* acc = (unsigned long long*)h->align_acc.p;
+    unsigned long long local[kAlignTerms];
+    unsigned long long* back = h->xfer_pin[0] ? (unsigned long long*)h->xfer_pin[0] : local;  // the read-back of the sums
+
+    if ((rc = compare_row_side_locked(h, &rs, flag, base))) return rc;
+    double T[12], A[6][6] = {}, rr = 0.0;
+    memcpy(T, pose, sizeof T);
+    uint64_t inliers = 0;
+    uint32_t flags = 0, it = 0;
+    while (it < o->max_iterations) {
+        it++;
+        unsigned long long h_ctr[DC_WORDS];
+        if ((rc = compare_mesh_side_locked(h, rs, &o->compare, d_verts, n_verts, stride, d_tris, n_tris, T, dev, h_ctr))) return rc;
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemsetAsync(acc, 0, kAlignTerms * sizeof(unsigned long long), h->stream));
+        if (n_samples) {
+            hipLaunchKernelGGL(k_align_reduce, dim3(blocks), dim3(256), 0, h->stream, p, (const Row*)h->rows_dev.p, (const Deviation*)dev, acc);
+            HIPCHK(h, hipGetLastError());
+        }
+        HIPCHK(h, hipMemcpyAsync(back, acc, kAlignTerms * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        long long s[kAlignTerms];
+        memcpy(s, back, sizeof s);
+        for (int i = 0, k = 0; i < 6; i++)
+            for (int j = i; j < 6; j++, k++) A[i][j] = A[j][i] = (double)s[k] / kTrackScaleJJ;
+        double b[6];
+        for (int i = 0; i < 6; i++) b[i] = (double)s[21 + i] / kTrackScaleJR;
+        rr = (double)s[27] / kTrackScaleRR;
+        inliers = (uint64_t)s[28];
+        if (inliers < o->min_inliers) {
+            flags = HFPF_ALIGN_TOO_FEW;
+            break;
+        }
+        double xi[6];
+        if (!track_solve(A, b, o->damping, xi)) {
+            flags = HFPF_ALIGN_DEGENERATE;
+            break;
+        }
+        track_update(T, xi, p.c);
+        if ((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2] < o->eps_rotation * o->eps_rotation &&
+            (xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5] < o->eps_translation * o->eps_translation) {
+            flags = HFPF_ALIGN_CONVERGED;
+            break;
+        }
+    }
+    res->iterations = it;
+    res->flags = flags;
+    res->reserved = 0;
+    res->rows_sampled = n_samples;
+    res->inliers = inliers;
+    res->rms = inliers ? std::sqrt(rr / (double)inliers) : 0.0;
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) res->information[6 * i + j] = A[i][j];
+    memcpy(res->pose, T, sizeof T);
+    return HFPF_OK;
+}
+
+// The checks of both forms: the options, then compare's own on the mesh, the pose and max_distance, then the result.
+static const char* align_args_fault(const hfpf_handle* h, const hfpf_align_opts* o, const void* verts, uint64_t n_verts, uint32_t stride, const uint32_t* tris,
+                                    uint64_t n_tris, const double* pose, const hfpf_align_result* res, bool on_device)
+{
+    if (hfpf_check_align_opts(o) != HFPF_OK) return "invalid hfpf_align_opts";
+    if (const char* f = compare_args_fault(h, &o->compare, verts, n_verts, stride, tris, n_tris, pose, h, h, h, on_device)) return f;
+    if (!res || res->struct_size != sizeof(hfpf_align_result)) return "NULL result or wrong struct_size";
+    return nullptr;
+}
+
+int hfpf_align_mesh_device(hfpf_handle* h, const hfpf_align_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* dev_tris,
+                           uint64_t n_tris, const double* pose_3x4, hfpf_align_result* result)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (const char* f = align_args_fault(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, result, true))
+        return fail(h, HFPF_ERR_BAD_ARG, "align_mesh_device: %s", f);
+    if (int rc = local_read_prologue_locked(h, "align_mesh")) return rc;
+    return align_locked(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, result);
+}
+
+int hfpf_align_mesh(hfpf_handle* h, const hfpf_align_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
+                    const double* pose_3x4, hfpf_align_result* result)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (const char* f = align_args_fault(h, o, verts, n_verts, vertex_stride, tris, n_tris, pose_3x4, result, false))
+        return fail(h, HFPF_ERR_BAD_ARG, "align_mesh: %s", f);
+    if (int rc = local_read_prologue_locked(h, "align_mesh")) return rc;
+    const uint32_t* d_tris = nullptr;
+    if (int rc = upload_mesh_locked(h, "align_mesh", verts, n_verts, vertex_stride, tris, n_tris, &d_tris)) return rc;
+    return align_locked(h, o, h->dev_mesh.p, n_verts, vertex_stride, d_tris, n_tris, pose_3x4, result);
 }
 
 int hfpf_stats_export(hfpf_handle* h, const void** dev_words, uint64_t* n_words, const void** dev_cwords, uint64_t* n_cwords)

@@ -4165,4 +4165,71 @@ __global__ __launch_bounds__(256) void k_dev_rows(const Row* __restrict__ rows, 
     }
 }
 
+
+// ---- best-fitting a mesh to the model (hfpf_align_mesh*; contract in include/hfpf.h, numpy restatement tests/align_ref.py) --------------
+// Mesh-to-model point-to-plane ICP: per iteration compare's mesh kernels give every row its deviation record at the estimate T_k,
+// one launch of k_align_reduce sums the 6x6 normal equations of the sampled rows from those records, and the host solves them as a
+// track does.  The terms, their scales and the headroom are track's, so the sums are exact and do not depend on scheduling.
+constexpr int kAlignTerms = 29;  // 21 J_i J_j (i <= j, i outer), 6 J_i r, r r, inliers: the first 29 of kTrackTerms
+constexpr uint32_t kAlignSkipBoundary = 1u;  // = HFPF_ALIGN_SKIP_BOUNDARY
+
+struct AlignParams {
+    double c[3];     // the centre the twist is taken about: the middle of the bounding box
+    uint32_t flags;  // HFPF_ALIGN_*
+    uint32_t stride; // row j is sampled iff j % stride == 0
+    uint32_t n;      // sampled rows: sample s is row s * stride
+};
+
+// One sampled row per thread, grid-stride over at most kTrackMaxBlocks blocks.  The row's point and normal come in as k_track_reduce
+// loads them, its deviation record as two 16-byte loads.  Each thread keeps its 29 sums in registers; the block reduces them (DPP
+// across the wave, LDS across the four waves) and adds the non-zero ones to acc with one 64-bit atomic each.  acc is zeroed by the
+// host before the launch.
+__global__ __launch_bounds__(256) void k_align_reduce(const AlignParams p, const Row* __restrict__ rows, const Deviation* __restrict__ dev,
+                                                      unsigned long long* __restrict__ acc)
+{
+    __shared__ unsigned long long s_part[4][kAlignTerms];
+    unsigned long long sum[kAlignTerms];
+#pragma unroll
+    for (int k = 0; k < kAlignTerms; k++) sum[k] = 0;
+    for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < p.n; s += gridDim.x * blockDim.x) {
+        const uint32_t j = s * p.stride;  // < the row count, which is below 2^32 - 1
+        const uint4 d0 = *reinterpret_cast<const uint4*>(&dev[j].signed_distance);  // signed_distance, distance, tri, flags
+        const uint32_t flags = d0.w;
+        if (!(flags & kDevFound)) continue;
+        if ((p.flags & kAlignSkipBoundary) && (flags & (kDevOnEdge | kDevOnVertex))) continue;
+        const float4 d1 = *reinterpret_cast<const float4*>(&dev[j].q[0]);  // q, reserved
+        const Row* row = rows + j;
+        const float4 q0 = *reinterpret_cast<const float4*>(&row->x);   // x, y, z, nx
+        const float2 q1 = *reinterpret_cast<const float2*>(&row->ny);  // ny, nz
+        const double nx = q0.w, ny = q1.x, nz = q1.y;
+        if (!(((nx * nx + ny * ny) + nz * nz) <= 2.0)) continue;
+        const double qx = d1.x, qy = d1.y, qz = d1.z;
+        const double ax = qx - p.c[0], ay = qy - p.c[1], az = qz - p.c[2];
+        if (!(fmax(fmax(fabs(ax), fabs(ay)), fabs(az)) < kTrackHeadroom)) continue;
+        const double dx = qx - (double)q0.x, dy = qy - (double)q0.y, dz = qz - (double)q0.z;
+        const double r = (nx * dx + ny * dy) + nz * dz;
+        const double J[6] = {ay * nz - az * ny, az * nx - ax * nz, ax * ny - ay * nx, nx, ny, nz};
+        int k = 0;
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+#pragma unroll
+            for (int jj = i; jj < 6; jj++) sum[k++] += track_q(J[i] * J[jj], kTrackScaleJJ);
+#pragma unroll
+        for (int i = 0; i < 6; i++) sum[21 + i] += track_q(J[i] * r, kTrackScaleJR);
+        sum[27] += track_q(r * r, kTrackScaleRR);
+        sum[28] += 1;
+    }
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < kAlignTerms; k++) {
+        const unsigned long long t = wave_total_u64(sum[k]);
+        if (lane == 63) s_part[wave][k] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < kAlignTerms) {
+        const unsigned long long t = (s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + (s_part[2][threadIdx.x] + s_part[3][threadIdx.x]);
+        if (t) atomicAdd(&acc[threadIdx.x], t);
+    }
+}
+
 }  // namespace hfpf

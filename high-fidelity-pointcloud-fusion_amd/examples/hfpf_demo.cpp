@@ -2,11 +2,12 @@
 // synthetic sensor -> ~start -> N x PointCloud2 callbacks with tf poses -> periodic clean -> ~process ->
 // <dir>/test_cloud.pcd + <dir>/meta.csv.  Prints per-stage wall times.
 //
-//   hfpf_demo [--min-component N] [--reference mesh.ply [--max-deviation metres]] <out_dir> [frames=30] [W=640] [H=480] [resolution=0.001] [clean_every=10] [seed=0xF051] [pose_seed=0x5E3]
+//   hfpf_demo [--min-component N] [--reference mesh.ply [--max-deviation metres] [--align]] <out_dir> [frames=30] [W=640] [H=480] [resolution=0.001] [clean_every=10] [seed=0xF051] [pose_seed=0x5E3]
 // --min-component N: ~process saves only the connected components (26-neighbourhood) of at least N rows (hfpf_node_set_component_filter).
 // --reference mesh.ply: ~process also writes deviation.csv and deviation_summary.csv, the saved cloud measured against that mesh
 //   (binary little-endian PLY in the fusion frame; hfpf_node_set_reference_mesh); --max-deviation is the largest distance looked for
-//   (default 10 voxels, at most 32).
+//   (default 10 voxels, at most 32).  --align: the mesh is first best-fitted to the model from that pose with the same distance as its
+//   capture range (hfpf_node_set_reference_alignment); the compare runs at the refined pose, which alignment.csv records.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -47,7 +48,13 @@ int main(int argc, char** argv)
     uint32_t min_component = 0;
     const char* reference = nullptr;
     double max_deviation = 0.0;
+    bool align = false;
     while (argc > 2 && strncmp(argv[1], "--", 2) == 0) {
+        if (strcmp(argv[1], "--align") == 0) {
+            align = true;
+            argv += 1, argc -= 1;
+            continue;
+        }
         if (strcmp(argv[1], "--min-component") == 0) min_component = (uint32_t)strtoul(argv[2], nullptr, 0);
         else if (strcmp(argv[1], "--reference") == 0) reference = argv[2];
         else if (strcmp(argv[1], "--max-deviation") == 0) max_deviation = atof(argv[2]);
@@ -55,7 +62,7 @@ int main(int argc, char** argv)
         argv += 2, argc -= 2;
     }
     if (argc < 2 || strncmp(argv[1], "--", 2) == 0) {
-        fprintf(stderr, "usage: hfpf_demo [--min-component N] [--reference mesh.ply [--max-deviation metres]] <out_dir> [frames] [W] [H] [resolution] [clean_every] [seed] [pose_seed]\n");
+        fprintf(stderr, "usage: hfpf_demo [--min-component N] [--reference mesh.ply [--max-deviation metres] [--align]] <out_dir> [frames] [W] [H] [resolution] [clean_every] [seed] [pose_seed]\n");
         return 2;
     }
     const std::string dir = argv[1];
@@ -112,6 +119,18 @@ int main(int argc, char** argv)
         if (rc != HFPF_OK) {
             fprintf(stderr, "reference: %s\n", hfpf_node_last_error(node));
             return 1;
+        }
+        if (align) {
+            hfpf_align_opts ao;
+            memset(&ao, 0, sizeof ao);
+            ao.struct_size = sizeof ao;
+            ao.max_iterations = 20, ao.stride = 1, ao.min_inliers = 6;
+            ao.compare = dopt;
+            ao.damping = 1e-6, ao.eps_rotation = 1e-5, ao.eps_translation = 0.01 * (double)res;
+            if (hfpf_node_set_reference_alignment(node, &ao) != HFPF_OK) {
+                fprintf(stderr, "align: %s\n", hfpf_node_last_error(node));
+                return 1;
+            }
         }
     }
     hfpf_trigger_response r;

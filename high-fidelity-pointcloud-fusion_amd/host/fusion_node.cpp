@@ -40,6 +40,8 @@ struct hfpf_node {
     std::vector<float> ref_verts;       // packed x, y, z
     std::vector<uint32_t> ref_tris;
     double ref_pose[12] = {0};
+    bool align_on = false;              // hfpf_node_set_reference_alignment: the reference mesh is best-fitted before it is compared
+    hfpf_align_opts align_opts{};
     void* publish_user = nullptr;
     std::thread clean_thread;
     std::mutex cv_mtx;
@@ -221,15 +223,37 @@ int hfpf_node_reset(hfpf_node* n, hfpf_trigger_response* res)
 // deviation.csv and deviation_summary.csv beside the cloud: one line per saved row.  The compare runs on the full row set (with the
 // component filter's min_count when one is set); the saved rows are a subsequence of it in the same lexicographic order, so one walk
 // selects their records, and the row part of the summary is rebuilt from the selected records as include/hfpf.h defines it.
+// With alignment on the reference mesh is first best-fitted from its stored pose; the compare then runs at the refined pose, which
+// alignment.csv records.
 static int write_deviation(hfpf_node* n, const hfpf_row* saved, uint64_t n_saved)
 {
     hfpf_deviation_opts o = n->ref_opts;
     if (n->comp_on) o.min_count = n->comp_opts.min_count;
+    double pose[12];
+    memcpy(pose, n->ref_pose, sizeof pose);
+    if (n->align_on) {
+        hfpf_align_opts ao = n->align_opts;
+        if (n->comp_on) ao.compare.min_count = n->comp_opts.min_count;
+        hfpf_align_result ar;
+        memset(&ar, 0, sizeof ar);
+        ar.struct_size = sizeof ar;
+        int arc = hfpf_align_mesh(n->grid, &ao, n->ref_verts.data(), n->ref_verts.size() / 3, 12, n->ref_tris.data(), n->ref_tris.size() / 3, n->ref_pose, &ar);
+        if (arc != HFPF_OK) return arc;
+        memcpy(pose, ar.pose, sizeof pose);
+        FILE* af = fopen((n->directory_name + "/alignment.csv").c_str(), "w");
+        if (!af) return HFPF_ERR_IO;
+        fprintf(af, "iterations,flags,rows_sampled,inliers,rms,p0,p1,p2,p3,p4,p5,p6,p7,p8,p9,p10,p11\n%u,%u,%llu,%llu,%.17g", ar.iterations, ar.flags,
+                (unsigned long long)ar.rows_sampled, (unsigned long long)ar.inliers, ar.rms);
+        for (int i = 0; i < 12; i++) fprintf(af, ",%.17g", pose[i]);
+        fprintf(af, "\n");
+        const bool ok = !ferror(af);
+        if (fclose(af) != 0 || !ok) return HFPF_ERR_IO;
+    }
     hfpf_row* all = nullptr;
     hfpf_deviation* dev = nullptr;
     uint64_t n_all = 0;
     hfpf_deviation_summary s;
-    int rc = hfpf_compare_mesh(n->grid, &o, n->ref_verts.data(), n->ref_verts.size() / 3, 12, n->ref_tris.data(), n->ref_tris.size() / 3, n->ref_pose,
+    int rc = hfpf_compare_mesh(n->grid, &o, n->ref_verts.data(), n->ref_verts.size() / 3, 12, n->ref_tris.data(), n->ref_tris.size() / 3, pose,
                                n->comp_on ? &all : nullptr, &dev, &n_all, &s);
     if (rc != HFPF_OK) return rc;
     FILE* f = fopen((n->directory_name + "/deviation.csv").c_str(), "w");
@@ -413,6 +437,17 @@ int hfpf_node_set_reference_mesh(hfpf_node* n, const hfpf_deviation_opts* opts, 
     memcpy(n->ref_pose, pose_3x4, sizeof n->ref_pose);
     n->ref_opts = *opts;
     n->ref_on = true;
+    return HFPF_OK;
+}
+
+int hfpf_node_set_reference_alignment(hfpf_node* n, const hfpf_align_opts* opts)
+{
+    if (!n) return HFPF_ERR_BAD_ARG;
+    if (opts) {
+        if (hfpf_check_align_opts(opts) != HFPF_OK) return nfail(n, HFPF_ERR_BAD_ARG, "hfpf_node_set_reference_alignment: invalid hfpf_align_opts");
+        n->align_opts = *opts;
+    }
+    n->align_on = opts != nullptr;
     return HFPF_OK;
 }
 

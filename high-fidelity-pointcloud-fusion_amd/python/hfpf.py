@@ -94,6 +94,7 @@ EXPORTS = [
     "hfpf_extract_mesh", "hfpf_extract_mesh_device", "hfpf_free_mesh", "hfpf_write_ply", "hfpf_check_mesh_opts",
     "hfpf_check_component_opts", "hfpf_extract_components", "hfpf_extract_components_device", "hfpf_free_components",
     "hfpf_check_deviation_opts", "hfpf_compare_mesh", "hfpf_compare_mesh_device", "hfpf_free_deviation", "hfpf_read_ply",
+    "hfpf_check_align_opts", "hfpf_align_mesh", "hfpf_align_mesh_device",
     "hfpf_check_raycast_opts", "hfpf_raycast", "hfpf_raycast_device", "hfpf_raycast_view", "hfpf_raycast_view_device",
     "hfpf_snapshot", "hfpf_free_snapshot", "hfpf_restore", "hfpf_save", "hfpf_load", "hfpf_snapshot_info", "hfpf_config_from_snapshot",
 ]
@@ -319,6 +320,55 @@ def deviation_opts(min_count=0.0, max_distance=0.01):
 def check_deviation_opts(o):
     """hfpf_check_deviation_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
     return lib().hfpf_check_deviation_opts(C.byref(o) if o is not None else None)
+
+
+# hfpf_align_result.flags and hfpf_align_opts.flags (include/hfpf.h)
+ALIGN_CONVERGED, ALIGN_DEGENERATE, ALIGN_TOO_FEW = 1, 2, 4
+ALIGN_SKIP_BOUNDARY = 1
+
+
+class AlignOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("max_iterations", C.c_uint32), ("stride", C.c_uint32),
+                ("min_inliers", C.c_uint32), ("reserved0", C.c_uint32), ("compare", DeviationOpts), ("damping", C.c_double),
+                ("eps_rotation", C.c_double), ("eps_translation", C.c_double), ("reserved", C.c_uint64)]
+
+
+class AlignResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("rows_sampled", C.c_uint64), ("inliers", C.c_uint64), ("rms", C.c_double), ("information", C.c_double * 36),
+                ("pose", C.c_double * 12)]
+
+
+assert C.sizeof(AlignOpts) == 88 and C.sizeof(AlignResult) == 424
+
+
+def align_opts(max_iterations=10, stride=1, min_inliers=6, min_count=0.0, max_distance=0.01, damping=1e-6, eps_rotation=1e-6,
+               eps_translation=1e-6, skip_boundary=False):
+    """An hfpf_align_opts; min_count and max_distance (the capture range, at most 32 voxels) fill the embedded hfpf_deviation_opts."""
+    o = AlignOpts()
+    o.struct_size = C.sizeof(AlignOpts)
+    o.flags = ALIGN_SKIP_BOUNDARY if skip_boundary else 0
+    o.max_iterations, o.stride, o.min_inliers = int(max_iterations), int(stride), int(min_inliers)
+    o.compare = deviation_opts(min_count, max_distance)
+    o.damping, o.eps_rotation, o.eps_translation = float(damping), float(eps_rotation), float(eps_translation)
+    return o
+
+
+def align_result():
+    r = AlignResult()
+    r.struct_size = C.sizeof(AlignResult)
+    return r
+
+
+def check_align_opts(o):
+    """hfpf_check_align_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
+    return lib().hfpf_check_align_opts(C.byref(o) if o is not None else None)
+
+
+def _align_out(r):
+    """The result dict of an hfpf_align_result."""
+    return {"iterations": r.iterations, "flags": r.flags, "rows_sampled": r.rows_sampled, "inliers": r.inliers, "rms": r.rms,
+            "information": np.array(r.information[:], np.float64).reshape(6, 6), "pose": np.array(r.pose[:], np.float64).reshape(3, 4)}
 
 
 def read_ply(path):
@@ -558,6 +608,9 @@ def lib():
     for fn in (L.hfpf_compare_mesh, L.hfpf_compare_mesh_device):
         fn.argtypes = [vp, C.POINTER(DeviationOpts), vp, u64, u32, vp, u64, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64),
                        C.POINTER(DeviationSummary)]
+    L.hfpf_check_align_opts.argtypes = [C.POINTER(AlignOpts)]
+    for fn in (L.hfpf_align_mesh, L.hfpf_align_mesh_device):
+        fn.argtypes = [vp, C.POINTER(AlignOpts), vp, u64, u32, vp, u64, vp, C.POINTER(AlignResult)]
     L.hfpf_free_deviation.argtypes = [vp, vp]
     L.hfpf_free_deviation.restype = None
     L.hfpf_read_ply.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64)]
@@ -974,6 +1027,29 @@ class OccupancyGrid:
         finally:
             lib().hfpf_free_deviation(r, d)
         return (out_rows, dev, s.as_dict()) if rows else (dev, s.as_dict())
+
+    # -- best-fitting a triangle mesh to the model --
+    def align_mesh(self, verts, tris, pose=None, device=False, opts=None, n_verts=None, vertex_stride=None, n_tris=None, **kw):
+        """Refine the mesh frame -> fusion frame pose of a triangle mesh against the model's rows (hfpf_align_mesh): a dict of
+        iterations, flags, rows_sampled, inliers, rms, information (6x6) and pose (3x4, to hand to compare_mesh).  verts, tris, pose
+        and the device form's arguments as compare_mesh(); keywords as align_opts().  The capture range is max_distance."""
+        o = opts if opts is not None else align_opts(**kw)
+        pose = np.ascontiguousarray(np.eye(4)[:3] if pose is None else pose, np.float64).reshape(12)
+        r = align_result()
+        if device:
+            self._chk(lib().hfpf_align_mesh_device(self._h, C.byref(o), C.c_void_p(verts), int(n_verts), int(vertex_stride), C.c_void_p(tris),
+                                                   int(n_tris), _p(pose), C.byref(r)))
+            return _align_out(r)
+        verts = np.ascontiguousarray(verts)
+        if verts.dtype != MESH_VERTEX_DTYPE:
+            verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+        stride = int(vertex_stride) if vertex_stride is not None else verts.dtype.itemsize * (1 if verts.dtype == MESH_VERTEX_DTYPE else 3)
+        nv = int(n_verts) if n_verts is not None else len(verts)
+        nt = int(n_tris) if n_tris is not None else len(tris)
+        self._chk(lib().hfpf_align_mesh(self._h, C.byref(o), _p(verts) if verts.nbytes else None, nv, stride, _p(tris) if tris.nbytes else None, nt,
+                                        _p(pose), C.byref(r)))
+        return _align_out(r)
 
     # -- casting rays against the model --
     def raycast(self, rays, pose, opts=None, **kw):

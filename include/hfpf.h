@@ -825,6 +825,95 @@ int hfpf_compare_mesh_device(hfpf_handle* h, const hfpf_deviation_opts* o, const
  * left before anything is allocated. */
 int hfpf_read_ply(const char* path, hfpf_mesh_vertex** verts, uint64_t* n_verts, uint32_t** tris, uint64_t* n_tris);
 
+/* ---- best-fitting a triangle mesh to the fused model (mesh-to-model point-to-plane ICP; no reference counterpart) ---------------
+ * hfpf_compare_mesh measures the model against a mesh at a pose the caller knows; an align finds that pose.  It takes the mesh
+ * arguments of the section "deviation of the fused model from a triangle mesh" above and a start pose T_0 = pose_3x4 (mesh frame ->
+ * fusion frame) and returns a refined pose in the same convention; the caller then passes that pose to hfpf_compare_mesh.  It is
+ * that section's closest-point search and the section "refining a frame's pose against the fused model"'s normal equations, host
+ * solve and update, run in a loop, and nothing else (tests/align_ref.py).  All arithmetic is f64, one rounding per operation, left
+ * to right, never contracted, as in both.
+ * Row set: the row set of hfpf_compare_mesh with opts.compare.min_count, in lexicographic order; host frames still waiting are
+ *   launched first.  Row j is SAMPLED iff j % stride == 0; rows_sampled counts them and must be at most 2^26.
+ * Centre: c[a] = (bbox_min[a] + bbox_max[a]) * 0.5 (the handle's bounding box).
+ * Per iteration k = 1, 2, ... with T = T_{k-1}, for every sampled row: D = the hfpf_deviation record hfpf_compare_mesh returns for
+ *   that row against the mesh at T with opts.compare.max_distance -- exactly that record, its f32 fields included (a row's record
+ *   depends on the row and the mesh only, so sampling changes no record).  The row is an INLIER iff
+ *     D.flags & HFPF_DEV_FOUND;
+ *     with HFPF_ALIGN_SKIP_BOUNDARY neither HFPF_DEV_ON_EDGE nor HFPF_DEV_ON_VERTEX is set (a row hanging past the rim of a partial
+ *       mesh then does not pull on that rim; inside a closed mesh it drops the rows whose closest point lies on a crease);
+ *     (n.x*n.x + n.y*n.y) + n.z*n.z <= 2, n = (double) of the row's nx, ny, nz;
+ *     max(|a.x|, |a.y|, |a.z|) < 32 (metres: track's headroom rule)
+ *   with P = (double) of the row's x, y, z, Q = (double)D.q, d = Q - P, a = Q - c.  Per inlier
+ *     r = (n.x*d.x + n.y*d.y) + n.z*d.z
+ *     J = (a.y*n.z - a.z*n.y, a.z*n.x - a.x*n.z, a.x*n.y - a.y*n.x, n.x, n.y, n.z)      (twist order omega, tau)
+ *   and the inlier adds (int64) rint(v * s) for v = J_i*J_j (i <= j; s = 2^24), J_i*r (s = 2^28) and r*r (s = 2^32) into exact int64
+ *   sums, as a track's inlier does, and 1 to the inlier count.  Headroom as there: |J_i| < 64, and |r| < 2 because max_distance <= 1.
+ * On the host, word for word the track section: A, b, rr from the sums; inliers < min_inliers: HFPF_ALIGN_TOO_FEW, stop; Cholesky
+ *   of A + damping*I, a pivot not > 0: HFPF_ALIGN_DEGENERATE, stop; the two triangular solves; the Cayley update about c,
+ *   R_k = R(omega) R_{k-1}, t_k = (c + R(omega)(t_{k-1} - c)) + tau; HFPF_ALIGN_CONVERGED and stop when omega is below eps_rotation
+ *   and tau below eps_translation (the update is applied first); otherwise stop after max_iterations.
+ * The result: pose = the last estimate (T_0 when the first system was TOO_FEW or DEGENERATE), iterations = systems evaluated;
+ * inliers, rms = sqrt(rr / inliers) (0 without inliers) and information = A describe the last system evaluated.  HFPF_OK is
+ * returned whenever the arguments are valid: also for TOO_FEW and DEGENERATE, for an empty handle and one before its first clean
+ * pass, and for n_tris = 0 (all three: TOO_FEW after one system, pose = T_0).  A call changes nothing on the handle except
+ * device_bytes (its scratch: compare's, one deviation record per row, 232 bytes of sums).  Rejected with HFPF_ERR_BAD_ARG (the
+ * handle stays usable, the result is not written): what hfpf_check_align_opts rejects (struct_size != sizeof, flags beyond
+ * HFPF_ALIGN_SKIP_BOUNDARY, reserved0 or reserved != 0, max_iterations outside 1..64, stride outside 1..65536, min_inliers < 6,
+ * damping, eps_rotation or eps_translation not finite and >= 0, and whatever hfpf_check_deviation_opts rejects of opts.compare);
+ * every check hfpf_compare_mesh makes on the mesh, the pose and max_distance (at most 32 * res); a NULL result or one with a wrong
+ * struct_size; more than 2^26 sampled rows.  The pair list not fitting returns HFPF_ERR_CAPACITY as in compare (the handle stays
+ * usable); a handle with an RCCL communicator, or a failed handle, returns HFPF_ERR_STATE.
+ * LIMITATION: a row finds the mesh only within opts.compare.max_distance, at most 32 voxels: that is the capture range.  An align
+ * refines a coarse placement; it is not a global registration. */
+#define HFPF_ALIGN_CONVERGED 1u  /* the last update was below both eps */
+#define HFPF_ALIGN_DEGENERATE 2u /* a pivot of the damped system was <= 0; pose = the last good estimate */
+#define HFPF_ALIGN_TOO_FEW 4u    /* fewer than min_inliers inliers; pose = the last good estimate */
+
+#define HFPF_ALIGN_SKIP_BOUNDARY 1u /* hfpf_align_opts.flags: rows whose closest point lies on an edge or a vertex are no inliers */
+
+typedef struct hfpf_align_opts {
+    uint32_t struct_size;        /* = sizeof(hfpf_align_opts) */
+    uint32_t flags;              /* HFPF_ALIGN_SKIP_BOUNDARY or 0 */
+    uint32_t max_iterations;     /* 1..64 */
+    uint32_t stride;             /* 1..65536: the row sampling above */
+    uint32_t min_inliers;        /* >= 6 */
+    uint32_t reserved0;          /* 0 */
+    hfpf_deviation_opts compare; /* the row set's min_count and the search's max_distance (the capture range) */
+    double damping;              /* >= 0, added to the diagonal of the 6x6 system */
+    double eps_rotation;         /* radians */
+    double eps_translation;      /* metres */
+    uint64_t reserved;           /* 0 */
+} hfpf_align_opts;
+
+typedef struct hfpf_align_result {
+    uint32_t struct_size;    /* = sizeof(hfpf_align_result), set by the caller */
+    uint32_t iterations;
+    uint32_t flags;          /* HFPF_ALIGN_* */
+    uint32_t reserved;
+    uint64_t rows_sampled;   /* the same in every iteration */
+    uint64_t inliers;        /* of the last system evaluated */
+    double rms;              /* sqrt(rr / inliers) of that system */
+    double information[36];  /* its undamped J^T J, row-major, twist order (omega, tau) about the bounding box's centre */
+    double pose[12];         /* refined pose, row-major [R|t], mesh frame -> fusion frame */
+} hfpf_align_result;
+
+#ifdef __cplusplus
+static_assert(sizeof(hfpf_align_opts) == 88, "hfpf_align_opts is 88 bytes");
+static_assert(sizeof(hfpf_align_result) == 424, "hfpf_align_result is 424 bytes");
+#else
+_Static_assert(sizeof(hfpf_align_opts) == 88, "hfpf_align_opts is 88 bytes");
+_Static_assert(sizeof(hfpf_align_result) == 424, "hfpf_align_result is 424 bytes");
+#endif
+
+/* HFPF_OK if o passes the checks above that need no handle, else HFPF_ERR_BAD_ARG (host code; the node shell uses it too). */
+int hfpf_check_align_opts(const hfpf_align_opts* o);
+/* Mesh and pose in HOST memory (the mesh is uploaded once per call, as hfpf_compare_mesh uploads it). */
+int hfpf_align_mesh(hfpf_handle* h, const hfpf_align_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris,
+                    uint64_t n_tris, const double* pose_3x4, hfpf_align_result* result);
+/* The mesh is read in place from DEVICE memory (HBM); pose_3x4 and result are in host memory. */
+int hfpf_align_mesh_device(hfpf_handle* h, const hfpf_align_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride,
+                           const uint32_t* dev_tris, uint64_t n_tris, const double* pose_3x4, hfpf_align_result* result);
+
 /* <directory_name>/test_cloud.pcd (node.cpp:395): PCD v0.7 ASCII, FIELDS x y z rgb normal_x normal_y normal_z curvature */
 int hfpf_write_pcd(const hfpf_row* rows, uint64_t n_rows, const char* path);
 /* <directory_name>/meta.csv (node.cpp:396) with the header string of grid.hpp:462 */
@@ -863,7 +952,7 @@ int hfpf_get_occupied(hfpf_handle* h, int32_t* xyz, uint64_t cap, uint64_t* n_ou
  * WHAT A RESTORE IS.  hfpf_clear followed by putting that state in place.  Afterwards the handle is indistinguishable from the
  * source handle at the moment of the snapshot, in this sense:
  *   1. every read-only call (extract, extract_filtered, get_occupied, is_dirty, render*, query*, extract_mesh*, raycast*, track*,
- *      extract_components*, compare_mesh*)
+ *      extract_components*, compare_mesh*, align_mesh*)
  *      returns byte-identical output;
  *   2. any continuation (integrate*, clean, extract, clear, automatic frame ids included) produces byte-identical rows and occupied
  *      lists to the same continuation on the source handle;
@@ -980,7 +1069,7 @@ int hfpf_device_copy(hfpf_handle* h, void* dev_dst, const void* dev_src, uint64_
  * the copies; any enable).  6 = the component kernels of one hfpf_extract_components* call (index to compaction, the scans' read-backs
  * included, without the row set and the copies; any enable).  7 = the compare kernels of one hfpf_compare_mesh* call (binning to
  * the row kernel, the read-backs of the sizes included, without the row set and the copies; any enable).  total_ms / launches
- * accumulate since enable. */
+ * accumulate since enable.  hfpf_align_mesh* has no id of its own and is not filed under 7. */
 int hfpf_kernel_timing(hfpf_handle* h, int enable);
 int hfpf_get_kernel_time(hfpf_handle* h, int kernel_id, double* total_ms, uint64_t* launches);
 

@@ -111,6 +111,17 @@ int hfpf_node_set_component_filter(hfpf_node* n, const hfpf_component_opts* opts
 int hfpf_node_set_reference_mesh(hfpf_node* n, const hfpf_deviation_opts* opts, const void* verts, uint64_t n_verts, uint32_t vertex_stride,
                                  const uint32_t* tris, uint64_t n_tris, const double* pose_3x4);
 
+/* EXTENSION: best-fit, then compare.  With alignment options set and a reference mesh set, ~process first refines the reference
+ * mesh's pose against the model (hfpf_align_mesh of include/hfpf.h, started from the pose given to hfpf_node_set_reference_mesh; with a
+ * component filter set, opts->compare.min_count is replaced by the filter's, as the compare's is) and writes deviation.csv and
+ * deviation_summary.csv at the refined pose.  It also writes alignment.csv: the header
+ * iterations,flags,rows_sampled,inliers,rms,p0,...,p11 and one value line, rms and the 12 pose values (row-major [R|t]) as %.17g, so
+ * that the pose reads back bit for bit.  The stored pose of the reference mesh is not changed: every ~process starts from it again.
+ * Without a reference mesh the setting has no effect.  NULL turns it off again, the default: the files are then those of a node that
+ * never called this, and no alignment.csv is written.  Invalid options (hfpf_check_align_opts) are refused with HFPF_ERR_BAD_ARG and
+ * leave the setting as it was. */
+int hfpf_node_set_reference_alignment(hfpf_node* n, const hfpf_align_opts* opts);
+
 /* EXTENSION: keep the grid's session in a file and take it up again (hfpf_save / hfpf_load of include/hfpf.h on the node's grid, with
  * their errors).  Both run under the grid's own lock, so they are legal while the cloud callback and the clean thread run: a frame
  * or a clean pass lands wholly before or wholly after them.  Loading replaces the fused data only: the node stays started or stopped
