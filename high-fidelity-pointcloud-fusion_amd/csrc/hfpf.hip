@@ -321,7 +321,8 @@ struct hfpf_handle {
     DevBuf probe_a{bufs}, probe_b{bufs}, probe_c{bufs}, probe_d{bufs}, probe_e{bufs}, probe_f{bufs};
     DevBuf result_out{bufs};  // the host forms of the read-outs that return arrays: the device arrays of one call (result_alloc)
     DevBuf zbuf{bufs}, render_pose{bufs}, render_out{bufs};  // hfpf_render*: z-buffers of one chunk of views, the views' poses, hfpf_render's device planes
-    DevBuf track_in{bufs}, track_acc{bufs};                  // hfpf_track*: a host frame's device copy, the 30 int64 sums of one iteration
+    DevBuf track_in{bufs};                                   // hfpf_track*: a host frame's device copy
+    DevBuf icp_acc{bufs};                                    // refine_pose (hfpf_track*, hfpf_align_mesh*): the int64 sums of one iteration
     DevBuf query_in{bufs}, query_out{bufs};                  // hfpf_query*: a host cloud chunk or depth image, one chunk's hits and rows
     // hfpf_extract_mesh*: cube and corner keys, per corner s / record / marks / vertex counts and bases, per cube triangle counts and
     // bases, a unique count
@@ -332,7 +333,7 @@ struct hfpf_handle {
     // hfpf_compare_mesh*: the host form's mesh, the transformed vertices and triangle records, the bricks' keys / ranges / counters /
     // summary, the (brick, triangle) pairs (unsorted and sorted)
     DevBuf dev_mesh{bufs}, dev_tri{bufs}, dev_bins{bufs}, dev_pairs{bufs};
-    DevBuf align_dev{bufs}, align_acc{bufs};  // hfpf_align_mesh*: one iteration's deviation records, its 29 int64 sums
+    DevBuf align_dev{bufs};  // hfpf_align_mesh*: one iteration's deviation records
     DevBuf ray_in{bufs}, ray_out{bufs}, ray_map{bufs};  // hfpf_raycast*: a host chunk's rays, a chunk's (or band's) hits, the empty-space maps
     DevBuf snap_stage{bufs}, snap_err{bufs};            // hfpf_snapshot / hfpf_restore: the staging buffer (or one window of it), the range check's error word
     uint64_t bin_pool = 0;           // entries in bin_pt
@@ -907,6 +908,14 @@ void with_form(int form, Fn&& fn)
     else fn(std::integral_constant<int, kFormStrided>{});
 }
 
+// A run-time colour switch as a template argument: fn(std::true_type{}) or fn(std::false_type{}).
+template <typename Fn>
+void with_color(bool color, Fn&& fn)
+{
+    if (color) fn(std::true_type{});
+    else fn(std::false_type{});
+}
+
 // ... and k_integrate's colour and bin switches with it: fn(form, color, bin), each an integral constant.
 template <typename Fn>
 void with_form(int form, bool color, bool bin, Fn&& fn)
@@ -919,6 +928,22 @@ void with_form(int form, bool color, bool bin, Fn&& fn)
     };
     if (bin) with_bin(std::true_type{});
     else with_bin(std::false_type{});
+}
+
+// One launch of k_update_cells (REPLAY: in its buffer-replay mode) over nb bricks, the run-time colour and table as constants.
+template <bool COLOR, bool WIDE>
+constexpr UpdShape kUpdShapeOf = COLOR ? (WIDE ? kUpdWideColor : kUpdDenseColor) : (WIDE ? kUpdWide : kUpdDense);
+template <bool REPLAY>
+void launch_update_cells(bool color, bool wide, hipStream_t s, const GridParams& g, const Tables& t, uint32_t nb)
+{
+    with_color(color, [&](auto C) {
+        auto launch = [&](auto W) {
+            constexpr UpdShape S = kUpdShapeOf<C, W>;
+            hipLaunchKernelGGL((k_update_cells<C, S.threads, S.cap, S.slots, S.desc, S.waves, REPLAY>), dim3(nb), dim3(S.threads), 0, s, g, t, nb);
+        };
+        if (wide) launch(std::true_type{});
+        else launch(std::false_type{});
+    });
 }
 
 // The layout argument of a FORM kernel: *dl for depth images, lay for clouds.
@@ -1135,8 +1160,7 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
     } else {
         {  // the points that found no room in a bin (usually a few thousand, everything for a batch without a plan): direct forms
             const unsigned ogrid = (unsigned)std::min<uint64_t>(blocks_for((uint64_t)n_points * n_frames, 256), 8ull * 256);
-            if (color) hipLaunchKernelGGL(k_integrate_overflow<true>, dim3(ogrid), dim3(256), 0, h->stream, h->g, h->t, log_rot);
-            else hipLaunchKernelGGL(k_integrate_overflow<false>, dim3(ogrid), dim3(256), 0, h->stream, h->g, h->t, log_rot);
+            with_color(color, [&](auto C) { hipLaunchKernelGGL(k_integrate_overflow<C>, dim3(ogrid), dim3(256), 0, h->stream, h->g, h->t, log_rot); });
         }
         HIPCHK(h, detail_mark());
         if (have_plan) {
@@ -1144,22 +1168,14 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
                 detail_ran |= 2;
                 if (h->knobs.update_cells) {
                     const int shape = pick_update_shape(h, (double)n_points * n_frames, nb);
-#define HFPF_LAUNCH_UPDATE(C, S) \
-    hipLaunchKernelGGL((k_update_cells<C, S.threads, S.cap, S.slots, S.desc, S.waves>), dim3(nb), dim3(S.threads), 0, h->stream, h->g, h->t, nb)
-                    if (color && shape == 1) HFPF_LAUNCH_UPDATE(true, kUpdWideColor);
-                    else if (color) HFPF_LAUNCH_UPDATE(true, kUpdDenseColor);
-                    else if (shape == 1) HFPF_LAUNCH_UPDATE(false, kUpdWide);
-                    else HFPF_LAUNCH_UPDATE(false, kUpdDense);
-#undef HFPF_LAUNCH_UPDATE
+                    launch_update_cells<false>(color, shape == 1, h->stream, h->g, h->t, nb);
                 } else {
-                    if (color) hipLaunchKernelGGL(k_update<true>, dim3(nb), dim3(kUpdThreads), 0, h->stream, h->g, h->t, nb);
-                    else hipLaunchKernelGGL(k_update<false>, dim3(nb), dim3(kUpdThreads), 0, h->stream, h->g, h->t, nb);
+                    with_color(color, [&](auto C) { hipLaunchKernelGGL(k_update<C>, dim3(nb), dim3(kUpdThreads), 0, h->stream, h->g, h->t, nb); });
                 }
             }
             HIPCHK(h, detail_mark());
             detail_ran |= 4;
-            if (color) hipLaunchKernelGGL(k_buffer<true>, dim3(nb), dim3(256), 0, h->stream, h->g, h->t, nb);
-            else hipLaunchKernelGGL(k_buffer<false>, dim3(nb), dim3(256), 0, h->stream, h->g, h->t, nb);
+            with_color(color, [&](auto C) { hipLaunchKernelGGL(k_buffer<C>, dim3(nb), dim3(256), 0, h->stream, h->g, h->t, nb); });
             HIPCHK(h, detail_mark());
         } else {
             HIPCHK(h, detail_mark());
@@ -1509,12 +1525,10 @@ int clean_locked(hfpf_handle* h, int pre_rc)
         hipLaunchKernelGGL(k_depinc_fill, dim3(blocks_for(reg_ub, 256)), dim3(256), 0, s, t, reg_first, kCountOnDevice);
         HIPCHK(h, hipGetLastError());
         if (no_wait) {  // errors of this pass (capacity) surface at the next read-back and poison the handle there
-            if (t.color)
-                hipLaunchKernelGGL(k_replay<true>, dim3(blocks_for(reg_ub * kChains, 256)), dim3(256), 0, s, h->g, t, (const uint32_t*)t.touched_list, 1u, 0u,
+            with_color(t.color, [&](auto C) {
+                hipLaunchKernelGGL(k_replay<C>, dim3(blocks_for(reg_ub * kChains, 256)), dim3(256), 0, s, h->g, t, (const uint32_t*)t.touched_list, 1u, 0u,
                                    kCountOnDevice, n_normals);
-            else
-                hipLaunchKernelGGL(k_replay<false>, dim3(blocks_for(reg_ub * kChains, 256)), dim3(256), 0, s, h->g, t, (const uint32_t*)t.touched_list, 1u, 0u,
-                                   kCountOnDevice, n_normals);
+            });
             HIPCHK(h, hipGetLastError());
             return HFPF_OK;
         }
@@ -1567,13 +1581,8 @@ int clean_locked(hfpf_handle* h, int pre_rc)
         const bool stream = !full && h->binned && h->knobs.stream_replay && single >= (1ull << 16);
         if (stream) {
             const uint32_t nbk = (uint32_t)h->ss.n_bricks_known;
-#define HFPF_LAUNCH_STREAM(C, S) hipLaunchKernelGGL((k_update_cells<C, S.threads, S.cap, S.slots, S.desc, S.waves, true>), dim3(nbk), dim3(S.threads), 0, s, h->g, t, nbk)
             const bool wide = h->knobs.upd_shape_forced >= 0 ? h->knobs.upd_shape_forced == 1 : h->upd_wide;  // the shape the dependant updates of this session take
-            if (t.color && wide) HFPF_LAUNCH_STREAM(true, kUpdWideColor);
-            else if (t.color) HFPF_LAUNCH_STREAM(true, kUpdDenseColor);
-            else if (wide) HFPF_LAUNCH_STREAM(false, kUpdWide);
-            else HFPF_LAUNCH_STREAM(false, kUpdDense);
-#undef HFPF_LAUNCH_STREAM
+            launch_update_cells<true>(t.color, wide, s, h->g, t, nbk);
             HIPCHK(h, hipGetLastError());
         }
         const uint64_t walked = stream ? inc_touched - single : inc_touched;
@@ -1588,10 +1597,9 @@ int clean_locked(hfpf_handle* h, int pre_rc)
                 if ((rc = sort_keys_u32(h, t.touched_list, (uint32_t*)h->vals_a.p, inc_touched, slot_bits))) return rc;
                 cells = (const uint32_t*)h->vals_a.p;
             }
-            if (t.color)
-                hipLaunchKernelGGL(k_replay<true>, dim3(blocks_for(inc_touched * kChains, 256)), dim3(256), 0, s, h->g, t, cells, use_marks, stream ? 1u : 0u, inc_touched, n_normals);
-            else
-                hipLaunchKernelGGL(k_replay<false>, dim3(blocks_for(inc_touched * kChains, 256)), dim3(256), 0, s, h->g, t, cells, use_marks, stream ? 1u : 0u, inc_touched, n_normals);
+            with_color(t.color, [&](auto C) {
+                hipLaunchKernelGGL(k_replay<C>, dim3(blocks_for(inc_touched * kChains, 256)), dim3(256), 0, s, h->g, t, cells, use_marks, stream ? 1u : 0u, inc_touched, n_normals);
+            });
             HIPCHK(h, hipGetLastError());
         }
     }
@@ -2469,13 +2477,21 @@ int hfpf_render(hfpf_handle* h, const hfpf_render_opts* o, const double pose_3x4
 }
 
 // ---- pose tracking (include/hfpf.h) -------------------------------------------------------------------------------------
+// The checks on the options of refine_pose that hfpf_track* and hfpf_align_mesh* both make (Opts is either call's), with the call's
+// own stride limit.
+extern "C++" template <typename Opts>
+static bool refine_opts_ok(const Opts* o, uint32_t max_stride)
+{
+    if (o->max_iterations < 1 || o->max_iterations > 64 || o->stride < 1 || o->stride > max_stride || o->min_inliers < 6) return false;
+    if (!(std::isfinite(o->damping) && o->damping >= 0.0)) return false;
+    return std::isfinite(o->eps_rotation) && o->eps_rotation >= 0.0 && std::isfinite(o->eps_translation) && o->eps_translation >= 0.0;
+}
+
 static bool track_opts_ok(const hfpf_track_opts* o)
 {
     if (!o || o->struct_size != sizeof(hfpf_track_opts) || o->reserved != 0) return false;
-    if (o->max_iterations < 1 || o->max_iterations > 64 || o->stride < 1 || o->stride > 16 || o->min_inliers < 6) return false;
+    if (!refine_opts_ok(o, 16)) return false;
     if (!(o->max_distance > 0.0 && o->max_distance <= 1.0)) return false;
-    if (!(std::isfinite(o->damping) && o->damping >= 0.0)) return false;
-    if (!(std::isfinite(o->eps_rotation) && o->eps_rotation >= 0.0 && std::isfinite(o->eps_translation) && o->eps_translation >= 0.0)) return false;
     return view_opts_ok(&o->view);
 }
 
@@ -2595,72 +2611,40 @@ static void track_update(double T[12], const double xi[6], const double c[3])
     memcpy(T, out, sizeof out);
 }
 
-// Validated arguments in, under the lock: the model view once, then per iteration one k_track_reduce and the host solve.
-static int track_locked(hfpf_handle* h, const hfpf_track_opts* o, const PointSource& f, const double pose[12], hfpf_track_result* res)
-{
-    // the sampling of include/hfpf.h, at most 2^26 points (the headroom of the int64 sums); cols: sampled columns of a depth image
-    const uint32_t stride = o->stride;
-    const uint32_t cols = f.depth ? (f.ds.width + stride - 1) / stride : 0u;
-    const uint64_t n_samples = f.depth ? (uint64_t)cols * ((f.ds.height + stride - 1) / stride) : ((uint64_t)f.n + stride - 1) / stride;
-    if (n_samples > (1ull << 26)) return fail(h, HFPF_ERR_BAD_ARG, "track: more than 2^26 sampled points");
-    int rc;
-    if ((rc = local_read_prologue_locked(h, "track"))) return rc;
-    const uint8_t* frame = (const uint8_t*)f.dev;
-    if (f.host) {  // one copy per call, through the pinned buffers
-        if ((rc = scratch(h, h->track_in, f.bytes(f.n)))) return rc;
-        const hipError_t e = upload_pageable(h, h->track_in.p, f.host, f.bytes(f.n));
-        if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "track upload: %s", hipGetErrorString(e));
-        frame = (const uint8_t*)h->track_in.p;
-    }
-    RenderViews rv;
-    if ((rc = render_views_locked(h, &o->view, 1, pose, &rv))) return rc;
-    if ((rc = render_splat_locked(h, &rv, 0))) return rc;
-    if ((rc = scratch(h, h->track_acc, kTrackTerms * sizeof(unsigned long long)))) return rc;
+static_assert(HFPF_TRACK_CONVERGED == HFPF_ALIGN_CONVERGED && HFPF_TRACK_DEGENERATE == HFPF_ALIGN_DEGENERATE && HFPF_TRACK_TOO_FEW == HFPF_ALIGN_TOO_FEW,
+              "refine_pose writes one set of outcome flags for both calls");
 
-    TrackParams p{};
-    memcpy(p.T, pose, sizeof p.T);
-    memcpy(p.V, pose, sizeof p.V);
-    p.fx = o->view.fx, p.fy = o->view.fy, p.cx = o->view.cx, p.cy = o->view.cy, p.z_near = o->view.z_near, p.z_far = o->view.z_far;
-    p.max_d2 = o->max_distance * o->max_distance;
-    p.zc_lo = h->g.zc_lo, p.zc_hi = h->g.zc_hi;
-    p.width = o->view.width, p.height = o->view.height;
-    p.n_samples = (uint32_t)n_samples;
-    p.stride = stride;
-    p.cols = cols;
-    p.n_points = f.n;
-    const double c[3] = {pose[3], pose[7], pose[11]};
-    const int form = f.form(frame);
-    const DepthLayout dl = depth_layout(f.ds, nullptr, 0);
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(kTrackMaxBlocks, blocks_for(n_samples, 256));
-    const Row* rows = (const Row*)h->rows_dev.p;
-    const unsigned long long* zb = (const unsigned long long*)h->zbuf.p;
-    unsigned long long* acc = (unsigned long long*)h->track_acc.p;
+// The Gauss-Newton loop of hfpf_track* and hfpf_align_mesh* (include/hfpf.h, the track section), from the start pose.  Per iteration
+// enqueue(T, acc) zeroes acc and puts the n_terms int64 sums of k_track_reduce / k_align_reduce at the estimate T into it on
+// h->stream; the sums are read back, and the host solves and updates about c.  A failing enqueue returns its code at once and *res
+// (either call's result) stays as it was; otherwise the fields both results have are written, and *word29 is the last system's sum
+// 29 (track's points used; 0 with 29 terms).
+extern "C++" template <typename Opts, typename Enqueue, typename Res>
+static int refine_pose(hfpf_handle* h, const Opts* o, const double c[3], int n_terms, const double pose[12], Enqueue&& enqueue, Res* res, uint64_t* word29)
+{
+    const size_t bytes = (size_t)n_terms * sizeof(unsigned long long);
+    if (int rc = scratch(h, h->icp_acc, bytes)) return rc;
+    unsigned long long* acc = (unsigned long long*)h->icp_acc.p;
     unsigned long long local[kTrackTerms];
     unsigned long long* back = h->xfer_pin[0] ? (unsigned long long*)h->xfer_pin[0] : local;  // the read-back of the sums
-
     double T[12], A[6][6] = {}, rr = 0.0;
     memcpy(T, pose, sizeof T);
-    uint64_t inliers = 0, used = 0;
+    uint64_t inliers = 0;
     uint32_t flags = 0, it = 0;
     while (it < o->max_iterations) {
         it++;
-        memcpy(p.T, T, sizeof p.T);
-        HIPCHK(h, hipMemsetAsync(acc, 0, kTrackTerms * sizeof(unsigned long long), h->stream));
-        with_form(form, [&](auto F) {
-            hipLaunchKernelGGL((k_track_reduce<F>), dim3(blocks), dim3(256), 0, h->stream, p, frame, form_layout<F>(f.lay, &dl), rows, zb, acc);
-        });
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(back, acc, kTrackTerms * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+        if (int rc = enqueue(T, acc)) return rc;
+        HIPCHK(h, hipMemcpyAsync(back, acc, bytes, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        long long s[kTrackTerms];
-        memcpy(s, back, sizeof s);
+        long long s[kTrackTerms] = {};
+        memcpy(s, back, bytes);
         for (int i = 0, k = 0; i < 6; i++)
             for (int j = i; j < 6; j++, k++) A[i][j] = A[j][i] = (double)s[k] / kTrackScaleJJ;
         double b[6];
         for (int i = 0; i < 6; i++) b[i] = (double)s[21 + i] / kTrackScaleJR;
         rr = (double)s[27] / kTrackScaleRR;
         inliers = (uint64_t)s[28];
-        used = (uint64_t)s[29];
+        *word29 = (uint64_t)s[29];
         if (inliers < o->min_inliers) {
             flags = HFPF_TRACK_TOO_FEW;
             break;
@@ -2680,13 +2664,63 @@ static int track_locked(hfpf_handle* h, const hfpf_track_opts* o, const PointSou
     res->iterations = it;
     res->flags = flags;
     res->reserved = 0;
-    res->points_used = used;
     res->inliers = inliers;
     res->rms = inliers ? std::sqrt(rr / (double)inliers) : 0.0;
     for (int i = 0; i < 6; i++)
         for (int j = 0; j < 6; j++) res->information[6 * i + j] = A[i][j];
     memcpy(res->pose, T, sizeof T);
     return HFPF_OK;
+}
+
+// Validated arguments in, under the lock: the model view once, then refine_pose with one k_track_reduce per iteration.
+static int track_locked(hfpf_handle* h, const hfpf_track_opts* o, const PointSource& f, const double pose[12], hfpf_track_result* res)
+{
+    // the sampling of include/hfpf.h, at most 2^26 points (the headroom of the int64 sums); cols: sampled columns of a depth image
+    const uint32_t stride = o->stride;
+    const uint32_t cols = f.depth ? (f.ds.width + stride - 1) / stride : 0u;
+    const uint64_t n_samples = f.depth ? (uint64_t)cols * ((f.ds.height + stride - 1) / stride) : ((uint64_t)f.n + stride - 1) / stride;
+    if (n_samples > (1ull << 26)) return fail(h, HFPF_ERR_BAD_ARG, "track: more than 2^26 sampled points");
+    int rc;
+    if ((rc = local_read_prologue_locked(h, "track"))) return rc;
+    const uint8_t* frame = (const uint8_t*)f.dev;
+    if (f.host) {  // one copy per call, through the pinned buffers
+        if ((rc = scratch(h, h->track_in, f.bytes(f.n)))) return rc;
+        const hipError_t e = upload_pageable(h, h->track_in.p, f.host, f.bytes(f.n));
+        if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "track upload: %s", hipGetErrorString(e));
+        frame = (const uint8_t*)h->track_in.p;
+    }
+    RenderViews rv;
+    if ((rc = render_views_locked(h, &o->view, 1, pose, &rv))) return rc;
+    if ((rc = render_splat_locked(h, &rv, 0))) return rc;
+
+    TrackParams p{};
+    memcpy(p.V, pose, sizeof p.V);
+    p.fx = o->view.fx, p.fy = o->view.fy, p.cx = o->view.cx, p.cy = o->view.cy, p.z_near = o->view.z_near, p.z_far = o->view.z_far;
+    p.max_d2 = o->max_distance * o->max_distance;
+    p.zc_lo = h->g.zc_lo, p.zc_hi = h->g.zc_hi;
+    p.width = o->view.width, p.height = o->view.height;
+    p.n_samples = (uint32_t)n_samples;
+    p.stride = stride;
+    p.cols = cols;
+    p.n_points = f.n;
+    const double c[3] = {pose[3], pose[7], pose[11]};
+    const int form = f.form(frame);
+    const DepthLayout dl = depth_layout(f.ds, nullptr, 0);
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(kTrackMaxBlocks, blocks_for(n_samples, 256));
+    const Row* rows = (const Row*)h->rows_dev.p;
+    const unsigned long long* zb = (const unsigned long long*)h->zbuf.p;
+    uint64_t used = 0;
+    rc = refine_pose(h, o, c, kTrackTerms, pose, [&](const double* T, unsigned long long* acc) -> int {
+        memcpy(p.T, T, sizeof p.T);
+        HIPCHK(h, hipMemsetAsync(acc, 0, kTrackTerms * sizeof(unsigned long long), h->stream));
+        with_form(form, [&](auto F) {
+            hipLaunchKernelGGL((k_track_reduce<F>), dim3(blocks), dim3(256), 0, h->stream, p, frame, form_layout<F>(f.lay, &dl), rows, zb, acc);
+        });
+        HIPCHK(h, hipGetLastError());
+        return HFPF_OK;
+    }, res, &used);
+    if (!rc) res->points_used = used;
+    return rc;
 }
 
 static int track_depth_common(hfpf_handle* h, const hfpf_track_opts* o, const hfpf_depth_image* desc, const void* depth, bool on_device,
@@ -3559,14 +3593,12 @@ void hfpf_free_deviation(hfpf_row* rows, hfpf_deviation* dev)
 int hfpf_check_align_opts(const hfpf_align_opts* o)
 {
     if (!o || o->struct_size != sizeof(hfpf_align_opts) || (o->flags & ~HFPF_ALIGN_SKIP_BOUNDARY) || o->reserved0 != 0 || o->reserved != 0) return HFPF_ERR_BAD_ARG;
-    if (o->max_iterations < 1 || o->max_iterations > 64 || o->stride < 1 || o->stride > 65536 || o->min_inliers < 6) return HFPF_ERR_BAD_ARG;
-    if (!(std::isfinite(o->damping) && o->damping >= 0.0)) return HFPF_ERR_BAD_ARG;
-    if (!(std::isfinite(o->eps_rotation) && o->eps_rotation >= 0.0 && std::isfinite(o->eps_translation) && o->eps_translation >= 0.0)) return HFPF_ERR_BAD_ARG;
+    if (!refine_opts_ok(o, 65536)) return HFPF_ERR_BAD_ARG;
     return hfpf_check_deviation_opts(&o->compare);
 }
 
-// Validated arguments in, the mesh on the device, under the lock.  The row set; then compare's row side once and per iteration
-// compare's mesh side into h->align_dev, one k_align_reduce and track's host solve.  Not timed: hfpf_get_kernel_time has no id for it.
+// Validated arguments in, the mesh on the device, under the lock.  The row set; then compare's row side once and refine_pose with
+// compare's mesh side into h->align_dev and one k_align_reduce per iteration.  Not timed: hfpf_get_kernel_time has no id for it.
 static int align_locked(hfpf_handle* h, const hfpf_align_opts* o, const void* d_verts, uint64_t n_verts, uint32_t stride, const uint32_t* d_tris, uint64_t n_tris,
                         const double* pose, hfpf_align_result* res)
 {
@@ -3580,67 +3612,27 @@ static int align_locked(hfpf_handle* h, const hfpf_align_opts* o, const void* d_
     uint32_t *flag, *base;
     if ((rc = compare_row_scratch_locked(h, nr, "align_mesh", &rs, &flag, &base))) return rc;
     if ((rc = scratch(h, h->align_dev, (size_t)std::max<uint32_t>(rs.n, 1) * sizeof(Deviation)))) return rc;
-    if ((rc = scratch(h, h->align_acc, kAlignTerms * sizeof(unsigned long long)))) return rc;
     AlignParams p{};
     for (int a = 0; a < 3; a++) p.c[a] = (h->g.min[a] + h->g.max[a]) * 0.5;
     p.flags = o->flags, p.stride = o->stride, p.n = (uint32_t)n_samples;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(kTrackMaxBlocks, blocks_for(n_samples, 256));
     Deviation* dev = (Deviation*)h->align_dev.p;
-    unsigned long long* acc = (unsigned long long*)h->align_acc.p;
-    unsigned long long local[kAlignTerms];
-    unsigned long long* back = h->xfer_pin[0] ? (unsigned long long*)h->xfer_pin[0] : local;  // the read-back of the sums
 
     if ((rc = compare_row_side_locked(h, &rs, flag, base))) return rc;
-    double T[12], A[6][6] = {}, rr = 0.0;
-    memcpy(T, pose, sizeof T);
-    uint64_t inliers = 0;
-    uint32_t flags = 0, it = 0;
-    while (it < o->max_iterations) {
-        it++;
+    uint64_t none;
+    rc = refine_pose(h, o, p.c, kAlignTerms, pose, [&](const double* T, unsigned long long* acc) -> int {
         unsigned long long h_ctr[DC_WORDS];
-        if ((rc = compare_mesh_side_locked(h, rs, &o->compare, d_verts, n_verts, stride, d_tris, n_tris, T, dev, h_ctr))) return rc;
+        if (int e = compare_mesh_side_locked(h, rs, &o->compare, d_verts, n_verts, stride, d_tris, n_tris, T, dev, h_ctr)) return e;
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipMemsetAsync(acc, 0, kAlignTerms * sizeof(unsigned long long), h->stream));
-        if (n_samples) {
+        if (n_samples) {  // without rows the zeros are read back: TOO_FEW
             hipLaunchKernelGGL(k_align_reduce, dim3(blocks), dim3(256), 0, h->stream, p, (const Row*)h->rows_dev.p, (const Deviation*)dev, acc);
             HIPCHK(h, hipGetLastError());
         }
-        HIPCHK(h, hipMemcpyAsync(back, acc, kAlignTerms * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        long long s[kAlignTerms];
-        memcpy(s, back, sizeof s);
-        for (int i = 0, k = 0; i < 6; i++)
-            for (int j = i; j < 6; j++, k++) A[i][j] = A[j][i] = (double)s[k] / kTrackScaleJJ;
-        double b[6];
-        for (int i = 0; i < 6; i++) b[i] = (double)s[21 + i] / kTrackScaleJR;
-        rr = (double)s[27] / kTrackScaleRR;
-        inliers = (uint64_t)s[28];
-        if (inliers < o->min_inliers) {
-            flags = HFPF_ALIGN_TOO_FEW;
-            break;
-        }
-        double xi[6];
-        if (!track_solve(A, b, o->damping, xi)) {
-            flags = HFPF_ALIGN_DEGENERATE;
-            break;
-        }
-        track_update(T, xi, p.c);
-        if ((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2] < o->eps_rotation * o->eps_rotation &&
-            (xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5] < o->eps_translation * o->eps_translation) {
-            flags = HFPF_ALIGN_CONVERGED;
-            break;
-        }
-    }
-    res->iterations = it;
-    res->flags = flags;
-    res->reserved = 0;
-    res->rows_sampled = n_samples;
-    res->inliers = inliers;
-    res->rms = inliers ? std::sqrt(rr / (double)inliers) : 0.0;
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j < 6; j++) res->information[6 * i + j] = A[i][j];
-    memcpy(res->pose, T, sizeof T);
-    return HFPF_OK;
+        return HFPF_OK;
+    }, res, &none);
+    if (!rc) res->rows_sampled = n_samples;
+    return rc;
 }
 
 // The checks of both forms: the options, then compare's own on the mesh, the pose and max_distance, then the result.

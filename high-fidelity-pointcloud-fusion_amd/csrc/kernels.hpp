@@ -2311,6 +2311,55 @@ __device__ __forceinline__ unsigned long long wave_total_u64(unsigned long long 
 
 __device__ __forceinline__ unsigned long long track_q(double v, double scale) { return (unsigned long long)(long long)rint(v * scale); }
 
+// The ICP core that k_track_reduce and k_align_reduce share.  A thread's int64 sums travel by value, in and out of icp_accumulate:
+// handed over by reference, the compiler keeps a second copy of all of them across the sample loop (150 VGPRs instead of 92).
+template <int N>
+struct IcpSums {
+    unsigned long long v[N];  // 21 J_i J_j (i <= j, i outer), 6 J_i r, r r, inliers; beyond 28 the kernel's own counts
+};
+
+// One sample: the lever a (the point minus the centre the twist is taken about), the model normal n (the caller has checked
+// |n|^2 <= 2), the difference d (the point minus the model point).  A lever outside the headroom rejects the sample; otherwise
+// r = n . d, J = (a x n, n), the 28 quantised terms are added to v[0..27] and v[28] counts the inlier.
+template <int N>
+__device__ __forceinline__ IcpSums<N> icp_accumulate(IcpSums<N> sum, double ax, double ay, double az, double nx, double ny, double nz,
+                                                     double dx, double dy, double dz)
+{
+    static_assert(N >= 29, "icp_accumulate: 21 + 6 + 1 terms and the inlier count");
+    if (!(fmax(fmax(fabs(ax), fabs(ay)), fabs(az)) < kTrackHeadroom)) return sum;
+    const double r = (nx * dx + ny * dy) + nz * dz;
+    const double J[6] = {ay * nz - az * ny, az * nx - ax * nz, ax * ny - ay * nx, nx, ny, nz};
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = i; j < 6; j++) sum.v[k++] += track_q(J[i] * J[j], kTrackScaleJJ);
+#pragma unroll
+    for (int i = 0; i < 6; i++) sum.v[21 + i] += track_q(J[i] * r, kTrackScaleJR);
+    sum.v[27] += track_q(r * r, kTrackScaleRR);
+    sum.v[28] += 1;
+    return sum;
+}
+
+// The 256-thread block's totals of the sums (DPP across the wave, LDS across the four waves) into acc, which the host zeroed before
+// the launch: one 64-bit atomic per non-zero term.
+template <int N>
+__device__ __forceinline__ void icp_block_reduce(const IcpSums<N>& sum, unsigned long long* __restrict__ acc)
+{
+    __shared__ unsigned long long s_part[4][N];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const unsigned long long t = wave_total_u64(sum.v[k]);
+        if (lane == 63) s_part[wave][k] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        const unsigned long long t = (s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + (s_part[2][threadIdx.x] + s_part[3][threadIdx.x]);
+        if (t) atomicAdd(&acc[threadIdx.x], t);
+    }
+}
+
 // The two poses as the loop body reads them: from the kernarg segment (TrackParams is k_track_reduce's FIRST argument), behind an
 // empty asm as kernarg_tables() does.  Taken from the by-value argument, the compiler keeps all 24 doubles in scalar registers for
 // the whole loop and spills some of them.
@@ -2322,18 +2371,16 @@ __device__ __forceinline__ const TrackParams& track_kernarg()
 }
 
 // One sampled point per thread, grid-stride over at most kTrackMaxBlocks blocks, in any PointForm (load_point).  Sample s is pixel
-// (su * stride, sv * stride) of a depth image, record s * stride of a cloud.  Each thread keeps its 30 sums in registers; the
-// block reduces them (DPP across the wave, LDS across the four waves) and adds them to acc with one 64-bit atomic each.  acc is
-// zeroed by the host before the launch.
+// (su * stride, sv * stride) of a depth image, record s * stride of a cloud.  Each thread keeps its 30 sums in registers
+// (icp_accumulate; v[29] counts the points used); icp_block_reduce adds them to acc.
 template <int FORM>
 __global__ __launch_bounds__(256) void k_track_reduce(const TrackParams p, const uint8_t* __restrict__ frame, const PointLayout<FORM> lay,
                                                       const Row* __restrict__ rows, const unsigned long long* __restrict__ zbuf,
                                                       unsigned long long* __restrict__ acc)
 {
-    __shared__ unsigned long long s_part[4][kTrackTerms];
-    unsigned long long sum[kTrackTerms];
+    IcpSums<kTrackTerms> sum;
 #pragma unroll
-    for (int k = 0; k < kTrackTerms; k++) sum[k] = 0;
+    for (int k = 0; k < kTrackTerms; k++) sum.v[k] = 0;
     for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < p.n_samples; s += gridDim.x * blockDim.x) {
         uint64_t i = (uint64_t)s * p.stride;
         if constexpr (FORM == kFormDepth) {
@@ -2343,7 +2390,7 @@ __global__ __launch_bounds__(256) void k_track_reduce(const TrackParams p, const
         const F3 c = load_point<FORM>(frame, lay, i);
         const float x = c.x, y = c.y, z = c.z;
         if (!(__builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z) && z < p.zc_hi && z > p.zc_lo)) continue;
-        sum[29] += 1;
+        sum.v[29] += 1;
         const TrackParams& P = track_kernarg();
         const double* T = P.T;
         const double* V = P.V;
@@ -2371,30 +2418,9 @@ __global__ __launch_bounds__(256) void k_track_reduce(const TrackParams p, const
         const double nx = q0.w, ny = q1.x, nz = q1.y;
         if (!(((dx * dx + dy * dy) + dz * dz) <= p.max_d2)) continue;
         if (!(((nx * nx + ny * ny) + nz * nz) <= 2.0)) continue;
-        if (!(fmax(fmax(fabs(ax), fabs(ay)), fabs(az)) < kTrackHeadroom)) continue;
-        const double r = (nx * dx + ny * dy) + nz * dz;
-        const double J[6] = {ay * nz - az * ny, az * nx - ax * nz, ax * ny - ay * nx, nx, ny, nz};
-        int k = 0;
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-#pragma unroll
-            for (int j = i; j < 6; j++) sum[k++] += track_q(J[i] * J[j], kTrackScaleJJ);
-#pragma unroll
-        for (int i = 0; i < 6; i++) sum[21 + i] += track_q(J[i] * r, kTrackScaleJR);
-        sum[27] += track_q(r * r, kTrackScaleRR);
-        sum[28] += 1;
+        sum = icp_accumulate(sum, ax, ay, az, nx, ny, nz, dx, dy, dz);
     }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < kTrackTerms; k++) {
-        const unsigned long long t = wave_total_u64(sum[k]);
-        if (lane == 63) s_part[wave][k] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < kTrackTerms) {
-        const unsigned long long t = (s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + (s_part[2][threadIdx.x] + s_part[3][threadIdx.x]);
-        if (t) atomicAdd(&acc[threadIdx.x], t);
-    }
+    icp_block_reduce(sum, acc);
 }
 
 
@@ -4181,16 +4207,14 @@ struct AlignParams {
 };
 
 // One sampled row per thread, grid-stride over at most kTrackMaxBlocks blocks.  The row's point and normal come in as k_track_reduce
-// loads them, its deviation record as two 16-byte loads.  Each thread keeps its 29 sums in registers; the block reduces them (DPP
-// across the wave, LDS across the four waves) and adds the non-zero ones to acc with one 64-bit atomic each.  acc is zeroed by the
-// host before the launch.
+// loads them, its deviation record as two 16-byte loads.  Each thread keeps its 29 sums in registers (icp_accumulate);
+// icp_block_reduce adds them to acc.
 __global__ __launch_bounds__(256) void k_align_reduce(const AlignParams p, const Row* __restrict__ rows, const Deviation* __restrict__ dev,
                                                       unsigned long long* __restrict__ acc)
 {
-    __shared__ unsigned long long s_part[4][kAlignTerms];
-    unsigned long long sum[kAlignTerms];
+    IcpSums<kAlignTerms> sum;
 #pragma unroll
-    for (int k = 0; k < kAlignTerms; k++) sum[k] = 0;
+    for (int k = 0; k < kAlignTerms; k++) sum.v[k] = 0;
     for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < p.n; s += gridDim.x * blockDim.x) {
         const uint32_t j = s * p.stride;  // < the row count, which is below 2^32 - 1
         const uint4 d0 = *reinterpret_cast<const uint4*>(&dev[j].signed_distance);  // signed_distance, distance, tri, flags
@@ -4204,32 +4228,9 @@ __global__ __launch_bounds__(256) void k_align_reduce(const AlignParams p, const
         const double nx = q0.w, ny = q1.x, nz = q1.y;
         if (!(((nx * nx + ny * ny) + nz * nz) <= 2.0)) continue;
         const double qx = d1.x, qy = d1.y, qz = d1.z;
-        const double ax = qx - p.c[0], ay = qy - p.c[1], az = qz - p.c[2];
-        if (!(fmax(fmax(fabs(ax), fabs(ay)), fabs(az)) < kTrackHeadroom)) continue;
-        const double dx = qx - (double)q0.x, dy = qy - (double)q0.y, dz = qz - (double)q0.z;
-        const double r = (nx * dx + ny * dy) + nz * dz;
-        const double J[6] = {ay * nz - az * ny, az * nx - ax * nz, ax * ny - ay * nx, nx, ny, nz};
-        int k = 0;
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-#pragma unroll
-            for (int jj = i; jj < 6; jj++) sum[k++] += track_q(J[i] * J[jj], kTrackScaleJJ);
-#pragma unroll
-        for (int i = 0; i < 6; i++) sum[21 + i] += track_q(J[i] * r, kTrackScaleJR);
-        sum[27] += track_q(r * r, kTrackScaleRR);
-        sum[28] += 1;
+        sum = icp_accumulate(sum, qx - p.c[0], qy - p.c[1], qz - p.c[2], nx, ny, nz, qx - (double)q0.x, qy - (double)q0.y, qz - (double)q0.z);
     }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < kAlignTerms; k++) {
-        const unsigned long long t = wave_total_u64(sum[k]);
-        if (lane == 63) s_part[wave][k] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < kAlignTerms) {
-        const unsigned long long t = (s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + (s_part[2][threadIdx.x] + s_part[3][threadIdx.x]);
-        if (t) atomicAdd(&acc[threadIdx.x], t);
-    }
+    icp_block_reduce(sum, acc);
 }
 
 }  // namespace hfpf

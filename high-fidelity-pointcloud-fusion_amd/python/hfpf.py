@@ -204,17 +204,27 @@ def track_opts(K, width, height, max_iterations=10, stride=1, min_inliers=6, max
     return o
 
 
-def track_result():
-    r = TrackResult()
-    r.struct_size = C.sizeof(TrackResult)
+def _sized(cls):
+    """A result structure of the C ABI with its struct_size filled in."""
+    r = cls()
+    r.struct_size = C.sizeof(cls)
     return r
+
+
+def track_result():
+    return _sized(TrackResult)
+
+
+def _refine_out(r, own):
+    """The result dict of an hfpf_track_result or hfpf_align_result; own names the field only that one has."""
+    return {"iterations": r.iterations, "flags": r.flags, own: getattr(r, own), "inliers": r.inliers, "rms": r.rms,
+            "information": np.array(r.information[:], np.float64).reshape(6, 6), "pose": np.array(r.pose[:], np.float64).reshape(3, 4)}
 
 
 def _track_out(r):
     """(3x4 pose, result dict) of an hfpf_track_result."""
-    pose = np.array(r.pose[:], np.float64).reshape(3, 4)
-    return pose, {"iterations": r.iterations, "flags": r.flags, "points_used": r.points_used, "inliers": r.inliers, "rms": r.rms,
-                  "information": np.array(r.information[:], np.float64).reshape(6, 6), "pose": pose}
+    out = _refine_out(r, "points_used")
+    return out["pose"], out
 
 
 # hfpf_query_opts.flags and hfpf_query_hit.flags (include/hfpf.h)
@@ -355,20 +365,12 @@ def align_opts(max_iterations=10, stride=1, min_inliers=6, min_count=0.0, max_di
 
 
 def align_result():
-    r = AlignResult()
-    r.struct_size = C.sizeof(AlignResult)
-    return r
+    return _sized(AlignResult)
 
 
 def check_align_opts(o):
     """hfpf_check_align_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
     return lib().hfpf_check_align_opts(C.byref(o) if o is not None else None)
-
-
-def _align_out(r):
-    """The result dict of an hfpf_align_result."""
-    return {"iterations": r.iterations, "flags": r.flags, "rows_sampled": r.rows_sampled, "inliers": r.inliers, "rms": r.rms,
-            "information": np.array(r.information[:], np.float64).reshape(6, 6), "pose": np.array(r.pose[:], np.float64).reshape(3, 4)}
 
 
 def read_ply(path):
@@ -1039,7 +1041,7 @@ class OccupancyGrid:
         if device:
             self._chk(lib().hfpf_align_mesh_device(self._h, C.byref(o), C.c_void_p(verts), int(n_verts), int(vertex_stride), C.c_void_p(tris),
                                                    int(n_tris), _p(pose), C.byref(r)))
-            return _align_out(r)
+            return _refine_out(r, "rows_sampled")
         verts = np.ascontiguousarray(verts)
         if verts.dtype != MESH_VERTEX_DTYPE:
             verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
@@ -1049,7 +1051,7 @@ class OccupancyGrid:
         nt = int(n_tris) if n_tris is not None else len(tris)
         self._chk(lib().hfpf_align_mesh(self._h, C.byref(o), _p(verts) if verts.nbytes else None, nv, stride, _p(tris) if tris.nbytes else None, nt,
                                         _p(pose), C.byref(r)))
-        return _align_out(r)
+        return _refine_out(r, "rows_sampled")
 
     # -- casting rays against the model --
     def raycast(self, rays, pose, opts=None, **kw):

@@ -127,6 +127,54 @@ def test_bit_exact_against_track_ref(hfpf_mod, synth_mod, session, stride, fmt):
     assert got[1]["iterations"] > 1 and got[1]["inliers"] > 1000
 
 
+# The shared sample loop outside the sizes the tests above give it: kTrackMaxBlocks * 256 = 524,288 threads, one block = 256.
+
+@pytest.fixture(scope="module")
+def held_out_cloud(synth_mod):
+    depth, K, true = _held_out(synth_mod)
+    return depth_ref.packed_cloud(depth, K), K, _perturb(true, 2.0, (0.006, -0.005, 0.006))
+
+
+@pytest.fixture(scope="module")
+def doubled(session, held_out_cloud):
+    """The held-out frame's cloud twice over (614,400 records) and its reference result, computed once for both forms."""
+    cloud, K, guess = held_out_cloud
+    both = np.concatenate([cloud.reshape(-1), cloud.reshape(-1)])
+    xyz = both.view(np.float32).reshape(-1, 4)[:, :3]
+    assert len(xyz) == 2 * 640 * 480 > 2048 * 256
+    return both, _ref(session[2], TR.cloud_points(xyz, 1), guess, K, 640, 480, max_iterations=2)
+
+
+@pytest.mark.parametrize("fmt", ["packed", "wide"])
+def test_more_samples_than_grid_threads(hfpf_mod, session, held_out_cloud, doubled, fmt):
+    """Every thread of the full grid takes a second trip of the grid-stride loop."""
+    sc, g, rows = session
+    _, K, guess = held_out_cloud
+    both, ref = doubled
+    got = g.track(both if fmt == "packed" else _wide(both), PACKED if fmt == "packed" else WIDE, guess, K, 640, 480, stride=1,
+                  **dict(OPTS, max_iterations=2))
+    print("%s: %d iterations, flags %d, %d of %d used points inliers" % (fmt, got[1]["iterations"], got[1]["flags"], got[1]["inliers"],
+                                                                       got[1]["points_used"]))
+    _same_result(got, ref, "614,400 records, %s" % fmt)
+    assert got[1]["points_used"] == ref["points_used"] > 2048 * 256 // 2
+
+
+def test_fewer_samples_than_one_wave(hfpf_mod, session, held_out_cloud):
+    """40 used points: three of the block's four waves contribute zeros.  Below min_inliers = 6 inliers the result must be the
+    reference's TOO_FEW with the same sums."""
+    sc, g, rows = session
+    cloud, K, guess = held_out_cloud
+    rec = cloud.view(np.float32).reshape(-1, 4)
+    few = np.ascontiguousarray(rec[TR.used(rec[:, :3], Z_CLIP)][:40])
+    assert len(few) == 40
+    got = g.track(few.view(np.uint8).reshape(-1), PACKED, guess, K, 640, 480, stride=1, **OPTS)
+    ref = _ref(rows, TR.cloud_points(few[:, :3], 1), guess, K, 640, 480)
+    print("40 records: %d iterations, flags %d, %d of %d used points inliers" % (got[1]["iterations"], got[1]["flags"], got[1]["inliers"],
+                                                                              got[1]["points_used"]))
+    _same_result(got, ref, "40 records")
+    assert got[1]["points_used"] == 40 and (got[1]["inliers"] >= 6 or got[1]["flags"] == TR.TOO_FEW)
+
+
 # ---- 2. accuracy ----------------------------------------------------------------------------------------------------
 # Targets: translation error <= 1 mm and rotation error <= 0.1 degrees, and always at least 10x smaller than at the start.  The
 # first MI355X run measured 0.046-0.049 mm / 0.015-0.024 degrees from these starts (and 0.042 mm / 0.012 degrees from the true
