@@ -334,6 +334,7 @@ struct hfpf_handle {
     // summary, the (brick, triangle) pairs (unsorted and sorted)
     DevBuf dev_mesh{bufs}, dev_tri{bufs}, dev_bins{bufs}, dev_pairs{bufs};
     DevBuf align_dev{bufs};  // hfpf_align_mesh*: one iteration's deviation records
+    DevBuf cov_bins{bufs};   // hfpf_cover_mesh*: the summary, the 64-bit sample total, the triangles' sample counts and their offsets
     DevBuf ray_in{bufs}, ray_out{bufs}, ray_map{bufs};  // hfpf_raycast*: a host chunk's rays, a chunk's (or band's) hits, the empty-space maps
     DevBuf snap_stage{bufs}, snap_err{bufs};            // hfpf_snapshot / hfpf_restore: the staging buffer (or one window of it), the range check's error word
     uint64_t bin_pool = 0;           // entries in bin_pt
@@ -3514,20 +3515,28 @@ static int compare_locked(hfpf_handle* h, const hfpf_deviation_opts* o, const vo
     return HFPF_OK;
 }
 
-// The checks of both forms that need the handle but not the device.  0 = fine, else the text of the fault.
-static const char* compare_args_fault(const hfpf_handle* h, const hfpf_deviation_opts* o, const void* verts, uint64_t n_verts, uint32_t stride, const uint32_t* tris,
-                                      uint64_t n_tris, const double* pose, const void* dev, const void* n_rows, const void* summary, bool on_device)
+// The checks on a mesh and its pose that compare, align and cover share.  0 = fine, else the text of the fault.
+static const char* mesh_args_fault(const void* verts, uint64_t n_verts, uint32_t stride, const uint32_t* tris, uint64_t n_tris, const double* pose)
 {
-    if (hfpf_check_deviation_opts(o) != HFPF_OK) return "invalid hfpf_deviation_opts";
-    if (o->max_distance > 32.0 * h->g.res) return "max_distance exceeds 32 voxels";
     if (!pose) return "NULL pose";
     for (int i = 0; i < 12; i++)
         if (!std::isfinite(pose[i])) return "non-finite pose";
     if (stride < 12 || (stride & 3)) return "vertex_stride must be at least 12 and a multiple of 4";
     if ((!verts && n_verts) || (!tris && n_tris)) return "NULL mesh pointer with a non-zero count";
     if (n_verts >= 0xFFFFFFFFull || n_tris >= 0xFFFFFFFFull) return "n_verts and n_tris must stay below 2^32 - 1";
+    return nullptr;
+}
+static bool mesh_misaligned(const void* verts, const uint32_t* tris) { return ((((uintptr_t)verts) | ((uintptr_t)tris)) & 3) != 0; }
+
+// The checks of both forms that need the handle but not the device.  0 = fine, else the text of the fault.
+static const char* compare_args_fault(const hfpf_handle* h, const hfpf_deviation_opts* o, const void* verts, uint64_t n_verts, uint32_t stride, const uint32_t* tris,
+                                      uint64_t n_tris, const double* pose, const void* dev, const void* n_rows, const void* summary, bool on_device)
+{
+    if (hfpf_check_deviation_opts(o) != HFPF_OK) return "invalid hfpf_deviation_opts";
+    if (o->max_distance > 32.0 * h->g.res) return "max_distance exceeds 32 voxels";
+    if (const char* f = mesh_args_fault(verts, n_verts, stride, tris, n_tris, pose)) return f;
     if (!dev || !n_rows || !summary) return "NULL dev, n_rows or summary";
-    if (on_device && ((((uintptr_t)verts) | ((uintptr_t)tris)) & 3)) return "device mesh pointers must be 4-byte aligned";
+    if (on_device && mesh_misaligned(verts, tris)) return "device mesh pointers must be 4-byte aligned";
     return nullptr;
 }
 
@@ -3668,6 +3677,130 @@ int hfpf_align_mesh(hfpf_handle* h, const hfpf_align_opts* o, const void* verts,
     if (int rc = upload_mesh_locked(h, "align_mesh", verts, n_verts, vertex_stride, tris, n_tris, &d_tris)) return rc;
     return align_locked(h, o, h->dev_mesh.p, n_verts, vertex_stride, d_tris, n_tris, pose_3x4, result);
 }
+
+// ---- coverage of a triangle mesh by the model (include/hfpf.h) ----------------------------------------------------------------
+int hfpf_check_cover_opts(const hfpf_cover_opts* o)
+{
+    if (!o || o->struct_size != sizeof(hfpf_cover_opts) || (o->flags & ~HFPF_COVER_ABS_NORMAL) || o->reserved != 0) return HFPF_ERR_BAD_ARG;
+    if (o->radius < 1 || o->radius > kQueryMaxRadius || o->max_subdivision < 1 || o->max_subdivision > 64 || std::isnan(o->min_count)) return HFPF_ERR_BAD_ARG;
+    if (!(std::isfinite(o->max_distance) && o->max_distance > 0.0 && o->max_distance <= 1.0)) return HFPF_ERR_BAD_ARG;
+    if (!(std::isfinite(o->spacing) && o->spacing > 0.0)) return HFPF_ERR_BAD_ARG;
+    return std::isfinite(o->min_normal_dot) && o->min_normal_dot >= -2.0 && o->min_normal_dot <= 1.0 ? HFPF_OK : HFPF_ERR_BAD_ARG;
+}
+
+// Validated arguments in, the mesh on the device, n_tris > 0, under the lock.  The transformed vertices (compare's kernel); per
+// triangle a record, the geometry and a sample count; the scan of the counts; one lane per sample; per triangle its share of the
+// summary.  The 64-bit total is read back once in front of the scan (whose 32-bit total cannot tell an overflow): the capacity
+// check and the size of the sample launch.  *out: the n_tris records.  Not timed: hfpf_get_kernel_time has no id for it.
+static int cover_locked(hfpf_handle* h, const hfpf_cover_opts* o, const void* d_verts, uint64_t n_verts, uint32_t stride, const uint32_t* d_tris, uint64_t n_tris,
+                        const double* pose, bool on_device, ResultSet* out, hfpf_coverage_summary* summary)
+{
+    *out = ResultSet{};
+    int rc;
+    const size_t T1 = (size_t)n_tris + 1;
+    const size_t v_bytes = (size_t)std::max<uint64_t>(n_verts, 1) * 24;
+    if ((rc = scratch(h, h->dev_tri, v_bytes + (size_t)n_tris * sizeof(CovTri)))) return rc;
+    if ((rc = scratch(h, h->cov_bins, sizeof(CovSummary) + 8 + 2 * T1 * 4))) return rc;
+    double* V = (double*)h->dev_tri.p;
+    CovTri* geo = (CovTri*)((char*)h->dev_tri.p + v_bytes);
+    CovSummary* d_sum = (CovSummary*)h->cov_bins.p;
+    unsigned long long* d_total = (unsigned long long*)(d_sum + 1);
+    uint32_t* count = (uint32_t*)(d_total + 1);
+    uint32_t* offset = count + T1;
+    ResultSet set;
+    set.add((size_t)n_tris * sizeof(TriCoverage));
+    if ((rc = result_alloc(h, set, on_device, "cover_mesh"))) return rc;
+    TriCoverage* cov = (TriCoverage*)set.a[0].dev;
+    auto give_up = [&](int code) {
+        set.release();
+        return code;
+    };
+    DevParams vp{};  // what k_dev_verts reads of it
+    memcpy(vp.T, pose, sizeof vp.T);
+    vp.n_verts = n_verts, vp.n_tris = (uint32_t)n_tris, vp.stride = stride;
+    CovParams p{};
+    p.spacing = o->spacing, p.min_count = std::max(1.0, o->min_count), p.max_d2 = o->max_distance * o->max_distance, p.min_dot = o->min_normal_dot;
+    p.n_verts = n_verts, p.n_tris = (uint32_t)n_tris, p.max_sub = o->max_subdivision;
+    p.abs_normal = (o->flags & HFPF_COVER_ABS_NORMAL) ? 1u : 0u, p.radius = o->radius;
+    hipError_t e = hipMemsetAsync(d_sum, 0, sizeof(CovSummary) + 8, h->stream);
+    if (e != hipSuccess) return give_up(fail(h, HFPF_ERR_HIP, "cover_mesh: %s", hipGetErrorString(e)));
+    hipLaunchKernelGGL(k_dev_verts, dim3(blocks_for(n_verts, 256)), dim3(256), 0, h->stream, vp, (const uint8_t*)d_verts, V);
+    hipLaunchKernelGGL(k_cov_setup, dim3(blocks_for(T1, 256)), dim3(256), 0, h->stream, p, d_tris, (const double*)V, cov, geo, count, d_total);
+    unsigned long long total = 0;
+    if ((e = hipGetLastError()) == hipSuccess) e = hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return give_up(fail(h, HFPF_ERR_HIP, "cover_mesh: %s", hipGetErrorString(e)));
+    if (total > 0xFFFFFFFEull)  // nothing on the handle was touched: it stays usable
+        return give_up(fail(h, HFPF_ERR_CAPACITY, "cover_mesh: %llu samples exceed the 2^32 - 2 a call takes (a larger spacing or a smaller max_subdivision)", total));
+    if (total) {
+        uint64_t scanned = 0;
+        if ((rc = scan_counts_locked(h, count, offset, n_tris, &scanned))) return give_up(rc);
+        if (scanned != total) return give_up(fail(h, HFPF_ERR_STATE, "cover_mesh: the scan of the sample counts disagrees with their sum (internal)"));
+        hipLaunchKernelGGL(k_cov_samples, dim3(blocks_for(total, 256)), dim3(256), 0, h->stream, h->g, h->t, p, (const uint32_t*)offset, (const CovTri*)geo,
+                           (uint32_t)total, cov);
+    }
+    hipLaunchKernelGGL(k_cov_finish, dim3(blocks_for(n_tris, 256)), dim3(256), 0, h->stream, (uint32_t)n_tris, (const TriCoverage*)cov, (const CovTri*)geo, d_sum);
+    CovSummary hs;
+    if ((e = hipGetLastError()) == hipSuccess) e = hipMemcpyAsync(&hs, d_sum, sizeof hs, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return give_up(fail(h, HFPF_ERR_HIP, "cover_mesh: %s", hipGetErrorString(e)));
+    static_assert(sizeof(CovSummary) == sizeof(hfpf_coverage_summary), "the device summary is the public one, max_distance as bits");
+    memcpy(summary, &hs, sizeof hs);
+    *out = set;
+    return HFPF_OK;
+}
+
+// The checks of both forms.  0 = fine, else the text of the fault.
+static const char* cover_args_fault(const hfpf_cover_opts* o, const void* verts, uint64_t n_verts, uint32_t stride, const uint32_t* tris, uint64_t n_tris,
+                                    const double* pose, const void* cov, const void* summary, bool on_device)
+{
+    if (hfpf_check_cover_opts(o) != HFPF_OK) return "invalid hfpf_cover_opts";
+    if (const char* f = mesh_args_fault(verts, n_verts, stride, tris, n_tris, pose)) return f;
+    if (!cov || !summary) return "NULL cov or summary";
+    if (on_device && mesh_misaligned(verts, tris)) return "device mesh pointers must be 4-byte aligned";
+    return nullptr;
+}
+
+int hfpf_cover_mesh_device(hfpf_handle* h, const hfpf_cover_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* dev_tris,
+                           uint64_t n_tris, const double* pose_3x4, hfpf_tri_coverage** dev_cov, hfpf_coverage_summary* summary)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (const char* f = cover_args_fault(o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, dev_cov, summary, true))
+        return fail(h, HFPF_ERR_BAD_ARG, "cover_mesh_device: %s", f);
+    if (int rc = local_read_prologue_locked(h, "cover_mesh")) return rc;
+    ResultSet set;
+    hfpf_coverage_summary s;
+    memset(&s, 0, sizeof s);
+    if (n_tris)
+        if (int rc = cover_locked(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, true, &set, &s)) return rc;
+    *dev_cov = (hfpf_tri_coverage*)set.a[0].dev, *summary = s;
+    return HFPF_OK;
+}
+
+int hfpf_cover_mesh(hfpf_handle* h, const hfpf_cover_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
+                    const double* pose_3x4, hfpf_tri_coverage** cov, hfpf_coverage_summary* summary)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (const char* f = cover_args_fault(o, verts, n_verts, vertex_stride, tris, n_tris, pose_3x4, cov, summary, false))
+        return fail(h, HFPF_ERR_BAD_ARG, "cover_mesh: %s", f);
+    if (int rc = local_read_prologue_locked(h, "cover_mesh")) return rc;
+    hfpf_coverage_summary s;
+    memset(&s, 0, sizeof s);
+    void* host[3] = {nullptr, nullptr, nullptr};
+    if (n_tris) {
+        const uint32_t* d_tris = nullptr;
+        if (int rc = upload_mesh_locked(h, "cover_mesh", verts, n_verts, vertex_stride, tris, n_tris, &d_tris)) return rc;
+        ResultSet set;
+        if (int rc = cover_locked(h, o, h->dev_mesh.p, n_verts, vertex_stride, d_tris, n_tris, pose_3x4, false, &set, &s)) return rc;
+        if (int rc = result_to_host(h, set, "cover_mesh", host)) return rc;
+    }
+    *cov = (hfpf_tri_coverage*)host[0], *summary = s;
+    return HFPF_OK;
+}
+
+void hfpf_free_coverage(hfpf_tri_coverage* cov) { free(cov); }
 
 int hfpf_stats_export(hfpf_handle* h, const void** dev_words, uint64_t* n_words, const void** dev_cwords, uint64_t* n_cwords)
 {

@@ -3872,6 +3872,32 @@ __global__ __launch_bounds__(256) void k_dev_verts(const DevParams p, const uint
     for (int a = 0; a < 3; a++) V[3 * i + a] = ((p.T[4 * a] * x + p.T[4 * a + 1] * y) + p.T[4 * a + 2] * z) + p.T[4 * a + 3];
 }
 
+// The validity rules of a triangle, shared by compare and cover (include/hfpf.h, the deviation section), in the contract's order:
+// indices, finite coordinates, NN.  False when triangle k is invalid; else tr, its edges, NN and L2 = the longest edge squared.
+__device__ inline bool dev_tri_valid(const uint64_t n_verts, const uint32_t* __restrict__ tris, const double* __restrict__ V, const uint32_t k, DevTri& tr,
+                                     double (&ab)[3], double (&ac)[3], double& NN, double& L2)
+{
+    const uint32_t i0 = tris[3ull * k], i1 = tris[3ull * k + 1], i2 = tris[3ull * k + 2];
+    if (i0 >= n_verts || i1 >= n_verts || i2 >= n_verts) return false;  // before anything is loaded through them
+    bool finite = true;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        tr.A[a] = V[3ull * i0 + a], tr.B[a] = V[3ull * i1 + a], tr.C[a] = V[3ull * i2 + a];
+        finite = finite && isfinite(tr.A[a]) && isfinite(tr.B[a]) && isfinite(tr.C[a]);
+    }
+    if (!finite) return false;
+    double bc[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) ab[a] = tr.B[a] - tr.A[a], ac[a] = tr.C[a] - tr.A[a], bc[a] = tr.C[a] - tr.B[a];
+    tr.N[0] = ab[1] * ac[2] - ab[2] * ac[1];
+    tr.N[1] = ab[2] * ac[0] - ab[0] * ac[2];
+    tr.N[2] = ab[0] * ac[1] - ab[1] * ac[0];
+    NN = dev_dot(tr.N, tr.N);
+    if (!(isfinite(NN) && NN > 0.0)) return false;
+    L2 = fmax(dev_dot(ab, ab), fmax(dev_dot(ac, ac), dev_dot(bc, bc)));
+    return true;
+}
+
 // Triangle k: false when it is invalid.  Else tr, the range lo..hi of bricks its inflated box reaches, and everywhere = list it in
 // every brick.
 //
@@ -3894,26 +3920,11 @@ __global__ __launch_bounds__(256) void k_dev_verts(const DevParams p, const uint
 __device__ inline bool dev_tri_setup(const GridParams& g, const DevParams& p, const uint32_t* __restrict__ tris, const double* __restrict__ V, const uint32_t k,
                                      DevTri& tr, int32_t (&lo)[3], int32_t (&hi)[3], bool& everywhere)
 {
-    const uint32_t i0 = tris[3ull * k], i1 = tris[3ull * k + 1], i2 = tris[3ull * k + 2];
-    if (i0 >= p.n_verts || i1 >= p.n_verts || i2 >= p.n_verts) return false;  // before anything is loaded through them
+    double ab[3], ac[3], NN, L2;
+    if (!dev_tri_valid(p.n_verts, tris, V, k, tr, ab, ac, NN, L2)) return false;
     double M = 0.0;
-    bool finite = true;
 #pragma unroll
-    for (int a = 0; a < 3; a++) {
-        tr.A[a] = V[3ull * i0 + a], tr.B[a] = V[3ull * i1 + a], tr.C[a] = V[3ull * i2 + a];
-        finite = finite && isfinite(tr.A[a]) && isfinite(tr.B[a]) && isfinite(tr.C[a]);
-        M = fmax(M, fmax(fabs(tr.A[a]), fmax(fabs(tr.B[a]), fabs(tr.C[a]))));
-    }
-    if (!finite) return false;
-    const double ab[3] = {tr.B[0] - tr.A[0], tr.B[1] - tr.A[1], tr.B[2] - tr.A[2]};
-    const double ac[3] = {tr.C[0] - tr.A[0], tr.C[1] - tr.A[1], tr.C[2] - tr.A[2]};
-    const double bc[3] = {tr.C[0] - tr.B[0], tr.C[1] - tr.B[1], tr.C[2] - tr.B[2]};
-    tr.N[0] = ab[1] * ac[2] - ab[2] * ac[1];
-    tr.N[1] = ab[2] * ac[0] - ab[0] * ac[2];
-    tr.N[2] = ab[0] * ac[1] - ab[1] * ac[0];
-    const double NN = dev_dot(tr.N, tr.N);
-    if (!(isfinite(NN) && NN > 0.0)) return false;
-    const double L2 = fmax(dev_dot(ab, ab), fmax(dev_dot(ac, ac), dev_dot(bc, bc)));
+    for (int a = 0; a < 3; a++) M = fmax(M, fmax(fabs(tr.A[a]), fmax(fabs(tr.B[a]), fabs(tr.C[a]))));
     const double face = 0x1p-43 * ((L2 * sqrt(L2)) * (p.reach * p.reach)) / NN;
     everywhere = !(face <= p.face_cap);  // also an overflow to inf or NaN
     const double infl = (p.md * (1.0 + 0x1p-40) + face) + 0x1p-49 * (M + p.md);
@@ -4231,6 +4242,190 @@ __global__ __launch_bounds__(256) void k_align_reduce(const AlignParams p, const
         sum = icp_accumulate(sum, qx - p.c[0], qy - p.c[1], qz - p.c[2], nx, ny, nz, qx - (double)q0.x, qy - (double)q0.y, qz - (double)q0.z);
     }
     icp_block_reduce(sum, acc);
+}
+
+
+// ---- coverage of a triangle mesh by the model (hfpf_cover_mesh*; contract in include/hfpf.h, numpy restatement tests/cover_ref.py) -----
+// A triangle holds 1 to 4096 samples, so the work is laid out per SAMPLE: k_cov_setup gives every triangle its record, its geometry
+// and its sample count, an exclusive scan turns the counts into offsets, and k_cov_samples runs one lane per sample, whatever the
+// mix of triangle sizes.  A sample is a query (voxel_coords, valid_point, window_nearest: k_query's own calls); the per-triangle
+// counts are summed over the runs of equal triangle inside a wave and then with integer atomics, so nothing depends on the order.
+struct TriCoverage {  // = hfpf_tri_coverage; max_distance as the bits of a non-negative float, which order as the floats do
+    uint32_t n_samples, n_in_bbox, n_covered, flags;
+    float area;
+    uint32_t max_distance_bits;
+    long long sum_dist_q30;
+};
+static_assert(sizeof(TriCoverage) == 32, "coverage record is 32 bytes");
+
+struct CovSummary {  // = hfpf_coverage_summary, max_distance as bits
+    unsigned long long n_tris_valid, n_tris_invalid, n_tris_huge, n_samples, n_in_bbox, n_covered;
+    long long sum_dist_q30;
+    unsigned long long area_q40_lo, area_q40_hi, covered_q40_lo, covered_q40_hi;
+    uint32_t max_distance_bits, pad;
+};
+static_assert(sizeof(CovSummary) == 96, "coverage summary is 96 bytes");
+
+struct CovTri {  // a valid triangle as k_cov_samples reads it
+    double A[3], ab[3], ac[3], N[3];
+    double s;  // sqrt(NN)
+    uint32_t n, pad;
+};
+static_assert(sizeof(CovTri) == 112, "sampled triangle is 112 bytes");
+
+struct CovParams {
+    double spacing;
+    double min_count;  // max(1, min_count)
+    double max_d2;     // max_distance * max_distance
+    double min_dot;    // min_normal_dot; -2 = gate off
+    uint64_t n_verts;
+    uint32_t n_tris, max_sub;
+    uint32_t abs_normal;  // HFPF_COVER_ABS_NORMAL
+    int32_t radius;
+};
+
+constexpr uint32_t kCovValid = 1u, kCovCapped = 2u, kCovHuge = 4u;
+
+// One thread per triangle, and one more that zeroes the scan's extra element: the record (all zero for an invalid triangle), the
+// geometry and count[k] = n^2 (0 for an invalid one).  total += the counts, as 64 bits: the u32 scan cannot say that it overflowed.
+__global__ __launch_bounds__(256) void k_cov_setup(const CovParams p, const uint32_t* __restrict__ tris, const double* __restrict__ V,
+                                                   TriCoverage* __restrict__ cov, CovTri* __restrict__ geo, uint32_t* __restrict__ count,
+                                                   unsigned long long* __restrict__ total)
+{
+    const uint64_t kk = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    unsigned long long mine = 0;
+    if (kk < p.n_tris) {
+        const uint32_t k = (uint32_t)kk;
+        DevTri tr;
+        double ab[3], ac[3], NN = 0.0, L2 = 0.0;
+        TriCoverage c{};
+        if (dev_tri_valid(p.n_verts, tris, V, k, tr, ab, ac, NN, L2)) {
+            const double q = sqrt(L2) / p.spacing;
+            const uint32_t n = !(q > 1.0) ? 1u : q >= (double)p.max_sub ? p.max_sub : (uint32_t)ceil(q);
+            const double s = sqrt(NN), area_d = 0.5 * s;
+            c.n_samples = n * n;
+            c.flags = kCovValid | (q > (double)p.max_sub ? kCovCapped : 0u) | (!(area_d < 0x1p23) ? kCovHuge : 0u);
+            c.area = (float)area_d;
+            CovTri t;
+#pragma unroll
+            for (int a = 0; a < 3; a++) t.A[a] = tr.A[a], t.ab[a] = ab[a], t.ac[a] = ac[a], t.N[a] = tr.N[a];
+            t.s = s, t.n = n, t.pad = 0;
+            geo[k] = t;
+        }
+        cov[k] = c;
+        count[k] = c.n_samples;
+        mine = c.n_samples;
+    } else if (kk == p.n_tris) {
+        count[kk] = 0;
+    }
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
+    if ((threadIdx.x & 63u) == 0 && mine) atomicAdd(total, mine);
+}
+
+// One lane per sample g of `total` (offset = the exclusive scan of the counts, n_tris + 1 entries, the last one = total): its
+// triangle k is the one with offset[k] <= g < offset[k + 1] -- triangles without samples have an empty range and are never found --,
+// its sub-triangle the one numbered l = g - offset[k]: strip m = isqrt(l) holds i = n - 1 - m and 2 m + 1 sub-triangles, t = l - m^2
+// of them has kind = t & 1 and j = t >> 1.  Lanes of a wave hold ascending k, so a run of equal k is a contiguous stretch of lanes:
+// a segmented shuffle reduction leaves the run's sums in its first lane, which issues the atomics.
+__global__ __launch_bounds__(256) void k_cov_samples(const GridParams g, const Tables t, const CovParams p, const uint32_t* __restrict__ offset,
+                                                     const CovTri* __restrict__ geo, const uint32_t total, TriCoverage* __restrict__ cov)
+{
+    const uint64_t gg = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool live = gg < total;
+    uint32_t k = 0xFFFFFFFFu;  // a dead lane: a run of its own that adds nothing
+    uint32_t in_bbox = 0, covered = 0, dist_bits = 0;
+    long long sum_dist = 0;
+    if (live) {
+        const uint32_t s_idx = (uint32_t)gg;
+        uint32_t lo = 0, hi = p.n_tris;  // the first k with offset[k + 1] > s_idx (offset[n_tris] = total > s_idx)
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (offset[mid + 1] <= s_idx) lo = mid + 1;
+            else hi = mid;
+        }
+        k = lo;
+        const CovTri* tr = &geo[k];
+        const uint32_t n = tr->n, l = s_idx - offset[k];  // l < n^2 <= 4096
+        uint32_t m = (uint32_t)sqrtf((float)l);
+        m -= m * m > l ? 1u : 0u;
+        m += (m + 1u) * (m + 1u) <= l ? 1u : 0u;
+        const uint32_t tt = l - m * m, kind = tt & 1u, i = n - 1u - m, j = tt >> 1;
+        const double v = (double)(3u * i + 1u + kind) / (double)(3u * n), w = (double)(3u * j + 1u + kind) / (double)(3u * n);
+        F3 q;
+        q.x = (float)((tr->A[0] + v * tr->ab[0]) + w * tr->ac[0]);
+        q.y = (float)((tr->A[1] + v * tr->ab[1]) + w * tr->ac[1]);
+        q.z = (float)((tr->A[2] + v * tr->ab[2]) + w * tr->ac[2]);
+        if (__builtin_isfinite(q.x) && __builtin_isfinite(q.y) && __builtin_isfinite(q.z) && valid_point(g, q)) {  // USED, then IN_BBOX: k_query's tests
+            in_bbox = 1u;
+            int32_t vx[3];
+            voxel_coords(g, q, vx[0], vx[1], vx[2]);
+            const WindowNearest wn = window_nearest(g, t, q, vx, p.radius, p.min_count, p.max_d2);
+            if (wn.found) {
+                const double nx = t.nv_n[3 * (uint64_t)wn.nid], ny = t.nv_n[3 * (uint64_t)wn.nid + 1], nz = t.nv_n[3 * (uint64_t)wn.nid + 2];
+                const double c = (tr->N[0] * nx + tr->N[1] * ny) + tr->N[2] * nz, bound = p.min_dot * tr->s;
+                if (p.min_dot == -2.0 || c >= bound || (p.abs_normal && fabs(c) >= bound)) {
+                    const float d = (float)sqrt(wn.d2);
+                    covered = 1u;
+                    dist_bits = __float_as_uint(d);
+                    sum_dist = llrint((double)d * 0x1p30);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t k2 = __shfl_down(k, o);
+        const uint32_t b2 = __shfl_down(in_bbox, o), c2 = __shfl_down(covered, o), d2 = __shfl_down(dist_bits, o);
+        const long long s2 = __shfl_down(sum_dist, o);
+        if (lane + o < 64u && k2 == k) in_bbox += b2, covered += c2, dist_bits = max(dist_bits, d2), sum_dist += s2;
+    }
+    const uint32_t k_prev = __shfl_up(k, 1);
+    if (!live || (lane != 0 && k_prev == k)) return;  // not the first lane of a run
+    TriCoverage* c = &cov[k];
+    if (in_bbox) atomicAdd(&c->n_in_bbox, in_bbox);
+    if (covered) {
+        atomicAdd(&c->n_covered, covered);
+        atomicAdd((unsigned long long*)&c->sum_dist_q30, (unsigned long long)sum_dist);
+        atomicMax(&c->max_distance_bits, dist_bits);
+    }
+}
+
+// One thread per triangle: its share of the summary, reduced per wave, then u64 adds and a u32 max on the distance's bits.
+__global__ __launch_bounds__(256) void k_cov_finish(const uint32_t n_tris, const TriCoverage* __restrict__ cov, const CovTri* __restrict__ geo,
+                                                    CovSummary* __restrict__ sum)
+{
+    const uint64_t kk = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    unsigned long long w[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // the summary's 64-bit words in order
+    uint32_t bits = 0;
+    if (kk < n_tris) {
+        const TriCoverage c = cov[kk];
+        if (c.flags & kCovValid) {
+            w[0] = 1, w[3] = c.n_samples, w[4] = c.n_in_bbox, w[5] = c.n_covered, w[6] = (unsigned long long)c.sum_dist_q30;
+            bits = c.max_distance_bits;
+            if (c.flags & kCovHuge) {
+                w[2] = 1;
+            } else {
+                const double area_d = 0.5 * geo[kk].s;
+                const unsigned long long ta = (unsigned long long)rint(area_d * 0x1p40);
+                const unsigned long long tc = (unsigned long long)rint(((area_d * (double)c.n_covered) / (double)c.n_samples) * 0x1p40);
+                w[7] = ta & 0xFFFFFFFFull, w[8] = ta >> 32, w[9] = tc & 0xFFFFFFFFull, w[10] = tc >> 32;
+            }
+        } else {
+            w[1] = 1;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int i = 0; i < 11; i++) w[i] += __shfl_down(w[i], o);
+        bits = max(bits, __shfl_down(bits, o));
+    }
+    if ((threadIdx.x & 63u) != 0) return;
+    unsigned long long* out = &sum->n_tris_valid;
+#pragma unroll
+    for (int i = 0; i < 11; i++)
+        if (w[i]) atomicAdd(&out[i], w[i]);
+    if (bits) atomicMax(&sum->max_distance_bits, bits);
 }
 
 }  // namespace hfpf

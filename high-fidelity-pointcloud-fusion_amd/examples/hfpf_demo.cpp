@@ -2,12 +2,16 @@
 // synthetic sensor -> ~start -> N x PointCloud2 callbacks with tf poses -> periodic clean -> ~process ->
 // <dir>/test_cloud.pcd + <dir>/meta.csv.  Prints per-stage wall times.
 //
-//   hfpf_demo [--min-component N] [--reference mesh.ply [--max-deviation metres] [--align]] <out_dir> [frames=30] [W=640] [H=480] [resolution=0.001] [clean_every=10] [seed=0xF051] [pose_seed=0x5E3]
+//   hfpf_demo [--min-component N] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]]] <out_dir> [frames=30] [W=640] [H=480] [resolution=0.001] [clean_every=10] [seed=0xF051] [pose_seed=0x5E3]
 // --min-component N: ~process saves only the connected components (26-neighbourhood) of at least N rows (hfpf_node_set_component_filter).
 // --reference mesh.ply: ~process also writes deviation.csv and deviation_summary.csv, the saved cloud measured against that mesh
 //   (binary little-endian PLY in the fusion frame; hfpf_node_set_reference_mesh); --max-deviation is the largest distance looked for
 //   (default 10 voxels, at most 32).  --align: the mesh is first best-fitted to the model from that pose with the same distance as its
 //   capture range (hfpf_node_set_reference_alignment); the compare runs at the refined pose, which alignment.csv records.
+//   --coverage [spacing]: ~process also writes coverage.csv and coverage_summary.csv, how much of that mesh the model has rows near
+//   (hfpf_node_set_reference_coverage: samples `spacing` metres apart, one voxel by default, a window of 2 voxels, rows within 2
+//   voxels), and the demo prints the covered share of the mesh's area and of its samples.  A number behind --coverage is the spacing
+//   only when another argument follows it (the output directory).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -48,11 +52,21 @@ int main(int argc, char** argv)
     uint32_t min_component = 0;
     const char* reference = nullptr;
     double max_deviation = 0.0;
-    bool align = false;
+    bool align = false, coverage = false;
+    double spacing = 0.0;
     while (argc > 2 && strncmp(argv[1], "--", 2) == 0) {
         if (strcmp(argv[1], "--align") == 0) {
             align = true;
             argv += 1, argc -= 1;
+            continue;
+        }
+        if (strcmp(argv[1], "--coverage") == 0) {
+            coverage = true;
+            char* end = nullptr;
+            const double v = strtod(argv[2], &end);
+            const bool number = argc > 3 && end != argv[2] && *end == 0 && v > 0;
+            if (number) spacing = v;
+            argv += number ? 2 : 1, argc -= number ? 2 : 1;
             continue;
         }
         if (strcmp(argv[1], "--min-component") == 0) min_component = (uint32_t)strtoul(argv[2], nullptr, 0);
@@ -62,7 +76,7 @@ int main(int argc, char** argv)
         argv += 2, argc -= 2;
     }
     if (argc < 2 || strncmp(argv[1], "--", 2) == 0) {
-        fprintf(stderr, "usage: hfpf_demo [--min-component N] [--reference mesh.ply [--max-deviation metres] [--align]] <out_dir> [frames] [W] [H] [resolution] [clean_every] [seed] [pose_seed]\n");
+        fprintf(stderr, "usage: hfpf_demo [--min-component N] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]]] <out_dir> [frames] [W] [H] [resolution] [clean_every] [seed] [pose_seed]\n");
         return 2;
     }
     const std::string dir = argv[1];
@@ -132,6 +146,17 @@ int main(int argc, char** argv)
                 return 1;
             }
         }
+        if (coverage) {
+            hfpf_cover_opts vo;
+            memset(&vo, 0, sizeof vo);
+            vo.struct_size = sizeof vo;
+            vo.radius = 2, vo.max_subdivision = 64;
+            vo.max_distance = 2.0 * (double)res, vo.spacing = spacing > 0 ? spacing : (double)res, vo.min_normal_dot = -2.0;
+            if (hfpf_node_set_reference_coverage(node, &vo) != HFPF_OK) {
+                fprintf(stderr, "coverage: %s\n", hfpf_node_last_error(node));
+                return 1;
+            }
+        }
     }
     hfpf_trigger_response r;
     hfpf_node_start(node, &r);
@@ -166,6 +191,20 @@ int main(int argc, char** argv)
     hfpf_node_get_stats(node, &st);
     printf("%s\nframes %llu integrated %llu  callbacks %.3f s  cleans %.3f s (%llu passes)  process %.3f s\n", r.message,
            (unsigned long long)st.received, (unsigned long long)st.integrated, t_cb, t_clean, (unsigned long long)st.clean_passes, t_proc);
+    if (reference && coverage) {  // the value line of coverage_summary.csv
+        unsigned long long v[11] = {0};
+        FILE* f = fopen((dir + "/coverage_summary.csv").c_str(), "r");
+        const bool ok = f && fscanf(f, "%*[^\n]\n%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7],
+                                    &v[8], &v[9], &v[10]) == 11;
+        if (f) fclose(f);
+        if (!ok) {
+            fprintf(stderr, "coverage_summary.csv: cannot read it back\n");
+            return 1;
+        }
+        const double area = ((double)v[8] * 0x1p32 + (double)v[7]) * 0x1p-40, covered = ((double)v[10] * 0x1p32 + (double)v[9]) * 0x1p-40;
+        printf("coverage: %.6f of %.6f m^2 covered (%.1f %%), %llu of %llu samples (%.1f %%), %llu valid / %llu invalid / %llu huge triangles\n", covered, area,
+               area > 0 ? 100.0 * covered / area : 0.0, v[5], v[3], v[3] ? 100.0 * (double)v[5] / (double)v[3] : 0.0, v[0], v[1], v[2]);
+    }
     hfpf_node_destroy(node);
     return 0;
 }

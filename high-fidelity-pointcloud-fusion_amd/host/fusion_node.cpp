@@ -42,6 +42,8 @@ struct hfpf_node {
     double ref_pose[12] = {0};
     bool align_on = false;              // hfpf_node_set_reference_alignment: the reference mesh is best-fitted before it is compared
     hfpf_align_opts align_opts{};
+    bool cover_on = false;              // hfpf_node_set_reference_coverage: ~process also writes coverage.csv and coverage_summary.csv
+    hfpf_cover_opts cover_opts{};
     void* publish_user = nullptr;
     std::thread clean_thread;
     std::mutex cv_mtx;
@@ -224,13 +226,12 @@ int hfpf_node_reset(hfpf_node* n, hfpf_trigger_response* res)
 // component filter's min_count when one is set); the saved rows are a subsequence of it in the same lexicographic order, so one walk
 // selects their records, and the row part of the summary is rebuilt from the selected records as include/hfpf.h defines it.
 // With alignment on the reference mesh is first best-fitted from its stored pose; the compare then runs at the refined pose, which
-// alignment.csv records.
-static int write_deviation(hfpf_node* n, const hfpf_row* saved, uint64_t n_saved)
+// alignment.csv records.  pose: out, the pose the compare ran at.
+static int write_deviation(hfpf_node* n, const hfpf_row* saved, uint64_t n_saved, double pose[12])
 {
     hfpf_deviation_opts o = n->ref_opts;
     if (n->comp_on) o.min_count = n->comp_opts.min_count;
-    double pose[12];
-    memcpy(pose, n->ref_pose, sizeof pose);
+    memcpy(pose, n->ref_pose, 12 * sizeof(double));
     if (n->align_on) {
         hfpf_align_opts ao = n->align_opts;
         if (n->comp_on) ao.compare.min_count = n->comp_opts.min_count;
@@ -239,7 +240,7 @@ static int write_deviation(hfpf_node* n, const hfpf_row* saved, uint64_t n_saved
         ar.struct_size = sizeof ar;
         int arc = hfpf_align_mesh(n->grid, &ao, n->ref_verts.data(), n->ref_verts.size() / 3, 12, n->ref_tris.data(), n->ref_tris.size() / 3, n->ref_pose, &ar);
         if (arc != HFPF_OK) return arc;
-        memcpy(pose, ar.pose, sizeof pose);
+        memcpy(pose, ar.pose, 12 * sizeof(double));
         FILE* af = fopen((n->directory_name + "/alignment.csv").c_str(), "w");
         if (!af) return HFPF_ERR_IO;
         fprintf(af, "iterations,flags,rows_sampled,inliers,rms,p0,p1,p2,p3,p4,p5,p6,p7,p8,p9,p10,p11\n%u,%u,%llu,%llu,%.17g", ar.iterations, ar.flags,
@@ -303,6 +304,46 @@ static int write_deviation(hfpf_node* n, const hfpf_row* saved, uint64_t n_saved
     return rc;
 }
 
+// coverage.csv and coverage_summary.csv beside the cloud: hfpf_cover_mesh of the reference mesh at `pose`, the pose the deviation
+// files were written at; one line per triangle.  A component filter's min_count replaces the option's, as it does for the compare.
+static int write_coverage(hfpf_node* n, const double pose[12])
+{
+    hfpf_cover_opts o = n->cover_opts;
+    if (n->comp_on) o.min_count = n->comp_opts.min_count;
+    hfpf_tri_coverage* cov = nullptr;
+    hfpf_coverage_summary s;
+    const uint64_t n_tris = n->ref_tris.size() / 3;
+    int rc = hfpf_cover_mesh(n->grid, &o, n->ref_verts.data(), n->ref_verts.size() / 3, 12, n->ref_tris.data(), n_tris, pose, &cov, &s);
+    if (rc != HFPF_OK) return rc;
+    FILE* f = fopen((n->directory_name + "/coverage.csv").c_str(), "w");
+    if (!f) rc = HFPF_ERR_IO;
+    if (f) {
+        fprintf(f, "tri,n_samples,n_in_bbox,n_covered,flags,area,max_distance,sum_dist_q30\n");
+        for (uint64_t k = 0; k < n_tris; k++) {
+            const hfpf_tri_coverage& c = cov[k];
+            fprintf(f, "%llu,%u,%u,%u,%u,%.9g,%.9g,%lld\n", (unsigned long long)k, c.n_samples, c.n_in_bbox, c.n_covered, c.flags, c.area, c.max_distance,
+                    (long long)c.sum_dist_q30);
+        }
+        const bool ok = !ferror(f);
+        if (fclose(f) != 0 || !ok) rc = HFPF_ERR_IO;
+    }
+    if (rc == HFPF_OK) {
+        f = fopen((n->directory_name + "/coverage_summary.csv").c_str(), "w");
+        if (!f) rc = HFPF_ERR_IO;
+        else {
+            fprintf(f, "n_tris_valid,n_tris_invalid,n_tris_huge,n_samples,n_in_bbox,n_covered,sum_dist_q30,area_q40_lo,area_q40_hi,covered_q40_lo,"
+                       "covered_q40_hi,max_distance\n%llu,%llu,%llu,%llu,%llu,%llu,%lld,%llu,%llu,%llu,%llu,%.9g\n",
+                    (unsigned long long)s.n_tris_valid, (unsigned long long)s.n_tris_invalid, (unsigned long long)s.n_tris_huge, (unsigned long long)s.n_samples,
+                    (unsigned long long)s.n_in_bbox, (unsigned long long)s.n_covered, (long long)s.sum_dist_q30, (unsigned long long)s.area_q40_lo,
+                    (unsigned long long)s.area_q40_hi, (unsigned long long)s.covered_q40_lo, (unsigned long long)s.covered_q40_hi, s.max_distance);
+            const bool ok = !ferror(f);
+            if (fclose(f) != 0 || !ok) rc = HFPF_ERR_IO;
+        }
+    }
+    hfpf_free_coverage(cov);
+    return rc;
+}
+
 int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
 {
     if (!n) return HFPF_ERR_BAD_ARG;
@@ -328,7 +369,9 @@ int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
     if (rc == HFPF_OK) rc = hfpf_write_pcd(rows, nr, cloud_location.c_str());
     if (rc == HFPF_OK) rc = hfpf_write_meta_csv(rows, nr, meta_location.c_str());
     if (rc == HFPF_OK && n->publish) n->publish(n->publish_user, rows, nr, n->fusion_frame.c_str());  // processed_cloud_, node.cpp:158
-    if (rc == HFPF_OK && n->ref_on) rc = write_deviation(n, rows, nr);  // EXTENSION: the saved cloud measured against the reference mesh
+    double ref_pose[12];
+    if (rc == HFPF_OK && n->ref_on) rc = write_deviation(n, rows, nr, ref_pose);  // EXTENSION: the saved cloud measured against the reference mesh
+    if (rc == HFPF_OK && n->ref_on && n->cover_on) rc = write_coverage(n, ref_pose);  // EXTENSION: ... and how much of that mesh the model covers
     if (n->comp_on) hfpf_free_components(rows, labels, comps);
     else hfpf_free_rows(rows);
     if (rc == HFPF_OK && n->mesh_on) {  // EXTENSION: a triangle mesh of the same model next to the cloud
@@ -448,6 +491,17 @@ int hfpf_node_set_reference_alignment(hfpf_node* n, const hfpf_align_opts* opts)
         n->align_opts = *opts;
     }
     n->align_on = opts != nullptr;
+    return HFPF_OK;
+}
+
+int hfpf_node_set_reference_coverage(hfpf_node* n, const hfpf_cover_opts* opts)
+{
+    if (!n) return HFPF_ERR_BAD_ARG;
+    if (opts) {
+        if (hfpf_check_cover_opts(opts) != HFPF_OK) return nfail(n, HFPF_ERR_BAD_ARG, "hfpf_node_set_reference_coverage: invalid hfpf_cover_opts");
+        n->cover_opts = *opts;
+    }
+    n->cover_on = opts != nullptr;
     return HFPF_OK;
 }
 

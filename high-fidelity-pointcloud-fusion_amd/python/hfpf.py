@@ -95,6 +95,7 @@ EXPORTS = [
     "hfpf_check_component_opts", "hfpf_extract_components", "hfpf_extract_components_device", "hfpf_free_components",
     "hfpf_check_deviation_opts", "hfpf_compare_mesh", "hfpf_compare_mesh_device", "hfpf_free_deviation", "hfpf_read_ply",
     "hfpf_check_align_opts", "hfpf_align_mesh", "hfpf_align_mesh_device",
+    "hfpf_check_cover_opts", "hfpf_cover_mesh", "hfpf_cover_mesh_device", "hfpf_free_coverage",
     "hfpf_check_raycast_opts", "hfpf_raycast", "hfpf_raycast_device", "hfpf_raycast_view", "hfpf_raycast_view_device",
     "hfpf_snapshot", "hfpf_free_snapshot", "hfpf_restore", "hfpf_save", "hfpf_load", "hfpf_snapshot_info", "hfpf_config_from_snapshot",
 ]
@@ -373,6 +374,52 @@ def check_align_opts(o):
     return lib().hfpf_check_align_opts(C.byref(o) if o is not None else None)
 
 
+# hfpf_tri_coverage.flags, hfpf_cover_opts.flags and hfpf_tri_coverage (include/hfpf.h)
+COV_VALID, COV_CAPPED, COV_HUGE = 1, 2, 4
+COVER_ABS_NORMAL = 1
+TRI_COVERAGE_DTYPE = np.dtype([("n_samples", "<u4"), ("n_in_bbox", "<u4"), ("n_covered", "<u4"), ("flags", "<u4"), ("area", "<f4"),
+                               ("max_distance", "<f4"), ("sum_dist_q30", "<i8")])
+assert TRI_COVERAGE_DTYPE.itemsize == 32
+
+
+class CoverOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("radius", C.c_int32), ("max_subdivision", C.c_uint32),
+                ("min_count", C.c_double), ("max_distance", C.c_double), ("spacing", C.c_double), ("min_normal_dot", C.c_double),
+                ("reserved", C.c_uint64)]
+
+
+class CoverageSummary(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_tris_valid", "n_tris_invalid", "n_tris_huge", "n_samples", "n_in_bbox", "n_covered")] + [
+        ("sum_dist_q30", C.c_int64), ("area_q40_lo", C.c_uint64), ("area_q40_hi", C.c_uint64), ("covered_q40_lo", C.c_uint64),
+        ("covered_q40_hi", C.c_uint64), ("max_distance", C.c_float), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        """The fields, and the two areas in m^2 the q40 words stand for: area and covered_area."""
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["area"] = ((d["area_q40_hi"] << 32) + d["area_q40_lo"]) / 2.0 ** 40
+        d["covered_area"] = ((d["covered_q40_hi"] << 32) + d["covered_q40_lo"]) / 2.0 ** 40
+        return d
+
+
+assert C.sizeof(CoverOpts) == 56 and C.sizeof(CoverageSummary) == 96
+
+
+def cover_opts(radius=2, min_count=0.0, max_distance=0.01, spacing=0.005, max_subdivision=64, min_normal_dot=-2.0, abs_normal=False):
+    """An hfpf_cover_opts: the sample test's voxel window, count gate and largest distance (metres), the sample spacing (metres) and
+    its cap, and the normal gate (-2 = off; abs_normal passes either orientation)."""
+    o = CoverOpts()
+    o.struct_size = C.sizeof(CoverOpts)
+    o.flags = COVER_ABS_NORMAL if abs_normal else 0
+    o.radius, o.max_subdivision = int(radius), int(max_subdivision)
+    o.min_count, o.max_distance, o.spacing, o.min_normal_dot = float(min_count), float(max_distance), float(spacing), float(min_normal_dot)
+    return o
+
+
+def check_cover_opts(o):
+    """hfpf_check_cover_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
+    return lib().hfpf_check_cover_opts(C.byref(o) if o is not None else None)
+
+
 def read_ply(path):
     """hfpf_read_ply: (vertices of MESH_VERTEX_DTYPE, (n, 3) uint32 triangles) of a binary little-endian PLY (host code, no GPU
     needed); HfpfError with the reader's message otherwise."""
@@ -613,6 +660,11 @@ def lib():
     L.hfpf_check_align_opts.argtypes = [C.POINTER(AlignOpts)]
     for fn in (L.hfpf_align_mesh, L.hfpf_align_mesh_device):
         fn.argtypes = [vp, C.POINTER(AlignOpts), vp, u64, u32, vp, u64, vp, C.POINTER(AlignResult)]
+    L.hfpf_check_cover_opts.argtypes = [C.POINTER(CoverOpts)]
+    for fn in (L.hfpf_cover_mesh, L.hfpf_cover_mesh_device):
+        fn.argtypes = [vp, C.POINTER(CoverOpts), vp, u64, u32, vp, u64, vp, C.POINTER(vp), C.POINTER(CoverageSummary)]
+    L.hfpf_free_coverage.argtypes = [vp]
+    L.hfpf_free_coverage.restype = None
     L.hfpf_free_deviation.argtypes = [vp, vp]
     L.hfpf_free_deviation.restype = None
     L.hfpf_read_ply.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64)]
@@ -1052,6 +1104,36 @@ class OccupancyGrid:
         self._chk(lib().hfpf_align_mesh(self._h, C.byref(o), _p(verts) if verts.nbytes else None, nv, stride, _p(tris) if tris.nbytes else None, nt,
                                         _p(pose), C.byref(r)))
         return _refine_out(r, "rows_sampled")
+
+    # -- coverage of a triangle mesh by the model --
+    def cover_mesh(self, verts, tris, pose=None, device=False, opts=None, n_verts=None, vertex_stride=None, n_tris=None, **kw):
+        """Which parts of a triangle mesh the model has rows near (hfpf_cover_mesh): (records of TRI_COVERAGE_DTYPE, one per triangle;
+        summary dict with the derived floats area and covered_area in m^2).  verts, tris, pose and the device form's arguments as
+        compare_mesh(); keywords as cover_opts().  device=True runs hfpf_cover_mesh_device and returns (records pointer, summary);
+        free the pointer with device_free (it is 0 without triangles)."""
+        o = opts if opts is not None else cover_opts(**kw)
+        pose = np.ascontiguousarray(np.eye(4)[:3] if pose is None else pose, np.float64).reshape(12)
+        c, s = C.c_void_p(), CoverageSummary()
+        if device:
+            self._chk(lib().hfpf_cover_mesh_device(self._h, C.byref(o), C.c_void_p(verts), int(n_verts), int(vertex_stride), C.c_void_p(tris),
+                                                   int(n_tris), _p(pose), C.byref(c), C.byref(s)))
+            return c.value or 0, s.as_dict()
+        verts = np.ascontiguousarray(verts)
+        if verts.dtype != MESH_VERTEX_DTYPE:
+            verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+        stride = int(vertex_stride) if vertex_stride is not None else verts.dtype.itemsize * (1 if verts.dtype == MESH_VERTEX_DTYPE else 3)
+        nv = int(n_verts) if n_verts is not None else len(verts)
+        nt = int(n_tris) if n_tris is not None else len(tris)
+        self._chk(lib().hfpf_cover_mesh(self._h, C.byref(o), _p(verts) if verts.nbytes else None, nv, stride, _p(tris) if tris.nbytes else None, nt,
+                                        _p(pose), C.byref(c), C.byref(s)))
+        try:
+            cov = np.empty(nt if c.value else 0, TRI_COVERAGE_DTYPE)
+            if cov.nbytes:
+                C.memmove(cov.ctypes.data, c.value, cov.nbytes)
+        finally:
+            lib().hfpf_free_coverage(c)
+        return cov, s.as_dict()
 
     # -- casting rays against the model --
     def raycast(self, rays, pose, opts=None, **kw):

@@ -914,6 +914,120 @@ int hfpf_align_mesh(hfpf_handle* h, const hfpf_align_opts* o, const void* verts,
 int hfpf_align_mesh_device(hfpf_handle* h, const hfpf_align_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride,
                            const uint32_t* dev_tris, uint64_t n_tris, const double* pose_3x4, hfpf_align_result* result);
 
+/* ---- coverage of a triangle mesh by the fused model (no reference counterpart) --------------------------------------------------
+ * hfpf_compare_mesh asks how far every scanned row is from the reference surface; a cover asks the other half of an inspection:
+ * which parts of the reference surface have been scanned at all.  Every triangle is cut into sub-triangles no longer than
+ * `spacing`, the centroid of each is one sample, and a sample is covered when the model has a row near it (and, with the normal
+ * gate, one that faces the way the triangle does).  Everything is restatable from hfpf_extract's rows and hfpf_get_occupied's list
+ * (tests/cover_ref.py).
+ * Arithmetic: everything below is f64, one rounding per operation, left to right, never contracted, dot() as in the deviation
+ *   section.
+ * Mesh, pose, valid triangles: word for word those of the section "deviation of the fused model from a triangle mesh": verts,
+ *   n_verts, vertex_stride, tris, n_tris, pose_3x4 from the mesh frame to the fusion frame; V kept in f64; triangle k is VALID iff
+ *   its three indices are < n_verts, its nine transformed coordinates are finite and NN = dot(N, N) is finite and > 0.  The device
+ *   rejects an index out of range before it loads anything through it.  Invalid triangles are skipped and counted; their record is
+ *   all zero.
+ * Subdivision: per valid triangle with ab = B - A, ac = C - A, bc = C - B:
+ *   L2 = max(dot(ab,ab), max(dot(ac,ac), dot(bc,bc))); q = sqrt(L2) / spacing;
+ *   n = 1 when !(q > 1); n = max_subdivision when q >= max_subdivision, and HFPF_COV_CAPPED is set iff q > max_subdivision (the
+ *   samples are then coarser than asked); otherwise n = (uint32)ceil(q).
+ *   The triangle is cut into its n^2 congruent sub-triangles (i, j, kind): kind 0 is upright, for 0 <= i, 0 <= j, i + j <= n - 1;
+ *   kind 1 is inverted, for i + j <= n - 2.  Each contributes its centroid as one sample, which stands for area / n^2:
+ *     v = (double)(3i + 1 + kind) / (double)(3n); w = (double)(3j + 1 + kind) / (double)(3n);
+ *     S[a] = (A[a] + v*ab[a]) + w*ac[a]; p[a] = (float)S[a].
+ *   Nothing below depends on the order of the samples.
+ * Sample test: the sample's hit is the hfpf_query hit of the f32 point p under the identity pose with the call's radius, min_count
+ *   and max_distance and without the z-clip (exactly how a mesh corner sample and a raycast sample are defined).  IN_BBOX is that
+ *   hit's HFPF_QHIT_IN_BBOX.  With c = (N.x*nx + N.y*ny) + N.z*nz (nx, ny, nz the found row's f32 normal widened, N the triangle's)
+ *   and s = sqrt(NN), the sample is COVERED iff the hit is HFPF_QHIT_FOUND and
+ *     min_normal_dot == -2 (the gate is off), or c >= min_normal_dot * s, or HFPF_COVER_ABS_NORMAL is set and
+ *     fabs(c) >= min_normal_dot * s.
+ *   The gate inherits the rows' orientation, as the mesh, the raycast and the components do: a row's normal points to the side its
+ *   points were seen from, so a reference mesh wound the other way needs HFPF_COVER_ABS_NORMAL (or the gate off).  A covered sample
+ *   contributes distance = the hit's f32 distance.
+ * Per triangle (hfpf_tri_coverage): n_samples = n^2; n_in_bbox, n_covered; flags; area = (float)area_d with area_d = 0.5 * s;
+ *   max_distance = the largest covered sample's distance (0 without one; a max on the float's bits); sum_dist_q30 = the sum over
+ *   covered samples of rint((double)distance * 2^30).
+ * Summary: integer and max reductions only.  Per valid triangle ta = (uint64)rint(area_d * 2^40) and
+ *   tc = (uint64)rint(((area_d * (double)n_covered) / (double)n_samples) * 2^40).  A triangle with !(area_d < 2^23) is HUGE
+ *   (HFPF_COV_HUGE): it is sampled and recorded like any other, but adds nothing to the four area words.  Otherwise area_q40_lo adds
+ *   ta & 0xFFFFFFFF, area_q40_hi adds ta >> 32, and covered_q40_lo / covered_q40_hi the same of tc; n_tris < 2^32 - 1 keeps every word
+ *   below 2^64.  The area in m^2 is (hi * 2^32 + lo) / 2^40.  max_distance <= 1 keeps sum_dist_q30 below 2^62 for the 2^32 - 2
+ *   samples allowed.
+ * A call changes nothing on the handle except device_bytes (its scratch); host frames still waiting are launched first.  Rejected
+ * with HFPF_ERR_BAD_ARG (the handle stays usable, nothing is written): what hfpf_check_cover_opts rejects (struct_size != sizeof,
+ * flags beyond HFPF_COVER_ABS_NORMAL, reserved != 0, radius outside 1..4, max_subdivision outside 1..64, min_count NaN, max_distance
+ * not finite, not > 0 or > 1, spacing not finite or not > 0, min_normal_dot not finite or outside [-2, 1]); every check
+ * hfpf_compare_mesh makes on the mesh and the pose; a NULL cov or summary; for the device form verts or tris not 4-byte aligned.
+ * n_tris = 0 returns HFPF_OK with *cov = NULL and a zero summary; an empty handle, or one before its first clean pass, returns
+ * HFPF_OK with every valid triangle recorded and n_covered = 0.  More than 2^32 - 2 samples in total return HFPF_ERR_CAPACITY, the
+ * message names the count, and the handle stays usable.  A handle with an RCCL communicator, or a failed handle, returns
+ * HFPF_ERR_STATE as the other readers do. */
+#define HFPF_COV_VALID 1u  /* hfpf_tri_coverage.flags: the triangle is valid (an invalid one has an all-zero record) */
+#define HFPF_COV_CAPPED 2u /* q > max_subdivision: the samples are coarser than spacing */
+#define HFPF_COV_HUGE 4u   /* !(area_d < 2^23): not part of the summary's area words */
+
+#define HFPF_COVER_ABS_NORMAL 1u /* hfpf_cover_opts.flags: the normal gate also passes fabs(c) >= min_normal_dot * s */
+
+typedef struct hfpf_cover_opts {
+    uint32_t struct_size;        /* = sizeof(hfpf_cover_opts) */
+    uint32_t flags;              /* HFPF_COVER_ABS_NORMAL or 0 */
+    int32_t radius;              /* 1..4: the voxel window of the sample test */
+    uint32_t max_subdivision;    /* 1..64: the largest n */
+    double min_count;            /* rows with count < max(1, min_count) are no candidates */
+    double max_distance;         /* metres, > 0 and <= 1: a row farther from a sample does not cover it */
+    double spacing;              /* metres, > 0: the sub-triangles' longest edge is at most this (unless CAPPED) */
+    double min_normal_dot;       /* -2 = gate off, else in (-2, 1]: the cosine between the triangle's and the row's normal */
+    uint64_t reserved;           /* 0 */
+} hfpf_cover_opts;
+
+typedef struct hfpf_tri_coverage { /* 32 bytes, one per triangle */
+    uint32_t n_samples;          /* n^2 */
+    uint32_t n_in_bbox;          /* samples inside the bounding box */
+    uint32_t n_covered;          /* samples covered */
+    uint32_t flags;              /* HFPF_COV_* */
+    float area;                  /* (float)(0.5 * sqrt(NN)), m^2 */
+    float max_distance;          /* the largest covered sample's distance, 0 without one */
+    int64_t sum_dist_q30;
+} hfpf_tri_coverage;
+
+typedef struct hfpf_coverage_summary { /* 96 bytes */
+    uint64_t n_tris_valid;
+    uint64_t n_tris_invalid;
+    uint64_t n_tris_huge;
+    uint64_t n_samples;
+    uint64_t n_in_bbox;
+    uint64_t n_covered;
+    int64_t sum_dist_q30;
+    uint64_t area_q40_lo, area_q40_hi;       /* the mesh's area: (hi * 2^32 + lo) / 2^40 m^2 */
+    uint64_t covered_q40_lo, covered_q40_hi; /* the covered share of it, the same way */
+    float max_distance;          /* the largest covered sample's distance, 0 without one */
+    uint32_t pad;                /* 0 */
+} hfpf_coverage_summary;
+
+#ifdef __cplusplus
+static_assert(sizeof(hfpf_cover_opts) == 56, "hfpf_cover_opts is 56 bytes");
+static_assert(sizeof(hfpf_tri_coverage) == 32, "hfpf_tri_coverage is 32 bytes");
+static_assert(sizeof(hfpf_coverage_summary) == 96, "hfpf_coverage_summary is 96 bytes");
+#else
+_Static_assert(sizeof(hfpf_cover_opts) == 56, "hfpf_cover_opts is 56 bytes");
+_Static_assert(sizeof(hfpf_tri_coverage) == 32, "hfpf_tri_coverage is 32 bytes");
+_Static_assert(sizeof(hfpf_coverage_summary) == 96, "hfpf_coverage_summary is 96 bytes");
+#endif
+
+/* HFPF_OK if o passes the checks above, else HFPF_ERR_BAD_ARG (host code, no handle; the node shell uses it too). */
+int hfpf_check_cover_opts(const hfpf_cover_opts* o);
+/* Mesh, pose and outputs in HOST memory (the mesh is uploaded once per call, as hfpf_compare_mesh uploads it): *cov holds n_tris
+ * records and is freed by hfpf_free_coverage. */
+int hfpf_cover_mesh(hfpf_handle* h, const hfpf_cover_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris,
+                    uint64_t n_tris, const double* pose_3x4, hfpf_tri_coverage** cov, hfpf_coverage_summary* summary);
+void hfpf_free_coverage(hfpf_tri_coverage* cov);
+/* The mesh is read in place from DEVICE memory (HBM); *dev_cov is a device array of n_tris records, freed by hfpf_device_free(h, p).
+ * pose_3x4 and summary are in host memory. */
+int hfpf_cover_mesh_device(hfpf_handle* h, const hfpf_cover_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride,
+                           const uint32_t* dev_tris, uint64_t n_tris, const double* pose_3x4, hfpf_tri_coverage** dev_cov,
+                           hfpf_coverage_summary* summary);
+
 /* <directory_name>/test_cloud.pcd (node.cpp:395): PCD v0.7 ASCII, FIELDS x y z rgb normal_x normal_y normal_z curvature */
 int hfpf_write_pcd(const hfpf_row* rows, uint64_t n_rows, const char* path);
 /* <directory_name>/meta.csv (node.cpp:396) with the header string of grid.hpp:462 */
@@ -952,7 +1066,7 @@ int hfpf_get_occupied(hfpf_handle* h, int32_t* xyz, uint64_t cap, uint64_t* n_ou
  * WHAT A RESTORE IS.  hfpf_clear followed by putting that state in place.  Afterwards the handle is indistinguishable from the
  * source handle at the moment of the snapshot, in this sense:
  *   1. every read-only call (extract, extract_filtered, get_occupied, is_dirty, render*, query*, extract_mesh*, raycast*, track*,
- *      extract_components*, compare_mesh*, align_mesh*)
+ *      extract_components*, compare_mesh*, align_mesh*, cover_mesh*)
  *      returns byte-identical output;
  *   2. any continuation (integrate*, clean, extract, clear, automatic frame ids included) produces byte-identical rows and occupied
  *      lists to the same continuation on the source handle;

@@ -122,6 +122,16 @@ int hfpf_node_set_reference_mesh(hfpf_node* n, const hfpf_deviation_opts* opts, 
  * leave the setting as it was. */
 int hfpf_node_set_reference_alignment(hfpf_node* n, const hfpf_align_opts* opts);
 
+/* EXTENSION: which parts of the reference mesh were scanned.  With coverage options set and a reference mesh set, ~process also runs
+ * hfpf_cover_mesh of include/hfpf.h on that mesh, at the pose the deviation files are written at (the refined pose when alignment is
+ * on; with a component filter set, opts->min_count is replaced by the filter's, as the compare's is), and writes coverage.csv (header
+ * tri,n_samples,n_in_bbox,n_covered,flags,area,max_distance,sum_dist_q30, then one line per triangle of the mesh, floats as %.9g) and
+ * coverage_summary.csv (one header line, one value line: n_tris_valid, n_tris_invalid, n_tris_huge, n_samples, n_in_bbox, n_covered,
+ * sum_dist_q30, area_q40_lo, area_q40_hi, covered_q40_lo, covered_q40_hi, max_distance).  Without a reference mesh the setting has no
+ * effect.  NULL turns it off again, the default: neither file is then written.  Invalid options (hfpf_check_cover_opts) are refused
+ * with HFPF_ERR_BAD_ARG and leave the setting as it was. */
+int hfpf_node_set_reference_coverage(hfpf_node* n, const hfpf_cover_opts* opts);
+
 /* EXTENSION: keep the grid's session in a file and take it up again (hfpf_save / hfpf_load of include/hfpf.h on the node's grid, with
  * their errors).  Both run under the grid's own lock, so they are legal while the cloud callback and the clean thread run: a frame
  * or a clean pass lands wholly before or wholly after them.  Loading replaces the fused data only: the node stays started or stopped
