@@ -206,6 +206,8 @@ struct Knobs {
     bool stream_replay = true;       // HFPF_STREAM_REPLAY=0: every replay walks the chains
     float bin_slack = 2.0f;          // planned capacity of a bin region = the brick's demand in the previous launch x this (HFPF_BIN_SLACK)
     bool clean_small_nowait = true;  // small clean passes run without a mid-pass read-back (HFPF_CLEAN_NOWAIT=0 restores it)
+    bool clean_overlap = true;       // HFPF_CLEAN_OVERLAP=0: k_buffer stays behind the update kernel and a clean pass runs on the engine's stream alone
+    bool trace_clean = false;        // HFPF_TRACE_CLEAN=1: one stderr line per clean pass that launches kernels: which stream its front half took
     float test_bin_scale = 1.f;      // tests only (HFPF_TEST_BIN_SCALE): shrinks the planned bin regions so that they overflow into the direct forms
     bool test_table_skip = false;    // tests only (HFPF_TEST_TABLE_SKIP=1): Tables::test_table_skip
     bool mailbox = true;             // HFPF_MAILBOX=0: counter read-backs by blit copies + synchronize
@@ -238,6 +240,13 @@ struct Session {
     // source session's totals
     unsigned long long upd_miss_seen = 0, upd_member_seen = 0;
     unsigned long long pub_seq = 0;         // sequence number of a publish enqueued behind the last integrate call and still current (0: none).  snapshot: not carried; 0 makes the next read-back publish for itself
+    // ... and of that call's EARLY publish (second mailbox slot): the counters between k_buffer and the update kernel, with ev_ready
+    // recorded behind it; alive only while pub_seq is (0: none).  What lets a clean pass start beside the update kernel (clean_locked).
+    // snapshot: not carried; 0 is the plain path
+    unsigned long long early_seq = 0;
+    // A clean pass that began from the early publish leaves the call's final one unread: pick_update_shape takes the update kernel's
+    // words from it (window_from_final) unless a full read-back came first.  snapshot: not carried (0: nothing to take)
+    unsigned long long win_seq = 0;
     // Host frames uploaded, not yet launched: slots [pend_first, pend_first + pend_n); everything but pend_n is dead while pend_n == 0.
     // snapshot: not carried (hfpf_snapshot launches them first)
     uint32_t pend_n = 0, pend_first = 0;
@@ -300,7 +309,11 @@ struct hfpf_handle {
     uint64_t device_bytes = 0;
     unsigned long long* h_ctr = nullptr;      // pinned mirror of the counters
     unsigned long long* h_log_ctr = nullptr;  // pinned mirror of the region counters
-    unsigned long long* mbox = nullptr;       // coherent pinned mailbox k_publish_counters writes (null with HFPF_MAILBOX=0)
+    unsigned long long* mbox = nullptr;       // coherent pinned mailbox k_publish_counters writes (null with HFPF_MAILBOX=0): two slots of kMboxSlotWords
+    // The front half of a clean pass (sentinels, gate, candidate sort, k_normal, k_register) runs here beside the update kernel of
+    // the integrate call before it: it waits for ev_ready, the engine's stream waits for ev_front behind k_register (clean_locked)
+    hipStream_t front_stream = nullptr;
+    hipEvent_t ev_ready = nullptr, ev_front = nullptr;
     std::vector<DevBuf*> bufs;  // every DevBuf below, in declaration order (DevBuf's constructor): what hfpf_destroy frees
     DevBuf pend_a{bufs}, pend_b{bufs};  // the gate's pending-cell lists (Session::pend_valid)
     StageSlot stage[kStageSlots];
@@ -352,8 +365,8 @@ struct hfpf_handle {
     // ---- kernel timing ----
     bool timing = false;
     bool timing_detail = false;  // hfpf_kernel_timing(h, 2): also one event pair per kernel of an integrate call (ids 2..4)
-    std::vector<hipEvent_t> ev_detail;  // 4 events per call: before k_integrate, after it, after k_update*, after k_buffer
-    std::vector<uint8_t> ev_detail_ran;  // per call: bit k = the kernel between events k and k + 1 was launched
+    std::vector<hipEvent_t> ev_detail;  // 4 events per call: before k_integrate, after it, after k_update*, after k_buffer (or: after k_buffer, after k_update*)
+    std::vector<uint8_t> ev_detail_ran;  // per call: bit k = kernel id 2 + k was launched; bit 3 = k_buffer ran ahead of the update kernel
     // One pair per: integrate launch (id 0), clean pass (1), k_raycast / k_raycast_view launch (5), hfpf_extract_components* call (6),
     // hfpf_compare_mesh* call (7)
     TimedId timed[kTimedIds];
@@ -458,6 +471,7 @@ __global__ void k_set_ctr3(unsigned long long* ctr, int i0, unsigned long long v
 // arrival of the number equivalent to a synchronize for everything enqueued before it.
 constexpr int kMboxLogWords = 5;  // words 0..4 of each 16-word region-counter line are in use
 constexpr int kMboxWords = C_COUNT + kLogRegions * kMboxLogWords;  // + the sequence number in its own 64-byte line
+constexpr int kMboxSlotWords = (kMboxWords + 8 + 7) & ~7;  // a slot, whole 64-byte lines; slot 0: every read-back and the publish at the end of an integrate call, slot 1: the early publish
 __global__ __launch_bounds__(256) void k_publish_counters(const unsigned long long* __restrict__ ctr, const unsigned long long* __restrict__ log_ctr,
                                                           unsigned long long* mbox, unsigned long long seq)
 {
@@ -469,32 +483,44 @@ __global__ __launch_bounds__(256) void k_publish_counters(const unsigned long lo
     if (i == 0) __hip_atomic_store(&mbox[kMboxWords + 7], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-int read_counters(hfpf_handle* h)
+// The host's side of a publish: spins until `seq` has arrived in the slot at `box`.
+int await_mailbox(hfpf_handle* h, const unsigned long long* box, unsigned long long seq)
+{
+    const unsigned long long* flag = box + kMboxWords + 7;
+    for (uint64_t spins = 1;; spins++) {
+        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) break;
+        __builtin_ia32_pause();
+        if ((spins & 0xFFFF) == 0) {  // every ~1 ms: a failed stream would never publish
+            const hipError_t q = hipStreamQuery(h->stream);
+            if (q != hipSuccess && q != hipErrorNotReady) HIPCHK(h, q);
+            if (q == hipSuccess && __atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq)
+                return fail(h, HFPF_ERR_HIP, "counter mailbox: the stream drained without publishing sequence %llu", seq);
+        }
+    }
+    return HFPF_OK;
+}
+
+// early: the read-back at the head of a clean pass takes the EARLY publish of the pending integrate call (Session::early_seq;
+// the caller has checked that there is one) and leaves the final one to pick_update_shape.
+int read_counters(hfpf_handle* h, bool early = false)
 {
     if (h->mbox) {
         // An integrate call ends with a publish of its own (nothing has touched the counters since): the snapshot is already on
         // its way, so the host only waits -- no launch of its own behind a stream that has just drained.
-        unsigned long long seq = h->ss.pub_seq;
+        unsigned long long seq = early ? h->ss.early_seq : h->ss.pub_seq;
+        const unsigned long long* box = h->mbox + (early ? kMboxSlotWords : 0);
+        h->ss.win_seq = early ? h->ss.pub_seq : 0;
         h->ss.pub_seq = 0;
+        h->ss.early_seq = 0;
         if (seq == 0) {
             seq = ++h->mbox_seq;
             k_publish_counters<<<1, 256, 0, h->stream>>>(h->t.ctr, h->t.log_ctr, h->mbox, seq);
             HIPCHK(h, hipGetLastError());
         }
-        volatile unsigned long long* flag = h->mbox + kMboxWords + 7;
-        for (uint64_t spins = 1;; spins++) {
-            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) break;
-            __builtin_ia32_pause();
-            if ((spins & 0xFFFF) == 0) {  // every ~1 ms: a failed stream would never publish
-                const hipError_t q = hipStreamQuery(h->stream);
-                if (q != hipSuccess && q != hipErrorNotReady) HIPCHK(h, q);
-                if (q == hipSuccess && __atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq)
-                    return fail(h, HFPF_ERR_HIP, "counter mailbox: the stream drained without publishing sequence %llu", seq);
-            }
-        }
-        memcpy(h->h_ctr, h->mbox, C_COUNT * sizeof(unsigned long long));
+        if (int rc = await_mailbox(h, box, seq)) return rc;
+        memcpy(h->h_ctr, box, C_COUNT * sizeof(unsigned long long));
         for (int r = 0; r < kLogRegions; r++)
-            for (int w = 0; w < kMboxLogWords; w++) h->h_log_ctr[r * 16 + w] = h->mbox[C_COUNT + r * kMboxLogWords + w];
+            for (int w = 0; w < kMboxLogWords; w++) h->h_log_ctr[r * 16 + w] = box[C_COUNT + r * kMboxLogWords + w];
     } else {
         HIPCHK(h, hipMemcpyAsync(h->h_ctr, h->t.ctr, C_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->h_log_ctr, h->t.log_ctr, kLogRegions * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
@@ -560,6 +586,8 @@ Knobs read_knobs()
     if (const char* sr = getenv("HFPF_STREAM_REPLAY")) k.stream_replay = sr[0] != '0';
     if (const char* bs = getenv("HFPF_BIN_SLACK")) k.bin_slack = std::max(1.0f, std::min(4.0f, (float)atof(bs)));
     if (const char* nw = getenv("HFPF_CLEAN_NOWAIT")) k.clean_small_nowait = nw[0] != '0';
+    if (const char* co = getenv("HFPF_CLEAN_OVERLAP")) k.clean_overlap = co[0] != '0';
+    if (const char* tc = getenv("HFPF_TRACE_CLEAN")) k.trace_clean = tc[0] != '0';
     if (const char* bs = getenv("HFPF_TEST_BIN_SCALE")) k.test_bin_scale = std::max(0.f, std::min(1.f, (float)atof(bs)));
     const char* ts = getenv("HFPF_TEST_TABLE_SKIP");
     k.test_table_skip = ts && ts[0] == '1';
@@ -666,6 +694,8 @@ int reset_state(hfpf_handle* h, uint64_t bricks_used = ~0ull, uint64_t normals_u
     const uint64_t nb = std::min<uint64_t>(bricks_used, t.max_bricks);                     // ids 1..nb (+ the unused id 0)
     const uint64_t nsl = std::min<uint64_t>(h->n_slots, (nb + 1) * (uint64_t)kBrickCells);  // their cells
     const uint64_t nn = std::min<uint64_t>(normals_used, t.max_normals);
+    // (a clean pass that failed on the host half-way through its front half has not joined front_stream to the engine's stream)
+    if (h->front_stream) HIPCHK(h, hipStreamSynchronize(h->front_stream));
     HIPCHK(h, hipMemsetAsync(t.dir, 0, h->dir_entries * 4, s));
     HIPCHK(h, hipMemsetAsync(t.info, 0, nsl * 8, s));
     HIPCHK(h, hipMemsetAsync(t.first_frame, 0xFF, nsl * 4, s));
@@ -784,10 +814,13 @@ int with_sort_tmp(hfpf_handle* h, Fn&& fn)
 
 // Cell keys: only the low GridParams::key_bits bits are significant (an all-ones sentinel still sorts behind every valid key:
 // a valid cell has x < dim <= 2^bits_x - 1, so its key is never all ones).
-int sort_keys_u64(hfpf_handle* h, uint64_t* in, uint64_t* out, uint64_t n, unsigned bits = 0)
+// on: the stream the sort runs on (default: the engine's).  sort_tmp is the handle's one buffer: whoever sorts elsewhere sees to it
+// that the engine's stream runs no sort, scan or unique meanwhile (clean_locked).
+int sort_keys_u64(hfpf_handle* h, uint64_t* in, uint64_t* out, uint64_t n, unsigned bits = 0, hipStream_t on = nullptr)
 {
     const unsigned kb = bits ? bits : h->g.key_bits;
-    return with_sort_tmp(h, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_keys<sort_config>(tmp, bytes, in, out, (size_t)n, 0, kb, h->stream); });
+    const hipStream_t st = on ? on : h->stream;
+    return with_sort_tmp(h, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_keys<sort_config>(tmp, bytes, in, out, (size_t)n, 0, kb, st); });
 }
 
 int sort_keys_u32(hfpf_handle* h, uint32_t* in, uint32_t* out, uint64_t n, unsigned bits = 32)
@@ -865,6 +898,29 @@ int acquire_stage(hfpf_handle* h, uint32_t n_frames, StageSlot** out)
 // members belong in the denominator too: a caller that reads the counters between a clean pass and the next integrate call
 // (hfpf_get_counters, hfpf_get_kernel_time) makes a window that holds the replay alone -- a few hundred misses against no update
 // member at all, which used to switch the session to the wide shape (bench.py's per-kernel pass did exactly that).
+// The last clean pass began from the early publish of the integrate call before it (Session::win_seq): the words the update kernel
+// of that call wrote -- the table misses and the member pairs -- are taken from the call's final publish here, so that the window
+// below covers what it covered when the pass read that publish itself.  Nothing else of the final publish is used: it ran beside
+// the front half of the pass, which moves other counters.  By now the update kernel has usually long finished; the engine's
+// stream holds the back half of the pass and this call's k_integrate meanwhile.
+int window_from_final(hfpf_handle* h)
+{
+    const unsigned long long seq = h->ss.win_seq;
+    h->ss.win_seq = 0;
+    if (!seq || !h->mbox) return HFPF_OK;
+    if (int rc = await_mailbox(h, h->mbox, seq)) return rc;
+    unsigned long long member = h->mbox[C_DEP_MEMBER], tested = h->mbox[C_DEP_TESTED];
+    for (int r = 0; r < kLogRegions; r++) {
+        tested += h->mbox[C_COUNT + r * kMboxLogWords + 2];
+        member += h->mbox[C_COUNT + r * kMboxLogWords + 3];
+    }
+    h->h_ctr[C_DEP_TESTED] = tested;
+    h->h_ctr[C_DEP_MEMBER] = member;
+    h->h_ctr[C_TABLE_MISS] = h->mbox[C_TABLE_MISS];
+    h->h_ctr[C_UPD_ROUNDS] = h->mbox[C_UPD_ROUNDS];
+    return HFPF_OK;
+}
+
 int pick_update_shape(hfpf_handle* h, double points, uint32_t nb)
 {
     (void)points;
@@ -1021,6 +1077,7 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
     if (!dl && (rc = check_cloud_layout(h, "integrate", lay, true))) return rc;
     if (n_frames > 65535) return fail(h, HFPF_ERR_BAD_ARG, "integrate: at most 65535 frames per call");
     h->ss.pub_seq = 0;  // kernels are about to be enqueued: a counter snapshot already on its way is no longer the latest
+    h->ss.early_seq = 0;
     StageSlot* s = nullptr;
     if ((rc = acquire_stage(h, n_frames, &s))) return rc;
     memcpy(s->h_pose, poses, (size_t)n_frames * 12 * sizeof(double));
@@ -1147,6 +1204,7 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
         }
     } detail_guard{h, h->ev_detail.size()};
     uint8_t detail_ran = 1;  // k_integrate (+ its overflow kernel) always runs
+    unsigned long long early_seq = 0;
     auto detail_mark = [&]() -> hipError_t {  // per-kernel boundaries of this call (detail timing only)
         if (!h->timing_detail) return hipSuccess;
         hipEvent_t e = nullptr;
@@ -1165,9 +1223,29 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
         }
         HIPCHK(h, detail_mark());
         if (have_plan) {
-            if (h->h_ctr[C_NORMALS] > 0 || h->ss.normals_possible) {  // without a normal record no cell has dependants
+            const bool update = h->h_ctr[C_NORMALS] > 0 || h->ss.normals_possible;  // without a normal record no cell has dependants
+            // k_buffer ahead of the update kernel (both only read the bins, and they write disjoint tables): everything a clean
+            // pass reads at its head is then final while the update kernel -- the longer of the two by far -- still runs, and an
+            // early publish + ev_ready let the pass begin beside it (clean_locked).  Only where that can happen: a batch on a
+            // single rank with the mailbox; otherwise the order of old.
+            const bool buffer_first = update && h->knobs.clean_overlap && h->mbox && n_frames >= 4 && !h->dist_on;
+            auto launch_buffer = [&]() {
+                detail_ran |= 4;
+                with_color(color, [&](auto C) { hipLaunchKernelGGL(k_buffer<C>, dim3(nb), dim3(256), 0, h->stream, h->g, h->t, nb); });
+            };
+            if (buffer_first) {
+                detail_ran |= 8;  // events 1..2 bracket k_buffer and 2..3 the update kernel (resolve_timing)
+                launch_buffer();
+                early_seq = ++h->mbox_seq;
+                k_publish_counters<<<1, 256, 0, h->stream>>>(h->t.ctr, h->t.log_ctr, h->mbox + kMboxSlotWords, early_seq);
+                HIPCHK(h, hipGetLastError());
+                HIPCHK(h, hipEventRecord(h->ev_ready, h->stream));
+                HIPCHK(h, detail_mark());
+            }
+            if (update) {
                 detail_ran |= 2;
                 if (h->knobs.update_cells) {
+                    if ((rc = window_from_final(h))) return rc;
                     const int shape = pick_update_shape(h, (double)n_points * n_frames, nb);
                     launch_update_cells<false>(color, shape == 1, h->stream, h->g, h->t, nb);
                 } else {
@@ -1175,9 +1253,10 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
                 }
             }
             HIPCHK(h, detail_mark());
-            detail_ran |= 4;
-            with_color(color, [&](auto C) { hipLaunchKernelGGL(k_buffer<C>, dim3(nb), dim3(256), 0, h->stream, h->g, h->t, nb); });
-            HIPCHK(h, detail_mark());
+            if (!buffer_first) {
+                launch_buffer();
+                HIPCHK(h, detail_mark());
+            }
         } else {
             HIPCHK(h, detail_mark());
             HIPCHK(h, detail_mark());
@@ -1194,9 +1273,11 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
     h->ss.dirty = true;  // state_changed = true, grid.hpp:189
     h->frames_integrated += n_frames;
     if (h->mbox && n_frames >= 4) {  // a batch: the next call is probably a clean pass, which starts by reading the counters
+        if ((rc = window_from_final(h))) return rc;  // (a final publish nobody has read yet is about to be overwritten)
         h->ss.pub_seq = ++h->mbox_seq;
         k_publish_counters<<<1, 256, 0, h->stream>>>(h->t.ctr, h->t.log_ctr, h->mbox, h->ss.pub_seq);
         HIPCHK(h, hipGetLastError());
+        h->ss.early_seq = early_seq;
     } else {
         h->ss.pub_seq = 0;
     }
@@ -1223,8 +1304,9 @@ int resolve_timing(hfpf_handle* h)
     for (size_t c = 0; 4 * c + 3 < h->ev_detail.size() && c < h->ev_detail_ran.size(); c++) {
         for (int k = 0; k < 3; k++) {
             if (!(h->ev_detail_ran[c] & (1u << k))) continue;  // not launched in this call (e.g. no dependants yet: no k_update_cells)
+            const int at = (k && (h->ev_detail_ran[c] & 8u)) ? 3 - k : k;  // k_buffer ran ahead of the update kernel: their brackets change places
             float ms = 0.f;
-            HIPCHK(h, hipEventElapsedTime(&ms, h->ev_detail[4 * c + k], h->ev_detail[4 * c + k + 1]));
+            HIPCHK(h, hipEventElapsedTime(&ms, h->ev_detail[4 * c + at], h->ev_detail[4 * c + at + 1]));
             h->timed[kTimeDetail + k].ms += (double)ms;
             h->timed[kTimeDetail + k].n++;
         }
@@ -1426,18 +1508,32 @@ int dist_exchange_locked(hfpf_handle* h, int pre_rc)
 
 // k_gate with four tiles per workgroup only when the input is large enough to fill the chip that way (one reservation per
 // list and workgroup; small inputs keep one tile so that the latency-heavy stencil probes spread over as many CUs as possible).
-void launch_gate(hfpf_handle* h, const uint32_t* cells_a, uint64_t n_a, const uint32_t* cells_b, uint64_t n_b, uint32_t* pend_out)
+void launch_gate(hfpf_handle* h, hipStream_t s, const uint32_t* cells_a, uint64_t n_a, const uint32_t* cells_b, uint64_t n_b, uint32_t* pend_out)
 {
     const uint64_t n = n_a + n_b;
     if (n >= (1ull << 20))
-        hipLaunchKernelGGL(k_gate<4>, dim3(blocks_for(n, 256 * 4)), dim3(256), 0, h->stream, h->g, h->t, cells_a, n_a, cells_b, n_b, pend_out);
+        hipLaunchKernelGGL(k_gate<4>, dim3(blocks_for(n, 256 * 4)), dim3(256), 0, s, h->g, h->t, cells_a, n_a, cells_b, n_b, pend_out);
     else
-        hipLaunchKernelGGL(k_gate<1>, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->g, h->t, cells_a, n_a, cells_b, n_b, pend_out);
+        hipLaunchKernelGGL(k_gate<1>, dim3(blocks_for(n, 256)), dim3(256), 0, s, h->g, h->t, cells_a, n_a, cells_b, n_b, pend_out);
 }
 
 // One clean pass.  Two host read-backs: at the start (what the integrate launches since the last pass produced) and after the
 // dependant-table update (how many cells to replay, overflow bits).  Everything between them is sized from upper bounds on the
 // host and reads its exact counts from the device counters.
+//
+// The front half -- sentinels, gate, candidate sort, k_normal, k_register: a chain of small launches over a few ten thousand
+// candidates -- reads nothing the update kernel of the integrate call before it writes (the statistic sums and its pair counters),
+// and writes nothing that kernel reads for the cells it is written for (cand_key, the pending lists, the records of NEW ids and
+// their lines, stat_id, bit 1 of an info word and the nd_mask bit of a candidate, pre_dep of UNOCCUPIED cells, reg_occ, dep_tmp,
+// touched_list, directory entries of bricks beyond the call's; the update reads the list bits of info words, pre_dep of occupied
+// cells, dep[] and the lines of older records).  So when that call is still pending and left an early publish (integrate_device_locked), the pass takes its
+// head-of-pass counters from it and runs the front half on front_stream beside the update kernel: front_stream waits for
+// ev_ready, the engine's stream for ev_front, and the back half -- the filing of pre-dependants (it rewrites info words the
+// update reads: k_clean_file), the dependant-table update, the replays -- follows on the engine's stream as ever.  Scratch: pend_b,
+// keys_a and sort_tmp are the front half's alone until ev_front; the engine's stream holds only the update kernel and a publish.
+// The early publish cannot show an error bit the update kernel raises: like the errors of a no-wait pass it surfaces at the next
+// read-back and poisons the handle there.  Everything else -- no call pending, a read-back since (hfpf_sync, hfpf_get_counters),
+// a distributed session, the un-binned forms, a compacting pass, HFPF_CLEAN_OVERLAP=0 -- is the plain sequence on one stream.
 int clean_locked(hfpf_handle* h, int pre_rc)
 {
     Tables& t = h->t;
@@ -1446,7 +1542,8 @@ int clean_locked(hfpf_handle* h, int pre_rc)
     // collective: every rank cleans at the same schedule point; a rank that is already unusable (pre_rc) still says so to its peers
     if (h->dist_on && (rc = dist_exchange_locked(h, pre_rc))) return rc;
     if (pre_rc) return pre_rc;
-    if ((rc = read_counters(h))) return rc;
+    const bool early = h->knobs.clean_overlap && !h->dist_on && h->binned && h->mbox && h->ss.pub_seq && h->ss.early_seq;
+    if ((rc = read_counters(h, early))) return rc;
     if ((rc = check_device_errors(h))) return rc;
     const uint64_t n_occ = std::min<uint64_t>(h->h_ctr[C_OCC], t.max_occ);
     const uint64_t n_normals = h->h_ctr[C_NORMALS];
@@ -1492,9 +1589,20 @@ int clean_locked(hfpf_handle* h, int pre_rc)
     // one entry per cell occupied since the last pass (the pre-dependants filed at the head of the pass).
     const uint64_t live_ub = std::min<uint64_t>(h->h_ctr[C_REG], t.max_reg) + std::min<uint64_t>(h->h_ctr[C_PREREG], t.max_reg);
     bool full = h->h_ctr[C_DEP] + 2 * live_ub + 2 * reg_ub + n_new_occ > t.max_dep;
-    // sentinels + the pass's list counters + the pre-dependants of the cells occupied since the last pass become their lists
-    hipLaunchKernelGGL(k_clean_begin, dim3(blocks_for(n_in, 256)), dim3(256), 0, s, t, n_in, (const uint32_t*)(t.occ_list + h->ss.gate_done), n_new_occ, full ? 1u : 0u);
-    launch_gate(h, (const uint32_t*)h->pend_a.p, n_pend, (const uint32_t*)(t.occ_list + h->ss.gate_done), n_new_occ, (uint32_t*)h->pend_b.p);
+    const bool overlap = early && !full;
+    const uint32_t* new_cells = (const uint32_t*)(t.occ_list + h->ss.gate_done);
+    if (h->knobs.trace_clean)
+        fprintf(stderr, "hfpf: clean pass %llu: %llu candidates, front half %s\n", (unsigned long long)h->clean_passes, (unsigned long long)n_in,
+                overlap ? "beside the update kernel" : "on the engine's stream");
+    if (overlap) {  // the front half beside the update kernel; `s` is the engine's stream again behind k_register
+        s = h->front_stream;
+        HIPCHK(h, hipStreamWaitEvent(s, h->ev_ready, 0));
+        hipLaunchKernelGGL(k_clean_front, dim3(blocks_for(n_in, 256)), dim3(256), 0, s, t, n_in);
+    } else {
+        // sentinels + the pass's list counters + the pre-dependants of the cells occupied since the last pass become their lists
+        hipLaunchKernelGGL(k_clean_begin, dim3(blocks_for(n_in, 256)), dim3(256), 0, s, t, n_in, new_cells, n_new_occ, full ? 1u : 0u);
+    }
+    launch_gate(h, s, (const uint32_t*)h->pend_a.p, n_pend, new_cells, n_new_occ, (uint32_t*)h->pend_b.p);
     HIPCHK(h, hipGetLastError());
     h->ss.gate_done = n_occ;
     h->ss.normals_possible = true;
@@ -1504,7 +1612,7 @@ int clean_locked(hfpf_handle* h, int pre_rc)
     // canonical order: ascending (x,y,z) key; record id = n_normals + rank + 1
     // (with HFPF_MORTON_IDS the candidate keys are Z-order codes: three interleaved axes of the widest axis' bits)
     const unsigned cand_bits = HFPF_MORTON_IDS ? 3u * std::max(h->g.key_sy, std::max(h->g.key_sx - h->g.key_sy, h->g.key_bits - h->g.key_sx)) : h->g.key_bits;
-    if ((rc = sort_keys_u64(h, t.cand_key, (uint64_t*)h->keys_a.p, n_in, cand_bits))) return rc;
+    if ((rc = sort_keys_u64(h, t.cand_key, (uint64_t*)h->keys_a.p, n_in, cand_bits, s))) return rc;
     hipLaunchKernelGGL(k_normal, dim3(blocks_for(n_in, 128)), dim3(128), 0, s, h->g, t, (const uint64_t*)h->keys_a.p, kCountOnDevice, n_normals);
     const bool reg_small = n_in < (1ull << 18);  // tiles per workgroup: kernels.hpp k_register
     const uint64_t reg_tile = 256ull * (reg_small ? kRegTilesSmall : kRegTilesLarge);  // step-major, whole workgroups per step
@@ -1513,6 +1621,12 @@ int clean_locked(hfpf_handle* h, int pre_rc)
     if (reg_small) hipLaunchKernelGGL(k_register<kRegTilesSmall>, dim3((unsigned)std::max<uint64_t>(reg_blocks, 1)), dim3(256), 0, s, h->g, t, kCountOnDevice, n_normals, count_deps);
     else hipLaunchKernelGGL(k_register<kRegTilesLarge>, dim3((unsigned)std::max<uint64_t>(reg_blocks, 1)), dim3(256), 0, s, h->g, t, kCountOnDevice, n_normals, count_deps);
     HIPCHK(h, hipGetLastError());
+    if (overlap) {
+        HIPCHK(h, hipEventRecord(h->ev_front, s));
+        s = h->stream;
+        HIPCHK(h, hipStreamWaitEvent(s, h->ev_front, 0));
+        if (n_new_occ) hipLaunchKernelGGL(k_clean_file, dim3(blocks_for(n_new_occ, 256)), dim3(256), 0, s, t, new_cells, n_new_occ);
+    }
     uint64_t n_reg = 0, n_pre = 0, inc_touched = 0;
     // registrations already present in dep[]: every pass files all of its own, so that is the counter as this pass found it
     const uint64_t reg_first = std::min<uint64_t>(h->h_ctr[C_REG], t.max_reg);
@@ -1653,6 +1767,9 @@ int hfpf_create(const hfpf_config* cfg, hfpf_handle** out)
         if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
         for (hipStream_t cs : h->copy_more)
             if (cs) (void)hipStreamDestroy(cs);
+        if (h->ev_ready) (void)hipEventDestroy(h->ev_ready);
+        if (h->ev_front) (void)hipEventDestroy(h->ev_front);
+        if (h->front_stream) (void)hipStreamDestroy(h->front_stream);
         if (h->stream) (void)hipStreamDestroy(h->stream);
         delete h;
         return rc;
@@ -1668,6 +1785,9 @@ int hfpf_create(const hfpf_config* cfg, hfpf_handle** out)
     if ((e = hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking)) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)));
     for (int k = 0; k + 1 < h->knobs.copy_streams; k++)
         if ((e = hipStreamCreateWithFlags(&h->copy_more[k], hipStreamNonBlocking)) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)));
+    if ((e = hipStreamCreateWithFlags(&h->front_stream, hipStreamNonBlocking)) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)));
+    if ((e = hipEventCreateWithFlags(&h->ev_ready, hipEventDisableTiming)) != hipSuccess || (e = hipEventCreateWithFlags(&h->ev_front, hipEventDisableTiming)) != hipSuccess)
+        return bail(fail(h, HFPF_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e)));
     if ((e = hipHostMalloc((void**)&h->h_ctr, C_COUNT * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess)
         return bail(fail(h, HFPF_ERR_HIP, "hipHostMalloc: %s", hipGetErrorString(e)));
     memset(h->h_ctr, 0, C_COUNT * sizeof(unsigned long long));
@@ -1675,9 +1795,9 @@ int hfpf_create(const hfpf_config* cfg, hfpf_handle** out)
         return bail(fail(h, HFPF_ERR_HIP, "hipHostMalloc: %s", hipGetErrorString(e)));
     memset(h->h_log_ctr, 0, kLogRegions * 16 * sizeof(unsigned long long));
     if (h->knobs.mailbox) {
-        if ((e = hipHostMalloc((void**)&h->mbox, (kMboxWords + 8) * sizeof(unsigned long long), hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess)
+        if ((e = hipHostMalloc((void**)&h->mbox, 2 * kMboxSlotWords * sizeof(unsigned long long), hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess)
             return bail(fail(h, HFPF_ERR_HIP, "hipHostMalloc (mailbox): %s", hipGetErrorString(e)));
-        memset(h->mbox, 0, (kMboxWords + 8) * sizeof(unsigned long long));
+        memset(h->mbox, 0, 2 * kMboxSlotWords * sizeof(unsigned long long));
     }
     {
         int per_cu = 0, cus = 0;
@@ -1721,6 +1841,7 @@ int hfpf_destroy(hfpf_handle* h)
     if (!h) return HFPF_OK;
     (void)hipSetDevice(h->cfg.device);
     (void)hipStreamSynchronize(h->stream);
+    if (h->front_stream) (void)hipStreamSynchronize(h->front_stream);
     for (void* p : h->allocs) (void)hipFree(p);
     for (DevBuf* b : h->bufs)
         if (b->p) (void)hipFree(b->p);
@@ -1763,6 +1884,9 @@ int hfpf_destroy(hfpf_handle* h)
     if (h->h_ctr) (void)hipHostFree(h->h_ctr);
     if (h->h_log_ctr) (void)hipHostFree(h->h_log_ctr);
     if (h->mbox) (void)hipHostFree(h->mbox);
+    if (h->ev_ready) (void)hipEventDestroy(h->ev_ready);
+    if (h->ev_front) (void)hipEventDestroy(h->ev_front);
+    if (h->front_stream) (void)hipStreamDestroy(h->front_stream);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return HFPF_OK;

@@ -1517,16 +1517,18 @@ __device__ __forceinline__ uint64_t cand_count(const Tables& t, uint64_t base)
     const uint64_t room = t.max_normals > base ? t.max_normals - base : 0;
     return n < room ? n : room;
 }
-// Head of a clean pass, one launch: all-ones sentinels behind the candidate keys the gate is about to write (they sort to the
-// end), the pass's list counters back to zero, and (k_materialize_new in the comments: this part) the cells occupied since the
+// Head of a clean pass: all-ones sentinels behind the candidate keys the gate is about to write (they sort to the end), the pass's
+// list counters back to zero, and (k_materialize_new in the comments: this part, clean_file) the cells occupied since the
 // previous pass -- the new tail of occ_list, imported ones included -- that carry a pre-dependant get it filed as their list: entry,
 // info word, flag bit, and a place in prereg_list (what a compacting rebuild re-creates the entry from); one reservation per list
 // and workgroup.  lists_only: a compacting rebuild follows in this pass and writes every entry and info word itself.  No room in
 // dep[] is E_DEP, which the host answers by compacting.  n_in >= n_new (the gate's input contains the new cells).
-__global__ __launch_bounds__(256) void k_clean_begin(const Tables t, const uint64_t n_in, const uint32_t* __restrict__ new_cells, const uint64_t n_new,
-                                                     const uint32_t lists_only)
+// One launch (k_clean_begin) when the pass runs alone.  A pass whose front half runs beside the update kernel of the integrate call
+// before it (hfpf.hip clean_locked) takes the two parts apart: k_clean_front with the front half, k_clean_file at the head of the
+// back half -- the update reads the info word and pre_dep of exactly the cells the filing rewrites, and nothing between the two
+// launches (k_gate, the sort, k_normal, k_register) reads a filed entry, the list bits of an info word or the flag.
+__device__ __forceinline__ void clean_front(const Tables& t, const uint64_t i, const uint64_t n_in)
 {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_in) t.cand_key[i] = ~0ull;
     if (i == 0) {
         t.ctr[C_CAND] = 0;
@@ -1534,6 +1536,9 @@ __global__ __launch_bounds__(256) void k_clean_begin(const Tables t, const uint6
         t.ctr[C_TOUCHED] = 0;
     }
     if (i < (uint64_t)kLogRegions) t.log_ctr[i * 16 + 4] = 0;  // touched cells in single-run bricks (k_depinc_offsets)
+}
+__device__ __forceinline__ void clean_file(const Tables& t, const uint64_t i, const uint32_t* __restrict__ new_cells, const uint64_t n_new, const uint32_t lists_only)
+{
     if ((uint64_t)blockIdx.x * blockDim.x >= n_new) return;  // block-uniform
     uint32_t slot = 0, nid = 0;
     if (i < n_new) {
@@ -1554,6 +1559,21 @@ __global__ __launch_bounds__(256) void k_clean_begin(const Tables t, const uint6
     }
     t.dep[off] = make_dep_entry(t, nid);
     t.info[slot] = (t.info[slot] & 3ull) | (1ull << kDepCntShift) | ((uint64_t)off << kDepOffShift);
+}
+__global__ __launch_bounds__(256) void k_clean_begin(const Tables t, const uint64_t n_in, const uint32_t* __restrict__ new_cells, const uint64_t n_new,
+                                                     const uint32_t lists_only)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    clean_front(t, i, n_in);
+    clean_file(t, i, new_cells, n_new, lists_only);
+}
+__global__ __launch_bounds__(256) void k_clean_front(const Tables t, const uint64_t n_in)
+{
+    clean_front(t, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, n_in);
+}
+__global__ __launch_bounds__(256) void k_clean_file(const Tables t, const uint32_t* __restrict__ new_cells, const uint64_t n_new)
+{
+    clean_file(t, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, new_cells, n_new, 0u);
 }
 
 // K4: one thread per candidate, in ascending order of the sorted keys (Z-order codes with HFPF_MORTON_IDS); record id = base + rank + 1.

@@ -230,7 +230,10 @@ int hfpf_is_dirty(hfpf_handle* h);
  * waiting for it; a pool that overflows inside such a pass (HFPF_ERR_CAPACITY: normal records, registrations, dependant table)
  * is returned by the next call that reads the counters back (this one included, on its next invocation), and the handle then
  * refuses work until hfpf_clear.  Integrate calls enqueued in between run on the tables as the failed pass left them; their
- * results are discarded with the handle's state at hfpf_clear.  HFPF_CLEAN_NOWAIT=0 makes every pass wait and report itself. */
+ * results are discarded with the handle's state at hfpf_clear.  HFPF_CLEAN_NOWAIT=0 makes every pass wait and report itself.
+ * A pass that directly follows an integrate call of four or more frames starts from counters published before that call's
+ * update kernel has finished (its front half runs beside it; HFPF_CLEAN_OVERLAP=0 switches that off): an error that kernel
+ * raises is deferred in the same way. */
 int hfpf_clean(hfpf_handle* h);
 
 /* OccupancyGrid::downloadData (grid.hpp:456-488; call site node.cpp:398) split in two: the ordered
