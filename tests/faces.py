@@ -1,0 +1,273 @@
+"""Scenes whose model is cut by all six faces of the grid, and the boundary inputs of the read-outs (imported by tests only).
+
+The synthetic surface (plane z = 0.56 + 0.05 x, sphere r = 0.10 at (0.05, 0, 0.45), a box) sits in the middle of scenes.BBOX_1M,
+more than 100 voxels from every face.  The boxes here are cut out of it, so that rows lie in every face layer (index 0 and dim - 1),
+occupied cells lie at index == dim (the storage has dim + 1 cells an axis; such a cell never has a row), every window of a read-out
+is clipped somewhere, and a triangle or a ray near the model leaves the grid."""
+import numpy as np
+
+import scenes
+
+CUT_BBOX = (-0.105, 0.1035, -0.0715, 0.0735, 0.38, 0.5575)
+THIN_BBOX = (-0.105, 0.1035, -0.0715, 0.0735, 0.5530, 0.5595)
+FAR_SHIFT = (3.2, -1.7, 2.0)
+# name -> (bbox, resolution, shift of the fusion frame, dims)
+DEFS = {"cut": (CUT_BBOX, 0.002, (0.0, 0.0, 0.0), (104, 72, 88)),
+        "cut3": (CUT_BBOX, 0.003, (0.0, 0.0, 0.0), (69, 48, 59)),
+        "thin": (THIN_BBOX, 0.001, (0.0, 0.0, 0.0), (208, 144, 6)),
+        "far": (CUT_BBOX, 0.002, FAR_SHIFT, (104, 72, 88))}
+NAMES = tuple(DEFS)
+SIX = ("cut", "cut3", "far")   # the scenes every face of which cuts a surface
+# what the CPU oracle alone gives (asserted exactly in test_faces_ref.py only): rows, live rows, live rows in the layers
+# x=0, x=dim-1, y=0, y=dim-1, z=0, z=dim-1, occupied cells at index == dim per axis
+ORACLE_TABLE = {"cut": (10087, 9872, (140, 45, 132, 114, 291, 260), (42, 216, 1358)),
+                "cut3": (5185, 4812, (66, 22, 76, 78, 174, 388), (36, 143, 582)),
+                "thin": (5230, 5230, (0, 0, 33, 8, 0, 272), (0, 66, 97)),
+                "far": (10087, 9897, (140, 45, 132, 112, 290, 255), (42, 216, 1358))}
+CAPS = dict(max_bricks=60000, max_log_points=4 << 20, max_normals=1 << 20, max_frames=4096)
+IDENT = np.hstack([np.eye(3), np.zeros((3, 1))])
+
+
+class FaceScene(scenes.Scene):
+    """scenes.Scene(8, 320, 240, res, bbox, clean_every=4) with the default seeds.  Every frame is rendered from the scene's own
+    pose; it is integrated with the same rotation and the translation moved by `shift`, into the box moved by the same amount: the
+    same surface, fused elsewhere (the z-clip acts in the camera frame and does not notice)."""
+
+    def __init__(self, name):
+        bbox, res, shift, dims = DEFS[name]
+        moved = tuple(float(b) + float(shift[i // 2]) for i, b in enumerate(bbox))
+        super().__init__(8, 320, 240, res, bbox=moved, clean_every=4)
+        self.name, self.dims, self.shift = name, dims, np.asarray(shift, np.float64)
+        self.render_poses = self.poses
+        self.poses = [np.hstack([p[:, :3], p[:, 3:] + self.shift.reshape(3, 1)]) for p in self.render_poses]
+
+    def frame(self, f):
+        import hfpf_synth as S
+        return S.frame(self.seed, f, self.W, self.H, self.render_poses[f], noise_sigma=self.noise, nan_permille=self.nan_permille,
+                       fx=self.fx, layout=self.layout)
+
+
+def face_counts(rows, occ, dims):
+    """(rows, live rows, live rows in the six face layers, occupied cells at index == dim per axis)."""
+    live = rows[rows["count"] > 0]
+    layers = []
+    for a, k in enumerate(("ix", "iy", "iz")):
+        layers += [int((live[k] == 0).sum()), int((live[k] == dims[a] - 1).sum())]
+    occ = np.asarray(occ).reshape(-1, 3)
+    return len(rows), len(live), tuple(layers), tuple(int((occ[:, a] == dims[a]).sum()) for a in range(3))
+
+
+def check_conditions(name, rows, occ, dims):
+    """The conditions a session must meet before it is used: without them its tests would pass without touching a face."""
+    assert tuple(dims) == DEFS[name][3], "%s: dims %r" % (name, dims)
+    n, n_live, layers, at_dim = face_counts(rows, occ, dims)
+    print("%s: %d rows / %d live; face layers %r; occupied at index == dim %r" % (name, n, n_live, layers, at_dim))
+    for k in ("ix", "iy", "iz"):
+        assert (rows[k] >= 0).all(), "a row with a negative index"
+    for a, k in enumerate(("ix", "iy", "iz")):
+        assert (rows[k] < dims[a]).all(), "a row at index >= dim was emitted"
+    if name in SIX:
+        assert min(layers) >= 20, "%s: a face layer holds fewer than 20 live rows: %r" % (name, layers)
+        assert min(at_dim) >= 1, "%s: an axis without an occupied cell at index == dim: %r" % (name, at_dim)
+    else:
+        assert dims[2] < 8 and layers[2] > 0 and layers[3] > 0 and layers[5] > 0, "%s: %r %r" % (name, dims, layers)
+    return layers, at_dim
+
+
+def in_face_layer(vox, dims):
+    """Per (n, 3) voxel: whether it lies in one of the six face layers."""
+    v = np.asarray(vox, np.int64).reshape(-1, 3)
+    d = np.asarray(dims, np.int64)
+    return ((v == 0) | (v == d - 1)).any(axis=1)
+
+
+def lo_hi(bbox):
+    b = np.asarray(bbox, np.float64)
+    return b[0::2], b[1::2]
+
+
+def centroids(rows):
+    return np.stack([rows["x"], rows["y"], rows["z"]], axis=1)
+
+
+# ---- a. query points ----------------------------------------------------------------------------------------------------
+
+def lattice_values(bbox, res, dims, axis):
+    """(float)(min + i * res) for i in {0, 1, dim-1, dim, dim+1} and the f32 neighbours on both sides of each: 15 f32 values that
+    land on cell boundaries and on the two faces of `axis`."""
+    lo = float(bbox[2 * axis])
+    d = int(dims[axis])
+    c = np.array([lo + i * float(res) for i in (0, 1, d - 1, d, d + 1)], np.float64).astype(np.float32)
+    return np.concatenate([np.nextafter(c, np.float32(-np.inf)), c, np.nextafter(c, np.float32(np.inf))])
+
+
+def query_points(rows, bbox, res, dims, seed=0xFACE, per_face=5000, per_value=400):
+    """About 60,000 f32 points (identity pose): every live row's centroid jittered by N(0, one voxel); per face a sheet of random
+    points within +-5 voxels of it, on both sides; the lattice values of every axis crossed with random positions on the others."""
+    rng = np.random.default_rng(seed)
+    lo, hi = lo_hi(bbox)
+    res = float(res)
+    live = rows[rows["count"] > 0]
+    out = [(centroids(live).astype(np.float64) + rng.normal(0.0, res, (len(live), 3))).astype(np.float32)]
+    for axis in range(3):
+        for face in (lo[axis], hi[axis]):
+            p = rng.uniform(lo - 5 * res, hi + 5 * res, (per_face, 3))
+            p[:, axis] = face + rng.uniform(-5 * res, 5 * res, per_face)
+            out.append(p.astype(np.float32))
+    for axis in range(3):
+        vals = lattice_values(bbox, res, dims, axis)
+        p = rng.uniform(lo - 2 * res, hi + 2 * res, (len(vals) * per_value, 3)).astype(np.float32)
+        p[:, axis] = np.repeat(vals, per_value)
+        out.append(p)
+    return np.ascontiguousarray(np.vstack(out))
+
+
+# ---- c. rays ------------------------------------------------------------------------------------------------------------
+
+def ray_t_max(bbox, res, step=0.5, max_samples=400):
+    """A march long enough to cross the whole box from 0.05 m outside it, cut to ~max_samples samples."""
+    lo, hi = lo_hi(bbox)
+    return float(min(np.linalg.norm(hi - lo) + 0.06, max_samples * step * float(res)))
+
+
+def ray_sets(bbox, res, seed=0xFACE + 1):
+    """[(label, (n, 6) f32 rays {o, d})], about 3000 rays in all (identity pose): from 0.05 m outside each face at points inside;
+    axis-parallel (two rates exactly 0) through random points; in each face's plane and one f32 step inside and outside it; from
+    inside the box outwards; past the box altogether, some parallel to a face 1 mm outside it."""
+    rng = np.random.default_rng(seed)
+    lo, hi = lo_hi(bbox)
+    span = hi - lo
+    sets = []
+
+    def inside(n):
+        return rng.uniform(lo, hi, (n, 3))
+
+    def add(label, parts):
+        sets.append((label, np.ascontiguousarray(np.vstack(parts).astype(np.float32))))
+
+    out = []
+    for axis in range(3):                                  # 6 x 150 from outside a face, aimed at points inside
+        for side, face in ((-1.0, lo[axis]), (1.0, hi[axis])):
+            o = rng.uniform(lo - 0.02, hi + 0.02, (150, 3))
+            o[:, axis] = face + side * 0.05
+            out.append(np.hstack([o, inside(150) - o]))
+    add("from outside a face", out)
+    out = []
+    for axis in range(3):                                  # 6 x 100 axis-parallel, entering through a face
+        for sign in (1.0, -1.0):
+            o = inside(100)
+            o[:, axis] = (lo[axis] - 0.01) if sign > 0 else (hi[axis] + 0.01)
+            d = np.zeros((100, 3))
+            d[:, axis] = sign
+            out.append(np.hstack([o, d]))
+    add("axis-parallel", out)
+    out = []
+    for axis in range(3):                                  # 6 faces x 3 planes x 30 rays lying in the plane
+        for face in (lo[axis], hi[axis]):
+            f = np.float32(face)
+            for plane in (np.nextafter(f, np.float32(-np.inf)), f, np.nextafter(f, np.float32(np.inf))):
+                o = rng.uniform(lo - 0.01, hi + 0.01, (30, 3))
+                o[:, axis] = float(plane)
+                d = inside(30) - o
+                d[:, axis] = 0.0
+                out.append(np.hstack([o, d]))
+    add("in a face's plane", out)
+    o = inside(500)                                        # from inside, leaving the box
+    add("from inside", [np.hstack([o, rng.normal(size=(500, 3))])])
+    c = (lo + hi) / 2                                      # 300 that miss the box: pointing away from outside it
+    d = rng.normal(size=(300, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    out = [np.hstack([c + d * (span * 0.6 + 0.02), d + rng.normal(0, 0.2, d.shape)])]
+    for axis in range(3):                                  # 6 x 30 parallel to a face, 1 mm outside it
+        for side, face in ((-1.0, lo[axis]), (1.0, hi[axis])):
+            o = rng.uniform(lo - 0.01, hi + 0.01, (30, 3))
+            o[:, axis] = face + side * 0.001
+            d = inside(30) - o
+            d[:, axis] = 0.0
+            out.append(np.hstack([o, d]))
+    add("past the box", out)
+    return sets
+
+
+def rays(bbox, res, seed=0xFACE + 1):
+    return np.ascontiguousarray(np.vstack([r for _, r in ray_sets(bbox, res, seed)]))
+
+
+def face_pairs(bbox, res, n=60, step=0.5, seed=0xFACE + 2):
+    """Per face, n pairs of axis-parallel rays on one line, pointing inwards: [(outer rays, inner rays, m, offset in t)].  The inner
+    ray starts on the face's plane (the f32 nearest to it), the outer one m march steps of `step` voxels before it, with the smallest
+    m in 16..256 for which that origin is an f32 exactly: then sample k + m of the outer ray and sample k of the inner one are the same
+    f64 sums, and the same f32 point.  A face without such an m is left out (the z faces of `thin`: a step of 0.5 mm has bits 2^10
+    times finer than the f32 spacing at 0.55 m)."""
+    rng = np.random.default_rng(seed)
+    lo, hi = lo_hi(bbox)
+    dt = float(step) * float(res)
+    out = []
+    for axis in range(3):
+        for sign, face in ((1.0, lo[axis]), (-1.0, hi[axis])):
+            f = float(np.float32(face))
+            m = next((m for m in range(16, 257) if float(np.float32(f - sign * (m * dt))) == f - sign * (m * dt)), None)
+            if m is None:
+                continue
+            assert (f - sign * (m * dt)) + sign * (m * dt) == f
+            o = rng.uniform(lo, hi, (n, 3)).astype(np.float32)
+            d = np.zeros((n, 3), np.float32)
+            d[:, axis] = sign
+            o[:, axis] = np.float32(f)
+            inner = np.hstack([o, d])
+            o = o.copy()
+            o[:, axis] = np.float32(f - sign * (m * dt))
+            out.append((np.hstack([o, d]), inner, m, m * dt))
+    return out
+
+
+def outside_view(bbox, W=160, H=120):
+    """(pose, K) of a camera 0.08 m outside the z-min face, looking along +z through it at the whole box."""
+    lo, hi = lo_hi(bbox)
+    c = (lo + hi) / 2
+    pose = np.hstack([np.eye(3), np.array([[c[0]], [c[1]], [lo[2] - 0.08]])])
+    f = 0.08 * W / (hi[0] - lo[0]) * 0.8   # the z-min face fills the image and a little of its surroundings
+    return pose, (f, f, (W - 1) / 2.0, (H - 1) / 2.0)
+
+
+# ---- e. meshes ----------------------------------------------------------------------------------------------------------
+
+def huge_quad(bbox):
+    """Two triangles under an oblique pose through the centre of the box, six times its longest side across (as the quad of
+    test_gpu_deviation is to the 1 m box): they leave the grid on every side."""
+    lo, hi = lo_hi(bbox)
+    h = 3.0 * float((hi - lo).max())
+    quad = np.array([[-h, -h, 0], [h, -h, 0], [h, h, 0], [-h, h, 0]], np.float32)
+    a, b = 0.4, 0.3
+    R = (np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1.0]]) @
+         np.array([[1, 0, 0], [0, np.cos(b), -np.sin(b)], [0, np.sin(b), np.cos(b)]]))
+    return quad, np.array([[0, 1, 2], [0, 2, 3]], np.uint32), np.hstack([R, ((lo + hi) / 2).reshape(3, 1)])
+
+
+def near_faces(p, bbox, res):
+    """Per face (x-min, x-max, y-min, y-max, z-min, z-max) the number of points p (n, 3) within one voxel of it.  A lattice plane
+    on a face is never IN_BBOX, so cubes touching it stay open (include/hfpf.h); lattice plane 0 is (float)bbox_min, which is on or
+    outside the min face unless the rounding went inwards.  Where it did not, the outermost cube that can be meshed is cube 1, and the
+    count is of the points within one voxel of lattice plane 1 instead."""
+    lo, hi = lo_hi(bbox)
+    p = np.asarray(p, np.float64)
+    res = float(res)
+    out = []
+    for a in range(3):
+        i0 = 0 if float(np.float32(lo[a])) > lo[a] else 1
+        out += [int((p[:, a] <= lo[a] + (i0 + 1) * res).sum()), int((p[:, a] >= hi[a] - res).sum())]
+    return out
+
+
+def shift_pose(voxels, res):
+    return np.hstack([np.eye(3), (np.asarray(voxels, np.float64) * float(res)).reshape(3, 1)])
+
+
+def outside_own_cell(rows, bbox, res, dims):
+    """Live rows in a face layer whose centroid does not lie in the cell of their own voxel index (the centroid of a voxel's members
+    is a mean of projections onto a line, not of points of the cell)."""
+    lo, _ = lo_hi(bbox)
+    live = rows[rows["count"] > 0]
+    cell = np.floor((centroids(live).astype(np.float64) - lo) / float(res)).astype(np.int64)
+    vox = np.stack([live["ix"], live["iy"], live["iz"]], axis=1).astype(np.int64)
+    return live[(cell != vox).any(axis=1) & in_face_layer(vox, dims)]

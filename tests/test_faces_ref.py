@@ -1,0 +1,110 @@
+"""CPU: the numpy restatements of the read-outs at the faces of the grid.  The references of query, mesh and raycast are written for any
+box and any dims, and had only ever run on models more than 100 voxels from every face; here they run on the CPU oracle's rows and
+occupied list of the scenes of tests/faces.py and are checked against their own independent forms.  This is also the one place where
+the oracle's figures for the four scenes are asserted exactly."""
+import warnings
+
+import numpy as np
+import pytest
+
+import faces
+import mesh_ref as M
+import query_ref as Q
+import raycast_ref as RC
+import scenes
+
+_MODELS = {}
+
+
+def _model(oracle_mod, synth_mod, name):
+    """(scene, rows, occupied, dims, res) of the oracle alone, computed once per scene."""
+    if name not in _MODELS:
+        sc = faces.FaceScene(name)
+        og = oracle_mod.OracleGrid(resolution=sc.resolution, bbox=sc.bbox, fuse_color=True)
+        rows = scenes.run(og, sc, "capture", color=True)
+        occ = og.occupied()
+        dims, res = og.dims
+        og.close()
+        _MODELS[name] = (sc, rows, occ, dims, res)
+    return _MODELS[name]
+
+
+@pytest.fixture(params=["cut", "thin"])
+def model(request, oracle_mod, synth_mod):
+    return _model(oracle_mod, synth_mod, request.param)
+
+
+@pytest.mark.parametrize("name", faces.NAMES)
+def test_the_scenes_are_what_the_oracle_says(oracle_mod, synth_mod, name):
+    sc, rows, occ, dims, res = _model(oracle_mod, synth_mod, name)
+    assert faces.face_counts(rows, occ, dims) == faces.ORACLE_TABLE[name]
+    faces.check_conditions(name, rows, occ, dims)
+    if name == "cut":  # every dim a multiple of 8: the index-dim cells sit alone in the last brick of their axis
+        assert all(d % 8 == 0 for d in dims) and [(d + 1 + 7) // 8 for d in dims] == [14, 10, 12]
+    if name == "far":
+        assert np.abs(np.asarray(sc.bbox)).min() > 1.5
+
+
+@pytest.mark.parametrize("radius", [0, 1, 2, 3, 4])
+def test_query_is_the_brute_force_scan(model, radius):
+    sc, rows, occ, dims, res = model
+    pts = faces.query_points(rows, sc.bbox, res, dims)
+    pts = pts[np.random.default_rng(radius).choice(len(pts), 1500, replace=False)]
+    for kw in (dict(), dict(min_count=3.0), dict(max_distance=1.5 * res)):
+        a = Q.query(rows, occ, pts, faces.IDENT, sc.bbox, res, radius=radius, **kw)
+        b = Q.brute_force(rows, occ, pts, faces.IDENT, sc.bbox, res, radius=radius, **kw)
+        assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes(), kw
+    f = a[0]["flags"]
+    at_dim = (f & Q.IN_BBOX != 0) & (a[0]["voxel"] == np.asarray(dims)).any(axis=1)
+    assert at_dim.any() and not (f[at_dim] & Q.HAS_ROW).any()
+    assert (f & Q.IN_BBOX == 0).any()
+
+
+def test_mesh_agrees_with_the_unwelded_construction_and_stays_in_the_box(model):
+    sc, rows, occ, dims, res = model
+    v, t, sizes = M.mesh(rows, occ, sc.bbox, res, dims, radius=2)
+    assert len(t) > 1000 and t.max() < len(v)
+    loose = M.mesh_unwelded(rows, occ, sc.bbox, res, dims, radius=2)
+    welded = M.positions(v)[np.asarray(t, np.int64)]
+    assert loose.shape == welded.shape
+    assert loose.tobytes() == welded.tobytes()
+    lo, hi = faces.lo_hi(sc.bbox)
+    p = M.positions(v).astype(np.float64)
+    assert (p >= lo).all() and (p <= hi).all(), "a vertex outside the closed box"
+
+
+def test_raycast_of_axis_parallel_and_in_face_rays_raises_no_warning(model):
+    sc, rows, occ, dims, res = model
+    sets = dict(faces.ray_sets(sc.bbox, res))
+    rays = np.vstack([sets["axis-parallel"][::3], sets["in a face's plane"][::3]])
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        h = RC.raycast(rows, occ, rays, faces.IDENT, sc.bbox, res, radius=2, step=0.5, t_range=(0.0, faces.ray_t_max(sc.bbox, res)))
+    assert (h["flags"] & RC.USED != 0).all() and (h["flags"] & RC.HIT != 0).any()
+
+
+def test_a_ray_from_beyond_a_face_and_one_from_the_face_cross_at_the_same_point(model):
+    """Two inward rays on one axis-parallel line, one starting on a face's plane and one m march steps before it, m chosen so that
+    the outer origin is an f32 exactly: sample k + m of the outer ray is sample k of the inner one, bit for bit.  Both therefore see
+    the same signed distances and rows: the same flags, the same crossing interval (the outer index is m larger), the same
+    attributes; t and p are the same f64 expressions up to the association of a sum, so t differs by the offset and p is the same
+    point, each to within one f32 spacing."""
+    sc, rows, occ, dims, res = model
+    t1 = faces.ray_t_max(sc.bbox, res) - 0.05
+    n_hit = 0
+    pairs = faces.face_pairs(sc.bbox, res)
+    assert len(pairs) >= 4
+    for outer, inner, m, off in pairs:
+        kw = dict(radius=2, step=0.5)
+        ho = RC.raycast(rows, occ, outer, faces.IDENT, sc.bbox, res, t_range=(0.0, t1 + off), **kw)
+        hi = RC.raycast(rows, occ, inner, faces.IDENT, sc.bbox, res, t_range=(0.0, t1), **kw)
+        hit = hi["flags"] & RC.HIT != 0
+        n_hit += int(hit.sum())
+        assert np.array_equal(ho["flags"], hi["flags"])
+        assert np.array_equal(ho["sample"][hit], hi["sample"][hit] + m)
+        for k in ("row_voxel", "n", "rgb", "count"):
+            assert ho[k].tobytes() == hi[k].tobytes(), k
+        assert (np.abs(ho["p"][hit] - hi["p"][hit]) <= np.spacing(np.abs(hi["p"][hit]))).all()
+        d = np.abs((ho["t"][hit].astype(np.float64) - hi["t"][hit].astype(np.float64)) - off)
+        assert (d <= np.spacing(ho["t"][hit])).all()
+    assert n_hit >= 30
