@@ -3,7 +3,10 @@
 The synthetic surface (plane z = 0.56 + 0.05 x, sphere r = 0.10 at (0.05, 0, 0.45), a box) sits in the middle of scenes.BBOX_1M,
 more than 100 voxels from every face.  The boxes here are cut out of it, so that rows lie in every face layer (index 0 and dim - 1),
 occupied cells lie at index == dim (the storage has dim + 1 cells an axis; such a cell never has a row), every window of a read-out
-is clipped somewhere, and a triangle or a ray near the model leaves the grid."""
+is clipped somewhere, and a triangle or a ray near the model leaves the grid.  Four of the scenes fuse the same surface where a map
+frame puts it, 137 m to 1024 m from the origin: an f32 step is 1/131 to 1/16 of a voxel there, so input points, centroids and lattice
+points land exactly on cell boundaries and box faces and candidate rows tie for the nearest (boundary_counts, on_lattice_plane,
+query_ref.nearest_ties count what each scene contains)."""
 import numpy as np
 
 import scenes
@@ -11,19 +14,52 @@ import scenes
 CUT_BBOX = (-0.105, 0.1035, -0.0715, 0.0735, 0.38, 0.5575)
 THIN_BBOX = (-0.105, 0.1035, -0.0715, 0.0735, 0.5530, 0.5595)
 FAR_SHIFT = (3.2, -1.7, 2.0)
-# name -> (bbox, resolution, shift of the fusion frame, dims)
-DEFS = {"cut": (CUT_BBOX, 0.002, (0.0, 0.0, 0.0), (104, 72, 88)),
-        "cut3": (CUT_BBOX, 0.003, (0.0, 0.0, 0.0), (69, 48, 59)),
-        "thin": (THIN_BBOX, 0.001, (0.0, 0.0, 0.0), (208, 144, 6)),
-        "far": (CUT_BBOX, 0.002, FAR_SHIFT, (104, 72, 88))}
-NAMES = tuple(DEFS)
-SIX = ("cut", "cut3", "far")   # the scenes every face of which cuts a surface
+# A box of whole cells at a power-of-two resolution: every lattice plane min + i * res, and every one of them moved by a whole number
+# of metres, is an f32 exactly, so transformed points land ON cell boundaries and box faces; (max - min) / res is an exact integer.
+DYADIC_RES = 2.0 ** -9
+DYADIC_BBOX = tuple(k * DYADIC_RES for k in (-54, 53, -37, 38, 195, 285))
+SHIFT_137 = (137.0, -52.0, 23.0)
+SHIFT_128 = (128.0, -64.0, 32.0)
+SHIFT_1024 = (1024.0, -512.0, 256.0)
+SHIFTED_COV = dict(pcl_shifted_cov=True)
+# name -> (bbox, resolution, shift of the fusion frame, dims, config of engine and oracle)
+DEFS = {"cut": (CUT_BBOX, 0.002, (0.0, 0.0, 0.0), (104, 72, 88), {}),
+        "cut3": (CUT_BBOX, 0.003, (0.0, 0.0, 0.0), (69, 48, 59), {}),
+        "thin": (THIN_BBOX, 0.001, (0.0, 0.0, 0.0), (208, 144, 6), {}),
+        "far": (CUT_BBOX, 0.002, FAR_SHIFT, (104, 72, 88), {}),
+        # 137 m out an f32 step is 1.5e-5 m, 1/131 of a voxel.  With the default (single-pass f32) covariance the normals of far137
+        # are rounding noise, as the reference's would be: arbitrary but deterministic, so any change in operation order shows
+        "far137": (CUT_BBOX, 0.002, SHIFT_137, (104, 72, 88), {}),
+        "far137s": (CUT_BBOX, 0.002, SHIFT_137, (104, 72, 88), SHIFTED_COV),
+        "dy128s": (DYADIC_BBOX, DYADIC_RES, SHIFT_128, (107, 75, 90), SHIFTED_COV),
+        "dy1024s": (DYADIC_BBOX, DYADIC_RES, SHIFT_1024, (107, 75, 90), SHIFTED_COV)}
+ALL = tuple(DEFS)
+NAMES = ("cut", "cut3", "thin", "far", "far137s", "dy128s")   # every read-out
+HOT_NAMES = ("far137", "dy1024s")                              # hot path, query and mesh only
+SIX = ("cut", "cut3", "far", "far137", "far137s")   # the scenes every face of which cuts a surface, with cells at index == dim
+DYADIC = ("dy128s", "dy1024s")                      # every face cuts a surface; a box of whole cells has no cell at index == dim
+SHIFTED = ("far", "far137", "far137s", "dy128s", "dy1024s")
 # what the CPU oracle alone gives (asserted exactly in test_faces_ref.py only): rows, live rows, live rows in the layers
 # x=0, x=dim-1, y=0, y=dim-1, z=0, z=dim-1, occupied cells at index == dim per axis
 ORACLE_TABLE = {"cut": (10087, 9872, (140, 45, 132, 114, 291, 260), (42, 216, 1358)),
                 "cut3": (5185, 4812, (66, 22, 76, 78, 174, 388), (36, 143, 582)),
                 "thin": (5230, 5230, (0, 0, 33, 8, 0, 272), (0, 66, 97)),
-                "far": (10087, 9897, (140, 45, 132, 112, 290, 255), (42, 216, 1358))}
+                "far": (10087, 9897, (140, 45, 132, 112, 290, 255), (42, 216, 1358)),
+                "far137": (10085, 10011, (140, 45, 128, 111, 275, 252), (42, 216, 1357)),
+                "far137s": (10085, 9863, (140, 45, 132, 114, 291, 258), (42, 216, 1357)),
+                "dy128s": (13871, 13583, (145, 43, 194, 170, 300, 681), (0, 0, 0)),
+                "dy1024s": (13462, 13175, (145, 47, 186, 152, 297, 682), (0, 0, 0))}
+# boundary_counts() of the dyadic scenes (asserted exactly in test_faces_ref.py only): in-box input points, those of them on an exact
+# cell boundary, used points exactly on the plane of a box face
+BOUNDARY_TABLE = {"dy128s": (58260, 729, 96), "dy1024s": (58121, 5838, 866)}
+# half of the last two, as the floor check_conditions holds every session to
+BOUNDARY_FLOOR = {"dy128s": (360, 48), "dy1024s": (2900, 430)}
+Z_CLIP = (0.28, 0.6)   # the default z-clip of engine and oracle
+# Per option set of test_gpu_faces.QUERY_OPTS, half of query_ref.nearest_ties(...).sum() over query_points() on the oracle's exact rows
+# alone: far137 gives 0, 5, 10, 12, 12, 10, 7 and far137s 0, 949, 1367, 1524, 1615, 1366, 1187 (radius 0 has one candidate a point).
+# Point and centroid are f32s of spacing 2^-16 (x), 2^-18 (y), 2^-19 m (z) there, so d2 is a sum of three small integer squares scaled
+# by powers of two, and equal sums are common.
+TIE_FLOOR = {"far137": (0, 2, 5, 6, 6, 5, 3), "far137s": (0, 474, 683, 762, 807, 683, 593)}
 CAPS = dict(max_bricks=60000, max_log_points=4 << 20, max_normals=1 << 20, max_frames=4096)
 IDENT = np.hstack([np.eye(3), np.zeros((3, 1))])
 
@@ -34,10 +70,10 @@ class FaceScene(scenes.Scene):
     same surface, fused elsewhere (the z-clip acts in the camera frame and does not notice)."""
 
     def __init__(self, name):
-        bbox, res, shift, dims = DEFS[name]
+        bbox, res, shift, dims, config = DEFS[name]
         moved = tuple(float(b) + float(shift[i // 2]) for i, b in enumerate(bbox))
         super().__init__(8, 320, 240, res, bbox=moved, clean_every=4)
-        self.name, self.dims, self.shift = name, dims, np.asarray(shift, np.float64)
+        self.name, self.dims, self.shift, self.config = name, dims, np.asarray(shift, np.float64), dict(config)
         self.render_poses = self.poses
         self.poses = [np.hstack([p[:, :3], p[:, 3:] + self.shift.reshape(3, 1)]) for p in self.render_poses]
 
@@ -69,9 +105,48 @@ def check_conditions(name, rows, occ, dims):
     if name in SIX:
         assert min(layers) >= 20, "%s: a face layer holds fewer than 20 live rows: %r" % (name, layers)
         assert min(at_dim) >= 1, "%s: an axis without an occupied cell at index == dim: %r" % (name, at_dim)
+    elif name in DYADIC:
+        # max = min + dim * res exactly: a point of cell dim would have p >= max, and the strict box test drops it
+        assert min(layers) >= 20, "%s: a face layer holds fewer than 20 live rows: %r" % (name, layers)
+        assert at_dim == (0, 0, 0), "%s: a box of whole cells with an occupied cell at index == dim: %r" % (name, at_dim)
+        n_in, on_cell, on_face = boundary_counts(FaceScene(name))
+        print("%s: %d input points in the box, %d on an exact cell boundary, %d exactly on a face's plane" % (name, n_in, on_cell, on_face))
+        assert on_cell >= BOUNDARY_FLOOR[name][0] and on_face >= BOUNDARY_FLOOR[name][1], "%s: %r" % (name, (n_in, on_cell, on_face))
     else:
         assert dims[2] < 8 and layers[2] > 0 and layers[3] > 0 and layers[5] > 0, "%s: %r %r" % (name, dims, layers)
     return layers, at_dim
+
+
+def boundary_counts(scene):
+    """(input points in the box, those of them with a coordinate exactly on a cell boundary, used points with a coordinate exactly on
+    the plane of a box face) over the scene's frames, with no engine or oracle: integrate's transform restated (f64 from the widened
+    f32 input, left to right, one rounding to f32; query_ref.transform), its z-clip in the camera frame and its strict box test.  p -
+    min is exact in f64, so for a power-of-two resolution "the quotient is a whole number" is decided exactly; the points on a face's
+    plane fail the strict test and are not among the first figure."""
+    import query_ref as Q
+    lo, hi = lo_hi(scene.bbox)
+    res = float(np.float32(scene.resolution))   # engine and oracle keep (double)(float)resolution
+    lay = scene.layout
+    n_in = on_cell = on_face = 0
+    for f in range(scene.n_frames):
+        rec = np.frombuffer(scene.frame(f), np.uint8).reshape(-1, lay["point_step"])
+        xyz = np.stack([rec[:, lay[k]:lay[k] + 4].copy().view(np.float32)[:, 0] for k in ("off_x", "off_y", "off_z")], axis=1)
+        xyz = xyz[Q.used(xyz, True, Z_CLIP)]
+        p = Q.transform(scene.poses[f], xyz).astype(np.float64)
+        inside = ((p > lo) & (p < hi)).all(axis=1)
+        q = (p - lo) / res
+        n_in += int(inside.sum())
+        on_cell += int((inside & (q == np.floor(q)).any(axis=1)).sum())
+        on_face += int(((p == lo) | (p == hi)).any(axis=1).sum())
+    return n_in, on_cell, on_face
+
+
+def on_lattice_plane(p, bbox, res):
+    """Per (n, 3) f32 point: whether a coordinate lies exactly on a lattice plane min + i * res (decided exactly where p - min and the
+    division by res are exact in f64: a power-of-two resolution), and the exact integer quotients floor((p - min) / res)."""
+    lo, _ = lo_hi(bbox)
+    q = (np.asarray(p, np.float32).astype(np.float64) - lo) / float(res)
+    return (q == np.floor(q)).any(axis=1), np.floor(q).astype(np.int64)
 
 
 def in_face_layer(vox, dims):

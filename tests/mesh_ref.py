@@ -150,6 +150,20 @@ def mesh(rows, occupied, bbox, res, dims, radius=2, min_count=0.0, max_distance=
     return (verts, tris, sizes, ends) if with_ends else (verts, tris, sizes)
 
 
+def cubes_with_a_tied_corner(rows, occupied, bbox, res, dims, radius=2, min_count=0.0, max_distance=np.inf):
+    """The number of meshed cubes with a corner sample whose nearest row was decided by the tie rule (query_ref.nearest_ties)."""
+    cubes = cube_set(rows, dims, min_count)
+    corners = corner_set(cubes)
+    if not len(cubes):
+        return 0
+    pts = lattice_points(corners, bbox, res)
+    hits, _ = Q.query(rows, occupied, pts, IDENT, bbox, res, radius=radius, min_count=min_count, max_distance=max_distance)
+    tied = Q.nearest_ties(rows, hits, pts, radius, min_count, max_distance)
+    idx = np.stack([np.searchsorted(corners, cubes + offset_key(c)) for c in range(8)], axis=1)
+    meshed = ((hits["flags"] & Q.FOUND) != 0)[idx].all(axis=1)
+    return int((meshed & tied[idx].any(axis=1)).sum())
+
+
 def mesh_unwelded(rows, occupied, bbox, res, dims, radius=2, min_count=0.0, max_distance=np.inf):
     """Per meshed cube and tetrahedron, each triangle's three positions computed from its own edge's endpoints: (n, 3, 3) f32 in the
     triangle order of mesh(), without any shared vertex numbering."""

@@ -149,6 +149,43 @@ def query(rows, occupied, points, pose, bbox, res, z_clip=(0.28, 0.6), radius=1,
     return hits, out
 
 
+def nearest_ties(rows, hits, pts, radius, min_count=0.0, max_distance=np.inf):
+    """Per point (bool): FOUND, and the smallest d2 is shared by two or more candidate rows of the window, so that the tie rule
+    (the lexicographically smallest (ix, iy, iz)) decided the row.  hits = query()'s of pts under the identity pose with the same
+    options; d2 is query()'s expression, compared exactly."""
+    p = np.asarray(pts, np.float32).reshape(-1, 3)
+    tied = np.zeros(len(p), bool)
+    idx = np.flatnonzero(hits["flags"] & FOUND != 0)
+    cand = candidates(rows, min_count)
+    if not len(idx) or not len(cand):
+        return tied
+    ck = keys(cand["ix"], cand["iy"], cand["iz"])
+    pv = hits["voxel"][idx].astype(np.int64)
+    pp = p[idx].astype(np.float64)
+    md2 = float(max_distance) * float(max_distance)
+    best_d2 = np.full(len(idx), np.inf)
+    n_best = np.zeros(len(idx), np.int64)
+    cx, cy, cz = (cand[k].astype(np.float64) for k in ("x", "y", "z"))
+    r = int(radius)
+    for ox in range(-r, r + 1):
+        for oy in range(-r, r + 1):
+            for oz in range(-r, r + 1):
+                t = pv + np.array([ox, oy, oz], np.int64)
+                ok = ((t >= 0) & (t < (1 << KEY_BITS))).all(axis=1)
+                tk = keys(t[:, 0], t[:, 1], t[:, 2])
+                j = np.minimum(np.searchsorted(ck, tk), len(ck) - 1)
+                ok &= ck[j] == tk
+                dx, dy, dz = pp[:, 0] - cx[j], pp[:, 1] - cy[j], pp[:, 2] - cz[j]
+                d2 = (dx * dx + dy * dy) + dz * dz
+                ok &= d2 <= md2
+                less = ok & (d2 < best_d2)
+                n_best = np.where(less, 1, n_best + (ok & (d2 == best_d2)))
+                best_d2 = np.where(less, d2, best_d2)
+    assert (n_best >= 1).all(), "a found point without a candidate"
+    tied[idx] = n_best >= 2
+    return tied
+
+
 def brute_force(rows, occupied, points, pose, bbox, res, z_clip=(0.28, 0.6), radius=1, min_count=0.0, max_distance=np.inf, zclip=False):
     """The same by an O(N * M) scan of every candidate row per point (tests of query() itself)."""
     hits, p, v, ib = _finish(points, pose, bbox, res, occupied, z_clip, zclip)

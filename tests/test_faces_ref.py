@@ -1,7 +1,7 @@
 """CPU: the numpy restatements of the read-outs at the faces of the grid.  The references of query, mesh and raycast are written for any
 box and any dims, and had only ever run on models more than 100 voxels from every face; here they run on the CPU oracle's rows and
 occupied list of the scenes of tests/faces.py and are checked against their own independent forms.  This is also the one place where
-the oracle's figures for the four scenes are asserted exactly."""
+the oracle's figures for the scenes are asserted exactly."""
 import warnings
 
 import numpy as np
@@ -20,7 +20,7 @@ def _model(oracle_mod, synth_mod, name):
     """(scene, rows, occupied, dims, res) of the oracle alone, computed once per scene."""
     if name not in _MODELS:
         sc = faces.FaceScene(name)
-        og = oracle_mod.OracleGrid(resolution=sc.resolution, bbox=sc.bbox, fuse_color=True)
+        og = oracle_mod.OracleGrid(resolution=sc.resolution, bbox=sc.bbox, fuse_color=True, **sc.config)
         rows = scenes.run(og, sc, "capture", color=True)
         occ = og.occupied()
         dims, res = og.dims
@@ -34,7 +34,7 @@ def model(request, oracle_mod, synth_mod):
     return _model(oracle_mod, synth_mod, request.param)
 
 
-@pytest.mark.parametrize("name", faces.NAMES)
+@pytest.mark.parametrize("name", faces.ALL)
 def test_the_scenes_are_what_the_oracle_says(oracle_mod, synth_mod, name):
     sc, rows, occ, dims, res = _model(oracle_mod, synth_mod, name)
     assert faces.face_counts(rows, occ, dims) == faces.ORACLE_TABLE[name]
@@ -43,6 +43,43 @@ def test_the_scenes_are_what_the_oracle_says(oracle_mod, synth_mod, name):
         assert all(d % 8 == 0 for d in dims) and [(d + 1 + 7) // 8 for d in dims] == [14, 10, 12]
     if name == "far":
         assert np.abs(np.asarray(sc.bbox)).min() > 1.5
+    if name.startswith("far137"):
+        assert np.abs(np.asarray(sc.bbox)).min() > 23
+    if name in faces.DYADIC:
+        lo, hi = faces.lo_hi(sc.bbox)
+        assert res == faces.DYADIC_RES and np.array_equal((hi - lo) / res, np.asarray(dims, np.float64)), "a box of whole cells"
+        assert np.array_equal(np.asarray(sc.bbox, np.float32).astype(np.float64), np.asarray(sc.bbox))
+        assert faces.boundary_counts(sc) == faces.BOUNDARY_TABLE[name]
+
+
+def test_near_the_origin_the_dyadic_box_meets_next_to_no_boundary(synth_mod):
+    """What the shift is for: the same box and stream without it put 2 of 58,271 points on a cell boundary."""
+    sc = faces.FaceScene("dy128s")
+    sc.bbox, sc.poses = faces.DYADIC_BBOX, sc.render_poses
+    assert faces.boundary_counts(sc) == (58271, 2, 1)
+
+
+@pytest.mark.parametrize("name", ["far137s", "dy128s"])
+def test_nearest_ties_is_the_brute_force_count(oracle_mod, synth_mod, name):
+    """query_ref.nearest_ties against a scan of every candidate row per point, on 3000 of the scene's query points."""
+    sc, rows, occ, dims, res = _model(oracle_mod, synth_mod, name)
+    pts = faces.query_points(rows, sc.bbox, res, dims)
+    pts = pts[np.random.default_rng(7).choice(len(pts), 3000, replace=False)]
+    cand = Q.candidates(rows, 0.0)
+    cv = np.stack([cand["ix"], cand["iy"], cand["iz"]], axis=1).astype(np.int64)
+    cxyz = faces.centroids(cand).astype(np.float64)
+    for radius in (1, 3):
+        hits, _ = Q.query(rows, occ, pts, faces.IDENT, sc.bbox, res, radius=radius)
+        tied = Q.nearest_ties(rows, hits, pts, radius)
+        want = np.zeros(len(pts), bool)
+        for i in np.flatnonzero(hits["flags"] & Q.FOUND != 0):
+            near = np.abs(cv - hits["voxel"][i].astype(np.int64)).max(axis=1) <= radius
+            d = pts[i].astype(np.float64) - cxyz[near]
+            d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+            want[i] = (d2 == d2.min()).sum() >= 2
+        print("%s, radius %d: %d of %d found points tie" % (name, radius, want.sum(), (hits["flags"] & Q.FOUND != 0).sum()))
+        assert np.array_equal(tied, want)
+        assert want.sum() >= 1, "a scene without ties shows nothing"
 
 
 @pytest.mark.parametrize("radius", [0, 1, 2, 3, 4])

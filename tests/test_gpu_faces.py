@@ -1,8 +1,10 @@
 """GPU: every read-out on a model cut by all six faces of the grid.  The sessions of the other read-out tests build their models in
-the middle of a 1 m box, more than 100 voxels from every face; the four scenes of tests/faces.py put rows into every face layer,
-occupied cells at index == dim, clipped windows everywhere and a last brick that holds nothing but index-dim cells.  Everything is
-byte for byte against the numpy restatement of that read-out, run on the session's own extract() rows and occupied() list; the
-"this run contained" assertions keep a scene that stops touching a face from passing vacuously."""
+the middle of a 1 m box, more than 100 voxels from every face; the scenes of tests/faces.py put rows into every face layer,
+occupied cells at index == dim, clipped windows everywhere and a last brick that holds nothing but index-dim cells.  Four of them
+fuse the same surface 137 m to 1024 m from the origin, where an f32 step is 1/131 to 1/16 of a voxel: input points, centroids and
+lattice points land exactly on cell boundaries and box faces, and candidate rows tie for the nearest.  Everything is byte for byte
+against the numpy restatement of that read-out, run on the session's own extract() rows and occupied() list; the "this run
+contained" assertions keep a scene that stops touching a face, a boundary or a tie from passing vacuously."""
 import numpy as np
 import pytest
 
@@ -25,11 +27,14 @@ from test_gpu_mesh import _device as mesh_device, _same as mesh_same
 from test_gpu_query import _same as query_same
 from test_gpu_raycast import _device_rays, _same as ray_same
 from test_gpu_render import _counters, _same as render_same
+import test_gpu_track as TT
+import track_ref as TR
 
 pytestmark = pytest.mark.gpu
 INF = float("inf")
 IDENT = faces.IDENT
-NAMES = faces.NAMES
+NAMES = faces.NAMES                        # every read-out
+HOT_NAMES = faces.NAMES + faces.HOT_NAMES  # hot path, query and mesh
 STEP = 0.5
 
 
@@ -40,7 +45,7 @@ class Session:
         self.name, self.H = name, hfpf_mod
         self.sc = faces.FaceScene(name)
         self.bbox = self.sc.bbox
-        self.g = hfpf_mod.OccupancyGrid(resolution=self.sc.resolution, bbox=self.bbox, fuse_color=True, **caps)
+        self.g = hfpf_mod.OccupancyGrid(resolution=self.sc.resolution, bbox=self.bbox, fuse_color=True, **self.sc.config, **caps)
         self.rows = scenes.run(self.g, self.sc, "integrate").copy()
         self.occ = self.g.occupied().copy()
         self.dims, self.res = self.g.dims
@@ -83,20 +88,21 @@ def sessions(hfpf_mod, synth_mod):
 
 # ---- 0. the hot path ------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", HOT_NAMES)
 def test_hot_path_against_the_oracle(oracle_mod, sessions, name):
-    """Rows and occupied list against the oracle.  `far` asserts the exact comparison only: the 1e-5 of scenes.compare_rows was set
-    for coordinates near 1 m, and the f32 recurrence's own noise at 4 m is printed here for the ledger of DESIGN.md, not bounded."""
+    """Rows and occupied list against the oracle.  The shifted scenes assert the exact comparison only: the 1e-5 of
+    scenes.compare_rows was set for coordinates near 1 m (at 137 m one f32 step is 1.5e-5), and the f32 recurrence's own noise at 4 m
+    to 1024 m is printed here for the ledger of DESIGN.md, not bounded."""
     s = sessions(name)
-    og = oracle_mod.OracleGrid(resolution=s.sc.resolution, bbox=s.bbox, fuse_color=True, exact_moments=True)
+    og = oracle_mod.OracleGrid(resolution=s.sc.resolution, bbox=s.bbox, fuse_color=True, exact_moments=True, **s.sc.config)
     ref = scenes.run(og, s.sc, "capture", color=True)
     exact, occ_ref = og.extract_exact(), og.occupied()
     og.close()
     assert np.array_equal(occ_ref, s.occ), "occupied lists differ"
     rep = scenes.compare_rows_exact(exact, s.rows)
     assert rep["exact_bytes_differing"] == 0
-    if name == "far":
-        print("far, oracle's recurrences against the engine: %r" % scenes.error_report(ref, s.rows))
+    if name in faces.SHIFTED:
+        print("%s, oracle's recurrences against the engine: %r" % (name, scenes.error_report(ref, s.rows)))
     else:
         scenes.compare_rows(ref, s.rows)
 
@@ -108,14 +114,20 @@ QUERY_OPTS = [(0, 0.0, INF), (1, 0.0, INF), (2, 0.0, INF), (3, 0.0, INF), (4, 0.
 
 
 @pytest.mark.parametrize("opt", QUERY_OPTS, ids=["r%d_mc%g_md%g" % o for o in QUERY_OPTS])
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", HOT_NAMES)
 def test_query(sessions, name, opt):
     s = sessions(name)
     radius, min_count, md = opt
     kw = dict(radius=radius, min_count=min_count, max_distance=md * s.res)
     pts = faces.query_points(s.rows, s.bbox, s.res, s.dims)
+    if name in faces.DYADIC:  # and every live row's own centroid, unjittered: a mean that can lie exactly on a lattice plane
+        own = faces.centroids(s.rows[s.rows["count"] > 0])
+        pts = np.ascontiguousarray(np.vstack([pts, own]))
     got = s.g.query(pts, IDENT, **kw)
     ref = Q.query(s.rows, s.occ, pts, IDENT, s.bbox, s.res, **kw)
+    if name in faces.TIE_FLOOR:
+        ties = int(Q.nearest_ties(s.rows, ref[0], pts, radius, min_count, md * s.res).sum())
+        print("%s %r: %d found points whose nearest row was decided by the tie rule" % (name, opt, ties))
     f = got[0]["flags"]
     at_dim = (f & Q.IN_BBOX != 0) & (got[0]["voxel"] == np.asarray(s.dims)).any(axis=1)
     found = f & Q.FOUND != 0
@@ -123,9 +135,19 @@ def test_query(sessions, name, opt):
     print("%s %r: %d points, %d in the box, %d of them in a cell of index dim (%d occupied), %d found, %d of them a face-layer row" % (
         name, opt, len(pts), (f & Q.IN_BBOX != 0).sum(), at_dim.sum(), (f[at_dim] & Q.OCCUPIED != 0).sum(), found.sum(), on_face.sum()))
     query_same(got, ref, "%s %r" % (name, opt))
-    assert at_dim.any() and not (f[at_dim] & Q.HAS_ROW).any() and (f[at_dim] & Q.OCCUPIED).any()
+    if name in faces.DYADIC:  # max = min + dim * res exactly: no point of the box has an index == dim
+        assert not at_dim.any()
+    else:
+        assert at_dim.any() and not (f[at_dim] & Q.HAS_ROW).any() and (f[at_dim] & Q.OCCUPIED).any()
     assert on_face.sum() >= 100
     assert (f & Q.IN_BBOX == 0).any()
+    if name in faces.TIE_FLOOR:
+        assert ties >= faces.TIE_FLOOR[name][QUERY_OPTS.index(opt)]
+    if name in faces.DYADIC:
+        on, quotient = faces.on_lattice_plane(own, s.bbox, s.res)
+        print("%s: %d of %d own centroids have a coordinate exactly on a lattice plane" % (name, on.sum(), len(own)))
+        assert on.sum() >= 100
+        assert np.array_equal(got[0]["voxel"][len(pts) - len(own):][on], quotient[on]), "a centroid on a lattice plane in another cell"
 
 
 # ---- b. mesh --------------------------------------------------------------------------------------------------------------------
@@ -134,7 +156,7 @@ MESH_OPTS = [(1, 0.0), (2, 0.0), (4, 0.0), (2, 3.0)]
 
 
 @pytest.mark.parametrize("opt", MESH_OPTS, ids=["r%d_mc%g" % o for o in MESH_OPTS])
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", HOT_NAMES)
 def test_mesh(sessions, name, opt):
     s = sessions(name)
     kw = dict(radius=opt[0], min_count=opt[1])
@@ -151,18 +173,25 @@ def test_mesh(sessions, name, opt):
     print("%s %r: %d vertices, %d triangles, %r; vertices within a voxel of each face %r" % (name, opt, len(v), len(t), sizes, near))
     if name in ("cut", "far"):
         assert min(near) >= 1, near
-    if name == "far":
+    if name in faces.DYADIC:
+        for a in range(3):
+            c = lo[a] + np.arange(s.dims[a] + 2, dtype=np.float64) * s.res
+            assert np.array_equal(c.astype(np.float32).astype(np.float64), c), "a lattice point that is no f32"
+        tied = M.cubes_with_a_tied_corner(s.rows, s.occ, s.bbox, s.res, s.dims, **kw)
+        print("%s %r: %d meshed cubes with a corner sample whose nearest row was decided by the tie rule" % (name, opt, tied))
+        assert tied >= 1
+    if name in faces.SHIFTED:
         # the vertices' source corners against mesh_ref.lattice_points: a vertex of an edge (a, d) has p[axis] = (float)(c_a + t * 0)
         # = c_a[axis] wherever d[axis] = 0, so on every axis the lattice values must occur among the vertices' coordinates bit for
-        # bit, and a vertex of any edge but the cube diagonals carries at least one (at 4 m the f32 spacing is 2.4e-7 to 4.8e-7 m:
-        # a lattice point rounded another way would show here, independently of mesh_ref's own vertices)
+        # bit, and a vertex of any edge but the cube diagonals carries at least one (at 4 m the f32 spacing is 2.4e-7 to 4.8e-7 m,
+        # at 137 m 1.5e-5 m: a lattice point rounded another way would show here, independently of mesh_ref's own vertices)
         assert (ea["ix"] >= 0).all() and (eb["ix"] >= 0).all(), "every vertex has two defined source corners"
         on = np.zeros(len(v), bool)
         for a, k in enumerate(("x", "y", "z")):
             i = np.arange(s.dims[a] + 1, dtype=np.int64)
             line = M.lattice_points(Q.keys(*(i if b == a else 0 * i for b in range(3))), s.bbox, s.res)[:, a]
             on |= np.isin(v[k], line)
-        print("far: %d of %d vertices carry a lattice value" % (on.sum(), len(v)))
+        print("%s: %d of %d vertices carry a lattice value" % (name, on.sum(), len(v)))
         assert on.mean() > 0.5
 
 
@@ -230,14 +259,21 @@ def _cover_kw(s):
     return dict(radius=2, max_distance=2 * s.res, spacing=s.res)
 
 
+def _compare(s, pose, md, every=1):
+    """(got, ref) of compare against the session's own mesh: the device form on the device copy, or, to bound the reference's run
+    time (it grows with the pairs of rows and nearby triangles), the host form on every `every`-th triangle."""
+    v, t, dv, dt = s.own_mesh()
+    if every == 1:
+        return dev_device(s.g, s.H, dv, len(v), 32, dt, len(t), pose, max_distance=md), D.compare(s.rows, v, 32, t, pose, 0.0, md)
+    t = np.ascontiguousarray(t[::every])
+    return s.g.compare_mesh(v, t, pose, max_distance=md), D.compare(s.rows, v, 32, t, pose, 0.0, md)
+
+
 @pytest.mark.parametrize("voxels", [3, 20])
 @pytest.mark.parametrize("name", NAMES)
 def test_compare_own_mesh(sessions, name, voxels):
     s = sessions(name)
-    v, t, dv, dt = s.own_mesh()
-    md = voxels * s.res
-    ref = D.compare(s.rows, v, 32, t, IDENT, 0.0, md)
-    got = dev_device(s.g, s.H, dv, len(v), 32, dt, len(t), IDENT, max_distance=md)
+    got, ref = _compare(s, IDENT, voxels * s.res, 4 if name in faces.DYADIC else 1)
     print("%s, %d voxels: found %d of %d, max %.6f" % (name, voxels, got[1]["n_found"], got[1]["n_rows"], got[1]["max_abs"]))
     dev_same(got, ref, "%s, own mesh, %d voxels" % (name, voxels))
     assert got[1]["n_found"] > 0.5 * len(s.rows)
@@ -275,8 +311,7 @@ def test_compare_and_cover_a_displaced_mesh(sessions, name):
     s = sessions(name)
     v, t, dv, dt = s.own_mesh()
     pose = faces.shift_pose((3, -2, 4), s.res)
-    ref = D.compare(s.rows, v, 32, t, pose, 0.0, 3 * s.res)
-    got = dev_device(s.g, s.H, dv, len(v), 32, dt, len(t), pose, max_distance=3 * s.res)
+    got, ref = _compare(s, pose, 3 * s.res, 4 if name in ("far137s", "dy128s") else 1)
     dev_same(got, ref, "%s, displaced mesh" % name)
     assert 0 < got[1]["n_found"] < len(s.rows)
     ref = V.cover(s.rows, s.occ, v, 32, t, pose, s.bbox, s.res, **_cover_kw(s))
@@ -312,13 +347,16 @@ def _align_start(s):
     return rigid(0.3, (0.5, 1.0, -0.4), tuple(np.array([0.6, -0.64, 0.48]) * 2 * s.res), A.centre(s.bbox))
 
 
-@pytest.mark.parametrize("name", ["cut", "far"])
+@pytest.mark.parametrize("name", ["cut", "far", "far137s"])
 def test_align_own_mesh(sessions, name):
-    """In `far` the twist is taken about a centre 4 m from the origin."""
+    """In `far` the twist is taken about a centre 4 m from the origin, in `far137s` 148 m from it (every 8th row there: the
+    reference's candidate pairs grow with the coordinates' magnitude, as the engine's brick inflation does)."""
     s = sessions(name)
     v, t, dv, dt = s.own_mesh()
     start = _align_start(s)
     kw = dict(ALIGN_KW, max_distance=8 * s.res)
+    if name == "far137s":
+        kw["stride"] = 8
     ref = A.align(s.rows, v, 32, t, start, s.bbox, **kw)
     print("%s: %d iterations, flags %d, %d of %d inliers, rms %r, corners %.6f -> %.6f m" % (
         name, ref["iterations"], ref["flags"], ref["inliers"], ref["rows_sampled"], ref["history"], corner_displacement(start, IDENT, s.bbox),
@@ -329,15 +367,42 @@ def test_align_own_mesh(sessions, name):
     align_equal(s.g.align_mesh(v, t, start, **kw), ref, "%s, host form" % name)
 
 
-def test_render_far(sessions):
-    """Render is defined on rows and a z-buffer, not on the grid; one view of the model fused 4 m from the origin all the same."""
-    s = sessions("far")
+def _render_two_views(s):
     K, W, H, z_range = (300.0, 300.0, 159.5, 119.5), 320, 240, (0.05, 3.0)
     for pose in (s.sc.poses[0], s.sc.poses[5]):
         got = s.g.render(pose, K, W, H, z_range=z_range, min_count=1, splat_radius=2, max_splat_radius=4, cull_backfaces=True, world_normals=True)
         ref = R.render(s.rows, pose, K, W, H, s.res, z_range, 1, 2, 4, R.CULL_BACKFACES | R.WORLD_NORMALS)
-        render_same(got, ref, "far")
+        render_same(got, ref, s.name)
         assert (~np.isnan(got["depth"])).sum() > 1000
+
+
+def test_render_far(sessions):
+    """Render is defined on rows and a z-buffer, not on the grid; one view of the model fused 4 m from the origin all the same."""
+    _render_two_views(sessions("far"))
+
+
+def test_render_far137s(sessions):
+    """And 148 m from it: the camera-frame point of a row is a difference of two large numbers."""
+    _render_two_views(sessions("far137s"))
+
+
+def test_track_depth_far137s(synth_mod, sessions):
+    """hfpf_track_depth of a held-out frame of the same stream against the model fused 148 m out, byte for byte against track_ref:
+    the sums stay in headroom only because they are taken about the camera centre c with the lever a = pw - c."""
+    s = sessions("far137s")
+    assert s.sc.resolution == TT.RES
+    W, H, f = 320, 240, s.sc.n_frames + 1
+    seen = synth_mod.pose(s.sc.pose_seed, f)
+    depth, _, K = synth_mod.depth_frame(s.sc.seed, f, W, H, seen)
+    true = np.hstack([seen[:, :3], seen[:, 3:] + s.sc.shift.reshape(3, 1)])
+    guess = TT._perturb(true, 2.0, (0.006, -0.005, 0.006))
+    got = s.g.track_depth(depth, guess, K, stride=1, **TT.OPTS)
+    ref = TT._ref(s.rows, TR.depth_points(depth, K, 1), guess, K, W, H)
+    print("far137s: %d iterations, flags %d, %d of %d used points inliers, rms %.2e, error %s -> %s" % (
+        got[1]["iterations"], got[1]["flags"], got[1]["inliers"], got[1]["points_used"], got[1]["rms"], TT._errors(guess, true),
+        TT._errors(got[0], true)))
+    TT._same_result(got, ref, "far137s")
+    assert ref["iterations"] > 1 and ref["inliers"] > 1000
 
 
 # ---- f. a restored handle gives the same bytes -----------------------------------------------------------------------------------
@@ -361,20 +426,27 @@ def _one_of_each(s, g, pts, rays):
     return out
 
 
-def test_a_restored_handle_gives_the_same_bytes(hfpf_mod, sessions):
-    s = sessions("cut")
+def _restored_handle_gives_the_same_bytes(hfpf_mod, s):
     pts = faces.query_points(s.rows, s.bbox, s.res, s.dims)
     rays = faces.rays(s.bbox, s.res)
     first = _one_of_each(s, s.g, pts, rays)
     blob = s.g.snapshot()
     larger = dict(faces.CAPS, max_bricks=100000, max_normals=2 << 20, max_frames=8192)  # (max_log_points must be the snapshot's)
-    with hfpf_mod.OccupancyGrid(resolution=s.sc.resolution, bbox=s.bbox, fuse_color=True, **larger) as g2:
+    with hfpf_mod.OccupancyGrid(resolution=s.sc.resolution, bbox=s.bbox, fuse_color=True, **s.sc.config, **larger) as g2:
         g2.restore(blob)
         assert g2.extract().tobytes() == s.rows.tobytes() and g2.occupied().tobytes() == s.occ.tobytes()
         second = _one_of_each(s, g2, pts, rays)
     for k in first:
         assert first[k] == second[k], "%s differs on the restored handle" % k
     assert len(first["mesh"]) > 100000 and len(first["components"]) > len(s.rows.tobytes())
+
+
+def test_a_restored_handle_gives_the_same_bytes(hfpf_mod, sessions):
+    _restored_handle_gives_the_same_bytes(hfpf_mod, sessions("cut"))
+
+
+def test_a_restored_far137s_handle_gives_the_same_bytes(hfpf_mod, sessions):
+    _restored_handle_gives_the_same_bytes(hfpf_mod, sessions("far137s"))
 
 
 # ---- g. nothing changes ----------------------------------------------------------------------------------------------------------

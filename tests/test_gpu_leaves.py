@@ -3,8 +3,22 @@ random inputs (bit-exact: these feed integer voxel indices and discrete membersh
 import numpy as np
 import pytest
 
+import faces
+
 pytestmark = pytest.mark.gpu
 TINY = dict(max_bricks=1024, max_log_points=1 << 16, max_normals=1 << 12, max_frames=16)
+
+
+def _moved(bbox, shift):
+    return tuple(float(b) + float(shift[i // 2]) for i, b in enumerate(bbox))
+
+
+# Boxes of tests/faces.py in a map frame: at 137 m an f32 step is 1/131 of a 2 mm voxel; the dyadic boxes have every cell boundary an
+# f32 exactly, with f32 steps of 1/512 to 1/128 (128 m) and 1/64 to 1/16 (1024 m) of a voxel.  bbox -> the shift it was moved by
+FAR = {_moved(faces.CUT_BBOX, faces.SHIFT_137): faces.SHIFT_137,
+       _moved(faces.DYADIC_BBOX, faces.SHIFT_128): faces.SHIFT_128,
+       _moved(faces.DYADIC_BBOX, faces.SHIFT_1024): faces.SHIFT_1024}
+FAR_SETS = [(faces.DYADIC_RES if s != faces.SHIFT_137 else 0.002, b) for b, s in FAR.items()]
 
 
 def _bits(a):
@@ -16,7 +30,7 @@ def _bits(a):
     (0.001, (-0.5, 0.5, -0.5, 0.5, 0.0, 1.0)),
     (0.0005, (-1.0, 1.0, -0.5, 0.5, 0.0, 1.0)),
     (0.001, (-1.25, 1.25, -1.0, 1.0, 0.0, 2.0)),  # config 5 grid: 2499 x 1999 x 1999
-])
+] + FAR_SETS)
 def test_transform_zclip_index_bbox_bit_exact(oracle_mod, hfpf_mod, synth_mod, res, bbox):
     rng = np.random.default_rng(11)
     n = 1 << 20
@@ -26,11 +40,14 @@ def test_transform_zclip_index_bbox_bit_exact(oracle_mod, hfpf_mod, synth_mod, r
     pts[1000:2000, 2] = np.float32(0.6)
     pts[2000:2100] = np.nan
     pts[2100:2200, 0] = np.inf
+    shift = np.asarray(FAR.get(bbox, (0.0, 0.0, 0.0)), np.float64)  # the pose's translation moves with the box
+    n_valid = 0
     og = oracle_mod.OracleGrid(resolution=res, bbox=bbox)
     with hfpf_mod.OccupancyGrid(resolution=res, bbox=bbox, **TINY) as g:
         assert g.dims == og.dims
         for f in range(3):
             T = synth_mod.pose(0x5E3, f)
+            T = np.hstack([T[:, :3], T[:, 3:] + shift.reshape(3, 1)])
             q, idx, flags = g.probe_points(T, pts)
             q_ref = oracle_mod.probe_transform(T, pts)
             assert np.array_equal(_bits(q), _bits(q_ref))
@@ -39,6 +56,8 @@ def test_transform_zclip_index_bbox_bit_exact(oracle_mod, hfpf_mod, synth_mod, r
             assert np.array_equal((flags & 2) != 0, valid_ref)
             z = pts[:, 2].astype(np.float64)
             assert np.array_equal((flags & 1) != 0, (z < 0.6) & (z > 0.28))
+            n_valid += int(valid_ref.sum())
+    assert n_valid > 10000 and (bbox not in FAR or n_valid < 3 * n // 2), "the points should land in and around the box"
 
 
 @pytest.mark.parametrize("res,bbox", [
@@ -46,7 +65,9 @@ def test_transform_zclip_index_bbox_bit_exact(oracle_mod, hfpf_mod, synth_mod, r
     (0.001, (-0.5, 0.5, -0.5, 0.5, 0.0, 1.0)),
     (0.0005, (-1.0, 1.0, -0.5, 0.5, 0.0, 1.0)),
     (0.001, (-1.25, 1.25, -1.0, 1.0, 0.0, 2.0)),
-])
+    # min = 0 and r = (float)0.003, for which r * (1 / r) rounds to 1 - 2^-53: at a = 2^j * r the fast product floors to 2^j - 1
+    (0.003, (0.0, 0.75, 0.0, 0.75, 0.0, 0.75)),
+] + FAR_SETS)
 def test_voxel_index_on_exact_cell_boundaries(oracle_mod, hfpf_mod, synth_mod, res, bbox):
     """The device computes the index as floor(a * (1/res)) and falls back to the exact IEEE division whenever that product is
     within 1e-6 of an integer (geometry.hpp voxel_axis).  Identity pose, coordinates ON the voxel boundaries of all three
@@ -55,10 +76,15 @@ def test_voxel_index_on_exact_cell_boundaries(oracle_mod, hfpf_mod, synth_mod, r
     r = float(np.float32(res))  # the grid stores (double)(float)resolution
     n_cells = 60000
     pts = []
+    n_fast_wrong = 0  # boundaries that are an f32 exactly and where floor(a * (1 / r)) is not floor(a / r): the fallback's own case
     for a in range(3):
         lo, hi = bbox[2 * a], bbox[2 * a + 1]
         k = rng.integers(0, int((hi - lo) / r) + 1, size=n_cells)
+        d = (lo + k * r).astype(np.float32).astype(np.float64) - lo
+        n_fast_wrong += int((np.floor(d * (1.0 / r)) != np.floor(d / r)).sum())
         edge = (lo + k * r).astype(np.float32)  # nearest f32 to the boundary
+        if res == faces.DYADIC_RES:
+            assert np.array_equal(edge.astype(np.float64), lo + k * r), "a dyadic boundary that is no f32"
         for step in range(-3, 4):
             c = edge.copy()
             for _ in range(abs(step)):
@@ -79,6 +105,9 @@ def test_voxel_index_on_exact_cell_boundaries(oracle_mod, hfpf_mod, synth_mod, r
         assert np.array_equal((flags & 2) != 0, valid_ref)
     # the construction really hits both sides of boundaries: neighbouring ulp steps must land in different cells somewhere
     assert len(np.unique(idx_ref[:, 0])) > 100
+    print("res %r: %d boundary values at which the fast product alone gives another cell" % (res, n_fast_wrong))
+    if res == 0.003:
+        assert n_fast_wrong >= 100
 
 
 def test_projection_membership_bit_exact(oracle_mod, hfpf_mod):
