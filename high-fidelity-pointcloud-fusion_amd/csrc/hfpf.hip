@@ -32,6 +32,7 @@
 #include "../../include/hfpf.h"
 #include "../../include/hfpf_probe.h"
 #include "kernels.hpp"
+#include "scratch_layout.hpp"
 
 using namespace hfpf;
 
@@ -450,6 +451,23 @@ int scratch(hfpf_handle* h, DevBuf& b, size_t bytes)
     HIPCHK(h, hipMalloc(&b.p, want));
     b.bytes = want;
     h->device_bytes += want;
+    return HFPF_OK;
+}
+
+template <typename T>  // one array of `count` T in b: the typed pointer, taken once, after the allocation
+int scratch_n(hfpf_handle* h, DevBuf& b, uint64_t count, T** out)
+{
+    const int rc = scratch(h, b, count * sizeof(T));
+    *out = rc ? nullptr : static_cast<T*>(b.p);
+    return rc;
+}
+
+// Several arrays in b (scratch_layout.hpp): one allocation of the layout's bytes, then every declared pointer is set.
+int scratch(hfpf_handle* h, DevBuf& b, const ScratchLayout& lay)
+{
+    if (!lay.fits()) return fail(h, HFPF_ERR_STATE, "a scratch layout declares too many arrays (internal)");
+    if (int rc = scratch(h, b, (size_t)lay.bytes())) return rc;
+    lay.place(b.p);
     return HFPF_OK;
 }
 
@@ -1433,15 +1451,22 @@ int import_gathered_locked(hfpf_handle* h, const void* dev_buffer, uint64_t slic
 // leave the collective sequence at the same point: the failed rank with its own error, the others with HFPF_ERR_DIST.  Without
 // it a rank that returns early (capacity overflow, poisoned handle, failed allocation) leaves its peers blocked in the next
 // ncclAllGather / ncclAllReduce for ever.  payloads_out (world entries, may be null) receives every rank's payload.
+// h->ex_counts: the status word of every rank, then this rank's own (what it sends into the gather).
+ScratchLayout ex_counts_layout(int world, unsigned long long** all, unsigned long long** mine)
+{
+    return ScratchLayout().add(all, (uint64_t)world).add(mine, 1);
+}
+
 int dist_status_gather_locked(hfpf_handle* h, int local_rc, uint64_t payload, const char* where, unsigned long long* payloads_out)
 {
     constexpr unsigned long long kFailBit = 1ull << 63;
     const std::string local_err = h->err;  // keep the text of the local failure: the calls below may overwrite it
-    unsigned long long* d_counts = (unsigned long long*)h->ex_counts.p;
-    if (!d_counts || !h->h_counts) return fail(h, HFPF_ERR_DIST, "%s: no status buffer (hfpf_dist_init did not complete)", where);
+    if (!h->ex_counts.p || !h->h_counts) return fail(h, HFPF_ERR_DIST, "%s: no status buffer (hfpf_dist_init did not complete)", where);
+    unsigned long long *d_counts, *d_mine;
+    ex_counts_layout(h->world, &d_counts, &d_mine).place(h->ex_counts.p);  // allocated by hfpf_dist_init alone, never grown
     h->h_counts[h->world] = (payload & ~kFailBit) | (local_rc ? kFailBit : 0ull);
-    HIPCHK(h, hipMemcpyAsync(d_counts + h->world, h->h_counts + h->world, 8, hipMemcpyHostToDevice, h->stream));
-    NCCLCHK(h, g_rccl.AllGather(d_counts + h->world, d_counts, 1, ncclUint64_, (ncclComm_t_)h->comm, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_mine, h->h_counts + h->world, 8, hipMemcpyHostToDevice, h->stream));
+    NCCLCHK(h, g_rccl.AllGather(d_mine, d_counts, 1, ncclUint64_, (ncclComm_t_)h->comm, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->h_counts, d_counts, (size_t)h->world * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     int failed_rank = -1;
@@ -2253,31 +2278,36 @@ int hfpf_clean(hfpf_handle* h)
     return rc;
 }
 
-// First half of extract (and of a render): the row set of `opt` built on the device into h->rows_dev, row j = the j-th in
-// lexicographic (x, y, z) order; *n_out rows.  `stats` are the (possibly merged) sums to finalise.
-static int build_rows_locked(hfpf_handle* h, const unsigned long long* stats, const ExtractOpts& opt, uint64_t* n_out)
+// The row set of a read-out.  rows live in h->rows_dev.  record_of_row (row -> id of its normal record) lives in h->vals_b, the
+// output of the row sort: it is dead as soon as the caller sorts through the handle's sort buffers (keys_a/b, vals_a/b) again.
+struct RowSet {
+    const Row* rows = nullptr;
+    const uint32_t* record_of_row = nullptr;
+    uint64_t n = 0;
+};
+
+// First half of extract (and of a render): the row set of `opt` built on the device, row j = the j-th in lexicographic (x, y, z)
+// order.  `stats` are the (possibly merged) sums to finalise.
+static int build_rows_locked(hfpf_handle* h, const unsigned long long* stats, const ExtractOpts& opt, RowSet* out)
 {
     Tables& t = h->t;
     int rc;
-    *n_out = 0;
+    *out = RowSet{};
     const uint64_t n = h->h_ctr[C_NORMALS];
     if (n == 0) return HFPF_OK;
-    if ((rc = scratch(h, h->keys_a, n * 8))) return rc;
-    if ((rc = scratch(h, h->keys_b, n * 8))) return rc;
-    if ((rc = scratch(h, h->vals_a, n * 4))) return rc;
-    if ((rc = scratch(h, h->vals_b, n * 4))) return rc;
+    uint64_t *keys_in, *keys_out; if ((rc = scratch_n(h, h->keys_a, n, &keys_in)) || (rc = scratch_n(h, h->keys_b, n, &keys_out))) return rc;
+    uint32_t *vals_in, *vals_out; if ((rc = scratch_n(h, h->vals_a, n, &vals_in)) || (rc = scratch_n(h, h->vals_b, n, &vals_out))) return rc;
     hipLaunchKernelGGL(k_set_ctr, dim3(1), dim3(1), 0, h->stream, t.ctr, (int)C_ROWS, 0ull);
-    hipLaunchKernelGGL(k_extract_keys, dim3(blocks_for(n, 256 * kExtractTiles)), dim3(256), 0, h->stream, h->g, t, stats, n, opt, (uint64_t*)h->keys_a.p, (uint32_t*)h->vals_a.p);
+    hipLaunchKernelGGL(k_extract_keys, dim3(blocks_for(n, 256 * kExtractTiles)), dim3(256), 0, h->stream, h->g, t, stats, n, opt, keys_in, vals_in);
     HIPCHK(h, hipGetLastError());
-    if ((rc = sort_pairs_u64(h, (uint64_t*)h->keys_a.p, (uint64_t*)h->keys_b.p, (uint32_t*)h->vals_a.p, (uint32_t*)h->vals_b.p, n))) return rc;
+    if ((rc = sort_pairs_u64(h, keys_in, keys_out, vals_in, vals_out, n))) return rc;
     if ((rc = read_counters(h))) return rc;
     const uint64_t nr = h->h_ctr[C_ROWS];
     if (nr == 0) return HFPF_OK;
-    if ((rc = scratch(h, h->rows_dev, nr * sizeof(Row)))) return rc;
-    hipLaunchKernelGGL(k_extract_rows, dim3(blocks_for(nr, 256)), dim3(256), 0, h->stream, h->g, t, stats, nr, opt, (const uint64_t*)h->keys_b.p,
-                       (const uint32_t*)h->vals_b.p, (Row*)h->rows_dev.p);
+    Row* rows; if ((rc = scratch_n(h, h->rows_dev, nr, &rows))) return rc;
+    hipLaunchKernelGGL(k_extract_rows, dim3(blocks_for(nr, 256)), dim3(256), 0, h->stream, h->g, t, stats, nr, opt, keys_out, vals_out, rows);
     HIPCHK(h, hipGetLastError());
-    *n_out = nr;
+    *out = RowSet{rows, vals_out, nr};
     return HFPF_OK;
 }
 
@@ -2335,14 +2365,21 @@ struct ResultSet {
     };
     Array a[3];
     int n = 0;
-    bool owned = false;  // device form: the arrays are allocations of their own, the caller's once the call succeeds
-    void add(size_t bytes, bool absent = false, const void* borrow = nullptr) { a[n++] = Array{bytes, absent, borrow, nullptr}; }
-    void release()  // error paths of the device form
+    bool owned = false;  // device form: the arrays are allocations of their own, and this set frees them unless it hands them over
+    ResultSet() = default;
+    ResultSet(const ResultSet&) = delete;
+    ResultSet& operator=(const ResultSet&) = delete;
+    ~ResultSet()  // every error exit behind result_alloc
     {
-        for (Array& x : a) {
-            if (owned) (void)hipFree(x.dev);
-            x.dev = nullptr;
-        }
+        for (Array& x : a)
+            if (owned && x.dev) (void)hipFree(x.dev);
+    }
+    void add(size_t bytes, bool absent = false, const void* borrow = nullptr) { a[n++] = Array{bytes, absent, borrow, nullptr}; }
+    void keep(ResultSet* to)  // the success exit: the arrays go to *to, which describes them and frees nothing
+    {
+        for (int i = 0; i < 3; i++) to->a[i] = a[i];
+        to->n = n;
+        owned = false;
     }
 };
 
@@ -2356,20 +2393,18 @@ static int result_alloc(hfpf_handle* h, ResultSet& set, bool on_device, const ch
             if (set.a[i].absent) continue;
             const hipError_t e = hipMalloc(&set.a[i].dev, set.a[i].bytes);
             if (e == hipSuccess) continue;
-            set.release();
             return fail(h, HFPF_ERR_HIP, "%s: device allocation of %llu bytes failed: %s", what, (unsigned long long)set.a[i].bytes, hipGetErrorString(e));
         }
         return HFPF_OK;
     }
-    size_t off[3] = {0, 0, 0}, total = 0;
-    for (int i = 0; i < set.n; i++) {
-        off[i] = total;
-        if (!set.a[i].absent && !set.a[i].borrow) total += (set.a[i].bytes + 15) & ~(size_t)15;
-    }
-    if (total)
-        if (int rc = scratch(h, h->result_out, total)) return rc;
+    ScratchLayout lay;
+    uint8_t* slice[3] = {nullptr, nullptr, nullptr};
     for (int i = 0; i < set.n; i++)
-        if (!set.a[i].absent) set.a[i].dev = set.a[i].borrow ? const_cast<void*>(set.a[i].borrow) : (char*)h->result_out.p + off[i];
+        if (!set.a[i].absent && !set.a[i].borrow) lay.add(&slice[i], set.a[i].bytes, 16);
+    if (lay.bytes())
+        if (int rc = scratch(h, h->result_out, lay)) return rc;
+    for (int i = 0; i < set.n; i++)
+        if (!set.a[i].absent) set.a[i].dev = set.a[i].borrow ? const_cast<void*>(set.a[i].borrow) : slice[i];
     return HFPF_OK;
 }
 
@@ -2403,16 +2438,16 @@ static int extract_locked(hfpf_handle* h, const unsigned long long* stats, const
         opt.classify_threshold = o->classify_threshold;
         opt.paint_white = o->paint_white ? 1 : 0;
     }
-    uint64_t nr = 0;
+    RowSet rs;
     int rc;
-    if ((rc = build_rows_locked(h, stats, opt, &nr))) return rc;
-    if (nr == 0) return HFPF_OK;
+    if ((rc = build_rows_locked(h, stats, opt, &rs))) return rc;
+    if (rs.n == 0) return HFPF_OK;
     ResultSet set;
-    set.add(nr * sizeof(Row), false, h->rows_dev.p);
+    set.add(rs.n * sizeof(Row), false, rs.rows);
     void* host[3];
     if ((rc = result_alloc(h, set, false, "extract")) || (rc = result_to_host(h, set, "extract", host))) return rc;
     *rows = (hfpf_row*)host[0];
-    *n_rows = nr;
+    *n_rows = rs.n;
     return HFPF_OK;
 }
 
@@ -2438,15 +2473,16 @@ int hfpf_extract_filtered(hfpf_handle* h, const hfpf_extract_opts* opts, hfpf_ro
         // against an extract that sorts and downloads the same records; a list of touched records would need a second collective.
         const uint64_t n_mine = h->h_ctr[C_NORMALS];
         const uint64_t words = (n_mine + 1) * kStatWords;
-        if (!rc) rc = scratch(h, h->stats_total, words * 8);
+        unsigned long long* total = nullptr;
+        if (!rc) rc = scratch_n(h, h->stats_total, words, &total);
         std::vector<unsigned long long> n_of(h->world, 0ull);
         if ((rc = dist_status_gather_locked(h, rc, n_mine, "statistics all-reduce of extract", n_of.data()))) return rc;
         for (int r = 0; r < h->world; r++)  // every rank sees the same payloads, so all of them take this exit or none does
             if (n_of[r] != n_of[0])
                 return fail(h, HFPF_ERR_DIST, "rank %d holds %llu normal records, rank 0 %llu: the ranks did not run the same clean schedule", r,
                             (unsigned long long)n_of[r], (unsigned long long)n_of[0]);
-        NCCLCHK(h, g_rccl.AllReduce(t.stats, h->stats_total.p, words, ncclUint64_, ncclSum_, (ncclComm_t_)h->comm, h->stream));
-        stats = (const unsigned long long*)h->stats_total.p;
+        NCCLCHK(h, g_rccl.AllReduce(t.stats, total, words, ncclUint64_, ncclSum_, (ncclComm_t_)h->comm, h->stream));
+        stats = total;
     }
     return extract_locked(h, stats, opts, rows, n_rows);
 }
@@ -2494,22 +2530,24 @@ static int local_read_prologue_locked(hfpf_handle* h, const char* what = "render
 // The views of a render (or the model view of a track): the row set, the z-buffer scratch of one chunk of views, the poses on the
 // device and the splat's parameters.
 struct RenderViews {
-    uint64_t n_rows;
+    RowSet rows;
+    unsigned long long* zbuf;  // per_chunk z-buffers
+    double* pose_d;            // n_views poses
     uint32_t n_views, per_chunk;
     RenderParams p;
 };
 static int render_views_locked(hfpf_handle* h, const hfpf_render_opts* o, uint32_t n_views, const double* poses, RenderViews* rv)
 {
     int rc;
-    uint64_t nr = 0;
     const ExtractOpts opt{std::max(1.0, o->min_count), -1, 0};  // count >= max(1, min_count), the compare of k_extract_keys
-    if ((rc = build_rows_locked(h, h->t.stats, opt, &nr))) return rc;
+    if ((rc = build_rows_locked(h, h->t.stats, opt, &rv->rows))) return rc;
+    const uint64_t nr = rv->rows.n;
     if (nr > 0xFFFFFFFFull) return fail(h, HFPF_ERR_CAPACITY, "render: %llu rows do not fit the 32-bit row field of a z-buffer word", (unsigned long long)nr);
     const uint64_t WH = (uint64_t)o->width * o->height;
     const uint32_t per_chunk = (uint32_t)std::min<uint64_t>({(uint64_t)kRenderChunkViews, std::max<uint64_t>(1, kRenderZbufBytes / (8 * WH)), n_views});
-    if ((rc = scratch(h, h->zbuf, per_chunk * WH * 8))) return rc;
-    if ((rc = scratch(h, h->render_pose, (size_t)n_views * 12 * sizeof(double)))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->render_pose.p, poses, (size_t)n_views * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if ((rc = scratch_n(h, h->zbuf, per_chunk * WH, &rv->zbuf))) return rc;
+    if ((rc = scratch_n(h, h->render_pose, 12ull * n_views, &rv->pose_d))) return rc;
+    HIPCHK(h, hipMemcpyAsync(rv->pose_d, poses, (size_t)n_views * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     RenderParams& p = rv->p;
     p = RenderParams{};
     p.width = o->width;
@@ -2520,7 +2558,6 @@ static int render_views_locked(hfpf_handle* h, const hfpf_render_opts* o, uint32
     p.max_radius = o->max_splat_radius;
     p.fx = o->fx, p.fy = o->fy, p.cx = o->cx, p.cy = o->cy, p.z_near = o->z_near, p.z_far = o->z_far;
     p.r_num = (0.5 * h->g.res) * std::max(o->fx, o->fy);
-    rv->n_rows = nr;
     rv->n_views = n_views;
     rv->per_chunk = per_chunk;
     return HFPF_OK;
@@ -2532,11 +2569,10 @@ static int render_splat_locked(hfpf_handle* h, RenderViews* rv, uint32_t v0)
     RenderParams& p = rv->p;
     p.n_views = std::min(rv->per_chunk, rv->n_views - v0);
     const uint64_t pix = p.n_views * (uint64_t)p.width * p.height;
-    const double* pose_d = (const double*)h->render_pose.p + 12ull * v0;
-    HIPCHK(h, hipMemsetAsync(h->zbuf.p, 0xFF, pix * 8, h->stream));
-    if (rv->n_rows)
-        hipLaunchKernelGGL(k_render_splat, dim3(blocks_for(rv->n_rows, 256)), dim3(256), 0, h->stream, (const Row*)h->rows_dev.p, (uint32_t)rv->n_rows,
-                           pose_d, p, (unsigned long long*)h->zbuf.p);
+    HIPCHK(h, hipMemsetAsync(rv->zbuf, 0xFF, pix * 8, h->stream));
+    if (rv->rows.n)
+        hipLaunchKernelGGL(k_render_splat, dim3(blocks_for(rv->rows.n, 256)), dim3(256), 0, h->stream, rv->rows.rows, (uint32_t)rv->rows.n,
+                           rv->pose_d + 12ull * v0, p, rv->zbuf);
     HIPCHK(h, hipGetLastError());
     return HFPF_OK;
 }
@@ -2547,15 +2583,13 @@ static int render_locked(hfpf_handle* h, const hfpf_render_opts* o, uint32_t n_v
     RenderViews rv;
     if (int rc = render_views_locked(h, o, n_views, poses, &rv)) return rc;
     const uint64_t WH = (uint64_t)o->width * o->height;
-    const Row* rows = (const Row*)h->rows_dev.p;
     for (uint32_t v0 = 0; v0 < n_views; v0 += rv.per_chunk) {
         if (int rc = render_splat_locked(h, &rv, v0)) return rc;
         const RenderParams& p = rv.p;
         const uint64_t pix = p.n_views * WH, off = v0 * WH;
-        const double* pose_d = (const double*)h->render_pose.p + 12ull * v0;
         const RenderPlanes pl{dev.depth ? dev.depth + off : nullptr, dev.normal ? dev.normal + 3 * off : nullptr, dev.rgb ? dev.rgb + off : nullptr,
                               dev.count ? dev.count + off : nullptr, dev.voxel ? dev.voxel + 3 * off : nullptr};
-        hipLaunchKernelGGL(k_render_resolve, dim3(blocks_for(pix, 256)), dim3(256), 0, h->stream, rows, (const unsigned long long*)h->zbuf.p, pose_d, p, pl);
+        hipLaunchKernelGGL(k_render_resolve, dim3(blocks_for(pix, 256)), dim3(256), 0, h->stream, rv.rows.rows, rv.zbuf, rv.pose_d + 12ull * v0, p, pl);
         HIPCHK(h, hipGetLastError());
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2583,19 +2617,19 @@ int hfpf_render(hfpf_handle* h, const hfpf_render_opts* o, const double pose_3x4
     const uint64_t WH = (uint64_t)o->width * o->height;
     void* host[5] = {host_out->depth, host_out->normal, host_out->rgb, host_out->count, host_out->voxel};
     const uint64_t bytes[5] = {4 * WH, 12 * WH, 4 * WH, 4 * WH, 12 * WH};
-    uint64_t off[5], total = 0;
-    for (int k = 0; k < 5; k++) {
-        off[k] = total;
-        if (host[k]) total += (bytes[k] + 255) & ~255ull;
-    }
-    if (int rc = scratch(h, h->render_out, total)) return rc;
-    char* base = (char*)h->render_out.p;
-    auto at = [&](int k) -> void* { return host[k] ? base + off[k] : nullptr; };
-    const hfpf_render_planes dev{(float*)at(0), (float*)at(1), (uint32_t*)at(2), (uint32_t*)at(3), (int32_t*)at(4)};
+    hfpf_render_planes dev{};
+    ScratchLayout lay;
+    if (host[0]) lay.add(&dev.depth, WH, 256);
+    if (host[1]) lay.add(&dev.normal, 3 * WH, 256);
+    if (host[2]) lay.add(&dev.rgb, WH, 256);
+    if (host[3]) lay.add(&dev.count, WH, 256);
+    if (host[4]) lay.add(&dev.voxel, 3 * WH, 256);
+    if (int rc = scratch(h, h->render_out, lay)) return rc;
     if (int rc = render_locked(h, o, 1, pose_3x4, dev)) return rc;
+    const void* plane[5] = {dev.depth, dev.normal, dev.rgb, dev.count, dev.voxel};
     for (int k = 0; k < 5; k++) {
         if (!host[k]) continue;
-        const hipError_t e = download_pageable(h, host[k], base + off[k], bytes[k], 0);  // every plane through the pinned buffers
+        const hipError_t e = download_pageable(h, host[k], plane[k], bytes[k], 0);  // every plane through the pinned buffers
         if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "render copy: %s", hipGetErrorString(e));
     }
     return HFPF_OK;
@@ -2748,8 +2782,7 @@ extern "C++" template <typename Opts, typename Enqueue, typename Res>
 static int refine_pose(hfpf_handle* h, const Opts* o, const double c[3], int n_terms, const double pose[12], Enqueue&& enqueue, Res* res, uint64_t* word29)
 {
     const size_t bytes = (size_t)n_terms * sizeof(unsigned long long);
-    if (int rc = scratch(h, h->icp_acc, bytes)) return rc;
-    unsigned long long* acc = (unsigned long long*)h->icp_acc.p;
+    unsigned long long* acc; if (int rc = scratch_n(h, h->icp_acc, (uint64_t)n_terms, &acc)) return rc;
     unsigned long long local[kTrackTerms];
     unsigned long long* back = h->xfer_pin[0] ? (unsigned long long*)h->xfer_pin[0] : local;  // the read-back of the sums
     double T[12], A[6][6] = {}, rr = 0.0;
@@ -2809,10 +2842,10 @@ static int track_locked(hfpf_handle* h, const hfpf_track_opts* o, const PointSou
     if ((rc = local_read_prologue_locked(h, "track"))) return rc;
     const uint8_t* frame = (const uint8_t*)f.dev;
     if (f.host) {  // one copy per call, through the pinned buffers
-        if ((rc = scratch(h, h->track_in, f.bytes(f.n)))) return rc;
-        const hipError_t e = upload_pageable(h, h->track_in.p, f.host, f.bytes(f.n));
+        uint8_t* staged; if ((rc = scratch_n(h, h->track_in, f.bytes(f.n), &staged))) return rc;
+        const hipError_t e = upload_pageable(h, staged, f.host, f.bytes(f.n));
         if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "track upload: %s", hipGetErrorString(e));
-        frame = (const uint8_t*)h->track_in.p;
+        frame = staged;
     }
     RenderViews rv;
     if ((rc = render_views_locked(h, &o->view, 1, pose, &rv))) return rc;
@@ -2832,8 +2865,8 @@ static int track_locked(hfpf_handle* h, const hfpf_track_opts* o, const PointSou
     const int form = f.form(frame);
     const DepthLayout dl = depth_layout(f.ds, nullptr, 0);
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(kTrackMaxBlocks, blocks_for(n_samples, 256));
-    const Row* rows = (const Row*)h->rows_dev.p;
-    const unsigned long long* zb = (const unsigned long long*)h->zbuf.p;
+    const Row* rows = rv.rows.rows;
+    const unsigned long long* zb = rv.zbuf;
     uint64_t used = 0;
     rc = refine_pose(h, o, c, kTrackTerms, pose, [&](const double* T, unsigned long long* acc) -> int {
         memcpy(p.T, T, sizeof p.T);
@@ -2929,23 +2962,24 @@ static int query_locked(hfpf_handle* h, const hfpf_query_opts* o, const PointSou
         return HFPF_OK;
     }
     const uint32_t chunk = std::min(f.n, kQueryChunk);
-    if ((rc = scratch(h, h->query_out, (size_t)chunk * (sizeof(QueryHit) + (rows ? sizeof(Row) : 0))))) return rc;
-    QueryHit* dh = (QueryHit*)h->query_out.p;
-    Row* dr = rows ? (Row*)((char*)h->query_out.p + (size_t)chunk * sizeof(QueryHit)) : nullptr;
-    if ((rc = scratch(h, h->query_in, f.bytes(chunk)))) return rc;
+    QueryHit* dh; Row* dr = nullptr;
+    ScratchLayout out = ScratchLayout().add(&dh, chunk);
+    if (rows) out.add(&dr, chunk);
+    if ((rc = scratch(h, h->query_out, out))) return rc;
+    uint8_t* in; if ((rc = scratch_n(h, h->query_in, f.bytes(chunk), &in))) return rc;
     if (f.depth) {  // the whole image once; the chunks index into it
-        const hipError_t e = upload_pageable(h, h->query_in.p, f.host, f.bytes(f.n));
+        const hipError_t e = upload_pageable(h, in, f.host, f.bytes(f.n));
         if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "query upload: %s", hipGetErrorString(e));
     }
     for (uint64_t first = 0; first < f.n; first += chunk) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, f.n - first);
         uint64_t k_first = first;
         if (!f.depth) {  // this chunk's records
-            const hipError_t e = upload_pageable(h, h->query_in.p, (const uint8_t*)f.host + first * f.lay.point_step, f.bytes(n));
+            const hipError_t e = upload_pageable(h, in, (const uint8_t*)f.host + first * f.lay.point_step, f.bytes(n));
             if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "query upload: %s", hipGetErrorString(e));
             k_first = 0;
         }
-        if ((rc = launch((const uint8_t*)h->query_in.p, k_first, n, dh, dr))) return rc;
+        if ((rc = launch(in, k_first, n, dh, dr))) return rc;
         hipError_t e = download_pageable(h, hits + first, dh, (size_t)n * sizeof(QueryHit), 0);
         if (e == hipSuccess && rows) e = download_pageable(h, rows + first, dr, (size_t)n * sizeof(Row), 0);
         if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "query download: %s", hipGetErrorString(e));
@@ -3033,29 +3067,22 @@ static int ray_setup_locked(hfpf_handle* h, const hfpf_raycast_opts* o, uint32_t
     p->n_samples = n_samples;
     p->radius = o->radius;
     p->cull = (o->flags & HFPF_RAYCAST_CULL_BACKFACES) ? 1u : 0u;
-    uint64_t cells[kRayLevels], total = 0;
+    uint64_t cells[kRayLevels];
     for (int l = 0; l < kRayLevels; l++) {
         for (int a = 0; a < 3; a++) p->mdim[l][a] = l == 0 ? h->g.bdim[a] : (p->mdim[l - 1][a] + 3) / 4;
         cells[l] = (uint64_t)p->mdim[l][0] * p->mdim[l][1] * p->mdim[l][2];
-        total += (cells[l] + 255) & ~255ull;
     }
     if (cells[0] > 0xFFFFFFFFull) return fail(h, HFPF_ERR_CAPACITY, "raycast: %llu directory entries exceed the 32-bit map index", (unsigned long long)cells[0]);
-    const uint64_t has_bytes = (cells[0] + 255) & ~255ull;
-    if (int rc = scratch(h, h->ray_map, has_bytes + total)) return rc;
-    uint8_t* has = (uint8_t*)h->ray_map.p;
-    uint8_t* m = has + has_bytes;
-    uint8_t* maps[kRayLevels];
-    for (int l = 0; l < kRayLevels; l++) {
-        maps[l] = m;
-        p->map[l] = m;
-        m += (cells[l] + 255) & ~255ull;
-    }
+    uint8_t *has, *maps[kRayLevels];
+    ScratchLayout lay = ScratchLayout().add(&has, cells[0], 256);  // every map in whole 256-byte lines
+    for (int l = 0; l < kRayLevels; l++) lay.add(&maps[l], cells[l], 256);
+    if (int rc = scratch(h, h->ray_map, lay)) return rc;
+    for (int l = 0; l < kRayLevels; l++) p->map[l] = maps[l];
     hipLaunchKernelGGL(k_ray_map_bricks, dim3(blocks_for(cells[0], 256)), dim3(256), 0, h->stream, h->t, (uint32_t)cells[0], has);
-    hipLaunchKernelGGL(k_ray_map_dilate, dim3(blocks_for(cells[0], 256)), dim3(256), 0, h->stream, (const uint8_t*)has, p->mdim[0][0], p->mdim[0][1],
-                       p->mdim[0][2], maps[0]);
+    hipLaunchKernelGGL(k_ray_map_dilate, dim3(blocks_for(cells[0], 256)), dim3(256), 0, h->stream, has, p->mdim[0][0], p->mdim[0][1], p->mdim[0][2], maps[0]);
     for (int l = 1; l < kRayLevels; l++)
-        hipLaunchKernelGGL(k_ray_map_up, dim3(blocks_for(cells[l], 256)), dim3(256), 0, h->stream, (const uint8_t*)maps[l - 1], p->mdim[l - 1][0],
-                           p->mdim[l - 1][1], p->mdim[l - 1][2], p->mdim[l][0], p->mdim[l][1], p->mdim[l][2], maps[l]);
+        hipLaunchKernelGGL(k_ray_map_up, dim3(blocks_for(cells[l], 256)), dim3(256), 0, h->stream, maps[l - 1], p->mdim[l - 1][0], p->mdim[l - 1][1],
+                           p->mdim[l - 1][2], p->mdim[l][0], p->mdim[l][1], p->mdim[l][2], maps[l]);
     HIPCHK(h, hipGetLastError());
     return HFPF_OK;
 }
@@ -3088,14 +3115,13 @@ static int raycast_common(hfpf_handle* h, const hfpf_raycast_opts* o, const hfpf
         return HFPF_OK;
     }
     const uint64_t chunk = std::min(n_rays, kRayChunk);
-    if ((rc = scratch(h, h->ray_in, chunk * sizeof(hfpf_ray)))) return rc;
-    if ((rc = scratch(h, h->ray_out, chunk * sizeof(RayHit)))) return rc;
+    hfpf_ray* d_rays; RayHit* d_hits; if ((rc = scratch_n(h, h->ray_in, chunk, &d_rays)) || (rc = scratch_n(h, h->ray_out, chunk, &d_hits))) return rc;
     for (uint64_t first = 0; first < n_rays; first += chunk) {
         const uint64_t n = std::min(chunk, n_rays - first);
-        hipError_t e = upload_pageable(h, h->ray_in.p, rays + first, n * sizeof(hfpf_ray));
+        hipError_t e = upload_pageable(h, d_rays, rays + first, n * sizeof(hfpf_ray));
         if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "raycast upload: %s", hipGetErrorString(e));
-        if ((rc = launch((const hfpf_ray*)h->ray_in.p, n, (hfpf_ray_hit*)h->ray_out.p))) return rc;
-        e = download_pageable(h, hits + first, h->ray_out.p, n * sizeof(RayHit), 0);
+        if ((rc = launch(d_rays, n, (hfpf_ray_hit*)d_hits))) return rc;
+        e = download_pageable(h, hits + first, d_hits, n * sizeof(RayHit), 0);
         if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "raycast download: %s", hipGetErrorString(e));
     }
     return HFPF_OK;
@@ -3135,16 +3161,15 @@ static int raycast_view_common(hfpf_handle* h, const hfpf_raycast_opts* o, uint3
     p.fx = fx, p.fy = fy, p.cx = cx, p.cy = cy;
     p.width = width;
     p.view_stride = WH;
-    if ((rc = scratch(h, h->render_pose, (size_t)n_views * 12 * sizeof(double)))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->render_pose.p, poses, (size_t)n_views * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    double* pose_d; if ((rc = scratch_n(h, h->render_pose, 12ull * n_views, &pose_d))) return rc;
+    HIPCHK(h, hipMemcpyAsync(pose_d, poses, (size_t)n_views * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     const uint64_t tiles_x = (width + 7ull) / 8;
     auto launch = [&](uint32_t v0, uint32_t nv, uint32_t row0, uint32_t rows, RayHit* dh) -> int {
         p.row0 = row0;
         p.rows = rows;
         const uint64_t tiles = tiles_x * ((rows + 7ull) / 8);
         return timed_launch(h, kTimeRaycast, [&] {
-            hipLaunchKernelGGL(k_raycast_view, dim3(blocks_for(tiles * 64, 256), nv), dim3(256), 0, h->stream, h->g, h->t, p,
-                               (const double*)h->render_pose.p + 12ull * v0, dh);
+            hipLaunchKernelGGL(k_raycast_view, dim3(blocks_for(tiles * 64, 256), nv), dim3(256), 0, h->stream, h->g, h->t, p, pose_d + 12ull * v0, dh);
         });
     };
     if (on_device) {
@@ -3154,11 +3179,11 @@ static int raycast_view_common(hfpf_handle* h, const hfpf_raycast_opts* o, uint3
         return HFPF_OK;
     }
     const uint32_t band = (uint32_t)std::min<uint64_t>(height, std::max<uint64_t>(8, (kRayChunk / width) & ~7ull));
-    if ((rc = scratch(h, h->ray_out, (uint64_t)band * width * sizeof(RayHit)))) return rc;
+    RayHit* d_hits; if ((rc = scratch_n(h, h->ray_out, (uint64_t)band * width, &d_hits))) return rc;
     for (uint32_t row0 = 0; row0 < height; row0 += band) {
         const uint32_t rows = std::min(band, height - row0);
-        if ((rc = launch(0, 1, row0, rows, (RayHit*)h->ray_out.p))) return rc;
-        const hipError_t e = download_pageable(h, hits + (uint64_t)row0 * width, h->ray_out.p, (uint64_t)rows * width * sizeof(RayHit), 0);
+        if ((rc = launch(0, 1, row0, rows, d_hits))) return rc;
+        const hipError_t e = download_pageable(h, hits + (uint64_t)row0 * width, d_hits, (uint64_t)rows * width * sizeof(RayHit), 0);
         if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "raycast download: %s", hipGetErrorString(e));
     }
     return HFPF_OK;
@@ -3185,23 +3210,29 @@ int hfpf_check_mesh_opts(const hfpf_mesh_opts* o)
 }
 static bool mesh_opts_ok(const hfpf_mesh_opts* o) { return hfpf_check_mesh_opts(o) == HFPF_OK; }
 
-// One 1-D dilation of the sorted unique keys in[0, n_in): k_mesh_dilate into keys_a, sort into keys_b, unique into out.  in may be
-// out: scratch() synchronises before it reallocates, and the dilation has read in by then.
-static int mesh_dilate_locked(hfpf_handle* h, DevBuf& in, uint64_t n_in, int axis, int lo, int hi, int32_t lim, DevBuf& out, uint64_t* n_out)
+// h->mesh_ctr: the count a unique pass leaves, and behind it the word a corner lookup that misses sets (a broken invariant).
+static int mesh_ctr_locked(hfpf_handle* h, uint64_t** n_unique, uint32_t** miss)
+{
+    return scratch(h, h->mesh_ctr, ScratchLayout().add(n_unique, 1).add(miss, 2));
+}
+
+// One 1-D dilation of the sorted unique keys in[0, n_in): k_mesh_dilate into keys_a, sort into keys_b, unique into out (*out_keys).
+// in may be out, and is therefore the one buffer read here through the pointer of an earlier allocation: the dilation that reads it
+// is enqueued before scratch() of out, which synchronises before it reallocates.
+static int mesh_dilate_locked(hfpf_handle* h, const DevBuf& in, uint64_t n_in, int axis, int lo, int hi, int32_t lim, DevBuf& out, const uint64_t** out_keys, uint64_t* n_out)
 {
     const uint64_t n = n_in * (uint64_t)(hi - lo + 1);
     int rc;
-    if ((rc = scratch(h, h->keys_a, n * 8))) return rc;
-    if ((rc = scratch(h, h->keys_b, n * 8))) return rc;
-    hipLaunchKernelGGL(k_mesh_dilate, dim3(blocks_for(n_in, 256)), dim3(256), 0, h->stream, (const uint64_t*)in.p, n_in, axis, lo, hi, lim,
-                       (uint64_t*)h->keys_a.p);
+    uint64_t *dilated, *sorted, *unique, *n_unique; uint32_t* miss;
+    if ((rc = scratch_n(h, h->keys_a, n, &dilated)) || (rc = scratch_n(h, h->keys_b, n, &sorted))) return rc;
+    hipLaunchKernelGGL(k_mesh_dilate, dim3(blocks_for(n_in, 256)), dim3(256), 0, h->stream, static_cast<const uint64_t*>(in.p), n_in, axis, lo, hi, lim, dilated);
     HIPCHK(h, hipGetLastError());
     unsigned xbits = 0;  // x <= dim[0]: the keys are below 2^(42 + xbits)
     while ((uint32_t)h->g.dim[0] >> xbits) xbits++;
-    if ((rc = sort_keys_u64(h, (uint64_t*)h->keys_a.p, (uint64_t*)h->keys_b.p, n, 2 * kMeshKeyBits + xbits))) return rc;
-    if ((rc = scratch(h, out, n * 8))) return rc;
-    if ((rc = scratch(h, h->mesh_ctr, 16))) return rc;
-    return unique_keys_locked(h, (const uint64_t*)h->keys_b.p, n, (uint64_t*)out.p, (uint64_t*)h->mesh_ctr.p, n_out);
+    if ((rc = sort_keys_u64(h, dilated, sorted, n, 2 * kMeshKeyBits + xbits))) return rc;
+    if ((rc = scratch_n(h, out, n, &unique)) || (rc = mesh_ctr_locked(h, &n_unique, &miss))) return rc;
+    *out_keys = unique;
+    return unique_keys_locked(h, sorted, n, unique, n_unique, n_out);
 }
 
 // Validated arguments in, under the lock.  The row set, the cube set (the rows' cells dilated by 1) and the corner set (the cubes
@@ -3209,51 +3240,46 @@ static int mesh_dilate_locked(hfpf_handle* h, DevBuf& in, uint64_t n_in, int axi
 // arrays (*out: vertices, triangles).  The read-backs are the sizes between the stages.
 static int mesh_locked(hfpf_handle* h, const hfpf_mesh_opts* o, bool on_device, ResultSet* out, uint64_t* n_verts, uint64_t* n_tris)
 {
-    *out = ResultSet{}, *n_verts = 0, *n_tris = 0;
+    *n_verts = 0, *n_tris = 0;  // (*out: the caller's fresh, empty set)
     int rc;
     if ((rc = local_read_prologue_locked(h, "mesh"))) return rc;
     for (int a = 0; a < 3; a++)
         if (h->g.dim[a] >= (1 << kMeshKeyBits) - 1) return fail(h, HFPF_ERR_CAPACITY, "mesh: a grid dimension of 2^21 - 1 cells or more");
-    uint64_t nr = 0;
+    RowSet rs;
     const ExtractOpts opt{std::max(1.0, o->min_count), -1, 0};  // count >= max(1, min_count), the compare of k_extract_keys
-    if ((rc = build_rows_locked(h, h->t.stats, opt, &nr))) return rc;
+    if ((rc = build_rows_locked(h, h->t.stats, opt, &rs))) return rc;
+    const uint64_t nr = rs.n;
     if (nr == 0) return HFPF_OK;
-    if ((rc = scratch(h, h->mesh_cube, nr * 8))) return rc;
-    hipLaunchKernelGGL(k_mesh_row_keys, dim3(blocks_for(nr, 256)), dim3(256), 0, h->stream, (const Row*)h->rows_dev.p, nr, (uint64_t*)h->mesh_cube.p);
+    uint64_t* row_keys; if ((rc = scratch_n(h, h->mesh_cube, nr, &row_keys))) return rc;
+    hipLaunchKernelGGL(k_mesh_row_keys, dim3(blocks_for(nr, 256)), dim3(256), 0, h->stream, rs.rows, nr, row_keys);
     HIPCHK(h, hipGetLastError());
     uint64_t n = nr;
+    const uint64_t *cubes = nullptr, *corners = nullptr;
     for (int a = 0; a < 3; a++)
-        if ((rc = mesh_dilate_locked(h, h->mesh_cube, n, a, -1, 1, h->g.dim[a] - 1, h->mesh_cube, &n))) return rc;
+        if ((rc = mesh_dilate_locked(h, h->mesh_cube, n, a, -1, 1, h->g.dim[a] - 1, h->mesh_cube, &cubes, &n))) return rc;
     const uint64_t nc = n;
     for (int a = 0; a < 3; a++)
-        if ((rc = mesh_dilate_locked(h, a == 0 ? h->mesh_cube : h->mesh_corner, n, a, 0, 1, h->g.dim[a], h->mesh_corner, &n))) return rc;
+        if ((rc = mesh_dilate_locked(h, a == 0 ? h->mesh_cube : h->mesh_corner, n, a, 0, 1, h->g.dim[a], h->mesh_corner, &corners, &n))) return rc;
     const uint64_t nk = n;
     // vertex and triangle ids are 32-bit: at most 7 vertices a corner and 12 triangles a cube
     if (7 * nk >= 0xFFFFFFFFull || 12 * nc >= 0xFFFFFFFFull)
         return fail(h, HFPF_ERR_CAPACITY, "mesh: %llu corners / %llu cubes exceed the 32-bit vertex and triangle ids", (unsigned long long)nk,
                     (unsigned long long)nc);
     const uint64_t K1 = nk + 1, C1 = nc + 1;
-    if ((rc = scratch(h, h->mesh_kdata, K1 * 20))) return rc;
-    if ((rc = scratch(h, h->mesh_cdata, C1 * 8))) return rc;
-    float* s = (float*)h->mesh_kdata.p;
-    uint32_t* nid = (uint32_t*)(s + K1);
-    uint32_t* marks = nid + K1;
-    uint32_t* vcount = marks + K1;
-    uint32_t* vbase = vcount + K1;
-    uint32_t* tcount = (uint32_t*)h->mesh_cdata.p;
-    uint32_t* tbase = tcount + C1;
-    const uint64_t* cubes = (const uint64_t*)h->mesh_cube.p;
-    const uint64_t* corners = (const uint64_t*)h->mesh_corner.p;
+    float* s;  // per corner (nk + 1 entries each): the sample, the nearest row, the edge marks, the vertex count and its scan
+    uint32_t *nid, *marks, *vcount, *vbase;
+    uint32_t *tcount, *tbase;  // per cube (nc + 1 entries each): the triangle count and its scan
+    if ((rc = scratch(h, h->mesh_kdata, ScratchLayout().add(&s, K1).add(&nid, K1).add(&marks, K1).add(&vcount, K1).add(&vbase, K1)))) return rc;
+    if ((rc = scratch(h, h->mesh_cdata, ScratchLayout().add(&tcount, C1).add(&tbase, C1)))) return rc;
     const MeshParams p{std::max(1.0, o->min_count), o->max_distance * o->max_distance, o->radius};
-    uint32_t* miss = (uint32_t*)h->mesh_ctr.p + 2;  // behind the unique count: set by a corner lookup that misses (a broken invariant)
+    uint64_t* n_unique; uint32_t* miss; if ((rc = mesh_ctr_locked(h, &n_unique, &miss))) return rc;
     HIPCHK(h, hipMemsetAsync(miss, 0, 4, h->stream));
     hipLaunchKernelGGL(k_mesh_sample, dim3(blocks_for(nk, 256)), dim3(256), 0, h->stream, h->g, h->t, p, corners, (uint32_t)nk, s, nid);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemsetAsync(marks, 0, K1 * 4, h->stream));
-    hipLaunchKernelGGL(k_mesh_mark, dim3(blocks_for(C1, 256)), dim3(256), 0, h->stream, cubes, (uint32_t)nc, corners, (uint32_t)nk, (const float*)s,
-                       (const uint32_t*)nid, marks, tcount, miss);
+    hipLaunchKernelGGL(k_mesh_mark, dim3(blocks_for(C1, 256)), dim3(256), 0, h->stream, cubes, (uint32_t)nc, corners, (uint32_t)nk, s, nid, marks, tcount, miss);
     HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(k_mesh_vcount, dim3(blocks_for(K1, 256)), dim3(256), 0, h->stream, (const uint32_t*)marks, (uint32_t)nk, vcount);
+    hipLaunchKernelGGL(k_mesh_vcount, dim3(blocks_for(K1, 256)), dim3(256), 0, h->stream, marks, (uint32_t)nk, vcount);
     HIPCHK(h, hipGetLastError());
     uint64_t nv = 0, nt = 0;
     if ((rc = scan_counts_locked(h, vcount, vbase, nk, &nv))) return rc;
@@ -3268,19 +3294,14 @@ static int mesh_locked(hfpf_handle* h, const hfpf_mesh_opts* o, bool on_device, 
     if ((rc = result_alloc(h, set, on_device, "mesh"))) return rc;
     MeshVertex* dv = (MeshVertex*)set.a[0].dev;
     uint32_t* dt = (uint32_t*)set.a[1].dev;
-    hipLaunchKernelGGL(k_mesh_vertices, dim3(blocks_for(nk, 256)), dim3(256), 0, h->stream, h->g, h->t, corners, (uint32_t)nk, (const float*)s,
-                       (const uint32_t*)nid, (const uint32_t*)marks, (const uint32_t*)vbase, dv, miss);
-    hipLaunchKernelGGL(k_mesh_triangles, dim3(blocks_for(nc, 256)), dim3(256), 0, h->stream, cubes, (uint32_t)nc, corners, (uint32_t)nk, (const float*)s,
-                       (const uint32_t*)nid, (const uint32_t*)marks, (const uint32_t*)vbase, (const uint32_t*)tbase, dt, miss);
+    hipLaunchKernelGGL(k_mesh_vertices, dim3(blocks_for(nk, 256)), dim3(256), 0, h->stream, h->g, h->t, corners, (uint32_t)nk, s, nid, marks, vbase, dv, miss);
+    hipLaunchKernelGGL(k_mesh_triangles, dim3(blocks_for(nc, 256)), dim3(256), 0, h->stream, cubes, (uint32_t)nc, corners, (uint32_t)nk, s, nid, marks, vbase, tbase, dt, miss);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(&missed, miss, 4, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess || missed) {
-        set.release();
-        if (missed) return fail(h, HFPF_ERR_STATE, "mesh: a corner of a cube or an edge is missing from the corner set (internal)");
-        return fail(h, HFPF_ERR_HIP, "mesh: %s", hipGetErrorString(e));
-    }
-    *out = set, *n_verts = nv, *n_tris = nt;
+    if (missed) return fail(h, HFPF_ERR_STATE, "mesh: a corner of a cube or an edge is missing from the corner set (internal)");
+    if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "mesh: %s", hipGetErrorString(e));
+    set.keep(out), *n_verts = nv, *n_tris = nt;
     return HFPF_OK;
 }
 
@@ -3334,60 +3355,55 @@ int hfpf_check_component_opts(const hfpf_component_opts* o)
 static int components_locked(hfpf_handle* h, const hfpf_component_opts* o, bool on_device, bool want_rows, ResultSet* out, uint64_t* n_rows,
                              uint64_t* n_comps)
 {
-    *out = ResultSet{}, *n_rows = 0, *n_comps = 0;
+    *n_rows = 0, *n_comps = 0;  // (*out: the caller's fresh, empty set)
     int rc;
     if ((rc = local_read_prologue_locked(h, "components"))) return rc;
-    uint64_t nr = 0;
+    RowSet rs;
     const ExtractOpts opt{o->min_count, -1, 0};  // the compare of hfpf_extract_filtered, 0 keeps all
-    if ((rc = build_rows_locked(h, h->t.stats, opt, &nr))) return rc;
+    if ((rc = build_rows_locked(h, h->t.stats, opt, &rs))) return rc;
+    const uint64_t nr = rs.n;
     if (nr == 0) return HFPF_OK;
     if (nr >= 0xFFFFFFFFull) return fail(h, HFPF_ERR_CAPACITY, "components: %llu rows exceed the 32-bit row index", (unsigned long long)nr);
     const uint64_t n_rec = h->h_ctr[C_NORMALS];
     const uint32_t n = (uint32_t)nr;
     const uint64_t R1 = nr + 1;
-    if ((rc = scratch(h, h->comp_index, (n_rec + 1) * 4))) return rc;
-    if ((rc = scratch(h, h->comp_rows, R1 * 24))) return rc;
-    uint32_t* row_of = (uint32_t*)h->comp_index.p;
-    uint32_t* parent = (uint32_t*)h->comp_rows.p;  // (each of the six arrays has nr + 1 entries)
-    uint32_t* root = parent + R1;
-    uint32_t* comp_of = root + R1;
-    uint32_t* flag = comp_of + R1;   // root flags, later the rows' keep flags
-    uint32_t* cbase = flag + R1;     // scan of the root flags
-    uint32_t* rbase = cbase + R1;    // scan of the rows' keep flags
-    const Row* rows = (const Row*)h->rows_dev.p;
+    uint32_t *row_of, *parent, *root, *comp_of;
+    uint32_t *flag, *cbase, *rbase;  // root flags, later the rows' keep flags; the scan of the root flags; the scan of the keep flags
+    if ((rc = scratch_n(h, h->comp_index, n_rec + 1, &row_of))) return rc;
+    if ((rc = scratch(h, h->comp_rows, ScratchLayout().add(&parent, R1).add(&root, R1).add(&comp_of, R1).add(&flag, R1).add(&cbase, R1).add(&rbase, R1)))) return rc;
+    const Row* rows = rs.rows;
     const CompParams p{o->min_normal_dot, o->min_points, o->min_rows, o->keep_largest, o->reach};
     const dim3 grid_r(blocks_for(nr, 256)), grid_r1(blocks_for(R1, 256));
     Timed timed(h);
     if (timed.rc) return timed.rc;
     HIPCHK(h, hipMemsetAsync(row_of, 0xFF, (n_rec + 1) * 4, h->stream));
-    hipLaunchKernelGGL(k_comp_index, grid_r, dim3(256), 0, h->stream, (const uint32_t*)h->vals_b.p, n, row_of, parent);
-    hipLaunchKernelGGL(k_comp_link, grid_r, dim3(256), 0, h->stream, h->g, h->t, p, rows, n, (const uint32_t*)row_of, (uint32_t)n_rec, parent);
-    hipLaunchKernelGGL(k_comp_flatten, grid_r1, dim3(256), 0, h->stream, (const uint32_t*)parent, n, root, flag);
+    hipLaunchKernelGGL(k_comp_index, grid_r, dim3(256), 0, h->stream, rs.record_of_row, n, row_of, parent);
+    hipLaunchKernelGGL(k_comp_link, grid_r, dim3(256), 0, h->stream, h->g, h->t, p, rows, n, row_of, (uint32_t)n_rec, parent);
+    hipLaunchKernelGGL(k_comp_flatten, grid_r1, dim3(256), 0, h->stream, parent, n, root, flag);
     HIPCHK(h, hipGetLastError());
     uint64_t nc = 0;
     if ((rc = scan_counts_locked(h, flag, cbase, nr, &nc))) return rc;
     const uint64_t C1 = nc + 1;
-    if ((rc = scratch(h, h->comp_recs, nc * sizeof(Component) + C1 * 8))) return rc;
-    Component* recs = (Component*)h->comp_recs.p;
-    uint32_t* keep = (uint32_t*)(recs + nc);
-    uint32_t* kbase = keep + C1;
+    Component* recs; uint32_t *keep, *kbase;  // per component (nc + 1 entries each): the keep flag and its scan
+    if ((rc = scratch(h, h->comp_recs, ScratchLayout().add(&recs, nc).add(&keep, C1).add(&kbase, C1)))) return rc;
     const dim3 grid_c1(blocks_for(C1, 256));
-    hipLaunchKernelGGL(k_comp_init, grid_r, dim3(256), 0, h->stream, (const uint32_t*)root, (const uint32_t*)cbase, n, comp_of, recs);
-    hipLaunchKernelGGL(k_comp_reduce, grid_r, dim3(256), 0, h->stream, rows, (const uint32_t*)comp_of, n, recs);
+    hipLaunchKernelGGL(k_comp_init, grid_r, dim3(256), 0, h->stream, root, cbase, n, comp_of, recs);
+    hipLaunchKernelGGL(k_comp_reduce, grid_r, dim3(256), 0, h->stream, rows, comp_of, n, recs);
     if (o->keep_largest == 0) {
-        hipLaunchKernelGGL(k_comp_keep, grid_c1, dim3(256), 0, h->stream, (const Component*)recs, (uint32_t)nc, p, keep);
+        hipLaunchKernelGGL(k_comp_keep, grid_c1, dim3(256), 0, h->stream, recs, (uint32_t)nc, p, keep);
         HIPCHK(h, hipGetLastError());
-    } else {  // the row set's sort buffers are free again: k_comp_index has read vals_b, and nc <= nr
-        hipLaunchKernelGGL(k_comp_rank_keys, grid_c1, dim3(256), 0, h->stream, (const Component*)recs, (uint32_t)nc, p, (uint64_t*)h->keys_a.p,
-                           (uint32_t*)h->vals_a.p, keep);
+    } else {  // the components ranked through the sort buffers: nc <= nr, so nothing grows, and k_comp_index has read record_of_row
+        uint64_t *keys_in, *keys_out; if ((rc = scratch_n(h, h->keys_a, nc, &keys_in)) || (rc = scratch_n(h, h->keys_b, nc, &keys_out))) return rc;
+        uint32_t *vals_in, *vals_out; if ((rc = scratch_n(h, h->vals_a, nc, &vals_in)) || (rc = scratch_n(h, h->vals_b, nc, &vals_out))) return rc;
+        rs.record_of_row = nullptr;  // dead from here: vals_out is the same memory
+        hipLaunchKernelGGL(k_comp_rank_keys, grid_c1, dim3(256), 0, h->stream, recs, (uint32_t)nc, p, keys_in, vals_in, keep);
         HIPCHK(h, hipGetLastError());
-        if ((rc = sort_pairs_u64(h, (uint64_t*)h->keys_a.p, (uint64_t*)h->keys_b.p, (uint32_t*)h->vals_a.p, (uint32_t*)h->vals_b.p, nc, 64))) return rc;
+        if ((rc = sort_pairs_u64(h, keys_in, keys_out, vals_in, vals_out, nc, 64))) return rc;
         const uint32_t front = (uint32_t)std::min<uint64_t>(nc, o->keep_largest);
-        hipLaunchKernelGGL(k_comp_rank_keep, dim3(blocks_for(front, 256)), dim3(256), 0, h->stream, (const uint64_t*)h->keys_b.p,
-                           (const uint32_t*)h->vals_b.p, front, keep);
+        hipLaunchKernelGGL(k_comp_rank_keep, dim3(blocks_for(front, 256)), dim3(256), 0, h->stream, keys_out, vals_out, front, keep);
         HIPCHK(h, hipGetLastError());
     }
-    hipLaunchKernelGGL(k_comp_row_keep, grid_r1, dim3(256), 0, h->stream, (const uint32_t*)comp_of, (const uint32_t*)keep, n, flag);
+    hipLaunchKernelGGL(k_comp_row_keep, grid_r1, dim3(256), 0, h->stream, comp_of, keep, n, flag);
     HIPCHK(h, hipGetLastError());
     uint64_t nk = 0, nkr = 0;
     if ((rc = scan_counts_locked(h, keep, kbase, nc, &nk))) return rc;
@@ -3398,16 +3414,13 @@ static int components_locked(hfpf_handle* h, const hfpf_component_opts* o, bool 
     set.add(nkr * 4);
     set.add(nk * sizeof(Component));
     if ((rc = result_alloc(h, set, on_device, "components"))) return rc;
-    hipLaunchKernelGGL(k_comp_compact, grid_r, dim3(256), 0, h->stream, rows, n, (const uint32_t*)comp_of, (const uint32_t*)keep, (const uint32_t*)kbase,
-                       (const uint32_t*)rbase, (const Component*)recs, (Row*)set.a[0].dev, (uint32_t*)set.a[1].dev, (Component*)set.a[2].dev);
+    hipLaunchKernelGGL(k_comp_compact, grid_r, dim3(256), 0, h->stream, rows, n, comp_of, keep, kbase, rbase, recs, (Row*)set.a[0].dev, (uint32_t*)set.a[1].dev,
+                       (Component*)set.a[2].dev);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) rc = timed.file(kTimeComponents);
     if (e == hipSuccess && !rc) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess || rc) {
-        set.release();
-        return rc ? rc : fail(h, HFPF_ERR_HIP, "components: %s", hipGetErrorString(e));
-    }
-    *out = set, *n_rows = nkr, *n_comps = nk;
+    if (e != hipSuccess || rc) return rc ? rc : fail(h, HFPF_ERR_HIP, "components: %s", hipGetErrorString(e));
+    set.keep(out), *n_rows = nkr, *n_comps = nk;
     return HFPF_OK;
 }
 
@@ -3470,58 +3483,75 @@ static unsigned bits_for_count(uint64_t n)  // bits that hold 0..n-1 (at least 1
     return b;
 }
 
+// A triangle mesh as the calls take it (vertices of `stride` bytes that begin with three floats), in host or in device memory.
+struct MeshRef {
+    const void* verts;
+    uint64_t n_verts;
+    uint32_t stride;
+    const uint32_t* tris;
+    uint64_t n_tris;
+};
+
+// h->dev_tri: the mesh's vertices in the fusion frame (k_dev_verts), then one record per triangle -- compare's DevTri or cover's CovTri.
+extern "C++" template <typename Rec>
+static int dev_tri_scratch_locked(hfpf_handle* h, const MeshRef& m, double** V, Rec** recs)
+{
+    return scratch(h, h->dev_tri, ScratchLayout().add(V, 3 * std::max<uint64_t>(m.n_verts, 1)).add(recs, m.n_tris));
+}
+
 // The two halves of a compare, shared with hfpf_align_mesh*.  ROW SIDE (compare_row_side_locked, once per call; it does not depend on
-// the pose): the rows of h->rows_dev keyed by the brick of their point and sorted, and the list of bricks that hold rows.  MESH SIDE
+// the pose): the rows of a row set keyed by the brick of their point and sorted, and the list of bricks that hold rows.  MESH SIDE
 // (compare_mesh_side_locked, once per pose): the transformed vertices, the triangles' records and pair count, the pairs, their sort
 // and per-brick ranges, and k_dev_rows into a Deviation array.  The read-backs are the sizes between the stages.
+struct DevCounters {  // zeroed together in front of every mesh side
+    unsigned long long ctr[DC_WORDS];
+    DevSummary sum;
+};
+static_assert(sizeof(DevCounters) == DC_WORDS * 8 + sizeof(DevSummary), "the counters and the summary are adjacent");
 struct DevRowSide {
     uint32_t n = 0;   // rows
     uint64_t nb = 0;  // bricks that hold rows
+    const Row* rows = nullptr;
+    const uint32_t* sorted_row = nullptr;  // rank in brick order -> row (h->vals_b, once the row side has sorted)
     // slices of h->dev_bins
     uint64_t* ub_key = nullptr;
-    unsigned long long* ctr = nullptr;
-    DevSummary* d_sum = nullptr;
-    uint32_t *ub_start = nullptr, *tstart = nullptr, *tend = nullptr;
+    DevCounters* counters = nullptr;
+    uint32_t *flag = nullptr, *base = nullptr;  // per sorted row: first of its brick, and the scan
+    uint32_t *ub_start = nullptr, *trange = nullptr;  // trange: per brick the start of its triangle range, then (at + n) the end
 };
 
 // what: the caller's name in messages.  Allocates; a compare opens its Timed bracket behind it, before compare_row_side_locked.
-static int compare_row_scratch_locked(hfpf_handle* h, uint64_t nr, const char* what, DevRowSide* rs, uint32_t** flag, uint32_t** base)
+static int compare_row_scratch_locked(hfpf_handle* h, const RowSet& rows, const char* what, DevRowSide* rs)
 {
-    if (nr >= 0xFFFFFFFFull) return fail(h, HFPF_ERR_CAPACITY, "%s: %llu rows exceed the 32-bit row index", what, (unsigned long long)nr);
-    const uint32_t n = (uint32_t)nr;
-    const size_t R1 = (size_t)n + 1;
-    const size_t bins_bytes = (size_t)n * 8 + DC_WORDS * 8 + sizeof(DevSummary) + (3 * R1 + 2 * (size_t)n) * 4;
-    if (int rc = scratch(h, h->dev_bins, bins_bytes)) return rc;
+    if (rows.n >= 0xFFFFFFFFull) return fail(h, HFPF_ERR_CAPACITY, "%s: %llu rows exceed the 32-bit row index", what, (unsigned long long)rows.n);
+    const uint32_t n = (uint32_t)rows.n;
+    const uint64_t R1 = (uint64_t)n + 1;
     rs->n = n;
-    rs->ub_key = (uint64_t*)h->dev_bins.p;
-    rs->ctr = (unsigned long long*)(rs->ub_key + n);
-    rs->d_sum = (DevSummary*)(rs->ctr + DC_WORDS);
-    *flag = (uint32_t*)(rs->d_sum + 1);
-    *base = *flag + R1;
-    rs->ub_start = *base + R1;
-    rs->tstart = rs->ub_start + R1;
-    rs->tend = rs->tstart + n;
-    return HFPF_OK;
+    rs->rows = rows.rows;
+    return scratch(h, h->dev_bins,
+                   ScratchLayout().add(&rs->ub_key, n).add(&rs->counters, 1).add(&rs->flag, R1).add(&rs->base, R1).add(&rs->ub_start, R1).add(&rs->trange, 2 * (uint64_t)n));
 }
 
-static int compare_row_side_locked(hfpf_handle* h, DevRowSide* rs, uint32_t* flag, uint32_t* base)
+// Sorts through the handle's sort buffers: the row set's record_of_row is dead behind it, and vals_b is rs->sorted_row.
+static int compare_row_side_locked(hfpf_handle* h, DevRowSide* rs)
 {
     const uint32_t n = rs->n;
     if (!n) return HFPF_OK;
     int rc;
     const GridParams& g = h->g;
-    const Row* rows = (const Row*)h->rows_dev.p;
+    uint64_t *keys_in, *keys_out; if ((rc = scratch_n(h, h->keys_a, n, &keys_in)) || (rc = scratch_n(h, h->keys_b, n, &keys_out))) return rc;
+    uint32_t *vals_in, *vals_out; if ((rc = scratch_n(h, h->vals_a, n, &vals_in)) || (rc = scratch_n(h, h->vals_b, n, &vals_out))) return rc;  // (no growth: the row set's own sort was of at least n pairs)
     const size_t R1 = (size_t)n + 1;
     const dim3 grid_r(blocks_for(n, 256)), grid_r1(blocks_for(R1, 256));
-    hipLaunchKernelGGL(k_dev_row_keys, grid_r, dim3(256), 0, h->stream, g, rows, n, (uint64_t*)h->keys_a.p, (uint32_t*)h->vals_a.p);
+    hipLaunchKernelGGL(k_dev_row_keys, grid_r, dim3(256), 0, h->stream, g, rs->rows, n, keys_in, vals_in);
     HIPCHK(h, hipGetLastError());
     const unsigned key_bits = bits_for_count((uint64_t)g.bdim[0] * (uint64_t)g.bdim[1] * (uint64_t)g.bdim[2]);
-    if ((rc = sort_pairs_u64(h, (uint64_t*)h->keys_a.p, (uint64_t*)h->keys_b.p, (uint32_t*)h->vals_a.p, (uint32_t*)h->vals_b.p, n, key_bits))) return rc;
-    hipLaunchKernelGGL(k_dev_row_flags, grid_r1, dim3(256), 0, h->stream, (const uint64_t*)h->keys_b.p, n, flag);
+    if ((rc = sort_pairs_u64(h, keys_in, keys_out, vals_in, vals_out, n, key_bits))) return rc;
+    rs->sorted_row = vals_out;
+    hipLaunchKernelGGL(k_dev_row_flags, grid_r1, dim3(256), 0, h->stream, keys_out, n, rs->flag);
     HIPCHK(h, hipGetLastError());
-    if ((rc = scan_counts_locked(h, flag, base, n, &rs->nb))) return rc;
-    hipLaunchKernelGGL(k_dev_bricks, grid_r1, dim3(256), 0, h->stream, (const uint64_t*)h->keys_b.p, (const uint32_t*)flag, (const uint32_t*)base, n, (uint32_t)rs->nb,
-                       rs->ub_key, rs->ub_start);
+    if ((rc = scan_counts_locked(h, rs->flag, rs->base, n, &rs->nb))) return rc;
+    hipLaunchKernelGGL(k_dev_bricks, grid_r1, dim3(256), 0, h->stream, keys_out, rs->flag, rs->base, n, (uint32_t)rs->nb, rs->ub_key, rs->ub_start);
     HIPCHK(h, hipGetLastError());
     return HFPF_OK;
 }
@@ -3529,8 +3559,8 @@ static int compare_row_side_locked(hfpf_handle* h, DevRowSide* rs, uint32_t* fla
 // The mesh at `pose` against the row side: the counters, the summary and the bricks' triangle ranges are zeroed first, so it may run
 // any number of times behind one row side.  out: n Deviation records (untouched without rows); h_ctr: the DC_WORDS counters read back.
 // The launch of k_dev_rows is left unchecked for the caller's hipGetLastError.
-static int compare_mesh_side_locked(hfpf_handle* h, const DevRowSide& rs, const hfpf_deviation_opts* o, const void* d_verts, uint64_t n_verts, uint32_t stride,
-                                    const uint32_t* d_tris, uint64_t n_tris, const double* pose, Deviation* out, unsigned long long h_ctr[DC_WORDS])
+static int compare_mesh_side_locked(hfpf_handle* h, const DevRowSide& rs, const hfpf_deviation_opts* o, const MeshRef& m, const double* pose, Deviation* out,
+                                    unsigned long long h_ctr[DC_WORDS])
 {
     int rc;
     const uint32_t n = rs.n;
@@ -3545,22 +3575,21 @@ static int compare_mesh_side_locked(hfpf_handle* h, const DevRowSide& rs, const 
     // point X that can matter (within the inflated box of a triangle that reaches a brick): both within `box` + slack of the origin
     p.reach = 2.0 * (box + 64.0 * g.res + 4.0 * (double)g.ball_r + o->max_distance);
     p.face_cap = 4.0 * g.res;
-    p.n_verts = n_verts, p.n_tris = (uint32_t)n_tris, p.stride = stride;
+    p.n_verts = m.n_verts, p.n_tris = (uint32_t)m.n_tris, p.stride = m.stride;
     p.nb = (uint32_t)nb, p.tile = h->knobs.test_dev_tile;
-    HIPCHK(h, hipMemsetAsync(rs.ctr, 0, DC_WORDS * 8 + sizeof(DevSummary), h->stream));
-    if (n) HIPCHK(h, hipMemsetAsync(rs.tstart, 0, 2 * (size_t)n * 4, h->stream));
+    unsigned long long* d_ctr = rs.counters->ctr;
+    HIPCHK(h, hipMemsetAsync(rs.counters, 0, sizeof(DevCounters), h->stream));
+    if (n) HIPCHK(h, hipMemsetAsync(rs.trange, 0, 2 * (size_t)n * 4, h->stream));
     for (int i = 0; i < DC_WORDS; i++) h_ctr[i] = 0;
-    if (n_tris) {
-        const size_t v_bytes = (size_t)std::max<uint64_t>(n_verts, 1) * 24;
-        if ((rc = scratch(h, h->dev_tri, v_bytes + (size_t)n_tris * sizeof(DevTri)))) return rc;
-        double* V = (double*)h->dev_tri.p;
-        DevTri* recs = (DevTri*)((char*)h->dev_tri.p + v_bytes);
-        const dim3 grid_t(blocks_for(n_tris * 64, 256));
-        hipLaunchKernelGGL(k_dev_verts, dim3(blocks_for(n_verts, 256)), dim3(256), 0, h->stream, p, (const uint8_t*)d_verts, V);
-        hipLaunchKernelGGL(k_dev_tris<false>, grid_t, dim3(256), 0, h->stream, g, p, d_tris, (const double*)V, (const uint64_t*)rs.ub_key, recs, rs.ctr, (uint64_t*)nullptr,
-                           (uint64_t)0);
+    double* V = nullptr; DevTri* recs = nullptr;
+    uint64_t *pairs_in = nullptr, *pairs = nullptr;  // pairs: read only inside a non-empty triangle range, and those need pairs
+    if (m.n_tris) {
+        if ((rc = dev_tri_scratch_locked(h, m, &V, &recs))) return rc;
+        const dim3 grid_t(blocks_for(m.n_tris * 64, 256));
+        hipLaunchKernelGGL(k_dev_verts, dim3(blocks_for(m.n_verts, 256)), dim3(256), 0, h->stream, p, (const uint8_t*)m.verts, V);
+        hipLaunchKernelGGL(k_dev_tris<false>, grid_t, dim3(256), 0, h->stream, g, p, m.tris, V, rs.ub_key, recs, d_ctr, (uint64_t*)nullptr, (uint64_t)0);
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(h_ctr, rs.ctr, DC_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h_ctr, d_ctr, DC_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         const uint64_t np = h_ctr[DC_PAIRS];
         if (np) {
@@ -3568,113 +3597,100 @@ static int compare_mesh_side_locked(hfpf_handle* h, const DevRowSide& rs, const 
             // handle's tables were not touched, so it stays usable
             if (np > 0xFFFFFFFEull)
                 return fail(h, HFPF_ERR_CAPACITY, "compare_mesh: %llu (triangle, brick) pairs exceed the 32-bit pair index", (unsigned long long)np);
-            if (scratch(h, h->dev_pairs, (size_t)np * 16) != HFPF_OK) {
+            if (scratch(h, h->dev_pairs, ScratchLayout().add(&pairs_in, np).add(&pairs, np)) != HFPF_OK) {  // the pairs as emitted, then sorted
                 (void)hipGetLastError();
                 return fail(h, HFPF_ERR_CAPACITY, "compare_mesh: no device memory for %llu (triangle, brick) pairs", (unsigned long long)np);
             }
-            uint64_t* pairs_in = (uint64_t*)h->dev_pairs.p;
-            uint64_t* pairs = pairs_in + np;
-            hipLaunchKernelGGL(k_dev_tris<true>, grid_t, dim3(256), 0, h->stream, g, p, d_tris, (const double*)V, (const uint64_t*)rs.ub_key, recs, rs.ctr, pairs_in, np);
+            hipLaunchKernelGGL(k_dev_tris<true>, grid_t, dim3(256), 0, h->stream, g, p, m.tris, V, rs.ub_key, recs, d_ctr, pairs_in, np);
             HIPCHK(h, hipGetLastError());
             if ((rc = sort_keys_u64(h, pairs_in, pairs, np, 32 + bits_for_count(nb)))) return rc;
-            hipLaunchKernelGGL(k_dev_tri_ranges, dim3(blocks_for(np, 256)), dim3(256), 0, h->stream, (const uint64_t*)pairs, (uint32_t)np, (uint32_t)nb, rs.tstart, rs.tend);
+            hipLaunchKernelGGL(k_dev_tri_ranges, dim3(blocks_for(np, 256)), dim3(256), 0, h->stream, pairs, (uint32_t)np, (uint32_t)nb, rs.trange, rs.trange + n);
             HIPCHK(h, hipGetLastError());
         }
     }
-    if (n) {
-        const uint64_t* pairs = h->dev_pairs.p ? (const uint64_t*)h->dev_pairs.p + h_ctr[DC_PAIRS] : nullptr;  // read only inside a non-empty range
-        const DevTri* recs = n_tris ? (const DevTri*)((char*)h->dev_tri.p + (size_t)std::max<uint64_t>(n_verts, 1) * 24) : nullptr;
-        hipLaunchKernelGGL(k_dev_rows, dim3((unsigned)nb), dim3(256), 0, h->stream, (const Row*)h->rows_dev.p, (const uint32_t*)h->vals_b.p, (const uint32_t*)rs.ub_start,
-                           (const uint32_t*)rs.tstart, (const uint32_t*)rs.tend, pairs, recs, p.md2, (uint32_t)p.tile, out, rs.d_sum);
-    }
+    if (n)
+        hipLaunchKernelGGL(k_dev_rows, dim3((unsigned)nb), dim3(256), 0, h->stream, rs.rows, rs.sorted_row, rs.ub_start, rs.trange, rs.trange + n, pairs, recs, p.md2,
+                           (uint32_t)p.tile, out, &rs.counters->sum);
     return HFPF_OK;
 }
 
 // Validated arguments in, the mesh on the device, under the lock.  The row set; then (timed as kernel id 7) the row side and the mesh
-// side into *out (the rows -- absent without want_rows; the host form takes them from h->rows_dev --, the deviations; empty without
+// side into *out (the rows -- absent without want_rows; the host form takes them from the row set --, the deviations; empty without
 // rows), and the read-back of the summary.
-static int compare_locked(hfpf_handle* h, const hfpf_deviation_opts* o, const void* d_verts, uint64_t n_verts, uint32_t stride, const uint32_t* d_tris,
-                          uint64_t n_tris, const double* pose, bool on_device, bool want_rows, ResultSet* out, hfpf_deviation_summary* summary)
+static int compare_locked(hfpf_handle* h, const hfpf_deviation_opts* o, const MeshRef& m, const double* pose, bool on_device, bool want_rows, ResultSet* out,
+                          hfpf_deviation_summary* summary)
 {
-    *out = ResultSet{};
     int rc;
-    uint64_t nr = 0;
+    RowSet rows;
     const ExtractOpts opt{o->min_count, -1, 0};  // the compare of hfpf_extract_filtered, 0 keeps all
-    if ((rc = build_rows_locked(h, h->t.stats, opt, &nr))) return rc;
+    if ((rc = build_rows_locked(h, h->t.stats, opt, &rows))) return rc;
     DevRowSide rs;
-    uint32_t *flag, *base;
-    if ((rc = compare_row_scratch_locked(h, nr, "compare_mesh", &rs, &flag, &base))) return rc;
+    if ((rc = compare_row_scratch_locked(h, rows, "compare_mesh", &rs))) return rc;
     const uint32_t n = rs.n;
     Timed timed(h);
     if (timed.rc) return timed.rc;
-    if ((rc = compare_row_side_locked(h, &rs, flag, base))) return rc;
-    const Row* rows = (const Row*)h->rows_dev.p;
+    if ((rc = compare_row_side_locked(h, &rs))) return rc;
     ResultSet set;
     if (n) {
-        set.add((size_t)n * sizeof(Row), !want_rows, rows);
+        set.add((size_t)n * sizeof(Row), !want_rows, rows.rows);
         set.add((size_t)n * sizeof(Deviation));
         if ((rc = result_alloc(h, set, on_device, "compare_mesh"))) return rc;
     }
     unsigned long long h_ctr[DC_WORDS];
-    if ((rc = compare_mesh_side_locked(h, rs, o, d_verts, n_verts, stride, d_tris, n_tris, pose, (Deviation*)set.a[1].dev, h_ctr))) {
-        set.release();
-        return rc;
-    }
+    if ((rc = compare_mesh_side_locked(h, rs, o, m, pose, (Deviation*)set.a[1].dev, h_ctr))) return rc;
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) rc = timed.file(kTimeCompare);
-    if (e == hipSuccess && !rc && on_device && want_rows && n) e = hipMemcpyAsync(set.a[0].dev, rows, (size_t)n * sizeof(Row), hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess && !rc && on_device && want_rows && n) e = hipMemcpyAsync(set.a[0].dev, rows.rows, (size_t)n * sizeof(Row), hipMemcpyDeviceToDevice, h->stream);
     DevSummary hs;
-    if (e == hipSuccess && !rc) e = hipMemcpyAsync(&hs, rs.d_sum, sizeof hs, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(&hs, &rs.counters->sum, sizeof hs, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && !rc) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess || rc) {
-        set.release();
-        return rc ? rc : fail(h, HFPF_ERR_HIP, "compare_mesh: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess || rc) return rc ? rc : fail(h, HFPF_ERR_HIP, "compare_mesh: %s", hipGetErrorString(e));
     memset(summary, 0, sizeof *summary);
-    summary->n_rows = nr, summary->n_found = hs.n_found, summary->n_negative = hs.n_negative;
-    summary->n_tris_invalid = h_ctr[DC_INVALID], summary->n_tris_valid = n_tris - h_ctr[DC_INVALID];
+    summary->n_rows = rows.n, summary->n_found = hs.n_found, summary->n_negative = hs.n_negative;
+    summary->n_tris_invalid = h_ctr[DC_INVALID], summary->n_tris_valid = m.n_tris - h_ctr[DC_INVALID];
     memcpy(&summary->max_abs, &hs.max_abs_bits, 4);
     summary->sum_abs_q30 = hs.sum_abs_q30, summary->sum_sq_q30 = hs.sum_sq_q30;
-    *out = set;
+    set.keep(out);
     return HFPF_OK;
 }
 
 // The checks on a mesh and its pose that compare, align and cover share.  0 = fine, else the text of the fault.
-static const char* mesh_args_fault(const void* verts, uint64_t n_verts, uint32_t stride, const uint32_t* tris, uint64_t n_tris, const double* pose)
+static const char* mesh_args_fault(const MeshRef& m, const double* pose)
 {
     if (!pose) return "NULL pose";
     for (int i = 0; i < 12; i++)
         if (!std::isfinite(pose[i])) return "non-finite pose";
-    if (stride < 12 || (stride & 3)) return "vertex_stride must be at least 12 and a multiple of 4";
-    if ((!verts && n_verts) || (!tris && n_tris)) return "NULL mesh pointer with a non-zero count";
-    if (n_verts >= 0xFFFFFFFFull || n_tris >= 0xFFFFFFFFull) return "n_verts and n_tris must stay below 2^32 - 1";
+    if (m.stride < 12 || (m.stride & 3)) return "vertex_stride must be at least 12 and a multiple of 4";
+    if ((!m.verts && m.n_verts) || (!m.tris && m.n_tris)) return "NULL mesh pointer with a non-zero count";
+    if (m.n_verts >= 0xFFFFFFFFull || m.n_tris >= 0xFFFFFFFFull) return "n_verts and n_tris must stay below 2^32 - 1";
     return nullptr;
 }
-static bool mesh_misaligned(const void* verts, const uint32_t* tris) { return ((((uintptr_t)verts) | ((uintptr_t)tris)) & 3) != 0; }
+static bool mesh_misaligned(const MeshRef& m) { return ((((uintptr_t)m.verts) | ((uintptr_t)m.tris)) & 3) != 0; }
 
 // The checks of both forms that need the handle but not the device.  0 = fine, else the text of the fault.
-static const char* compare_args_fault(const hfpf_handle* h, const hfpf_deviation_opts* o, const void* verts, uint64_t n_verts, uint32_t stride, const uint32_t* tris,
-                                      uint64_t n_tris, const double* pose, const void* dev, const void* n_rows, const void* summary, bool on_device)
+static const char* compare_args_fault(const hfpf_handle* h, const hfpf_deviation_opts* o, const MeshRef& m, const double* pose, const void* dev, const void* n_rows,
+                                      const void* summary, bool on_device)
 {
     if (hfpf_check_deviation_opts(o) != HFPF_OK) return "invalid hfpf_deviation_opts";
     if (o->max_distance > 32.0 * h->g.res) return "max_distance exceeds 32 voxels";
-    if (const char* f = mesh_args_fault(verts, n_verts, stride, tris, n_tris, pose)) return f;
+    if (const char* f = mesh_args_fault(m, pose)) return f;
     if (!dev || !n_rows || !summary) return "NULL dev, n_rows or summary";
-    if (on_device && mesh_misaligned(verts, tris)) return "device mesh pointers must be 4-byte aligned";
+    if (on_device && mesh_misaligned(m)) return "device mesh pointers must be 4-byte aligned";
     return nullptr;
 }
 
-// The host forms' mesh to the device (h->dev_mesh): the vertices as they are (stride and all), the indices behind them at a 16-byte
-// boundary (*d_tris).
-static int upload_mesh_locked(hfpf_handle* h, const char* what, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
-                              const uint32_t** d_tris)
+// The host forms' mesh to the device (h->dev_mesh, *dev): the vertices as they are (stride and all), the indices behind them at a
+// 16-byte boundary.
+static int upload_mesh_locked(hfpf_handle* h, const char* what, const MeshRef& host, MeshRef* dev)
 {
-    const size_t v_bytes = n_verts ? (size_t)(n_verts - 1) * vertex_stride + 12 : 0, v_room = (v_bytes + 15) & ~(size_t)15, t_bytes = (size_t)n_tris * 12;
-    if (int rc = scratch(h, h->dev_mesh, v_room + t_bytes + 16)) return rc;
-    hipError_t e = v_bytes ? upload_pageable(h, h->dev_mesh.p, verts, v_bytes) : hipSuccess;
-    if (e == hipSuccess && t_bytes) e = upload_pageable(h, (char*)h->dev_mesh.p + v_room, tris, t_bytes);
+    const uint64_t v_bytes = host.n_verts ? (host.n_verts - 1) * host.stride + 12 : 0;
+    uint8_t* d_verts; uint32_t* d_tris;
+    // (16 spare bytes behind the indices: the request is part of the recorded device_bytes)
+    if (int rc = scratch(h, h->dev_mesh, ScratchLayout().add(&d_verts, v_bytes, 16).add(&d_tris, 3 * host.n_tris).skip(16))) return rc;
+    hipError_t e = v_bytes ? upload_pageable(h, d_verts, host.verts, v_bytes) : hipSuccess;
+    if (e == hipSuccess && host.n_tris) e = upload_pageable(h, d_tris, host.tris, host.n_tris * 12);
     if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "%s upload: %s", what, hipGetErrorString(e));
-    *d_tris = (const uint32_t*)((char*)h->dev_mesh.p + v_room);
+    *dev = MeshRef{d_verts, host.n_verts, host.stride, d_tris, host.n_tris};
     return HFPF_OK;
 }
 
@@ -3684,12 +3700,12 @@ int hfpf_compare_mesh_device(hfpf_handle* h, const hfpf_deviation_opts* o, const
 {
     if (!h) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
-    if (const char* f = compare_args_fault(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, dev_dev, n_rows, summary, true))
-        return fail(h, HFPF_ERR_BAD_ARG, "compare_mesh_device: %s", f);
+    const MeshRef m{dev_verts, n_verts, vertex_stride, dev_tris, n_tris};
+    if (const char* f = compare_args_fault(h, o, m, pose_3x4, dev_dev, n_rows, summary, true)) return fail(h, HFPF_ERR_BAD_ARG, "compare_mesh_device: %s", f);
     if (int rc = local_read_prologue_locked(h, "compare_mesh")) return rc;
     ResultSet set;
     hfpf_deviation_summary s;
-    if (int rc = compare_locked(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, true, dev_rows != nullptr, &set, &s)) return rc;
+    if (int rc = compare_locked(h, o, m, pose_3x4, true, dev_rows != nullptr, &set, &s)) return rc;
     if (dev_rows) *dev_rows = (hfpf_row*)set.a[0].dev;
     *dev_dev = (hfpf_deviation*)set.a[1].dev, *n_rows = s.n_rows, *summary = s;
     return HFPF_OK;
@@ -3700,14 +3716,14 @@ int hfpf_compare_mesh(hfpf_handle* h, const hfpf_deviation_opts* o, const void* 
 {
     if (!h) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
-    if (const char* f = compare_args_fault(h, o, verts, n_verts, vertex_stride, tris, n_tris, pose_3x4, dev, n_rows, summary, false))
-        return fail(h, HFPF_ERR_BAD_ARG, "compare_mesh: %s", f);
+    const MeshRef m{verts, n_verts, vertex_stride, tris, n_tris};
+    if (const char* f = compare_args_fault(h, o, m, pose_3x4, dev, n_rows, summary, false)) return fail(h, HFPF_ERR_BAD_ARG, "compare_mesh: %s", f);
     if (int rc = local_read_prologue_locked(h, "compare_mesh")) return rc;
-    const uint32_t* d_tris = nullptr;
-    if (int rc = upload_mesh_locked(h, "compare_mesh", verts, n_verts, vertex_stride, tris, n_tris, &d_tris)) return rc;
+    MeshRef d;
+    if (int rc = upload_mesh_locked(h, "compare_mesh", m, &d)) return rc;
     ResultSet set;
     hfpf_deviation_summary s;
-    if (int rc = compare_locked(h, o, h->dev_mesh.p, n_verts, vertex_stride, d_tris, n_tris, pose_3x4, false, rows != nullptr, &set, &s)) return rc;
+    if (int rc = compare_locked(h, o, d, pose_3x4, false, rows != nullptr, &set, &s)) return rc;
     void* host[3] = {nullptr, nullptr, nullptr};
     if (s.n_rows)
         if (int rc = result_to_host(h, set, "compare_mesh", host)) return rc;
@@ -3732,34 +3748,31 @@ int hfpf_check_align_opts(const hfpf_align_opts* o)
 
 // Validated arguments in, the mesh on the device, under the lock.  The row set; then compare's row side once and refine_pose with
 // compare's mesh side into h->align_dev and one k_align_reduce per iteration.  Not timed: hfpf_get_kernel_time has no id for it.
-static int align_locked(hfpf_handle* h, const hfpf_align_opts* o, const void* d_verts, uint64_t n_verts, uint32_t stride, const uint32_t* d_tris, uint64_t n_tris,
-                        const double* pose, hfpf_align_result* res)
+static int align_locked(hfpf_handle* h, const hfpf_align_opts* o, const MeshRef& m, const double* pose, hfpf_align_result* res)
 {
     int rc;
-    uint64_t nr = 0;
+    RowSet rows;
     const ExtractOpts opt{o->compare.min_count, -1, 0};
-    if ((rc = build_rows_locked(h, h->t.stats, opt, &nr))) return rc;
-    const uint64_t n_samples = (nr + o->stride - 1) / o->stride;
+    if ((rc = build_rows_locked(h, h->t.stats, opt, &rows))) return rc;
+    const uint64_t n_samples = (rows.n + o->stride - 1) / o->stride;
     if (n_samples > (1ull << 26)) return fail(h, HFPF_ERR_BAD_ARG, "align_mesh: more than 2^26 sampled rows");
     DevRowSide rs;
-    uint32_t *flag, *base;
-    if ((rc = compare_row_scratch_locked(h, nr, "align_mesh", &rs, &flag, &base))) return rc;
-    if ((rc = scratch(h, h->align_dev, (size_t)std::max<uint32_t>(rs.n, 1) * sizeof(Deviation)))) return rc;
+    if ((rc = compare_row_scratch_locked(h, rows, "align_mesh", &rs))) return rc;
+    Deviation* dev; if ((rc = scratch_n(h, h->align_dev, std::max<uint32_t>(rs.n, 1), &dev))) return rc;
     AlignParams p{};
     for (int a = 0; a < 3; a++) p.c[a] = (h->g.min[a] + h->g.max[a]) * 0.5;
     p.flags = o->flags, p.stride = o->stride, p.n = (uint32_t)n_samples;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(kTrackMaxBlocks, blocks_for(n_samples, 256));
-    Deviation* dev = (Deviation*)h->align_dev.p;
 
-    if ((rc = compare_row_side_locked(h, &rs, flag, base))) return rc;
+    if ((rc = compare_row_side_locked(h, &rs))) return rc;
     uint64_t none;
     rc = refine_pose(h, o, p.c, kAlignTerms, pose, [&](const double* T, unsigned long long* acc) -> int {
         unsigned long long h_ctr[DC_WORDS];
-        if (int e = compare_mesh_side_locked(h, rs, &o->compare, d_verts, n_verts, stride, d_tris, n_tris, T, dev, h_ctr)) return e;
+        if (int e = compare_mesh_side_locked(h, rs, &o->compare, m, T, dev, h_ctr)) return e;
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipMemsetAsync(acc, 0, kAlignTerms * sizeof(unsigned long long), h->stream));
         if (n_samples) {  // without rows the zeros are read back: TOO_FEW
-            hipLaunchKernelGGL(k_align_reduce, dim3(blocks), dim3(256), 0, h->stream, p, (const Row*)h->rows_dev.p, (const Deviation*)dev, acc);
+            hipLaunchKernelGGL(k_align_reduce, dim3(blocks), dim3(256), 0, h->stream, p, rows.rows, dev, acc);
             HIPCHK(h, hipGetLastError());
         }
         return HFPF_OK;
@@ -3769,11 +3782,10 @@ static int align_locked(hfpf_handle* h, const hfpf_align_opts* o, const void* d_
 }
 
 // The checks of both forms: the options, then compare's own on the mesh, the pose and max_distance, then the result.
-static const char* align_args_fault(const hfpf_handle* h, const hfpf_align_opts* o, const void* verts, uint64_t n_verts, uint32_t stride, const uint32_t* tris,
-                                    uint64_t n_tris, const double* pose, const hfpf_align_result* res, bool on_device)
+static const char* align_args_fault(const hfpf_handle* h, const hfpf_align_opts* o, const MeshRef& m, const double* pose, const hfpf_align_result* res, bool on_device)
 {
     if (hfpf_check_align_opts(o) != HFPF_OK) return "invalid hfpf_align_opts";
-    if (const char* f = compare_args_fault(h, &o->compare, verts, n_verts, stride, tris, n_tris, pose, h, h, h, on_device)) return f;
+    if (const char* f = compare_args_fault(h, &o->compare, m, pose, h, h, h, on_device)) return f;
     if (!res || res->struct_size != sizeof(hfpf_align_result)) return "NULL result or wrong struct_size";
     return nullptr;
 }
@@ -3783,10 +3795,10 @@ int hfpf_align_mesh_device(hfpf_handle* h, const hfpf_align_opts* o, const void*
 {
     if (!h) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
-    if (const char* f = align_args_fault(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, result, true))
-        return fail(h, HFPF_ERR_BAD_ARG, "align_mesh_device: %s", f);
+    const MeshRef m{dev_verts, n_verts, vertex_stride, dev_tris, n_tris};
+    if (const char* f = align_args_fault(h, o, m, pose_3x4, result, true)) return fail(h, HFPF_ERR_BAD_ARG, "align_mesh_device: %s", f);
     if (int rc = local_read_prologue_locked(h, "align_mesh")) return rc;
-    return align_locked(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, result);
+    return align_locked(h, o, m, pose_3x4, result);
 }
 
 int hfpf_align_mesh(hfpf_handle* h, const hfpf_align_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
@@ -3794,12 +3806,12 @@ int hfpf_align_mesh(hfpf_handle* h, const hfpf_align_opts* o, const void* verts,
 {
     if (!h) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
-    if (const char* f = align_args_fault(h, o, verts, n_verts, vertex_stride, tris, n_tris, pose_3x4, result, false))
-        return fail(h, HFPF_ERR_BAD_ARG, "align_mesh: %s", f);
+    const MeshRef m{verts, n_verts, vertex_stride, tris, n_tris};
+    if (const char* f = align_args_fault(h, o, m, pose_3x4, result, false)) return fail(h, HFPF_ERR_BAD_ARG, "align_mesh: %s", f);
     if (int rc = local_read_prologue_locked(h, "align_mesh")) return rc;
-    const uint32_t* d_tris = nullptr;
-    if (int rc = upload_mesh_locked(h, "align_mesh", verts, n_verts, vertex_stride, tris, n_tris, &d_tris)) return rc;
-    return align_locked(h, o, h->dev_mesh.p, n_verts, vertex_stride, d_tris, n_tris, pose_3x4, result);
+    MeshRef d;
+    if (int rc = upload_mesh_locked(h, "align_mesh", m, &d)) return rc;
+    return align_locked(h, o, d, pose_3x4, result);
 }
 
 // ---- coverage of a triangle mesh by the model (include/hfpf.h) ----------------------------------------------------------------
@@ -3812,76 +3824,70 @@ int hfpf_check_cover_opts(const hfpf_cover_opts* o)
     return std::isfinite(o->min_normal_dot) && o->min_normal_dot >= -2.0 && o->min_normal_dot <= 1.0 ? HFPF_OK : HFPF_ERR_BAD_ARG;
 }
 
+struct CovCounters {  // zeroed together in front of the setup
+    CovSummary sum;
+    unsigned long long total;  // samples of all triangles
+};
+static_assert(sizeof(CovCounters) == sizeof(CovSummary) + 8, "the summary and the total are adjacent");
+
 // Validated arguments in, the mesh on the device, n_tris > 0, under the lock.  The transformed vertices (compare's kernel); per
 // triangle a record, the geometry and a sample count; the scan of the counts; one lane per sample; per triangle its share of the
 // summary.  The 64-bit total is read back once in front of the scan (whose 32-bit total cannot tell an overflow): the capacity
 // check and the size of the sample launch.  *out: the n_tris records.  Not timed: hfpf_get_kernel_time has no id for it.
-static int cover_locked(hfpf_handle* h, const hfpf_cover_opts* o, const void* d_verts, uint64_t n_verts, uint32_t stride, const uint32_t* d_tris, uint64_t n_tris,
-                        const double* pose, bool on_device, ResultSet* out, hfpf_coverage_summary* summary)
+static int cover_locked(hfpf_handle* h, const hfpf_cover_opts* o, const MeshRef& m, const double* pose, bool on_device, ResultSet* out, hfpf_coverage_summary* summary)
 {
-    *out = ResultSet{};
     int rc;
-    const size_t T1 = (size_t)n_tris + 1;
-    const size_t v_bytes = (size_t)std::max<uint64_t>(n_verts, 1) * 24;
-    if ((rc = scratch(h, h->dev_tri, v_bytes + (size_t)n_tris * sizeof(CovTri)))) return rc;
-    if ((rc = scratch(h, h->cov_bins, sizeof(CovSummary) + 8 + 2 * T1 * 4))) return rc;
-    double* V = (double*)h->dev_tri.p;
-    CovTri* geo = (CovTri*)((char*)h->dev_tri.p + v_bytes);
-    CovSummary* d_sum = (CovSummary*)h->cov_bins.p;
-    unsigned long long* d_total = (unsigned long long*)(d_sum + 1);
-    uint32_t* count = (uint32_t*)(d_total + 1);
-    uint32_t* offset = count + T1;
+    const uint64_t n_tris = m.n_tris, T1 = n_tris + 1;
+    double* V; CovTri* geo; CovCounters* ctr;
+    uint32_t *count, *offset;  // per triangle (n_tris + 1 entries each): the sample count and its scan
+    if ((rc = dev_tri_scratch_locked(h, m, &V, &geo)) || (rc = scratch(h, h->cov_bins, ScratchLayout().add(&ctr, 1).add(&count, T1).add(&offset, T1)))) return rc;
+    CovSummary* d_sum = &ctr->sum;
+    unsigned long long* d_total = &ctr->total;
     ResultSet set;
     set.add((size_t)n_tris * sizeof(TriCoverage));
     if ((rc = result_alloc(h, set, on_device, "cover_mesh"))) return rc;
     TriCoverage* cov = (TriCoverage*)set.a[0].dev;
-    auto give_up = [&](int code) {
-        set.release();
-        return code;
-    };
     DevParams vp{};  // what k_dev_verts reads of it
     memcpy(vp.T, pose, sizeof vp.T);
-    vp.n_verts = n_verts, vp.n_tris = (uint32_t)n_tris, vp.stride = stride;
+    vp.n_verts = m.n_verts, vp.n_tris = (uint32_t)n_tris, vp.stride = m.stride;
     CovParams p{};
     p.spacing = o->spacing, p.min_count = std::max(1.0, o->min_count), p.max_d2 = o->max_distance * o->max_distance, p.min_dot = o->min_normal_dot;
-    p.n_verts = n_verts, p.n_tris = (uint32_t)n_tris, p.max_sub = o->max_subdivision;
+    p.n_verts = m.n_verts, p.n_tris = (uint32_t)n_tris, p.max_sub = o->max_subdivision;
     p.abs_normal = (o->flags & HFPF_COVER_ABS_NORMAL) ? 1u : 0u, p.radius = o->radius;
-    hipError_t e = hipMemsetAsync(d_sum, 0, sizeof(CovSummary) + 8, h->stream);
-    if (e != hipSuccess) return give_up(fail(h, HFPF_ERR_HIP, "cover_mesh: %s", hipGetErrorString(e)));
-    hipLaunchKernelGGL(k_dev_verts, dim3(blocks_for(n_verts, 256)), dim3(256), 0, h->stream, vp, (const uint8_t*)d_verts, V);
-    hipLaunchKernelGGL(k_cov_setup, dim3(blocks_for(T1, 256)), dim3(256), 0, h->stream, p, d_tris, (const double*)V, cov, geo, count, d_total);
+    hipError_t e = hipMemsetAsync(ctr, 0, sizeof(CovCounters), h->stream);
+    if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "cover_mesh: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(k_dev_verts, dim3(blocks_for(m.n_verts, 256)), dim3(256), 0, h->stream, vp, (const uint8_t*)m.verts, V);
+    hipLaunchKernelGGL(k_cov_setup, dim3(blocks_for(T1, 256)), dim3(256), 0, h->stream, p, m.tris, V, cov, geo, count, d_total);
     unsigned long long total = 0;
     if ((e = hipGetLastError()) == hipSuccess) e = hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return give_up(fail(h, HFPF_ERR_HIP, "cover_mesh: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "cover_mesh: %s", hipGetErrorString(e));
     if (total > 0xFFFFFFFEull)  // nothing on the handle was touched: it stays usable
-        return give_up(fail(h, HFPF_ERR_CAPACITY, "cover_mesh: %llu samples exceed the 2^32 - 2 a call takes (a larger spacing or a smaller max_subdivision)", total));
+        return fail(h, HFPF_ERR_CAPACITY, "cover_mesh: %llu samples exceed the 2^32 - 2 a call takes (a larger spacing or a smaller max_subdivision)", total);
     if (total) {
         uint64_t scanned = 0;
-        if ((rc = scan_counts_locked(h, count, offset, n_tris, &scanned))) return give_up(rc);
-        if (scanned != total) return give_up(fail(h, HFPF_ERR_STATE, "cover_mesh: the scan of the sample counts disagrees with their sum (internal)"));
-        hipLaunchKernelGGL(k_cov_samples, dim3(blocks_for(total, 256)), dim3(256), 0, h->stream, h->g, h->t, p, (const uint32_t*)offset, (const CovTri*)geo,
-                           (uint32_t)total, cov);
+        if ((rc = scan_counts_locked(h, count, offset, n_tris, &scanned))) return rc;
+        if (scanned != total) return fail(h, HFPF_ERR_STATE, "cover_mesh: the scan of the sample counts disagrees with their sum (internal)");
+        hipLaunchKernelGGL(k_cov_samples, dim3(blocks_for(total, 256)), dim3(256), 0, h->stream, h->g, h->t, p, offset, geo, (uint32_t)total, cov);
     }
-    hipLaunchKernelGGL(k_cov_finish, dim3(blocks_for(n_tris, 256)), dim3(256), 0, h->stream, (uint32_t)n_tris, (const TriCoverage*)cov, (const CovTri*)geo, d_sum);
+    hipLaunchKernelGGL(k_cov_finish, dim3(blocks_for(n_tris, 256)), dim3(256), 0, h->stream, (uint32_t)n_tris, cov, geo, d_sum);
     CovSummary hs;
     if ((e = hipGetLastError()) == hipSuccess) e = hipMemcpyAsync(&hs, d_sum, sizeof hs, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return give_up(fail(h, HFPF_ERR_HIP, "cover_mesh: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "cover_mesh: %s", hipGetErrorString(e));
     static_assert(sizeof(CovSummary) == sizeof(hfpf_coverage_summary), "the device summary is the public one, max_distance as bits");
     memcpy(summary, &hs, sizeof hs);
-    *out = set;
+    set.keep(out);
     return HFPF_OK;
 }
 
 // The checks of both forms.  0 = fine, else the text of the fault.
-static const char* cover_args_fault(const hfpf_cover_opts* o, const void* verts, uint64_t n_verts, uint32_t stride, const uint32_t* tris, uint64_t n_tris,
-                                    const double* pose, const void* cov, const void* summary, bool on_device)
+static const char* cover_args_fault(const hfpf_cover_opts* o, const MeshRef& m, const double* pose, const void* cov, const void* summary, bool on_device)
 {
     if (hfpf_check_cover_opts(o) != HFPF_OK) return "invalid hfpf_cover_opts";
-    if (const char* f = mesh_args_fault(verts, n_verts, stride, tris, n_tris, pose)) return f;
+    if (const char* f = mesh_args_fault(m, pose)) return f;
     if (!cov || !summary) return "NULL cov or summary";
-    if (on_device && mesh_misaligned(verts, tris)) return "device mesh pointers must be 4-byte aligned";
+    if (on_device && mesh_misaligned(m)) return "device mesh pointers must be 4-byte aligned";
     return nullptr;
 }
 
@@ -3890,14 +3896,14 @@ int hfpf_cover_mesh_device(hfpf_handle* h, const hfpf_cover_opts* o, const void*
 {
     if (!h) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
-    if (const char* f = cover_args_fault(o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, dev_cov, summary, true))
-        return fail(h, HFPF_ERR_BAD_ARG, "cover_mesh_device: %s", f);
+    const MeshRef m{dev_verts, n_verts, vertex_stride, dev_tris, n_tris};
+    if (const char* f = cover_args_fault(o, m, pose_3x4, dev_cov, summary, true)) return fail(h, HFPF_ERR_BAD_ARG, "cover_mesh_device: %s", f);
     if (int rc = local_read_prologue_locked(h, "cover_mesh")) return rc;
     ResultSet set;
     hfpf_coverage_summary s;
     memset(&s, 0, sizeof s);
     if (n_tris)
-        if (int rc = cover_locked(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, true, &set, &s)) return rc;
+        if (int rc = cover_locked(h, o, m, pose_3x4, true, &set, &s)) return rc;
     *dev_cov = (hfpf_tri_coverage*)set.a[0].dev, *summary = s;
     return HFPF_OK;
 }
@@ -3907,17 +3913,17 @@ int hfpf_cover_mesh(hfpf_handle* h, const hfpf_cover_opts* o, const void* verts,
 {
     if (!h) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
-    if (const char* f = cover_args_fault(o, verts, n_verts, vertex_stride, tris, n_tris, pose_3x4, cov, summary, false))
-        return fail(h, HFPF_ERR_BAD_ARG, "cover_mesh: %s", f);
+    const MeshRef m{verts, n_verts, vertex_stride, tris, n_tris};
+    if (const char* f = cover_args_fault(o, m, pose_3x4, cov, summary, false)) return fail(h, HFPF_ERR_BAD_ARG, "cover_mesh: %s", f);
     if (int rc = local_read_prologue_locked(h, "cover_mesh")) return rc;
     hfpf_coverage_summary s;
     memset(&s, 0, sizeof s);
     void* host[3] = {nullptr, nullptr, nullptr};
     if (n_tris) {
-        const uint32_t* d_tris = nullptr;
-        if (int rc = upload_mesh_locked(h, "cover_mesh", verts, n_verts, vertex_stride, tris, n_tris, &d_tris)) return rc;
+        MeshRef d;
+        if (int rc = upload_mesh_locked(h, "cover_mesh", m, &d)) return rc;
         ResultSet set;
-        if (int rc = cover_locked(h, o, h->dev_mesh.p, n_verts, vertex_stride, d_tris, n_tris, pose_3x4, false, &set, &s)) return rc;
+        if (int rc = cover_locked(h, o, d, pose_3x4, false, &set, &s)) return rc;
         if (int rc = result_to_host(h, set, "cover_mesh", host)) return rc;
     }
     *cov = (hfpf_tri_coverage*)host[0], *summary = s;
@@ -4033,7 +4039,8 @@ int hfpf_dist_init(hfpf_handle* h, int rank, int world, const void* id128)
     {  // exchange buffers for epochs of up to 4 M newly occupied cells per rank exist from here on; larger epochs grow them
         const uint64_t recs = std::min<uint64_t>(h->t.max_occ, 4ull << 20);
         int rc;
-        if ((rc = scratch(h, h->ex_counts, (size_t)(world + 1) * 8)) || (rc = scratch(h, h->ex_send, recs * sizeof(EpochRec))) ||
+        unsigned long long *d_counts, *d_mine;
+        if ((rc = scratch(h, h->ex_counts, ex_counts_layout(world, &d_counts, &d_mine))) || (rc = scratch(h, h->ex_send, recs * sizeof(EpochRec))) ||
             (rc = scratch(h, h->ex_recv, (size_t)world * recs * sizeof(EpochRec))))
             return rc;
         h->ex_cap_records = recs;
@@ -4549,12 +4556,11 @@ void snap_spans(hfpf_handle* h, const SnapUsed& u, const SnapSection* sec, uint3
 }
 
 // Pack (device -> staging) or unpack the part of the payload inside the window [w0, w1) (multiples of 16); the staging buffer
-// holds that window from its first byte.
+// holds that window from its first byte.  err: the range check's error words.
 template <bool PACK>
-int snap_move_window(hfpf_handle* h, const SnapUsed& u, const SnapSection* sec, uint32_t n_sec, const std::vector<SnapSpan>& spans, const SnapLimits& lim, uint64_t w0,
-                     uint64_t w1)
+int snap_move_window(hfpf_handle* h, uint8_t* stage, uint32_t* err, const SnapSection* sec, uint32_t n_sec, const std::vector<SnapSpan>& spans, const SnapLimits& lim,
+                     uint64_t w0, uint64_t w1)
 {
-    uint8_t* stage = (uint8_t*)h->snap_stage.p;
     SnapSpans sp;
     memset(&sp, 0, sizeof sp);
     auto flush = [&]() {
@@ -4585,11 +4591,10 @@ int snap_move_window(hfpf_handle* h, const SnapUsed& u, const SnapSection* sec, 
         if (lo >= hi) continue;
         const uint32_t first = (uint32_t)((lo - sec[i].offset) / 16), n = (uint32_t)((hi - lo) / 16);
         uint4* rec = (uint4*)(stage + (lo - w0));
-        if (sec[i].id == SS_BRICKS) hipLaunchKernelGGL(k_snap_bricks<PACK>, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->t, lim, rec, first, n, (uint32_t*)h->snap_err.p);
-        else hipLaunchKernelGGL(k_snap_frames<PACK>, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->t, rec, first, n, (uint32_t*)h->snap_err.p);
+        if (sec[i].id == SS_BRICKS) hipLaunchKernelGGL(k_snap_bricks<PACK>, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->t, lim, rec, first, n, err);
+        else hipLaunchKernelGGL(k_snap_frames<PACK>, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->t, rec, first, n, err);
     }
     HIPCHK(h, hipGetLastError());
-    (void)u;
     return HFPF_OK;
 }
 
@@ -4730,7 +4735,8 @@ int snapshot_locked(hfpf_handle* h, void** blob_out, uint64_t* bytes_out)
 
     uint64_t window = 0;
     if ((rc = snap_stage_alloc(h, hd.payload_bytes, &window))) return rc;
-    if ((rc = scratch(h, h->snap_err, 64))) return rc;
+    uint32_t* err; if ((rc = scratch_n(h, h->snap_err, 16, &err))) return rc;
+    uint8_t* stage = static_cast<uint8_t*>(h->snap_stage.p);
     uint8_t* blob = (uint8_t*)host_result_alloc(hd.total_bytes);
     if (!blob) return fail(h, HFPF_ERR_CAPACITY, "snapshot: host allocation of %llu bytes failed", (unsigned long long)hd.total_bytes);
     std::vector<SnapSpan> spans;
@@ -4738,9 +4744,9 @@ int snapshot_locked(hfpf_handle* h, void** blob_out, uint64_t* bytes_out)
     const SnapLimits lim = snap_limits(h, u);
     for (uint64_t w0 = 0; w0 < hd.payload_bytes; w0 += window) {
         const uint64_t w1 = std::min(hd.payload_bytes, w0 + window);
-        hipError_t e = hipMemsetAsync(h->snap_stage.p, 0, w1 - w0, h->stream);  // the gaps between sections are zero
-        if (e == hipSuccess) rc = snap_move_window<true>(h, u, hd.sec, hd.n_sections, spans, lim, w0, w1);
-        if (e == hipSuccess && !rc) e = download_pageable(h, blob + HFPF_SNAPSHOT_HEADER_BYTES + w0, h->snap_stage.p, w1 - w0);
+        hipError_t e = hipMemsetAsync(stage, 0, w1 - w0, h->stream);  // the gaps between sections are zero
+        if (e == hipSuccess) rc = snap_move_window<true>(h, stage, err, hd.sec, hd.n_sections, spans, lim, w0, w1);
+        if (e == hipSuccess && !rc) e = download_pageable(h, blob + HFPF_SNAPSHOT_HEADER_BYTES + w0, stage, w1 - w0);
         if (e != hipSuccess) rc = fail(h, HFPF_ERR_HIP, "snapshot download: %s", hipGetErrorString(e));
         if (rc) {
             free(blob);
@@ -4793,10 +4799,8 @@ int restore_locked(hfpf_handle* h, const void* blob, uint64_t bytes)
     SnapUsed u{};
     u.n_bricks = hd.n_bricks, u.n_normals = hd.n_normals, u.n_occ = hd.n_occ, u.n_reg = hd.n_reg, u.n_prereg = hd.n_prereg, u.n_dep = hd.n_dep;
     u.n_frames = hd.n_frames, u.n_pend = hd.n_pend;
-    uint64_t log_total = 0;
     for (int r = 0; r < kLogRegions; r++) {
         u.log_n[r] = hd.log_n[r];
-        log_total += hd.log_n[r];
         if (hd.log_n[r] > t.log_region_cap || hd.n_linked[r] > hd.log_n[r]) return fail(h, HFPF_ERR_BAD_ARG, "restore: log region %d out of range", r);
     }
     if (u.n_bricks > t.max_bricks || u.n_normals > t.max_normals || u.n_occ > t.max_occ || u.n_reg > t.max_reg || u.n_prereg > t.max_reg || u.n_dep > t.max_dep ||
@@ -4824,7 +4828,6 @@ int restore_locked(hfpf_handle* h, const void* blob, uint64_t bytes)
             if (n_r != u.log_n[r]) return fail(h, HFPF_ERR_BAD_ARG, "restore: log counters in the payload do not match the header");
         }
     }
-    (void)log_total;
     // ---- from here on a failure leaves the handle as after hfpf_clear ----
     if ((rc = clear_locked(h))) return rc;
     auto bail = [&](int code) {
@@ -4837,31 +4840,33 @@ int restore_locked(hfpf_handle* h, const void* blob, uint64_t bytes)
     };
     uint64_t window = 0;
     if ((rc = snap_stage_alloc(h, hd.payload_bytes, &window))) return bail(rc);
-    if ((rc = scratch(h, h->snap_err, 64))) return bail(rc);
-    if (u.n_pend && (rc = scratch(h, h->pend_a, u.n_pend * 4))) return bail(rc);
-    if (hipMemsetAsync(h->snap_err.p, 0, 64, h->stream) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore: hipMemsetAsync failed"));
+    uint32_t *err, *pend = nullptr;  // pend: read below u.n_pend only
+    if ((rc = scratch_n(h, h->snap_err, 16, &err))) return bail(rc);
+    if (u.n_pend && (rc = scratch_n(h, h->pend_a, u.n_pend, &pend))) return bail(rc);
+    uint8_t* stage = static_cast<uint8_t*>(h->snap_stage.p);
+    if (hipMemsetAsync(err, 0, 64, h->stream) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore: hipMemsetAsync failed"));
     std::vector<SnapSpan> spans;
     snap_spans(h, u, hd.sec, hd.n_sections, &spans);
     const SnapLimits lim = snap_limits(h, u);
     for (uint64_t w0 = 0; w0 < hd.payload_bytes; w0 += window) {
         const uint64_t w1 = std::min(hd.payload_bytes, w0 + window);
-        const hipError_t e = upload_pageable(h, h->snap_stage.p, payload + w0, w1 - w0);
+        const hipError_t e = upload_pageable(h, stage, payload + w0, w1 - w0);
         if (e != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore upload: %s", hipGetErrorString(e)));
-        if ((rc = snap_move_window<false>(h, u, hd.sec, hd.n_sections, spans, lim, w0, w1))) return bail(rc);
+        if ((rc = snap_move_window<false>(h, stage, err, hd.sec, hd.n_sections, spans, lim, w0, w1))) return bail(rc);
         if (w1 < hd.payload_bytes && hipStreamSynchronize(h->stream) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore: unpack failed"));  // the window is reused
     }
     // range check of every index a later kernel would follow, before anything else touches the tables
-    if (u.n_bricks) hipLaunchKernelGGL(k_snap_check_slots, dim3(blocks_for(u.n_bricks * (uint64_t)kBrickCells, 256)), dim3(256), 0, h->stream, h->t, lim, (uint32_t*)h->snap_err.p);
+    if (u.n_bricks) hipLaunchKernelGGL(k_snap_check_slots, dim3(blocks_for(u.n_bricks * (uint64_t)kBrickCells, 256)), dim3(256), 0, h->stream, h->t, lim, err);
     {
         uint64_t max_log = 0;
         for (int r = 0; r < kLogRegions; r++) max_log = std::max(max_log, u.log_n[r]);
-        if (max_log) hipLaunchKernelGGL(k_snap_check_log, dim3(blocks_for(max_log, 256), kLogRegions), dim3(256), 0, h->stream, h->t, lim, (uint32_t*)h->snap_err.p);
+        if (max_log) hipLaunchKernelGGL(k_snap_check_log, dim3(blocks_for(max_log, 256), kLogRegions), dim3(256), 0, h->stream, h->t, lim, err);
         const uint64_t n_list = std::max({u.n_normals + 1, u.n_reg, u.n_prereg, u.n_occ, u.n_pend});
-        hipLaunchKernelGGL(k_snap_check_lists, dim3(blocks_for(n_list, 256)), dim3(256), 0, h->stream, h->g, h->t, lim, (const uint32_t*)h->pend_a.p, (uint32_t*)h->snap_err.p);
+        hipLaunchKernelGGL(k_snap_check_lists, dim3(blocks_for(n_list, 256)), dim3(256), 0, h->stream, h->g, h->t, lim, pend, err);
     }
     if (hipGetLastError() != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore: launch of the range check failed"));
     uint32_t err_word = 0;
-    if (hipMemcpyAsync(&err_word, h->snap_err.p, 4, hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
+    if (hipMemcpyAsync(&err_word, err, 4, hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
         return bail(fail(h, HFPF_ERR_HIP, "restore: reading the range check's result failed"));
     if (err_word) return bail(fail(h, HFPF_ERR_IO, "restore: the snapshot's tables hold indices outside their pools (range check bits 0x%x); the handle has been cleared", err_word));
     header_to_session(hd, h);
@@ -5054,13 +5059,12 @@ int hfpf_get_occupied(hfpf_handle* h, int32_t* xyz, uint64_t cap, uint64_t* n_ou
     const uint64_t n = std::min<uint64_t>(h->h_ctr[C_OCC], h->t.max_occ);
     *n_out = n;
     if (!xyz || n == 0) return HFPF_OK;
-    if ((rc = scratch(h, h->keys_a, n * 8))) return rc;
-    if ((rc = scratch(h, h->keys_b, n * 8))) return rc;
-    hipLaunchKernelGGL(k_occupied_keys, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->g, h->t, n, (uint64_t*)h->keys_a.p);
+    uint64_t *unsorted, *sorted; if ((rc = scratch_n(h, h->keys_a, n, &unsorted)) || (rc = scratch_n(h, h->keys_b, n, &sorted))) return rc;
+    hipLaunchKernelGGL(k_occupied_keys, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->g, h->t, n, unsorted);
     HIPCHK(h, hipGetLastError());
-    if ((rc = sort_keys_u64(h, (uint64_t*)h->keys_a.p, (uint64_t*)h->keys_b.p, n))) return rc;
+    if ((rc = sort_keys_u64(h, unsorted, sorted, n))) return rc;
     std::vector<uint64_t> keys(n);
-    HIPCHK(h, hipMemcpyAsync(keys.data(), h->keys_b.p, n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(keys.data(), sorted, n * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (uint64_t i = 0; i < std::min(n, cap); i++) key_coords(h->g, keys[i], xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
     return HFPF_OK;
@@ -5124,10 +5128,15 @@ int hfpf_get_kernel_time(hfpf_handle* h, int kernel_id, double* total_ms, uint64
 }
 
 // ---- leaf probes (include/hfpf_probe.h) ----------------------------------------------------------
-#define PROBE_UP(buf, src, bytes)                                                  \
-    if ((rc = scratch(h, buf, (bytes)))) return rc;                                \
-    HIPCHK(h, hipMemcpyAsync(buf.p, (src), (bytes), hipMemcpyHostToDevice, h->stream));
-#define PROBE_DOWN(dst, buf, bytes) HIPCHK(h, hipMemcpyAsync((dst), buf.p, (bytes), hipMemcpyDeviceToHost, h->stream));
+// An input of a probe: `count` T from host memory into buf (*d), enqueued.  An output is a scratch_n and a probe_down.
+extern "C++" template <typename T>
+static int probe_up(hfpf_handle* h, DevBuf& buf, const T* src, uint64_t count, T** d)
+{
+    if (int rc = scratch_n(h, buf, count, d)) return rc;
+    HIPCHK(h, hipMemcpyAsync(*d, src, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    return HFPF_OK;
+}
+#define PROBE_DOWN(dst, d, count) HIPCHK(h, hipMemcpyAsync((dst), (d), (count) * sizeof *(d), hipMemcpyDeviceToHost, h->stream));
 
 int hfpf_probe_points(hfpf_handle* h, const double pose[12], const float* xyz, uint64_t n, float* q_out, int32_t* idx_out, uint8_t* flags_out)
 {
@@ -5136,17 +5145,15 @@ int hfpf_probe_points(hfpf_handle* h, const double pose[12], const float* xyz, u
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (n == 0) return HFPF_OK;
     int rc;
-    PROBE_UP(h->probe_a, pose, 12 * sizeof(double));
-    PROBE_UP(h->probe_b, xyz, n * 12);
-    if ((rc = scratch(h, h->probe_c, n * 12))) return rc;
-    if ((rc = scratch(h, h->probe_d, n * 12))) return rc;
-    if ((rc = scratch(h, h->probe_e, n))) return rc;
-    hipLaunchKernelGGL(k_probe_points, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->g, (const double*)h->probe_a.p, (const float*)h->probe_b.p, n,
-                       (float*)h->probe_c.p, (int32_t*)h->probe_d.p, (uint8_t*)h->probe_e.p);
+    double* d_pose; float *d_xyz, *d_q;
+    int32_t* d_idx; uint8_t* d_flags;
+    if ((rc = probe_up(h, h->probe_a, pose, 12, &d_pose)) || (rc = probe_up(h, h->probe_b, xyz, 3 * n, &d_xyz))) return rc;
+    if ((rc = scratch_n(h, h->probe_c, 3 * n, &d_q)) || (rc = scratch_n(h, h->probe_d, 3 * n, &d_idx)) || (rc = scratch_n(h, h->probe_e, n, &d_flags))) return rc;
+    hipLaunchKernelGGL(k_probe_points, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->g, d_pose, d_xyz, n, d_q, d_idx, d_flags);
     HIPCHK(h, hipGetLastError());
-    PROBE_DOWN(q_out, h->probe_c, n * 12);
-    PROBE_DOWN(idx_out, h->probe_d, n * 12);
-    PROBE_DOWN(flags_out, h->probe_e, n);
+    PROBE_DOWN(q_out, d_q, 3 * n);
+    PROBE_DOWN(idx_out, d_idx, 3 * n);
+    PROBE_DOWN(flags_out, d_flags, n);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return HFPF_OK;
 }
@@ -5158,16 +5165,14 @@ int hfpf_probe_normals(hfpf_handle* h, uint64_t n, const int32_t* cells, const u
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (n == 0) return HFPF_OK;
     int rc;
-    PROBE_UP(h->probe_a, cells, n * 12);
-    PROBE_UP(h->probe_b, occ, n * 125);
-    PROBE_UP(h->probe_c, vps, n * 12);
-    if ((rc = scratch(h, h->probe_d, n * 12))) return rc;
-    if ((rc = scratch(h, h->probe_e, n * 4))) return rc;
-    hipLaunchKernelGGL(k_probe_normals, dim3(blocks_for(n, 64)), dim3(64), 0, h->stream, h->g, n, (const int32_t*)h->probe_a.p, (const uint8_t*)h->probe_b.p,
-                       (const float*)h->probe_c.p, (float*)h->probe_d.p, (int32_t*)h->probe_e.p);
+    int32_t *d_cells, *d_totals; uint8_t* d_occ; float *d_vps, *d_normals;
+    if ((rc = probe_up(h, h->probe_a, cells, 3 * n, &d_cells)) || (rc = probe_up(h, h->probe_b, occ, 125 * n, &d_occ))) return rc;
+    if ((rc = probe_up(h, h->probe_c, vps, 3 * n, &d_vps))) return rc;
+    if ((rc = scratch_n(h, h->probe_d, 3 * n, &d_normals)) || (rc = scratch_n(h, h->probe_e, n, &d_totals))) return rc;
+    hipLaunchKernelGGL(k_probe_normals, dim3(blocks_for(n, 64)), dim3(64), 0, h->stream, h->g, n, d_cells, d_occ, d_vps, d_normals, d_totals);
     HIPCHK(h, hipGetLastError());
-    PROBE_DOWN(normals_out, h->probe_d, n * 12);
-    PROBE_DOWN(totals_out, h->probe_e, n * 4);
+    PROBE_DOWN(normals_out, d_normals, 3 * n);
+    PROBE_DOWN(totals_out, d_totals, n);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return HFPF_OK;
 }
@@ -5180,18 +5185,15 @@ int hfpf_probe_project(hfpf_handle* h, uint64_t n, const float* pts, const float
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (n == 0) return HFPF_OK;
     int rc;
-    PROBE_UP(h->probe_a, pts, n * 12);
-    PROBE_UP(h->probe_b, centres, n * 12);
-    PROBE_UP(h->probe_c, normals, n * 12);
-    if ((rc = scratch(h, h->probe_d, n * 12))) return rc;
-    if ((rc = scratch(h, h->probe_e, n * 8))) return rc;
-    if ((rc = scratch(h, h->probe_f, n))) return rc;
-    hipLaunchKernelGGL(k_probe_project, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->g, n, (const float*)h->probe_a.p, (const float*)h->probe_b.p,
-                       (const float*)h->probe_c.p, (float*)h->probe_d.p, (double*)h->probe_e.p, (uint8_t*)h->probe_f.p);
+    float *d_pts, *d_centres, *d_normals, *d_proj; double* d_dist; uint8_t* d_member;
+    if ((rc = probe_up(h, h->probe_a, pts, 3 * n, &d_pts)) || (rc = probe_up(h, h->probe_b, centres, 3 * n, &d_centres))) return rc;
+    if ((rc = probe_up(h, h->probe_c, normals, 3 * n, &d_normals))) return rc;
+    if ((rc = scratch_n(h, h->probe_d, 3 * n, &d_proj)) || (rc = scratch_n(h, h->probe_e, n, &d_dist)) || (rc = scratch_n(h, h->probe_f, n, &d_member))) return rc;
+    hipLaunchKernelGGL(k_probe_project, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->g, n, d_pts, d_centres, d_normals, d_proj, d_dist, d_member);
     HIPCHK(h, hipGetLastError());
-    PROBE_DOWN(proj_out, h->probe_d, n * 12);
-    PROBE_DOWN(dist_out, h->probe_e, n * 8);
-    PROBE_DOWN(member_out, h->probe_f, n);
+    PROBE_DOWN(proj_out, d_proj, 3 * n);
+    PROBE_DOWN(dist_out, d_dist, n);
+    PROBE_DOWN(member_out, d_member, n);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return HFPF_OK;
 }
@@ -5205,17 +5207,15 @@ int hfpf_probe_depth(hfpf_handle* h, const hfpf_depth_image* desc, const void* d
     int rc = depth_spec(h, desc, depth, color, &ds);
     if (rc) return rc;
     const uint32_t n = ds.width * ds.height;
-    PROBE_UP(h->probe_a, depth, ds.depth_bytes());
-    if (ds.color_bpp) {
-        PROBE_UP(h->probe_b, color, ds.color_bytes());
-    }
-    if ((rc = scratch(h, h->probe_c, (size_t)n * 12))) return rc;
-    if ((rc = scratch(h, h->probe_d, (size_t)n * 4))) return rc;
-    hipLaunchKernelGGL(k_probe_depth, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, depth_layout(ds, h->probe_b.p, 0), (const uint8_t*)h->probe_a.p, n,
-                       (float*)h->probe_c.p, (uint32_t*)h->probe_d.p);
+    uint8_t *d_depth, *d_color = nullptr;  // (without colour depth_layout() passes no colour image)
+    float* d_xyz; uint32_t* d_rgb;
+    if ((rc = probe_up(h, h->probe_a, (const uint8_t*)depth, ds.depth_bytes(), &d_depth))) return rc;
+    if (ds.color_bpp && (rc = probe_up(h, h->probe_b, (const uint8_t*)color, ds.color_bytes(), &d_color))) return rc;
+    if ((rc = scratch_n(h, h->probe_c, 3 * (uint64_t)n, &d_xyz)) || (rc = scratch_n(h, h->probe_d, n, &d_rgb))) return rc;
+    hipLaunchKernelGGL(k_probe_depth, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, depth_layout(ds, d_color, 0), d_depth, n, d_xyz, d_rgb);
     HIPCHK(h, hipGetLastError());
-    PROBE_DOWN(xyz_out, h->probe_c, (size_t)n * 12);
-    PROBE_DOWN(rgb_out, h->probe_d, (size_t)n * 4);
+    PROBE_DOWN(xyz_out, d_xyz, 3 * (uint64_t)n);
+    PROBE_DOWN(rgb_out, d_rgb, n);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return HFPF_OK;
 }
@@ -5227,17 +5227,13 @@ int hfpf_probe_trig(hfpf_handle* h, uint64_t n, const float* y, const float* x, 
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (n == 0) return HFPF_OK;
     int rc;
-    PROBE_UP(h->probe_a, y, n * 4);
-    PROBE_UP(h->probe_b, x, n * 4);
-    if ((rc = scratch(h, h->probe_c, n * 4))) return rc;
-    if ((rc = scratch(h, h->probe_d, n * 4))) return rc;
-    if ((rc = scratch(h, h->probe_e, n * 4))) return rc;
-    hipLaunchKernelGGL(k_probe_trig, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, n, (const float*)h->probe_a.p, (const float*)h->probe_b.p,
-                       (float*)h->probe_c.p, (float*)h->probe_d.p, (float*)h->probe_e.p);
+    float *d_y, *d_x, *d_atan2, *d_cos, *d_sin; if ((rc = probe_up(h, h->probe_a, y, n, &d_y)) || (rc = probe_up(h, h->probe_b, x, n, &d_x))) return rc;
+    if ((rc = scratch_n(h, h->probe_c, n, &d_atan2)) || (rc = scratch_n(h, h->probe_d, n, &d_cos)) || (rc = scratch_n(h, h->probe_e, n, &d_sin))) return rc;
+    hipLaunchKernelGGL(k_probe_trig, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, n, d_y, d_x, d_atan2, d_cos, d_sin);
     HIPCHK(h, hipGetLastError());
-    PROBE_DOWN(atan2_out, h->probe_c, n * 4);
-    PROBE_DOWN(cos_out, h->probe_d, n * 4);
-    PROBE_DOWN(sin_out, h->probe_e, n * 4);
+    PROBE_DOWN(atan2_out, d_atan2, n);
+    PROBE_DOWN(cos_out, d_cos, n);
+    PROBE_DOWN(sin_out, d_sin, n);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return HFPF_OK;
 }

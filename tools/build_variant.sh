@@ -13,6 +13,9 @@ if [ "$1" = "--rev" ]; then
   for f in det_math.hpp geometry.hpp tables.hpp stats.hpp kernels.hpp hfpf.hip; do
     git -C $R show $REV:high-fidelity-pointcloud-fusion_amd/csrc/$f > $TMP/high-fidelity-pointcloud-fusion_amd/csrc/$f
   done
+  # (a revision from before the header existed builds without it)
+  git -C $R show $REV:high-fidelity-pointcloud-fusion_amd/csrc/scratch_layout.hpp > $TMP/high-fidelity-pointcloud-fusion_amd/csrc/scratch_layout.hpp 2>/dev/null ||
+    rm -f $TMP/high-fidelity-pointcloud-fusion_amd/csrc/scratch_layout.hpp
   for f in hfpf.h hfpf_probe.h; do git -C $R show $REV:include/$f > $TMP/include/$f; done
   SRC=$TMP/high-fidelity-pointcloud-fusion_amd/csrc
 fi
