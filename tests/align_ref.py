@@ -20,6 +20,24 @@ def centre(bbox):
     return [(b[0] + b[1]) * 0.5, (b[2] + b[3]) * 0.5, (b[4] + b[5]) * 0.5]
 
 
+def rigid(deg, axis, t, c):
+    """The 3x4 pose of a rotation of `deg` degrees about `axis` through c, followed by the translation t."""
+    k = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    a = np.radians(deg)
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    R = np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * (K @ K)
+    c = np.asarray(c, np.float64)
+    return np.hstack([R, (c - R @ c + np.asarray(t, np.float64)).reshape(3, 1)])
+
+
+def corner_displacement(pose, true_pose, bbox):
+    """The largest displacement of a corner of the bbox under pose o true_pose^-1: 0 when the pose is the true one."""
+    P, Q = np.vstack([pose, [0, 0, 0, 1]]), np.vstack([true_pose, [0, 0, 0, 1]])
+    M = P @ np.linalg.inv(Q)
+    corners = np.array([[bbox[i], bbox[2 + j], bbox[4 + k], 1.0] for i in (0, 1) for j in (0, 1) for k in (0, 1)])
+    return float(np.linalg.norm((corners @ M.T - corners)[:, :3], axis=1).max())
+
+
 def terms(rows, dev, c, flags=0):
     """(inlier mask, J (n, 6), r) of the sampled rows and their deviation records."""
     found = (dev["flags"] & D.FOUND) != 0

@@ -60,8 +60,6 @@ Z_CLIP = (0.28, 0.6)   # the default z-clip of engine and oracle
 # Point and centroid are f32s of spacing 2^-16 (x), 2^-18 (y), 2^-19 m (z) there, so d2 is a sum of three small integer squares scaled
 # by powers of two, and equal sums are common.
 TIE_FLOOR = {"far137": (0, 2, 5, 6, 6, 5, 3), "far137s": (0, 474, 683, 762, 807, 683, 593)}
-CAPS = dict(max_bricks=60000, max_log_points=4 << 20, max_normals=1 << 20, max_frames=4096)
-IDENT = np.hstack([np.eye(3), np.zeros((3, 1))])
 
 
 class FaceScene(scenes.Scene):

@@ -32,6 +32,29 @@ class Scene:
         yield ("clean",)
 
 
+class DepthScene:
+    """A seeded stream of synthetic depth frames (uint16 + RGB8) with random poses and a clean schedule."""
+
+    def __init__(self, n_frames, W, H, clean_every=4, depth_scale=0.001, seed=0xD3F7, pose_seed=0x5E3):
+        self.n_frames, self.W, self.H, self.clean_every, self.depth_scale = n_frames, W, H, clean_every, depth_scale
+        self.poses = [S.pose(pose_seed, f) for f in range(n_frames)]
+        self.frames = [S.depth_frame(seed, f, W, H, self.poses[f], depth_scale=depth_scale) for f in range(n_frames)]
+        self.K = self.frames[0][2]
+
+    def schedule(self):
+        return Scene.schedule(self)
+
+    def cloud(self, f):
+        """Frame f as the packed cloud tests/depth_ref.py makes of it."""
+        import depth_ref
+        depth, rgb, K = self.frames[f]
+        return depth_ref.packed_cloud(depth, K, rgb, depth_ref.COLOR_RGB8, self.depth_scale)
+
+    def integrate(self, g, f):
+        depth, rgb, K = self.frames[f]
+        g.integrate_depth(depth, self.poses[f], K, color=rgb, depth_scale=self.depth_scale)
+
+
 def run(grid, scene, capture_name, color=False):
     """Drive an oracle grid (capture) or an engine grid (integrate) through the scene's schedule.  color=True also hands
     the oracle the rgb field (its colour extension, fuse_color=True)."""

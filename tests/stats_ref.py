@@ -131,3 +131,37 @@ def rows_from_moments(mom, normals, bbox_min, resolution=0.005, K=3, ball_radius
         rows[f] = fl[f]
     rows["rgb"] = row_rgb(mom["m"], color)
     return rows
+
+
+# ---- configurations with a bound on either side of a power of two (what the scale tests run) ----
+
+def floor_log2(b):
+    m, e = math.frexp(b)  # b = m * 2^e, 0.5 <= m < 1: exact, no logarithm
+    return e - 1
+
+
+def straddles():
+    """(K, resolution, ball_radius below, ball_radius above, which bound) with Bm (or Bm^2) on either side of a power of two, found
+    by stepping ball_radius through neighbouring doubles around (K + 2) res / (2 target)."""
+    found = []
+    for K in (1, 3, 5):
+        for res in (0.001, 0.005):
+            res32 = float(np.float32(res))
+            for which, target in ((0, 0.25), (0, 1.0), (0, 4.0), (1, math.sqrt(0.5)), (1, math.sqrt(2.0)), (1, math.sqrt(8.0))):
+                ball = (K + 2.0) * res32 / (2.0 * target)
+                want = floor_log2(target * target * 1.0000001) if which else floor_log2(target)
+                lo = hi = ball
+                for _ in range(64):  # walk to a pair of neighbouring doubles with the bound's exponent on either side
+                    if floor_log2(bounds(K, res, lo, 0.001)[which]) >= want:
+                        lo = math.nextafter(lo, math.inf)  # larger radius, smaller bound
+                    if floor_log2(bounds(K, res, hi, 0.001)[which]) < want:
+                        hi = math.nextafter(hi, 0.0)
+                e_lo, e_hi = (floor_log2(bounds(K, res, b, 0.001)[which]) for b in (lo, hi))
+                if e_lo == want - 1 and e_hi == want and abs(lo - hi) <= 4 * math.ulp(ball):
+                    found.append((K, res, lo, hi, which))
+    return found
+
+
+STRADDLES = straddles()
+# the combination the scene tests (CPU and GPU) run: K = 3 at 1 mm, Bm across 2^-2, i.e. ball_radius across 10 mm
+STRADDLE_SCENE = next(s for s in STRADDLES if s[0] == 3 and s[1] == 0.001 and s[4] == 0 and 0.009 < s[2] < 0.011)

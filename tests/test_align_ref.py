@@ -46,34 +46,16 @@ def surface_mesh(m=41, lo=-0.16, hi=0.16, ylo=None, yhi=None):
     return verts, np.concatenate([np.stack([a, b, c], 1), np.stack([a, c, d], 1)]).astype(np.uint32)
 
 
-def rigid(deg, axis, t, c):
-    """The 3x4 pose of a rotation of `deg` degrees about `axis` through c, followed by the translation t."""
-    k = np.asarray(axis, np.float64) / np.linalg.norm(axis)
-    a = np.radians(deg)
-    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
-    R = np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * (K @ K)
-    c = np.asarray(c, np.float64)
-    return np.hstack([R, (c - R @ c + np.asarray(t, np.float64)).reshape(3, 1)])
-
-
-def corner_displacement(pose, true_pose, bbox):
-    """The largest displacement of a corner of the bbox under pose o true_pose^-1: 0 when the pose is the true one."""
-    P, Q = np.vstack([pose, [0, 0, 0, 1]]), np.vstack([true_pose, [0, 0, 0, 1]])
-    M = P @ np.linalg.inv(Q)
-    corners = np.array([[bbox[i], bbox[2 + j], bbox[4 + k], 1.0] for i in (0, 1) for j in (0, 1) for k in (0, 1)])
-    return float(np.linalg.norm((corners @ M.T - corners)[:, :3], axis=1).max())
-
-
 def test_reference_converges_on_a_displaced_patch():
     rows = patch_rows()
     verts, tris = surface_mesh()
     # the mesh file is the surface moved by S^-1, so the true mesh -> fusion pose is S; the start pose is the identity
-    S = rigid(0.8, (0.3, -0.5, 1.0), (0.003, -0.002, 0.0025), A.centre(BBOX))
+    S = A.rigid(0.8, (0.3, -0.5, 1.0), (0.003, -0.002, 0.0025), A.centre(BBOX))
     S4 = np.vstack([S, [0, 0, 0, 1]])
     moved = (np.hstack([verts.astype(np.float64), np.ones((len(verts), 1))]) @ np.linalg.inv(S4).T)[:, :3].astype(np.float32)
     start = np.eye(4)[:3]
     got = A.align(rows, moved, 12, tris, start, BBOX, max_iterations=30, max_distance=MD, eps_rotation=1e-5, eps_translation=1e-5)
-    d0, d1 = corner_displacement(start, S, BBOX), corner_displacement(got["pose"], S, BBOX)
+    d0, d1 = A.corner_displacement(start, S, BBOX), A.corner_displacement(got["pose"], S, BBOX)
     print("patch: %d rows, %d iterations, flags %d, inliers %d, rms %.3e -> %.3e, corner displacement %.6f -> %.6f m" % (
         len(rows), got["iterations"], got["flags"], got["inliers"], got["history"][0], got["rms"], d0, d1))
     assert got["flags"] == A.CONVERGED
@@ -83,7 +65,7 @@ def test_reference_converges_on_a_displaced_patch():
     # sampling: every third row, the same mesh
     s3 = A.align(rows, moved, 12, tris, start, BBOX, max_iterations=30, stride=3, max_distance=MD, eps_rotation=1e-5, eps_translation=1e-5)
     assert s3["rows_sampled"] == (len(rows) + 2) // 3 and s3["flags"] == A.CONVERGED
-    assert corner_displacement(s3["pose"], S, BBOX) < d0
+    assert A.corner_displacement(s3["pose"], S, BBOX) < d0
 
 
 def test_plane_only_mesh_pins_the_degenerate_path():
@@ -97,7 +79,7 @@ def test_plane_only_mesh_pins_the_degenerate_path():
     r["count"] = 1
     quad = np.array([[-1, -1, 0.2], [1, -1, 0.2], [1, 1, 0.2], [-1, 1, 0.2]], np.float32)
     t2 = np.array([[0, 1, 2], [0, 2, 3]], np.uint32)
-    start = rigid(0.0, (0, 0, 1), (0, 0, 0.004), (0, 0, 0))
+    start = A.rigid(0.0, (0, 0, 1), (0, 0, 0.004), (0, 0, 0))
     got = A.align(r, quad, 12, t2, start, BBOX, max_distance=MD, damping=0.0)
     assert got["flags"] == A.DEGENERATE and got["iterations"] == 1 and got["inliers"] == len(r)
     assert got["pose"].tobytes() == np.ascontiguousarray(start, np.float64).tobytes()
@@ -105,7 +87,7 @@ def test_plane_only_mesh_pins_the_degenerate_path():
     damped = A.align(r, quad, 12, t2, start, BBOX, max_distance=MD, damping=1e-6)
     assert damped["flags"] == A.CONVERGED and abs(damped["pose"][2, 3]) < 1e-5
     # no triangle in reach: TOO_FEW after one system, the pose untouched
-    far = rigid(0.0, (0, 0, 1), (0, 0, 0.1), (0, 0, 0))
+    far = A.rigid(0.0, (0, 0, 1), (0, 0, 0.1), (0, 0, 0))
     none = A.align(r, quad, 12, t2, far, BBOX, max_distance=MD)
     assert none["flags"] == A.TOO_FEW and none["iterations"] == 1 and none["inliers"] == 0 and none["rms"] == 0.0
     assert none["pose"].tobytes() == np.ascontiguousarray(far, np.float64).tobytes()

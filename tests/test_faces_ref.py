@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import faces
+from gpu_support import IDENT
 import mesh_ref as M
 import query_ref as Q
 import raycast_ref as RC
@@ -69,7 +70,7 @@ def test_nearest_ties_is_the_brute_force_count(oracle_mod, synth_mod, name):
     cv = np.stack([cand["ix"], cand["iy"], cand["iz"]], axis=1).astype(np.int64)
     cxyz = faces.centroids(cand).astype(np.float64)
     for radius in (1, 3):
-        hits, _ = Q.query(rows, occ, pts, faces.IDENT, sc.bbox, res, radius=radius)
+        hits, _ = Q.query(rows, occ, pts, IDENT, sc.bbox, res, radius=radius)
         tied = Q.nearest_ties(rows, hits, pts, radius)
         want = np.zeros(len(pts), bool)
         for i in np.flatnonzero(hits["flags"] & Q.FOUND != 0):
@@ -88,8 +89,8 @@ def test_query_is_the_brute_force_scan(model, radius):
     pts = faces.query_points(rows, sc.bbox, res, dims)
     pts = pts[np.random.default_rng(radius).choice(len(pts), 1500, replace=False)]
     for kw in (dict(), dict(min_count=3.0), dict(max_distance=1.5 * res)):
-        a = Q.query(rows, occ, pts, faces.IDENT, sc.bbox, res, radius=radius, **kw)
-        b = Q.brute_force(rows, occ, pts, faces.IDENT, sc.bbox, res, radius=radius, **kw)
+        a = Q.query(rows, occ, pts, IDENT, sc.bbox, res, radius=radius, **kw)
+        b = Q.brute_force(rows, occ, pts, IDENT, sc.bbox, res, radius=radius, **kw)
         assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes(), kw
     f = a[0]["flags"]
     at_dim = (f & Q.IN_BBOX != 0) & (a[0]["voxel"] == np.asarray(dims)).any(axis=1)
@@ -116,7 +117,7 @@ def test_raycast_of_axis_parallel_and_in_face_rays_raises_no_warning(model):
     rays = np.vstack([sets["axis-parallel"][::3], sets["in a face's plane"][::3]])
     with warnings.catch_warnings():
         warnings.simplefilter("error")
-        h = RC.raycast(rows, occ, rays, faces.IDENT, sc.bbox, res, radius=2, step=0.5, t_range=(0.0, faces.ray_t_max(sc.bbox, res)))
+        h = RC.raycast(rows, occ, rays, IDENT, sc.bbox, res, radius=2, step=0.5, t_range=(0.0, faces.ray_t_max(sc.bbox, res)))
     assert (h["flags"] & RC.USED != 0).all() and (h["flags"] & RC.HIT != 0).any()
 
 
@@ -133,8 +134,8 @@ def test_a_ray_from_beyond_a_face_and_one_from_the_face_cross_at_the_same_point(
     assert len(pairs) >= 4
     for outer, inner, m, off in pairs:
         kw = dict(radius=2, step=0.5)
-        ho = RC.raycast(rows, occ, outer, faces.IDENT, sc.bbox, res, t_range=(0.0, t1 + off), **kw)
-        hi = RC.raycast(rows, occ, inner, faces.IDENT, sc.bbox, res, t_range=(0.0, t1), **kw)
+        ho = RC.raycast(rows, occ, outer, IDENT, sc.bbox, res, t_range=(0.0, t1 + off), **kw)
+        hi = RC.raycast(rows, occ, inner, IDENT, sc.bbox, res, t_range=(0.0, t1), **kw)
         hit = hi["flags"] & RC.HIT != 0
         n_hit += int(hit.sum())
         assert np.array_equal(ho["flags"], hi["flags"])

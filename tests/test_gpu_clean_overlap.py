@@ -10,8 +10,7 @@ import numpy as np
 import pytest
 
 import scenes
-from test_gpu_parity import SMALL
-from test_gpu_snapshot import _contract
+from gpu_support import SMALL_CAPS, contract_counters
 
 pytestmark = pytest.mark.gpu
 
@@ -86,7 +85,7 @@ def _engine(hfpf_mod, monkeypatch, capfd, sc, ops, overlap, **kw):
     monkeypatch.setenv("HFPF_CLEAN_OVERLAP", "1" if overlap else "0")
     monkeypatch.setenv("HFPF_TRACE_CLEAN", "1")
     capfd.readouterr()
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **dict(SMALL, **kw)) as g:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **dict(SMALL_CAPS, **kw)) as g:
         st = Stream(g, sc)
         _drive(g, st, ops)
         rows = g.extract().copy()
@@ -208,22 +207,22 @@ def test_snapshot_after_an_overlapped_clean(oracle_mod, hfpf_mod, synth_mod, mon
     monkeypatch.setenv("HFPF_CLEAN_OVERLAP", "1")
     monkeypatch.setenv("HFPF_TRACE_CLEAN", "1")
     capfd.readouterr()
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as src:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as src:
         st = Stream(src, sc)
         _drive(src, st, plain[:4])  # two batches, two passes: the second one overlapped
         blob = src.snapshot()
         assert _passes(capfd) == (1, 1)
-        with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as dst:
+        with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as dst:
             dst.restore(blob)
-            assert _contract(src) == _contract(dst)
+            assert contract_counters(src) == contract_counters(dst)
             st2 = Stream(dst, sc)
             _drive(dst, st2, plain[4:])
             rows = dst.extract().copy()
-            c_dst = _contract(dst)
+            c_dst = contract_counters(dst)
             st2.free()
         _drive(src, st, plain[4:])  # the source goes on as if nothing had happened
         assert src.extract().tobytes() == whole.tobytes()
-        c_src = _contract(src)
+        c_src = contract_counters(src)
         st.free()
     assert rows.tobytes() == whole.tobytes(), "the restored handle's continuation differs from the uninterrupted run"
     assert c_dst == c_src and all(c_src[k] == c_whole[k] for k in c_src)
@@ -251,7 +250,7 @@ def test_capacity_error_around_an_overlapped_pass(hfpf_mod, synth_mod, monkeypat
     sc = _scene(8)
     plain = _plan(sc)
     monkeypatch.setenv("HFPF_TRACE_CLEAN", "1")
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as g:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as g:
         st = Stream(g, sc)
         _drive(g, st, plain[:2])
         c1 = g.counters()
@@ -265,7 +264,7 @@ def test_capacity_error_around_an_overlapped_pass(hfpf_mod, synth_mod, monkeypat
     for overlap in (True, False):
         monkeypatch.setenv("HFPF_CLEAN_OVERLAP", "1" if overlap else "0")
         capfd.readouterr()
-        with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **dict(SMALL, **{pool: cap})) as g:
+        with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **dict(SMALL_CAPS, **{pool: cap})) as g:
             st = Stream(g, sc)
             at, err = _until_error(hfpf_mod, g, st, plain)
             print("%s = %d, HFPF_CLEAN_OVERLAP=%d: op %r raised %r; passes (beside, alone) = %r" % (pool, cap, overlap, at, err, _passes(capfd)))

@@ -9,18 +9,18 @@ import numpy as np
 import pytest
 
 import cover_ref as V
-from test_gpu_render import RES, DepthScene, _counters, _grid, _run
+from gpu_support import IDENT, RES, counters, cover_device, coverage_sums, grid, run, same_coverage, uploaded
+from scenes import DepthScene
 
 pytestmark = pytest.mark.gpu
-IDENT = np.eye(4)[:3]
 OWN = 4000  # triangles of the model's own mesh that are covered
 
 
 @pytest.fixture(scope="module")
 def session(hfpf_mod, synth_mod):
     sc = DepthScene(3, 160, 120, clean_every=2)
-    g = _grid(hfpf_mod)
-    _run(g, sc)
+    g = grid(hfpf_mod)
+    run(g, sc)
     rows = g.extract().copy()
     occ = g.occupied().copy()
     verts, tris = g.extract_mesh()
@@ -34,36 +34,6 @@ def _ref(g, rows, occ, verts, stride, tris, pose, **kw):
     return V.cover(rows, occ, verts, stride, tris, pose, tuple(g.cfg.bbox), g.dims[1], **kw)
 
 
-def _same(got, ref, what):
-    (gc, gs), (rc, rs) = got, ref
-    assert len(gc) == len(rc), "%s: %d vs %d records" % (what, len(gc), len(rc))
-    a, b = gc.view(np.uint8).reshape(len(gc), -1), rc.view(np.uint8).reshape(len(rc), -1)
-    bad = np.flatnonzero((a != b).any(axis=1))
-    assert bad.size == 0, "%s: records differ at %d of %d triangles, first %d: %r vs %r" % (what, bad.size, len(gc), bad[0], gc[bad[0]], rc[bad[0]])
-    for k in V.SUMMARY_KEYS:
-        assert gs[k] == rs[k], "%s: summary %s: %r vs %r" % (what, k, gs[k], rs[k])
-
-
-def _device(g, H, d_verts, n_verts, stride, d_tris, n_tris, pose, **kw):
-    """The device form on a mesh in HBM, downloaded: (records, summary)."""
-    c, s = g.cover_mesh(d_verts, d_tris, pose, device=True, n_verts=n_verts, vertex_stride=stride, n_tris=n_tris, **kw)
-    try:
-        cov = g.device_download(c, n_tris * 32).view(H.TRI_COVERAGE_DTYPE) if c else np.zeros(0, H.TRI_COVERAGE_DTYPE)
-    finally:
-        if c:
-            g.device_free(c)
-    return cov, s
-
-
-def _sums(cov, s):
-    for k in ("n_samples", "n_in_bbox", "n_covered", "sum_dist_q30"):
-        assert s[k] == sum(int(x) for x in cov[k]), k
-    valid = (cov["flags"] & V.VALID) != 0
-    assert s["n_tris_valid"] == int(valid.sum()) and s["n_tris_invalid"] == int((~valid).sum())
-    assert s["max_distance"] == (float(cov["max_distance"].max()) if len(cov) else 0.0) and s["pad"] == 0
-    assert not cov[~valid].view(np.uint8).any(), "an invalid triangle's record is all zero"
-
-
 # ---- 1. the model's own mesh, without leaving HBM ----------------------------------------------------------------------
 
 @pytest.mark.parametrize("voxels", [1.0, 0.5])
@@ -74,18 +44,18 @@ def test_own_mesh_device_and_host_forms(hfpf_mod, session, voxels):
     dv, nv, dt, nt = g.extract_mesh_device()
     try:
         assert nv == len(verts) and nt == len(tris)
-        dev = _device(g, hfpf_mod, dv, nv, 32, dt, OWN, IDENT, **kw)
+        dev = cover_device(g, hfpf_mod, dv, nv, 32, dt, OWN, IDENT, **kw)
     finally:
         g.device_free(dv), g.device_free(dt)
     s = dev[1]
     print("own mesh, spacing %.1f voxels: %d samples, %d covered, area %.6f m^2, covered %.6f m^2" % (voxels, s["n_samples"], s["n_covered"], s["area"],
                                                                                                      s["covered_area"]))
-    _same(dev, ref, "device form, spacing %.1f" % voxels)
+    same_coverage(dev, ref, "device form, spacing %.1f" % voxels)
     host = g.cover_mesh(verts, tris[:OWN], IDENT, **kw)
-    _same(host, ref, "host form, spacing %.1f" % voxels)
+    same_coverage(host, ref, "host form, spacing %.1f" % voxels)
     assert host[0].tobytes() == dev[0].tobytes() and host[1] == dev[1]
     assert s["n_covered"] > 0 and s["n_samples"] >= OWN - s["n_tris_invalid"] and s["n_samples"] < 70000
-    _sums(*dev)
+    coverage_sums(*dev)
     assert 0.0 < s["covered_area"] <= s["area"]
 
 
@@ -110,10 +80,10 @@ def test_two_huge_triangles_through_the_box(hfpf_mod, session, max_subdivision):
     got = g.cover_mesh(quad, t2, pose, **kw)
     cov, s = got
     print("quad, cap %d: %d samples, %d in the box, %d covered" % (max_subdivision, s["n_samples"], s["n_in_bbox"], s["n_covered"]))
-    _same(got, _ref(g, rows, occ, quad, 12, t2, pose, **kw), "quad, cap %d" % max_subdivision)
+    same_coverage(got, _ref(g, rows, occ, quad, 12, t2, pose, **kw), "quad, cap %d" % max_subdivision)
     assert (cov["flags"] == V.VALID | V.CAPPED).all() and (cov["n_samples"] == max_subdivision ** 2).all()
     assert 0 < s["n_covered"] < s["n_samples"] and s["n_in_bbox"] < s["n_samples"]
-    _sums(cov, s)
+    coverage_sums(cov, s)
 
 
 # ---- 3. a mixed soup: every n, every lane position of a triangle boundary, every invalid kind ----------------------------
@@ -153,20 +123,16 @@ def test_mixed_soup_with_invalid_triangles(hfpf_mod, session):
     n = np.sqrt(cov["n_samples"]).astype(int)
     print("soup: %d samples, %d in the box, %d covered, %d invalid, n from %d to %d, %d capped" % (
         s["n_samples"], s["n_in_bbox"], s["n_covered"], s["n_tris_invalid"], n[n > 0].min(), n.max(), int(((cov["flags"] & V.CAPPED) != 0).sum())))
-    _same(got, ref, "soup")
-    _sums(cov, s)
+    same_coverage(got, ref, "soup")
+    coverage_sums(cov, s)
     assert s["n_tris_invalid"] == 78 and s["n_tris_valid"] == 777 - 78
     assert n[n > 0].min() == 1 and n.max() == 24 and ((cov["flags"] & V.CAPPED) != 0).any() and len(np.unique(n)) > 12
     assert 0 < s["n_covered"] < s["n_in_bbox"] <= s["n_samples"] < 150000
     # triangle boundaries at every lane position of a wave
     first = np.cumsum(cov["n_samples"].astype(np.int64)) - cov["n_samples"]
     assert len(np.unique(first[cov["n_samples"] > 0] % 64)) == 64
-    dsv, dst = g.device_alloc(sv.nbytes), g.device_alloc(st.nbytes)
-    try:
-        g.device_upload(dsv, sv), g.device_upload(dst, st)
-        _same(_device(g, hfpf_mod, dsv, len(sv), 12, dst, len(st), pose, **kw), ref, "soup, device form")
-    finally:
-        g.device_free(dsv), g.device_free(dst)
+    with uploaded(g, sv, st) as (dsv, dst):
+        same_coverage(cover_device(g, hfpf_mod, dsv, len(sv), 12, dst, len(st), pose, **kw), ref, "soup, device form")
 
 
 # ---- 4. the normal gate ------------------------------------------------------------------------------------------------
@@ -179,7 +145,7 @@ def test_normal_gate_on_the_reversed_own_mesh(hfpf_mod, session):
     for name, kw in (("off", dict(min_normal_dot=-2.0)), ("gate", dict(min_normal_dot=0.5)), ("abs", dict(min_normal_dot=0.5, abs_normal=True))):
         for winding, tt in (("own", tris[:OWN]), ("reversed", back)):
             got = g.cover_mesh(verts, tt, IDENT, **base, **kw)
-            _same(got, _ref(g, rows, occ, verts, 32, tt, IDENT, **base, **kw), "%s, %s winding" % (name, winding))
+            same_coverage(got, _ref(g, rows, occ, verts, 32, tt, IDENT, **base, **kw), "%s, %s winding" % (name, winding))
             res[name, winding] = got[1]["n_covered"]
     print("normal gate: %r" % res)
     for winding in ("own", "reversed"):  # each gate passes a subset of the next
@@ -195,7 +161,7 @@ def test_min_count_above_the_median(hfpf_mod, session):
     kw = dict(radius=2, max_distance=2 * RES, spacing=RES)
     all_rows = g.cover_mesh(verts, tris[:OWN], IDENT, **kw)
     got = g.cover_mesh(verts, tris[:OWN], IDENT, min_count=mc, **kw)
-    _same(got, _ref(g, rows, occ, verts, 32, tris[:OWN], IDENT, min_count=mc, **kw), "min_count %.0f" % mc)
+    same_coverage(got, _ref(g, rows, occ, verts, 32, tris[:OWN], IDENT, min_count=mc, **kw), "min_count %.0f" % mc)
     assert got[0].tobytes() != all_rows[0].tobytes() and 0 < got[1]["n_covered"] < all_rows[1]["n_covered"]
 
 
@@ -206,7 +172,7 @@ def test_translated_mesh_is_not_covered(hfpf_mod, session):
     pose = np.hstack([np.eye(3), [[0.0], [0.0], [10 * RES]]])
     kw = dict(radius=2, max_distance=1.0, spacing=RES)
     got = g.cover_mesh(verts, tris[:OWN], pose, **kw)
-    _same(got, _ref(g, rows, occ, verts, 32, tris[:OWN], pose, **kw), "ten voxels along +z")
+    same_coverage(got, _ref(g, rows, occ, verts, 32, tris[:OWN], pose, **kw), "ten voxels along +z")
     here = g.cover_mesh(verts, tris[:OWN], IDENT, **kw)
     cov, s = got
     assert s["n_covered"] == 0 and s["sum_dist_q30"] == 0 and s["max_distance"] == 0.0 and s["covered_q40_lo"] == 0 and s["covered_q40_hi"] == 0
@@ -228,14 +194,14 @@ def test_empty_and_edge_cases_leave_the_handle_usable(hfpf_mod, session):
     ptr, s = g.cover_mesh(0, 0, IDENT, device=True, n_verts=0, vertex_stride=12, n_tris=0)
     assert ptr == 0 and {k: s[k] for k in V.SUMMARY_KEYS} == zero
     kw = dict(radius=2, max_distance=2 * RES, spacing=RES)
-    with _grid(H) as fresh:
+    with grid(H) as fresh:
         no_rows, no_occ = np.zeros(0, H.ROW_DTYPE), np.zeros((0, 3), np.int32)
         ref = V.cover(no_rows, no_occ, tri1[0], 12, tri1[1], IDENT, tuple(fresh.cfg.bbox), fresh.dims[1], **kw)
         got = fresh.cover_mesh(*tri1, IDENT, **kw)
-        _same(got, ref, "a fresh handle")
+        same_coverage(got, ref, "a fresh handle")
         assert got[0]["n_in_bbox"][0] == got[0]["n_samples"][0] > 1 and got[1]["n_covered"] == 0 and got[1]["n_tris_valid"] == 1
         sc.integrate(fresh, 0)  # points, but no clean pass yet
-        _same(fresh.cover_mesh(*tri1, IDENT, **kw), ref, "frames but no clean pass")
+        same_coverage(fresh.cover_mesh(*tri1, IDENT, **kw), ref, "frames but no clean pass")
     # every BAD_ARG of include/hfpf.h
     L, h = H.lib(), g._h
     v, t = np.ascontiguousarray(tri1[0]), np.ascontiguousarray(tri1[1])
@@ -283,12 +249,12 @@ def test_cover_is_read_only_and_survives_a_restore(hfpf_mod, session):
     sc, g, rows, occ, verts, tris = session
     sv, st = soup(rows, _rigid())
     kw = dict(radius=2, max_distance=2 * RES, spacing=RES, max_subdivision=24, min_normal_dot=0.2)
-    before = (_counters(g), g.extract().tobytes(), g.occupied().tobytes())
+    before = (counters(g), g.extract().tobytes(), g.occupied().tobytes())
     own = g.cover_mesh(verts, tris[:OWN], IDENT, **kw)
     mixed = g.cover_mesh(sv, st, _rigid(), **kw)
-    assert (_counters(g), g.extract().tobytes(), g.occupied().tobytes()) == before
+    assert (counters(g), g.extract().tobytes(), g.occupied().tobytes()) == before
     blob = g.snapshot()
-    with _grid(hfpf_mod) as g2:
+    with grid(hfpf_mod) as g2:
         g2.restore(blob)
         for got, want, what in ((g2.cover_mesh(verts, tris[:OWN], IDENT, **kw), own, "own mesh"), (g2.cover_mesh(sv, st, _rigid(), **kw), mixed, "soup")):
             assert got[0].tobytes() == want[0].tobytes() and got[1] == want[1], "%s on the restored handle" % what

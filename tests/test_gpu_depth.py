@@ -12,64 +12,32 @@ import pytest
 
 import depth_ref as R
 import scenes
+from gpu_support import BBOX, DEPTH_CAPS, counters, grid, run, same_records
+from scenes import DepthScene
 
 pytestmark = pytest.mark.gpu
-CAPS = dict(max_bricks=120000, max_log_points=8 << 20, max_normals=1 << 21, max_frames=4096)
-BBOX = scenes.BBOX_1M
 
 
-def _counters(g):
-    c = g.counters()
-    c.pop("device_bytes")  # the frame ring is sized by the bytes of a frame: ~5 per pixel instead of 16
-    # how the binned update scheduled its work: depends on how host frames happened to be batched, not on what was fused
-    for k in ("points_direct", "table_misses", "update_extra_rounds"):
-        c.pop(k)
-    return c
-
-
-class DepthScene:
-    """A seeded stream of synthetic depth frames (uint16 + RGB8) with random poses and a clean schedule."""
-
-    def __init__(self, n_frames, W, H, clean_every=4, depth_scale=0.001, seed=0xD3F7, pose_seed=0x5E3):
-        import hfpf_synth as S
-        self.n_frames, self.W, self.H, self.clean_every, self.depth_scale = n_frames, W, H, clean_every, depth_scale
-        self.poses = [S.pose(pose_seed, f) for f in range(n_frames)]
-        self.frames = [S.depth_frame(seed, f, W, H, self.poses[f], depth_scale=depth_scale) for f in range(n_frames)]
-
-    def schedule(self):
-        return scenes.Scene.schedule(self)
-
-    def cloud(self, f):
-        depth, rgb, K = self.frames[f]
-        return R.packed_cloud(depth, K, rgb, R.COLOR_RGB8, self.depth_scale)
-
-
-def _run(g, sc, integrate):
-    for ev in sc.schedule():
-        if ev[0] == "integrate":
-            integrate(g, ev[1])
-        else:
-            g.clean()
-    return g.extract(), _counters(g)
+def _result(g):
+    return g.extract(), counters(g)
 
 
 def _cloud_session(hfpf_mod, sc, clouds=None, **kw):
     clouds = clouds or [sc.cloud(f) for f in range(sc.n_frames)]
-    with hfpf_mod.OccupancyGrid(resolution=kw.pop("resolution", 0.002), bbox=BBOX, fuse_color=kw.pop("fuse_color", True), **CAPS, **kw) as g:
-        return _run(g, sc, lambda g, f: g.integrate(clouds[f], sc.poses[f]))
+    with hfpf_mod.OccupancyGrid(resolution=kw.pop("resolution", 0.002), bbox=BBOX, fuse_color=kw.pop("fuse_color", True), **DEPTH_CAPS, **kw) as g:
+        run(g, sc, integrate=lambda g, f: g.integrate(clouds[f], sc.poses[f]))
+        return _result(g)
 
 
 def _depth_session(hfpf_mod, sc, **kw):
-    def step(g, f):
-        depth, rgb, K = sc.frames[f]
-        g.integrate_depth(depth, sc.poses[f], K, color=rgb, depth_scale=sc.depth_scale)
-    with hfpf_mod.OccupancyGrid(resolution=kw.pop("resolution", 0.002), bbox=BBOX, fuse_color=kw.pop("fuse_color", True), **CAPS, **kw) as g:
-        return _run(g, sc, step)
+    with hfpf_mod.OccupancyGrid(resolution=kw.pop("resolution", 0.002), bbox=BBOX, fuse_color=kw.pop("fuse_color", True), **DEPTH_CAPS, **kw) as g:
+        run(g, sc)
+        return _result(g)
 
 
 def _same(a, b):
     assert a[1] == b[1], "counters differ: %s vs %s" % (a[1], b[1])
-    assert len(a[0]) == len(b[0]) and a[0].tobytes() == b[0].tobytes(), "rows differ"
+    same_records(a[0], b[0], "rows", "rows")
 
 
 # ---- leaf -----------------------------------------------------------------------------------------------------------
@@ -85,7 +53,7 @@ def _probe_equal(g, depth, K, color=None, color_format=None, depth_scale=0.001):
 
 def test_probe_depth_bit_exact(hfpf_mod):
     rng = np.random.default_rng(7)
-    with hfpf_mod.OccupancyGrid(**CAPS) as g:
+    with hfpf_mod.OccupancyGrid(**DEPTH_CAPS) as g:
         all_counts = np.arange(65536, dtype=np.uint32).astype(np.uint16).reshape(256, 256)  # every count; corners included
         for scale, K in ((0.001, (615.0, 615.0, 319.5, 239.5)), (0.00025, (612.31, 608.93, 121.37, 144.81)),
                          (0.0001, (1000.1, 999.7, 300.3, -17.9)), (0.0010000000474974513, (201.0, 203.5, 0.0, 255.0))):
@@ -138,7 +106,7 @@ def test_pinned_and_device_batches_equal_pageable(hfpf_mod, synth_mod):
     sc = DepthScene(8, 320, 240, clean_every=4)
     ref = _depth_session(hfpf_mod, sc)
     # pinned: views of page-locked buffers, untouched until the session syncs
-    with hfpf_mod.OccupancyGrid(resolution=0.002, bbox=BBOX, fuse_color=True, **CAPS) as g:
+    with grid(hfpf_mod) as g:
         bufs = []
 
         def pinned(g, f):
@@ -150,7 +118,8 @@ def test_pinned_and_device_batches_equal_pageable(hfpf_mod, synth_mod):
             c[...] = rgb
             bufs.extend((bd, bc))
             g.integrate_depth_pinned(d, sc.poses[f], K, color=c)
-        got = _run(g, sc, pinned)
+        run(g, sc, integrate=pinned)
+        got = _result(g)
         for b in bufs:
             g.host_free(b)
     _same(got, ref)
@@ -158,7 +127,7 @@ def test_pinned_and_device_batches_equal_pageable(hfpf_mod, synth_mod):
     rng = np.random.default_rng(3)
     depth0, rgb0, K = sc.frames[0]
     dstride, cstride = (depth0.nbytes + 255) & ~255, (rgb0.nbytes + 255) & ~255
-    with hfpf_mod.OccupancyGrid(resolution=0.002, bbox=BBOX, fuse_color=True, **CAPS) as g:
+    with grid(hfpf_mod) as g:
         dd, dc = g.device_alloc(dstride * sc.n_frames), g.device_alloc(cstride * sc.n_frames)
         desc = hfpf_mod.depth_desc(sc.W, sc.H, hfpf_mod.DEPTH_U16, sc.W * 2, K, hfpf_mod.COLOR_RGB8, sc.W * 3)
         for start in range(0, sc.n_frames, 4):
@@ -169,7 +138,7 @@ def test_pinned_and_device_batches_equal_pageable(hfpf_mod, synth_mod):
             g.integrate_depth_device(desc, dd, dstride, 4, np.stack([sc.poses[f].reshape(12) for f in ids]), dev_color=dc,
                                      color_frame_stride=cstride, frame_ids=ids)
             g.clean()
-        got = g.extract(), _counters(g)
+        got = _result(g)
         g.device_free(dd)
         g.device_free(dc)
     _same(got, ref)
@@ -179,20 +148,25 @@ _CHILD = textwrap.dedent("""
     import sys
     sys.path[:0] = sys.argv[1].split(":")
     import numpy as np
-    import test_gpu_depth as T
+    import gpu_support as T
     import hfpf
-    sc = T.DepthScene(10, 160, 128, clean_every=5)
+    from scenes import DepthScene
+    sc = DepthScene(10, 160, 128, clean_every=5)
     clouds = [sc.cloud(f) for f in range(sc.n_frames)]
-    ref = T._cloud_session(hfpf, sc, clouds)
+    def session(integrate):
+        with T.grid(hfpf) as g:
+            T.run(g, sc, integrate=integrate)
+            return g.extract(), T.counters(g)
+    ref = session(lambda g, f: g.integrate(clouds[f], sc.poses[f]))
     def mixed(g, f):
         depth, rgb, K = sc.frames[f]
         if f % 3 == 1:
             g.integrate(clouds[f], sc.poses[f])
         else:
             g.integrate_depth(depth, sc.poses[f], K, color=rgb)
-    with hfpf.OccupancyGrid(resolution=0.002, bbox=T.BBOX, fuse_color=True, **T.CAPS) as g:
-        got = T._run(g, sc, mixed)
-    T._same(got, ref)
+    got = session(mixed)
+    assert got[1] == ref[1], "counters differ: %s vs %s" % (got[1], ref[1])
+    T.same_records(got[0], ref[0], "rows", "rows")
     print("mixed ok", len(got[0]))
 """)
 
@@ -209,9 +183,10 @@ def test_interleaved_cloud_and_depth_frames_equal_all_cloud(hfpf_mod, synth_mod,
 def _variant(hfpf_mod, sc, make, fuse_color=True):
     """make(f) -> (depth, K, color, color_format, depth_scale, cloud): the depth path against the cloud path."""
     items = [make(f) for f in range(sc.n_frames)]
-    with hfpf_mod.OccupancyGrid(resolution=0.002, bbox=BBOX, fuse_color=fuse_color, **CAPS) as g:
-        got = _run(g, sc, lambda g, f: g.integrate_depth(items[f][0], sc.poses[f], items[f][1], color=items[f][2],
-                                                          color_format=items[f][3], depth_scale=items[f][4]))
+    with hfpf_mod.OccupancyGrid(resolution=0.002, bbox=BBOX, fuse_color=fuse_color, **DEPTH_CAPS) as g:
+        run(g, sc, integrate=lambda g, f: g.integrate_depth(items[f][0], sc.poses[f], items[f][1], color=items[f][2],
+                                                            color_format=items[f][3], depth_scale=items[f][4]))
+        got = _result(g)
     ref = _cloud_session(hfpf_mod, sc, [it[5] for it in items], fuse_color=fuse_color)
     _same(got, ref)
     assert got[1]["points_in_bbox"] > 0
@@ -284,7 +259,7 @@ def test_bad_arguments_are_refused_and_the_handle_stays_usable(hfpf_mod, synth_m
         (desc(struct_size=64), p(depth), p(rgb)), (desc(reserved=1), p(depth), p(rgb)),
         (desc(), None, p(rgb)), (desc(), p(depth), None), (desc(color_format=hfpf_mod.COLOR_NONE), p(depth), p(rgb)),
     ]
-    with hfpf_mod.OccupancyGrid(resolution=0.002, bbox=BBOX, fuse_color=True, **CAPS) as g:
+    with grid(hfpf_mod) as g:
         for d, dp, cp in bad:
             assert L.hfpf_integrate_depth(g._h, C.byref(d), dp, cp, p(pose)) == -2, (d.width, d.depth_step, d.color_format)
             assert L.hfpf_probe_depth(g._h, C.byref(d), dp, cp, p(np.zeros(3 * 64 * 48, np.float32)), p(np.zeros(64 * 48, np.uint32))) == -2
@@ -299,7 +274,7 @@ def test_bad_arguments_are_refused_and_the_handle_stays_usable(hfpf_mod, synth_m
         g.integrate_depth(depth, sc.poses[0], K, color=rgb)
         g.integrate_depth(sc.frames[1][0], sc.poses[1], K, color=sc.frames[1][1])
         g.clean()
-        got = g.extract(), _counters(g)
+        got = _result(g)
     _same(got, _cloud_session(hfpf_mod, sc))
 
 
@@ -312,7 +287,7 @@ def test_node_depth_callback_writes_the_same_files(tmp_path, hfpf_mod, synth_mod
         d = tmp_path / kind
         d.mkdir()
         with hfpf_node.FusionNode(bounding_box=list(BBOX), directory_name=str(d), fusion_frame="base_link",
-                                  tf_lookup=lambda t, s: poses[(t, s)], clean_period_s=0.0, resolution=0.002, **CAPS) as node:
+                                  tf_lookup=lambda t, s: poses[(t, s)], clean_period_s=0.0, resolution=0.002, **DEPTH_CAPS) as node:
             depth, rgb, K = sc.frames[0]
             assert (node.publish_depth(depth, K, color=rgb, frame_id="camera_0") if kind == "depth" else
                     node.publish(sc.cloud(0), 1, sc.W * sc.H, frame_id="camera_0")) == 0  # not started
@@ -337,7 +312,7 @@ def test_two_virtual_ranks_equal_one_handle(hfpf_mod, synth_mod):
     import hfpf_dist
     sc = DepthScene(6, 160, 128, clean_every=3)
     ref = _depth_session(hfpf_mod, sc)
-    grids = [hfpf_mod.OccupancyGrid(resolution=0.002, bbox=BBOX, fuse_color=True, **CAPS) for _ in range(2)]
+    grids = [grid(hfpf_mod) for _ in range(2)]
     vr = hfpf_dist.LocalVirtualRanks(grids)
     depth0, rgb0, K = sc.frames[0]
     desc = hfpf_mod.depth_desc(sc.W, sc.H, hfpf_mod.DEPTH_U16, sc.W * 2, K, hfpf_mod.COLOR_RGB8, sc.W * 3)

@@ -12,47 +12,23 @@ import numpy as np
 import pytest
 
 import deviation_ref as D
-from test_gpu_render import BBOX, RES, DepthScene, _counters, _grid, _run
+from gpu_support import BBOX, IDENT, RES, compare_device, counters, grid, run, same_deviation
+from scenes import DepthScene
 
 pytestmark = pytest.mark.gpu
-IDENT = np.eye(4)[:3]
-SUMMARY = ("n_rows", "n_found", "n_negative", "n_tris_valid", "n_tris_invalid", "max_abs", "pad", "sum_abs_q30", "sum_sq_q30")
 
 
 @pytest.fixture(scope="module")
 def session(hfpf_mod, synth_mod):
     sc = DepthScene(3, 160, 120, clean_every=2)
-    g = _grid(hfpf_mod)
-    _run(g, sc)
+    g = grid(hfpf_mod)
+    run(g, sc)
     rows = g.extract().copy()
     verts, tris = g.extract_mesh()
     print("session: %d rows, own mesh %d vertices / %d triangles" % (len(rows), len(verts), len(tris)))
     assert len(rows) > 1000 and len(tris) > 1000
     yield sc, g, rows, verts, tris
     g.close()
-
-
-def _same(got, ref, what):
-    (gd, gs), (rd, rs) = got, ref
-    assert len(gd) == len(rd), "%s: %d vs %d rows" % (what, len(gd), len(rd))
-    a, b = gd.view(np.uint8).reshape(len(gd), -1), rd.view(np.uint8).reshape(len(rd), -1)
-    bad = np.flatnonzero((a != b).any(axis=1))
-    assert bad.size == 0, "%s: records differ at %d of %d rows, first %d: %r vs %r" % (what, bad.size, len(gd), bad[0], gd[bad[0]], rd[bad[0]])
-    for k in SUMMARY:
-        assert gs[k] == rs[k], "%s: summary %s: %r vs %r" % (what, k, gs[k], rs[k])
-
-
-def _device(g, H, d_verts, n_verts, stride, d_tris, n_tris, pose, rows=False, **kw):
-    """The device form on a mesh in HBM, downloaded: (dev, summary) or (rows, dev, summary)."""
-    r, d, nr, s = g.compare_mesh(d_verts, d_tris, pose, device=True, rows=rows, n_verts=n_verts, vertex_stride=stride, n_tris=n_tris, **kw)
-    try:
-        dev = g.device_download(d, nr * 32).view(H.DEVIATION_DTYPE) if nr else np.zeros(0, H.DEVIATION_DTYPE)
-        out_rows = g.device_download(r, nr * 64).view(H.ROW_DTYPE) if rows and nr else None
-    finally:
-        for p in (r, d):
-            if p:
-                g.device_free(p)
-    return (out_rows, dev, s) if rows else (dev, s)
 
 
 # ---- 1. the model's own mesh, without leaving HBM ----------------------------------------------------------------------
@@ -67,15 +43,15 @@ def test_own_mesh_device_and_host_forms(hfpf_mod, session, voxels):
     dv, nv, dt, nt = g.extract_mesh_device()
     try:
         assert nv == len(verts) and nt == len(tris)
-        got_rows, dev, s = _device(g, hfpf_mod, dv, nv, 32, dt, nt, IDENT, rows=True, max_distance=md)
+        got_rows, dev, s = compare_device(g, hfpf_mod, dv, nv, 32, dt, nt, IDENT, rows=True, max_distance=md)
     finally:
         g.device_free(dv), g.device_free(dt)
     print("own mesh, %d voxels: found %d of %d, max %.6f, rms %.6f" % (voxels, s["n_found"], s["n_rows"], s["max_abs"],
                                                                        (s["sum_sq_q30"] / 2.0 ** 30 / max(1, s["n_found"])) ** 0.5))
-    _same((dev, s), ref, "device form, %d voxels" % voxels)
+    same_deviation((dev, s), ref, "device form, %d voxels" % voxels)
     assert got_rows.tobytes() == rows.tobytes()
     host = g.compare_mesh(verts, tris, IDENT, max_distance=md)
-    _same(host, ref, "host form, %d voxels" % voxels)
+    same_deviation(host, ref, "host form, %d voxels" % voxels)
     # not a fidelity bound (DESIGN.md states the measured figures): the mesh is the rows' own surface, so a compare that finds less than
     # half of them within 3 voxels would be testing the "not found" path only
     assert s["n_found"] > 0.5 * len(rows)
@@ -89,7 +65,7 @@ def test_min_count_gates_the_row_set(hfpf_mod, session):
     assert 0 < len(gated) < len(rows)
     sv, st = soup(rows, 2000, seed=0x3C)
     got = g.compare_mesh(sv, st, IDENT, min_count=2.0, max_distance=5 * RES)
-    _same(got, D.compare(rows, sv, 12, st, IDENT, 2.0, 5 * RES), "min_count 2")
+    same_deviation(got, D.compare(rows, sv, 12, st, IDENT, 2.0, 5 * RES), "min_count 2")
     assert got[1]["n_rows"] == len(gated)
 
 
@@ -106,7 +82,7 @@ def test_two_huge_triangles_through_the_box(hfpf_mod, session):
     t2 = np.array([[0, 1, 2], [0, 2, 3]], np.uint32)
     for voxels in (4, 32):
         got = g.compare_mesh(quad, t2, pose, max_distance=voxels * RES)
-        _same(got, D.compare(rows, quad, 12, t2, pose, 0.0, voxels * RES), "quad, %d voxels" % voxels)
+        same_deviation(got, D.compare(rows, quad, 12, t2, pose, 0.0, voxels * RES), "quad, %d voxels" % voxels)
         print("quad, %d voxels: found %d of %d, negative %d" % (voxels, got[1]["n_found"], len(rows), got[1]["n_negative"]))
         assert 0 < got[1]["n_found"] < len(rows) and 0 < got[1]["n_negative"] < got[1]["n_found"]
         assert set(np.unique(got[0]["tri"])) == {0, 1, D.NO_TRI}
@@ -140,7 +116,7 @@ def test_soup_with_invalid_triangles(hfpf_mod, session):
         ref = D.compare(rows, sv, 12, st, IDENT, 0.0, voxels * RES)
         got = g.compare_mesh(sv, st, IDENT, max_distance=voxels * RES)
         print("soup, %d voxels: found %d of %d, invalid %d" % (voxels, got[1]["n_found"], len(rows), got[1]["n_tris_invalid"]))
-        _same(got, ref, "soup, %d voxels" % voxels)
+        same_deviation(got, ref, "soup, %d voxels" % voxels)
         assert got[1]["n_tris_invalid"] == 200 and got[1]["n_tris_valid"] == 4800 and got[1]["n_found"] > 0
     flags = got[0]["flags"][(got[0]["flags"] & 1) != 0]
     assert {1, 3, 5} == set(np.unique(flags)), "face, edge and vertex regions all occur"
@@ -166,19 +142,19 @@ def test_crowd_across_tiles_and_after_a_restore(hfpf_mod, session):
     ref = D.compare(rows, cv, 12, ct, IDENT, 0.0, md)
     got = g.compare_mesh(cv, ct, IDENT, max_distance=md)
     print("crowd: %d rows in the brick, found %d" % (in_brick, got[1]["n_found"]))
-    _same(got, ref, "crowd, default tile")
+    same_deviation(got, ref, "crowd, default tile")
     assert got[1]["n_found"] >= in_brick // 2
     own = g.compare_mesh(verts, tris, IDENT, max_distance=3 * RES)
     blob = g.snapshot()
     os.environ["HFPF_TEST_DEV_TILE"] = "32"
     try:
-        g2 = _grid(hfpf_mod)
+        g2 = grid(hfpf_mod)
     finally:
         del os.environ["HFPF_TEST_DEV_TILE"]
     try:
         g2.restore(blob)
-        _same(g2.compare_mesh(cv, ct, IDENT, max_distance=md), got, "crowd, tile 32, restored handle")
-        _same(g2.compare_mesh(verts, tris, IDENT, max_distance=3 * RES), own, "own mesh, tile 32, restored handle")
+        same_deviation(g2.compare_mesh(cv, ct, IDENT, max_distance=md), got, "crowd, tile 32, restored handle")
+        same_deviation(g2.compare_mesh(verts, tris, IDENT, max_distance=3 * RES), own, "own mesh, tile 32, restored handle")
     finally:
         g2.close()
 
@@ -206,7 +182,7 @@ def test_empty_and_edge_cases_leave_the_handle_usable(hfpf_mod, session):
     assert len(dev) == 0 and s["n_rows"] == 0 and s["n_found"] == 0 and s["n_tris_valid"] + s["n_tris_invalid"] == len(tris)
     r, d, nr, s = g.compare_mesh(0, 0, IDENT, device=True, rows=True, n_verts=0, vertex_stride=12, n_tris=0, min_count=1e9)
     assert (r, d, nr) == (0, 0, 0)
-    with _grid(H) as fresh:
+    with grid(H) as fresh:
         dev, s = fresh.compare_mesh(*tri1, IDENT)
         assert len(dev) == 0 and s["n_rows"] == 0 and s["n_tris_valid"] == 1
         sc.integrate(fresh, 0)  # points, but no clean pass yet
@@ -253,7 +229,7 @@ def test_empty_and_edge_cases_leave_the_handle_usable(hfpf_mod, session):
 
 def test_compare_is_read_only_and_timed(hfpf_mod, session):
     sc, g, rows, verts, tris = session
-    before = (_counters(g), g.extract().tobytes(), g.occupied().tobytes())
+    before = (counters(g), g.extract().tobytes(), g.occupied().tobytes())
     g.kernel_timing(True)
     try:
         g.compare_mesh(verts, tris, IDENT, max_distance=3 * RES)
@@ -261,4 +237,4 @@ def test_compare_is_read_only_and_timed(hfpf_mod, session):
     finally:
         g.kernel_timing(False)
     assert n == 1 and ms > 0
-    assert (_counters(g), g.extract().tobytes(), g.occupied().tobytes()) == before
+    assert (counters(g), g.extract().tobytes(), g.occupied().tobytes()) == before

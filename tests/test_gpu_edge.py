@@ -6,16 +6,16 @@ import numpy as np
 import pytest
 
 import scenes
+from gpu_support import SMALL_CAPS
 
 pytestmark = pytest.mark.gpu
-SMALL = dict(max_bricks=60000, max_log_points=4 << 20, max_normals=1 << 20, max_frames=4096)
 
 
 def _pair(oracle_mod, hfpf_mod, sc, **cfg):
     og = oracle_mod.OracleGrid(resolution=sc.resolution, bbox=sc.bbox, **cfg)
     ref = scenes.run(og, sc, "capture")
     occ_ref = og.occupied()
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **cfg, **SMALL) as eg:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **cfg, **SMALL_CAPS) as eg:
         got = scenes.run(eg, sc, "integrate")
         occ = eg.occupied()
     assert np.array_equal(occ_ref, occ)
@@ -56,7 +56,7 @@ def test_empty_nan_and_fully_clipped_frames(oracle_mod, hfpf_mod, synth_mod):
     nan_frame = np.full((n, 4), np.nan, np.float32)
     far_frame = np.zeros((n, 4), np.float32)
     far_frame[:, 2] = 2.0  # beyond the z-clip
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as g:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as g:
         g.integrate(np.zeros(0, np.uint8), sc.poses[0], n_points=0)
         assert g.state_changed
         g.integrate(nan_frame, sc.poses[0])
@@ -85,7 +85,7 @@ def test_explicit_frame_ids_out_of_order(oracle_mod, hfpf_mod, synth_mod):
         og.capture(sc.frame(f), sc.poses[f])
     og.clean()
     fb = sc.W * sc.H * 16
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as g:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as g:
         dev = g.device_alloc(fb)
         for f in (3, 1, 2, 0):
             g.device_upload(dev, sc.frame(f))
@@ -118,7 +118,7 @@ def test_capacity_errors_are_reported_not_fatal(hfpf_mod, synth_mod):
             g.integrate(sc.frame(1), sc.poses[1])
         assert e.value.code == -3
     # misaligned record layout
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as g:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as g:
         with pytest.raises(hfpf_mod.HfpfError) as e:
             g.integrate(sc.frame(0), sc.poses[0], point_step=18, off_x=1, off_y=5, off_z=9, off_rgb=13)
         assert e.value.code == -2
@@ -129,12 +129,12 @@ def test_concurrent_callers_are_serialised_and_order_free(hfpf_mod, synth_mod):
     node.cpp:291); integer sums make the result independent of the interleaving."""
     sc = scenes.Scene(8, 160, 120, 0.005)
     fb = sc.W * sc.H * 16
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as a:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as a:
         for f in range(8):
             a.integrate(sc.frame(f), sc.poses[f])
         a.clean()
         ref = a.extract()
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as b:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as b:
         devs = [b.device_alloc(fb) for _ in range(8)]
         for f in range(8):
             b.device_upload(devs[f], sc.frame(f))
@@ -164,10 +164,10 @@ def test_pinned_host_entry_point_matches_bounce_path(hfpf_mod, synth_mod):
     hfpf_integrate (bounce copy) frame by frame, with more frames in flight than the staging ring has slots; a pageable buffer
     is refused."""
     sc = scenes.Scene(12, 160, 120, 0.001, fx=615.0, clean_every=5)
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as a:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as a:
         ref = scenes.run(a, sc, "integrate")
     fb = sc.W * sc.H * 16
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as g:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as g:
         pinned = g.host_alloc(sc.n_frames * fb)
         for f in range(sc.n_frames):
             pinned[f * fb:(f + 1) * fb] = sc.frame(f)

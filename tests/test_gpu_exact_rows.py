@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 import scenes
-from test_gpu_parity import SMALL
-from test_stats_ref import STRADDLE_SCENE
+from gpu_support import IDENT, SMALL_CAPS, run_virtual
+from stats_ref import STRADDLE_SCENE
 
 pytestmark = pytest.mark.gpu
 
@@ -30,7 +30,7 @@ def _oracle(oracle_mod, sc, key, **cfg):
 
 def _check(oracle_mod, hfpf_mod, sc, key, engine_kw=None, **cfg):
     ref, exact, mom = _oracle(oracle_mod, sc, key, **cfg)
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **cfg, **(engine_kw or {}), **SMALL) as eg:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **cfg, **(engine_kw or {}), **SMALL_CAPS) as eg:
         got = scenes.run(eg, sc, "integrate")
     scenes.compare_rows(ref, got)
     rep = scenes.compare_rows_exact(exact, got, cylinder_radius=cfg.get("cylinder_radius", 0.001))
@@ -133,10 +133,9 @@ RANKS_SCENE = dict(n_frames=7, W=160, H=120, resolution=0.001, fx=615.0, clean_e
 
 def test_two_virtual_ranks(oracle_mod, hfpf_mod, synth_mod):
     """Each rank holds partial words; they are summed at extract."""
-    from test_gpu_multirank import _run_virtual
     sc = scenes.Scene(**RANKS_SCENE)
     ref, exact, mom = _oracle(oracle_mod, sc, "ranks")
-    rows, occ, ctrs = _run_virtual(hfpf_mod, sc, 2)
+    rows, occ, ctrs = run_virtual(hfpf_mod, sc, 2)
     assert all(c["frames_integrated"] > 0 for c in ctrs)
     scenes.compare_rows(ref, rows)
     assert scenes.compare_rows_exact(exact, rows)["exact_bytes_differing"] == 0
@@ -150,10 +149,9 @@ def test_query_winner_rows(oracle_mod, hfpf_mod, synth_mod):
     live = exact[exact["count"] > 0]
     rng = np.random.default_rng(0xE7AC)
     pts = (np.stack([live["x"], live["y"], live["z"]], axis=1) + rng.normal(0.0, 0.0005, (len(live), 3))).astype(np.float32)
-    ident = np.hstack([np.eye(3), np.zeros((3, 1))])
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as eg:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as eg:
         scenes.run(eg, sc, "integrate")
-        hits, rows = eg.query(pts, ident, radius=1, rows=True)
+        hits, rows = eg.query(pts, IDENT, radius=1, rows=True)
     found = rows["ix"] >= 0
     assert found.sum() > 10000
     rows = rows[found]

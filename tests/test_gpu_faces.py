@@ -13,26 +13,17 @@ import components_ref as CR
 import cover_ref as V
 import deviation_ref as D
 import faces
+import gpu_support as G
 import mesh_ref as M
 import query_ref as Q
 import raycast_ref as RC
 import render_ref as R
 import scenes
-from test_align_ref import corner_displacement, rigid
-from test_gpu_align import _equal as align_equal, _fitted
-from test_gpu_components import _device as comp_device, _same as comp_same
-from test_gpu_cover import _device as cover_device, _same as cover_same, _sums
-from test_gpu_deviation import _device as dev_device, _same as dev_same
-from test_gpu_mesh import _device as mesh_device, _same as mesh_same
-from test_gpu_query import _same as query_same
-from test_gpu_raycast import _device_rays, _same as ray_same
-from test_gpu_render import _counters, _same as render_same
-import test_gpu_track as TT
 import track_ref as TR
+from gpu_support import IDENT
 
 pytestmark = pytest.mark.gpu
 INF = float("inf")
-IDENT = faces.IDENT
 NAMES = faces.NAMES                        # every read-out
 HOT_NAMES = faces.NAMES + faces.HOT_NAMES  # hot path, query and mesh
 STEP = 0.5
@@ -41,7 +32,7 @@ STEP = 0.5
 class Session:
     """One scene fused on the engine with colour, its rows and occupied list, and what the read-out tests share of it."""
 
-    def __init__(self, hfpf_mod, name, caps=faces.CAPS):
+    def __init__(self, hfpf_mod, name, caps=G.SMALL_CAPS):
         self.name, self.H = name, hfpf_mod
         self.sc = faces.FaceScene(name)
         self.bbox = self.sc.bbox
@@ -50,7 +41,7 @@ class Session:
         self.occ = self.g.occupied().copy()
         self.dims, self.res = self.g.dims
         faces.check_conditions(name, self.rows, self.occ, self.dims)
-        self.counters = _counters(self.g)
+        self.counters = G.counters(self.g)
         for a in (self.rows, self.occ):
             a.setflags(write=False)
         self._mesh = None
@@ -134,7 +125,7 @@ def test_query(sessions, name, opt):
     on_face = found & faces.in_face_layer(got[0]["row_voxel"], s.dims)
     print("%s %r: %d points, %d in the box, %d of them in a cell of index dim (%d occupied), %d found, %d of them a face-layer row" % (
         name, opt, len(pts), (f & Q.IN_BBOX != 0).sum(), at_dim.sum(), (f[at_dim] & Q.OCCUPIED != 0).sum(), found.sum(), on_face.sum()))
-    query_same(got, ref, "%s %r" % (name, opt))
+    G.same_query(got, ref, "%s %r" % (name, opt))
     if name in faces.DYADIC:  # max = min + dim * res exactly: no point of the box has an index == dim
         assert not at_dim.any()
     else:
@@ -162,8 +153,8 @@ def test_mesh(sessions, name, opt):
     kw = dict(radius=opt[0], min_count=opt[1])
     rv, rt, sizes, (ea, eb) = M.mesh(s.rows, s.occ, s.bbox, s.res, s.dims, with_ends=True, **kw)
     host = s.g.extract_mesh(**kw)
-    mesh_same(host, (rv, rt), "%s, host form %r" % (name, opt))
-    mesh_same(mesh_device(s.g, **kw), (rv, rt), "%s, device form %r" % (name, opt))
+    G.same_mesh(host, (rv, rt), "%s, host form %r" % (name, opt))
+    G.same_mesh(G.mesh_device(s.g, **kw), (rv, rt), "%s, device form %r" % (name, opt))
     v, t = host
     assert len(t) > 1000 and t.max() < len(v), "a triangle index out of range"
     lo, hi = faces.lo_hi(s.bbox)
@@ -211,8 +202,8 @@ def test_raycast(sessions, name, opt):
     on_face = faces.in_face_layer(ref["row_voxel"][hit], s.dims).sum()
     print("%s %r: %d rays, %d samples a ray, %d hits (%d on a face-layer row), %d near without a hit" % (
         name, opt, len(rays), RC.n_samples(0.0, kw["t_range"][1], STEP, s.res), hit.sum(), on_face, ((ref["flags"] & RC.NEAR != 0) & ~hit).sum()))
-    ray_same(s.g.raycast(rays, IDENT, **kw), ref, "%s, host form %r" % (name, opt))
-    ray_same(_device_rays(s.g, rays, IDENT, **kw), ref, "%s, device form %r" % (name, opt))
+    G.same_rays(s.g.raycast(rays, IDENT, **kw), ref, "%s, host form %r" % (name, opt))
+    G.same_rays(G.rays_device(s.g, rays, IDENT, **kw), ref, "%s, device form %r" % (name, opt))
     assert hit.sum() >= 200 and on_face >= 1
 
 
@@ -225,7 +216,7 @@ def test_raycast_view_through_a_face(sessions, name):
     ref = RC.raycast_view(s.rows, s.occ, pose, K, 160, 120, s.bbox, s.res, **kw)
     hit = ref["flags"] & RC.HIT != 0
     print("%s: view of 160 x 120 from outside the z-min face: %d hits" % (name, hit.sum()))
-    ray_same(s.g.raycast_view(pose, K, 160, 120, **kw), ref, "%s, view" % name)
+    G.same_rays(s.g.raycast_view(pose, K, 160, 120, **kw), ref, "%s, view" % name)
     assert hit.sum() >= 200
 
 
@@ -244,8 +235,8 @@ def test_components(sessions, name, opt):
     got = s.g.extract_components(**kw)
     print("%s %r: %d of %d rows kept in %d components, largest %d" % (name, opt, len(got[0]), len(s.rows), len(got[2]),
                                                                       got[2]["n_rows"].max() if len(got[2]) else 0))
-    comp_same(got, ref, "%s %r" % (name, opt))
-    comp_same(comp_device(s.g, s.H, **kw), ref, "%s, device form %r" % (name, opt))
+    G.same_components(got, ref, "%s %r" % (name, opt))
+    G.same_components(G.components_device(s.g, s.H, **kw), ref, "%s, device form %r" % (name, opt))
     assert len(got[2]) >= 1 and (got[2]["hi"] < np.asarray(s.dims)).all() and (got[2]["lo"] >= 0).all(), "a component reaches index dim"
     if opt[2]:
         assert 0 < len(got[0]) < len(s.rows), "min_rows should drop something and keep something"
@@ -264,7 +255,7 @@ def _compare(s, pose, md, every=1):
     time (it grows with the pairs of rows and nearby triangles), the host form on every `every`-th triangle."""
     v, t, dv, dt = s.own_mesh()
     if every == 1:
-        return dev_device(s.g, s.H, dv, len(v), 32, dt, len(t), pose, max_distance=md), D.compare(s.rows, v, 32, t, pose, 0.0, md)
+        return G.compare_device(s.g, s.H, dv, len(v), 32, dt, len(t), pose, max_distance=md), D.compare(s.rows, v, 32, t, pose, 0.0, md)
     t = np.ascontiguousarray(t[::every])
     return s.g.compare_mesh(v, t, pose, max_distance=md), D.compare(s.rows, v, 32, t, pose, 0.0, md)
 
@@ -275,7 +266,7 @@ def test_compare_own_mesh(sessions, name, voxels):
     s = sessions(name)
     got, ref = _compare(s, IDENT, voxels * s.res, 4 if name in faces.DYADIC else 1)
     print("%s, %d voxels: found %d of %d, max %.6f" % (name, voxels, got[1]["n_found"], got[1]["n_rows"], got[1]["max_abs"]))
-    dev_same(got, ref, "%s, own mesh, %d voxels" % (name, voxels))
+    G.same_deviation(got, ref, "%s, own mesh, %d voxels" % (name, voxels))
     assert got[1]["n_found"] > 0.5 * len(s.rows)
 
 
@@ -297,10 +288,10 @@ def test_cover_own_mesh(sessions, name):
     s = sessions(name)
     v, t, dv, dt = s.own_mesh()
     ref = V.cover(s.rows, s.occ, v, 32, t, IDENT, s.bbox, s.res, **_cover_kw(s))
-    got = cover_device(s.g, s.H, dv, len(v), 32, dt, len(t), IDENT, **_cover_kw(s))
+    got = G.cover_device(s.g, s.H, dv, len(v), 32, dt, len(t), IDENT, **_cover_kw(s))
     print("%s: %d samples, %d in the box, %d covered" % (name, got[1]["n_samples"], got[1]["n_in_bbox"], got[1]["n_covered"]))
-    cover_same(got, ref, "%s, own mesh" % name)
-    _sums(*got)
+    G.same_coverage(got, ref, "%s, own mesh" % name)
+    G.coverage_sums(*got)
     assert got[1]["n_covered"] > 0.5 * got[1]["n_samples"]
 
 
@@ -312,13 +303,13 @@ def test_compare_and_cover_a_displaced_mesh(sessions, name):
     v, t, dv, dt = s.own_mesh()
     pose = faces.shift_pose((3, -2, 4), s.res)
     got, ref = _compare(s, pose, 3 * s.res, 4 if name in ("far137s", "dy128s") else 1)
-    dev_same(got, ref, "%s, displaced mesh" % name)
+    G.same_deviation(got, ref, "%s, displaced mesh" % name)
     assert 0 < got[1]["n_found"] < len(s.rows)
     ref = V.cover(s.rows, s.occ, v, 32, t, pose, s.bbox, s.res, **_cover_kw(s))
-    got = cover_device(s.g, s.H, dv, len(v), 32, dt, len(t), pose, **_cover_kw(s))
+    got = G.cover_device(s.g, s.H, dv, len(v), 32, dt, len(t), pose, **_cover_kw(s))
     print("%s, displaced: %d samples, %d in the box, %d covered" % (name, got[1]["n_samples"], got[1]["n_in_bbox"], got[1]["n_covered"]))
-    cover_same(got, ref, "%s, displaced mesh" % name)
-    _sums(*got)
+    G.same_coverage(got, ref, "%s, displaced mesh" % name)
+    G.coverage_sums(*got)
     assert 0 < got[1]["n_in_bbox"] < got[1]["n_samples"]
 
 
@@ -328,13 +319,13 @@ def test_two_huge_triangles_through_the_box(sessions, name):
     quad, t2, pose = faces.huge_quad(s.bbox)
     for voxels in (4, 32):
         got = s.g.compare_mesh(quad, t2, pose, max_distance=voxels * s.res)
-        dev_same(got, D.compare(s.rows, quad, 12, t2, pose, 0.0, voxels * s.res), "%s, quad, %d voxels" % (name, voxels))
+        G.same_deviation(got, D.compare(s.rows, quad, 12, t2, pose, 0.0, voxels * s.res), "%s, quad, %d voxels" % (name, voxels))
         print("%s, quad, %d voxels: found %d of %d, negative %d" % (name, voxels, got[1]["n_found"], len(s.rows), got[1]["n_negative"]))
         assert 0 < got[1]["n_found"] and 0 < got[1]["n_negative"] < got[1]["n_found"]
     assert got[1]["n_found"] > len(s.rows) // 2
     got = s.g.cover_mesh(quad, t2, pose, **_cover_kw(s))
-    cover_same(got, V.cover(s.rows, s.occ, quad, 12, t2, pose, s.bbox, s.res, **_cover_kw(s)), "%s, quad" % name)
-    _sums(*got)
+    G.same_coverage(got, V.cover(s.rows, s.occ, quad, 12, t2, pose, s.bbox, s.res, **_cover_kw(s)), "%s, quad" % name)
+    G.coverage_sums(*got)
     print("%s, quad: %d samples, %d in the box, %d covered" % (name, got[1]["n_samples"], got[1]["n_in_bbox"], got[1]["n_covered"]))
     assert (got[0]["flags"] == V.VALID | V.CAPPED).all() and got[1]["n_in_bbox"] < got[1]["n_samples"]
 
@@ -344,7 +335,7 @@ ALIGN_KW = dict(max_iterations=5, stride=4, eps_rotation=1e-5, eps_translation=1
 
 def _align_start(s):
     """0.3 degrees about the centre of the box and 2 voxels of translation away from the true pose (the identity)."""
-    return rigid(0.3, (0.5, 1.0, -0.4), tuple(np.array([0.6, -0.64, 0.48]) * 2 * s.res), A.centre(s.bbox))
+    return A.rigid(0.3, (0.5, 1.0, -0.4), tuple(np.array([0.6, -0.64, 0.48]) * 2 * s.res), A.centre(s.bbox))
 
 
 @pytest.mark.parametrize("name", ["cut", "far", "far137s"])
@@ -359,12 +350,12 @@ def test_align_own_mesh(sessions, name):
         kw["stride"] = 8
     ref = A.align(s.rows, v, 32, t, start, s.bbox, **kw)
     print("%s: %d iterations, flags %d, %d of %d inliers, rms %r, corners %.6f -> %.6f m" % (
-        name, ref["iterations"], ref["flags"], ref["inliers"], ref["rows_sampled"], ref["history"], corner_displacement(start, IDENT, s.bbox),
-        corner_displacement(ref["pose"], IDENT, s.bbox)))
-    assert _fitted(ref) and ref["rms"] < ref["history"][0], "the reference must have fitted: equality of two failed fits shows nothing"
+        name, ref["iterations"], ref["flags"], ref["inliers"], ref["rows_sampled"], ref["history"], A.corner_displacement(start, IDENT, s.bbox),
+        A.corner_displacement(ref["pose"], IDENT, s.bbox)))
+    assert G.fitted(ref) and ref["rms"] < ref["history"][0], "the reference must have fitted: equality of two failed fits shows nothing"
     got = s.g.align_mesh(dv, dt, start, device=True, n_verts=len(v), vertex_stride=32, n_tris=len(t), **kw)
-    align_equal(got, ref, "%s, device form" % name)
-    align_equal(s.g.align_mesh(v, t, start, **kw), ref, "%s, host form" % name)
+    G.same_align(got, ref, "%s, device form" % name)
+    G.same_align(s.g.align_mesh(v, t, start, **kw), ref, "%s, host form" % name)
 
 
 def _render_two_views(s):
@@ -372,7 +363,7 @@ def _render_two_views(s):
     for pose in (s.sc.poses[0], s.sc.poses[5]):
         got = s.g.render(pose, K, W, H, z_range=z_range, min_count=1, splat_radius=2, max_splat_radius=4, cull_backfaces=True, world_normals=True)
         ref = R.render(s.rows, pose, K, W, H, s.res, z_range, 1, 2, 4, R.CULL_BACKFACES | R.WORLD_NORMALS)
-        render_same(got, ref, s.name)
+        G.same_planes(got, ref, s.name)
         assert (~np.isnan(got["depth"])).sum() > 1000
 
 
@@ -390,18 +381,18 @@ def test_track_depth_far137s(synth_mod, sessions):
     """hfpf_track_depth of a held-out frame of the same stream against the model fused 148 m out, byte for byte against track_ref:
     the sums stay in headroom only because they are taken about the camera centre c with the lever a = pw - c."""
     s = sessions("far137s")
-    assert s.sc.resolution == TT.RES
+    assert s.sc.resolution == G.RES
     W, H, f = 320, 240, s.sc.n_frames + 1
     seen = synth_mod.pose(s.sc.pose_seed, f)
     depth, _, K = synth_mod.depth_frame(s.sc.seed, f, W, H, seen)
     true = np.hstack([seen[:, :3], seen[:, 3:] + s.sc.shift.reshape(3, 1)])
-    guess = TT._perturb(true, 2.0, (0.006, -0.005, 0.006))
-    got = s.g.track_depth(depth, guess, K, stride=1, **TT.OPTS)
-    ref = TT._ref(s.rows, TR.depth_points(depth, K, 1), guess, K, W, H)
+    guess = G.perturb(true, 2.0, (0.006, -0.005, 0.006))
+    got = s.g.track_depth(depth, guess, K, stride=1, **G.TRACK_OPTS)
+    ref = G.track_reference(s.rows, TR.depth_points(depth, K, 1), guess, K, W, H)
     print("far137s: %d iterations, flags %d, %d of %d used points inliers, rms %.2e, error %s -> %s" % (
-        got[1]["iterations"], got[1]["flags"], got[1]["inliers"], got[1]["points_used"], got[1]["rms"], TT._errors(guess, true),
-        TT._errors(got[0], true)))
-    TT._same_result(got, ref, "far137s")
+        got[1]["iterations"], got[1]["flags"], got[1]["inliers"], got[1]["points_used"], got[1]["rms"], G.pose_errors(guess, true),
+        G.pose_errors(got[0], true)))
+    G.same_track(got, ref, "far137s")
     assert ref["iterations"] > 1 and ref["inliers"] > 1000
 
 
@@ -431,7 +422,7 @@ def _restored_handle_gives_the_same_bytes(hfpf_mod, s):
     rays = faces.rays(s.bbox, s.res)
     first = _one_of_each(s, s.g, pts, rays)
     blob = s.g.snapshot()
-    larger = dict(faces.CAPS, max_bricks=100000, max_normals=2 << 20, max_frames=8192)  # (max_log_points must be the snapshot's)
+    larger = dict(G.SMALL_CAPS, max_bricks=100000, max_normals=2 << 20, max_frames=8192)  # (max_log_points must be the snapshot's)
     with hfpf_mod.OccupancyGrid(resolution=s.sc.resolution, bbox=s.bbox, fuse_color=True, **s.sc.config, **larger) as g2:
         g2.restore(blob)
         assert g2.extract().tobytes() == s.rows.tobytes() and g2.occupied().tobytes() == s.occ.tobytes()
@@ -460,4 +451,4 @@ def test_the_read_outs_changed_nothing(sessions, name):
     s.g.raycast_view(*faces.outside_view(s.bbox), 160, 120, radius=1, step=STEP, t_range=(0.06, 0.2))
     assert s.g.extract().tobytes() == s.rows.tobytes()
     assert s.g.occupied().tobytes() == s.occ.tobytes()
-    assert _counters(s.g) == s.counters
+    assert G.counters(s.g) == s.counters

@@ -7,8 +7,9 @@ import numpy as np
 import pytest
 
 import mesh_ref as M
-from test_gpu_render import DepthScene, _counters, _grid, _run
-from test_mesh_cpu import read_ply
+from gpu_support import BBOX, DEPTH_CAPS, RES, grid, mesh_device, node_feed, node_grid, run, same_mesh, same_planes, two_handles, unchanged
+from pcd_io import read_ply
+from scenes import DepthScene
 
 pytestmark = pytest.mark.gpu
 INF = float("inf")
@@ -20,8 +21,8 @@ OPTION_SETS = [(1, 0.0, INF), (2, 0.0, INF), (4, 0.0, INF), (2, 3.0, INF), (2, 0
 @pytest.fixture(scope="module")
 def session(hfpf_mod, synth_mod):
     sc = DepthScene(12, 640, 480, clean_every=4)
-    g = _grid(hfpf_mod)
-    _run(g, sc)
+    g = grid(hfpf_mod)
+    run(g, sc)
     rows = g.extract().copy()
     occ = g.occupied()
     yield sc, g, rows, occ
@@ -34,28 +35,6 @@ def _ref(g, rows, occ, radius, min_count, max_distance):
     return v, t
 
 
-def _device(g, **kw):
-    dv, nv, dt, nt = g.extract_mesh_device(**kw)
-    try:
-        v = g.device_download(dv, nv * 32).view(M.VERTEX_DTYPE) if nv else np.zeros(0, M.VERTEX_DTYPE)
-        t = g.device_download(dt, nt * 12).view(np.uint32).reshape(-1, 3) if nt else np.zeros((0, 3), np.uint32)
-    finally:
-        for p in (dv, dt):
-            if p:
-                g.device_free(p)
-    return v, t
-
-
-def _same(got, ref, what):
-    (gv, gt), (rv, rt) = got, ref
-    assert len(gv) == len(rv), "%s: %d vertices vs %d" % (what, len(gv), len(rv))
-    assert len(gt) == len(rt), "%s: %d triangles vs %d" % (what, len(gt), len(rt))
-    bad = np.flatnonzero((gv.view(np.uint8).reshape(len(gv), -1) != rv.view(np.uint8).reshape(len(rv), -1)).any(axis=1))
-    assert bad.size == 0, "%s: %d vertices differ, first %d: %r vs %r" % (what, bad.size, bad[0], gv[bad[0]], rv[bad[0]])
-    badt = np.flatnonzero((gt != rt).any(axis=1))
-    assert badt.size == 0, "%s: %d triangles differ, first %d: %r vs %r" % (what, badt.size, badt[0], gt[badt[0]], rt[badt[0]])
-
-
 # ---- 1. byte-identical to the numpy contract -----------------------------------------------------------------------------
 
 @pytest.mark.parametrize("opt", OPTION_SETS, ids=["r%d_mc%g_md%g" % o for o in OPTION_SETS])
@@ -66,8 +45,8 @@ def test_host_and_device_forms_are_byte_identical_to_mesh_ref(hfpf_mod, session,
     host = g.extract_mesh(**kw)
     assert len(host[1]) > 1000
     ref = _ref(g, rows, occ, radius, min_count, max_distance)
-    _same(host, ref, "host form %r" % (opt,))
-    _same(_device(g, **kw), ref, "device form %r" % (opt,))
+    same_mesh(host, ref, "host form %r" % (opt,))
+    same_mesh(mesh_device(g, **kw), ref, "device form %r" % (opt,))
 
 
 # ---- 2. geometry ---------------------------------------------------------------------------------------------------------
@@ -119,23 +98,18 @@ def test_a_mesh_changes_nothing(hfpf_mod, synth_mod):
     def look(g, i):
         g.extract_mesh(radius=1 + i % 4)
 
-    with _grid(hfpf_mod) as a, _grid(hfpf_mod) as b:
-        _run(a, sc)
-        v0, t0 = b.extract_mesh()  # before the first clean
+    def on_empty(b):  # before the first clean
+        v0, t0 = b.extract_mesh()
         assert len(v0) == 0 and len(t0) == 0
         assert b.extract_mesh_device() == (0, 0, 0, 0)
-        _run(b, sc, between=look)
-        ra, rb = a.extract(), b.extract()
-        assert len(ra) > 0 and ra.tobytes() == rb.tobytes()
-        assert _counters(a) == _counters(b)
+
+    with two_handles(hfpf_mod, sc, look, on_empty) as (a, b, rb):
         ia = a.render(sc.poses[2], K, sc.W, sc.H, z_range=(0.05, 3.0), splat_radius=2)
-        ib = b.render(sc.poses[2], K, sc.W, sc.H, z_range=(0.05, 3.0), splat_radius=2)
-        for k in ia:
-            assert ia[k].tobytes() == ib[k].tobytes(), k
+        same_planes(ia, b.render(sc.poses[2], K, sc.W, sc.H, z_range=(0.05, 3.0), splat_radius=2), "a render of both handles")
         one, two = b.extract_mesh(), b.extract_mesh()
-        _same(one, two, "second mesh")
-        _same(one, _ref(b, rb, b.occupied(), 2, 0.0, INF), "mesh_ref")
-        assert b.extract().tobytes() == ra.tobytes() and _counters(a) == _counters(b)
+        same_mesh(one, two, "second mesh")
+        same_mesh(one, _ref(b, rb, b.occupied(), 2, 0.0, INF), "mesh_ref")
+        unchanged(a, b, rb)
 
 
 def test_bad_arguments_are_refused_and_the_handle_stays_usable(hfpf_mod, synth_mod):
@@ -145,8 +119,8 @@ def test_bad_arguments_are_refused_and_the_handle_stays_usable(hfpf_mod, synth_m
            "radius 5": ("radius", 5), "min_count nan": ("min_count", float("nan")), "max_distance 0": ("max_distance", 0.0),
            "max_distance -1": ("max_distance", -1.0), "max_distance nan": ("max_distance", float("nan"))}
     L = H_.lib()
-    with _grid(hfpf_mod) as g:
-        _run(g, sc)
+    with grid(hfpf_mod) as g:
+        run(g, sc)
         want = g.extract().copy()
         ref = _ref(g, want, g.occupied(), 2, 0.0, INF)
         v, nv, t, nt = C.c_void_p(7), C.c_uint64(7), C.c_void_p(7), C.c_uint64(7)
@@ -164,29 +138,22 @@ def test_bad_arguments_are_refused_and_the_handle_stays_usable(hfpf_mod, synth_m
                 assert fn(g._h, C.byref(o), *args) == -2, "NULL output %d" % k
             assert (v.value, nv.value, t.value, nt.value) == (7, 7, 7, 7), "a refused call wrote its output"
         assert g.extract().tobytes() == want.tobytes()
-        _same(g.extract_mesh(), ref, "after the refusals")
-        _same(_device(g), ref, "device form after the refusals")
+        same_mesh(g.extract_mesh(), ref, "after the refusals")
+        same_mesh(mesh_device(g), ref, "device form after the refusals")
 
 
 # ---- 4. the node shell ---------------------------------------------------------------------------------------------------
 
 def test_node_writes_mesh_ply(hfpf_mod, synth_mod, tmp_path):
     import hfpf_node
-    from test_gpu_render import BBOX, CAPS, RES
     sc = DepthScene(6, 320, 240, clean_every=0)
     opts = hfpf_mod.mesh_opts(radius=2)
-    caps = dict(CAPS)
+    caps = dict(DEPTH_CAPS)
     with hfpf_node.FusionNode(BBOX, directory_name=str(tmp_path), resolution=RES, final_clean_on_process=True, **caps) as n:
         n.set_mesh_output(opts)
-        n.start()
-        for f in range(sc.n_frames):
-            depth, rgb, K = sc.frames[f]
-            pose = sc.poses[f]
-            n._tf_py = lambda target, source, pose=pose: pose
-            assert n.publish_depth(depth, K, color=rgb) == 1
+        node_feed(n, sc)
         # the mesh the node will write: the same model, meshed through the engine handle before ~process clears it
-        g = hfpf_mod.OccupancyGrid.__new__(hfpf_mod.OccupancyGrid)
-        g._h, g._transport = C.c_void_p(hfpf_node.lib().hfpf_node_grid(n._h)), None
+        g = node_grid(hfpf_mod, hfpf_node, n)
         g.clean()
         v, t = g.extract_mesh(opts=opts)
         g._h = None

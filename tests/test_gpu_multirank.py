@@ -5,45 +5,18 @@ import numpy as np
 import pytest
 
 import scenes
+from gpu_support import SMALL_CAPS, run_virtual
 
 pytestmark = pytest.mark.gpu
-SMALL = dict(max_bricks=60000, max_log_points=4 << 20, max_normals=1 << 20, max_frames=4096)
-
-
-def _run_virtual(hfpf_mod, sc, world, fuse_color=False, deal=None, gathered=False):
-    import hfpf_dist
-    grids = [hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, fuse_color=fuse_color, **SMALL) for _ in range(world)]
-    vr = hfpf_dist.LocalVirtualRanks(grids, gathered=gathered)
-    deal = deal or (lambda f: f % world)
-    fb = sc.W * sc.H * 16
-    try:
-        for ev in sc.schedule():
-            if ev[0] == "integrate":
-                f = ev[1]
-                g = grids[deal(f)]
-                dev = g.device_alloc(fb)
-                g.device_upload(dev, sc.frame(f))
-                g.integrate_device(dev, 1, fb, sc.W * sc.H, sc.poses[f].reshape(1, 12), frame_ids=np.array([f], np.uint32))
-                g.sync()
-                g.device_free(dev)
-            else:
-                vr.clean_all()
-        rows = vr.extract(on=world - 1)
-        occ = grids[0].occupied()
-        ctrs = [g.counters() for g in grids]
-    finally:
-        for g in grids:
-            g.close()
-    return rows, occ, ctrs
 
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_virtual_ranks_bit_identical_to_single_handle(oracle_mod, hfpf_mod, synth_mod, world):
     sc = scenes.Scene(7, 160, 120, 0.001, fx=615.0, clean_every=3)
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as one:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as one:
         single = scenes.run(one, sc, "integrate")
         occ_single = one.occupied()
-    rows, occ, ctrs = _run_virtual(hfpf_mod, sc, world)
+    rows, occ, ctrs = run_virtual(hfpf_mod, sc, world)
     assert np.array_equal(occ, occ_single), "replicated occupancy differs from the single-GPU run"
     assert rows.tobytes() == single.tobytes(), "sharded result is not bit-identical to one GPU fusing all frames"
     assert sum(c["points_presented"] for c in ctrs) == sc.n_frames * sc.W * sc.H
@@ -58,9 +31,9 @@ def test_virtual_ranks_viewpoint_latch_is_global_min(hfpf_mod, synth_mod):
     """A cell first seen by rank 1 (frame 1) and later by rank 0 (frame 2) must orient with frame 1's viewpoint on
     both ranks: 5 mm voxels make most cells multi-frame."""
     sc = scenes.Scene(6, 160, 120, 0.005, clean_every=2)
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as one:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as one:
         single = scenes.run(one, sc, "integrate")
-    rows, _, _ = _run_virtual(hfpf_mod, sc, 2)
+    rows, _, _ = run_virtual(hfpf_mod, sc, 2)
     assert rows.tobytes() == single.tobytes()
 
 
@@ -70,12 +43,12 @@ def test_gathered_import_unequal_and_zero_counts(hfpf_mod, synth_mod):
     rank 2 gets no frame before the first clean, rank 0 two frames, rank 1 one."""
     sc = scenes.Scene(7, 160, 120, 0.001, fx=615.0, clean_every=3)
     owner = {0: 0, 1: 1, 2: 0, 3: 2, 4: 2, 5: 1, 6: 2}
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as one:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as one:
         single = scenes.run(one, sc, "integrate")
-    rows, _, ctrs = _run_virtual(hfpf_mod, sc, 3, deal=lambda f: owner[f], gathered=True)
+    rows, _, ctrs = run_virtual(hfpf_mod, sc, 3, deal=lambda f: owner[f], gathered=True)
     assert rows.tobytes() == single.tobytes()
     assert [c["frames_integrated"] for c in ctrs] == [2, 2, 3]
-    rows2, _, _ = _run_virtual(hfpf_mod, sc, 3, deal=lambda f: owner[f], gathered=False)  # the record-list transport agrees
+    rows2, _, _ = run_virtual(hfpf_mod, sc, 3, deal=lambda f: owner[f], gathered=False)  # the record-list transport agrees
     assert rows2.tobytes() == single.tobytes()
 
 
@@ -83,7 +56,7 @@ def test_failed_clean_poisons_the_handle_until_clear(hfpf_mod, synth_mod):
     """A capacity error in the middle of a clean pass leaves the tables half updated: the handle refuses further work
     (HFPF_ERR_STATE) until hfpf_clear instead of silently losing candidates on a retry."""
     sc = scenes.Scene(2, 160, 120, 0.001, fx=615.0)
-    caps = dict(SMALL, max_normals=256)
+    caps = dict(SMALL_CAPS, max_normals=256)
     with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **caps) as g:
         g.integrate(sc.frame(0), sc.poses[0])
         with pytest.raises(hfpf_mod.HfpfError) as e:
@@ -95,15 +68,15 @@ def test_failed_clean_poisons_the_handle_until_clear(hfpf_mod, synth_mod):
             assert e2.value.code == -5 and "hfpf_clear" in str(e2.value)
         g.clear()
         assert len(g.extract()) == 0
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as g:  # and a roomy handle is unaffected
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as g:  # and a roomy handle is unaffected
         assert len(scenes.run(g, sc, "integrate")) > 1000
 
 
 def test_virtual_ranks_with_colour(oracle_mod, hfpf_mod, synth_mod):
     sc = scenes.Scene(4, 160, 120, 0.001, fx=615.0, clean_every=2)
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, fuse_color=True, **SMALL) as one:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, fuse_color=True, **SMALL_CAPS) as one:
         single = scenes.run(one, sc, "integrate")
-    rows, _, _ = _run_virtual(hfpf_mod, sc, 2, fuse_color=True)
+    rows, _, _ = run_virtual(hfpf_mod, sc, 2, fuse_color=True)
     assert rows.tobytes() == single.tobytes()
     assert (rows["rgb"][rows["count"] > 0] != 0).any()
     og = oracle_mod.OracleGrid(resolution=sc.resolution, bbox=sc.bbox, fuse_color=True)
@@ -114,9 +87,9 @@ def test_rccl_path_world_size_one(hfpf_mod, synth_mod):
     """The engine's own RCCL collectives (dlopen'ed librccl: all-gather of counts/records in clean, all-reduce of the
     statistic sums in extract) with a single rank: exercises loading, communicator creation and every call site."""
     sc = scenes.Scene(4, 160, 120, 0.001, fx=615.0, clean_every=2)
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as a:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as a:
         ref = scenes.run(a, sc, "integrate")
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as b:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as b:
         b.dist_init_rccl(0, 1, hfpf_mod.dist_unique_id())
         got = scenes.run(b, sc, "integrate")
     assert ref.tobytes() == got.tobytes()
@@ -141,7 +114,7 @@ def _two_proc_worker(rank, world, port, q, scene_kw):
         os.environ["MASTER_PORT"] = str(port)
         dist.init_process_group("gloo", rank=rank, world_size=world)
         sc = scenes.Scene(seed=0xF051 + 7919 * rank, pose_seed=0x5E3 + 104729 * rank, **scene_kw)
-        g = hfpf.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL)
+        g = hfpf.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS)
         g.attach_transport(hfpf_dist.HostStagedTransport(dist))
         fb = sc.W * sc.H * 16
         dev = g.device_alloc(fb)
@@ -186,7 +159,7 @@ def test_two_processes_one_stream_each_equal_single_process(hfpf_mod, synth_mod)
     assert res[0] == res[1], "ranks disagree on the merged rows"
     streams = [scenes.Scene(seed=0xF051 + 7919 * r, pose_seed=0x5E3 + 104729 * r, **kw) for r in range(2)]
     fb = 160 * 120 * 16
-    with hfpf_mod.OccupancyGrid(resolution=0.001, bbox=streams[0].bbox, **SMALL) as one:
+    with hfpf_mod.OccupancyGrid(resolution=0.001, bbox=streams[0].bbox, **SMALL_CAPS) as one:
         dev = one.device_alloc(fb)
         for f in range(kw["n_frames"]):
             for r in range(2):
@@ -207,8 +180,8 @@ def test_virtual_rank_failure_abandons_the_pass_on_every_rank(hfpf_mod, synth_mo
     must the statistics merge of extract."""
     import hfpf_dist
     sc = scenes.Scene(2, 160, 120, 0.001, fx=615.0)
-    grids = [hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL),
-             hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **dict(SMALL, max_log_points=4096))]
+    grids = [hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS),
+             hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **dict(SMALL_CAPS, max_log_points=4096))]
     vr = hfpf_dist.LocalVirtualRanks(grids)
     try:
         for r, g in enumerate(grids):
@@ -234,7 +207,7 @@ def test_rccl_world_size_one_poisoned_rank_returns_instead_of_blocking(hfpf_mod,
     hfpf_clean and from hfpf_extract with an error -- it enters the status all-gather with its fail bit set, which is what
     keeps its peers from waiting in ncclAllGather / ncclAllReduce -- and hfpf_clear makes it usable again."""
     sc = scenes.Scene(2, 160, 120, 0.001, fx=615.0)
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **dict(SMALL, max_normals=256)) as g:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **dict(SMALL_CAPS, max_normals=256)) as g:
         g.dist_init_rccl(0, 1, hfpf_mod.dist_unique_id())
         g.integrate(sc.frame(0), sc.poses[0])
         with pytest.raises(hfpf_mod.HfpfError) as e:
@@ -246,7 +219,7 @@ def test_rccl_world_size_one_poisoned_rank_returns_instead_of_blocking(hfpf_mod,
             assert e2.value.code == -5 and "hfpf_clear" in str(e2.value)
         g.clear()
         assert len(g.extract()) == 0  # through the status gather + all-reduce again, healthy
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **dict(SMALL, max_log_points=4096)) as g:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **dict(SMALL_CAPS, max_log_points=4096)) as g:
         g.dist_init_rccl(0, 1, hfpf_mod.dist_unique_id())
         g.integrate(sc.frame(0), sc.poses[0])
         with pytest.raises(hfpf_mod.HfpfError) as e:  # sticky overflow bit: found by the export in FRONT of the exchange
@@ -289,7 +262,7 @@ def test_rccl_world_size_one_deferred_host_frame_failure_goes_through_the_consen
     world size RCCL can form here: the failing rank comes back from clean and extract with its error (not a hang), is poisoned,
     and hfpf_clear revives it."""
     sc = scenes.Scene(1, 160, 120, 0.001, fx=615.0)
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **dict(SMALL, max_frames=50, max_log_points=24 << 20, max_normals=4 << 20)) as g:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **dict(SMALL_CAPS, max_frames=50, max_log_points=24 << 20, max_normals=4 << 20)) as g:
         g.dist_init_rccl(0, 1, hfpf_mod.dist_unique_id())
         dev, deferred = _fail_by_deferred_host_frame(g, hfpf_mod, sc)
         assert deferred, "the host frame was launched at once: the stream was idle (box too slow for this test's timing assumption)"
@@ -325,9 +298,9 @@ def _two_proc_failing_worker(rank, world, port, q, scene_kw, mode="log"):
         os.environ["MASTER_PORT"] = str(port)
         dist.init_process_group("gloo", rank=rank, world_size=world)
         sc = scenes.Scene(seed=0xF051 + 7919 * rank, pose_seed=0x5E3 + 104729 * rank, **scene_kw)
-        caps = SMALL
+        caps = SMALL_CAPS
         if rank == 1:
-            caps = dict(SMALL, max_log_points=4096) if mode == "log" else dict(SMALL, max_frames=50, max_log_points=24 << 20, max_normals=4 << 20)
+            caps = dict(SMALL_CAPS, max_log_points=4096) if mode == "log" else dict(SMALL_CAPS, max_frames=50, max_log_points=24 << 20, max_normals=4 << 20)
         g = hfpf.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **caps)
         g.attach_transport(hfpf_dist.HostStagedTransport(dist))
         if rank == 1 and mode == "deferred":

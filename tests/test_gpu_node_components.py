@@ -1,32 +1,16 @@
 """GPU: the node shell's component filter (hfpf_node_set_component_filter).  With it set, ~process writes test_cloud.pcd and meta.csv
 from the rows hfpf_extract_components keeps; with NULL the files are byte-identical to those of a node that never called it."""
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
 import components_ref as CR
-from test_gpu_components import add_patches, in_boxes
-from test_gpu_render import BBOX, CAPS, RES, DepthScene
+from gpu_support import BBOX, DEPTH_CAPS, RES, add_patches, in_boxes, node_feed, node_grid
+from scenes import DepthScene
 
 pytestmark = pytest.mark.gpu
 FILES = ("test_cloud.pcd", "meta.csv")
-
-
-def _feed(n, sc):
-    n.start()
-    for f in range(sc.n_frames):
-        depth, rgb, K = sc.frames[f]
-        n._tf_py = lambda target, source, pose=sc.poses[f]: pose
-        assert n.publish_depth(depth, K, color=rgb) == 1
-
-
-def _grid_of(hfpf_mod, hfpf_node, n):
-    """The node's engine handle as an OccupancyGrid (not owned: reset _h before it is collected)."""
-    g = hfpf_mod.OccupancyGrid.__new__(hfpf_mod.OccupancyGrid)
-    g._h, g._transport = C.c_void_p(hfpf_node.lib().hfpf_node_grid(n._h)), None
-    return g
 
 
 def _read(d):
@@ -38,12 +22,12 @@ def test_process_writes_the_kept_rows(hfpf_mod, synth_mod, tmp_path):
     sc = DepthScene(6, 320, 240, clean_every=0)
     published = []
     with hfpf_node.FusionNode(BBOX, directory_name=str(tmp_path), resolution=RES, final_clean_on_process=True,
-                              publisher=lambda rows, frame: published.append(rows), **CAPS) as n:
+                              publisher=lambda rows, frame: published.append(rows), **DEPTH_CAPS) as n:
         with pytest.raises(hfpf_mod.HfpfError) as e:
             n.set_component_filter(reach=7)
         assert e.value.code == -2
-        _feed(n, sc)
-        g = _grid_of(hfpf_mod, hfpf_node, n)
+        node_feed(n, sc)
+        g = node_grid(hfpf_mod, hfpf_node, n)
         try:
             g.clean()
             boxes = add_patches(g)  # two specks well clear of the surface
@@ -76,11 +60,11 @@ def test_null_filter_writes_what_a_plain_node_writes(hfpf_mod, synth_mod, tmp_pa
     for name in ("plain", "off"):
         d = tmp_path / name
         os.makedirs(str(d))
-        with hfpf_node.FusionNode(BBOX, directory_name=str(d), resolution=RES, final_clean_on_process=True, **CAPS) as n:
+        with hfpf_node.FusionNode(BBOX, directory_name=str(d), resolution=RES, final_clean_on_process=True, **DEPTH_CAPS) as n:
             if name == "off":
                 n.set_component_filter(reach=1, min_rows=1000)
                 n.set_component_filter(None)
-            _feed(n, sc)
+            node_feed(n, sc)
             rc, ok, msg = n.process()
             assert rc == 0 and ok, msg
         out[name] = _read(d)

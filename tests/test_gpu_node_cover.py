@@ -6,9 +6,8 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_align import KW, MD, START
-from test_gpu_node_components import _feed, _grid_of
-from test_gpu_render import BBOX, CAPS, RES, DepthScene
+from gpu_support import ALIGN_KW, ALIGN_MD, ALIGN_START, BBOX, DEPTH_CAPS, RES, node_feed, node_grid
+from scenes import DepthScene
 
 pytestmark = pytest.mark.gpu
 COVER = dict(radius=2, max_distance=2 * RES, spacing=RES, min_normal_dot=0.3)
@@ -33,27 +32,27 @@ def _parse(path, dtype):
 def test_process_writes_the_coverage_files(hfpf_mod, synth_mod, tmp_path, mode):
     import hfpf_node
     sc = DepthScene(3, 160, 120, clean_every=0)
-    with hfpf_node.FusionNode(BBOX, directory_name=str(tmp_path), resolution=RES, final_clean_on_process=True, **CAPS) as n:
+    with hfpf_node.FusionNode(BBOX, directory_name=str(tmp_path), resolution=RES, final_clean_on_process=True, **DEPTH_CAPS) as n:
         with pytest.raises(hfpf_mod.HfpfError) as e:
             n.set_reference_coverage(spacing=0.0)
         assert e.value.code == -2
         n.set_reference_coverage(**COVER)  # without a reference mesh: no effect
-        _feed(n, sc)
-        g = _grid_of(hfpf_mod, hfpf_node, n)
+        node_feed(n, sc)
+        g = node_grid(hfpf_mod, hfpf_node, n)
         try:
             g.clean()
             verts, tris = g.extract_mesh()
             tris = np.ascontiguousarray(tris[::8])  # spread over the whole model, so that an align has something to hold on to
-            fit = g.align_mesh(verts, tris, START, **KW) if mode == "aligned" else None
-            pose = fit["pose"] if fit else START
+            fit = g.align_mesh(verts, tris, ALIGN_START, **ALIGN_KW) if mode == "aligned" else None
+            pose = fit["pose"] if fit else ALIGN_START
             cov, s = g.cover_mesh(verts, tris, pose, **COVER)
-            at_start = g.cover_mesh(verts, tris, START, **COVER)[1]
+            at_start = g.cover_mesh(verts, tris, ALIGN_START, **COVER)[1]
         finally:
             g._h = None
         assert len(tris) > 1000 and 0 < s["n_covered"] < s["n_samples"]
-        n.set_reference_mesh(verts, tris, START, max_distance=MD)
+        n.set_reference_mesh(verts, tris, ALIGN_START, max_distance=ALIGN_MD)
         if mode == "aligned":
-            n.set_reference_alignment(**KW)
+            n.set_reference_alignment(**ALIGN_KW)
         if mode == "off":
             with pytest.raises(hfpf_mod.HfpfError):
                 n.set_reference_coverage(radius=9)  # refused: the setting stays as it was ...
@@ -69,7 +68,7 @@ def test_process_writes_the_coverage_files(hfpf_mod, synth_mod, tmp_path, mode):
         line = open(os.path.join(str(tmp_path), "alignment.csv")).read().splitlines()[1].split(",")
         assert np.array([float(x) for x in line[5:]]).tobytes() == np.ascontiguousarray(pose, np.float64).tobytes()
         print("covered at the start pose %d, at the refined pose %d of %d samples" % (at_start["n_covered"], s["n_covered"], s["n_samples"]))
-        assert not np.array_equal(np.asarray(pose), np.asarray(START)), "the align moved the mesh"
+        assert not np.array_equal(np.asarray(pose), np.asarray(ALIGN_START)), "the align moved the mesh"
     got = _parse(files[0], hfpf_mod.TRI_COVERAGE_DTYPE)
     assert got.tobytes() == cov.tobytes()
     head, line = open(files[1]).read().splitlines()

@@ -5,27 +5,11 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_node_components import _feed, _grid_of
-from test_gpu_render import BBOX, CAPS, RES, DepthScene
+from gpu_support import BBOX, DEPTH_CAPS, RES, deviation_csv, deviation_summary_csv, node_feed, node_grid
+from scenes import DepthScene
 
 pytestmark = pytest.mark.gpu
 MD = 4 * RES
-
-
-def _csv(rows, dev):
-    lines = ["ix,iy,iz,signed_distance,distance,tri,flags"]
-    for r, d in zip(rows, dev):
-        lines.append("%d,%d,%d,%s,%s,%d,%d" % (r["ix"], r["iy"], r["iz"], _g(d["signed_distance"]), _g(d["distance"]), d["tri"], d["flags"]))
-    return "\n".join(lines) + "\n"
-
-
-def _g(v):
-    return "nan" if np.isnan(v) else "%.9g" % float(v)
-
-
-def _summary_csv(s):
-    keys = ("n_rows", "n_found", "n_negative", "n_tris_valid", "n_tris_invalid", "max_abs", "sum_abs_q30", "sum_sq_q30")
-    return ",".join(keys) + "\n" + ",".join(_g(s[k]) if k == "max_abs" else "%d" % s[k] for k in keys) + "\n"
 
 
 @pytest.mark.parametrize("filtered", [False, True], ids=["plain", "component_filter"])
@@ -33,12 +17,12 @@ def test_process_writes_the_deviation_files(hfpf_mod, synth_mod, tmp_path, filte
     import deviation_ref as D
     import hfpf_node
     sc = DepthScene(4, 320, 240, clean_every=0)
-    with hfpf_node.FusionNode(BBOX, directory_name=str(tmp_path), resolution=RES, final_clean_on_process=True, **CAPS) as n:
+    with hfpf_node.FusionNode(BBOX, directory_name=str(tmp_path), resolution=RES, final_clean_on_process=True, **DEPTH_CAPS) as n:
         with pytest.raises(hfpf_mod.HfpfError) as e:
             n.set_reference_mesh(np.zeros((3, 3), np.float32), [[0, 1, 2]], max_distance=-1.0)
         assert e.value.code == -2
-        _feed(n, sc)
-        g = _grid_of(hfpf_mod, hfpf_node, n)
+        node_feed(n, sc)
+        g = node_grid(hfpf_mod, hfpf_node, n)
         try:
             g.clean()
             verts, tris = g.extract_mesh()
@@ -62,5 +46,5 @@ def test_process_writes_the_deviation_files(hfpf_mod, synth_mod, tmp_path, filte
         n.set_reference_mesh(verts, tris, max_distance=MD)
         rc, ok, msg = n.process()
         assert rc == 0 and ok, msg
-    assert open(os.path.join(str(tmp_path), "deviation.csv")).read() == _csv(rows, dev)
-    assert open(os.path.join(str(tmp_path), "deviation_summary.csv")).read() == _summary_csv(summary)
+    assert open(os.path.join(str(tmp_path), "deviation.csv")).read() == deviation_csv(rows, dev)
+    assert open(os.path.join(str(tmp_path), "deviation_summary.csv")).read() == deviation_summary_csv(summary)

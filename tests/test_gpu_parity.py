@@ -3,17 +3,17 @@ import numpy as np
 import pytest
 
 import scenes
+from gpu_support import SMALL_CAPS
 
 pytestmark = pytest.mark.gpu
 
-SMALL = dict(max_bricks=60000, max_log_points=4 << 20, max_normals=1 << 20, max_frames=4096)
 
 
 def _both(oracle_mod, hfpf_mod, scene, **cfg):
     og = oracle_mod.OracleGrid(resolution=scene.resolution, bbox=scene.bbox, **cfg)
     ref = scenes.run(og, scene, "capture")
     occ_ref = og.occupied()
-    with hfpf_mod.OccupancyGrid(resolution=scene.resolution, bbox=scene.bbox, **cfg, **SMALL) as eg:
+    with hfpf_mod.OccupancyGrid(resolution=scene.resolution, bbox=scene.bbox, **cfg, **SMALL_CAPS) as eg:
         got = scenes.run(eg, scene, "integrate")
         occ_got = eg.occupied()
         ctr = eg.counters()
@@ -56,7 +56,7 @@ def test_full_resolution_frames_with_tile_hint_vs_oracle(oracle_mod, hfpf_mod, s
     ref = scenes.run(og, sc, "capture")
     occ_ref = og.occupied()
     og.close()
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, frame_width=640, **SMALL) as eg:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, frame_width=640, **SMALL_CAPS) as eg:
         got = scenes.run(eg, sc, "integrate")
         assert np.array_equal(occ_ref, eg.occupied())
     assert len(ref) > 100000
@@ -77,7 +77,7 @@ def test_compacting_rebuild_path(oracle_mod, hfpf_mod, synth_mod):
     sc = scenes.Scene(6, 160, 120, 0.001, fx=615.0, clean_every=1)
     og = oracle_mod.OracleGrid(resolution=sc.resolution, bbox=sc.bbox)
     ref = scenes.run(og, sc, "capture")
-    cap = dict(SMALL)
+    cap = dict(SMALL_CAPS)
     cap["max_normals"] = int(len(ref) * 1.3) + 64
     with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **cap) as eg:
         got = scenes.run(eg, sc, "integrate")
@@ -99,9 +99,9 @@ def test_colour_extension_does_not_change_geometry(oracle_mod, hfpf_mod, synth_m
     sc = scenes.Scene(5, 160, 120, 0.001, fx=615.0, clean_every=2)
     og = oracle_mod.OracleGrid(resolution=sc.resolution, bbox=sc.bbox, fuse_color=True)
     ref = scenes.run(og, sc, "capture", color=True)
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as a:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as a:
         ra = scenes.run(a, sc, "integrate")
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, fuse_color=True, **SMALL) as b:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, fuse_color=True, **SMALL_CAPS) as b:
         rb = scenes.run(b, sc, "integrate")
     assert (ra["rgb"] == 0).all()
     for f in ra.dtype.names:
@@ -113,14 +113,14 @@ def test_colour_extension_does_not_change_geometry(oracle_mod, hfpf_mod, synth_m
     assert has.sum() > 1000 and len(np.unique(rb["rgb"][has])) > 1000  # real colours, not a constant
     # PCL32 layout (rgb at offset 16) reads the same colours
     sc32 = scenes.Scene(5, 160, 120, 0.001, fx=615.0, clean_every=2, layout=synth_mod.LAYOUT_PCL32)
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, fuse_color=True, **SMALL) as c:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, fuse_color=True, **SMALL_CAPS) as c:
         rc = scenes.run(c, sc32, "integrate")
     assert rc.tobytes() == rb.tobytes()
 
 
 def test_clear_then_rerun_is_identical(hfpf_mod, synth_mod):
     sc = scenes.Scene(4, 160, 120, 0.005, clean_every=2)
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as g:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as g:
         r1 = scenes.run(g, sc, "integrate")
         g.clear()
         assert g.state_changed
@@ -137,10 +137,10 @@ def test_clear_after_a_larger_session_leaves_nothing_behind(hfpf_mod, synth_mod)
     small = scenes.Scene(3, 160, 120, 0.001, fx=615.0, seed=0xBEEF, pose_seed=0x77, clean_every=2, max_angle=5.0)
     fresh = {}
     for name, sc in (("big", big), ("small", small)):
-        with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as g:
+        with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as g:
             fresh[name] = scenes.run(g, sc, "integrate").tobytes()
             assert len(fresh[name])
-    with hfpf_mod.OccupancyGrid(resolution=big.resolution, bbox=big.bbox, **SMALL) as g:
+    with hfpf_mod.OccupancyGrid(resolution=big.resolution, bbox=big.bbox, **SMALL_CAPS) as g:
         assert scenes.run(g, big, "integrate").tobytes() == fresh["big"]
         used_big = g.counters()["bricks_allocated"]
         g.clear()
@@ -159,7 +159,7 @@ def test_long_batches_take_the_larger_dry_run_vs_oracle(oracle_mod, hfpf_mod, sy
     sc = scenes.Scene(144, 96, 72, 0.001, fx=92.25, clean_every=72)
     og = oracle_mod.OracleGrid(resolution=sc.resolution, bbox=sc.bbox)
     ref = scenes.run(og, sc, "capture")
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as g:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as g:
         fb = sc.W * sc.H * 16
         dev = g.device_alloc(sc.n_frames * fb)
         for f in range(sc.n_frames):
@@ -178,7 +178,7 @@ def test_long_batches_take_the_larger_dry_run_vs_oracle(oracle_mod, hfpf_mod, sy
 def test_batched_device_frames_equal_single_host_frames(hfpf_mod, synth_mod):
     """hfpf_integrate_device with several frames per launch == one hfpf_integrate per frame (order-free sums)."""
     sc = scenes.Scene(6, 160, 120, 0.001, fx=615.0)
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as a:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as a:
         for f in range(3):
             a.integrate(sc.frame(f), sc.poses[f])
         a.clean()
@@ -186,7 +186,7 @@ def test_batched_device_frames_equal_single_host_frames(hfpf_mod, synth_mod):
             a.integrate(sc.frame(f), sc.poses[f])
         a.clean()
         ra = a.extract()
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as b:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as b:
         fb = sc.W * sc.H * 16
         dev = b.device_alloc(6 * fb)
         for f in range(6):
@@ -206,11 +206,11 @@ def test_binned_and_direct_update_are_bit_identical(oracle_mod, hfpf_mod, synth_
     sc = scenes.Scene(7, 160, 120, 0.001, fx=615.0, clean_every=2)
     og = oracle_mod.OracleGrid(resolution=sc.resolution, bbox=sc.bbox)
     ref = scenes.run(og, sc, "capture")
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, binned_update=binned, **SMALL) as g:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, binned_update=binned, **SMALL_CAPS) as g:
         got = scenes.run(g, sc, "integrate")
         ctr = g.counters()
     scenes.compare_rows(ref, got)
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, binned_update=not binned, **SMALL) as g2:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, binned_update=not binned, **SMALL_CAPS) as g2:
         other = scenes.run(g2, sc, "integrate")
         ctr2 = g2.counters()
     assert got.tobytes() == other.tobytes()
@@ -225,7 +225,7 @@ def test_frame_width_hint_changes_nothing(oracle_mod, hfpf_mod, synth_mod, layou
     sc = scenes.Scene(5, 160, 128, 0.001, fx=615.0, clean_every=2, layout=getattr(synth_mod, layout_name))
     rows = {}
     for fw in (0, 160, 100, 48):  # 48: width is a multiple of 16 but 160*128/48 is not integral -> falls back
-        with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, frame_width=fw, **SMALL) as eg:
+        with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, frame_width=fw, **SMALL_CAPS) as eg:
             rows[fw] = scenes.run(eg, sc, "integrate")
     assert len(rows[0]) > 1000
     for fw in (160, 100, 48):
@@ -242,12 +242,12 @@ def test_full_record_table_falls_back_to_device_atomics(oracle_mod, hfpf_mod, sy
     sc = scenes.Scene(7, 160, 120, 0.001, fx=615.0, clean_every=2)
     og = oracle_mod.OracleGrid(resolution=sc.resolution, bbox=sc.bbox)
     ref = scenes.run(og, sc, "capture")
-    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as g:
+    with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as g:
         plain = scenes.run(g, sc, "integrate")
     monkeypatch.setenv("HFPF_TEST_TABLE_SKIP", "1")
     for form in ("cells", "points"):
         monkeypatch.setenv("HFPF_UPDATE_FORM", form)
-        with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL) as g:
+        with hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **SMALL_CAPS) as g:
             got = scenes.run(g, sc, "integrate")
         scenes.compare_rows(ref, got)
         assert got.tobytes() == plain.tobytes(), form
@@ -329,7 +329,7 @@ def test_registration_contest_on_unoccupied_cells_follows_the_key_order(oracle_m
     pose = synth_mod.identity_pose()
     frames = [_plane_frame(0.0), _plane_frame(0.0022, seed=2)]
     og = oracle_mod.OracleGrid(resolution=0.001, bbox=scenes.BBOX_1M)
-    with hfpf_mod.OccupancyGrid(resolution=0.001, bbox=scenes.BBOX_1M, **SMALL) as eg:
+    with hfpf_mod.OccupancyGrid(resolution=0.001, bbox=scenes.BBOX_1M, **SMALL_CAPS) as eg:
         for fr in frames:
             og.capture(fr, pose)
             og.clean()

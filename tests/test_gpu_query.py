@@ -8,12 +8,10 @@ import pytest
 
 import depth_ref
 import query_ref as Q
-from test_gpu_render import DepthScene, _counters, _grid, _run
+from gpu_support import IDENT, Z_CLIP, grid, held_out, run, same_planes, same_query, two_handles, unchanged, uploaded
+from scenes import DepthScene
 
 pytestmark = pytest.mark.gpu
-Z_CLIP = (0.28, 0.6)   # the handle's default z-clip (node.cpp:92-93)
-HELD_OUT = 40          # frame index of the synthetic stream that is queried and never integrated
-SEED, POSE_SEED = 0xD3F7, 0x5E3
 INF = float("inf")
 # (radius, min_count, max_distance, zclip): every radius, a count gate, a distance gate, both z-clip settings
 OPTION_SETS = [(0, 0.0, INF, False), (1, 0.0, INF, True), (2, 3.0, 0.003, False), (4, 0.0, INF, True), (1, 2.0, 0.0015, False)]
@@ -28,43 +26,25 @@ def _ref(g, rows, occ, pts, pose, radius, min_count, max_distance, zclip):
                    zclip=zclip)
 
 
-def _same(got, ref, what):
-    for x, y, name in ((got[0], ref[0], "hits"), (got[1], ref[1], "rows")):
-        if x is None and y is None:
-            continue
-        assert len(x) == len(y), "%s: %s: %d vs %d" % (what, name, len(x), len(y))
-        a, b = x.view(np.uint8).reshape(len(x), -1), y.view(np.uint8).reshape(len(y), -1)
-        bad = np.flatnonzero((a != b).any(axis=1))
-        assert bad.size == 0, "%s: %s differ at %d of %d points, first %d: %r vs %r" % (what, name, bad.size, len(x), bad[0], x[bad[0]],
-                                                                                       y[bad[0]])
-
-
-def _held_out(synth_mod, W=640, H=480, f=HELD_OUT):
-    pose = synth_mod.pose(POSE_SEED, f)
-    depth, _, K = synth_mod.depth_frame(SEED, f, W, H, pose)
-    return depth, K, pose
-
-
 def _point_sets(synth_mod, g, rows):
     """(label, points (N, 3) f32, pose, depth image or None) of the three sets."""
-    depth, K, pose = _held_out(synth_mod)
+    depth, K, pose = held_out(synth_mod)
     rng = np.random.default_rng(0x9E7)
     b = np.asarray(_bbox(g))
     span = b[1::2] - b[0::2]
     rand = rng.uniform(b[0::2] - 0.05 * span, b[1::2] + 0.05 * span, (100000, 3)).astype(np.float32)
-    ident = np.hstack([np.eye(3), np.zeros((3, 1))])
     live = rows[rows["count"] > 0]
     xyz = np.stack([live["x"], live["y"], live["z"]], axis=1).astype(np.float32)
     jit = (xyz + rng.normal(0.0, 0.002, xyz.shape)).astype(np.float32)
-    return [("held-out depth frame", Q.depth_points(depth, K), pose, (depth, K)), ("random in and around the bbox", rand, ident, None),
-            ("jittered row centroids", jit, ident, None)]
+    return [("held-out depth frame", Q.depth_points(depth, K), pose, (depth, K)), ("random in and around the bbox", rand, IDENT, None),
+            ("jittered row centroids", jit, IDENT, None)]
 
 
 @pytest.fixture(scope="module")
 def session(hfpf_mod, synth_mod):
     sc = DepthScene(12, 640, 480, clean_every=4)
-    g = _grid(hfpf_mod)
-    _run(g, sc)
+    g = grid(hfpf_mod)
+    run(g, sc)
     rows = g.extract().copy()
     occ = g.occupied()
     yield sc, g, rows, occ
@@ -85,7 +65,7 @@ def test_bit_exact_against_query_ref(hfpf_mod, synth_mod, session, opt):
         print("%s, %s: %d points, %d used, %d in bbox, %d occupied, %d has_row, %d found" % (
             label, opt, len(pts), (flags & Q.USED != 0).sum(), (flags & Q.IN_BBOX != 0).sum(), (flags & Q.OCCUPIED != 0).sum(),
             (flags & Q.HAS_ROW != 0).sum(), (flags & Q.FOUND != 0).sum()))
-        _same(got, ref, "%s, %s" % (label, opt))
+        same_query(got, ref, "%s, %s" % (label, opt))
         assert (flags & Q.FOUND != 0).sum() > (20 if img is None and label.startswith("random") else 10000)
 
 
@@ -93,9 +73,9 @@ def test_bit_exact_against_query_ref(hfpf_mod, synth_mod, session, opt):
 
 def test_a_frame_queried_after_its_integrate_lands_in_occupied_cells(hfpf_mod, synth_mod):
     sc = DepthScene(6, 640, 480, clean_every=3)
-    depth, K, pose = _held_out(synth_mod)
-    with _grid(hfpf_mod) as g:
-        _run(g, sc)
+    depth, K, pose = held_out(synth_mod)
+    with grid(hfpf_mod) as g:
+        run(g, sc)
         g.integrate_depth(depth, pose, K)  # a host frame: the query launches it first
         hits, _ = g.query_depth(depth, pose, K, radius=1, zclip=True, rows=False)
         f = hits["flags"]
@@ -109,32 +89,28 @@ def test_a_frame_queried_after_its_integrate_lands_in_occupied_cells(hfpf_mod, s
         assert np.array_equal(inside, (pflags & 3) == 3)
         assert hits["voxel"][used].tobytes() == idx[used].tobytes()
         assert hits["p"][used].tobytes() == q[used].tobytes()
-        _same((hits, None), (_ref(g, g.extract(), g.occupied(), pts, pose, 1, 0.0, INF, True)[0], None), "after integrate")
+        same_query((hits, None), (_ref(g, g.extract(), g.occupied(), pts, pose, 1, 0.0, INF, True)[0], None), "after integrate")
 
 
 # ---- 3. equivalent inputs -------------------------------------------------------------------------------------------
 
 def test_host_cloud_device_cloud_and_depth_forms_agree(hfpf_mod, synth_mod, session):
     sc, g, rows, occ = session
-    depth, K, pose = _held_out(synth_mod)
+    depth, K, pose = held_out(synth_mod)
     kw = dict(radius=2, min_count=2.0, zclip=True)
     a = g.query_depth(depth, pose, K, **kw)
     cloud = depth_ref.packed_cloud(depth, K)  # 16-byte records: the packed form
     layout16 = dict(point_step=16, off_x=0, off_y=4, off_z=8)
     b = g.query(cloud, pose, layout=layout16, **kw)
     c = g.query(Q.depth_points(depth, K), pose, **kw)  # 12-byte records: the strided form
-    dev = g.device_alloc(cloud.nbytes)
-    try:
-        g.device_upload(dev, cloud)
+    with uploaded(g, cloud) as (dev,):
         d = g.query_device(dev, len(cloud) // 16, pose, layout=layout16, **kw)
         e = g.query_device(dev, len(cloud) // 16 - 1, pose, layout=dict(point_step=16, off_x=8, off_y=4, off_z=0), **kw)  # strided
-    finally:
-        g.device_free(dev)
     for what, x in (("host packed cloud", b), ("host strided cloud", c), ("device packed cloud", d)):
-        _same(x, a, what)
+        same_query(x, a, what)
     assert (a[0]["flags"] & Q.FOUND != 0).sum() > 100000
     # x and z swapped: the same as a host cloud with that layout
-    _same(e, g.query(cloud[:len(cloud) - 16], pose, layout=dict(point_step=16, off_x=8, off_y=4, off_z=0), **kw), "swapped axes")
+    same_query(e, g.query(cloud[:len(cloud) - 16], pose, layout=dict(point_step=16, off_x=8, off_y=4, off_z=0), **kw), "swapped axes")
     # without rows, the hits are those of a call with rows
     h, r = g.query_depth(depth, pose, K, rows=False, **kw)
     assert r is None and h.tobytes() == a[0].tobytes()
@@ -157,22 +133,14 @@ def test_queries_change_nothing(hfpf_mod, synth_mod):
         else:
             g.query_depth(sc.frames[i % sc.n_frames][0], sc.poses[0], K, radius=1, zclip=True)
 
-    with _grid(hfpf_mod) as a, _grid(hfpf_mod) as b:
-        _run(a, sc)
-        b.query(pts, sc.poses[0])  # on the empty handle
-        _run(b, sc, between=look)
-        ra, rb = a.extract(), b.extract()
-        assert len(ra) > 0 and ra.tobytes() == rb.tobytes()
-        assert _counters(a) == _counters(b)
+    with two_handles(hfpf_mod, sc, look, lambda b: b.query(pts, sc.poses[0])) as (a, b, rb):
         ia = a.render(sc.poses[2], K, sc.W, sc.H, z_range=(0.05, 3.0), splat_radius=2)
-        ib = b.render(sc.poses[2], K, sc.W, sc.H, z_range=(0.05, 3.0), splat_radius=2)
-        for k in ia:
-            assert ia[k].tobytes() == ib[k].tobytes(), k
+        same_planes(ia, b.render(sc.poses[2], K, sc.W, sc.H, z_range=(0.05, 3.0), splat_radius=2), "a render of both handles")
         one = b.query(pts, sc.poses[1], radius=2)
         two = b.query(pts, sc.poses[1], radius=2)
-        _same(one, two, "second query")
-        _same(one, _ref(b, rb, b.occupied(), pts, sc.poses[1], 2, 0.0, INF, False), "query_ref")
-        assert b.extract().tobytes() == ra.tobytes() and _counters(a) == _counters(b)
+        same_query(one, two, "second query")
+        same_query(one, _ref(b, rb, b.occupied(), pts, sc.poses[1], 2, 0.0, INF, False), "query_ref")
+        unchanged(a, b, rb)
 
 
 # ---- 5. edges -------------------------------------------------------------------------------------------------------
@@ -180,7 +148,7 @@ def test_queries_change_nothing(hfpf_mod, synth_mod):
 def test_empty_and_uncleaned_handles_find_nothing(hfpf_mod, synth_mod):
     sc = DepthScene(3, 320, 240, clean_every=0)
     depth, K = sc.frames[0][0], sc.K
-    with _grid(hfpf_mod) as g:
+    with grid(hfpf_mod) as g:
         hits, rows = g.query_depth(depth, sc.poses[0], K, radius=4)
         assert not (hits["flags"] & (Q.OCCUPIED | Q.HAS_ROW | Q.FOUND)).any() and (hits["flags"] & Q.IN_BBOX).any()
         assert (rows["ix"] == -1).all() and not rows["count"].any()
@@ -190,14 +158,14 @@ def test_empty_and_uncleaned_handles_find_nothing(hfpf_mod, synth_mod):
         pts = Q.depth_points(depth, K)
         got = g.query_depth(depth, sc.poses[0], K, radius=4, zclip=True)
         assert not (got[0]["flags"] & Q.FOUND).any() and (got[0]["flags"] & Q.OCCUPIED != 0).sum() > 10000
-        _same(got, _ref(g, g.extract(), g.occupied(), pts, sc.poses[0], 4, 0.0, INF, True), "before the first clean")
+        same_query(got, _ref(g, g.extract(), g.occupied(), pts, sc.poses[0], 4, 0.0, INF, True), "before the first clean")
 
 
 def test_bad_arguments_are_refused_and_the_handle_stays_usable(hfpf_mod, synth_mod):
     H_ = hfpf_mod
     sc = DepthScene(6, 160, 120, clean_every=3)
-    with _grid(hfpf_mod) as ref:
-        _run(ref, sc)
+    with grid(hfpf_mod) as ref:
+        run(ref, sc)
         want = ref.extract().copy()
     L = H_.lib()
     bad = {"struct_size": ("struct_size", C.sizeof(H_.QueryOpts) - 8), "flags": ("flags", 2), "reserved0": ("reserved0", 1),
@@ -208,7 +176,7 @@ def test_bad_arguments_are_refused_and_the_handle_stays_usable(hfpf_mod, synth_m
     depth, K = sc.frames[0][0], sc.K
     d = H_._image_desc(depth, K, None, None, 0.001)
     n_px = sc.W * sc.H
-    with _grid(hfpf_mod) as g:
+    with grid(hfpf_mod) as g:
         for i, ev in enumerate(sc.schedule()):
             if ev[0] == "integrate":
                 sc.integrate(g, ev[1])
@@ -270,7 +238,7 @@ def test_bad_arguments_are_refused_and_the_handle_stays_usable(hfpf_mod, synth_m
                 g.device_free(dev)
         assert g.extract().tobytes() == want.tobytes()
         occ = g.occupied()
-        _same(g.query(pts, sc.poses[0], radius=2), _ref(g, want, occ, pts, sc.poses[0], 2, 0.0, INF, False), "after the refusals")
+        same_query(g.query(pts, sc.poses[0], radius=2), _ref(g, want, occ, pts, sc.poses[0], 2, 0.0, INF, False), "after the refusals")
 
 
 def test_a_cloud_of_several_chunks_is_exact(hfpf_mod, synth_mod, session):
@@ -280,7 +248,6 @@ def test_a_cloud_of_several_chunks_is_exact(hfpf_mod, synth_mod, session):
     xyz = np.stack([live["x"], live["y"], live["z"]], axis=1).astype(np.float32)
     n = (1 << 20) * 2 + 12345  # three chunks of the host forms
     pts = (xyz[rng.integers(0, len(xyz), n)] + rng.normal(0.0, 0.003, (n, 3))).astype(np.float32)
-    ident = np.hstack([np.eye(3), np.zeros((3, 1))])
-    got = g.query(pts, ident, radius=1, min_count=2.0)
-    _same(got, _ref(g, rows, occ, pts, ident, 1, 2.0, INF, False), "three chunks")
+    got = g.query(pts, IDENT, radius=1, min_count=2.0)
+    same_query(got, _ref(g, rows, occ, pts, IDENT, 1, 2.0, INF, False), "three chunks")
     assert (got[0]["flags"] & Q.FOUND != 0).sum() > n // 2

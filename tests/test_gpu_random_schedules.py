@@ -7,9 +7,9 @@ import numpy as np
 import pytest
 
 import scenes
+from gpu_support import SMALL_CAPS
 
 pytestmark = pytest.mark.gpu
-SMALL = dict(max_bricks=60000, max_log_points=4 << 20, max_normals=1 << 20, max_frames=4096)
 
 
 def _script(rng, n_frames):
@@ -51,7 +51,7 @@ def test_random_schedule(oracle_mod, hfpf_mod, synth_mod, seed):
     ops = _script(rng, sc.n_frames)
     og = oracle_mod.OracleGrid(resolution=res, bbox=sc.bbox, **cfg)
     fw = W if (seed // 2) % 2 else 0  # scheduling hint on for half of the seeds (120-row scenes fall back to runs)
-    eg = hfpf_mod.OccupancyGrid(resolution=res, bbox=sc.bbox, binned_update=bool(seed % 2), frame_width=fw, **cfg, **SMALL)
+    eg = hfpf_mod.OccupancyGrid(resolution=res, bbox=sc.bbox, binned_update=bool(seed % 2), frame_width=fw, **cfg, **SMALL_CAPS)
     n_checked = 0
     try:
         for op in ops:

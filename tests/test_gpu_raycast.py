@@ -8,11 +8,10 @@ import pytest
 
 import query_ref as Q
 import raycast_ref as RC
-from test_gpu_render import DepthScene, _counters, _grid, _run
+from gpu_support import HELD_OUT, IDENT, POSE_SEED, SEED, counters, grid, rays_device, run, same_rays, two_handles, unchanged, uploaded
+from scenes import DepthScene
 
 pytestmark = pytest.mark.gpu
-HELD_OUT = 40          # frame index of the synthetic stream that is viewed and never integrated
-SEED, POSE_SEED = 0xD3F7, 0x5E3
 INF = float("inf")
 VIEW_W, VIEW_H = 128, 96   # (96 x 72 gave 95 NEAR-without-HIT rays on the reference at radius 3: enlarged to meet the condition)
 VIEW_Z = (0.25, 0.65)
@@ -23,19 +22,10 @@ OPTION_SETS = [dict(radius=1, min_count=0.0, max_distance=INF, step=0.5, cull_ba
                dict(radius=3, min_count=0.0, max_distance=0.004, step=0.5, cull_backfaces=False),
                dict(radius=4, min_count=0.0, max_distance=0.006, step=1.5, cull_backfaces=True)]
 IDS = ["r%d_mc%g_md%g_s%g_c%d" % (o["radius"], o["min_count"], o["max_distance"], o["step"], o["cull_backfaces"]) for o in OPTION_SETS]
-IDENT = RC.IDENT
 
 
 def _bbox(g):
     return tuple(g.cfg.bbox)
-
-
-def _same(got, ref, what):
-    got, ref = np.ascontiguousarray(got).reshape(-1), np.ascontiguousarray(ref).reshape(-1)
-    assert len(got) == len(ref), "%s: %d vs %d hits" % (what, len(got), len(ref))
-    a, b = got.view(np.uint8).reshape(len(got), -1), ref.view(np.uint8).reshape(len(ref), -1)
-    bad = np.flatnonzero((a != b).any(axis=1))
-    assert bad.size == 0, "%s: hits differ at %d of %d rays, first %d: %r vs %r" % (what, bad.size, len(got), bad[0], got[bad[0]], ref[bad[0]])
 
 
 def _view(synth_mod, W=VIEW_W, H=VIEW_H, f=HELD_OUT):
@@ -113,22 +103,12 @@ def _coverage(label, opt, ref, hit_min, near_min):
 @pytest.fixture(scope="module")
 def session(hfpf_mod, synth_mod):
     sc = DepthScene(12, 640, 480, clean_every=4)
-    g = _grid(hfpf_mod)
-    _run(g, sc)
+    g = grid(hfpf_mod)
+    run(g, sc)
     rows = g.extract().copy()
     occ = g.occupied()
     yield sc, g, rows, occ
     g.close()
-
-
-def _device_rays(g, rays, pose, **kw):
-    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
-    d = g.device_alloc(max(1, rays.nbytes))
-    try:
-        g.device_upload(d, rays)
-        return g.raycast_device(d, len(rays), pose, **kw)
-    finally:
-        g.device_free(d)
 
 
 # ---- 1. byte-identical to the dense march of the numpy contract ---------------------------------------------------------------
@@ -140,14 +120,14 @@ def test_byte_identical_to_raycast_ref(hfpf_mod, synth_mod, session, opt):
     pose, K = _view(synth_mod)
     ref = RC.raycast_view(rows, occ, pose, K, VIEW_W, VIEW_H, _bbox(g), res, t_range=VIEW_Z, **opt)
     _coverage("held-out view %dx%d" % (VIEW_W, VIEW_H), opt, ref, 1000, 100)
-    _same(g.raycast_view(pose, K, VIEW_W, VIEW_H, t_range=VIEW_Z, **opt), ref, "view, host form, %s" % opt)
-    _same(g.raycast_views_device([pose], K, VIEW_W, VIEW_H, t_range=VIEW_Z, **opt), ref, "view, device form, %s" % opt)
+    same_rays(g.raycast_view(pose, K, VIEW_W, VIEW_H, t_range=VIEW_Z, **opt), ref, "view, host form, %s" % opt)
+    same_rays(g.raycast_views_device([pose], K, VIEW_W, VIEW_H, t_range=VIEW_Z, **opt), ref, "view, device form, %s" % opt)
     # (the axis-aligned set has 2,400 rays, 400 a direction, and meets the same condition)
     for label, rays, hit_min, near_min in (("random rays", _random_rays(g, rows, res), 1000, 100), ("axis rays on cell boundaries", _axis_rays(g, rows, res), 1000, 100)):
         ref = RC.raycast(rows, occ, rays, IDENT, _bbox(g), res, t_range=RAY_T, **opt)
         _coverage(label, opt, ref, hit_min, near_min)
-        _same(g.raycast(rays, IDENT, t_range=RAY_T, **opt), ref, "%s, host form, %s" % (label, opt))
-        _same(_device_rays(g, rays, IDENT, t_range=RAY_T, **opt), ref, "%s, device form, %s" % (label, opt))
+        same_rays(g.raycast(rays, IDENT, t_range=RAY_T, **opt), ref, "%s, host form, %s" % (label, opt))
+        same_rays(rays_device(g, rays, IDENT, t_range=RAY_T, **opt), ref, "%s, device form, %s" % (label, opt))
 
 
 # ---- 2. equivalent forms ------------------------------------------------------------------------------------------------------
@@ -161,8 +141,8 @@ def test_equivalent_forms(hfpf_mod, synth_mod, session):
     batch = g.raycast_views_device(poses, K, 160, 120, **kw)
     for v, p in enumerate(poses):
         single = g.raycast_view(p, K, 160, 120, **kw)
-        _same(batch[v], single, "view %d of a batch against the host form" % v)
-        _same(g.raycast_views_device([p], K, 160, 120, **kw), single, "view %d alone on the device" % v)
+        same_rays(batch[v], single, "view %d of a batch against the host form" % v)
+        same_rays(g.raycast_views_device([p], K, 160, 120, **kw), single, "view %d alone on the device" % v)
         assert (single["flags"] & RC.HIT != 0).sum() > 1000
     # more than 2^20 rays through the host form (two chunks) against the same rays cast in two halves
     base = _random_rays(g, rows, res, seed=0xB22)
@@ -172,8 +152,8 @@ def test_equivalent_forms(hfpf_mod, synth_mod, session):
     kw = dict(radius=2, step=1.0, t_range=RAY_T)
     whole = g.raycast(rays, IDENT, **kw)
     half = len(rays) // 2 + 7
-    _same(whole, np.concatenate([g.raycast(rays[:half], IDENT, **kw), g.raycast(rays[half:], IDENT, **kw)]), "chunked host call against two halves")
-    _same(whole, _device_rays(g, rays, IDENT, **kw), "chunked host call against one device call")
+    same_rays(whole, np.concatenate([g.raycast(rays[:half], IDENT, **kw), g.raycast(rays[half:], IDENT, **kw)]), "chunked host call against two halves")
+    same_rays(whole, rays_device(g, rays, IDENT, **kw), "chunked host call against one device call")
     assert (whole["flags"] & RC.HIT != 0).sum() > 100000
 
 
@@ -214,24 +194,21 @@ def test_a_raycast_changes_nothing(hfpf_mod, synth_mod):
     def look(g, i):
         g.raycast_view(sc.poses[i % sc.n_frames], K, 80, 60, radius=1 + i % 4, t_range=VIEW_Z, cull_backfaces=bool(i & 1))
 
-    with _grid(hfpf_mod) as a, _grid(hfpf_mod) as b:
-        _run(a, sc)
-        h0 = b.raycast_view(sc.poses[0], K, 80, 60, t_range=VIEW_Z)  # before the first clean
+    def on_empty(b):  # before the first clean
+        h0 = b.raycast_view(sc.poses[0], K, 80, 60, t_range=VIEW_Z)
         assert (h0["flags"] == RC.USED).all()
-        _run(b, sc, between=look)
-        ra, rb = a.extract(), b.extract()
-        assert len(ra) > 0 and ra.tobytes() == rb.tobytes()
-        assert _counters(a) == _counters(b)
+
+    with two_handles(hfpf_mod, sc, look, on_empty) as (a, b, rb):
         one = b.raycast_view(sc.poses[2], K, sc.W, sc.H, t_range=VIEW_Z)
         two = b.raycast_view(sc.poses[2], K, sc.W, sc.H, t_range=VIEW_Z)
-        _same(one, two, "second raycast")
+        same_rays(one, two, "second raycast")
         assert (one["flags"] & RC.HIT != 0).sum() > 10000
-        assert b.extract().tobytes() == ra.tobytes() and _counters(a) == _counters(b)
+        unchanged(a, b, rb)
         depth, rgb, Kf = sc.frames[1]
         for g in (a, b):
             g.integrate_depth(depth, sc.poses[1], Kf, color=rgb)
             g.clean()
-        assert a.extract().tobytes() == b.extract().tobytes() and _counters(a) == _counters(b)
+        assert a.extract().tobytes() == b.extract().tobytes() and counters(a) == counters(b)
         assert a.occupied().tobytes() == b.occupied().tobytes()
 
 
@@ -244,8 +221,8 @@ def test_bad_arguments_are_refused_and_the_handle_stays_usable(hfpf_mod, synth_m
     nan, inf = float("nan"), float("inf")
     bad = [("struct_size", 56), ("flags", 2), ("reserved0", 1), ("reserved", 1), ("radius", 0), ("radius", 5), ("min_count", nan), ("max_distance", 0.0),
            ("max_distance", nan), ("step", 0.1), ("step", 4.5), ("step", nan), ("t_min", -0.1), ("t_min", nan), ("t_min", 2.0), ("t_max", inf)]
-    with _grid(hfpf_mod) as g:
-        _run(g, sc)
+    with grid(hfpf_mod) as g:
+        run(g, sc)
         want = g.extract().copy()
         pose = np.ascontiguousarray(sc.poses[1], np.float64).reshape(12)
         K = sc.K
@@ -288,22 +265,22 @@ def test_bad_arguments_are_refused_and_the_handle_stays_usable(hfpf_mod, synth_m
         assert hits.tobytes() == before
         g.device_free(dev)
         assert g.extract().tobytes() == want.tobytes()
-        _same(g.raycast_view(pose, K, 40, 30, t_range=VIEW_Z), good, "after the refusals")
+        same_rays(g.raycast_view(pose, K, 40, 30, t_range=VIEW_Z), good, "after the refusals")
 
 
 def test_empty_and_cleared_handles_return_no_hits(hfpf_mod, synth_mod):
     sc = DepthScene(4, 160, 120, clean_every=2)
     rays = np.array([[0, 0, -0.2, 0, 0, 1], [np.nan, 0, 0, 0, 0, 1], [0, 0, 0, 0, 0, 0]], np.float32)
-    with _grid(hfpf_mod) as g:
+    with grid(hfpf_mod) as g:
         def check():
             h = g.raycast_view(sc.poses[0], sc.K, 32, 24, t_range=VIEW_Z)
-            _same(h, RC.raycast_view(np.zeros(0, hfpf_mod.ROW_DTYPE), np.zeros((0, 3), np.int32), sc.poses[0], sc.K, 32, 24, _bbox(g), g.dims[1], t_range=VIEW_Z),
+            same_rays(h, RC.raycast_view(np.zeros(0, hfpf_mod.ROW_DTYPE), np.zeros((0, 3), np.int32), sc.poses[0], sc.K, 32, 24, _bbox(g), g.dims[1], t_range=VIEW_Z),
                   "empty model")
             assert (h["flags"] == RC.USED).all()
             r = g.raycast(rays, IDENT, t_range=RAY_T)
             assert list(r["flags"]) == [RC.USED, 0, 0] and (r["t"].view(np.uint32) == RC.NAN_BITS).all() and (r["row_voxel"] == -1).all()
         check()
-        _run(g, sc)
+        run(g, sc)
         assert (g.raycast_view(sc.poses[0], sc.K, 32, 24, t_range=VIEW_Z)["flags"] & RC.HIT != 0).any()
         g.clear()
         check()
@@ -317,8 +294,8 @@ def test_full_size_view_against_the_sparse_oracle(hfpf_mod, synth_mod):
     W, H, n_frames = 640, 480, 24
     sc = DepthScene(n_frames, W, H, clean_every=8)
     opt = dict(radius=2, step=0.5, t_range=VIEW_Z)
-    with _grid(hfpf_mod, resolution=0.001, max_bricks=400000, max_log_points=n_frames * W * H, max_normals=8 << 20) as g:
-        _run(g, sc)
+    with grid(hfpf_mod, resolution=0.001, max_bricks=400000, max_log_points=n_frames * W * H, max_normals=8 << 20) as g:
+        run(g, sc)
         res = g.dims[1]
         pose, K = _view(synth_mod, W, H)
         h = g.raycast_view(pose, K, W, H, **opt).reshape(-1)
@@ -335,12 +312,8 @@ def test_full_size_view_against_the_sparse_oracle(hfpf_mod, synth_mod):
             return (O[ray] + tk[:, None] * D[ray]).astype(np.float32)
 
         def query(pts):
-            d = g.device_alloc(pts.nbytes)
-            try:
-                g.device_upload(d, np.ascontiguousarray(pts))
+            with uploaded(g, pts) as (d,):
                 return g.query_device(d, len(pts), IDENT, radius=opt["radius"])
-            finally:
-                g.device_free(d)
 
         k = h["sample"][hit].astype(np.int64)
         (qa, ra), (qb, rb) = query(samples(hit, k - 1)), query(samples(hit, k))

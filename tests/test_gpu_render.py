@@ -6,55 +6,12 @@ import numpy as np
 import pytest
 
 import render_ref as R
-import scenes
+from gpu_support import BBOX, grid, run, same_planes, two_handles, unchanged
+from scenes import DepthScene
 
 pytestmark = pytest.mark.gpu
-CAPS = dict(max_bricks=120000, max_log_points=8 << 20, max_normals=1 << 21, max_frames=4096)
-BBOX = scenes.BBOX_1M
-RES = 0.002
 PLANES = ("depth", "normal", "rgb", "count", "voxel")
 Z_RANGE = (0.05, 3.0)
-
-
-class DepthScene:
-    """A seeded stream of synthetic depth frames (uint16 + RGB8) with random poses and a clean schedule (as test_gpu_depth)."""
-
-    def __init__(self, n_frames, W, H, clean_every=4, seed=0xD3F7, pose_seed=0x5E3):
-        import hfpf_synth as S
-        self.n_frames, self.W, self.H, self.clean_every = n_frames, W, H, clean_every
-        self.poses = [S.pose(pose_seed, f) for f in range(n_frames)]
-        self.frames = [S.depth_frame(seed, f, W, H, self.poses[f]) for f in range(n_frames)]
-        self.K = self.frames[0][2]
-
-    def schedule(self):
-        return scenes.Scene.schedule(self)
-
-    def integrate(self, g, f):
-        depth, rgb, K = self.frames[f]
-        g.integrate_depth(depth, self.poses[f], K, color=rgb)
-
-
-def _grid(hfpf_mod, resolution=RES, **kw):
-    return hfpf_mod.OccupancyGrid(resolution=resolution, bbox=BBOX, fuse_color=True, **dict(CAPS, **kw))
-
-
-def _run(g, sc, between=None):
-    for i, ev in enumerate(sc.schedule()):
-        if ev[0] == "integrate":
-            sc.integrate(g, ev[1])
-        else:
-            g.clean()
-        if between:
-            between(g, i)
-
-
-def _counters(g):
-    c = g.counters()
-    c.pop("device_bytes")  # counts the scratch a render keeps (include/hfpf.h)
-    # how the binned update scheduled its work: depends on how host frames were batched (a render launches waiting frames)
-    for k in ("points_direct", "table_misses", "update_extra_rounds"):
-        c.pop(k)
-    return c
 
 
 def _pose(R3, t):
@@ -74,15 +31,6 @@ def _behind(pose, rows):
     return _pose(pose[:, :3] @ np.diag([-1.0, 1.0, -1.0]), 2 * c - pose[:, 3])
 
 
-def _same(got, ref, what):
-    for name in got:
-        a, b = np.ascontiguousarray(got[name]), np.ascontiguousarray(ref[name])
-        if a.tobytes() != b.tobytes():
-            bad = np.flatnonzero((a.view(np.uint32) != b.view(np.uint32)).reshape(a.shape[0] * a.shape[1], -1).any(axis=1))
-            raise AssertionError("%s: plane %s differs at %d pixels, first (v, u) = %s: %r vs %r" % (
-                what, name, bad.size, divmod(int(bad[0]), a.shape[1]), a.reshape(-1, *a.shape[2:])[bad[0]], b.reshape(-1, *b.shape[2:])[bad[0]]))
-
-
 def _empty(img):
     assert (img["depth"].view(np.uint32) == R.NAN_BITS).all() and (img["normal"].view(np.uint32) == R.NAN_BITS).all()
     assert not img["rgb"].any() and not img["count"].any() and (img["voxel"] == -1).all()
@@ -91,8 +39,8 @@ def _empty(img):
 @pytest.fixture(scope="module")
 def session(hfpf_mod, synth_mod):
     sc = DepthScene(12, 640, 480, clean_every=4)
-    g = _grid(hfpf_mod)
-    _run(g, sc)
+    g = grid(hfpf_mod)
+    run(g, sc)
     rows = g.extract().copy()
     yield sc, g, rows
     g.close()
@@ -121,7 +69,7 @@ def test_bit_exact_against_render_ref(hfpf_mod, session):
             got = g.render(pose, sc.K, sc.W, sc.H, **kw)
             flags = (R.CULL_BACKFACES if cull else 0) | (R.WORLD_NORMALS if wn else 0)
             ref = R.render(rows, pose, sc.K, sc.W, sc.H, res, Z_RANGE, mc, rad, 4, flags)
-            _same(got, ref, "%s, options %r" % (label, OPTION_SETS[oi]))
+            same_planes(got, ref, "%s, options %r" % (label, OPTION_SETS[oi]))
             drawn = ~np.isnan(got["depth"])
             assert (got["count"][drawn] >= max(1, mc)).all()
             n_drawn.setdefault(label, []).append(int(drawn.sum()))
@@ -137,7 +85,7 @@ def test_count_zero_rows_are_never_drawn(hfpf_mod, session):
     for mc in (0, 1):
         got = g.render(pose, sc.K, sc.W, sc.H, z_range=Z_RANGE, min_count=mc, splat_radius=1)
         assert (got["count"][~np.isnan(got["depth"])] > 0).all()
-        _same(got, R.render(rows, pose, sc.K, sc.W, sc.H, g.dims[1], Z_RANGE, mc, 1), "origin view")
+        same_planes(got, R.render(rows, pose, sc.K, sc.W, sc.H, g.dims[1], Z_RANGE, mc, 1), "origin view")
 
 
 # ---- 2. batches ---------------------------------------------------------------------------------------------------
@@ -173,7 +121,7 @@ def test_device_batch_equals_single_views(hfpf_mod, session):
     got = _device_batch(g, poses, K, W, H, PLANES, **kw)
     for v, pose in enumerate(poses):
         one = g.render(pose, K, W, H, **kw)
-        _same({p: got[p][v] for p in PLANES}, one, "view %d of 70" % v)
+        same_planes({p: got[p][v] for p in PLANES}, one, "view %d of 70" % v)
     assert (~np.isnan(got["depth"])).sum() > 70 * 100
     # 17 views of 2048 x 1024: 16 views fill the 256 MB z-buffer chunk, the 17th is a second chunk
     W, H = 2048, 1024
@@ -183,9 +131,9 @@ def test_device_batch_equals_single_views(hfpf_mod, session):
     got = _device_batch(g, poses, K, W, H, ("depth", "rgb"), **kw)
     for v in (0, 15, 16):
         one = g.render(poses[v], K, W, H, planes=("depth", "rgb"), **kw)
-        _same({p: got[p][v] for p in ("depth", "rgb")}, one, "view %d of 17 at 2048x1024" % v)
+        same_planes({p: got[p][v] for p in ("depth", "rgb")}, one, "view %d of 17 at 2048x1024" % v)
     ref = R.render(rows, poses[16], K, W, H, g.dims[1], Z_RANGE, 2, 1)
-    _same({p: got[p][16] for p in ("depth", "rgb")}, {p: ref[p] for p in ("depth", "rgb")}, "view 16 against render_ref")
+    same_planes({p: got[p][16] for p in ("depth", "rgb")}, {p: ref[p] for p in ("depth", "rgb")}, "view 16 against render_ref")
 
 
 # ---- 3. no side effects ---------------------------------------------------------------------------------------------
@@ -202,27 +150,21 @@ def test_renders_change_nothing(hfpf_mod, synth_mod):
             g.render_device(np.stack([sc.poses[0], sc.poses[1]]), K, sc.W, sc.H, {"count": ptr}, z_range=Z_RANGE)
             g.device_free(ptr)
 
-    with _grid(hfpf_mod) as a, _grid(hfpf_mod) as b:
-        _run(a, sc)
-        b.render(sc.poses[0], K, sc.W, sc.H)  # on the empty handle
-        _run(b, sc, between=look)
-        ra, rb = a.extract(), b.extract()
-        assert len(ra) > 0 and ra.tobytes() == rb.tobytes()
-        assert _counters(a) == _counters(b)
+    with two_handles(hfpf_mod, sc, look, lambda b: b.render(sc.poses[0], K, sc.W, sc.H)) as (a, b, rb):
         one = b.render(sc.poses[2], K, sc.W, sc.H, z_range=Z_RANGE, splat_radius=2)
         two = b.render(sc.poses[2], K, sc.W, sc.H, z_range=Z_RANGE, splat_radius=2)
-        _same(one, two, "second render")
-        _same(one, R.render(rb, sc.poses[2], K, sc.W, sc.H, b.dims[1], Z_RANGE, 0, 2), "render_ref")
-        assert b.extract().tobytes() == ra.tobytes() and _counters(a) == _counters(b)
+        same_planes(one, two, "second render")
+        same_planes(one, R.render(rb, sc.poses[2], K, sc.W, sc.H, b.dims[1], Z_RANGE, 0, 2), "render_ref")
+        unchanged(a, b, rb)
 
 
 # ---- 4. edges -------------------------------------------------------------------------------------------------------
 
 def test_empty_and_cleared_handles_render_nothing(hfpf_mod, synth_mod):
     sc = DepthScene(3, 160, 120, clean_every=0)
-    with _grid(hfpf_mod) as g:
+    with grid(hfpf_mod) as g:
         _empty(g.render(sc.poses[0], sc.K, sc.W, sc.H, splat_radius=2))
-        _run(g, sc)
+        run(g, sc)
         img = g.render(sc.poses[0], sc.K, sc.W, sc.H, z_range=Z_RANGE)
         assert (~np.isnan(img["depth"])).sum() > 100
         g.clear()
@@ -236,8 +178,8 @@ def test_empty_and_cleared_handles_render_nothing(hfpf_mod, synth_mod):
 def test_bad_arguments_are_refused_and_the_handle_stays_usable(hfpf_mod, synth_mod):
     H_ = hfpf_mod
     sc = DepthScene(6, 160, 120, clean_every=3)
-    with _grid(hfpf_mod) as ref:
-        _run(ref, sc)
+    with grid(hfpf_mod) as ref:
+        run(ref, sc)
         want = ref.extract().copy()
     L = H_.lib()
     bad = {
@@ -249,7 +191,7 @@ def test_bad_arguments_are_refused_and_the_handle_stays_usable(hfpf_mod, synth_m
         "radius -2": ("splat_radius", -2), "radius 16": ("splat_radius", 16), "max radius -1": ("max_splat_radius", -1),
         "max radius 16": ("max_splat_radius", 16),
     }
-    with _grid(hfpf_mod) as g:
+    with grid(hfpf_mod) as g:
         for i, ev in enumerate(sc.schedule()):
             if ev[0] == "integrate":
                 sc.integrate(g, ev[1])
@@ -292,8 +234,8 @@ MIN_COVERAGE = 0.9
 
 def test_round_trip_from_an_integrate_pose(hfpf_mod, synth_mod):
     sc = DepthScene(8, 640, 480, clean_every=4)
-    with _grid(hfpf_mod) as g:
-        _run(g, sc)
+    with grid(hfpf_mod) as g:
+        run(g, sc)
         for f in (0, 5):
             depth, _, K = sc.frames[f]
             img = g.render(sc.poses[f], K, sc.W, sc.H, planes=("depth",), z_range=(0.1, 2.0), splat_radius=-1, max_splat_radius=4)
@@ -314,7 +256,7 @@ def test_two_million_rows_against_render_ref(hfpf_mod, synth_mod):
     sc = DepthScene(120, 640, 480, clean_every=30)
     with hfpf_mod.OccupancyGrid(resolution=0.001, bbox=BBOX, fuse_color=True, max_bricks=400000, max_log_points=120 * 640 * 480,
                                 max_normals=24 << 20, max_frames=4096, frame_width=640) as g:
-        _run(g, sc)
+        run(g, sc)
         rows = g.extract()
         assert len(rows) > 1_000_000, len(rows)
         for pose, kw in ((sc.poses[17], dict(splat_radius=-1, max_splat_radius=3, cull_backfaces=True)),
@@ -323,4 +265,4 @@ def test_two_million_rows_against_render_ref(hfpf_mod, synth_mod):
             flags = (R.CULL_BACKFACES if kw.get("cull_backfaces") else 0) | (R.WORLD_NORMALS if kw.get("world_normals") else 0)
             ref = R.render(rows, pose, sc.K, sc.W, sc.H, g.dims[1], Z_RANGE, kw.get("min_count", 0), kw["splat_radius"],
                            kw.get("max_splat_radius", 4), flags)
-            _same(got, ref, "2M-row model, %r" % kw)
+            same_planes(got, ref, "2M-row model, %r" % kw)

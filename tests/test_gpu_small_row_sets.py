@@ -8,8 +8,8 @@ The model is the scene of __graft_entry__.smoke() (4 frames of 160 x 120 at 1 mm
 apart, get 10, 8, 6, 4 and 2 more points at their fused positions, after which the counts separate behind the first, second, third
 and fifth row.  The thresholds are read from the sorted count column and the sizes they leave are asserted.
 
-Small sets are compared with components_ref, mesh_ref, deviation_ref and align_ref by the comparisons of test_gpu_components,
-test_gpu_mesh, test_gpu_deviation and test_gpu_align: byte for byte.  The whole model's results are compared with the same references
+Small sets are compared with components_ref, mesh_ref, deviation_ref and align_ref by the comparisons of
+tests/gpu_support.py: byte for byte.  The whole model's results are compared with the same references
 once, on their first visit, and must come back byte for byte on every later one.  tests/test_small_row_sets_scene.py holds the CPU
 check of the statement about the counts."""
 import numpy as np
@@ -19,19 +19,13 @@ import align_ref as A
 import components_ref as CR
 import cover_ref as V
 import deviation_ref as D
+import gpu_support as G
 import mesh_ref as M
 import raycast_ref as RC
 import scenes
-import test_gpu_align as TA
-import test_gpu_components as TC
-import test_gpu_cover as TV
-import test_gpu_deviation as TD
-import test_gpu_mesh as TM
-import test_gpu_raycast as TR
-from test_align_ref import rigid
+from gpu_support import IDENT
 
 pytestmark = pytest.mark.gpu
-IDENT = np.eye(4)[:3]
 RES = 0.001
 MD = 6 * RES  # compare's and align's max_distance
 EXTRA = (10, 8, 6, 4, 2)
@@ -81,12 +75,8 @@ def session(hfpf_mod, synth_mod):
 
 
 def _device_compare(g, H, verts, tris, pose, **kw):
-    dv, dt = g.device_alloc(max(verts.nbytes, 16)), g.device_alloc(max(tris.nbytes, 16))
-    try:
-        g.device_upload(dv, verts), g.device_upload(dt, tris)
-        return TD._device(g, H, dv, len(verts), verts.dtype.itemsize, dt, len(tris), pose, rows=True, **kw)
-    finally:
-        g.device_free(dv), g.device_free(dt)
+    with G.uploaded(g, verts, tris) as (dv, dt):
+        return G.compare_device(g, H, dv, len(verts), verts.dtype.itemsize, dt, len(tris), pose, rows=True, **kw)
 
 
 def _read_outs(g, H, mc, mesh, start):
@@ -96,10 +86,10 @@ def _read_outs(g, H, mc, mesh, start):
     mkw = dict(radius=2, min_count=mc)
     return dict(
         filtered=g.extract_filtered(mc).copy(),
-        components=(g.extract_components(**ckw), TC._device(g, H, **ckw)),
-        mesh=(g.extract_mesh(**mkw), TM._device(g, **mkw)),
+        components=(g.extract_components(**ckw), G.components_device(g, H, **ckw)),
+        mesh=(g.extract_mesh(**mkw), G.mesh_device(g, **mkw)),
         compare=(g.compare_mesh(sv, st, IDENT, rows=True, min_count=mc, max_distance=MD), _device_compare(g, H, sv, st, IDENT, min_count=mc, max_distance=MD)),
-        align=(g.align_mesh(sv, st, start, min_count=mc, **ALIGN_KW), TA._device_align(g, sv, st, start, min_count=mc, **ALIGN_KW)))
+        align=(g.align_mesh(sv, st, start, min_count=mc, **ALIGN_KW), G.align_device(g, sv, st, start, min_count=mc, **ALIGN_KW)))
 
 
 def test_small_row_sets_between_visits_of_the_whole_model(hfpf_mod, session):
@@ -112,17 +102,17 @@ def test_small_row_sets_between_visits_of_the_whole_model(hfpf_mod, session):
     sv, st = mesh
     print("own mesh of the five best rows: %d vertices, %d triangles" % (len(sv), len(st)))
     assert len(st) > 0
-    start = rigid(0.3, (0.5, 1.0, -0.4), (0.6 * 1.5 * RES, -0.64 * 1.5 * RES, 0.48 * 1.5 * RES), A.centre(bbox))
+    start = A.rigid(0.3, (0.5, 1.0, -0.4), (0.6 * 1.5 * RES, -0.64 * 1.5 * RES, 0.48 * 1.5 * RES), A.centre(bbox))
     whole = _read_outs(g, H, 0.0, mesh, start)  # the first growth of every buffer, pinned by the references like the small sets
     assert whole["filtered"].tobytes() == rows.tobytes() and len(whole["mesh"][0][1]) > 1000 and whole["align"][0]["iterations"] >= 1
     ref_whole = dict(components=CR.components(rows, reach=1), mesh=M.mesh(rows, occ, bbox, res, dims, radius=2)[:2],
                      compare=D.compare(rows, sv, 32, st, IDENT, 0.0, MD), align=A.align(rows, sv, 32, st, start, bbox, **ALIGN_KW))
     for form in (0, 1):
         name = "the whole model on the fresh handle, %s form" % ("host", "device")[form]
-        TC._same(whole["components"][form], ref_whole["components"], name)
-        TM._same(whole["mesh"][form], ref_whole["mesh"], name)
-        TD._same(whole["compare"][form][1:], ref_whole["compare"], name)
-        TA._equal(whole["align"][form], ref_whole["align"], name)
+        G.same_components(whole["components"][form], ref_whole["components"], name)
+        G.same_mesh(whole["mesh"][form], ref_whole["mesh"], name)
+        G.same_deviation(whole["compare"][form][1:], ref_whole["compare"], name)
+        G.same_align(whole["align"][form], ref_whole["align"], name)
     visits = 0
     for k in ORDER:
         mc = thr[k]
@@ -133,28 +123,28 @@ def test_small_row_sets_between_visits_of_the_whole_model(hfpf_mod, session):
         for form in (0, 1):
             name = "%s, %s form" % (what, ("host", "device")[form])
             if k == 0:
-                TC._same(got["components"][form], whole["components"][0], name)
-                TM._same(got["mesh"][form], whole["mesh"][0], name)
+                G.same_components(got["components"][form], whole["components"][0], name)
+                G.same_mesh(got["mesh"][form], whole["mesh"][0], name)
                 assert got["compare"][form][0].tobytes() == rows.tobytes(), name
-                TD._same(got["compare"][form][1:], whole["compare"][0][1:], name)
-                TA._equal(got["align"][form], whole["align"][0], name)
+                G.same_deviation(got["compare"][form][1:], whole["compare"][0][1:], name)
+                G.same_align(got["align"][form], whole["align"][0], name)
                 continue
             assert len(gated) == k
-            TC._same(got["components"][form], CR.components(gated, reach=1), name)
+            G.same_components(got["components"][form], CR.components(gated, reach=1), name)
             ref_mesh = M.mesh(rows, occ, bbox, res, dims, radius=2, min_count=mc)[:2]
-            TM._same(got["mesh"][form], ref_mesh, name)
+            G.same_mesh(got["mesh"][form], ref_mesh, name)
             assert got["compare"][form][0].tobytes() == gated.tobytes(), name
-            TD._same(got["compare"][form][1:], D.compare(rows, sv, 32, st, IDENT, mc, MD), name)
-            TA._equal(got["align"][form], A.align(rows, sv, 32, st, start, bbox, min_count=mc, **ALIGN_KW), name)
+            G.same_deviation(got["compare"][form][1:], D.compare(rows, sv, 32, st, IDENT, mc, MD), name)
+            G.same_align(got["align"][form], A.align(rows, sv, 32, st, start, bbox, min_count=mc, **ALIGN_KW), name)
         if k == 0:
             visits += 1
         if k == 0 and visits == 2:  # the whole model between 1 row and 3 rows: the two read-outs that take no min_count gate from it
             ckw = dict(radius=2, max_distance=2 * RES, spacing=RES)
-            TV._same(g.cover_mesh(sv, st, IDENT, **ckw), V.cover(rows, occ, sv, 32, st, IDENT, bbox, res, **ckw), "cover_mesh")
+            G.same_coverage(g.cover_mesh(sv, st, IDENT, **ckw), V.cover(rows, occ, sv, 32, st, IDENT, bbox, res, **ckw), "cover_mesh")
             K = (sc.fx * VIEW[0] / sc.W, sc.fx * VIEW[0] / sc.W, (VIEW[0] - 1) / 2.0, (VIEW[1] - 1) / 2.0)
             pose = np.asarray(sc.poses[0], np.float64).reshape(3, 4)
             hits = g.raycast_view(pose, K, VIEW[0], VIEW[1], t_range=(0.25, 0.65))
-            TR._same(hits, RC.raycast_view(rows, occ, pose, K, VIEW[0], VIEW[1], bbox, res, t_range=(0.25, 0.65)), "raycast_view")
+            G.same_rays(hits, RC.raycast_view(rows, occ, pose, K, VIEW[0], VIEW[1], bbox, res, t_range=(0.25, 0.65)), "raycast_view")
             assert (hits["flags"] & RC.HIT != 0).any()
     assert visits == 2
     assert g.extract().tobytes() == rows.tobytes(), "the read-outs changed the model"

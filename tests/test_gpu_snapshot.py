@@ -6,23 +6,15 @@ import numpy as np
 import pytest
 
 import scenes
+from gpu_support import SMALL_CAPS, contract_counters
 
 pytestmark = pytest.mark.gpu
-SMALL = dict(max_bricks=60000, max_log_points=4 << 20, max_normals=1 << 20, max_frames=4096)  # tests/test_gpu_random_schedules.py
-# hfpf_get_counters fields that results depend on (the contract's list)
-CONTRACT = ("points_presented", "points_zclip_pass", "points_in_bbox", "points_buffered", "dep_pairs_tested", "dep_pairs_member",
-            "voxels_occupied", "voxels_with_normal", "bricks_allocated", "registrations", "frames_integrated", "clean_passes", "replay_members")
 VIEW_K = (120.0, 120.0, 63.5, 47.5)
 VIEW_Z = (0.05, 2.0)
 
 
-def _contract(g):
-    c = g.counters()
-    return {k: c[k] for k in CONTRACT}
-
-
 def _grid(hfpf_mod, sc, **kw):
-    return hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **dict(SMALL, **kw))
+    return hfpf_mod.OccupancyGrid(resolution=sc.resolution, bbox=sc.bbox, **dict(SMALL_CAPS, **kw))
 
 
 def _scene(n=6, **kw):
@@ -37,7 +29,7 @@ def test_read_only_identity(hfpf_mod, synth_mod, color):
         scenes.run(src, sc, "integrate")  # ends with a clean
         blob = src.snapshot()
         info = hfpf_mod.snapshot_info(blob)
-        assert info["total_bytes"] == len(blob) and info["max_log_points"] == SMALL["max_log_points"]
+        assert info["total_bytes"] == len(blob) and info["max_log_points"] == SMALL_CAPS["max_log_points"]
         assert info["voxels_with_normal"] > 1000 and info["frames_integrated"] == 7 and info["next_frame_id"] == 7
         assert info["max_bricks"] <= 30000 and info["max_normals"] <= 1 << 19
         # the other update form, other pool sizes, no tiling hint
@@ -62,7 +54,7 @@ def test_read_only_identity(hfpf_mod, synth_mod, color):
             rows = dst.extract()
             assert len(rows) > 1000 and (not color or (rows["rgb"][rows["count"] > 0] != 0).any())
             assert (dst.render(sc.poses[0], VIEW_K, 128, 96, z_range=VIEW_Z, splat_radius=1)["count"] > 0).any()
-            assert _contract(src) == _contract(dst)
+            assert contract_counters(src) == contract_counters(dst)
 
 
 # ---- 2. continuation under random schedules -------------------------------------------------------------------------------
@@ -126,7 +118,7 @@ def test_continuation_random_schedule(oracle_mod, hfpf_mod, synth_mod, seed):
     fw = W if (seed // 2) % 2 else 0
 
     def make(flip=False):  # a handoff also alternates the update form of the new handle
-        return hfpf_mod.OccupancyGrid(resolution=res, bbox=sc.bbox, binned_update=bool(seed % 2) != flip, frame_width=fw, **cfg, **SMALL)
+        return hfpf_mod.OccupancyGrid(resolution=res, bbox=sc.bbox, binned_update=bool(seed % 2) != flip, frame_width=fw, **cfg, **SMALL_CAPS)
 
     og = oracle_mod.OracleGrid(resolution=res, bbox=sc.bbox, **cfg)
     plain, handed = make(), make()
@@ -163,7 +155,7 @@ def test_continuation_random_schedule(oracle_mod, hfpf_mod, synth_mod, seed):
                 assert handed.state_changed == dirty
         assert np.array_equal(og.occupied(), plain.occupied())
         assert plain.occupied().tobytes() == handed.occupied().tobytes()
-        assert _contract(plain) == _contract(handed)
+        assert contract_counters(plain) == contract_counters(handed)
     finally:
         plain.close()
         handed.close()
@@ -184,7 +176,7 @@ def test_waiting_host_frames_are_in_the_snapshot(hfpf_mod, synth_mod):
             g.clean()
         ra, rb = a.extract(), b.extract()
         assert len(ra) > 1000 and ra.tobytes() == rb.tobytes()
-        assert a.occupied().tobytes() == b.occupied().tobytes() and _contract(a) == _contract(b)
+        assert a.occupied().tobytes() == b.occupied().tobytes() and contract_counters(a) == contract_counters(b)
 
 
 # ---- 4. files ------------------------------------------------------------------------------------------------------------
@@ -204,7 +196,7 @@ def test_files(hfpf_mod, synth_mod, tmp_path):
                 g.clean()
             want = src.extract()
             assert len(want) >= len(rows) and want.tobytes() == by_file.extract().tobytes() == by_blob.extract().tobytes()
-            assert _contract(by_file) == _contract(by_blob) == _contract(src)
+            assert contract_counters(by_file) == contract_counters(by_blob) == contract_counters(src)
     # damaged and missing files are refused and leave the target as it was
     half, flipped = str(tmp_path / "half.hfpf"), str(tmp_path / "flipped.hfpf")
     open(half, "wb").write(blob[:len(blob) // 2])
@@ -248,7 +240,7 @@ def test_mismatch_is_refused_and_the_target_lives_on(hfpf_mod, synth_mod):
     for kw, code in cases:
         # the target's own session: 768 points for the handle with 2048 records, three frames otherwise
         own = scenes.Scene(2, 32, 24, 0.001, fx=615.0) if code == -3 else scenes.Scene(3, 128, 96, 0.001, fx=615.0)
-        with hfpf_mod.OccupancyGrid(**dict(base, **dict(SMALL, **kw))) as g:
+        with hfpf_mod.OccupancyGrid(**dict(base, **dict(SMALL_CAPS, **kw))) as g:
             g.integrate(own.frame(0), own.poses[0])
             g.clean()
             had, had_occ = g.extract().copy(), g.occupied()
@@ -288,7 +280,7 @@ def test_canonical_bytes(hfpf_mod, synth_mod, monkeypatch):
         i1, i2 = hfpf_mod.snapshot_info(one), hfpf_mod.snapshot_info(again)
         assert i1["payload_checksum"] == i2["payload_checksum"] and one[H:] == again[H:]
         assert {k for k in i1 if i1[k] != i2[k]} <= {"flags"}
-    with _grid(hfpf_mod, sc, max_bricks=4 * SMALL["max_bricks"], max_normals=4 * SMALL["max_normals"]) as big:
+    with _grid(hfpf_mod, sc, max_bricks=4 * SMALL_CAPS["max_bricks"], max_normals=4 * SMALL_CAPS["max_normals"]) as big:
         scenes.run(big, sc, "integrate")
         big.integrate(sc.frame(1), sc.poses[1])
         assert len(big.snapshot()) == len(one)
@@ -352,7 +344,7 @@ def test_node_session_handoff(hfpf_mod, synth_mod, tmp_path):
 
     def node(d):
         n = hfpf_node.FusionNode(bounding_box=list(sc.bbox), directory_name=str(d), tf_lookup=lambda t, s: sc.poses[int(s)],
-                                 resolution=sc.resolution, final_clean_on_process=True, **SMALL)
+                                 resolution=sc.resolution, final_clean_on_process=True, **SMALL_CAPS)
         n.start()
         return n
 

@@ -5,10 +5,10 @@ An id outside 0..7 is HFPF_ERR_BAD_ARG, which include/hfpf.h numbers -2."""
 import numpy as np
 import pytest
 
-from test_gpu_render import DepthScene, _grid, _run
+from gpu_support import IDENT, grid, run
+from scenes import DepthScene
 
 pytestmark = pytest.mark.gpu
-IDENT = np.eye(4)[:3]
 W, H = 160, 120
 QUAD = np.array([[-3, -3, 0], [3, -3, 0], [3, 3, 0], [-3, 3, 0]], np.float32)
 QUAD_TRIS = np.array([[0, 1, 2], [0, 2, 3]], np.uint32)
@@ -43,8 +43,8 @@ def _rays(rows, n=64):
 @pytest.fixture(scope="module")
 def session(hfpf_mod, synth_mod):
     sc = DepthScene(4, W, H, clean_every=4)
-    g = _grid(hfpf_mod)
-    _run(g, sc)
+    g = grid(hfpf_mod)
+    run(g, sc)
     rows = g.extract().copy()
     assert len(rows) > 0
     # two more frames of the same stream as packed clouds in HBM, for hfpf_integrate_device
@@ -143,8 +143,8 @@ def test_early_exits_count_only_the_calls_that_reached_the_bracket(hfpf_mod, syn
     """hfpf_extract_components that keeps nothing leaves through its nk == 0 exit, behind the bracket's start: it counts.  On a cleared
     handle the call returns with no rows, in front of the bracket: it does not."""
     sc = DepthScene(4, W, H, clean_every=4)
-    with _grid(hfpf_mod) as g:
-        _run(g, sc)
+    with grid(hfpf_mod) as g:
+        run(g, sc)
         assert len(g.extract()) > 0
         g.kernel_timing(1)
         for form in (False, True):

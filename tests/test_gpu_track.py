@@ -2,77 +2,23 @@
 defined on the rows hfpf_extract returns, so its results are compared byte for byte with tests/track_ref.py run on the extracted
 rows."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
 
 import depth_ref
 import track_ref as TR
-from test_gpu_render import DepthScene, _run
+from gpu_support import (TRACK_OPTS, Z_CLIP, Z_RANGE, grid, held_out, perturb, pose_errors, run, same_planes, same_track, track_reference,
+                         two_handles, unchanged, uploaded)
+from scenes import DepthScene
 
 pytestmark = pytest.mark.gpu
-CAPS = dict(max_bricks=120000, max_log_points=8 << 20, max_normals=1 << 21, max_frames=4096)
-BBOX = (-0.5, 0.5, -0.5, 0.5, 0.0, 1.0)
-RES = 0.002
-Z_CLIP = (0.28, 0.6)  # the handle's default z-clip (node.cpp:92-93)
-Z_RANGE = (0.05, 3.0)
-HELD_OUT = 40          # frame index of the synthetic stream that is tracked and never integrated
-SEED, POSE_SEED = 0xD3F7, 0x5E3
-OPTS = dict(max_iterations=30, max_distance=0.03, damping=1e-6, eps_rotation=1e-6, eps_translation=1e-6, z_range=Z_RANGE,
-            splat_radius=-1, max_splat_radius=4, cull_backfaces=True)
-
-
-def _grid(hfpf_mod):
-    return hfpf_mod.OccupancyGrid(resolution=RES, bbox=BBOX, fuse_color=True, **CAPS)
-
-
-def _rot(axis, deg):
-    a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
-    th = math.radians(deg)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    return np.eye(3) + math.sin(th) * K + (1 - math.cos(th)) * (K @ K)
-
-
-def _perturb(pose, deg, shift, axis=(1.0, -0.5, 0.3)):
-    return np.hstack([_rot(axis, deg) @ pose[:, :3], (pose[:, 3] + np.asarray(shift, np.float64)).reshape(3, 1)])
-
-
-def _errors(pose, ref):
-    dR = pose[:, :3] @ ref[:, :3].T
-    return float(np.linalg.norm(pose[:, 3] - ref[:, 3])), math.degrees(math.acos(max(-1.0, min(1.0, (np.trace(dR) - 1) / 2))))
-
-
-def _held_out(synth_mod, W=640, H=480, f=HELD_OUT):
-    pose = synth_mod.pose(POSE_SEED, f)
-    depth, _, K = synth_mod.depth_frame(SEED, f, W, H, pose)
-    return depth, K, pose
 
 
 def _as_f32(depth):
     d = depth.astype(np.float32) * np.float32(0.001)
     d[depth == 0] = np.nan
     return d
-
-
-def _view(K, W, H):
-    return dict(K=K, width=W, height=H, z_range=Z_RANGE, splat_radius=-1, max_splat_radius=4, flags=1)
-
-
-def _ref(rows, points, pose, K, W, H, **kw):
-    o = dict(OPTS, **kw)
-    return TR.track(rows, points, pose, RES, _view(K, W, H), Z_CLIP, max_iterations=o["max_iterations"], min_inliers=6,
-                    max_distance=o["max_distance"], damping=o["damping"], eps_rotation=o["eps_rotation"],
-                    eps_translation=o["eps_translation"])
-
-
-def _same_result(got, ref, what):
-    pose, r = got
-    assert pose.tobytes() == np.asarray(ref["pose"], np.float64).tobytes(), "%s: pose %r vs %r" % (what, pose, ref["pose"])
-    for k in ("iterations", "flags", "inliers", "points_used"):
-        assert r[k] == ref[k], "%s: %s %r vs %r" % (what, k, r[k], ref[k])
-    assert np.float64(r["rms"]).tobytes() == np.float64(ref["rms"]).tobytes(), "%s: rms %r vs %r" % (what, r["rms"], ref["rms"])
-    assert r["information"].tobytes() == np.asarray(ref["information"], np.float64).tobytes(), "%s: information" % what
 
 
 def _wide(cloud):
@@ -95,8 +41,8 @@ def _bytes(res):
 @pytest.fixture(scope="module")
 def session(hfpf_mod, synth_mod):
     sc = DepthScene(12, 640, 480, clean_every=4)
-    g = _grid(hfpf_mod)
-    _run(g, sc)
+    g = grid(hfpf_mod)
+    run(g, sc)
     rows = g.extract().copy()
     yield sc, g, rows
     g.close()
@@ -108,22 +54,22 @@ def session(hfpf_mod, synth_mod):
 @pytest.mark.parametrize("stride,fmt", [(1, "u16"), (2, "f32"), (2, "u16"), (1, "f32"), (2, "packed"), (2, "wide")])
 def test_bit_exact_against_track_ref(hfpf_mod, synth_mod, session, stride, fmt):
     sc, g, rows = session
-    depth, K, true = _held_out(synth_mod)
-    guess = _perturb(true, 2.0, (0.006, -0.005, 0.006))  # 1 cm, 2 degrees
+    depth, K, true = held_out(synth_mod)
+    guess = perturb(true, 2.0, (0.006, -0.005, 0.006))  # 1 cm, 2 degrees
     if fmt in ("u16", "f32"):
         img = depth if fmt == "u16" else _as_f32(depth)
-        got = g.track_depth(img, guess, K, stride=stride, **OPTS)
-        ref = _ref(rows, TR.depth_points(img, K, stride), guess, K, 640, 480)
+        got = g.track_depth(img, guess, K, stride=stride, **TRACK_OPTS)
+        ref = track_reference(rows, TR.depth_points(img, K, stride), guess, K, 640, 480)
     else:
         cloud = depth_ref.packed_cloud(depth, K)
         xyz = cloud.view(np.float32).reshape(-1, 4)[:, :3]
         got = g.track(cloud if fmt == "packed" else _wide(cloud), PACKED if fmt == "packed" else WIDE, guess, K, 640, 480,
-                      stride=stride, **OPTS)
-        ref = _ref(rows, TR.cloud_points(xyz, stride), guess, K, 640, 480)
+                      stride=stride, **TRACK_OPTS)
+        ref = track_reference(rows, TR.cloud_points(xyz, stride), guess, K, 640, 480)
     print("stride %d %s: %d iterations, flags %d, %d of %d used points inliers, rms %.2e, error %s -> %s" % (
         stride, fmt, got[1]["iterations"], got[1]["flags"], got[1]["inliers"], got[1]["points_used"], got[1]["rms"],
-        _errors(guess, true), _errors(got[0], true)))
-    _same_result(got, ref, "stride %d, %s depth" % (stride, fmt))
+        pose_errors(guess, true), pose_errors(got[0], true)))
+    same_track(got, ref, "stride %d, %s depth" % (stride, fmt))
     assert got[1]["iterations"] > 1 and got[1]["inliers"] > 1000
 
 
@@ -131,8 +77,8 @@ def test_bit_exact_against_track_ref(hfpf_mod, synth_mod, session, stride, fmt):
 
 @pytest.fixture(scope="module")
 def held_out_cloud(synth_mod):
-    depth, K, true = _held_out(synth_mod)
-    return depth_ref.packed_cloud(depth, K), K, _perturb(true, 2.0, (0.006, -0.005, 0.006))
+    depth, K, true = held_out(synth_mod)
+    return depth_ref.packed_cloud(depth, K), K, perturb(true, 2.0, (0.006, -0.005, 0.006))
 
 
 @pytest.fixture(scope="module")
@@ -142,7 +88,7 @@ def doubled(session, held_out_cloud):
     both = np.concatenate([cloud.reshape(-1), cloud.reshape(-1)])
     xyz = both.view(np.float32).reshape(-1, 4)[:, :3]
     assert len(xyz) == 2 * 640 * 480 > 2048 * 256
-    return both, _ref(session[2], TR.cloud_points(xyz, 1), guess, K, 640, 480, max_iterations=2)
+    return both, track_reference(session[2], TR.cloud_points(xyz, 1), guess, K, 640, 480, max_iterations=2)
 
 
 @pytest.mark.parametrize("fmt", ["packed", "wide"])
@@ -152,10 +98,10 @@ def test_more_samples_than_grid_threads(hfpf_mod, session, held_out_cloud, doubl
     _, K, guess = held_out_cloud
     both, ref = doubled
     got = g.track(both if fmt == "packed" else _wide(both), PACKED if fmt == "packed" else WIDE, guess, K, 640, 480, stride=1,
-                  **dict(OPTS, max_iterations=2))
+                  **dict(TRACK_OPTS, max_iterations=2))
     print("%s: %d iterations, flags %d, %d of %d used points inliers" % (fmt, got[1]["iterations"], got[1]["flags"], got[1]["inliers"],
                                                                        got[1]["points_used"]))
-    _same_result(got, ref, "614,400 records, %s" % fmt)
+    same_track(got, ref, "614,400 records, %s" % fmt)
     assert got[1]["points_used"] == ref["points_used"] > 2048 * 256 // 2
 
 
@@ -167,11 +113,11 @@ def test_fewer_samples_than_one_wave(hfpf_mod, session, held_out_cloud):
     rec = cloud.view(np.float32).reshape(-1, 4)
     few = np.ascontiguousarray(rec[TR.used(rec[:, :3], Z_CLIP)][:40])
     assert len(few) == 40
-    got = g.track(few.view(np.uint8).reshape(-1), PACKED, guess, K, 640, 480, stride=1, **OPTS)
-    ref = _ref(rows, TR.cloud_points(few[:, :3], 1), guess, K, 640, 480)
+    got = g.track(few.view(np.uint8).reshape(-1), PACKED, guess, K, 640, 480, stride=1, **TRACK_OPTS)
+    ref = track_reference(rows, TR.cloud_points(few[:, :3], 1), guess, K, 640, 480)
     print("40 records: %d iterations, flags %d, %d of %d used points inliers" % (got[1]["iterations"], got[1]["flags"], got[1]["inliers"],
                                                                               got[1]["points_used"]))
-    _same_result(got, ref, "40 records")
+    same_track(got, ref, "40 records")
     assert got[1]["points_used"] == 40 and (got[1]["inliers"] >= 6 or got[1]["flags"] == TR.TOO_FEW)
 
 
@@ -186,11 +132,11 @@ MAX_T_ERR, MAX_R_ERR = 1e-3, 0.1
                                        (1.5, (-0.01, 0.0, 0.012))])
 def test_accuracy_at_640x480(hfpf_mod, synth_mod, session, deg, shift):
     sc, g, rows = session
-    depth, K, true = _held_out(synth_mod)
-    guess = _perturb(true, deg, shift)
-    e0 = _errors(guess, true)
-    pose, r = g.track_depth(depth, guess, K, **OPTS)
-    e1 = _errors(pose, true)
+    depth, K, true = held_out(synth_mod)
+    guess = perturb(true, deg, shift)
+    e0 = pose_errors(guess, true)
+    pose, r = g.track_depth(depth, guess, K, **TRACK_OPTS)
+    e1 = pose_errors(pose, true)
     print("start %.4f m / %.3f deg -> %.6f m / %.4f deg: %d iterations, flags %d, %d inliers, rms %.2e" % (
         *e0, *e1, r["iterations"], r["flags"], r["inliers"], r["rms"]))
     assert e1[0] * 10 <= e0[0] and e1[1] * 10 <= e0[1]
@@ -199,9 +145,9 @@ def test_accuracy_at_640x480(hfpf_mod, synth_mod, session, deg, shift):
 
 def test_starting_at_the_true_pose_stays_there(hfpf_mod, synth_mod, session):
     sc, g, rows = session
-    depth, K, true = _held_out(synth_mod)
-    pose, r = g.track_depth(depth, true, K, **OPTS)
-    e = _errors(pose, true)
+    depth, K, true = held_out(synth_mod)
+    pose, r = g.track_depth(depth, true, K, **TRACK_OPTS)
+    e = pose_errors(pose, true)
     print("from the true pose: %.6f m / %.4f deg in %d iterations, flags %d" % (*e, r["iterations"], r["flags"]))
     assert r["flags"] == TR.CONVERGED and r["iterations"] <= 3
     assert e[0] < 2e-4
@@ -211,19 +157,15 @@ def test_starting_at_the_true_pose_stays_there(hfpf_mod, synth_mod, session):
 
 def test_cloud_host_and_device_depth_agree(hfpf_mod, synth_mod, session):
     sc, g, rows = session
-    depth, K, true = _held_out(synth_mod)
-    guess = _perturb(true, 1.0, (0.004, 0.004, -0.004))
-    a = g.track_depth(depth, guess, K, **OPTS)
+    depth, K, true = held_out(synth_mod)
+    guess = perturb(true, 1.0, (0.004, 0.004, -0.004))
+    a = g.track_depth(depth, guess, K, **TRACK_OPTS)
     cloud = depth_ref.packed_cloud(depth, K)
-    b = g.track(cloud, PACKED, guess, K, 640, 480, **OPTS)
-    c = g.track(_wide(cloud), WIDE, guess, K, 640, 480, **OPTS)
+    b = g.track(cloud, PACKED, guess, K, 640, 480, **TRACK_OPTS)
+    c = g.track(_wide(cloud), WIDE, guess, K, 640, 480, **TRACK_OPTS)
     desc = hfpf_mod.depth_desc(640, 480, hfpf_mod.DEPTH_U16, 640 * 2, K)
-    ptr = g.device_alloc(depth.nbytes)
-    try:
-        g.device_upload(ptr, np.ascontiguousarray(depth))
-        d = g.track_depth_device(desc, ptr, guess, **OPTS)
-    finally:
-        g.device_free(ptr)
+    with uploaded(g, depth) as (ptr,):
+        d = g.track_depth_device(desc, ptr, guess, **TRACK_OPTS)
     assert a[1]["inliers"] > 1000
     for what, other in (("packed cloud", b), ("32-byte cloud", c), ("device depth", d)):
         assert _bytes(other) == _bytes(a), what
@@ -231,46 +173,28 @@ def test_cloud_host_and_device_depth_agree(hfpf_mod, synth_mod, session):
 
 # ---- 4. no side effects ---------------------------------------------------------------------------------------------
 
-def _counters(g):
-    c = g.counters()
-    c.pop("device_bytes")  # counts the scratch a track keeps (include/hfpf.h)
-    # how the binned update scheduled its work: depends on how host frames were batched (a track, like a render, launches
-    # waiting frames first); test_gpu_render.py excludes the same three
-    for k in ("points_direct", "table_misses", "update_extra_rounds"):
-        c.pop(k)
-    return c
-
-
 def test_tracks_change_nothing(hfpf_mod, synth_mod):
     sc = DepthScene(10, 320, 240, clean_every=3)
-    depth, K, true = _held_out(synth_mod, 320, 240)
+    depth, K, true = held_out(synth_mod, 320, 240)
 
     def look(g, i):
-        g.track_depth(depth, _perturb(true, 1.0, (0.005, 0.0, 0.0)), K, **dict(OPTS, max_iterations=3))
+        g.track_depth(depth, perturb(true, 1.0, (0.005, 0.0, 0.0)), K, **dict(TRACK_OPTS, max_iterations=3))
 
-    with _grid(hfpf_mod) as a, _grid(hfpf_mod) as b:
-        _run(a, sc)
-        look(b, -1)  # on the empty handle
-        _run(b, sc, between=look)
-        ra, rb = a.extract(), b.extract()
-        assert len(ra) > 0 and ra.tobytes() == rb.tobytes()
-        assert _counters(a) == _counters(b)
+    with two_handles(hfpf_mod, sc, look, lambda b: look(b, -1)) as (a, b, rb):
         ia = a.render(sc.poses[2], K, sc.W, sc.H, z_range=Z_RANGE, splat_radius=-1)
-        ib = b.render(sc.poses[2], K, sc.W, sc.H, z_range=Z_RANGE, splat_radius=-1)
-        for p in ia:
-            assert ia[p].tobytes() == ib[p].tobytes(), p
-        assert b.extract().tobytes() == ra.tobytes() and _counters(a) == _counters(b)
+        same_planes(ia, b.render(sc.poses[2], K, sc.W, sc.H, z_range=Z_RANGE, splat_radius=-1), "a render of both handles")
+        unchanged(a, b, rb)
 
 
 # ---- 5. edges -------------------------------------------------------------------------------------------------------
 
 def test_empty_and_uncleaned_handles_return_the_guess(hfpf_mod, synth_mod):
     sc = DepthScene(3, 160, 120, clean_every=0)
-    depth, K, true = _held_out(synth_mod, 160, 120)
-    guess = _perturb(true, 1.0, (0.01, 0.0, 0.0))
-    with _grid(hfpf_mod) as g:
+    depth, K, true = held_out(synth_mod, 160, 120)
+    guess = perturb(true, 1.0, (0.01, 0.0, 0.0))
+    with grid(hfpf_mod) as g:
         for label in ("empty", "integrated, never cleaned"):
-            pose, r = g.track_depth(depth, guess, K, **OPTS)
+            pose, r = g.track_depth(depth, guess, K, **TRACK_OPTS)
             assert r["flags"] == TR.TOO_FEW and r["inliers"] == 0 and r["iterations"] == 1, label
             assert pose.tobytes() == guess.tobytes(), label
             assert r["points_used"] > 1000, label
@@ -278,7 +202,7 @@ def test_empty_and_uncleaned_handles_return_the_guess(hfpf_mod, synth_mod):
                 sc.integrate(g, f)
         assert len(g.extract()) == 0
         g.clean()
-        pose, r = g.track_depth(depth, guess, K, **OPTS)
+        pose, r = g.track_depth(depth, guess, K, **TRACK_OPTS)
         assert r["flags"] != TR.TOO_FEW and r["inliers"] > 1000
 
 
@@ -286,9 +210,9 @@ def test_bad_arguments_are_refused_and_the_handle_stays_usable(hfpf_mod, synth_m
     H_ = hfpf_mod
     sc, g, rows = session
     L = H_.lib()
-    depth, K, true = _held_out(synth_mod, 160, 120)
+    depth, K, true = held_out(synth_mod, 160, 120)
     pose = np.ascontiguousarray(true, np.float64).reshape(12)
-    want = g.track_depth(depth, true, K, **OPTS)
+    want = g.track_depth(depth, true, K, **TRACK_OPTS)
     desc0 = H_.depth_desc(160, 120, H_.DEPTH_U16, 320, K)
     bad_opts = {"struct_size": ("struct_size", C.sizeof(H_.TrackOpts) - 8), "reserved": ("reserved", 1),
                 "iterations 0": ("max_iterations", 0), "iterations 65": ("max_iterations", 65), "stride 0": ("stride", 0),
@@ -300,7 +224,7 @@ def test_bad_arguments_are_refused_and_the_handle_stays_usable(hfpf_mod, synth_m
                 "view fx 0": ("fx", 0.0), "view z_near >= z_far": ("z_near", 5.0), "view radius 16": ("splat_radius", 16)}
 
     def opts():
-        return H_.track_opts(K, 160, 120, **OPTS)
+        return H_.track_opts(K, 160, 120, **TRACK_OPTS)
 
     def call(o=None, desc=None, img=depth, p=pose, res=None):
         r = res if res is not None else H_.track_result()
@@ -344,5 +268,5 @@ def test_bad_arguments_are_refused_and_the_handle_stays_usable(hfpf_mod, synth_m
                             C.byref(H_.track_result())) == -2, what
     assert L.hfpf_track(g._h, C.byref(opts()), None, 100, 16, 0, 4, 8, pose.ctypes.data, C.byref(H_.track_result())) == -2, "NULL cloud"
     # the handle is still usable, and two identical calls give identical bytes
-    again = g.track_depth(depth, true, K, **OPTS)
-    assert _bytes(again) == _bytes(want) and _bytes(g.track_depth(depth, true, K, **OPTS)) == _bytes(want)
+    again = g.track_depth(depth, true, K, **TRACK_OPTS)
+    assert _bytes(again) == _bytes(want) and _bytes(g.track_depth(depth, true, K, **TRACK_OPTS)) == _bytes(want)

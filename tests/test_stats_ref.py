@@ -146,41 +146,9 @@ def test_exact_moments_off_by_default_and_refused_when_off(oracle_mod, synth_mod
 
 # ---- the scales ----
 
-def _floor_log2(b):
-    m, e = math.frexp(b)  # b = m * 2^e, 0.5 <= m < 1: exact, no logarithm
-    return e - 1
-
-
-def _straddles():
-    """(K, resolution, ball_radius below, ball_radius above, which bound) with Bm (or Bm^2) on either side of a power of two, found
-    by stepping ball_radius through neighbouring doubles around (K + 2) res / (2 target)."""
-    found = []
-    for K in (1, 3, 5):
-        for res in (0.001, 0.005):
-            res32 = float(np.float32(res))
-            for which, target in ((0, 0.25), (0, 1.0), (0, 4.0), (1, math.sqrt(0.5)), (1, math.sqrt(2.0)), (1, math.sqrt(8.0))):
-                ball = (K + 2.0) * res32 / (2.0 * target)
-                want = _floor_log2(target * target * 1.0000001) if which else _floor_log2(target)
-                lo = hi = ball
-                for _ in range(64):  # walk to a pair of neighbouring doubles with the bound's exponent on either side
-                    if _floor_log2(R.bounds(K, res, lo, 0.001)[which]) >= want:
-                        lo = math.nextafter(lo, math.inf)  # larger radius, smaller bound
-                    if _floor_log2(R.bounds(K, res, hi, 0.001)[which]) < want:
-                        hi = math.nextafter(hi, 0.0)
-                e_lo, e_hi = (_floor_log2(R.bounds(K, res, b, 0.001)[which]) for b in (lo, hi))
-                if e_lo == want - 1 and e_hi == want and abs(lo - hi) <= 4 * math.ulp(ball):
-                    found.append((K, res, lo, hi, which))
-    return found
-
-
-STRADDLES = _straddles()
-# the combination the scene tests (here and on the GPU) run: K = 3 at 1 mm, Bm across 2^-2, i.e. ball_radius across 10 mm
-STRADDLE_SCENE = next(s for s in STRADDLES if s[0] == 3 and s[1] == 0.001 and s[4] == 0 and 0.009 < s[2] < 0.011)
-
-
 def test_scales_on_either_side_of_a_power_of_two(oracle_mod):
-    assert len(STRADDLES) >= 24
-    for K, res, b_below, b_above, which in STRADDLES:
+    assert len(R.STRADDLES) >= 24
+    for K, res, b_below, b_above, which in R.STRADDLES:
         for ball, side in ((b_below, -1), (b_above, 0)):
             bnd = R.bounds(K, res, ball, 0.001)
             sc4 = R.scales(K, res, ball, 0.001)
@@ -190,7 +158,7 @@ def test_scales_on_either_side_of_a_power_of_two(oracle_mod):
             for b, f in zip(bnd, sc4):
                 m, e = math.frexp(float(f))
                 assert m == 0.5, "scale %r is not a power of two" % f
-                assert float(f) == math.ldexp(1.0, 26 - _floor_log2(b)), (K, res, ball, b, f)
+                assert float(f) == math.ldexp(1.0, 26 - R.floor_log2(b)), (K, res, ball, b, f)
                 assert 2.0 ** 26 <= b * float(f) < 2.0 ** 27
             # the largest values the bounds admit, as f32: every contribution stays below 2^27 in magnitude
             u = np.float32(bnd[0])
@@ -206,7 +174,7 @@ def test_scales_on_either_side_of_a_power_of_two(oracle_mod):
 def test_rows_at_a_straddling_scale_pair(oracle_mod, synth_mod):
     """The same scene on either side of the power of two: fs differs by a factor two, the words of u follow, and each side's
     rows are the numpy restatement's byte for byte."""
-    K, res, b_below, b_above, which = STRADDLE_SCENE
+    K, res, b_below, b_above, which = R.STRADDLE_SCENE
     sc = scenes.Scene(3, 160, 120, res, fx=615.0, clean_every=2)
     out = []
     for ball in (b_below, b_above):
