@@ -117,7 +117,14 @@ typedef struct hfpf_counters {
 void hfpf_default_config(hfpf_config* cfg);
 int hfpf_abi_version(void);
 
-/* OccupancyGrid(), setResolution, setDimensions, setK, construct  (grid.hpp:111,614,604,138,621). */
+/* OccupancyGrid(), setResolution, setDimensions, setK, construct  (grid.hpp:111,614,604,138,621).
+ * SIZE LIMITS (HFPF_ERR_BAD_CONFIG, before anything is allocated): with dim[a] = (int)((max[a] - min[a]) / (double)resolution),
+ *   (max[a] - min[a]) / (double)resolution < 2097151 on every axis: at most 2,097,150 cells, so that a cell index 0..dim fits a
+ *     21-bit key field (an all-ones field is kept as the sentinel);
+ *   the brick directory, one 32-bit word per 8 x 8 x 8 cells of the dim + 1 storage cells an axis, has at most 4.0e9 entries
+ *     ((dim[0] + 8) / 8 * ((dim[1] + 8) / 8) * ((dim[2] + 8) / 8), integer divisions): its linear index is 32-bit.
+ * Both limits are reached by tests/test_gpu_deep.py: the hot path and every read-out run at 2,097,150 cells an axis and at
+ * 1579^3 = 3.94e9 directory entries (16 GB of device memory for the directory alone). */
 int hfpf_create(const hfpf_config* cfg, hfpf_handle** out);
 /* The reference never destroys its grid (no destructor; leaks). */
 int hfpf_destroy(hfpf_handle* h);
@@ -867,7 +874,11 @@ int hfpf_read_ply(const char* path, hfpf_mesh_vertex** verts, uint64_t* n_verts,
  * struct_size; more than 2^26 sampled rows.  The pair list not fitting returns HFPF_ERR_CAPACITY as in compare (the handle stays
  * usable); a handle with an RCCL communicator, or a failed handle, returns HFPF_ERR_STATE.
  * LIMITATION: a row finds the mesh only within opts.compare.max_distance, at most 32 voxels: that is the capture range.  An align
- * refines a coarse placement; it is not a global registration. */
+ * refines a coarse placement; it is not a global registration.
+ * LIMITATION: the headroom rule is taken about the centre of the handle's bounding box, so a model all of which lies 32 m or more
+ * (on one axis) from that centre has no inlier: HFPF_ALIGN_TOO_FEW after one system, pose = T_0.  A box with 2,097,150 cells of 2 mm
+ * on an axis and the model at one end of it is such a case (tests/test_gpu_deep.py asserts this answer); a box up to 64 m across
+ * around the model is not. */
 #define HFPF_ALIGN_CONVERGED 1u  /* the last update was below both eps */
 #define HFPF_ALIGN_DEGENERATE 2u /* a pivot of the damped system was <= 0; pose = the last good estimate */
 #define HFPF_ALIGN_TOO_FEW 4u    /* fewer than min_inliers inliers; pose = the last good estimate */

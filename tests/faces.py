@@ -6,7 +6,9 @@ occupied cells lie at index == dim (the storage has dim + 1 cells an axis; such 
 is clipped somewhere, and a triangle or a ray near the model leaves the grid.  Four of the scenes fuse the same surface where a map
 frame puts it, 137 m to 1024 m from the origin: an f32 step is 1/131 to 1/16 of a voxel there, so input points, centroids and lattice
 points land exactly on cell boundaries and box faces and candidate rows tie for the nearest (boundary_counts, on_lattice_plane,
-query_ref.nearest_ties count what each scene contains)."""
+query_ref.nearest_ties count what each scene contains).  Four more (DEEP) keep the surface and CUT_BBOX's max corner and push the min
+corner away until the cell and brick indices are the largest a handle takes; the model then fills a 10^-5 part of the box, so the
+input generators below take the box they aim at from the caller, who passes FaceScene.model_box."""
 import numpy as np
 
 import scenes
@@ -22,6 +24,24 @@ SHIFT_137 = (137.0, -52.0, 23.0)
 SHIFT_128 = (128.0, -64.0, 32.0)
 SHIFT_1024 = (1024.0, -512.0, 256.0)
 SHIFTED_COV = dict(pcl_shifted_cov=True)
+# The largest indices: CUT_BBOX's max corner with the min corner pushed away until an axis has DEEP_CELLS cells (the most hfpf_create
+# takes: index == dim = 0x1FFFFE then uses all 21 bits of a key field) or every axis DEEP3_CELLS (1579^3 = 3.94e9 directory entries, just
+# under the 4.0e9 hfpf_create takes and well over 2^31).  The surface stays at 0.5 m, so coordinates keep full f32 precision: the
+# opposite corner of the parameter space from the far* scenes.
+DEEP_CELLS = 2097150
+DEEP3_CELLS = 12630
+
+
+def deep_bbox(cells, res=0.002):
+    """CUT_BBOX with the min of every axis that has cells[a] > 0 moved to max - (cells[a] + 0.25) * (double)(float)res."""
+    r = float(np.float32(res))
+    b = list(CUT_BBOX)
+    for a, n in enumerate(cells):
+        if n:
+            b[2 * a] = b[2 * a + 1] - (n + 0.25) * r
+    return tuple(b)
+
+
 # name -> (bbox, resolution, shift of the fusion frame, dims, config of engine and oracle)
 DEFS = {"cut": (CUT_BBOX, 0.002, (0.0, 0.0, 0.0), (104, 72, 88), {}),
         "cut3": (CUT_BBOX, 0.003, (0.0, 0.0, 0.0), (69, 48, 59), {}),
@@ -32,13 +52,19 @@ DEFS = {"cut": (CUT_BBOX, 0.002, (0.0, 0.0, 0.0), (104, 72, 88), {}),
         "far137": (CUT_BBOX, 0.002, SHIFT_137, (104, 72, 88), {}),
         "far137s": (CUT_BBOX, 0.002, SHIFT_137, (104, 72, 88), SHIFTED_COV),
         "dy128s": (DYADIC_BBOX, DYADIC_RES, SHIFT_128, (107, 75, 90), SHIFTED_COV),
-        "dy1024s": (DYADIC_BBOX, DYADIC_RES, SHIFT_1024, (107, 75, 90), SHIFTED_COV)}
+        "dy1024s": (DYADIC_BBOX, DYADIC_RES, SHIFT_1024, (107, 75, 90), SHIFTED_COV),
+        "deepx": (deep_bbox((DEEP_CELLS, 0, 0)), 0.002, (0.0, 0.0, 0.0), (DEEP_CELLS, 72, 88), {}),
+        "deepy": (deep_bbox((0, DEEP_CELLS, 0)), 0.002, (0.0, 0.0, 0.0), (104, DEEP_CELLS, 88), {}),
+        "deepz": (deep_bbox((0, 0, DEEP_CELLS)), 0.002, (0.0, 0.0, 0.0), (104, 72, DEEP_CELLS), {}),
+        "deep3": (deep_bbox((DEEP3_CELLS,) * 3), 0.002, (0.0, 0.0, 0.0), (DEEP3_CELLS,) * 3, {})}
 ALL = tuple(DEFS)
 NAMES = ("cut", "cut3", "thin", "far", "far137s", "dy128s")   # every read-out
 HOT_NAMES = ("far137", "dy1024s")                              # hot path, query and mesh only
 SIX = ("cut", "cut3", "far", "far137", "far137s")   # the scenes every face of which cuts a surface, with cells at index == dim
 DYADIC = ("dy128s", "dy1024s")                      # every face cuts a surface; a box of whole cells has no cell at index == dim
 SHIFTED = ("far", "far137", "far137s", "dy128s", "dy1024s")
+DEEP = ("deepx", "deepy", "deepz", "deep3")          # the model in the max corner of a grid with the largest indices
+DEEP_AXES = {"deepx": (0,), "deepy": (1,), "deepz": (2,), "deep3": (0, 1, 2)}
 # what the CPU oracle alone gives (asserted exactly in test_faces_ref.py only): rows, live rows, live rows in the layers
 # x=0, x=dim-1, y=0, y=dim-1, z=0, z=dim-1, occupied cells at index == dim per axis
 ORACLE_TABLE = {"cut": (10087, 9872, (140, 45, 132, 114, 291, 260), (42, 216, 1358)),
@@ -48,7 +74,13 @@ ORACLE_TABLE = {"cut": (10087, 9872, (140, 45, 132, 114, 291, 260), (42, 216, 13
                 "far137": (10085, 10011, (140, 45, 128, 111, 275, 252), (42, 216, 1357)),
                 "far137s": (10085, 9863, (140, 45, 132, 114, 291, 258), (42, 216, 1357)),
                 "dy128s": (13871, 13583, (145, 43, 194, 170, 300, 681), (0, 0, 0)),
-                "dy1024s": (13462, 13175, (145, 47, 186, 152, 297, 682), (0, 0, 0))}
+                "dy1024s": (13462, 13175, (145, 47, 186, 152, 297, 682), (0, 0, 0)),
+                # rows at ix 2096923..2097149 / iy 2096998..2097149 / iz 2097045..2097149 / 12403..12629, 12472.., 12525..; largest
+                # linear brick index of a row 3.1e7, 4.1e7, 3.4e7 and 3,936,827,528 (every row of deep3 lies above 2^31)
+                "deepx": (19967, 19464, (0, 45, 240, 215, 291, 260), (42, 335, 1358)),
+                "deepy": (14618, 14263, (196, 53, 0, 116, 351, 1291), (49, 158, 3582)),
+                "deepz": (18171, 17912, (109, 150, 169, 153, 0, 820), (107, 209, 975)),
+                "deep3": (45342, 44294, (0, 162, 0, 206, 0, 2972), (117, 211, 2409))}
 # boundary_counts() of the dyadic scenes (asserted exactly in test_faces_ref.py only): in-box input points, those of them on an exact
 # cell boundary, used points exactly on the plane of a box face
 BOUNDARY_TABLE = {"dy128s": (58260, 729, 96), "dy1024s": (58121, 5838, 866)}
@@ -72,6 +104,9 @@ class FaceScene(scenes.Scene):
         moved = tuple(float(b) + float(shift[i // 2]) for i, b in enumerate(bbox))
         super().__init__(8, 320, 240, res, bbox=moved, clean_every=4)
         self.name, self.dims, self.shift, self.config = name, dims, np.asarray(shift, np.float64), dict(config)
+        # where the model is, for the input generators below to aim at: a deep scene's model fills a 10^-5 part of its box.  What the
+        # box means (IN_BBOX, the faces, the lattice) is always taken from bbox
+        self.model_box = CUT_BBOX if name in DEEP else moved
         self.render_poses = self.poses
         self.poses = [np.hstack([p[:, :3], p[:, 3:] + self.shift.reshape(3, 1)]) for p in self.render_poses]
 
@@ -110,9 +145,50 @@ def check_conditions(name, rows, occ, dims):
         n_in, on_cell, on_face = boundary_counts(FaceScene(name))
         print("%s: %d input points in the box, %d on an exact cell boundary, %d exactly on a face's plane" % (name, n_in, on_cell, on_face))
         assert on_cell >= BOUNDARY_FLOOR[name][0] and on_face >= BOUNDARY_FLOOR[name][1], "%s: %r" % (name, (n_in, on_cell, on_face))
+    elif name in DEEP:
+        # without these a later change of a constant turns the deep tests vacuous: the widths are hfpf_create's own (key_widths)
+        widths = key_widths(dims)
+        lin = brick_lin(rows, dims)
+        print("%s: key widths %r, Morton width %d, largest linear brick index of a row %d (%d rows above 2^31)" % (
+            name, widths, 3 * max(widths), lin.max(), (lin > 2 ** 31).sum()))
+        for a in DEEP_AXES[name]:
+            k = ("ix", "iy", "iz")[a]
+            assert layers[2 * a + 1] >= 20, "%s: the max layer of axis %d holds fewer than 20 live rows: %r" % (name, a, layers)
+            assert int(rows[k].max()) == dims[a] - 1, "%s: no row at index dim - 1 of axis %d" % (name, a)
+            assert at_dim[a] >= 1, "%s: axis %d without an occupied cell at index == dim: %r" % (name, a, at_dim)
+            assert layers[2 * a] == 0 and int(rows[k].min()) > 0, "%s: the min layer of axis %d is not empty" % (name, a)
+        if name == "deep3":
+            assert prod_bdims(dims) > 2 ** 31 and lin.max() > 2 ** 31 and (lin > 2 ** 31).sum() >= 1000, "%s: brick indices below 2^31" % name
+        else:
+            assert widths[DEEP_AXES[name][0]] == KEY_FIELD_BITS, "%s: the deep axis' key field has %r bits" % (name, widths)
+            assert 3 * max(widths) == 63, "%s: Morton width %d" % (name, 3 * max(widths))
     else:
         assert dims[2] < 8 and layers[2] > 0 and layers[3] > 0 and layers[5] > 0, "%s: %r %r" % (name, dims, layers)
     return layers, at_dim
+
+
+KEY_FIELD_BITS = 21   # bits of a key field at the largest grid (tables.hpp, query_ref.KEY_BITS)
+
+
+def key_widths(dims):
+    """Per axis, the bits that hold 0..dim (the storage has dim + 1 cells an axis): hfpf_create's bits_for, restated.  A handle's
+    cell key is x << (wy + wz) | y << wz | z, and the candidates of a clean pass are sorted over 3 * max(widths) bits of Morton code."""
+    return tuple(max(1, int(d).bit_length()) for d in dims)
+
+
+def brick_dims(dims):
+    return tuple((int(d) + 1 + 7) // 8 for d in dims)
+
+
+def prod_bdims(dims):
+    b = brick_dims(dims)
+    return b[0] * b[1] * b[2]
+
+
+def brick_lin(rows, dims):
+    """Per row, the linear index of its 8 x 8 x 8 brick in the directory, (bx * bdim_y + by) * bdim_z + bz, as int64."""
+    b = brick_dims(dims)
+    return (rows["ix"].astype(np.int64) // 8 * b[1] + rows["iy"].astype(np.int64) // 8) * b[2] + rows["iz"].astype(np.int64) // 8
 
 
 def boundary_counts(scene):
@@ -266,14 +342,16 @@ def rays(bbox, res, seed=0xFACE + 1):
     return np.ascontiguousarray(np.vstack([r for _, r in ray_sets(bbox, res, seed)]))
 
 
-def face_pairs(bbox, res, n=60, step=0.5, seed=0xFACE + 2):
+def face_pairs(bbox, res, n=60, step=0.5, seed=0xFACE + 2, model_box=None):
     """Per face, n pairs of axis-parallel rays on one line, pointing inwards: [(outer rays, inner rays, m, offset in t)].  The inner
     ray starts on the face's plane (the f32 nearest to it), the outer one m march steps of `step` voxels before it, with the smallest
     m in 16..256 for which that origin is an f32 exactly: then sample k + m of the outer ray and sample k of the inner one are the same
     f64 sums, and the same f32 point.  A face without such an m is left out (the z faces of `thin`: a step of 0.5 mm has bits 2^10
-    times finer than the f32 spacing at 0.55 m)."""
+    times finer than the f32 spacing at 0.55 m).  The faces are those of bbox (before a plane inside the grid the outer ray could meet a
+    surface the inner one never sees); the lines run through random points of model_box (bbox by default)."""
     rng = np.random.default_rng(seed)
     lo, hi = lo_hi(bbox)
+    mlo, mhi = lo_hi(bbox if model_box is None else model_box)
     dt = float(step) * float(res)
     out = []
     for axis in range(3):
@@ -283,7 +361,7 @@ def face_pairs(bbox, res, n=60, step=0.5, seed=0xFACE + 2):
             if m is None:
                 continue
             assert (f - sign * (m * dt)) + sign * (m * dt) == f
-            o = rng.uniform(lo, hi, (n, 3)).astype(np.float32)
+            o = rng.uniform(mlo, mhi, (n, 3)).astype(np.float32)
             d = np.zeros((n, 3), np.float32)
             d[:, axis] = sign
             o[:, axis] = np.float32(f)
@@ -294,11 +372,15 @@ def face_pairs(bbox, res, n=60, step=0.5, seed=0xFACE + 2):
     return out
 
 
-def outside_view(bbox, W=160, H=120):
-    """(pose, K) of a camera 0.08 m outside the z-min face, looking along +z through it at the whole box."""
+def outside_view(bbox, W=160, H=120, max_face=False):
+    """(pose, K) of a camera 0.08 m outside the z-min face, looking along +z through it at the whole box; with max_face, outside the
+    z-max face looking along -z (half a turn about x)."""
     lo, hi = lo_hi(bbox)
     c = (lo + hi) / 2
-    pose = np.hstack([np.eye(3), np.array([[c[0]], [c[1]], [lo[2] - 0.08]])])
+    if max_face:
+        pose = np.hstack([np.diag([1.0, -1.0, -1.0]), np.array([[c[0]], [c[1]], [hi[2] + 0.08]])])
+    else:
+        pose = np.hstack([np.eye(3), np.array([[c[0]], [c[1]], [lo[2] - 0.08]])])
     f = 0.08 * W / (hi[0] - lo[0]) * 0.8   # the z-min face fills the image and a little of its surroundings
     return pose, (f, f, (W - 1) / 2.0, (H - 1) / 2.0)
 

@@ -12,6 +12,7 @@ import numpy as np
 import align_ref as A
 import cover_ref as V
 import deviation_ref as D
+import faces
 import mesh_ref as M
 import scenes
 import track_ref as TR
@@ -71,6 +72,50 @@ def held_out(synth_mod, W=640, H=480, f=HELD_OUT):
     pose = synth_mod.pose(POSE_SEED, f)
     depth, _, K = synth_mod.depth_frame(SEED, f, W, H, pose)
     return depth, K, pose
+
+
+# ---- one fused scene of tests/faces.py ------------------------------------------------------------------------------------------
+
+class Session:
+    """One scene fused on the engine with colour, its rows and occupied list, and what the read-out tests share of it."""
+
+    def __init__(self, hfpf_mod, name, caps=SMALL_CAPS, **kw):
+        self.name, self.H = name, hfpf_mod
+        self.sc = faces.FaceScene(name)
+        self.bbox, self.model_box = self.sc.bbox, self.sc.model_box
+        self.g = hfpf_mod.OccupancyGrid(resolution=self.sc.resolution, bbox=self.bbox, fuse_color=True, **self.sc.config, **caps, **kw)
+        self._mesh = None
+        try:
+            self.rows = scenes.run(self.g, self.sc, "integrate").copy()
+            self.occ = self.g.occupied().copy()
+            self.dims, self.res = self.g.dims
+            print("%s: dims %r, device_bytes %d" % (name, self.dims, self.g.counters()["device_bytes"]))
+            faces.check_conditions(name, self.rows, self.occ, self.dims)
+        except BaseException:
+            self.g.close()
+            raise
+        self.counters = counters(self.g)
+        for a in (self.rows, self.occ):
+            a.setflags(write=False)
+
+    def own_mesh(self):
+        """The session's own mesh at radius 2: (host vertices, host triangles, device vertices, device triangles)."""
+        if self._mesh is None:
+            v, t = self.g.extract_mesh(radius=2)
+            dv, nv, dt, nt = self.g.extract_mesh_device(radius=2)
+            assert nv == len(v) and nt == len(t) and nt > 1000, "the own mesh: %d / %d vertices, %d / %d triangles" % (nv, len(v), nt, len(t))
+            assert self.g.device_download(dv, nv * 32).tobytes() == v.tobytes() and self.g.device_download(dt, nt * 12).tobytes() == t.tobytes(), \
+                "the own mesh: host and device forms differ"
+            self._mesh = (v, t, dv, dt)
+        return self._mesh
+
+    def close(self):
+        if self.g is None:
+            return
+        if self._mesh is not None:
+            self.g.device_free(self._mesh[2]), self.g.device_free(self._mesh[3])
+        self.g.close()
+        self.g = None
 
 
 # ---- comparators ------------------------------------------------------------------------------------------------------------------

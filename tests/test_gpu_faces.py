@@ -29,39 +29,6 @@ HOT_NAMES = faces.NAMES + faces.HOT_NAMES  # hot path, query and mesh
 STEP = 0.5
 
 
-class Session:
-    """One scene fused on the engine with colour, its rows and occupied list, and what the read-out tests share of it."""
-
-    def __init__(self, hfpf_mod, name, caps=G.SMALL_CAPS):
-        self.name, self.H = name, hfpf_mod
-        self.sc = faces.FaceScene(name)
-        self.bbox = self.sc.bbox
-        self.g = hfpf_mod.OccupancyGrid(resolution=self.sc.resolution, bbox=self.bbox, fuse_color=True, **self.sc.config, **caps)
-        self.rows = scenes.run(self.g, self.sc, "integrate").copy()
-        self.occ = self.g.occupied().copy()
-        self.dims, self.res = self.g.dims
-        faces.check_conditions(name, self.rows, self.occ, self.dims)
-        self.counters = G.counters(self.g)
-        for a in (self.rows, self.occ):
-            a.setflags(write=False)
-        self._mesh = None
-
-    def own_mesh(self):
-        """The session's own mesh at radius 2: (host vertices, host triangles, device vertices, device triangles)."""
-        if self._mesh is None:
-            v, t = self.g.extract_mesh(radius=2)
-            dv, nv, dt, nt = self.g.extract_mesh_device(radius=2)
-            assert nv == len(v) and nt == len(t) and nt > 1000
-            assert self.g.device_download(dv, nv * 32).tobytes() == v.tobytes() and self.g.device_download(dt, nt * 12).tobytes() == t.tobytes()
-            self._mesh = (v, t, dv, dt)
-        return self._mesh
-
-    def close(self):
-        if self._mesh is not None:
-            self.g.device_free(self._mesh[2]), self.g.device_free(self._mesh[3])
-        self.g.close()
-
-
 @pytest.fixture(scope="module")
 def sessions(hfpf_mod, synth_mod):
     """name -> Session, each built when first asked for and closed at the end of the module."""
@@ -69,7 +36,7 @@ def sessions(hfpf_mod, synth_mod):
 
     def get(name):
         if name not in made:
-            made[name] = Session(hfpf_mod, name)
+            made[name] = G.Session(hfpf_mod, name)
         return made[name]
 
     yield get
