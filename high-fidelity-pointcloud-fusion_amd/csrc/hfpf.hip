@@ -208,7 +208,8 @@ struct Knobs {
     float bin_slack = 2.0f;          // planned capacity of a bin region = the brick's demand in the previous launch x this (HFPF_BIN_SLACK)
     bool clean_small_nowait = true;  // small clean passes run without a mid-pass read-back (HFPF_CLEAN_NOWAIT=0 restores it)
     bool clean_overlap = true;       // HFPF_CLEAN_OVERLAP=0: k_buffer stays behind the update kernel and a clean pass runs on the engine's stream alone
-    bool trace_clean = false;        // HFPF_TRACE_CLEAN=1: one stderr line per clean pass that launches kernels: which stream its front half took
+    bool early_replay = true;        // HFPF_EARLY_REPLAY=0: the buffer replay of an overlapped small pass stays behind the dependant-table update (k_replay)
+    bool trace_clean = false;        // HFPF_TRACE_CLEAN=1: one stderr line per clean pass that launches kernels: which stream its front half took, which replay
     float test_bin_scale = 1.f;      // tests only (HFPF_TEST_BIN_SCALE): shrinks the planned bin regions so that they overflow into the direct forms
     bool test_table_skip = false;    // tests only (HFPF_TEST_TABLE_SKIP=1): Tables::test_table_skip
     bool mailbox = true;             // HFPF_MAILBOX=0: counter read-backs by blit copies + synchronize
@@ -313,8 +314,9 @@ struct hfpf_handle {
     unsigned long long* mbox = nullptr;       // coherent pinned mailbox k_publish_counters writes (null with HFPF_MAILBOX=0): two slots of kMboxSlotWords
     // The front half of a clean pass (sentinels, gate, candidate sort, k_normal, k_register) runs here beside the update kernel of
     // the integrate call before it: it waits for ev_ready, the engine's stream waits for ev_front behind k_register (clean_locked)
+    // and, at the end of the pass, for ev_replay behind the registration-fed replay that follows k_register there
     hipStream_t front_stream = nullptr;
-    hipEvent_t ev_ready = nullptr, ev_front = nullptr;
+    hipEvent_t ev_ready = nullptr, ev_front = nullptr, ev_replay = nullptr;
     std::vector<DevBuf*> bufs;  // every DevBuf below, in declaration order (DevBuf's constructor): what hfpf_destroy frees
     DevBuf pend_a{bufs}, pend_b{bufs};  // the gate's pending-cell lists (Session::pend_valid)
     StageSlot stage[kStageSlots];
@@ -605,6 +607,7 @@ Knobs read_knobs()
     if (const char* bs = getenv("HFPF_BIN_SLACK")) k.bin_slack = std::max(1.0f, std::min(4.0f, (float)atof(bs)));
     if (const char* nw = getenv("HFPF_CLEAN_NOWAIT")) k.clean_small_nowait = nw[0] != '0';
     if (const char* co = getenv("HFPF_CLEAN_OVERLAP")) k.clean_overlap = co[0] != '0';
+    if (const char* er = getenv("HFPF_EARLY_REPLAY")) k.early_replay = er[0] != '0';
     if (const char* tc = getenv("HFPF_TRACE_CLEAN")) k.trace_clean = tc[0] != '0';
     if (const char* bs = getenv("HFPF_TEST_BIN_SCALE")) k.test_bin_scale = std::max(0.f, std::min(1.f, (float)atof(bs)));
     const char* ts = getenv("HFPF_TEST_TABLE_SKIP");
@@ -1556,6 +1559,13 @@ void launch_gate(hfpf_handle* h, hipStream_t s, const uint32_t* cells_a, uint64_
 // ev_ready, the engine's stream for ev_front, and the back half -- the filing of pre-dependants (it rewrites info words the
 // update reads: k_clean_file), the dependant-table update, the replays -- follows on the engine's stream as ever.  Scratch: pend_b,
 // keys_a and sort_tmp are the front half's alone until ev_front; the engine's stream holds only the update kernel and a publish.
+// A small (no-wait) overlapped pass also replays there, behind k_register (k_replay_reg, HFPF_EARLY_REPLAY=0 switches it off).  It
+// READS reg_occ from the pass's first registration on, nv_line of the new records, buf_head and the log -- chains and log are final
+// behind k_integrate_overflow and k_buffer, ahead of ev_ready, and the update kernel appends to neither -- and WRITES integer atomic
+// adds into the statistics of the NEW records (no list names them yet, so the update kernel adds to none of them) and into the
+// striped replay counter (word 1 of the log_ctr lines; the update kernel's are words 2 and 3).  It touches neither info, dep[] nor
+// dep_tmp, so the back half -- file, offsets, fill -- runs beside it; k_depinc_fill then leaves no note, and the engine's stream
+// waits for ev_replay at the end of the pass, ahead of whatever appends to the log, publishes or reads next.
 // The early publish cannot show an error bit the update kernel raises: like the errors of a no-wait pass it surfaces at the next
 // read-back and poisons the handle there.  Everything else -- no call pending, a read-back since (hfpf_sync, hfpf_get_counters),
 // a distributed session, the un-binned forms, a compacting pass, HFPF_CLEAN_OVERLAP=0 -- is the plain sequence on one stream.
@@ -1616,9 +1626,17 @@ int clean_locked(hfpf_handle* h, int pre_rc)
     bool full = h->h_ctr[C_DEP] + 2 * live_ub + 2 * reg_ub + n_new_occ > t.max_dep;
     const bool overlap = early && !full;
     const uint32_t* new_cells = (const uint32_t*)(t.occ_list + h->ss.gate_done);
+    // registrations already present in dep[]: every pass files all of its own, so that is the counter as this pass found it
+    const uint64_t reg_first = std::min<uint64_t>(h->h_ctr[C_REG], t.max_reg);
+    // A pass is SMALL when its upper bounds are: then the replay is launched over the bound and reads its count on the device,
+    // and the host does not wait for the pass at all (no mid-pass read-back: the GPU is not left idle for a host round trip, and
+    // the next integrate call is enqueued behind the pass at once).  The bound above makes sure the pass cannot run out of dep[]
+    // half-way (the one overflow the host would have to repair by compacting).
+    const bool no_wait = !full && reg_ub < (1ull << 21) && h->knobs.clean_small_nowait;
+    const bool replay_early = overlap && no_wait && h->knobs.early_replay;  // the replay too goes beside the update kernel (below)
     if (h->knobs.trace_clean)
-        fprintf(stderr, "hfpf: clean pass %llu: %llu candidates, front half %s\n", (unsigned long long)h->clean_passes, (unsigned long long)n_in,
-                overlap ? "beside the update kernel" : "on the engine's stream");
+        fprintf(stderr, "hfpf: clean pass %llu: %llu candidates, front half %s, replay %s\n", (unsigned long long)h->clean_passes, (unsigned long long)n_in,
+                overlap ? "beside the update kernel" : "on the engine's stream", replay_early ? "fed from the registrations" : "behind the dependant-table update");
     if (overlap) {  // the front half beside the update kernel; `s` is the engine's stream again behind k_register
         s = h->front_stream;
         HIPCHK(h, hipStreamWaitEvent(s, h->ev_ready, 0));
@@ -1648,22 +1666,26 @@ int clean_locked(hfpf_handle* h, int pre_rc)
     HIPCHK(h, hipGetLastError());
     if (overlap) {
         HIPCHK(h, hipEventRecord(h->ev_front, s));
+        if (replay_early) {  // still beside the update kernel; the engine's stream joins it at the end of the pass (ev_replay)
+            with_color(t.color, [&](auto C) {
+                hipLaunchKernelGGL(k_replay_reg<C>, dim3(blocks_for(reg_ub * kChains, 256)), dim3(256), 0, s, h->g, t, reg_first, kCountOnDevice);
+            });
+            HIPCHK(h, hipGetLastError());
+            HIPCHK(h, hipEventRecord(h->ev_replay, s));
+        }
         s = h->stream;
         HIPCHK(h, hipStreamWaitEvent(s, h->ev_front, 0));
         if (n_new_occ) hipLaunchKernelGGL(k_clean_file, dim3(blocks_for(n_new_occ, 256)), dim3(256), 0, s, t, new_cells, n_new_occ);
     }
     uint64_t n_reg = 0, n_pre = 0, inc_touched = 0;
-    // registrations already present in dep[]: every pass files all of its own, so that is the counter as this pass found it
-    const uint64_t reg_first = std::min<uint64_t>(h->h_ctr[C_REG], t.max_reg);
-    // A pass is SMALL when its upper bounds are: then the replay is launched over the bound and reads the touched-cell count on
-    // the device, and the host does not wait for the pass at all (no mid-pass read-back: the GPU is not left idle for a host
-    // round trip, and the next integrate call is enqueued behind the replay at once).  The bound above makes sure the pass
-    // cannot run out of dep[] half-way (the one overflow the host would have to repair by compacting).
-    const bool no_wait = !full && reg_ub < (1ull << 21) && h->knobs.clean_small_nowait;
     if (!full) {
         hipLaunchKernelGGL(k_depinc_offsets, dim3(blocks_for(reg_ub, 256 * kListTiles)), dim3(256), 0, s, t, kCountOnDevice);
-        hipLaunchKernelGGL(k_depinc_fill, dim3(blocks_for(reg_ub, 256)), dim3(256), 0, s, t, reg_first, kCountOnDevice);
+        hipLaunchKernelGGL(k_depinc_fill, dim3(blocks_for(reg_ub, 256)), dim3(256), 0, s, t, reg_first, kCountOnDevice, replay_early ? 0u : 1u);
         HIPCHK(h, hipGetLastError());
+        if (replay_early) {  // nothing that appends to the log or the chains, or publishes the counters, gets ahead of the replay
+            HIPCHK(h, hipStreamWaitEvent(s, h->ev_replay, 0));
+            return HFPF_OK;
+        }
         if (no_wait) {  // errors of this pass (capacity) surface at the next read-back and poison the handle there
             with_color(t.color, [&](auto C) {
                 hipLaunchKernelGGL(k_replay<C>, dim3(blocks_for(reg_ub * kChains, 256)), dim3(256), 0, s, h->g, t, (const uint32_t*)t.touched_list, 1u, 0u,
@@ -1794,6 +1816,7 @@ int hfpf_create(const hfpf_config* cfg, hfpf_handle** out)
             if (cs) (void)hipStreamDestroy(cs);
         if (h->ev_ready) (void)hipEventDestroy(h->ev_ready);
         if (h->ev_front) (void)hipEventDestroy(h->ev_front);
+        if (h->ev_replay) (void)hipEventDestroy(h->ev_replay);
         if (h->front_stream) (void)hipStreamDestroy(h->front_stream);
         if (h->stream) (void)hipStreamDestroy(h->stream);
         delete h;
@@ -1811,7 +1834,8 @@ int hfpf_create(const hfpf_config* cfg, hfpf_handle** out)
     for (int k = 0; k + 1 < h->knobs.copy_streams; k++)
         if ((e = hipStreamCreateWithFlags(&h->copy_more[k], hipStreamNonBlocking)) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)));
     if ((e = hipStreamCreateWithFlags(&h->front_stream, hipStreamNonBlocking)) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)));
-    if ((e = hipEventCreateWithFlags(&h->ev_ready, hipEventDisableTiming)) != hipSuccess || (e = hipEventCreateWithFlags(&h->ev_front, hipEventDisableTiming)) != hipSuccess)
+    if ((e = hipEventCreateWithFlags(&h->ev_ready, hipEventDisableTiming)) != hipSuccess || (e = hipEventCreateWithFlags(&h->ev_front, hipEventDisableTiming)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&h->ev_replay, hipEventDisableTiming)) != hipSuccess)
         return bail(fail(h, HFPF_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e)));
     if ((e = hipHostMalloc((void**)&h->h_ctr, C_COUNT * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess)
         return bail(fail(h, HFPF_ERR_HIP, "hipHostMalloc: %s", hipGetErrorString(e)));
@@ -1911,6 +1935,7 @@ int hfpf_destroy(hfpf_handle* h)
     if (h->mbox) (void)hipHostFree(h->mbox);
     if (h->ev_ready) (void)hipEventDestroy(h->ev_ready);
     if (h->ev_front) (void)hipEventDestroy(h->ev_front);
+    if (h->ev_replay) (void)hipEventDestroy(h->ev_replay);
     if (h->front_stream) (void)hipStreamDestroy(h->front_stream);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;

@@ -13,6 +13,7 @@
 //   K5 k_register         +-K line walk, dependant registration (grid.hpp:403-417,443-449)
 //      k_link_log         chains the point-log entries the direct form appended since the last clean (4 interleaved chains per cell)
 //      k_replay           buffer replay of the cells that gained registrants (grid.hpp:418-440)
+//      k_replay_reg       the same, one walk per registration of the pass, before the dependant-table update
 //      k_depinc_*/k_dep_* incremental update / compacting rebuild of the per-cell dependant table
 //   K6 k_extract_*        ordered compaction of normal_found voxels            (grid.hpp:463-480)
 //      k_epoch_*          multi-GPU exchange of newly occupied cells
@@ -1895,6 +1896,78 @@ __global__ __launch_bounds__(256) void k_replay(const GridParams g, const Tables
     if (threadIdx.x == 0 && s_rep) atomicAdd(&t.log_ctr[(blockIdx.x & (kLogRegions - 1)) * 16 + 1], (unsigned long long)s_rep);
 }
 
+// K5c: the same replay, registration-centric: fed from what k_register left (reg_occ[reg_first .. C_REG): one (cell, new record)
+// pair each) instead of the updated lists, so it needs neither info, dep[] nor the note in dep_tmp and can run before the
+// dependant-table update -- beside the update kernel of the integrate call before the pass (hfpf.hip clean_locked).  kChains
+// adjacent lanes take one registration: the record's line comes from nv_line (the two halves of its dependant entry), lane `sub`
+// walks chain `sub` of the cell.  A cell that gains several registrants in a pass is walked once per registrant here (k_replay:
+// once per three); the sums are integer atomics into records no list names yet, so neither the order nor the update kernel matters.
+template <bool COLOR>
+__global__ __launch_bounds__(256) void k_replay_reg(const GridParams g, const Tables t, const uint64_t reg_first, const uint64_t n_reg_arg)
+{
+    __shared__ unsigned long long queue[4][kQueueRows * kQueueStride];
+    __shared__ unsigned int s_rep;
+    const uint64_t n_reg = n_reg_arg == kCountOnDevice ? min((uint64_t)t.ctr[C_REG], t.max_reg) : n_reg_arg;
+    if (reg_first + (uint64_t)blockIdx.x * (256u / kChains) >= n_reg) return;  // block-uniform: the grid is sized from an upper bound
+    unsigned long long* q = queue[threadIdx.x >> 6];
+    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t j = reg_first + gid / kChains;    // registration
+    const uint32_t sub = (uint32_t)(gid % kChains);  // which of the cell's interleaved chains this lane walks
+    uint32_t nid = 0, head = 0;
+    if (j < n_reg) {
+        const uint2 r = t.reg_occ[j];  // (cell, record): neighbouring registrations are key-adjacent voxels at the same line step
+        nid = r.y;
+        head = t.buf_head[(uint64_t)r.x * kChains + sub];
+    }
+    uint32_t any = head;  // a cell none of whose chains holds a point costs no more than this
+#pragma unroll
+    for (uint32_t o = 1; o < kChains; o <<= 1) any |= (uint32_t)__shfl_xor((int)any, (int)o);
+    StatDeltaT<COLOR> d;
+    stat_delta_zero(d);
+    if (any) {
+        float4 e0, e1;
+        pre_list_entry(t, nid, e0, e1);
+        const F3 la = F3{e0.y, e0.z, e0.w}, lab = F3{e1.x, e1.y, e1.z};
+        const LineDiv ldv = line_div_of(e1.w);
+        uint32_t e = head;
+        while (e) {  // (links: see k_replay)
+            const float4 p = t.log_pt[e];
+            const uint32_t rgb = COLOR ? t.log_rgb[e] : 0u;
+            float sp, distf;
+            if (line_member_hoisted(g, F3{p.x, p.y, p.z}, la, lab, ldv, sp, distf)) stat_delta_add(d, pair_delta(g, sp, distf), rgb);
+            e = __float_as_uint(p.w);
+        }
+    }
+    // sum the sub-chains of the cell (kChains adjacent lanes) before the flush: one record update per registration
+#pragma unroll
+    for (int w = 0; w < kStatUsed; w++) {
+        long long v = d.v[w];
+#pragma unroll
+        for (uint32_t o = 1; o < kChains; o <<= 1) v += __shfl_xor(v, (int)o);
+        d.v[w] = v;
+    }
+    if constexpr (COLOR) {
+#pragma unroll
+        for (int w = 0; w < 3; w++) {
+            long long v = d.rgb[w];
+#pragma unroll
+            for (uint32_t o = 1; o < kChains; o <<= 1) v += __shfl_xor(v, (int)o);
+            d.rgb[w] = v;
+        }
+    }
+    const bool member = sub == 0 && d.v[SW_COUNT] != 0;
+    uint32_t replayed = member ? (uint32_t)d.v[SW_COUNT] : 0u;
+    wave_flush_members(t, q, member, d, nid);
+    // replayed members, counted as k_replay counts them (word 1 of the striped counter lines)
+    if (threadIdx.x == 0) s_rep = 0;
+    __syncthreads();
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) replayed += __shfl_down(replayed, o);
+    if ((threadIdx.x & 63u) == 0 && replayed) atomicAdd(&s_rep, replayed);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_rep) atomicAdd(&t.log_ctr[(blockIdx.x & (kLogRegions - 1)) * 16 + 1], (unsigned long long)s_rep);
+}
+
 // ---- dependant table rebuild --------------------------------------------------------------------
 __device__ __forceinline__ uint32_t reg_slot(const Tables& t, uint64_t j, uint64_t n_reg) { return j < n_reg ? t.reg_occ[j].x : t.prereg_list[j - n_reg]; }
 
@@ -2021,8 +2094,10 @@ __global__ __launch_bounds__(256) void k_depinc_offsets(const Tables t, const ui
     if (threadIdx.x == 0 && s_single) atomicAdd(&t.log_ctr[(blockIdx.x & (kLogRegions - 1)) * 16 + 4], (unsigned long long)s_single);
 }
 
-__global__ __launch_bounds__(256) void k_depinc_fill(const Tables t, const uint64_t reg_first, const uint64_t n_reg_arg)
+__global__ __launch_bounds__(256) void k_depinc_fill(const Tables t, const uint64_t reg_first, const uint64_t n_reg_arg, const uint32_t leave_note)
 {
+    // leave_note = 0: the replay of this pass has been fed from reg_occ (k_replay_reg) and nobody will read the note: the scratch word
+    // goes straight back to zero, what it has to be between passes.
     const uint64_t n_reg = n_reg_arg == kCountOnDevice ? min((uint64_t)t.ctr[C_REG], t.max_reg) : n_reg_arg;
     const uint64_t j = reg_first + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n_reg) return;
@@ -2034,7 +2109,7 @@ __global__ __launch_bounds__(256) void k_depinc_fill(const Tables t, const uint6
     t.dep[(info >> kDepOffShift) + k] = make_dep_entry(t, r.y);
     // exactly (new length - old length) tickets are drawn per cell: whoever draws the last one turns the cursor word into the
     // note for the replay -- this cell gained registrants, they sit behind entry `old length` -- which the replay clears again
-    if (k + 1 == (uint32_t)((info >> kDepCntShift) & kDepCntMask)) t.dep_tmp[r.x] = kTouchedMark | ((v >> 16) & kDepOldMax);
+    if (k + 1 == (uint32_t)((info >> kDepCntShift) & kDepCntMask)) t.dep_tmp[r.x] = leave_note ? kTouchedMark | ((v >> 16) & kDepOldMax) : 0u;
 }
 
 

@@ -44,7 +44,8 @@ constexpr uint32_t kNoFrame = 0xFFFFFFFFu;
 constexpr uint64_t kNormal = 2ull;
 // dep_tmp (per slot, scratch of the dependant-table update): during the incremental fill  old length << 16 | append cursor;
 // afterwards, until the replay has taken note,  kTouchedMark | old length  (the entries behind `old length` are the registrants
-// of the running pass); kDepPoison marks a cell the update had to give up on.  Zero between passes.
+// of the running pass; no note where the pass has replayed from its registrations already: k_replay_reg); kDepPoison marks a cell
+// the update had to give up on.  Zero between passes.
 constexpr uint32_t kTouchedMark = 0x40000000u, kDepPoison = 0x80000000u, kDepOldMax = 0x7FFFu;
 constexpr int kDepCntShift = 2;
 constexpr uint64_t kDepCntMask = 0xFFFFull;
