@@ -31,12 +31,14 @@
 
 #include "../../include/hfpf.h"
 #include "../../include/hfpf_probe.h"
+#include "host_plan.hpp"
 #include "kernels.hpp"
 #include "scratch_layout.hpp"
 
 using namespace hfpf;
 
 static_assert(sizeof(hfpf_row) == sizeof(Row), "hfpf_row layout");
+static_assert(kSlotsPerBrick == (uint64_t)kBrickCells, "host_plan.hpp sizes the slot sort for these bricks");
 
 namespace {
 
@@ -172,10 +174,6 @@ class StagePool {
 
 constexpr int kStageSlots = 8;
 constexpr size_t kXferChunk = 16u << 20;  // bytes per pinned chunk of extract's row download
-#ifndef HFPF_PROBE_FRAMES
-#define HFPF_PROBE_FRAMES 8
-#endif
-constexpr int kProbeFrames = HFPF_PROBE_FRAMES;  // frames of a plan-less batch that go ahead of the rest to measure the per-brick demand
 constexpr int kFrameSlots = 8;  // uploads run ahead of the kernels by up to this many frames
 
 // A validated hfpf_depth_image as the kernels take it (depth_spec below).  32-bit fields only: two specs are compared with memcmp
@@ -421,14 +419,6 @@ int dev_alloc(hfpf_handle* h, T** out, uint64_t count, int memset_byte = 0, bool
     if (do_memset) HIPCHK(h, hipMemsetAsync(p, memset_byte, bytes, h->stream));
     *out = (T*)p;
     return HFPF_OK;
-}
-
-// Entries the bin pool of a launch of `pts` points needs: every brick has two regions, each planned for the brick's whole demand of
-// the previous launch x slack (x 1.5 at least when the plan comes from the dry run's sample) + 64.
-uint64_t bin_pool_entries(const hfpf_handle* h, uint64_t pts, uint64_t bricks)
-{
-    const double per_point = 2.0 * std::max(1.5, (double)h->knobs.bin_slack) + 0.125;
-    return (uint64_t)(per_point * (double)pts) + 128ull * (bricks + 1);
 }
 
 hipError_t sync_copy_streams(hfpf_handle* h)
@@ -942,16 +932,14 @@ int window_from_final(hfpf_handle* h)
     return HFPF_OK;
 }
 
-int pick_update_shape(hfpf_handle* h, double points, uint32_t nb)
+int pick_update_shape(hfpf_handle* h)
 {
-    (void)points;
-    (void)nb;
     if (h->knobs.upd_shape_forced >= 0) return h->knobs.upd_shape_forced;
     const unsigned long long miss = h->h_ctr[C_TABLE_MISS], member = h->h_ctr[C_DEP_MEMBER] + h->h_ctr[C_REPLAY_MEMBER];
     if (h->knobs.trace_shape)
         fprintf(stderr, "hfpf: update shape window: %llu table misses, %llu members (%llu of them replayed so far), %s\n", miss - std::min(miss, h->ss.upd_miss_seen),
                 member - std::min(member, h->ss.upd_member_seen), h->h_ctr[C_REPLAY_MEMBER], h->upd_wide ? "wide" : "dense");
-    if (!h->upd_wide && miss > h->ss.upd_miss_seen && (miss - h->ss.upd_miss_seen) * 500ull > member - std::min(member, h->ss.upd_member_seen)) h->upd_wide = true;
+    if (!h->upd_wide && update_shape_goes_wide(miss, member, h->ss.upd_miss_seen, h->ss.upd_member_seen)) h->upd_wide = true;
     h->ss.upd_miss_seen = miss;
     h->ss.upd_member_seen = member;
     return h->upd_wide ? 1 : 0;
@@ -1112,35 +1100,37 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
 
     const int form = dl ? kFormDepth : packed16(lay, dev_base, true, frame_stride) ? kFormPacked16 : kFormStrided;
     const dim3 block(256);
+    const uint64_t pts = (uint64_t)n_points * n_frames;
     const uint64_t n_tiles = (uint64_t)blocks_for(n_points, 256) * n_frames;
-    // 16x16-pixel tiles when the caller told us the image width and the frame tiles exactly (hfpf_config.frame_width)
-    // (a depth frame carries its own width)
-    const uint32_t fw = dl ? dl->width : h->cfg.frame_width;
-    const uint32_t row_w = (fw >= 16 && fw % 16 == 0 && n_points % fw == 0 && (n_points / fw) % 16 == 0) ? fw : 0u;
+    // (hfpf_config.frame_width; a depth frame carries its own width)
+    const uint32_t row_w = tile_row_width(dl ? dl->width : h->cfg.frame_width, n_points);
     const dim3 grid((unsigned)std::min<uint64_t>(n_tiles, (uint64_t)h->integrate_grid));
     Timed timed(h);
     if (timed.rc) return timed.rc;
     const bool color = h->t.color != 0;
     const bool bin = h->binned;
-    const uint32_t pre_possible = (h->h_ctr[C_NORMALS] > 0 || h->ss.normals_possible) ? 1u : 0u;  // a clean pass has run: unoccupied cells may carry a dependant
+    // (ahead of the dry run: its read-back cannot change the answer, normal records exist only behind a pass that set normals_possible)
+    const OrderPlan order = plan_order(h->h_ctr[C_NORMALS], h->ss.normals_possible, h->knobs.clean_overlap, h->mbox != nullptr, n_frames, h->dist_on);
     // k_integrate on the batch's first launch_frames frames; probe = 1: the dry run
     auto launch_integrate = [&](dim3 grid_, bool bin_, uint32_t launch_frames, uint32_t log_rot, uint32_t probe) {
         with_form(form, color, bin_, [&](auto F, auto C, auto B) {
             hipLaunchKernelGGL((k_integrate<F == kFormPacked16, C, B, F == kFormDepth>), grid_, block, 0, h->stream, IntegrateArgs{h->g, h->t},
                                (const uint8_t*)dev_base, frame_stride, n_points, launch_frames, form_layout<F>(lay, dl), (const double*)s->d_pose,
-                               (const uint32_t*)s->d_ids, row_w, log_rot, probe, pre_possible);
+                               (const uint32_t*)s->d_ids, row_w, log_rot, probe, order.update ? 1u : 0u);
         });
     };
-    // frames of the dry run: twice as many for a long batch.  For 150 frames of 640x480 with random poses the first 8 find 46 % of
-    // the bricks the batch touches and 16 find 50 % (32: 57 %), and the plan made from the larger sample sends 30 % fewer points
-    // through the overflow list (268 K instead of 382 K per 1000-frame pass): whole job +1.5 %; 32 frames add nothing.
-    const uint32_t probe_frames = n_frames >= 8u * (uint32_t)kProbeFrames ? 2u * (uint32_t)kProbeFrames : (uint32_t)kProbeFrames;
-    if (bin && !h->ss.bin_have_hist && n_frames > probe_frames) {
-        // No plan for the per-brick bins yet (first batch of a session): a dry run of the batch's first frames claims their
-        // bricks and records the per-region demand, so that the real launch below parks from its first point.  One extra
-        // read-back (the brick count), once per session; batches of up to kProbeFrames frames just take the direct forms.
-        HIPCHK(h, hipMemsetAsync(h->t.bin_fill, 0, 2 * (h->t.max_bricks + 2) * 4, h->stream));
-        HIPCHK(h, hipMemsetAsync(h->t.bin_capb, 0, 2 * (h->t.max_bricks + 2) * 4, h->stream));
+    // no region exists: every lane takes the direct forms (or none, in the dry run) and the demand is recorded
+    auto reset_bins = [&]() -> hipError_t {
+        hipError_t e = hipMemsetAsync(&h->t.ctr[C_OVF], 0, sizeof(unsigned long long), h->stream);  // (k_bin_place does this where there is a plan)
+        if (!e) e = hipMemsetAsync(h->t.bin_fill, 0, 2 * (h->t.max_bricks + 2) * 4, h->stream);
+        if (!e) e = hipMemsetAsync(h->t.bin_capb, 0, 2 * (h->t.max_bricks + 2) * 4, h->stream);
+        return e;
+    };
+    const uint32_t probe_frames = probe_frames_for(n_frames);
+    if (wants_probe(bin, h->ss.bin_have_hist, n_frames, probe_frames)) {
+        // A dry run of the batch's first frames claims their bricks and records the per-region demand, so that the real launch
+        // below parks from its first point.  One extra read-back (the brick count), once per session.
+        HIPCHK(h, reset_bins());
         const dim3 pgrid((unsigned)std::min<uint64_t>((uint64_t)blocks_for(n_points, 256) * probe_frames, (uint64_t)h->integrate_grid));
         launch_integrate(pgrid, true, probe_frames, 0, 1);
         HIPCHK(h, hipGetLastError());
@@ -1150,34 +1140,16 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
         h->ss.bin_from_probe = true;  // the plan of the launch below comes from a sample: more slack per region
         h->ss.bin_prev_points = (double)n_points * probe_frames;
     }
-    const uint32_t nb_known = (uint32_t)h->ss.n_bricks_known;
-    // a plan = per-brick bin regions sized from the previous launch's demand; without one nothing is parked (direct forms)
-    const bool have_plan = bin && h->ss.bin_have_hist && nb_known > 0;
-    // Bricks this launch may discover get spare regions of an average brick's size: as many as the session found between its last
-    // two counter read-backs (x2), i.e. half the known bricks right after the dry run and a few hundred in the steady state.
-    uint32_t spare = 0, spare_cap = 0;
-    if (have_plan && h->knobs.bin_spare) {
-        const uint64_t grown = h->ss.n_bricks_known - std::min(h->ss.n_bricks_known, h->ss.n_bricks_before);
-        spare = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(2 * grown, 256), std::max<uint64_t>(nb_known / 2, 256));
-        spare = (uint32_t)std::min<uint64_t>(spare, h->t.max_bricks - std::min<uint64_t>(h->t.max_bricks, nb_known));
-    }
-    const uint32_t nb = nb_known + spare;  // bricks the per-brick kernels of this call look at
+    const BinPlan bp = plan_bins({bin, h->ss.bin_have_hist, h->ss.bin_from_probe, h->ss.n_bricks_known, h->ss.n_bricks_before, h->t.max_bricks,
+                                  h->ss.bin_prev_points, h->knobs.bin_spare, h->knobs.bin_slack, h->knobs.test_bin_scale}, pts);
+    const uint32_t nb = bp.nb;
     if (bin) {
-        // pool for this launch's parked points (+25 % plan slack, +64 per brick)
-        const uint64_t pts = (uint64_t)n_points * n_frames;
-        uint64_t pool = bin_pool_entries(h, pts, nb_known);  // two regions per brick, each sized for the whole brick
-        if (spare) {  // an average brick's share of the batch, both regions, within what a 32-bit index still addresses
-            spare_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(pts / std::max(1u, nb_known), 64), 1u << 15);
-            const uint64_t room = 0xFFFFFFFFull - std::min<uint64_t>(pool, 0xFFFFFFFFull);
-            if (2ull * spare * spare_cap > room) spare_cap = (uint32_t)(room / (2ull * spare));
-            pool += 2ull * spare * spare_cap;
-        }
-        if (pool > 0xFFFFFFFFull) return fail(h, HFPF_ERR_BAD_ARG, "integrate: batch too large for the binned update (split the call)");
-        if (h->bin_pool < pool) {
-            int rc2 = scratch(h, h->bin_pt_buf, pool * sizeof(float4));
+        if (bp.too_large) return fail(h, HFPF_ERR_BAD_ARG, "integrate: batch too large for the binned update (split the call)");
+        if (h->bin_pool < bp.pool) {
+            int rc2 = scratch(h, h->bin_pt_buf, bp.pool * sizeof(float4));
             if (rc2) return rc2;
-            if (color && (rc2 = scratch(h, h->bin_rgb_buf, pool * 4))) return rc2;
-            h->bin_pool = pool;
+            if (color && (rc2 = scratch(h, h->bin_rgb_buf, bp.pool * 4))) return rc2;
+            h->bin_pool = bp.pool;
         }
         h->t.bin_pt = (float4*)h->bin_pt_buf.p;
         h->t.bin_rgb = (uint32_t*)h->bin_rgb_buf.p;
@@ -1190,22 +1162,19 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
         h->t.ovf_pt = (float4*)h->ovf_pt_buf.p;
         h->t.ovf_aux = (uint2*)h->ovf_aux_buf.p;
         h->t.ovf_cap = pts;
-        if (have_plan) {
-            const float scale = (float)((double)pts / std::max(1.0, h->ss.bin_prev_points)) * h->knobs.test_bin_scale;
-            const uint32_t n_regions = 2u * (nb_known + 1u);  // two per brick: cells with / without a normal
+        if (bp.have_plan) {
+            const uint32_t n_regions = 2u * (bp.nb_known + 1u);  // two per brick: cells with / without a normal
             const uint32_t n_planned = 2u * (nb + 1u);        // ... and the spare ones behind them
             const uint32_t all_regions = 2u * (uint32_t)(h->t.max_bricks + 2);
             int rc2 = scratch(h, h->bin_sums, (size_t)blocks_for(all_regions, kBinPlanTile) * sizeof(uint32_t));
             if (rc2) return rc2;
-            hipLaunchKernelGGL(k_bin_plan, dim3(blocks_for(n_planned, kBinPlanTile)), dim3(256), 0, h->stream, h->t, n_regions, n_planned, spare_cap, scale,
-                               h->ss.bin_from_probe ? std::max(1.5f, h->knobs.bin_slack) : h->knobs.bin_slack, (uint32_t*)h->bin_sums.p);
+            hipLaunchKernelGGL(k_bin_plan, dim3(blocks_for(n_planned, kBinPlanTile)), dim3(256), 0, h->stream, h->t, n_regions, n_planned, bp.spare_cap, bp.scale,
+                               bp.slack, (uint32_t*)h->bin_sums.p);
             h->ss.bin_from_probe = false;
             hipLaunchKernelGGL(k_bin_place, dim3(blocks_for(all_regions, kBinPlanTile)), dim3(256), 0, h->stream, h->t, n_planned, all_regions, h->bin_pool,
                                (const uint32_t*)h->bin_sums.p);
-        } else {  // no plan yet: no region exists, every lane takes the direct forms, the demand is recorded
-            HIPCHK(h, hipMemsetAsync(&h->t.ctr[C_OVF], 0, sizeof(unsigned long long), h->stream));  // (k_bin_place does this where there is a plan)
-            HIPCHK(h, hipMemsetAsync(h->t.bin_fill, 0, 2 * (h->t.max_bricks + 2) * 4, h->stream));
-            HIPCHK(h, hipMemsetAsync(h->t.bin_capb, 0, 2 * (h->t.max_bricks + 2) * 4, h->stream));
+        } else {  // no plan yet
+            HIPCHK(h, reset_bins());
         }
     }
     const uint32_t log_rot = (uint32_t)((h->launch_seq++ * 17u) & (kLogRegions - 1));
@@ -1239,22 +1208,16 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
         for (int k = 0; k < 3; k++) HIPCHK(h, detail_mark());
     } else {
         {  // the points that found no room in a bin (usually a few thousand, everything for a batch without a plan): direct forms
-            const unsigned ogrid = (unsigned)std::min<uint64_t>(blocks_for((uint64_t)n_points * n_frames, 256), 8ull * 256);
+            const unsigned ogrid = (unsigned)std::min<uint64_t>(blocks_for(pts, 256), 8ull * 256);
             with_color(color, [&](auto C) { hipLaunchKernelGGL(k_integrate_overflow<C>, dim3(ogrid), dim3(256), 0, h->stream, h->g, h->t, log_rot); });
         }
         HIPCHK(h, detail_mark());
-        if (have_plan) {
-            const bool update = h->h_ctr[C_NORMALS] > 0 || h->ss.normals_possible;  // without a normal record no cell has dependants
-            // k_buffer ahead of the update kernel (both only read the bins, and they write disjoint tables): everything a clean
-            // pass reads at its head is then final while the update kernel -- the longer of the two by far -- still runs, and an
-            // early publish + ev_ready let the pass begin beside it (clean_locked).  Only where that can happen: a batch on a
-            // single rank with the mailbox; otherwise the order of old.
-            const bool buffer_first = update && h->knobs.clean_overlap && h->mbox && n_frames >= 4 && !h->dist_on;
+        if (bp.have_plan) {
             auto launch_buffer = [&]() {
                 detail_ran |= 4;
                 with_color(color, [&](auto C) { hipLaunchKernelGGL(k_buffer<C>, dim3(nb), dim3(256), 0, h->stream, h->g, h->t, nb); });
             };
-            if (buffer_first) {
+            if (order.buffer_first) {  // ... ahead of the update kernel (plan_order)
                 detail_ran |= 8;  // events 1..2 bracket k_buffer and 2..3 the update kernel (resolve_timing)
                 launch_buffer();
                 early_seq = ++h->mbox_seq;
@@ -1263,18 +1226,17 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
                 HIPCHK(h, hipEventRecord(h->ev_ready, h->stream));
                 HIPCHK(h, detail_mark());
             }
-            if (update) {
+            if (order.update) {
                 detail_ran |= 2;
                 if (h->knobs.update_cells) {
                     if ((rc = window_from_final(h))) return rc;
-                    const int shape = pick_update_shape(h, (double)n_points * n_frames, nb);
-                    launch_update_cells<false>(color, shape == 1, h->stream, h->g, h->t, nb);
+                    launch_update_cells<false>(color, pick_update_shape(h) == 1, h->stream, h->g, h->t, nb);
                 } else {
                     with_color(color, [&](auto C) { hipLaunchKernelGGL(k_update<C>, dim3(nb), dim3(kUpdThreads), 0, h->stream, h->g, h->t, nb); });
                 }
             }
             HIPCHK(h, detail_mark());
-            if (!buffer_first) {
+            if (!order.buffer_first) {
                 launch_buffer();
                 HIPCHK(h, detail_mark());
             }
@@ -1293,7 +1255,7 @@ int integrate_device_locked(hfpf_handle* h, const void* dev_base, uint32_t n_fra
     s->pending = true;
     h->ss.dirty = true;  // state_changed = true, grid.hpp:189
     h->frames_integrated += n_frames;
-    if (h->mbox && n_frames >= 4) {  // a batch: the next call is probably a clean pass, which starts by reading the counters
+    if (order.final_publish) {  // a batch: the next call is probably a clean pass, which starts by reading the counters
         if ((rc = window_from_final(h))) return rc;  // (a final publish nobody has read yet is about to be overwritten)
         h->ss.pub_seq = ++h->mbox_seq;
         k_publish_counters<<<1, 256, 0, h->stream>>>(h->t.ctr, h->t.log_ctr, h->mbox, h->ss.pub_seq);
@@ -1569,20 +1531,23 @@ void launch_gate(hfpf_handle* h, hipStream_t s, const uint32_t* cells_a, uint64_
 // The early publish cannot show an error bit the update kernel raises: like the errors of a no-wait pass it surfaces at the next
 // read-back and poisons the handle there.  Everything else -- no call pending, a read-back since (hfpf_sync, hfpf_get_counters),
 // a distributed session, the un-binned forms, a compacting pass, HFPF_CLEAN_OVERLAP=0 -- is the plain sequence on one stream.
+// Who decides (host_plan.hpp): clean_starts_early whether the head-of-pass counters come from the early publish; plan_clean, from
+// those counters, whether the pass compacts, overlaps, waits, replays early; plan_replay the replay of a waited pass.  This function
+// enqueues what they say, and changes one answer only: a pass whose incremental update ran out of dep[] compacts after all.
 int clean_locked(hfpf_handle* h, int pre_rc)
 {
     Tables& t = h->t;
-    hipStream_t s = h->stream;
     int rc;
     // collective: every rank cleans at the same schedule point; a rank that is already unusable (pre_rc) still says so to its peers
     if (h->dist_on && (rc = dist_exchange_locked(h, pre_rc))) return rc;
     if (pre_rc) return pre_rc;
-    const bool early = h->knobs.clean_overlap && !h->dist_on && h->binned && h->mbox && h->ss.pub_seq && h->ss.early_seq;
+    const bool early = clean_starts_early(h->knobs.clean_overlap, h->dist_on, h->binned, h->mbox != nullptr, h->ss.pub_seq, h->ss.early_seq);
     if ((rc = read_counters(h, early))) return rc;
     if ((rc = check_device_errors(h))) return rc;
-    const uint64_t n_occ = std::min<uint64_t>(h->h_ctr[C_OCC], t.max_occ);
-    const uint64_t n_normals = h->h_ctr[C_NORMALS];
-    const uint64_t n_pend = h->ss.pend_valid ? h->h_ctr[C_PEND] : 0;  // cells the previous pass left without a normal (pend_a)
+    const unsigned long long* c = h->h_ctr;
+    const CleanPlan p = plan_clean({c[C_OCC], c[C_NORMALS], c[C_PEND], c[C_REG], c[C_PREREG], c[C_DEP]}, t.max_occ, t.max_reg, t.max_dep, h->ss.gate_done,
+                                   h->ss.pend_valid, h->g.K, early, h->knobs.clean_small_nowait, h->knobs.early_replay);
+    const uint64_t n_occ = p.n_occ, n_normals = p.n_normals, n_pend = p.n_pend, n_new_occ = p.n_new_occ, n_in = p.n_in, reg_ub = p.reg_ub;
     h->ss.occ_exported = n_occ;  // everything occupied so far (locally or imported) has been exchanged
     h->ss.frames_exported = std::max(h->ss.frames_exported, h->ss.frames_seen);  // ... and the viewpoints of the frames the last export covered
     h->ss.dirty = false;  // state_changed = false, grid.hpp:313
@@ -1601,51 +1566,29 @@ int clean_locked(hfpf_handle* h, int pre_rc)
         }
         // entries appended by k_buffer arrive chained; only k_integrate's direct form leaves marked entries behind
         if (max_new && !h->binned && h->h_ctr[C_BUFFERED] != h->ss.direct_linked) {  // (the binned form chains its few direct appends itself)
-            hipLaunchKernelGGL(k_link_log, dim3(blocks_for(max_new, 256), kLogRegions), dim3(256), 0, s, t, lr);
+            hipLaunchKernelGGL(k_link_log, dim3(blocks_for(max_new, 256), kLogRegions), dim3(256), 0, h->stream, t, lr);
             HIPCHK(h, hipGetLastError());
         }
         h->ss.direct_linked = h->h_ctr[C_BUFFERED];
     }
-    if (n_occ == 0) return HFPF_OK;
+    if (n_occ == 0 || n_in == 0) return HFPF_OK;  // no candidates: nothing to do
 
-    // candidates: the cells that failed the gate last time (pending list) + the cells occupied since (new tail of occ_list)
-    const uint64_t n_new_occ = n_occ - std::min(n_occ, h->ss.gate_done);
-    const uint64_t n_in = n_pend + n_new_occ;  // upper bound of everything this pass can produce per candidate
-    if (n_in == 0) return HFPF_OK;
     if ((rc = scratch(h, h->pend_b, n_in * 4))) return rc;
     if ((rc = scratch(h, h->keys_a, n_in * 8))) return rc;
-    // The registration counts of this pass are bounded by (2K+1) * n_in; the kernels below read the exact counts from the
-    // device counters (kCountOnDevice), and the host picks the values up at the read-back after them.
-    const uint64_t reg_ub = (2ull * (uint64_t)h->g.K + 1ull) * n_in;
-    // Incremental update of the dependant table, or a compacting rebuild?  A conservative space estimate decides (C_DEP as of the
-    // read-back above: nothing has changed it since).  What one incremental update can take from dep[]: a block of the next
-    // power-of-two capacity for every list that outgrows its own (kernels.hpp dep_capacity) -- below twice its new length, i.e.
-    // at most twice (all live entries: registrations + filed pre-dependants so far, + the registration bound of this pass) -- and
-    // one entry per cell occupied since the last pass (the pre-dependants filed at the head of the pass).
-    const uint64_t live_ub = std::min<uint64_t>(h->h_ctr[C_REG], t.max_reg) + std::min<uint64_t>(h->h_ctr[C_PREREG], t.max_reg);
-    bool full = h->h_ctr[C_DEP] + 2 * live_ub + 2 * reg_ub + n_new_occ > t.max_dep;
-    const bool overlap = early && !full;
     const uint32_t* new_cells = (const uint32_t*)(t.occ_list + h->ss.gate_done);
-    // registrations already present in dep[]: every pass files all of its own, so that is the counter as this pass found it
-    const uint64_t reg_first = std::min<uint64_t>(h->h_ctr[C_REG], t.max_reg);
-    // A pass is SMALL when its upper bounds are: then the replay is launched over the bound and reads its count on the device,
-    // and the host does not wait for the pass at all (no mid-pass read-back: the GPU is not left idle for a host round trip, and
-    // the next integrate call is enqueued behind the pass at once).  The bound above makes sure the pass cannot run out of dep[]
-    // half-way (the one overflow the host would have to repair by compacting).
-    const bool no_wait = !full && reg_ub < (1ull << 21) && h->knobs.clean_small_nowait;
-    const bool replay_early = overlap && no_wait && h->knobs.early_replay;  // the replay too goes beside the update kernel (below)
     if (h->knobs.trace_clean)
         fprintf(stderr, "hfpf: clean pass %llu: %llu candidates, front half %s, replay %s\n", (unsigned long long)h->clean_passes, (unsigned long long)n_in,
-                overlap ? "beside the update kernel" : "on the engine's stream", replay_early ? "fed from the registrations" : "behind the dependant-table update");
-    if (overlap) {  // the front half beside the update kernel; `s` is the engine's stream again behind k_register
-        s = h->front_stream;
-        HIPCHK(h, hipStreamWaitEvent(s, h->ev_ready, 0));
-        hipLaunchKernelGGL(k_clean_front, dim3(blocks_for(n_in, 256)), dim3(256), 0, s, t, n_in);
+                p.overlap ? "beside the update kernel" : "on the engine's stream", p.replay_early ? "fed from the registrations" : "behind the dependant-table update");
+    // the front half: beside the update kernel on a stream of its own, or on the engine's like everything behind k_register
+    const hipStream_t front = p.overlap ? h->front_stream : h->stream;
+    if (p.overlap) {
+        HIPCHK(h, hipStreamWaitEvent(front, h->ev_ready, 0));
+        hipLaunchKernelGGL(k_clean_front, dim3(blocks_for(n_in, 256)), dim3(256), 0, front, t, n_in);
     } else {
         // sentinels + the pass's list counters + the pre-dependants of the cells occupied since the last pass become their lists
-        hipLaunchKernelGGL(k_clean_begin, dim3(blocks_for(n_in, 256)), dim3(256), 0, s, t, n_in, new_cells, n_new_occ, full ? 1u : 0u);
+        hipLaunchKernelGGL(k_clean_begin, dim3(blocks_for(n_in, 256)), dim3(256), 0, front, t, n_in, new_cells, n_new_occ, p.full ? 1u : 0u);
     }
-    launch_gate(h, s, (const uint32_t*)h->pend_a.p, n_pend, new_cells, n_new_occ, (uint32_t*)h->pend_b.p);
+    launch_gate(h, front, (const uint32_t*)h->pend_a.p, n_pend, new_cells, n_new_occ, (uint32_t*)h->pend_b.p);
     HIPCHK(h, hipGetLastError());
     h->ss.gate_done = n_occ;
     h->ss.normals_possible = true;
@@ -1655,40 +1598,41 @@ int clean_locked(hfpf_handle* h, int pre_rc)
     // canonical order: ascending (x,y,z) key; record id = n_normals + rank + 1
     // (with HFPF_MORTON_IDS the candidate keys are Z-order codes: three interleaved axes of the widest axis' bits)
     const unsigned cand_bits = HFPF_MORTON_IDS ? 3u * std::max(h->g.key_sy, std::max(h->g.key_sx - h->g.key_sy, h->g.key_bits - h->g.key_sx)) : h->g.key_bits;
-    if ((rc = sort_keys_u64(h, t.cand_key, (uint64_t*)h->keys_a.p, n_in, cand_bits, s))) return rc;
-    hipLaunchKernelGGL(k_normal, dim3(blocks_for(n_in, 128)), dim3(128), 0, s, h->g, t, (const uint64_t*)h->keys_a.p, kCountOnDevice, n_normals);
+    if ((rc = sort_keys_u64(h, t.cand_key, (uint64_t*)h->keys_a.p, n_in, cand_bits, front))) return rc;
+    hipLaunchKernelGGL(k_normal, dim3(blocks_for(n_in, 128)), dim3(128), 0, front, h->g, t, (const uint64_t*)h->keys_a.p, kCountOnDevice, n_normals);
     const bool reg_small = n_in < (1ull << 18);  // tiles per workgroup: kernels.hpp k_register
     const uint64_t reg_tile = 256ull * (reg_small ? kRegTilesSmall : kRegTilesLarge);  // step-major, whole workgroups per step
     const uint64_t reg_blocks = ((n_in + reg_tile - 1) / reg_tile) * (2ull * (uint64_t)h->g.K + 1ull);
-    const uint32_t count_deps = full ? 0u : 1u;  // (the compacting rebuild counts for itself, from zero)
-    if (reg_small) hipLaunchKernelGGL(k_register<kRegTilesSmall>, dim3((unsigned)std::max<uint64_t>(reg_blocks, 1)), dim3(256), 0, s, h->g, t, kCountOnDevice, n_normals, count_deps);
-    else hipLaunchKernelGGL(k_register<kRegTilesLarge>, dim3((unsigned)std::max<uint64_t>(reg_blocks, 1)), dim3(256), 0, s, h->g, t, kCountOnDevice, n_normals, count_deps);
+    const uint32_t count_deps = p.full ? 0u : 1u;  // (the compacting rebuild counts for itself, from zero)
+    if (reg_small) hipLaunchKernelGGL(k_register<kRegTilesSmall>, dim3((unsigned)std::max<uint64_t>(reg_blocks, 1)), dim3(256), 0, front, h->g, t, kCountOnDevice, n_normals, count_deps);
+    else hipLaunchKernelGGL(k_register<kRegTilesLarge>, dim3((unsigned)std::max<uint64_t>(reg_blocks, 1)), dim3(256), 0, front, h->g, t, kCountOnDevice, n_normals, count_deps);
     HIPCHK(h, hipGetLastError());
-    if (overlap) {
-        HIPCHK(h, hipEventRecord(h->ev_front, s));
-        if (replay_early) {  // still beside the update kernel; the engine's stream joins it at the end of the pass (ev_replay)
+    if (p.overlap) {
+        HIPCHK(h, hipEventRecord(h->ev_front, front));
+        if (p.replay_early) {  // still beside the update kernel; the engine's stream joins it at the end of the pass (ev_replay)
             with_color(t.color, [&](auto C) {
-                hipLaunchKernelGGL(k_replay_reg<C>, dim3(blocks_for(reg_ub * kChains, 256)), dim3(256), 0, s, h->g, t, reg_first, kCountOnDevice);
+                hipLaunchKernelGGL(k_replay_reg<C>, dim3(blocks_for(reg_ub * kChains, 256)), dim3(256), 0, front, h->g, t, p.reg_first, kCountOnDevice);
             });
             HIPCHK(h, hipGetLastError());
-            HIPCHK(h, hipEventRecord(h->ev_replay, s));
+            HIPCHK(h, hipEventRecord(h->ev_replay, front));
         }
-        s = h->stream;
-        HIPCHK(h, hipStreamWaitEvent(s, h->ev_front, 0));
-        if (n_new_occ) hipLaunchKernelGGL(k_clean_file, dim3(blocks_for(n_new_occ, 256)), dim3(256), 0, s, t, new_cells, n_new_occ);
+        HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_front, 0));
+        if (n_new_occ) hipLaunchKernelGGL(k_clean_file, dim3(blocks_for(n_new_occ, 256)), dim3(256), 0, h->stream, t, new_cells, n_new_occ);
     }
+    // the back half, on the engine's stream
     uint64_t n_reg = 0, n_pre = 0, inc_touched = 0;
-    if (!full) {
-        hipLaunchKernelGGL(k_depinc_offsets, dim3(blocks_for(reg_ub, 256 * kListTiles)), dim3(256), 0, s, t, kCountOnDevice);
-        hipLaunchKernelGGL(k_depinc_fill, dim3(blocks_for(reg_ub, 256)), dim3(256), 0, s, t, reg_first, kCountOnDevice, replay_early ? 0u : 1u);
+    bool full = p.full;  // the one mode a pass may change: dep[] ran out under an incremental update (a reaction to the read-back below, not a plan)
+    if (!p.full) {
+        hipLaunchKernelGGL(k_depinc_offsets, dim3(blocks_for(reg_ub, 256 * kListTiles)), dim3(256), 0, h->stream, t, kCountOnDevice);
+        hipLaunchKernelGGL(k_depinc_fill, dim3(blocks_for(reg_ub, 256)), dim3(256), 0, h->stream, t, p.reg_first, kCountOnDevice, p.replay_early ? 0u : 1u);
         HIPCHK(h, hipGetLastError());
-        if (replay_early) {  // nothing that appends to the log or the chains, or publishes the counters, gets ahead of the replay
-            HIPCHK(h, hipStreamWaitEvent(s, h->ev_replay, 0));
+        if (p.replay_early) {  // nothing that appends to the log or the chains, or publishes the counters, gets ahead of the replay
+            HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_replay, 0));
             return HFPF_OK;
         }
-        if (no_wait) {  // errors of this pass (capacity) surface at the next read-back and poison the handle there
+        if (p.no_wait) {  // errors of this pass (capacity) surface at the next read-back and poison the handle there
             with_color(t.color, [&](auto C) {
-                hipLaunchKernelGGL(k_replay<C>, dim3(blocks_for(reg_ub * kChains, 256)), dim3(256), 0, s, h->g, t, (const uint32_t*)t.touched_list, 1u, 0u,
+                hipLaunchKernelGGL(k_replay<C>, dim3(blocks_for(reg_ub * kChains, 256)), dim3(256), 0, h->stream, h->g, t, (const uint32_t*)t.touched_list, 1u, 0u,
                                    kCountOnDevice, n_normals);
             });
             HIPCHK(h, hipGetLastError());
@@ -1699,8 +1643,8 @@ int clean_locked(hfpf_handle* h, int pre_rc)
         n_pre = std::min<uint64_t>(h->h_ctr[C_PREREG], t.max_reg);
         inc_touched = h->h_ctr[C_TOUCHED];
         if (h->h_ctr[C_ERR] == (unsigned long long)E_DEP) {  // dep[] ran out mid-way: compact
-            hipLaunchKernelGGL(k_set_ctr, dim3(1), dim3(1), 0, s, t.ctr, (int)C_ERR, 0ull);
-            if (inc_touched) hipLaunchKernelGGL(k_dep_reset, dim3(blocks_for(inc_touched, 256)), dim3(256), 0, s, t, inc_touched);  // poisoned cursors
+            hipLaunchKernelGGL(k_set_ctr, dim3(1), dim3(1), 0, h->stream, t.ctr, (int)C_ERR, 0ull);
+            if (inc_touched) hipLaunchKernelGGL(k_dep_reset, dim3(blocks_for(inc_touched, 256)), dim3(256), 0, h->stream, t, inc_touched);  // poisoned cursors
             full = true;
         } else if ((rc = check_device_errors(h))) {
             return rc;
@@ -1718,15 +1662,15 @@ int clean_locked(hfpf_handle* h, int pre_rc)
         // touched_list holds one entry per distinct cell among the n_all registrations: every normal record registers on at most
         // 2K+1 cells, so n_reg + n_pre <= max_normals * (2K+1) = max_reg = max_touched
         if (n_all > h->max_touched) return fail(h, HFPF_ERR_CAPACITY, "registrations: %llu > %llu", (unsigned long long)n_all, (unsigned long long)h->max_touched);
-        hipLaunchKernelGGL(k_set_ctr3, dim3(1), dim3(1), 0, s, t.ctr, (int)C_DEP, 0ull, (int)C_TOUCHED, 0ull, -1, 0ull);
+        hipLaunchKernelGGL(k_set_ctr3, dim3(1), dim3(1), 0, h->stream, t.ctr, (int)C_DEP, 0ull, (int)C_TOUCHED, 0ull, -1, 0ull);
         if (n_all) {
-            hipLaunchKernelGGL(k_dep_count, dim3(blocks_for(n_all, 256)), dim3(256), 0, s, t, n_reg, n_pre);
+            hipLaunchKernelGGL(k_dep_count, dim3(blocks_for(n_all, 256)), dim3(256), 0, h->stream, t, n_reg, n_pre);
             HIPCHK(h, hipGetLastError());
             if ((rc = read_counters(h))) return rc;
             const uint64_t n_touched = h->h_ctr[C_TOUCHED];
-            hipLaunchKernelGGL(k_dep_offsets, dim3(blocks_for(n_touched, 256)), dim3(256), 0, s, t, n_touched);
-            hipLaunchKernelGGL(k_dep_fill, dim3(blocks_for(n_all, 256)), dim3(256), 0, s, t, n_reg, n_pre);
-            hipLaunchKernelGGL(k_dep_reset, dim3(blocks_for(n_touched, 256)), dim3(256), 0, s, t, n_touched);
+            hipLaunchKernelGGL(k_dep_offsets, dim3(blocks_for(n_touched, 256)), dim3(256), 0, h->stream, t, n_touched);
+            hipLaunchKernelGGL(k_dep_fill, dim3(blocks_for(n_all, 256)), dim3(256), 0, h->stream, t, n_reg, n_pre);
+            hipLaunchKernelGGL(k_dep_reset, dim3(blocks_for(n_touched, 256)), dim3(256), 0, h->stream, t, n_touched);
             HIPCHK(h, hipGetLastError());
             inc_touched = n_touched;  // superset of the cells touched by this pass; k_replay filters by record id
         }
@@ -1734,36 +1678,25 @@ int clean_locked(hfpf_handle* h, int pre_rc)
         if ((rc = check_device_errors(h))) return rc;
     }
     // buffer replay of the cells that gained registrants in this pass (touched_list is still intact)
-    if (inc_touched) {
-        const uint32_t use_marks = full ? 0u : 1u;  // (a compacting rebuild leaves no notes and the lists in no particular order)
-        // Bricks whose buffered points are ONE contiguous run of the log (the epoch was handed over in one integrate call, the
-        // brick is new in it) replay by streaming that run: worth its launch over every brick when enough of the touched cells
-        // lie in such bricks.  The chain walk takes the others.
-        const uint64_t single = full ? 0 : std::min<uint64_t>(h->h_ctr[C_TOUCHED_SINGLE], inc_touched);
-        const bool stream = !full && h->binned && h->knobs.stream_replay && single >= (1ull << 16);
-        if (stream) {
-            const uint32_t nbk = (uint32_t)h->ss.n_bricks_known;
-            const bool wide = h->knobs.upd_shape_forced >= 0 ? h->knobs.upd_shape_forced == 1 : h->upd_wide;  // the shape the dependant updates of this session take
-            launch_update_cells<true>(t.color, wide, s, h->g, t, nbk);
-            HIPCHK(h, hipGetLastError());
+    const ReplayPlan rp = plan_replay(inc_touched, h->h_ctr[C_TOUCHED_SINGLE], full, h->binned, h->knobs.stream_replay, h->ss.n_bricks_known);
+    if (rp.stream) {
+        const uint32_t nbk = (uint32_t)h->ss.n_bricks_known;
+        const bool wide = h->knobs.upd_shape_forced >= 0 ? h->knobs.upd_shape_forced == 1 : h->upd_wide;  // the shape the dependant updates of this session take
+        launch_update_cells<true>(t.color, wide, h->stream, h->g, t, nbk);
+        HIPCHK(h, hipGetLastError());
+    }
+    if (rp.walked) {
+        const uint32_t* cells = t.touched_list;
+        if (rp.sort_walked) {
+            if ((rc = scratch(h, h->vals_a, inc_touched * 4))) return rc;
+            if ((rc = sort_keys_u32(h, t.touched_list, (uint32_t*)h->vals_a.p, inc_touched, rp.slot_bits))) return rc;
+            cells = (const uint32_t*)h->vals_a.p;
         }
-        const uint64_t walked = stream ? inc_touched - single : inc_touched;
-        if (walked) {
-            // a 256-point tile appends consecutive log entries for neighbouring cells, so walking the cells in slot (brick-major)
-            // order lets adjacent lanes share cache lines of the log; a short list is not worth the sort's launches
-            const uint32_t* cells = t.touched_list;
-            if (walked >= (1ull << 18)) {
-                if ((rc = scratch(h, h->vals_a, inc_touched * 4))) return rc;
-                unsigned slot_bits = 9;  // slot = brick * 512 + cell; the brick count is as of the read-back just above
-                while ((1ull << slot_bits) < (h->ss.n_bricks_known + 2) * (uint64_t)kBrickCells && slot_bits < 32) slot_bits++;
-                if ((rc = sort_keys_u32(h, t.touched_list, (uint32_t*)h->vals_a.p, inc_touched, slot_bits))) return rc;
-                cells = (const uint32_t*)h->vals_a.p;
-            }
-            with_color(t.color, [&](auto C) {
-                hipLaunchKernelGGL(k_replay<C>, dim3(blocks_for(inc_touched * kChains, 256)), dim3(256), 0, s, h->g, t, cells, use_marks, stream ? 1u : 0u, inc_touched, n_normals);
-            });
-            HIPCHK(h, hipGetLastError());
-        }
+        with_color(t.color, [&](auto C) {
+            hipLaunchKernelGGL(k_replay<C>, dim3(blocks_for(inc_touched * kChains, 256)), dim3(256), 0, h->stream, h->g, t, cells, rp.use_marks, rp.stream ? 1u : 0u, inc_touched,
+                               n_normals);
+        });
+        HIPCHK(h, hipGetLastError());
     }
     return HFPF_OK;
 }
@@ -1865,7 +1798,7 @@ int hfpf_create(const hfpf_config* cfg, hfpf_handle** out)
             return bail(rc);
         if (h->cfg.max_call_points && h->binned) {
             const uint64_t pts = h->cfg.max_call_points;
-            const uint64_t pool = std::min<uint64_t>(bin_pool_entries(h, pts, h->cfg.max_bricks), 0xFFFFFFFFull);
+            const uint64_t pool = std::min<uint64_t>(bin_pool_entries(h->knobs.bin_slack, pts, h->cfg.max_bricks), 0xFFFFFFFFull);
             if ((rc = scratch(h, h->bin_pt_buf, pool * sizeof(float4)))) return bail(rc);
             if (h->t.color && (rc = scratch(h, h->bin_rgb_buf, pool * 4))) return bail(rc);
             h->bin_pool = pool;

@@ -1,0 +1,192 @@
+// csrc/host_plan.hpp -- what kind of integrate call or clean pass this is.  Host only and free of HIP, so g++ alone compiles it
+// (tests/host_plan_check.cpp).
+//
+// Pure functions over counters, capacities, knobs and session fields: they decide and count, and nothing else.  The two functions that
+// enqueue (integrate_device_locked and clean_locked) read a const plan from here; launch geometry stays at the launch
+// sites, with the kernels' tile constants.  The thresholds below lie far beyond what a test can reach in seconds on the device.
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+
+namespace hfpf {
+
+#ifndef HFPF_PROBE_FRAMES
+#define HFPF_PROBE_FRAMES 8
+#endif
+constexpr int kProbeFrames = HFPF_PROBE_FRAMES;  // frames of a plan-less batch that go ahead of the rest to measure the per-brick demand
+constexpr uint64_t kSlotsPerBrick = 512;         // = kBrickCells (tables.hpp)
+
+// ---- the clean pass ----
+
+// The pass may take its head-of-pass counters from the early publish of the integrate call before it (evaluated before that read-back).
+inline bool clean_starts_early(bool clean_overlap, bool dist_on, bool binned, bool has_mailbox, unsigned long long pub_seq, unsigned long long early_seq)
+{
+    return clean_overlap && !dist_on && binned && has_mailbox && pub_seq && early_seq;
+}
+
+struct CleanHead {  // the counter words as the head-of-pass read-back found them
+    unsigned long long occ, normals, pend, reg, prereg, dep;
+};
+struct CleanPlan {
+    uint64_t n_occ, n_normals;
+    uint64_t n_pend;     // cells the previous pass left without a normal (pend_a)
+    uint64_t n_new_occ;  // cells occupied since the last pass (new tail of occ_list)
+    uint64_t n_in;       // candidates = the two together: upper bound of everything this pass can produce per candidate.  0 (or n_occ == 0): nothing to do
+    uint64_t reg_ub;     // bound of the pass's registration counts; the kernels read the exact counts on the device
+    uint64_t reg_first;  // registrations already present in dep[]: every pass files all of its own, so that is the counter as this pass found it
+    bool full;           // a compacting rebuild of the dependant table instead of the incremental update
+    bool overlap;        // the front half beside the update kernel
+    bool no_wait;        // a SMALL pass: no mid-pass read-back
+    bool replay_early;   // the replay too goes beside the update kernel
+};
+inline CleanPlan plan_clean(const CleanHead& c, uint64_t max_occ, uint64_t max_reg, uint64_t max_dep, uint64_t gate_done, bool pend_valid, int K, bool early,
+                            bool clean_small_nowait, bool early_replay)
+{
+    CleanPlan p{};
+    p.n_occ = std::min<uint64_t>(c.occ, max_occ);
+    p.n_normals = c.normals;
+    p.n_pend = pend_valid ? c.pend : 0;
+    p.n_new_occ = p.n_occ - std::min(p.n_occ, gate_done);
+    p.n_in = p.n_pend + p.n_new_occ;
+    // The registration counts of this pass are bounded by (2K+1) * n_in; the kernels read the exact counts from the device counters
+    // (kCountOnDevice), and the host picks the values up at the read-back after them.
+    p.reg_ub = (2ull * (uint64_t)K + 1ull) * p.n_in;
+    // Incremental update of the dependant table, or a compacting rebuild?  A conservative space estimate decides (C_DEP as of the
+    // head-of-pass read-back: nothing has changed it since).  What one incremental update can take from dep[]: a block of the next
+    // power-of-two capacity for every list that outgrows its own (kernels.hpp dep_capacity) -- below twice its new length, i.e.
+    // at most twice (all live entries: registrations + filed pre-dependants so far, + the registration bound of this pass) -- and
+    // one entry per cell occupied since the last pass (the pre-dependants filed at the head of the pass).
+    const uint64_t live_ub = std::min<uint64_t>(c.reg, max_reg) + std::min<uint64_t>(c.prereg, max_reg);
+    p.full = c.dep + 2 * live_ub + 2 * p.reg_ub + p.n_new_occ > max_dep;
+    p.overlap = early && !p.full;
+    p.reg_first = std::min<uint64_t>(c.reg, max_reg);
+    // A pass is SMALL when its upper bounds are: then the replay is launched over the bound and reads its count on the device,
+    // and the host does not wait for the pass at all (no mid-pass read-back: the GPU is not left idle for a host round trip, and
+    // the next integrate call is enqueued behind the pass at once).  The bound above makes sure the pass cannot run out of dep[]
+    // half-way (the one overflow the host would have to repair by compacting).
+    p.no_wait = !p.full && p.reg_ub < (1ull << 21) && clean_small_nowait;
+    p.replay_early = p.overlap && p.no_wait && early_replay;
+    return p;
+}
+
+// The buffer replay of the inc_touched cells that gained registrants in a waited pass (full: behind a compacting rebuild, planned or not).
+struct ReplayPlan {
+    bool stream;         // the bricks of one contiguous log run replay by streaming it; the chain walk takes the other cells
+    uint64_t walked;     // cells the chain walk has work for (0: no walk)
+    bool sort_walked;    // ... in slot order
+    unsigned slot_bits;  // key bits of that sort: slot = brick * 512 + cell
+    uint32_t use_marks;  // (a compacting rebuild leaves no notes and the lists in no particular order)
+};
+inline ReplayPlan plan_replay(uint64_t inc_touched, unsigned long long touched_single, bool full, bool binned, bool stream_replay, uint64_t n_bricks_known)
+{
+    ReplayPlan r{};
+    r.use_marks = full ? 0u : 1u;
+    // Bricks whose buffered points are ONE contiguous run of the log (the epoch was handed over in one integrate call, the
+    // brick is new in it) replay by streaming that run: worth its launch over every brick when enough of the touched cells
+    // lie in such bricks.  The chain walk takes the others.
+    const uint64_t single = full ? 0 : std::min<uint64_t>(touched_single, inc_touched);
+    r.stream = !full && binned && stream_replay && single >= (1ull << 16);
+    r.walked = r.stream ? inc_touched - single : inc_touched;
+    // a 256-point tile appends consecutive log entries for neighbouring cells, so walking the cells in slot (brick-major)
+    // order lets adjacent lanes share cache lines of the log; a short list is not worth the sort's launches
+    r.sort_walked = r.walked >= (1ull << 18);
+    r.slot_bits = 9;  // the brick count is as of the read-back just ahead of the replay
+    while ((1ull << r.slot_bits) < (n_bricks_known + 2) * kSlotsPerBrick && r.slot_bits < 32) r.slot_bits++;
+    return r;
+}
+
+// ---- the integrate call ----
+
+// frames of the dry run: twice as many for a long batch.  For 150 frames of 640x480 with random poses the first 8 find 46 % of
+// the bricks the batch touches and 16 find 50 % (32: 57 %), and the plan made from the larger sample sends 30 % fewer points
+// through the overflow list (268 K instead of 382 K per 1000-frame pass): whole job +1.5 %; 32 frames add nothing.
+inline uint32_t probe_frames_for(uint32_t n_frames) { return n_frames >= 8u * (uint32_t)kProbeFrames ? 2u * (uint32_t)kProbeFrames : (uint32_t)kProbeFrames; }
+// No plan for the per-brick bins yet (first batch of a session): batches of up to probe_frames frames just take the direct forms.
+inline bool wants_probe(bool bin, bool bin_have_hist, uint32_t n_frames, uint32_t probe_frames) { return bin && !bin_have_hist && n_frames > probe_frames; }
+
+// 16x16-pixel tiles when the caller told us the image width and the frame tiles exactly (0: none)
+inline uint32_t tile_row_width(uint32_t fw, uint32_t n_points) { return (fw >= 16 && fw % 16 == 0 && n_points % fw == 0 && (n_points / fw) % 16 == 0) ? fw : 0u; }
+
+// Entries the bin pool of a launch of `pts` points needs: every brick has two regions, each planned for the brick's whole demand of
+// the previous launch x slack (x 1.5 at least when the plan comes from the dry run's sample) + 64.
+inline uint64_t bin_pool_entries(float bin_slack, uint64_t pts, uint64_t bricks)
+{
+    const double per_point = 2.0 * std::max(1.5, (double)bin_slack) + 0.125;
+    return (uint64_t)(per_point * (double)pts) + 128ull * (bricks + 1);
+}
+
+struct BinState {  // what plan_bins reads of the handle: session fields (as of the dry run's read-back, where there was one), a capacity, knobs
+    bool bin, have_hist, from_probe;
+    uint64_t n_bricks_known, n_bricks_before, max_bricks;
+    double prev_points;
+    bool knob_spare;
+    float knob_slack, test_scale;
+};
+struct BinPlan {
+    bool have_plan;      // per-brick bin regions sized from the previous launch's demand; without one nothing is parked (direct forms)
+    uint32_t nb_known;
+    uint32_t spare;      // regions for bricks this launch may discover ...
+    uint32_t spare_cap;  // ... of this many entries each
+    uint32_t nb;         // bricks the per-brick kernels of this call look at
+    uint64_t pool;       // entries for this launch's parked points (+25 % plan slack, +64 per brick)
+    bool too_large;      // ... more than a 32-bit index addresses
+    float scale, slack;  // k_bin_plan: this launch's points over the previous one's; capacity over demand
+};
+inline BinPlan plan_bins(const BinState& s, uint64_t pts)
+{
+    BinPlan p{};
+    p.nb_known = (uint32_t)s.n_bricks_known;
+    p.have_plan = s.bin && s.have_hist && p.nb_known > 0;
+    // Bricks this launch may discover get spare regions of an average brick's size: as many as the session found between its last
+    // two counter read-backs (x2), i.e. half the known bricks right after the dry run and a few hundred in the steady state.
+    if (p.have_plan && s.knob_spare) {
+        const uint64_t grown = s.n_bricks_known - std::min(s.n_bricks_known, s.n_bricks_before);
+        p.spare = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(2 * grown, 256), std::max<uint64_t>(p.nb_known / 2, 256));
+        p.spare = (uint32_t)std::min<uint64_t>(p.spare, s.max_bricks - std::min<uint64_t>(s.max_bricks, p.nb_known));
+    }
+    p.nb = p.nb_known + p.spare;
+    if (s.bin) {
+        p.pool = bin_pool_entries(s.knob_slack, pts, p.nb_known);  // two regions per brick, each sized for the whole brick
+        if (p.spare) {  // an average brick's share of the batch, both regions, within what a 32-bit index still addresses
+            p.spare_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(pts / std::max(1u, p.nb_known), 64), 1u << 15);
+            const uint64_t room = 0xFFFFFFFFull - std::min<uint64_t>(p.pool, 0xFFFFFFFFull);
+            if (2ull * p.spare * p.spare_cap > room) p.spare_cap = (uint32_t)(room / (2ull * p.spare));
+            p.pool += 2ull * p.spare * p.spare_cap;
+        }
+    }
+    p.too_large = p.pool > 0xFFFFFFFFull;
+    p.scale = (float)((double)pts / std::max(1.0, s.prev_points)) * s.test_scale;
+    p.slack = s.from_probe ? std::max(1.5f, s.knob_slack) : s.knob_slack;  // a plan from a sample: more slack per region
+    return p;
+}
+
+// A batch: the next call is probably a clean pass, which starts by reading the counters.
+inline bool is_batch(uint32_t n_frames, bool has_mailbox) { return has_mailbox && n_frames >= 4; }
+
+struct OrderPlan {
+    bool update;  // a clean pass has run: unoccupied cells may carry a dependant.  Without a normal record no cell has dependants: no update kernel
+    // k_buffer ahead of the update kernel (both only read the bins, and they write disjoint tables): everything a clean
+    // pass reads at its head is then final while the update kernel -- the longer of the two by far -- still runs, and an
+    // early publish + ev_ready let the pass begin beside it (clean_locked).  Only where that can happen: a batch on a
+    // single rank with the mailbox; otherwise the order of old.
+    bool buffer_first;
+    bool final_publish;  // the call ends with a publish of the counters
+};
+inline OrderPlan plan_order(unsigned long long c_normals, bool normals_possible, bool clean_overlap, bool has_mailbox, uint32_t n_frames, bool dist_on)
+{
+    OrderPlan o{};
+    o.update = c_normals > 0 || normals_possible;
+    o.final_publish = is_batch(n_frames, has_mailbox);
+    o.buffer_first = o.update && clean_overlap && o.final_publish && !dist_on;
+    return o;
+}
+
+// k_update_cells leaves its dense shape when the items that found no slot in its table exceed one in 500 member pairs of the window
+// since (miss_seen, member_seen).  A member count below member_seen (after a restore) is an empty window.
+inline bool update_shape_goes_wide(unsigned long long miss, unsigned long long member, unsigned long long miss_seen, unsigned long long member_seen)
+{
+    return miss > miss_seen && (miss - miss_seen) * 500ull > member - std::min(member, member_seen);
+}
+
+}  // namespace hfpf

@@ -1,0 +1,26 @@
+"""CPU: what kind of integrate call or clean pass this is (csrc/host_plan.hpp), at the thresholds no device test reaches in seconds.
+tests/host_plan_check.cpp is a program of its own: it includes only that header, is built with the address and undefined-behaviour
+sanitizers (their runtime linked into the executable) and run as an ordinary process in the environment as it is."""
+import os
+import shutil
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "high-fidelity-pointcloud-fusion_amd", "csrc")
+
+
+def test_plans_match_the_values_worked_out_by_hand(tmp_path):
+    cxx = shutil.which("g++")
+    assert cxx, "g++ is part of the build of this package"
+    exe = os.path.join(tmp_path, "host_plan_check")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan",
+                           "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "host_plan_check.cpp")])
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    assert r.returncode == 0 and "host_plan ok" in r.stdout, r.stdout[-4000:]
+
+
+def test_the_header_is_free_of_hip():
+    text = open(os.path.join(CSRC, "host_plan.hpp")).read()
+    assert "hip" not in text.lower().replace("free of hip", "")
+    assert "host_plan.hpp" in open(os.path.join(CSRC, "Makefile")).read()
+    assert "host_plan.hpp" in open(os.path.join(ROOT, "high-fidelity-pointcloud-fusion_amd", "CMakeLists.txt")).read()

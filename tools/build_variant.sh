@@ -13,9 +13,11 @@ if [ "$1" = "--rev" ]; then
   for f in det_math.hpp geometry.hpp tables.hpp stats.hpp kernels.hpp hfpf.hip; do
     git -C $R show $REV:high-fidelity-pointcloud-fusion_amd/csrc/$f > $TMP/high-fidelity-pointcloud-fusion_amd/csrc/$f
   done
-  # (a revision from before the header existed builds without it)
-  git -C $R show $REV:high-fidelity-pointcloud-fusion_amd/csrc/scratch_layout.hpp > $TMP/high-fidelity-pointcloud-fusion_amd/csrc/scratch_layout.hpp 2>/dev/null ||
-    rm -f $TMP/high-fidelity-pointcloud-fusion_amd/csrc/scratch_layout.hpp
+  # (a revision from before one of these headers existed builds without it)
+  for f in scratch_layout.hpp host_plan.hpp; do
+    git -C $R show $REV:high-fidelity-pointcloud-fusion_amd/csrc/$f > $TMP/high-fidelity-pointcloud-fusion_amd/csrc/$f 2>/dev/null ||
+      rm -f $TMP/high-fidelity-pointcloud-fusion_amd/csrc/$f
+  done
   for f in hfpf.h hfpf_probe.h; do git -C $R show $REV:include/$f > $TMP/include/$f; done
   SRC=$TMP/high-fidelity-pointcloud-fusion_amd/csrc
 fi
