@@ -212,6 +212,7 @@ struct Knobs {
     bool test_table_skip = false;    // tests only (HFPF_TEST_TABLE_SKIP=1): Tables::test_table_skip
     bool mailbox = true;             // HFPF_MAILBOX=0: counter read-backs by blit copies + synchronize
     int test_dev_tile = kDevTileDefault;  // tests only (HFPF_TEST_DEV_TILE=8..256): triangles per LDS tile of k_dev_rows
+    int cons_chunk = 0;              // HFPF_CONSISTENCY_CHUNK=1..64: frames per chunk of k_consistency (0: plan_consistency decides); tests
     int stage_threads = 0;           // HFPF_STAGE_THREADS: helpers of the StagePool (default half the process's cores - 1, at most 7; 0 = none)
 };
 
@@ -283,6 +284,7 @@ struct hfpf_handle {
     Knobs knobs;
     bool binned = false;  // two-pass (binned) dependant update (default; HFPF_FLAG_DIRECT_UPDATE switches it off)
     int integrate_grid = 1536;
+    int compute_units = 1;  // of the device (plan_consistency)
     size_t dir_entries = 0;
     uint64_t n_slots = 0;
     uint64_t max_touched = 0;
@@ -349,6 +351,8 @@ struct hfpf_handle {
     DevBuf dev_mesh{bufs}, dev_tri{bufs}, dev_bins{bufs}, dev_pairs{bufs};
     DevBuf align_dev{bufs};  // hfpf_align_mesh*: one iteration's deviation records
     DevBuf cov_bins{bufs};   // hfpf_cover_mesh*: the summary, the 64-bit sample total, the triangles' sample counts and their offsets
+    // hfpf_depth_consistency*: one upload's frames of the host form, the poses, the records / summary / keep marks and their scan
+    DevBuf cons_in{bufs}, cons_pose{bufs}, cons_recs{bufs};
     DevBuf ray_in{bufs}, ray_out{bufs}, ray_map{bufs};  // hfpf_raycast*: a host chunk's rays, a chunk's (or band's) hits, the empty-space maps
     DevBuf snap_stage{bufs}, snap_err{bufs};            // hfpf_snapshot / hfpf_restore: the staging buffer (or one window of it), the range check's error word
     uint64_t bin_pool = 0;           // entries in bin_pt
@@ -603,6 +607,7 @@ Knobs read_knobs()
     const char* ts = getenv("HFPF_TEST_TABLE_SKIP");
     k.test_table_skip = ts && ts[0] == '1';
     if (const char* dt = getenv("HFPF_TEST_DEV_TILE")) k.test_dev_tile = std::max(8, std::min(atoi(dt), kDevTileMax));
+    if (const char* cc = getenv("HFPF_CONSISTENCY_CHUNK")) k.cons_chunk = std::max(1, std::min(atoi(cc), (int)kConsChunkFrames));
     const char* mb = getenv("HFPF_MAILBOX");
     k.mailbox = !mb || mb[0] != '0';
     int cores = (int)std::thread::hardware_concurrency();
@@ -1787,6 +1792,7 @@ int hfpf_create(const hfpf_config* cfg, hfpf_handle** out)
         if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess) cus = prop.multiProcessorCount;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->binned ? k_integrate<true, false, true> : k_integrate<true, false, false>, 256, 0) != hipSuccess) per_cu = 4;
         h->integrate_grid = std::max(1, per_cu) * std::max(1, cus);
+        h->compute_units = std::max(1, cus);
     }
     if ((rc = alloc_tables(h))) return bail(rc);
     {
@@ -3889,6 +3895,209 @@ int hfpf_cover_mesh(hfpf_handle* h, const hfpf_cover_opts* o, const void* verts,
 }
 
 void hfpf_free_coverage(hfpf_tri_coverage* cov) { free(cov); }
+
+// ---- rows that depth frames see through (include/hfpf.h) -------------------------------------------------------------------
+int hfpf_check_consistency_opts(const hfpf_consistency_opts* o)
+{
+    if (!o || o->struct_size != sizeof(hfpf_consistency_opts) || (o->flags & ~HFPF_CONSISTENCY_DROP) || o->reserved != 0) return HFPF_ERR_BAD_ARG;
+    if (o->window < 0 || o->window > 2 || std::isnan(o->min_count)) return HFPF_ERR_BAD_ARG;
+    if (!(std::isfinite(o->z_near) && std::isfinite(o->z_far) && 0.0 < o->z_near && o->z_near < o->z_far)) return HFPF_ERR_BAD_ARG;
+    if (!(std::isfinite(o->tolerance) && o->tolerance > 0.0 && o->tolerance <= 1.0)) return HFPF_ERR_BAD_ARG;
+    if (!(std::isfinite(o->slope) && o->slope >= 0.0 && o->slope <= 1.0)) return HFPF_ERR_BAD_ARG;
+    if (!(std::isfinite(o->min_cos) && o->min_cos >= -1.0 && o->min_cos <= 1.0)) return HFPF_ERR_BAD_ARG;
+    return std::isfinite(o->through_ratio) && o->through_ratio >= 0.0 ? HFPF_OK : HFPF_ERR_BAD_ARG;
+}
+
+constexpr uint32_t kConsMaxFrames = 1u << 20;
+
+// The frames of a call, host or device.
+struct ConsFrames {
+    const void* depth;
+    uint64_t stride;
+    uint32_t n;
+    const double* poses;
+};
+
+// The checks of both forms (HFPF_ERR_BAD_ARG; nothing on the handle changes) and the descriptor as the kernels take it.
+static int consistency_args_locked(hfpf_handle* h, const hfpf_consistency_opts* o, const hfpf_depth_image* desc, const ConsFrames& f, const void* cons,
+                                   const void* n_rows, const void* summary, bool on_device, DepthSpec* ds)
+{
+    if (hfpf_check_consistency_opts(o) != HFPF_OK) return fail(h, HFPF_ERR_BAD_ARG, "depth_consistency: invalid hfpf_consistency_opts");
+    if (!cons || !n_rows || !summary) return fail(h, HFPF_ERR_BAD_ARG, "depth_consistency: NULL cons, n_rows or summary");
+    if (f.n > kConsMaxFrames) return fail(h, HFPF_ERR_BAD_ARG, "depth_consistency: %u frames exceed 2^20", f.n);
+    // the descriptor as hfpf_query_depth checks it; without frames there is no image to be NULL
+    PointSource src{};
+    if (int rc = colorless_depth_source(h, desc, f.n ? f.depth : (const void*)desc, &src)) return rc;
+    *ds = src.ds;
+    if (f.n == 0) return HFPF_OK;
+    if (!f.poses) return fail(h, HFPF_ERR_BAD_ARG, "depth_consistency: NULL poses");
+    for (uint64_t i = 0; i < 12ull * f.n; i++)
+        if (!std::isfinite(f.poses[i])) return fail(h, HFPF_ERR_BAD_ARG, "depth_consistency: pose %llu is not finite", (unsigned long long)(i / 12));
+    const uint32_t dbpp = ds->depth_f32 ? 4u : 2u;
+    if (f.stride < ds->depth_bytes() || f.stride % dbpp)
+        return fail(h, HFPF_ERR_BAD_ARG, "depth_consistency: depth_frame_stride %llu (an image takes %zu bytes, samples %u)", (unsigned long long)f.stride,
+                    ds->depth_bytes(), dbpp);
+    if (on_device && (uintptr_t)f.depth % dbpp) return fail(h, HFPF_ERR_BAD_ARG, "depth_consistency_device: the images must be aligned to the sample size");
+    return HFPF_OK;
+}
+
+// k_consistency over the n frames at `dev` (frame_base = the index of the first in the call; d_pose = its pose), in the launches
+// plan_consistency cuts them into.  plain: this span is the whole call and one chunk covers it.
+static int consistency_span_locked(hfpf_handle* h, const RowSet& rs, ConsParams p, const void* dev, uint32_t n, uint32_t frame_base, const double* d_pose,
+                                   const ConsPlan& plan, bool plain, ConsRec* recs)
+{
+    p.depth = (const uint8_t*)dev;
+    p.n_frames = n;
+    p.per_chunk = plan.frames_per_chunk;
+    p.frame_base = frame_base;
+    p.plain = plain ? 1u : 0u;
+    for (uint32_t c0 = 0; c0 < plan.n_chunks; c0 += plan.chunks_per_launch) {
+        p.chunk0 = c0;
+        const uint32_t nc = std::min(plan.chunks_per_launch, plan.n_chunks - c0);
+        hipLaunchKernelGGL(k_consistency, dim3(blocks_for(rs.n, kConsRowTile), nc), dim3(kConsRowTile), 0, h->stream, rs.rows, (uint32_t)rs.n, d_pose, p, recs);
+        HIPCHK(h, hipGetLastError());
+    }
+    return HFPF_OK;
+}
+
+// Validated arguments in, under the lock, behind the read prologue.  The row set; the records (k_cons_init unless one plain launch
+// writes them whole, k_consistency per span of frames: the device form has one span, the host form one per upload of at most
+// kXferChunk bytes); flags, keep marks and summary (k_cons_finish); with HFPF_CONSISTENCY_DROP the scan of the marks and the
+// compaction.  *out: rows (absent without want_rows) and records.  Not timed: hfpf_get_kernel_time has no id for it.
+static int consistency_locked(hfpf_handle* h, const hfpf_consistency_opts* o, const hfpf_depth_image* desc, const DepthSpec& ds, const ConsFrames& f,
+                              bool on_device, bool want_rows, ResultSet* out, uint64_t* n_out, hfpf_consistency_summary* summary)
+{
+    int rc;
+    *n_out = 0;
+    memset(summary, 0, sizeof *summary);
+    RowSet rs;
+    const ExtractOpts opt{o->min_count, -1, 0};  // the compare of hfpf_extract_filtered, 0 keeps all
+    if ((rc = build_rows_locked(h, h->t.stats, opt, &rs))) return rc;
+    const uint64_t nr = rs.n;
+    if (nr == 0) return HFPF_OK;
+    if (nr >= 0xFFFFFFFFull) return fail(h, HFPF_ERR_CAPACITY, "depth_consistency: %llu rows exceed the 32-bit row index", (unsigned long long)nr);
+    const uint32_t n = (uint32_t)nr;
+    const uint64_t R1 = nr + 1;
+    ConsRec* recs; ConsSummary* d_sum; uint32_t *keep, *base;
+    if ((rc = scratch(h, h->cons_recs, ScratchLayout().add(&recs, nr).add(&d_sum, 1).add(&keep, R1).add(&base, R1)))) return rc;
+    double* d_pose = nullptr;
+    if (f.n) {
+        if ((rc = scratch_n(h, h->cons_pose, 12ull * f.n, &d_pose))) return rc;
+        HIPCHK(h, hipMemcpyAsync(d_pose, f.poses, (size_t)f.n * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    ConsParams p{};
+    p.frame_stride = f.stride;
+    p.width = ds.width, p.height = ds.height, p.depth_step = ds.depth_step, p.depth_f32 = ds.depth_f32;
+    p.gate = o->min_cos >= 0.0 ? 1u : 0u;
+    p.window = o->window;
+    p.unit = ds.unit;
+    p.fx = desc->fx, p.fy = desc->fy, p.cx = desc->cx, p.cy = desc->cy;
+    p.z_near = o->z_near, p.z_far = o->z_far, p.tolerance = o->tolerance, p.slope = o->slope, p.min_cos2 = o->min_cos * o->min_cos;
+    p.through_ratio = o->through_ratio;
+    p.min_through = std::max(1u, o->min_through);
+    p.drop = (o->flags & HFPF_CONSISTENCY_DROP) ? 1u : 0u;
+    // frames per upload of the host form: whole frames, padding between them included, in at most kXferChunk bytes (one at least)
+    const size_t img = ds.depth_bytes();
+    uint32_t per_upload = f.n;
+    if (!on_device && f.n) per_upload = (uint32_t)std::min<uint64_t>(f.n, img <= kXferChunk ? 1 + (kXferChunk - img) / f.stride : 1);
+    const uint32_t forced = (uint32_t)h->knobs.cons_chunk;
+    const bool one_span = per_upload == f.n;
+    const bool plain = f.n && one_span && plan_consistency(nr, f.n, (uint32_t)h->compute_units, forced).single;
+    HIPCHK(h, hipMemsetAsync(d_sum, 0, sizeof(ConsSummary), h->stream));
+    if (!plain) {
+        hipLaunchKernelGGL(k_cons_init, dim3(blocks_for(nr, 256)), dim3(256), 0, h->stream, n, recs);
+        HIPCHK(h, hipGetLastError());
+    }
+    for (uint32_t f0 = 0; f0 < f.n; f0 += per_upload) {
+        const uint32_t nf = std::min(per_upload, f.n - f0);
+        const void* dev = (const uint8_t*)f.depth + (uint64_t)f0 * f.stride;
+        if (!on_device) {
+            const size_t bytes = (size_t)(nf - 1) * f.stride + img;
+            uint8_t* d_in;
+            if ((rc = scratch_n(h, h->cons_in, bytes, &d_in))) return rc;
+            const hipError_t e = upload_pageable(h, d_in, dev, bytes);  // complete on return: the next upload may overwrite it
+            if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "depth_consistency upload: %s", hipGetErrorString(e));
+            dev = d_in;
+        }
+        const ConsPlan plan = plan_consistency(nr, nf, (uint32_t)h->compute_units, forced);
+        if ((rc = consistency_span_locked(h, rs, p, dev, nf, f0, d_pose + 12ull * f0, plan, plain, recs))) return rc;
+        if (!on_device) HIPCHK(h, hipStreamSynchronize(h->stream));  // ... and this span's kernels have read it
+    }
+    hipLaunchKernelGGL(k_cons_finish, dim3(blocks_for(R1, 256)), dim3(256), 0, h->stream, n, p, recs, keep, d_sum);
+    HIPCHK(h, hipGetLastError());
+    uint64_t nk = nr;
+    if (p.drop)
+        if ((rc = scan_counts_locked(h, keep, base, nr, &nk))) return rc;
+    ConsSummary hs;
+    HIPCHK(h, hipMemcpyAsync(&hs, d_sum, sizeof hs, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    static_assert(sizeof(ConsSummary) == sizeof(hfpf_consistency_summary), "the device summary is the public one");
+    memcpy(summary, &hs, sizeof hs);
+    if (nk == 0) return HFPF_OK;
+    ResultSet set;
+    set.add((size_t)nk * sizeof(Row), !want_rows, p.drop ? nullptr : rs.rows);
+    set.add((size_t)nk * sizeof(ConsRec), false, p.drop ? nullptr : recs);
+    if ((rc = result_alloc(h, set, on_device, "depth_consistency"))) return rc;
+    hipError_t e = hipSuccess;
+    if (p.drop) {
+        hipLaunchKernelGGL(k_cons_compact, dim3(blocks_for(nr, 256)), dim3(256), 0, h->stream, rs.rows, n, recs, keep, base, (Row*)set.a[0].dev, (ConsRec*)set.a[1].dev);
+        e = hipGetLastError();
+    } else if (on_device) {  // the borrowed arrays into the caller's
+        if (want_rows) e = hipMemcpyAsync(set.a[0].dev, rs.rows, set.a[0].bytes, hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(set.a[1].dev, recs, set.a[1].bytes, hipMemcpyDeviceToDevice, h->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "depth_consistency: %s", hipGetErrorString(e));
+    set.keep(out), *n_out = nk;
+    return HFPF_OK;
+}
+
+int hfpf_depth_consistency_device(hfpf_handle* h, const hfpf_consistency_opts* o, const hfpf_depth_image* desc, const void* dev_depth,
+                                  uint64_t depth_frame_stride, uint32_t n_frames, const double* poses, hfpf_row** dev_rows,
+                                  hfpf_row_consistency** dev_cons, uint64_t* n_rows, hfpf_consistency_summary* summary)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    const ConsFrames f{dev_depth, depth_frame_stride, n_frames, poses};
+    DepthSpec ds;
+    if (int rc = consistency_args_locked(h, o, desc, f, dev_cons, n_rows, summary, true, &ds)) return rc;
+    if (int rc = local_read_prologue_locked(h, "depth_consistency")) return rc;
+    ResultSet set;
+    uint64_t nk = 0;
+    hfpf_consistency_summary s;
+    if (int rc = consistency_locked(h, o, desc, ds, f, true, dev_rows != nullptr, &set, &nk, &s)) return rc;
+    if (dev_rows) *dev_rows = (hfpf_row*)set.a[0].dev;
+    *dev_cons = (hfpf_row_consistency*)set.a[1].dev, *n_rows = nk, *summary = s;
+    return HFPF_OK;
+}
+
+int hfpf_depth_consistency(hfpf_handle* h, const hfpf_consistency_opts* o, const hfpf_depth_image* desc, const void* depth, uint64_t depth_frame_stride,
+                           uint32_t n_frames, const double* poses, hfpf_row** rows, hfpf_row_consistency** cons, uint64_t* n_rows,
+                           hfpf_consistency_summary* summary)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    const ConsFrames f{depth, depth_frame_stride, n_frames, poses};
+    DepthSpec ds;
+    if (int rc = consistency_args_locked(h, o, desc, f, cons, n_rows, summary, false, &ds)) return rc;
+    if (int rc = local_read_prologue_locked(h, "depth_consistency")) return rc;
+    ResultSet set;
+    uint64_t nk = 0;
+    hfpf_consistency_summary s;
+    if (int rc = consistency_locked(h, o, desc, ds, f, false, rows != nullptr, &set, &nk, &s)) return rc;
+    void* host[3] = {nullptr, nullptr, nullptr};
+    if (nk)
+        if (int rc = result_to_host(h, set, "depth_consistency", host)) return rc;
+    if (rows) *rows = (hfpf_row*)host[0];
+    *cons = (hfpf_row_consistency*)host[1], *n_rows = nk, *summary = s;
+    return HFPF_OK;
+}
+
+void hfpf_free_consistency(hfpf_row* rows, hfpf_row_consistency* cons)
+{
+    free(rows);
+    free(cons);
+}
 
 int hfpf_stats_export(hfpf_handle* h, const void** dev_words, uint64_t* n_words, const void** dev_cwords, uint64_t* n_cwords)
 {

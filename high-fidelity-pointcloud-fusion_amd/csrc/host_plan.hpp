@@ -189,4 +189,35 @@ inline bool update_shape_goes_wide(unsigned long long miss, unsigned long long m
     return miss > miss_seen && (miss - miss_seen) * 500ull > member - std::min(member, member_seen);
 }
 
+// ---- the depth-consistency read-out ----
+
+constexpr uint32_t kConsChunkFrames = 64;       // frames per chunk at most: their poses sit in LDS (6 KB), as a render's views do
+constexpr uint32_t kConsRowTile = 256;          // rows per workgroup of k_consistency
+constexpr uint32_t kConsLaunchChunks = 32768;   // chunks per launch at most (grid.y)
+
+// How k_consistency walks `frames` frames for `rows` rows: chunk c of a span holds frames [c * frames_per_chunk, min(frames,
+// (c + 1) * frames_per_chunk)), and a launch takes chunks_per_launch chunks (the last launch fewer).  A workgroup is one row tile x
+// one chunk.  Few row tiles: shorter chunks, so that tiles x chunks reaches four workgroups per compute unit; many: whole chunks of
+// 64, since every chunk costs a row its atomics.  `forced` (HFPF_CONSISTENCY_CHUNK, 1..64; 0 = none) overrides the chunk length.
+struct ConsPlan {
+    uint32_t frames_per_chunk;   // 1..64 (1 when there are no frames)
+    uint32_t n_chunks;           // ceil(frames / frames_per_chunk)
+    uint32_t chunks_per_launch;  // 1..kConsLaunchChunks
+    bool single;                 // one chunk covers every frame: the records need no atomics
+};
+inline ConsPlan plan_consistency(uint64_t rows, uint32_t frames, uint32_t compute_units, uint32_t forced = 0)
+{
+    ConsPlan p{};
+    const uint64_t tiles = std::max<uint64_t>(1, (rows + kConsRowTile - 1) / kConsRowTile);
+    const uint64_t want_groups = 4ull * std::max(1u, compute_units);
+    const uint64_t want_chunks = std::max<uint64_t>(1, (want_groups + tiles - 1) / tiles);
+    uint64_t per = (frames + want_chunks - 1) / want_chunks;
+    if (forced) per = forced;
+    p.frames_per_chunk = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(per, 1), kConsChunkFrames);
+    p.n_chunks = (frames + p.frames_per_chunk - 1) / p.frames_per_chunk;
+    p.chunks_per_launch = std::min(std::max(p.n_chunks, 1u), kConsLaunchChunks);
+    p.single = p.n_chunks <= 1;
+    return p;
+}
+
 }  // namespace hfpf

@@ -4523,4 +4523,174 @@ __global__ __launch_bounds__(256) void k_cov_finish(const uint32_t n_tris, const
     if (bits) atomicMax(&sum->max_distance_bits, bits);
 }
 
+
+// ---- depth consistency (hfpf_depth_consistency*, include/hfpf.h) ---------------------------------------------------------
+// The inverse of the splat: per (row, frame) one depth pixel (or a window of them) is gathered where k_render_splat scatters a row.
+// The grid is (row tiles) x (frame chunks, plan_consistency in host_plan.hpp); the depth pointer, the frame stride, the
+// intrinsics and the loop over the chunk's frames are wave-uniform, only the pixel address is per lane.
+struct ConsRec {  // = hfpf_row_consistency
+    uint32_t n_in_view, n_tested, n_support, n_through, n_occluded, first_through, flags, reserved;
+};
+static_assert(sizeof(ConsRec) == 32, "a consistency record is 32 bytes");
+struct ConsSummary {  // = hfpf_consistency_summary
+    unsigned long long n_rows, n_seen, n_supported, n_contradicted, n_kept, pairs_tested, pairs_support, pairs_through;
+};
+constexpr uint32_t kConsSeen = 1u, kConsSupported = 2u, kConsContradicted = 4u, kConsNone = 0xFFFFFFFFu;
+
+struct ConsParams {
+    const uint8_t* depth;   // frame 0 of this span
+    uint64_t frame_stride;  // bytes between two frames
+    uint32_t width, height, depth_step, depth_f32;
+    uint32_t n_frames;      // frames of this span
+    uint32_t per_chunk;     // frames per chunk (<= kConsChunkFrames)
+    uint32_t chunk0;        // first chunk of this launch
+    uint32_t frame_base;    // index of the span's frame 0 in the call: what first_through counts from
+    uint32_t plain;         // one launch of one chunk covers the call: plain stores of whole records, no atomics
+    uint32_t gate;          // min_cos >= 0
+    int32_t window;
+    float unit;             // (float)depth_scale
+    double fx, fy, cx, cy, z_near, z_far, tolerance, slope, min_cos2;
+    // what k_cons_finish reads
+    double through_ratio;
+    uint32_t min_through;   // max(1, min_through)
+    uint32_t drop;
+};
+
+// Every record of a call that accumulates with atomics (and of one without frames): zero counters, first_through = none.
+__global__ __launch_bounds__(256) void k_cons_init(const uint32_t n_rows, ConsRec* __restrict__ recs)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_rows) return;
+    uint4* r = reinterpret_cast<uint4*>(&recs[j]);
+    r[0] = make_uint4(0u, 0u, 0u, 0u);
+    r[1] = make_uint4(0u, kConsNone, 0u, 0u);
+}
+
+// One thread per row, looping over its chunk's frames with the five counters and first_through in registers.  `poses`: the span's.
+__global__ __launch_bounds__(256) void k_consistency(const Row* __restrict__ rows, const uint32_t n_rows, const double* __restrict__ poses,
+                                                     const ConsParams p, ConsRec* __restrict__ recs)
+{
+    __shared__ double s_pose[kConsChunkFrames * 12];
+    const uint32_t f0 = (p.chunk0 + blockIdx.y) * p.per_chunk;  // < p.n_frames: the host launches no empty chunk
+    const uint32_t nf = min(p.per_chunk, p.n_frames - f0);
+    for (uint32_t i = threadIdx.x; i < nf * 12u; i += blockDim.x) s_pose[i] = poses[12ull * f0 + i];
+    __syncthreads();
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_rows) return;
+    const float4 q0 = *reinterpret_cast<const float4*>(&rows[j].x);   // x, y, z, nx
+    const float2 q1 = *reinterpret_cast<const float2*>(&rows[j].ny);  // ny, nz
+    const double x = q0.x, y = q0.y, z = q0.z, nx = q0.w, ny = q1.x, nz = q1.y;
+    uint32_t n_in_view = 0, n_tested = 0, n_support = 0, n_through = 0, n_occluded = 0, first_through = kConsNone;
+    const int W = (int)p.width, H = (int)p.height, win = p.window;
+    for (uint32_t f = 0; f < nf; f++) {
+        const double* T = &s_pose[12 * f];
+        const double dx = x - T[3], dy = y - T[7], dz = z - T[11];
+        const double zc = (T[2] * dx + T[6] * dy) + T[10] * dz;
+        if (!(p.z_near < zc && zc < p.z_far)) continue;
+        const double xc = (T[0] * dx + T[4] * dy) + T[8] * dz;
+        const double yc = (T[1] * dx + T[5] * dy) + T[9] * dz;
+        const double u = (xc / zc) * p.fx + p.cx;
+        const double w = (yc / zc) * p.fy + p.cy;
+        if (!(fabs(u) < 1073741824.0 && fabs(w) < 1073741824.0)) continue;
+        const int pu = (int)floor(u + 0.5), pv = (int)floor(w + 0.5);
+        if (pu < 0 || pu >= W || pv < 0 || pv >= H) continue;
+        n_in_view++;
+        if (p.gate) {
+            const double c = -((nx * dx + ny * dy) + nz * dz), d2 = (dx * dx + dy * dy) + dz * dz;
+            if (!(c > 0.0 && c * c >= p.min_cos2 * d2)) continue;
+        }
+        n_tested++;
+        const double tol = p.tolerance + p.slope * zc;
+        const uint8_t* img = p.depth + (uint64_t)(f0 + f) * p.frame_stride;  // wave-uniform
+        const int x0 = max(pu - win, 0), x1 = min(pu + win, W - 1), y0 = max(pv - win, 0), y1 = min(pv + win, H - 1);
+        bool support = false, any = false, occluded = false;
+        for (int py = y0; py <= y1 && !support; py++) {
+            const uint8_t* line = img + (uint64_t)py * p.depth_step;
+            for (int px = x0; px <= x1; px++) {
+                double zd;
+                if (p.depth_f32) {
+                    const float d = reinterpret_cast<const float*>(line)[px];
+                    if (!__builtin_isfinite(d)) continue;
+                    zd = (double)d;
+                } else {
+                    const uint16_t d = reinterpret_cast<const uint16_t*>(line)[px];
+                    if (d == 0) continue;
+                    zd = (double)((float)d * p.unit);
+                }
+                const double g = zd - zc;
+                if (fabs(g) <= tol) {  // rule 1 wins whatever else the window holds: leaving here is exact
+                    support = true;
+                    break;
+                }
+                any = true;
+                occluded = occluded || g < -tol;
+            }
+        }
+        if (support) {
+            n_support++;
+        } else if (any) {
+            if (occluded) {
+                n_occluded++;
+            } else {
+                n_through++;
+                first_through = min(first_through, p.frame_base + f0 + f);
+            }
+        }
+    }
+    ConsRec* r = &recs[j];
+    if (p.plain) {
+        uint4* o = reinterpret_cast<uint4*>(r);
+        o[0] = make_uint4(n_in_view, n_tested, n_support, n_through);
+        o[1] = make_uint4(n_occluded, first_through, 0u, 0u);
+        return;
+    }
+    if (n_in_view) atomicAdd(&r->n_in_view, n_in_view);
+    if (n_tested) atomicAdd(&r->n_tested, n_tested);
+    if (n_support) atomicAdd(&r->n_support, n_support);
+    if (n_through) atomicAdd(&r->n_through, n_through);
+    if (n_occluded) atomicAdd(&r->n_occluded, n_occluded);
+    if (first_through != kConsNone) atomicMin(&r->first_through, first_through);
+}
+
+// One thread per row (n_rows + 1 entries of keep, the last one 0 for the scan): the record's flags, the keep mark, and the row's
+// share of the summary, reduced per wave, then u64 adds.
+__global__ __launch_bounds__(256) void k_cons_finish(const uint32_t n_rows, const ConsParams p, ConsRec* __restrict__ recs, uint32_t* __restrict__ keep,
+                                                     ConsSummary* __restrict__ sum)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    unsigned long long w[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the summary's words in order
+    if (j < n_rows) {
+        const ConsRec r = recs[j];
+        const bool contra = r.n_through >= p.min_through && (double)r.n_through > p.through_ratio * (double)r.n_support;
+        const uint32_t flags = (r.n_tested ? kConsSeen : 0u) | (r.n_support ? kConsSupported : 0u) | (contra ? kConsContradicted : 0u);
+        recs[j].flags = flags;
+        keep[j] = (p.drop && contra) ? 0u : 1u;
+        w[0] = 1, w[1] = r.n_tested ? 1 : 0, w[2] = r.n_support ? 1 : 0, w[3] = contra ? 1 : 0, w[4] = contra ? 0 : 1;
+        w[5] = r.n_tested, w[6] = r.n_support, w[7] = r.n_through;
+    } else if (j == n_rows) {
+        keep[j] = 0u;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) w[i] += __shfl_down(w[i], o);
+    }
+    if ((threadIdx.x & 63u) != 0) return;
+    unsigned long long* out = &sum->n_rows;
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+        if (w[i]) atomicAdd(&out[i], w[i]);
+}
+
+// HFPF_CONSISTENCY_DROP: kept rows (out_rows may be null) and their records at base[j], the scan of keep.
+__global__ __launch_bounds__(256) void k_cons_compact(const Row* __restrict__ rows, const uint32_t n_rows, const ConsRec* __restrict__ recs,
+                                                      const uint32_t* __restrict__ keep, const uint32_t* __restrict__ base,
+                                                      Row* __restrict__ out_rows, ConsRec* __restrict__ out_recs)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_rows || !keep[j]) return;
+    const uint32_t o = base[j];
+    if (out_rows) out_rows[o] = rows[j];
+    out_recs[o] = recs[j];
+}
+
 }  // namespace hfpf

@@ -44,6 +44,13 @@ struct hfpf_node {
     hfpf_align_opts align_opts{};
     bool cover_on = false;              // hfpf_node_set_reference_coverage: ~process also writes coverage.csv and coverage_summary.csv
     hfpf_cover_opts cover_opts{};
+    bool cons_on = false;               // hfpf_node_set_depth_consistency: ~process also writes consistency.csv and consistency_summary.csv
+    hfpf_consistency_opts cons_opts{};
+    uint32_t cons_keep = 0;             // depth images the ring holds at most
+    std::mutex cons_mtx;                // the ring below: the depth callback fills it, ~process reads it
+    hfpf_depth_image cons_desc{};       // descriptor of the images in the ring
+    std::vector<std::vector<uint8_t>> cons_frames;  // host copies of the last integrated depth images, oldest first
+    std::vector<double> cons_poses;     // 12 per image
     void* publish_user = nullptr;
     std::thread clean_thread;
     std::mutex cv_mtx;
@@ -186,6 +193,32 @@ int hfpf_node_on_point_cloud(hfpf_node* n, const hfpf_cloud_msg* msg)
     return 1;
 }
 
+static void forget_depth(hfpf_node* n)
+{
+    std::lock_guard<std::mutex> lk(n->cons_mtx);
+    n->cons_frames.clear();
+    n->cons_poses.clear();
+}
+
+// The ring of hfpf_node_set_depth_consistency: a host copy of a depth image the engine has just taken (so its descriptor is valid)
+// and its pose.  An image of another descriptor empties the ring first: one call compares frames of one descriptor.
+static void remember_depth(hfpf_node* n, const hfpf_depth_msg* msg, const double pose[12])
+{
+    std::lock_guard<std::mutex> lk(n->cons_mtx);
+    if (!n->cons_on || n->cons_keep == 0) return;
+    const hfpf_depth_image& d = msg->image;
+    if (!n->cons_frames.empty() && memcmp(&n->cons_desc, &d, sizeof d) != 0) n->cons_frames.clear(), n->cons_poses.clear();
+    n->cons_desc = d;
+    const size_t bytes = (size_t)(d.height - 1) * d.depth_step + (size_t)d.width * (d.depth_format == HFPF_DEPTH_F32 ? 4u : 2u);
+    if (n->cons_frames.size() >= n->cons_keep) {
+        n->cons_frames.erase(n->cons_frames.begin());
+        n->cons_poses.erase(n->cons_poses.begin(), n->cons_poses.begin() + 12);
+    }
+    const uint8_t* src = (const uint8_t*)msg->depth;
+    n->cons_frames.emplace_back(src, src + bytes);
+    n->cons_poses.insert(n->cons_poses.end(), pose, pose + 12);
+}
+
 int hfpf_node_on_depth_image(hfpf_node* n, const hfpf_depth_msg* msg)
 {
     if (!n || !msg) return HFPF_ERR_BAD_ARG;
@@ -194,6 +227,7 @@ int hfpf_node_on_depth_image(hfpf_node* n, const hfpf_depth_msg* msg)
     int rc = hfpf_integrate_depth(n->grid, &msg->image, msg->depth, msg->color, pose);
     if (rc != HFPF_OK) return nfail(n, rc, hfpf_last_error(n->grid));
     n->integrated++;
+    remember_depth(n, msg, pose);
     return 1;
 }
 
@@ -218,6 +252,7 @@ int hfpf_node_reset(hfpf_node* n, hfpf_trigger_response* res)
     if (!n) return HFPF_ERR_BAD_ARG;
     n->start_ = false;                       // node.cpp:354
     n->cloud_subscription_started_ = false;  // node.cpp:357 (clouds_.clear(): no queue here; the grid is NOT touched)
+    forget_depth(n);
     set_res(res, true, "");
     return HFPF_OK;
 }
@@ -344,6 +379,87 @@ static int write_coverage(hfpf_node* n, const double pose[12])
     return rc;
 }
 
+// consistency.csv and consistency_summary.csv beside the cloud: hfpf_depth_consistency of the depth images in the ring, one line per
+// saved row.  Built like the deviation files: the call runs on the full row set (with the component filter's min_count when one is
+// set, and never with HFPF_CONSISTENCY_DROP: this is a report), one walk selects the saved rows' records, and under a filter the
+// summary is rebuilt from the selected records as include/hfpf.h defines it.
+static int write_consistency(hfpf_node* n, const hfpf_row* saved, uint64_t n_saved)
+{
+    hfpf_consistency_opts o;
+    hfpf_depth_image desc;
+    std::vector<uint8_t> frames;
+    std::vector<double> poses;
+    uint64_t stride = 0;
+    uint32_t n_frames = 0;
+    {
+        std::lock_guard<std::mutex> lk(n->cons_mtx);
+        o = n->cons_opts;
+        desc = n->cons_desc;
+        poses = n->cons_poses;
+        n_frames = (uint32_t)n->cons_frames.size();
+        stride = n_frames ? n->cons_frames[0].size() : 0;  // a whole number of samples: depth_step is one
+        frames.resize((size_t)stride * n_frames);
+        for (uint32_t f = 0; f < n_frames; f++) memcpy(frames.data() + (size_t)f * stride, n->cons_frames[f].data(), stride);
+    }
+    o.flags &= ~HFPF_CONSISTENCY_DROP;
+    if (n->comp_on) o.min_count = n->comp_opts.min_count;
+    if (n_frames == 0) {  // nothing seen yet: any valid descriptor serves a call without frames
+        memset(&desc, 0, sizeof desc);
+        desc.struct_size = sizeof desc;
+        desc.width = desc.height = 1, desc.depth_format = HFPF_DEPTH_U16, desc.depth_step = 2, desc.depth_scale = 0.001f;
+        desc.fx = desc.fy = 1.0;
+    }
+    hfpf_row* all = nullptr;
+    hfpf_row_consistency* cons = nullptr;
+    uint64_t n_all = 0;
+    hfpf_consistency_summary s;
+    int rc = hfpf_depth_consistency(n->grid, &o, &desc, frames.data(), stride, n_frames, poses.data(), n->comp_on ? &all : nullptr, &cons, &n_all, &s);
+    if (rc != HFPF_OK) return rc;
+    FILE* f = fopen((n->directory_name + "/consistency.csv").c_str(), "w");
+    if (!f) rc = HFPF_ERR_IO;
+    if (f) {
+        fprintf(f, "ix,iy,iz,n_in_view,n_tested,n_support,n_through,n_occluded,first_through,flags\n");
+        if (n->comp_on) memset(&s, 0, sizeof s);
+        uint64_t j = 0;
+        for (uint64_t i = 0; i < n_saved && rc == HFPF_OK; i++) {
+            const hfpf_row& r = saved[i];
+            if (n->comp_on)
+                while (j < n_all && (all[j].ix != r.ix || all[j].iy != r.iy || all[j].iz != r.iz)) j++;
+            else j = i;
+            if (j >= n_all) {
+                rc = HFPF_ERR_STATE;  // cannot happen: both row sets come from one state of the grid
+                break;
+            }
+            const hfpf_row_consistency& c = cons[j];
+            fprintf(f, "%d,%d,%d,%u,%u,%u,%u,%u,%u,%u\n", r.ix, r.iy, r.iz, c.n_in_view, c.n_tested, c.n_support, c.n_through, c.n_occluded, c.first_through,
+                    c.flags);
+            if (n->comp_on) {
+                s.n_rows++;
+                s.n_seen += (c.flags & HFPF_CONS_SEEN) ? 1 : 0;
+                s.n_supported += (c.flags & HFPF_CONS_SUPPORTED) ? 1 : 0;
+                s.n_contradicted += (c.flags & HFPF_CONS_CONTRADICTED) ? 1 : 0;
+                s.pairs_tested += c.n_tested, s.pairs_support += c.n_support, s.pairs_through += c.n_through;
+            }
+        }
+        if (n->comp_on) s.n_kept = s.n_rows - s.n_contradicted;
+        const bool ok = !ferror(f);
+        if (fclose(f) != 0 || !ok) rc = rc == HFPF_OK ? HFPF_ERR_IO : rc;
+    }
+    if (rc == HFPF_OK) {
+        f = fopen((n->directory_name + "/consistency_summary.csv").c_str(), "w");
+        if (!f) rc = HFPF_ERR_IO;
+        else {
+            fprintf(f, "n_rows,n_seen,n_supported,n_contradicted,n_kept,pairs_tested,pairs_support,pairs_through\n%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu\n",
+                    (unsigned long long)s.n_rows, (unsigned long long)s.n_seen, (unsigned long long)s.n_supported, (unsigned long long)s.n_contradicted,
+                    (unsigned long long)s.n_kept, (unsigned long long)s.pairs_tested, (unsigned long long)s.pairs_support, (unsigned long long)s.pairs_through);
+            const bool ok = !ferror(f);
+            if (fclose(f) != 0 || !ok) rc = HFPF_ERR_IO;
+        }
+    }
+    hfpf_free_consistency(all, cons);
+    return rc;
+}
+
 int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
 {
     if (!n) return HFPF_ERR_BAD_ARG;
@@ -372,6 +488,7 @@ int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
     double ref_pose[12];
     if (rc == HFPF_OK && n->ref_on) rc = write_deviation(n, rows, nr, ref_pose);  // EXTENSION: the saved cloud measured against the reference mesh
     if (rc == HFPF_OK && n->ref_on && n->cover_on) rc = write_coverage(n, ref_pose);  // EXTENSION: ... and how much of that mesh the model covers
+    if (rc == HFPF_OK && n->cons_on) rc = write_consistency(n, rows, nr);  // EXTENSION: what the last depth images say about every saved row
     if (n->comp_on) hfpf_free_components(rows, labels, comps);
     else hfpf_free_rows(rows);
     if (rc == HFPF_OK && n->mesh_on) {  // EXTENSION: a triangle mesh of the same model next to the cloud
@@ -431,6 +548,7 @@ int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
         set_res(res, false, hfpf_last_error(n->grid));
         return nfail(n, rc, hfpf_last_error(n->grid));
     }
+    forget_depth(n);  // the images in the ring belong to the session that was just saved and cleared
     char m[200];
     snprintf(m, sizeof m, "saved %llu points", (unsigned long long)nr);
     set_res(res, true, std::string(m) + " to " + cloud_location);
@@ -505,6 +623,22 @@ int hfpf_node_set_reference_coverage(hfpf_node* n, const hfpf_cover_opts* opts)
     return HFPF_OK;
 }
 
+int hfpf_node_set_depth_consistency(hfpf_node* n, const hfpf_consistency_opts* opts, uint32_t keep_frames)
+{
+    if (!n) return HFPF_ERR_BAD_ARG;
+    if (opts && (hfpf_check_consistency_opts(opts) != HFPF_OK || keep_frames < 1 || keep_frames > 4096))
+        return nfail(n, HFPF_ERR_BAD_ARG, "hfpf_node_set_depth_consistency: invalid hfpf_consistency_opts, or keep_frames outside 1..4096");
+    std::lock_guard<std::mutex> lk(n->cons_mtx);
+    if (opts) n->cons_opts = *opts, n->cons_keep = keep_frames;
+    n->cons_on = opts != nullptr;
+    if (!opts) n->cons_frames.clear(), n->cons_poses.clear();
+    while (n->cons_frames.size() > n->cons_keep) {  // a smaller ring keeps the newest
+        n->cons_frames.erase(n->cons_frames.begin());
+        n->cons_poses.erase(n->cons_poses.begin(), n->cons_poses.begin() + 12);
+    }
+    return HFPF_OK;
+}
+
 int hfpf_node_save_session(hfpf_node* n, const char* path)
 {
     if (!n || !path) return HFPF_ERR_BAD_ARG;
@@ -516,6 +650,7 @@ int hfpf_node_load_session(hfpf_node* n, const char* path)
 {
     if (!n || !path) return HFPF_ERR_BAD_ARG;
     const int rc = hfpf_load(n->grid, path);  // start_ / cloud_subscription_started_ and the node's counters stay as they are
+    forget_depth(n);                          // the images in the ring were not fused into the loaded session (nor into what a failed load leaves)
     return rc == HFPF_OK ? rc : nfail(n, rc, hfpf_last_error(n->grid));
 }
 

@@ -96,6 +96,7 @@ EXPORTS = [
     "hfpf_check_deviation_opts", "hfpf_compare_mesh", "hfpf_compare_mesh_device", "hfpf_free_deviation", "hfpf_read_ply",
     "hfpf_check_align_opts", "hfpf_align_mesh", "hfpf_align_mesh_device",
     "hfpf_check_cover_opts", "hfpf_cover_mesh", "hfpf_cover_mesh_device", "hfpf_free_coverage",
+    "hfpf_check_consistency_opts", "hfpf_depth_consistency", "hfpf_depth_consistency_device", "hfpf_free_consistency",
     "hfpf_check_raycast_opts", "hfpf_raycast", "hfpf_raycast_device", "hfpf_raycast_view", "hfpf_raycast_view_device",
     "hfpf_snapshot", "hfpf_free_snapshot", "hfpf_restore", "hfpf_save", "hfpf_load", "hfpf_snapshot_info", "hfpf_config_from_snapshot",
 ]
@@ -420,6 +421,50 @@ def check_cover_opts(o):
     return lib().hfpf_check_cover_opts(C.byref(o) if o is not None else None)
 
 
+# hfpf_consistency_opts.flags, hfpf_row_consistency.flags and hfpf_row_consistency (include/hfpf.h)
+CONSISTENCY_DROP = 1
+CONS_SEEN, CONS_SUPPORTED, CONS_CONTRADICTED = 1, 2, 4
+CONS_NONE = 0xFFFFFFFF  # first_through of a row no frame sees through
+ROW_CONSISTENCY_DTYPE = np.dtype([(k, "<u4") for k in ("n_in_view", "n_tested", "n_support", "n_through", "n_occluded", "first_through",
+                                                       "flags", "reserved")])
+assert ROW_CONSISTENCY_DTYPE.itemsize == 32
+
+
+class ConsistencyOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("window", C.c_int32), ("min_through", C.c_uint32),
+                ("min_count", C.c_double), ("z_near", C.c_double), ("z_far", C.c_double), ("tolerance", C.c_double), ("slope", C.c_double),
+                ("min_cos", C.c_double), ("through_ratio", C.c_double), ("reserved", C.c_uint64)]
+
+
+class ConsistencySummary(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_rows", "n_seen", "n_supported", "n_contradicted", "n_kept", "pairs_tested", "pairs_support",
+                                          "pairs_through")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+assert C.sizeof(ConsistencyOpts) == 80 and C.sizeof(ConsistencySummary) == 64
+
+
+def consistency_opts(window=0, min_through=1, min_count=0.0, z_range=(0.01, 100.0), tolerance=0.004, slope=0.0, min_cos=0.3,
+                     through_ratio=1.0, drop=False):
+    """An hfpf_consistency_opts: the pixel window's half-width, the THROUGH frames a contradiction needs and their ratio to the SUPPORT
+    frames, the count gate, the depth range, tol = tolerance + slope * zc (metres), and the facing gate (below 0 = off)."""
+    o = ConsistencyOpts()
+    o.struct_size = C.sizeof(ConsistencyOpts)
+    o.flags = CONSISTENCY_DROP if drop else 0
+    o.window, o.min_through = int(window), int(min_through)
+    o.min_count, o.z_near, o.z_far = float(min_count), float(z_range[0]), float(z_range[1])
+    o.tolerance, o.slope, o.min_cos, o.through_ratio = float(tolerance), float(slope), float(min_cos), float(through_ratio)
+    return o
+
+
+def check_consistency_opts(o):
+    """hfpf_check_consistency_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
+    return lib().hfpf_check_consistency_opts(C.byref(o) if o is not None else None)
+
+
 def read_ply(path):
     """hfpf_read_ply: (vertices of MESH_VERTEX_DTYPE, (n, 3) uint32 triangles) of a binary little-endian PLY (host code, no GPU
     needed); HfpfError with the reader's message otherwise."""
@@ -667,6 +712,12 @@ def lib():
     L.hfpf_free_coverage.restype = None
     L.hfpf_free_deviation.argtypes = [vp, vp]
     L.hfpf_free_deviation.restype = None
+    L.hfpf_check_consistency_opts.argtypes = [C.POINTER(ConsistencyOpts)]
+    for fn in (L.hfpf_depth_consistency, L.hfpf_depth_consistency_device):
+        fn.argtypes = [vp, C.POINTER(ConsistencyOpts), C.POINTER(DepthImage), vp, u64, u32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64),
+                       C.POINTER(ConsistencySummary)]
+    L.hfpf_free_consistency.argtypes = [vp, vp]
+    L.hfpf_free_consistency.restype = None
     L.hfpf_read_ply.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64)]
     dbl = C.c_double
     L.hfpf_check_raycast_opts.argtypes = [C.POINTER(RaycastOpts)]
@@ -1134,6 +1185,51 @@ class OccupancyGrid:
         finally:
             lib().hfpf_free_coverage(c)
         return cov, s.as_dict()
+
+    # -- rows that depth frames see through --
+    def depth_consistency(self, frames, poses, K, depth_scale=0.001, opts=None, rows=True, desc=None, depth_frame_stride=None, n_frames=None,
+                          **kw):
+        """What depth frames in pageable memory say about every row (hfpf_depth_consistency): (rows of ROW_DTYPE or None with
+        rows=False, cons of ROW_CONSISTENCY_DTYPE, summary dict).  frames: an (n, H, W) uint16 or float32 array (rows and frames may be
+        padded: a view of a larger array); poses: n 3x4 [R|t], camera -> fusion frame.  Keywords as consistency_opts().  desc,
+        depth_frame_stride and n_frames override what the array's shape and strides give (frames is then any buffer)."""
+        o = opts if opts is not None else consistency_opts(**kw)
+        frames = np.asarray(frames)
+        if desc is None:
+            if frames.ndim != 3:
+                raise ValueError("frames must be an (n, H, W) array")
+            d = _image_desc(frames[0] if len(frames) else np.zeros(frames.shape[1:], frames.dtype), K, None, None, depth_scale)
+            n = len(frames)
+            stride = frames.strides[0] if n else d.depth_step * d.height
+        else:
+            d, n, stride = desc, int(n_frames), int(depth_frame_stride)
+        n = int(n_frames) if n_frames is not None else n
+        stride = int(depth_frame_stride) if depth_frame_stride is not None else stride
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1)
+        r, c, nr, s = C.c_void_p(), C.c_void_p(), C.c_uint64(), ConsistencySummary()
+        self._chk(lib().hfpf_depth_consistency(self._h, C.byref(o), C.byref(d), C.c_void_p(frames.ctypes.data) if frames.size else None, stride, n,
+                                               _p(poses) if poses.size else None, C.byref(r) if rows else None, C.byref(c), C.byref(nr), C.byref(s)))
+        try:
+            out = np.empty(nr.value, ROW_DTYPE) if rows else None
+            cons = np.empty(nr.value, ROW_CONSISTENCY_DTYPE)
+            if nr.value:
+                if rows:
+                    C.memmove(out.ctypes.data, r.value, out.nbytes)
+                C.memmove(cons.ctypes.data, c.value, cons.nbytes)
+        finally:
+            lib().hfpf_free_consistency(r, c)
+        return out, cons, s.as_dict()
+
+    def depth_consistency_device(self, desc, dev_depth, depth_frame_stride, n_frames, poses, opts=None, rows=True, **kw):
+        """The same for frames resident in HBM (hfpf_depth_consistency_device): (rows pointer or 0, cons pointer, n_rows, summary
+        dict); free the pointers with device_free (they are 0 without rows)."""
+        o = opts if opts is not None else consistency_opts(**kw)
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1)
+        r, c, nr, s = C.c_void_p(), C.c_void_p(), C.c_uint64(), ConsistencySummary()
+        self._chk(lib().hfpf_depth_consistency_device(self._h, C.byref(o), C.byref(desc), C.c_void_p(dev_depth), int(depth_frame_stride), int(n_frames),
+                                                      _p(poses) if poses.size else None, C.byref(r) if rows else None, C.byref(c), C.byref(nr),
+                                                      C.byref(s)))
+        return r.value or 0, c.value or 0, nr.value, s.as_dict()
 
     # -- casting rays against the model --
     def raycast(self, rays, pose, opts=None, **kw):

@@ -17,7 +17,8 @@ EXPORTS = ["hfpf_node_default_params", "hfpf_node_create", "hfpf_node_destroy", 
            "hfpf_node_start", "hfpf_node_stop", "hfpf_node_reset", "hfpf_node_process", "hfpf_node_clean_now", "hfpf_node_grid",
            "hfpf_node_get_stats", "hfpf_node_set_publisher", "hfpf_node_on_depth_image",
            "hfpf_node_set_mesh_output", "hfpf_node_save_session", "hfpf_node_load_session", "hfpf_node_set_component_filter",
-           "hfpf_node_set_reference_mesh", "hfpf_node_set_reference_alignment", "hfpf_node_set_reference_coverage"]
+           "hfpf_node_set_reference_mesh", "hfpf_node_set_reference_alignment", "hfpf_node_set_reference_coverage",
+           "hfpf_node_set_depth_consistency"]
 
 
 class Params(C.Structure):
@@ -71,6 +72,7 @@ def lib():
                                                    C.c_uint64, C.c_void_p]
         L.hfpf_node_set_reference_alignment.argtypes = [C.c_void_p, C.POINTER(hfpf.AlignOpts)]
         L.hfpf_node_set_reference_coverage.argtypes = [C.c_void_p, C.POINTER(hfpf.CoverOpts)]
+        L.hfpf_node_set_depth_consistency.argtypes = [C.c_void_p, C.POINTER(hfpf.ConsistencyOpts), C.c_uint32]
         L.hfpf_node_save_session.argtypes = [C.c_void_p, C.c_char_p]
         L.hfpf_node_load_session.argtypes = [C.c_void_p, C.c_char_p]
         _lib = L
@@ -227,6 +229,15 @@ class FusionNode:
         its keywords) at the pose the deviation files use; set_reference_coverage(None) with no keywords turns it off."""
         o = opts if opts is not None else (hfpf.cover_opts(**kw) if kw else None)
         rc = lib().hfpf_node_set_reference_coverage(self._h, C.byref(o) if o is not None else None)
+        if rc < 0:
+            raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
+
+    def set_depth_consistency(self, opts=None, keep_frames=64, **kw):
+        """~process also writes consistency.csv and consistency_summary.csv: hfpf_depth_consistency (these hfpf.consistency_opts, or
+        its keywords) of the last keep_frames depth images the node integrated; set_depth_consistency(None) with no keywords turns it
+        off."""
+        o = opts if opts is not None else (hfpf.consistency_opts(**kw) if kw else None)
+        rc = lib().hfpf_node_set_depth_consistency(self._h, C.byref(o) if o is not None else None, int(keep_frames))
         if rc < 0:
             raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
 

@@ -1042,6 +1042,111 @@ int hfpf_cover_mesh_device(hfpf_handle* h, const hfpf_cover_opts* o, const void*
                            const uint32_t* dev_tris, uint64_t n_tris, const double* pose_3x4, hfpf_tri_coverage** dev_cov,
                            hfpf_coverage_summary* summary);
 
+/* ---- rows that later depth frames see through (the inverse of hfpf_render; no reference counterpart) ----------------------------
+ * An occupancy grid keeps a voxel that was occupied once: a hand that crossed the view, a part that was moved, a slab of flying
+ * pixels that passed the gate.  min_count cannot drop them when they were seen for many frames, hfpf_extract_components cannot when
+ * they touch the surface.  What tells them apart is that depth frames look straight through them: this read-out gathers, per
+ * (row, frame), the depth pixel the row projects onto and counts what it says.  Everything is restatable from
+ * hfpf_extract_filtered's rows (tests/consistency_ref.py).
+ * Arithmetic: everything below is f64, one rounding per operation, left to right, never contracted, unless stated otherwise.
+ * Row set: the rows hfpf_extract_filtered would return at this point of the call sequence with the same min_count (0 keeps all), in
+ *   lexicographic (ix, iy, iz) order; host frames still waiting are launched first.  Row j has f32 (x, y, z) and normal (nx, ny, nz),
+ *   widened to f64.
+ * Frames: n_frames depth images of ONE descriptor desc, frame f's image f * depth_frame_stride bytes behind `depth`; poses holds
+ *   n_frames * 12 f64, row-major [R|t], camera -> fusion frame (the integrate convention).  desc is checked exactly as hfpf_query_depth
+ *   checks it (colour fields included; no colour image is read).
+ * Projection of row j into frame f, T = pose f (the lines of the render contract):
+ *   dx = (double)x - T[3], dy = (double)y - T[7], dz = (double)z - T[11]
+ *   xc = (T[0]*dx + T[4]*dy) + T[8]*dz,  yc = (T[1]*dx + T[5]*dy) + T[9]*dz,  zc = (T[2]*dx + T[6]*dy) + T[10]*dz
+ *   u = (xc / zc) * fx + cx,  v = (yc / zc) * fy + cy;  pu = floor(u + 0.5), pv = floor(v + 0.5)
+ *   IN_VIEW iff z_near < zc < z_far, |u| < 2^30 and |v| < 2^30, 0 <= pu < width and 0 <= pv < height.
+ * Facing gate: c = -((nx*dx + ny*dy) + nz*dz), d2 = (dx*dx + dy*dy) + dz*dz.  With min_cos >= 0 an IN_VIEW row is TESTED iff
+ *   c > 0 && c*c >= (min_cos*min_cos) * d2 (no square root); with min_cos < 0 the gate is off and every IN_VIEW row is TESTED.
+ * Depth sample of pixel (px, py) of frame f: HFPF_DEPTH_U16: count d, valid iff d != 0, zd = (double)((float)d * unit) with
+ *   unit = (float)depth_scale (the f32 product of the depth-frame contract); HFPF_DEPTH_F32: valid iff isfinite(d), zd = (double)d.
+ *   Nothing behind (height - 1) * depth_step + width * sample size of a frame is read.
+ * Class of a TESTED (row, frame): tol = tolerance + slope * zc; over the valid pixels (pu + i, pv + j), |i|, |j| <= window, inside
+ *   the image, with g = zd - zc, the first rule that matches:
+ *     1. SUPPORT   iff some fabs(g) <= tol
+ *     2. NO_DEPTH  iff there is no valid pixel
+ *     3. OCCLUDED  iff some g < -tol
+ *     4. THROUGH   otherwise: every valid pixel lies more than tol behind the row.
+ *   The class does not depend on the order the window is visited in.
+ * Per row: n_in_view, n_tested, n_support, n_through, n_occluded count frames; first_through = the smallest frame index classed
+ *   THROUGH (0xFFFFFFFF: none).  A row is CONTRADICTED iff n_through >= max(1, min_through) and
+ *   (double)n_through > through_ratio * (double)n_support.
+ * Output: without HFPF_CONSISTENCY_DROP every row of the row set and its record; with it only the rows that are not CONTRADICTED
+ *   and their records, order kept.  Rows are byte-identical to hfpf_extract_filtered's.  summary always describes the whole row set;
+ *   n_kept = n_rows - n_contradicted.  Everything is an integer sum or a minimum: nothing depends on scheduling, nor on how the
+ *   frames are split into launches or uploads (HFPF_CONSISTENCY_CHUNK=1..64 forces the frames per chunk; tests).
+ * A call changes nothing on the handle except device_bytes (its scratch: 32 bytes and two words per row, the poses and, for the host
+ * form, one upload's frames and the output).  Rejected with HFPF_ERR_BAD_ARG (the handle stays usable, nothing is written):
+ * struct_size != sizeof, unknown flags, reserved != 0, window outside 0..2, min_count NaN, not 0 < z_near < z_far with both finite,
+ * tolerance not finite or outside (0, 1], slope not finite or outside [0, 1], min_cos not finite or outside [-1, 1], through_ratio
+ * not finite or below 0, every check of hfpf_depth_image, a NULL depth or poses with n_frames > 0, a non-finite pose,
+ * depth_frame_stride below one image or not a multiple of the sample size, n_frames > 2^20, a NULL cons, n_rows or summary (rows may
+ * be NULL: not produced), on the device an image not aligned to its sample size.  n_frames = 0 returns the row set with all-zero
+ * records and first_through = 0xFFFFFFFF.  An empty handle, or one before its first clean pass, returns HFPF_OK with 0 rows and NULL
+ * arrays.  A handle with an RCCL communicator returns HFPF_ERR_STATE (a distributed form is not provided); a failed handle returns
+ * HFPF_ERR_STATE as extract does.  Render, track, mesh and the other readers do NOT honour the result.  Every call returns when its
+ * outputs are complete. */
+#define HFPF_CONSISTENCY_DROP 1u /* output only the rows that are not CONTRADICTED */
+#define HFPF_CONS_SEEN 1u         /* hfpf_row_consistency.flags: n_tested > 0 */
+#define HFPF_CONS_SUPPORTED 2u    /* n_support > 0 */
+#define HFPF_CONS_CONTRADICTED 4u /* the rule above */
+
+typedef struct hfpf_consistency_opts {
+    uint32_t struct_size;  /* = sizeof(hfpf_consistency_opts) */
+    uint32_t flags;        /* HFPF_CONSISTENCY_* */
+    int32_t window;        /* 0..2: half-width, in pixels, of the window searched around (pu, pv) */
+    uint32_t min_through;  /* a row is CONTRADICTED only with at least max(1, min_through) THROUGH frames */
+    double min_count;      /* rows with count < min_count are dropped before the test (0 keeps all) */
+    double z_near, z_far;  /* a row is IN_VIEW only iff z_near < zc < z_far */
+    double tolerance;      /* metres, (0, 1]: tol = tolerance + slope * zc */
+    double slope;          /* [0, 1] */
+    double min_cos;        /* [-1, 1]: the facing gate; below 0 = off */
+    double through_ratio;  /* >= 0: CONTRADICTED needs n_through > through_ratio * n_support */
+    uint64_t reserved;     /* 0 */
+} hfpf_consistency_opts;
+
+typedef struct hfpf_row_consistency { /* 32 bytes, one per output row */
+    uint32_t n_in_view, n_tested, n_support, n_through, n_occluded;
+    uint32_t first_through; /* smallest frame index classed THROUGH; 0xFFFFFFFF: none */
+    uint32_t flags;         /* HFPF_CONS_* */
+    uint32_t reserved;      /* 0 */
+} hfpf_row_consistency;
+
+typedef struct hfpf_consistency_summary { /* 64 bytes; always of the whole row set */
+    uint64_t n_rows, n_seen, n_supported, n_contradicted, n_kept;
+    uint64_t pairs_tested, pairs_support, pairs_through; /* the sums of n_tested, n_support, n_through */
+} hfpf_consistency_summary;
+
+/* (four 32-bit fields, seven doubles and the reserved word: 80 bytes) */
+#ifdef __cplusplus
+static_assert(sizeof(hfpf_consistency_opts) == 80, "hfpf_consistency_opts is 80 bytes");
+static_assert(sizeof(hfpf_row_consistency) == 32, "hfpf_row_consistency is 32 bytes");
+static_assert(sizeof(hfpf_consistency_summary) == 64, "hfpf_consistency_summary is 64 bytes");
+#else
+_Static_assert(sizeof(hfpf_consistency_opts) == 80, "hfpf_consistency_opts is 80 bytes");
+_Static_assert(sizeof(hfpf_row_consistency) == 32, "hfpf_row_consistency is 32 bytes");
+_Static_assert(sizeof(hfpf_consistency_summary) == 64, "hfpf_consistency_summary is 64 bytes");
+#endif
+
+/* HFPF_OK if o passes the checks above, else HFPF_ERR_BAD_ARG (host code, no handle; the node shell uses it too). */
+int hfpf_check_consistency_opts(const hfpf_consistency_opts* o);
+/* Frames, poses and outputs in pageable HOST memory: the frames are uploaded in chunks through the pinned staging (the split does
+ * not change a byte of the result); *rows (optional: rows == NULL = not produced) and *cons hold *n_rows entries each and are freed
+ * by hfpf_free_consistency. */
+int hfpf_depth_consistency(hfpf_handle* h, const hfpf_consistency_opts* o, const hfpf_depth_image* desc, const void* depth,
+                           uint64_t depth_frame_stride, uint32_t n_frames, const double* poses, hfpf_row** rows, hfpf_row_consistency** cons,
+                           uint64_t* n_rows, hfpf_consistency_summary* summary);
+void hfpf_free_consistency(hfpf_row* rows, hfpf_row_consistency* cons);
+/* The frames are read in place from DEVICE memory (HBM); poses and summary stay in host memory; *dev_rows and *dev_cons are device
+ * arrays, each freed by hfpf_device_free(h, p). */
+int hfpf_depth_consistency_device(hfpf_handle* h, const hfpf_consistency_opts* o, const hfpf_depth_image* desc, const void* dev_depth,
+                                  uint64_t depth_frame_stride, uint32_t n_frames, const double* poses, hfpf_row** dev_rows,
+                                  hfpf_row_consistency** dev_cons, uint64_t* n_rows, hfpf_consistency_summary* summary);
+
 /* <directory_name>/test_cloud.pcd (node.cpp:395): PCD v0.7 ASCII, FIELDS x y z rgb normal_x normal_y normal_z curvature */
 int hfpf_write_pcd(const hfpf_row* rows, uint64_t n_rows, const char* path);
 /* <directory_name>/meta.csv (node.cpp:396) with the header string of grid.hpp:462 */
@@ -1080,7 +1185,7 @@ int hfpf_get_occupied(hfpf_handle* h, int32_t* xyz, uint64_t cap, uint64_t* n_ou
  * WHAT A RESTORE IS.  hfpf_clear followed by putting that state in place.  Afterwards the handle is indistinguishable from the
  * source handle at the moment of the snapshot, in this sense:
  *   1. every read-only call (extract, extract_filtered, get_occupied, is_dirty, render*, query*, extract_mesh*, raycast*, track*,
- *      extract_components*, compare_mesh*, align_mesh*, cover_mesh*)
+ *      extract_components*, compare_mesh*, align_mesh*, cover_mesh*, depth_consistency*)
  *      returns byte-identical output;
  *   2. any continuation (integrate*, clean, extract, clear, automatic frame ids included) produces byte-identical rows and occupied
  *      lists to the same continuation on the source handle;

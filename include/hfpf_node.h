@@ -132,6 +132,21 @@ int hfpf_node_set_reference_alignment(hfpf_node* n, const hfpf_align_opts* opts)
  * with HFPF_ERR_BAD_ARG and leave the setting as it was. */
 int hfpf_node_set_reference_coverage(hfpf_node* n, const hfpf_cover_opts* opts);
 
+/* EXTENSION: what the last depth images say about every saved row.  With consistency options set the node keeps host copies of the
+ * last keep_frames (1..4096) depth images hfpf_node_on_depth_image integrated, with their poses; an image whose hfpf_depth_image
+ * differs from the ring's empties the ring first.  ~process then also runs hfpf_depth_consistency of include/hfpf.h on those images
+ * (frame index = position in the ring, oldest first; no frames: all-zero records) and writes, beside test_cloud.pcd, consistency.csv
+ * (header ix,iy,iz,n_in_view,n_tested,n_support,n_through,n_occluded,first_through,flags, then one line per row of the saved cloud)
+ * and consistency_summary.csv (one header line, one value line: n_rows, n_seen, n_supported, n_contradicted, n_kept, pairs_tested,
+ * pairs_support, pairs_through).  It is a report: HFPF_CONSISTENCY_DROP in opts->flags is ignored, and the saved cloud and the mesh
+ * are not filtered by it.  With a component filter set the lines are those of the kept rows: the call runs on the full row set with
+ * the filter's min_count (opts->min_count is then ignored), the kept rows' records are selected and the summary is rebuilt from
+ * them.  ~reset, hfpf_node_load_session and a ~process that saved its cloud empty the ring.  Clouds (hfpf_node_on_point_cloud) are
+ * not kept.  NULL opts turns it off again, the default, and drops the ring: the files are then byte-identical to those of a node
+ * that never called this.  Invalid options (hfpf_check_consistency_opts) or a keep_frames outside 1..4096 are refused with
+ * HFPF_ERR_BAD_ARG and leave the setting as it was. */
+int hfpf_node_set_depth_consistency(hfpf_node* n, const hfpf_consistency_opts* opts, uint32_t keep_frames);
+
 /* EXTENSION: keep the grid's session in a file and take it up again (hfpf_save / hfpf_load of include/hfpf.h on the node's grid, with
  * their errors).  Both run under the grid's own lock, so they are legal while the cloud callback and the clean thread run: a frame
  * or a clean pass lands wholly before or wholly after them.  Loading replaces the fused data only: the node stays started or stopped
