@@ -259,6 +259,9 @@ struct Session {
     // exchange cursors (multi-GPU, hfpf_epoch_*).  snapshot: not carried; handles that exchange refuse snapshot and restore
     uint64_t occ_exported = 0;              // occ_list entries already exchanged
     uint64_t frames_exported = 0, frames_seen = 0;  // frame_list entries already exchanged / as of the last export
+    // |H|, the HIDDEN voxels of hfpf_hide_* (hfpf_handle::hidden_words holds the bits; Tables::hidden points at them while this is not 0).
+    // snapshot: carried, as the HIDDEN section (present when this is not 0); restore counts the section's bits
+    uint64_t n_hidden = 0;
 };
 
 // Kernel timing (hfpf_get_kernel_time): one row per public kernel id.  Ids 0, 1, 5, 6, 7 bracket work with an event pair (Timed
@@ -309,6 +312,7 @@ struct hfpf_handle {
     hipStream_t copy_more[3] = {nullptr, nullptr, nullptr};
     std::vector<void*> allocs;
     uint64_t device_bytes = 0;
+    uint64_t* hidden_words = nullptr;  // the HIDDEN bits, (max_bricks + 1) * 8 words, allocated by the first call that hides a row (hide_words_locked); all zero while Session::n_hidden is 0
     unsigned long long* h_ctr = nullptr;      // pinned mirror of the counters
     unsigned long long* h_log_ctr = nullptr;  // pinned mirror of the region counters
     unsigned long long* mbox = nullptr;       // coherent pinned mailbox k_publish_counters writes (null with HFPF_MAILBOX=0): two slots of kMboxSlotWords
@@ -353,6 +357,7 @@ struct hfpf_handle {
     DevBuf cov_bins{bufs};   // hfpf_cover_mesh*: the summary, the 64-bit sample total, the triangles' sample counts and their offsets
     // hfpf_depth_consistency*: one upload's frames of the host form, the poses, the records / summary / keep marks and their scan
     DevBuf cons_in{bufs}, cons_pose{bufs}, cons_recs{bufs};
+    DevBuf hide_in{bufs}, hide_mark{bufs};  // hfpf_hide_*: one upload's entries of the host form (voxels, then selector words); the mark words and the call's counters
     DevBuf ray_in{bufs}, ray_out{bufs}, ray_map{bufs};  // hfpf_raycast*: a host chunk's rays, a chunk's (or band's) hits, the empty-space maps
     DevBuf snap_stage{bufs}, snap_err{bufs};            // hfpf_snapshot / hfpf_restore: the staging buffer (or one window of it), the range check's error word
     uint64_t bin_pool = 0;           // entries in bin_pt
@@ -722,6 +727,8 @@ int reset_state(hfpf_handle* h, uint64_t bricks_used = ~0ull, uint64_t normals_u
     HIPCHK(h, hipMemsetAsync(t.occ_mask, 0, (nb + 1) * 8 * 8, s));
     HIPCHK(h, hipMemsetAsync(t.stats, 0, (nn + 1) * kStatWords * 8, s));
     HIPCHK(h, hipMemsetAsync(t.nd_mask, 0, (nb + 1) * 8 * 2 * 8, s));
+    if (h->hidden_words) HIPCHK(h, hipMemsetAsync(h->hidden_words, 0, (nb + 1) * 8 * 8, s));
+    t.hidden = nullptr;  // H is empty (Session::n_hidden)
     HIPCHK(h, hipMemsetAsync(t.ctr, 0, C_COUNT * 8, s));
     HIPCHK(h, hipMemsetAsync(t.log_ctr, 0, kLogRegions * 16 * 8, s));
     HIPCHK(h, hipMemsetAsync(t.bin_fill, 0, 2 * (t.max_bricks + 2) * 4, s));
@@ -4099,6 +4106,208 @@ void hfpf_free_consistency(hfpf_row* rows, hfpf_row_consistency* cons)
     free(cons);
 }
 
+// ---- hidden rows (include/hfpf.h) ------------------------------------------------------------------------------------------
+static_assert(kHideOpHide == HFPF_HIDE && kHideOpShow == HFPF_SHOW && kHideOpOthers == HFPF_HIDE_OTHERS, "host_plan.hpp mirrors the ops of include/hfpf.h");
+
+int hfpf_check_hide_opts(const hfpf_hide_opts* o)
+{
+    return o && hide_opts_ok(o->struct_size, (uint32_t)sizeof(hfpf_hide_opts), o->op, o->flags, o->reserved) ? HFPF_OK : HFPF_ERR_BAD_ARG;
+}
+
+// The prologue of the calls that change or list H: the refusals of hfpf_snapshot (H travels in a snapshot), then the read prologue.
+static int hide_prologue_locked(hfpf_handle* h, const char* what)
+{
+    if (h->dist_on) return fail(h, HFPF_ERR_STATE, "%s: not available on a handle with an RCCL communicator", what);
+    if (h->epoch_used) return fail(h, HFPF_ERR_STATE, "%s: this handle has exchanged epoch records or statistic words; a distributed form is not provided", what);
+    return read_prologue_locked(h);
+}
+
+// The HIDDEN bits: allocated, all zero, by the first call that needs to write them.
+static int hide_words_locked(hfpf_handle* h)
+{
+    if (h->hidden_words) return HFPF_OK;
+    return dev_alloc(h, &h->hidden_words, (h->t.max_bricks + 1) * 8);
+}
+
+// The scratch of one call: the mark words of the used bricks and the counters, zeroed.
+struct HideCall {
+    unsigned long long* mark;
+    HideCounts* cnt;
+    uint32_t nb;  // bricks in use (ids 1..nb)
+};
+static int hide_begin_locked(hfpf_handle* h, HideCall* c)
+{
+    c->nb = (uint32_t)std::min<uint64_t>(h->h_ctr[C_BRICKS], h->t.max_bricks);
+    const ScratchLayout lay = ScratchLayout().add(&c->mark, ((uint64_t)c->nb + 1) * 8).add(&c->cnt, 1);
+    if (int rc = scratch(h, h->hide_mark, lay)) return rc;
+    HIPCHK(h, hipMemsetAsync(h->hide_mark.p, 0, (size_t)lay.bytes(), h->stream));
+    return HFPF_OK;
+}
+
+// k_hide_mark over n entries on the device, kHideLaunchEntries a launch.
+static int hide_mark_locked(hfpf_handle* h, const HideCall& c, const hfpf_hide_opts* o, const void* dev_voxels, uint64_t n, uint32_t voxel_stride, const void* dev_select,
+                            uint32_t select_stride)
+{
+    for (uint64_t i0 = 0; i0 < n; i0 += kHideLaunchEntries) {
+        HideList L{};
+        L.voxels = (const uint8_t*)dev_voxels + i0 * voxel_stride;
+        L.select = dev_select ? (const uint8_t*)dev_select + i0 * select_stride : nullptr;
+        L.n = std::min(kHideLaunchEntries, n - i0);
+        L.voxel_stride = voxel_stride, L.select_stride = select_stride, L.select_mask = o->select_mask, L.select_value = o->select_value;
+        L.n_bricks = c.nb;
+        hipLaunchKernelGGL(k_hide_mark, dim3(blocks_for(L.n, 256)), dim3(256), 0, h->stream, h->g, h->t, L, c.mark, c.cnt);
+        HIPCHK(h, hipGetLastError());
+    }
+    return HFPF_OK;
+}
+
+// Second half of every form: H' = op(H, mark) over the words of the used bricks, the counts, Tables::hidden.  mark == NULL: nothing
+// is marked (the count of a restored H).  Without the HIDDEN bits the op is counted first and they are allocated only when H' is not
+// empty.  Complete on return.
+static int hide_apply_locked(hfpf_handle* h, const HideCall& c, uint32_t op, const unsigned long long* mark, HideCounts* out)
+{
+    const unsigned blocks = blocks_for((uint64_t)c.nb * 8, 256);
+    auto run = [&](uint64_t* words, bool write) -> int {
+        HIPCHK(h, hipMemsetAsync(&c.cnt->n_changed, 0, 4 * sizeof(unsigned long long), h->stream));
+        hipLaunchKernelGGL(k_hide_apply, dim3(blocks), dim3(256), 0, h->stream, h->g, h->t, op, c.nb, mark, (const uint64_t*)words, write ? words : (uint64_t*)nullptr, c.cnt);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(out, c.cnt, sizeof *out, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return HFPF_OK;
+    };
+    int rc;
+    if (!h->hidden_words) {
+        if ((rc = run(nullptr, false))) return rc;
+        if (out->n_hidden == 0) return HFPF_OK;  // H stays empty: nothing to allocate
+        if ((rc = hide_words_locked(h))) return rc;
+    }
+    if ((rc = run(h->hidden_words, true))) return rc;
+    h->ss.n_hidden = out->n_hidden;
+    h->t.hidden = out->n_hidden ? h->hidden_words : nullptr;
+    return HFPF_OK;
+}
+
+static void hide_result(hfpf_hide_result* res, const HideCounts& k)
+{
+    if (!res) return;
+    res->reserved = 0;
+    res->n_selected = k.n_selected, res->n_matched = k.n_matched, res->n_changed = k.n_changed, res->n_hidden = k.n_hidden, res->n_full = k.n_full;
+}
+
+// Both list forms: validated here (HFPF_ERR_BAD_ARG: nothing on the handle changes), then mark and apply.  The host form uploads
+// hide_entries_per_upload entries at a time (voxels, then selector words) and marks them; the device form marks in place.
+static int hide_voxels_common(hfpf_handle* h, const hfpf_hide_opts* o, const void* voxels, uint64_t n, uint32_t voxel_stride, const void* select, uint32_t select_stride,
+                              hfpf_hide_result* res, bool on_device)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    const char* what = on_device ? "hide_voxels_device" : "hide_voxels";
+    if (hfpf_check_hide_opts(o) != HFPF_OK) return fail(h, HFPF_ERR_BAD_ARG, "%s: invalid hfpf_hide_opts", what);
+    if (res && res->struct_size != sizeof(hfpf_hide_result)) return fail(h, HFPF_ERR_BAD_ARG, "%s: hfpf_hide_result.struct_size", what);
+    if (!hide_list_ok(voxels != nullptr, n, voxel_stride, select != nullptr, select_stride))
+        return fail(h, HFPF_ERR_BAD_ARG, "%s: voxel_stride %u / select_stride %u (at least 12 / 4, multiples of 4), or NULL voxels with n > 0", what, voxel_stride, select_stride);
+    if (on_device && !hide_device_aligned((uint64_t)(uintptr_t)voxels, (uint64_t)(uintptr_t)select)) return fail(h, HFPF_ERR_BAD_ARG, "%s: device pointers must be 4-byte aligned", what);
+    int rc;
+    if ((rc = hide_prologue_locked(h, what))) return rc;
+    HideCounts k{};
+    hide_result(res, k);
+    if (h->h_ctr[C_NORMALS] == 0) return HFPF_OK;  // no rows yet: F, M and H are empty
+    HideCall c;
+    if ((rc = hide_begin_locked(h, &c))) return rc;
+    if (on_device) {
+        if ((rc = hide_mark_locked(h, c, o, voxels, n, voxel_stride, select, select_stride))) return rc;
+    } else {
+        const uint64_t per = hide_entries_per_upload(voxel_stride, select != nullptr, select_stride, kXferChunk);
+        for (uint64_t i0 = 0; i0 < n; i0 += per) {
+            const uint64_t ne = std::min(per, n - i0);
+            const uint64_t vb = hide_span_bytes(ne, voxel_stride, kHideVoxelBytes), sb = select ? hide_span_bytes(ne, select_stride, kHideSelectBytes) : 0;
+            uint8_t *d_vox, *d_sel;
+            if ((rc = scratch(h, h->hide_in, ScratchLayout().add(&d_vox, vb, 16).add(&d_sel, sb, 16)))) return rc;
+            hipError_t e = upload_pageable(h, d_vox, (const uint8_t*)voxels + i0 * voxel_stride, vb);  // complete on return
+            if (e == hipSuccess && select) e = upload_pageable(h, d_sel, (const uint8_t*)select + i0 * select_stride, sb);
+            if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "%s upload: %s", what, hipGetErrorString(e));
+            if ((rc = hide_mark_locked(h, c, o, d_vox, ne, voxel_stride, select ? d_sel : nullptr, select_stride))) return rc;
+            if (i0 + per < n) HIPCHK(h, hipStreamSynchronize(h->stream));  // the next upload overwrites what this launch reads
+        }
+    }
+    if ((rc = hide_apply_locked(h, c, o->op, c.mark, &k))) return rc;
+    hide_result(res, k);
+    return HFPF_OK;
+}
+
+int hfpf_hide_voxels(hfpf_handle* h, const hfpf_hide_opts* o, const void* voxels, uint64_t n, uint32_t voxel_stride, const void* select, uint32_t select_stride,
+                     hfpf_hide_result* res)
+{
+    return hide_voxels_common(h, o, voxels, n, voxel_stride, select, select_stride, res, false);
+}
+
+int hfpf_hide_voxels_device(hfpf_handle* h, const hfpf_hide_opts* o, const void* dev_voxels, uint64_t n, uint32_t voxel_stride, const void* dev_select,
+                            uint32_t select_stride, hfpf_hide_result* res)
+{
+    return hide_voxels_common(h, o, dev_voxels, n, voxel_stride, dev_select, select_stride, res, true);
+}
+
+int hfpf_hide_box(hfpf_handle* h, uint32_t op, const int32_t lo[3], const int32_t hi[3], hfpf_hide_result* res)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (!hide_op_ok(op) || !lo || !hi) return fail(h, HFPF_ERR_BAD_ARG, "hide_box: unknown op %u, or NULL lo / hi", op);
+    if (res && res->struct_size != sizeof(hfpf_hide_result)) return fail(h, HFPF_ERR_BAD_ARG, "hide_box: hfpf_hide_result.struct_size");
+    int rc;
+    if ((rc = hide_prologue_locked(h, "hide_box"))) return rc;
+    HideCounts k{};
+    hide_result(res, k);
+    if (h->h_ctr[C_NORMALS] == 0) return HFPF_OK;
+    HideCall c;
+    if ((rc = hide_begin_locked(h, &c))) return rc;
+    const HideBox box = clip_hide_box(lo, hi, h->g.dim);
+    if (!box.empty) {
+        HideBoxArgs B;
+        for (int a = 0; a < 3; a++) B.lo[a] = box.lo[a], B.hi[a] = box.hi[a];
+        hipLaunchKernelGGL(k_hide_box, dim3(blocks_for((uint64_t)c.nb * 8, 256)), dim3(256), 0, h->stream, h->g, h->t, B, c.nb, c.mark, c.cnt);
+        HIPCHK(h, hipGetLastError());
+    }
+    if ((rc = hide_apply_locked(h, c, op, c.mark, &k))) return rc;
+    k.n_selected = k.n_matched;  // the box form has no entries: both are |M|
+    hide_result(res, k);
+    return HFPF_OK;
+}
+
+int hfpf_show_all(hfpf_handle* h)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (int rc = hide_prologue_locked(h, "show_all")) return rc;
+    if (h->ss.n_hidden == 0) return HFPF_OK;
+    const uint64_t nb = std::min<uint64_t>(h->h_ctr[C_BRICKS], h->t.max_bricks);
+    HIPCHK(h, hipMemsetAsync(h->hidden_words, 0, (nb + 1) * 8 * 8, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->ss.n_hidden = 0;
+    h->t.hidden = nullptr;
+    return HFPF_OK;
+}
+
+int hfpf_get_hidden(hfpf_handle* h, int32_t* xyz, uint64_t cap, uint64_t* n_out)
+{
+    if (!h || !n_out) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    int rc;
+    if ((rc = hide_prologue_locked(h, "get_hidden"))) return rc;
+    const uint64_t nh = h->ss.n_hidden, n = h->h_ctr[C_NORMALS];
+    *n_out = nh;
+    if (!xyz || nh == 0 || n == 0) return HFPF_OK;
+    uint64_t *unsorted, *sorted; if ((rc = scratch_n(h, h->keys_a, n, &unsorted)) || (rc = scratch_n(h, h->keys_b, n, &sorted))) return rc;
+    hipLaunchKernelGGL(k_hidden_keys, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->t, n, unsorted);
+    HIPCHK(h, hipGetLastError());
+    if ((rc = sort_keys_u64(h, unsorted, sorted, n))) return rc;  // the keys of the records that are not hidden are all ones: behind
+    const uint64_t take = std::min(nh, cap);
+    std::vector<uint64_t> keys(take);
+    if (take) HIPCHK(h, hipMemcpyAsync(keys.data(), sorted, take * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (uint64_t i = 0; i < take; i++) key_coords(h->g, keys[i], xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+    return HFPF_OK;
+}
+
 int hfpf_stats_export(hfpf_handle* h, const void** dev_words, uint64_t* n_words, const void** dev_cwords, uint64_t* n_cwords)
 {
     if (!h || !dev_words || !n_words) return HFPF_ERR_BAD_ARG;
@@ -4565,7 +4774,8 @@ constexpr uint32_t kSnapSemanticFlags = HFPF_FLAG_FUSE_COLOR | HFPF_FLAG_PCL_SHI
 
 enum SnapSectionId : uint32_t {
     SS_CTR = 1, SS_LOG_CTR, SS_INFO, SS_FIRST_FRAME, SS_BUF_HEAD, SS_STAT_ID, SS_PRE_DEP, SS_OCC_MASK, SS_ND_MASK, SS_BRICKS, SS_LOG_PT, SS_LOG_RGB,
-    SS_NV_KEY, SS_NV_SLOT, SS_NV_C, SS_NV_N, SS_NV_LINE, SS_STATS, SS_REG_OCC, SS_DEP, SS_OCC_LIST, SS_PREREG, SS_FRAMES, SS_PEND
+    SS_NV_KEY, SS_NV_SLOT, SS_NV_C, SS_NV_N, SS_NV_LINE, SS_STATS, SS_REG_OCC, SS_DEP, SS_OCC_LIST, SS_PREREG, SS_FRAMES, SS_PEND,
+    SS_HIDDEN  // the HIDDEN bits of hfpf_hide_*, 64 bytes per brick; the last section, present only when something is hidden
 };
 struct SnapSection {
     uint32_t id, reserved;
@@ -4635,6 +4845,7 @@ const char* snap_parse_header(const void* blob, uint64_t bytes, SnapHeader* hd)
 struct SnapUsed {
     uint64_t n_bricks, n_normals, n_occ, n_reg, n_prereg, n_dep, n_frames, n_pend;
     uint64_t log_n[kLogRegions];
+    bool hidden;  // the session hides rows: the blob carries SS_HIDDEN (snapshot: Session::n_hidden; restore: the header lists the section)
 };
 
 inline uint64_t up16(uint64_t v) { return (v + 15) & ~15ull; }
@@ -4664,6 +4875,10 @@ uint32_t snap_layout(const SnapUsed& u, bool color, uint64_t region_cap, SnapSec
     for (const auto& a : all) {
         sec[n++] = SnapSection{a.id, 0u, off, a.bytes};
         off += up256(a.bytes);
+    }
+    if (u.hidden) {
+        sec[n++] = SnapSection{SS_HIDDEN, 0u, off, u.n_bricks * 64};
+        off += up256(u.n_bricks * 64);
     }
     *payload_bytes = off;
     return n;
@@ -4708,6 +4923,7 @@ void snap_spans(hfpf_handle* h, const SnapUsed& u, const SnapSection* sec, uint3
     add(SS_OCC_LIST, t.occ_list);
     add(SS_PREREG, t.prereg_list);
     add(SS_PEND, h->pend_a.p);
+    if (u.hidden) add(SS_HIDDEN, h->hidden_words + 8);
     uint64_t off_pt = at(SS_LOG_PT).offset, off_rgb = at(SS_LOG_RGB).offset;
     for (int r = 0; r < kLogRegions; r++) {
         if (!u.log_n[r]) continue;
@@ -4866,6 +5082,7 @@ int snapshot_locked(hfpf_handle* h, void** blob_out, uint64_t* bytes_out)
     u.n_pend = h->ss.pend_valid ? h->h_ctr[C_PEND] : 0;
     if (u.n_pend * 4 > h->pend_a.bytes) return fail(h, HFPF_ERR_STATE, "snapshot: pending-cell list of %llu entries exceeds its buffer (internal)", (unsigned long long)u.n_pend);
     for (int r = 0; r < kLogRegions; r++) u.log_n[r] = std::min<uint64_t>(h->h_log_ctr[r * 16], t.log_region_cap);
+    u.hidden = snapshot_carries_hidden(h->ss.n_hidden);
 
     uint8_t hdr_bytes[HFPF_SNAPSHOT_HEADER_BYTES];
     memset(hdr_bytes, 0, sizeof hdr_bytes);
@@ -4966,6 +5183,7 @@ int restore_locked(hfpf_handle* h, const void* blob, uint64_t bytes)
     SnapUsed u{};
     u.n_bricks = hd.n_bricks, u.n_normals = hd.n_normals, u.n_occ = hd.n_occ, u.n_reg = hd.n_reg, u.n_prereg = hd.n_prereg, u.n_dep = hd.n_dep;
     u.n_frames = hd.n_frames, u.n_pend = hd.n_pend;
+    for (uint32_t i = 0; i < hd.n_sections; i++) u.hidden = u.hidden || hd.sec[i].id == SS_HIDDEN;  // (the layout below must then agree)
     for (int r = 0; r < kLogRegions; r++) {
         u.log_n[r] = hd.log_n[r];
         if (hd.log_n[r] > t.log_region_cap || hd.n_linked[r] > hd.log_n[r]) return fail(h, HFPF_ERR_BAD_ARG, "restore: log region %d out of range", r);
@@ -5010,6 +5228,7 @@ int restore_locked(hfpf_handle* h, const void* blob, uint64_t bytes)
     uint32_t *err, *pend = nullptr;  // pend: read below u.n_pend only
     if ((rc = scratch_n(h, h->snap_err, 16, &err))) return bail(rc);
     if (u.n_pend && (rc = scratch_n(h, h->pend_a, u.n_pend, &pend))) return bail(rc);
+    if (u.hidden && (rc = hide_words_locked(h))) return bail(rc);
     uint8_t* stage = static_cast<uint8_t*>(h->snap_stage.p);
     if (hipMemsetAsync(err, 0, 64, h->stream) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore: hipMemsetAsync failed"));
     std::vector<SnapSpan> spans;
@@ -5039,6 +5258,12 @@ int restore_locked(hfpf_handle* h, const void* blob, uint64_t bytes)
     header_to_session(hd, h);
     if ((rc = read_counters(h))) return bail(rc);  // h_ctr, h_log_ctr, n_bricks_known from the restored device counters
     h->ss.n_bricks_before = h->ss.n_bricks_known;
+    if (u.hidden) {  // |H| and Tables::hidden from the restored bits; they must lie inside normal_found
+        HideCall c;
+        HideCounts k{};
+        if ((rc = hide_begin_locked(h, &c)) || (rc = hide_apply_locked(h, c, HFPF_HIDE, nullptr, &k))) return bail(rc);
+        if (k.n_bad) return bail(fail(h, HFPF_ERR_IO, "restore: the snapshot hides voxels that hold no row (%llu plane words); the handle has been cleared", k.n_bad));
+    }
     if (h->binned) {
         // Entries the source's direct form appended since its last clean are still unchained; the binned form never runs
         // k_link_log at a clean pass (its own appends arrive chained), so they are chained here.

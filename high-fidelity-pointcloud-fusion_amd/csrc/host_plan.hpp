@@ -220,4 +220,62 @@ inline ConsPlan plan_consistency(uint64_t rows, uint32_t frames, uint32_t comput
     return p;
 }
 
+// ---- hidden rows (hfpf_hide_*, include/hfpf.h) ----
+
+constexpr uint32_t kHideOpHide = 1, kHideOpShow = 2, kHideOpOthers = 3;  // = HFPF_HIDE, HFPF_SHOW, HFPF_HIDE_OTHERS
+constexpr uint32_t kHideVoxelBytes = 12, kHideSelectBytes = 4;           // what an entry reads at its voxel / its selector word
+constexpr uint64_t kHideLaunchEntries = 1ull << 30;                      // entries per launch of the mark kernel at most
+
+inline bool hide_op_ok(uint32_t op) { return op == kHideOpHide || op == kHideOpShow || op == kHideOpOthers; }
+// the fields of hfpf_hide_opts (expect = its sizeof)
+inline bool hide_opts_ok(uint32_t struct_size, uint32_t expect, uint32_t op, uint32_t flags, uint32_t reserved)
+{
+    return struct_size == expect && hide_op_ok(op) && flags == 0 && reserved == 0;
+}
+inline bool hide_stride_ok(uint32_t stride, uint32_t least) { return stride >= least && stride % 4 == 0; }
+// the list of a call: the select stride counts only with a selector; a NULL list must be empty
+inline bool hide_list_ok(bool have_voxels, uint64_t n, uint32_t voxel_stride, bool have_select, uint32_t select_stride)
+{
+    if (!hide_stride_ok(voxel_stride, kHideVoxelBytes)) return false;
+    if (have_select && !hide_stride_ok(select_stride, kHideSelectBytes)) return false;
+    return have_voxels || n == 0;
+}
+inline bool hide_device_aligned(uint64_t voxels_addr, uint64_t select_addr) { return ((voxels_addr | select_addr) & 3u) == 0; }
+
+// One (brick, x-plane) word of H under an op: old = its HIDDEN bits, mark = the matched cells, found = its normal_found bits (F).
+// constexpr, so that the apply kernel and tests/hide_plan_check.cpp run the same line.
+constexpr uint64_t hide_word_op(uint32_t op, uint64_t old, uint64_t mark, uint64_t found)
+{
+    const uint64_t m = mark & found;
+    return op == kHideOpHide ? (old | m) : op == kHideOpShow ? (old & ~m) : (old | (found & ~m));
+}
+
+// The box of hfpf_hide_box against the grid: inclusive voxel indices, may reach outside 0..dim-1, lo > hi on an axis = empty.
+struct HideBox {
+    int32_t lo[3], hi[3];  // clipped to 0..dim-1 (meaningless when empty)
+    bool empty;
+};
+inline HideBox clip_hide_box(const int32_t lo[3], const int32_t hi[3], const int32_t dim[3])
+{
+    HideBox b{};
+    for (int a = 0; a < 3; a++) {
+        b.lo[a] = std::max<int32_t>(lo[a], 0);
+        b.hi[a] = std::min<int32_t>(hi[a], dim[a] - 1);
+        if (b.lo[a] > b.hi[a]) b.empty = true;
+    }
+    return b;
+}
+
+// Host lists go up in chunks: entries per upload (one at least), so that neither array's span exceeds chunk_bytes ...
+inline uint64_t hide_entries_per_upload(uint32_t voxel_stride, bool have_select, uint32_t select_stride, uint64_t chunk_bytes)
+{
+    const uint64_t stride = std::max<uint64_t>(voxel_stride, have_select ? select_stride : 0);
+    return std::max<uint64_t>(1, chunk_bytes / std::max<uint64_t>(stride, 1));
+}
+// ... and the bytes n > 0 entries of `stride` span when each reads `item` bytes (nothing behind the last entry's item is read)
+inline uint64_t hide_span_bytes(uint64_t n, uint32_t stride, uint32_t item) { return (n - 1) * (uint64_t)stride + item; }
+
+// A snapshot carries the HIDDEN section only when something is hidden: a blob of a handle with H empty is the blob of old.
+inline bool snapshot_carries_hidden(uint64_t n_hidden) { return n_hidden != 0; }
+
 }  // namespace hfpf

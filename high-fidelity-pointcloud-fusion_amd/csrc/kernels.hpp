@@ -20,6 +20,7 @@
 #pragma once
 #include <type_traits>
 
+#include "host_plan.hpp"  // hide_word_op (constexpr: host and device)
 #include "stats.hpp"
 
 namespace hfpf {
@@ -2147,6 +2148,11 @@ __global__ __launch_bounds__(256) void k_extract_keys(const GridParams g, const 
             const long long cnt = (long long)stats[nid * kStatWords + SW_COUNT];
             if ((double)(int)cnt < opt.min_count) valid = 0;  // int count against a double threshold, grid.hpp:561
         }
+        if (t.hidden && valid) {  // (uniform: a kernel argument) a record whose cell is HIDDEN is no row (hfpf_hide_*)
+            uint64_t plane, bit;
+            slot_plane_bit(t.nv_slot[nid], plane, bit);
+            if (t.hidden[plane] & bit) valid = 0;
+        }
         keys[j] = valid ? key : ~0ull;
         vals[j] = (uint32_t)nid;
         n_valid += valid;
@@ -2561,7 +2567,8 @@ __device__ __forceinline__ uint64_t plane_window(int ya, int yb, int za, int zb)
 
 // The enumeration every window walk shares (query, mesh, raycast samples, component links): the cells with a record inside the
 // box [lo, hi] (0 <= lo, hi <= dim - 1 per axis, at most two bricks an axis), brick by brick through the directory, per x-plane of a
-// touched brick the nd_mask normal_found word ANDed with the box's (y, z) mask.  visit(cx, cy, cz, nid) sees each of them once.
+// touched brick the nd_mask normal_found word ANDed with the box's (y, z) mask, less the plane's HIDDEN word while anything is hidden
+// (Tables::hidden).  visit(cx, cy, cz, nid) sees each of them once.
 template <typename Visit>
 __device__ __forceinline__ void window_walk(const GridParams& g, const Tables& t, const int lo[3], const int hi[3], Visit&& visit)
 {
@@ -2575,7 +2582,9 @@ __device__ __forceinline__ void window_walk(const GridParams& g, const Tables& t
                                                     min(hi[2] - 8 * bz, 7));
                 const int x1 = min(hi[0], 8 * bx + 7);
                 for (int cx = max(lo[0], 8 * bx); cx <= x1; cx++) {
-                    uint64_t w = t.nd_mask[((uint64_t)b * 8u + (uint32_t)(cx & 7)) * 2] & wmask;
+                    const uint64_t plane = (uint64_t)b * 8u + (uint32_t)(cx & 7);
+                    uint64_t w = t.nd_mask[plane * 2] & wmask;
+                    if (t.hidden) w &= ~t.hidden[plane];  // (uniform: a kernel argument) HIDDEN cells hold no row (hfpf_hide_*)
                     while (w) {
                         const int bitn = __builtin_ctzll(w);
                         w &= w - 1;
@@ -3593,6 +3602,138 @@ __global__ __launch_bounds__(256) void k_occupied_keys(const GridParams g, const
     int32_t x, y, z;
     slot_coords(g, t, t.occ_list[j], x, y, z);
     keys[j] = make_key(g, x, y, z);
+}
+
+// ---- hidden rows (hfpf_hide_*, include/hfpf.h) -------------------------------------------------------------------------------
+// H is Tables::hidden, one word per (brick, x-plane).  A call marks the matched cells M in a scratch array of the same shape (from a
+// list: k_hide_mark; from a box: k_hide_box), then k_hide_apply turns every word of the used bricks into op(old, mark, normal_found)
+// and counts.  Word w = brick * 8 + (x & 7); the words of brick 0 (the null brick) are never touched.
+struct HideCounts {  // one call's counters, zeroed in front of it
+    unsigned long long n_selected, n_matched;
+    unsigned long long n_changed, n_hidden, n_full, n_bad;  // k_hide_apply; n_bad: words whose HIDDEN bits leave F (a restored blob)
+};
+struct HideList {  // the entries of one launch
+    const uint8_t* voxels;  // entry i: three int32 at voxels + i * voxel_stride
+    const uint8_t* select;  // NULL: every entry is selected; else a uint32 at select + i * select_stride
+    uint64_t n;
+    uint32_t voxel_stride, select_stride, select_mask, select_value;
+    uint32_t n_bricks;      // brick ids the mark array covers (1..n_bricks)
+};
+struct HideBoxArgs {
+    int32_t lo[3], hi[3];  // inclusive, inside 0..dim-1 (host_plan.hpp clip_hide_box)
+};
+
+// dst[k] += the workgroup's sum of v[k]: reduced per wave (wave64), then in LDS, then ONE device atomic per workgroup and counter, as
+// k_extract_keys counts its rows.  Every thread of the workgroup calls it (barriers).
+template <int N>
+__device__ __forceinline__ void hide_block_count(const uint32_t (&v)[N], unsigned long long* dst)
+{
+    __shared__ unsigned int s[N];
+    if (threadIdx.x < N) s[threadIdx.x] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        uint32_t x = v[k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);
+        if ((threadIdx.x & 63u) == 0 && x) atomicAdd(&s[k], x);
+    }
+    __syncthreads();
+    if (threadIdx.x < N && s[threadIdx.x]) atomicAdd(&dst[threadIdx.x], (unsigned long long)s[threadIdx.x]);
+}
+
+// One lane per entry: select test, range test, directory lookup (32-bit unsigned linear index, window_walk's arithmetic), the cell's
+// record and normal_found bit; a matched entry sets its cell's bit in mark.
+__global__ __launch_bounds__(256) void k_hide_mark(const GridParams g, const Tables t, const HideList L, unsigned long long* __restrict__ mark,
+                                                   HideCounts* __restrict__ cnt)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    uint32_t c[2] = {0, 0};  // selected, matched
+    if (i < L.n) {
+        bool sel = true;
+        if (L.select) sel = (*reinterpret_cast<const uint32_t*>(L.select + i * L.select_stride) & L.select_mask) == L.select_value;
+        if (sel) {
+            c[0] = 1;
+            const int32_t* v = reinterpret_cast<const int32_t*>(L.voxels + i * L.voxel_stride);
+            const int32_t x = v[0], y = v[1], z = v[2];
+            if (valid_coord(g, x, y, z)) {
+                const uint32_t b = t.dir[brick_index(g, x, y, z)];
+                if (b != 0 && b != kLock && b <= L.n_bricks) {
+                    const uint64_t plane = (uint64_t)b * 8u + ((uint32_t)x & 7u);
+                    const uint64_t bit = 1ull << ((((uint32_t)y & 7u) << 3) | ((uint32_t)z & 7u));
+                    if ((t.nd_mask[plane * 2] & bit) && t.stat_id[b * kBrickCells + local_index(x, y, z)] != 0) {
+                        c[1] = 1;
+                        atomicOr(&mark[plane], (unsigned long long)bit);
+                    }
+                }
+            }
+        }
+    }
+    hide_block_count(c, &cnt->n_selected);
+}
+
+// F on plane word w: the normal_found bits of the cells extract emits, and the word's brick coordinates.  The storage has dim + 1 cells
+// an axis, and a cell at index == dim may hold a record; it is no row (k_extract_keys' valid_coord), so it is no part of F.
+__device__ __forceinline__ uint64_t hide_full_word(const GridParams& g, const Tables& t, const uint64_t w, int& bx, int& by, int& bz)
+{
+    const uint32_t lin = t.brick_lin[w >> 3];
+    bz = (int)(lin % (uint32_t)g.bdim[2]);
+    const uint32_t r = lin / (uint32_t)g.bdim[2];
+    by = (int)(r % (uint32_t)g.bdim[1]), bx = (int)(r / (uint32_t)g.bdim[1]);
+    const int yb = min(g.dim[1] - 1 - 8 * by, 7), zb = min(g.dim[2] - 1 - 8 * bz, 7);
+    if (8 * bx + (int)(w & 7u) >= g.dim[0] || yb < 0 || zb < 0) return 0ull;
+    return t.nd_mask[w * 2] & plane_window(0, yb, 0, zb);
+}
+
+// One lane per (brick, x-plane) word of the used bricks: the box's (y, z) window on that plane, ANDed with F.
+__global__ __launch_bounds__(256) void k_hide_box(const GridParams g, const Tables t, const HideBoxArgs B, const uint32_t n_bricks,
+                                                  unsigned long long* __restrict__ mark, HideCounts* __restrict__ cnt)
+{
+    const uint64_t w = 8u + (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    uint32_t c[1] = {0};
+    if (w < ((uint64_t)n_bricks + 1) * 8u) {
+        int bx, by, bz;
+        const uint64_t full = hide_full_word(g, t, w, bx, by, bz);
+        const int x = 8 * bx + (int)(w & 7u);
+        const int ya = max(B.lo[1] - 8 * by, 0), yb = min(B.hi[1] - 8 * by, 7), za = max(B.lo[2] - 8 * bz, 0), zb = min(B.hi[2] - 8 * bz, 7);
+        if (x >= B.lo[0] && x <= B.hi[0] && ya <= yb && za <= zb) {
+            const uint64_t m = plane_window(ya, yb, za, zb) & full;
+            if (m) mark[w] = m;
+            c[0] = (uint32_t)__popcll(m);
+        }
+    }
+    hide_block_count(c, &cnt->n_matched);
+}
+
+// One lane per word of the used bricks: new = op(old, mark, F) (host_plan.hpp hide_word_op).  mark == NULL: nothing is
+// marked; hid_in == NULL: H is empty; hid_out == NULL: count only.
+__global__ __launch_bounds__(256) void k_hide_apply(const GridParams g, const Tables t, const uint32_t op, const uint32_t n_bricks, const unsigned long long* __restrict__ mark,
+                                                    const uint64_t* hid_in, uint64_t* hid_out, HideCounts* __restrict__ cnt)
+{
+    const uint64_t w = 8u + (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    uint32_t c[4] = {0, 0, 0, 0};  // changed, hidden, full, bad
+    if (w < ((uint64_t)n_bricks + 1) * 8u) {
+        int bx, by, bz;
+        const uint64_t found = hide_full_word(g, t, w, bx, by, bz);
+        const uint64_t old = hid_in ? hid_in[w] : 0ull;
+        const uint64_t nw = hide_word_op(op, old, mark ? (uint64_t)mark[w] : 0ull, found);
+        if (hid_out && nw != old) hid_out[w] = nw;
+        c[0] = (uint32_t)__popcll(old ^ nw);
+        c[1] = (uint32_t)__popcll(nw);
+        c[2] = (uint32_t)__popcll(found);
+        c[3] = (old & ~found) ? 1u : 0u;
+    }
+    hide_block_count(c, &cnt->n_changed);
+}
+
+// hfpf_get_hidden: the key of every record whose cell is HIDDEN, all ones for the others (they sort behind).  t.hidden != NULL.
+__global__ __launch_bounds__(256) void k_hidden_keys(const Tables t, const uint64_t n_normals, uint64_t* __restrict__ keys)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_normals) return;
+    uint64_t plane, bit;
+    slot_plane_bit(t.nv_slot[j + 1], plane, bit);
+    keys[j] = (t.hidden[plane] & bit) ? t.nv_key[j + 1] : ~0ull;
 }
 
 // ---- leaf probes (tests only; same device functions as the kernels above) -------------------------

@@ -21,6 +21,7 @@
 //              nd_mask[8][2] u64     normal_found bits and has-dependants bits, same bit order: one 16-byte read tells
 //                                    k_integrate what to do with a point (22 k bricks x 128 B stay in L2, where the
 //                                    8-byte info words of 10^7 cells do not).
+//              hidden[8] u64         HIDDEN bits of hfpf_hide_* (same bit order; allocated by the first call that hides a row)
 //   point log: log_pt float4 (x,y,z, w = slot until linked, then `next`) (+ log_rgb u32 with colour fusion): the
 //              reference's per-voxel buffers (grid.hpp:70,211,230) as one append-only array.
 //   normals:   nv_key u64, nv_slot u32, nv_c/nv_n float3, stats[8] i64 per record (stats.hpp)
@@ -160,6 +161,11 @@ struct Tables {
     unsigned long long* log_ctr;  // kLogRegions append counters, one per 128-byte line (index r*16)
     uint64_t log_region_cap;      // entries per log region
     uint64_t max_bricks, max_log, max_occ, max_normals, max_reg, max_dep, max_frames;
+    // HIDDEN bits (hfpf_hide_*, include/hfpf.h): per brick and x-plane ONE word, indexed and numbered as the normal_found word of nd_mask
+    // (brick * 8 + (x & 7), bit = (y & 7) * 8 + (z & 7)); hidden is a subset of normal_found.  NULL whenever nothing is hidden: the
+    // two places that decide what a row is (k_extract_keys, window_walk) test the pointer, nothing else reads it.  Last member, so that
+    // no other member moves in the kernel arguments.
+    const uint64_t* hidden;
 };
 
 __device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }

@@ -2,8 +2,10 @@
 // synthetic sensor -> ~start -> N x PointCloud2 callbacks with tf poses -> periodic clean -> ~process ->
 // <dir>/test_cloud.pcd + <dir>/meta.csv.  Prints per-stage wall times.
 //
-//   hfpf_demo [--min-component N] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]]] <out_dir> [frames=30] [W=640] [H=480] [resolution=0.001] [clean_every=10] [seed=0xF051] [pose_seed=0x5E3]
+//   hfpf_demo [--min-component N [--hide-filtered]] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]]] <out_dir> [frames=30] [W=640] [H=480] [resolution=0.001] [clean_every=10] [seed=0xF051] [pose_seed=0x5E3]
 // --min-component N: ~process saves only the connected components (26-neighbourhood) of at least N rows (hfpf_node_set_component_filter).
+//   --hide-filtered: the rows the filter drops are hidden on the device (hfpf_node_set_hide_filtered), so that the reports of --reference
+//   see the cleaned model too, not only test_cloud.pcd and meta.csv.
 // --reference mesh.ply: ~process also writes deviation.csv and deviation_summary.csv, the saved cloud measured against that mesh
 //   (binary little-endian PLY in the fusion frame; hfpf_node_set_reference_mesh); --max-deviation is the largest distance looked for
 //   (default 10 voxels, at most 32).  --align: the mesh is first best-fitted to the model from that pose with the same distance as its
@@ -52,11 +54,16 @@ int main(int argc, char** argv)
     uint32_t min_component = 0;
     const char* reference = nullptr;
     double max_deviation = 0.0;
-    bool align = false, coverage = false;
+    bool align = false, coverage = false, hide_filtered = false;
     double spacing = 0.0;
     while (argc > 2 && strncmp(argv[1], "--", 2) == 0) {
         if (strcmp(argv[1], "--align") == 0) {
             align = true;
+            argv += 1, argc -= 1;
+            continue;
+        }
+        if (strcmp(argv[1], "--hide-filtered") == 0) {
+            hide_filtered = true;
             argv += 1, argc -= 1;
             continue;
         }
@@ -76,7 +83,7 @@ int main(int argc, char** argv)
         argv += 2, argc -= 2;
     }
     if (argc < 2 || strncmp(argv[1], "--", 2) == 0) {
-        fprintf(stderr, "usage: hfpf_demo [--min-component N] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]]] <out_dir> [frames] [W] [H] [resolution] [clean_every] [seed] [pose_seed]\n");
+        fprintf(stderr, "usage: hfpf_demo [--min-component N [--hide-filtered]] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]]] <out_dir> [frames] [W] [H] [resolution] [clean_every] [seed] [pose_seed]\n");
         return 2;
     }
     const std::string dir = argv[1];
@@ -114,6 +121,7 @@ int main(int argc, char** argv)
             fprintf(stderr, "component filter: %s\n", hfpf_node_last_error(node));
             return 1;
         }
+        hfpf_node_set_hide_filtered(node, hide_filtered ? 1 : 0);
     }
     if (reference) {
         hfpf_mesh_vertex* mv = nullptr;

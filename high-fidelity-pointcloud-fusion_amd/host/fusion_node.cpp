@@ -27,6 +27,7 @@ struct hfpf_node {
     std::atomic<bool> cloud_subscription_started_{false};  // node.cpp:136
     std::string pointcloud_frame_;                         // node.cpp:128
     std::mutex frame_mtx;
+    double bbox_min[3] = {0, 0, 0};  // of the grid: hfpf_node_hide_box turns metres into voxel indices
     double clean_period_s = 5.0;
     bool final_clean = false;
     bool write_variants = false;
@@ -35,7 +36,9 @@ struct hfpf_node {
     hfpf_mesh_opts mesh_opts{};
     bool comp_on = false;               // hfpf_node_set_component_filter: ~process saves the rows of the kept components only
     hfpf_component_opts comp_opts{};
-    bool ref_on = false;                // hfpf_node_set_reference_mesh: ~process also writes deviation.csv and deviation_summary.csv
+    bool hide_filtered = false;         // hfpf_node_set_hide_filtered: ~process hides what the component filter drops, so that every file leaves it out
+    bool comp_rows = false;             // of the running ~process: the saved rows are the filter's selection from the full row set (comp_on, not hidden)
+    bool ref_on = false;               // hfpf_node_set_reference_mesh: ~process also writes deviation.csv and deviation_summary.csv
     hfpf_deviation_opts ref_opts{};
     std::vector<float> ref_verts;       // packed x, y, z
     std::vector<uint32_t> ref_tris;
@@ -129,6 +132,7 @@ int hfpf_node_create(const hfpf_node_params* p, hfpf_tf_lookup_fn tf, void* tf_u
     hfpf_config cfg = p->engine;
     cfg.struct_size = sizeof cfg;
     memcpy(cfg.bbox, p->bounding_box, 6 * sizeof(double));
+    for (int a = 0; a < 3; a++) n->bbox_min[a] = p->bounding_box[2 * a];
     int rc = hfpf_create(&cfg, &n->grid);
     if (rc != HFPF_OK) {
         g_err = hfpf_last_error(nullptr);
@@ -265,11 +269,11 @@ int hfpf_node_reset(hfpf_node* n, hfpf_trigger_response* res)
 static int write_deviation(hfpf_node* n, const hfpf_row* saved, uint64_t n_saved, double pose[12])
 {
     hfpf_deviation_opts o = n->ref_opts;
-    if (n->comp_on) o.min_count = n->comp_opts.min_count;
+    if (n->comp_rows) o.min_count = n->comp_opts.min_count;
     memcpy(pose, n->ref_pose, 12 * sizeof(double));
     if (n->align_on) {
         hfpf_align_opts ao = n->align_opts;
-        if (n->comp_on) ao.compare.min_count = n->comp_opts.min_count;
+        if (n->comp_rows) ao.compare.min_count = n->comp_opts.min_count;
         hfpf_align_result ar;
         memset(&ar, 0, sizeof ar);
         ar.struct_size = sizeof ar;
@@ -290,17 +294,17 @@ static int write_deviation(hfpf_node* n, const hfpf_row* saved, uint64_t n_saved
     uint64_t n_all = 0;
     hfpf_deviation_summary s;
     int rc = hfpf_compare_mesh(n->grid, &o, n->ref_verts.data(), n->ref_verts.size() / 3, 12, n->ref_tris.data(), n->ref_tris.size() / 3, pose,
-                               n->comp_on ? &all : nullptr, &dev, &n_all, &s);
+                               n->comp_rows ? &all : nullptr, &dev, &n_all, &s);
     if (rc != HFPF_OK) return rc;
     FILE* f = fopen((n->directory_name + "/deviation.csv").c_str(), "w");
     if (!f) rc = HFPF_ERR_IO;
     if (f) {
         fprintf(f, "ix,iy,iz,signed_distance,distance,tri,flags\n");
-        if (n->comp_on) s.n_rows = s.n_found = s.n_negative = 0, s.max_abs = 0.f, s.sum_abs_q30 = s.sum_sq_q30 = 0;
+        if (n->comp_rows) s.n_rows = s.n_found = s.n_negative = 0, s.max_abs = 0.f, s.sum_abs_q30 = s.sum_sq_q30 = 0;
         uint64_t j = 0;
         for (uint64_t i = 0; i < n_saved && rc == HFPF_OK; i++) {
             const hfpf_row& r = saved[i];
-            if (n->comp_on)
+            if (n->comp_rows)
                 while (j < n_all && (all[j].ix != r.ix || all[j].iy != r.iy || all[j].iz != r.iz)) j++;
             else j = i;
             if (j >= n_all) {
@@ -309,7 +313,7 @@ static int write_deviation(hfpf_node* n, const hfpf_row* saved, uint64_t n_saved
             }
             const hfpf_deviation& d = dev[j];
             fprintf(f, "%d,%d,%d,%.9g,%.9g,%u,%u\n", r.ix, r.iy, r.iz, d.signed_distance, d.distance, d.tri, d.flags);
-            if (n->comp_on) {
+            if (n->comp_rows) {
                 s.n_rows++;
                 if (d.flags & HFPF_DEV_FOUND) {
                     const double w = (double)d.distance;
@@ -344,7 +348,7 @@ static int write_deviation(hfpf_node* n, const hfpf_row* saved, uint64_t n_saved
 static int write_coverage(hfpf_node* n, const double pose[12])
 {
     hfpf_cover_opts o = n->cover_opts;
-    if (n->comp_on) o.min_count = n->comp_opts.min_count;
+    if (n->comp_rows) o.min_count = n->comp_opts.min_count;
     hfpf_tri_coverage* cov = nullptr;
     hfpf_coverage_summary s;
     const uint64_t n_tris = n->ref_tris.size() / 3;
@@ -402,7 +406,7 @@ static int write_consistency(hfpf_node* n, const hfpf_row* saved, uint64_t n_sav
         for (uint32_t f = 0; f < n_frames; f++) memcpy(frames.data() + (size_t)f * stride, n->cons_frames[f].data(), stride);
     }
     o.flags &= ~HFPF_CONSISTENCY_DROP;
-    if (n->comp_on) o.min_count = n->comp_opts.min_count;
+    if (n->comp_rows) o.min_count = n->comp_opts.min_count;
     if (n_frames == 0) {  // nothing seen yet: any valid descriptor serves a call without frames
         memset(&desc, 0, sizeof desc);
         desc.struct_size = sizeof desc;
@@ -413,17 +417,17 @@ static int write_consistency(hfpf_node* n, const hfpf_row* saved, uint64_t n_sav
     hfpf_row_consistency* cons = nullptr;
     uint64_t n_all = 0;
     hfpf_consistency_summary s;
-    int rc = hfpf_depth_consistency(n->grid, &o, &desc, frames.data(), stride, n_frames, poses.data(), n->comp_on ? &all : nullptr, &cons, &n_all, &s);
+    int rc = hfpf_depth_consistency(n->grid, &o, &desc, frames.data(), stride, n_frames, poses.data(), n->comp_rows ? &all : nullptr, &cons, &n_all, &s);
     if (rc != HFPF_OK) return rc;
     FILE* f = fopen((n->directory_name + "/consistency.csv").c_str(), "w");
     if (!f) rc = HFPF_ERR_IO;
     if (f) {
         fprintf(f, "ix,iy,iz,n_in_view,n_tested,n_support,n_through,n_occluded,first_through,flags\n");
-        if (n->comp_on) memset(&s, 0, sizeof s);
+        if (n->comp_rows) memset(&s, 0, sizeof s);
         uint64_t j = 0;
         for (uint64_t i = 0; i < n_saved && rc == HFPF_OK; i++) {
             const hfpf_row& r = saved[i];
-            if (n->comp_on)
+            if (n->comp_rows)
                 while (j < n_all && (all[j].ix != r.ix || all[j].iy != r.iy || all[j].iz != r.iz)) j++;
             else j = i;
             if (j >= n_all) {
@@ -433,7 +437,7 @@ static int write_consistency(hfpf_node* n, const hfpf_row* saved, uint64_t n_sav
             const hfpf_row_consistency& c = cons[j];
             fprintf(f, "%d,%d,%d,%u,%u,%u,%u,%u,%u,%u\n", r.ix, r.iy, r.iz, c.n_in_view, c.n_tested, c.n_support, c.n_through, c.n_occluded, c.first_through,
                     c.flags);
-            if (n->comp_on) {
+            if (n->comp_rows) {
                 s.n_rows++;
                 s.n_seen += (c.flags & HFPF_CONS_SEEN) ? 1 : 0;
                 s.n_supported += (c.flags & HFPF_CONS_SUPPORTED) ? 1 : 0;
@@ -441,7 +445,7 @@ static int write_consistency(hfpf_node* n, const hfpf_row* saved, uint64_t n_sav
                 s.pairs_tested += c.n_tested, s.pairs_support += c.n_support, s.pairs_through += c.n_through;
             }
         }
-        if (n->comp_on) s.n_kept = s.n_rows - s.n_contradicted;
+        if (n->comp_rows) s.n_kept = s.n_rows - s.n_contradicted;
         const bool ok = !ferror(f);
         if (fclose(f) != 0 || !ok) rc = rc == HFPF_OK ? HFPF_ERR_IO : rc;
     }
@@ -480,8 +484,29 @@ int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
     uint32_t* labels = nullptr;
     hfpf_component* comps = nullptr;
     uint64_t ncomp = 0;
-    int rc = n->comp_on ? hfpf_extract_components(n->grid, &n->comp_opts, &rows, &labels, &nr, &comps, &ncomp)  // EXTENSION: without the specks
-                        : hfpf_extract(n->grid, &rows, &nr);                                                  // grid_.downloadData, node.cpp:398
+    int rc = HFPF_OK;
+    n->comp_rows = n->comp_on && !n->hide_filtered;
+    if (n->comp_on && n->hide_filtered) {
+        // EXTENSION: the filter runs in HBM and what it drops is hidden (HFPF_HIDE_OTHERS on the kept rows, read in place): from here
+        // on this is a node without a component filter whose every file leaves those rows out.  hfpf_clear below empties the set.
+        hfpf_row* d_rows = nullptr;
+        uint32_t* d_labels = nullptr;
+        hfpf_component* d_comps = nullptr;
+        uint64_t n_kept = 0;
+        rc = hfpf_extract_components_device(n->grid, &n->comp_opts, &d_rows, &d_labels, &n_kept, &d_comps, &ncomp);
+        if (rc == HFPF_OK) {
+            hfpf_hide_opts ho;
+            memset(&ho, 0, sizeof ho);
+            ho.struct_size = sizeof ho;
+            ho.op = HFPF_HIDE_OTHERS;
+            rc = hfpf_hide_voxels_device(n->grid, &ho, d_rows, n_kept, sizeof(hfpf_row), nullptr, 0, nullptr);
+        }
+        for (void* p : {(void*)d_rows, (void*)d_labels, (void*)d_comps})
+            if (p) hfpf_device_free(n->grid, p);
+    }
+    if (rc == HFPF_OK)
+        rc = n->comp_rows ? hfpf_extract_components(n->grid, &n->comp_opts, &rows, &labels, &nr, &comps, &ncomp)  // EXTENSION: without the specks
+                          : hfpf_extract(n->grid, &rows, &nr);                                                  // grid_.downloadData, node.cpp:398
     if (rc == HFPF_OK) rc = hfpf_write_pcd(rows, nr, cloud_location.c_str());
     if (rc == HFPF_OK) rc = hfpf_write_meta_csv(rows, nr, meta_location.c_str());
     if (rc == HFPF_OK && n->publish) n->publish(n->publish_user, rows, nr, n->fusion_frame.c_str());  // processed_cloud_, node.cpp:158
@@ -489,7 +514,7 @@ int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
     if (rc == HFPF_OK && n->ref_on) rc = write_deviation(n, rows, nr, ref_pose);  // EXTENSION: the saved cloud measured against the reference mesh
     if (rc == HFPF_OK && n->ref_on && n->cover_on) rc = write_coverage(n, ref_pose);  // EXTENSION: ... and how much of that mesh the model covers
     if (rc == HFPF_OK && n->cons_on) rc = write_consistency(n, rows, nr);  // EXTENSION: what the last depth images say about every saved row
-    if (n->comp_on) hfpf_free_components(rows, labels, comps);
+    if (n->comp_rows) hfpf_free_components(rows, labels, comps);
     else hfpf_free_rows(rows);
     if (rc == HFPF_OK && n->mesh_on) {  // EXTENSION: a triangle mesh of the same model next to the cloud
         hfpf_mesh_vertex* mv = nullptr;
@@ -576,6 +601,33 @@ int hfpf_node_set_component_filter(hfpf_node* n, const hfpf_component_opts* opts
     }
     n->comp_on = opts != nullptr;
     return HFPF_OK;
+}
+
+int hfpf_node_set_hide_filtered(hfpf_node* n, int on)
+{
+    if (!n) return HFPF_ERR_BAD_ARG;
+    n->hide_filtered = on != 0;
+    return HFPF_OK;
+}
+
+int hfpf_node_hide_box(hfpf_node* n, uint32_t op, const double box_m[6], hfpf_hide_result* res)
+{
+    if (!n) return HFPF_ERR_BAD_ARG;
+    if (!box_m) return nfail(n, HFPF_ERR_BAD_ARG, "hfpf_node_hide_box: NULL box");
+    int32_t dims[3], lo[3], hi[3];
+    double resolution = 0.0;
+    int rc = hfpf_get_dims(n->grid, dims, &resolution);
+    if (rc != HFPF_OK) return nfail(n, rc, hfpf_last_error(n->grid));
+    for (int a = 0; a < 3; a++) {
+        int32_t* out[2] = {&lo[a], &hi[a]};
+        for (int k = 0; k < 2; k++) {
+            const double v = floor((box_m[2 * a + k] - n->bbox_min[a]) / resolution);  // voxel = floor((p - bbox_min) / res), the query contract
+            if (std::isnan(v)) return nfail(n, HFPF_ERR_BAD_ARG, "hfpf_node_hide_box: a bound is not a number");
+            *out[k] = v < -2147483648.0 ? INT32_MIN : v > 2147483647.0 ? INT32_MAX : (int32_t)v;
+        }
+    }
+    rc = hfpf_hide_box(n->grid, op, lo, hi, res);  // (takes the grid's lock: frames and clean passes fall before or after it)
+    return rc == HFPF_OK ? rc : nfail(n, rc, hfpf_last_error(n->grid));
 }
 
 int hfpf_node_set_reference_mesh(hfpf_node* n, const hfpf_deviation_opts* opts, const void* verts, uint64_t n_verts, uint32_t vertex_stride,

@@ -97,6 +97,7 @@ EXPORTS = [
     "hfpf_check_align_opts", "hfpf_align_mesh", "hfpf_align_mesh_device",
     "hfpf_check_cover_opts", "hfpf_cover_mesh", "hfpf_cover_mesh_device", "hfpf_free_coverage",
     "hfpf_check_consistency_opts", "hfpf_depth_consistency", "hfpf_depth_consistency_device", "hfpf_free_consistency",
+    "hfpf_check_hide_opts", "hfpf_hide_voxels", "hfpf_hide_voxels_device", "hfpf_hide_box", "hfpf_show_all", "hfpf_get_hidden",
     "hfpf_check_raycast_opts", "hfpf_raycast", "hfpf_raycast_device", "hfpf_raycast_view", "hfpf_raycast_view_device",
     "hfpf_snapshot", "hfpf_free_snapshot", "hfpf_restore", "hfpf_save", "hfpf_load", "hfpf_snapshot_info", "hfpf_config_from_snapshot",
 ]
@@ -465,6 +466,40 @@ def check_consistency_opts(o):
     return lib().hfpf_check_consistency_opts(C.byref(o) if o is not None else None)
 
 
+# hfpf_hide_opts.op, hfpf_hide_opts and hfpf_hide_result (include/hfpf.h)
+HIDE, SHOW, HIDE_OTHERS = 1, 2, 3
+HIDE_OPS = {"hide": HIDE, "show": SHOW, "hide_others": HIDE_OTHERS}
+
+
+class HideOpts(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("struct_size", "op", "select_mask", "select_value", "flags", "reserved")]
+
+
+class HideResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_uint64) for k in ("n_selected", "n_matched", "n_changed",
+                                                                                                       "n_hidden", "n_full")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("n_selected", "n_matched", "n_changed", "n_hidden", "n_full")}
+
+
+assert C.sizeof(HideOpts) == 24 and C.sizeof(HideResult) == 48
+
+
+def hide_opts(op="hide", select_mask=0, select_value=0):
+    """An hfpf_hide_opts: the op ("hide", "show", "hide_others" or its number) and the selector's mask and value."""
+    o = HideOpts()
+    o.struct_size = C.sizeof(HideOpts)
+    o.op = HIDE_OPS.get(op, op)
+    o.select_mask, o.select_value = int(select_mask) & 0xFFFFFFFF, int(select_value) & 0xFFFFFFFF
+    return o
+
+
+def check_hide_opts(o):
+    """hfpf_check_hide_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
+    return lib().hfpf_check_hide_opts(C.byref(o) if o is not None else None)
+
+
 def read_ply(path):
     """hfpf_read_ply: (vertices of MESH_VERTEX_DTYPE, (n, 3) uint32 triangles) of a binary little-endian PLY (host code, no GPU
     needed); HfpfError with the reader's message otherwise."""
@@ -718,6 +753,12 @@ def lib():
                        C.POINTER(ConsistencySummary)]
     L.hfpf_free_consistency.argtypes = [vp, vp]
     L.hfpf_free_consistency.restype = None
+    L.hfpf_check_hide_opts.argtypes = [C.POINTER(HideOpts)]
+    for fn in (L.hfpf_hide_voxels, L.hfpf_hide_voxels_device):
+        fn.argtypes = [vp, C.POINTER(HideOpts), vp, u64, u32, vp, u32, C.POINTER(HideResult)]
+    L.hfpf_hide_box.argtypes = [vp, u32, vp, vp, C.POINTER(HideResult)]
+    L.hfpf_show_all.argtypes = [vp]
+    L.hfpf_get_hidden.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.hfpf_read_ply.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64)]
     dbl = C.c_double
     L.hfpf_check_raycast_opts.argtypes = [C.POINTER(RaycastOpts)]
@@ -1365,6 +1406,54 @@ class OccupancyGrid:
 
     def clear(self):
         self._chk(lib().hfpf_clear(self._h))
+
+    # -- hiding rows from every read-out --
+    def hide_voxels(self, voxels, op="hide", select=None, select_mask=0, select_value=0, device=False, n=None, voxel_stride=None,
+                    select_stride=None, opts=None):
+        """hfpf_hide_voxels: op on the voxels of a list; returns the counts as a dict.  voxels: an (n, 3) int32 array (stride 12), a
+        ROW_DTYPE array (stride 64), or any array whose rows begin with three int32, `voxel_stride` bytes apart.  select: an array of
+        one uint32 word per entry, `select_stride` bytes apart (default: its item size); entry i is selected iff (word & select_mask)
+        == select_value.  device=True (hfpf_hide_voxels_device): voxels and select are device pointers, and n, voxel_stride (and
+        select_stride with a selector) are required."""
+        o = opts if opts is not None else hide_opts(op, select_mask, select_value)
+        res = HideResult()
+        res.struct_size = C.sizeof(HideResult)
+        if device:
+            self._chk(lib().hfpf_hide_voxels_device(self._h, C.byref(o), C.c_void_p(voxels), int(n), int(voxel_stride), C.c_void_p(select) if select else None,
+                                                    int(select_stride or 0), C.byref(res)))
+            return res.as_dict()
+        voxels = np.asarray(voxels)
+        if voxels.dtype.names is None and voxel_stride is None:
+            voxels = np.ascontiguousarray(voxels, dtype=np.int32).reshape(-1, 3)
+        n = len(voxels) if n is None else int(n)
+        vs = int(voxel_stride) if voxel_stride is not None else (voxels.strides[0] if len(voxels) > 1 else max(12, voxels.dtype.itemsize))
+        ss = 0
+        if select is not None:
+            ss = int(select_stride) if select_stride is not None else (select.strides[0] if len(select) else select.dtype.itemsize)
+        self._chk(lib().hfpf_hide_voxels(self._h, C.byref(o), C.c_void_p(voxels.ctypes.data) if n else None, n, vs,
+                                         C.c_void_p(select.ctypes.data) if select is not None else None, ss, C.byref(res)))
+        return res.as_dict()
+
+    def hide_box(self, lo, hi, op="hide"):
+        """hfpf_hide_box: op on the voxels lo..hi (inclusive indices; the box may reach outside the grid); returns the counts."""
+        lo3, hi3 = np.ascontiguousarray(lo, dtype=np.int32).reshape(3), np.ascontiguousarray(hi, dtype=np.int32).reshape(3)
+        res = HideResult()
+        res.struct_size = C.sizeof(HideResult)
+        self._chk(lib().hfpf_hide_box(self._h, HIDE_OPS.get(op, op), _p(lo3), _p(hi3), C.byref(res)))
+        return res.as_dict()
+
+    def show_all(self):
+        """hfpf_show_all: nothing is hidden any more."""
+        self._chk(lib().hfpf_show_all(self._h))
+
+    def hidden(self):
+        """hfpf_get_hidden: the hidden voxels, (n, 3) int32 in ascending (x, y, z) order."""
+        n = C.c_uint64()
+        self._chk(lib().hfpf_get_hidden(self._h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 3), dtype=np.int32)
+        if n.value:
+            self._chk(lib().hfpf_get_hidden(self._h, _p(out), n.value, C.byref(n)))
+        return out
 
     # -- keeping a session --
     def snapshot(self):

@@ -18,7 +18,7 @@ EXPORTS = ["hfpf_node_default_params", "hfpf_node_create", "hfpf_node_destroy", 
            "hfpf_node_get_stats", "hfpf_node_set_publisher", "hfpf_node_on_depth_image",
            "hfpf_node_set_mesh_output", "hfpf_node_save_session", "hfpf_node_load_session", "hfpf_node_set_component_filter",
            "hfpf_node_set_reference_mesh", "hfpf_node_set_reference_alignment", "hfpf_node_set_reference_coverage",
-           "hfpf_node_set_depth_consistency"]
+           "hfpf_node_set_depth_consistency", "hfpf_node_set_hide_filtered", "hfpf_node_hide_box"]
 
 
 class Params(C.Structure):
@@ -73,6 +73,8 @@ def lib():
         L.hfpf_node_set_reference_alignment.argtypes = [C.c_void_p, C.POINTER(hfpf.AlignOpts)]
         L.hfpf_node_set_reference_coverage.argtypes = [C.c_void_p, C.POINTER(hfpf.CoverOpts)]
         L.hfpf_node_set_depth_consistency.argtypes = [C.c_void_p, C.POINTER(hfpf.ConsistencyOpts), C.c_uint32]
+        L.hfpf_node_set_hide_filtered.argtypes = [C.c_void_p, C.c_int]
+        L.hfpf_node_hide_box.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(hfpf.HideResult)]
         L.hfpf_node_save_session.argtypes = [C.c_void_p, C.c_char_p]
         L.hfpf_node_load_session.argtypes = [C.c_void_p, C.c_char_p]
         _lib = L
@@ -240,6 +242,24 @@ class FusionNode:
         rc = lib().hfpf_node_set_depth_consistency(self._h, C.byref(o) if o is not None else None, int(keep_frames))
         if rc < 0:
             raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
+
+    def set_hide_filtered(self, on=True):
+        """With a component filter set, ~process hides the rows the filter drops (hfpf_hide_voxels_device), so that mesh.ply, the
+        variants and the reports leave them out as test_cloud.pcd does; off by default."""
+        rc = lib().hfpf_node_set_hide_filtered(self._h, 1 if on else 0)
+        if rc < 0:
+            raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
+
+    def hide_box(self, box_m, op="hide"):
+        """hfpf_node_hide_box: op ("hide", "show", "hide_others") on a box in fusion-frame metres (xmin, xmax, ymin, ymax, zmin, zmax);
+        returns the counts of hfpf_hide_box."""
+        box = np.ascontiguousarray(box_m, np.float64).reshape(6)
+        res = hfpf.HideResult()
+        res.struct_size = C.sizeof(hfpf.HideResult)
+        rc = lib().hfpf_node_hide_box(self._h, hfpf.HIDE_OPS.get(op, op), box.ctypes.data_as(C.c_void_p), C.byref(res))
+        if rc < 0:
+            raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
+        return res.as_dict()
 
     def save_session(self, path):
         """The grid's session to a file (hfpf_save); legal while capture and the clean thread run."""

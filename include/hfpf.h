@@ -680,7 +680,7 @@ int hfpf_raycast_view_device(hfpf_handle* h, const hfpf_raycast_opts* o, uint32_
  *   comps[c] = the hfpf_component below.  With min_rows = min_points = keep_largest = 0 the output is the plain labelling of every row.
  * A call changes nothing on the handle except device_bytes (its scratch: 4 bytes per normal record, 24 per row, 64 per component,
  * the sort and scan buffers and, for the host form, the output).  Render, track, query, mesh and raycast do NOT honour a component
- * filter: they see every row.  Rejected with HFPF_ERR_BAD_ARG (the handle stays usable, nothing is written): struct_size != sizeof,
+ * filter, unless hidden with hfpf_hide_voxels: they see every row.  Rejected with HFPF_ERR_BAD_ARG (the handle stays usable, nothing is written): struct_size != sizeof,
  * flags, reserved0 or reserved != 0, reach outside 1..4, min_count NaN, min_normal_dot not finite or outside [-2, 1], a NULL n_rows,
  * n_comps, labels or comps pointer (rows may be NULL: not produced).  An empty handle, or one before its first clean pass, returns
  * HFPF_OK with 0 rows, 0 components and NULL arrays.  A handle with an RCCL communicator returns HFPF_ERR_STATE (a distributed form
@@ -1088,7 +1088,8 @@ int hfpf_cover_mesh_device(hfpf_handle* h, const hfpf_cover_opts* o, const void*
  * be NULL: not produced), on the device an image not aligned to its sample size.  n_frames = 0 returns the row set with all-zero
  * records and first_through = 0xFFFFFFFF.  An empty handle, or one before its first clean pass, returns HFPF_OK with 0 rows and NULL
  * arrays.  A handle with an RCCL communicator returns HFPF_ERR_STATE (a distributed form is not provided); a failed handle returns
- * HFPF_ERR_STATE as extract does.  Render, track, mesh and the other readers do NOT honour the result.  Every call returns when its
+ * HFPF_ERR_STATE as extract does.  Render, track, mesh and the other readers do NOT honour the result, unless hidden with
+ * hfpf_hide_voxels.  Every call returns when its
  * outputs are complete. */
 #define HFPF_CONSISTENCY_DROP 1u /* output only the rows that are not CONTRADICTED */
 #define HFPF_CONS_SEEN 1u         /* hfpf_row_consistency.flags: n_tested > 0 */
@@ -1147,6 +1148,84 @@ int hfpf_depth_consistency_device(hfpf_handle* h, const hfpf_consistency_opts* o
                                   uint64_t depth_frame_stride, uint32_t n_frames, const double* poses, hfpf_row** dev_rows,
                                   hfpf_row_consistency** dev_cons, uint64_t* n_rows, hfpf_consistency_summary* summary);
 
+/* ---- hiding rows from every read-out: erase, crop, and making the filters above count (no reference counterpart) ----------------
+ * hfpf_extract_components and hfpf_depth_consistency tell which rows do not belong to the surface; these calls make every read-out
+ * leave such rows out, and add "erase this box" and "crop to this box".  Everything is restatable from hfpf_extract's rows
+ * (tests/hide_ref.py).
+ * State: a handle carries a set H of HIDDEN voxels, empty at create.  F, the FULL ROW SET, is the voxels of the rows hfpf_extract
+ *   would return with H empty; H is a subset of F at all times.  "The rows hfpf_extract would return" means F minus H everywhere in
+ *   this header: extract, extract_filtered, render*, track*, query* (HAS_ROW / FOUND), extract_mesh*, raycast*, extract_components*,
+ *   compare_mesh*, align_mesh*, cover_mesh* and depth_consistency* are defined through those rows and inherit the rule.  NOT affected:
+ *   occupancy (hfpf_get_occupied, HFPF_QHIT_OCCUPIED), every field of hfpf_counters except device_bytes, hfpf_is_dirty, integrate and
+ *   clean: a hidden voxel goes on collecting points and acts as a dependant like any other.  A voxel that gets its row in a later
+ *   clean pass is visible.  H lasts until these calls change it, hfpf_clear empties it, or hfpf_restore / hfpf_load replace it by the
+ *   snapshot's.
+ * Entries: a voxel list has n entries; entry i's voxel is three int32 (ix, iy, iz) at voxels + i * voxel_stride (12: a packed
+ *   triplet list such as hfpf_get_occupied's; 64: an hfpf_row array as it is; at least 12 and a multiple of 4).  An optional selector
+ *   word is a uint32 at select + i * select_stride (at least 4, a multiple of 4).  Entry i is SELECTED iff select == NULL or
+ *   (word & select_mask) == select_value: hfpf_row_consistency.flags (select = &cons[0].flags, stride 32) with mask = value =
+ *   HFPF_CONS_CONTRADICTED and the rows of the same call as voxels hides the contradicted rows; a labels array with mask ~0 and
+ *   value c hides component c.  An entry is MATCHED iff it is SELECTED, 0 <= i_a < dim_a on every axis and its voxel is in F.
+ *   M = the set of distinct matched voxels.  Nothing behind the 12 bytes of an entry's voxel or the 4 of its selector word is read.
+ * Ops: HFPF_HIDE: H' = H + M.  HFPF_SHOW: H' = H - M.  HFPF_HIDE_OTHERS: H' = H + (F - M): "keep only these", "crop"; cumulative
+ *   (it never shows what was hidden before); with n = 0 it hides everything.
+ * Box form: M = the voxels of F with lo[a] <= i_a <= hi[a] on every axis (inclusive voxel indices; the box may reach outside
+ *   0..dim-1; lo > hi on an axis is the empty box); same ops.
+ * Result (res may be NULL): n_selected = entries selected, n_matched = entries matched (duplicates counted), n_changed = the voxels
+ *   in exactly one of H and H', n_hidden = |H'|, n_full = |F|; for the box form n_selected = n_matched = |M|.  Integer counts:
+ *   nothing depends on scheduling, nor on duplicates in the list or on how a host list is split into uploads.
+ * Host frames still waiting are launched first and a clean pass that returned without waiting is waited for, as hfpf_extract does;
+ * deferred errors surface as they do there.  Every call returns when H' is in place.  The first call that hides a voxel allocates
+ * the hidden bits (64 bytes per brick of max_bricks, counted in device_bytes).
+ * Rejected with HFPF_ERR_BAD_ARG (the handle stays usable, H is unchanged): struct_size != sizeof, an unknown op, flags or reserved
+ * != 0, a bad stride, a NULL voxels with n > 0, a device pointer not 4-byte aligned, NULL lo or hi, a result whose struct_size !=
+ * sizeof.  HFPF_ERR_STATE: a failed handle, as extract; a handle with an RCCL communicator; a handle that has exported or imported
+ * epoch records (the rule of hfpf_snapshot: a distributed form is not provided).  An empty handle, or one before its first clean
+ * pass, returns HFPF_OK with an all-zero result. */
+#define HFPF_HIDE 1u        /* H' = H + M */
+#define HFPF_SHOW 2u        /* H' = H - M */
+#define HFPF_HIDE_OTHERS 3u /* H' = H + (F - M) */
+
+typedef struct hfpf_hide_opts {
+    uint32_t struct_size;  /* = sizeof(hfpf_hide_opts) */
+    uint32_t op;           /* HFPF_HIDE, HFPF_SHOW or HFPF_HIDE_OTHERS */
+    uint32_t select_mask;  /* entry i is SELECTED iff select == NULL or (word & select_mask) == select_value */
+    uint32_t select_value;
+    uint32_t flags;        /* 0 */
+    uint32_t reserved;     /* 0 */
+} hfpf_hide_opts;
+
+typedef struct hfpf_hide_result {
+    uint32_t struct_size;  /* = sizeof(hfpf_hide_result), set by the caller */
+    uint32_t reserved;     /* written 0 */
+    uint64_t n_selected, n_matched, n_changed, n_hidden, n_full;
+} hfpf_hide_result;
+
+#ifdef __cplusplus
+static_assert(sizeof(hfpf_hide_opts) == 24, "hfpf_hide_opts is 24 bytes");
+static_assert(sizeof(hfpf_hide_result) == 48, "hfpf_hide_result is 48 bytes");
+#else
+_Static_assert(sizeof(hfpf_hide_opts) == 24, "hfpf_hide_opts is 24 bytes");
+_Static_assert(sizeof(hfpf_hide_result) == 48, "hfpf_hide_result is 48 bytes");
+#endif
+
+/* HFPF_OK if o passes the checks above, else HFPF_ERR_BAD_ARG (host code, no handle; the node shell uses it too). */
+int hfpf_check_hide_opts(const hfpf_hide_opts* o);
+/* voxels and select in pageable HOST memory: uploaded in chunks through the pinned staging. */
+int hfpf_hide_voxels(hfpf_handle* h, const hfpf_hide_opts* o, const void* voxels, uint64_t n, uint32_t voxel_stride, const void* select,
+                     uint32_t select_stride, hfpf_hide_result* res);
+/* The same with voxels and select in DEVICE memory (HBM), 4-byte aligned, read in place: the rows, labels or records a *_device
+ * read-out returned go straight back in.  o and res stay in host memory. */
+int hfpf_hide_voxels_device(hfpf_handle* h, const hfpf_hide_opts* o, const void* dev_voxels, uint64_t n, uint32_t voxel_stride,
+                            const void* dev_select, uint32_t select_stride, hfpf_hide_result* res);
+/* op on the box lo..hi (host memory, inclusive voxel indices). */
+int hfpf_hide_box(hfpf_handle* h, uint32_t op, const int32_t lo[3], const int32_t hi[3], hfpf_hide_result* res);
+/* H = {} (the hidden bits stay allocated). */
+int hfpf_show_all(hfpf_handle* h);
+/* The voxels of H in ascending (x,y,z) order, as hfpf_get_occupied lists the occupied ones: xyz may be NULL to query the count; at
+ * most cap triplets are written. */
+int hfpf_get_hidden(hfpf_handle* h, int32_t* xyz, uint64_t cap, uint64_t* n_out);
+
 /* <directory_name>/test_cloud.pcd (node.cpp:395): PCD v0.7 ASCII, FIELDS x y z rgb normal_x normal_y normal_z curvature */
 int hfpf_write_pcd(const hfpf_row* rows, uint64_t n_rows, const char* path);
 /* <directory_name>/meta.csv (node.cpp:396) with the header string of grid.hpp:462 */
@@ -1184,10 +1263,11 @@ int hfpf_get_occupied(hfpf_handle* h, int32_t* xyz, uint64_t cap, uint64_t* n_ou
  *
  * WHAT A RESTORE IS.  hfpf_clear followed by putting that state in place.  Afterwards the handle is indistinguishable from the
  * source handle at the moment of the snapshot, in this sense:
- *   1. every read-only call (extract, extract_filtered, get_occupied, is_dirty, render*, query*, extract_mesh*, raycast*, track*,
- *      extract_components*, compare_mesh*, align_mesh*, cover_mesh*, depth_consistency*)
- *      returns byte-identical output;
- *   2. any continuation (integrate*, clean, extract, clear, automatic frame ids included) produces byte-identical rows and occupied
+ *   1. every read-only call (extract, extract_filtered, get_occupied, get_hidden, is_dirty, render*, query*, extract_mesh*,
+ *      raycast*, track*, extract_components*, compare_mesh*, align_mesh*, cover_mesh*, depth_consistency*)
+ *      returns byte-identical output: the HIDDEN set of hfpf_hide_* travels in the snapshot, as one more section that is present only
+ *      when the set is not empty (a snapshot of a handle that hides nothing, hfpf_show_all included, is the blob it always was);
+ *   2. any continuation (integrate*, clean, extract, clear, hide_*, show_all, automatic frame ids included) produces byte-identical rows and occupied
  *      lists to the same continuation on the source handle;
  *   3. hfpf_get_counters agrees in every field results depend on: points_presented, points_zclip_pass, points_in_bbox,
  *      points_buffered, dep_pairs_tested, dep_pairs_member, voxels_occupied, voxels_with_normal, bricks_allocated, registrations,

@@ -95,10 +95,29 @@ int hfpf_node_set_mesh_output(hfpf_node* n, const hfpf_mesh_opts* opts);
 
 /* EXTENSION: with a component filter set, ~process saves the model without its specks: test_cloud.pcd and meta.csv (and the
  * published cloud) hold the rows hfpf_extract_components keeps with these options instead of every row.  mesh.ply and the
- * write_variants files are not filtered.  NULL turns it off again, the default: the files are then byte-identical to those of a node
+ * write_variants files are not filtered, unless hidden with hfpf_hide_voxels (hfpf_node_set_hide_filtered below does that for the
+ * rows this filter drops).  NULL turns it off again, the default: the files are then byte-identical to those of a node
  * that never called this.  Invalid options (hfpf_check_component_opts) are refused with HFPF_ERR_BAD_ARG and leave the setting as it
  * was. */
 int hfpf_node_set_component_filter(hfpf_node* n, const hfpf_component_opts* opts);
+
+/* EXTENSION: make every file leave out what the component filter drops.  With this on (default off) and a component filter set,
+ * ~process first runs the filter in HBM (hfpf_extract_components_device) and hides the rows it drops (hfpf_hide_voxels_device of
+ * include/hfpf.h: HFPF_HIDE_OTHERS on the kept rows, stride 64, read in place), then goes on as a node without a component filter.
+ * test_cloud.pcd and meta.csv are then byte-identical to those of the filter alone; mesh.ply, the write_variants files,
+ * deviation*.csv, coverage*.csv, alignment.csv and consistency*.csv are those of the direct calls on a handle with the same rows hidden
+ * (their own min_count options apply again: the filter's no longer replaces them).  ~process clears the grid at its end as before,
+ * which empties the hidden set.  With it off, or without a component filter, every file is byte-identical to that of a node that
+ * never called this. */
+int hfpf_node_set_hide_filtered(hfpf_node* n, int on);
+
+/* EXTENSION: the operator's "erase this" (HFPF_HIDE), "bring it back" (HFPF_SHOW) or "crop to this" (HFPF_HIDE_OTHERS) during a scan:
+ * hfpf_hide_box of include/hfpf.h on the node's grid for a box in fusion-frame metres, box_m = xmin,xmax,ymin,ymax,zmin,zmax.  Each
+ * bound becomes an inclusive voxel index with the voxel = floor((p - bbox_min) / res) of the query contract (saturated to the int32
+ * range; a NaN bound is refused with HFPF_ERR_BAD_ARG).  It runs under the grid's own lock, like save and load: a frame or a clean
+ * pass lands wholly before or wholly after it.  Rows that appear later are visible; ~process (its hfpf_clear) empties the set, ~reset does not touch the grid.
+ * res may be NULL.  Errors as hfpf_hide_box. */
+int hfpf_node_hide_box(hfpf_node* n, uint32_t op, const double box_m[6], hfpf_hide_result* res);
 
 /* EXTENSION: with a reference mesh set, ~process also measures the saved cloud against it (hfpf_compare_mesh of include/hfpf.h) and
  * writes, beside test_cloud.pcd, deviation.csv (header ix,iy,iz,signed_distance,distance,tri,flags, then one line per row of the saved
