@@ -207,9 +207,10 @@ struct Knobs {
     bool clean_small_nowait = true;  // small clean passes run without a mid-pass read-back (HFPF_CLEAN_NOWAIT=0 restores it)
     bool clean_overlap = true;       // HFPF_CLEAN_OVERLAP=0: k_buffer stays behind the update kernel and a clean pass runs on the engine's stream alone
     bool early_replay = true;        // HFPF_EARLY_REPLAY=0: the buffer replay of an overlapped small pass stays behind the dependant-table update (k_replay)
-    bool trace_clean = false;        // HFPF_TRACE_CLEAN=1: one stderr line per clean pass that launches kernels: which stream its front half took, which replay
+    bool trace_clean = false;        // HFPF_TRACE_CLEAN=1: one stderr line per clean pass that launches kernels: which stream its front half took, which replay; a second one ("clean forms"): which size-gated forms
     float test_bin_scale = 1.f;      // tests only (HFPF_TEST_BIN_SCALE): shrinks the planned bin regions so that they overflow into the direct forms
     bool test_table_skip = false;    // tests only (HFPF_TEST_TABLE_SKIP=1): Tables::test_table_skip
+    CleanLimits limits;              // tests only (HFPF_TEST_STREAM_MIN, _SORT_MIN, _REG_LARGE_MIN, _GATE4_MIN, each >= 1): the sizes at which a clean pass changes its form
     bool mailbox = true;             // HFPF_MAILBOX=0: counter read-backs by blit copies + synchronize
     int test_dev_tile = kDevTileDefault;  // tests only (HFPF_TEST_DEV_TILE=8..256): triangles per LDS tile of k_dev_rows
     int cons_chunk = 0;              // HFPF_CONSISTENCY_CHUNK=1..64: frames per chunk of k_consistency (0: plan_consistency decides); tests
@@ -611,6 +612,13 @@ Knobs read_knobs()
     if (const char* bs = getenv("HFPF_TEST_BIN_SCALE")) k.test_bin_scale = std::max(0.f, std::min(1.f, (float)atof(bs)));
     const char* ts = getenv("HFPF_TEST_TABLE_SKIP");
     k.test_table_skip = ts && ts[0] == '1';
+    const auto limit = [](const char* name, uint64_t& v) {
+        if (const char* e = getenv(name)) v = (uint64_t)std::max(1ll, atoll(e));
+    };
+    limit("HFPF_TEST_STREAM_MIN", k.limits.stream_min_single);
+    limit("HFPF_TEST_SORT_MIN", k.limits.sort_min_walked);
+    limit("HFPF_TEST_REG_LARGE_MIN", k.limits.reg_large_min);
+    limit("HFPF_TEST_GATE4_MIN", k.limits.gate4_min);
     if (const char* dt = getenv("HFPF_TEST_DEV_TILE")) k.test_dev_tile = std::max(8, std::min(atoi(dt), kDevTileMax));
     if (const char* cc = getenv("HFPF_CONSISTENCY_CHUNK")) k.cons_chunk = std::max(1, std::min(atoi(cc), (int)kConsChunkFrames));
     const char* mb = getenv("HFPF_MAILBOX");
@@ -1513,7 +1521,7 @@ int dist_exchange_locked(hfpf_handle* h, int pre_rc)
 void launch_gate(hfpf_handle* h, hipStream_t s, const uint32_t* cells_a, uint64_t n_a, const uint32_t* cells_b, uint64_t n_b, uint32_t* pend_out)
 {
     const uint64_t n = n_a + n_b;
-    if (n >= (1ull << 20))
+    if (gate_tiles(n, h->knobs.limits) == 4)
         hipLaunchKernelGGL(k_gate<4>, dim3(blocks_for(n, 256 * 4)), dim3(256), 0, s, h->g, h->t, cells_a, n_a, cells_b, n_b, pend_out);
     else
         hipLaunchKernelGGL(k_gate<1>, dim3(blocks_for(n, 256)), dim3(256), 0, s, h->g, h->t, cells_a, n_a, cells_b, n_b, pend_out);
@@ -1558,7 +1566,7 @@ int clean_locked(hfpf_handle* h, int pre_rc)
     if ((rc = check_device_errors(h))) return rc;
     const unsigned long long* c = h->h_ctr;
     const CleanPlan p = plan_clean({c[C_OCC], c[C_NORMALS], c[C_PEND], c[C_REG], c[C_PREREG], c[C_DEP]}, t.max_occ, t.max_reg, t.max_dep, h->ss.gate_done,
-                                   h->ss.pend_valid, h->g.K, early, h->knobs.clean_small_nowait, h->knobs.early_replay);
+                                   h->ss.pend_valid, h->g.K, early, h->knobs.clean_small_nowait, h->knobs.early_replay, h->knobs.limits);
     const uint64_t n_occ = p.n_occ, n_normals = p.n_normals, n_pend = p.n_pend, n_new_occ = p.n_new_occ, n_in = p.n_in, reg_ub = p.reg_ub;
     h->ss.occ_exported = n_occ;  // everything occupied so far (locally or imported) has been exchanged
     h->ss.frames_exported = std::max(h->ss.frames_exported, h->ss.frames_seen);  // ... and the viewpoints of the frames the last export covered
@@ -1591,6 +1599,19 @@ int clean_locked(hfpf_handle* h, int pre_rc)
     if (h->knobs.trace_clean)
         fprintf(stderr, "hfpf: clean pass %llu: %llu candidates, front half %s, replay %s\n", (unsigned long long)h->clean_passes, (unsigned long long)n_in,
                 p.overlap ? "beside the update kernel" : "on the engine's stream", p.replay_early ? "fed from the registrations" : "behind the dependant-table update");
+    // ... and a second line with the size-gated forms the pass takes (CleanLimits): a no-wait pass knows them here, a waited one ahead of its replay
+    const auto trace_forms = [&](const ReplayPlan* rp, uint64_t touched, const char* compacting) {
+        if (!h->knobs.trace_clean) return;
+        char tail[160];
+        if (rp)
+            snprintf(tail, sizeof tail, "waited: single %llu, walked %llu, %s, use_marks %u", (unsigned long long)(touched - rp->walked), (unsigned long long)rp->walked,
+                     rp->walked && rp->sort_walked ? "sorted" : "unsorted", rp->use_marks);
+        else
+            snprintf(tail, sizeof tail, "no-wait");
+        fprintf(stderr, "hfpf: clean forms %llu: gate tiles %d (%llu pending + %llu new), register %s, compacting %s, %s\n", (unsigned long long)h->clean_passes,
+                gate_tiles(n_in, h->knobs.limits), (unsigned long long)n_pend, (unsigned long long)n_new_occ, register_large(n_in, h->knobs.limits) ? "large" : "small", compacting, tail);
+    };
+    if (p.no_wait) trace_forms(nullptr, 0, "no");
     // the front half: beside the update kernel on a stream of its own, or on the engine's like everything behind k_register
     const hipStream_t front = p.overlap ? h->front_stream : h->stream;
     if (p.overlap) {
@@ -1612,7 +1633,7 @@ int clean_locked(hfpf_handle* h, int pre_rc)
     const unsigned cand_bits = HFPF_MORTON_IDS ? 3u * std::max(h->g.key_sy, std::max(h->g.key_sx - h->g.key_sy, h->g.key_bits - h->g.key_sx)) : h->g.key_bits;
     if ((rc = sort_keys_u64(h, t.cand_key, (uint64_t*)h->keys_a.p, n_in, cand_bits, front))) return rc;
     hipLaunchKernelGGL(k_normal, dim3(blocks_for(n_in, 128)), dim3(128), 0, front, h->g, t, (const uint64_t*)h->keys_a.p, kCountOnDevice, n_normals);
-    const bool reg_small = n_in < (1ull << 18);  // tiles per workgroup: kernels.hpp k_register
+    const bool reg_small = !register_large(n_in, h->knobs.limits);  // tiles per workgroup: kernels.hpp k_register
     const uint64_t reg_tile = 256ull * (reg_small ? kRegTilesSmall : kRegTilesLarge);  // step-major, whole workgroups per step
     const uint64_t reg_blocks = ((n_in + reg_tile - 1) / reg_tile) * (2ull * (uint64_t)h->g.K + 1ull);
     const uint32_t count_deps = p.full ? 0u : 1u;  // (the compacting rebuild counts for itself, from zero)
@@ -1690,7 +1711,8 @@ int clean_locked(hfpf_handle* h, int pre_rc)
         if ((rc = check_device_errors(h))) return rc;
     }
     // buffer replay of the cells that gained registrants in this pass (touched_list is still intact)
-    const ReplayPlan rp = plan_replay(inc_touched, h->h_ctr[C_TOUCHED_SINGLE], full, h->binned, h->knobs.stream_replay, h->ss.n_bricks_known);
+    const ReplayPlan rp = plan_replay(inc_touched, h->h_ctr[C_TOUCHED_SINGLE], full, h->binned, h->knobs.stream_replay, h->ss.n_bricks_known, h->knobs.limits);
+    trace_forms(&rp, inc_touched, !full ? "no" : p.full ? "planned" : "after the incremental update ran out");
     if (rp.stream) {
         const uint32_t nbk = (uint32_t)h->ss.n_bricks_known;
         const bool wide = h->knobs.upd_shape_forced >= 0 ? h->knobs.upd_shape_forced == 1 : h->upd_wide;  // the shape the dependant updates of this session take

@@ -3,7 +3,9 @@
 //
 // Pure functions over counters, capacities, knobs and session fields: they decide and count, and nothing else.  The two functions that
 // enqueue (integrate_device_locked and clean_locked) read a const plan from here; launch geometry stays at the launch
-// sites, with the kernels' tile constants.  The thresholds below lie far beyond what a test can reach in seconds on the device.
+// sites, with the kernels' tile constants.  The defaults of the clean pass's thresholds (CleanLimits) lie far beyond what a test can
+// reach in seconds on the device: the plan functions take them as a parameter, tests/host_plan_check.cpp pins the defaults, and a
+// device test lowers them (HFPF_TEST_*_MIN) so that frames of test size take the forms behind them (tests/test_gpu_clean_forms.py).
 #pragma once
 
 #include <algorithm>
@@ -18,6 +20,20 @@ constexpr int kProbeFrames = HFPF_PROBE_FRAMES;  // frames of a plan-less batch 
 constexpr uint64_t kSlotsPerBrick = 512;         // = kBrickCells (tables.hpp)
 
 // ---- the clean pass ----
+
+// The sizes at which a clean pass changes its form.  The defaults are what every session runs with; only tests set others.
+struct CleanLimits {
+    uint64_t stream_min_single = 1ull << 16;  // touched cells in single-run bricks from which the replay streams their runs (plan_replay)
+    uint64_t sort_min_walked = 1ull << 18;    // cells of the chain walk from which they are sorted into slot order first (plan_replay)
+    uint64_t reg_large_min = 1ull << 18;      // candidates from which k_register takes its large tile count (register_large)
+    uint64_t gate4_min = 1ull << 20;          // cells from which k_gate takes four tiles per workgroup (gate_tiles)
+    uint64_t nowait_max_reg = 1ull << 21;     // registration bound below which a pass is SMALL (plan_clean)
+};
+
+// Tiles per workgroup of k_gate over n cells (pending + new): four only when the input is large enough to fill the device that way.
+inline int gate_tiles(uint64_t n, const CleanLimits& lim = CleanLimits{}) { return n >= lim.gate4_min ? 4 : 1; }
+// k_register over n_in candidates: kRegTilesLarge tiles per workgroup (kernels.hpp) or kRegTilesSmall.
+inline bool register_large(uint64_t n_in, const CleanLimits& lim = CleanLimits{}) { return n_in >= lim.reg_large_min; }
 
 // The pass may take its head-of-pass counters from the early publish of the integrate call before it (evaluated before that read-back).
 inline bool clean_starts_early(bool clean_overlap, bool dist_on, bool binned, bool has_mailbox, unsigned long long pub_seq, unsigned long long early_seq)
@@ -41,7 +57,7 @@ struct CleanPlan {
     bool replay_early;   // the replay too goes beside the update kernel
 };
 inline CleanPlan plan_clean(const CleanHead& c, uint64_t max_occ, uint64_t max_reg, uint64_t max_dep, uint64_t gate_done, bool pend_valid, int K, bool early,
-                            bool clean_small_nowait, bool early_replay)
+                            bool clean_small_nowait, bool early_replay, const CleanLimits& lim = CleanLimits{})
 {
     CleanPlan p{};
     p.n_occ = std::min<uint64_t>(c.occ, max_occ);
@@ -65,7 +81,7 @@ inline CleanPlan plan_clean(const CleanHead& c, uint64_t max_occ, uint64_t max_r
     // and the host does not wait for the pass at all (no mid-pass read-back: the GPU is not left idle for a host round trip, and
     // the next integrate call is enqueued behind the pass at once).  The bound above makes sure the pass cannot run out of dep[]
     // half-way (the one overflow the host would have to repair by compacting).
-    p.no_wait = !p.full && p.reg_ub < (1ull << 21) && clean_small_nowait;
+    p.no_wait = !p.full && p.reg_ub < lim.nowait_max_reg && clean_small_nowait;
     p.replay_early = p.overlap && p.no_wait && early_replay;
     return p;
 }
@@ -78,7 +94,8 @@ struct ReplayPlan {
     unsigned slot_bits;  // key bits of that sort: slot = brick * 512 + cell
     uint32_t use_marks;  // (a compacting rebuild leaves no notes and the lists in no particular order)
 };
-inline ReplayPlan plan_replay(uint64_t inc_touched, unsigned long long touched_single, bool full, bool binned, bool stream_replay, uint64_t n_bricks_known)
+inline ReplayPlan plan_replay(uint64_t inc_touched, unsigned long long touched_single, bool full, bool binned, bool stream_replay, uint64_t n_bricks_known,
+                              const CleanLimits& lim = CleanLimits{})
 {
     ReplayPlan r{};
     r.use_marks = full ? 0u : 1u;
@@ -86,11 +103,11 @@ inline ReplayPlan plan_replay(uint64_t inc_touched, unsigned long long touched_s
     // brick is new in it) replay by streaming that run: worth its launch over every brick when enough of the touched cells
     // lie in such bricks.  The chain walk takes the others.
     const uint64_t single = full ? 0 : std::min<uint64_t>(touched_single, inc_touched);
-    r.stream = !full && binned && stream_replay && single >= (1ull << 16);
+    r.stream = !full && binned && stream_replay && single >= lim.stream_min_single;
     r.walked = r.stream ? inc_touched - single : inc_touched;
     // a 256-point tile appends consecutive log entries for neighbouring cells, so walking the cells in slot (brick-major)
     // order lets adjacent lanes share cache lines of the log; a short list is not worth the sort's launches
-    r.sort_walked = r.walked >= (1ull << 18);
+    r.sort_walked = r.walked >= lim.sort_min_walked;
     r.slot_bits = 9;  // the brick count is as of the read-back just ahead of the replay
     while ((1ull << r.slot_bits) < (n_bricks_known + 2) * kSlotsPerBrick && r.slot_bits < 32) r.slot_bits++;
     return r;

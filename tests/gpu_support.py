@@ -6,6 +6,7 @@ modules and conftests only."""
 import contextlib
 import ctypes as C
 import math
+import re
 
 import numpy as np
 
@@ -66,6 +67,70 @@ CONTRACT = ("points_presented", "points_zclip_pass", "points_in_bbox", "points_b
 def contract_counters(g):
     c = g.counters()
     return {k: c[k] for k in CONTRACT}
+
+
+# ---- batches from HBM and what HFPF_TRACE_CLEAN=1 says of the passes behind them ---------------------------------------------------
+
+class DeviceFrames:
+    """The frames of a scenes.Scene in HBM of one handle, handed over in batches with hfpf_integrate_device.  clouds: the frames as one
+    uint8 array (frame_bytes(sc)), so that several handles share one rendering of the scene."""
+
+    def __init__(self, g, sc, clouds=None):
+        self.g, self.sc = g, sc
+        self.stride = sc.W * sc.H * 16
+        clouds = frame_bytes(sc) if clouds is None else clouds
+        assert clouds.nbytes == self.stride * sc.n_frames, "%d bytes for %d frames of %d" % (clouds.nbytes, sc.n_frames, self.stride)
+        self.dev = g.device_alloc(clouds.nbytes)
+        g.device_upload(self.dev, clouds)
+
+    def integrate(self, first, n):
+        poses = np.stack([np.asarray(self.sc.poses[f], np.float64).reshape(12) for f in range(first, first + n)])
+        self.g.integrate_device(self.dev + first * self.stride, n, self.stride, self.sc.W * self.sc.H, poses)
+
+    def free(self):
+        self.g.device_free(self.dev)
+
+
+def frame_bytes(sc):
+    """Every frame of a scenes.Scene (packed 16-byte records), one behind the other."""
+    return np.concatenate([np.ascontiguousarray(sc.frame(f)).view(np.uint8).reshape(-1) for f in range(sc.n_frames)])
+
+
+# every variable that changes which form an integrate call or a clean pass takes (INTEGRATION.md 6a): a run "with defaults" has none set
+FORM_VARIABLES = ("HFPF_CLEAN_NOWAIT", "HFPF_CLEAN_OVERLAP", "HFPF_EARLY_REPLAY", "HFPF_STREAM_REPLAY", "HFPF_MAILBOX", "HFPF_BIN_SPARE",
+                  "HFPF_BIN_SLACK", "HFPF_UPD_SHAPE", "HFPF_UPDATE_FORM", "HFPF_BINNED", "HFPF_HOST_BATCH", "HFPF_TEST_BIN_SCALE",
+                  "HFPF_TEST_TABLE_SKIP", "HFPF_TEST_STREAM_MIN", "HFPF_TEST_SORT_MIN", "HFPF_TEST_REG_LARGE_MIN", "HFPF_TEST_GATE4_MIN")
+
+_PASS_LINE = re.compile(r"hfpf: clean pass (\d+): (\d+) candidates, front half (beside the update kernel|on the engine's stream), "
+                        r"replay (fed from the registrations|behind the dependant-table update)$")
+_FORMS_LINE = re.compile(r"hfpf: clean forms (\d+): gate tiles ([14]) \((\d+) pending \+ (\d+) new\), register (small|large), "
+                         r"compacting (no|planned|after the incremental update ran out), "
+                         r"(no-wait|waited: single (\d+), walked (\d+), (sorted|unsorted), use_marks ([01]))$")
+
+
+def clean_trace(err):
+    """What the stderr text of a run with HFPF_TRACE_CLEAN=1 says of its clean passes: (lines, passes).  lines: every `hfpf: clean`
+    line as printed.  passes: one dict per pass that launched kernels, in order, from its two lines -- pass, candidates, beside (front
+    half beside the update kernel), fed (replay fed from the registrations), gate_tiles, pending, new, register ('small' | 'large'),
+    compacting ('no' | 'planned' | 'after the incremental update ran out'), waited, and for a waited pass single (cells streamed),
+    walked, sorted, use_marks (0 and False for a no-wait pass).  A line with either prefix that does not parse fails, and so does a
+    pass with one line of the two."""
+    lines = [ln for ln in err.splitlines() if ln.startswith("hfpf: clean ")]
+    first, second = {}, {}
+    for ln in lines:
+        if ln.startswith("hfpf: clean pass"):
+            m = _PASS_LINE.match(ln)
+            assert m, "trace line not understood: %r" % ln
+            first[int(m.group(1))] = dict(candidates=int(m.group(2)), beside=m.group(3).startswith("beside"), fed=m.group(4).startswith("fed"))
+        elif ln.startswith("hfpf: clean forms"):
+            m = _FORMS_LINE.match(ln)
+            assert m, "trace line not understood: %r" % ln
+            waited = m.group(7) != "no-wait"
+            second[int(m.group(1))] = dict(gate_tiles=int(m.group(2)), pending=int(m.group(3)), new=int(m.group(4)), register=m.group(5),
+                                           compacting=m.group(6), waited=waited, single=int(m.group(8) or 0), walked=int(m.group(9) or 0),
+                                           sorted=m.group(10) == "sorted", use_marks=int(m.group(11) or 0))
+    assert sorted(first) == sorted(second), "passes with a `clean pass` line %r, with a `clean forms` line %r" % (sorted(first), sorted(second))
+    return lines, [dict(first[n], **second[n], **{"pass": n}) for n in sorted(first)]
 
 
 def held_out(synth_mod, W=640, H=480, f=HELD_OUT):

@@ -131,6 +131,88 @@ void replay()
     CHECK(plan_replay(1, 0, false, true, true, 1ull << 30).slot_bits == 32);
 }
 
+// The sizes at which a clean pass changes its form: the defaults are pinned, and each field decides at limit - 1 / limit, at its
+// default and lowered (what tests/test_gpu_clean_forms.py sets on the device).
+static_assert(CleanLimits{}.stream_min_single == 65536, "default of stream_min_single");
+static_assert(CleanLimits{}.sort_min_walked == 262144, "default of sort_min_walked");
+static_assert(CleanLimits{}.reg_large_min == 262144, "default of reg_large_min");
+static_assert(CleanLimits{}.gate4_min == 1048576, "default of gate4_min");
+static_assert(CleanLimits{}.nowait_max_reg == 2097152, "default of nowait_max_reg");
+
+void limits()
+{
+    const CleanLimits def{};
+    CleanLimits low{};
+    low.stream_min_single = 256;
+    low.sort_min_walked = 1024;
+    low.reg_large_min = 1024;
+    low.gate4_min = 4096;
+    low.nowait_max_reg = 700;
+
+    // k_gate: four tiles from gate4_min cells on
+    CHECK(gate_tiles(1048575) == 1 && gate_tiles(1048576) == 4 && gate_tiles(0) == 1);
+    CHECK(gate_tiles(1048575, def) == 1 && gate_tiles(1048576, def) == 4);
+    CHECK(gate_tiles(4095, low) == 1 && gate_tiles(4096, low) == 4);
+    // k_register: the large tile count from reg_large_min candidates on
+    CHECK(!register_large(262143) && register_large(262144) && !register_large(0));
+    CHECK(!register_large(262143, def) && register_large(262144, def));
+    CHECK(!register_large(1023, low) && register_large(1024, low));
+
+    // the streaming replay: single-run cells (cut to the touched ones) from stream_min_single on
+    ReplayPlan r = plan_replay(100000, 65535, false, true, true, 100, def);
+    CHECK(!r.stream && r.walked == 100000);
+    r = plan_replay(100000, 65536, false, true, true, 100, def);
+    CHECK(r.stream && r.walked == 34464);
+    r = plan_replay(1000, 255, false, true, true, 100, low);
+    CHECK(!r.stream && r.walked == 1000 && !r.sort_walked);
+    r = plan_replay(1000, 256, false, true, true, 100, low);
+    CHECK(r.stream && r.walked == 744 && !r.sort_walked && r.use_marks == 1);
+    // more single-run cells reported than cells touched: cut, everything streams, nothing is walked or sorted
+    r = plan_replay(300, 70000, false, true, true, 100, low);
+    CHECK(r.stream && r.walked == 0 && !r.sort_walked);
+    r = plan_replay(255, 70000, false, true, true, 100, low);  // ... and the cut count decides
+    CHECK(!r.stream && r.walked == 255);
+    r = plan_replay(65535, 1ull << 40, false, true, true, 100);
+    CHECK(!r.stream && r.walked == 65535);
+    r = plan_replay(65536, 1ull << 40, false, true, true, 100);
+    CHECK(r.stream && r.walked == 0 && !r.sort_walked);
+    // a compacting rebuild never streams and leaves no notes, however many single-run cells and however low the limit
+    r = plan_replay(5000, 5000, true, true, true, 100, low);
+    CHECK(!r.stream && r.walked == 5000 && r.sort_walked && r.use_marks == 0);
+    r = plan_replay(1ull << 20, 1ull << 20, true, true, true, 100);
+    CHECK(!r.stream && r.walked == (1ull << 20) && r.sort_walked && r.use_marks == 0);
+    CHECK(!plan_replay(5000, 5000, false, false, true, 100, low).stream);  // un-binned
+    CHECK(!plan_replay(5000, 5000, false, true, false, 100, low).stream);  // knob off
+
+    // the sorted walk: from sort_min_walked walked cells on, counted behind what streams
+    CHECK(!plan_replay(262143, 0, false, true, true, 100, def).sort_walked);
+    CHECK(plan_replay(262144, 0, false, true, true, 100, def).sort_walked);
+    CHECK(!plan_replay(1023, 0, false, true, true, 100, low).sort_walked);
+    CHECK(plan_replay(1024, 0, false, true, true, 100, low).sort_walked);
+    r = plan_replay(1280, 256, false, true, true, 100, low);  // 1024 left to walk
+    CHECK(r.stream && r.walked == 1024 && r.sort_walked);
+    r = plan_replay(1280, 257, false, true, true, 100, low);
+    CHECK(r.stream && r.walked == 1023 && !r.sort_walked);
+    CHECK(plan_replay(1280, 256, false, true, true, 6, low).slot_bits == 12);  // the key bits do not depend on the limits
+
+    // a SMALL pass: registration bound below nowait_max_reg (K = 3: 7 per candidate)
+    auto fresh = [](uint64_t n_in, const CleanLimits& lim) {
+        return plan_clean(CleanHead{n_in, 0, 0, 0, 0, 0}, kBig, kBig, kBig, 0, false, 3, true, true, true, lim);
+    };
+    CleanPlan p = fresh(299593, def);
+    CHECK(p.reg_ub == 2097151 && p.no_wait && p.replay_early);
+    p = fresh(299594, def);
+    CHECK(p.reg_ub == 2097158 && !p.no_wait && !p.replay_early && p.overlap);
+    p = fresh(99, low);  // 693 < 700
+    CHECK(p.reg_ub == 693 && p.no_wait && p.replay_early);
+    p = fresh(100, low);  // 700
+    CHECK(p.reg_ub == 700 && !p.no_wait && !p.replay_early && p.overlap && !p.full);
+    // the other limits do not enter plan_clean
+    CleanLimits other = low;
+    other.nowait_max_reg = def.nowait_max_reg;
+    CHECK(fresh(299593, other).no_wait && !fresh(299594, other).no_wait);
+}
+
 void probe()
 {
     CHECK(probe_frames_for(1) == 8 && probe_frames_for(63) == 8);
@@ -278,6 +360,7 @@ int main()
     clamps();
     early_start();
     replay();
+    limits();
     probe();
     tiles();
     bin_plans();

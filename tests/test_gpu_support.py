@@ -159,3 +159,28 @@ def test_uploaded_frees_what_it_allocated():
             assert g.memory[a] == _rows(3).tobytes() and len(g.memory[b]) == 0 and g.freed == []
             raise RuntimeError("the body failed")
     assert sorted(g.freed) == [a, b]
+
+
+PASS_1 = "hfpf: clean pass 1: 71159 candidates, front half on the engine's stream, replay behind the dependant-table update"
+FORMS_1 = "hfpf: clean forms 1: gate tiles 4 (0 pending + 71159 new), register large, compacting no, no-wait"
+PASS_2 = "hfpf: clean pass 2: 43535 candidates, front half beside the update kernel, replay fed from the registrations"
+FORMS_2 = "hfpf: clean forms 2: gate tiles 1 (11786 pending + 31749 new), register small, compacting planned, waited: single 300, walked 2000, sorted, use_marks 0"
+
+
+def test_clean_trace_reads_both_lines_of_a_pass():
+    lines, passes = G.clean_trace("\n".join(["hfpf: shape window", PASS_1, FORMS_1, "something else", PASS_2, FORMS_2, ""]))
+    assert lines == [PASS_1, FORMS_1, PASS_2, FORMS_2]
+    assert passes[0] == {"pass": 1, "candidates": 71159, "beside": False, "fed": False, "gate_tiles": 4, "pending": 0, "new": 71159, "register": "large",
+                         "compacting": "no", "waited": False, "single": 0, "walked": 0, "sorted": False, "use_marks": 0}
+    assert passes[1] == {"pass": 2, "candidates": 43535, "beside": True, "fed": True, "gate_tiles": 1, "pending": 11786, "new": 31749, "register": "small",
+                         "compacting": "planned", "waited": True, "single": 300, "walked": 2000, "sorted": True, "use_marks": 0}
+    _, passes = G.clean_trace(PASS_2 + "\n" + FORMS_2.replace(", sorted,", ", unsorted,").replace("planned", "after the incremental update ran out"))
+    assert not passes[0]["sorted"] and passes[0]["compacting"] == "after the incremental update ran out"
+    assert G.clean_trace("") == ([], [])
+
+
+@pytest.mark.parametrize("text", [PASS_1, FORMS_1, PASS_1 + "\n" + FORMS_2, PASS_1 + "\n" + FORMS_1 + " or so",
+                                  PASS_1 + "\n" + FORMS_1.replace("tiles 4", "tiles 2"), PASS_1.replace("71159 candidates", "many candidates") + "\n" + FORMS_1])
+def test_clean_trace_rejects_a_missing_or_garbled_line(text):
+    with pytest.raises(AssertionError):
+        G.clean_trace(text)
