@@ -1627,12 +1627,17 @@ __global__ __launch_bounds__(128) void k_normal(const GridParams g, const Tables
                     total++;
                 }
         }
-    F3 normal = m.normal(total);
+    // grid.hpp:301: getNormal leaves the normal alone when fewer than 3 cells are valid and occupied (a gate below 2 lets such a
+    // candidate through), and the oracle settles "alone" as zero; the moments of one or two points would give 0/0 instead
+    F3 normal = {0.f, 0.f, 0.f};
     const F3 centre = voxel_center(g, x, y, z);  // grid.hpp:391
-    const uint32_t ff = t.first_frame[slot];
-    F3 vp = {0.f, 0.f, 0.f};
-    if (ff != kNoFrame && ff < t.max_frames) vp = F3{t.frame_vp[3 * (uint64_t)ff], t.frame_vp[3 * (uint64_t)ff + 1], t.frame_vp[3 * (uint64_t)ff + 2]};
-    normal = orient_normal(normal, vp, centre);
+    if (total >= 3) {
+        normal = m.normal(total);
+        const uint32_t ff = t.first_frame[slot];
+        F3 vp = {0.f, 0.f, 0.f};
+        if (ff != kNoFrame && ff < t.max_frames) vp = F3{t.frame_vp[3 * (uint64_t)ff], t.frame_vp[3 * (uint64_t)ff + 1], t.frame_vp[3 * (uint64_t)ff + 2]};
+        normal = orient_normal(normal, vp, centre);
+    }
     const uint64_t nid = base + r + 1;
     t.nv_key[nid] = key;
     t.nv_slot[nid] = slot;

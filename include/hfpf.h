@@ -57,7 +57,11 @@ typedef struct hfpf_config {
     double bbox[6];           /* xmin,xmax,ymin,ymax,zmin,zmax; launch param `bounding_box` (node.cpp:451,162) */
     int32_t k;                /* occupancy stencil half-width; must be 2 (grid.hpp:334 hard-codes 125 probes) */
     int32_t K;                /* line half-length in voxel steps (template arg, node.cpp:311,317) = 3 */
-    int32_t gate;             /* a voxel gets a normal when occupied neighbours > gate (grid.hpp:352) = 20 */
+    int32_t gate;             /* a voxel gets a normal when occupied neighbours > gate (grid.hpp:352) = 20.  The count includes the
+                                 voxel itself and only cells of the 5 x 5 x 5 stencil inside the grid.  Any value is accepted.  Below 2
+                                 the gate also passes voxels with one or two such cells: no plane fits fewer than three points
+                                 (grid.hpp:301), and their rows keep a zero normal (see hfpf_row).  At 2 to 4 every stencil that passes
+                                 can still be collinear, and a collinear stencil gives a NaN normal */
     double cylinder_radius;   /* kCylinderRadius, grid.hpp:36 = 0.001 */
     double ball_radius;       /* kBballRadius, grid.hpp:35 = 0.015 */
     double z_clip_min;        /* kZmin, node.cpp:92 = 0.28 (camera frame, strict) */
@@ -81,12 +85,28 @@ typedef struct hfpf_config {
     uint64_t max_call_points;
 } hfpf_config;
 
-/* One emitted voxel = one line of test_cloud.pcd + one line of meta.csv (grid.hpp:466-480). 64 bytes. */
+/* One emitted voxel = one line of test_cloud.pcd + one line of meta.csv (grid.hpp:466-480). 64 bytes.
+ *
+ * THE NORMAL is the reference's plane fit of the occupied stencil cells' centres (single-pass f32 covariance, pcl::eigen33), turned
+ * towards the viewpoint of the voxel's first frame.  It is a unit vector but for two cases, which are the reference's arithmetic and
+ * are reproduced, not repaired:
+ *   NaN in all three components: the cross products of the eigen-solve are all exactly zero and the normal is 0/0.  That happens
+ *     when the covariance has rank one (every collinear stencil, at any gate that lets one pass) and when the f32 covariance of a flat
+ *     stencil cancels far from the origin (a surface along the grid at 100 m and more, where the coordinates' squares eat the f32
+ *     mantissa; HFPF_FLAG_PCL_SHIFTED_COV takes the moments about the first point and has none of these).  Neighbours of such a
+ *     voxel may carry normals that are rounding noise: unit vectors, deterministic, unrelated to the surface.
+ *   zero in all three components: fewer than three stencil cells were valid and occupied, so there was no fit (gate below 2 only).
+ * Either row has count == 0, x = y = z = 0 and zero statistics: no point lies within a cylinder about a NaN or zero-length line,
+ * and the voxel registers in no other cell (NaN) or in its own cell alone (zero).  Sign and payload of the NaN are unspecified;
+ * compare by isnan.  Every read-out that takes rows by count >= max(1, min_count) (render, track, query and what is built on it:
+ * mesh, raycast, cover) never sees such a row; extract, extract_filtered and components at min_count 0, compare_mesh, depth_consistency,
+ * hide and snapshot carry it.  A NaN normal fails every gate on a normal (components' min_normal_dot, depth_consistency's min_cos: a NaN
+ * compares false); a zero normal has the dot product 0 with everything. */
 typedef struct hfpf_row {
     int32_t ix, iy, iz;  /* voxel index triplet */
     uint32_t count;      /* points in cylinder (VoxelInfo::count) */
     float x, y, z;       /* cylinder-filtered mean of projected points (VoxelInfo::centroid); (0,0,0) when count==0 */
-    float nx, ny, nz;    /* VoxelInfo::normal */
+    float nx, ny, nz;    /* VoxelInfo::normal: a unit vector, or NaN NaN NaN, or 0 0 0 (above); the latter two only with count == 0 */
     float sdx, sdy, sdz; /* VoxelInfo::sd (population variance per axis, as the reference's Welford recurrence) */
     float mean_dist;     /* VoxelInfo::mean_dist */
     float sd_dist;       /* VoxelInfo::sd_dist */
