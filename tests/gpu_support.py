@@ -101,6 +101,13 @@ FORM_VARIABLES = ("HFPF_CLEAN_NOWAIT", "HFPF_CLEAN_OVERLAP", "HFPF_EARLY_REPLAY"
                   "HFPF_BIN_SLACK", "HFPF_UPD_SHAPE", "HFPF_UPDATE_FORM", "HFPF_BINNED", "HFPF_HOST_BATCH", "HFPF_TEST_BIN_SCALE",
                   "HFPF_TEST_TABLE_SKIP", "HFPF_TEST_STREAM_MIN", "HFPF_TEST_SORT_MIN", "HFPF_TEST_REG_LARGE_MIN", "HFPF_TEST_GATE4_MIN")
 
+# the clean pass's lowered thresholds (HFPF_TEST_*_MIN) and HFPF_CLEAN_NOWAIT=0, so that frames of test size take the size-gated forms
+STREAM_MIN, SORT_MIN, REG_LARGE_MIN, GATE4_MIN = 256, 1024, 1024, 4096
+WAITED = {"HFPF_CLEAN_NOWAIT": "0"}
+STREAM = {"HFPF_TEST_STREAM_MIN": str(STREAM_MIN)}
+SORT = {"HFPF_TEST_SORT_MIN": str(SORT_MIN)}
+LARGE = {"HFPF_TEST_GATE4_MIN": str(GATE4_MIN), "HFPF_TEST_REG_LARGE_MIN": str(REG_LARGE_MIN)}
+
 _PASS_LINE = re.compile(r"hfpf: clean pass (\d+): (\d+) candidates, front half (beside the update kernel|on the engine's stream), "
                         r"replay (fed from the registrations|behind the dependant-table update)$")
 _FORMS_LINE = re.compile(r"hfpf: clean forms (\d+): gate tiles ([14]) \((\d+) pending \+ (\d+) new\), register (small|large), "

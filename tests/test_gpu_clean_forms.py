@@ -21,16 +21,12 @@ import numpy as np
 import pytest
 
 import scenes
-from gpu_support import FORM_VARIABLES, SMALL_CAPS, DeviceFrames, clean_trace, contract_counters, frame_bytes
+from gpu_support import (FORM_VARIABLES, GATE4_MIN, LARGE, SMALL_CAPS, SORT, SORT_MIN, STREAM, STREAM_MIN, WAITED, DeviceFrames, clean_trace,
+                         contract_counters, frame_bytes)
 
 pytestmark = pytest.mark.gpu
 
 EPOCH = 12
-STREAM_MIN, SORT_MIN, REG_LARGE_MIN, GATE4_MIN = 256, 1024, 1024, 4096
-WAITED = {"HFPF_CLEAN_NOWAIT": "0"}
-STREAM = {"HFPF_TEST_STREAM_MIN": str(STREAM_MIN)}
-SORT = {"HFPF_TEST_SORT_MIN": str(SORT_MIN)}
-LARGE = {"HFPF_TEST_GATE4_MIN": str(GATE4_MIN), "HFPF_TEST_REG_LARGE_MIN": str(REG_LARGE_MIN)}
 
 Run = collections.namedtuple("Run", "rows occ contract counters passes")
 
