@@ -356,6 +356,9 @@ struct hfpf_handle {
     DevBuf dev_mesh{bufs}, dev_tri{bufs}, dev_bins{bufs}, dev_pairs{bufs};
     DevBuf align_dev{bufs};  // hfpf_align_mesh*: one iteration's deviation records
     DevBuf cov_bins{bufs};   // hfpf_cover_mesh*: the summary, the 64-bit sample total, the triangles' sample counts and their offsets
+    // hfpf_plan_views*: the samples' target marks; their scan; the targets (point + triangle, weight); the views' bitsets and the
+    // remaining set; the cover records, the scores, the gains and the call's state words
+    DevBuf plan_mark{bufs}, plan_scan{bufs}, plan_targets{bufs}, plan_bits{bufs}, plan_ctr{bufs};
     // hfpf_depth_consistency*: one upload's frames of the host form, the poses, the records / summary / keep marks and their scan
     DevBuf cons_in{bufs}, cons_pose{bufs}, cons_recs{bufs};
     DevBuf hide_in{bufs}, hide_mark{bufs};  // hfpf_hide_*: one upload's entries of the host form (voxels, then selector words); the mark words and the call's counters
@@ -3823,11 +3826,21 @@ struct CovCounters {  // zeroed together in front of the setup
 };
 static_assert(sizeof(CovCounters) == sizeof(CovSummary) + 8, "the summary and the total are adjacent");
 
+// The samples of a cover as hfpf_plan_views* meets them again.
+struct CovSamples {
+    CovTri* geo;       // per triangle
+    uint32_t* offset;  // n_tris + 1
+    uint32_t* target;  // total + 1: 1 = IN_BBOX and not COVERED (the last word 0, for the scan); NULL without samples
+    uint64_t total;
+};
+
 // Validated arguments in, the mesh on the device, n_tris > 0, under the lock.  The transformed vertices (compare's kernel); per
 // triangle a record, the geometry and a sample count; the scan of the counts; one lane per sample; per triangle its share of the
 // summary.  The 64-bit total is read back once in front of the scan (whose 32-bit total cannot tell an overflow): the capacity
-// check and the size of the sample launch.  *out: the n_tris records.  Not timed: hfpf_get_kernel_time has no id for it.
-static int cover_locked(hfpf_handle* h, const hfpf_cover_opts* o, const MeshRef& m, const double* pose, bool on_device, ResultSet* out, hfpf_coverage_summary* summary)
+// check and the size of the sample launch.  cov: room for the n_tris records.  keep != NULL (hfpf_plan_views*): the samples are also
+// marked as targets (k_cov_samples<true>) and *keep describes them.  Not timed: hfpf_get_kernel_time has no id for it.
+static int cover_run_locked(hfpf_handle* h, const hfpf_cover_opts* o, const MeshRef& m, const double* pose, TriCoverage* cov, hfpf_coverage_summary* summary,
+                            CovSamples* keep)
 {
     int rc;
     const uint64_t n_tris = m.n_tris, T1 = n_tris + 1;
@@ -3836,10 +3849,6 @@ static int cover_locked(hfpf_handle* h, const hfpf_cover_opts* o, const MeshRef&
     if ((rc = dev_tri_scratch_locked(h, m, &V, &geo)) || (rc = scratch(h, h->cov_bins, ScratchLayout().add(&ctr, 1).add(&count, T1).add(&offset, T1)))) return rc;
     CovSummary* d_sum = &ctr->sum;
     unsigned long long* d_total = &ctr->total;
-    ResultSet set;
-    set.add((size_t)n_tris * sizeof(TriCoverage));
-    if ((rc = result_alloc(h, set, on_device, "cover_mesh"))) return rc;
-    TriCoverage* cov = (TriCoverage*)set.a[0].dev;
     DevParams vp{};  // what k_dev_verts reads of it
     memcpy(vp.T, pose, sizeof vp.T);
     vp.n_verts = m.n_verts, vp.n_tris = (uint32_t)n_tris, vp.stride = m.stride;
@@ -3861,8 +3870,17 @@ static int cover_locked(hfpf_handle* h, const hfpf_cover_opts* o, const MeshRef&
         uint64_t scanned = 0;
         if ((rc = scan_counts_locked(h, count, offset, n_tris, &scanned))) return rc;
         if (scanned != total) return fail(h, HFPF_ERR_STATE, "cover_mesh: the scan of the sample counts disagrees with their sum (internal)");
-        hipLaunchKernelGGL(k_cov_samples, dim3(blocks_for(total, 256)), dim3(256), 0, h->stream, h->g, h->t, p, offset, geo, (uint32_t)total, cov);
+        if (keep) {
+            if ((rc = scratch_n(h, h->plan_mark, total + 1, &keep->target))) return rc;
+            HIPCHK(h, hipMemsetAsync(keep->target + total, 0, 4, h->stream));
+            hipLaunchKernelGGL(k_cov_samples<true>, dim3(blocks_for(total, 256)), dim3(256), 0, h->stream, h->g, h->t, p, offset, geo, (uint32_t)total, cov,
+                               keep->target);
+        } else {
+            hipLaunchKernelGGL(k_cov_samples<false>, dim3(blocks_for(total, 256)), dim3(256), 0, h->stream, h->g, h->t, p, offset, geo, (uint32_t)total, cov,
+                               (uint32_t*)nullptr);
+        }
     }
+    if (keep) keep->geo = geo, keep->offset = offset, keep->total = total;
     hipLaunchKernelGGL(k_cov_finish, dim3(blocks_for(n_tris, 256)), dim3(256), 0, h->stream, (uint32_t)n_tris, cov, geo, d_sum);
     CovSummary hs;
     if ((e = hipGetLastError()) == hipSuccess) e = hipMemcpyAsync(&hs, d_sum, sizeof hs, hipMemcpyDeviceToHost, h->stream);
@@ -3870,6 +3888,16 @@ static int cover_locked(hfpf_handle* h, const hfpf_cover_opts* o, const MeshRef&
     if (e != hipSuccess) return fail(h, HFPF_ERR_HIP, "cover_mesh: %s", hipGetErrorString(e));
     static_assert(sizeof(CovSummary) == sizeof(hfpf_coverage_summary), "the device summary is the public one, max_distance as bits");
     memcpy(summary, &hs, sizeof hs);
+    return HFPF_OK;
+}
+
+// A cover into records of its own.  *out: the n_tris records.
+static int cover_locked(hfpf_handle* h, const hfpf_cover_opts* o, const MeshRef& m, const double* pose, bool on_device, ResultSet* out, hfpf_coverage_summary* summary)
+{
+    ResultSet set;
+    set.add((size_t)m.n_tris * sizeof(TriCoverage));
+    if (int rc = result_alloc(h, set, on_device, "cover_mesh")) return rc;
+    if (int rc = cover_run_locked(h, o, m, pose, (TriCoverage*)set.a[0].dev, summary, nullptr)) return rc;
     set.keep(out);
     return HFPF_OK;
 }
@@ -3924,6 +3952,210 @@ int hfpf_cover_mesh(hfpf_handle* h, const hfpf_cover_opts* o, const void* verts,
 }
 
 void hfpf_free_coverage(hfpf_tri_coverage* cov) { free(cov); }
+
+// ---- view planning (include/hfpf.h) ---------------------------------------------------------------------------------------------
+int hfpf_check_plan_opts(const hfpf_plan_opts* o)
+{
+    if (!o || o->struct_size != sizeof(hfpf_plan_opts) || (o->flags & ~(HFPF_PLAN_TWO_SIDED | HFPF_PLAN_MODEL_OCCLUDES)) || o->reserved0 != 0 || o->reserved != 0)
+        return HFPF_ERR_BAD_ARG;
+    if (hfpf_check_cover_opts(&o->cover) != HFPF_OK || !view_opts_ok(&o->view)) return HFPF_ERR_BAD_ARG;
+    if (!(std::isfinite(o->occluder_near) && o->occluder_near > 0.0 && o->occluder_near <= o->view.z_near)) return HFPF_ERR_BAD_ARG;
+    if (!(std::isfinite(o->min_cos) && o->min_cos >= -1.0 && o->min_cos <= 1.0)) return HFPF_ERR_BAD_ARG;
+    if (!(std::isfinite(o->tolerance) && o->tolerance > 0.0 && o->tolerance <= 1.0)) return HFPF_ERR_BAD_ARG;
+    if (!(std::isfinite(o->slope) && o->slope >= 0.0 && o->slope <= 1.0)) return HFPF_ERR_BAD_ARG;
+    return o->max_views >= 1 && o->max_views <= 256 ? HFPF_OK : HFPF_ERR_BAD_ARG;
+}
+
+constexpr uint32_t kPlanMaxViews = 4096;
+constexpr uint64_t kPlanMaxPairs = 1ull << 35;  // (target, view) pairs: 4 GiB of bitsets
+
+// The views of one depth-buffer chunk: the zbuf rule of a render on 4-byte words, or what HFPF_PLAN_CHUNK=1..64 forces (tests).
+static uint32_t plan_chunk_views(uint64_t WH, uint32_t n_views)
+{
+    uint64_t per = std::min<uint64_t>({(uint64_t)kRenderChunkViews, std::max<uint64_t>(1, kRenderZbufBytes / (4 * WH)), std::max<uint32_t>(n_views, 1)});
+    if (const char* e = getenv("HFPF_PLAN_CHUNK")) {
+        const long v = strtol(e, nullptr, 10);
+        if (v >= 1 && v <= 64) per = std::min<uint64_t>(per, (uint64_t)v);
+    }
+    return (uint32_t)per;
+}
+
+// Validated arguments in, the mesh on the device, n_tris > 0, under the lock.  The cover with the samples marked; the scan of the
+// marks (its total, the number of targets, is read back: the capacity check and the size of everything behind it); then, without a
+// host wait: compaction, per chunk of views the occluder splats and the visibility words, the greedy
+// rounds, the triangle records.  One read-back of the scores and the state words ends the call.  *out: the n_tris records
+// (absent without want_plan).  Not timed: hfpf_get_kernel_time has no id for it.
+static int plan_locked(hfpf_handle* h, const hfpf_plan_opts* o, const MeshRef& m, const double* pose, const double* poses, uint32_t n_views, bool on_device,
+                       bool want_plan, ResultSet* out, hfpf_view_score* scores, hfpf_plan_summary* summary)
+{
+    int rc;
+    const uint64_t n_tris = m.n_tris, NV1 = std::max<uint32_t>(n_views, 1);
+    PlanState* st; PlanScore* score; unsigned long long* gain; TriCoverage* cov;
+    if ((rc = scratch(h, h->plan_ctr, ScratchLayout().add(&st, 1).add(&score, NV1).add(&gain, 2 * NV1).add(&cov, n_tris)))) return rc;
+    ResultSet set;
+    set.add((size_t)n_tris * sizeof(TriPlan), !want_plan);
+    if ((rc = result_alloc(h, set, on_device, "plan_views"))) return rc;
+    TriPlan* plan = (TriPlan*)set.a[0].dev;  // NULL when absent
+    hfpf_plan_summary S;
+    memset(&S, 0, sizeof S);
+    CovSamples cs{};
+    if ((rc = cover_run_locked(h, &o->cover, m, pose, cov, &S.coverage, &cs))) return rc;
+    // hi * 2^32 + lo >= 2^62 iff hi + (lo >> 32) >= 2^30 (both words are below 2^63)
+    if (S.coverage.area_q40_hi + (S.coverage.area_q40_lo >> 32) >= (1ull << 30)) return fail(h, HFPF_ERR_CAPACITY, "plan_views: the mesh's area is 2^22 m^2 or more: the q40 sums would not fit");
+    uint64_t n_targets = 0;
+    uint32_t* toff = nullptr;
+    if (cs.total) {
+        if ((rc = scratch_n(h, h->plan_scan, cs.total + 1, &toff)) || (rc = scan_counts_locked(h, cs.target, toff, cs.total, &n_targets))) return rc;
+    }
+    if (n_targets * n_views > kPlanMaxPairs)  // nothing on the handle was touched: it stays usable
+        return fail(h, HFPF_ERR_CAPACITY, "plan_views: %llu targets x %u views exceed the 2^35 pairs a call takes (fewer views, or a larger spacing)",
+                    (unsigned long long)n_targets, n_views);
+    const uint64_t n_words = (n_targets + 63) / 64, W1 = std::max<uint64_t>(n_words, 1), WH = (uint64_t)o->view.width * o->view.height;
+    float4* tp; unsigned long long *tw, *remaining, *bits;
+    if ((rc = scratch(h, h->plan_targets, ScratchLayout().add(&tp, std::max<uint64_t>(n_targets, 1)).add(&tw, std::max<uint64_t>(n_targets, 1))))) return rc;
+    if ((rc = scratch(h, h->plan_bits, ScratchLayout().add(&remaining, W1).add(&bits, std::max<uint64_t>(n_views * n_words, 1))))) return rc;
+    const bool look = n_targets && n_views;
+    RowSet rows{};
+    uint32_t* zbuf = nullptr;
+    double* pose_d = nullptr;
+    const uint32_t per_chunk = plan_chunk_views(WH, n_views);
+    PlanParams p{};
+    if (look) {
+        if (o->flags & HFPF_PLAN_MODEL_OCCLUDES) {
+            const ExtractOpts opt{std::max(1.0, o->view.min_count), -1, 0};  // the rows of a render
+            if ((rc = build_rows_locked(h, h->t.stats, opt, &rows))) return rc;
+            if (rows.n > 0xFFFFFFFFull) return fail(h, HFPF_ERR_CAPACITY, "plan_views: %llu rows exceed the 2^32 - 1 a splat launch takes", (unsigned long long)rows.n);
+        }
+        if ((rc = scratch_n(h, h->zbuf, per_chunk * WH, &zbuf)) || (rc = scratch_n(h, h->render_pose, 12ull * n_views, &pose_d))) return rc;
+        HIPCHK(h, hipMemcpyAsync(pose_d, poses, (size_t)n_views * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        p.width = o->view.width, p.height = o->view.height;
+        p.cull = (o->view.flags & HFPF_RENDER_CULL_BACKFACES) ? 1u : 0u, p.two_sided = (o->flags & HFPF_PLAN_TWO_SIDED) ? 1u : 0u;
+        p.radius = o->view.splat_radius, p.max_radius = o->view.max_splat_radius;
+        p.fx = o->view.fx, p.fy = o->view.fy, p.cx = o->view.cx, p.cy = o->view.cy, p.z_near = o->view.z_near, p.z_far = o->view.z_far;
+        p.occ_near = o->occluder_near;
+        p.r_num_samples = (0.5 * o->cover.spacing) * std::max(o->view.fx, o->view.fy);
+        p.r_num_rows = (0.5 * h->g.res) * std::max(o->view.fx, o->view.fy);
+        p.min_cos = o->min_cos, p.tolerance = o->tolerance, p.slope = o->slope;
+    }
+
+    HIPCHK(h, hipMemsetAsync(st, 0, sizeof(PlanState) + NV1 * (sizeof(PlanScore) + 16), h->stream));  // the state, the scores and the gains are adjacent
+    hipLaunchKernelGGL(k_plan_begin, dim3(blocks_for(std::max<uint64_t>(W1, n_views), 256)), dim3(256), 0, h->stream, (uint32_t)n_targets, n_words, remaining, n_views,
+                       score);
+    if (plan) hipLaunchKernelGGL(k_plan_tri_begin, dim3(blocks_for(n_tris, 256)), dim3(256), 0, h->stream, (uint32_t)n_tris, cov, plan);
+    if (n_targets) {
+        hipLaunchKernelGGL(k_plan_compact, dim3(blocks_for(cs.total, 256)), dim3(256), 0, h->stream, cs.offset, cs.geo, (uint32_t)n_tris, (uint32_t)cs.total,
+                           cs.target, toff, tp, tw);
+    }
+    HIPCHK(h, hipGetLastError());
+    const unsigned t_blocks = blocks_for(n_targets, 256);
+    for (uint32_t v0 = 0; look && v0 < n_views; v0 += per_chunk) {
+        p.n_views = std::min(per_chunk, n_views - v0);
+        HIPCHK(h, hipMemsetAsync(zbuf, 0xFF, p.n_views * WH * 4, h->stream));
+        hipLaunchKernelGGL(k_plan_splat_samples, dim3(blocks_for(cs.total, 256)), dim3(256), 0, h->stream, cs.offset, cs.geo, (uint32_t)n_tris, (uint32_t)cs.total,
+                           pose_d + 12ull * v0, p, zbuf);
+        if (rows.n)
+            hipLaunchKernelGGL(k_plan_splat_rows, dim3(blocks_for(rows.n, 256)), dim3(256), 0, h->stream, rows.rows, (uint32_t)rows.n, pose_d + 12ull * v0, p, zbuf);
+        hipLaunchKernelGGL(k_plan_visible, dim3(t_blocks, p.n_views), dim3(256), 0, h->stream, tp, tw, (uint32_t)n_targets, cs.geo, pose_d + 12ull * v0, p, zbuf, v0,
+                           n_words, bits, score);
+        HIPCHK(h, hipGetLastError());
+    }
+    const uint32_t rounds = look ? std::min(o->max_views, n_views) : 0u;  // every round takes a view or ends the selection
+    for (uint32_t k = 0; k < rounds; k++) {
+        hipLaunchKernelGGL(k_plan_gain, dim3(t_blocks, n_views), dim3(256), 0, h->stream, tw, (uint32_t)n_targets, n_words, bits, remaining, score, st, gain);
+        hipLaunchKernelGGL(k_plan_argmax, dim3(1), dim3(256), 0, h->stream, k, n_views, (unsigned long long)o->min_gain_q40, score, gain, st);
+        hipLaunchKernelGGL(k_plan_take, dim3(blocks_for(n_words, 256)), dim3(256), 0, h->stream, n_words, bits, remaining, st);
+    }
+    if (n_targets)
+        hipLaunchKernelGGL(k_plan_finish, dim3(t_blocks), dim3(256), 0, h->stream, tp, tw, (uint32_t)n_targets, n_words, look ? n_views : 0u, bits, remaining, plan, st);
+    HIPCHK(h, hipGetLastError());
+    PlanState hs;
+    std::vector<PlanScore> hsc(NV1);
+    HIPCHK(h, hipMemcpyAsync(&hs, st, sizeof hs, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(hsc.data(), score, NV1 * sizeof(PlanScore), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    S.n_views = n_views, S.n_selected = hs.n_selected;
+    S.n_targets = n_targets, S.n_reachable = hs.n_reachable, S.n_planned = hs.n_planned;
+    S.target_q40 = hs.target_q40, S.reachable_q40 = hs.reachable_q40, S.planned_q40 = hs.planned_q40;
+    static_assert(sizeof(PlanScore) == sizeof(hfpf_view_score) && sizeof(TriPlan) == sizeof(hfpf_tri_plan), "the device records are the public ones");
+    if (n_views) memcpy(scores, hsc.data(), (size_t)n_views * sizeof(PlanScore));
+    *summary = S;
+    set.keep(out);
+    return HFPF_OK;
+}
+
+// The checks of both forms.  0 = fine, else the text of the fault.
+static const char* plan_args_fault(const hfpf_plan_opts* o, const MeshRef& m, const double* pose, const double* poses, uint32_t n_views, const void* scores,
+                                   const void* summary, bool on_device)
+{
+    if (hfpf_check_plan_opts(o) != HFPF_OK) return "invalid hfpf_plan_opts";
+    if (const char* f = mesh_args_fault(m, pose)) return f;
+    if (!scores || !summary) return "NULL scores or summary";
+    if (n_views > kPlanMaxViews) return "more than 4096 views";
+    if (n_views && !poses) return "NULL poses";
+    for (uint64_t i = 0; i < 12ull * n_views; i++)
+        if (!std::isfinite(poses[i])) return "a view's pose is not finite";
+    if (on_device && mesh_misaligned(m)) return "device mesh pointers must be 4-byte aligned";
+    return nullptr;
+}
+
+// n_tris = 0: nothing to plan.
+static void plan_empty(uint32_t n_views, hfpf_view_score* scores, hfpf_plan_summary* summary)
+{
+    memset(summary, 0, sizeof *summary);
+    summary->n_views = n_views;
+    for (uint32_t v = 0; v < n_views; v++) {
+        memset(&scores[v], 0, sizeof scores[v]);
+        scores[v].rank = -1;
+    }
+}
+
+int hfpf_plan_views_device(hfpf_handle* h, const hfpf_plan_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* dev_tris,
+                           uint64_t n_tris, const double* pose_3x4, const double* poses, uint32_t n_views, hfpf_view_score* scores, hfpf_tri_plan** dev_plan,
+                           hfpf_plan_summary* summary)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    const MeshRef m{dev_verts, n_verts, vertex_stride, dev_tris, n_tris};
+    if (const char* f = plan_args_fault(o, m, pose_3x4, poses, n_views, scores, summary, true)) return fail(h, HFPF_ERR_BAD_ARG, "plan_views_device: %s", f);
+    if (int rc = local_read_prologue_locked(h, "plan_views")) return rc;
+    ResultSet set;
+    if (n_tris) {
+        if (int rc = plan_locked(h, o, m, pose_3x4, poses, n_views, true, dev_plan != nullptr, &set, scores, summary)) return rc;
+    } else {
+        plan_empty(n_views, scores, summary);
+    }
+    if (dev_plan) *dev_plan = (hfpf_tri_plan*)set.a[0].dev;
+    return HFPF_OK;
+}
+
+int hfpf_plan_views(hfpf_handle* h, const hfpf_plan_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
+                    const double* pose_3x4, const double* poses, uint32_t n_views, hfpf_view_score* scores, hfpf_tri_plan** plan, hfpf_plan_summary* summary)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    const MeshRef m{verts, n_verts, vertex_stride, tris, n_tris};
+    if (const char* f = plan_args_fault(o, m, pose_3x4, poses, n_views, scores, summary, false)) return fail(h, HFPF_ERR_BAD_ARG, "plan_views: %s", f);
+    if (int rc = local_read_prologue_locked(h, "plan_views")) return rc;
+    void* host[3] = {nullptr, nullptr, nullptr};
+    if (n_tris) {
+        MeshRef d;
+        if (int rc = upload_mesh_locked(h, "plan_views", m, &d)) return rc;
+        // the scores and the summary reach the caller only when the records have too: a failed download writes nothing
+        std::vector<hfpf_view_score> sc(std::max<uint32_t>(n_views, 1));
+        hfpf_plan_summary s;
+        ResultSet set;
+        if (int rc = plan_locked(h, o, d, pose_3x4, poses, n_views, false, plan != nullptr, &set, sc.data(), &s)) return rc;
+        if (int rc = result_to_host(h, set, "plan_views", host)) return rc;
+        if (n_views) memcpy(scores, sc.data(), (size_t)n_views * sizeof(hfpf_view_score));
+        *summary = s;
+    } else {
+        plan_empty(n_views, scores, summary);
+    }
+    if (plan) *plan = (hfpf_tri_plan*)host[0];
+    return HFPF_OK;
+}
+
+void hfpf_free_plan(hfpf_tri_plan* plan) { free(plan); }
 
 // ---- rows that depth frames see through (include/hfpf.h) -------------------------------------------------------------------
 int hfpf_check_consistency_opts(const hfpf_consistency_opts* o)

@@ -4568,8 +4568,37 @@ __global__ __launch_bounds__(256) void k_cov_setup(const CovParams p, const uint
 // its sub-triangle the one numbered l = g - offset[k]: strip m = isqrt(l) holds i = n - 1 - m and 2 m + 1 sub-triangles, t = l - m^2
 // of them has kind = t & 1 and j = t >> 1.  Lanes of a wave hold ascending k, so a run of equal k is a contiguous stretch of lanes:
 // a segmented shuffle reduction leaves the run's sums in its first lane, which issues the atomics.
+// Sample s_idx < total: its triangle k (the first with offset[k + 1] > s_idx; offset[n_tris] = total > s_idx) and its f32 point p.
+// Shared by k_cov_samples and the plan kernels, which meet the same samples again.
+__device__ __forceinline__ F3 cov_sample_point(const uint32_t* __restrict__ offset, const CovTri* __restrict__ geo, const uint32_t n_tris, const uint32_t s_idx,
+                                               uint32_t& k)
+{
+    uint32_t lo = 0, hi = n_tris;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (offset[mid + 1] <= s_idx) lo = mid + 1;
+        else hi = mid;
+    }
+    k = lo;
+    const CovTri* tr = &geo[k];
+    const uint32_t n = tr->n, l = s_idx - offset[k];  // l < n^2 <= 4096
+    uint32_t m = (uint32_t)sqrtf((float)l);
+    m -= m * m > l ? 1u : 0u;
+    m += (m + 1u) * (m + 1u) <= l ? 1u : 0u;
+    const uint32_t tt = l - m * m, kind = tt & 1u, i = n - 1u - m, j = tt >> 1;
+    const double v = (double)(3u * i + 1u + kind) / (double)(3u * n), w = (double)(3u * j + 1u + kind) / (double)(3u * n);
+    F3 q;
+    q.x = (float)((tr->A[0] + v * tr->ab[0]) + w * tr->ac[0]);
+    q.y = (float)((tr->A[1] + v * tr->ab[1]) + w * tr->ac[1]);
+    q.z = (float)((tr->A[2] + v * tr->ab[2]) + w * tr->ac[2]);
+    return q;
+}
+
+// EMIT (hfpf_plan_views*): target[s] = 1 for a sample that is IN_BBOX and not COVERED, else 0.  Without it `target` is not touched.
+template <bool EMIT>
 __global__ __launch_bounds__(256) void k_cov_samples(const GridParams g, const Tables t, const CovParams p, const uint32_t* __restrict__ offset,
-                                                     const CovTri* __restrict__ geo, const uint32_t total, TriCoverage* __restrict__ cov)
+                                                     const CovTri* __restrict__ geo, const uint32_t total, TriCoverage* __restrict__ cov,
+                                                     uint32_t* __restrict__ target)
 {
     const uint64_t gg = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u;
@@ -4578,25 +4607,8 @@ __global__ __launch_bounds__(256) void k_cov_samples(const GridParams g, const T
     uint32_t in_bbox = 0, covered = 0, dist_bits = 0;
     long long sum_dist = 0;
     if (live) {
-        const uint32_t s_idx = (uint32_t)gg;
-        uint32_t lo = 0, hi = p.n_tris;  // the first k with offset[k + 1] > s_idx (offset[n_tris] = total > s_idx)
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            if (offset[mid + 1] <= s_idx) lo = mid + 1;
-            else hi = mid;
-        }
-        k = lo;
+        const F3 q = cov_sample_point(offset, geo, p.n_tris, (uint32_t)gg, k);
         const CovTri* tr = &geo[k];
-        const uint32_t n = tr->n, l = s_idx - offset[k];  // l < n^2 <= 4096
-        uint32_t m = (uint32_t)sqrtf((float)l);
-        m -= m * m > l ? 1u : 0u;
-        m += (m + 1u) * (m + 1u) <= l ? 1u : 0u;
-        const uint32_t tt = l - m * m, kind = tt & 1u, i = n - 1u - m, j = tt >> 1;
-        const double v = (double)(3u * i + 1u + kind) / (double)(3u * n), w = (double)(3u * j + 1u + kind) / (double)(3u * n);
-        F3 q;
-        q.x = (float)((tr->A[0] + v * tr->ab[0]) + w * tr->ac[0]);
-        q.y = (float)((tr->A[1] + v * tr->ab[1]) + w * tr->ac[1]);
-        q.z = (float)((tr->A[2] + v * tr->ab[2]) + w * tr->ac[2]);
         if (__builtin_isfinite(q.x) && __builtin_isfinite(q.y) && __builtin_isfinite(q.z) && valid_point(g, q)) {  // USED, then IN_BBOX: k_query's tests
             in_bbox = 1u;
             int32_t vx[3];
@@ -4613,6 +4625,7 @@ __global__ __launch_bounds__(256) void k_cov_samples(const GridParams g, const T
                 }
             }
         }
+        if (EMIT) target[gg] = in_bbox & ~covered;
     }
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -4667,6 +4680,303 @@ __global__ __launch_bounds__(256) void k_cov_finish(const uint32_t n_tris, const
     for (int i = 0; i < 11; i++)
         if (w[i]) atomicAdd(&out[i], w[i]);
     if (bits) atomicMax(&sum->max_distance_bits, bits);
+}
+
+
+// ---- view planning (hfpf_plan_views*; contract in include/hfpf.h, numpy restatement tests/plan_ref.py) -----------------------------
+// The cover kernels above mark the TARGETS (k_cov_samples<true>); a scan of the marks numbers them and k_plan_compact stores each
+// target's point, triangle and weight.  Per chunk of at most 64 views: every sample of the mesh (k_plan_splat_samples) and, on
+// request, every drawn row of the model (k_plan_splat_rows) is an occluder in a 32-bit depth buffer -- the bits of a positive f32
+// order as integers, so the pixel's nearest depth is an atomicMin that does not depend on the order --, then k_plan_visible runs one
+// lane per (target, view): a wave's ballot is one 64-bit word of the view's visibility bitset.  The greedy rounds (k_plan_gain,
+// k_plan_argmax, k_plan_take) are enqueued without a host wait; a device-side `done` word makes the rounds behind the last useful
+// one fall through.  Everything summed is an integer, so nothing depends on scheduling or on the chunking of the views.
+struct PlanScore {  // = hfpf_view_score
+    int32_t rank;
+    uint32_t n_in_view, n_facing, n_visible;
+    unsigned long long visible_q40, gain_q40, gain_samples;
+};
+static_assert(sizeof(PlanScore) == 40, "view score is 40 bytes");
+
+struct TriPlan {  // = hfpf_tri_plan
+    uint32_t n_targets, n_reachable, n_planned, flags;
+};
+static_assert(sizeof(TriPlan) == 16, "triangle plan record is 16 bytes");
+
+struct PlanState {  // the words of one call, zeroed together
+    unsigned long long n_reachable, n_planned, target_q40, reachable_q40, planned_q40;  // n_targets is the scan's total
+    uint32_t done, best, n_selected, pad;
+};
+
+struct PlanParams {
+    uint32_t width, height;
+    uint32_t n_views;      // views of this chunk
+    uint32_t cull;         // HFPF_RENDER_CULL_BACKFACES, on the rows
+    uint32_t two_sided;    // HFPF_PLAN_TWO_SIDED
+    int32_t radius;        // >= 0 fixed, -1 auto
+    int32_t max_radius;
+    uint32_t pad;
+    double fx, fy, cx, cy, z_near, z_far, occ_near;
+    double r_num_samples;  // (0.5 * cover.spacing) * max(fx, fy)
+    double r_num_rows;     // (0.5 * res) * max(fx, fy)
+    double min_cos, tolerance, slope;
+};
+
+// The render contract's projection of (x, y, z) into the view T: false unless z_lo < zc < z_far and |u|, |v| < 2^30.
+__device__ __forceinline__ bool plan_project(const double* T, const PlanParams& p, const double z_lo, const double x, const double y, const double z, double& dx,
+                                             double& dy, double& dz, double& zc, int& pu, int& pv)
+{
+    dx = x - T[3], dy = y - T[7], dz = z - T[11];
+    zc = (T[2] * dx + T[6] * dy) + T[10] * dz;
+    if (!(z_lo < zc && zc < p.z_far)) return false;
+    const double xc = (T[0] * dx + T[4] * dy) + T[8] * dz;
+    const double yc = (T[1] * dx + T[5] * dy) + T[9] * dz;
+    const double u = (xc / zc) * p.fx + p.cx;
+    const double w = (yc / zc) * p.fy + p.cy;
+    if (!(fabs(u) < 1073741824.0 && fabs(w) < 1073741824.0)) return false;
+    pu = (int)floor(u + 0.5), pv = (int)floor(w + 0.5);
+    return true;
+}
+
+// One occluder into the depth buffer zv of its view: the splat of k_render_splat on 32-bit words (the same plain load in front of
+// the atomic: words only ever decrease, so the skip is exact).  |pu|, |pv| <= 2^30 and r <= 15: the window's bounds do not wrap.
+__device__ __forceinline__ void plan_splat(const PlanParams& p, uint32_t* __restrict__ zv, const double zc, const int pu, const int pv, const double r_num)
+{
+    int r = p.radius;
+    if (r < 0) {
+        const double ra = floor(r_num / zc);
+        r = ra < (double)p.max_radius ? (int)ra : p.max_radius;
+    }
+    const int x0 = max(pu - r, 0), x1 = min(pu + r, (int)p.width - 1);
+    const int y0 = max(pv - r, 0), y1 = min(pv + r, (int)p.height - 1);
+    const uint32_t word = __float_as_uint((float)zc);
+    for (int py = y0; py <= y1; py++)
+        for (int px = x0; px <= x1; px++) {
+            uint32_t* a = zv + (uint64_t)py * p.width + (uint64_t)px;
+            if (__hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > word) atomicMin(a, word);
+        }
+}
+
+// One lane per sample of `total`, looping over the chunk's views (their poses in LDS, as in k_render_splat): every sample of a valid
+// triangle with a finite point occludes, in the box or not, target or not.
+__global__ __launch_bounds__(256) void k_plan_splat_samples(const uint32_t* __restrict__ offset, const CovTri* __restrict__ geo, const uint32_t n_tris,
+                                                            const uint32_t total, const double* __restrict__ poses, const PlanParams p,
+                                                            uint32_t* __restrict__ zbuf)
+{
+    __shared__ double s_pose[kRenderChunkViews * 12];
+    for (uint32_t i = threadIdx.x; i < p.n_views * 12u; i += blockDim.x) s_pose[i] = poses[i];
+    __syncthreads();
+    const uint64_t gg = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (gg >= total) return;
+    uint32_t k;
+    const F3 q = cov_sample_point(offset, geo, n_tris, (uint32_t)gg, k);
+    if (!(__builtin_isfinite(q.x) && __builtin_isfinite(q.y) && __builtin_isfinite(q.z))) return;
+    const uint64_t WH = (uint64_t)p.width * p.height;
+    for (uint32_t v = 0; v < p.n_views; v++) {
+        double dx, dy, dz, zc;
+        int pu, pv;
+        if (plan_project(&s_pose[12 * v], p, p.occ_near, q.x, q.y, q.z, dx, dy, dz, zc, pu, pv)) plan_splat(p, zbuf + v * WH, zc, pu, pv, p.r_num_samples);
+    }
+}
+
+// HFPF_PLAN_MODEL_OCCLUDES: one lane per drawn row of the model, with the rows' own splat rule and the back-face cull of the view.
+__global__ __launch_bounds__(256) void k_plan_splat_rows(const Row* __restrict__ rows, const uint32_t n_rows, const double* __restrict__ poses,
+                                                         const PlanParams p, uint32_t* __restrict__ zbuf)
+{
+    __shared__ double s_pose[kRenderChunkViews * 12];
+    for (uint32_t i = threadIdx.x; i < p.n_views * 12u; i += blockDim.x) s_pose[i] = poses[i];
+    __syncthreads();
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_rows) return;
+    const float4 q0 = *reinterpret_cast<const float4*>(&rows[j].x);   // x, y, z, nx
+    const float2 q1 = *reinterpret_cast<const float2*>(&rows[j].ny);  // ny, nz
+    const double nx = q0.w, ny = q1.x, nz = q1.y;
+    const uint64_t WH = (uint64_t)p.width * p.height;
+    for (uint32_t v = 0; v < p.n_views; v++) {
+        double dx, dy, dz, zc;
+        int pu, pv;
+        if (!plan_project(&s_pose[12 * v], p, p.occ_near, q0.x, q0.y, q0.z, dx, dy, dz, zc, pu, pv)) continue;
+        if (p.cull && !(((nx * dx + ny * dy) + nz * dz) < 0.0)) continue;
+        plan_splat(p, zbuf + v * WH, zc, pu, pv, p.r_num_rows);
+    }
+}
+
+// One lane per sample: a target stores its point with its triangle in the fourth word, and its weight, at its number toff[s].
+__global__ __launch_bounds__(256) void k_plan_compact(const uint32_t* __restrict__ offset, const CovTri* __restrict__ geo, const uint32_t n_tris,
+                                                      const uint32_t total, const uint32_t* __restrict__ target, const uint32_t* __restrict__ toff,
+                                                      float4* __restrict__ tp, unsigned long long* __restrict__ tw)
+{
+    const uint64_t gg = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (gg >= total || !target[gg]) return;
+    uint32_t k;
+    const F3 q = cov_sample_point(offset, geo, n_tris, (uint32_t)gg, k);
+    const uint32_t n = geo[k].n;
+    const double area_d = 0.5 * geo[k].s;
+    const uint32_t at = toff[gg];
+    tp[at] = make_float4(q.x, q.y, q.z, __uint_as_float(k));
+    tw[at] = !(area_d < 0x1p23) ? 0ull : (unsigned long long)rint((area_d / (double)(n * n)) * 0x1p40);
+}
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    return v;  // in lane 0
+}
+
+// Grid (target tiles, views of the chunk): one lane per (target, view), a wave = 64 consecutive targets = one word of the view's
+// bitset bits[(v0 + v) * n_words + word], stored by lane 0 with a plain store.  The counts are the ballots' popcounts, visible_q40 a
+// wave sum: one integer atomic per wave, view and non-zero figure.  No lane leaves before the ballots.
+__global__ __launch_bounds__(256) void k_plan_visible(const float4* __restrict__ tp, const unsigned long long* __restrict__ tw, const uint32_t n_targets,
+                                                      const CovTri* __restrict__ geo, const double* __restrict__ poses, const PlanParams p,
+                                                      const uint32_t* __restrict__ zbuf, const uint32_t v0, const uint64_t n_words,
+                                                      unsigned long long* __restrict__ bits, PlanScore* __restrict__ score)
+{
+    const uint32_t v = blockIdx.y;
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const double* T = poses + 12ull * v;  // wave-uniform
+    bool in_view = false, facing = false, visible = false;
+    unsigned long long w = 0;
+    if (i < n_targets) {
+        const float4 q = tp[i];
+        double dx, dy, dz, zc;
+        int pu, pv;
+        if (plan_project(T, p, p.z_near, q.x, q.y, q.z, dx, dy, dz, zc, pu, pv) && pu >= 0 && pu < (int)p.width && pv >= 0 && pv < (int)p.height) {
+            in_view = true;
+            const double* N = geo[__float_as_uint(q.w)].N;
+            const double NN = dev_dot(N, N);
+            const double c = -((N[0] * dx + N[1] * dy) + N[2] * dz), d2 = (dx * dx + dy * dy) + dz * dz;
+            facing = p.min_cos < 0.0 || ((c > 0.0 || p.two_sided) && c * c >= ((p.min_cos * p.min_cos) * NN) * d2);
+            if (facing) {
+                const float depth32 = (float)zc;
+                const float zmin = __uint_as_float(zbuf[v * ((uint64_t)p.width * p.height) + (uint64_t)pv * p.width + (uint64_t)pu]);
+                visible = (double)depth32 - (double)zmin <= p.tolerance + p.slope * zc;
+                if (visible) w = tw[i];
+            }
+        }
+    }
+    const unsigned long long b_view = __ballot(in_view), b_face = __ballot(facing), b_vis = __ballot(visible);
+    const unsigned long long sum_w = b_vis ? wave_sum_u64(w) : 0ull;  // (b_vis is wave-uniform)
+    if ((threadIdx.x & 63u) != 0 || i >= n_targets) return;
+    bits[(uint64_t)(v0 + v) * n_words + (i >> 6)] = b_vis;
+    PlanScore* s = &score[v0 + v];
+    if (b_view) atomicAdd(&s->n_in_view, (uint32_t)__popcll(b_view));
+    if (b_face) atomicAdd(&s->n_facing, (uint32_t)__popcll(b_face));
+    if (b_vis) {
+        atomicAdd(&s->n_visible, (uint32_t)__popcll(b_vis));
+        if (sum_w) atomicAdd(&s->visible_q40, sum_w);
+    }
+}
+
+// remaining = every target: all ones, the last word cut to n_targets bits.  rank = -1 for every view.
+__global__ __launch_bounds__(256) void k_plan_begin(const uint32_t n_targets, const uint64_t n_words, unsigned long long* __restrict__ remaining,
+                                                    const uint32_t n_views, PlanScore* __restrict__ score)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i < n_words) remaining[i] = (i + 1 < n_words || (n_targets & 63u) == 0) ? ~0ull : (1ull << (n_targets & 63u)) - 1ull;
+    if (i < n_views) score[i].rank = -1;
+}
+
+// Grid (target tiles, views): G(v) and C(v) of the views not yet selected, as u64 sums gain[2 v], gain[2 v + 1] (zero on entry:
+// k_plan_argmax clears them behind its read).
+__global__ __launch_bounds__(256) void k_plan_gain(const unsigned long long* __restrict__ tw, const uint32_t n_targets, const uint64_t n_words,
+                                                   const unsigned long long* __restrict__ bits, const unsigned long long* __restrict__ remaining,
+                                                   const PlanScore* __restrict__ score, const PlanState* __restrict__ st, unsigned long long* __restrict__ gain)
+{
+    const uint32_t v = blockIdx.y;
+    if (st->done || score[v].rank >= 0) return;  // block-uniform
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint64_t wi = (i >> 6) < n_words ? (i >> 6) : n_words - 1;  // wave-uniform; a wave beyond the targets reads the last word and adds nothing
+    const unsigned long long word = i < n_targets ? bits[(uint64_t)v * n_words + wi] & remaining[wi] : 0ull;
+    if (!__ballot(word != 0ull)) return;  // wave-uniform
+    const unsigned long long w = (word >> (threadIdx.x & 63u)) & 1ull ? tw[i] : 0ull;
+    const unsigned long long sum_w = wave_sum_u64(w);
+    if ((threadIdx.x & 63u) != 0) return;
+    if (sum_w) atomicAdd(&gain[2 * v], sum_w);
+    atomicAdd(&gain[2 * v + 1], (unsigned long long)__popcll(word));
+}
+
+// One workgroup: the best unselected view of round `round` -- the largest G, then the larger C, then the smaller index --; below
+// max(1, min_gain) the selection is done.
+__global__ __launch_bounds__(256) void k_plan_argmax(const uint32_t round, const uint32_t n_views, const unsigned long long min_gain,
+                                                     PlanScore* __restrict__ score, unsigned long long* __restrict__ gain, PlanState* __restrict__ st)
+{
+    __shared__ unsigned long long s_g[256], s_c[256];
+    __shared__ uint32_t s_v[256];
+    if (st->done) return;  // uniform: nobody has written it yet
+    unsigned long long bg = 0, bc = 0;
+    uint32_t bv = 0xFFFFFFFFu;
+    for (uint32_t v = threadIdx.x; v < n_views; v += 256u) {  // ascending v per thread: a strict > keeps the smaller index
+        if (score[v].rank >= 0) continue;
+        const unsigned long long G = gain[2 * v], Cn = gain[2 * v + 1];
+        gain[2 * v] = 0, gain[2 * v + 1] = 0;
+        if (bv == 0xFFFFFFFFu || G > bg || (G == bg && Cn > bc)) bg = G, bc = Cn, bv = v;
+    }
+    s_g[threadIdx.x] = bg, s_c[threadIdx.x] = bc, s_v[threadIdx.x] = bv;
+    __syncthreads();
+    for (uint32_t o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) {
+            const unsigned long long g2 = s_g[threadIdx.x + o], c2 = s_c[threadIdx.x + o];
+            const uint32_t v2 = s_v[threadIdx.x + o], v1 = s_v[threadIdx.x];
+            const unsigned long long g1 = s_g[threadIdx.x], c1 = s_c[threadIdx.x];
+            if (v2 != 0xFFFFFFFFu && (v1 == 0xFFFFFFFFu || g2 > g1 || (g2 == g1 && (c2 > c1 || (c2 == c1 && v2 < v1)))))
+                s_g[threadIdx.x] = g2, s_c[threadIdx.x] = c2, s_v[threadIdx.x] = v2;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const unsigned long long need = min_gain > 1ull ? min_gain : 1ull;
+    if (s_v[0] == 0xFFFFFFFFu || s_g[0] < need) {
+        st->done = 1u;
+        return;
+    }
+    PlanScore* s = &score[s_v[0]];
+    s->rank = (int32_t)round, s->gain_q40 = s_g[0], s->gain_samples = s_c[0];
+    st->best = s_v[0], st->n_selected = round + 1u;
+}
+
+// R_{k+1} = R_k \ VIS(best).
+__global__ __launch_bounds__(256) void k_plan_take(const uint64_t n_words, const unsigned long long* __restrict__ bits, unsigned long long* __restrict__ remaining,
+                                                   const PlanState* __restrict__ st)
+{
+    if (st->done) return;
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i < n_words) remaining[i] &= ~bits[(uint64_t)st->best * n_words + i];
+}
+
+__global__ __launch_bounds__(256) void k_plan_tri_begin(const uint32_t n_tris, const TriCoverage* __restrict__ cov, TriPlan* __restrict__ plan)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (k < n_tris) plan[k] = TriPlan{0u, 0u, 0u, cov[k].flags};
+}
+
+// One lane per target: reachable = its bit in the union of every view's bitset (the word is wave-uniform), planned = its bit has
+// left `remaining`.  The triangle records (plan may be NULL) take one atomic per set figure, the totals one per wave.
+__global__ __launch_bounds__(256) void k_plan_finish(const float4* __restrict__ tp, const unsigned long long* __restrict__ tw, const uint32_t n_targets,
+                                                     const uint64_t n_words, const uint32_t n_views, const unsigned long long* __restrict__ bits,
+                                                     const unsigned long long* __restrict__ remaining, TriPlan* __restrict__ plan, PlanState* __restrict__ st)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const bool live = i < n_targets;
+    const uint64_t wi = (i >> 6) < n_words ? (i >> 6) : n_words - 1;
+    unsigned long long any = 0;
+    for (uint32_t v = 0; v < n_views; v++) any |= bits[(uint64_t)v * n_words + wi];
+    const unsigned long long lane_bit = 1ull << (threadIdx.x & 63u);
+    const bool reach = live && (any & lane_bit), planned = live && !(remaining[wi] & lane_bit);
+    const unsigned long long w = live ? tw[i] : 0ull;
+    if (live && plan) {
+        TriPlan* t = &plan[__float_as_uint(tp[i].w)];
+        atomicAdd(&t->n_targets, 1u);
+        if (reach) atomicAdd(&t->n_reachable, 1u);
+        if (planned) atomicAdd(&t->n_planned, 1u);
+    }
+    const unsigned long long b_reach = __ballot(reach), b_plan = __ballot(planned);
+    const unsigned long long s_all = wave_sum_u64(w), s_reach = wave_sum_u64(reach ? w : 0ull), s_plan = wave_sum_u64(planned ? w : 0ull);
+    if ((threadIdx.x & 63u) != 0) return;
+    if (b_reach) atomicAdd(&st->n_reachable, (unsigned long long)__popcll(b_reach));
+    if (b_plan) atomicAdd(&st->n_planned, (unsigned long long)__popcll(b_plan));
+    if (s_all) atomicAdd(&st->target_q40, s_all);
+    if (s_reach) atomicAdd(&st->reachable_q40, s_reach);
+    if (s_plan) atomicAdd(&st->planned_q40, s_plan);
 }
 
 

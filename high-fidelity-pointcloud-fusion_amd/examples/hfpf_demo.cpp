@@ -2,7 +2,7 @@
 // synthetic sensor -> ~start -> N x PointCloud2 callbacks with tf poses -> periodic clean -> ~process ->
 // <dir>/test_cloud.pcd + <dir>/meta.csv.  Prints per-stage wall times.
 //
-//   hfpf_demo [--min-component N [--hide-filtered]] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]]] <out_dir> [frames=30] [W=640] [H=480] [resolution=0.001] [clean_every=10] [seed=0xF051] [pose_seed=0x5E3]
+//   hfpf_demo [--min-component N [--hide-filtered]] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]] [--plan poses.txt]] <out_dir> [frames=30] [W=640] [H=480] [resolution=0.001] [clean_every=10] [seed=0xF051] [pose_seed=0x5E3]
 // --min-component N: ~process saves only the connected components (26-neighbourhood) of at least N rows (hfpf_node_set_component_filter).
 //   --hide-filtered: the rows the filter drops are hidden on the device (hfpf_node_set_hide_filtered), so that the reports of --reference
 //   see the cleaned model too, not only test_cloud.pcd and meta.csv.
@@ -14,6 +14,10 @@
 //   (hfpf_node_set_reference_coverage: samples `spacing` metres apart, one voxel by default, a window of 2 voxels, rows within 2
 //   voxels), and the demo prints the covered share of the mesh's area and of its samples.  A number behind --coverage is the spacing
 //   only when another argument follows it (the output directory).
+//   --plan poses.txt: ~process also writes view_plan.csv and view_plan_summary.csv, which of the candidate camera poses in poses.txt
+//   (12 numbers per pose, row-major [R|t], camera -> fusion frame, separated by white space) would see the most of that mesh not
+//   yet scanned (hfpf_node_set_view_candidates: the coverage settings above, a 640 x 480 sensor of 525 px focal length between 0.3 and
+//   3 m, up to 8 views), and the demo prints the selected views in rank order.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -56,6 +60,7 @@ int main(int argc, char** argv)
     double max_deviation = 0.0;
     bool align = false, coverage = false, hide_filtered = false;
     double spacing = 0.0;
+    const char* plan = nullptr;
     while (argc > 2 && strncmp(argv[1], "--", 2) == 0) {
         if (strcmp(argv[1], "--align") == 0) {
             align = true;
@@ -79,11 +84,12 @@ int main(int argc, char** argv)
         if (strcmp(argv[1], "--min-component") == 0) min_component = (uint32_t)strtoul(argv[2], nullptr, 0);
         else if (strcmp(argv[1], "--reference") == 0) reference = argv[2];
         else if (strcmp(argv[1], "--max-deviation") == 0) max_deviation = atof(argv[2]);
+        else if (strcmp(argv[1], "--plan") == 0) plan = argv[2];
         else break;
         argv += 2, argc -= 2;
     }
     if (argc < 2 || strncmp(argv[1], "--", 2) == 0) {
-        fprintf(stderr, "usage: hfpf_demo [--min-component N [--hide-filtered]] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]]] <out_dir> [frames] [W] [H] [resolution] [clean_every] [seed] [pose_seed]\n");
+        fprintf(stderr, "usage: hfpf_demo [--min-component N [--hide-filtered]] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]] [--plan poses.txt]] <out_dir> [frames] [W] [H] [resolution] [clean_every] [seed] [pose_seed]\n");
         return 2;
     }
     const std::string dir = argv[1];
@@ -165,6 +171,32 @@ int main(int argc, char** argv)
                 return 1;
             }
         }
+        if (plan) {
+            std::vector<double> poses;
+            FILE* f = fopen(plan, "r");
+            double v;
+            while (f && fscanf(f, "%lf", &v) == 1) poses.push_back(v);
+            if (f) fclose(f);
+            if (!f || poses.empty() || poses.size() % 12) {
+                fprintf(stderr, "plan: %s does not hold 12 numbers per pose\n", plan);
+                return 1;
+            }
+            hfpf_plan_opts po;
+            memset(&po, 0, sizeof po);
+            po.struct_size = sizeof po;
+            po.cover.struct_size = sizeof po.cover;
+            po.cover.radius = 2, po.cover.max_subdivision = 64;
+            po.cover.max_distance = 2.0 * (double)res, po.cover.spacing = spacing > 0 ? spacing : (double)res, po.cover.min_normal_dot = -2.0;
+            po.view.struct_size = sizeof po.view;
+            po.view.width = 640, po.view.height = 480;
+            po.view.fx = po.view.fy = 525.0, po.view.cx = 319.5, po.view.cy = 239.5;
+            po.view.z_near = 0.3, po.view.z_far = 3.0, po.view.splat_radius = -1, po.view.max_splat_radius = 4;
+            po.occluder_near = 0.01, po.min_cos = 0.2, po.tolerance = 2.0 * (double)res, po.slope = 0.0, po.max_views = 8;
+            if (hfpf_node_set_view_candidates(node, &po, poses.data(), (uint32_t)(poses.size() / 12)) != HFPF_OK) {
+                fprintf(stderr, "plan: %s\n", hfpf_node_last_error(node));
+                return 1;
+            }
+        }
     }
     hfpf_trigger_response r;
     hfpf_node_start(node, &r);
@@ -212,6 +244,26 @@ int main(int argc, char** argv)
         const double area = ((double)v[8] * 0x1p32 + (double)v[7]) * 0x1p-40, covered = ((double)v[10] * 0x1p32 + (double)v[9]) * 0x1p-40;
         printf("coverage: %.6f of %.6f m^2 covered (%.1f %%), %llu of %llu samples (%.1f %%), %llu valid / %llu invalid / %llu huge triangles\n", covered, area,
                area > 0 ? 100.0 * covered / area : 0.0, v[5], v[3], v[3] ? 100.0 * (double)v[5] / (double)v[3] : 0.0, v[0], v[1], v[2]);
+    }
+    if (reference && plan) {  // view_plan.csv: the selected views in rank order
+        struct Line { unsigned view; int rank; unsigned long long visible, gain, samples; };
+        std::vector<Line> sel;
+        FILE* f = fopen((dir + "/view_plan.csv").c_str(), "r");
+        if (!f || fscanf(f, "%*[^\n]\n") != 0) {
+            fprintf(stderr, "view_plan.csv: cannot read it back\n");
+            return 1;
+        }
+        Line l;
+        unsigned a, b, c;
+        while (fscanf(f, "%u,%d,%u,%u,%u,%llu,%llu,%llu\n", &l.view, &l.rank, &a, &b, &c, &l.visible, &l.gain, &l.samples) == 8)
+            if (l.rank >= 0) sel.push_back(l);
+        fclose(f);
+        for (int k = 0; k < (int)sel.size(); k++)
+            for (const Line& x : sel)
+                if (x.rank == k)
+                    printf("plan: rank %d = view %u, adds %.6f m^2 (%llu samples) of %.6f m^2 it sees\n", k, x.view, (double)x.gain * 0x1p-40, x.samples,
+                           (double)x.visible * 0x1p-40);
+        if (sel.empty()) printf("plan: no candidate view adds anything\n");
     }
     hfpf_node_destroy(node);
     return 0;

@@ -47,6 +47,9 @@ struct hfpf_node {
     hfpf_align_opts align_opts{};
     bool cover_on = false;              // hfpf_node_set_reference_coverage: ~process also writes coverage.csv and coverage_summary.csv
     hfpf_cover_opts cover_opts{};
+    bool plan_on = false;               // hfpf_node_set_view_candidates: ~process also writes view_plan.csv and view_plan_summary.csv
+    hfpf_plan_opts plan_opts{};
+    std::vector<double> plan_poses;     // 12 per candidate view
     bool cons_on = false;               // hfpf_node_set_depth_consistency: ~process also writes consistency.csv and consistency_summary.csv
     hfpf_consistency_opts cons_opts{};
     uint32_t cons_keep = 0;             // depth images the ring holds at most
@@ -383,6 +386,38 @@ static int write_coverage(hfpf_node* n, const double pose[12])
     return rc;
 }
 
+// view_plan.csv and view_plan_summary.csv beside the cloud: hfpf_plan_views of the reference mesh at `pose`, the pose the deviation
+// files were written at, for the candidate views; one line per view.  A component filter's min_count replaces the cover's, as it does
+// for the coverage files.
+static int write_view_plan(hfpf_node* n, const double pose[12])
+{
+    hfpf_plan_opts o = n->plan_opts;
+    if (n->comp_rows) o.cover.min_count = n->comp_opts.min_count;
+    const uint32_t n_views = (uint32_t)(n->plan_poses.size() / 12);
+    std::vector<hfpf_view_score> sc(std::max<uint32_t>(n_views, 1));
+    hfpf_plan_summary s;
+    int rc = hfpf_plan_views(n->grid, &o, n->ref_verts.data(), n->ref_verts.size() / 3, 12, n->ref_tris.data(), n->ref_tris.size() / 3, pose,
+                             n->plan_poses.data(), n_views, sc.data(), nullptr, &s);
+    if (rc != HFPF_OK) return rc;
+    FILE* f = fopen((n->directory_name + "/view_plan.csv").c_str(), "w");
+    if (!f) return HFPF_ERR_IO;
+    fprintf(f, "view,rank,n_in_view,n_facing,n_visible,visible_q40,gain_q40,gain_samples\n");
+    for (uint32_t v = 0; v < n_views; v++)
+        fprintf(f, "%u,%d,%u,%u,%u,%llu,%llu,%llu\n", v, sc[v].rank, sc[v].n_in_view, sc[v].n_facing, sc[v].n_visible, (unsigned long long)sc[v].visible_q40,
+                (unsigned long long)sc[v].gain_q40, (unsigned long long)sc[v].gain_samples);
+    bool ok = !ferror(f);
+    if (fclose(f) != 0 || !ok) return HFPF_ERR_IO;
+    f = fopen((n->directory_name + "/view_plan_summary.csv").c_str(), "w");
+    if (!f) return HFPF_ERR_IO;
+    fprintf(f, "n_views,n_selected,n_targets,n_reachable,n_planned,target_q40,reachable_q40,planned_q40,n_samples,n_in_bbox,n_covered\n"
+               "%u,%u,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu\n",
+            s.n_views, s.n_selected, (unsigned long long)s.n_targets, (unsigned long long)s.n_reachable, (unsigned long long)s.n_planned,
+            (unsigned long long)s.target_q40, (unsigned long long)s.reachable_q40, (unsigned long long)s.planned_q40,
+            (unsigned long long)s.coverage.n_samples, (unsigned long long)s.coverage.n_in_bbox, (unsigned long long)s.coverage.n_covered);
+    ok = !ferror(f);
+    return fclose(f) != 0 || !ok ? HFPF_ERR_IO : HFPF_OK;
+}
+
 // consistency.csv and consistency_summary.csv beside the cloud: hfpf_depth_consistency of the depth images in the ring, one line per
 // saved row.  Built like the deviation files: the call runs on the full row set (with the component filter's min_count when one is
 // set, and never with HFPF_CONSISTENCY_DROP: this is a report), one walk selects the saved rows' records, and under a filter the
@@ -513,6 +548,7 @@ int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
     double ref_pose[12];
     if (rc == HFPF_OK && n->ref_on) rc = write_deviation(n, rows, nr, ref_pose);  // EXTENSION: the saved cloud measured against the reference mesh
     if (rc == HFPF_OK && n->ref_on && n->cover_on) rc = write_coverage(n, ref_pose);  // EXTENSION: ... and how much of that mesh the model covers
+    if (rc == HFPF_OK && n->ref_on && n->plan_on) rc = write_view_plan(n, ref_pose);  // EXTENSION: ... and from where to scan what it does not
     if (rc == HFPF_OK && n->cons_on) rc = write_consistency(n, rows, nr);  // EXTENSION: what the last depth images say about every saved row
     if (n->comp_rows) hfpf_free_components(rows, labels, comps);
     else hfpf_free_rows(rows);
@@ -672,6 +708,20 @@ int hfpf_node_set_reference_coverage(hfpf_node* n, const hfpf_cover_opts* opts)
         n->cover_opts = *opts;
     }
     n->cover_on = opts != nullptr;
+    return HFPF_OK;
+}
+
+int hfpf_node_set_view_candidates(hfpf_node* n, const hfpf_plan_opts* opts, const double* poses, uint32_t n_views)
+{
+    if (!n) return HFPF_ERR_BAD_ARG;
+    if (opts) {
+        bool ok = hfpf_check_plan_opts(opts) == HFPF_OK && n_views <= 4096 && (poses || !n_views);
+        for (uint64_t i = 0; ok && i < 12ull * n_views; i++) ok = std::isfinite(poses[i]);
+        if (!ok) return nfail(n, HFPF_ERR_BAD_ARG, "hfpf_node_set_view_candidates: invalid hfpf_plan_opts, more than 4096 views, or NULL or non-finite poses");
+        n->plan_opts = *opts;
+        n->plan_poses.assign(poses, poses + 12ull * n_views);
+    }
+    n->plan_on = opts != nullptr;
     return HFPF_OK;
 }
 

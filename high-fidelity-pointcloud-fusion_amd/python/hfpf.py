@@ -96,6 +96,7 @@ EXPORTS = [
     "hfpf_check_deviation_opts", "hfpf_compare_mesh", "hfpf_compare_mesh_device", "hfpf_free_deviation", "hfpf_read_ply",
     "hfpf_check_align_opts", "hfpf_align_mesh", "hfpf_align_mesh_device",
     "hfpf_check_cover_opts", "hfpf_cover_mesh", "hfpf_cover_mesh_device", "hfpf_free_coverage",
+    "hfpf_check_plan_opts", "hfpf_plan_views", "hfpf_plan_views_device", "hfpf_free_plan",
     "hfpf_check_consistency_opts", "hfpf_depth_consistency", "hfpf_depth_consistency_device", "hfpf_free_consistency",
     "hfpf_check_hide_opts", "hfpf_hide_voxels", "hfpf_hide_voxels_device", "hfpf_hide_box", "hfpf_show_all", "hfpf_get_hidden",
     "hfpf_check_raycast_opts", "hfpf_raycast", "hfpf_raycast_device", "hfpf_raycast_view", "hfpf_raycast_view_device",
@@ -422,6 +423,59 @@ def check_cover_opts(o):
     return lib().hfpf_check_cover_opts(C.byref(o) if o is not None else None)
 
 
+# hfpf_plan_opts.flags, hfpf_view_score and hfpf_tri_plan (include/hfpf.h)
+PLAN_TWO_SIDED, PLAN_MODEL_OCCLUDES = 1, 2
+VIEW_SCORE_DTYPE = np.dtype([("rank", "<i4"), ("n_in_view", "<u4"), ("n_facing", "<u4"), ("n_visible", "<u4"), ("visible_q40", "<u8"),
+                             ("gain_q40", "<u8"), ("gain_samples", "<u8")])
+TRI_PLAN_DTYPE = np.dtype([("n_targets", "<u4"), ("n_reachable", "<u4"), ("n_planned", "<u4"), ("flags", "<u4")])
+assert VIEW_SCORE_DTYPE.itemsize == 40 and TRI_PLAN_DTYPE.itemsize == 16
+
+
+class PlanOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("cover", CoverOpts), ("view", RenderOpts),
+                ("occluder_near", C.c_double), ("min_cos", C.c_double), ("tolerance", C.c_double), ("slope", C.c_double),
+                ("min_gain_q40", C.c_uint64), ("max_views", C.c_uint32), ("reserved0", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class PlanSummary(C.Structure):
+    _fields_ = [("coverage", CoverageSummary), ("n_views", C.c_uint32), ("n_selected", C.c_uint32)] + [
+        (k, C.c_uint64) for k in ("n_targets", "n_reachable", "n_planned", "target_q40", "reachable_q40", "planned_q40")]
+
+    def as_dict(self):
+        """The fields (coverage as CoverageSummary.as_dict gives it)."""
+        d = {k: getattr(self, k) for k, _ in self._fields_[1:]}
+        d["coverage"] = self.coverage.as_dict()
+        return d
+
+
+assert C.sizeof(PlanOpts) == 208 and C.sizeof(PlanSummary) == 152
+
+
+def plan_opts(K, width, height, cover=None, view=None, occluder_near=None, min_cos=0.0, tolerance=0.004, slope=0.0, min_gain_q40=0, max_views=8,
+              two_sided=False, model_occludes=False, **kw):
+    """An hfpf_plan_opts: the sensor (K = (fx, fy, cx, cy), width, height and the other keywords of render_opts(), or a ready `view`),
+    what a target is (the keywords of cover_opts(), or a ready `cover`; the view's own min_count is view_min_count), the nearest distance at which a surface still blocks a ray
+    (default: the view's z_near), the facing gate (min_cos < 0 = off), the depth test (tolerance + slope * zc, metres) and the
+    greedy selection (max_views, min_gain_q40)."""
+    ck = {k: kw.pop(k) for k in ("radius", "min_count", "max_distance", "spacing", "max_subdivision", "min_normal_dot", "abs_normal") if k in kw}
+    if "view_min_count" in kw:  # min_count is the cover's, as in cover_opts()
+        kw["min_count"] = kw.pop("view_min_count")
+    o = PlanOpts()
+    o.struct_size = C.sizeof(PlanOpts)
+    o.flags = (PLAN_TWO_SIDED if two_sided else 0) | (PLAN_MODEL_OCCLUDES if model_occludes else 0)
+    o.cover = cover if cover is not None else cover_opts(**ck)
+    o.view = view if view is not None else render_opts(K, width, height, **kw)
+    o.occluder_near = float(o.view.z_near if occluder_near is None else occluder_near)
+    o.min_cos, o.tolerance, o.slope = float(min_cos), float(tolerance), float(slope)
+    o.min_gain_q40, o.max_views = int(min_gain_q40), int(max_views)
+    return o
+
+
+def check_plan_opts(o):
+    """hfpf_check_plan_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
+    return lib().hfpf_check_plan_opts(C.byref(o) if o is not None else None)
+
+
 # hfpf_consistency_opts.flags, hfpf_row_consistency.flags and hfpf_row_consistency (include/hfpf.h)
 CONSISTENCY_DROP = 1
 CONS_SEEN, CONS_SUPPORTED, CONS_CONTRADICTED = 1, 2, 4
@@ -745,6 +799,11 @@ def lib():
         fn.argtypes = [vp, C.POINTER(CoverOpts), vp, u64, u32, vp, u64, vp, C.POINTER(vp), C.POINTER(CoverageSummary)]
     L.hfpf_free_coverage.argtypes = [vp]
     L.hfpf_free_coverage.restype = None
+    L.hfpf_check_plan_opts.argtypes = [C.POINTER(PlanOpts)]
+    for fn in (L.hfpf_plan_views, L.hfpf_plan_views_device):
+        fn.argtypes = [vp, C.POINTER(PlanOpts), vp, u64, u32, vp, u64, vp, vp, u32, vp, C.POINTER(vp), C.POINTER(PlanSummary)]
+    L.hfpf_free_plan.argtypes = [vp]
+    L.hfpf_free_plan.restype = None
     L.hfpf_free_deviation.argtypes = [vp, vp]
     L.hfpf_free_deviation.restype = None
     L.hfpf_check_consistency_opts.argtypes = [C.POINTER(ConsistencyOpts)]
@@ -1226,6 +1285,42 @@ class OccupancyGrid:
         finally:
             lib().hfpf_free_coverage(c)
         return cov, s.as_dict()
+
+    # -- planning the next views against a reference mesh --
+    def plan_views(self, verts, tris, poses, pose=None, device=False, opts=None, tri_plan=True, n_verts=None, vertex_stride=None, n_tris=None, **kw):
+        """Score candidate camera poses by the reference surface they would add (hfpf_plan_views): (scores of VIEW_SCORE_DTYPE, one per
+        view; records of TRI_PLAN_DTYPE, one per triangle, or None with tri_plan=False; summary dict).  poses: n 3x4 [R|t], camera ->
+        fusion frame; verts, tris, pose and the device form's arguments as compare_mesh(); keywords as plan_opts().  device=True runs
+        hfpf_plan_views_device and returns the records as a device pointer (0 without triangles or with tri_plan=False): free it with
+        device_free."""
+        o = opts if opts is not None else plan_opts(**kw)
+        pose = np.ascontiguousarray(np.eye(4)[:3] if pose is None else pose, np.float64).reshape(12)
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        nv = len(poses)
+        room = np.zeros(max(nv, 1), VIEW_SCORE_DTYPE)  # never NULL, also without views
+        scores, sp = room[:nv], _p(room)
+        t, s = C.c_void_p(), PlanSummary()
+        tp = C.byref(t) if tri_plan else None
+        if device:
+            self._chk(lib().hfpf_plan_views_device(self._h, C.byref(o), C.c_void_p(verts), int(n_verts), int(vertex_stride), C.c_void_p(tris),
+                                                   int(n_tris), _p(pose), _p(poses) if nv else None, nv, sp, tp, C.byref(s)))
+            return scores, t.value or 0, s.as_dict()
+        verts = np.ascontiguousarray(verts)
+        if verts.dtype != MESH_VERTEX_DTYPE:
+            verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+        stride = int(vertex_stride) if vertex_stride is not None else verts.dtype.itemsize * (1 if verts.dtype == MESH_VERTEX_DTYPE else 3)
+        n_v = int(n_verts) if n_verts is not None else len(verts)
+        nt = int(n_tris) if n_tris is not None else len(tris)
+        self._chk(lib().hfpf_plan_views(self._h, C.byref(o), _p(verts) if verts.nbytes else None, n_v, stride, _p(tris) if tris.nbytes else None, nt,
+                                        _p(pose), _p(poses) if nv else None, nv, sp, tp, C.byref(s)))
+        try:
+            rec = np.empty(nt if t.value else 0, TRI_PLAN_DTYPE) if tri_plan else None
+            if tri_plan and rec.nbytes:
+                C.memmove(rec.ctypes.data, t.value, rec.nbytes)
+        finally:
+            lib().hfpf_free_plan(t)
+        return scores, rec, s.as_dict()
 
     # -- rows that depth frames see through --
     def depth_consistency(self, frames, poses, K, depth_scale=0.001, opts=None, rows=True, desc=None, depth_frame_stride=None, n_frames=None,

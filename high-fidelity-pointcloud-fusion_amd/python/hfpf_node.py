@@ -18,6 +18,7 @@ EXPORTS = ["hfpf_node_default_params", "hfpf_node_create", "hfpf_node_destroy", 
            "hfpf_node_get_stats", "hfpf_node_set_publisher", "hfpf_node_on_depth_image",
            "hfpf_node_set_mesh_output", "hfpf_node_save_session", "hfpf_node_load_session", "hfpf_node_set_component_filter",
            "hfpf_node_set_reference_mesh", "hfpf_node_set_reference_alignment", "hfpf_node_set_reference_coverage",
+           "hfpf_node_set_view_candidates",
            "hfpf_node_set_depth_consistency", "hfpf_node_set_hide_filtered", "hfpf_node_hide_box"]
 
 
@@ -72,6 +73,7 @@ def lib():
                                                    C.c_uint64, C.c_void_p]
         L.hfpf_node_set_reference_alignment.argtypes = [C.c_void_p, C.POINTER(hfpf.AlignOpts)]
         L.hfpf_node_set_reference_coverage.argtypes = [C.c_void_p, C.POINTER(hfpf.CoverOpts)]
+        L.hfpf_node_set_view_candidates.argtypes = [C.c_void_p, C.POINTER(hfpf.PlanOpts), C.c_void_p, C.c_uint32]
         L.hfpf_node_set_depth_consistency.argtypes = [C.c_void_p, C.POINTER(hfpf.ConsistencyOpts), C.c_uint32]
         L.hfpf_node_set_hide_filtered.argtypes = [C.c_void_p, C.c_int]
         L.hfpf_node_hide_box.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(hfpf.HideResult)]
@@ -223,6 +225,16 @@ class FusionNode:
         compares, and also writes alignment.csv; set_reference_alignment(None) with no keywords turns it off."""
         o = opts if opts is not None else (hfpf.align_opts(**kw) if kw else None)
         rc = lib().hfpf_node_set_reference_alignment(self._h, C.byref(o) if o is not None else None)
+        if rc < 0:
+            raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
+
+    def set_view_candidates(self, poses=None, opts=None, **kw):
+        """~process also writes view_plan.csv and view_plan_summary.csv: hfpf_plan_views of the reference mesh for these candidate
+        poses (n 3x4 [R|t], camera -> fusion frame) with these hfpf.plan_opts, or its keywords, at the pose the deviation files use;
+        set_view_candidates(None) turns it off."""
+        o = None if poses is None else (opts if opts is not None else hfpf.plan_opts(**kw))
+        p = np.ascontiguousarray(poses if poses is not None else np.zeros((0, 12)), np.float64).reshape(-1, 12)
+        rc = lib().hfpf_node_set_view_candidates(self._h, C.byref(o) if o is not None else None, p.ctypes.data if len(p) else None, len(p))
         if rc < 0:
             raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
 

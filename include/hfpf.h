@@ -1062,6 +1062,122 @@ int hfpf_cover_mesh_device(hfpf_handle* h, const hfpf_cover_opts* o, const void*
                            const uint32_t* dev_tris, uint64_t n_tris, const double* pose_3x4, hfpf_tri_coverage** dev_cov,
                            hfpf_coverage_summary* summary);
 
+/* ---- planning the next views: candidate poses scored by unscanned reference surface (no reference counterpart) -------------------
+ * hfpf_cover_mesh says which parts of a reference mesh have not been scanned; a plan says where to move the sensor next.  Every
+ * cover sample that is in the box and not covered is a TARGET; per candidate camera pose the call counts the targets that pose
+ * would see -- in range, facing the camera and not hidden behind the reference surface (or, on request, the model) -- and a greedy
+ * selection picks up to max_views poses by marginal gain.  Everything is restatable from hfpf_extract's rows and
+ * hfpf_get_occupied's list (tests/plan_ref.py).
+ * Arithmetic: everything below is f64, one rounding per operation, left to right, never contracted, unless stated otherwise.
+ * Mesh, pose, valid triangles, subdivision, sample points, sample test: word for word those of the coverage section, driven by the
+ *   embedded hfpf_cover_opts `cover`.  Per sample s of a valid triangle k that gives the f32 point p, the triangle's f64 normal N
+ *   with NN = dot(N, N) and s_k = sqrt(NN), IN_BBOX and COVERED.  A sample is a TARGET iff it is IN_BBOX and not COVERED.  The call
+ *   also returns the hfpf_coverage_summary hfpf_cover_mesh would return for the same arguments, byte for byte.
+ * Weight: w_s = (uint64)rint((area_d / (double)n_samples) * 2^40), and 0 for a triangle with HFPF_COV_HUGE.  When the summary's area
+ *   hi * 2^32 + lo is >= 2^62 the call returns HFPF_ERR_CAPACITY (the handle stays usable): every sum below stays under 2^63.
+ * View: the embedded hfpf_render_opts `view`, checked as hfpf_render checks it, supplies width, height, the intrinsics, z_near,
+ *   z_far, min_count, splat_radius, max_splat_radius and HFPF_RENDER_CULL_BACKFACES (HFPF_RENDER_WORLD_NORMALS has no effect).
+ *   occluder_near, 0 < occluder_near <= z_near: a surface nearer than the sensor's minimum range still blocks a ray.  poses holds
+ *   n_views * 12 f64 in HOST memory, row-major [R|t], camera -> fusion frame.
+ * Projection of a point into view v: the lines of the render section with (x, y, z) = p widened: dx, dy, dz, xc, yc, zc, u, v,
+ *   pu, pv and depth32 = (float)zc.
+ * Occluders of view v: every sample of a valid triangle whose p is finite, in the box or not, target or not, with
+ *   occluder_near < zc < z_far and |u|, |v| < 2^30, splat over (pu + i, pv + j), |i|, |j| <= r, inside the image; r = splat_radius,
+ *   or for -1: min(max_splat_radius, floor(((0.5 * cover.spacing) * max(fx, fy)) / zc)).  With HFPF_PLAN_MODEL_OCCLUDES also the rows
+ *   hfpf_render would draw with `view`, z_near replaced by occluder_near, with their own splat rule (res in the auto radius) and
+ *   the back-face cull when the view asks for it (the cull applies to the rows only).  zmin(v, pixel) = the smallest depth32 of all
+ *   occluder candidates of that pixel: a minimum, independent of any order.
+ * Target classes in view v: c = -((N.x*dx + N.y*dy) + N.z*dz), d2 = (dx*dx + dy*dy) + dz*dz.
+ *   IN_VIEW iff z_near < zc < z_far, |u|, |v| < 2^30 and (pu, pv) is inside the image.
+ *   FACING iff IN_VIEW and: min_cos < 0 (the gate is off), or c > 0 && c*c >= ((min_cos*min_cos) * NN) * d2, or
+ *     HFPF_PLAN_TWO_SIDED is set and c*c >= ((min_cos*min_cos) * NN) * d2.
+ *   VISIBLE iff FACING and (double)depth32 - (double)zmin(v, (pu, pv)) <= tolerance + slope * zc.  A target splats into its own
+ *     pixel, so zmin <= depth32 always.
+ * Per view (hfpf_view_score): n_in_view, n_facing, n_visible count targets; visible_q40 = the sum of w_s over VISIBLE targets;
+ *   rank, gain_q40, gain_samples from the selection.
+ * Greedy selection: R_0 = all targets.  Round k = 0 .. max_views - 1, over the views not yet selected: G(v) = the sum of w_s over
+ *   R_k n VIS(v), C(v) = that set's size.  The best view has the largest G; ties go to the larger C, then to the smaller view index.
+ *   The selection stops when G(best) < max(1, min_gain_q40).  Otherwise rank[best] = k, gain_q40 = G, gain_samples = C and
+ *   R_{k+1} = R_k \ VIS(best).  Unselected views keep rank = -1 and zero gains.
+ * Per triangle (hfpf_tri_plan, optional): n_targets; n_reachable = targets VISIBLE from at least one candidate; n_planned = targets
+ *   VISIBLE from at least one selected view; flags = the cover flags (an invalid triangle has an all-zero record).
+ * Summary (hfpf_plan_summary): the coverage summary; n_views, n_selected; n_targets, n_reachable, n_planned; target_q40,
+ *   reachable_q40, planned_q40 = the sums of w_s over those sets.  Everything is an integer sum or a minimum: nothing depends on
+ *   scheduling or on how the views are split into depth-buffer chunks (HFPF_PLAN_CHUNK=1..64 in the environment forces the views per
+ *   chunk, for tests).
+ * A call changes nothing on the handle except device_bytes (its scratch); host frames still waiting are launched first.  Rejected
+ * with HFPF_ERR_BAD_ARG (the handle stays usable, nothing is written): what hfpf_check_plan_opts rejects (struct_size != sizeof,
+ * flags beyond the two below, reserved fields != 0, everything hfpf_check_cover_opts rejects in `cover`, everything hfpf_render
+ * rejects in `view`, occluder_near not finite or outside (0, z_near], min_cos not finite or outside [-1, 1], tolerance not finite
+ * or outside (0, 1], slope not finite or outside [0, 1], max_views outside 1..256); n_views > 4096; NULL or non-finite poses with
+ * n_views > 0; a NULL scores or summary; the mesh checks of hfpf_compare_mesh; for the device form verts or tris not 4-byte
+ * aligned.  More than 2^35 (target, view) pairs return HFPF_ERR_CAPACITY, the message names both numbers, and the handle stays
+ * usable.  n_views = 0 gives the coverage summary and a zero plan; n_tris = 0 gives all zero (n_views and the ranks of -1 apart) and a
+ * NULL plan.  A handle before
+ * its first clean pass makes every in-box sample a target.  A handle with an RCCL communicator, or a failed handle, returns
+ * HFPF_ERR_STATE as the other readers do. */
+#define HFPF_PLAN_TWO_SIDED 1u      /* hfpf_plan_opts.flags: the facing gate passes either side of a triangle */
+#define HFPF_PLAN_MODEL_OCCLUDES 2u /* the rows hfpf_render would draw occlude too */
+
+typedef struct hfpf_plan_opts {
+    uint32_t struct_size;    /* = sizeof(hfpf_plan_opts) */
+    uint32_t flags;          /* HFPF_PLAN_* */
+    hfpf_cover_opts cover;   /* what a target is */
+    hfpf_render_opts view;   /* the sensor at every candidate pose */
+    double occluder_near;    /* metres, in (0, view.z_near] */
+    double min_cos;          /* < 0 = gate off, else the smallest cosine between the triangle's normal and the ray to the camera */
+    double tolerance, slope; /* a target is visible when it lies at most tolerance + slope * zc behind the pixel's nearest occluder */
+    uint64_t min_gain_q40;   /* the selection stops below max(1, min_gain_q40) */
+    uint32_t max_views;      /* 1..256 */
+    uint32_t reserved0;      /* 0 */
+    uint64_t reserved;       /* 0 */
+} hfpf_plan_opts;
+
+typedef struct hfpf_view_score { /* 40 bytes, one per candidate view */
+    int32_t rank;            /* the round that selected the view, -1 = not selected */
+    uint32_t n_in_view, n_facing, n_visible;
+    uint64_t visible_q40;    /* visible target area: / 2^40 m^2 */
+    uint64_t gain_q40, gain_samples; /* what the view added when it was selected */
+} hfpf_view_score;
+
+typedef struct hfpf_tri_plan { /* 16 bytes, one per triangle */
+    uint32_t n_targets, n_reachable, n_planned;
+    uint32_t flags;          /* HFPF_COV_* */
+} hfpf_tri_plan;
+
+typedef struct hfpf_plan_summary { /* 152 bytes */
+    hfpf_coverage_summary coverage;
+    uint32_t n_views, n_selected;
+    uint64_t n_targets, n_reachable, n_planned;
+    uint64_t target_q40, reachable_q40, planned_q40;
+} hfpf_plan_summary;
+
+#ifdef __cplusplus
+static_assert(sizeof(hfpf_plan_opts) == 208, "hfpf_plan_opts is 208 bytes");
+static_assert(sizeof(hfpf_view_score) == 40, "hfpf_view_score is 40 bytes");
+static_assert(sizeof(hfpf_tri_plan) == 16, "hfpf_tri_plan is 16 bytes");
+static_assert(sizeof(hfpf_plan_summary) == 152, "hfpf_plan_summary is 152 bytes");
+#else
+_Static_assert(sizeof(hfpf_plan_opts) == 208, "hfpf_plan_opts is 208 bytes");
+_Static_assert(sizeof(hfpf_view_score) == 40, "hfpf_view_score is 40 bytes");
+_Static_assert(sizeof(hfpf_tri_plan) == 16, "hfpf_tri_plan is 16 bytes");
+_Static_assert(sizeof(hfpf_plan_summary) == 152, "hfpf_plan_summary is 152 bytes");
+#endif
+
+/* HFPF_OK if o passes the checks above, else HFPF_ERR_BAD_ARG (host code, no handle; the node shell uses it too). */
+int hfpf_check_plan_opts(const hfpf_plan_opts* o);
+/* Mesh, pose, poses and outputs in HOST memory: scores holds n_views records (the caller's array); *plan, when plan is not NULL,
+ * holds n_tris records and is freed by hfpf_free_plan. */
+int hfpf_plan_views(hfpf_handle* h, const hfpf_plan_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris,
+                    uint64_t n_tris, const double* pose_3x4, const double* poses, uint32_t n_views, hfpf_view_score* scores, hfpf_tri_plan** plan,
+                    hfpf_plan_summary* summary);
+void hfpf_free_plan(hfpf_tri_plan* plan);
+/* The mesh is read in place from DEVICE memory (HBM); *dev_plan is a device array of n_tris records, freed by hfpf_device_free(h, p).
+ * pose_3x4, poses, scores and summary are in host memory. */
+int hfpf_plan_views_device(hfpf_handle* h, const hfpf_plan_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride,
+                           const uint32_t* dev_tris, uint64_t n_tris, const double* pose_3x4, const double* poses, uint32_t n_views,
+                           hfpf_view_score* scores, hfpf_tri_plan** dev_plan, hfpf_plan_summary* summary);
+
 /* ---- rows that later depth frames see through (the inverse of hfpf_render; no reference counterpart) ----------------------------
  * An occupancy grid keeps a voxel that was occupied once: a hand that crossed the view, a part that was moved, a slab of flying
  * pixels that passed the gate.  min_count cannot drop them when they were seen for many frames, hfpf_extract_components cannot when

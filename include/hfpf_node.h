@@ -151,6 +151,17 @@ int hfpf_node_set_reference_alignment(hfpf_node* n, const hfpf_align_opts* opts)
  * with HFPF_ERR_BAD_ARG and leave the setting as it was. */
 int hfpf_node_set_reference_coverage(hfpf_node* n, const hfpf_cover_opts* opts);
 
+/* EXTENSION: from where to scan what is still missing.  With candidate views set and a reference mesh set, ~process also runs
+ * hfpf_plan_views of include/hfpf.h on that mesh, at the pose the deviation files are written at (the refined pose when alignment is
+ * on; with a component filter set, opts->cover.min_count is replaced by the filter's, as the coverage's is), and writes view_plan.csv
+ * (header view,rank,n_in_view,n_facing,n_visible,visible_q40,gain_q40,gain_samples, then one line per candidate view) and
+ * view_plan_summary.csv (one header line, one value line: n_views, n_selected, n_targets, n_reachable, n_planned, target_q40,
+ * reachable_q40, planned_q40, and of the embedded coverage summary n_samples, n_in_bbox, n_covered).  poses holds n_views * 12 f64,
+ * row-major [R|t], camera -> fusion frame; the node keeps a copy.  Without a reference mesh the setting has no effect.  A NULL opts
+ * turns it off again, the default: neither file is then written.  Invalid options (hfpf_check_plan_opts), more than 4096 views and
+ * NULL or non-finite poses are refused with HFPF_ERR_BAD_ARG and leave the setting as it was. */
+int hfpf_node_set_view_candidates(hfpf_node* n, const hfpf_plan_opts* opts, const double* poses, uint32_t n_views);
+
 /* EXTENSION: what the last depth images say about every saved row.  With consistency options set the node keeps host copies of the
  * last keep_frames (1..4096) depth images hfpf_node_on_depth_image integrated, with their poses; an image whose hfpf_depth_image
  * differs from the ring's empties the ring first.  ~process then also runs hfpf_depth_consistency of include/hfpf.h on those images
