@@ -2523,6 +2523,25 @@ static int local_read_prologue_locked(hfpf_handle* h, const char* what = "render
     return read_prologue_locked(h);
 }
 
+// The camera of view.hpp from the options of a view, and from a depth image with the z range of its call.
+static Pinhole pinhole_of(const hfpf_render_opts& o) { return Pinhole{o.fx, o.fy, o.cx, o.cy, o.z_near, o.z_far, o.width, o.height}; }
+static Pinhole pinhole_of(const hfpf_depth_image& d, double z_near, double z_far) { return Pinhole{d.fx, d.fy, d.cx, d.cy, z_near, z_far, d.width, d.height}; }
+
+// Views per chunk of depth buffers with word_bytes a pixel: at most kRenderChunkViews (their poses sit in LDS) and kRenderZbufBytes
+// of buffers, one view at least.
+static uint32_t view_chunk(uint64_t WH, size_t word_bytes, uint32_t n_views)
+{
+    return (uint32_t)std::min<uint64_t>({(uint64_t)kRenderChunkViews, std::max<uint64_t>(1, kRenderZbufBytes / (word_bytes * WH)), std::max<uint32_t>(n_views, 1)});
+}
+
+// n poses (12 f64 each, host memory) into the scratch buffer `buf`, enqueued on the handle's stream.
+static int upload_poses(hfpf_handle* h, DevBuf& buf, const double* poses, uint64_t n, double** pose_d)
+{
+    if (int rc = scratch_n(h, buf, 12ull * n, pose_d)) return rc;
+    HIPCHK(h, hipMemcpyAsync(*pose_d, poses, (size_t)n * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    return HFPF_OK;
+}
+
 // The views of a render (or the model view of a track): the row set, the z-buffer scratch of one chunk of views, the poses on the
 // device and the splat's parameters.
 struct RenderViews {
@@ -2540,19 +2559,16 @@ static int render_views_locked(hfpf_handle* h, const hfpf_render_opts* o, uint32
     const uint64_t nr = rv->rows.n;
     if (nr > 0xFFFFFFFFull) return fail(h, HFPF_ERR_CAPACITY, "render: %llu rows do not fit the 32-bit row field of a z-buffer word", (unsigned long long)nr);
     const uint64_t WH = (uint64_t)o->width * o->height;
-    const uint32_t per_chunk = (uint32_t)std::min<uint64_t>({(uint64_t)kRenderChunkViews, std::max<uint64_t>(1, kRenderZbufBytes / (8 * WH)), n_views});
+    const uint32_t per_chunk = view_chunk(WH, sizeof *rv->zbuf, n_views);
     if ((rc = scratch_n(h, h->zbuf, per_chunk * WH, &rv->zbuf))) return rc;
-    if ((rc = scratch_n(h, h->render_pose, 12ull * n_views, &rv->pose_d))) return rc;
-    HIPCHK(h, hipMemcpyAsync(rv->pose_d, poses, (size_t)n_views * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if ((rc = upload_poses(h, h->render_pose, poses, n_views, &rv->pose_d))) return rc;
     RenderParams& p = rv->p;
     p = RenderParams{};
-    p.width = o->width;
-    p.height = o->height;
+    p.cam = pinhole_of(*o);
     p.cull = (o->flags & HFPF_RENDER_CULL_BACKFACES) ? 1u : 0u;
     p.world_normals = (o->flags & HFPF_RENDER_WORLD_NORMALS) ? 1u : 0u;
     p.radius = o->splat_radius;
     p.max_radius = o->max_splat_radius;
-    p.fx = o->fx, p.fy = o->fy, p.cx = o->cx, p.cy = o->cy, p.z_near = o->z_near, p.z_far = o->z_far;
     p.r_num = (0.5 * h->g.res) * std::max(o->fx, o->fy);
     rv->n_views = n_views;
     rv->per_chunk = per_chunk;
@@ -2564,7 +2580,7 @@ static int render_splat_locked(hfpf_handle* h, RenderViews* rv, uint32_t v0)
 {
     RenderParams& p = rv->p;
     p.n_views = std::min(rv->per_chunk, rv->n_views - v0);
-    const uint64_t pix = p.n_views * (uint64_t)p.width * p.height;
+    const uint64_t pix = p.n_views * (uint64_t)p.cam.width * p.cam.height;
     HIPCHK(h, hipMemsetAsync(rv->zbuf, 0xFF, pix * 8, h->stream));
     if (rv->rows.n)
         hipLaunchKernelGGL(k_render_splat, dim3(blocks_for(rv->rows.n, 256)), dim3(256), 0, h->stream, rv->rows.rows, (uint32_t)rv->rows.n,
@@ -2849,10 +2865,9 @@ static int track_locked(hfpf_handle* h, const hfpf_track_opts* o, const PointSou
 
     TrackParams p{};
     memcpy(p.V, pose, sizeof p.V);
-    p.fx = o->view.fx, p.fy = o->view.fy, p.cx = o->view.cx, p.cy = o->view.cy, p.z_near = o->view.z_near, p.z_far = o->view.z_far;
+    p.cam = pinhole_of(o->view);
     p.max_d2 = o->max_distance * o->max_distance;
     p.zc_lo = h->g.zc_lo, p.zc_hi = h->g.zc_hi;
-    p.width = o->view.width, p.height = o->view.height;
     p.n_samples = (uint32_t)n_samples;
     p.stride = stride;
     p.cols = cols;
@@ -3157,8 +3172,7 @@ static int raycast_view_common(hfpf_handle* h, const hfpf_raycast_opts* o, uint3
     p.fx = fx, p.fy = fy, p.cx = cx, p.cy = cy;
     p.width = width;
     p.view_stride = WH;
-    double* pose_d; if ((rc = scratch_n(h, h->render_pose, 12ull * n_views, &pose_d))) return rc;
-    HIPCHK(h, hipMemcpyAsync(pose_d, poses, (size_t)n_views * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    double* pose_d; if ((rc = upload_poses(h, h->render_pose, poses, n_views, &pose_d))) return rc;
     const uint64_t tiles_x = (width + 7ull) / 8;
     auto launch = [&](uint32_t v0, uint32_t nv, uint32_t row0, uint32_t rows, RayHit* dh) -> int {
         p.row0 = row0;
@@ -3972,12 +3986,12 @@ constexpr uint64_t kPlanMaxPairs = 1ull << 35;  // (target, view) pairs: 4 GiB o
 // The views of one depth-buffer chunk: the zbuf rule of a render on 4-byte words, or what HFPF_PLAN_CHUNK=1..64 forces (tests).
 static uint32_t plan_chunk_views(uint64_t WH, uint32_t n_views)
 {
-    uint64_t per = std::min<uint64_t>({(uint64_t)kRenderChunkViews, std::max<uint64_t>(1, kRenderZbufBytes / (4 * WH)), std::max<uint32_t>(n_views, 1)});
+    uint32_t per = view_chunk(WH, sizeof(uint32_t), n_views);
     if (const char* e = getenv("HFPF_PLAN_CHUNK")) {
         const long v = strtol(e, nullptr, 10);
-        if (v >= 1 && v <= 64) per = std::min<uint64_t>(per, (uint64_t)v);
+        if (v >= 1 && v <= 64) per = std::min(per, (uint32_t)v);
     }
-    return (uint32_t)per;
+    return per;
 }
 
 // Validated arguments in, the mesh on the device, n_tris > 0, under the lock.  The cover with the samples marked; the scan of the
@@ -4026,12 +4040,10 @@ static int plan_locked(hfpf_handle* h, const hfpf_plan_opts* o, const MeshRef& m
             if ((rc = build_rows_locked(h, h->t.stats, opt, &rows))) return rc;
             if (rows.n > 0xFFFFFFFFull) return fail(h, HFPF_ERR_CAPACITY, "plan_views: %llu rows exceed the 2^32 - 1 a splat launch takes", (unsigned long long)rows.n);
         }
-        if ((rc = scratch_n(h, h->zbuf, per_chunk * WH, &zbuf)) || (rc = scratch_n(h, h->render_pose, 12ull * n_views, &pose_d))) return rc;
-        HIPCHK(h, hipMemcpyAsync(pose_d, poses, (size_t)n_views * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        p.width = o->view.width, p.height = o->view.height;
+        if ((rc = scratch_n(h, h->zbuf, per_chunk * WH, &zbuf)) || (rc = upload_poses(h, h->render_pose, poses, n_views, &pose_d))) return rc;
+        p.cam = pinhole_of(o->view);
         p.cull = (o->view.flags & HFPF_RENDER_CULL_BACKFACES) ? 1u : 0u, p.two_sided = (o->flags & HFPF_PLAN_TWO_SIDED) ? 1u : 0u;
         p.radius = o->view.splat_radius, p.max_radius = o->view.max_splat_radius;
-        p.fx = o->view.fx, p.fy = o->view.fy, p.cx = o->view.cx, p.cy = o->view.cy, p.z_near = o->view.z_near, p.z_far = o->view.z_far;
         p.occ_near = o->occluder_near;
         p.r_num_samples = (0.5 * o->cover.spacing) * std::max(o->view.fx, o->view.fy);
         p.r_num_rows = (0.5 * h->g.res) * std::max(o->view.fx, o->view.fy);
@@ -4242,18 +4254,15 @@ static int consistency_locked(hfpf_handle* h, const hfpf_consistency_opts* o, co
     ConsRec* recs; ConsSummary* d_sum; uint32_t *keep, *base;
     if ((rc = scratch(h, h->cons_recs, ScratchLayout().add(&recs, nr).add(&d_sum, 1).add(&keep, R1).add(&base, R1)))) return rc;
     double* d_pose = nullptr;
-    if (f.n) {
-        if ((rc = scratch_n(h, h->cons_pose, 12ull * f.n, &d_pose))) return rc;
-        HIPCHK(h, hipMemcpyAsync(d_pose, f.poses, (size_t)f.n * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    }
+    if (f.n && (rc = upload_poses(h, h->cons_pose, f.poses, f.n, &d_pose))) return rc;
     ConsParams p{};
     p.frame_stride = f.stride;
-    p.width = ds.width, p.height = ds.height, p.depth_step = ds.depth_step, p.depth_f32 = ds.depth_f32;
+    p.depth_step = ds.depth_step, p.depth_f32 = ds.depth_f32;
     p.gate = o->min_cos >= 0.0 ? 1u : 0u;
     p.window = o->window;
     p.unit = ds.unit;
-    p.fx = desc->fx, p.fy = desc->fy, p.cx = desc->cx, p.cy = desc->cy;
-    p.z_near = o->z_near, p.z_far = o->z_far, p.tolerance = o->tolerance, p.slope = o->slope, p.min_cos2 = o->min_cos * o->min_cos;
+    p.cam = pinhole_of(*desc, o->z_near, o->z_far);
+    p.tolerance = o->tolerance, p.slope = o->slope, p.min_cos2 = o->min_cos * o->min_cos;
     p.through_ratio = o->through_ratio;
     p.min_through = std::max(1u, o->min_through);
     p.drop = (o->flags & HFPF_CONSISTENCY_DROP) ? 1u : 0u;

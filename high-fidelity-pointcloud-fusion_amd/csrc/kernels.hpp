@@ -22,6 +22,7 @@
 
 #include "host_plan.hpp"  // hide_word_op (constexpr: host and device)
 #include "stats.hpp"
+#include "view.hpp"       // the pinhole view: Pinhole, view_depth / view_pixel, view_radius
 
 namespace hfpf {
 
@@ -2265,58 +2266,68 @@ constexpr size_t kRenderZbufBytes = 256ull << 20;     // z-buffer scratch of one
 constexpr unsigned long long kRenderEmpty = ~0ull;
 
 struct RenderParams {
-    uint32_t width, height;
+    Pinhole cam;
     uint32_t n_views;        // views of this chunk
     uint32_t cull;           // HFPF_RENDER_CULL_BACKFACES
     uint32_t world_normals;  // HFPF_RENDER_WORLD_NORMALS
     int32_t radius;          // >= 0 fixed, -1 auto
     int32_t max_radius;
-    uint32_t pad;
-    double fx, fy, cx, cy, z_near, z_far;
     double r_num;            // (0.5 * res) * max(fx, fy): the auto radius is floor(r_num / zc), evaluated as the contract writes it
 };
 
-// One thread per row, looping over the chunk's views.  Of the 64-byte row only count, x..z and nx..nz are read.  A candidate first
-// reads the pixel's word with a plain load and skips the atomic when it is already <= its own: words only ever decrease, so a stale
-// value is >= the current one and the skip is exact.  Under overdraw most candidates end there.
+// What every kernel with a camera shares beside view.hpp.  A chunk's n poses into LDS, before the block's first return:
+__device__ __forceinline__ void stage_poses(double* s_pose, const double* __restrict__ poses, const uint32_t n)
+{
+    for (uint32_t i = threadIdx.x; i < n * 12u; i += blockDim.x) s_pose[i] = poses[i];
+    __syncthreads();
+}
+
+// Of the 64-byte row a view reads the point and the normal: one 16-byte and one 8-byte load.
+struct RowPN {
+    double x, y, z, nx, ny, nz;
+};
+__device__ __forceinline__ RowPN row_point_normal(const Row& r)
+{
+    const float4 q0 = *reinterpret_cast<const float4*>(&r.x);   // x, y, z, nx
+    const float2 q1 = *reinterpret_cast<const float2*>(&r.ny);  // ny, nz
+    return RowPN{q0.x, q0.y, q0.z, q0.w, q1.x, q1.y};
+}
+
+// One candidate into the depth buffer zv of its view: `word` (64 bits with the row behind the depth, or the depth's 32 alone) into the
+// window of radius r around (pu, pv), clipped to the image.  A candidate first reads the pixel's word with a plain load and skips the
+// atomic when it is already <= its own: words only ever decrease, so a stale value is >= the current one and the skip is exact.
+// Under overdraw most candidates end there.  |pu|, |pv| <= 2^30 and r <= 15: the window's bounds do not wrap.
+template <typename Word>
+__device__ __forceinline__ void view_splat(Word* __restrict__ zv, const Pinhole& k, const int pu, const int pv, const int r, const Word word)
+{
+    const int x0 = max(pu - r, 0), x1 = min(pu + r, (int)k.width - 1);
+    const int y0 = max(pv - r, 0), y1 = min(pv + r, (int)k.height - 1);
+    for (int py = y0; py <= y1; py++)
+        for (int px = x0; px <= x1; px++) {
+            Word* a = zv + (uint64_t)py * k.width + (uint64_t)px;
+            if (__hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > word) atomicMin(a, word);
+        }
+}
+
+// One thread per row, looping over the chunk's views.  The back-face cull sits between the two halves of the projection: behind a
+// one-piece projection it costs this kernel two VGPRs.
 __global__ __launch_bounds__(256) void k_render_splat(const Row* __restrict__ rows, const uint32_t n_rows, const double* __restrict__ poses,
                                                       const RenderParams p, unsigned long long* __restrict__ zbuf)
 {
     __shared__ double s_pose[kRenderChunkViews * 12];
-    for (uint32_t i = threadIdx.x; i < p.n_views * 12u; i += blockDim.x) s_pose[i] = poses[i];
-    __syncthreads();
+    stage_poses(s_pose, poses, p.n_views);
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n_rows) return;
-    const float4 q0 = *reinterpret_cast<const float4*>(&rows[j].x);   // x, y, z, nx
-    const float2 q1 = *reinterpret_cast<const float2*>(&rows[j].ny);  // ny, nz
-    const double x = q0.x, y = q0.y, z = q0.z, nx = q0.w, ny = q1.x, nz = q1.y;
-    const uint64_t W = p.width, WH = (uint64_t)p.width * p.height;
+    const RowPN q = row_point_normal(rows[j]);
+    const uint64_t WH = (uint64_t)p.cam.width * p.cam.height;
     for (uint32_t v = 0; v < p.n_views; v++) {
         const double* T = &s_pose[12 * v];
-        const double dx = x - T[3], dy = y - T[7], dz = z - T[11];
-        const double zc = (T[2] * dx + T[6] * dy) + T[10] * dz;
-        if (!(p.z_near < zc && zc < p.z_far)) continue;
-        if (p.cull && !(((nx * dx + ny * dy) + nz * dz) < 0.0)) continue;
-        const double xc = (T[0] * dx + T[4] * dy) + T[8] * dz;
-        const double yc = (T[1] * dx + T[5] * dy) + T[9] * dz;
-        const double u = (xc / zc) * p.fx + p.cx;
-        const double w = (yc / zc) * p.fy + p.cy;
-        if (!(fabs(u) < 1073741824.0 && fabs(w) < 1073741824.0)) continue;
-        const int pu = (int)floor(u + 0.5), pv = (int)floor(w + 0.5);
-        int r = p.radius;
-        if (r < 0) {
-            const double ra = floor(p.r_num / zc);
-            r = ra < (double)p.max_radius ? (int)ra : p.max_radius;
-        }
-        const int x0 = max(pu - r, 0), x1 = min(pu + r, (int)p.width - 1);
-        const int y0 = max(pv - r, 0), y1 = min(pv + r, (int)p.height - 1);
-        const unsigned long long word = (unsigned long long)__float_as_uint((float)zc) << 32 | j;
-        unsigned long long* zv = zbuf + v * WH;
-        for (int py = y0; py <= y1; py++)
-            for (int px = x0; px <= x1; px++) {
-                unsigned long long* a = zv + (uint64_t)py * W + (uint64_t)px;
-                if (__hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > word) atomicMin(a, word);
-            }
+        double dx, dy, dz, zc;
+        int pu, pv;
+        if (!view_depth(T, p.cam, p.cam.z_near, q.x, q.y, q.z, dx, dy, dz, zc)) continue;
+        if (p.cull && !(((q.nx * dx + q.ny * dy) + q.nz * dz) < 0.0)) continue;
+        if (!view_pixel(T, p.cam, dx, dy, dz, zc, pu, pv)) continue;
+        view_splat(zbuf + v * WH, p.cam, pu, pv, view_radius(p.radius, p.max_radius, p.r_num, zc), (unsigned long long)__float_as_uint((float)zc) << 32 | j);
     }
 }
 
@@ -2332,7 +2343,7 @@ struct RenderPlanes {
 __global__ __launch_bounds__(256) void k_render_resolve(const Row* __restrict__ rows, const unsigned long long* __restrict__ zbuf,
                                                         const double* __restrict__ poses, const RenderParams p, const RenderPlanes o)
 {
-    const uint64_t WH = (uint64_t)p.width * p.height;
+    const uint64_t WH = (uint64_t)p.cam.width * p.cam.height;
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= WH * p.n_views) return;
     const unsigned long long word = zbuf[i];
@@ -2385,10 +2396,9 @@ constexpr uint32_t kTrackMaxBlocks = 2048;
 struct TrackParams {
     double T[12];          // the estimate T_k, camera -> fusion frame
     double V[12];          // the view pose (the input pose T0); c = (V[3], V[7], V[11])
-    double fx, fy, cx, cy, z_near, z_far;
+    Pinhole cam;           // the view
     double max_d2;         // max_distance * max_distance
     float zc_lo, zc_hi;    // the handle's z-clip as float compares (GridParams)
-    uint32_t width, height;  // the view
     uint32_t n_samples;    // sampled points
     uint32_t stride;
     uint32_t cols;         // depth: sampled columns, ceil(image width / stride)
@@ -2505,26 +2515,19 @@ __global__ __launch_bounds__(256) void k_track_reduce(const TrackParams p, const
         const double wy = ((T[4] * px + T[5] * py) + T[6] * pz) + T[7];
         const double wz = ((T[8] * px + T[9] * py) + T[10] * pz) + T[11];
         // a = pw - c: also the offset the view's projection starts from
-        const double ax = wx - V[3], ay = wy - V[7], az = wz - V[11];
-        const double zc = (V[2] * ax + V[6] * ay) + V[10] * az;
-        if (!(p.z_near < zc && zc < p.z_far)) continue;
-        const double xc = (V[0] * ax + V[4] * ay) + V[8] * az;
-        const double yc = (V[1] * ax + V[5] * ay) + V[9] * az;
-        const double u = (xc / zc) * p.fx + p.cx;
-        const double w = (yc / zc) * p.fy + p.cy;
-        if (!(fabs(u) < 1073741824.0 && fabs(w) < 1073741824.0)) continue;
-        const int pu = (int)floor(u + 0.5), pv = (int)floor(w + 0.5);
-        if (pu < 0 || pv < 0 || pu >= (int)p.width || pv >= (int)p.height) continue;
-        const unsigned long long word = zbuf[(uint64_t)pv * p.width + (uint64_t)pu];
+        double ax, ay, az, zc;
+        int pu, pv;
+        // (the halves one by one: behind view_project's && this kernel takes four more VGPRs and its depth form loses a wave)
+        if (!view_depth(V, p.cam, p.cam.z_near, wx, wy, wz, ax, ay, az, zc)) continue;
+        if (!view_pixel(V, p.cam, ax, ay, az, zc, pu, pv)) continue;
+        if (!view_inside(p.cam, pu, pv)) continue;
+        const unsigned long long word = zbuf[(uint64_t)pv * p.cam.width + (uint64_t)pu];
         if (word == kRenderEmpty) continue;
-        const Row* row = rows + (uint32_t)word;
-        const float4 q0 = *reinterpret_cast<const float4*>(&row->x);   // x, y, z, nx
-        const float2 q1 = *reinterpret_cast<const float2*>(&row->ny);  // ny, nz
-        const double dx = wx - (double)q0.x, dy = wy - (double)q0.y, dz = wz - (double)q0.z;
-        const double nx = q0.w, ny = q1.x, nz = q1.y;
+        const RowPN m = row_point_normal(rows[(uint32_t)word]);
+        const double dx = wx - m.x, dy = wy - m.y, dz = wz - m.z;
         if (!(((dx * dx + dy * dy) + dz * dz) <= p.max_d2)) continue;
-        if (!(((nx * nx + ny * ny) + nz * nz) <= 2.0)) continue;
-        sum = icp_accumulate(sum, ax, ay, az, nx, ny, nz, dx, dy, dz);
+        if (!(((m.nx * m.nx + m.ny * m.ny) + m.nz * m.nz) <= 2.0)) continue;
+        sum = icp_accumulate(sum, ax, ay, az, m.nx, m.ny, m.nz, dx, dy, dz);
     }
     icp_block_reduce(sum, acc);
 }
@@ -4458,8 +4461,8 @@ struct AlignParams {
     uint32_t n;      // sampled rows: sample s is row s * stride
 };
 
-// One sampled row per thread, grid-stride over at most kTrackMaxBlocks blocks.  The row's point and normal come in as k_track_reduce
-// loads them, its deviation record as two 16-byte loads.  Each thread keeps its 29 sums in registers (icp_accumulate);
+// One sampled row per thread, grid-stride over at most kTrackMaxBlocks blocks.  The row's point and normal come in through
+// row_point_normal, its deviation record as two 16-byte loads.  Each thread keeps its 29 sums in registers (icp_accumulate);
 // icp_block_reduce adds them to acc.
 __global__ __launch_bounds__(256) void k_align_reduce(const AlignParams p, const Row* __restrict__ rows, const Deviation* __restrict__ dev,
                                                       unsigned long long* __restrict__ acc)
@@ -4474,13 +4477,10 @@ __global__ __launch_bounds__(256) void k_align_reduce(const AlignParams p, const
         if (!(flags & kDevFound)) continue;
         if ((p.flags & kAlignSkipBoundary) && (flags & (kDevOnEdge | kDevOnVertex))) continue;
         const float4 d1 = *reinterpret_cast<const float4*>(&dev[j].q[0]);  // q, reserved
-        const Row* row = rows + j;
-        const float4 q0 = *reinterpret_cast<const float4*>(&row->x);   // x, y, z, nx
-        const float2 q1 = *reinterpret_cast<const float2*>(&row->ny);  // ny, nz
-        const double nx = q0.w, ny = q1.x, nz = q1.y;
-        if (!(((nx * nx + ny * ny) + nz * nz) <= 2.0)) continue;
+        const RowPN m = row_point_normal(rows[j]);
+        if (!(((m.nx * m.nx + m.ny * m.ny) + m.nz * m.nz) <= 2.0)) continue;
         const double qx = d1.x, qy = d1.y, qz = d1.z;
-        sum = icp_accumulate(sum, qx - p.c[0], qy - p.c[1], qz - p.c[2], nx, ny, nz, qx - (double)q0.x, qy - (double)q0.y, qz - (double)q0.z);
+        sum = icp_accumulate(sum, qx - p.c[0], qy - p.c[1], qz - p.c[2], m.nx, m.ny, m.nz, qx - m.x, qy - m.y, qz - m.z);
     }
     icp_block_reduce(sum, acc);
 }
@@ -4709,95 +4709,59 @@ struct PlanState {  // the words of one call, zeroed together
 };
 
 struct PlanParams {
-    uint32_t width, height;
+    Pinhole cam;
     uint32_t n_views;      // views of this chunk
     uint32_t cull;         // HFPF_RENDER_CULL_BACKFACES, on the rows
     uint32_t two_sided;    // HFPF_PLAN_TWO_SIDED
     int32_t radius;        // >= 0 fixed, -1 auto
     int32_t max_radius;
-    uint32_t pad;
-    double fx, fy, cx, cy, z_near, z_far, occ_near;
+    double occ_near;
     double r_num_samples;  // (0.5 * cover.spacing) * max(fx, fy)
     double r_num_rows;     // (0.5 * res) * max(fx, fy)
     double min_cos, tolerance, slope;
 };
 
-// The render contract's projection of (x, y, z) into the view T: false unless z_lo < zc < z_far and |u|, |v| < 2^30.
-__device__ __forceinline__ bool plan_project(const double* T, const PlanParams& p, const double z_lo, const double x, const double y, const double z, double& dx,
-                                             double& dy, double& dz, double& zc, int& pu, int& pv)
-{
-    dx = x - T[3], dy = y - T[7], dz = z - T[11];
-    zc = (T[2] * dx + T[6] * dy) + T[10] * dz;
-    if (!(z_lo < zc && zc < p.z_far)) return false;
-    const double xc = (T[0] * dx + T[4] * dy) + T[8] * dz;
-    const double yc = (T[1] * dx + T[5] * dy) + T[9] * dz;
-    const double u = (xc / zc) * p.fx + p.cx;
-    const double w = (yc / zc) * p.fy + p.cy;
-    if (!(fabs(u) < 1073741824.0 && fabs(w) < 1073741824.0)) return false;
-    pu = (int)floor(u + 0.5), pv = (int)floor(w + 0.5);
-    return true;
-}
-
-// One occluder into the depth buffer zv of its view: the splat of k_render_splat on 32-bit words (the same plain load in front of
-// the atomic: words only ever decrease, so the skip is exact).  |pu|, |pv| <= 2^30 and r <= 15: the window's bounds do not wrap.
-__device__ __forceinline__ void plan_splat(const PlanParams& p, uint32_t* __restrict__ zv, const double zc, const int pu, const int pv, const double r_num)
-{
-    int r = p.radius;
-    if (r < 0) {
-        const double ra = floor(r_num / zc);
-        r = ra < (double)p.max_radius ? (int)ra : p.max_radius;
-    }
-    const int x0 = max(pu - r, 0), x1 = min(pu + r, (int)p.width - 1);
-    const int y0 = max(pv - r, 0), y1 = min(pv + r, (int)p.height - 1);
-    const uint32_t word = __float_as_uint((float)zc);
-    for (int py = y0; py <= y1; py++)
-        for (int px = x0; px <= x1; px++) {
-            uint32_t* a = zv + (uint64_t)py * p.width + (uint64_t)px;
-            if (__hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > word) atomicMin(a, word);
-        }
-}
-
 // One lane per sample of `total`, looping over the chunk's views (their poses in LDS, as in k_render_splat): every sample of a valid
-// triangle with a finite point occludes, in the box or not, target or not.
+// triangle with a finite point occludes, in the box or not, target or not.  A depth buffer word is the bits of (float)zc.
 __global__ __launch_bounds__(256) void k_plan_splat_samples(const uint32_t* __restrict__ offset, const CovTri* __restrict__ geo, const uint32_t n_tris,
                                                             const uint32_t total, const double* __restrict__ poses, const PlanParams p,
                                                             uint32_t* __restrict__ zbuf)
 {
     __shared__ double s_pose[kRenderChunkViews * 12];
-    for (uint32_t i = threadIdx.x; i < p.n_views * 12u; i += blockDim.x) s_pose[i] = poses[i];
-    __syncthreads();
+    stage_poses(s_pose, poses, p.n_views);
     const uint64_t gg = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (gg >= total) return;
     uint32_t k;
     const F3 q = cov_sample_point(offset, geo, n_tris, (uint32_t)gg, k);
     if (!(__builtin_isfinite(q.x) && __builtin_isfinite(q.y) && __builtin_isfinite(q.z))) return;
-    const uint64_t WH = (uint64_t)p.width * p.height;
+    const uint64_t WH = (uint64_t)p.cam.width * p.cam.height;
     for (uint32_t v = 0; v < p.n_views; v++) {
         double dx, dy, dz, zc;
         int pu, pv;
-        if (plan_project(&s_pose[12 * v], p, p.occ_near, q.x, q.y, q.z, dx, dy, dz, zc, pu, pv)) plan_splat(p, zbuf + v * WH, zc, pu, pv, p.r_num_samples);
+        if (!view_project(&s_pose[12 * v], p.cam, p.occ_near, q.x, q.y, q.z, dx, dy, dz, zc, pu, pv)) continue;
+        view_splat(zbuf + v * WH, p.cam, pu, pv, view_radius(p.radius, p.max_radius, p.r_num_samples, zc), __float_as_uint((float)zc));
     }
 }
 
-// HFPF_PLAN_MODEL_OCCLUDES: one lane per drawn row of the model, with the rows' own splat rule and the back-face cull of the view.
+// HFPF_PLAN_MODEL_OCCLUDES: one lane per drawn row of the model, with the rows' own splat rule and the back-face cull of the view,
+// between the halves of the projection as in k_render_splat.
 __global__ __launch_bounds__(256) void k_plan_splat_rows(const Row* __restrict__ rows, const uint32_t n_rows, const double* __restrict__ poses,
                                                          const PlanParams p, uint32_t* __restrict__ zbuf)
 {
     __shared__ double s_pose[kRenderChunkViews * 12];
-    for (uint32_t i = threadIdx.x; i < p.n_views * 12u; i += blockDim.x) s_pose[i] = poses[i];
-    __syncthreads();
+    stage_poses(s_pose, poses, p.n_views);
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n_rows) return;
-    const float4 q0 = *reinterpret_cast<const float4*>(&rows[j].x);   // x, y, z, nx
-    const float2 q1 = *reinterpret_cast<const float2*>(&rows[j].ny);  // ny, nz
-    const double nx = q0.w, ny = q1.x, nz = q1.y;
-    const uint64_t WH = (uint64_t)p.width * p.height;
+    const RowPN q = row_point_normal(rows[j]);
+    const uint64_t WH = (uint64_t)p.cam.width * p.cam.height;
     for (uint32_t v = 0; v < p.n_views; v++) {
+        const double* T = &s_pose[12 * v];
         double dx, dy, dz, zc;
         int pu, pv;
-        if (!plan_project(&s_pose[12 * v], p, p.occ_near, q0.x, q0.y, q0.z, dx, dy, dz, zc, pu, pv)) continue;
-        if (p.cull && !(((nx * dx + ny * dy) + nz * dz) < 0.0)) continue;
-        plan_splat(p, zbuf + v * WH, zc, pu, pv, p.r_num_rows);
+        if (!view_depth(T, p.cam, p.occ_near, q.x, q.y, q.z, dx, dy, dz, zc)) continue;
+        if (p.cull && !(((q.nx * dx + q.ny * dy) + q.nz * dz) < 0.0)) continue;
+        if (!view_pixel(T, p.cam, dx, dy, dz, zc, pu, pv)) continue;
+        view_splat(zbuf + v * WH, p.cam, pu, pv, view_radius(p.radius, p.max_radius, p.r_num_rows, zc), __float_as_uint((float)zc));
     }
 }
 
@@ -4840,7 +4804,7 @@ __global__ __launch_bounds__(256) void k_plan_visible(const float4* __restrict__
         const float4 q = tp[i];
         double dx, dy, dz, zc;
         int pu, pv;
-        if (plan_project(T, p, p.z_near, q.x, q.y, q.z, dx, dy, dz, zc, pu, pv) && pu >= 0 && pu < (int)p.width && pv >= 0 && pv < (int)p.height) {
+        if (view_project(T, p.cam, p.cam.z_near, q.x, q.y, q.z, dx, dy, dz, zc, pu, pv) && view_inside(p.cam, pu, pv)) {
             in_view = true;
             const double* N = geo[__float_as_uint(q.w)].N;
             const double NN = dev_dot(N, N);
@@ -4848,7 +4812,7 @@ __global__ __launch_bounds__(256) void k_plan_visible(const float4* __restrict__
             facing = p.min_cos < 0.0 || ((c > 0.0 || p.two_sided) && c * c >= ((p.min_cos * p.min_cos) * NN) * d2);
             if (facing) {
                 const float depth32 = (float)zc;
-                const float zmin = __uint_as_float(zbuf[v * ((uint64_t)p.width * p.height) + (uint64_t)pv * p.width + (uint64_t)pu]);
+                const float zmin = __uint_as_float(zbuf[v * ((uint64_t)p.cam.width * p.cam.height) + (uint64_t)pv * p.cam.width + (uint64_t)pu]);
                 visible = (double)depth32 - (double)zmin <= p.tolerance + p.slope * zc;
                 if (visible) w = tw[i];
             }
@@ -4996,7 +4960,7 @@ constexpr uint32_t kConsSeen = 1u, kConsSupported = 2u, kConsContradicted = 4u, 
 struct ConsParams {
     const uint8_t* depth;   // frame 0 of this span
     uint64_t frame_stride;  // bytes between two frames
-    uint32_t width, height, depth_step, depth_f32;
+    uint32_t depth_step, depth_f32;
     uint32_t n_frames;      // frames of this span
     uint32_t per_chunk;     // frames per chunk (<= kConsChunkFrames)
     uint32_t chunk0;        // first chunk of this launch
@@ -5005,7 +4969,8 @@ struct ConsParams {
     uint32_t gate;          // min_cos >= 0
     int32_t window;
     float unit;             // (float)depth_scale
-    double fx, fy, cx, cy, z_near, z_far, tolerance, slope, min_cos2;
+    Pinhole cam;            // the depth images' intrinsics and size, the call's z range
+    double tolerance, slope, min_cos2;
     // what k_cons_finish reads
     double through_ratio;
     uint32_t min_through;   // max(1, min_through)
@@ -5029,30 +4994,22 @@ __global__ __launch_bounds__(256) void k_consistency(const Row* __restrict__ row
     __shared__ double s_pose[kConsChunkFrames * 12];
     const uint32_t f0 = (p.chunk0 + blockIdx.y) * p.per_chunk;  // < p.n_frames: the host launches no empty chunk
     const uint32_t nf = min(p.per_chunk, p.n_frames - f0);
-    for (uint32_t i = threadIdx.x; i < nf * 12u; i += blockDim.x) s_pose[i] = poses[12ull * f0 + i];
-    __syncthreads();
+    stage_poses(s_pose, poses + 12ull * f0, nf);
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n_rows) return;
-    const float4 q0 = *reinterpret_cast<const float4*>(&rows[j].x);   // x, y, z, nx
-    const float2 q1 = *reinterpret_cast<const float2*>(&rows[j].ny);  // ny, nz
-    const double x = q0.x, y = q0.y, z = q0.z, nx = q0.w, ny = q1.x, nz = q1.y;
+    const RowPN q = row_point_normal(rows[j]);
     uint32_t n_in_view = 0, n_tested = 0, n_support = 0, n_through = 0, n_occluded = 0, first_through = kConsNone;
-    const int W = (int)p.width, H = (int)p.height, win = p.window;
+    const int W = (int)p.cam.width, H = (int)p.cam.height, win = p.window;
     for (uint32_t f = 0; f < nf; f++) {
+        double dx, dy, dz, zc;
+        int pu, pv;
         const double* T = &s_pose[12 * f];
-        const double dx = x - T[3], dy = y - T[7], dz = z - T[11];
-        const double zc = (T[2] * dx + T[6] * dy) + T[10] * dz;
-        if (!(p.z_near < zc && zc < p.z_far)) continue;
-        const double xc = (T[0] * dx + T[4] * dy) + T[8] * dz;
-        const double yc = (T[1] * dx + T[5] * dy) + T[9] * dz;
-        const double u = (xc / zc) * p.fx + p.cx;
-        const double w = (yc / zc) * p.fy + p.cy;
-        if (!(fabs(u) < 1073741824.0 && fabs(w) < 1073741824.0)) continue;
-        const int pu = (int)floor(u + 0.5), pv = (int)floor(w + 0.5);
-        if (pu < 0 || pu >= W || pv < 0 || pv >= H) continue;
+        if (!view_depth(T, p.cam, p.cam.z_near, q.x, q.y, q.z, dx, dy, dz, zc)) continue;
+        if (!view_pixel(T, p.cam, dx, dy, dz, zc, pu, pv)) continue;
+        if (!view_inside(p.cam, pu, pv)) continue;
         n_in_view++;
         if (p.gate) {
-            const double c = -((nx * dx + ny * dy) + nz * dz), d2 = (dx * dx + dy * dy) + dz * dz;
+            const double c = -((q.nx * dx + q.ny * dy) + q.nz * dz), d2 = (dx * dx + dy * dy) + dz * dz;
             if (!(c > 0.0 && c * c >= p.min_cos2 * d2)) continue;
         }
         n_tested++;

@@ -75,6 +75,28 @@ def test_bit_exact_against_render_ref(hfpf_mod, session):
             n_drawn.setdefault(label, []).append(int(drawn.sum()))
     print("pixels drawn per view and option set:", n_drawn)
     assert all(max(n) > 1000 for n in n_drawn.values()), n_drawn  # every view sees a good part of the model
+    # a grazing view: the camera plane passes 1e-8 m in front of two rows, one on the optical axis (drawn, its auto radius capped),
+    # the other far to the side at the same depth: it passes the z test and its u leaves +-2^30
+    pose, K, z_range = _grazing(R.drawn_rows(rows, 1), sc.K)
+    W, H = 64, 48
+    ok, zc, _, _ = R.project(R.drawn_rows(rows, 1), pose, K, z_range)
+    assert ((z_range[0] < zc) & (zc < z_range[1]) & ~ok).any(), "no drawn row passes the z test and fails the 2^30 test"
+    ref = R.render(rows, pose, K, W, H, res, z_range, 1, -1, 4, 0)
+    assert (~np.isnan(ref["depth"])).any(), "the grazing view draws no row"
+    same_planes(g.render(pose, K, W, H, z_range=z_range, min_count=1, splat_radius=-1, max_splat_radius=4), ref, "grazing view")
+
+
+def _grazing(drawn, K):
+    """(pose, K, z_range): row 0 of `drawn` on the optical axis and the row farthest from it on the camera's x axis, both 1e-8 m in
+    front of the camera plane; z_near = 1e-9."""
+    p = np.stack([drawn[k].astype(np.float64) for k in ("x", "y", "z")], axis=-1)
+    d = p - p[0]
+    x = d[np.argmax((d * d).sum(axis=1))]
+    x /= np.linalg.norm(x)
+    z = np.eye(3)[np.argmin(np.abs(x))]  # the world axis farthest from x, made orthogonal to it
+    z = z - (z @ x) * x
+    z /= np.linalg.norm(z)
+    return _pose(np.stack([x, np.cross(z, x), z], axis=-1), p[0] - 1e-8 * z), (K[0], K[1], 32.0, 24.0), (1e-9, 3.0)
 
 
 def test_count_zero_rows_are_never_drawn(hfpf_mod, session):

@@ -14,7 +14,7 @@ if [ "$1" = "--rev" ]; then
     git -C $R show $REV:high-fidelity-pointcloud-fusion_amd/csrc/$f > $TMP/high-fidelity-pointcloud-fusion_amd/csrc/$f
   done
   # (a revision from before one of these headers existed builds without it)
-  for f in scratch_layout.hpp host_plan.hpp; do
+  for f in scratch_layout.hpp host_plan.hpp view.hpp; do
     git -C $R show $REV:high-fidelity-pointcloud-fusion_amd/csrc/$f > $TMP/high-fidelity-pointcloud-fusion_amd/csrc/$f 2>/dev/null ||
       rm -f $TMP/high-fidelity-pointcloud-fusion_amd/csrc/$f
   done
