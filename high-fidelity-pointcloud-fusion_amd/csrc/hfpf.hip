@@ -359,6 +359,10 @@ struct hfpf_handle {
     // hfpf_plan_views*: the samples' target marks; their scan; the targets (point + triangle, weight); the views' bitsets and the
     // remaining set; the cover records, the scores, the gains and the call's state words
     DevBuf plan_mark{bufs}, plan_scan{bufs}, plan_targets{bufs}, plan_bits{bufs}, plan_ctr{bufs};
+    // hfpf_section_mesh*: the counters, the planes, the plane records and the per-plane counts and bases; the segment and point keys
+    // (unsorted, sorted, unique) and the sort's values; per point its f64 coordinates, forest, root, flags, scan and degrees.  The
+    // transformed vertices lie in dev_tri, a host mesh in dev_mesh
+    DevBuf sec_ctr{bufs}, sec_keys{bufs}, sec_data{bufs};
     // hfpf_depth_consistency*: one upload's frames of the host form, the poses, the records / summary / keep marks and their scan
     DevBuf cons_in{bufs}, cons_pose{bufs}, cons_recs{bufs};
     DevBuf hide_in{bufs}, hide_mark{bufs};  // hfpf_hide_*: one upload's entries of the host form (voxels, then selector words); the mark words and the call's counters
@@ -3966,6 +3970,217 @@ int hfpf_cover_mesh(hfpf_handle* h, const hfpf_cover_opts* o, const void* verts,
 }
 
 void hfpf_free_coverage(hfpf_tri_coverage* cov) { free(cov); }
+
+// ---- planar sections of a mesh (include/hfpf.h) -------------------------------------------------------------------------------------
+int hfpf_check_section_opts(const hfpf_section_opts* o)
+{
+    return o && o->struct_size == sizeof(hfpf_section_opts) && o->flags == 0 && o->reserved == 0 ? HFPF_OK : HFPF_ERR_BAD_ARG;
+}
+
+static_assert(sizeof(SecPoint) == sizeof(hfpf_section_point) && sizeof(SecSegment) == sizeof(hfpf_section_segment) &&
+                  sizeof(SecContour) == sizeof(hfpf_section_contour) && sizeof(SecPlane) == sizeof(hfpf_section_plane),
+              "the device records are the public ones");
+static_assert(kSecMaxPlanes == HFPF_SECTION_MAX_PLANES && kSecPlaneCap == HFPF_SECTION_MAX_PLANE_SEGMENTS, "host_plan.hpp restates the header's limits");
+
+struct SectionCounts {
+    uint64_t n_points = 0, n_segments = 0, n_contours = 0;
+};
+
+// Validated arguments in, the mesh on the device, under the lock.  The transformed vertices (compare's kernel); the count pass over
+// every chunk of planes; the read-back of the per-plane counts (the cap test, the bases and the size of everything behind); the emit
+// pass; the two sorts and the unique; points, links, flatten, the scan of the root flags (the number of contours: only now can the
+// three result arrays be sized, so the kernels behind write every record once and whole); label, measure, finish; the read-back of
+// the plane records.  recs and S are the caller's locals: nothing of the caller's is written before the call has succeeded.  Not timed:
+// hfpf_get_kernel_time has no id for it (tools/section_rate.py times it with events of its own).
+static int section_locked(hfpf_handle* h, const MeshRef& m, const double* pose, const double* planes, uint32_t n_planes, bool on_device, ResultSet* out,
+                          SectionCounts* nout, std::vector<hfpf_section_plane>* recs, hfpf_section_summary* S)
+{
+    int rc;
+    memset(S, 0, sizeof *S);
+    recs->assign(n_planes, hfpf_section_plane{});
+    *nout = SectionCounts{};
+    if (m.n_tris == 0) return HFPF_OK;
+    const uint64_t P1 = (uint64_t)n_planes + 1;
+    double* V; SecCounters* ctr; double* d_planes; SecPlane* d_recs;
+    uint32_t *count, *first;  // per plane (n_planes + 1 entries each): the crossings (later the emit pass's cursor) and their exclusive sums
+    if ((rc = scratch_n(h, h->dev_tri, 3 * std::max<uint64_t>(m.n_verts, 1), &V))) return rc;
+    if ((rc = scratch(h, h->sec_ctr, ScratchLayout().add(&ctr, 1).add(&d_planes, 4 * P1).add(&d_recs, P1).add(&count, P1).add(&first, P1)))) return rc;
+    HIPCHK(h, hipMemsetAsync(ctr, 0, sizeof(SecCounters), h->stream));
+    HIPCHK(h, hipMemsetAsync(count, 0, P1 * 4, h->stream));
+    HIPCHK(h, hipMemsetAsync(d_recs, 0, P1 * sizeof(SecPlane), h->stream));
+    if (n_planes) HIPCHK(h, hipMemcpyAsync(d_planes, planes, (size_t)n_planes * 32, hipMemcpyHostToDevice, h->stream));
+    DevParams vp{};  // what k_dev_verts reads of it
+    memcpy(vp.T, pose, sizeof vp.T);
+    vp.n_verts = m.n_verts, vp.n_tris = (uint32_t)m.n_tris, vp.stride = m.stride;
+    SecParams p{};
+    for (int a = 0; a < 3; a++) p.c[a] = (h->g.min[a] + h->g.max[a]) * 0.5;
+    p.n_verts = m.n_verts, p.n_tris = (uint32_t)m.n_tris;
+    const uint32_t n_chunks = section_chunks(n_planes);
+    const dim3 grid_t(section_grid(m.n_tris));
+    hipLaunchKernelGGL(k_dev_verts, dim3(blocks_for(m.n_verts, 256)), dim3(256), 0, h->stream, vp, (const uint8_t*)m.verts, V);
+    for (uint32_t c = 0; c < n_chunks; c++) {
+        p.plane0 = c * kSecChunkPlanes, p.np = section_chunk_planes(n_planes, c), p.count_tris = c == 0 ? 1u : 0u;
+        hipLaunchKernelGGL(k_section<false>, grid_t, dim3(256), 0, h->stream, p, m.tris, V, d_planes, count, (const uint32_t*)nullptr, (uint64_t*)nullptr,
+                           (uint32_t*)nullptr, (uint64_t*)nullptr, ctr);
+    }
+    HIPCHK(h, hipGetLastError());
+    SecCounters hc;
+    std::vector<uint32_t> h_count(P1, 0u);
+    HIPCHK(h, hipMemcpyAsync(&hc, ctr, sizeof hc, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h_count.data(), count, P1 * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<uint64_t> first64(P1, 0);
+    const SecCapFault cap = section_cap_test(h_count.data(), n_planes, first64.data());
+    if (cap.over) {  // nothing on the handle was touched: it stays usable
+        if (cap.plane < n_planes)
+            return fail(h, HFPF_ERR_CAPACITY, "section_mesh: plane %u has %llu segments, more than the 2^20 a plane may have", cap.plane, (unsigned long long)cap.count);
+        return fail(h, HFPF_ERR_CAPACITY, "section_mesh: %llu segments in all exceed the 2^31 - 1 a call takes", (unsigned long long)cap.count);
+    }
+    S->n_tris_valid = hc.n_valid, S->n_tris_invalid = hc.n_invalid, S->n_tris_far = hc.n_far;
+    const uint64_t ns = cap.count;
+    if (ns == 0) return HFPF_OK;
+    std::vector<uint32_t> first32(P1);
+    for (uint64_t j = 0; j < P1; j++) first32[j] = (uint32_t)first64[j];
+    HIPCHK(h, hipMemcpyAsync(first, first32.data(), P1 * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(count, 0, P1 * 4, h->stream));
+    uint64_t *seg_in, *seg_out, *pk, *pk_sorted, *pk_unique, *ucount;
+    uint32_t *val_in, *val_out;
+    if ((rc = scratch(h, h->sec_keys, ScratchLayout().add(&seg_in, ns).add(&seg_out, ns).add(&pk, 2 * ns).add(&pk_sorted, 2 * ns).add(&pk_unique, 2 * ns)
+                                          .add(&ucount, 1).add(&val_in, ns).add(&val_out, ns))))
+        return rc;
+    // (an append that the count pass did not announce would leave a hole: all ones sort behind every key and fail k_sec_link's test)
+    HIPCHK(h, hipMemsetAsync(val_in, 0xFF, ns * 4, h->stream));
+    HIPCHK(h, hipMemsetAsync(seg_in, 0xFF, ns * 8, h->stream));
+    HIPCHK(h, hipMemsetAsync(pk, 0xFF, 2 * ns * 8, h->stream));
+    p.n_total = (uint32_t)ns;
+    for (uint32_t c = 0; c < n_chunks; c++) {
+        p.plane0 = c * kSecChunkPlanes, p.np = section_chunk_planes(n_planes, c), p.count_tris = 0;
+        hipLaunchKernelGGL(k_section<true>, grid_t, dim3(256), 0, h->stream, p, m.tris, V, d_planes, count, first, seg_in, val_in, pk, ctr);
+    }
+    HIPCHK(h, hipGetLastError());
+    if ((rc = sort_pairs_u64(h, seg_in, seg_out, val_in, val_out, ns, kSecSegKeyBits))) return rc;
+    if ((rc = sort_keys_u64(h, pk, pk_sorted, 2 * ns, kSecPointKeyBits))) return rc;
+    uint64_t np = 0;
+    if ((rc = unique_keys_locked(h, pk_sorted, 2 * ns, pk_unique, ucount, &np))) return rc;
+    if (np == 0 || np > 2 * ns) return fail(h, HFPF_ERR_STATE, "section_mesh: %llu points from %llu segments (internal)", (unsigned long long)np, (unsigned long long)ns);
+    const uint64_t N1 = np + 1;
+    double* Pd;
+    uint32_t *parent, *root, *flag, *cbase, *deg_out, *deg_in;
+    if ((rc = scratch(h, h->sec_data, ScratchLayout().add(&Pd, 3 * np).add(&parent, N1).add(&root, N1).add(&flag, N1).add(&cbase, N1).add(&deg_out, N1)
+                                          .add(&deg_in, N1))))
+        return rc;
+    const dim3 grid_p(blocks_for(np, 256)), grid_p1(blocks_for(N1, 256)), grid_s(blocks_for(ns, 256));
+    uint64_t* seg_ends = seg_in;  // the unsorted segment keys are dead behind their sort
+    hipLaunchKernelGGL(k_sec_points, grid_p, dim3(256), 0, h->stream, pk_unique, (uint32_t)np, d_planes, n_planes, V, m.n_verts, Pd, parent, deg_out, deg_in);
+    hipLaunchKernelGGL(k_sec_link, grid_s, dim3(256), 0, h->stream, val_out, (uint32_t)ns, pk, pk_unique, (uint32_t)np, seg_ends, parent, deg_out, deg_in);
+    hipLaunchKernelGGL(k_comp_flatten, grid_p1, dim3(256), 0, h->stream, parent, (uint32_t)np, root, flag);
+    HIPCHK(h, hipGetLastError());
+    uint64_t nc = 0;
+    if ((rc = scan_counts_locked(h, flag, cbase, np, &nc))) return rc;
+    if (nc == 0) return fail(h, HFPF_ERR_STATE, "section_mesh: no contour for %llu points (internal)", (unsigned long long)np);
+    ResultSet set;
+    set.add(np * sizeof(SecPoint));
+    set.add(ns * sizeof(SecSegment));
+    set.add(nc * sizeof(SecContour));
+    if ((rc = result_alloc(h, set, on_device, "section_mesh"))) return rc;
+    SecPoint* pts = (SecPoint*)set.a[0].dev;
+    SecSegment* segs = (SecSegment*)set.a[1].dev;
+    SecContour* conts = (SecContour*)set.a[2].dev;
+    HIPCHK(h, hipMemsetAsync(conts, 0, nc * sizeof(SecContour), h->stream));
+    hipLaunchKernelGGL(k_sec_label, grid_p, dim3(256), 0, h->stream, root, cbase, (uint32_t)np, pk_unique, Pd, deg_out, deg_in, pts, conts);
+    hipLaunchKernelGGL(k_sec_measure, grid_s, dim3(256), 0, h->stream, seg_out, seg_ends, (uint32_t)ns, d_planes, pts, Pd, segs, conts);
+    hipLaunchKernelGGL(k_sec_finish, dim3(blocks_for(nc, 256)), dim3(256), 0, h->stream, (uint32_t)nc, conts, d_recs, &ctr->n_closed);
+    HIPCHK(h, hipGetLastError());
+    static_assert(sizeof(SecPlane) == sizeof(hfpf_section_plane), "the device plane record is the public one");
+    if (n_planes) HIPCHK(h, hipMemcpyAsync(recs->data(), d_recs, (size_t)n_planes * sizeof(SecPlane), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&hc, ctr, sizeof hc, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    uint64_t fs = 0, fp = 0, fc = 0;
+    for (hfpf_section_plane& r : *recs) {  // the planes before it, also for a plane that has nothing
+        r.first_segment = (uint32_t)fs, r.first_point = (uint32_t)fp, r.first_contour = (uint32_t)fc;
+        fs += r.n_segments, fp += r.n_points, fc += r.n_contours;
+    }
+    if (fs != ns || fp != np || fc != nc) return fail(h, HFPF_ERR_STATE, "section_mesh: the plane records do not add up to the arrays (internal)");
+    S->n_segments = ns, S->n_points = np, S->n_contours = nc, S->n_closed = hc.n_closed;
+    nout->n_points = np, nout->n_segments = ns, nout->n_contours = nc;
+    set.keep(out);
+    return HFPF_OK;
+}
+
+// The checks of both forms, all of them before anything is read through a mesh pointer.  0 = fine, else the text of the fault.
+static const char* section_args_fault(const hfpf_section_opts* o, const MeshRef& m, const double* pose, const double* planes, uint32_t n_planes,
+                                      const void* const outs[8], bool on_device)
+{
+    if (hfpf_check_section_opts(o) != HFPF_OK) return "invalid hfpf_section_opts";
+    if (const char* f = mesh_args_fault(m, pose)) return f;
+    if (const char* f = section_counts_fault(m.n_verts, m.n_tris, n_planes)) return f;
+    if (!planes && n_planes) return "NULL planes with a non-zero count";
+    if (section_first_bad_plane(planes, n_planes) != n_planes) return "a plane with a non-finite value or a normal of no finite length > 0";
+    for (int i = 0; i < 7; i++)
+        if (!outs[i]) return "NULL output pointer";
+    if (!outs[7] && n_planes) return "NULL plane records with a non-zero count";
+    if (on_device && mesh_misaligned(m)) return "device mesh pointers must be 4-byte aligned";
+    return nullptr;
+}
+
+int hfpf_section_mesh_device(hfpf_handle* h, const hfpf_section_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* dev_tris,
+                             uint64_t n_tris, const double* pose_3x4, const double* planes, uint32_t n_planes, hfpf_section_point** dev_points, uint64_t* n_points,
+                             hfpf_section_segment** dev_segments, uint64_t* n_segments, hfpf_section_contour** dev_contours, uint64_t* n_contours,
+                             hfpf_section_plane* plane_recs, hfpf_section_summary* summary)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    const MeshRef m{dev_verts, n_verts, vertex_stride, dev_tris, n_tris};
+    const void* const outs[8] = {dev_points, n_points, dev_segments, n_segments, dev_contours, n_contours, summary, plane_recs};
+    if (const char* f = section_args_fault(o, m, pose_3x4, planes, n_planes, outs, true)) return fail(h, HFPF_ERR_BAD_ARG, "section_mesh_device: %s", f);
+    if (int rc = local_read_prologue_locked(h, "section_mesh")) return rc;
+    ResultSet set;
+    SectionCounts n;
+    std::vector<hfpf_section_plane> recs;
+    hfpf_section_summary s;
+    if (int rc = section_locked(h, m, pose_3x4, planes, n_planes, true, &set, &n, &recs, &s)) return rc;
+    *dev_points = (hfpf_section_point*)set.a[0].dev, *dev_segments = (hfpf_section_segment*)set.a[1].dev, *dev_contours = (hfpf_section_contour*)set.a[2].dev;
+    *n_points = n.n_points, *n_segments = n.n_segments, *n_contours = n.n_contours, *summary = s;
+    if (n_planes) memcpy(plane_recs, recs.data(), (size_t)n_planes * sizeof(hfpf_section_plane));
+    return HFPF_OK;
+}
+
+int hfpf_section_mesh(hfpf_handle* h, const hfpf_section_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
+                      const double* pose_3x4, const double* planes, uint32_t n_planes, hfpf_section_point** points, uint64_t* n_points,
+                      hfpf_section_segment** segments, uint64_t* n_segments, hfpf_section_contour** contours, uint64_t* n_contours, hfpf_section_plane* plane_recs,
+                      hfpf_section_summary* summary)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    const MeshRef m{verts, n_verts, vertex_stride, tris, n_tris};
+    const void* const outs[8] = {points, n_points, segments, n_segments, contours, n_contours, summary, plane_recs};
+    if (const char* f = section_args_fault(o, m, pose_3x4, planes, n_planes, outs, false)) return fail(h, HFPF_ERR_BAD_ARG, "section_mesh: %s", f);
+    if (int rc = local_read_prologue_locked(h, "section_mesh")) return rc;
+    SectionCounts n;
+    std::vector<hfpf_section_plane> recs(n_planes, hfpf_section_plane{});
+    hfpf_section_summary s;
+    memset(&s, 0, sizeof s);
+    void* host[3] = {nullptr, nullptr, nullptr};
+    if (n_tris) {
+        MeshRef d;
+        if (int rc = upload_mesh_locked(h, "section_mesh", m, &d)) return rc;
+        ResultSet set;
+        if (int rc = section_locked(h, d, pose_3x4, planes, n_planes, false, &set, &n, &recs, &s)) return rc;
+        if (n.n_segments)
+            if (int rc = result_to_host(h, set, "section_mesh", host)) return rc;
+    }
+    *points = (hfpf_section_point*)host[0], *segments = (hfpf_section_segment*)host[1], *contours = (hfpf_section_contour*)host[2];
+    *n_points = n.n_points, *n_segments = n.n_segments, *n_contours = n.n_contours, *summary = s;
+    if (n_planes) memcpy(plane_recs, recs.data(), (size_t)n_planes * sizeof(hfpf_section_plane));
+    return HFPF_OK;
+}
+
+void hfpf_free_section(hfpf_section_point* points, hfpf_section_segment* segments, hfpf_section_contour* contours)
+{
+    free(points);
+    free(segments);
+    free(contours);
+}
 
 // ---- view planning (include/hfpf.h) ---------------------------------------------------------------------------------------------
 int hfpf_check_plan_opts(const hfpf_plan_opts* o)

@@ -295,4 +295,84 @@ inline uint64_t hide_span_bytes(uint64_t n, uint32_t stride, uint32_t item) { re
 // A snapshot carries the HIDDEN section only when something is hidden: a blob of a handle with H empty is the blob of old.
 inline bool snapshot_carries_hidden(uint64_t n_hidden) { return n_hidden != 0; }
 
+// ---- planar sections of a mesh (hfpf_section_mesh*, include/hfpf.h) ----
+
+constexpr uint32_t kSecChunkPlanes = 64;             // planes per launch of k_section: they sit in LDS (2 KB), as a consistency chunk's poses do
+constexpr uint32_t kSecMaxPlanes = 4096;             // = HFPF_SECTION_MAX_PLANES: 12 bits of a key
+constexpr uint64_t kSecMaxVerts = 1ull << 26;        // 26 bits of a key per vertex index
+constexpr uint64_t kSecPlaneCap = 1ull << 20;        // = HFPF_SECTION_MAX_PLANE_SEGMENTS: keeps the q32 and q28 sums below 2^62
+constexpr uint64_t kSecTotalCap = (1ull << 31) - 1;  // segments of a call: twice as many points still have 32-bit ids
+constexpr uint32_t kSecTriTile = 256;                // triangles per workgroup of k_section
+constexpr unsigned kSecSegKeyBits = 44, kSecPointKeyBits = 64;  // what the two sorts compare
+
+// A point's key: plane | va | vb with va < vb, so that ascending keys are ascending (plane, va, vb).  constexpr: the kernels and
+// tests/section_plan_check.cpp run the same lines.
+constexpr uint64_t sec_point_key(uint32_t plane, uint32_t a, uint32_t b)
+{
+    return ((uint64_t)plane << 52) | ((uint64_t)(a < b ? a : b) << 26) | (uint64_t)(a < b ? b : a);
+}
+constexpr uint32_t sec_key_plane(uint64_t key) { return (uint32_t)(key >> 52); }
+constexpr uint32_t sec_key_va(uint64_t key) { return (uint32_t)(key >> 26) & 0x3FFFFFFu; }
+constexpr uint32_t sec_key_vb(uint64_t key) { return (uint32_t)key & 0x3FFFFFFu; }
+// A segment's key: plane | triangle (n_tris < 2^32 - 1); ascending keys are ascending (plane, triangle).
+constexpr uint64_t sec_segment_key(uint32_t plane, uint32_t tri) { return ((uint64_t)plane << 32) | tri; }
+constexpr uint32_t sec_seg_plane(uint64_t key) { return (uint32_t)(key >> 32); }
+constexpr uint32_t sec_seg_tri(uint64_t key) { return (uint32_t)key; }
+
+// The counts of a call that need no pointer: 0 = fine, else the text of the fault.
+inline const char* section_counts_fault(uint64_t n_verts, uint64_t n_tris, uint64_t n_planes)
+{
+    if (n_verts > kSecMaxVerts) return "n_verts must not exceed 2^26";
+    if (n_tris >= 0xFFFFFFFFull) return "n_tris must stay below 2^32 - 1";
+    if (n_planes > kSecMaxPlanes) return "n_planes must not exceed 4096";
+    return nullptr;
+}
+// One plane (n.x, n.y, n.z, d): all four finite, nn = dot(n, n) finite and > 0, evaluated as the contract writes it.
+inline bool section_plane_ok(const double* p)
+{
+    for (int i = 0; i < 4; i++)
+        if (!(p[i] - p[i] == 0.0)) return false;  // false for an infinity and for a NaN
+    const double nn = (p[0] * p[0] + p[1] * p[1]) + p[2] * p[2];
+    return nn - nn == 0.0 && nn > 0.0;
+}
+// The first plane of n that fails, or n.
+inline uint32_t section_first_bad_plane(const double* planes, uint32_t n)
+{
+    for (uint32_t j = 0; j < n; j++)
+        if (!section_plane_ok(planes + 4ull * j)) return j;
+    return n;
+}
+
+// How k_section walks the planes: chunk c holds planes [64 c, min(n, 64 (c + 1))); a call without planes still runs one (empty)
+// chunk, which counts the triangles.  The grid is one lane per triangle, one workgroup at least.
+inline uint32_t section_chunks(uint32_t n_planes) { return std::max(1u, (n_planes + kSecChunkPlanes - 1) / kSecChunkPlanes); }
+inline uint32_t section_chunk_planes(uint32_t n_planes, uint32_t chunk)
+{
+    const uint64_t first = (uint64_t)chunk * kSecChunkPlanes;
+    return first >= n_planes ? 0u : (uint32_t)std::min<uint64_t>(kSecChunkPlanes, n_planes - first);
+}
+inline uint32_t section_grid(uint64_t n_tris) { return (uint32_t)std::max<uint64_t>(1, (n_tris + kSecTriTile - 1) / kSecTriTile); }
+
+// The cap test over the per-plane segment counts: the first plane beyond kSecPlaneCap (and its count), else the total beyond
+// kSecTotalCap (plane = n_planes), else fine.  first[] (n_planes + 1 entries, when not NULL) gets the exclusive sums.
+struct SecCapFault {
+    bool over;
+    uint32_t plane;  // n_planes: the total is what exceeds
+    uint64_t count;
+};
+inline SecCapFault section_cap_test(const uint32_t* counts, uint32_t n_planes, uint64_t* first, uint64_t plane_cap = kSecPlaneCap, uint64_t total_cap = kSecTotalCap)
+{
+    uint64_t total = 0;
+    SecCapFault bad{false, 0, 0};
+    for (uint32_t j = 0; j < n_planes; j++) {
+        if (first) first[j] = total;
+        if (!bad.over && counts[j] > plane_cap) bad = SecCapFault{true, j, counts[j]};
+        total += counts[j];
+    }
+    if (first) first[n_planes] = total;
+    if (!bad.over && total > total_cap) bad = SecCapFault{true, n_planes, total};
+    if (!bad.over) bad.count = total;
+    return bad;
+}
+
 }  // namespace hfpf

@@ -5106,4 +5106,272 @@ __global__ __launch_bounds__(256) void k_cons_compact(const Row* __restrict__ ro
     out_recs[o] = recs[j];
 }
 
+// ---- planar sections of a mesh (hfpf_section_mesh*; contract in include/hfpf.h, numpy restatement tests/section_ref.py) --------------
+// k_dev_verts transforms the vertices.  k_section meets every triangle with a chunk of planes, first to count the crossings per
+// plane, then to append them: a 64-bit segment key (plane | triangle), the append position as the sort's value, and the keys of the
+// two points in segment orientation.  The sort of the segment keys gives the (plane, triangle) order whatever the append order was;
+// the sort and unique of the point keys number the points; k_sec_points computes a point from its key alone; k_sec_link finds a
+// segment's two points by binary search, counts the degrees and unites the two in comp_unite's forest (a contour's root is its
+// smallest point); k_comp_flatten and a scan of the root flags number the contours; k_sec_label, k_sec_measure and k_sec_finish are
+// the reductions per point, per segment and per contour.  Integer atomics only: nothing depends on the schedule.
+struct SecPoint {  // = hfpf_section_point
+    float x, y, z;
+    uint32_t plane, va, vb, contour, ends;
+};
+struct SecSegment {  // = hfpf_section_segment
+    uint32_t p0, p1, tri, contour;
+};
+struct __attribute__((aligned(8))) SecContour {  // = hfpf_section_contour
+    uint32_t plane, first_point, n_points, n_segments, n_ends, flags;
+    long long length_q32, area_q28;
+    unsigned long long reserved;
+};
+struct __attribute__((aligned(8))) SecPlane {  // = hfpf_section_plane (the three first_* words are the host's prefix sums)
+    uint32_t first_segment, n_segments, first_point, n_points, first_contour, n_contours, n_closed, n_branched;
+    long long length_q32, area_q28;
+    unsigned long long reserved[2];
+};
+struct SecCounters {  // zeroed in front of the count pass
+    unsigned long long n_valid, n_invalid, n_far, n_closed;
+};
+static_assert(sizeof(SecPoint) == 32 && sizeof(SecSegment) == 16 && sizeof(SecContour) == 48 && sizeof(SecPlane) == 64, "the section records");
+
+constexpr uint32_t kSecClosed = 1u, kSecBranched = 2u;
+constexpr uint32_t kSecOpenMark = 0x80000000u;  // a contour's flags between k_sec_label and k_sec_finish: some point is not (1 in, 1 out)
+constexpr double kSecHeadroom = 32.0;           // metres about the box's centre: the IN RANGE rule
+
+struct SecParams {
+    double c[3];        // the centre of the bounding box
+    uint64_t n_verts;
+    uint32_t n_tris;
+    uint32_t plane0, np;   // this chunk: its first plane and how many (0..kSecChunkPlanes)
+    uint32_t count_tris;   // 1: this launch also counts the valid, invalid and far triangles (one launch per call)
+    uint32_t n_total;      // EMIT: the segments of the call (the bound of every append)
+};
+
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_section(const SecParams p, const uint32_t* __restrict__ tris, const double* __restrict__ V,
+                                                 const double* __restrict__ planes, uint32_t* __restrict__ count, const uint32_t* __restrict__ first,
+                                                 uint64_t* __restrict__ seg_key, uint32_t* __restrict__ seg_val, uint64_t* __restrict__ pt_key,
+                                                 SecCounters* __restrict__ ctr)
+{
+    __shared__ double s_plane[kSecChunkPlanes * 4];
+    for (uint32_t i = threadIdx.x; i < 4u * p.np; i += 256u) s_plane[i] = planes[4ull * p.plane0 + i];
+    __syncthreads();
+    const uint64_t k64 = (uint64_t)blockIdx.x * kSecTriTile + threadIdx.x;
+    const bool live = k64 < p.n_tris;  // no lane leaves before the last ballot
+    const uint32_t k = live ? (uint32_t)k64 : 0u;
+    const unsigned lane = threadIdx.x & 63u;
+    DevTri tr;
+    bool valid = false, act = false;
+    if (live) {
+        double ab[3], ac[3], NN, L2;
+        valid = dev_tri_valid(p.n_verts, tris, V, k, tr, ab, ac, NN, L2);
+        act = valid;
+        if (valid) {
+#pragma unroll
+            for (int a = 0; a < 3; a++)
+                act = act && fabs(tr.A[a] - p.c[a]) < kSecHeadroom && fabs(tr.B[a] - p.c[a]) < kSecHeadroom && fabs(tr.C[a] - p.c[a]) < kSecHeadroom;
+        }
+    }
+    if (!EMIT && p.count_tris) {
+        const unsigned long long mv = __ballot(valid), mi = __ballot(live && !valid), mf = __ballot(valid && !act);
+        if (lane == 0) {
+            if (mv) atomicAdd(&ctr->n_valid, (unsigned long long)__popcll(mv));
+            if (mi) atomicAdd(&ctr->n_invalid, (unsigned long long)__popcll(mi));
+            if (mf) atomicAdd(&ctr->n_far, (unsigned long long)__popcll(mf));
+        }
+    }
+    uint32_t idx[3] = {0u, 0u, 0u};
+    if (EMIT && act) idx[0] = tris[3ull * k], idx[1] = tris[3ull * k + 1], idx[2] = tris[3ull * k + 2];
+    for (uint32_t j = 0; j < p.np; j++) {
+        const double* q = &s_plane[4u * j];
+        uint32_t in_mask = 0u;
+        if (act) {
+            const double sa = dev_dot(q, tr.A) - q[3], sb = dev_dot(q, tr.B) - q[3], sc = dev_dot(q, tr.C) - q[3];
+            in_mask = (sa < 0.0 ? 1u : 0u) | (sb < 0.0 ? 2u : 0u) | (sc < 0.0 ? 4u : 0u);
+        }
+        const bool cross = in_mask != 0u && in_mask != 7u;
+        const unsigned long long m = __ballot(cross);
+        if (m == 0ull) continue;  // wave-uniform
+        const uint32_t plane = p.plane0 + j;
+        const unsigned leader = (unsigned)__ffsll((long long)m) - 1u;
+        uint32_t base = 0u;
+        if (lane == leader) base = atomicAdd(&count[plane], (uint32_t)__popcll(m));  // one atomic per wave and plane
+        if (!EMIT) continue;
+        base = __shfl(base, (int)leader);
+        if (!cross) continue;
+        const uint64_t pos = (uint64_t)first[plane] + base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (pos >= p.n_total) continue;  // the count pass sized the arrays for exactly these appends
+        const bool lone_in = __popc(in_mask) == 1;
+        const uint32_t bit = lone_in ? in_mask : (in_mask ^ 7u);  // the vertex that differs from the other two
+        const int L = bit == 1u ? 0 : (bit == 2u ? 1 : 2);
+        const uint32_t vL = idx[L], vN = idx[(L + 1) % 3], vP = idx[(L + 2) % 3];
+        const uint64_t k_prev = sec_point_key(plane, vP, vL), k_next = sec_point_key(plane, vL, vN);
+        seg_key[pos] = sec_segment_key(plane, k);
+        seg_val[pos] = (uint32_t)pos;
+        pt_key[2ull * pos] = lone_in ? k_prev : k_next;
+        pt_key[2ull * pos + 1] = lone_in ? k_next : k_prev;
+    }
+}
+
+// One lane per unique point: P from its key alone, always from the lower index to the higher.  Also the point's entry in the forest
+// and its two degree words.
+__global__ __launch_bounds__(256) void k_sec_points(const uint64_t* __restrict__ ukeys, const uint32_t n_points, const double* __restrict__ planes,
+                                                    const uint32_t n_planes, const double* __restrict__ V, const uint64_t n_verts, double* __restrict__ Pd,
+                                                    uint32_t* __restrict__ parent, uint32_t* __restrict__ deg_out, uint32_t* __restrict__ deg_in)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_points) return;
+    const uint64_t key = ukeys[i];
+    const uint32_t plane = sec_key_plane(key), va = sec_key_va(key), vb = sec_key_vb(key);
+    parent[i] = i;
+    deg_out[i] = 0u;
+    deg_in[i] = 0u;
+    if (plane >= n_planes || va >= n_verts || vb >= n_verts) {  // no key the emit pass writes; nothing is loaded through such a key
+        Pd[3ull * i] = Pd[3ull * i + 1] = Pd[3ull * i + 2] = 0.0;
+        return;
+    }
+    const double* q = planes + 4ull * plane;
+    const double* A = V + 3ull * va;
+    const double* B = V + 3ull * vb;
+    const double sa = dev_dot(q, A) - q[3], sb = dev_dot(q, B) - q[3];
+    const double t = sa / (sa - sb);
+#pragma unroll
+    for (int a = 0; a < 3; a++) Pd[3ull * i + a] = A[a] + t * (B[a] - A[a]);
+}
+
+// The rank of `key` in the sorted, distinct ukeys[0, n): every key searched for is in the list.
+__device__ __forceinline__ uint32_t sec_rank(const uint64_t* __restrict__ ukeys, const uint32_t n, const uint64_t key)
+{
+    uint32_t lo = 0u, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (ukeys[mid] < key) lo = mid + 1u;
+        else hi = mid;
+    }
+    return lo < n ? lo : n - 1u;
+}
+
+// One lane per segment, in sorted order: its two points (seg_ends: p0 | p1 << 32), their degrees and their union.
+__global__ __launch_bounds__(256) void k_sec_link(const uint32_t* __restrict__ val_sorted, const uint32_t n_segs, const uint64_t* __restrict__ pt_key,
+                                                  const uint64_t* __restrict__ ukeys, const uint32_t n_points, uint64_t* __restrict__ seg_ends,
+                                                  uint32_t* __restrict__ parent, uint32_t* __restrict__ deg_out, uint32_t* __restrict__ deg_in)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_segs) return;
+    const uint32_t src = val_sorted[i];
+    if (src >= n_segs) {  // (the values are a permutation of 0 .. n_segs - 1)
+        seg_ends[i] = 0ull;
+        return;
+    }
+    const uint32_t p0 = sec_rank(ukeys, n_points, pt_key[2ull * src]), p1 = sec_rank(ukeys, n_points, pt_key[2ull * src + 1]);
+    seg_ends[i] = (uint64_t)p0 | ((uint64_t)p1 << 32);
+    atomicAdd(&deg_out[p0], 1u);
+    atomicAdd(&deg_in[p1], 1u);
+    comp_unite(parent, p0, p1);
+}
+
+// One lane per point: its record, and its share of its contour's record (zeroed before).  A root writes the words nobody adds to.
+// Points are in (plane, va, vb) order, so many waves hold one contour: such a wave reduces in registers first.
+__global__ __launch_bounds__(256) void k_sec_label(const uint32_t* __restrict__ root, const uint32_t* __restrict__ cbase, const uint32_t n_points,
+                                                   const uint64_t* __restrict__ ukeys, const double* __restrict__ Pd, const uint32_t* __restrict__ deg_out,
+                                                   const uint32_t* __restrict__ deg_in, SecPoint* __restrict__ pts, SecContour* __restrict__ conts)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    const bool live = j < n_points;
+    const uint32_t jj = live ? j : n_points - 1u;  // (n_points > 0) a dead lane mirrors the last point and adds nothing
+    const uint32_t r = root[jj], c = cbase[r];
+    const uint32_t n_out = deg_out[jj], n_in = deg_in[jj];
+    if (live) {
+        const uint64_t key = ukeys[j];
+        pts[j] = SecPoint{(float)Pd[3ull * j], (float)Pd[3ull * j + 1], (float)Pd[3ull * j + 2], sec_key_plane(key), sec_key_va(key), sec_key_vb(key), c,
+                          min(n_out, 65535u) | (min(n_in, 65535u) << 16)};
+        if (r == j) conts[c].plane = sec_key_plane(key), conts[c].first_point = j;
+    }
+    uint32_t n = live ? 1u : 0u, ends = (live && n_in + n_out == 1u) ? 1u : 0u;
+    uint32_t flags = !live ? 0u : ((n_in == 1u && n_out == 1u) ? 0u : kSecOpenMark) | ((n_in > 1u || n_out > 1u) ? kSecBranched : 0u);
+    const bool uniform = __all(c == __shfl(c, 0));
+    if (uniform) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            n += __shfl_down(n, o);
+            ends += __shfl_down(ends, o);
+            flags |= __shfl_down(flags, o);
+        }
+        if ((threadIdx.x & 63u) != 0) return;
+    } else if (!live) {
+        return;
+    }
+    SecContour* k = &conts[c];
+    atomicAdd(&k->n_points, n);
+    if (ends) atomicAdd(&k->n_ends, ends);
+    if (flags) atomicOr(&k->flags, flags);
+}
+
+// One lane per segment: its record, and its terms of its contour's length and area about the representative's point.
+__global__ __launch_bounds__(256) void k_sec_measure(const uint64_t* __restrict__ seg_sorted, const uint64_t* __restrict__ seg_ends, const uint32_t n_segs,
+                                                     const double* __restrict__ planes, const SecPoint* __restrict__ pts, const double* __restrict__ Pd,
+                                                     SecSegment* __restrict__ segs, SecContour* __restrict__ conts)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool live = i < n_segs;
+    const uint32_t ii = live ? i : n_segs - 1u;  // (n_segs > 0)
+    const uint64_t key = seg_sorted[ii], ends = seg_ends[ii];
+    SecSegment s{(uint32_t)ends, (uint32_t)(ends >> 32), sec_seg_tri(key), 0u};
+    const uint32_t c = pts[s.p0].contour;
+    s.contour = c;
+    if (live) segs[i] = s;
+    const double* q = planes + 4ull * sec_seg_plane(key);
+    const double* P0 = Pd + 3ull * s.p0;
+    const double* P1 = Pd + 3ull * s.p1;
+    const double* Pr = Pd + 3ull * conts[c].first_point;
+    double e[3], a[3], b[3], U[3];
+    const double root_nn = sqrt(dev_dot(q, q));
+#pragma unroll
+    for (int x = 0; x < 3; x++) e[x] = P1[x] - P0[x], a[x] = P0[x] - Pr[x], b[x] = P1[x] - Pr[x], U[x] = q[x] / root_nn;
+    const double X[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+    long long len = live ? (long long)rint(sqrt(dev_dot(e, e)) * 4294967296.0) : 0ll;
+    long long area = live ? (long long)rint((0.5 * dev_dot(U, X)) * 268435456.0) : 0ll;
+    uint32_t n = live ? 1u : 0u;
+    const bool uniform = __all(c == __shfl(c, 0));
+    if (uniform) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            n += __shfl_down(n, o);
+            len += __shfl_down(len, o);
+            area += __shfl_down(area, o);
+        }
+        if ((threadIdx.x & 63u) != 0) return;
+    } else if (!live) {
+        return;
+    }
+    SecContour* k = &conts[c];
+    atomicAdd(&k->n_segments, n);
+    atomicAdd((unsigned long long*)&k->length_q32, (unsigned long long)len);
+    atomicAdd((unsigned long long*)&k->area_q28, (unsigned long long)area);
+}
+
+// One lane per contour: its final flags, and its share of its plane's record (zeroed before).
+__global__ __launch_bounds__(256) void k_sec_finish(const uint32_t n_conts, SecContour* __restrict__ conts, SecPlane* __restrict__ recs,
+                                                    unsigned long long* __restrict__ n_closed)
+{
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= n_conts) return;
+    const SecContour k = conts[c];
+    const bool closed = (k.flags & kSecOpenMark) == 0u, branched = (k.flags & kSecBranched) != 0u;
+    conts[c].flags = (closed ? kSecClosed : 0u) | (branched ? kSecBranched : 0u);
+    SecPlane* r = &recs[k.plane];
+    atomicAdd(&r->n_segments, k.n_segments);
+    atomicAdd(&r->n_points, k.n_points);
+    atomicAdd(&r->n_contours, 1u);
+    if (branched) atomicAdd(&r->n_branched, 1u);
+    atomicAdd((unsigned long long*)&r->length_q32, (unsigned long long)k.length_q32);
+    if (closed) {
+        atomicAdd(&r->n_closed, 1u);
+        atomicAdd((unsigned long long*)&r->area_q28, (unsigned long long)k.area_q28);
+        atomicAdd(n_closed, 1ull);
+    }
+}
+
 }  // namespace hfpf

@@ -2,7 +2,10 @@
 // synthetic sensor -> ~start -> N x PointCloud2 callbacks with tf poses -> periodic clean -> ~process ->
 // <dir>/test_cloud.pcd + <dir>/meta.csv.  Prints per-stage wall times.
 //
-//   hfpf_demo [--min-component N [--hide-filtered]] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]] [--plan poses.txt]] <out_dir> [frames=30] [W=640] [H=480] [resolution=0.001] [clean_every=10] [seed=0xF051] [pose_seed=0x5E3]
+//   hfpf_demo [--section planes.txt] [--min-component N [--hide-filtered]] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]] [--plan poses.txt]] <out_dir> [frames=30] [W=640] [H=480] [resolution=0.001] [clean_every=10] [seed=0xF051] [pose_seed=0x5E3]
+// --section planes.txt: ~process also writes mesh.ply (hfpf_node_set_mesh_output: a window of 2 voxels) and cuts that mesh with the
+//   planes in planes.txt (four numbers per plane, n.x n.y n.z d in the fusion frame, separated by white space;
+//   hfpf_node_set_section_planes): sections.csv and section_summary.csv, and the demo prints every plane's contours, length and area.
 // --min-component N: ~process saves only the connected components (26-neighbourhood) of at least N rows (hfpf_node_set_component_filter).
 //   --hide-filtered: the rows the filter drops are hidden on the device (hfpf_node_set_hide_filtered), so that the reports of --reference
 //   see the cleaned model too, not only test_cloud.pcd and meta.csv.
@@ -19,6 +22,7 @@
 //   yet scanned (hfpf_node_set_view_candidates: the coverage settings above, a 640 x 480 sensor of 525 px focal length between 0.3 and
 //   3 m, up to 8 views), and the demo prints the selected views in rank order.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -61,6 +65,7 @@ int main(int argc, char** argv)
     bool align = false, coverage = false, hide_filtered = false;
     double spacing = 0.0;
     const char* plan = nullptr;
+    const char* section = nullptr;
     while (argc > 2 && strncmp(argv[1], "--", 2) == 0) {
         if (strcmp(argv[1], "--align") == 0) {
             align = true;
@@ -85,11 +90,12 @@ int main(int argc, char** argv)
         else if (strcmp(argv[1], "--reference") == 0) reference = argv[2];
         else if (strcmp(argv[1], "--max-deviation") == 0) max_deviation = atof(argv[2]);
         else if (strcmp(argv[1], "--plan") == 0) plan = argv[2];
+        else if (strcmp(argv[1], "--section") == 0) section = argv[2];
         else break;
         argv += 2, argc -= 2;
     }
     if (argc < 2 || strncmp(argv[1], "--", 2) == 0) {
-        fprintf(stderr, "usage: hfpf_demo [--min-component N [--hide-filtered]] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]] [--plan poses.txt]] <out_dir> [frames] [W] [H] [resolution] [clean_every] [seed] [pose_seed]\n");
+        fprintf(stderr, "usage: hfpf_demo [--section planes.txt] [--min-component N [--hide-filtered]] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]] [--plan poses.txt]] <out_dir> [frames] [W] [H] [resolution] [clean_every] [seed] [pose_seed]\n");
         return 2;
     }
     const std::string dir = argv[1];
@@ -115,6 +121,28 @@ int main(int argc, char** argv)
     if (hfpf_node_create(&p, lookup, &tf, &node) != HFPF_OK) {
         fprintf(stderr, "create: %s\n", hfpf_node_last_error(nullptr));
         return 1;
+    }
+    if (section) {
+        std::vector<double> planes;
+        FILE* f = fopen(section, "r");
+        double v;
+        while (f && fscanf(f, "%lf", &v) == 1) planes.push_back(v);
+        if (f) fclose(f);
+        if (!f || planes.empty() || planes.size() % 4) {
+            fprintf(stderr, "section: %s does not hold 4 numbers per plane\n", section);
+            return 1;
+        }
+        hfpf_mesh_opts mo;
+        memset(&mo, 0, sizeof mo);
+        mo.struct_size = sizeof mo;
+        mo.radius = 2, mo.max_distance = HUGE_VAL;
+        hfpf_section_opts so;
+        memset(&so, 0, sizeof so);
+        so.struct_size = sizeof so;
+        if (hfpf_node_set_mesh_output(node, &mo) != HFPF_OK || hfpf_node_set_section_planes(node, &so, planes.data(), (uint32_t)(planes.size() / 4)) != HFPF_OK) {
+            fprintf(stderr, "section: %s\n", hfpf_node_last_error(node));
+            return 1;
+        }
     }
     if (min_component) {
         hfpf_component_opts co;
@@ -231,6 +259,19 @@ int main(int argc, char** argv)
     hfpf_node_get_stats(node, &st);
     printf("%s\nframes %llu integrated %llu  callbacks %.3f s  cleans %.3f s (%llu passes)  process %.3f s\n", r.message,
            (unsigned long long)st.received, (unsigned long long)st.integrated, t_cb, t_clean, (unsigned long long)st.clean_passes, t_proc);
+    if (section) {  // section_summary.csv: one line per plane
+        FILE* f = fopen((dir + "/section_summary.csv").c_str(), "r");
+        if (!f || fscanf(f, "%*[^\n]\n") != 0) {
+            fprintf(stderr, "section_summary.csv: cannot read it back\n");
+            return 1;
+        }
+        unsigned v[9];
+        long long len, area;
+        while (fscanf(f, "%u,%u,%u,%u,%u,%u,%u,%u,%u,%lld,%lld\n", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8], &len, &area) == 11)
+            printf("section: plane %u: %u segments in %u contours (%u closed, %u branched), length %.6f m, closed area %.6f m^2\n", v[0], v[2], v[6], v[7], v[8],
+                   (double)len * 0x1p-32, (double)area * 0x1p-28);
+        fclose(f);
+    }
     if (reference && coverage) {  // the value line of coverage_summary.csv
         unsigned long long v[11] = {0};
         FILE* f = fopen((dir + "/coverage_summary.csv").c_str(), "r");

@@ -57,6 +57,9 @@ struct hfpf_node {
     hfpf_depth_image cons_desc{};       // descriptor of the images in the ring
     std::vector<std::vector<uint8_t>> cons_frames;  // host copies of the last integrated depth images, oldest first
     std::vector<double> cons_poses;     // 12 per image
+    bool sec_on = false;                // hfpf_node_set_section_planes: ~process also writes sections.csv and section_summary.csv
+    hfpf_section_opts sec_opts{};
+    std::vector<double> sec_planes;     // 4 per plane
     void* publish_user = nullptr;
     std::thread clean_thread;
     std::mutex cv_mtx;
@@ -499,10 +502,59 @@ static int write_consistency(hfpf_node* n, const hfpf_row* saved, uint64_t n_sav
     return rc;
 }
 
+// sections.csv and section_summary.csv beside mesh.ply: hfpf_section_mesh of the mesh that file holds (identity pose) with the node's
+// planes; one line per segment, then one line per plane.
+static int write_sections(hfpf_node* n, const hfpf_mesh_vertex* mv, uint64_t nmv, const uint32_t* mt, uint64_t nmt)
+{
+    const double ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    const uint32_t n_planes = (uint32_t)(n->sec_planes.size() / 4);
+    hfpf_section_point* pts = nullptr;
+    hfpf_section_segment* segs = nullptr;
+    hfpf_section_contour* conts = nullptr;
+    uint64_t np = 0, ns = 0, nc = 0;
+    std::vector<hfpf_section_plane> recs(n_planes);
+    hfpf_section_summary s;
+    int rc = hfpf_section_mesh(n->grid, &n->sec_opts, mv, nmv, sizeof(hfpf_mesh_vertex), mt, nmt, ident, n->sec_planes.data(), n_planes, &pts, &np, &segs, &ns,
+                               &conts, &nc, recs.data(), &s);
+    if (rc != HFPF_OK) return rc;
+    FILE* f = fopen((n->directory_name + "/sections.csv").c_str(), "w");
+    if (!f) rc = HFPF_ERR_IO;
+    else {
+        fprintf(f, "plane,contour,tri,x0,y0,z0,x1,y1,z1\n");
+        for (uint64_t i = 0; i < ns; i++) {
+            const hfpf_section_point &a = pts[segs[i].p0], &b = pts[segs[i].p1];
+            fprintf(f, "%u,%u,%u,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g\n", a.plane, segs[i].contour, segs[i].tri, a.x, a.y, a.z, b.x, b.y, b.z);
+        }
+        const bool ok = !ferror(f);
+        if (fclose(f) != 0 || !ok) rc = HFPF_ERR_IO;
+    }
+    if (rc == HFPF_OK) {
+        f = fopen((n->directory_name + "/section_summary.csv").c_str(), "w");
+        if (!f) rc = HFPF_ERR_IO;
+        else {
+            fprintf(f, "plane,first_segment,n_segments,first_point,n_points,first_contour,n_contours,n_closed,n_branched,length_q32,area_q28\n");
+            for (uint32_t j = 0; j < n_planes; j++) {
+                const hfpf_section_plane& r = recs[j];
+                fprintf(f, "%u,%u,%u,%u,%u,%u,%u,%u,%u,%lld,%lld\n", j, r.first_segment, r.n_segments, r.first_point, r.n_points, r.first_contour, r.n_contours,
+                        r.n_closed, r.n_branched, (long long)r.length_q32, (long long)r.area_q28);
+            }
+            const bool ok = !ferror(f);
+            if (fclose(f) != 0 || !ok) rc = HFPF_ERR_IO;
+        }
+    }
+    hfpf_free_section(pts, segs, conts);
+    return rc;
+}
+
 int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
 {
     if (!n) return HFPF_ERR_BAD_ARG;
     n->process_calls++;
+    if (n->sec_on && !n->mesh_on) {  // EXTENSION: the sections cut the mesh of mesh.ply; nothing is written and the grid is kept
+        const std::string m = "section planes are set but mesh output is not (hfpf_node_set_mesh_output)";
+        set_res(res, false, m);
+        return nfail(n, HFPF_ERR_STATE, m);
+    }
     // The reference polls until both queues are empty (node.cpp:380-394); integrate calls are already in stream order here.
     if (n->final_clean && hfpf_is_dirty(n->grid) > 0) {
         int rc = hfpf_clean(n->grid);
@@ -558,6 +610,7 @@ int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
         uint64_t nmv = 0, nmt = 0;
         rc = hfpf_extract_mesh(n->grid, &n->mesh_opts, &mv, &nmv, &mt, &nmt);
         if (rc == HFPF_OK) rc = hfpf_write_ply(mv, nmv, mt, nmt, (n->directory_name + "/mesh.ply").c_str());
+        if (rc == HFPF_OK && n->sec_on) rc = write_sections(n, mv, nmv, mt, nmt);  // EXTENSION: ... and its profiles in the node's planes
         hfpf_free_mesh(mv, mt);
     }
     if (rc == HFPF_OK && n->write_variants) {  // the reference's `#if 0` block, node.cpp:399-437
@@ -624,6 +677,26 @@ int hfpf_node_set_mesh_output(hfpf_node* n, const hfpf_mesh_opts* opts)
         n->mesh_opts = *opts;
     }
     n->mesh_on = opts != nullptr;
+    return HFPF_OK;
+}
+
+int hfpf_node_set_section_planes(hfpf_node* n, const hfpf_section_opts* opts, const double* planes, uint32_t n_planes)
+{
+    if (!n) return HFPF_ERR_BAD_ARG;
+    if (opts) {
+        bool ok = hfpf_check_section_opts(opts) == HFPF_OK && n_planes <= HFPF_SECTION_MAX_PLANES && (planes || !n_planes);
+        for (uint32_t j = 0; ok && j < n_planes; j++) {
+            const double* p = planes + 4ull * j;
+            const double nn = (p[0] * p[0] + p[1] * p[1]) + p[2] * p[2];
+            ok = std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]) && std::isfinite(p[3]) && std::isfinite(nn) && nn > 0.0;
+        }
+        if (!ok) return nfail(n, HFPF_ERR_BAD_ARG, "hfpf_node_set_section_planes: invalid hfpf_section_opts, more than 4096 planes, or a plane that is not finite");
+        n->sec_opts = *opts;
+        n->sec_planes.assign(planes, planes + 4ull * n_planes);
+    } else {
+        n->sec_planes.clear();
+    }
+    n->sec_on = opts != nullptr;
     return HFPF_OK;
 }
 

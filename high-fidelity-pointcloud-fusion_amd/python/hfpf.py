@@ -97,6 +97,7 @@ EXPORTS = [
     "hfpf_check_align_opts", "hfpf_align_mesh", "hfpf_align_mesh_device",
     "hfpf_check_cover_opts", "hfpf_cover_mesh", "hfpf_cover_mesh_device", "hfpf_free_coverage",
     "hfpf_check_plan_opts", "hfpf_plan_views", "hfpf_plan_views_device", "hfpf_free_plan",
+    "hfpf_check_section_opts", "hfpf_section_mesh", "hfpf_section_mesh_device", "hfpf_free_section",
     "hfpf_check_consistency_opts", "hfpf_depth_consistency", "hfpf_depth_consistency_device", "hfpf_free_consistency",
     "hfpf_check_hide_opts", "hfpf_hide_voxels", "hfpf_hide_voxels_device", "hfpf_hide_box", "hfpf_show_all", "hfpf_get_hidden",
     "hfpf_check_raycast_opts", "hfpf_raycast", "hfpf_raycast_device", "hfpf_raycast_view", "hfpf_raycast_view_device",
@@ -421,6 +422,47 @@ def cover_opts(radius=2, min_count=0.0, max_distance=0.01, spacing=0.005, max_su
 def check_cover_opts(o):
     """hfpf_check_cover_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
     return lib().hfpf_check_cover_opts(C.byref(o) if o is not None else None)
+
+
+# hfpf_section_contour.flags and the section records (include/hfpf.h)
+SECTION_CLOSED, SECTION_BRANCHED = 1, 2
+SECTION_MAX_PLANES, SECTION_MAX_PLANE_SEGMENTS = 4096, 1 << 20
+SECTION_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("plane", "<u4"), ("va", "<u4"), ("vb", "<u4"), ("contour", "<u4"),
+                                ("ends", "<u4")])
+SECTION_SEGMENT_DTYPE = np.dtype([("p0", "<u4"), ("p1", "<u4"), ("tri", "<u4"), ("contour", "<u4")])
+SECTION_CONTOUR_DTYPE = np.dtype([("plane", "<u4"), ("first_point", "<u4"), ("n_points", "<u4"), ("n_segments", "<u4"), ("n_ends", "<u4"),
+                                  ("flags", "<u4"), ("length_q32", "<i8"), ("area_q28", "<i8"), ("reserved", "<u8")])
+SECTION_PLANE_DTYPE = np.dtype([("first_segment", "<u4"), ("n_segments", "<u4"), ("first_point", "<u4"), ("n_points", "<u4"),
+                                ("first_contour", "<u4"), ("n_contours", "<u4"), ("n_closed", "<u4"), ("n_branched", "<u4"),
+                                ("length_q32", "<i8"), ("area_q28", "<i8"), ("reserved", "<u8", (2,))])
+assert (SECTION_POINT_DTYPE.itemsize, SECTION_SEGMENT_DTYPE.itemsize, SECTION_CONTOUR_DTYPE.itemsize, SECTION_PLANE_DTYPE.itemsize) == (32, 16, 48, 64)
+
+
+class SectionOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class SectionSummary(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_tris_valid", "n_tris_invalid", "n_tris_far", "n_segments", "n_points", "n_contours", "n_closed",
+                                          "reserved")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+assert C.sizeof(SectionOpts) == 16 and C.sizeof(SectionSummary) == 64
+
+
+def section_opts():
+    """An hfpf_section_opts (it has no settings yet)."""
+    o = SectionOpts()
+    o.struct_size = C.sizeof(SectionOpts)
+    return o
+
+
+def check_section_opts(o):
+    """hfpf_check_section_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
+    return lib().hfpf_check_section_opts(C.byref(o) if o is not None else None)
 
 
 # hfpf_plan_opts.flags, hfpf_view_score and hfpf_tri_plan (include/hfpf.h)
@@ -804,6 +846,12 @@ def lib():
         fn.argtypes = [vp, C.POINTER(PlanOpts), vp, u64, u32, vp, u64, vp, vp, u32, vp, C.POINTER(vp), C.POINTER(PlanSummary)]
     L.hfpf_free_plan.argtypes = [vp]
     L.hfpf_free_plan.restype = None
+    L.hfpf_check_section_opts.argtypes = [C.POINTER(SectionOpts)]
+    for fn in (L.hfpf_section_mesh, L.hfpf_section_mesh_device):
+        fn.argtypes = [vp, C.POINTER(SectionOpts), vp, u64, u32, vp, u64, vp, vp, u32, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64),
+                       C.POINTER(vp), C.POINTER(u64), vp, C.POINTER(SectionSummary)]
+    L.hfpf_free_section.argtypes = [vp, vp, vp]
+    L.hfpf_free_section.restype = None
     L.hfpf_free_deviation.argtypes = [vp, vp]
     L.hfpf_free_deviation.restype = None
     L.hfpf_check_consistency_opts.argtypes = [C.POINTER(ConsistencyOpts)]
@@ -1285,6 +1333,48 @@ class OccupancyGrid:
         finally:
             lib().hfpf_free_coverage(c)
         return cov, s.as_dict()
+
+    # -- planar sections of a triangle mesh --
+    def section_mesh(self, verts, tris, pose=None, planes=(), device=False, opts=None, n_verts=None, vertex_stride=None, n_tris=None):
+        """Cut a triangle mesh with planes (hfpf_section_mesh): (points of SECTION_POINT_DTYPE, segments of SECTION_SEGMENT_DTYPE,
+        contours of SECTION_CONTOUR_DTYPE, one record of SECTION_PLANE_DTYPE per plane, summary dict).  planes: (n, 4) float64 rows
+        (n.x, n.y, n.z, d) in the fusion frame; verts, tris, pose and the device form's arguments as compare_mesh().  device=True runs
+        hfpf_section_mesh_device and returns the three arrays as (pointer, count) pairs in HBM: free the pointers with device_free
+        (they are 0 without segments).  section_mesh_device() is that form by name."""
+        o = opts if opts is not None else section_opts()
+        pose = np.ascontiguousarray(np.eye(4)[:3] if pose is None else pose, np.float64).reshape(12)
+        planes = np.ascontiguousarray(planes, np.float64).reshape(-1, 4)
+        recs = np.zeros(len(planes), SECTION_PLANE_DTYPE)
+        pp, rp = (_p(planes), _p(recs)) if len(planes) else (None, None)
+        p, s, c, npt, ns, nc, summ = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_uint64(), SectionSummary()
+        outs = (C.byref(p), C.byref(npt), C.byref(s), C.byref(ns), C.byref(c), C.byref(nc), rp, C.byref(summ))
+        if device:
+            self._chk(lib().hfpf_section_mesh_device(self._h, C.byref(o), C.c_void_p(verts), int(n_verts), int(vertex_stride), C.c_void_p(tris),
+                                                     int(n_tris), _p(pose), pp, len(planes), *outs))
+            return (p.value or 0, npt.value), (s.value or 0, ns.value), (c.value or 0, nc.value), recs, summ.as_dict()
+        verts = np.ascontiguousarray(verts)
+        if verts.dtype != MESH_VERTEX_DTYPE:
+            verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+        stride = int(vertex_stride) if vertex_stride is not None else verts.dtype.itemsize * (1 if verts.dtype == MESH_VERTEX_DTYPE else 3)
+        nv = int(n_verts) if n_verts is not None else len(verts)
+        nt = int(n_tris) if n_tris is not None else len(tris)
+        self._chk(lib().hfpf_section_mesh(self._h, C.byref(o), _p(verts) if verts.nbytes else None, nv, stride, _p(tris) if tris.nbytes else None, nt,
+                                          _p(pose), pp, len(planes), *outs))
+        try:
+            points = np.empty(npt.value, SECTION_POINT_DTYPE)
+            segments = np.empty(ns.value, SECTION_SEGMENT_DTYPE)
+            contours = np.empty(nc.value, SECTION_CONTOUR_DTYPE)
+            for a, q in ((points, p), (segments, s), (contours, c)):
+                if a.nbytes:
+                    C.memmove(a.ctypes.data, q.value, a.nbytes)
+        finally:
+            lib().hfpf_free_section(p, s, c)
+        return points, segments, contours, recs, summ.as_dict()
+
+    def section_mesh_device(self, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose=None, planes=(), opts=None):
+        """hfpf_section_mesh_device on a mesh in HBM (as extract_mesh_device leaves it): section_mesh(device=True)."""
+        return self.section_mesh(dev_verts, dev_tris, pose, planes, device=True, opts=opts, n_verts=n_verts, vertex_stride=vertex_stride, n_tris=n_tris)
 
     # -- planning the next views against a reference mesh --
     def plan_views(self, verts, tris, poses, pose=None, device=False, opts=None, tri_plan=True, n_verts=None, vertex_stride=None, n_tris=None, **kw):

@@ -1178,6 +1178,150 @@ int hfpf_plan_views_device(hfpf_handle* h, const hfpf_plan_opts* o, const void* 
                            const uint32_t* dev_tris, uint64_t n_tris, const double* pose_3x4, const double* poses, uint32_t n_views,
                            hfpf_view_score* scores, hfpf_tri_plan** dev_plan, hfpf_plan_summary* summary);
 
+/* ---- planar sections of a triangle mesh: contours, lengths and areas (no reference counterpart) -------------------------------------
+ * The read-outs above measure the model against a reference mesh; a section measures geometry on its own terms: the profile of a
+ * mesh in a given plane, its length, the area it encloses, whether it is closed.  The mesh is any mesh -- a CAD model, or the
+ * model's own (hfpf_extract_mesh_device leaves it in HBM, and the device form cuts it there).  Every output is an integer
+ * reduction, a sort rank or a union-find label: nothing depends on scheduling.  Everything is restatable from the arguments alone
+ * (tests/section_ref.py); the fused model plays no part.
+ * Arithmetic: everything below is f64, one rounding per operation, left to right, never contracted.
+ *   dot(u, v) = (u.x*v.x + u.y*v.y) + u.z*v.z; cross(u, v) = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x), written
+ *   out as N is in the deviation section; vector sums and differences per component.
+ * Mesh, pose, valid triangles: word for word those of the section "deviation of the fused model from a triangle mesh": verts,
+ *   n_verts, vertex_stride, tris, n_tris, pose_3x4 from the mesh frame to the fusion frame; V kept in f64; triangle k is VALID iff
+ *   its three indices are < n_verts, its nine transformed coordinates are finite and NN = dot(N, N) is finite and > 0.  The device
+ *   rejects an index out of range before it loads anything through it.  A valid triangle is IN RANGE iff each of its nine
+ *   coordinates has |V[a] - c[a]| < 32 (metres: track's headroom rule), c[a] = (bbox_min[a] + bbox_max[a]) * 0.5 the centre
+ *   hfpf_align_mesh uses.  Invalid triangles and valid triangles that are not in range (FAR) are skipped and counted:
+ *   n_tris_invalid, n_tris_far; n_tris_valid counts the valid ones, far or not.
+ * Planes: n_planes * 4 f64 in HOST memory, (n.x, n.y, n.z, d) per plane, in the fusion frame; n need not be a unit vector.  For
+ *   vertex i and plane j: s = dot(n, V_i) - d.  The vertex is INSIDE iff s < 0 (the rule of the mesh and of raycast).  There is no
+ *   "on the plane" case: s == 0 is outside.
+ * Crossing: an in-range triangle crosses plane j iff its three vertices are not all inside and not all outside.  Exactly one
+ *   vertex L (position 0, 1 or 2 in the triangle) then differs from the other two; with next(L) and prev(L) the positions after
+ *   and before it in the triangle's cyclic index order, the crossing lies on the edges (L, next(L)) and (prev(L), L).
+ * Points: a point is identified by (plane, va, vb), va < vb the vertex indices of the edge (a crossing edge has two distinct
+ *   indices: its ends lie on different sides).  t = s_va / (s_va - s_vb); P[a] = V_va[a] + t * (V_vb[a] - V_va[a]): always from the
+ *   lower index to the higher, so the triangles that share an edge share the point bit for bit.  The points are numbered 0.. in
+ *   ascending (plane, va, vb) order.  Welding follows the mesh's indices: two vertices with equal coordinates but different indices
+ *   are NOT merged (a triangle soup gives one open contour per segment).  n_verts <= 2^26, so that (plane: 12 bits | va: 26 | vb:
+ *   26) is one 64-bit sort key.
+ * Segments: one per (crossing triangle, plane), in ascending (plane, triangle) order.  If L is INSIDE the segment runs from the
+ *   point on (prev(L), L) to the point on (L, next(L)); if L is outside, the other way.  That is the direction of cross(n, N), N
+ *   the triangle's winding normal: the section of a closed, outward-wound mesh runs counter-clockwise seen from the side n points
+ *   to, and its area below is positive.  A plane through vertices gives zero-length segments; they are kept, there is no special
+ *   case.
+ * Contours: the connected components of the points under "joined by a segment".  A contour's representative is its smallest
+ *   point; contours are numbered by ascending representative, which groups them by plane.  Per point n_out counts the segments that
+ *   start there and n_in those that end there, each saturated at 65535.  A contour is CLOSED iff every point of it has n_in == 1
+ *   and n_out == 1; BRANCHED iff some point of it has n_in > 1 or n_out > 1 (a non-manifold edge, or inconsistent winding);
+ *   n_ends = its points with n_in + n_out == 1.
+ * Length and area: order-free fixed-point sums over the contour's segments, P0 and P1 the f64 points of p0 and p1:
+ *     e = P1 - P0;                       length_q32 += (int64)rint(sqrt(dot(e, e)) * 2^32)
+ *     a = P0 - Pr; b = P1 - Pr;          area_q28   += (int64)rint((0.5 * dot(U, cross(a, b))) * 2^28)
+ *   with nn = dot(n, n), U[a] = n[a] / sqrt(nn) and Pr the representative's f64 point.  The area is meaningful for a closed contour
+ *   and reported for all; its sign is only as good as the mesh's winding.  Headroom: in-range coordinates keep a segment below 2^7 m
+ *   and an area term below 2^13 m^2, so the at most 2^20 segments a plane may have keep either sum below 2^62.
+ * Records: hfpf_section_point (x, y, z = (float)P per axis; ends = n_out | n_in << 16), hfpf_section_segment, hfpf_section_contour
+ *   (first_point = the representative), one hfpf_section_plane per plane (first_segment, first_point and first_contour are the
+ *   totals of the planes before it, also for a plane that has none; length_q32 over all its contours, area_q28 over its CLOSED
+ *   contours only) and one hfpf_section_summary.  Reserved words are 0.
+ * A call needs no fused model (an empty handle works) and changes nothing on the handle except device_bytes (its scratch); it
+ * returns when its outputs are complete.  Rejected with HFPF_ERR_BAD_ARG (the handle stays usable, nothing is written), all of it
+ * before anything is read through a mesh pointer: what hfpf_check_section_opts rejects (struct_size != sizeof, flags or reserved != 0);
+ * every check hfpf_compare_mesh makes on the mesh and the pose; n_verts > 2^26; n_planes > 4096; NULL planes with n_planes > 0; a
+ * plane with a non-finite value or with nn not finite or not > 0; a NULL output pointer (points, n_points, segments, n_segments,
+ * contours, n_contours, summary; plane_recs with n_planes > 0); for the device form verts or tris not 4-byte aligned.  n_planes = 0
+ * or n_tris = 0 returns HFPF_OK with NULL arrays, zeroed plane records and the triangle counts.  A plane with more than 2^20
+ * segments, or more than 2^31 - 1 segments in all, returns HFPF_ERR_CAPACITY; the message names the plane and its count (or the
+ * total), nothing is written, and the handle stays usable.  A handle with an RCCL communicator, or a failed handle, returns
+ * HFPF_ERR_STATE as the other mesh readers do.
+ * LIMITATION: sections of the model's own mesh are open wherever the scan is: the CLOSED flags then say where the scan has holes. */
+#define HFPF_SECTION_CLOSED 1u   /* hfpf_section_contour.flags: every point has n_in == 1 and n_out == 1 */
+#define HFPF_SECTION_BRANCHED 2u /* some point has n_in > 1 or n_out > 1 */
+#define HFPF_SECTION_MAX_PLANES 4096u
+#define HFPF_SECTION_MAX_PLANE_SEGMENTS (1u << 20)
+
+typedef struct hfpf_section_opts {
+    uint32_t struct_size;        /* = sizeof(hfpf_section_opts) */
+    uint32_t flags;              /* 0 */
+    uint64_t reserved;           /* 0 */
+} hfpf_section_opts;
+
+typedef struct hfpf_section_point { /* 32 bytes */
+    float x, y, z;               /* (float)P */
+    uint32_t plane;
+    uint32_t va, vb;             /* the edge's vertex indices, va < vb */
+    uint32_t contour;
+    uint32_t ends;               /* n_out | n_in << 16 */
+} hfpf_section_point;
+
+typedef struct hfpf_section_segment { /* 16 bytes */
+    uint32_t p0, p1;             /* from point p0 to point p1 */
+    uint32_t tri;
+    uint32_t contour;
+} hfpf_section_segment;
+
+typedef struct hfpf_section_contour { /* 48 bytes */
+    uint32_t plane;
+    uint32_t first_point;        /* the representative */
+    uint32_t n_points, n_segments, n_ends;
+    uint32_t flags;              /* HFPF_SECTION_* */
+    int64_t length_q32;          /* / 2^32 m */
+    int64_t area_q28;            /* / 2^28 m^2 */
+    uint64_t reserved;           /* 0 */
+} hfpf_section_contour;
+
+typedef struct hfpf_section_plane { /* 64 bytes, one per plane */
+    uint32_t first_segment, n_segments;
+    uint32_t first_point, n_points;
+    uint32_t first_contour, n_contours;
+    uint32_t n_closed, n_branched;
+    int64_t length_q32;          /* over all its contours */
+    int64_t area_q28;            /* over its closed contours */
+    uint64_t reserved[2];        /* 0 */
+} hfpf_section_plane;
+
+typedef struct hfpf_section_summary { /* 64 bytes */
+    uint64_t n_tris_valid, n_tris_invalid, n_tris_far;
+    uint64_t n_segments, n_points, n_contours, n_closed;
+    uint64_t reserved;           /* 0 */
+} hfpf_section_summary;
+
+#ifdef __cplusplus
+static_assert(sizeof(hfpf_section_opts) == 16, "hfpf_section_opts is 16 bytes");
+static_assert(sizeof(hfpf_section_point) == 32, "hfpf_section_point is 32 bytes");
+static_assert(sizeof(hfpf_section_segment) == 16, "hfpf_section_segment is 16 bytes");
+static_assert(sizeof(hfpf_section_contour) == 48, "hfpf_section_contour is 48 bytes");
+static_assert(sizeof(hfpf_section_plane) == 64, "hfpf_section_plane is 64 bytes");
+static_assert(sizeof(hfpf_section_summary) == 64, "hfpf_section_summary is 64 bytes");
+#else
+_Static_assert(sizeof(hfpf_section_opts) == 16, "hfpf_section_opts is 16 bytes");
+_Static_assert(sizeof(hfpf_section_point) == 32, "hfpf_section_point is 32 bytes");
+_Static_assert(sizeof(hfpf_section_segment) == 16, "hfpf_section_segment is 16 bytes");
+_Static_assert(sizeof(hfpf_section_contour) == 48, "hfpf_section_contour is 48 bytes");
+_Static_assert(sizeof(hfpf_section_plane) == 64, "hfpf_section_plane is 64 bytes");
+_Static_assert(sizeof(hfpf_section_summary) == 64, "hfpf_section_summary is 64 bytes");
+#endif
+
+/* HFPF_OK if o passes the checks above, else HFPF_ERR_BAD_ARG (host code, no handle; the node shell uses it too). */
+int hfpf_check_section_opts(const hfpf_section_opts* o);
+/* Mesh, pose, planes and outputs in HOST memory (the mesh is uploaded once per call, as hfpf_compare_mesh uploads it): *points,
+ * *segments and *contours hold *n_points, *n_segments and *n_contours records and are freed by hfpf_free_section; plane_recs is the
+ * caller's array of n_planes records. */
+int hfpf_section_mesh(hfpf_handle* h, const hfpf_section_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris,
+                      uint64_t n_tris, const double* pose_3x4, const double* planes, uint32_t n_planes, hfpf_section_point** points, uint64_t* n_points,
+                      hfpf_section_segment** segments, uint64_t* n_segments, hfpf_section_contour** contours, uint64_t* n_contours,
+                      hfpf_section_plane* plane_recs, hfpf_section_summary* summary);
+void hfpf_free_section(hfpf_section_point* points, hfpf_section_segment* segments, hfpf_section_contour* contours);
+/* The mesh is read in place from DEVICE memory (HBM); *dev_points, *dev_segments and *dev_contours are device arrays, each freed by
+ * hfpf_device_free(h, p).  pose_3x4, planes, plane_recs and summary are in host memory. */
+int hfpf_section_mesh_device(hfpf_handle* h, const hfpf_section_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride,
+                             const uint32_t* dev_tris, uint64_t n_tris, const double* pose_3x4, const double* planes, uint32_t n_planes,
+                             hfpf_section_point** dev_points, uint64_t* n_points, hfpf_section_segment** dev_segments, uint64_t* n_segments,
+                             hfpf_section_contour** dev_contours, uint64_t* n_contours, hfpf_section_plane* plane_recs,
+                             hfpf_section_summary* summary);
+
 /* ---- rows that later depth frames see through (the inverse of hfpf_render; no reference counterpart) ----------------------------
  * An occupancy grid keeps a voxel that was occupied once: a hand that crossed the view, a part that was moved, a slab of flying
  * pixels that passed the gate.  min_count cannot drop them when they were seen for many frames, hfpf_extract_components cannot when

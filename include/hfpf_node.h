@@ -93,6 +93,18 @@ int hfpf_node_set_publisher(hfpf_node* n, hfpf_publish_fn fn, void* user);
  * refused with HFPF_ERR_BAD_ARG and leave the setting as it was.  (hfpf_node_params keeps its size: it is part of the ABI.) */
 int hfpf_node_set_mesh_output(hfpf_node* n, const hfpf_mesh_opts* opts);
 
+/* EXTENSION: profiles of the saved mesh.  With section planes set and mesh output set, ~process also cuts the mesh it writes to
+ * mesh.ply (hfpf_section_mesh of include/hfpf.h: that mesh, identity pose, these planes) and writes, beside it, sections.csv (header
+ * plane,contour,tri,x0,y0,z0,x1,y1,z1, then one line per segment in (plane, triangle) order: its plane, contour and triangle and the
+ * x, y, z of its two points p0 and p1, floats as %.9g) and section_summary.csv (header plane,first_segment,n_segments,first_point,
+ * n_points,first_contour,n_contours,n_closed,n_branched,length_q32,area_q28, then one line per plane with its hfpf_section_plane).
+ * planes holds n_planes * 4 f64 (n.x, n.y, n.z, d) in the fusion frame; the node keeps a copy.  With section planes set and mesh
+ * output NOT set, ~process returns HFPF_ERR_STATE with success=false before it writes anything, and keeps the grid: set the mesh
+ * output (or drop the planes) and call it again.  NULL opts turns it off again, the default: neither file is then written.  Invalid
+ * options (hfpf_check_section_opts), more than 4096 planes, NULL planes with n_planes > 0 and a plane with a non-finite value or a
+ * normal of no finite length > 0 are refused with HFPF_ERR_BAD_ARG and leave the setting as it was. */
+int hfpf_node_set_section_planes(hfpf_node* n, const hfpf_section_opts* opts, const double* planes, uint32_t n_planes);
+
 /* EXTENSION: with a component filter set, ~process saves the model without its specks: test_cloud.pcd and meta.csv (and the
  * published cloud) hold the rows hfpf_extract_components keeps with these options instead of every row.  mesh.ply and the
  * write_variants files are not filtered, unless hidden with hfpf_hide_voxels (hfpf_node_set_hide_filtered below does that for the
