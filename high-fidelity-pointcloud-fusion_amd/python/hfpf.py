@@ -32,6 +32,35 @@ class HfpfError(RuntimeError):
         self.code = code
 
 
+def _sized(cls):
+    """A structure of the C ABI with its struct_size filled in."""
+    r = cls()
+    r.struct_size = C.sizeof(cls)
+    return r
+
+
+def _or(opts, make, *a, **kw):
+    """The caller's ready `opts`, or make(*a, **kw) without one."""
+    return opts if opts is not None else make(*a, **kw)
+
+
+def _opts_checker(kind):
+    """The module-level check_<kind>_opts(o) of hfpf_check_<kind>_opts."""
+    def check(o):
+        return getattr(lib(), "hfpf_check_%s_opts" % kind)(C.byref(o) if o is not None else None)
+    check.__name__ = check.__qualname__ = "check_%s_opts" % kind
+    check.__doc__ = "hfpf_check_%s_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)." % kind
+    return check
+
+
+class _Record(C.Structure):
+    """A summary or result structure of the C ABI: as_dict() gives its fields (those DICT_FIELDS names, or all)."""
+    DICT_FIELDS = None
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in self.DICT_FIELDS or [n for n, _ in self._fields_]}
+
+
 class Config(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -119,8 +148,7 @@ class DepthImage(C.Structure):
 
 def depth_desc(width, height, depth_format, depth_step, K, color_format=COLOR_NONE, color_step=0, depth_scale=0.001):
     """An hfpf_depth_image; K = (fx, fy, cx, cy)."""
-    d = DepthImage()
-    d.struct_size = C.sizeof(DepthImage)
+    d = _sized(DepthImage)
     d.width, d.height, d.depth_format, d.depth_step = width, height, depth_format, depth_step
     d.depth_scale = depth_scale
     d.fx, d.fy, d.cx, d.cy = (float(k) for k in K)
@@ -169,8 +197,7 @@ class RenderPlanes(C.Structure):
 def render_opts(K, width, height, z_range=(0.01, 100.0), min_count=0.0, splat_radius=0, max_splat_radius=4, cull_backfaces=False,
                 world_normals=False):
     """An hfpf_render_opts; K = (fx, fy, cx, cy), splat_radius -1 = auto (capped at max_splat_radius)."""
-    o = RenderOpts()
-    o.struct_size = C.sizeof(RenderOpts)
+    o = _sized(RenderOpts)
     o.width, o.height = int(width), int(height)
     o.flags = (RENDER_CULL_BACKFACES if cull_backfaces else 0) | (RENDER_WORLD_NORMALS if world_normals else 0)
     o.fx, o.fy, o.cx, o.cy = (float(k) for k in K)
@@ -199,21 +226,13 @@ class TrackResult(C.Structure):
 def track_opts(K, width, height, max_iterations=10, stride=1, min_inliers=6, max_distance=0.02, damping=1e-6, eps_rotation=1e-6,
                eps_translation=1e-6, z_range=(0.01, 100.0), min_count=0.0, splat_radius=-1, max_splat_radius=4, cull_backfaces=True):
     """An hfpf_track_opts; the view is a render_opts of (K, width, height) with the view keywords."""
-    o = TrackOpts()
-    o.struct_size = C.sizeof(TrackOpts)
+    o = _sized(TrackOpts)
     o.max_iterations, o.stride, o.min_inliers = int(max_iterations), int(stride), int(min_inliers)
     o.view = render_opts(K, width, height, z_range=z_range, min_count=min_count, splat_radius=splat_radius,
                          max_splat_radius=max_splat_radius, cull_backfaces=cull_backfaces)
     o.max_distance, o.damping = float(max_distance), float(damping)
     o.eps_rotation, o.eps_translation = float(eps_rotation), float(eps_translation)
     return o
-
-
-def _sized(cls):
-    """A result structure of the C ABI with its struct_size filled in."""
-    r = cls()
-    r.struct_size = C.sizeof(cls)
-    return r
 
 
 def track_result():
@@ -247,8 +266,7 @@ class QueryOpts(C.Structure):
 
 def query_opts(radius=1, min_count=0.0, max_distance=float("inf"), zclip=False):
     """An hfpf_query_opts: the (2 radius + 1)^3 voxel window, the count and distance gates, HFPF_QUERY_ZCLIP."""
-    o = QueryOpts()
-    o.struct_size = C.sizeof(QueryOpts)
+    o = _sized(QueryOpts)
     o.flags = QUERY_ZCLIP if zclip else 0
     o.radius = int(radius)
     o.min_count, o.max_distance = float(min_count), float(max_distance)
@@ -268,8 +286,7 @@ assert MESH_VERTEX_DTYPE.itemsize == 32
 
 def mesh_opts(radius=2, min_count=0.0, max_distance=float("inf")):
     """An hfpf_mesh_opts: the query window of the corner samples (1..4), the count gate and the distance gate."""
-    o = MeshOpts()
-    o.struct_size = C.sizeof(MeshOpts)
+    o = _sized(MeshOpts)
     o.radius = int(radius)
     o.min_count, o.max_distance = float(min_count), float(max_distance)
     return o
@@ -290,17 +307,14 @@ assert COMPONENT_DTYPE.itemsize == 48
 def component_opts(reach=1, min_count=0.0, min_normal_dot=-2.0, min_rows=0, min_points=0, keep_largest=0):
     """An hfpf_component_opts: the neighbour reach in voxels (1..4), the count gate of the row set, the normal gate of an edge (-2 =
     off) and the three keep tests of a component (0 = off)."""
-    o = ComponentOpts()
-    o.struct_size = C.sizeof(ComponentOpts)
+    o = _sized(ComponentOpts)
     o.reach = int(reach)
     o.min_count, o.min_normal_dot = float(min_count), float(min_normal_dot)
     o.min_rows, o.keep_largest, o.min_points = int(min_rows), int(keep_largest), int(min_points)
     return o
 
 
-def check_component_opts(o):
-    """hfpf_check_component_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
-    return lib().hfpf_check_component_opts(C.byref(o) if o is not None else None)
+check_component_opts = _opts_checker("component")
 
 
 class DeviationOpts(C.Structure):
@@ -308,13 +322,10 @@ class DeviationOpts(C.Structure):
                 ("reserved", C.c_uint64)]
 
 
-class DeviationSummary(C.Structure):
+class DeviationSummary(_Record):
     _fields_ = [("n_rows", C.c_uint64), ("n_found", C.c_uint64), ("n_negative", C.c_uint64), ("n_tris_valid", C.c_uint64),
                 ("n_tris_invalid", C.c_uint64), ("max_abs", C.c_float), ("pad", C.c_uint32), ("sum_abs_q30", C.c_int64),
                 ("sum_sq_q30", C.c_int64)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 # hfpf_deviation and its flags (include/hfpf.h)
@@ -326,15 +337,12 @@ assert DEVIATION_DTYPE.itemsize == 32
 
 def deviation_opts(min_count=0.0, max_distance=0.01):
     """An hfpf_deviation_opts: the count gate of the row set and the largest distance (metres, at most 32 voxels) a winner may have."""
-    o = DeviationOpts()
-    o.struct_size = C.sizeof(DeviationOpts)
+    o = _sized(DeviationOpts)
     o.min_count, o.max_distance = float(min_count), float(max_distance)
     return o
 
 
-def check_deviation_opts(o):
-    """hfpf_check_deviation_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
-    return lib().hfpf_check_deviation_opts(C.byref(o) if o is not None else None)
+check_deviation_opts = _opts_checker("deviation")
 
 
 # hfpf_align_result.flags and hfpf_align_opts.flags (include/hfpf.h)
@@ -360,8 +368,7 @@ assert C.sizeof(AlignOpts) == 88 and C.sizeof(AlignResult) == 424
 def align_opts(max_iterations=10, stride=1, min_inliers=6, min_count=0.0, max_distance=0.01, damping=1e-6, eps_rotation=1e-6,
                eps_translation=1e-6, skip_boundary=False):
     """An hfpf_align_opts; min_count and max_distance (the capture range, at most 32 voxels) fill the embedded hfpf_deviation_opts."""
-    o = AlignOpts()
-    o.struct_size = C.sizeof(AlignOpts)
+    o = _sized(AlignOpts)
     o.flags = ALIGN_SKIP_BOUNDARY if skip_boundary else 0
     o.max_iterations, o.stride, o.min_inliers = int(max_iterations), int(stride), int(min_inliers)
     o.compare = deviation_opts(min_count, max_distance)
@@ -373,9 +380,7 @@ def align_result():
     return _sized(AlignResult)
 
 
-def check_align_opts(o):
-    """hfpf_check_align_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
-    return lib().hfpf_check_align_opts(C.byref(o) if o is not None else None)
+check_align_opts = _opts_checker("align")
 
 
 # hfpf_tri_coverage.flags, hfpf_cover_opts.flags and hfpf_tri_coverage (include/hfpf.h)
@@ -392,14 +397,14 @@ class CoverOpts(C.Structure):
                 ("reserved", C.c_uint64)]
 
 
-class CoverageSummary(C.Structure):
+class CoverageSummary(_Record):
     _fields_ = [(k, C.c_uint64) for k in ("n_tris_valid", "n_tris_invalid", "n_tris_huge", "n_samples", "n_in_bbox", "n_covered")] + [
         ("sum_dist_q30", C.c_int64), ("area_q40_lo", C.c_uint64), ("area_q40_hi", C.c_uint64), ("covered_q40_lo", C.c_uint64),
         ("covered_q40_hi", C.c_uint64), ("max_distance", C.c_float), ("pad", C.c_uint32)]
 
     def as_dict(self):
         """The fields, and the two areas in m^2 the q40 words stand for: area and covered_area."""
-        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d = super().as_dict()
         d["area"] = ((d["area_q40_hi"] << 32) + d["area_q40_lo"]) / 2.0 ** 40
         d["covered_area"] = ((d["covered_q40_hi"] << 32) + d["covered_q40_lo"]) / 2.0 ** 40
         return d
@@ -411,17 +416,14 @@ assert C.sizeof(CoverOpts) == 56 and C.sizeof(CoverageSummary) == 96
 def cover_opts(radius=2, min_count=0.0, max_distance=0.01, spacing=0.005, max_subdivision=64, min_normal_dot=-2.0, abs_normal=False):
     """An hfpf_cover_opts: the sample test's voxel window, count gate and largest distance (metres), the sample spacing (metres) and
     its cap, and the normal gate (-2 = off; abs_normal passes either orientation)."""
-    o = CoverOpts()
-    o.struct_size = C.sizeof(CoverOpts)
+    o = _sized(CoverOpts)
     o.flags = COVER_ABS_NORMAL if abs_normal else 0
     o.radius, o.max_subdivision = int(radius), int(max_subdivision)
     o.min_count, o.max_distance, o.spacing, o.min_normal_dot = float(min_count), float(max_distance), float(spacing), float(min_normal_dot)
     return o
 
 
-def check_cover_opts(o):
-    """hfpf_check_cover_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
-    return lib().hfpf_check_cover_opts(C.byref(o) if o is not None else None)
+check_cover_opts = _opts_checker("cover")
 
 
 # hfpf_section_contour.flags and the section records (include/hfpf.h)
@@ -442,12 +444,9 @@ class SectionOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
 
 
-class SectionSummary(C.Structure):
+class SectionSummary(_Record):
     _fields_ = [(k, C.c_uint64) for k in ("n_tris_valid", "n_tris_invalid", "n_tris_far", "n_segments", "n_points", "n_contours", "n_closed",
                                           "reserved")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 assert C.sizeof(SectionOpts) == 16 and C.sizeof(SectionSummary) == 64
@@ -455,14 +454,10 @@ assert C.sizeof(SectionOpts) == 16 and C.sizeof(SectionSummary) == 64
 
 def section_opts():
     """An hfpf_section_opts (it has no settings yet)."""
-    o = SectionOpts()
-    o.struct_size = C.sizeof(SectionOpts)
-    return o
+    return _sized(SectionOpts)
 
 
-def check_section_opts(o):
-    """hfpf_check_section_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
-    return lib().hfpf_check_section_opts(C.byref(o) if o is not None else None)
+check_section_opts = _opts_checker("section")
 
 
 # hfpf_plan_opts.flags, hfpf_view_score and hfpf_tri_plan (include/hfpf.h)
@@ -479,13 +474,14 @@ class PlanOpts(C.Structure):
                 ("min_gain_q40", C.c_uint64), ("max_views", C.c_uint32), ("reserved0", C.c_uint32), ("reserved", C.c_uint64)]
 
 
-class PlanSummary(C.Structure):
+class PlanSummary(_Record):
     _fields_ = [("coverage", CoverageSummary), ("n_views", C.c_uint32), ("n_selected", C.c_uint32)] + [
         (k, C.c_uint64) for k in ("n_targets", "n_reachable", "n_planned", "target_q40", "reachable_q40", "planned_q40")]
+    DICT_FIELDS = [k for k, _ in _fields_[1:]]
 
     def as_dict(self):
         """The fields (coverage as CoverageSummary.as_dict gives it)."""
-        d = {k: getattr(self, k) for k, _ in self._fields_[1:]}
+        d = super().as_dict()
         d["coverage"] = self.coverage.as_dict()
         return d
 
@@ -502,20 +498,17 @@ def plan_opts(K, width, height, cover=None, view=None, occluder_near=None, min_c
     ck = {k: kw.pop(k) for k in ("radius", "min_count", "max_distance", "spacing", "max_subdivision", "min_normal_dot", "abs_normal") if k in kw}
     if "view_min_count" in kw:  # min_count is the cover's, as in cover_opts()
         kw["min_count"] = kw.pop("view_min_count")
-    o = PlanOpts()
-    o.struct_size = C.sizeof(PlanOpts)
+    o = _sized(PlanOpts)
     o.flags = (PLAN_TWO_SIDED if two_sided else 0) | (PLAN_MODEL_OCCLUDES if model_occludes else 0)
-    o.cover = cover if cover is not None else cover_opts(**ck)
-    o.view = view if view is not None else render_opts(K, width, height, **kw)
+    o.cover = _or(cover, cover_opts, **ck)
+    o.view = _or(view, render_opts, K, width, height, **kw)
     o.occluder_near = float(o.view.z_near if occluder_near is None else occluder_near)
     o.min_cos, o.tolerance, o.slope = float(min_cos), float(tolerance), float(slope)
     o.min_gain_q40, o.max_views = int(min_gain_q40), int(max_views)
     return o
 
 
-def check_plan_opts(o):
-    """hfpf_check_plan_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
-    return lib().hfpf_check_plan_opts(C.byref(o) if o is not None else None)
+check_plan_opts = _opts_checker("plan")
 
 
 # hfpf_consistency_opts.flags, hfpf_row_consistency.flags and hfpf_row_consistency (include/hfpf.h)
@@ -533,12 +526,9 @@ class ConsistencyOpts(C.Structure):
                 ("min_cos", C.c_double), ("through_ratio", C.c_double), ("reserved", C.c_uint64)]
 
 
-class ConsistencySummary(C.Structure):
+class ConsistencySummary(_Record):
     _fields_ = [(k, C.c_uint64) for k in ("n_rows", "n_seen", "n_supported", "n_contradicted", "n_kept", "pairs_tested", "pairs_support",
                                           "pairs_through")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 assert C.sizeof(ConsistencyOpts) == 80 and C.sizeof(ConsistencySummary) == 64
@@ -548,8 +538,7 @@ def consistency_opts(window=0, min_through=1, min_count=0.0, z_range=(0.01, 100.
                      through_ratio=1.0, drop=False):
     """An hfpf_consistency_opts: the pixel window's half-width, the THROUGH frames a contradiction needs and their ratio to the SUPPORT
     frames, the count gate, the depth range, tol = tolerance + slope * zc (metres), and the facing gate (below 0 = off)."""
-    o = ConsistencyOpts()
-    o.struct_size = C.sizeof(ConsistencyOpts)
+    o = _sized(ConsistencyOpts)
     o.flags = CONSISTENCY_DROP if drop else 0
     o.window, o.min_through = int(window), int(min_through)
     o.min_count, o.z_near, o.z_far = float(min_count), float(z_range[0]), float(z_range[1])
@@ -557,9 +546,7 @@ def consistency_opts(window=0, min_through=1, min_count=0.0, z_range=(0.01, 100.
     return o
 
 
-def check_consistency_opts(o):
-    """hfpf_check_consistency_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
-    return lib().hfpf_check_consistency_opts(C.byref(o) if o is not None else None)
+check_consistency_opts = _opts_checker("consistency")
 
 
 # hfpf_hide_opts.op, hfpf_hide_opts and hfpf_hide_result (include/hfpf.h)
@@ -571,12 +558,9 @@ class HideOpts(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("struct_size", "op", "select_mask", "select_value", "flags", "reserved")]
 
 
-class HideResult(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_uint64) for k in ("n_selected", "n_matched", "n_changed",
-                                                                                                       "n_hidden", "n_full")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k in ("n_selected", "n_matched", "n_changed", "n_hidden", "n_full")}
+class HideResult(_Record):
+    DICT_FIELDS = ("n_selected", "n_matched", "n_changed", "n_hidden", "n_full")
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_uint64) for k in DICT_FIELDS]
 
 
 assert C.sizeof(HideOpts) == 24 and C.sizeof(HideResult) == 48
@@ -584,16 +568,31 @@ assert C.sizeof(HideOpts) == 24 and C.sizeof(HideResult) == 48
 
 def hide_opts(op="hide", select_mask=0, select_value=0):
     """An hfpf_hide_opts: the op ("hide", "show", "hide_others" or its number) and the selector's mask and value."""
-    o = HideOpts()
-    o.struct_size = C.sizeof(HideOpts)
+    o = _sized(HideOpts)
     o.op = HIDE_OPS.get(op, op)
     o.select_mask, o.select_value = int(select_mask) & 0xFFFFFFFF, int(select_value) & 0xFFFFFFFF
     return o
 
 
-def check_hide_opts(o):
-    """hfpf_check_hide_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
-    return lib().hfpf_check_hide_opts(C.byref(o) if o is not None else None)
+check_hide_opts = _opts_checker("hide")
+
+
+def _copy_out(outs, free, *free_args):
+    """numpy copies of engine-owned host arrays, which free(*free_args) then releases (always, also when a copy cannot be
+    allocated).  outs: (pointer, count or shape, dtype, wanted) each; an unwanted array comes back as None."""
+    try:
+        copies = tuple(np.empty(shape, dtype) if wanted else None for _, shape, dtype, wanted in outs)
+        for a, (ptr, _, _, _) in zip(copies, outs):
+            if a is not None and a.nbytes:
+                C.memmove(a.ctypes.data, ptr.value, a.nbytes)
+        return copies
+    finally:
+        free(*free_args)
+
+
+def _mesh_out(v, nv, t, nt):
+    """(vertices, triangles) copied out of the two host arrays of an hfpf_extract_mesh or hfpf_read_ply, which are freed."""
+    return _copy_out([(v, nv.value, MESH_VERTEX_DTYPE, True), (t, (nt.value, 3), np.uint32, True)], lib().hfpf_free_mesh, v, t)
 
 
 def read_ply(path):
@@ -603,16 +602,7 @@ def read_ply(path):
     rc = lib().hfpf_read_ply(os.fsencode(str(path)), C.byref(v), C.byref(nv), C.byref(t), C.byref(nt))
     if rc != 0:
         raise HfpfError(rc, (lib().hfpf_last_error(None) or b"").decode())
-    try:
-        verts = np.empty(nv.value, MESH_VERTEX_DTYPE)
-        tris = np.empty((nt.value, 3), np.uint32)
-        if nv.value:
-            C.memmove(verts.ctypes.data, v.value, verts.nbytes)
-        if nt.value:
-            C.memmove(tris.ctypes.data, t.value, tris.nbytes)
-    finally:
-        lib().hfpf_free_mesh(v, t)
-    return verts, tris
+    return _mesh_out(v, nv, t, nt)
 
 
 # hfpf_raycast_opts.flags, hfpf_ray_hit.flags, hfpf_ray and hfpf_ray_hit (include/hfpf.h)
@@ -633,8 +623,7 @@ class RaycastOpts(C.Structure):
 def raycast_opts(radius=2, min_count=0.0, max_distance=float("inf"), step=0.5, t_range=(0.0, 1.0), cull_backfaces=False):
     """An hfpf_raycast_opts: the query window of the samples (1..4), the count and distance gates, the sample spacing in voxels and
     the ray interval (metres along a general ray, z_near / z_far of a view)."""
-    o = RaycastOpts()
-    o.struct_size = C.sizeof(RaycastOpts)
+    o = _sized(RaycastOpts)
     o.flags = RAYCAST_CULL_BACKFACES if cull_backfaces else 0
     o.radius = int(radius)
     o.min_count, o.max_distance, o.step = float(min_count), float(max_distance), float(step)
@@ -642,9 +631,7 @@ def raycast_opts(radius=2, min_count=0.0, max_distance=float("inf"), step=0.5, t
     return o
 
 
-def check_raycast_opts(o):
-    """hfpf_check_raycast_opts: 0 (HFPF_OK) or the error code (host code, no handle, no GPU needed)."""
-    return lib().hfpf_check_raycast_opts(C.byref(o) if o is not None else None)
+check_raycast_opts = _opts_checker("raycast")
 
 
 def _rays(rays):
@@ -682,8 +669,7 @@ def _snapshot_info_struct(info):
     """A SnapshotInfo from the dict snapshot_info() returns (or a SnapshotInfo as it is)."""
     if isinstance(info, SnapshotInfo):
         return info
-    s = SnapshotInfo()
-    s.struct_size = C.sizeof(SnapshotInfo)
+    s = _sized(SnapshotInfo)
     for name, ctype in SnapshotInfo._fields_:
         if name in ("struct_size", "reserved", "reserved0") or name not in info:
             continue
@@ -699,9 +685,8 @@ def snapshot_info(blob):
     """hfpf_snapshot_info: what the header of a snapshot says, as a dict (host code: no handle, no GPU).  blob: bytes-like, at
     least its first SNAPSHOT_HEADER_BYTES bytes."""
     raw = np.frombuffer(blob, dtype=np.uint8) if blob is not None else None
-    s = SnapshotInfo()
-    s.struct_size = C.sizeof(SnapshotInfo)
-    rc = lib().hfpf_snapshot_info(_p(raw) if raw is not None and raw.size else None, raw.size if raw is not None else 0, C.byref(s))
+    s = _sized(SnapshotInfo)
+    rc =lib().hfpf_snapshot_info(_p(raw) if raw is not None and raw.size else None, raw.size if raw is not None else 0, C.byref(s))
     if rc != 0:
         raise HfpfError(rc, "not a snapshot of this format (hfpf_snapshot_info)")
     out = {n: getattr(s, n) for n, _ in SnapshotInfo._fields_ if n not in ("struct_size", "reserved", "reserved0")}
@@ -759,8 +744,10 @@ def lib():
         raise HfpfError(-4, "libhfpf.so not built (%s); run __graft_entry__.build() -- there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
     vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32
+    for name in ("hfpf_default_config", "hfpf_free_rows", "hfpf_free_mesh", "hfpf_free_components", "hfpf_free_deviation", "hfpf_free_coverage",
+                 "hfpf_free_plan", "hfpf_free_section", "hfpf_free_consistency", "hfpf_free_snapshot"):  # the void functions
+        getattr(L, name).restype = None
     L.hfpf_default_config.argtypes = [C.POINTER(Config)]
-    L.hfpf_default_config.restype = None
     L.hfpf_abi_version.restype = C.c_int
     L.hfpf_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
     L.hfpf_destroy.argtypes = [vp]
@@ -777,7 +764,6 @@ def lib():
     L.hfpf_extract.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     L.hfpf_extract_filtered.argtypes = [vp, C.POINTER(ExtractOpts), C.POINTER(vp), C.POINTER(u64)]
     L.hfpf_free_rows.argtypes = [vp]
-    L.hfpf_free_rows.restype = None
     L.hfpf_write_pcd.argtypes = [vp, u64, C.c_char_p]
     L.hfpf_write_meta_csv.argtypes = [vp, u64, C.c_char_p]
     L.hfpf_write_pcd_xyzrgb.argtypes = [vp, u64, C.c_char_p, u32, i32, i32]
@@ -821,14 +807,12 @@ def lib():
     L.hfpf_extract_mesh.argtypes = [vp, C.POINTER(MeshOpts), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64)]
     L.hfpf_extract_mesh_device.argtypes = [vp, C.POINTER(MeshOpts), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64)]
     L.hfpf_free_mesh.argtypes = [vp, vp]
-    L.hfpf_free_mesh.restype = None
     L.hfpf_write_ply.argtypes = [vp, u64, vp, u64, C.c_char_p]
     L.hfpf_check_mesh_opts.argtypes = [C.POINTER(MeshOpts)]
     L.hfpf_check_component_opts.argtypes = [C.POINTER(ComponentOpts)]
     for fn in (L.hfpf_extract_components, L.hfpf_extract_components_device):
         fn.argtypes = [vp, C.POINTER(ComponentOpts), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64)]
     L.hfpf_free_components.argtypes = [vp, vp, vp]
-    L.hfpf_free_components.restype = None
     L.hfpf_check_deviation_opts.argtypes = [C.POINTER(DeviationOpts)]
     for fn in (L.hfpf_compare_mesh, L.hfpf_compare_mesh_device):
         fn.argtypes = [vp, C.POINTER(DeviationOpts), vp, u64, u32, vp, u64, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64),
@@ -840,26 +824,21 @@ def lib():
     for fn in (L.hfpf_cover_mesh, L.hfpf_cover_mesh_device):
         fn.argtypes = [vp, C.POINTER(CoverOpts), vp, u64, u32, vp, u64, vp, C.POINTER(vp), C.POINTER(CoverageSummary)]
     L.hfpf_free_coverage.argtypes = [vp]
-    L.hfpf_free_coverage.restype = None
     L.hfpf_check_plan_opts.argtypes = [C.POINTER(PlanOpts)]
     for fn in (L.hfpf_plan_views, L.hfpf_plan_views_device):
         fn.argtypes = [vp, C.POINTER(PlanOpts), vp, u64, u32, vp, u64, vp, vp, u32, vp, C.POINTER(vp), C.POINTER(PlanSummary)]
     L.hfpf_free_plan.argtypes = [vp]
-    L.hfpf_free_plan.restype = None
     L.hfpf_check_section_opts.argtypes = [C.POINTER(SectionOpts)]
     for fn in (L.hfpf_section_mesh, L.hfpf_section_mesh_device):
         fn.argtypes = [vp, C.POINTER(SectionOpts), vp, u64, u32, vp, u64, vp, vp, u32, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64),
                        C.POINTER(vp), C.POINTER(u64), vp, C.POINTER(SectionSummary)]
     L.hfpf_free_section.argtypes = [vp, vp, vp]
-    L.hfpf_free_section.restype = None
     L.hfpf_free_deviation.argtypes = [vp, vp]
-    L.hfpf_free_deviation.restype = None
     L.hfpf_check_consistency_opts.argtypes = [C.POINTER(ConsistencyOpts)]
     for fn in (L.hfpf_depth_consistency, L.hfpf_depth_consistency_device):
         fn.argtypes = [vp, C.POINTER(ConsistencyOpts), C.POINTER(DepthImage), vp, u64, u32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64),
                        C.POINTER(ConsistencySummary)]
     L.hfpf_free_consistency.argtypes = [vp, vp]
-    L.hfpf_free_consistency.restype = None
     L.hfpf_check_hide_opts.argtypes = [C.POINTER(HideOpts)]
     for fn in (L.hfpf_hide_voxels, L.hfpf_hide_voxels_device):
         fn.argtypes = [vp, C.POINTER(HideOpts), vp, u64, u32, vp, u32, C.POINTER(HideResult)]
@@ -875,7 +854,6 @@ def lib():
     L.hfpf_raycast_view_device.argtypes = [vp, C.POINTER(RaycastOpts), u32, u32, dbl, dbl, dbl, dbl, u32, vp, vp]
     L.hfpf_snapshot.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     L.hfpf_free_snapshot.argtypes = [vp]
-    L.hfpf_free_snapshot.restype = None
     L.hfpf_restore.argtypes = [vp, vp, u64]
     L.hfpf_save.argtypes = [vp, C.c_char_p]
     L.hfpf_load.argtypes = [vp, C.c_char_p]
@@ -887,6 +865,49 @@ def lib():
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _pose12(pose, identity=False):
+    """The twelve contiguous doubles of one 3x4 [R|t]; identity=True: no pose stands for the identity."""
+    if pose is None and identity:
+        pose = np.eye(4)[:3]
+    return np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+
+
+def _poses(poses, n=-1, flat=False):
+    """The contiguous doubles of a batch of 3x4 poses: (n, 12), or flat as the consistency calls take them."""
+    poses = np.ascontiguousarray(poses, dtype=np.float64)
+    return poses.reshape(-1) if flat else poses.reshape(n, 12)
+
+
+def _cloud_args(cloud, layout, n_points, device=False):
+    """(cloud, n_points, point_step, off_x, off_y, off_z) of a cloud of records.  No layout = packed (x, y, z) float32 triples.  A
+    host cloud is made contiguous (and float32 without a layout), and n_points defaults to the records it holds; with device=True
+    the cloud is a device pointer, passed on as it is."""
+    if not device:
+        cloud = np.ascontiguousarray(cloud) if layout else np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+    layout = layout or dict(point_step=12, off_x=0, off_y=4, off_z=8)
+    step = layout["point_step"]
+    if n_points is None:
+        n_points = cloud.nbytes // step
+    return cloud, n_points, step, layout["off_x"], layout["off_y"], layout["off_z"]
+
+
+def _mesh_args(verts, tris, device, n_verts, vertex_stride, n_tris):
+    """The five mesh arguments of the C ABI, (vertices, n_verts, vertex_stride, triangles, n_tris), and the arrays that have to
+    outlive the call.  device=True: verts and tris are device pointers and the three numbers are required.  Otherwise verts are
+    MESH_VERTEX_DTYPE records (stride 32) or an (n, 3) float32 array (stride 12), tris (n, 3) uint32, the three numbers override
+    what the arrays give, and an array of no bytes is passed as NULL."""
+    if device:
+        return (C.c_void_p(verts), int(n_verts), int(vertex_stride), C.c_void_p(tris), int(n_tris)), ()
+    verts = np.ascontiguousarray(verts)
+    if verts.dtype != MESH_VERTEX_DTYPE:
+        verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+    tris = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+    stride = int(vertex_stride) if vertex_stride is not None else verts.dtype.itemsize * (1 if verts.dtype == MESH_VERTEX_DTYPE else 3)
+    nv = int(n_verts) if n_verts is not None else len(verts)
+    nt = int(n_tris) if n_tris is not None else len(tris)
+    return (_p(verts) if verts.nbytes else None, nv, stride, _p(tris) if tris.nbytes else None, nt), (verts, tris)
 
 
 def default_config():
@@ -965,6 +986,25 @@ class OccupancyGrid:
             raise HfpfError(rc, lib().hfpf_last_error(self._h).decode())
         return rc
 
+    def _device_results(self, n, outs, call):
+        """Where a device form leaves its results.  outs: (the caller's device pointer or 0, dtype, wanted) per result;
+        call(*pointers) runs the C call.  With the caller's first pointer the results stay in the caller's buffers and None is
+        returned; without it they go through scratch device buffers of n records and come back as a tuple of numpy arrays (None
+        for an unwanted one)."""
+        if outs[0][0]:
+            call(*(ptr for ptr, _, _ in outs))
+            return None
+        bufs = []
+        try:
+            for _, dtype, wanted in outs:
+                bufs.append(self.device_alloc(max(1, n) * dtype.itemsize) if wanted else 0)
+            call(*bufs)
+            return tuple(self.device_download(b, n * dtype.itemsize).view(dtype) if b else None for b, (_, dtype, _) in zip(bufs, outs))
+        finally:
+            for b in bufs:
+                if b:
+                    self.device_free(b)
+
     def close(self):
         if getattr(self, "_h", None):
             lib().hfpf_destroy(self._h)
@@ -993,7 +1033,7 @@ class OccupancyGrid:
     def integrate(self, buf, pose, n_points=None, point_step=16, off_x=0, off_y=4, off_z=8, off_rgb=12):
         """addPoints + capture stage for one host frame (PointCloud2-style records)."""
         buf = np.ascontiguousarray(buf)
-        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        pose = _pose12(pose)
         if n_points is None:
             n_points = buf.nbytes // point_step
         self._chk(lib().hfpf_integrate(self._h, _p(buf), n_points, point_step, off_x, off_y, off_z, off_rgb, _p(pose)))
@@ -1009,14 +1049,14 @@ class OccupancyGrid:
 
     def integrate_pinned(self, buf, pose, n_points=None, point_step=16, off_x=0, off_y=4, off_z=8, off_rgb=12):
         """One frame straight from page-locked memory (a view from host_alloc): asynchronous, no bounce copy."""
-        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        pose = _pose12(pose)
         if n_points is None:
             n_points = buf.nbytes // point_step
         self._chk(lib().hfpf_integrate_pinned(self._h, C.c_void_p(buf.ctypes.data), n_points, point_step, off_x, off_y, off_z, off_rgb, _p(pose)))
 
     def integrate_device(self, dev_ptr, n_frames, frame_stride, n_points, poses, frame_ids=None, point_step=16, off_x=0,
                          off_y=4, off_z=8, off_rgb=12):
-        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(n_frames, 12)
+        poses = _poses(poses, n_frames)
         ids = None
         if frame_ids is not None:
             ids = np.ascontiguousarray(frame_ids, dtype=np.uint32)
@@ -1027,21 +1067,21 @@ class OccupancyGrid:
         """One registered depth (+ colour) frame from numpy images in pageable memory (hfpf_integrate_depth).
         K = (fx, fy, cx, cy); depth uint16 (counts of depth_scale metres) or float32 (metres)."""
         d = _image_desc(depth, K, color, color_format, depth_scale)
-        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        pose = _pose12(pose)
         self._chk(lib().hfpf_integrate_depth(self._h, C.byref(d), C.c_void_p(depth.ctypes.data),
                                              C.c_void_p(color.ctypes.data) if color is not None else None, _p(pose)))
 
     def integrate_depth_pinned(self, depth, pose, K, color=None, color_format=None, depth_scale=0.001):
         """The same for images that are views of page-locked memory (host_alloc); they must stay untouched until the next sync."""
         d = _image_desc(depth, K, color, color_format, depth_scale)
-        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        pose = _pose12(pose)
         self._chk(lib().hfpf_integrate_depth_pinned(self._h, C.byref(d), C.c_void_p(depth.ctypes.data),
                                                     C.c_void_p(color.ctypes.data) if color is not None else None, _p(pose)))
 
     def integrate_depth_device(self, desc, dev_depth, depth_frame_stride, n_frames, poses, dev_color=0, color_frame_stride=0,
                                frame_ids=None):
         """n_frames depth frames resident in HBM (hfpf_integrate_depth_device); desc from depth_desc()."""
-        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(n_frames, 12)
+        poses = _poses(poses, n_frames)
         ids = np.ascontiguousarray(frame_ids, dtype=np.uint32) if frame_ids is not None else None
         self._chk(lib().hfpf_integrate_depth_device(self._h, C.byref(desc), C.c_void_p(dev_depth), depth_frame_stride,
                                                     C.c_void_p(dev_color) if dev_color else None, color_frame_stride, n_frames,
@@ -1086,8 +1126,8 @@ class OccupancyGrid:
         """One view of the fused model (hfpf_render): pose = camera -> fusion frame 3x4, K = (fx, fy, cx, cy).  Keywords as
         render_opts (z_range, min_count, splat_radius, max_splat_radius, cull_backfaces, world_normals), or a ready `opts`.
         Returns {plane: HxW (depth, rgb, count) or HxWx3 (normal, voxel) array} for the requested planes."""
-        o = opts if opts is not None else render_opts(K, width, height, **kw)
-        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        o = _or(opts, render_opts, K, width, height, **kw)
+        pose = _pose12(pose)
         out, pl = {}, RenderPlanes()
         for name, dt, ch in RENDER_PLANES:
             if name in planes:
@@ -1102,8 +1142,8 @@ class OccupancyGrid:
     def render_device(self, poses, K, width, height, dev_planes, opts=None, **kw):
         """len(poses) views into device planes (hfpf_render_device): dev_planes = {plane: device pointer}; view v of a plane
         starts v * width * height elements (x 3 for normal and voxel) behind its pointer."""
-        o = opts if opts is not None else render_opts(K, width, height, **kw)
-        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12)
+        o = _or(opts, render_opts, K, width, height, **kw)
+        poses = _poses(poses)
         pl = RenderPlanes()
         for name, ptr in dev_planes.items():
             if name not in RenderPlanes.__dict__:
@@ -1116,16 +1156,16 @@ class OccupancyGrid:
         """Refine the camera -> fusion pose of one depth image in pageable memory (hfpf_track_depth).  The model view defaults to the
         image's own intrinsics and size with back faces culled; keywords as track_opts.  Returns (3x4 pose, result dict)."""
         d = _image_desc(depth, K, None, None, depth_scale)
-        o = opts if opts is not None else track_opts(K, depth.shape[1], depth.shape[0], **kw)
-        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        o = _or(opts, track_opts, K, depth.shape[1], depth.shape[0], **kw)
+        pose = _pose12(pose)
         r = track_result()
         self._chk(lib().hfpf_track_depth(self._h, C.byref(o), C.byref(d), C.c_void_p(depth.ctypes.data), _p(pose), C.byref(r)))
         return _track_out(r)
 
     def track_depth_device(self, desc, dev_depth, pose, opts=None, **kw):
         """The same for a depth image resident in HBM (hfpf_track_depth_device); desc from depth_desc()."""
-        o = opts if opts is not None else track_opts((desc.fx, desc.fy, desc.cx, desc.cy), desc.width, desc.height, **kw)
-        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        o = _or(opts, track_opts, (desc.fx, desc.fy, desc.cx, desc.cy), desc.width, desc.height, **kw)
+        pose = _pose12(pose)
         r = track_result()
         self._chk(lib().hfpf_track_depth_device(self._h, C.byref(o), C.byref(desc), C.c_void_p(dev_depth), _p(pose), C.byref(r)))
         return _track_out(r)
@@ -1133,15 +1173,11 @@ class OccupancyGrid:
     def track(self, cloud, layout, pose, view_K, width, height, n_points=None, opts=None, **kw):
         """Refine the pose of one cloud of records in pageable memory (hfpf_track); layout = dict(point_step, off_x, off_y, off_z)
         (extra keys such as off_rgb are ignored); the model view is (view_K, width, height)."""
-        cloud = np.ascontiguousarray(cloud)
-        step = layout["point_step"]
-        if n_points is None:
-            n_points = cloud.nbytes // step
-        o = opts if opts is not None else track_opts(view_K, width, height, **kw)
-        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        cloud, *layout = _cloud_args(cloud, layout, n_points)
+        o = _or(opts, track_opts, view_K, width, height, **kw)
+        pose = _pose12(pose)
         r = track_result()
-        self._chk(lib().hfpf_track(self._h, C.byref(o), _p(cloud), n_points, step, layout["off_x"], layout["off_y"], layout["off_z"],
-                                   _p(pose), C.byref(r)))
+        self._chk(lib().hfpf_track(self._h, C.byref(o), _p(cloud), *layout, _p(pose), C.byref(r)))
         return _track_out(r)
 
     # -- querying the model at given points --
@@ -1150,19 +1186,12 @@ class OccupancyGrid:
         """Nearest row within the voxel window of each point of a cloud in pageable memory (hfpf_query).  cloud: an (N, 3) float32
         array, or records with layout = dict(point_step, off_x, off_y, off_z) (extra keys are ignored).  Returns (hits, rows):
         numpy arrays of QUERY_HIT_DTYPE and ROW_DTYPE; rows is None with rows=False."""
-        cloud = np.ascontiguousarray(cloud)
-        if layout is None:
-            cloud = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
-            layout = dict(point_step=12, off_x=0, off_y=4, off_z=8)
-        step = layout["point_step"]
-        if n_points is None:
-            n_points = cloud.nbytes // step
-        o = opts if opts is not None else query_opts(radius, min_count, max_distance, zclip)
-        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        cloud, n_points, *layout = _cloud_args(cloud, layout, n_points)
+        o = _or(opts, query_opts, radius, min_count, max_distance, zclip)
+        pose = _pose12(pose)
         hits = np.empty(n_points, QUERY_HIT_DTYPE)
         out = np.empty(n_points, ROW_DTYPE) if rows else None
-        self._chk(lib().hfpf_query(self._h, C.byref(o), _p(cloud), n_points, step, layout["off_x"], layout["off_y"], layout["off_z"], _p(pose),
-                                   _p(hits), _p(out) if rows else None))
+        self._chk(lib().hfpf_query(self._h, C.byref(o), _p(cloud), n_points, *layout, _p(pose), _p(hits), _p(out) if rows else None))
         return hits, out
 
     def query_device(self, dev_cloud, n_points, pose, layout=None, dev_hits=0, dev_rows=0, rows=True, opts=None, radius=1, min_count=0.0,
@@ -1170,50 +1199,28 @@ class OccupancyGrid:
         """The same for a cloud resident in HBM, read in place (hfpf_query_device); layout defaults to packed (x, y, z) f32 triples.
         With dev_hits (and dev_rows, or 0 for none) the results stay in those device buffers and None is returned; otherwise they go
         to scratch device buffers and come back as (hits, rows) numpy arrays as query() returns them."""
-        layout = layout or dict(point_step=12, off_x=0, off_y=4, off_z=8)
-        o = opts if opts is not None else query_opts(radius, min_count, max_distance, zclip)
-        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
-        own = not dev_hits
-        if own:
-            dev_hits = self.device_alloc(max(1, n_points) * QUERY_HIT_DTYPE.itemsize)
-            dev_rows = self.device_alloc(max(1, n_points) * ROW_DTYPE.itemsize) if rows else 0
-        try:
-            self._chk(lib().hfpf_query_device(self._h, C.byref(o), C.c_void_p(dev_cloud), n_points, layout["point_step"], layout["off_x"],
-                                              layout["off_y"], layout["off_z"], _p(pose), C.c_void_p(dev_hits),
-                                              C.c_void_p(dev_rows) if dev_rows else None))
-            if not own:
-                return None
-            hits = self.device_download(dev_hits, n_points * QUERY_HIT_DTYPE.itemsize).view(QUERY_HIT_DTYPE)
-            out = self.device_download(dev_rows, n_points * ROW_DTYPE.itemsize).view(ROW_DTYPE) if rows else None
-            return hits, out
-        finally:
-            if own:
-                self.device_free(dev_hits)
-                if dev_rows:
-                    self.device_free(dev_rows)
+        dev_cloud, n_points, *layout = _cloud_args(dev_cloud, layout, n_points, device=True)
+        o = _or(opts, query_opts, radius, min_count, max_distance, zclip)
+        pose = _pose12(pose)
+
+        def call(hits, out):
+            self._chk(lib().hfpf_query_device(self._h, C.byref(o), C.c_void_p(dev_cloud), n_points, *layout, _p(pose), C.c_void_p(hits),
+                                              C.c_void_p(out) if out else None))
+        return self._device_results(n_points, [(dev_hits, QUERY_HIT_DTYPE, True), (dev_rows, ROW_DTYPE, rows)], call)
 
     # -- a surface of the model --
     def extract_mesh(self, opts=None, radius=2, min_count=0.0, max_distance=float("inf")):
         """The triangle mesh of the fused model (hfpf_extract_mesh): (vertices of MESH_VERTEX_DTYPE, (n, 3) uint32 triangles), copied
         out of the engine's host arrays."""
-        o = opts if opts is not None else mesh_opts(radius, min_count, max_distance)
+        o = _or(opts, mesh_opts, radius, min_count, max_distance)
         v, nv, t, nt = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
         self._chk(lib().hfpf_extract_mesh(self._h, C.byref(o), C.byref(v), C.byref(nv), C.byref(t), C.byref(nt)))
-        try:
-            verts = np.empty(nv.value, MESH_VERTEX_DTYPE)
-            tris = np.empty((nt.value, 3), np.uint32)
-            if nv.value:
-                C.memmove(verts.ctypes.data, v.value, verts.nbytes)
-            if nt.value:
-                C.memmove(tris.ctypes.data, t.value, tris.nbytes)
-        finally:
-            lib().hfpf_free_mesh(v, t)
-        return verts, tris
+        return _mesh_out(v, nv, t, nt)
 
     def extract_mesh_device(self, opts=None, radius=2, min_count=0.0, max_distance=float("inf")):
         """The same mesh in HBM (hfpf_extract_mesh_device): (vertex pointer, n_verts, triangle pointer, n_tris); free both pointers with
         device_free (they are 0 for an empty mesh)."""
-        o = opts if opts is not None else mesh_opts(radius, min_count, max_distance)
+        o = _or(opts, mesh_opts, radius, min_count, max_distance)
         v, nv, t, nt = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
         self._chk(lib().hfpf_extract_mesh_device(self._h, C.byref(o), C.byref(v), C.byref(nv), C.byref(t), C.byref(nt)))
         return v.value or 0, nv.value, t.value or 0, nt.value
@@ -1224,26 +1231,14 @@ class OccupancyGrid:
         None with rows=False, uint32 labels, comps of COMPONENT_DTYPE), copied out of the engine's host arrays.  Keywords as
         component_opts().  device=True runs hfpf_extract_components_device instead and returns (rows pointer, labels pointer, n_rows,
         comps pointer, n_comps) in HBM; free the pointers with device_free (they are 0 when nothing is kept)."""
-        o = opts if opts is not None else component_opts(**kw)
+        o = _or(opts, component_opts, **kw)
         r, l, nr, c, nc = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
-        rp = C.byref(r) if rows else None
+        fn = lib().hfpf_extract_components_device if device else lib().hfpf_extract_components
+        self._chk(fn(self._h, C.byref(o), C.byref(r) if rows else None, C.byref(l), C.byref(nr), C.byref(c), C.byref(nc)))
         if device:
-            self._chk(lib().hfpf_extract_components_device(self._h, C.byref(o), rp, C.byref(l), C.byref(nr), C.byref(c), C.byref(nc)))
             return r.value or 0, l.value or 0, nr.value, c.value or 0, nc.value
-        self._chk(lib().hfpf_extract_components(self._h, C.byref(o), rp, C.byref(l), C.byref(nr), C.byref(c), C.byref(nc)))
-        try:
-            out = np.empty(nr.value, ROW_DTYPE) if rows else None
-            labels = np.empty(nr.value, np.uint32)
-            comps = np.empty(nc.value, COMPONENT_DTYPE)
-            if nr.value:
-                if rows:
-                    C.memmove(out.ctypes.data, r.value, out.nbytes)
-                C.memmove(labels.ctypes.data, l.value, labels.nbytes)
-            if nc.value:
-                C.memmove(comps.ctypes.data, c.value, comps.nbytes)
-        finally:
-            lib().hfpf_free_components(r, l, c)
-        return out, labels, comps
+        return _copy_out([(r, nr.value, ROW_DTYPE, rows), (l, nr.value, np.uint32, True), (c, nc.value, COMPONENT_DTYPE, True)],
+                         lib().hfpf_free_components, r, l, c)
 
     # -- deviation from a triangle mesh --
     def compare_mesh(self, verts, tris, pose=None, device=False, opts=None, rows=False, n_verts=None, vertex_stride=None, n_tris=None, **kw):
@@ -1253,32 +1248,15 @@ class OccupancyGrid:
         deviation_opts().  device=True runs hfpf_compare_mesh_device: verts and tris are device pointers (n_verts, vertex_stride and
         n_tris are then required) and the result is (rows pointer or 0, dev pointer, n_rows, summary); free the pointers with
         device_free (they are 0 without rows)."""
-        o = opts if opts is not None else deviation_opts(**kw)
-        pose = np.ascontiguousarray(np.eye(4)[:3] if pose is None else pose, np.float64).reshape(12)
+        o = _or(opts, deviation_opts, **kw)
+        pose = _pose12(pose, identity=True)
+        mesh, keep = _mesh_args(verts, tris, device, n_verts, vertex_stride, n_tris)
         r, d, nr, s = C.c_void_p(), C.c_void_p(), C.c_uint64(), DeviationSummary()
-        rp = C.byref(r) if rows else None
+        fn = lib().hfpf_compare_mesh_device if device else lib().hfpf_compare_mesh
+        self._chk(fn(self._h, C.byref(o), *mesh, _p(pose), C.byref(r) if rows else None, C.byref(d), C.byref(nr), C.byref(s)))
         if device:
-            self._chk(lib().hfpf_compare_mesh_device(self._h, C.byref(o), C.c_void_p(verts), int(n_verts), int(vertex_stride), C.c_void_p(tris),
-                                                     int(n_tris), _p(pose), rp, C.byref(d), C.byref(nr), C.byref(s)))
             return r.value or 0, d.value or 0, nr.value, s.as_dict()
-        verts = np.ascontiguousarray(verts)
-        if verts.dtype != MESH_VERTEX_DTYPE:
-            verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
-        stride = int(vertex_stride) if vertex_stride is not None else verts.dtype.itemsize * (1 if verts.dtype == MESH_VERTEX_DTYPE else 3)
-        nv = int(n_verts) if n_verts is not None else len(verts)
-        nt = int(n_tris) if n_tris is not None else len(tris)
-        self._chk(lib().hfpf_compare_mesh(self._h, C.byref(o), _p(verts) if verts.nbytes else None, nv, stride, _p(tris) if tris.nbytes else None, nt,
-                                          _p(pose), rp, C.byref(d), C.byref(nr), C.byref(s)))
-        try:
-            dev = np.empty(nr.value, DEVIATION_DTYPE)
-            out_rows = np.empty(nr.value, ROW_DTYPE) if rows else None
-            if nr.value:
-                C.memmove(dev.ctypes.data, d.value, dev.nbytes)
-                if rows:
-                    C.memmove(out_rows.ctypes.data, r.value, out_rows.nbytes)
-        finally:
-            lib().hfpf_free_deviation(r, d)
+        out_rows, dev = _copy_out([(r, nr.value, ROW_DTYPE, rows), (d, nr.value, DEVIATION_DTYPE, True)], lib().hfpf_free_deviation, r, d)
         return (out_rows, dev, s.as_dict()) if rows else (dev, s.as_dict())
 
     # -- best-fitting a triangle mesh to the model --
@@ -1286,22 +1264,12 @@ class OccupancyGrid:
         """Refine the mesh frame -> fusion frame pose of a triangle mesh against the model's rows (hfpf_align_mesh): a dict of
         iterations, flags, rows_sampled, inliers, rms, information (6x6) and pose (3x4, to hand to compare_mesh).  verts, tris, pose
         and the device form's arguments as compare_mesh(); keywords as align_opts().  The capture range is max_distance."""
-        o = opts if opts is not None else align_opts(**kw)
-        pose = np.ascontiguousarray(np.eye(4)[:3] if pose is None else pose, np.float64).reshape(12)
+        o = _or(opts, align_opts, **kw)
+        pose = _pose12(pose, identity=True)
+        mesh, keep = _mesh_args(verts, tris, device, n_verts, vertex_stride, n_tris)
         r = align_result()
-        if device:
-            self._chk(lib().hfpf_align_mesh_device(self._h, C.byref(o), C.c_void_p(verts), int(n_verts), int(vertex_stride), C.c_void_p(tris),
-                                                   int(n_tris), _p(pose), C.byref(r)))
-            return _refine_out(r, "rows_sampled")
-        verts = np.ascontiguousarray(verts)
-        if verts.dtype != MESH_VERTEX_DTYPE:
-            verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
-        stride = int(vertex_stride) if vertex_stride is not None else verts.dtype.itemsize * (1 if verts.dtype == MESH_VERTEX_DTYPE else 3)
-        nv = int(n_verts) if n_verts is not None else len(verts)
-        nt = int(n_tris) if n_tris is not None else len(tris)
-        self._chk(lib().hfpf_align_mesh(self._h, C.byref(o), _p(verts) if verts.nbytes else None, nv, stride, _p(tris) if tris.nbytes else None, nt,
-                                        _p(pose), C.byref(r)))
+        fn = lib().hfpf_align_mesh_device if device else lib().hfpf_align_mesh
+        self._chk(fn(self._h, C.byref(o), *mesh, _p(pose), C.byref(r)))
         return _refine_out(r, "rows_sampled")
 
     # -- coverage of a triangle mesh by the model --
@@ -1310,28 +1278,15 @@ class OccupancyGrid:
         summary dict with the derived floats area and covered_area in m^2).  verts, tris, pose and the device form's arguments as
         compare_mesh(); keywords as cover_opts().  device=True runs hfpf_cover_mesh_device and returns (records pointer, summary);
         free the pointer with device_free (it is 0 without triangles)."""
-        o = opts if opts is not None else cover_opts(**kw)
-        pose = np.ascontiguousarray(np.eye(4)[:3] if pose is None else pose, np.float64).reshape(12)
+        o = _or(opts, cover_opts, **kw)
+        pose = _pose12(pose, identity=True)
+        mesh, keep = _mesh_args(verts, tris, device, n_verts, vertex_stride, n_tris)
         c, s = C.c_void_p(), CoverageSummary()
+        fn = lib().hfpf_cover_mesh_device if device else lib().hfpf_cover_mesh
+        self._chk(fn(self._h, C.byref(o), *mesh, _p(pose), C.byref(c), C.byref(s)))
         if device:
-            self._chk(lib().hfpf_cover_mesh_device(self._h, C.byref(o), C.c_void_p(verts), int(n_verts), int(vertex_stride), C.c_void_p(tris),
-                                                   int(n_tris), _p(pose), C.byref(c), C.byref(s)))
             return c.value or 0, s.as_dict()
-        verts = np.ascontiguousarray(verts)
-        if verts.dtype != MESH_VERTEX_DTYPE:
-            verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
-        stride = int(vertex_stride) if vertex_stride is not None else verts.dtype.itemsize * (1 if verts.dtype == MESH_VERTEX_DTYPE else 3)
-        nv = int(n_verts) if n_verts is not None else len(verts)
-        nt = int(n_tris) if n_tris is not None else len(tris)
-        self._chk(lib().hfpf_cover_mesh(self._h, C.byref(o), _p(verts) if verts.nbytes else None, nv, stride, _p(tris) if tris.nbytes else None, nt,
-                                        _p(pose), C.byref(c), C.byref(s)))
-        try:
-            cov = np.empty(nt if c.value else 0, TRI_COVERAGE_DTYPE)
-            if cov.nbytes:
-                C.memmove(cov.ctypes.data, c.value, cov.nbytes)
-        finally:
-            lib().hfpf_free_coverage(c)
+        cov, = _copy_out([(c, mesh[4] if c.value else 0, TRI_COVERAGE_DTYPE, True)], lib().hfpf_free_coverage, c)  # mesh[4]: n_tris
         return cov, s.as_dict()
 
     # -- planar sections of a triangle mesh --
@@ -1341,35 +1296,20 @@ class OccupancyGrid:
         (n.x, n.y, n.z, d) in the fusion frame; verts, tris, pose and the device form's arguments as compare_mesh().  device=True runs
         hfpf_section_mesh_device and returns the three arrays as (pointer, count) pairs in HBM: free the pointers with device_free
         (they are 0 without segments).  section_mesh_device() is that form by name."""
-        o = opts if opts is not None else section_opts()
-        pose = np.ascontiguousarray(np.eye(4)[:3] if pose is None else pose, np.float64).reshape(12)
+        o = _or(opts, section_opts)
+        pose = _pose12(pose, identity=True)
         planes = np.ascontiguousarray(planes, np.float64).reshape(-1, 4)
         recs = np.zeros(len(planes), SECTION_PLANE_DTYPE)
         pp, rp = (_p(planes), _p(recs)) if len(planes) else (None, None)
+        mesh, keep = _mesh_args(verts, tris, device, n_verts, vertex_stride, n_tris)
         p, s, c, npt, ns, nc, summ = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_uint64(), SectionSummary()
-        outs = (C.byref(p), C.byref(npt), C.byref(s), C.byref(ns), C.byref(c), C.byref(nc), rp, C.byref(summ))
+        fn = lib().hfpf_section_mesh_device if device else lib().hfpf_section_mesh
+        self._chk(fn(self._h, C.byref(o), *mesh, _p(pose), pp, len(planes), C.byref(p), C.byref(npt), C.byref(s), C.byref(ns), C.byref(c),
+                     C.byref(nc), rp, C.byref(summ)))
         if device:
-            self._chk(lib().hfpf_section_mesh_device(self._h, C.byref(o), C.c_void_p(verts), int(n_verts), int(vertex_stride), C.c_void_p(tris),
-                                                     int(n_tris), _p(pose), pp, len(planes), *outs))
             return (p.value or 0, npt.value), (s.value or 0, ns.value), (c.value or 0, nc.value), recs, summ.as_dict()
-        verts = np.ascontiguousarray(verts)
-        if verts.dtype != MESH_VERTEX_DTYPE:
-            verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
-        stride = int(vertex_stride) if vertex_stride is not None else verts.dtype.itemsize * (1 if verts.dtype == MESH_VERTEX_DTYPE else 3)
-        nv = int(n_verts) if n_verts is not None else len(verts)
-        nt = int(n_tris) if n_tris is not None else len(tris)
-        self._chk(lib().hfpf_section_mesh(self._h, C.byref(o), _p(verts) if verts.nbytes else None, nv, stride, _p(tris) if tris.nbytes else None, nt,
-                                          _p(pose), pp, len(planes), *outs))
-        try:
-            points = np.empty(npt.value, SECTION_POINT_DTYPE)
-            segments = np.empty(ns.value, SECTION_SEGMENT_DTYPE)
-            contours = np.empty(nc.value, SECTION_CONTOUR_DTYPE)
-            for a, q in ((points, p), (segments, s), (contours, c)):
-                if a.nbytes:
-                    C.memmove(a.ctypes.data, q.value, a.nbytes)
-        finally:
-            lib().hfpf_free_section(p, s, c)
+        points, segments, contours = _copy_out([(p, npt.value, SECTION_POINT_DTYPE, True), (s, ns.value, SECTION_SEGMENT_DTYPE, True),
+                                                (c, nc.value, SECTION_CONTOUR_DTYPE, True)], lib().hfpf_free_section, p, s, c)
         return points, segments, contours, recs, summ.as_dict()
 
     def section_mesh_device(self, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose=None, planes=(), opts=None):
@@ -1383,34 +1323,20 @@ class OccupancyGrid:
         fusion frame; verts, tris, pose and the device form's arguments as compare_mesh(); keywords as plan_opts().  device=True runs
         hfpf_plan_views_device and returns the records as a device pointer (0 without triangles or with tri_plan=False): free it with
         device_free."""
-        o = opts if opts is not None else plan_opts(**kw)
-        pose = np.ascontiguousarray(np.eye(4)[:3] if pose is None else pose, np.float64).reshape(12)
-        poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
-        nv = len(poses)
-        room = np.zeros(max(nv, 1), VIEW_SCORE_DTYPE)  # never NULL, also without views
-        scores, sp = room[:nv], _p(room)
+        o = _or(opts, plan_opts, **kw)
+        pose = _pose12(pose, identity=True)
+        poses = _poses(poses)
+        n_views = len(poses)
+        room = np.zeros(max(n_views, 1), VIEW_SCORE_DTYPE)  # never NULL, also without views
+        mesh, keep = _mesh_args(verts, tris, device, n_verts, vertex_stride, n_tris)
         t, s = C.c_void_p(), PlanSummary()
-        tp = C.byref(t) if tri_plan else None
+        fn = lib().hfpf_plan_views_device if device else lib().hfpf_plan_views
+        self._chk(fn(self._h, C.byref(o), *mesh, _p(pose), _p(poses) if n_views else None, n_views, _p(room), C.byref(t) if tri_plan else None,
+                     C.byref(s)))
         if device:
-            self._chk(lib().hfpf_plan_views_device(self._h, C.byref(o), C.c_void_p(verts), int(n_verts), int(vertex_stride), C.c_void_p(tris),
-                                                   int(n_tris), _p(pose), _p(poses) if nv else None, nv, sp, tp, C.byref(s)))
-            return scores, t.value or 0, s.as_dict()
-        verts = np.ascontiguousarray(verts)
-        if verts.dtype != MESH_VERTEX_DTYPE:
-            verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
-        stride = int(vertex_stride) if vertex_stride is not None else verts.dtype.itemsize * (1 if verts.dtype == MESH_VERTEX_DTYPE else 3)
-        n_v = int(n_verts) if n_verts is not None else len(verts)
-        nt = int(n_tris) if n_tris is not None else len(tris)
-        self._chk(lib().hfpf_plan_views(self._h, C.byref(o), _p(verts) if verts.nbytes else None, n_v, stride, _p(tris) if tris.nbytes else None, nt,
-                                        _p(pose), _p(poses) if nv else None, nv, sp, tp, C.byref(s)))
-        try:
-            rec = np.empty(nt if t.value else 0, TRI_PLAN_DTYPE) if tri_plan else None
-            if tri_plan and rec.nbytes:
-                C.memmove(rec.ctypes.data, t.value, rec.nbytes)
-        finally:
-            lib().hfpf_free_plan(t)
-        return scores, rec, s.as_dict()
+            return room[:n_views], t.value or 0, s.as_dict()
+        rec, = _copy_out([(t, mesh[4] if t.value else 0, TRI_PLAN_DTYPE, tri_plan)], lib().hfpf_free_plan, t)  # mesh[4]: n_tris
+        return room[:n_views], rec, s.as_dict()
 
     # -- rows that depth frames see through --
     def depth_consistency(self, frames, poses, K, depth_scale=0.001, opts=None, rows=True, desc=None, depth_frame_stride=None, n_frames=None,
@@ -1419,7 +1345,7 @@ class OccupancyGrid:
         rows=False, cons of ROW_CONSISTENCY_DTYPE, summary dict).  frames: an (n, H, W) uint16 or float32 array (rows and frames may be
         padded: a view of a larger array); poses: n 3x4 [R|t], camera -> fusion frame.  Keywords as consistency_opts().  desc,
         depth_frame_stride and n_frames override what the array's shape and strides give (frames is then any buffer)."""
-        o = opts if opts is not None else consistency_opts(**kw)
+        o = _or(opts, consistency_opts, **kw)
         frames = np.asarray(frames)
         if desc is None:
             if frames.ndim != 3:
@@ -1431,26 +1357,18 @@ class OccupancyGrid:
             d, n, stride = desc, int(n_frames), int(depth_frame_stride)
         n = int(n_frames) if n_frames is not None else n
         stride = int(depth_frame_stride) if depth_frame_stride is not None else stride
-        poses = np.ascontiguousarray(poses, np.float64).reshape(-1)
+        poses = _poses(poses, flat=True)
         r, c, nr, s = C.c_void_p(), C.c_void_p(), C.c_uint64(), ConsistencySummary()
         self._chk(lib().hfpf_depth_consistency(self._h, C.byref(o), C.byref(d), C.c_void_p(frames.ctypes.data) if frames.size else None, stride, n,
                                                _p(poses) if poses.size else None, C.byref(r) if rows else None, C.byref(c), C.byref(nr), C.byref(s)))
-        try:
-            out = np.empty(nr.value, ROW_DTYPE) if rows else None
-            cons = np.empty(nr.value, ROW_CONSISTENCY_DTYPE)
-            if nr.value:
-                if rows:
-                    C.memmove(out.ctypes.data, r.value, out.nbytes)
-                C.memmove(cons.ctypes.data, c.value, cons.nbytes)
-        finally:
-            lib().hfpf_free_consistency(r, c)
+        out, cons = _copy_out([(r, nr.value, ROW_DTYPE, rows), (c, nr.value, ROW_CONSISTENCY_DTYPE, True)], lib().hfpf_free_consistency, r, c)
         return out, cons, s.as_dict()
 
     def depth_consistency_device(self, desc, dev_depth, depth_frame_stride, n_frames, poses, opts=None, rows=True, **kw):
         """The same for frames resident in HBM (hfpf_depth_consistency_device): (rows pointer or 0, cons pointer, n_rows, summary
         dict); free the pointers with device_free (they are 0 without rows)."""
-        o = opts if opts is not None else consistency_opts(**kw)
-        poses = np.ascontiguousarray(poses, np.float64).reshape(-1)
+        o = _or(opts, consistency_opts, **kw)
+        poses = _poses(poses, flat=True)
         r, c, nr, s = C.c_void_p(), C.c_void_p(), C.c_uint64(), ConsistencySummary()
         self._chk(lib().hfpf_depth_consistency_device(self._h, C.byref(o), C.byref(desc), C.c_void_p(dev_depth), int(depth_frame_stride), int(n_frames),
                                                       _p(poses) if poses.size else None, C.byref(r) if rows else None, C.byref(c), C.byref(nr),
@@ -1461,9 +1379,9 @@ class OccupancyGrid:
     def raycast(self, rays, pose, opts=None, **kw):
         """First surface crossing of each ray (hfpf_raycast).  rays: (n, 6) float32 (origin, direction) in the camera frame or RAY_DTYPE
         records in pageable memory; pose = camera -> fusion frame 3x4.  Keywords as raycast_opts().  Returns RAY_HIT_DTYPE hits."""
-        o = opts if opts is not None else raycast_opts(**kw)
+        o = _or(opts, raycast_opts, **kw)
         rays = _rays(rays)
-        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        pose = _pose12(pose)
         hits = np.empty(len(rays), RAY_HIT_DTYPE)
         self._chk(lib().hfpf_raycast(self._h, C.byref(o), _p(rays) if len(rays) else None, len(rays), _p(pose), _p(hits)))
         return hits
@@ -1471,25 +1389,17 @@ class OccupancyGrid:
     def raycast_device(self, dev_rays, n_rays, pose, dev_hits=0, opts=None, **kw):
         """The same for rays resident in HBM (hfpf_raycast_device).  With dev_hits the hits stay in that device buffer and None is
         returned; otherwise they go to a scratch device buffer and come back as raycast() returns them."""
-        o = opts if opts is not None else raycast_opts(**kw)
-        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
-        own = not dev_hits
-        if own:
-            dev_hits = self.device_alloc(max(1, n_rays) * RAY_HIT_DTYPE.itemsize)
-        try:
-            self._chk(lib().hfpf_raycast_device(self._h, C.byref(o), C.c_void_p(dev_rays), n_rays, _p(pose), C.c_void_p(dev_hits)))
-            if not own:
-                return None
-            return self.device_download(dev_hits, n_rays * RAY_HIT_DTYPE.itemsize).view(RAY_HIT_DTYPE)
-        finally:
-            if own:
-                self.device_free(dev_hits)
+        o = _or(opts, raycast_opts, **kw)
+        pose = _pose12(pose)
+        got = self._device_results(n_rays, [(dev_hits, RAY_HIT_DTYPE, True)], lambda hits: self._chk(
+            lib().hfpf_raycast_device(self._h, C.byref(o), C.c_void_p(dev_rays), n_rays, _p(pose), C.c_void_p(hits))))
+        return got and got[0]
 
     def raycast_view(self, pose, K, width, height, opts=None, **kw):
         """The view rays of one pinhole view (hfpf_raycast_view): K = (fx, fy, cx, cy), t_range = (z_near, z_far); hit i = pixel
         (i % width, i // width), its t the camera-frame depth.  Returns (height, width) RAY_HIT_DTYPE hits."""
-        o = opts if opts is not None else raycast_opts(**kw)
-        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        o = _or(opts, raycast_opts, **kw)
+        pose = _pose12(pose)
         hits = np.empty((int(height), int(width)), RAY_HIT_DTYPE)
         self._chk(lib().hfpf_raycast_view(self._h, C.byref(o), int(width), int(height), float(K[0]), float(K[1]), float(K[2]), float(K[3]),
                                           _p(pose), _p(hits) if hits.size else None))
@@ -1498,28 +1408,20 @@ class OccupancyGrid:
     def raycast_views_device(self, poses, K, width, height, dev_hits=0, opts=None, **kw):
         """A batch of views into HBM (hfpf_raycast_view_device): poses (n, 3, 4); view v's hits start v * width * height behind
         dev_hits.  Without dev_hits they go to a scratch device buffer and come back as (n, height, width) hits."""
-        o = opts if opts is not None else raycast_opts(**kw)
-        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12)
+        o = _or(opts, raycast_opts, **kw)
+        poses = _poses(poses)
         n = len(poses) * int(width) * int(height)
-        own = not dev_hits
-        if own:
-            dev_hits = self.device_alloc(max(1, n) * RAY_HIT_DTYPE.itemsize)
-        try:
-            self._chk(lib().hfpf_raycast_view_device(self._h, C.byref(o), int(width), int(height), float(K[0]), float(K[1]), float(K[2]),
-                                                     float(K[3]), len(poses), _p(poses) if len(poses) else None, C.c_void_p(dev_hits)))
-            if not own:
-                return None
-            return self.device_download(dev_hits, n * RAY_HIT_DTYPE.itemsize).view(RAY_HIT_DTYPE).reshape(len(poses), int(height), int(width))
-        finally:
-            if own:
-                self.device_free(dev_hits)
+        got = self._device_results(n, [(dev_hits, RAY_HIT_DTYPE, True)], lambda hits: self._chk(lib().hfpf_raycast_view_device(
+            self._h, C.byref(o), int(width), int(height), float(K[0]), float(K[1]), float(K[2]), float(K[3]), len(poses),
+            _p(poses) if len(poses) else None, C.c_void_p(hits))))
+        return got and got[0].reshape(len(poses), int(height), int(width))
 
     def query_depth(self, depth, pose, K, depth_scale=0.001, opts=None, radius=1, min_count=0.0, max_distance=float("inf"), zclip=False,
                     rows=True):
         """Query every pixel of one depth image in pageable memory (hfpf_query_depth); hit / row i = pixel (i % W, i // W)."""
         d = _image_desc(depth, K, None, None, depth_scale)
-        o = opts if opts is not None else query_opts(radius, min_count, max_distance, zclip)
-        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        o = _or(opts, query_opts, radius, min_count, max_distance, zclip)
+        pose = _pose12(pose)
         n = d.width * d.height
         hits = np.empty(n, QUERY_HIT_DTYPE)
         out = np.empty(n, ROW_DTYPE) if rows else None
@@ -1600,9 +1502,8 @@ class OccupancyGrid:
         one uint32 word per entry, `select_stride` bytes apart (default: its item size); entry i is selected iff (word & select_mask)
         == select_value.  device=True (hfpf_hide_voxels_device): voxels and select are device pointers, and n, voxel_stride (and
         select_stride with a selector) are required."""
-        o = opts if opts is not None else hide_opts(op, select_mask, select_value)
-        res = HideResult()
-        res.struct_size = C.sizeof(HideResult)
+        o = _or(opts, hide_opts, op, select_mask, select_value)
+        res = _sized(HideResult)
         if device:
             self._chk(lib().hfpf_hide_voxels_device(self._h, C.byref(o), C.c_void_p(voxels), int(n), int(voxel_stride), C.c_void_p(select) if select else None,
                                                     int(select_stride or 0), C.byref(res)))
@@ -1622,8 +1523,7 @@ class OccupancyGrid:
     def hide_box(self, lo, hi, op="hide"):
         """hfpf_hide_box: op on the voxels lo..hi (inclusive indices; the box may reach outside the grid); returns the counts."""
         lo3, hi3 = np.ascontiguousarray(lo, dtype=np.int32).reshape(3), np.ascontiguousarray(hi, dtype=np.int32).reshape(3)
-        res = HideResult()
-        res.struct_size = C.sizeof(HideResult)
+        res = _sized(HideResult)
         self._chk(lib().hfpf_hide_box(self._h, HIDE_OPS.get(op, op), _p(lo3), _p(hi3), C.byref(res)))
         return res.as_dict()
 
@@ -1702,7 +1602,7 @@ class OccupancyGrid:
 
     # -- leaf probes (tests) --
     def probe_points(self, pose, xyz):
-        pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(12)
+        pose = _pose12(pose)
         xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
         n = xyz.shape[0]
         q = np.zeros((n, 3), np.float32)
