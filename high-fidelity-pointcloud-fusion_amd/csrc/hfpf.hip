@@ -2355,7 +2355,7 @@ static void* host_result_alloc(size_t want)
 }
 
 // The arrays a read-out returns, up to three (extract, mesh, components, compare_mesh).  result_alloc gives each a device array;
-// the kernels fill them; the device form hands them to the caller, the host form downloads them with result_to_host.
+// the kernels fill them; result_deliver hands them to the caller of the device form and downloads them for the host form's.
 struct ResultSet {
     struct Array {
         size_t bytes = 0;
@@ -2427,6 +2427,14 @@ static int result_to_host(hfpf_handle* h, const ResultSet& set, const char* what
     }
     if (!ok) return fail(h, HFPF_ERR_CAPACITY, "%s: host allocation of the result failed", what);
     return fail(h, HFPF_ERR_HIP, "%s copy: %s", what, hipGetErrorString(e));
+}
+
+// The delivery of both forms, behind ResultSet::keep.  Device form: the device arrays themselves, now the caller's (out[i]; NULL for an
+// absent or a never-added one).  Host form: result_to_host; an empty set downloads nothing and gives three NULLs.
+static int result_deliver(hfpf_handle* h, const ResultSet& set, bool on_device, const char* what, void* out[3])
+{
+    for (int i = 0; i < 3; i++) out[i] = on_device ? set.a[i].dev : nullptr;
+    return on_device || set.n == 0 ? HFPF_OK : result_to_host(h, set, what, out);
 }
 
 // Shared tail of extract: `stats` are the (possibly merged) sums to finalise.
@@ -3249,14 +3257,13 @@ static int mesh_dilate_locked(hfpf_handle* h, const DevBuf& in, uint64_t n_in, i
     return unique_keys_locked(h, sorted, n, unique, n_unique, n_out);
 }
 
-// Validated arguments in, under the lock.  The row set, the cube set (the rows' cells dilated by 1) and the corner set (the cubes
-// dilated by (0, +1)), the corner samples, the edge marks and triangle counts, two scans, then vertices and triangles into device
-// arrays (*out: vertices, triangles).  The read-backs are the sizes between the stages.
+// Validated arguments in, under the lock, behind the read prologue.  The row set, the cube set (the rows' cells dilated by 1) and the
+// corner set (the cubes dilated by (0, +1)), the corner samples, the edge marks and triangle counts, two scans, then vertices and
+// triangles into device arrays (*out: vertices, triangles).  The read-backs are the sizes between the stages.
 static int mesh_locked(hfpf_handle* h, const hfpf_mesh_opts* o, bool on_device, ResultSet* out, uint64_t* n_verts, uint64_t* n_tris)
 {
     *n_verts = 0, *n_tris = 0;  // (*out: the caller's fresh, empty set)
     int rc;
-    if ((rc = local_read_prologue_locked(h, "mesh"))) return rc;
     for (int a = 0; a < 3; a++)
         if (h->g.dim[a] >= (1 << kMeshKeyBits) - 1) return fail(h, HFPF_ERR_CAPACITY, "mesh: a grid dimension of 2^21 - 1 cells or more");
     RowSet rs;
@@ -3319,33 +3326,37 @@ static int mesh_locked(hfpf_handle* h, const hfpf_mesh_opts* o, bool on_device, 
     return HFPF_OK;
 }
 
-int hfpf_extract_mesh_device(hfpf_handle* h, const hfpf_mesh_opts* o, hfpf_mesh_vertex** dev_verts, uint64_t* n_verts, uint32_t** dev_tris,
-                             uint64_t* n_tris)
-{
-    if (!h) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    if (!mesh_opts_ok(o) || !dev_verts || !n_verts || !dev_tris || !n_tris) return fail(h, HFPF_ERR_BAD_ARG, "mesh: invalid options or a NULL output");
-    ResultSet set;
-    const int rc = mesh_locked(h, o, true, &set, n_verts, n_tris);
-    *dev_verts = (hfpf_mesh_vertex*)set.a[0].dev, *dev_tris = (uint32_t*)set.a[1].dev;
-    return rc;
-}
-
-int hfpf_extract_mesh(hfpf_handle* h, const hfpf_mesh_opts* o, hfpf_mesh_vertex** verts, uint64_t* n_verts, uint32_t** tris, uint64_t* n_tris)
+// The read-outs below come as a host and a `_device` form of one *_common function, all written alike: the NULL handle, the lock,
+// the argument check, the read prologue, the call's own empty case, the mesh on the device (mesh_on_device_locked), *_locked into
+// locals, result_deliver, and only then the caller's outputs.  WHEN THE CALLER'S MEMORY IS WRITTEN: never on HFPF_ERR_BAD_ARG; on
+// any other failure compare, align, cover, section, plan and consistency write nothing either, while mesh and components leave the
+// NULL / 0 they set behind the argument check; every output is filled on success.
+static int extract_mesh_common(hfpf_handle* h, const hfpf_mesh_opts* o, bool on_device, hfpf_mesh_vertex** verts, uint64_t* n_verts, uint32_t** tris,
+                               uint64_t* n_tris)
 {
     if (!h) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
     if (!mesh_opts_ok(o) || !verts || !n_verts || !tris || !n_tris) return fail(h, HFPF_ERR_BAD_ARG, "mesh: invalid options or a NULL output");
     *verts = nullptr, *tris = nullptr, *n_verts = 0, *n_tris = 0;
-    ResultSet set;
+    ResultSet set;  // empty (nv = 0) without a vertex or without a triangle: NULL arrays, no download
     uint64_t nv = 0, nt = 0;
+    void* out[3];
     int rc;
-    if ((rc = mesh_locked(h, o, false, &set, &nv, &nt))) return rc;
-    if (nv == 0) return HFPF_OK;
-    void* host[3];
-    if ((rc = result_to_host(h, set, "mesh", host))) return rc;
-    *verts = (hfpf_mesh_vertex*)host[0], *tris = (uint32_t*)host[1], *n_verts = nv, *n_tris = nt;
+    if ((rc = local_read_prologue_locked(h, "mesh")) || (rc = mesh_locked(h, o, on_device, &set, &nv, &nt))) return rc;
+    if ((rc = result_deliver(h, set, on_device, "mesh", out))) return rc;
+    *verts = (hfpf_mesh_vertex*)out[0], *tris = (uint32_t*)out[1], *n_verts = nv, *n_tris = nt;
     return HFPF_OK;
+}
+
+int hfpf_extract_mesh_device(hfpf_handle* h, const hfpf_mesh_opts* o, hfpf_mesh_vertex** dev_verts, uint64_t* n_verts, uint32_t** dev_tris,
+                             uint64_t* n_tris)
+{
+    return extract_mesh_common(h, o, true, dev_verts, n_verts, dev_tris, n_tris);
+}
+
+int hfpf_extract_mesh(hfpf_handle* h, const hfpf_mesh_opts* o, hfpf_mesh_vertex** verts, uint64_t* n_verts, uint32_t** tris, uint64_t* n_tris)
+{
+    return extract_mesh_common(h, o, false, verts, n_verts, tris, n_tris);
 }
 
 void hfpf_free_mesh(hfpf_mesh_vertex* verts, uint32_t* tris)
@@ -3362,16 +3373,15 @@ int hfpf_check_component_opts(const hfpf_component_opts* o)
     return std::isfinite(o->min_normal_dot) && o->min_normal_dot >= -2.0 && o->min_normal_dot <= 1.0 ? HFPF_OK : HFPF_ERR_BAD_ARG;
 }
 
-// Validated arguments in, under the lock.  The row set, then (timed as kernel id 6) index, link, flatten, the scan of the root flags,
-// the per-component reductions, the keep flags (through a sort for keep_largest), the scans of kept components and kept rows, and
-// the compaction into *out (rows -- absent without want_rows --, labels, component records).  The read-backs are the sizes between
-// the stages.
+// Validated arguments in, under the lock, behind the read prologue.  The row set, then (timed as kernel id 6) index, link, flatten,
+// the scan of the root flags, the per-component reductions, the keep flags (through a sort for keep_largest), the scans of kept
+// components and kept rows, and the compaction into *out (rows -- absent without want_rows --, labels, component records).  The
+// read-backs are the sizes between the stages.
 static int components_locked(hfpf_handle* h, const hfpf_component_opts* o, bool on_device, bool want_rows, ResultSet* out, uint64_t* n_rows,
                              uint64_t* n_comps)
 {
     *n_rows = 0, *n_comps = 0;  // (*out: the caller's fresh, empty set)
     int rc;
-    if ((rc = local_read_prologue_locked(h, "components"))) return rc;
     RowSet rs;
     const ExtractOpts opt{o->min_count, -1, 0};  // the compare of hfpf_extract_filtered, 0 keeps all
     if ((rc = build_rows_locked(h, h->t.stats, opt, &rs))) return rc;
@@ -3443,37 +3453,35 @@ static bool component_args_ok(const hfpf_component_opts* o, const void* labels, 
     return hfpf_check_component_opts(o) == HFPF_OK && labels && n_rows && comps && n_comps;
 }
 
-int hfpf_extract_components_device(hfpf_handle* h, const hfpf_component_opts* o, hfpf_row** dev_rows, uint32_t** dev_labels, uint64_t* n_rows,
-                                   hfpf_component** dev_comps, uint64_t* n_comps)
-{
-    if (!h) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    if (!component_args_ok(o, dev_labels, n_rows, dev_comps, n_comps)) return fail(h, HFPF_ERR_BAD_ARG, "components: invalid options or a NULL output");
-    ResultSet set;
-    const int rc = components_locked(h, o, true, dev_rows != nullptr, &set, n_rows, n_comps);
-    if (dev_rows) *dev_rows = (hfpf_row*)set.a[0].dev;
-    *dev_labels = (uint32_t*)set.a[1].dev, *dev_comps = (hfpf_component*)set.a[2].dev;
-    return rc;
-}
-
-int hfpf_extract_components(hfpf_handle* h, const hfpf_component_opts* o, hfpf_row** rows, uint32_t** labels, uint64_t* n_rows, hfpf_component** comps,
-                            uint64_t* n_comps)
+static int extract_components_common(hfpf_handle* h, const hfpf_component_opts* o, bool on_device, hfpf_row** rows, uint32_t** labels, uint64_t* n_rows,
+                                     hfpf_component** comps, uint64_t* n_comps)
 {
     if (!h) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
     if (!component_args_ok(o, labels, n_rows, comps, n_comps)) return fail(h, HFPF_ERR_BAD_ARG, "components: invalid options or a NULL output");
     if (rows) *rows = nullptr;
     *labels = nullptr, *comps = nullptr, *n_rows = 0, *n_comps = 0;
-    ResultSet set;
+    ResultSet set;  // empty (nc = 0) without a row or without a kept component: NULL arrays, no download
     uint64_t nr = 0, nc = 0;
+    void* out[3];
     int rc;
-    if ((rc = components_locked(h, o, false, rows != nullptr, &set, &nr, &nc))) return rc;
-    if (nc == 0) return HFPF_OK;
-    void* host[3];
-    if ((rc = result_to_host(h, set, "components", host))) return rc;
-    if (rows) *rows = (hfpf_row*)host[0];
-    *labels = (uint32_t*)host[1], *comps = (hfpf_component*)host[2], *n_rows = nr, *n_comps = nc;
+    if ((rc = local_read_prologue_locked(h, "components")) || (rc = components_locked(h, o, on_device, rows != nullptr, &set, &nr, &nc))) return rc;
+    if ((rc = result_deliver(h, set, on_device, "components", out))) return rc;
+    if (rows) *rows = (hfpf_row*)out[0];
+    *labels = (uint32_t*)out[1], *comps = (hfpf_component*)out[2], *n_rows = nr, *n_comps = nc;
     return HFPF_OK;
+}
+
+int hfpf_extract_components_device(hfpf_handle* h, const hfpf_component_opts* o, hfpf_row** dev_rows, uint32_t** dev_labels, uint64_t* n_rows,
+                                   hfpf_component** dev_comps, uint64_t* n_comps)
+{
+    return extract_components_common(h, o, true, dev_rows, dev_labels, n_rows, dev_comps, n_comps);
+}
+
+int hfpf_extract_components(hfpf_handle* h, const hfpf_component_opts* o, hfpf_row** rows, uint32_t** labels, uint64_t* n_rows, hfpf_component** comps,
+                            uint64_t* n_comps)
+{
+    return extract_components_common(h, o, false, rows, labels, n_rows, comps, n_comps);
 }
 
 void hfpf_free_components(hfpf_row* rows, uint32_t* labels, hfpf_component* comps)
@@ -3708,42 +3716,53 @@ static int upload_mesh_locked(hfpf_handle* h, const char* what, const MeshRef& h
     return HFPF_OK;
 }
 
+// The mesh input of both forms (*d): the caller's device mesh where it is, the caller's host mesh through upload_mesh_locked.
+static int mesh_on_device_locked(hfpf_handle* h, const char* what, const MeshRef& m, bool on_device, MeshRef* d)
+{
+    if (!on_device) return upload_mesh_locked(h, what, m, d);
+    *d = m;
+    return HFPF_OK;
+}
+
+// A fault in the arguments of the calls that take a mesh: "<name>: <fault>", from the device form "<name>_device: <fault>".
+static int args_fail(hfpf_handle* h, const char* name, bool on_device, const char* fault)
+{
+    return fail(h, HFPF_ERR_BAD_ARG, "%s%s: %s", name, on_device ? "_device" : "", fault);
+}
+
+// A mesh without triangles is a mesh like any other here: the host form uploads it (the scratch request shows in device_bytes) and
+// the call runs with it.  Without rows the set stays empty: NULL arrays beside the summary, no download.
+static int compare_common(hfpf_handle* h, const hfpf_deviation_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris,
+                          uint64_t n_tris, const double* pose, bool on_device, hfpf_row** rows, hfpf_deviation** dev, uint64_t* n_rows,
+                          hfpf_deviation_summary* summary)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    const MeshRef m{verts, n_verts, vertex_stride, tris, n_tris};
+    if (const char* f = compare_args_fault(h, o, m, pose, dev, n_rows, summary, on_device)) return args_fail(h, "compare_mesh", on_device, f);
+    MeshRef d;
+    ResultSet set;
+    hfpf_deviation_summary s;
+    void* out[3];
+    int rc;
+    if ((rc = local_read_prologue_locked(h, "compare_mesh")) || (rc = mesh_on_device_locked(h, "compare_mesh", m, on_device, &d))) return rc;
+    if ((rc = compare_locked(h, o, d, pose, on_device, rows != nullptr, &set, &s)) || (rc = result_deliver(h, set, on_device, "compare_mesh", out))) return rc;
+    if (rows) *rows = (hfpf_row*)out[0];
+    *dev = (hfpf_deviation*)out[1], *n_rows = s.n_rows, *summary = s;
+    return HFPF_OK;
+}
+
 int hfpf_compare_mesh_device(hfpf_handle* h, const hfpf_deviation_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride,
                              const uint32_t* dev_tris, uint64_t n_tris, const double* pose_3x4, hfpf_row** dev_rows, hfpf_deviation** dev_dev,
                              uint64_t* n_rows, hfpf_deviation_summary* summary)
 {
-    if (!h) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    const MeshRef m{dev_verts, n_verts, vertex_stride, dev_tris, n_tris};
-    if (const char* f = compare_args_fault(h, o, m, pose_3x4, dev_dev, n_rows, summary, true)) return fail(h, HFPF_ERR_BAD_ARG, "compare_mesh_device: %s", f);
-    if (int rc = local_read_prologue_locked(h, "compare_mesh")) return rc;
-    ResultSet set;
-    hfpf_deviation_summary s;
-    if (int rc = compare_locked(h, o, m, pose_3x4, true, dev_rows != nullptr, &set, &s)) return rc;
-    if (dev_rows) *dev_rows = (hfpf_row*)set.a[0].dev;
-    *dev_dev = (hfpf_deviation*)set.a[1].dev, *n_rows = s.n_rows, *summary = s;
-    return HFPF_OK;
+    return compare_common(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, true, dev_rows, dev_dev, n_rows, summary);
 }
 
 int hfpf_compare_mesh(hfpf_handle* h, const hfpf_deviation_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris,
                       uint64_t n_tris, const double* pose_3x4, hfpf_row** rows, hfpf_deviation** dev, uint64_t* n_rows, hfpf_deviation_summary* summary)
 {
-    if (!h) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    const MeshRef m{verts, n_verts, vertex_stride, tris, n_tris};
-    if (const char* f = compare_args_fault(h, o, m, pose_3x4, dev, n_rows, summary, false)) return fail(h, HFPF_ERR_BAD_ARG, "compare_mesh: %s", f);
-    if (int rc = local_read_prologue_locked(h, "compare_mesh")) return rc;
-    MeshRef d;
-    if (int rc = upload_mesh_locked(h, "compare_mesh", m, &d)) return rc;
-    ResultSet set;
-    hfpf_deviation_summary s;
-    if (int rc = compare_locked(h, o, d, pose_3x4, false, rows != nullptr, &set, &s)) return rc;
-    void* host[3] = {nullptr, nullptr, nullptr};
-    if (s.n_rows)
-        if (int rc = result_to_host(h, set, "compare_mesh", host)) return rc;
-    if (rows) *rows = (hfpf_row*)host[0];
-    *dev = (hfpf_deviation*)host[1], *n_rows = s.n_rows, *summary = s;
-    return HFPF_OK;
+    return compare_common(h, o, verts, n_verts, vertex_stride, tris, n_tris, pose_3x4, false, rows, dev, n_rows, summary);
 }
 
 void hfpf_free_deviation(hfpf_row* rows, hfpf_deviation* dev)
@@ -3804,28 +3823,30 @@ static const char* align_args_fault(const hfpf_handle* h, const hfpf_align_opts*
     return nullptr;
 }
 
-int hfpf_align_mesh_device(hfpf_handle* h, const hfpf_align_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* dev_tris,
-                           uint64_t n_tris, const double* pose_3x4, hfpf_align_result* result)
+// As in a compare, a mesh without triangles is uploaded and run.  No arrays: align_locked writes *result last, once the fit has ended.
+static int align_common(hfpf_handle* h, const hfpf_align_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
+                        const double* pose, bool on_device, hfpf_align_result* result)
 {
     if (!h) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
-    const MeshRef m{dev_verts, n_verts, vertex_stride, dev_tris, n_tris};
-    if (const char* f = align_args_fault(h, o, m, pose_3x4, result, true)) return fail(h, HFPF_ERR_BAD_ARG, "align_mesh_device: %s", f);
-    if (int rc = local_read_prologue_locked(h, "align_mesh")) return rc;
-    return align_locked(h, o, m, pose_3x4, result);
+    const MeshRef m{verts, n_verts, vertex_stride, tris, n_tris};
+    if (const char* f = align_args_fault(h, o, m, pose, result, on_device)) return args_fail(h, "align_mesh", on_device, f);
+    MeshRef d;
+    int rc;
+    if ((rc = local_read_prologue_locked(h, "align_mesh")) || (rc = mesh_on_device_locked(h, "align_mesh", m, on_device, &d))) return rc;
+    return align_locked(h, o, d, pose, result);
+}
+
+int hfpf_align_mesh_device(hfpf_handle* h, const hfpf_align_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* dev_tris,
+                           uint64_t n_tris, const double* pose_3x4, hfpf_align_result* result)
+{
+    return align_common(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, true, result);
 }
 
 int hfpf_align_mesh(hfpf_handle* h, const hfpf_align_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
                     const double* pose_3x4, hfpf_align_result* result)
 {
-    if (!h) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    const MeshRef m{verts, n_verts, vertex_stride, tris, n_tris};
-    if (const char* f = align_args_fault(h, o, m, pose_3x4, result, false)) return fail(h, HFPF_ERR_BAD_ARG, "align_mesh: %s", f);
-    if (int rc = local_read_prologue_locked(h, "align_mesh")) return rc;
-    MeshRef d;
-    if (int rc = upload_mesh_locked(h, "align_mesh", m, &d)) return rc;
-    return align_locked(h, o, d, pose_3x4, result);
+    return align_common(h, o, verts, n_verts, vertex_stride, tris, n_tris, pose_3x4, false, result);
 }
 
 // ---- coverage of a triangle mesh by the model (include/hfpf.h) ----------------------------------------------------------------
@@ -3930,43 +3951,37 @@ static const char* cover_args_fault(const hfpf_cover_opts* o, const MeshRef& m, 
     return nullptr;
 }
 
-int hfpf_cover_mesh_device(hfpf_handle* h, const hfpf_cover_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* dev_tris,
-                           uint64_t n_tris, const double* pose_3x4, hfpf_tri_coverage** dev_cov, hfpf_coverage_summary* summary)
+// A mesh without triangles is answered here, in front of any upload or scratch request: a zeroed summary and a NULL cov.
+static int cover_common(hfpf_handle* h, const hfpf_cover_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
+                        const double* pose, bool on_device, hfpf_tri_coverage** cov, hfpf_coverage_summary* summary)
 {
     if (!h) return HFPF_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(h->mtx);
-    const MeshRef m{dev_verts, n_verts, vertex_stride, dev_tris, n_tris};
-    if (const char* f = cover_args_fault(o, m, pose_3x4, dev_cov, summary, true)) return fail(h, HFPF_ERR_BAD_ARG, "cover_mesh_device: %s", f);
-    if (int rc = local_read_prologue_locked(h, "cover_mesh")) return rc;
+    const MeshRef m{verts, n_verts, vertex_stride, tris, n_tris};
+    if (const char* f = cover_args_fault(o, m, pose, cov, summary, on_device)) return args_fail(h, "cover_mesh", on_device, f);
+    MeshRef d;
     ResultSet set;
-    hfpf_coverage_summary s;
-    memset(&s, 0, sizeof s);
-    if (n_tris)
-        if (int rc = cover_locked(h, o, m, pose_3x4, true, &set, &s)) return rc;
-    *dev_cov = (hfpf_tri_coverage*)set.a[0].dev, *summary = s;
+    hfpf_coverage_summary s{};
+    void* out[3];
+    int rc;
+    if ((rc = local_read_prologue_locked(h, "cover_mesh"))) return rc;
+    if (n_tris && (rc = mesh_on_device_locked(h, "cover_mesh", m, on_device, &d))) return rc;
+    if (n_tris && (rc = cover_locked(h, o, d, pose, on_device, &set, &s))) return rc;
+    if ((rc = result_deliver(h, set, on_device, "cover_mesh", out))) return rc;
+    *cov = (hfpf_tri_coverage*)out[0], *summary = s;
     return HFPF_OK;
+}
+
+int hfpf_cover_mesh_device(hfpf_handle* h, const hfpf_cover_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* dev_tris,
+                           uint64_t n_tris, const double* pose_3x4, hfpf_tri_coverage** dev_cov, hfpf_coverage_summary* summary)
+{
+    return cover_common(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, true, dev_cov, summary);
 }
 
 int hfpf_cover_mesh(hfpf_handle* h, const hfpf_cover_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
                     const double* pose_3x4, hfpf_tri_coverage** cov, hfpf_coverage_summary* summary)
 {
-    if (!h) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    const MeshRef m{verts, n_verts, vertex_stride, tris, n_tris};
-    if (const char* f = cover_args_fault(o, m, pose_3x4, cov, summary, false)) return fail(h, HFPF_ERR_BAD_ARG, "cover_mesh: %s", f);
-    if (int rc = local_read_prologue_locked(h, "cover_mesh")) return rc;
-    hfpf_coverage_summary s;
-    memset(&s, 0, sizeof s);
-    void* host[3] = {nullptr, nullptr, nullptr};
-    if (n_tris) {
-        MeshRef d;
-        if (int rc = upload_mesh_locked(h, "cover_mesh", m, &d)) return rc;
-        ResultSet set;
-        if (int rc = cover_locked(h, o, d, pose_3x4, false, &set, &s)) return rc;
-        if (int rc = result_to_host(h, set, "cover_mesh", host)) return rc;
-    }
-    *cov = (hfpf_tri_coverage*)host[0], *summary = s;
-    return HFPF_OK;
+    return cover_common(h, o, verts, n_verts, vertex_stride, tris, n_tris, pose_3x4, false, cov, summary);
 }
 
 void hfpf_free_coverage(hfpf_tri_coverage* cov) { free(cov); }
@@ -3986,20 +4001,16 @@ struct SectionCounts {
     uint64_t n_points = 0, n_segments = 0, n_contours = 0;
 };
 
-// Validated arguments in, the mesh on the device, under the lock.  The transformed vertices (compare's kernel); the count pass over
-// every chunk of planes; the read-back of the per-plane counts (the cap test, the bases and the size of everything behind); the emit
-// pass; the two sorts and the unique; points, links, flatten, the scan of the root flags (the number of contours: only now can the
-// three result arrays be sized, so the kernels behind write every record once and whole); label, measure, finish; the read-back of
-// the plane records.  recs and S are the caller's locals: nothing of the caller's is written before the call has succeeded.  Not timed:
-// hfpf_get_kernel_time has no id for it (tools/section_rate.py times it with events of its own).
+// Validated arguments in, the mesh on the device, n_tris > 0, under the lock.  The transformed vertices (compare's kernel); the count
+// pass over every chunk of planes; the read-back of the per-plane counts (the cap test, the bases and the size of everything behind);
+// the emit pass; the two sorts and the unique; points, links, flatten, the scan of the root flags (the number of contours: only now
+// can the three result arrays be sized, so the kernels behind write every record once and whole); label, measure, finish; the
+// read-back of the plane records.  *out, *nout, *recs (n_planes records) and *S are section_common's locals, empty and zeroed.  Not
+// timed: hfpf_get_kernel_time has no id for it (tools/section_rate.py times it with events of its own).
 static int section_locked(hfpf_handle* h, const MeshRef& m, const double* pose, const double* planes, uint32_t n_planes, bool on_device, ResultSet* out,
                           SectionCounts* nout, std::vector<hfpf_section_plane>* recs, hfpf_section_summary* S)
 {
     int rc;
-    memset(S, 0, sizeof *S);
-    recs->assign(n_planes, hfpf_section_plane{});
-    *nout = SectionCounts{};
-    if (m.n_tris == 0) return HFPF_OK;
     const uint64_t P1 = (uint64_t)n_planes + 1;
     double* V; SecCounters* ctr; double* d_planes; SecPlane* d_recs;
     uint32_t *count, *first;  // per plane (n_planes + 1 entries each): the crossings (later the emit pass's cursor) and their exclusive sums
@@ -4123,26 +4134,42 @@ static const char* section_args_fault(const hfpf_section_opts* o, const MeshRef&
     return nullptr;
 }
 
+// A mesh without triangles is answered here, in front of any upload or scratch request: zeroed records and summary and NULL arrays.
+// Without planes, or when no plane meets a triangle, section_locked leaves the set empty: NULL arrays beside the counts, no download.
+static int section_common(hfpf_handle* h, const hfpf_section_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
+                          const double* pose, const double* planes, uint32_t n_planes, bool on_device, hfpf_section_point** points, uint64_t* n_points,
+                          hfpf_section_segment** segments, uint64_t* n_segments, hfpf_section_contour** contours, uint64_t* n_contours, hfpf_section_plane* plane_recs,
+                          hfpf_section_summary* summary)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    const MeshRef m{verts, n_verts, vertex_stride, tris, n_tris};
+    const void* const outs[8] = {points, n_points, segments, n_segments, contours, n_contours, summary, plane_recs};
+    if (const char* f = section_args_fault(o, m, pose, planes, n_planes, outs, on_device)) return args_fail(h, "section_mesh", on_device, f);
+    MeshRef d;
+    ResultSet set;
+    SectionCounts n;
+    std::vector<hfpf_section_plane> recs(n_planes, hfpf_section_plane{});
+    hfpf_section_summary s{};
+    void* out[3];
+    int rc;
+    if ((rc = local_read_prologue_locked(h, "section_mesh"))) return rc;
+    if (n_tris && (rc = mesh_on_device_locked(h, "section_mesh", m, on_device, &d))) return rc;
+    if (n_tris && (rc = section_locked(h, d, pose, planes, n_planes, on_device, &set, &n, &recs, &s))) return rc;
+    if ((rc = result_deliver(h, set, on_device, "section_mesh", out))) return rc;
+    *points = (hfpf_section_point*)out[0], *segments = (hfpf_section_segment*)out[1], *contours = (hfpf_section_contour*)out[2];
+    *n_points = n.n_points, *n_segments = n.n_segments, *n_contours = n.n_contours, *summary = s;
+    if (n_planes) memcpy(plane_recs, recs.data(), (size_t)n_planes * sizeof(hfpf_section_plane));
+    return HFPF_OK;
+}
+
 int hfpf_section_mesh_device(hfpf_handle* h, const hfpf_section_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* dev_tris,
                              uint64_t n_tris, const double* pose_3x4, const double* planes, uint32_t n_planes, hfpf_section_point** dev_points, uint64_t* n_points,
                              hfpf_section_segment** dev_segments, uint64_t* n_segments, hfpf_section_contour** dev_contours, uint64_t* n_contours,
                              hfpf_section_plane* plane_recs, hfpf_section_summary* summary)
 {
-    if (!h) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    const MeshRef m{dev_verts, n_verts, vertex_stride, dev_tris, n_tris};
-    const void* const outs[8] = {dev_points, n_points, dev_segments, n_segments, dev_contours, n_contours, summary, plane_recs};
-    if (const char* f = section_args_fault(o, m, pose_3x4, planes, n_planes, outs, true)) return fail(h, HFPF_ERR_BAD_ARG, "section_mesh_device: %s", f);
-    if (int rc = local_read_prologue_locked(h, "section_mesh")) return rc;
-    ResultSet set;
-    SectionCounts n;
-    std::vector<hfpf_section_plane> recs;
-    hfpf_section_summary s;
-    if (int rc = section_locked(h, m, pose_3x4, planes, n_planes, true, &set, &n, &recs, &s)) return rc;
-    *dev_points = (hfpf_section_point*)set.a[0].dev, *dev_segments = (hfpf_section_segment*)set.a[1].dev, *dev_contours = (hfpf_section_contour*)set.a[2].dev;
-    *n_points = n.n_points, *n_segments = n.n_segments, *n_contours = n.n_contours, *summary = s;
-    if (n_planes) memcpy(plane_recs, recs.data(), (size_t)n_planes * sizeof(hfpf_section_plane));
-    return HFPF_OK;
+    return section_common(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, planes, n_planes, true, dev_points, n_points, dev_segments, n_segments,
+                          dev_contours, n_contours, plane_recs, summary);
 }
 
 int hfpf_section_mesh(hfpf_handle* h, const hfpf_section_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
@@ -4150,29 +4177,8 @@ int hfpf_section_mesh(hfpf_handle* h, const hfpf_section_opts* o, const void* ve
                       hfpf_section_segment** segments, uint64_t* n_segments, hfpf_section_contour** contours, uint64_t* n_contours, hfpf_section_plane* plane_recs,
                       hfpf_section_summary* summary)
 {
-    if (!h) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    const MeshRef m{verts, n_verts, vertex_stride, tris, n_tris};
-    const void* const outs[8] = {points, n_points, segments, n_segments, contours, n_contours, summary, plane_recs};
-    if (const char* f = section_args_fault(o, m, pose_3x4, planes, n_planes, outs, false)) return fail(h, HFPF_ERR_BAD_ARG, "section_mesh: %s", f);
-    if (int rc = local_read_prologue_locked(h, "section_mesh")) return rc;
-    SectionCounts n;
-    std::vector<hfpf_section_plane> recs(n_planes, hfpf_section_plane{});
-    hfpf_section_summary s;
-    memset(&s, 0, sizeof s);
-    void* host[3] = {nullptr, nullptr, nullptr};
-    if (n_tris) {
-        MeshRef d;
-        if (int rc = upload_mesh_locked(h, "section_mesh", m, &d)) return rc;
-        ResultSet set;
-        if (int rc = section_locked(h, d, pose_3x4, planes, n_planes, false, &set, &n, &recs, &s)) return rc;
-        if (n.n_segments)
-            if (int rc = result_to_host(h, set, "section_mesh", host)) return rc;
-    }
-    *points = (hfpf_section_point*)host[0], *segments = (hfpf_section_segment*)host[1], *contours = (hfpf_section_contour*)host[2];
-    *n_points = n.n_points, *n_segments = n.n_segments, *n_contours = n.n_contours, *summary = s;
-    if (n_planes) memcpy(plane_recs, recs.data(), (size_t)n_planes * sizeof(hfpf_section_plane));
-    return HFPF_OK;
+    return section_common(h, o, verts, n_verts, vertex_stride, tris, n_tris, pose_3x4, planes, n_planes, false, points, n_points, segments, n_segments, contours,
+                          n_contours, plane_recs, summary);
 }
 
 void hfpf_free_section(hfpf_section_point* points, hfpf_section_segment* segments, hfpf_section_contour* contours)
@@ -4336,50 +4342,44 @@ static void plan_empty(uint32_t n_views, hfpf_view_score* scores, hfpf_plan_summ
     }
 }
 
+// A mesh without triangles is answered here, in front of any upload or scratch request: plan_empty and a NULL plan.  The scores and
+// the summary are computed into locals in both forms, so they reach the caller only when the records have too.
+static int plan_common(hfpf_handle* h, const hfpf_plan_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
+                       const double* pose, const double* poses, uint32_t n_views, bool on_device, hfpf_view_score* scores, hfpf_tri_plan** plan,
+                       hfpf_plan_summary* summary)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    const MeshRef m{verts, n_verts, vertex_stride, tris, n_tris};
+    if (const char* f = plan_args_fault(o, m, pose, poses, n_views, scores, summary, on_device)) return args_fail(h, "plan_views", on_device, f);
+    MeshRef d;
+    ResultSet set;
+    std::vector<hfpf_view_score> sc(std::max<uint32_t>(n_views, 1));
+    hfpf_plan_summary s;
+    void* out[3];
+    int rc;
+    if ((rc = local_read_prologue_locked(h, "plan_views"))) return rc;
+    if (n_tris == 0) plan_empty(n_views, sc.data(), &s);
+    if (n_tris && (rc = mesh_on_device_locked(h, "plan_views", m, on_device, &d))) return rc;
+    if (n_tris && (rc = plan_locked(h, o, d, pose, poses, n_views, on_device, plan != nullptr, &set, sc.data(), &s))) return rc;
+    if ((rc = result_deliver(h, set, on_device, "plan_views", out))) return rc;
+    if (n_views) memcpy(scores, sc.data(), (size_t)n_views * sizeof(hfpf_view_score));
+    *summary = s;
+    if (plan) *plan = (hfpf_tri_plan*)out[0];
+    return HFPF_OK;
+}
+
 int hfpf_plan_views_device(hfpf_handle* h, const hfpf_plan_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* dev_tris,
                            uint64_t n_tris, const double* pose_3x4, const double* poses, uint32_t n_views, hfpf_view_score* scores, hfpf_tri_plan** dev_plan,
                            hfpf_plan_summary* summary)
 {
-    if (!h) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    const MeshRef m{dev_verts, n_verts, vertex_stride, dev_tris, n_tris};
-    if (const char* f = plan_args_fault(o, m, pose_3x4, poses, n_views, scores, summary, true)) return fail(h, HFPF_ERR_BAD_ARG, "plan_views_device: %s", f);
-    if (int rc = local_read_prologue_locked(h, "plan_views")) return rc;
-    ResultSet set;
-    if (n_tris) {
-        if (int rc = plan_locked(h, o, m, pose_3x4, poses, n_views, true, dev_plan != nullptr, &set, scores, summary)) return rc;
-    } else {
-        plan_empty(n_views, scores, summary);
-    }
-    if (dev_plan) *dev_plan = (hfpf_tri_plan*)set.a[0].dev;
-    return HFPF_OK;
+    return plan_common(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, poses, n_views, true, scores, dev_plan, summary);
 }
 
 int hfpf_plan_views(hfpf_handle* h, const hfpf_plan_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
                     const double* pose_3x4, const double* poses, uint32_t n_views, hfpf_view_score* scores, hfpf_tri_plan** plan, hfpf_plan_summary* summary)
 {
-    if (!h) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    const MeshRef m{verts, n_verts, vertex_stride, tris, n_tris};
-    if (const char* f = plan_args_fault(o, m, pose_3x4, poses, n_views, scores, summary, false)) return fail(h, HFPF_ERR_BAD_ARG, "plan_views: %s", f);
-    if (int rc = local_read_prologue_locked(h, "plan_views")) return rc;
-    void* host[3] = {nullptr, nullptr, nullptr};
-    if (n_tris) {
-        MeshRef d;
-        if (int rc = upload_mesh_locked(h, "plan_views", m, &d)) return rc;
-        // the scores and the summary reach the caller only when the records have too: a failed download writes nothing
-        std::vector<hfpf_view_score> sc(std::max<uint32_t>(n_views, 1));
-        hfpf_plan_summary s;
-        ResultSet set;
-        if (int rc = plan_locked(h, o, d, pose_3x4, poses, n_views, false, plan != nullptr, &set, sc.data(), &s)) return rc;
-        if (int rc = result_to_host(h, set, "plan_views", host)) return rc;
-        if (n_views) memcpy(scores, sc.data(), (size_t)n_views * sizeof(hfpf_view_score));
-        *summary = s;
-    } else {
-        plan_empty(n_views, scores, summary);
-    }
-    if (plan) *plan = (hfpf_tri_plan*)host[0];
-    return HFPF_OK;
+    return plan_common(h, o, verts, n_verts, vertex_stride, tris, n_tris, pose_3x4, poses, n_views, false, scores, plan, summary);
 }
 
 void hfpf_free_plan(hfpf_tri_plan* plan) { free(plan); }
@@ -4537,45 +4537,39 @@ static int consistency_locked(hfpf_handle* h, const hfpf_consistency_opts* o, co
     return HFPF_OK;
 }
 
+static int consistency_common(hfpf_handle* h, const hfpf_consistency_opts* o, const hfpf_depth_image* desc, const void* depth, uint64_t depth_frame_stride,
+                              uint32_t n_frames, const double* poses, bool on_device, hfpf_row** rows, hfpf_row_consistency** cons, uint64_t* n_rows,
+                              hfpf_consistency_summary* summary)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    const ConsFrames f{depth, depth_frame_stride, n_frames, poses};
+    DepthSpec ds;
+    if (int rc = consistency_args_locked(h, o, desc, f, cons, n_rows, summary, on_device, &ds)) return rc;
+    ResultSet set;  // empty (nk = 0) without a row, or with none kept: NULL arrays beside the summary, no download
+    uint64_t nk = 0;
+    hfpf_consistency_summary s;
+    void* out[3];
+    int rc;
+    if ((rc = local_read_prologue_locked(h, "depth_consistency")) || (rc = consistency_locked(h, o, desc, ds, f, on_device, rows != nullptr, &set, &nk, &s))) return rc;
+    if ((rc = result_deliver(h, set, on_device, "depth_consistency", out))) return rc;
+    if (rows) *rows = (hfpf_row*)out[0];
+    *cons = (hfpf_row_consistency*)out[1], *n_rows = nk, *summary = s;
+    return HFPF_OK;
+}
+
 int hfpf_depth_consistency_device(hfpf_handle* h, const hfpf_consistency_opts* o, const hfpf_depth_image* desc, const void* dev_depth,
                                   uint64_t depth_frame_stride, uint32_t n_frames, const double* poses, hfpf_row** dev_rows,
                                   hfpf_row_consistency** dev_cons, uint64_t* n_rows, hfpf_consistency_summary* summary)
 {
-    if (!h) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    const ConsFrames f{dev_depth, depth_frame_stride, n_frames, poses};
-    DepthSpec ds;
-    if (int rc = consistency_args_locked(h, o, desc, f, dev_cons, n_rows, summary, true, &ds)) return rc;
-    if (int rc = local_read_prologue_locked(h, "depth_consistency")) return rc;
-    ResultSet set;
-    uint64_t nk = 0;
-    hfpf_consistency_summary s;
-    if (int rc = consistency_locked(h, o, desc, ds, f, true, dev_rows != nullptr, &set, &nk, &s)) return rc;
-    if (dev_rows) *dev_rows = (hfpf_row*)set.a[0].dev;
-    *dev_cons = (hfpf_row_consistency*)set.a[1].dev, *n_rows = nk, *summary = s;
-    return HFPF_OK;
+    return consistency_common(h, o, desc, dev_depth, depth_frame_stride, n_frames, poses, true, dev_rows, dev_cons, n_rows, summary);
 }
 
 int hfpf_depth_consistency(hfpf_handle* h, const hfpf_consistency_opts* o, const hfpf_depth_image* desc, const void* depth, uint64_t depth_frame_stride,
                            uint32_t n_frames, const double* poses, hfpf_row** rows, hfpf_row_consistency** cons, uint64_t* n_rows,
                            hfpf_consistency_summary* summary)
 {
-    if (!h) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    const ConsFrames f{depth, depth_frame_stride, n_frames, poses};
-    DepthSpec ds;
-    if (int rc = consistency_args_locked(h, o, desc, f, cons, n_rows, summary, false, &ds)) return rc;
-    if (int rc = local_read_prologue_locked(h, "depth_consistency")) return rc;
-    ResultSet set;
-    uint64_t nk = 0;
-    hfpf_consistency_summary s;
-    if (int rc = consistency_locked(h, o, desc, ds, f, false, rows != nullptr, &set, &nk, &s)) return rc;
-    void* host[3] = {nullptr, nullptr, nullptr};
-    if (nk)
-        if (int rc = result_to_host(h, set, "depth_consistency", host)) return rc;
-    if (rows) *rows = (hfpf_row*)host[0];
-    *cons = (hfpf_row_consistency*)host[1], *n_rows = nk, *summary = s;
-    return HFPF_OK;
+    return consistency_common(h, o, desc, depth, depth_frame_stride, n_frames, poses, false, rows, cons, n_rows, summary);
 }
 
 void hfpf_free_consistency(hfpf_row* rows, hfpf_row_consistency* cons)

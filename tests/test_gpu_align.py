@@ -11,7 +11,7 @@ import pytest
 
 import align_ref as A
 from gpu_support import (ALIGN_KW, ALIGN_MD, ALIGN_START, BBOX, DEPTH_CAPS, IDENT, RES, align_device, counters, deviation_csv,
-                         deviation_summary_csv, fitted, grid, node_feed, node_grid, run, same_align, same_deviation)
+                         deviation_summary_csv, fitted, grid, node_feed, node_grid, run, same_align, same_deviation, uploaded)
 from scenes import DepthScene
 
 pytestmark = pytest.mark.gpu
@@ -153,6 +153,51 @@ def test_bad_arguments_leave_the_handle_usable(hfpf_mod, session):
     assert L.hfpf_align_mesh(h, C.byref(H.align_opts(**ALIGN_KW)), v.ctypes.data, len(v), 32, t.ctypes.data, len(t), pose.ctypes.data, C.byref(wrong)) == -2
     assert call(o=opts(compare=dict(max_distance=32 * RES), max_iterations=1), n_tris=64) == 0  # the bound itself is legal
     assert res.iterations == 1 and res.rows_sampled == len(rows)
+    assert g.extract().tobytes() == rows.tobytes()
+
+
+def test_both_forms_on_an_empty_handle_and_the_rejections_of_the_device_form(hfpf_mod, session):
+    """What test_too_few_empty_mesh_and_empty_handle and test_bad_arguments_leave_the_handle_usable ask of the host form, through
+    hfpf_align_mesh_device: TOO_FEW at the start pose on a handle without rows, and a rejected call leaves the result as it was."""
+    H = hfpf_mod
+    sc, g, rows, verts, tris = session
+    v, t = np.ascontiguousarray(verts[:64]), np.array([[0, 1, 2], [3, 4, 5], [6, 6, 7]], np.uint32)
+    with grid(hfpf_mod) as fresh:
+        host, dev = fresh.align_mesh(v, t, ALIGN_START, **ALIGN_KW), align_device(fresh, v, t, ALIGN_START, **ALIGN_KW)
+        _too_few(host, ALIGN_START, 0)
+        same_align(dev, host, "an empty handle, device form")
+        assert dev["rows_sampled"] == 0
+    L = H.lib()
+    pose = np.ascontiguousarray(ALIGN_START, np.float64).reshape(12)
+    bad_pose = pose.copy()
+    bad_pose[5] = np.nan
+    res = H.align_result()
+    res.iterations, res.rows_sampled, res.rms = 0x5A5A, 0x5A5A5A5A, 90.0
+    marker = bytes(res)
+
+    def opts(compare=None, **kw):
+        o = H.align_opts(**ALIGN_KW)
+        for k, val in kw.items():
+            setattr(o, k, val)
+        for k, val in (compare or {}).items():
+            setattr(o.compare, k, val)
+        return o
+
+    wrong = H.align_result()
+    wrong.struct_size = 400
+    with uploaded(g, v, t) as (dv, dt):
+        def call(o=None, verts=dv, n_verts=len(v), stride=32, tris=dt, n_tris=len(t), pose=pose.ctypes.data, result=res):
+            o = o if o is not None else H.align_opts(**ALIGN_KW)
+            return L.hfpf_align_mesh_device(g._h, C.byref(o), verts, n_verts, stride, tris, n_tris, pose, C.byref(result) if result is not None else None)
+
+        faults = [dict(pose=bad_pose.ctypes.data), dict(pose=None), dict(o=opts(stride=0)), dict(o=opts(max_iterations=65)),
+                  dict(o=opts(compare=dict(max_distance=33 * RES))), dict(result=None), dict(result=wrong), dict(o=opts(min_inliers=5)), dict(o=opts(flags=2)),
+                  dict(o=opts(reserved=1)), dict(o=opts(compare=dict(struct_size=24))), dict(stride=8), dict(stride=14), dict(verts=None), dict(tris=None),
+                  dict(n_verts=2 ** 32 - 1), dict(n_tris=2 ** 32 - 1), dict(verts=dv + 2), dict(tris=dt + 1)]
+        for kw in faults:
+            assert call(**kw) == -2, kw
+            assert bytes(res) == marker, "a rejected call writes nothing: %r" % (kw,)
+        assert call(o=opts(max_iterations=1)) == 0 and res.iterations == 1 and res.rows_sampled == len(rows)  # the handle is still usable
     assert g.extract().tobytes() == rows.tobytes()
 
 

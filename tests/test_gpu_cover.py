@@ -243,6 +243,70 @@ def test_empty_and_edge_cases_leave_the_handle_usable(hfpf_mod, session):
     assert g.extract().tobytes() == rows.tobytes()
 
 
+def test_both_forms_return_the_documented_empties(hfpf_mod, session):
+    """A mesh without triangles (vertices or none) and an empty handle: the same records and the same summary out of either form."""
+    sc, g, rows, occ, verts, tris = session
+    kw = dict(radius=2, max_distance=2 * RES, spacing=RES)
+    no_tris = np.zeros((0, 3), np.uint32)
+    with uploaded(g, verts) as (dv,):
+        pairs = [(g.cover_mesh(verts, no_tris, IDENT, **kw), g.cover_mesh(dv, 0, IDENT, device=True, n_verts=len(verts), vertex_stride=32, n_tris=0, **kw)),
+                 (g.cover_mesh(np.zeros((0, 3), np.float32), no_tris, IDENT), g.cover_mesh(0, 0, IDENT, device=True, n_verts=0, vertex_stride=12, n_tris=0))]
+    for host, dev in pairs:
+        assert len(host[0]) == 0 and dev[0] == 0 and host[1] == dev[1] and all(x == 0 for x in host[1].values())
+    c = [float(np.median(rows[k])) for k in ("x", "y", "z")]
+    tv = np.array([c, [c[0] + 0.01, c[1], c[2]], [c[0], c[1] + 0.01, c[2]], [c[0], c[1], c[2] + 0.01]], np.float32)
+    tt = np.array([[0, 1, 2], [0, 1, 3], [1, 1, 2]], np.uint32)  # the last one is invalid
+    with grid(hfpf_mod) as fresh:
+        ref = V.cover(np.zeros(0, hfpf_mod.ROW_DTYPE), np.zeros((0, 3), np.int32), tv, 12, tt, IDENT, tuple(fresh.cfg.bbox), fresh.dims[1], **kw)
+        host = fresh.cover_mesh(tv, tt, IDENT, **kw)
+        with uploaded(fresh, tv, tt) as (dv, dt):
+            dev = cover_device(fresh, hfpf_mod, dv, len(tv), 12, dt, len(tt), IDENT, **kw)
+        same_coverage(host, ref, "an empty handle, host form")
+        assert host[0].tobytes() == dev[0].tobytes() and host[1] == dev[1] and host[1]["n_covered"] == 0 < host[1]["n_in_bbox"]
+
+
+def test_every_rejection_of_the_device_form_leaves_the_outputs_untouched(hfpf_mod, session):
+    """The BAD_ARGs of test_empty_and_edge_cases_leave_the_handle_usable again, through hfpf_cover_mesh_device on a mesh in HBM."""
+    H = hfpf_mod
+    sc, g, rows, occ, verts, tris = session
+    L = H.lib()
+    kw = dict(radius=2, max_distance=2 * RES, spacing=RES)
+    c = [float(np.median(rows[k])) for k in ("x", "y", "z")]
+    v, t = np.array([c, [c[0] + 0.01, c[1], c[2]], [c[0], c[1] + 0.01, c[2]]], np.float32), np.array([[0, 1, 2]], np.uint32)
+    pose = np.ascontiguousarray(IDENT, np.float64).reshape(12)
+    bad_pose = pose.copy()
+    bad_pose[7] = np.inf
+    out = dict(c=C.c_void_p(0x5A), s=H.CoverageSummary())
+    C.memset(C.byref(out["s"]), 0x5A, C.sizeof(out["s"]))
+    untouched = bytes(out["s"])
+
+    def opts(**fields):
+        o = H.cover_opts(**kw)
+        for k, val in fields.items():
+            setattr(o, k, val)
+        return o
+
+    with uploaded(g, v, t) as (dv, dt):
+        def call(o=None, verts=dv, n_verts=3, stride=12, tris=dt, n_tris=1, pose=pose.ctypes.data, cov=True, s=True):
+            o = o if o is not None else H.cover_opts(**kw)
+            return L.hfpf_cover_mesh_device(g._h, C.byref(o), verts, n_verts, stride, tris, n_tris, pose, C.byref(out["c"]) if cov else None,
+                                            C.byref(out["s"]) if s else None)
+
+        faults = [dict(o=opts(struct_size=48)), dict(o=opts(flags=2)), dict(o=opts(reserved=7)), dict(o=opts(radius=0)), dict(o=opts(radius=5)),
+                  dict(o=opts(max_subdivision=0)), dict(o=opts(max_subdivision=65)), dict(o=opts(min_count=float("nan"))),
+                  dict(o=opts(max_distance=0.0)), dict(o=opts(max_distance=1.5)), dict(o=opts(max_distance=float("inf"))),
+                  dict(o=opts(spacing=0.0)), dict(o=opts(spacing=float("inf"))), dict(o=opts(min_normal_dot=-2.5)), dict(o=opts(min_normal_dot=1.5)),
+                  dict(o=opts(min_normal_dot=float("nan"))),
+                  dict(pose=None), dict(pose=bad_pose.ctypes.data), dict(stride=8), dict(stride=14), dict(verts=None), dict(tris=None),
+                  dict(n_verts=2 ** 32 - 1), dict(n_tris=2 ** 32 - 1), dict(cov=False), dict(s=False), dict(verts=dv + 2), dict(tris=dt + 1)]
+        for f in faults:
+            assert call(**f) == -2, f
+            assert out["c"].value == 0x5A and bytes(out["s"]) == untouched, "a rejected call writes nothing: %r" % (f,)
+        assert call() == 0 and out["c"].value not in (None, 0x5A) and out["s"].n_tris_valid == 1  # the handle is still usable
+        g.device_free(out["c"].value)
+    assert g.extract().tobytes() == rows.tobytes()
+
+
 # ---- 8. a cover is read-only, and a restored handle answers the same ---------------------------------------------------------
 
 def test_cover_is_read_only_and_survives_a_restore(hfpf_mod, session):

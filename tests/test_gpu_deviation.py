@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import deviation_ref as D
-from gpu_support import BBOX, IDENT, RES, compare_device, counters, grid, run, same_deviation
+from gpu_support import BBOX, IDENT, RES, compare_device, counters, grid, run, same_deviation, uploaded
 from scenes import DepthScene
 
 pytestmark = pytest.mark.gpu
@@ -222,6 +222,71 @@ def test_empty_and_edge_cases_leave_the_handle_usable(hfpf_mod, session):
         L.hfpf_free_deviation(out["r"], out["d"])
     finally:
         g.device_free(dv), g.device_free(dt)
+    assert g.extract().tobytes() == rows.tobytes()
+
+
+def test_both_forms_return_the_documented_empties(hfpf_mod, session):
+    """A mesh without triangles, a gate no row passes and an empty handle: the same arrays and the same summary out of either form."""
+    sc, g, rows, verts, tris = session
+    none = g.compare_mesh(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint32), IDENT, rows=True)
+    dev = compare_device(g, hfpf_mod, 0, 0, 12, 0, 0, IDENT, rows=True)
+    assert none[0].tobytes() == dev[0].tobytes() == rows.tobytes() and none[1].tobytes() == dev[1].tobytes() and none[2] == dev[2]
+    assert none[2]["n_rows"] == len(rows) and none[2]["n_found"] == 0 and none[2]["n_tris_valid"] == none[2]["n_tris_invalid"] == 0
+    _not_found(none[1])
+    with grid(hfpf_mod) as fresh:
+        for h, kw, what in ((g, dict(min_count=1e9), "no row passes the gate"), (fresh, dict(), "an empty handle")):
+            host = h.compare_mesh(verts, tris, IDENT, rows=True, **kw)
+            with uploaded(h, verts, tris) as (hv, ht):
+                r, d, nr, s = h.compare_mesh(hv, ht, IDENT, device=True, rows=True, n_verts=len(verts), vertex_stride=32, n_tris=len(tris), **kw)
+            assert (r, d, nr) == (0, 0, 0) and len(host[0]) == len(host[1]) == 0 and s == host[2], what
+            assert s["n_rows"] == s["n_found"] == 0 and s["n_tris_valid"] + s["n_tris_invalid"] == len(tris), what
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_every_rejection_leaves_the_outputs_untouched(hfpf_mod, session, device):
+    """Every HFPF_ERR_BAD_ARG of either form, with each output preset to a sentinel and compared after the call."""
+    H = hfpf_mod
+    sc, g, rows, verts, tris = session
+    L = H.lib()
+    v, t = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], np.float32), np.array([[0, 1, 2]], np.uint32)
+    pose = np.ascontiguousarray(IDENT, np.float64).reshape(12)
+    bad_pose = pose.copy()
+    bad_pose[7] = np.inf
+    fn = L.hfpf_compare_mesh_device if device else L.hfpf_compare_mesh
+
+    def opts(**kw):
+        o = H.deviation_opts()
+        for k, val in kw.items():
+            setattr(o, k, val)
+        return o
+
+    with uploaded(g, v, t) as (dv, dt):
+        mv, mt = (dv, dt) if device else (v.ctypes.data, t.ctypes.data)
+
+        def call(o=None, verts=mv, n_verts=3, stride=12, tris=mt, n_tris=1, pose=pose.ctypes.data, rows=True, dev=True, n=True, s=True):
+            o = o if o is not None else H.deviation_opts()
+            out = dict(r=C.c_void_p(0x5A), d=C.c_void_p(0x5A), n=C.c_uint64(0x5A), s=H.DeviationSummary())
+            C.memset(C.byref(out["s"]), 0x5A, C.sizeof(out["s"]))
+            rc = fn(g._h, C.byref(o), verts, n_verts, stride, tris, n_tris, pose, C.byref(out["r"]) if rows else None, C.byref(out["d"]) if dev else None,
+                    C.byref(out["n"]) if n else None, C.byref(out["s"]) if s else None)
+            untouched = (out["r"].value, out["d"].value, out["n"].value) == (0x5A, 0x5A, 0x5A) and bytes(out["s"]) == b"\x5a" * C.sizeof(out["s"])
+            return rc, untouched, out
+
+        faults = [dict(o=opts(max_distance=33 * RES)), dict(o=opts(struct_size=24)), dict(o=opts(flags=2)), dict(o=opts(reserved=7)),
+                  dict(o=opts(min_count=float("nan"))), dict(o=opts(max_distance=0.0)), dict(o=opts(max_distance=float("inf"))),
+                  dict(pose=None), dict(pose=bad_pose.ctypes.data), dict(stride=8), dict(stride=14), dict(verts=None), dict(tris=None),
+                  dict(n_verts=2 ** 32 - 1), dict(n_tris=2 ** 32 - 1), dict(dev=False), dict(n=False), dict(s=False)]
+        if device:
+            faults += [dict(verts=dv + 2), dict(tris=dt + 1)]
+        for kw in faults:
+            rc, untouched, _ = call(**kw)
+            assert rc == -2 and untouched, kw
+        rc, untouched, out = call(rows=False)  # and the unspoiled call works on the same handle, without the optional rows
+        assert rc == 0 and not untouched and out["r"].value == 0x5A and out["n"].value == len(rows) == out["s"].n_rows
+        if device:
+            g.device_free(out["d"].value)
+        else:
+            L.hfpf_free_deviation(None, out["d"])
     assert g.extract().tobytes() == rows.tobytes()
 
 

@@ -202,6 +202,30 @@ def test_fresh_handle_and_frames_without_a_clean_pass(hfpf_mod, session):
         S.same_plan(fresh.plan_views(verts, tris, S.ring(6), IDENT, **S.VIEW, **kw), ref, "frames but no clean pass")
 
 
+def test_both_forms_return_the_documented_empties(hfpf_mod, session):
+    """No triangles (nothing to plan: every rank -1, a summary that holds n_views alone, no records), no views, and a handle without
+    rows: the same bytes out of either form."""
+    sc, g, rows, occ, verts, tris = session
+    kw = dict(S.MAIN, spacing=4 * RES)
+    none = np.zeros((0, 12))
+    with uploaded(g, verts, tris) as (dv, dt):
+        host = g.plan_views(verts, np.zeros((0, 3), np.uint32), S.ring(3), IDENT, **S.VIEW, **kw)
+        dev = g.plan_views(dv, 0, S.ring(3), IDENT, device=True, n_verts=len(verts), vertex_stride=12, n_tris=0, **S.VIEW, **kw)
+        assert len(host[1]) == 0 and dev[1] == 0 and host[0].tobytes() == dev[0].tobytes() and host[2] == dev[2]
+        assert (host[0]["rank"] == -1).all() and not any(host[0][k].any() for k in host[0].dtype.names if k != "rank")
+        s = host[2]
+        assert s["n_views"] == 3 and not any(s[k] for k in s if k not in ("n_views", "coverage")) and not any(s["coverage"].values())
+        host = g.plan_views(verts, tris, none, IDENT, **S.VIEW, **kw)
+        dev = S.plan_device(g, hfpf_mod, dv, len(verts), 12, dt, len(tris), none, IDENT, **S.VIEW, **kw)
+        assert len(dev[0]) == 0 and dev[1].tobytes() == host[1].tobytes() and dev[2] == host[2] and host[2]["n_targets"] > 0 == host[2]["n_selected"]
+    with grid(hfpf_mod) as fresh:
+        host = fresh.plan_views(verts, tris, S.ring(6), IDENT, **S.VIEW, **kw)
+        with uploaded(fresh, verts, tris) as (dv, dt):
+            dev = S.plan_device(fresh, hfpf_mod, dv, len(verts), 12, dt, len(tris), S.ring(6), IDENT, **S.VIEW, **kw)
+        assert dev[0].tobytes() == host[0].tobytes() and dev[1].tobytes() == host[1].tobytes() and dev[2] == host[2]
+        assert host[2]["n_targets"] == host[2]["coverage"]["n_in_bbox"] > 0, "every in-box sample is a target"
+
+
 # ---- 6. refusals ----------------------------------------------------------------------------------------------------------------------
 
 def test_every_bad_arg_writes_nothing_and_leaves_the_handle_usable(hfpf_mod, session):
@@ -211,7 +235,7 @@ def test_every_bad_arg_writes_nothing_and_leaves_the_handle_usable(hfpf_mod, ses
     v, t = S.chips(3)
     pose = np.ascontiguousarray(IDENT, np.float64).reshape(12)
     poses = np.ascontiguousarray(S.ring(2), np.float64).reshape(-1)
-    out = dict(sc=np.frombuffer(b"\xab" * 80, H.VIEW_SCORE_DTYPE).copy(), t=C.c_void_p(), s=H.PlanSummary())
+    out = dict(sc=np.frombuffer(b"\xab" * 80, H.VIEW_SCORE_DTYPE).copy(), t=C.c_void_p(0xAB), s=H.PlanSummary())
     C.memset(C.byref(out["s"]), 0xAB, C.sizeof(out["s"]))
     untouched = (out["sc"].tobytes(), bytes(out["s"]))
     dv, dt = g.device_alloc(64), g.device_alloc(64)
@@ -248,9 +272,9 @@ def test_every_bad_arg_writes_nothing_and_leaves_the_handle_usable(hfpf_mod, ses
                   dict(pose=None), dict(pose=bad_pose.ctypes.data), dict(stride=8), dict(stride=14), dict(verts=None), dict(tris=None),
                   dict(n_verts=2 ** 32 - 1), dict(n_tris=2 ** 32 - 1), dict(scores=False), dict(s=False),
                   dict(device=True, verts=dv + 2, tris=dt), dict(device=True, verts=dv, tris=dt + 1)]
-        for f in faults:
+        for f in faults + [dict(dict(device=True, verts=dv, tris=dt), **f) for f in faults if "device" not in f]:  # each through both forms
             assert call(**f) == -2, f
-            assert out["t"].value is None and (out["sc"].tobytes(), bytes(out["s"])) == untouched, "a rejected call writes nothing: %r" % (f,)
+            assert out["t"].value == 0xAB and (out["sc"].tobytes(), bytes(out["s"])) == untouched, "a rejected call writes nothing: %r" % (f,)
         assert call(poses=None, n_views=0) == 0 and out["s"].n_targets == 3 and out["s"].n_views == 0, "no views need no poses"
         L.hfpf_free_plan(out["t"])
         out["t"] = C.c_void_p()
@@ -275,6 +299,16 @@ def test_capacity_refusal_at_2_to_the_35_pairs(hfpf_mod):
         with pytest.raises(hfpf_mod.HfpfError) as e:
             fresh.plan_views(verts, tris, poses, IDENT, tri_plan=False, **S.SMALL_VIEW, **kw)
         assert e.value.code == -3 and str(n * 4096) in str(e.value) and "4096 views" in str(e.value), str(e.value)
+        # the device form refuses alike, and neither the scores nor the summary nor the records' pointer is written
+        o, pose, flat = hfpf_mod.plan_opts(**S.SMALL_VIEW, **kw), np.ascontiguousarray(IDENT, np.float64).reshape(12), np.ascontiguousarray(poses).reshape(-1)
+        out_sc, out_t, out_s = np.full(4096 * hfpf_mod.VIEW_SCORE_DTYPE.itemsize, 0xAB, np.uint8), C.c_void_p(0xAB), hfpf_mod.PlanSummary()
+        C.memset(C.byref(out_s), 0xAB, C.sizeof(out_s))
+        with uploaded(fresh, verts, tris) as (dv, dt):
+            rc = hfpf_mod.lib().hfpf_plan_views_device(fresh._h, C.byref(o), dv, len(verts), 12, dt, n, pose.ctypes.data, flat.ctypes.data, 4096,
+                                                       out_sc.ctypes.data, C.byref(out_t), C.byref(out_s))
+        msg = hfpf_mod.lib().hfpf_last_error(fresh._h).decode()
+        assert rc == -3 and str(n * 4096) in msg and "4096 views" in msg, msg
+        assert (out_sc == 0xAB).all() and out_t.value == 0xAB and bytes(out_s) == b"\xab" * C.sizeof(out_s), "a refused call writes nothing"
         scores, rec, s = fresh.plan_views(verts[:9], tris[:3], poses[:2], IDENT, **S.SMALL_VIEW, **kw)  # the handle stays usable
         assert s["n_targets"] == 3 * 4096 and s["n_views"] == 2
 

@@ -308,6 +308,18 @@ def test_no_planes_and_no_triangles_return_the_documented_empties(hfpf_mod, empt
     assert (p, npt, s, ns, c, nc) == (0, 0, 0, 0, 0, 0) and recs.tobytes() == bytes(64) and summ["n_tris_valid"] == 12
 
 
+def test_the_device_form_returns_the_same_empties(hfpf_mod, empty):
+    """No planes, no triangles and no vertices through hfpf_section_mesh_device: NULL arrays, and the records and the summary of the host form."""
+    verts, tris = S.soup()
+    for v, t, planes, what in ((verts, tris, np.zeros((0, 4)), "no planes"), (CUBE_V, np.zeros((0, 3), np.uint32), S.soup_planes(), "no triangles"),
+                               (np.zeros((0, 3), np.float32), CUBE_T, S.soup_planes(), "no vertices")):
+        host = empty.section_mesh(v, t, S.IDENT, planes)
+        with uploaded(empty, v, t) as (dv, dt):
+            (p, npt), (s, ns), (c, nc), recs, summ = empty.section_mesh_device(dv, len(v), 12, dt, len(t), S.IDENT, planes)
+        assert (p, npt, s, ns, c, nc) == (0, 0, 0, 0, 0, 0) and len(host[0]) == len(host[1]) == len(host[2]) == 0, what
+        assert recs.tobytes() == host[3].tobytes() == bytes(64 * len(planes)) and summ == host[4], what
+
+
 def test_device_bytes_do_not_shrink(hfpf_mod, empty, shapes):
     verts, tris = shapes
     seen = [empty.counters()["device_bytes"]]
