@@ -5237,7 +5237,7 @@ int hfpf_clear(hfpf_handle* h)
 namespace {
 
 constexpr uint32_t kSnapVersion = 1;
-constexpr uint32_t kSnapLayoutRev = 1;  // bump when a table's meaning changes without its shape changing
+constexpr uint32_t kSnapLayoutRev = 2;  // bump when a table's meaning changes without its shape changing (2: the colour log's section is sized by the total)
 constexpr uint64_t kSnapLayoutTag = ((uint64_t)kSnapLayoutRev << 48) | ((uint64_t)kChains << 40) | ((uint64_t)kLogRegions << 32) | ((uint64_t)kStatWords << 24) |
                                     ((uint64_t)sizeof(DepEntry) << 16) | ((uint64_t)C_COUNT << 8) | (uint64_t)kBrickShift;
 constexpr char kSnapMagic[8] = {'H', 'F', 'P', 'F', 'S', 'N', 'A', 'P'};
@@ -5330,10 +5330,12 @@ uint32_t snap_layout(const SnapUsed& u, bool color, uint64_t region_cap, SnapSec
 {
     const uint64_t cells = u.n_bricks * (uint64_t)kBrickCells, rec = u.n_normals ? u.n_normals + 1 : 0;
     uint64_t log_pt = 0, log_rgb = 0;
-    for (int r = 0; r < kLogRegions; r++) {
-        log_pt += u.log_n[r] * sizeof(float4);
-        if (u.log_n[r]) log_rgb += up16(snap_rgb_head(region_cap, r) + u.log_n[r] * 4);
-    }
+    for (int r = 0; r < kLogRegions; r++) log_pt += u.log_n[r] * sizeof(float4);
+    // The colour log's regions are packed one behind the other, each with its head and padded to 16 bytes (snap_spans): how many bytes
+    // that takes depends on how the buffered points spread over the append regions, which is scheduling.  The section is sized by the
+    // total alone -- a head and a padding of less than 16 bytes each per region -- so that a blob's size follows the counts only.
+    if (log_pt) log_rgb = up16(log_pt / sizeof(float4) * 4) + 32ull * kLogRegions;
+    (void)region_cap;
     const struct {
         uint32_t id;
         uint64_t bytes;

@@ -1575,7 +1575,9 @@ int hfpf_get_occupied(hfpf_handle* h, int32_t* xyz, uint64_t cap, uint64_t* n_ou
  * hfpf_stats_export), returns HFPF_ERR_STATE from all four calls: a distributed snapshot is not provided.
  *
  * SIZE.  A snapshot's size follows what the session used, never the pool capacities; unused bytes are zero, so two snapshots of one
- * state are equal byte for byte.  Between a snapshot and the snapshot of its restore elsewhere the payload and its checksum are equal; of
+ * state are equal byte for byte.  The size is a function of the session's counts alone (bricks, records, occupied and pending cells,
+ * registrations, dependant entries, buffered points, frames, whether anything is hidden) -- not of how the buffered points happened
+ * to spread over the point log's append regions, which differs from run to run.  Between a snapshot and the snapshot of its restore elsewhere the payload and its checksum are equal; of
  * the header only `flags` may differ (it records the handle's own flags word, HFPF_FLAG_DIRECT_UPDATE included): capacities are not
  * stored, only the needed ones. */
 #define HFPF_SNAPSHOT_HEADER_BYTES 4096u /* hfpf_snapshot_info needs this many leading bytes of a blob or file */
