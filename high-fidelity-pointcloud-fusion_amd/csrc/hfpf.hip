@@ -18,6 +18,7 @@
 #endif
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <cmath>
 #include <cstdarg>
@@ -363,6 +364,10 @@ struct hfpf_handle {
     // (unsorted, sorted, unique) and the sort's values; per point its f64 coordinates, forest, root, flags, scan and degrees.  The
     // transformed vertices lie in dev_tri, a host mesh in dev_mesh
     DevBuf sec_ctr{bufs}, sec_keys{bufs}, sec_data{bufs};
+    // hfpf_mesh_topology*: the counters and the per-vertex words (marks, root flags and their scan, degrees); the two forests over the
+    // vertices and their roots; the half-edge keys and values (unsorted, sorted) and the per-half-edge words (counts, listed flags and
+    // their scan).  The transformed vertices lie in dev_tri, a host mesh in dev_mesh
+    DevBuf top_verts{bufs}, top_forest{bufs}, top_keys{bufs};
     // hfpf_depth_consistency*: one upload's frames of the host form, the poses, the records / summary / keep marks and their scan
     DevBuf cons_in{bufs}, cons_pose{bufs}, cons_recs{bufs};
     DevBuf hide_in{bufs}, hide_mark{bufs};  // hfpf_hide_*: one upload's entries of the host form (voxels, then selector words); the mark words and the call's counters
@@ -615,8 +620,7 @@ Knobs read_knobs()
     if (const char* nw = getenv("HFPF_CLEAN_NOWAIT")) k.clean_small_nowait = nw[0] != '0';
     if (const char* co = getenv("HFPF_CLEAN_OVERLAP")) k.clean_overlap = co[0] != '0';
     if (const char* er = getenv("HFPF_EARLY_REPLAY")) k.early_replay = er[0] != '0';
-    if (const char* tc = getenv("HFPF_TRACE_CLEAN")) k.trace_clean = tc[0] != '0';
-    if (const char* bs = getenv("HFPF_TEST_BIN_SCALE")) k.test_bin_scale = std::max(0.f, std::min(1.f, (float)atof(bs)));
+    if (const char* tc = getenv("HFPF_TRACE_CLEAN")) k.trace_clean = tc[0] != '0';    if (const char* bs = getenv("HFPF_TEST_BIN_SCALE")) k.test_bin_scale = std::max(0.f, std::min(1.f, (float)atof(bs)));
     const char* ts = getenv("HFPF_TEST_TABLE_SKIP");
     k.test_table_skip = ts && ts[0] == '1';
     const auto limit = [](const char* name, uint64_t& v) {
@@ -2354,8 +2358,9 @@ static void* host_result_alloc(size_t want)
     return malloc(want);
 }
 
-// The arrays a read-out returns, up to three (extract, mesh, components, compare_mesh).  result_alloc gives each a device array;
+// The arrays a read-out returns, up to kResultArrays (four: hfpf_mesh_topology).  result_alloc gives each a device array;
 // the kernels fill them; result_deliver hands them to the caller of the device form and downloads them for the host form's.
+constexpr int kResultArrays = 4;
 struct ResultSet {
     struct Array {
         size_t bytes = 0;
@@ -2363,7 +2368,7 @@ struct ResultSet {
         const void* borrow = nullptr;  // device memory of the handle that already holds the array: the host form downloads from it
         void* dev = nullptr;           // the device array (result_alloc)
     };
-    Array a[3];
+    Array a[kResultArrays];
     int n = 0;
     bool owned = false;  // device form: the arrays are allocations of their own, and this set frees them unless it hands them over
     ResultSet() = default;
@@ -2377,7 +2382,7 @@ struct ResultSet {
     void add(size_t bytes, bool absent = false, const void* borrow = nullptr) { a[n++] = Array{bytes, absent, borrow, nullptr}; }
     void keep(ResultSet* to)  // the success exit: the arrays go to *to, which describes them and frees nothing
     {
-        for (int i = 0; i < 3; i++) to->a[i] = a[i];
+        for (int i = 0; i < kResultArrays; i++) to->a[i] = a[i];
         to->n = n;
         owned = false;
     }
@@ -2398,7 +2403,7 @@ static int result_alloc(hfpf_handle* h, ResultSet& set, bool on_device, const ch
         return HFPF_OK;
     }
     ScratchLayout lay;
-    uint8_t* slice[3] = {nullptr, nullptr, nullptr};
+    uint8_t* slice[kResultArrays] = {};
     for (int i = 0; i < set.n; i++)
         if (!set.a[i].absent && !set.a[i].borrow) lay.add(&slice[i], set.a[i].bytes, 16);
     if (lay.bytes())
@@ -2409,10 +2414,10 @@ static int result_alloc(hfpf_handle* h, ResultSet& set, bool on_device, const ch
 }
 
 // The host form's tail: every present array into pageable memory the caller will free() (out[i]; NULL for an absent one).
-static int result_to_host(hfpf_handle* h, const ResultSet& set, const char* what, void* out[3])
+static int result_to_host(hfpf_handle* h, const ResultSet& set, const char* what, void* out[kResultArrays])
 {
     bool ok = true;
-    for (int i = 0; i < 3; i++) {
+    for (int i = 0; i < kResultArrays; i++) {
         const bool present = i < set.n && !set.a[i].absent;
         out[i] = present ? host_result_alloc(set.a[i].bytes) : nullptr;
         ok = ok && (!present || out[i]);
@@ -2421,7 +2426,7 @@ static int result_to_host(hfpf_handle* h, const ResultSet& set, const char* what
     for (int i = 0; i < set.n && ok && e == hipSuccess; i++)
         if (out[i]) e = download_pageable(h, out[i], set.a[i].dev, set.a[i].bytes);
     if (ok && e == hipSuccess) return HFPF_OK;
-    for (int i = 0; i < 3; i++) {
+    for (int i = 0; i < kResultArrays; i++) {
         free(out[i]);
         out[i] = nullptr;
     }
@@ -2431,9 +2436,9 @@ static int result_to_host(hfpf_handle* h, const ResultSet& set, const char* what
 
 // The delivery of both forms, behind ResultSet::keep.  Device form: the device arrays themselves, now the caller's (out[i]; NULL for an
 // absent or a never-added one).  Host form: result_to_host; an empty set downloads nothing and gives three NULLs.
-static int result_deliver(hfpf_handle* h, const ResultSet& set, bool on_device, const char* what, void* out[3])
+static int result_deliver(hfpf_handle* h, const ResultSet& set, bool on_device, const char* what, void* out[kResultArrays])
 {
-    for (int i = 0; i < 3; i++) out[i] = on_device ? set.a[i].dev : nullptr;
+    for (int i = 0; i < kResultArrays; i++) out[i] = on_device ? set.a[i].dev : nullptr;
     return on_device || set.n == 0 ? HFPF_OK : result_to_host(h, set, what, out);
 }
 
@@ -2452,7 +2457,7 @@ static int extract_locked(hfpf_handle* h, const unsigned long long* stats, const
     if (rs.n == 0) return HFPF_OK;
     ResultSet set;
     set.add(rs.n * sizeof(Row), false, rs.rows);
-    void* host[3];
+    void* host[kResultArrays];
     if ((rc = result_alloc(h, set, false, "extract")) || (rc = result_to_host(h, set, "extract", host))) return rc;
     *rows = (hfpf_row*)host[0];
     *n_rows = rs.n;
@@ -3340,7 +3345,7 @@ static int extract_mesh_common(hfpf_handle* h, const hfpf_mesh_opts* o, bool on_
     *verts = nullptr, *tris = nullptr, *n_verts = 0, *n_tris = 0;
     ResultSet set;  // empty (nv = 0) without a vertex or without a triangle: NULL arrays, no download
     uint64_t nv = 0, nt = 0;
-    void* out[3];
+    void* out[kResultArrays];
     int rc;
     if ((rc = local_read_prologue_locked(h, "mesh")) || (rc = mesh_locked(h, o, on_device, &set, &nv, &nt))) return rc;
     if ((rc = result_deliver(h, set, on_device, "mesh", out))) return rc;
@@ -3463,7 +3468,7 @@ static int extract_components_common(hfpf_handle* h, const hfpf_component_opts* 
     *labels = nullptr, *comps = nullptr, *n_rows = 0, *n_comps = 0;
     ResultSet set;  // empty (nc = 0) without a row or without a kept component: NULL arrays, no download
     uint64_t nr = 0, nc = 0;
-    void* out[3];
+    void* out[kResultArrays];
     int rc;
     if ((rc = local_read_prologue_locked(h, "components")) || (rc = components_locked(h, o, on_device, rows != nullptr, &set, &nr, &nc))) return rc;
     if ((rc = result_deliver(h, set, on_device, "components", out))) return rc;
@@ -3743,7 +3748,7 @@ static int compare_common(hfpf_handle* h, const hfpf_deviation_opts* o, const vo
     MeshRef d;
     ResultSet set;
     hfpf_deviation_summary s;
-    void* out[3];
+    void* out[kResultArrays];
     int rc;
     if ((rc = local_read_prologue_locked(h, "compare_mesh")) || (rc = mesh_on_device_locked(h, "compare_mesh", m, on_device, &d))) return rc;
     if ((rc = compare_locked(h, o, d, pose, on_device, rows != nullptr, &set, &s)) || (rc = result_deliver(h, set, on_device, "compare_mesh", out))) return rc;
@@ -3962,7 +3967,7 @@ static int cover_common(hfpf_handle* h, const hfpf_cover_opts* o, const void* ve
     MeshRef d;
     ResultSet set;
     hfpf_coverage_summary s{};
-    void* out[3];
+    void* out[kResultArrays];
     int rc;
     if ((rc = local_read_prologue_locked(h, "cover_mesh"))) return rc;
     if (n_tris && (rc = mesh_on_device_locked(h, "cover_mesh", m, on_device, &d))) return rc;
@@ -4151,7 +4156,7 @@ static int section_common(hfpf_handle* h, const hfpf_section_opts* o, const void
     SectionCounts n;
     std::vector<hfpf_section_plane> recs(n_planes, hfpf_section_plane{});
     hfpf_section_summary s{};
-    void* out[3];
+    void* out[kResultArrays];
     int rc;
     if ((rc = local_read_prologue_locked(h, "section_mesh"))) return rc;
     if (n_tris && (rc = mesh_on_device_locked(h, "section_mesh", m, on_device, &d))) return rc;
@@ -4186,6 +4191,213 @@ void hfpf_free_section(hfpf_section_point* points, hfpf_section_segment* segment
     free(points);
     free(segments);
     free(contours);
+}
+
+// ---- open edges of a mesh: boundary loops, shells, watertightness (include/hfpf.h) ------------------------------------------------------
+int hfpf_check_topology_opts(const hfpf_topology_opts* o)
+{
+    return o && o->struct_size == sizeof(hfpf_topology_opts) && o->flags == 0 && o->reserved == 0 ? HFPF_OK : HFPF_ERR_BAD_ARG;
+}
+
+static_assert(sizeof(TopEdge) == sizeof(hfpf_topology_edge) && sizeof(TopLoop) == sizeof(hfpf_topology_loop) && sizeof(TopShell) == sizeof(hfpf_topology_shell),
+              "the device records are the public ones");
+static_assert(kTopMaxVerts == HFPF_TOPOLOGY_MAX_VERTS && kTopNone == HFPF_TOPOLOGY_NONE && kTopBoundary == HFPF_TOPOLOGY_BOUNDARY &&
+                  kTopNonManifold == HFPF_TOPOLOGY_NONMANIFOLD && kTopMiswound == HFPF_TOPOLOGY_MISWOUND,
+              "host_plan.hpp restates the header's constants");
+static_assert(kTopLoopClosed == HFPF_TOPOLOGY_LOOP_CLOSED && kTopLoopBranched == HFPF_TOPOLOGY_LOOP_BRANCHED && kTopShellOpen == HFPF_TOPOLOGY_SHELL_OPEN &&
+                  kTopShellNonManifold == HFPF_TOPOLOGY_SHELL_NONMANIFOLD && kTopShellMiswound == HFPF_TOPOLOGY_SHELL_MISWOUND &&
+                  kTopShellWatertight == HFPF_TOPOLOGY_SHELL_WATERTIGHT,
+              "kernels.hpp restates the header's flags");
+
+struct TopologyCounts {
+    uint64_t n_edges = 0, n_loops = 0, n_shells = 0;
+};
+
+// Validated arguments in, the mesh on the device, n_tris > 0, under the lock.  The transformed vertices (compare's kernel); the emit
+// pass (half-edges, vertex marks, the shells' forest); flatten and the scan of the root flags (the number of shells, and the read-back
+// of the triangle counts); the sort; the run walk (classes, degrees, the loops' forest); the scans of the listed flags and of the
+// loops' root flags (only now can the result arrays be sized, so the kernels behind write every record once and whole); the
+// reductions per vertex, triangle, edge and listed edge; finish; the read-back of the counters.  *out, *nout and *S are
+// topology_common's locals, empty and zeroed.  Not timed: hfpf_get_kernel_time has no id for it (tools/topology_rate.py times it
+// with events of its own).
+static int topology_locked(hfpf_handle* h, const MeshRef& m, const double* pose, bool on_device, bool want_tri_shell, ResultSet* out, TopologyCounts* nout,
+                           hfpf_topology_summary* S)
+{
+    int rc;
+    const uint64_t N1 = m.n_verts + 1, n_slots = 3 * m.n_tris;
+    double* V; TopCounters* ctr;
+    uint32_t *used, *flag, *base, *deg_out, *deg_in;     // per vertex (n_verts + 1 entries each); flag and base serve the shells, then the loops
+    uint32_t *parent_s, *parent_l, *root_s, *root_l;     // the shells' and the loops' forest
+    uint64_t *key_in, *key_out;
+    uint32_t *val_in, *val_out, *use, *listed, *lbase;   // per half-edge slot (use, listed and lbase: n_slots + 1 entries)
+    if ((rc = scratch_n(h, h->dev_tri, 3 * std::max<uint64_t>(m.n_verts, 1), &V))) return rc;
+    if ((rc = scratch(h, h->top_verts, ScratchLayout().add(&ctr, 1).add(&used, N1).add(&flag, N1).add(&base, N1).add(&deg_out, N1).add(&deg_in, N1)))) return rc;
+    if ((rc = scratch(h, h->top_forest, ScratchLayout().add(&parent_s, N1).add(&parent_l, N1).add(&root_s, N1).add(&root_l, N1)))) return rc;
+    if ((rc = scratch(h, h->top_keys, ScratchLayout().add(&key_in, n_slots).add(&key_out, n_slots).add(&val_in, n_slots).add(&val_out, n_slots)
+                                          .add(&use, n_slots + 1).add(&listed, n_slots + 1).add(&lbase, n_slots + 1))))
+        return rc;
+    HIPCHK(h, hipMemsetAsync(ctr, 0, sizeof(TopCounters), h->stream));
+    // HFPF_TRACE_TOPOLOGY=1 (read per call, so that tools/topology_rate.py can time untraced calls on the same handle): one stderr
+    // line with the host's clock where the stream is drained anyway (and, traced only, in front of the first kernel and behind the sort)
+    const char* const trace_env = getenv("HFPF_TRACE_TOPOLOGY");
+    const bool trace = trace_env && trace_env[0] != '0';
+    double stamp[6] = {0, 0, 0, 0, 0, 0};
+    const auto mark = [&](int i) { if (trace) stamp[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    if (trace) HIPCHK(h, hipStreamSynchronize(h->stream));
+    mark(0);
+    DevParams vp{};  // what k_dev_verts reads of it
+    memcpy(vp.T, pose, sizeof vp.T);
+    vp.n_verts = m.n_verts, vp.n_tris = (uint32_t)m.n_tris, vp.stride = m.stride;
+    TopParams p{};
+    for (int a = 0; a < 3; a++) p.c[a] = (h->g.min[a] + h->g.max[a]) * 0.5;
+    p.n_verts = m.n_verts, p.n_tris = (uint32_t)m.n_tris;
+    const uint32_t nv = (uint32_t)m.n_verts;
+    const dim3 grid_v(blocks_for(m.n_verts, 256)), grid_v1(blocks_for(N1, 256)), grid_t(blocks_for(m.n_tris, 256));
+    hipLaunchKernelGGL(k_top_init, grid_v, dim3(256), 0, h->stream, m.n_verts, parent_s, parent_l, used, deg_out, deg_in);
+    hipLaunchKernelGGL(k_dev_verts, grid_v, dim3(256), 0, h->stream, vp, (const uint8_t*)m.verts, V);
+    hipLaunchKernelGGL(k_top_emit, grid_t, dim3(256), 0, h->stream, p, m.tris, V, key_in, val_in, used, parent_s, ctr);
+    hipLaunchKernelGGL(k_comp_flatten, grid_v1, dim3(256), 0, h->stream, parent_s, nv, root_s, flag);
+    hipLaunchKernelGGL(k_top_mask, grid_v, dim3(256), 0, h->stream, flag, used, (const uint32_t*)nullptr, m.n_verts);
+    HIPCHK(h, hipGetLastError());
+    uint64_t n_shells = 0;
+    if ((rc = scan_counts_locked(h, flag, base, m.n_verts, &n_shells))) return rc;
+    TopCounters hc;
+    HIPCHK(h, hipMemcpy(&hc, ctr, sizeof hc, hipMemcpyDeviceToHost));  // (the scan's read-back has synchronised the stream)
+    mark(1);
+    S->n_tris_valid = hc.n_valid, S->n_tris_invalid = hc.n_invalid, S->n_tris_far = hc.n_far;
+    const uint64_t n_used = hc.n_valid - hc.n_far, n_he = 3 * n_used;
+    if (hc.n_far > hc.n_valid || n_used > m.n_tris || (n_used == 0) != (n_shells == 0))
+        return fail(h, HFPF_ERR_STATE, "mesh_topology: %llu used triangles in %llu shells (internal)", (unsigned long long)n_used, (unsigned long long)n_shells);
+    ResultSet set;
+    if (n_used == 0) {  // nothing but the optional per-triangle words, all of them "skipped"
+        for (int i = 0; i < 3; i++) set.add(0, true);
+        set.add((size_t)m.n_tris * 4, !want_tri_shell);
+        if ((rc = result_alloc(h, set, on_device, "mesh_topology"))) return rc;
+        if (want_tri_shell) {
+            HIPCHK(h, hipMemsetAsync(set.a[3].dev, 0xFF, (size_t)m.n_tris * 4, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+        }
+        set.keep(out);
+        return HFPF_OK;
+    }
+    uint32_t* vshell = parent_s;  // the shells' forest is dead behind its flatten
+    hipLaunchKernelGGL(k_top_vlabel, grid_v, dim3(256), 0, h->stream, root_s, base, used, (const uint32_t*)nullptr, m.n_verts, vshell);
+    HIPCHK(h, hipGetLastError());
+    if ((rc = sort_pairs_u64(h, key_in, key_out, val_in, val_out, n_slots, kTopKeyBits))) return rc;
+    if (trace) HIPCHK(h, hipStreamSynchronize(h->stream));
+    mark(2);
+    const dim3 grid_e(blocks_for(n_he, 256)), grid_e1(blocks_for(n_he + 1, 256));
+    hipLaunchKernelGGL(k_top_classify, grid_e1, dim3(256), 0, h->stream, key_out, n_he, use, listed, parent_l, deg_out, deg_in, ctr);
+    HIPCHK(h, hipGetLastError());
+    uint64_t n_listed = 0, n_loops = 0;
+    if ((rc = scan_counts_locked(h, listed, lbase, n_he, &n_listed))) return rc;
+    mark(3);
+    hipLaunchKernelGGL(k_comp_flatten, grid_v1, dim3(256), 0, h->stream, parent_l, nv, root_l, flag);
+    hipLaunchKernelGGL(k_top_mask, grid_v, dim3(256), 0, h->stream, flag, deg_out, deg_in, m.n_verts);
+    HIPCHK(h, hipGetLastError());
+    if ((rc = scan_counts_locked(h, flag, base, m.n_verts, &n_loops))) return rc;
+    mark(4);
+    uint32_t* vloop = parent_l;  // as vshell
+    hipLaunchKernelGGL(k_top_vlabel, grid_v, dim3(256), 0, h->stream, root_l, base, deg_out, deg_in, m.n_verts, vloop);
+    HIPCHK(h, hipGetLastError());
+    set.add(n_listed * sizeof(TopEdge), n_listed == 0);
+    set.add(n_loops * sizeof(TopLoop), n_loops == 0);
+    set.add(n_shells * sizeof(TopShell));
+    set.add((size_t)m.n_tris * 4, !want_tri_shell);
+    if ((rc = result_alloc(h, set, on_device, "mesh_topology"))) return rc;
+    TopEdge* edges = (TopEdge*)set.a[0].dev;
+    TopLoop* loops = (TopLoop*)set.a[1].dev;
+    TopShell* shells = (TopShell*)set.a[2].dev;
+    uint32_t* tri_shell = (uint32_t*)set.a[3].dev;
+    if (n_loops) HIPCHK(h, hipMemsetAsync(loops, 0, n_loops * sizeof(TopLoop), h->stream));
+    HIPCHK(h, hipMemsetAsync(shells, 0, n_shells * sizeof(TopShell), h->stream));
+    hipLaunchKernelGGL(k_top_vertices, grid_v, dim3(256), 0, h->stream, m.n_verts, used, vshell, vloop, root_s, root_l, deg_out, deg_in, shells, (uint32_t)n_shells, loops,
+                       (uint32_t)n_loops, ctr);
+    hipLaunchKernelGGL(k_top_tris, grid_t, dim3(256), 0, h->stream, p, m.tris, V, vshell, shells, (uint32_t)n_shells, tri_shell);
+    hipLaunchKernelGGL(k_top_edges, grid_e, dim3(256), 0, h->stream, key_out, val_out, n_he, use, lbase, vshell, vloop, m.n_verts, shells, (uint32_t)n_shells, edges,
+                       (uint32_t)n_listed);
+    if (n_listed)
+        hipLaunchKernelGGL(k_top_loops, dim3(blocks_for(n_listed, 256)), dim3(256), 0, h->stream, edges, (uint32_t)n_listed, V, m.n_verts, loops, (uint32_t)n_loops);
+    hipLaunchKernelGGL(k_top_finish, dim3(blocks_for(std::max(n_loops, n_shells), 256)), dim3(256), 0, h->stream, (uint32_t)n_loops, loops, (uint32_t)n_shells, shells,
+                       ctr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(&hc, ctr, sizeof hc, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    mark(5);
+    if (trace)
+        fprintf(stderr, "hfpf: topology: %llu triangles: vertices, emit, shells %.3f ms; sort %.3f ms; run walk, listed scan %.3f ms; loops %.3f ms; "
+                        "allocation, reductions, finish %.3f ms\n",
+                (unsigned long long)m.n_tris, stamp[1] - stamp[0], stamp[2] - stamp[1], stamp[3] - stamp[2], stamp[4] - stamp[3], stamp[5] - stamp[4]);
+    if (hc.n_boundary + hc.n_nonmanifold + hc.n_miswound != n_listed || hc.n_interior + n_listed != hc.n_edges)
+        return fail(h, HFPF_ERR_STATE, "mesh_topology: the edge classes do not add up to the arrays (internal)");
+    S->n_verts_used = hc.n_verts_used, S->n_edges = hc.n_edges, S->n_interior = hc.n_interior, S->n_boundary = hc.n_boundary;
+    S->n_nonmanifold = hc.n_nonmanifold, S->n_miswound = hc.n_miswound, S->n_loops = n_loops, S->n_closed_loops = hc.n_closed_loops;
+    S->n_shells = n_shells, S->n_watertight = hc.n_watertight;
+    nout->n_edges = n_listed, nout->n_loops = n_loops, nout->n_shells = n_shells;
+    set.keep(out);
+    return HFPF_OK;
+}
+
+// The checks of both forms, all of them before anything is read through a mesh pointer.  0 = fine, else the text of the fault.
+static const char* topology_args_fault(const hfpf_topology_opts* o, const MeshRef& m, const double* pose, const void* const outs[7], bool on_device)
+{
+    if (hfpf_check_topology_opts(o) != HFPF_OK) return "invalid hfpf_topology_opts";
+    if (const char* f = mesh_args_fault(m, pose)) return f;
+    if (const char* f = topology_counts_fault(m.n_verts, m.n_tris)) return f;
+    for (int i = 0; i < 7; i++)
+        if (!outs[i]) return "NULL output pointer";
+    if (on_device && mesh_misaligned(m)) return "device mesh pointers must be 4-byte aligned";
+    return nullptr;
+}
+
+// A mesh without triangles is answered here, in front of any upload or scratch request: a zeroed summary and NULL arrays.  tri_shell
+// may be NULL: the per-triangle words are then not produced.
+static int topology_common(hfpf_handle* h, const hfpf_topology_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
+                           const double* pose, bool on_device, hfpf_topology_edge** edges, uint64_t* n_edges, hfpf_topology_loop** loops, uint64_t* n_loops,
+                           hfpf_topology_shell** shells, uint64_t* n_shells, uint32_t** tri_shell, hfpf_topology_summary* summary)
+{
+    if (!h) return HFPF_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    const MeshRef m{verts, n_verts, vertex_stride, tris, n_tris};
+    const void* const outs[7] = {edges, n_edges, loops, n_loops, shells, n_shells, summary};
+    if (const char* f = topology_args_fault(o, m, pose, outs, on_device)) return args_fail(h, "mesh_topology", on_device, f);
+    MeshRef d;
+    ResultSet set;
+    TopologyCounts n;
+    hfpf_topology_summary s{};
+    void* out[kResultArrays];
+    int rc;
+    if ((rc = local_read_prologue_locked(h, "mesh_topology"))) return rc;
+    if (n_tris && (rc = mesh_on_device_locked(h, "mesh_topology", m, on_device, &d))) return rc;
+    if (n_tris && (rc = topology_locked(h, d, pose, on_device, tri_shell != nullptr, &set, &n, &s))) return rc;
+    if ((rc = result_deliver(h, set, on_device, "mesh_topology", out))) return rc;
+    *edges = (hfpf_topology_edge*)out[0], *loops = (hfpf_topology_loop*)out[1], *shells = (hfpf_topology_shell*)out[2];
+    if (tri_shell) *tri_shell = (uint32_t*)out[3];
+    *n_edges = n.n_edges, *n_loops = n.n_loops, *n_shells = n.n_shells, *summary = s;
+    return HFPF_OK;
+}
+
+int hfpf_mesh_topology_device(hfpf_handle* h, const hfpf_topology_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* dev_tris,
+                              uint64_t n_tris, const double* pose_3x4, hfpf_topology_edge** dev_edges, uint64_t* n_edges, hfpf_topology_loop** dev_loops,
+                              uint64_t* n_loops, hfpf_topology_shell** dev_shells, uint64_t* n_shells, uint32_t** dev_tri_shell, hfpf_topology_summary* summary)
+{
+    return topology_common(h, o, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose_3x4, true, dev_edges, n_edges, dev_loops, n_loops, dev_shells, n_shells,
+                           dev_tri_shell, summary);
+}
+
+int hfpf_mesh_topology(hfpf_handle* h, const hfpf_topology_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris, uint64_t n_tris,
+                       const double* pose_3x4, hfpf_topology_edge** edges, uint64_t* n_edges, hfpf_topology_loop** loops, uint64_t* n_loops,
+                       hfpf_topology_shell** shells, uint64_t* n_shells, uint32_t** tri_shell, hfpf_topology_summary* summary)
+{
+    return topology_common(h, o, verts, n_verts, vertex_stride, tris, n_tris, pose_3x4, false, edges, n_edges, loops, n_loops, shells, n_shells, tri_shell, summary);
+}
+
+void hfpf_free_topology(hfpf_topology_edge* edges, hfpf_topology_loop* loops, hfpf_topology_shell* shells, uint32_t* tri_shell)
+{
+    free(edges);
+    free(loops);
+    free(shells);
+    free(tri_shell);
 }
 
 // ---- view planning (include/hfpf.h) ---------------------------------------------------------------------------------------------
@@ -4356,7 +4568,7 @@ static int plan_common(hfpf_handle* h, const hfpf_plan_opts* o, const void* vert
     ResultSet set;
     std::vector<hfpf_view_score> sc(std::max<uint32_t>(n_views, 1));
     hfpf_plan_summary s;
-    void* out[3];
+    void* out[kResultArrays];
     int rc;
     if ((rc = local_read_prologue_locked(h, "plan_views"))) return rc;
     if (n_tris == 0) plan_empty(n_views, sc.data(), &s);
@@ -4549,7 +4761,7 @@ static int consistency_common(hfpf_handle* h, const hfpf_consistency_opts* o, co
     ResultSet set;  // empty (nk = 0) without a row, or with none kept: NULL arrays beside the summary, no download
     uint64_t nk = 0;
     hfpf_consistency_summary s;
-    void* out[3];
+    void* out[kResultArrays];
     int rc;
     if ((rc = local_read_prologue_locked(h, "depth_consistency")) || (rc = consistency_locked(h, o, desc, ds, f, on_device, rows != nullptr, &set, &nk, &s))) return rc;
     if ((rc = result_deliver(h, set, on_device, "depth_consistency", out))) return rc;

@@ -375,4 +375,37 @@ inline SecCapFault section_cap_test(const uint32_t* counts, uint32_t n_planes, u
     return bad;
 }
 
+// ---- open edges of a mesh (hfpf_mesh_topology*, include/hfpf.h) ----
+
+constexpr uint64_t kTopMaxVerts = 1ull << 26;      // = HFPF_TOPOLOGY_MAX_VERTS: 26 bits of an edge key per vertex index
+constexpr uint64_t kTopMaxHalfEdges = 1ull << 32;  // 3 n_tris stays below it: a half-edge id is the sort's 32-bit value
+constexpr unsigned kTopKeyBits = 52;               // what the sort compares: va | vb
+constexpr uint64_t kTopForward = 1ull << 52;       // above the compared bits: the half-edge runs va -> vb
+constexpr uint64_t kTopSkipped = ~0ull;            // the key of a skipped triangle's slots: behind every edge (an edge has va < vb)
+constexpr uint32_t kTopNone = 0xFFFFFFFFu;         // = HFPF_TOPOLOGY_NONE
+constexpr uint32_t kTopBoundary = 1u, kTopNonManifold = 2u, kTopMiswound = 3u;  // hfpf_topology_edge.kind; 0 = INTERIOR, never listed
+
+// A half-edge's key from its two indices in the triangle's order.
+constexpr uint64_t top_edge_key(uint32_t from, uint32_t to)
+{
+    return from < to ? (((uint64_t)from << 26) | (uint64_t)to | kTopForward) : (((uint64_t)to << 26) | (uint64_t)from);
+}
+constexpr uint32_t top_key_va(uint64_t key) { return (uint32_t)(key >> 26) & 0x3FFFFFFu; }
+constexpr uint32_t top_key_vb(uint64_t key) { return (uint32_t)key & 0x3FFFFFFu; }
+constexpr bool top_same_edge(uint64_t a, uint64_t b) { return ((a ^ b) & (kTopForward - 1)) == 0; }
+// The class of an edge from its exact (or saturated: the classes part below 3) counts.
+constexpr uint32_t top_edge_kind(uint32_t n_fwd, uint32_t n_bwd)
+{
+    return n_fwd + n_bwd == 1 ? kTopBoundary : (n_fwd + n_bwd >= 3 ? kTopNonManifold : (n_fwd == 1 && n_bwd == 1 ? 0u : kTopMiswound));
+}
+constexpr uint32_t top_edge_uses(uint32_t n_fwd, uint32_t n_bwd) { return (n_fwd < 65535u ? n_fwd : 65535u) | ((n_bwd < 65535u ? n_bwd : 65535u) << 16); }
+
+// The counts of a call that need no pointer: 0 = fine, else the text of the fault.
+inline const char* topology_counts_fault(uint64_t n_verts, uint64_t n_tris)
+{
+    if (n_verts > kTopMaxVerts) return "n_verts must not exceed 2^26";
+    if (n_tris >= (kTopMaxHalfEdges + 2) / 3) return "3 * n_tris must stay below 2^32";
+    return nullptr;
+}
+
 }  // namespace hfpf

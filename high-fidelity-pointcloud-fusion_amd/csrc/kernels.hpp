@@ -5149,6 +5149,15 @@ struct SecParams {
     uint32_t n_total;      // EMIT: the segments of the call (the bound of every append)
 };
 
+// The IN RANGE rule of a valid triangle: each of its nine coordinates within kSecHeadroom of the box's centre c.
+__device__ __forceinline__ bool sec_in_range(const DevTri& tr, const double (&c)[3])
+{
+    bool in = true;
+#pragma unroll
+    for (int a = 0; a < 3; a++) in = in && fabs(tr.A[a] - c[a]) < kSecHeadroom && fabs(tr.B[a] - c[a]) < kSecHeadroom && fabs(tr.C[a] - c[a]) < kSecHeadroom;
+    return in;
+}
+
 template <bool EMIT>
 __global__ __launch_bounds__(256) void k_section(const SecParams p, const uint32_t* __restrict__ tris, const double* __restrict__ V,
                                                  const double* __restrict__ planes, uint32_t* __restrict__ count, const uint32_t* __restrict__ first,
@@ -5167,12 +5176,7 @@ __global__ __launch_bounds__(256) void k_section(const SecParams p, const uint32
     if (live) {
         double ab[3], ac[3], NN, L2;
         valid = dev_tri_valid(p.n_verts, tris, V, k, tr, ab, ac, NN, L2);
-        act = valid;
-        if (valid) {
-#pragma unroll
-            for (int a = 0; a < 3; a++)
-                act = act && fabs(tr.A[a] - p.c[a]) < kSecHeadroom && fabs(tr.B[a] - p.c[a]) < kSecHeadroom && fabs(tr.C[a] - p.c[a]) < kSecHeadroom;
-        }
+        act = valid && sec_in_range(tr, p.c);
     }
     if (!EMIT && p.count_tris) {
         const unsigned long long mv = __ballot(valid), mi = __ballot(live && !valid), mf = __ballot(valid && !act);
@@ -5372,6 +5376,356 @@ __global__ __launch_bounds__(256) void k_sec_finish(const uint32_t n_conts, SecC
         atomicAdd((unsigned long long*)&r->area_q28, (unsigned long long)k.area_q28);
         atomicAdd(n_closed, 1ull);
     }
+}
+
+// ---- open edges of a mesh (hfpf_mesh_topology*; contract in include/hfpf.h, numpy restatement tests/topology_ref.py) ----------------
+// The section's contour stage in vertex-index space.  k_dev_verts transforms the vertices.  k_top_emit writes a used triangle's three
+// half-edges at slots 3k .. 3k + 2 (key: va | vb with the direction above the sorted bits; value: the slot), marks its vertices
+// and unites them in the shells' forest (comp_unite: a shell's root is its smallest vertex).  The stable sort brings an edge's
+// half-edges together in ascending id; k_top_classify has the lane at the start of each run walk it, count the two directions and, for
+// a boundary edge, count the degrees of its ends and unite them in the loops' forest.  k_comp_flatten, k_top_mask and a scan of the
+// root flags number shells and loops by ascending representative; a scan of the listed flags places the edge records.  Behind the one
+// allocation of the results k_top_vertices, k_top_tris, k_top_edges, k_top_loops and k_top_finish are the reductions per vertex,
+// triangle, edge, listed edge and record.  Integer atomics only: nothing depends on the schedule.  A mesh is mostly one shell, so
+// every sum is first reduced over the wave's runs of lanes with the same label (top_run): one atomic per run, not per lane.
+struct TopEdge {  // = hfpf_topology_edge
+    uint32_t p0, p1, tri, kind, uses, loop, shell, reserved;
+};
+struct __attribute__((aligned(8))) TopLoop {  // = hfpf_topology_loop
+    uint32_t first_vertex, n_verts, n_edges, n_ends, flags, shell;
+    long long length_q32, area_q28[3];
+    unsigned long long reserved;
+};
+struct __attribute__((aligned(8))) TopShell {  // = hfpf_topology_shell
+    uint32_t first_vertex, n_verts, n_tris, flags, n_edges, n_boundary, n_nonmanifold, n_miswound, n_loops, reserved0;
+    long long area_q32, volume_q40;
+    unsigned long long reserved;
+};
+struct TopCounters {  // zeroed in front of the emit pass
+    unsigned long long n_valid, n_invalid, n_far, n_verts_used, n_edges, n_interior, n_boundary, n_nonmanifold, n_miswound, n_closed_loops, n_watertight;
+};
+static_assert(sizeof(TopEdge) == 32 && sizeof(TopLoop) == 64 && sizeof(TopShell) == 64, "the topology records");
+
+constexpr uint32_t kTopLoopClosed = 1u, kTopLoopBranched = 2u;
+constexpr uint32_t kTopLoopOpenMark = 0x80000000u;  // a loop's flags between k_top_vertices and k_top_finish: some vertex is not (1 in, 1 out)
+constexpr uint32_t kTopShellOpen = 1u, kTopShellNonManifold = 2u, kTopShellMiswound = 4u, kTopShellWatertight = 8u;
+
+struct TopParams {
+    double c[3];       // the centre of the bounding box
+    uint64_t n_verts;
+    uint32_t n_tris;
+};
+
+// The wave's lanes in runs of neighbours with the same label: `end` = the lane behind this lane's run, head = its first lane.  Every
+// lane of the wave calls it.
+struct TopRun {
+    unsigned end;
+    bool head;
+};
+__device__ __forceinline__ TopRun top_run(const uint32_t label, const unsigned lane)
+{
+    const uint32_t prev = __shfl_up(label, 1);
+    const unsigned long long heads = __ballot(lane == 0u || prev != label);
+    const unsigned long long above = heads & ~((2ull << lane) - 1ull);  // (lane 63: 2 << 63 is 0, the mask is empty)
+    return TopRun{above ? (unsigned)__ffsll((long long)above) - 1u : 64u, ((heads >> lane) & 1ull) != 0ull};
+}
+// v summed over the lanes from this one to the end of its run: the head ends with the run's total.  After the step of offset o a
+// lane holds the sum over [lane, min(lane + 2 o, end)).
+template <typename T>
+__device__ __forceinline__ T top_run_sum(T v, const TopRun r, const unsigned lane)
+{
+#pragma unroll
+    for (unsigned o = 1; o < 64u; o <<= 1) {
+        const T w = __shfl_down(v, o);
+        if (lane + o < r.end) v += w;
+    }
+    return v;
+}
+
+// Every vertex a root of both forests, unused, without a boundary edge.
+__global__ __launch_bounds__(256) void k_top_init(const uint64_t n_verts, uint32_t* __restrict__ parent_s, uint32_t* __restrict__ parent_l,
+                                                  uint32_t* __restrict__ used, uint32_t* __restrict__ deg_out, uint32_t* __restrict__ deg_in)
+{
+    const uint64_t v = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (v >= n_verts) return;
+    parent_s[v] = (uint32_t)v, parent_l[v] = (uint32_t)v;
+    used[v] = 0u, deg_out[v] = 0u, deg_in[v] = 0u;
+}
+
+// One lane per triangle: its class (k_section's tests), its three half-edges or three skipped slots, its vertices' marks and union.
+__global__ __launch_bounds__(256) void k_top_emit(const TopParams p, const uint32_t* __restrict__ tris, const double* __restrict__ V,
+                                                  uint64_t* __restrict__ key, uint32_t* __restrict__ val, uint32_t* __restrict__ used,
+                                                  uint32_t* __restrict__ parent, TopCounters* __restrict__ ctr)
+{
+    const uint64_t k64 = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const bool live = k64 < p.n_tris;  // no lane leaves before the ballots
+    const uint32_t k = live ? (uint32_t)k64 : 0u;
+    DevTri tr;
+    bool valid = false, act = false;
+    if (live) {
+        double ab[3], ac[3], NN, L2;
+        valid = dev_tri_valid(p.n_verts, tris, V, k, tr, ab, ac, NN, L2);
+        act = valid && sec_in_range(tr, p.c);
+    }
+    const unsigned long long mv = __ballot(valid), mi = __ballot(live && !valid), mf = __ballot(valid && !act);
+    if ((threadIdx.x & 63u) == 0u) {
+        if (mv) atomicAdd(&ctr->n_valid, (unsigned long long)__popcll(mv));
+        if (mi) atomicAdd(&ctr->n_invalid, (unsigned long long)__popcll(mi));
+        if (mf) atomicAdd(&ctr->n_far, (unsigned long long)__popcll(mf));
+    }
+    if (!live) return;
+    const uint64_t s = 3ull * k;
+    val[s] = (uint32_t)s, val[s + 1] = (uint32_t)s + 1u, val[s + 2] = (uint32_t)s + 2u;
+    if (!act) {
+        key[s] = key[s + 1] = key[s + 2] = kTopSkipped;
+        return;
+    }
+    const uint32_t i0 = tris[s], i1 = tris[s + 1], i2 = tris[s + 2];  // in range and distinct: the triangle is valid
+    key[s] = top_edge_key(i0, i1), key[s + 1] = top_edge_key(i1, i2), key[s + 2] = top_edge_key(i2, i0);
+    used[i0] = 1u, used[i1] = 1u, used[i2] = 1u;  // (every writer stores the same word)
+    comp_unite(parent, i0, i1);
+    comp_unite(parent, i0, i2);
+}
+
+// k_comp_flatten calls every vertex that is its own parent a root; a root counts only when the vertex takes part: a | b non-zero (b
+// may be NULL).
+__global__ __launch_bounds__(256) void k_top_mask(uint32_t* __restrict__ flag, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                  const uint64_t n_verts)
+{
+    const uint64_t v = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (v >= n_verts) return;
+    if ((a[v] | (b ? b[v] : 0u)) == 0u) flag[v] = 0u;
+}
+
+// label[v] = the number of v's component (base = the exclusive scan of the root flags), kTopNone for a vertex that takes no part.
+__global__ __launch_bounds__(256) void k_top_vlabel(const uint32_t* __restrict__ root, const uint32_t* __restrict__ base, const uint32_t* __restrict__ a,
+                                                    const uint32_t* __restrict__ b, const uint64_t n_verts, uint32_t* __restrict__ label)
+{
+    const uint64_t v = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (v >= n_verts) return;
+    label[v] = (a[v] | (b ? b[v] : 0u)) != 0u ? base[root[v]] : kTopNone;
+}
+
+// One lane per sorted half-edge of a used triangle (n_he of them; the skipped slots sort behind).  The first of a run walks it,
+// however long it is: use[i] = the edge's saturated counts, listed[i] = 1 for an edge that is not INTERIOR (listed has n_he + 1
+// entries, the last one 0 for the scan).  A boundary edge's ends get their degrees and their union.
+__global__ __launch_bounds__(256) void k_top_classify(const uint64_t* __restrict__ key, const uint64_t n_he, uint32_t* __restrict__ use,
+                                                      uint32_t* __restrict__ listed, uint32_t* __restrict__ parent, uint32_t* __restrict__ deg_out,
+                                                      uint32_t* __restrict__ deg_in, TopCounters* __restrict__ ctr)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const bool live = i < n_he;  // no lane leaves before the ballots
+    bool start = false;
+    uint32_t kind = 0u;
+    if (live) {
+        const uint64_t e = key[i];
+        start = e != kTopSkipped && (i == 0 || !top_same_edge(key[i - 1], e));
+        if (start) {
+            uint32_t n_fwd = 0u, n_bwd = 0u;
+            for (uint64_t j = i; j < n_he; j++) {
+                const uint64_t f = key[j];
+                if (!top_same_edge(f, e)) break;
+                if (f & kTopForward) n_fwd++;
+                else n_bwd++;
+            }
+            kind = top_edge_kind(n_fwd, n_bwd);
+            use[i] = top_edge_uses(n_fwd, n_bwd);
+            if (kind == kTopBoundary) {
+                const uint32_t p0 = n_fwd ? top_key_va(e) : top_key_vb(e), p1 = n_fwd ? top_key_vb(e) : top_key_va(e);
+                atomicAdd(&deg_out[p0], 1u);
+                atomicAdd(&deg_in[p1], 1u);
+                comp_unite(parent, p0, p1);
+            }
+        } else {
+            use[i] = 0u;
+        }
+        listed[i] = start && kind != 0u ? 1u : 0u;
+    } else if (i == n_he) {
+        listed[i] = 0u;
+    }
+    const unsigned long long me = __ballot(start), mb = __ballot(start && kind == kTopBoundary), mn = __ballot(start && kind == kTopNonManifold),
+                             mm = __ballot(start && kind == kTopMiswound);
+    if ((threadIdx.x & 63u) != 0u || me == 0ull) return;
+    atomicAdd(&ctr->n_edges, (unsigned long long)__popcll(me));
+    if (me & ~(mb | mn | mm)) atomicAdd(&ctr->n_interior, (unsigned long long)__popcll(me & ~(mb | mn | mm)));
+    if (mb) atomicAdd(&ctr->n_boundary, (unsigned long long)__popcll(mb));
+    if (mn) atomicAdd(&ctr->n_nonmanifold, (unsigned long long)__popcll(mn));
+    if (mm) atomicAdd(&ctr->n_miswound, (unsigned long long)__popcll(mm));
+}
+
+// One lane per vertex: its share of its shell's and of its loop's record (both zeroed before).  A representative writes the words
+// nobody adds to.
+__global__ __launch_bounds__(256) void k_top_vertices(const uint64_t n_verts, const uint32_t* __restrict__ used, const uint32_t* __restrict__ vshell,
+                                                      const uint32_t* __restrict__ vloop, const uint32_t* __restrict__ root_s,
+                                                      const uint32_t* __restrict__ root_l, const uint32_t* __restrict__ deg_out,
+                                                      const uint32_t* __restrict__ deg_in, TopShell* __restrict__ shells, const uint32_t n_shells,
+                                                      TopLoop* __restrict__ loops, const uint32_t n_loops, TopCounters* __restrict__ ctr)
+{
+    const uint64_t v = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const unsigned lane = threadIdx.x & 63u;
+    const bool live = v < n_verts;  // no lane leaves before the last shuffle
+    const bool in_shell = live && used[v] != 0u;
+    const uint32_t n_out = live ? deg_out[v] : 0u, n_in = live ? deg_in[v] : 0u;
+    const bool on_rim = n_out + n_in != 0u;
+    uint32_t s = in_shell ? vshell[v] : kTopNone, l = on_rim ? vloop[v] : kTopNone;
+    if (s >= n_shells) s = kTopNone;
+    if (l >= n_loops) l = kTopNone;
+    if (s != kTopNone && root_s[v] == (uint32_t)v) shells[s].first_vertex = (uint32_t)v;
+    if (l != kTopNone && root_l[v] == (uint32_t)v) loops[l].first_vertex = (uint32_t)v, loops[l].shell = s;
+    const unsigned long long mu = __ballot(in_shell);
+    if (lane == 0u && mu) atomicAdd(&ctr->n_verts_used, (unsigned long long)__popcll(mu));
+    const TopRun rs = top_run(s, lane);
+    const uint32_t nv = top_run_sum(s != kTopNone ? 1u : 0u, rs, lane);
+    if (rs.head && s != kTopNone) atomicAdd(&shells[s].n_verts, nv);
+    // a wave holds at most 64 of each: vertices | ends << 8 | not (1 in, 1 out) << 16 | branched << 24 in one word
+    const uint32_t mine = l == kTopNone ? 0u : 1u | (n_in + n_out == 1u ? 1u << 8 : 0u) | (n_in == 1u && n_out == 1u ? 0u : 1u << 16) |
+                                               (n_in > 1u || n_out > 1u ? 1u << 24 : 0u);
+    const TopRun rl = top_run(l, lane);
+    const uint32_t w = top_run_sum(mine, rl, lane);
+    if (!rl.head || l == kTopNone) return;
+    TopLoop* k = &loops[l];
+    atomicAdd(&k->n_verts, w & 0xFFu);
+    if ((w >> 8) & 0xFFu) atomicAdd(&k->n_ends, (w >> 8) & 0xFFu);
+    const uint32_t flags = ((w >> 16) & 0xFFu ? kTopLoopOpenMark : 0u) | ((w >> 24) ? kTopLoopBranched : 0u);
+    if (flags) atomicOr(&k->flags, flags);
+}
+
+// One lane per triangle: its shell (tri_shell, when wanted) and its terms of the shell's triangle count, area and volume about the
+// representative's point (k_top_vertices has named it).
+__global__ __launch_bounds__(256) void k_top_tris(const TopParams p, const uint32_t* __restrict__ tris, const double* __restrict__ V,
+                                                  const uint32_t* __restrict__ vshell, TopShell* __restrict__ shells, const uint32_t n_shells,
+                                                  uint32_t* __restrict__ tri_shell)
+{
+    const uint64_t k64 = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const unsigned lane = threadIdx.x & 63u;
+    const bool live = k64 < p.n_tris;  // no lane leaves before the last shuffle
+    const uint32_t k = live ? (uint32_t)k64 : 0u;
+    DevTri tr;
+    double NN = 0.0;
+    bool act = false;
+    if (live) {
+        double ab[3], ac[3], L2;
+        act = dev_tri_valid(p.n_verts, tris, V, k, tr, ab, ac, NN, L2) && sec_in_range(tr, p.c);
+    }
+    uint32_t s = act ? vshell[tris[3ull * k]] : kTopNone;
+    if (s >= n_shells) s = kTopNone;
+    if (live && tri_shell) tri_shell[k] = s;
+    long long area = 0ll, volume = 0ll;
+    if (s != kTopNone) {
+        const double* Pr = V + 3ull * shells[s].first_vertex;
+        double a[3], b[3], c[3];
+#pragma unroll
+        for (int x = 0; x < 3; x++) a[x] = tr.A[x] - Pr[x], b[x] = tr.B[x] - Pr[x], c[x] = tr.C[x] - Pr[x];
+        const double X[3] = {b[1] * c[2] - b[2] * c[1], b[2] * c[0] - b[0] * c[2], b[0] * c[1] - b[1] * c[0]};
+        area = (long long)rint((0.5 * sqrt(NN)) * 4294967296.0);
+        volume = (long long)rint((dev_dot(a, X) / 6.0) * 1099511627776.0);
+    }
+    const TopRun r = top_run(s, lane);
+    const uint32_t n = top_run_sum(s != kTopNone ? 1u : 0u, r, lane);
+    area = top_run_sum(area, r, lane);
+    volume = top_run_sum(volume, r, lane);
+    if (!r.head || s == kTopNone) return;
+    TopShell* h = &shells[s];
+    atomicAdd(&h->n_tris, n);
+    atomicAdd((unsigned long long*)&h->area_q32, (unsigned long long)area);
+    atomicAdd((unsigned long long*)&h->volume_q40, (unsigned long long)volume);
+}
+
+// One lane per sorted half-edge: the first of a run adds the edge to its shell's counts and writes the record of a listed edge at its
+// place (base = the exclusive scan of the listed flags).  The other lanes of a run carry the shell's label and add nothing, so that
+// the runs of a wave stay as long as the shell is.
+__global__ __launch_bounds__(256) void k_top_edges(const uint64_t* __restrict__ key, const uint32_t* __restrict__ val, const uint64_t n_he,
+                                                   const uint32_t* __restrict__ use, const uint32_t* __restrict__ base, const uint32_t* __restrict__ vshell,
+                                                   const uint32_t* __restrict__ vloop, const uint64_t n_verts, TopShell* __restrict__ shells,
+                                                   const uint32_t n_shells, TopEdge* __restrict__ edges, const uint32_t n_listed)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const unsigned lane = threadIdx.x & 63u;
+    const uint64_t e = i < n_he ? key[i] : kTopSkipped;  // no lane leaves before the last shuffle
+    const uint32_t va = top_key_va(e), vb = top_key_vb(e);
+    const bool real = e != kTopSkipped && vb < n_verts;  // (va < vb in every key the emit pass writes)
+    const bool start = real && (i == 0 || !top_same_edge(key[i - 1], e));
+    uint32_t s = real ? vshell[va] : kTopNone;
+    if (s >= n_shells) s = kTopNone;
+    uint32_t mine = 0u;  // a wave holds at most 64 of each: edges | boundary << 8 | non-manifold << 16 | miswound << 24 in one word
+    if (start) {
+        const uint32_t uses = use[i], kind = top_edge_kind(uses & 0xFFFFu, uses >> 16);
+        mine = 1u | (kind == kTopBoundary ? 1u << 8 : 0u) | (kind == kTopNonManifold ? 1u << 16 : 0u) | (kind == kTopMiswound ? 1u << 24 : 0u);
+        const uint32_t o = base[i];
+        if (kind != 0u && o < n_listed) {
+            const bool back = kind == kTopBoundary && !(e & kTopForward);
+            edges[o] = TopEdge{back ? vb : va, back ? va : vb, val[i] / 3u, kind, uses, kind == kTopBoundary ? vloop[va] : kTopNone, s, 0u};
+        }
+    }
+    const TopRun r = top_run(s, lane);
+    const uint32_t w = top_run_sum(mine, r, lane);
+    if (!r.head || s == kTopNone || w == 0u) return;
+    TopShell* h = &shells[s];
+    atomicAdd(&h->n_edges, w & 0xFFu);
+    if ((w >> 8) & 0xFFu) atomicAdd(&h->n_boundary, (w >> 8) & 0xFFu);
+    if ((w >> 16) & 0xFFu) atomicAdd(&h->n_nonmanifold, (w >> 16) & 0xFFu);
+    if (w >> 24) atomicAdd(&h->n_miswound, w >> 24);
+}
+
+// One lane per listed edge: a boundary edge's terms of its loop's edge count, length and vector area about the representative's point.
+__global__ __launch_bounds__(256) void k_top_loops(const TopEdge* __restrict__ edges, const uint32_t n_listed, const double* __restrict__ V,
+                                                   const uint64_t n_verts, TopLoop* __restrict__ loops, const uint32_t n_loops)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const unsigned lane = threadIdx.x & 63u;
+    uint32_t l = kTopNone, p0 = 0u, p1 = 0u;  // no lane leaves before the last shuffle
+    if (i < n_listed) {
+        const TopEdge e = edges[i];
+        if (e.kind == kTopBoundary && e.loop < n_loops && e.p0 < n_verts && e.p1 < n_verts) l = e.loop, p0 = e.p0, p1 = e.p1;
+    }
+    long long len = 0ll, area[3] = {0ll, 0ll, 0ll};
+    if (l != kTopNone) {
+        const double* P0 = V + 3ull * p0;
+        const double* P1 = V + 3ull * p1;
+        const double* Pr = V + 3ull * loops[l].first_vertex;
+        double d[3], a[3], b[3];
+#pragma unroll
+        for (int x = 0; x < 3; x++) d[x] = P1[x] - P0[x], a[x] = P0[x] - Pr[x], b[x] = P1[x] - Pr[x];
+        const double X[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+        len = (long long)rint(sqrt(dev_dot(d, d)) * 4294967296.0);
+#pragma unroll
+        for (int x = 0; x < 3; x++) area[x] = (long long)rint((0.5 * X[x]) * 268435456.0);
+    }
+    const TopRun r = top_run(l, lane);
+    const uint32_t n = top_run_sum(l != kTopNone ? 1u : 0u, r, lane);
+    len = top_run_sum(len, r, lane);
+#pragma unroll
+    for (int x = 0; x < 3; x++) area[x] = top_run_sum(area[x], r, lane);
+    if (!r.head || l == kTopNone) return;
+    TopLoop* k = &loops[l];
+    atomicAdd(&k->n_edges, n);
+    atomicAdd((unsigned long long*)&k->length_q32, (unsigned long long)len);
+#pragma unroll
+    for (int x = 0; x < 3; x++) atomicAdd((unsigned long long*)&k->area_q28[x], (unsigned long long)area[x]);
+}
+
+// One lane per loop and per shell: the final flags, a loop's share of its shell's record and the summary's two counts.
+__global__ __launch_bounds__(256) void k_top_finish(const uint32_t n_loops, TopLoop* __restrict__ loops, const uint32_t n_shells, TopShell* __restrict__ shells,
+                                                    TopCounters* __restrict__ ctr)
+{
+    const uint64_t c = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    bool closed = false, tight = false;
+    if (c < n_loops) {
+        const uint32_t f = loops[c].flags, s = loops[c].shell;
+        closed = (f & kTopLoopOpenMark) == 0u;
+        loops[c].flags = (closed ? kTopLoopClosed : 0u) | ((f & kTopLoopBranched) ? kTopLoopBranched : 0u);
+        if (s < n_shells) atomicAdd(&shells[s].n_loops, 1u);
+    }
+    if (c < n_shells) {
+        const TopShell* h = &shells[c];
+        const uint32_t f = (h->n_boundary ? kTopShellOpen : 0u) | (h->n_nonmanifold ? kTopShellNonManifold : 0u) | (h->n_miswound ? kTopShellMiswound : 0u);
+        tight = f == 0u;
+        shells[c].flags = tight ? kTopShellWatertight : f;
+    }
+    const unsigned long long mc = __ballot(closed), mt = __ballot(tight);
+    if ((threadIdx.x & 63u) != 0u) return;
+    if (mc) atomicAdd(&ctr->n_closed_loops, (unsigned long long)__popcll(mc));
+    if (mt) atomicAdd(&ctr->n_watertight, (unsigned long long)__popcll(mt));
 }
 
 }  // namespace hfpf

@@ -2,10 +2,13 @@
 // synthetic sensor -> ~start -> N x PointCloud2 callbacks with tf poses -> periodic clean -> ~process ->
 // <dir>/test_cloud.pcd + <dir>/meta.csv.  Prints per-stage wall times.
 //
-//   hfpf_demo [--section planes.txt] [--min-component N [--hide-filtered]] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]] [--plan poses.txt]] <out_dir> [frames=30] [W=640] [H=480] [resolution=0.001] [clean_every=10] [seed=0xF051] [pose_seed=0x5E3]
+//   hfpf_demo [--mesh-topology] [--section planes.txt] [--min-component N [--hide-filtered]] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]] [--plan poses.txt]] <out_dir> [frames=30] [W=640] [H=480] [resolution=0.001] [clean_every=10] [seed=0xF051] [pose_seed=0x5E3]
 // --section planes.txt: ~process also writes mesh.ply (hfpf_node_set_mesh_output: a window of 2 voxels) and cuts that mesh with the
 //   planes in planes.txt (four numbers per plane, n.x n.y n.z d in the fusion frame, separated by white space;
 //   hfpf_node_set_section_planes): sections.csv and section_summary.csv, and the demo prints every plane's contours, length and area.
+// --mesh-topology: ~process also writes mesh.ply (as --section does) and the open edges, boundary loops and shells of that mesh
+//   (hfpf_node_set_mesh_topology): mesh_edges.csv, mesh_loops.csv, mesh_shells.csv and mesh_topology_summary.csv, and the demo prints
+//   the summary and the five longest loops.
 // --min-component N: ~process saves only the connected components (26-neighbourhood) of at least N rows (hfpf_node_set_component_filter).
 //   --hide-filtered: the rows the filter drops are hidden on the device (hfpf_node_set_hide_filtered), so that the reports of --reference
 //   see the cleaned model too, not only test_cloud.pcd and meta.csv.
@@ -66,9 +69,15 @@ int main(int argc, char** argv)
     double spacing = 0.0;
     const char* plan = nullptr;
     const char* section = nullptr;
+    bool topology = false;
     while (argc > 2 && strncmp(argv[1], "--", 2) == 0) {
         if (strcmp(argv[1], "--align") == 0) {
             align = true;
+            argv += 1, argc -= 1;
+            continue;
+        }
+        if (strcmp(argv[1], "--mesh-topology") == 0) {
+            topology = true;
             argv += 1, argc -= 1;
             continue;
         }
@@ -95,7 +104,7 @@ int main(int argc, char** argv)
         argv += 2, argc -= 2;
     }
     if (argc < 2 || strncmp(argv[1], "--", 2) == 0) {
-        fprintf(stderr, "usage: hfpf_demo [--section planes.txt] [--min-component N [--hide-filtered]] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]] [--plan poses.txt]] <out_dir> [frames] [W] [H] [resolution] [clean_every] [seed] [pose_seed]\n");
+        fprintf(stderr, "usage: hfpf_demo [--mesh-topology] [--section planes.txt] [--min-component N [--hide-filtered]] [--reference mesh.ply [--max-deviation metres] [--align] [--coverage [spacing]] [--plan poses.txt]] <out_dir> [frames] [W] [H] [resolution] [clean_every] [seed] [pose_seed]\n");
         return 2;
     }
     const std::string dir = argv[1];
@@ -121,6 +130,19 @@ int main(int argc, char** argv)
     if (hfpf_node_create(&p, lookup, &tf, &node) != HFPF_OK) {
         fprintf(stderr, "create: %s\n", hfpf_node_last_error(nullptr));
         return 1;
+    }
+    if (topology) {
+        hfpf_mesh_opts mo;
+        memset(&mo, 0, sizeof mo);
+        mo.struct_size = sizeof mo;
+        mo.radius = 2, mo.max_distance = HUGE_VAL;
+        hfpf_topology_opts to;
+        memset(&to, 0, sizeof to);
+        to.struct_size = sizeof to;
+        if (hfpf_node_set_mesh_output(node, &mo) != HFPF_OK || hfpf_node_set_mesh_topology(node, &to) != HFPF_OK) {
+            fprintf(stderr, "mesh-topology: %s\n", hfpf_node_last_error(node));
+            return 1;
+        }
     }
     if (section) {
         std::vector<double> planes;
@@ -259,6 +281,44 @@ int main(int argc, char** argv)
     hfpf_node_get_stats(node, &st);
     printf("%s\nframes %llu integrated %llu  callbacks %.3f s  cleans %.3f s (%llu passes)  process %.3f s\n", r.message,
            (unsigned long long)st.received, (unsigned long long)st.integrated, t_cb, t_clean, (unsigned long long)st.clean_passes, t_proc);
+    if (topology) {  // mesh_topology_summary.csv: one line; mesh_loops.csv: one line per loop
+        unsigned long long w[13];
+        FILE* f = fopen((dir + "/mesh_topology_summary.csv").c_str(), "r");
+        if (!f || fscanf(f, "%*[^\n]\n") != 0 ||
+            fscanf(f, "%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu", &w[0], &w[1], &w[2], &w[3], &w[4], &w[5], &w[6], &w[7], &w[8], &w[9], &w[10],
+                   &w[11], &w[12]) != 13) {
+            fprintf(stderr, "mesh_topology_summary.csv: cannot read it back\n");
+            return 1;
+        }
+        fclose(f);
+        printf("mesh topology: %llu triangles used (%llu invalid, %llu far), %llu vertices, %llu edges: %llu interior, %llu boundary, %llu non-manifold, "
+               "%llu miswound; %llu loops (%llu closed); %llu shells (%llu watertight)\n",
+               w[0] - w[2], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10], w[11], w[12]);
+        struct Loop {
+            unsigned id, first, nv, ne, ends, flags, shell;
+            long long len, a[3];
+        };
+        std::vector<Loop> loops;
+        Loop l;
+        f = fopen((dir + "/mesh_loops.csv").c_str(), "r");
+        if (!f || fscanf(f, "%*[^\n]\n") != 0) {
+            fprintf(stderr, "mesh_loops.csv: cannot read it back\n");
+            return 1;
+        }
+        while (fscanf(f, "%u,%u,%u,%u,%u,%u,%u,%lld,%lld,%lld,%lld\n", &l.id, &l.first, &l.nv, &l.ne, &l.ends, &l.flags, &l.shell, &l.len, &l.a[0], &l.a[1], &l.a[2]) == 11)
+            loops.push_back(l);
+        fclose(f);
+        for (int k = 0; k < 5 && !loops.empty(); k++) {  // the five longest, longest first
+            size_t best = 0;
+            for (size_t i = 1; i < loops.size(); i++)
+                if (loops[i].len > loops[best].len) best = i;
+            const Loop& b = loops[best];
+            printf("mesh topology: loop %u: %u edges, length %.6f m, vector area (%.6f, %.6f, %.6f) m^2, %s%s, shell %u\n", b.id, b.ne, (double)b.len * 0x1p-32,
+                   (double)b.a[0] * 0x1p-28, (double)b.a[1] * 0x1p-28, (double)b.a[2] * 0x1p-28, (b.flags & HFPF_TOPOLOGY_LOOP_CLOSED) ? "closed" : "open",
+                   (b.flags & HFPF_TOPOLOGY_LOOP_BRANCHED) ? ", branched" : "", b.shell);
+            loops.erase(loops.begin() + (long)best);
+        }
+    }
     if (section) {  // section_summary.csv: one line per plane
         FILE* f = fopen((dir + "/section_summary.csv").c_str(), "r");
         if (!f || fscanf(f, "%*[^\n]\n") != 0) {

@@ -60,6 +60,8 @@ struct hfpf_node {
     bool sec_on = false;                // hfpf_node_set_section_planes: ~process also writes sections.csv and section_summary.csv
     hfpf_section_opts sec_opts{};
     std::vector<double> sec_planes;     // 4 per plane
+    bool top_on = false;                // hfpf_node_set_mesh_topology: ~process also writes mesh_edges.csv, mesh_loops.csv, mesh_shells.csv and the summary
+    hfpf_topology_opts top_opts{};
     void* publish_user = nullptr;
     std::thread clean_thread;
     std::mutex cv_mtx;
@@ -546,10 +548,69 @@ static int write_sections(hfpf_node* n, const hfpf_mesh_vertex* mv, uint64_t nmv
     return rc;
 }
 
+// mesh_edges.csv, mesh_loops.csv, mesh_shells.csv and mesh_topology_summary.csv beside mesh.ply: hfpf_mesh_topology_device of the mesh
+// that file holds (the same options extract the same mesh), read in HBM where hfpf_extract_mesh_device leaves it, identity pose.
+static int write_topology(hfpf_node* n)
+{
+    const double ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    hfpf_mesh_vertex* dv = nullptr;
+    uint32_t* dt = nullptr;
+    uint64_t nv = 0, nt = 0, ne = 0, nl = 0, ns = 0;
+    hfpf_topology_edge* de = nullptr;
+    hfpf_topology_loop* dl = nullptr;
+    hfpf_topology_shell* ds = nullptr;
+    hfpf_topology_summary s;
+    int rc = hfpf_extract_mesh_device(n->grid, &n->mesh_opts, &dv, &nv, &dt, &nt);
+    if (rc == HFPF_OK) rc = hfpf_mesh_topology_device(n->grid, &n->top_opts, dv, nv, sizeof(hfpf_mesh_vertex), dt, nt, ident, &de, &ne, &dl, &nl, &ds, &ns, nullptr, &s);
+    std::vector<hfpf_topology_edge> edges(rc == HFPF_OK ? ne : 0);
+    std::vector<hfpf_topology_loop> loops(rc == HFPF_OK ? nl : 0);
+    std::vector<hfpf_topology_shell> shells(rc == HFPF_OK ? ns : 0);
+    if (rc == HFPF_OK && ne) rc = hfpf_device_download(n->grid, edges.data(), de, ne * sizeof(hfpf_topology_edge));
+    if (rc == HFPF_OK && nl) rc = hfpf_device_download(n->grid, loops.data(), dl, nl * sizeof(hfpf_topology_loop));
+    if (rc == HFPF_OK && ns) rc = hfpf_device_download(n->grid, shells.data(), ds, ns * sizeof(hfpf_topology_shell));
+    for (void* p : {(void*)dv, (void*)dt, (void*)de, (void*)dl, (void*)ds})
+        if (p) hfpf_device_free(n->grid, p);
+    if (rc != HFPF_OK) return rc;
+    auto finish = [](FILE* f) { return ferror(f) | fclose(f) ? HFPF_ERR_IO : HFPF_OK; };
+    FILE* f = fopen((n->directory_name + "/mesh_edges.csv").c_str(), "w");
+    if (!f) return HFPF_ERR_IO;
+    fprintf(f, "p0,p1,tri,kind,uses,loop,shell\n");
+    for (const hfpf_topology_edge& e : edges) fprintf(f, "%u,%u,%u,%u,%u,%u,%u\n", e.p0, e.p1, e.tri, e.kind, e.uses, e.loop, e.shell);
+    if ((rc = finish(f))) return rc;
+    if (!(f = fopen((n->directory_name + "/mesh_loops.csv").c_str(), "w"))) return HFPF_ERR_IO;
+    fprintf(f, "loop,first_vertex,n_verts,n_edges,n_ends,flags,shell,length_q32,area_q28_x,area_q28_y,area_q28_z\n");
+    for (uint64_t i = 0; i < nl; i++) {
+        const hfpf_topology_loop& l = loops[i];
+        fprintf(f, "%llu,%u,%u,%u,%u,%u,%u,%lld,%lld,%lld,%lld\n", (unsigned long long)i, l.first_vertex, l.n_verts, l.n_edges, l.n_ends, l.flags, l.shell,
+                (long long)l.length_q32, (long long)l.area_q28[0], (long long)l.area_q28[1], (long long)l.area_q28[2]);
+    }
+    if ((rc = finish(f))) return rc;
+    if (!(f = fopen((n->directory_name + "/mesh_shells.csv").c_str(), "w"))) return HFPF_ERR_IO;
+    fprintf(f, "shell,first_vertex,n_verts,n_tris,flags,n_edges,n_boundary,n_nonmanifold,n_miswound,n_loops,area_q32,volume_q40\n");
+    for (uint64_t i = 0; i < ns; i++) {
+        const hfpf_topology_shell& h = shells[i];
+        fprintf(f, "%llu,%u,%u,%u,%u,%u,%u,%u,%u,%u,%lld,%lld\n", (unsigned long long)i, h.first_vertex, h.n_verts, h.n_tris, h.flags, h.n_edges, h.n_boundary,
+                h.n_nonmanifold, h.n_miswound, h.n_loops, (long long)h.area_q32, (long long)h.volume_q40);
+    }
+    if ((rc = finish(f))) return rc;
+    if (!(f = fopen((n->directory_name + "/mesh_topology_summary.csv").c_str(), "w"))) return HFPF_ERR_IO;
+    fprintf(f, "n_tris_valid,n_tris_invalid,n_tris_far,n_verts_used,n_edges,n_interior,n_boundary,n_nonmanifold,n_miswound,n_loops,n_closed_loops,n_shells,"
+               "n_watertight\n");
+    const uint64_t w[13] = {s.n_tris_valid, s.n_tris_invalid, s.n_tris_far, s.n_verts_used, s.n_edges, s.n_interior, s.n_boundary,
+                            s.n_nonmanifold, s.n_miswound, s.n_loops, s.n_closed_loops, s.n_shells, s.n_watertight};
+    for (int i = 0; i < 13; i++) fprintf(f, "%llu%c", (unsigned long long)w[i], i == 12 ? '\n' : ',');
+    return finish(f);
+}
+
 int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
 {
     if (!n) return HFPF_ERR_BAD_ARG;
     n->process_calls++;
+    if (n->top_on && !n->mesh_on) {  // EXTENSION: the topology is that of the mesh of mesh.ply; nothing is written and the grid is kept
+        const std::string m = "mesh topology is set but mesh output is not (hfpf_node_set_mesh_output)";
+        set_res(res, false, m);
+        return nfail(n, HFPF_ERR_STATE, m);
+    }
     if (n->sec_on && !n->mesh_on) {  // EXTENSION: the sections cut the mesh of mesh.ply; nothing is written and the grid is kept
         const std::string m = "section planes are set but mesh output is not (hfpf_node_set_mesh_output)";
         set_res(res, false, m);
@@ -612,6 +673,7 @@ int hfpf_node_process(hfpf_node* n, hfpf_trigger_response* res)
         if (rc == HFPF_OK) rc = hfpf_write_ply(mv, nmv, mt, nmt, (n->directory_name + "/mesh.ply").c_str());
         if (rc == HFPF_OK && n->sec_on) rc = write_sections(n, mv, nmv, mt, nmt);  // EXTENSION: ... and its profiles in the node's planes
         hfpf_free_mesh(mv, mt);
+        if (rc == HFPF_OK && n->top_on) rc = write_topology(n);  // EXTENSION: ... and its open edges, loops and shells
     }
     if (rc == HFPF_OK && n->write_variants) {  // the reference's `#if 0` block, node.cpp:399-437
         struct Variant {
@@ -697,6 +759,17 @@ int hfpf_node_set_section_planes(hfpf_node* n, const hfpf_section_opts* opts, co
         n->sec_planes.clear();
     }
     n->sec_on = opts != nullptr;
+    return HFPF_OK;
+}
+
+int hfpf_node_set_mesh_topology(hfpf_node* n, const hfpf_topology_opts* opts)
+{
+    if (!n) return HFPF_ERR_BAD_ARG;
+    if (opts) {
+        if (hfpf_check_topology_opts(opts) != HFPF_OK) return nfail(n, HFPF_ERR_BAD_ARG, "hfpf_node_set_mesh_topology: invalid hfpf_topology_opts");
+        n->top_opts = *opts;
+    }
+    n->top_on = opts != nullptr;
     return HFPF_OK;
 }
 

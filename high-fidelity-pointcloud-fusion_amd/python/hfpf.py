@@ -127,6 +127,7 @@ EXPORTS = [
     "hfpf_check_cover_opts", "hfpf_cover_mesh", "hfpf_cover_mesh_device", "hfpf_free_coverage",
     "hfpf_check_plan_opts", "hfpf_plan_views", "hfpf_plan_views_device", "hfpf_free_plan",
     "hfpf_check_section_opts", "hfpf_section_mesh", "hfpf_section_mesh_device", "hfpf_free_section",
+    "hfpf_check_topology_opts", "hfpf_mesh_topology", "hfpf_mesh_topology_device", "hfpf_free_topology",
     "hfpf_check_consistency_opts", "hfpf_depth_consistency", "hfpf_depth_consistency_device", "hfpf_free_consistency",
     "hfpf_check_hide_opts", "hfpf_hide_voxels", "hfpf_hide_voxels_device", "hfpf_hide_box", "hfpf_show_all", "hfpf_get_hidden",
     "hfpf_check_raycast_opts", "hfpf_raycast", "hfpf_raycast_device", "hfpf_raycast_view", "hfpf_raycast_view_device",
@@ -460,6 +461,43 @@ def section_opts():
 check_section_opts = _opts_checker("section")
 
 
+# hfpf_topology_edge.kind, the loops' and the shells' flags and the topology records (include/hfpf.h)
+TOPOLOGY_BOUNDARY, TOPOLOGY_NONMANIFOLD, TOPOLOGY_MISWOUND = 1, 2, 3
+TOPOLOGY_LOOP_CLOSED, TOPOLOGY_LOOP_BRANCHED = 1, 2
+TOPOLOGY_SHELL_OPEN, TOPOLOGY_SHELL_NONMANIFOLD, TOPOLOGY_SHELL_MISWOUND, TOPOLOGY_SHELL_WATERTIGHT = 1, 2, 4, 8
+TOPOLOGY_NONE, TOPOLOGY_MAX_VERTS = 0xFFFFFFFF, 1 << 26
+TOPOLOGY_EDGE_DTYPE = np.dtype([("p0", "<u4"), ("p1", "<u4"), ("tri", "<u4"), ("kind", "<u4"), ("uses", "<u4"), ("loop", "<u4"), ("shell", "<u4"),
+                                ("reserved", "<u4")])
+TOPOLOGY_LOOP_DTYPE = np.dtype([("first_vertex", "<u4"), ("n_verts", "<u4"), ("n_edges", "<u4"), ("n_ends", "<u4"), ("flags", "<u4"),
+                                ("shell", "<u4"), ("length_q32", "<i8"), ("area_q28", "<i8", (3,)), ("reserved", "<u8")])
+TOPOLOGY_SHELL_DTYPE = np.dtype([("first_vertex", "<u4"), ("n_verts", "<u4"), ("n_tris", "<u4"), ("flags", "<u4"), ("n_edges", "<u4"),
+                                 ("n_boundary", "<u4"), ("n_nonmanifold", "<u4"), ("n_miswound", "<u4"), ("n_loops", "<u4"), ("reserved0", "<u4"),
+                                 ("area_q32", "<i8"), ("volume_q40", "<i8"), ("reserved", "<u8")])
+assert (TOPOLOGY_EDGE_DTYPE.itemsize, TOPOLOGY_LOOP_DTYPE.itemsize, TOPOLOGY_SHELL_DTYPE.itemsize) == (32, 64, 64)
+
+
+class TopologyOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class TopologySummary(_Record):
+    _fields_ = [(k, C.c_uint64) for k in ("n_tris_valid", "n_tris_invalid", "n_tris_far", "n_verts_used", "n_edges", "n_interior", "n_boundary",
+                                          "n_nonmanifold", "n_miswound", "n_loops", "n_closed_loops", "n_shells", "n_watertight")] + [
+        ("reserved", C.c_uint64 * 3)]
+    DICT_FIELDS = [k for k, _ in _fields_[:13]]
+
+
+assert C.sizeof(TopologyOpts) == 16 and C.sizeof(TopologySummary) == 128
+
+
+def topology_opts():
+    """An hfpf_topology_opts (it has no settings yet)."""
+    return _sized(TopologyOpts)
+
+
+check_topology_opts = _opts_checker("topology")
+
+
 # hfpf_plan_opts.flags, hfpf_view_score and hfpf_tri_plan (include/hfpf.h)
 PLAN_TWO_SIDED, PLAN_MODEL_OCCLUDES = 1, 2
 VIEW_SCORE_DTYPE = np.dtype([("rank", "<i4"), ("n_in_view", "<u4"), ("n_facing", "<u4"), ("n_visible", "<u4"), ("visible_q40", "<u8"),
@@ -745,7 +783,7 @@ def lib():
     L = C.CDLL(LIB_PATH)
     vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32
     for name in ("hfpf_default_config", "hfpf_free_rows", "hfpf_free_mesh", "hfpf_free_components", "hfpf_free_deviation", "hfpf_free_coverage",
-                 "hfpf_free_plan", "hfpf_free_section", "hfpf_free_consistency", "hfpf_free_snapshot"):  # the void functions
+                 "hfpf_free_plan", "hfpf_free_section", "hfpf_free_topology", "hfpf_free_consistency", "hfpf_free_snapshot"):  # the void functions
         getattr(L, name).restype = None
     L.hfpf_default_config.argtypes = [C.POINTER(Config)]
     L.hfpf_abi_version.restype = C.c_int
@@ -833,6 +871,11 @@ def lib():
         fn.argtypes = [vp, C.POINTER(SectionOpts), vp, u64, u32, vp, u64, vp, vp, u32, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64),
                        C.POINTER(vp), C.POINTER(u64), vp, C.POINTER(SectionSummary)]
     L.hfpf_free_section.argtypes = [vp, vp, vp]
+    L.hfpf_check_topology_opts.argtypes = [C.POINTER(TopologyOpts)]
+    for fn in (L.hfpf_mesh_topology, L.hfpf_mesh_topology_device):
+        fn.argtypes = [vp, C.POINTER(TopologyOpts), vp, u64, u32, vp, u64, vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64),
+                       C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(TopologySummary)]
+    L.hfpf_free_topology.argtypes = [vp, vp, vp, vp]
     L.hfpf_free_deviation.argtypes = [vp, vp]
     L.hfpf_check_consistency_opts.argtypes = [C.POINTER(ConsistencyOpts)]
     for fn in (L.hfpf_depth_consistency, L.hfpf_depth_consistency_device):
@@ -1315,6 +1358,34 @@ class OccupancyGrid:
     def section_mesh_device(self, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose=None, planes=(), opts=None):
         """hfpf_section_mesh_device on a mesh in HBM (as extract_mesh_device leaves it): section_mesh(device=True)."""
         return self.section_mesh(dev_verts, dev_tris, pose, planes, device=True, opts=opts, n_verts=n_verts, vertex_stride=vertex_stride, n_tris=n_tris)
+
+    # -- open edges of a triangle mesh --
+    def mesh_topology(self, verts, tris, pose=None, device=False, opts=None, tri_shell=True, n_verts=None, vertex_stride=None, n_tris=None):
+        """Boundary loops, shells and watertightness of a triangle mesh (hfpf_mesh_topology): (edges of TOPOLOGY_EDGE_DTYPE, one per
+        edge that is not interior; loops of TOPOLOGY_LOOP_DTYPE; shells of TOPOLOGY_SHELL_DTYPE; uint32 tri_shell, one per triangle, or
+        None with tri_shell=False; summary dict).  verts, tris, pose and the device form's arguments as compare_mesh().  device=True
+        runs hfpf_mesh_topology_device and returns the three record arrays as (pointer, count) pairs in HBM and tri_shell as a pointer
+        (0 when not asked for): free the pointers with device_free (an empty array's is 0).  mesh_topology_device() is that form by
+        name."""
+        o = _or(opts, topology_opts)
+        pose = _pose12(pose, identity=True)
+        mesh, keep = _mesh_args(verts, tris, device, n_verts, vertex_stride, n_tris)
+        e, l, s, t, ne, nl, ns, summ = (C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_uint64(),
+                                        TopologySummary())
+        fn = lib().hfpf_mesh_topology_device if device else lib().hfpf_mesh_topology
+        self._chk(fn(self._h, C.byref(o), *mesh, _p(pose), C.byref(e), C.byref(ne), C.byref(l), C.byref(nl), C.byref(s), C.byref(ns),
+                     C.byref(t) if tri_shell else None, C.byref(summ)))
+        if device:
+            return (e.value or 0, ne.value), (l.value or 0, nl.value), (s.value or 0, ns.value), t.value or 0, summ.as_dict()
+        edges, loops, shells, per_tri = _copy_out([(e, ne.value, TOPOLOGY_EDGE_DTYPE, True), (l, nl.value, TOPOLOGY_LOOP_DTYPE, True),
+                                                   (s, ns.value, TOPOLOGY_SHELL_DTYPE, True), (t, mesh[4] if t.value else 0, np.uint32, tri_shell)],
+                                                  lib().hfpf_free_topology, e, l, s, t)  # mesh[4]: n_tris
+        return edges, loops, shells, per_tri, summ.as_dict()
+
+    def mesh_topology_device(self, dev_verts, n_verts, vertex_stride, dev_tris, n_tris, pose=None, opts=None, tri_shell=True):
+        """hfpf_mesh_topology_device on a mesh in HBM (as extract_mesh_device leaves it): mesh_topology(device=True)."""
+        return self.mesh_topology(dev_verts, dev_tris, pose, device=True, opts=opts, tri_shell=tri_shell, n_verts=n_verts, vertex_stride=vertex_stride,
+                                  n_tris=n_tris)
 
     # -- planning the next views against a reference mesh --
     def plan_views(self, verts, tris, poses, pose=None, device=False, opts=None, tri_plan=True, n_verts=None, vertex_stride=None, n_tris=None, **kw):

@@ -18,7 +18,7 @@ EXPORTS = ["hfpf_node_default_params", "hfpf_node_create", "hfpf_node_destroy", 
            "hfpf_node_get_stats", "hfpf_node_set_publisher", "hfpf_node_on_depth_image",
            "hfpf_node_set_mesh_output", "hfpf_node_save_session", "hfpf_node_load_session", "hfpf_node_set_component_filter",
            "hfpf_node_set_reference_mesh", "hfpf_node_set_reference_alignment", "hfpf_node_set_reference_coverage",
-           "hfpf_node_set_view_candidates", "hfpf_node_set_section_planes",
+           "hfpf_node_set_view_candidates", "hfpf_node_set_section_planes", "hfpf_node_set_mesh_topology",
            "hfpf_node_set_depth_consistency", "hfpf_node_set_hide_filtered", "hfpf_node_hide_box"]
 
 
@@ -69,6 +69,7 @@ def lib():
         L.hfpf_node_set_publisher.argtypes = [C.c_void_p, PUBLISH_FN, C.c_void_p]
         L.hfpf_node_set_mesh_output.argtypes = [C.c_void_p, C.POINTER(hfpf.MeshOpts)]
         L.hfpf_node_set_section_planes.argtypes = [C.c_void_p, C.POINTER(hfpf.SectionOpts), C.c_void_p, C.c_uint32]
+        L.hfpf_node_set_mesh_topology.argtypes = [C.c_void_p, C.POINTER(hfpf.TopologyOpts)]
         L.hfpf_node_set_component_filter.argtypes = [C.c_void_p, C.POINTER(hfpf.ComponentOpts)]
         L.hfpf_node_set_reference_mesh.argtypes = [C.c_void_p, C.POINTER(hfpf.DeviationOpts), C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
                                                    C.c_uint64, C.c_void_p]
@@ -191,6 +192,14 @@ class FusionNode:
         keywords turns it off."""
         o = opts if opts is not None else (hfpf.mesh_opts(**kw) if kw else None)
         rc = lib().hfpf_node_set_mesh_output(self._h, C.byref(o) if o is not None else None)
+        if rc < 0:
+            raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
+
+    def set_mesh_topology(self, on=True, opts=None):
+        """~process also writes mesh_edges.csv, mesh_loops.csv, mesh_shells.csv and mesh_topology_summary.csv: hfpf_mesh_topology_device
+        of the mesh it writes to mesh.ply; it needs set_mesh_output.  set_mesh_topology(False) turns it off."""
+        o = (opts if opts is not None else hfpf.topology_opts()) if on else None
+        rc = lib().hfpf_node_set_mesh_topology(self._h, C.byref(o) if o is not None else None)
         if rc < 0:
             raise hfpf.HfpfError(rc, lib().hfpf_node_last_error(self._h).decode())
 

@@ -1322,6 +1322,152 @@ int hfpf_section_mesh_device(hfpf_handle* h, const hfpf_section_opts* o, const v
                              hfpf_section_contour** dev_contours, uint64_t* n_contours, hfpf_section_plane* plane_recs,
                              hfpf_section_summary* summary);
 
+/* ---- open edges of a triangle mesh: boundary loops, shells, watertightness, area and volume (no reference counterpart) ----------------
+ * The first questions put to a scanned mesh: is it closed; if not, where are the holes and how long are their rims; if it is, what
+ * area and volume does it enclose; is it consistently wound.  A section answers them only in the planes the caller happened to
+ * choose; this read-out answers them for the whole mesh.  The mesh is any mesh, the model's own included (hfpf_extract_mesh_device
+ * leaves it in HBM, and the device form reads it there).  Every output is an integer reduction, a sort rank or a union-find label:
+ * nothing depends on scheduling, and everything is restatable from the arguments alone (tests/topology_ref.py); the fused model
+ * plays no part.
+ * Arithmetic: f64, one rounding per operation, left to right, never contracted; dot, cross, N and NN as the section and deviation
+ *   texts above define them.
+ * Mesh, pose, VALID, IN RANGE and FAR triangles: word for word those of the section "planar sections of a triangle mesh", the centre
+ *   c and the 32 m rule included; the device rejects an index out of range before it loads anything through it.  Invalid and far
+ *   triangles are skipped and counted (n_tris_invalid, n_tris_far; n_tris_valid counts the valid ones, far or not).  A USED triangle
+ *   is valid and in range; its three indices are distinct (a repeated one gives NN = 0).  n_verts <= 2^26 and 3 * n_tris < 2^32.
+ * Half-edges: used triangle k with the indices (i0, i1, i2) gives the half-edges 3k + c from i_c to i_(c+1 mod 3), c = 0, 1, 2.  The
+ *   EDGE of a half-edge is (va, vb) = (min, max) of its two indices; the half-edge is FORWARD iff i_c < i_(c+1).  Welding follows the
+ *   mesh's indices, as everywhere else: two vertices with equal coordinates but different indices are NOT merged, and a triangle soup
+ *   is all boundary.
+ * Edges: the distinct (va, vb), numbered in ascending (va, vb) order.  n_fwd and n_bwd count an edge's forward and backward
+ *   half-edges (each saturated at 65535 in the record, exact for the classification):
+ *     INTERIOR     n_fwd == 1 and n_bwd == 1           BOUNDARY   n_fwd + n_bwd == 1
+ *     NONMANIFOLD  n_fwd + n_bwd >= 3                  MISWOUND   n_fwd + n_bwd == 2, both in the same direction
+ *   (a triangle listed twice therefore shows as three MISWOUND edges).
+ * Shells: the connected components of the vertices of used triangles under "joined by a used triangle".  A shell's representative
+ *   is its smallest vertex index; shells are numbered by ascending representative; a vertex of no used triangle is in no shell.  Per
+ *   shell: n_verts, n_tris, n_edges, n_boundary, n_nonmanifold, n_miswound, n_loops; flags OPEN (n_boundary > 0), NONMANIFOLD
+ *   (n_nonmanifold > 0), MISWOUND (n_miswound > 0) and WATERTIGHT iff all three counts are 0.  With Pr the f64 point of the
+ *   representative and P0, P1, P2 those of a triangle's indices, over the shell's used triangles:
+ *     area_q32   += (int64)rint((0.5 * sqrt(NN)) * 2^32)
+ *     a = P0 - Pr; b = P1 - Pr; c = P2 - Pr;    volume_q40 += (int64)rint((dot(a, cross(b, c)) / 6.0) * 2^40)
+ *   The volume is reported for every shell and meaningful for a WATERTIGHT one: positive when the shell is wound outwards.
+ *   In-range coordinates keep a term below 2^16 m^3, so each fits an int64; the sums are two's-complement and wrap, and are right
+ *   whenever the true total fits.
+ * Loops: the connected components of the vertices of BOUNDARY edges under "joined by a boundary edge".  A loop's representative
+ *   is its smallest vertex index; loops are numbered by ascending representative.  A boundary edge runs from p0 to p1 as its one
+ *   half-edge runs (with its triangle's winding).  Per boundary vertex n_out counts the boundary edges that start there and n_in
+ *   those that end there.  A loop is CLOSED iff every vertex of it has n_in == 1 and n_out == 1; BRANCHED iff some vertex has
+ *   n_in > 1 or n_out > 1 (two holes that touch in a vertex, or mixed winding); n_ends = its vertices with n_in + n_out == 1;
+ *   shell = the shell of the representative (all of a loop's vertices share it).  Over the loop's edges, P0 and P1 the f64 points
+ *   of p0 and p1 and Pr the representative's:
+ *     e = P1 - P0;                    length_q32  += (int64)rint(sqrt(dot(e, e)) * 2^32)
+ *     X = cross(P0 - Pr, P1 - Pr);    area_q28[k] += (int64)rint((0.5 * X[k]) * 2^28), k = 0, 1, 2: the loop's vector area
+ *   The rim of a hole in an outward-wound surface runs clockwise seen from outside: its vector area points against the surface
+ *   normal.  The outer rim of a patch points along it; a lone triangle's loop has 0.5 * N.
+ * Records: one hfpf_topology_edge per edge that is NOT interior, in ascending (va, vb) order (p0, p1 = the half-edge's direction
+ *   for a BOUNDARY edge, (va, vb) otherwise; tri = the triangle of the edge's smallest half-edge id; uses = n_fwd | n_bwd << 16;
+ *   loop = 0xFFFFFFFF unless BOUNDARY); one hfpf_topology_loop per loop, one hfpf_topology_shell per shell; optionally tri_shell,
+ *   one uint32 per triangle: its shell, or 0xFFFFFFFF for a skipped one (not produced when its pointer is NULL; it is what lets a
+ *   caller drop small shells); one hfpf_topology_summary.  Reserved words are 0.  An array pointer is NULL exactly when its count
+ *   is 0 (tri_shell: n_tris).
+ * A call needs no fused model (an empty handle works) and changes nothing on the handle except device_bytes (its scratch); it
+ * returns when its outputs are complete.  Rejected with HFPF_ERR_BAD_ARG (the handle stays usable, nothing is written), all of it
+ * before anything is read through a mesh pointer: what hfpf_check_topology_opts rejects (struct_size != sizeof, flags or
+ * reserved != 0); every check hfpf_compare_mesh makes on the mesh and the pose; n_verts > 2^26; 3 * n_tris >= 2^32; a NULL output
+ * pointer (edges, n_edges, loops, n_loops, shells, n_shells, summary); for the device form verts or tris not 4-byte aligned.
+ * n_tris = 0 returns HFPF_OK with NULL arrays and a zeroed summary.  A handle with an RCCL communicator, or a failed handle, returns
+ * HFPF_ERR_STATE as the other mesh readers do.
+ * LIMITATION: welding is by index only.  Not provided: hole filling, repair, merging of coincident vertices. */
+#define HFPF_TOPOLOGY_BOUNDARY 1u    /* hfpf_topology_edge.kind */
+#define HFPF_TOPOLOGY_NONMANIFOLD 2u
+#define HFPF_TOPOLOGY_MISWOUND 3u
+#define HFPF_TOPOLOGY_LOOP_CLOSED 1u   /* hfpf_topology_loop.flags: every vertex has n_in == 1 and n_out == 1 */
+#define HFPF_TOPOLOGY_LOOP_BRANCHED 2u /* some vertex has n_in > 1 or n_out > 1 */
+#define HFPF_TOPOLOGY_SHELL_OPEN 1u        /* hfpf_topology_shell.flags: n_boundary > 0 */
+#define HFPF_TOPOLOGY_SHELL_NONMANIFOLD 2u /* n_nonmanifold > 0 */
+#define HFPF_TOPOLOGY_SHELL_MISWOUND 4u    /* n_miswound > 0 */
+#define HFPF_TOPOLOGY_SHELL_WATERTIGHT 8u  /* none of the three */
+#define HFPF_TOPOLOGY_NONE 0xFFFFFFFFu     /* no loop (hfpf_topology_edge.loop), no shell (tri_shell) */
+#define HFPF_TOPOLOGY_MAX_VERTS (1u << 26)
+
+typedef struct hfpf_topology_opts {
+    uint32_t struct_size;        /* = sizeof(hfpf_topology_opts) */
+    uint32_t flags;              /* 0 */
+    uint64_t reserved;           /* 0 */
+} hfpf_topology_opts;
+
+typedef struct hfpf_topology_edge { /* 32 bytes, one per edge that is not INTERIOR */
+    uint32_t p0, p1;             /* the half-edge's direction for BOUNDARY, (va, vb) otherwise */
+    uint32_t tri;                /* the triangle of the edge's smallest half-edge id */
+    uint32_t kind;               /* HFPF_TOPOLOGY_BOUNDARY, _NONMANIFOLD or _MISWOUND */
+    uint32_t uses;               /* n_fwd | n_bwd << 16, each saturated at 65535 */
+    uint32_t loop;               /* HFPF_TOPOLOGY_NONE unless BOUNDARY */
+    uint32_t shell;
+    uint32_t reserved;           /* 0 */
+} hfpf_topology_edge;
+
+typedef struct hfpf_topology_loop { /* 64 bytes */
+    uint32_t first_vertex;       /* the representative */
+    uint32_t n_verts, n_edges, n_ends;
+    uint32_t flags;              /* HFPF_TOPOLOGY_LOOP_* */
+    uint32_t shell;
+    int64_t length_q32;          /* / 2^32 m */
+    int64_t area_q28[3];         /* / 2^28 m^2: the vector area */
+    uint64_t reserved;           /* 0 */
+} hfpf_topology_loop;
+
+typedef struct hfpf_topology_shell { /* 64 bytes */
+    uint32_t first_vertex;       /* the representative */
+    uint32_t n_verts, n_tris;
+    uint32_t flags;              /* HFPF_TOPOLOGY_SHELL_* */
+    uint32_t n_edges, n_boundary, n_nonmanifold, n_miswound;
+    uint32_t n_loops;
+    uint32_t reserved0;          /* 0 */
+    int64_t area_q32;            /* / 2^32 m^2 */
+    int64_t volume_q40;          /* / 2^40 m^3 */
+    uint64_t reserved;           /* 0 */
+} hfpf_topology_shell;
+
+typedef struct hfpf_topology_summary { /* 128 bytes */
+    uint64_t n_tris_valid, n_tris_invalid, n_tris_far;
+    uint64_t n_verts_used;
+    uint64_t n_edges, n_interior, n_boundary, n_nonmanifold, n_miswound;
+    uint64_t n_loops, n_closed_loops;
+    uint64_t n_shells, n_watertight;
+    uint64_t reserved[3];        /* 0 */
+} hfpf_topology_summary;
+
+#ifdef __cplusplus
+static_assert(sizeof(hfpf_topology_opts) == 16, "hfpf_topology_opts is 16 bytes");
+static_assert(sizeof(hfpf_topology_edge) == 32, "hfpf_topology_edge is 32 bytes");
+static_assert(sizeof(hfpf_topology_loop) == 64, "hfpf_topology_loop is 64 bytes");
+static_assert(sizeof(hfpf_topology_shell) == 64, "hfpf_topology_shell is 64 bytes");
+static_assert(sizeof(hfpf_topology_summary) == 128, "hfpf_topology_summary is 128 bytes");
+#else
+_Static_assert(sizeof(hfpf_topology_opts) == 16, "hfpf_topology_opts is 16 bytes");
+_Static_assert(sizeof(hfpf_topology_edge) == 32, "hfpf_topology_edge is 32 bytes");
+_Static_assert(sizeof(hfpf_topology_loop) == 64, "hfpf_topology_loop is 64 bytes");
+_Static_assert(sizeof(hfpf_topology_shell) == 64, "hfpf_topology_shell is 64 bytes");
+_Static_assert(sizeof(hfpf_topology_summary) == 128, "hfpf_topology_summary is 128 bytes");
+#endif
+
+/* HFPF_OK if o passes the checks above, else HFPF_ERR_BAD_ARG (host code, no handle; the node shell uses it too). */
+int hfpf_check_topology_opts(const hfpf_topology_opts* o);
+/* Mesh, pose and outputs in HOST memory (the mesh is uploaded once per call, as hfpf_compare_mesh uploads it): *edges, *loops and
+ * *shells hold *n_edges, *n_loops and *n_shells records, *tri_shell (tri_shell may be NULL) n_tris words; hfpf_free_topology frees
+ * the four. */
+int hfpf_mesh_topology(hfpf_handle* h, const hfpf_topology_opts* o, const void* verts, uint64_t n_verts, uint32_t vertex_stride, const uint32_t* tris,
+                       uint64_t n_tris, const double* pose_3x4, hfpf_topology_edge** edges, uint64_t* n_edges, hfpf_topology_loop** loops, uint64_t* n_loops,
+                       hfpf_topology_shell** shells, uint64_t* n_shells, uint32_t** tri_shell, hfpf_topology_summary* summary);
+void hfpf_free_topology(hfpf_topology_edge* edges, hfpf_topology_loop* loops, hfpf_topology_shell* shells, uint32_t* tri_shell);
+/* The mesh is read in place from DEVICE memory (HBM); *dev_edges, *dev_loops, *dev_shells and *dev_tri_shell are device arrays,
+ * each freed by hfpf_device_free(h, p).  pose_3x4 and summary are in host memory. */
+int hfpf_mesh_topology_device(hfpf_handle* h, const hfpf_topology_opts* o, const void* dev_verts, uint64_t n_verts, uint32_t vertex_stride,
+                              const uint32_t* dev_tris, uint64_t n_tris, const double* pose_3x4, hfpf_topology_edge** dev_edges, uint64_t* n_edges,
+                              hfpf_topology_loop** dev_loops, uint64_t* n_loops, hfpf_topology_shell** dev_shells, uint64_t* n_shells,
+                              uint32_t** dev_tri_shell, hfpf_topology_summary* summary);
+
 /* ---- rows that later depth frames see through (the inverse of hfpf_render; no reference counterpart) ----------------------------
  * An occupancy grid keeps a voxel that was occupied once: a hand that crossed the view, a part that was moved, a slab of flying
  * pixels that passed the gate.  min_count cannot drop them when they were seen for many frames, hfpf_extract_components cannot when

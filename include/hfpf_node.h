@@ -105,6 +105,18 @@ int hfpf_node_set_mesh_output(hfpf_node* n, const hfpf_mesh_opts* opts);
  * normal of no finite length > 0 are refused with HFPF_ERR_BAD_ARG and leave the setting as it was. */
 int hfpf_node_set_section_planes(hfpf_node* n, const hfpf_section_opts* opts, const double* planes, uint32_t n_planes);
 
+/* EXTENSION: open edges of the saved mesh.  With mesh topology set and mesh output set, ~process also runs hfpf_mesh_topology_device
+ * (include/hfpf.h) on the mesh it writes to mesh.ply, read in HBM where hfpf_extract_mesh_device leaves it with the same options,
+ * identity pose, and writes beside it: mesh_edges.csv (header p0,p1,tri,kind,uses,loop,shell, then one line per edge that is not
+ * interior, in the call's order), mesh_loops.csv (header loop,first_vertex,n_verts,n_edges,n_ends,flags,shell,length_q32,area_q28_x,
+ * area_q28_y,area_q28_z), mesh_shells.csv (header shell,first_vertex,n_verts,n_tris,flags,n_edges,n_boundary,n_nonmanifold,n_miswound,
+ * n_loops,area_q32,volume_q40) and mesh_topology_summary.csv (header n_tris_valid,n_tris_invalid,n_tris_far,n_verts_used,n_edges,
+ * n_interior,n_boundary,n_nonmanifold,n_miswound,n_loops,n_closed_loops,n_shells,n_watertight, then one line); every value is an
+ * integer.  With mesh topology set and mesh output NOT set, ~process returns HFPF_ERR_STATE with success=false before it writes
+ * anything, and keeps the grid, exactly as with section planes.  NULL opts turns it off again, the default: none of the four files
+ * is then written.  Invalid options (hfpf_check_topology_opts) are refused with HFPF_ERR_BAD_ARG and leave the setting as it was. */
+int hfpf_node_set_mesh_topology(hfpf_node* n, const hfpf_topology_opts* opts);
+
 /* EXTENSION: with a component filter set, ~process saves the model without its specks: test_cloud.pcd and meta.csv (and the
  * published cloud) hold the rows hfpf_extract_components keeps with these options instead of every row.  mesh.ply and the
  * write_variants files are not filtered, unless hidden with hfpf_hide_voxels (hfpf_node_set_hide_filtered below does that for the
