@@ -1433,9 +1433,10 @@ int import_rank_slice_locked(hfpf_handle* h, const void* dev_buffer, uint64_t sl
 // rest of it is padding that is never read).
 int import_gathered_locked(hfpf_handle* h, const void* dev_buffer, uint64_t slice_stride_bytes, int world, int my_rank, const unsigned long long* counts)
 {
+    for (int r = 0; r < world; r++)  // every count is judged before any slice is imported: a refused call imports nothing
+        if (r != my_rank && counts[r] > slice_stride_bytes / sizeof(EpochRec)) return fail(h, HFPF_ERR_BAD_ARG, "gathered slice %d: %llu records do not fit the stride", r, counts[r]);
     for (int r = 0; r < world; r++) {
         if (r == my_rank) continue;
-        if (counts[r] * sizeof(EpochRec) > slice_stride_bytes) return fail(h, HFPF_ERR_BAD_ARG, "gathered slice %d: %llu records do not fit the stride", r, counts[r]);
         if (int rc = import_rank_slice_locked(h, dev_buffer, slice_stride_bytes, r, counts[r])) return rc;
     }
     return HFPF_OK;

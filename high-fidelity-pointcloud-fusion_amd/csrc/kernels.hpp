@@ -3567,7 +3567,9 @@ __global__ __launch_bounds__(256) void k_epoch_import(const GridParams g, const 
                 want = false;
             } else {
                 key_coords(g, r.key, x, y, z);
-                want = x <= g.dim[0] && y <= g.dim[1] && z <= g.dim[2];  // storage extent is dim+1 (grid.hpp:626)
+                // storage extent is dim+1 (grid.hpp:626): 0..dim is kept.  x is judged on the key's own bits: key_coords narrows
+                // them to int32, and a transport's key with more than 31 bits there would come out negative or as another cell's x
+                want = (r.key >> g.key_sx) <= (uint64_t)g.dim[0] && y <= g.dim[1] && z <= g.dim[2];
             }
         }
         const uint32_t bidx = want ? brick_index(g, x, y, z) : 0u;

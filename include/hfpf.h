@@ -1787,14 +1787,20 @@ int hfpf_dist_disable(hfpf_handle* h);
  * key, smallest frame id -- and two per frame integrated since the last exchange -- its viewpoint, which used to ride on every
  * cell record) -> import into every other rank -> hfpf_clean;
  * at the end add the ranks' hfpf_stats_export words and hand the totals to hfpf_extract_with_stats.
- * Exported pointers are device memory owned by the handle, valid until its next mutating call. */
+ * Exported pointers are device memory owned by the handle, valid until its next mutating call.
+ * What an import does with a record a transport hands in: a cell key is x << sx | y << sy | z with just enough bits per axis for
+ * 0..dim (hfpf_get_dims); storage is dim + 1 cells an axis, so a coordinate EQUAL to dim is kept and a key with a coordinate of
+ * dim + 1 or more -- x judged on all the key's bits above y -- is dropped.  A first_frame >= max_frames leaves the cell's latch as
+ * it was (the cell itself is still taken), and a frame record whose id is >= max_frames changes nothing.  None of these is an error.
+ * The cells an import adds count against max_normals * 4 and max_bricks like local ones: an overflow is HFPF_ERR_CAPACITY from
+ * the next call that reads the counters back (hfpf_clean), as for hfpf_integrate. */
 int hfpf_epoch_export(hfpf_handle* h, const void** dev_records, uint64_t* n_records);
 int hfpf_epoch_import(hfpf_handle* h, const void* dev_records, uint64_t n_records);
 /* Since ABI 3 the optional colour sums are words 5-7 of the same 8-word records: *dev_cwords is NULL, *n_cwords 0, and
  * hfpf_extract_with_stats ignores dev_cwords (both parameters are kept so that ABI-2 callers still link). */
 /* The receive side of a padded all-gather, as the RCCL path runs it: `world` slices of slice_stride_bytes each, slice r holding
- * counts[r] 32-byte records (padding behind them is never read); every slice but my_rank's is imported.  Unequal and zero
- * counts are the normal case. */
+ * counts[r] 16-byte records (padding behind them is never read); every slice but my_rank's is imported.  Unequal and zero
+ * counts are the normal case.  A foreign count that does not fit the stride is HFPF_ERR_BAD_ARG, and no slice is imported. */
 int hfpf_epoch_import_gathered(hfpf_handle* h, const void* dev_buffer, uint64_t slice_stride_bytes, int32_t world, int32_t my_rank,
                                const uint64_t* counts);
 int hfpf_stats_export(hfpf_handle* h, const void** dev_words, uint64_t* n_words, const void** dev_cwords, uint64_t* n_cwords);
