@@ -2,16 +2,19 @@
 // capture -> integrate -> clean -> extract path.  Only tests/, __graft_entry__.smoke() and
 // bench.py's cpu_baseline leg may load this; the product (libhfpf.so) never links or calls it.
 //
-// PARITY UNPINNED: the reference (REXJJ/high-fidelity-pointcloud-fusion) ships no tests, fixtures
-// or golden vectors, and cannot be built in this image (needs Eigen, PCL, ROS, Boost and the
-// un-vendored pointcloud_ros_utilities package; none present, no network).  This file is therefore
-// a restatement pinned only by reading the source.  Third-party leaves are restated from the
-// published algorithms of PCL 1.8 / Eigen 3.3 (the reference needs Eigen >= 3.3: the expression
+// PARITY: the reference (REXJJ/high-fidelity-pointcloud-fusion) ships no tests, fixtures or golden vectors.  Its node (node.cpp) needs
+// ROS, Boost and the un-vendored pointcloud_ros_utilities package and cannot be compiled here; its grid (grid.hpp), which holds
+// every rule restated below, CAN: oracle/ref_driver.cpp compiles it unmodified against the stand-in Eigen/PCL headers of
+// oracle/ref_shim into oracle/_ref/libhfpf_ref.so, and tests/test_reference_parity.py demands this file's occupied set, rows,
+// row order and dependant lists from it bit for bit (order_mode=1).  That pins control flow, state machine, clean order and
+// emit rule.  It does NOT pin the third-party leaves: they are stated once, in pcl_leaves.h, for this file and for the
+// stand-ins alike (common mode on purpose), restated from the published algorithms of PCL 1.8 / Eigen 3.3 (the reference needs
+// Eigen >= 3.3: the expression
 // `i*xres_*data->normal`, OccupancyGrid.hpp:405, mixes double and float scalars, which 3.2 rejects):
 //   pcl::transformPointCloud<PointT,double>      (call site node.cpp:289)
-//   pcl::computeMeanAndCovarianceMatrix (float)  (call site OccupancyGrid.hpp:302)
-//   pcl::eigen33 / computeRoots / computeRoots2  (call site OccupancyGrid.hpp:289)
-//   Eigen fixed-size-3 reductions: dot/squaredNorm evaluate c0 + (c1 + c2)
+//   pcl::computeMeanAndCovarianceMatrix (float)  (call site OccupancyGrid.hpp:302; pcl_leaves.h)
+//   pcl::eigen33 / computeRoots / computeRoots2  (call site OccupancyGrid.hpp:289; pcl_leaves.h)
+//   Eigen fixed-size-3 reductions: dot/squaredNorm evaluate c0 + (c1 + c2)  (pcl_leaves.h)
 //   atan2f/cosf/sinf: defined by det_math.h (see that header)
 //
 // File:line citations use these aliases:
@@ -51,19 +54,7 @@
 #include <unordered_set>
 #include <vector>
 
-#include "det_math.h"
-
-// -DORACLE_USE_LIBM swaps the three deterministic trig leaves for this machine's libm (sensitivity studies only:
-// tests/test_oracle_build_variants.py measures how many output rows depend on the last ulp of atan2f/cosf/sinf).
-#ifdef ORACLE_USE_LIBM
-#define ORACLE_ATAN2F(y, x) atan2f((y), (x))
-#define ORACLE_COSF(x) cosf((x))
-#define ORACLE_SINF(x) sinf((x))
-#else
-#define ORACLE_ATAN2F(y, x) odm_atan2f((y), (x))
-#define ORACLE_COSF(x) odm_cosf((x))
-#define ORACLE_SINF(x) odm_sinf((x))
-#endif
+#include "pcl_leaves.h"  // the PCL / Eigen leaves and the trig macros, shared with the compiled reference (oracle/ref_shim)
 
 namespace {
 
@@ -71,12 +62,7 @@ struct V3 {
     float x, y, z;
 };
 
-// Eigen fixed-size-3 reduction order: c0 + (c1 + c2).
-#ifdef ORACLE_SUM3_LEFT  // sensitivity study only: plain left-to-right order instead of Eigen's redux tree
-inline float sum3(float a, float b, float c) { return (a + b) + c; }
-#else
-inline float sum3(float a, float b, float c) { return a + (b + c); }
-#endif
+using hfpf_leaf::sum3;  // Eigen fixed-size-3 reduction order: c0 + (c1 + c2)
 inline float dot3(const V3& a, const V3& b) { return sum3(a.x * b.x, a.y * b.y, a.z * b.z); }
 inline V3 sub3(const V3& a, const V3& b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 inline V3 add3(const V3& a, const V3& b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
@@ -123,88 +109,14 @@ inline int to_int_x86(double v)
     return (int)v;
 }
 
-// ---- PCL leaves (restated; see header) -------------------------------------------------------
-
-// pcl::computeRoots2 (float)
-inline void compute_roots2(float b, float c, float roots[3])
-{
-    roots[0] = 0.0f;
-    float d = (float)((double)(b * b) - 4.0 * (double)c);
-    if ((double)d < 0.0) d = 0.0f;
-    float sd = sqrtf(d);
-    roots[2] = 0.5f * (b + sd);
-    roots[1] = 0.5f * (b - sd);
-}
-
-// pcl::computeRoots (float, symmetric 3x3 m)
-inline void compute_roots(const float m[3][3], float roots[3])
-{
-    float c0 = m[0][0] * m[1][1] * m[2][2] + 2.0f * m[0][1] * m[0][2] * m[1][2] - m[0][0] * m[1][2] * m[1][2] -
-               m[1][1] * m[0][2] * m[0][2] - m[2][2] * m[0][1] * m[0][1];
-    float c1 = m[0][0] * m[1][1] - m[0][1] * m[0][1] + m[0][0] * m[2][2] - m[0][2] * m[0][2] + m[1][1] * m[2][2] -
-               m[1][2] * m[1][2];
-    float c2 = m[0][0] + m[1][1] + m[2][2];
-
-    if (fabsf(c0) < FLT_EPSILON) {
-        compute_roots2(c2, c1, roots);
-        return;
-    }
-    const float s_inv3 = (float)(1.0 / 3.0);
-    const float s_sqrt3 = sqrtf(3.0f);
-    float c2_over_3 = c2 * s_inv3;
-    float a_over_3 = (c1 - c2 * c2_over_3) * s_inv3;
-    if (a_over_3 > 0.0f) a_over_3 = 0.0f;
-
-    float half_b = 0.5f * (c0 + c2_over_3 * (2.0f * c2_over_3 * c2_over_3 - c1));
-
-    float q = half_b * half_b + a_over_3 * a_over_3 * a_over_3;
-    if (q > 0.0f) q = 0.0f;
-
-    float rho = sqrtf(-a_over_3);
-    float theta = ORACLE_ATAN2F(sqrtf(-q), half_b) * s_inv3;
-    float cos_theta = ORACLE_COSF(theta);
-    float sin_theta = ORACLE_SINF(theta);
-    roots[0] = c2_over_3 + 2.0f * rho * cos_theta;
-    roots[1] = c2_over_3 - rho * (cos_theta + s_sqrt3 * sin_theta);
-    roots[2] = c2_over_3 - rho * (cos_theta - s_sqrt3 * sin_theta);
-
-    if (roots[0] >= roots[1]) std::swap(roots[0], roots[1]);
-    if (roots[1] >= roots[2]) {
-        std::swap(roots[1], roots[2]);
-        if (roots[0] >= roots[1]) std::swap(roots[0], roots[1]);
-    }
-    if (roots[0] <= 0.0f) compute_roots2(c2, c1, roots);
-}
-
-inline V3 cross3(const float a[3], const float b[3])
-{
-    return {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
-}
+// ---- PCL leaves: stated once in pcl_leaves.h, which the stand-in PCL of the compiled reference includes as well ----------------
 
 // pcl::eigen33(mat, eigenvalue, eigenvector): eigenvector of the smallest eigenvalue.
 inline V3 eigen33_smallest(const float mat[3][3])
 {
-    float scale = 0.0f;
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) scale = std::max(scale, fabsf(mat[i][j]));
-    if (scale <= FLT_MIN) scale = 1.0f;
-    float s[3][3];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) s[i][j] = mat[i][j] / scale;
-    float ev[3];
-    compute_roots(s, ev);
-    s[0][0] -= ev[0];
-    s[1][1] -= ev[0];
-    s[2][2] -= ev[0];
-    V3 vec1 = cross3(s[0], s[1]);
-    V3 vec2 = cross3(s[0], s[2]);
-    V3 vec3 = cross3(s[1], s[2]);
-    float len1 = dot3(vec1, vec1);
-    float len2 = dot3(vec2, vec2);
-    float len3 = dot3(vec3, vec3);
-    if (len1 >= len2 && len1 >= len3) return div3(vec1, sqrtf(len1));
-    if (len2 >= len1 && len2 >= len3) return div3(vec2, sqrtf(len2));
-    return div3(vec3, sqrtf(len3));
+    float value, v[3];
+    hfpf_leaf::eigen33_smallest(mat, value, v);
+    return {v[0], v[1], v[2]};
 }
 
 // grid.hpp:295-309 getNormal(cloud, normal) -> computeMeanAndCovarianceMatrix (single-pass float
@@ -212,36 +124,8 @@ inline V3 eigen33_smallest(const float mat[3][3])
 inline bool get_normal(const V3* pts, int n, V3& normal, bool shifted = false)
 {
     if (n < 3) return false;
-    float accu[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-#ifdef ORACLE_PCL_SHIFTED
-    shifted = true;
-#endif
-    // PCL >= 1.11 accumulates the moments of (p - K), K = first point; PCL <= 1.10 (assumed for the reference) uses K = 0
-    const V3 K = shifted ? pts[0] : V3{0.f, 0.f, 0.f};
-    for (int i = 0; i < n; i++) {
-        const float px = pts[i].x - K.x, py = pts[i].y - K.y, pz = pts[i].z - K.z;
-        accu[0] += px * px;
-        accu[1] += px * py;
-        accu[2] += px * pz;
-        accu[3] += py * py;
-        accu[4] += py * pz;
-        accu[5] += pz * pz;
-        accu[6] += px;
-        accu[7] += py;
-        accu[8] += pz;
-    }
-    const float fn = (float)n;
-    for (int j = 0; j < 9; j++) accu[j] /= fn;
-    float c[3][3];
-    c[0][0] = accu[0] - accu[6] * accu[6];
-    c[0][1] = accu[1] - accu[6] * accu[7];
-    c[0][2] = accu[2] - accu[6] * accu[8];
-    c[1][1] = accu[3] - accu[7] * accu[7];
-    c[1][2] = accu[4] - accu[7] * accu[8];
-    c[2][2] = accu[5] - accu[8] * accu[8];
-    c[1][0] = c[0][1];
-    c[2][0] = c[0][2];
-    c[2][1] = c[1][2];
+    float c[3][3], mean[3];
+    hfpf_leaf::mean_and_covariance(&pts[0].x, 3, (size_t)n, shifted, c, mean);
     normal = eigen33_smallest(c);
     return true;
 }
@@ -1263,6 +1147,22 @@ uint64_t horacle_dependants(void* h, int32_t x, int32_t y, int32_t z, int32_t* x
         for (uint64_t i = 0; i < std::min(n, cap); i++)
             Oracle::own_coords(v.data->dependants[i], xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
     return n;
+}
+
+// the cells that hold a non-empty dependants list, occupied or not, ascending key; returns their number
+uint64_t horacle_dependant_cells(void* h, int32_t* xyz, uint64_t cap)
+{
+    Oracle* o = (Oracle*)h;
+    std::vector<uint64_t> keys;
+    o->for_each_voxel([&](uint64_t key, const Voxel& v) {
+        if (v.data && !v.data->dependants.empty()) keys.push_back(key);
+    });
+    std::sort(keys.begin(), keys.end());
+    if (xyz) {
+        uint64_t n = std::min<uint64_t>(cap, keys.size());
+        for (uint64_t i = 0; i < n; i++) Oracle::own_coords(keys[i], xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+    }
+    return keys.size();
 }
 
 // ---- leaf probes (unit tests and GPU leaf-parity tests) ----

@@ -99,6 +99,8 @@ def lib():
         L.horacle_occupied.restype = C.c_uint64
         L.horacle_dependants.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64]
         L.horacle_dependants.restype = C.c_uint64
+        L.horacle_dependant_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.horacle_dependant_cells.restype = C.c_uint64
         L.horacle_probe_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.horacle_probe_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.horacle_probe_center.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -277,6 +279,14 @@ class OracleGrid:
         out = np.zeros((n, 3), dtype=np.int32)
         if n:
             lib().horacle_dependants(self._h, x, y, z, _p(out), n)
+        return out
+
+    def dependant_cells(self):
+        """The cells that hold a non-empty dependants list, occupied or not, ascending (x, y, z)."""
+        n = lib().horacle_dependant_cells(self._h, None, 0)
+        out = np.zeros((n, 3), dtype=np.int32)
+        if n:
+            lib().horacle_dependant_cells(self._h, _p(out), n)
         return out
 
     # ---- leaf probes ----

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Generates tests/golden/*.npz from the CPU oracle (run from the repo root: python tests/golden/make_golden.py).
 
-The reference ships no golden vectors and cannot be built or imported here (C++ needing Eigen/PCL/ROS), so these
-fixtures are produced by OUR restatement (oracle/hfpf_oracle.cpp): they pin the oracle against regressions and
-give the GPU engine a second, oracle-independent-at-runtime target.  "parity unpinned" still applies.
+The reference ships no golden vectors, so these fixtures are produced by OUR restatement (oracle/hfpf_oracle.cpp): they
+pin the oracle against regressions and give the GPU engine a second, oracle-independent-at-runtime target.  (The reference's
+node needs ROS and cannot be built; its grid can: reference_*.npz beside these files hold what the compiled reference grid
+itself computed, see make_reference_golden.py and DESIGN.md section 2.)
 Inputs are seeded; the scene fixtures store a SHA-256 of the generated frames so a drifting generator is caught.
 """
 import hashlib
