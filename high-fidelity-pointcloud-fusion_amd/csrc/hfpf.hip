@@ -31,7 +31,6 @@
 #include <vector>
 
 #include "../../include/hfpf.h"
-#include "../../include/hfpf_probe.h"
 #include "host_plan.hpp"
 #include "kernels.hpp"
 #include "scratch_layout.hpp"
@@ -5151,274 +5150,6 @@ int hfpf_device_download(hfpf_handle* h, void* host_dst, const void* dev_src, ui
 
 void hfpf_free_rows(hfpf_row* rows) { free(rows); }
 
-
-}  // extern "C" (the helper below is a template)
-
-namespace {
-// Formats rows [0,n) with `fmt_row` on several host threads (one contiguous chunk each) and writes the chunks in
-// order: ASCII formatting, not I/O, dominates the reference's savePCDFileASCII-style outputs.
-template <typename F>
-bool write_rows_parallel(FILE* f, uint64_t n, size_t bytes_per_row_hint, F fmt_row)
-{
-    if (n == 0) return true;
-    unsigned hw = std::thread::hardware_concurrency();
-    const unsigned n_thr = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(std::min<unsigned>(hw ? hw : 1, 16), n / 4096 + 1));
-    std::vector<std::string> parts(n_thr);
-    std::vector<std::thread> thr;
-    const uint64_t per = (n + n_thr - 1) / n_thr;
-    for (unsigned t = 0; t < n_thr; t++) {
-        thr.emplace_back([&, t] {
-            const uint64_t a = t * per, b = std::min<uint64_t>(n, a + per);
-            std::string& s = parts[t];
-            if (b > a) s.reserve((size_t)(b - a) * bytes_per_row_hint);
-            char line[256];
-            for (uint64_t i = a; i < b; i++) {
-                const int len = fmt_row(i, line, sizeof line);
-                if (len > 0) s.append(line, (size_t)len);
-            }
-        });
-    }
-    for (auto& t : thr) t.join();
-    for (auto& s : parts)
-        if (!s.empty() && fwrite(s.data(), 1, s.size(), f) != s.size()) return false;
-    return true;
-}
-}  // namespace
-
-extern "C" {
-
-int hfpf_write_pcd(const hfpf_row* rows, uint64_t n, const char* path)
-{
-    if (!path || (!rows && n)) return HFPF_ERR_BAD_ARG;
-    FILE* f = fopen(path, "w");
-    if (!f) return HFPF_ERR_IO;
-    // PCL PCDWriter::writeASCII layout for PointXYZRGBNormal (pcl::io::savePCDFileASCII, grid.hpp:485), precision 8.
-    fprintf(f, "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb normal_x normal_y normal_z curvature\n");
-    fprintf(f, "SIZE 4 4 4 4 4 4 4 4\nTYPE F F F U F F F F\nCOUNT 1 1 1 1 1 1 1 1\n");
-    fprintf(f, "WIDTH %llu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %llu\nDATA ascii\n", (unsigned long long)n, (unsigned long long)n);
-    // the reference never writes rgb (grid.hpp:471-479): a default-constructed PCL point has r=g=b=0, a=255
-    bool ok = write_rows_parallel(f, n, 96, [rows](uint64_t i, char* line, size_t cap) {
-        const hfpf_row& r = rows[i];
-        return snprintf(line, cap, "%.8g %.8g %.8g %u %.8g %.8g %.8g 0\n", r.x, r.y, r.z, 0xFF000000u | r.rgb, r.nx, r.ny, r.nz);
-    });
-    ok = ok && !ferror(f);
-    return (fclose(f) == 0 && ok) ? HFPF_OK : HFPF_ERR_IO;
-}
-
-int hfpf_write_meta_csv(const hfpf_row* rows, uint64_t n, const char* path)
-{
-    if (!path || (!rows && n)) return HFPF_ERR_BAD_ARG;
-    FILE* f = fopen(path, "w");
-    if (!f) return HFPF_ERR_IO;
-    fprintf(f, "Id,sdx,sdy,sdz,mean distance from normal, distance from normal sd, points in cylinder\n");  // grid.hpp:462 verbatim
-    // default ostream float formatting = %g (6 significant digits), grid.hpp:478
-    bool ok = write_rows_parallel(f, n, 80, [rows](uint64_t i, char* line, size_t cap) {
-        const hfpf_row& r = rows[i];
-        return snprintf(line, cap, "%llu,%g,%g,%g,%g,%g,%d\n", (unsigned long long)i, r.sdx, r.sdy, r.sdz, r.mean_dist, r.sd_dist, (int)r.count);
-    });
-    ok = ok && !ferror(f);
-    return (fclose(f) == 0 && ok) ? HFPF_OK : HFPF_ERR_IO;
-}
-
-// downloadHQ / downloadClassified / download(XYZRGB) (grid.hpp:491-575; only referenced inside `#if 0`, node.cpp:399-437)
-// as one writer over already extracted rows: PointXYZRGB cloud, optional count filter and colour coding.
-int hfpf_write_pcd_xyzrgb(const hfpf_row* rows, uint64_t n, const char* path, uint32_t min_count, int32_t classify_threshold, int32_t white)
-{
-    if (!path || (!rows && n)) return HFPF_ERR_BAD_ARG;
-    uint64_t kept = 0;
-    for (uint64_t i = 0; i < n; i++) kept += rows[i].count >= min_count ? 1 : 0;  // `if(data->count<threshold) continue;` grid.hpp:561
-    FILE* f = fopen(path, "w");
-    if (!f) return HFPF_ERR_IO;
-    fprintf(f, "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb\nSIZE 4 4 4 4\nTYPE F F F U\nCOUNT 1 1 1 1\n");
-    fprintf(f, "WIDTH %llu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %llu\nDATA ascii\n", (unsigned long long)kept, (unsigned long long)kept);
-    for (uint64_t i = 0; i < n; i++) {
-        const hfpf_row& r = rows[i];
-        if (r.count < min_count) continue;
-        uint32_t rgb = white ? 0x00FFFFFFu : r.rgb;                                                // pt.r=g=b=255, grid.hpp:527-529,558-560
-        if (classify_threshold >= 0 && (int64_t)r.count > (int64_t)classify_threshold) rgb = 0x00FF0000u;  // g=b=0, grid.hpp:530-534
-        fprintf(f, "%.8g %.8g %.8g %u\n", r.x, r.y, r.z, 0xFF000000u | rgb);
-    }
-    const bool ok = !ferror(f);
-    return (fclose(f) == 0 && ok) ? HFPF_OK : HFPF_ERR_IO;
-}
-
-// A mesh as binary little-endian PLY: 27 bytes a vertex (x y z nx ny nz as f32, red green blue), 13 a face (count 3, three u32).
-int hfpf_write_ply(const hfpf_mesh_vertex* verts, uint64_t n_verts, const uint32_t* tris, uint64_t n_tris, const char* path)
-{
-    if (!path || (!verts && n_verts) || (!tris && n_tris)) return HFPF_ERR_BAD_ARG;
-    FILE* f = fopen(path, "wb");
-    if (!f) return HFPF_ERR_IO;
-    fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %llu\nproperty float x\nproperty float y\nproperty float z\n"
-               "property float nx\nproperty float ny\nproperty float nz\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n"
-               "element face %llu\nproperty list uchar uint vertex_indices\nend_header\n",
-            (unsigned long long)n_verts, (unsigned long long)n_tris);
-    constexpr uint64_t kChunk = 1u << 16;
-    std::vector<uint8_t> buf(kChunk * 27);
-    bool ok = true;
-    for (uint64_t i0 = 0; i0 < n_verts && ok; i0 += kChunk) {
-        const uint64_t n = std::min(kChunk, n_verts - i0);
-        uint8_t* o = buf.data();
-        for (uint64_t i = i0; i < i0 + n; i++, o += 27) {
-            const hfpf_mesh_vertex& v = verts[i];
-            memcpy(o, &v.x, 24);  // x y z nx ny nz
-            o[24] = (uint8_t)(v.rgb >> 16), o[25] = (uint8_t)(v.rgb >> 8), o[26] = (uint8_t)v.rgb;
-        }
-        ok = fwrite(buf.data(), 27, n, f) == n;
-    }
-    for (uint64_t i0 = 0; i0 < n_tris && ok; i0 += kChunk) {
-        const uint64_t n = std::min(kChunk, n_tris - i0);
-        uint8_t* o = buf.data();
-        for (uint64_t i = i0; i < i0 + n; i++, o += 13) {
-            o[0] = 3;
-            memcpy(o + 1, tris + 3 * i, 12);
-        }
-        ok = fwrite(buf.data(), 13, n, f) == n;
-    }
-    ok = ok && !ferror(f);
-    return (fclose(f) == 0 && ok) ? HFPF_OK : HFPF_ERR_IO;
-}
-
-// The inverse of hfpf_write_ply (include/hfpf.h).  The header is parsed line by line; the vertex and face counts are checked against
-// the bytes the file has left before anything is allocated.
-int hfpf_read_ply(const char* path, hfpf_mesh_vertex** verts, uint64_t* n_verts, uint32_t** tris, uint64_t* n_tris)
-{
-    if (!path || !verts || !n_verts || !tris || !n_tris) return HFPF_ERR_BAD_ARG;
-    *verts = nullptr, *tris = nullptr, *n_verts = 0, *n_tris = 0;
-    FILE* f = fopen(path, "rb");
-    if (!f) return fail(nullptr, HFPF_ERR_IO, "read_ply: cannot open %s", path);
-    hfpf_mesh_vertex* hv = nullptr;
-    uint32_t* ht = nullptr;
-    auto bad = [&](const char* what) {
-        fclose(f);
-        free(hv), free(ht);
-        return fail(nullptr, HFPF_ERR_IO, "read_ply: %s: %s", path, what);
-    };
-    if (fseek(f, 0, SEEK_END) != 0) return bad("not seekable");
-    const long end = ftell(f);
-    if (end < 0 || fseek(f, 0, SEEK_SET) != 0) return bad("not seekable");
-    auto type_size = [](const char* t) -> int {
-        static const struct { const char* name; int size; } kTypes[] = {{"char", 1}, {"int8", 1}, {"uchar", 1}, {"uint8", 1}, {"short", 2}, {"int16", 2},
-            {"ushort", 2}, {"uint16", 2}, {"int", 4}, {"int32", 4}, {"uint", 4}, {"uint32", 4}, {"float", 4}, {"float32", 4}, {"double", 8}, {"float64", 8}};
-        for (const auto& k : kTypes)
-            if (strcmp(t, k.name) == 0) return k.size;
-        return 0;
-    };
-    auto is_float = [](const char* t) { return strcmp(t, "float") == 0 || strcmp(t, "float32") == 0; };
-    auto is_uchar = [](const char* t) { return strcmp(t, "uchar") == 0 || strcmp(t, "uint8") == 0; };
-    char line[512];
-    if (!fgets(line, sizeof line, f) || strncmp(line, "ply", 3) != 0) return bad("not a PLY file");
-    int element = 0;  // 0 = none yet, 1 = vertex, 2 = face, 3 = one behind them
-    bool format_ok = false, ended = false, face_list = false;
-    unsigned long long nv = 0, nt = 0;
-    int vsize = 0, off[9] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};  // x y z nx ny nz red green blue: byte offsets in a vertex record
-    static const char* const kNames[9] = {"x", "y", "z", "nx", "ny", "nz", "red", "green", "blue"};
-    for (int n_lines = 0; n_lines < 4096 && fgets(line, sizeof line, f); n_lines++) {
-        char a[64] = "", b[64] = "", c[64] = "", d[64] = "", e[64] = "";
-        const int nf = sscanf(line, "%63s %63s %63s %63s %63s", a, b, c, d, e);
-        if (nf < 1 || strcmp(a, "comment") == 0 || strcmp(a, "obj_info") == 0) continue;
-        if (strcmp(a, "end_header") == 0) {
-            ended = true;
-            break;
-        }
-        if (strcmp(a, "format") == 0) {
-            if (nf < 3 || strcmp(b, "binary_little_endian") != 0 || strcmp(c, "1.0") != 0) return bad("only format binary_little_endian 1.0 is read");
-            format_ok = true;
-        } else if (strcmp(a, "element") == 0) {
-            char* tail = nullptr;
-            const unsigned long long cnt = nf >= 3 ? strtoull(c, &tail, 10) : 0;
-            if (nf < 3 || !tail || *tail || c[0] == '-') return bad("malformed element line");
-            if (element == 0 && strcmp(b, "vertex") == 0) element = 1, nv = cnt;
-            else if (element == 1 && strcmp(b, "face") == 0) element = 2, nt = cnt;
-            else if (element >= 2) element = 3;
-            else return bad("the vertex element must come first and the face element second");
-        } else if (strcmp(a, "property") == 0) {
-            if (element == 1) {
-                const int sz = nf >= 3 ? type_size(b) : 0;
-                if (!sz) return bad("a vertex property must be a scalar of a known type");
-                for (int k = 0; k < 9; k++)
-                    if (strcmp(c, kNames[k]) == 0 && (k < 6 ? is_float(b) : is_uchar(b))) off[k] = vsize;
-                vsize += sz;
-            } else if (element == 2) {
-                const bool ok = nf >= 5 && strcmp(b, "list") == 0 && is_uchar(c) && (strcmp(d, "uint") == 0 || strcmp(d, "int") == 0 || strcmp(d, "uint32") == 0 ||
-                                                                                    strcmp(d, "int32") == 0) &&
-                                (strcmp(e, "vertex_indices") == 0 || strcmp(e, "vertex_index") == 0);
-                if (!ok || face_list) return bad("the face element must be one property list uchar uint|int vertex_indices");
-                face_list = true;
-            } else if (element == 0) {
-                return bad("a property outside an element");
-            }
-        } else {
-            return bad("unknown header line");
-        }
-    }
-    if (!ended || !format_ok) return bad("incomplete header");
-    if (element < 1 || off[0] < 0 || off[1] < 0 || off[2] < 0) return bad("the vertex element needs float x, y, z");
-    if (nt && !face_list) return bad("the face element has no vertex_indices list");
-    const long at = ftell(f);
-    if (at < 0) return bad("not seekable");
-    const unsigned long long left = (unsigned long long)(end - at);
-    if (nv >= 0xFFFFFFFFull || nt >= 0xFFFFFFFFull) return bad("more than 2^32 - 2 vertices or faces");
-    if (nv * (unsigned long long)vsize > left || nt * 13ull > left - nv * (unsigned long long)vsize) return bad("the file is shorter than its header claims");
-    hv = (hfpf_mesh_vertex*)malloc(std::max<size_t>((size_t)nv * sizeof(hfpf_mesh_vertex), 1));
-    ht = (uint32_t*)malloc(std::max<size_t>((size_t)nt * 12, 1));
-    if (!hv || !ht) return bad("out of memory");
-    constexpr uint64_t kChunk = 1u << 14;
-    std::vector<uint8_t> buf((size_t)kChunk * std::max(vsize, 13));
-    for (uint64_t i0 = 0; i0 < nv; i0 += kChunk) {
-        const uint64_t n = std::min<uint64_t>(kChunk, nv - i0);
-        if (fread(buf.data(), (size_t)vsize, n, f) != n) return bad("truncated vertex data");
-        for (uint64_t i = 0; i < n; i++) {
-            const uint8_t* r = buf.data() + i * (size_t)vsize;
-            hfpf_mesh_vertex v;
-            memset(&v, 0, sizeof v);
-            float* dst[6] = {&v.x, &v.y, &v.z, &v.nx, &v.ny, &v.nz};
-            for (int k = 0; k < 6; k++)
-                if (off[k] >= 0) memcpy(dst[k], r + off[k], 4);
-            for (int k = 6; k < 9; k++)
-                if (off[k] >= 0) v.rgb |= (uint32_t)r[off[k]] << (8 * (8 - k));
-            hv[i0 + i] = v;
-        }
-    }
-    for (uint64_t i0 = 0; i0 < nt; i0 += kChunk) {
-        const uint64_t n = std::min<uint64_t>(kChunk, nt - i0);
-        if (fread(buf.data(), 13, n, f) != n) return bad("truncated face data");
-        for (uint64_t i = 0; i < n; i++) {
-            const uint8_t* r = buf.data() + i * 13;
-            if (r[0] != 3) return bad("a face that is not a triangle");
-            memcpy(ht + 3 * (i0 + i), r + 1, 12);
-        }
-    }
-    fclose(f);
-    *verts = hv, *tris = ht, *n_verts = nv, *n_tris = nt;
-    return HFPF_OK;
-}
-
-// Same fields as hfpf_write_pcd with DATA binary (40 bytes/point): for outputs where ASCII formatting would dominate.
-int hfpf_write_pcd_binary(const hfpf_row* rows, uint64_t n, const char* path)
-{
-    if (!path || (!rows && n)) return HFPF_ERR_BAD_ARG;
-    FILE* f = fopen(path, "wb");
-    if (!f) return HFPF_ERR_IO;
-    fprintf(f, "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb normal_x normal_y normal_z curvature\n");
-    fprintf(f, "SIZE 4 4 4 4 4 4 4 4\nTYPE F F F U F F F F\nCOUNT 1 1 1 1 1 1 1 1\n");
-    fprintf(f, "WIDTH %llu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %llu\nDATA binary\n", (unsigned long long)n, (unsigned long long)n);
-    std::vector<char> buf;
-    buf.reserve(32 * 4096);
-    for (uint64_t i = 0; i < n; i++) {
-        const hfpf_row& r = rows[i];
-        const float zero = 0.f;
-        const uint32_t rgba = 0xFF000000u | r.rgb;
-        const void* fields[8] = {&r.x, &r.y, &r.z, &rgba, &r.nx, &r.ny, &r.nz, &zero};
-        for (int k = 0; k < 8; k++) buf.insert(buf.end(), (const char*)fields[k], (const char*)fields[k] + 4);
-        if (buf.size() >= 32 * 4096 || i + 1 == n) {
-            fwrite(buf.data(), 1, buf.size(), f);
-            buf.clear();
-        }
-    }
-    const bool ok = !ferror(f);
-    return (fclose(f) == 0 && ok) ? HFPF_OK : HFPF_ERR_IO;
-}
-
 // hfpf_clear under the handle's lock (hfpf_restore begins with it).
 static int clear_locked(hfpf_handle* h)
 {
@@ -5440,650 +5171,6 @@ int hfpf_clear(hfpf_handle* h)
     std::lock_guard<std::mutex> lk(h->mtx);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     return clear_locked(h);
-}
-
-// ---- snapshot / restore (include/hfpf.h) -----------------------------------------------------------------
-// A blob = a 4096-byte header + the payload: sections, each 256-byte aligned, listed in the header as (id, offset, bytes).  The
-// payload is what the staging buffer on the device holds: the pack kernels (kernels.hpp k_snap_*) gather the used prefix of every
-// pool into it and it crosses the link through download_pageable / upload_pageable, whole or in windows.
-}  // extern "C"
-namespace {
-
-constexpr uint32_t kSnapVersion = 1;
-constexpr uint32_t kSnapLayoutRev = 2;  // bump when a table's meaning changes without its shape changing (2: the colour log's section is sized by the total)
-constexpr uint64_t kSnapLayoutTag = ((uint64_t)kSnapLayoutRev << 48) | ((uint64_t)kChains << 40) | ((uint64_t)kLogRegions << 32) | ((uint64_t)kStatWords << 24) |
-                                    ((uint64_t)sizeof(DepEntry) << 16) | ((uint64_t)C_COUNT << 8) | (uint64_t)kBrickShift;
-constexpr char kSnapMagic[8] = {'H', 'F', 'P', 'F', 'S', 'N', 'A', 'P'};
-constexpr uint32_t kSnapMaxSections = 32;
-constexpr uint32_t kSnapSemanticFlags = HFPF_FLAG_FUSE_COLOR | HFPF_FLAG_PCL_SHIFTED_COV;
-
-enum SnapSectionId : uint32_t {
-    SS_CTR = 1, SS_LOG_CTR, SS_INFO, SS_FIRST_FRAME, SS_BUF_HEAD, SS_STAT_ID, SS_PRE_DEP, SS_OCC_MASK, SS_ND_MASK, SS_BRICKS, SS_LOG_PT, SS_LOG_RGB,
-    SS_NV_KEY, SS_NV_SLOT, SS_NV_C, SS_NV_N, SS_NV_LINE, SS_STATS, SS_REG_OCC, SS_DEP, SS_OCC_LIST, SS_PREREG, SS_FRAMES, SS_PEND,
-    SS_HIDDEN  // the HIDDEN bits of hfpf_hide_*, 64 bytes per brick; the last section, present only when something is hidden
-};
-struct SnapSection {
-    uint32_t id, reserved;
-    uint64_t offset, bytes;  // offset into the payload (a multiple of 256); bytes without the padding behind them
-};
-struct SnapHeader {  // at the front of the 4096 header bytes; the rest of them is zero.  Every field is naturally aligned: no padding.
-    char magic[8];
-    uint32_t version, header_bytes;
-    uint64_t layout_tag, total_bytes, payload_bytes, payload_checksum, header_checksum;  // header_checksum: over the 4096 bytes with this field 0
-    float resolution;
-    uint32_t flags;
-    double bbox[6];
-    int32_t k, K, gate, reserved0;
-    double cylinder_radius, ball_radius, z_clip_min, z_clip_max;
-    uint64_t need_bricks, log_points, need_normals, need_frames;
-    uint64_t frames_integrated, clean_passes, next_frame_id, voxels_occupied, voxels_with_normal;
-    uint32_t dirty, pend_valid, normals_possible, n_sections;
-    uint64_t gate_done, direct_linked;
-    uint64_t n_bricks, n_normals, n_occ, n_reg, n_prereg, n_dep, n_frames, n_pend;
-    uint64_t n_linked[kLogRegions], log_n[kLogRegions];
-    SnapSection sec[kSnapMaxSections];
-};
-static_assert(sizeof(SnapHeader) <= HFPF_SNAPSHOT_HEADER_BYTES, "the snapshot header has a fixed size");
-static_assert(sizeof(struct hfpf_snapshot_info) == 248, "hfpf_snapshot_info layout");
-
-// 64-bit checksum of n bytes (n a multiple of 32: sections are 256-byte aligned): four interleaved multiply-xorshift lanes over the
-// 8-byte words, folded at the end.  Not cryptographic: it catches truncation, bit rot and mixed-up files.
-uint64_t snap_checksum(const void* data, uint64_t n)
-{
-    const uint64_t kMul = 0x9E3779B97F4A7C15ull;
-    uint64_t a = 0x243F6A8885A308D3ull, b = 0x13198A2E03707344ull, c = 0xA4093822299F31D0ull, d = 0x082EFA98EC4E6C89ull;
-    const uint8_t* p = (const uint8_t*)data;
-    for (uint64_t i = 0; i + 32 <= n; i += 32) {
-        uint64_t w[4];
-        memcpy(w, p + i, 32);
-        a = (a ^ w[0]) * kMul, a ^= a >> 29;
-        b = (b ^ w[1]) * kMul, b ^= b >> 29;
-        c = (c ^ w[2]) * kMul, c ^= c >> 29;
-        d = (d ^ w[3]) * kMul, d ^= d >> 29;
-    }
-    uint64_t r = n;
-    for (uint64_t v : {a, b, c, d}) r = (r ^ v) * kMul, r ^= r >> 32;
-    return r;
-}
-
-uint64_t snap_header_checksum(const uint8_t* hdr)
-{
-    uint8_t tmp[HFPF_SNAPSHOT_HEADER_BYTES];
-    memcpy(tmp, hdr, sizeof tmp);
-    memset(tmp + offsetof(SnapHeader, header_checksum), 0, 8);
-    return snap_checksum(tmp, sizeof tmp);
-}
-
-// The header of a blob, validated as far as the header alone allows: 0, or why not (a static text).
-const char* snap_parse_header(const void* blob, uint64_t bytes, SnapHeader* hd)
-{
-    if (!blob || bytes < HFPF_SNAPSHOT_HEADER_BYTES) return "shorter than a snapshot header";
-    memcpy(hd, blob, sizeof *hd);
-    if (memcmp(hd->magic, kSnapMagic, 8) != 0) return "not a snapshot (magic)";
-    if (hd->version != kSnapVersion || hd->header_bytes != HFPF_SNAPSHOT_HEADER_BYTES) return "unknown snapshot format version";
-    if (hd->header_checksum != snap_header_checksum((const uint8_t*)blob)) return "header checksum mismatch";
-    if (hd->n_sections > kSnapMaxSections || hd->total_bytes != hd->payload_bytes + HFPF_SNAPSHOT_HEADER_BYTES || (hd->payload_bytes & 255u)) return "inconsistent header";
-    return nullptr;
-}
-
-// How much of every pool a session used (from the counters at snapshot, from the header at restore).
-struct SnapUsed {
-    uint64_t n_bricks, n_normals, n_occ, n_reg, n_prereg, n_dep, n_frames, n_pend;
-    uint64_t log_n[kLogRegions];
-    bool hidden;  // the session hides rows: the blob carries SS_HIDDEN (snapshot: Session::n_hidden; restore: the header lists the section)
-};
-
-inline uint64_t up16(uint64_t v) { return (v + 15) & ~15ull; }
-inline uint64_t up256(uint64_t v) { return (v + 255) & ~255ull; }
-// bytes in front of append region r of the colour log that make its first entry's unit 16-byte aligned (entries are 1-based)
-inline uint32_t snap_rgb_head(uint64_t region_cap, int r) { return (uint32_t)((((uint64_t)r * region_cap + 1) & 3u) * 4u); }
-
-// The sections of a session, in file order; the same function lays a blob out at snapshot and reads it back at restore.
-uint32_t snap_layout(const SnapUsed& u, bool color, uint64_t region_cap, SnapSection* sec, uint64_t* payload_bytes)
-{
-    const uint64_t cells = u.n_bricks * (uint64_t)kBrickCells, rec = u.n_normals ? u.n_normals + 1 : 0;
-    uint64_t log_pt = 0, log_rgb = 0;
-    for (int r = 0; r < kLogRegions; r++) log_pt += u.log_n[r] * sizeof(float4);
-    // The colour log's regions are packed one behind the other, each with its head and padded to 16 bytes (snap_spans): how many bytes
-    // that takes depends on how the buffered points spread over the append regions, which is scheduling.  The section is sized by the
-    // total alone -- a head and a padding of less than 16 bytes each per region -- so that a blob's size follows the counts only.
-    if (log_pt) log_rgb = up16(log_pt / sizeof(float4) * 4) + 32ull * kLogRegions;
-    (void)region_cap;
-    const struct {
-        uint32_t id;
-        uint64_t bytes;
-    } all[] = {{SS_CTR, C_COUNT * 8}, {SS_LOG_CTR, kLogRegions * 16 * 8}, {SS_INFO, cells * 8}, {SS_FIRST_FRAME, cells * 4}, {SS_BUF_HEAD, cells * 4 * kChains},
-               {SS_STAT_ID, cells * 4}, {SS_PRE_DEP, cells * 4}, {SS_OCC_MASK, u.n_bricks * 64}, {SS_ND_MASK, u.n_bricks * 128}, {SS_BRICKS, u.n_bricks * 16},
-               {SS_LOG_PT, log_pt}, {SS_LOG_RGB, color ? log_rgb : 0}, {SS_NV_KEY, rec * 8}, {SS_NV_SLOT, rec * 4}, {SS_NV_C, rec * 12}, {SS_NV_N, rec * 12},
-               {SS_NV_LINE, rec * 32}, {SS_STATS, rec * kStatWords * 8}, {SS_REG_OCC, u.n_reg * 8}, {SS_DEP, u.n_dep * sizeof(DepEntry)}, {SS_OCC_LIST, u.n_occ * 4},
-               {SS_PREREG, u.n_prereg * 4}, {SS_FRAMES, u.n_frames * 16}, {SS_PEND, u.n_pend * 4}};
-    uint32_t n = 0;
-    uint64_t off = 0;
-    for (const auto& a : all) {
-        sec[n++] = SnapSection{a.id, 0u, off, a.bytes};
-        off += up256(a.bytes);
-    }
-    if (u.hidden) {
-        sec[n++] = SnapSection{SS_HIDDEN, 0u, off, u.n_bricks * 64};
-        off += up256(u.n_bricks * 64);
-    }
-    *payload_bytes = off;
-    return n;
-}
-
-struct SnapSpan {  // kernels.hpp SnapSpans, one entry
-    uint64_t pool, stage, bytes;
-    uint32_t head;
-};
-
-// The copy spans of a session on this handle (everything but the two gathered sections).  pend = the pending-cell list.
-void snap_spans(hfpf_handle* h, const SnapUsed& u, const SnapSection* sec, uint32_t n_sec, std::vector<SnapSpan>* out)
-{
-    const Tables& t = h->t;
-    const uint64_t c0 = kBrickCells;  // the first cell of brick 1
-    auto at = [&](uint32_t id) -> const SnapSection& {
-        for (uint32_t i = 0; i < n_sec; i++)
-            if (sec[i].id == id) return sec[i];
-        return sec[0];
-    };
-    auto add = [&](uint32_t id, const void* pool, uint32_t head = 0) {
-        const SnapSection& s = at(id);
-        if (s.bytes) out->push_back(SnapSpan{(uint64_t)(uintptr_t)pool, s.offset, s.bytes, head});
-    };
-    add(SS_CTR, t.ctr);
-    add(SS_LOG_CTR, t.log_ctr);
-    add(SS_INFO, t.info + c0);
-    add(SS_FIRST_FRAME, t.first_frame + c0);
-    add(SS_BUF_HEAD, t.buf_head + c0 * kChains);
-    add(SS_STAT_ID, t.stat_id + c0);
-    add(SS_PRE_DEP, t.pre_dep + c0);
-    add(SS_OCC_MASK, t.occ_mask + 8);
-    add(SS_ND_MASK, t.nd_mask + 16);
-    add(SS_NV_KEY, t.nv_key, 8);  // record 0 does not exist: head
-    add(SS_NV_SLOT, t.nv_slot, 4);
-    add(SS_NV_C, t.nv_c, 12);
-    add(SS_NV_N, t.nv_n, 12);
-    add(SS_NV_LINE, t.nv_line, 32);
-    add(SS_STATS, t.stats);
-    add(SS_REG_OCC, t.reg_occ);
-    add(SS_DEP, t.dep);
-    add(SS_OCC_LIST, t.occ_list);
-    add(SS_PREREG, t.prereg_list);
-    add(SS_PEND, h->pend_a.p);
-    if (u.hidden) add(SS_HIDDEN, h->hidden_words + 8);
-    uint64_t off_pt = at(SS_LOG_PT).offset, off_rgb = at(SS_LOG_RGB).offset;
-    for (int r = 0; r < kLogRegions; r++) {
-        if (!u.log_n[r]) continue;
-        const uint64_t first = (uint64_t)r * t.log_region_cap + 1;  // the region's first entry
-        out->push_back(SnapSpan{(uint64_t)(uintptr_t)(t.log_pt + first), off_pt, u.log_n[r] * sizeof(float4), 0u});
-        off_pt += u.log_n[r] * sizeof(float4);
-        if (t.color) {
-            const uint32_t head = snap_rgb_head(t.log_region_cap, r);
-            out->push_back(SnapSpan{(uint64_t)(uintptr_t)(t.log_rgb + (first & ~3ull)), off_rgb, head + u.log_n[r] * 4, head});
-            off_rgb += up16(head + u.log_n[r] * 4);
-        }
-    }
-}
-
-// Pack (device -> staging) or unpack the part of the payload inside the window [w0, w1) (multiples of 16); the staging buffer
-// holds that window from its first byte.  err: the range check's error words.
-template <bool PACK>
-int snap_move_window(hfpf_handle* h, uint8_t* stage, uint32_t* err, const SnapSection* sec, uint32_t n_sec, const std::vector<SnapSpan>& spans, const SnapLimits& lim,
-                     uint64_t w0, uint64_t w1)
-{
-    SnapSpans sp;
-    memset(&sp, 0, sizeof sp);
-    auto flush = [&]() {
-        if (sp.n == 0) return;
-        hipLaunchKernelGGL(k_snap_copy<PACK>, dim3(sp.tile0[sp.n]), dim3(256), 0, h->stream, sp, stage);
-        memset(&sp, 0, sizeof sp);
-    };
-    for (const SnapSpan& full : spans) {
-        const uint64_t lo = std::max(full.stage, w0), hi = std::min(full.stage + up16(full.bytes), w1);
-        if (lo >= hi) continue;
-        const uint64_t skip = lo - full.stage;  // (a multiple of 16)
-        const uint64_t bytes = std::min(full.bytes - skip, hi - lo);
-        const uint32_t head = (uint32_t)(full.head > skip ? full.head - skip : 0);
-        const uint64_t tiles = (up16(bytes) / 16 + kSnapTileUnits - 1) / kSnapTileUnits;
-        if (sp.n == kSnapSpans || (uint64_t)sp.tile0[sp.n] + tiles > 0x7FFFFFFFull) flush();
-        sp.pool[sp.n] = full.pool + skip;
-        sp.stage[sp.n] = lo - w0;
-        sp.bytes[sp.n] = bytes;
-        sp.head[sp.n] = head;
-        sp.tile0[sp.n + 1] = sp.tile0[sp.n] + (uint32_t)tiles;
-        sp.n++;
-    }
-    flush();
-    // the gathered sections: 16-byte records
-    for (uint32_t i = 0; i < n_sec; i++) {
-        if ((sec[i].id != SS_BRICKS && sec[i].id != SS_FRAMES) || !sec[i].bytes) continue;
-        const uint64_t lo = std::max(sec[i].offset, w0), hi = std::min(sec[i].offset + sec[i].bytes, w1);
-        if (lo >= hi) continue;
-        const uint32_t first = (uint32_t)((lo - sec[i].offset) / 16), n = (uint32_t)((hi - lo) / 16);
-        uint4* rec = (uint4*)(stage + (lo - w0));
-        if (sec[i].id == SS_BRICKS) hipLaunchKernelGGL(k_snap_bricks<PACK>, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->t, lim, rec, first, n, err);
-        else hipLaunchKernelGGL(k_snap_frames<PACK>, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->t, rec, first, n, err);
-    }
-    HIPCHK(h, hipGetLastError());
-    return HFPF_OK;
-}
-
-// A staging buffer for `payload` bytes, or -- when the device has no room for it -- for the largest window it has room for (halved
-// until the allocation succeeds; a window is a multiple of 1 MB).  HFPF_TEST_SNAPSHOT_WINDOW=<bytes> (tests) caps it.
-int snap_stage_alloc(hfpf_handle* h, uint64_t payload, uint64_t* window)
-{
-    uint64_t want = std::max<uint64_t>(up256(payload), 4096);
-    if (const char* e = getenv("HFPF_TEST_SNAPSHOT_WINDOW")) want = std::min<uint64_t>(want, std::max<uint64_t>((uint64_t)atoll(e) & ~4095ull, 4096));
-    if (h->snap_stage.p && h->snap_stage.bytes >= want) {
-        *window = want;
-        return HFPF_OK;
-    }
-    if (h->snap_stage.p) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipFree(h->snap_stage.p));
-        h->device_bytes -= h->snap_stage.bytes;
-        h->snap_stage.p = nullptr, h->snap_stage.bytes = 0;
-    }
-    for (;;) {
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) {
-            h->snap_stage.p = p;
-            h->snap_stage.bytes = want;
-            h->device_bytes += want;
-            *window = want;
-            return HFPF_OK;
-        }
-        (void)hipGetLastError();
-        if (e != hipErrorOutOfMemory || want <= (1u << 20)) return fail(h, HFPF_ERR_HIP, "snapshot staging: hipMalloc(%llu) failed: %s", (unsigned long long)want, hipGetErrorString(e));
-        want = std::max<uint64_t>((want / 2 + (1u << 20) - 1) & ~(uint64_t)((1u << 20) - 1), 1u << 20);
-    }
-}
-
-int snap_refuse_distributed(hfpf_handle* h, const char* what)
-{
-    if (h->dist_on) return fail(h, HFPF_ERR_STATE, "%s: not available on a handle with an RCCL communicator", what);
-    if (h->epoch_used) return fail(h, HFPF_ERR_STATE, "%s: this handle has exchanged epoch records or statistic words; a distributed snapshot is not provided", what);
-    return HFPF_OK;
-}
-
-SnapLimits snap_limits(const hfpf_handle* h, const SnapUsed& u)
-{
-    SnapLimits lim;
-    memset(&lim, 0, sizeof lim);
-    lim.n_slots = (u.n_bricks + 1) * (uint64_t)kBrickCells;
-    lim.n_normals = u.n_normals, lim.n_dep = u.n_dep, lim.n_reg = u.n_reg, lim.n_prereg = u.n_prereg, lim.n_occ = u.n_occ, lim.n_pend = u.n_pend;
-    lim.max_frames = h->t.max_frames;
-    lim.dir_entries = h->dir_entries;
-    lim.region_cap = h->t.log_region_cap;
-    lim.n_bricks = (uint32_t)u.n_bricks;
-    for (int r = 0; r < kLogRegions; r++) lim.log_n[r] = (uint32_t)u.log_n[r];
-    return lim;
-}
-
-// The host state a snapshot carries, into the header and back: ONE field list, the same order in both.  Everything else in Session
-// is re-created after a restore or needs not be (see the notes there); frames_integrated and clean_passes travel too because a
-// clear leaves them alone.
-void session_to_header(const hfpf_handle* h, const SnapUsed& u, SnapHeader* hd)
-{
-    const Session& ss = h->ss;
-    hd->frames_integrated = h->frames_integrated;
-    hd->clean_passes = h->clean_passes;
-    hd->next_frame_id = ss.next_frame_id;
-    hd->dirty = ss.dirty ? 1 : 0;
-    hd->pend_valid = ss.pend_valid ? 1 : 0;
-    hd->normals_possible = ss.normals_possible ? 1 : 0;
-    hd->gate_done = ss.gate_done;
-    hd->direct_linked = ss.direct_linked;
-    for (int r = 0; r < kLogRegions; r++) hd->n_linked[r] = std::min(ss.n_linked[r], u.log_n[r]);
-}
-void header_to_session(const SnapHeader& hd, hfpf_handle* h)
-{
-    Session& ss = h->ss;
-    h->frames_integrated = hd.frames_integrated;
-    h->clean_passes = hd.clean_passes;
-    ss.next_frame_id = (uint32_t)hd.next_frame_id;
-    ss.dirty = hd.dirty != 0;
-    ss.pend_valid = hd.pend_valid != 0;
-    ss.normals_possible = hd.normals_possible != 0;
-    ss.gate_done = hd.gate_done;
-    ss.direct_linked = hd.direct_linked;
-    for (int r = 0; r < kLogRegions; r++) ss.n_linked[r] = hd.n_linked[r];
-}
-
-int snapshot_locked(hfpf_handle* h, void** blob_out, uint64_t* bytes_out)
-{
-    int rc = snap_refuse_distributed(h, "snapshot");
-    if (!rc) rc = read_prologue_locked(h);  // (the counter read-back waits for a clean pass still running)
-    if (rc) return rc;
-    const Tables& t = h->t;
-    const hfpf_config& c = h->cfg;
-    SnapUsed u{};
-    u.n_bricks = std::min<uint64_t>(h->h_ctr[C_BRICKS], t.max_bricks);
-    u.n_normals = std::min<uint64_t>(h->h_ctr[C_NORMALS], t.max_normals);
-    u.n_occ = std::min<uint64_t>(h->h_ctr[C_OCC], t.max_occ);
-    u.n_reg = std::min<uint64_t>(h->h_ctr[C_REG], t.max_reg);
-    u.n_prereg = std::min<uint64_t>(h->h_ctr[C_PREREG], t.max_reg);
-    u.n_dep = std::min<uint64_t>(h->h_ctr[C_DEP], t.max_dep);
-    u.n_frames = std::min<uint64_t>(h->h_ctr[C_FRAMES], t.max_frames);
-    u.n_pend = h->ss.pend_valid ? h->h_ctr[C_PEND] : 0;
-    if (u.n_pend * 4 > h->pend_a.bytes) return fail(h, HFPF_ERR_STATE, "snapshot: pending-cell list of %llu entries exceeds its buffer (internal)", (unsigned long long)u.n_pend);
-    for (int r = 0; r < kLogRegions; r++) u.log_n[r] = std::min<uint64_t>(h->h_log_ctr[r * 16], t.log_region_cap);
-    u.hidden = snapshot_carries_hidden(h->ss.n_hidden);
-
-    uint8_t hdr_bytes[HFPF_SNAPSHOT_HEADER_BYTES];
-    memset(hdr_bytes, 0, sizeof hdr_bytes);
-    SnapHeader hd;
-    memset(&hd, 0, sizeof hd);
-    memcpy(hd.magic, kSnapMagic, 8);
-    hd.version = kSnapVersion;
-    hd.header_bytes = HFPF_SNAPSHOT_HEADER_BYTES;
-    hd.layout_tag = kSnapLayoutTag;
-    hd.n_sections = snap_layout(u, t.color != 0, t.log_region_cap, hd.sec, &hd.payload_bytes);
-    hd.total_bytes = hd.payload_bytes + HFPF_SNAPSHOT_HEADER_BYTES;
-    hd.resolution = c.resolution;
-    hd.flags = c.flags;
-    memcpy(hd.bbox, c.bbox, sizeof hd.bbox);
-    hd.k = c.k, hd.K = c.K, hd.gate = c.gate;
-    hd.cylinder_radius = c.cylinder_radius, hd.ball_radius = c.ball_radius, hd.z_clip_min = c.z_clip_min, hd.z_clip_max = c.z_clip_max;
-    {
-        const uint64_t per = 2ull * (uint64_t)c.K + 1ull;  // max_occ = 4 n, max_reg = (2K+1) n, max_dep = 2 max_reg (alloc_tables)
-        uint64_t nn = std::max<uint64_t>(u.n_normals, 1);
-        nn = std::max(nn, (u.n_occ + 3) / 4);
-        nn = std::max(nn, (std::max(u.n_reg, u.n_prereg) + per - 1) / per);
-        nn = std::max(nn, (u.n_dep + 2 * per - 1) / (2 * per));
-        hd.need_normals = nn;
-    }
-    hd.need_bricks = std::max<uint64_t>(u.n_bricks, 1);
-    hd.log_points = c.max_log_points;
-    hd.need_frames = 1;  // raised below to the largest frame id + 1
-    hd.voxels_occupied = h->h_ctr[C_OCC];
-    hd.voxels_with_normal = h->h_ctr[C_NORMALS];
-    hd.n_bricks = u.n_bricks, hd.n_normals = u.n_normals, hd.n_occ = u.n_occ, hd.n_reg = u.n_reg, hd.n_prereg = u.n_prereg, hd.n_dep = u.n_dep;
-    hd.n_frames = u.n_frames, hd.n_pend = u.n_pend;
-    for (int r = 0; r < kLogRegions; r++) hd.log_n[r] = u.log_n[r];
-    session_to_header(h, u, &hd);
-
-    uint64_t window = 0;
-    if ((rc = snap_stage_alloc(h, hd.payload_bytes, &window))) return rc;
-    uint32_t* err; if ((rc = scratch_n(h, h->snap_err, 16, &err))) return rc;
-    uint8_t* stage = static_cast<uint8_t*>(h->snap_stage.p);
-    uint8_t* blob = (uint8_t*)host_result_alloc(hd.total_bytes);
-    if (!blob) return fail(h, HFPF_ERR_CAPACITY, "snapshot: host allocation of %llu bytes failed", (unsigned long long)hd.total_bytes);
-    std::vector<SnapSpan> spans;
-    snap_spans(h, u, hd.sec, hd.n_sections, &spans);
-    const SnapLimits lim = snap_limits(h, u);
-    for (uint64_t w0 = 0; w0 < hd.payload_bytes; w0 += window) {
-        const uint64_t w1 = std::min(hd.payload_bytes, w0 + window);
-        hipError_t e = hipMemsetAsync(stage, 0, w1 - w0, h->stream);  // the gaps between sections are zero
-        if (e == hipSuccess) rc = snap_move_window<true>(h, stage, err, hd.sec, hd.n_sections, spans, lim, w0, w1);
-        if (e == hipSuccess && !rc) e = download_pageable(h, blob + HFPF_SNAPSHOT_HEADER_BYTES + w0, stage, w1 - w0);
-        if (e != hipSuccess) rc = fail(h, HFPF_ERR_HIP, "snapshot download: %s", hipGetErrorString(e));
-        if (rc) {
-            free(blob);
-            return rc;
-        }
-    }
-    for (uint32_t i = 0; i < hd.n_sections; i++)  // the largest frame id this session integrated
-        if (hd.sec[i].id == SS_FRAMES)
-            for (uint64_t f = 0; f < u.n_frames; f++) {
-                uint32_t id;
-                memcpy(&id, blob + HFPF_SNAPSHOT_HEADER_BYTES + hd.sec[i].offset + 16 * f, 4);
-                hd.need_frames = std::max<uint64_t>(hd.need_frames, (uint64_t)id + 1);
-            }
-    hd.payload_checksum = snap_checksum(blob + HFPF_SNAPSHOT_HEADER_BYTES, hd.payload_bytes);
-    memcpy(hdr_bytes, &hd, sizeof hd);
-    hd.header_checksum = snap_header_checksum(hdr_bytes);
-    memcpy(hdr_bytes, &hd, sizeof hd);
-    memcpy(blob, hdr_bytes, sizeof hdr_bytes);
-    *blob_out = blob;
-    *bytes_out = hd.total_bytes;
-    return HFPF_OK;
-}
-
-int restore_locked(hfpf_handle* h, const void* blob, uint64_t bytes)
-{
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    int rc = snap_refuse_distributed(h, "restore");
-    if (rc) return rc;
-    // ---- everything the host can decide, before the handle is touched ----
-    SnapHeader hd;
-    if (const char* why = snap_parse_header(blob, bytes, &hd)) return fail(h, HFPF_ERR_BAD_ARG, "restore: %s", why);
-    if (hd.layout_tag != kSnapLayoutTag)
-        return fail(h, HFPF_ERR_BAD_ARG, "restore: the snapshot was written by a build with another table layout (tag %llx, this build %llx)", (unsigned long long)hd.layout_tag,
-                    (unsigned long long)kSnapLayoutTag);
-    if (bytes < hd.total_bytes) return fail(h, HFPF_ERR_BAD_ARG, "restore: %llu bytes given, the header says %llu", (unsigned long long)bytes, (unsigned long long)hd.total_bytes);
-    const uint8_t* payload = (const uint8_t*)blob + HFPF_SNAPSHOT_HEADER_BYTES;
-    if (snap_checksum(payload, hd.payload_bytes) != hd.payload_checksum) return fail(h, HFPF_ERR_BAD_ARG, "restore: payload checksum mismatch");
-    const hfpf_config& c = h->cfg;
-    const Tables& t = h->t;
-    uint32_t res_a, res_b;
-    memcpy(&res_a, &hd.resolution, 4);
-    memcpy(&res_b, &c.resolution, 4);
-    if (res_a != res_b || memcmp(hd.bbox, c.bbox, sizeof hd.bbox) != 0 || hd.k != c.k || hd.K != c.K || hd.gate != c.gate ||
-        memcmp(&hd.cylinder_radius, &c.cylinder_radius, 8) != 0 || memcmp(&hd.ball_radius, &c.ball_radius, 8) != 0 || memcmp(&hd.z_clip_min, &c.z_clip_min, 8) != 0 ||
-        memcmp(&hd.z_clip_max, &c.z_clip_max, 8) != 0 || ((hd.flags ^ c.flags) & kSnapSemanticFlags))
-        return fail(h, HFPF_ERR_BAD_CONFIG, "restore: the snapshot was made with another grid configuration (resolution, bbox, k, K, gate, radii, z-clips, colour / covariance flags)");
-    if (hd.log_points != c.max_log_points)
-        return fail(h, HFPF_ERR_BAD_CONFIG, "restore: max_log_points %llu, the snapshot needs exactly %llu (log indices are not remapped)", (unsigned long long)c.max_log_points,
-                    (unsigned long long)hd.log_points);
-    SnapUsed u{};
-    u.n_bricks = hd.n_bricks, u.n_normals = hd.n_normals, u.n_occ = hd.n_occ, u.n_reg = hd.n_reg, u.n_prereg = hd.n_prereg, u.n_dep = hd.n_dep;
-    u.n_frames = hd.n_frames, u.n_pend = hd.n_pend;
-    for (uint32_t i = 0; i < hd.n_sections; i++) u.hidden = u.hidden || hd.sec[i].id == SS_HIDDEN;  // (the layout below must then agree)
-    for (int r = 0; r < kLogRegions; r++) {
-        u.log_n[r] = hd.log_n[r];
-        if (hd.log_n[r] > t.log_region_cap || hd.n_linked[r] > hd.log_n[r]) return fail(h, HFPF_ERR_BAD_ARG, "restore: log region %d out of range", r);
-    }
-    if (u.n_bricks > t.max_bricks || u.n_normals > t.max_normals || u.n_occ > t.max_occ || u.n_reg > t.max_reg || u.n_prereg > t.max_reg || u.n_dep > t.max_dep ||
-        hd.need_frames > t.max_frames || u.n_frames > t.max_frames)
-        return fail(h, HFPF_ERR_CAPACITY,
-                    "restore: the session needs max_bricks >= %llu, max_normals >= %llu, max_frames >= %llu (this handle: %llu, %llu, %llu)", (unsigned long long)hd.need_bricks,
-                    (unsigned long long)hd.need_normals, (unsigned long long)hd.need_frames, (unsigned long long)t.max_bricks, (unsigned long long)t.max_normals,
-                    (unsigned long long)t.max_frames);
-    if (u.n_pend > u.n_occ || hd.gate_done > u.n_occ) return fail(h, HFPF_ERR_BAD_ARG, "restore: inconsistent header (pending cells)");
-    {   // the section table must be the one this build lays out for these counts, and the counters in the payload the header's
-        SnapSection want[kSnapMaxSections];
-        uint64_t pb = 0;
-        const uint32_t n = snap_layout(u, t.color != 0, t.log_region_cap, want, &pb);
-        if (n != hd.n_sections || pb != hd.payload_bytes || memcmp(want, hd.sec, n * sizeof(SnapSection)) != 0)
-            return fail(h, HFPF_ERR_BAD_ARG, "restore: section table does not match the header's counts");
-        unsigned long long ctr[C_COUNT];
-        memcpy(ctr, payload + hd.sec[0].offset, sizeof ctr);  // (section 0 is SS_CTR)
-        if (ctr[C_BRICKS] != u.n_bricks || ctr[C_NORMALS] != u.n_normals || ctr[C_OCC] != u.n_occ || ctr[C_REG] != u.n_reg || ctr[C_PREREG] != u.n_prereg ||
-            ctr[C_DEP] != u.n_dep || ctr[C_FRAMES] != u.n_frames || ctr[C_ERR] != 0)
-            return fail(h, HFPF_ERR_BAD_ARG, "restore: counters in the payload do not match the header");
-        const uint8_t* lc = payload + hd.sec[1].offset;  // SS_LOG_CTR
-        for (int r = 0; r < kLogRegions; r++) {
-            unsigned long long n_r;
-            memcpy(&n_r, lc + (size_t)r * 16 * 8, 8);
-            if (n_r != u.log_n[r]) return fail(h, HFPF_ERR_BAD_ARG, "restore: log counters in the payload do not match the header");
-        }
-    }
-    // ---- from here on a failure leaves the handle as after hfpf_clear ----
-    if ((rc = clear_locked(h))) return rc;
-    auto bail = [&](int code) {
-        const std::string msg = h->err;
-        (void)hipStreamSynchronize(h->stream);
-        (void)reset_state(h);  // in full: what was uploaded is not to be trusted
-        h->ss.dirty = true;
-        h->err = msg;
-        return code;
-    };
-    uint64_t window = 0;
-    if ((rc = snap_stage_alloc(h, hd.payload_bytes, &window))) return bail(rc);
-    uint32_t *err, *pend = nullptr;  // pend: read below u.n_pend only
-    if ((rc = scratch_n(h, h->snap_err, 16, &err))) return bail(rc);
-    if (u.n_pend && (rc = scratch_n(h, h->pend_a, u.n_pend, &pend))) return bail(rc);
-    if (u.hidden && (rc = hide_words_locked(h))) return bail(rc);
-    uint8_t* stage = static_cast<uint8_t*>(h->snap_stage.p);
-    if (hipMemsetAsync(err, 0, 64, h->stream) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore: hipMemsetAsync failed"));
-    std::vector<SnapSpan> spans;
-    snap_spans(h, u, hd.sec, hd.n_sections, &spans);
-    const SnapLimits lim = snap_limits(h, u);
-    for (uint64_t w0 = 0; w0 < hd.payload_bytes; w0 += window) {
-        const uint64_t w1 = std::min(hd.payload_bytes, w0 + window);
-        const hipError_t e = upload_pageable(h, stage, payload + w0, w1 - w0);
-        if (e != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore upload: %s", hipGetErrorString(e)));
-        if ((rc = snap_move_window<false>(h, stage, err, hd.sec, hd.n_sections, spans, lim, w0, w1))) return bail(rc);
-        if (w1 < hd.payload_bytes && hipStreamSynchronize(h->stream) != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore: unpack failed"));  // the window is reused
-    }
-    // range check of every index a later kernel would follow, before anything else touches the tables
-    if (u.n_bricks) hipLaunchKernelGGL(k_snap_check_slots, dim3(blocks_for(u.n_bricks * (uint64_t)kBrickCells, 256)), dim3(256), 0, h->stream, h->t, lim, err);
-    {
-        uint64_t max_log = 0;
-        for (int r = 0; r < kLogRegions; r++) max_log = std::max(max_log, u.log_n[r]);
-        if (max_log) hipLaunchKernelGGL(k_snap_check_log, dim3(blocks_for(max_log, 256), kLogRegions), dim3(256), 0, h->stream, h->t, lim, err);
-        const uint64_t n_list = std::max({u.n_normals + 1, u.n_reg, u.n_prereg, u.n_occ, u.n_pend});
-        hipLaunchKernelGGL(k_snap_check_lists, dim3(blocks_for(n_list, 256)), dim3(256), 0, h->stream, h->g, h->t, lim, pend, err);
-    }
-    if (hipGetLastError() != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore: launch of the range check failed"));
-    uint32_t err_word = 0;
-    if (hipMemcpyAsync(&err_word, err, 4, hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
-        return bail(fail(h, HFPF_ERR_HIP, "restore: reading the range check's result failed"));
-    if (err_word) return bail(fail(h, HFPF_ERR_IO, "restore: the snapshot's tables hold indices outside their pools (range check bits 0x%x); the handle has been cleared", err_word));
-    header_to_session(hd, h);
-    if ((rc = read_counters(h))) return bail(rc);  // h_ctr, h_log_ctr, n_bricks_known from the restored device counters
-    h->ss.n_bricks_before = h->ss.n_bricks_known;
-    if (u.hidden) {  // |H| and Tables::hidden from the restored bits; they must lie inside normal_found
-        HideCall c;
-        HideCounts k{};
-        if ((rc = hide_begin_locked(h, &c)) || (rc = hide_apply_locked(h, c, HFPF_HIDE, nullptr, &k))) return bail(rc);
-        if (k.n_bad) return bail(fail(h, HFPF_ERR_IO, "restore: the snapshot hides voxels that hold no row (%llu plane words); the handle has been cleared", k.n_bad));
-    }
-    if (h->binned) {
-        // Entries the source's direct form appended since its last clean are still unchained; the binned form never runs
-        // k_link_log at a clean pass (its own appends arrive chained), so they are chained here.
-        LinkRanges lr;
-        uint64_t max_new = 0;
-        for (int r = 0; r < kLogRegions; r++) {
-            const uint64_t base = (uint64_t)r * t.log_region_cap;
-            lr.first[r] = (uint32_t)(base + h->ss.n_linked[r] + 1);
-            lr.last[r] = (uint32_t)(base + u.log_n[r]);
-            max_new = std::max(max_new, u.log_n[r] - h->ss.n_linked[r]);
-        }
-        if (max_new && (hd.flags & HFPF_FLAG_DIRECT_UPDATE)) {
-            hipLaunchKernelGGL(k_link_log, dim3(blocks_for(max_new, 256), kLogRegions), dim3(256), 0, h->stream, h->t, lr);
-            if (hipGetLastError() != hipSuccess) return bail(fail(h, HFPF_ERR_HIP, "restore: k_link_log launch failed"));
-            for (int r = 0; r < kLogRegions; r++) h->ss.n_linked[r] = u.log_n[r];
-            h->ss.direct_linked = h->h_ctr[C_BUFFERED];
-        }
-    }
-    return HFPF_OK;
-}
-
-}  // namespace
-extern "C" {
-
-int hfpf_snapshot(hfpf_handle* h, void** blob, uint64_t* bytes)
-{
-    if (!h || !blob || !bytes) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    *blob = nullptr;
-    *bytes = 0;
-    return snapshot_locked(h, blob, bytes);
-}
-
-void hfpf_free_snapshot(void* blob) { free(blob); }
-
-int hfpf_restore(hfpf_handle* h, const void* blob, uint64_t bytes)
-{
-    if (!h) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    if (!blob) return fail(h, HFPF_ERR_BAD_ARG, "restore: null blob");
-    return restore_locked(h, blob, bytes);
-}
-
-int hfpf_save(hfpf_handle* h, const char* path)
-{
-    if (!h) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    if (!path) return fail(h, HFPF_ERR_BAD_ARG, "save: null path");
-    void* blob = nullptr;
-    uint64_t bytes = 0;
-    if (int rc = snapshot_locked(h, &blob, &bytes)) return rc;
-    FILE* f = fopen(path, "wb");
-    if (!f) {
-        free(blob);
-        return fail(h, HFPF_ERR_IO, "save: cannot open %s for writing", path);
-    }
-    const bool wrote = fwrite(blob, 1, bytes, f) == bytes;
-    const bool closed = fclose(f) == 0;
-    free(blob);
-    if (!wrote || !closed) {
-        remove(path);  // no partial file is left behind
-        return fail(h, HFPF_ERR_IO, "save: short write to %s", path);
-    }
-    return HFPF_OK;
-}
-
-int hfpf_load(hfpf_handle* h, const char* path)
-{
-    if (!h) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    if (!path) return fail(h, HFPF_ERR_BAD_ARG, "load: null path");
-    FILE* f = fopen(path, "rb");
-    if (!f) return fail(h, HFPF_ERR_IO, "load: cannot open %s", path);
-    uint8_t hdr[HFPF_SNAPSHOT_HEADER_BYTES];
-    SnapHeader hd;
-    if (fread(hdr, 1, sizeof hdr, f) != sizeof hdr) {
-        fclose(f);
-        return fail(h, HFPF_ERR_IO, "load: %s is shorter than a snapshot header", path);
-    }
-    if (const char* why = snap_parse_header(hdr, sizeof hdr, &hd)) {
-        fclose(f);
-        return fail(h, HFPF_ERR_BAD_ARG, "load: %s: %s", path, why);
-    }
-    uint8_t* blob = (uint8_t*)host_result_alloc(hd.total_bytes);
-    if (!blob) {
-        fclose(f);
-        return fail(h, HFPF_ERR_CAPACITY, "load: host allocation of %llu bytes failed", (unsigned long long)hd.total_bytes);
-    }
-    memcpy(blob, hdr, sizeof hdr);
-    const bool whole = fread(blob + sizeof hdr, 1, hd.payload_bytes, f) == hd.payload_bytes;
-    fclose(f);
-    int rc = whole ? restore_locked(h, blob, hd.total_bytes) : fail(h, HFPF_ERR_IO, "load: %s ends before the %llu bytes its header announces", path, (unsigned long long)hd.total_bytes);
-    free(blob);
-    return rc;
-}
-
-int hfpf_snapshot_info(const void* blob, uint64_t bytes, struct hfpf_snapshot_info* out)
-{
-    if (!blob || !out || out->struct_size != sizeof(struct hfpf_snapshot_info)) return HFPF_ERR_BAD_ARG;
-    SnapHeader hd;
-    if (snap_parse_header(blob, std::min<uint64_t>(bytes, HFPF_SNAPSHOT_HEADER_BYTES), &hd)) return HFPF_ERR_BAD_ARG;
-    struct hfpf_snapshot_info o;
-    memset(&o, 0, sizeof o);
-    o.struct_size = sizeof o;
-    o.format_version = hd.version;
-    o.layout_tag = hd.layout_tag;
-    o.total_bytes = hd.total_bytes;
-    o.payload_bytes = hd.payload_bytes;
-    o.payload_checksum = hd.payload_checksum;
-    o.resolution = hd.resolution;
-    o.flags = hd.flags;
-    memcpy(o.bbox, hd.bbox, sizeof o.bbox);
-    o.k = hd.k, o.K = hd.K, o.gate = hd.gate;
-    o.cylinder_radius = hd.cylinder_radius, o.ball_radius = hd.ball_radius, o.z_clip_min = hd.z_clip_min, o.z_clip_max = hd.z_clip_max;
-    o.max_bricks = hd.need_bricks, o.max_log_points = hd.log_points, o.max_normals = hd.need_normals, o.max_frames = hd.need_frames;
-    o.frames_integrated = hd.frames_integrated, o.clean_passes = hd.clean_passes, o.next_frame_id = hd.next_frame_id;
-    o.voxels_occupied = hd.voxels_occupied, o.voxels_with_normal = hd.voxels_with_normal;
-    *out = o;
-    return HFPF_OK;
-}
-
-int hfpf_config_from_snapshot(const struct hfpf_snapshot_info* info, hfpf_config* cfg)
-{
-    if (!info || !cfg || info->struct_size != sizeof(struct hfpf_snapshot_info)) return HFPF_ERR_BAD_ARG;
-    hfpf_default_config(cfg);
-    cfg->resolution = info->resolution;
-    memcpy(cfg->bbox, info->bbox, sizeof cfg->bbox);
-    cfg->k = info->k, cfg->K = info->K, cfg->gate = info->gate;
-    cfg->cylinder_radius = info->cylinder_radius, cfg->ball_radius = info->ball_radius;
-    cfg->z_clip_min = info->z_clip_min, cfg->z_clip_max = info->z_clip_max;
-    cfg->flags = info->flags & kSnapSemanticFlags;
-    cfg->max_bricks = info->max_bricks, cfg->max_log_points = info->max_log_points, cfg->max_normals = info->max_normals, cfg->max_frames = info->max_frames;
-    return HFPF_OK;
 }
 
 int hfpf_sync(hfpf_handle* h)
@@ -6206,115 +5293,10 @@ int hfpf_get_kernel_time(hfpf_handle* h, int kernel_id, double* total_ms, uint64
     return HFPF_OK;
 }
 
-// ---- leaf probes (include/hfpf_probe.h) ----------------------------------------------------------
-// An input of a probe: `count` T from host memory into buf (*d), enqueued.  An output is a scratch_n and a probe_down.
-extern "C++" template <typename T>
-static int probe_up(hfpf_handle* h, DevBuf& buf, const T* src, uint64_t count, T** d)
-{
-    if (int rc = scratch_n(h, buf, count, d)) return rc;
-    HIPCHK(h, hipMemcpyAsync(*d, src, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
-    return HFPF_OK;
-}
-#define PROBE_DOWN(dst, d, count) HIPCHK(h, hipMemcpyAsync((dst), (d), (count) * sizeof *(d), hipMemcpyDeviceToHost, h->stream));
-
-int hfpf_probe_points(hfpf_handle* h, const double pose[12], const float* xyz, uint64_t n, float* q_out, int32_t* idx_out, uint8_t* flags_out)
-{
-    if (!h || !pose || !xyz || !q_out || !idx_out || !flags_out) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (n == 0) return HFPF_OK;
-    int rc;
-    double* d_pose; float *d_xyz, *d_q;
-    int32_t* d_idx; uint8_t* d_flags;
-    if ((rc = probe_up(h, h->probe_a, pose, 12, &d_pose)) || (rc = probe_up(h, h->probe_b, xyz, 3 * n, &d_xyz))) return rc;
-    if ((rc = scratch_n(h, h->probe_c, 3 * n, &d_q)) || (rc = scratch_n(h, h->probe_d, 3 * n, &d_idx)) || (rc = scratch_n(h, h->probe_e, n, &d_flags))) return rc;
-    hipLaunchKernelGGL(k_probe_points, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->g, d_pose, d_xyz, n, d_q, d_idx, d_flags);
-    HIPCHK(h, hipGetLastError());
-    PROBE_DOWN(q_out, d_q, 3 * n);
-    PROBE_DOWN(idx_out, d_idx, 3 * n);
-    PROBE_DOWN(flags_out, d_flags, n);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return HFPF_OK;
-}
-
-int hfpf_probe_normals(hfpf_handle* h, uint64_t n, const int32_t* cells, const uint8_t* occ, const float* vps, float* normals_out, int32_t* totals_out)
-{
-    if (!h || !cells || !occ || !vps || !normals_out || !totals_out) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (n == 0) return HFPF_OK;
-    int rc;
-    int32_t *d_cells, *d_totals; uint8_t* d_occ; float *d_vps, *d_normals;
-    if ((rc = probe_up(h, h->probe_a, cells, 3 * n, &d_cells)) || (rc = probe_up(h, h->probe_b, occ, 125 * n, &d_occ))) return rc;
-    if ((rc = probe_up(h, h->probe_c, vps, 3 * n, &d_vps))) return rc;
-    if ((rc = scratch_n(h, h->probe_d, 3 * n, &d_normals)) || (rc = scratch_n(h, h->probe_e, n, &d_totals))) return rc;
-    hipLaunchKernelGGL(k_probe_normals, dim3(blocks_for(n, 64)), dim3(64), 0, h->stream, h->g, n, d_cells, d_occ, d_vps, d_normals, d_totals);
-    HIPCHK(h, hipGetLastError());
-    PROBE_DOWN(normals_out, d_normals, 3 * n);
-    PROBE_DOWN(totals_out, d_totals, n);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return HFPF_OK;
-}
-
-int hfpf_probe_project(hfpf_handle* h, uint64_t n, const float* pts, const float* centres, const float* normals, float* proj_out, double* dist_out,
-                       uint8_t* member_out)
-{
-    if (!h || !pts || !centres || !normals || !proj_out || !dist_out || !member_out) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (n == 0) return HFPF_OK;
-    int rc;
-    float *d_pts, *d_centres, *d_normals, *d_proj; double* d_dist; uint8_t* d_member;
-    if ((rc = probe_up(h, h->probe_a, pts, 3 * n, &d_pts)) || (rc = probe_up(h, h->probe_b, centres, 3 * n, &d_centres))) return rc;
-    if ((rc = probe_up(h, h->probe_c, normals, 3 * n, &d_normals))) return rc;
-    if ((rc = scratch_n(h, h->probe_d, 3 * n, &d_proj)) || (rc = scratch_n(h, h->probe_e, n, &d_dist)) || (rc = scratch_n(h, h->probe_f, n, &d_member))) return rc;
-    hipLaunchKernelGGL(k_probe_project, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, h->g, n, d_pts, d_centres, d_normals, d_proj, d_dist, d_member);
-    HIPCHK(h, hipGetLastError());
-    PROBE_DOWN(proj_out, d_proj, 3 * n);
-    PROBE_DOWN(dist_out, d_dist, n);
-    PROBE_DOWN(member_out, d_member, n);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return HFPF_OK;
-}
-
-int hfpf_probe_depth(hfpf_handle* h, const hfpf_depth_image* desc, const void* depth, const void* color, float* xyz_out, uint32_t* rgb_out)
-{
-    if (!h || !xyz_out || !rgb_out) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    DepthSpec ds;
-    int rc = depth_spec(h, desc, depth, color, &ds);
-    if (rc) return rc;
-    const uint32_t n = ds.width * ds.height;
-    uint8_t *d_depth, *d_color = nullptr;  // (without colour depth_layout() passes no colour image)
-    float* d_xyz; uint32_t* d_rgb;
-    if ((rc = probe_up(h, h->probe_a, (const uint8_t*)depth, ds.depth_bytes(), &d_depth))) return rc;
-    if (ds.color_bpp && (rc = probe_up(h, h->probe_b, (const uint8_t*)color, ds.color_bytes(), &d_color))) return rc;
-    if ((rc = scratch_n(h, h->probe_c, 3 * (uint64_t)n, &d_xyz)) || (rc = scratch_n(h, h->probe_d, n, &d_rgb))) return rc;
-    hipLaunchKernelGGL(k_probe_depth, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, depth_layout(ds, d_color, 0), d_depth, n, d_xyz, d_rgb);
-    HIPCHK(h, hipGetLastError());
-    PROBE_DOWN(xyz_out, d_xyz, 3 * (uint64_t)n);
-    PROBE_DOWN(rgb_out, d_rgb, n);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return HFPF_OK;
-}
-
-int hfpf_probe_trig(hfpf_handle* h, uint64_t n, const float* y, const float* x, float* atan2_out, float* cos_out, float* sin_out)
-{
-    if (!h || !y || !x || !atan2_out || !cos_out || !sin_out) return HFPF_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(h->mtx);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (n == 0) return HFPF_OK;
-    int rc;
-    float *d_y, *d_x, *d_atan2, *d_cos, *d_sin; if ((rc = probe_up(h, h->probe_a, y, n, &d_y)) || (rc = probe_up(h, h->probe_b, x, n, &d_x))) return rc;
-    if ((rc = scratch_n(h, h->probe_c, n, &d_atan2)) || (rc = scratch_n(h, h->probe_d, n, &d_cos)) || (rc = scratch_n(h, h->probe_e, n, &d_sin))) return rc;
-    hipLaunchKernelGGL(k_probe_trig, dim3(blocks_for(n, 256)), dim3(256), 0, h->stream, n, d_y, d_x, d_atan2, d_cos, d_sin);
-    HIPCHK(h, hipGetLastError());
-    PROBE_DOWN(atan2_out, d_atan2, n);
-    PROBE_DOWN(cos_out, d_cos, n);
-    PROBE_DOWN(sin_out, d_sin, n);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return HFPF_OK;
-}
-
 }  // extern "C"
+
+// ================================================================================================
+// What is no part of the hot path and builds on everything above, one unit each; nothing above names them.
+#include "snapshot.hpp"
+#include "probe.hpp"
+#include "file_io.hpp"

@@ -3598,12 +3598,6 @@ __global__ __launch_bounds__(256) void k_epoch_import(const GridParams g, const 
     if (overflow) atomicOr(&t.ctr[C_ERR], (unsigned long long)E_OCC);
 }
 
-__global__ __launch_bounds__(256) void k_add_u64(unsigned long long* __restrict__ dst, const unsigned long long* __restrict__ src, const uint64_t n)
-{
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) dst[j] += src[j];
-}
-
 // Diagnostic: keys of every occupied cell.
 __global__ __launch_bounds__(256) void k_occupied_keys(const GridParams g, const Tables t, const uint64_t n_occ, uint64_t* __restrict__ keys)
 {
@@ -3745,311 +3739,6 @@ __global__ __launch_bounds__(256) void k_hidden_keys(const Tables t, const uint6
     slot_plane_bit(t.nv_slot[j + 1], plane, bit);
     keys[j] = (t.hidden[plane] & bit) ? t.nv_key[j + 1] : ~0ull;
 }
-
-// ---- leaf probes (tests only; same device functions as the kernels above) -------------------------
-// One depth image, pixel by pixel, through the loads and the back-projection of k_integrate's DEPTH form.
-__global__ void k_probe_depth(const DepthLayout L, const uint8_t* __restrict__ dimg, const uint32_t n, float* __restrict__ xyz_out,
-                              uint32_t* __restrict__ rgb_out)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const vf4 r = depth_fetch<true>(dimg, L.color, L, i);
-    const F3 c = depth_point(L, r);
-    xyz_out[3 * (uint64_t)i] = c.x;
-    xyz_out[3 * (uint64_t)i + 1] = c.y;
-    xyz_out[3 * (uint64_t)i + 2] = c.z;
-    rgb_out[i] = __float_as_uint(r.y);
-}
-
-__global__ void k_probe_points(const GridParams g, const double* __restrict__ pose, const float* __restrict__ xyz, const uint64_t n,
-                               float* __restrict__ q_out, int32_t* __restrict__ idx_out, uint8_t* __restrict__ flags_out)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double T[12];
-    for (int k = 0; k < 12; k++) T[k] = pose[k];
-    const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-    const F3 q = transform_point(T, x, y, z);
-    int32_t ix, iy, iz;
-    voxel_coords(g, q, ix, iy, iz);
-    q_out[3 * i] = q.x;
-    q_out[3 * i + 1] = q.y;
-    q_out[3 * i + 2] = q.z;
-    idx_out[3 * i] = ix;
-    idx_out[3 * i + 1] = iy;
-    idx_out[3 * i + 2] = iz;
-    flags_out[i] = (zclip_pass(g, z) ? 1 : 0) | (valid_point(g, q) ? 2 : 0);
-}
-
-__global__ void k_probe_normals(const GridParams g, const uint64_t n, const int32_t* __restrict__ cells, const uint8_t* __restrict__ occ,
-                                const float* __restrict__ vps, float* __restrict__ normals_out, int32_t* __restrict__ totals_out)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t x = cells[3 * i], y = cells[3 * i + 1], z = cells[3 * i + 2];
-    Moments m;
-    m.clear();
-    int total = 0;
-    for (int d = 0; d < 125; d++) {
-        const int a = d / 25 - 2, b = (d / 5) % 5 - 2, c = d % 5 - 2;
-        if (!occ[125 * i + d] || !valid_coord(g, x + a, y + b, z + c)) continue;
-        m.add(voxel_center(g, x + a, y + b, z + c), g.cov_shifted != 0);
-        total++;
-    }
-    totals_out[i] = total;
-    F3 nrm = {0, 0, 0};
-    if (total >= 3) {
-        nrm = m.normal(total);
-        nrm = orient_normal(nrm, F3{vps[3 * i], vps[3 * i + 1], vps[3 * i + 2]}, voxel_center(g, x, y, z));
-    }
-    normals_out[3 * i] = nrm.x;
-    normals_out[3 * i + 1] = nrm.y;
-    normals_out[3 * i + 2] = nrm.z;
-}
-
-__global__ void k_probe_project(const GridParams g, const uint64_t n, const float* __restrict__ pts, const float* __restrict__ centres,
-                                const float* __restrict__ normals, float* __restrict__ proj_out, double* __restrict__ dist_out,
-                                uint8_t* __restrict__ member_out)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    F3 proj;
-    double dist;
-    const bool mem = cylinder_member(g, F3{pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]}, F3{centres[3 * i], centres[3 * i + 1], centres[3 * i + 2]},
-                                     F3{normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]}, proj, dist);
-    proj_out[3 * i] = proj.x;
-    proj_out[3 * i + 1] = proj.y;
-    proj_out[3 * i + 2] = proj.z;
-    dist_out[i] = dist;
-    F3 a, ab;
-    float dd, sp, distf;
-    line_of(g, F3{centres[3 * i], centres[3 * i + 1], centres[3 * i + 2]}, F3{normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]}, a, ab, dd);
-    const bool mem2 = line_member(g, F3{pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]}, a, ab, dd, sp, distf);  // the kernels' form
-    float sp3, distf3;  // the form with the hoisted division (k_update_cells): must agree bit for bit
-    const bool mem3 = line_member_hoisted(g, F3{pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]}, a, ab, line_div_of(dd), sp3, distf3);
-    const bool same = mem3 == mem2 && __float_as_uint(sp3) == __float_as_uint(sp) && __float_as_uint(distf3) == __float_as_uint(distf);
-    member_out[i] = (mem ? 1 : 0) | (mem2 ? 2 : 0) | (same ? 4 : 0);
-}
-
-__global__ void k_probe_trig(const uint64_t n, const float* __restrict__ y, const float* __restrict__ x, float* __restrict__ a_out,
-                             float* __restrict__ c_out, float* __restrict__ s_out)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    a_out[i] = det_atan2f(y[i], x[i]);
-    c_out[i] = det_cosf(x[i]);
-    s_out[i] = det_sinf(x[i]);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Snapshot / restore (include/hfpf.h): the used prefix of every pool <-> ONE contiguous staging buffer, so that a session
-// crosses the link as a few large copies.  A span is a run of 16-byte units that lies 16-byte aligned in its pool and in the
-// staging buffer; `head` leading bytes and everything behind `bytes` are not state (the unused record 0 of the record arrays,
-// the up to three entries in front of an append region of the colour log, the tail of a list whose length is no multiple of
-// four): packed as zeros, left alone in the pool when unpacked.  One launch takes up to kSnapSpans spans; a workgroup moves one
-// 16 KB tile (4 units per lane, loads first), so the lanes of a wave read and write 1 KB runs on both sides.
-constexpr uint32_t kSnapSpans = 48;
-constexpr uint32_t kSnapTileUnits = 1024;  // 16-byte units per workgroup
-struct SnapSpans {
-    uint64_t pool[kSnapSpans];    // address of the span's first unit in its pool
-    uint64_t stage[kSnapSpans];   // ... and its byte offset in the staging buffer
-    uint64_t bytes[kSnapSpans];   // span length, head included (a multiple of 4)
-    uint32_t head[kSnapSpans];
-    uint32_t tile0[kSnapSpans + 1];  // first tile of every span; tile0[n] = tiles of the launch
-    uint32_t n;
-};
-// One unit that holds a span's head or tail: word by word.
-template <bool PACK>
-__device__ __forceinline__ void snap_edge_unit(uint8_t* pool, uint8_t* st, uint64_t u, uint64_t head, uint64_t bytes)
-{
-    uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
-    const uint64_t b = u * 16;
-    const bool s0 = b >= head && b < bytes, s1 = b + 4 >= head && b + 4 < bytes, s2 = b + 8 >= head && b + 8 < bytes, s3 = b + 12 >= head && b + 12 < bytes;
-    if (PACK) {
-        if (s0) w0 = *reinterpret_cast<const uint32_t*>(pool + b);
-        if (s1) w1 = *reinterpret_cast<const uint32_t*>(pool + b + 4);
-        if (s2) w2 = *reinterpret_cast<const uint32_t*>(pool + b + 8);
-        if (s3) w3 = *reinterpret_cast<const uint32_t*>(pool + b + 12);
-        *reinterpret_cast<uint4*>(st + b) = make_uint4(w0, w1, w2, w3);
-    } else {
-        const uint4 v = *reinterpret_cast<const uint4*>(st + b);
-        if (s0) *reinterpret_cast<uint32_t*>(pool + b) = v.x;
-        if (s1) *reinterpret_cast<uint32_t*>(pool + b + 4) = v.y;
-        if (s2) *reinterpret_cast<uint32_t*>(pool + b + 8) = v.z;
-        if (s3) *reinterpret_cast<uint32_t*>(pool + b + 12) = v.w;
-    }
-}
-template <bool PACK>
-__global__ __launch_bounds__(256) void k_snap_copy(const SnapSpans sp, uint8_t* __restrict__ stage)
-{
-    uint32_t s = 0;
-    while (s + 1 < sp.n && blockIdx.x >= sp.tile0[s + 1]) s++;  // workgroup-uniform: scalar compares on the kernel arguments
-    const uint64_t bytes = sp.bytes[s], head = sp.head[s];
-    const uint64_t n_units = (bytes + 15) >> 4;
-    uint8_t* pool = reinterpret_cast<uint8_t*>(sp.pool[s]);
-    uint8_t* st = stage + sp.stage[s];
-    const uint8_t* src = PACK ? pool : st;
-    uint8_t* dst = PACK ? st : pool;
-    const uint64_t t0 = (uint64_t)(blockIdx.x - sp.tile0[s]) * kSnapTileUnits;
-    const uint64_t u0 = t0 + threadIdx.x, u1 = u0 + 256u, u2 = u0 + 512u, u3 = u0 + 768u;
-    // a tile that lies inside the span's whole units (all but a span's first and last tile): four loads in flight, four stores
-    if (t0 * 16 >= head && (t0 + kSnapTileUnits) * 16 <= bytes) {  // workgroup-uniform
-        const uint4 a = *reinterpret_cast<const uint4*>(src + u0 * 16), b = *reinterpret_cast<const uint4*>(src + u1 * 16);
-        const uint4 c = *reinterpret_cast<const uint4*>(src + u2 * 16), d = *reinterpret_cast<const uint4*>(src + u3 * 16);
-        *reinterpret_cast<uint4*>(dst + u0 * 16) = a;
-        *reinterpret_cast<uint4*>(dst + u1 * 16) = b;
-        *reinterpret_cast<uint4*>(dst + u2 * 16) = c;
-        *reinterpret_cast<uint4*>(dst + u3 * 16) = d;
-        return;
-    }
-    for (uint64_t u = u0; u < n_units && u < t0 + kSnapTileUnits; u += 256u) {
-        if (u * 16 >= head && u * 16 + 16 <= bytes) *reinterpret_cast<uint4*>(dst + u * 16) = *reinterpret_cast<const uint4*>(src + u * 16);
-        else snap_edge_unit<PACK>(pool, st, u, head, bytes);
-    }
-}
-
-// What the restored indices are checked against: the used range of every pool as the snapshot's header states it (the host has
-// compared those with the target's capacities before anything was uploaded).
-enum SnapErr : uint32_t {
-    SE_BRICK = 1,    // brick_lin outside the directory, or two bricks on one directory entry
-    SE_RUN = 2,      // a brick's run record outside the used part of its log region
-    SE_FRAME = 4,    // frame id >= max_frames
-    SE_HEAD = 8,     // a chain head that names no log entry
-    SE_SLOT = 16,    // stat_id / pre_dep beyond the records, first_frame beyond the frames
-    SE_DEP = 32,     // a dependant list outside dep[], or one of its entries naming no record
-    SE_LINK = 64,    // a log link that names no log entry / no slot
-    SE_RECORD = 128, // nv_slot outside the slots, nv_key outside the grid
-    SE_LIST = 256,   // reg_occ / prereg_list / occ_list / pending-cell entry outside the slots or the records
-};
-struct SnapLimits {
-    uint64_t n_slots;   // (bricks + 1) * 512: slots of the allocated bricks and the null brick
-    uint64_t n_normals, n_dep, n_reg, n_prereg, n_occ, n_pend, max_frames, dir_entries, region_cap;
-    uint32_t n_bricks;
-    uint32_t log_n[kLogRegions];
-};
-__device__ __forceinline__ bool snap_log_entry_ok(const SnapLimits& lim, uint32_t e)  // a 1-based log index that names a used entry
-{
-    if (e == 0) return false;
-    const uint64_t r = (uint64_t)(e - 1) / lim.region_cap;
-    return r < (uint64_t)kLogRegions && (uint64_t)(e - 1) - r * lim.region_cap < lim.log_n[r];
-}
-
-// Per-brick records: (brick_lin, run_start, run_len, run_cnt) of bricks first + 1 .. first + n as one 16-byte record each (the
-// run record of a brick that never buffered is not state: zeros).  Unpacking also rebuilds the directory from brick_lin -- the
-// compare-and-swap finds two bricks on one entry -- and checks the run record the streaming replay would follow.
-template <bool PACK>
-__global__ __launch_bounds__(256) void k_snap_bricks(const Tables t, const SnapLimits lim, uint4* __restrict__ rec, const uint32_t first, const uint32_t n, uint32_t* __restrict__ err)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t b = first + i + 1;
-    if (PACK) {
-        const uint32_t cnt = t.run_cnt[b];
-        rec[i] = make_uint4(t.brick_lin[b], cnt ? t.run_start[b] : 0u, cnt ? t.run_len[b] : 0u, cnt);
-        return;
-    }
-    const uint4 v = rec[i];
-    t.brick_lin[b] = v.x;
-    t.run_start[b] = v.y;
-    t.run_len[b] = v.z;
-    t.run_cnt[b] = v.w;
-    uint32_t e = 0;
-    if (v.x >= lim.dir_entries) e |= SE_BRICK;
-    else if (atomicCAS(&t.dir[v.x], 0u, b) != 0u) e |= SE_BRICK;
-    if (v.w == 1u) {  // one run: [run_start, run_start + run_len) is streamed
-        const uint64_t r = v.y ? (uint64_t)(v.y - 1) / lim.region_cap : (uint64_t)kLogRegions;
-        if (r >= (uint64_t)kLogRegions || (uint64_t)(v.y - 1) - r * lim.region_cap + v.z > lim.log_n[r]) e |= SE_RUN;
-    }
-    if (e) atomicOr(err, e);
-}
-
-// Frames: (id, viewpoint) of frame_list entries first .. first + n - 1 as one 16-byte record each: frame_vp is indexed by frame
-// id, and ids need not be dense.
-template <bool PACK>
-__global__ __launch_bounds__(256) void k_snap_frames(const Tables t, uint4* __restrict__ rec, const uint32_t first, const uint32_t n, uint32_t* __restrict__ err)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    if (PACK) {
-        const uint32_t id = t.frame_list[first + i];
-        uint4 v = make_uint4(id, 0u, 0u, 0u);
-        if (id < t.max_frames) {
-            v.y = __float_as_uint(t.frame_vp[3 * (uint64_t)id]);
-            v.z = __float_as_uint(t.frame_vp[3 * (uint64_t)id + 1]);
-            v.w = __float_as_uint(t.frame_vp[3 * (uint64_t)id + 2]);
-        }
-        rec[i] = v;
-        return;
-    }
-    const uint4 v = rec[i];
-    t.frame_list[first + i] = v.x;
-    if (v.x >= t.max_frames) {
-        atomicOr(err, (uint32_t)SE_FRAME);
-        return;
-    }
-    t.frame_vp[3 * (uint64_t)v.x] = __uint_as_float(v.y);
-    t.frame_vp[3 * (uint64_t)v.x + 1] = __uint_as_float(v.z);
-    t.frame_vp[3 * (uint64_t)v.x + 2] = __uint_as_float(v.w);
-}
-
-// Range check of a restored session, before any other kernel follows an index of it.  One thread per slot of the allocated bricks.
-__global__ __launch_bounds__(256) void k_snap_check_slots(const Tables t, const SnapLimits lim, uint32_t* __restrict__ err)
-{
-    const uint64_t slot = (uint64_t)kBrickCells + (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (slot >= lim.n_slots) return;
-    uint32_t e = 0;
-    const uint4 hd = *reinterpret_cast<const uint4*>(&t.buf_head[slot * kChains]);
-    static_assert(kChains == 4, "one 16-byte load reads a cell's chain heads");
-    if ((hd.x && !snap_log_entry_ok(lim, hd.x)) || (hd.y && !snap_log_entry_ok(lim, hd.y)) || (hd.z && !snap_log_entry_ok(lim, hd.z)) ||
-        (hd.w && !snap_log_entry_ok(lim, hd.w)))
-        e |= SE_HEAD;
-    const uint32_t ff = t.first_frame[slot];
-    if (t.stat_id[slot] > lim.n_normals || t.pre_dep[slot] > lim.n_normals || (ff != kNoFrame && ff >= lim.max_frames)) e |= SE_SLOT;
-    const uint64_t info = t.info[slot];
-    const uint64_t cnt = (info >> kDepCntShift) & kDepCntMask, off = info >> kDepOffShift;
-    if (cnt) {
-        if (off + cnt > lim.n_dep) {
-            e |= SE_DEP;
-        } else {
-            for (uint64_t k = 0; k < cnt; k++)
-                if (t.dep[off + k].sid > lim.n_normals) e |= SE_DEP;
-        }
-    }
-    if (e) atomicOr(err, e);
-}
-
-// ... one thread per used log entry (grid.y = append region): an unchained entry names its slot, a chained one the next entry or 0.
-__global__ __launch_bounds__(256) void k_snap_check_log(const Tables t, const SnapLimits lim, uint32_t* __restrict__ err)
-{
-    const uint32_t r = blockIdx.y;
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (i >= lim.log_n[r]) return;
-    const uint32_t w = __float_as_uint(t.log_pt[(uint64_t)r * lim.region_cap + i + 1].w);
-    const bool ok = (w & kLogUnlinked) ? (uint64_t)(w & ~kLogUnlinked) < lim.n_slots : (w == 0u || snap_log_entry_ok(lim, w));
-    if (!ok) atomicOr(err, (uint32_t)SE_LINK);
-}
-
-// ... one thread per index of the longest list: records, registrations, filed pre-dependants, occupied cells, pending cells.
-__global__ __launch_bounds__(256) void k_snap_check_lists(const GridParams g, const Tables t, const SnapLimits lim, const uint32_t* __restrict__ pend, uint32_t* __restrict__ err)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    uint32_t e = 0;
-    if (i >= 1 && i <= lim.n_normals) {
-        int32_t x, y, z;
-        const uint64_t key = t.nv_key[i];
-        key_coords(g, key, x, y, z);
-        if (t.nv_slot[i] >= lim.n_slots || (key >> g.key_bits) != 0 || x > g.dim[0] || y > g.dim[1] || z > g.dim[2]) e |= SE_RECORD;
-    }
-    if (i < lim.n_reg) {
-        const uint2 ro = t.reg_occ[i];
-        if (ro.x >= lim.n_slots || ro.y > lim.n_normals) e |= SE_LIST;
-    }
-    if (i < lim.n_prereg && t.prereg_list[i] >= lim.n_slots) e |= SE_LIST;
-    if (i < lim.n_occ && t.occ_list[i] >= lim.n_slots) e |= SE_LIST;
-    if (i < lim.n_pend && pend[i] >= lim.n_slots) e |= SE_LIST;
-    if (e) atomicOr(err, e);
-}
-
 
 // ---- deviation from a triangle mesh (hfpf_compare_mesh*; contract in include/hfpf.h, numpy restatement tests/deviation_ref.py) ---------
 // The rows are binned by the 8 x 8 x 8-voxel brick their own point P falls in (dev_cell: a monotone function of P, clamped to the

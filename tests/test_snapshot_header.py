@@ -1,5 +1,5 @@
 """CPU: hfpf_snapshot_info and hfpf_config_from_snapshot are host code (no handle, no GPU).  A header is written here by hand from
-the layout csrc/hfpf.hip documents (SnapHeader) with a restatement of its checksum, so the test also pins the format."""
+the layout csrc/snapshot.hpp documents (SnapHeader) with a restatement of its checksum, so the test also pins the format."""
 import ctypes as C
 import struct
 
@@ -11,7 +11,7 @@ MASK = (1 << 64) - 1
 
 
 def _checksum(data):
-    """snap_checksum of csrc/hfpf.hip: four multiply-xorshift lanes over the 8-byte words, folded with the length."""
+    """snap_checksum of csrc/snapshot.hpp: four multiply-xorshift lanes over the 8-byte words, folded with the length."""
     mul = 0x9E3779B97F4A7C15
     lanes = [0x243F6A8885A308D3, 0x13198A2E03707344, 0xA4093822299F31D0, 0x082EFA98EC4E6C89]
     words = struct.unpack("<%dQ" % (len(data) // 8), data)
@@ -45,7 +45,7 @@ def _header(magic=b"HFPFSNAP", version=1, header_bytes=HEADER, payload_bytes=512
 
 
 def test_info_struct_has_the_asserted_size(hfpf_mod):
-    assert C.sizeof(hfpf_mod.SnapshotInfo) == 248  # static_assert in csrc/hfpf.hip
+    assert C.sizeof(hfpf_mod.SnapshotInfo) == 248  # static_assert in csrc/snapshot.hpp
     assert hfpf_mod.SNAPSHOT_HEADER_BYTES == HEADER
 
 

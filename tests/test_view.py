@@ -4,6 +4,7 @@ undefined-behaviour sanitizers (their runtime linked into the executable) and ru
 is.  It evaluates the header on the table of cases below and prints bit patterns; render_ref.project / auto_radius,
 plan_ref.project and track_ref.associate say what they must be."""
 import os
+import re
 import shutil
 import struct
 import subprocess
@@ -156,7 +157,29 @@ def test_the_header_agrees_with_the_numpy_restatements_on_every_edge(tmp_path):
     assert all(seen.values()), seen  # the table reaches every branch it is there for
 
 
-def test_the_header_is_in_every_build_list():
-    assert "view.hpp" in open(os.path.join(CSRC, "Makefile")).read()
-    assert "view.hpp" in open(os.path.join(ROOT, "high-fidelity-pointcloud-fusion_amd", "CMakeLists.txt")).read()
-    assert "view.hpp" in open(os.path.join(ROOT, "tools", "build_variant.sh")).read()
+def included_files(path, seen):
+    """path and every file it reaches through #include "...", followed transitively (paths relative to the including file)"""
+    path = os.path.normpath(path)
+    if path in seen:
+        return seen
+    seen.add(path)
+    for rel in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', open(path).read(), re.M):
+        included_files(os.path.join(os.path.dirname(path), rel), seen)
+    return seen
+
+
+def test_every_included_file_is_in_the_one_build_list():
+    """csrc/Makefile's print-sources is the one list of the files libhfpf.so is built from: it holds everything hfpf.hip includes,
+    view.hpp among it, and the two other build paths ask the Makefile instead of naming a header of their own."""
+    out = subprocess.run(["make", "-s", "--no-print-directory", "-C", CSRC, "print-sources"], check=True, stdout=subprocess.PIPE, text=True).stdout
+    listed = {os.path.normpath(os.path.join(CSRC, f)) for f in out.split()}
+    assert all(os.path.isfile(f) for f in listed), sorted(f for f in listed if not os.path.isfile(f))
+    reached = included_files(os.path.join(CSRC, "hfpf.hip"), set())
+    assert len(reached) > 1 and reached <= listed, sorted(reached - listed)
+    assert os.path.join(CSRC, "view.hpp") in reached
+    cmake = open(os.path.join(ROOT, "high-fidelity-pointcloud-fusion_amd", "CMakeLists.txt")).read()
+    variant = open(os.path.join(ROOT, "tools", "build_variant.sh")).read()
+    # CMake asks the Makefile for the list and its engine target depends on what it was told
+    assert re.search(r"print-sources\s+OUTPUT_VARIABLE HFPF_ENGINE_SOURCES\b", cmake) and re.search(r"DEPENDS \$\{HFPF_ENGINE_SOURCES\}", cmake)
+    for text in (cmake, variant):
+        assert not re.search(r"\.hpp", text), "a build path names a csrc header of its own"

@@ -9,16 +9,8 @@ SRC=$R/high-fidelity-pointcloud-fusion_amd/csrc
 if [ "$1" = "--rev" ]; then
   REV=$2; shift 2
   TMP=$(mktemp -d)
-  mkdir -p $TMP/high-fidelity-pointcloud-fusion_amd/csrc $TMP/include
-  for f in det_math.hpp geometry.hpp tables.hpp stats.hpp kernels.hpp hfpf.hip; do
-    git -C $R show $REV:high-fidelity-pointcloud-fusion_amd/csrc/$f > $TMP/high-fidelity-pointcloud-fusion_amd/csrc/$f
-  done
-  # (a revision from before one of these headers existed builds without it)
-  for f in scratch_layout.hpp host_plan.hpp view.hpp; do
-    git -C $R show $REV:high-fidelity-pointcloud-fusion_amd/csrc/$f > $TMP/high-fidelity-pointcloud-fusion_amd/csrc/$f 2>/dev/null ||
-      rm -f $TMP/high-fidelity-pointcloud-fusion_amd/csrc/$f
-  done
-  for f in hfpf.h hfpf_probe.h; do git -C $R show $REV:include/$f > $TMP/include/$f; done
+  # the revision's own csrc/ and include/, whole: whatever its hfpf.hip includes is there, and no list of files is kept here
+  git -C $R archive $REV high-fidelity-pointcloud-fusion_amd/csrc include | tar -x -C $TMP
   SRC=$TMP/high-fidelity-pointcloud-fusion_amd/csrc
 fi
 NAME=$1; shift
